@@ -8,8 +8,12 @@ One "step" = one pass of the hot path over one batch of B independent frame pair
 `value` = frames/s = N * B * steps / max-over-ranks wall time.  Multi-GPU: one process per GPU, batches are
 independent (no RCCL collective on the data path); torch.distributed is used only for the barrier / max reduction.
 
-Prints ONE JSON line (rank 0).  Extra objects: "roofline" (dominant kernel, HIP-event timed on its launch stream)
-and "cpu_baseline" (the CPU oracle timed on a bounded sample of the same workload; rank 0, N=1 only).
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times --steps passes, writes the last pass's outputs when
+--dump-outputs DIR is given and prints the headline; "roofline" and "cpu_baseline" are null there.  With --full the side legs
+run after the headline as well: "roofline" (dominant kernel, HIP-event timed on its launch stream), "cpu_baseline" (the CPU
+oracle timed on a bounded sample of the same workload; rank 0, N=1 only), the oracle check of the timed batch, the other
+configurations (configs[0], [2], [3], [4], N > 1 strong scaling), the stream / PCIe / optical-flow figures and the measured
+traffic of the roofline's kernel.
 """
 import argparse
 import json
@@ -124,10 +128,12 @@ def measure_traffic_live(kernel, batch_pairs, nlanes, timeout_s, alg_bytes_per_l
             env.update(TMPDIR="/tmp", GFS_BENCH_NO_SUPERVISOR="1", GFS_BENCH_LIVE_TRAFFIC="0")
             # (only the roofline's kernel is instrumented: every other dispatch runs at full speed)
             cmd = [rp, "--pmc", counter, "--kernel-include-regex", kernel, "--output-format", "csv", "-d", d, "--", sys.executable,
-                   os.path.abspath(__file__), "--steps", "1",
+                   os.path.abspath(__file__), "--full", "--steps", "1",
                    "--warmup", "1", "--batch", str(batch_pairs), "--lanes", str(nlanes), "--distinct", "64", "--no-cpu-baseline", "--no-extras",
                    "--no-klt", "--verify", "0", "--prime", "0"]
-            p = subprocess.Popen(cmd, cwd="/tmp", env=env, stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, start_new_session=True, text=True)
+            err_path = os.path.join(d, "child.err")  # (kept for the note of a pass that does not finish)
+            with open(err_path, "w") as err_f:
+                p = subprocess.Popen(cmd, cwd="/tmp", env=env, stdout=subprocess.PIPE, stderr=err_f, start_new_session=True, text=True)
             try:
                 child_out, _ = p.communicate(timeout=timeout_s / 2)
             except subprocess.TimeoutExpired:
@@ -136,8 +142,12 @@ def measure_traffic_live(kernel, batch_pairs, nlanes, timeout_s, alg_bytes_per_l
                 except Exception:
                     p.kill()
                 p.wait()
+                try:
+                    tail = " | ".join(open(err_path, errors="replace").read().strip().splitlines()[-6:])[-1200:]
+                except Exception:
+                    tail = ""
                 shutil.rmtree(d, ignore_errors=True)
-                return dict(out, note=f"the {counter} pass did not finish in {timeout_s / 2:.0f} s (killed)")
+                return dict(out, note=f"the {counter} pass did not finish in {timeout_s / 2:.0f} s (killed)", stderr_tail=tail)
             try:  # the child's own line: algorithmic bytes of the kernel per step of ITS batch
                 cr = json.loads([ln_ for ln_ in child_out.splitlines() if ln_.startswith("{")][-1])["roofline"]
                 if cr["kernel"] == kernel:
@@ -252,15 +262,45 @@ def _gen_one(a):
     return p
 
 
+def usable_cpus():
+    """CPUs this process may keep busy: its affinity mask, capped by the cgroup CPU quota and by the thread budget the environment
+    sets (OMP_NUM_THREADS), where there is one.  os.cpu_count() alone counts the whole host."""
+    try:
+        n = len(os.sched_getaffinity(0))
+    except Exception:
+        n = os.cpu_count() or 1
+    try:
+        quota, period = open("/sys/fs/cgroup/cpu.max").read().split()[:2]
+        if quota != "max":
+            n = min(n, max(1, int(quota) // int(period)))
+    except Exception:
+        pass
+    try:
+        n = min(n, int(os.environ.get("OMP_NUM_THREADS", "0")) or n)
+    except ValueError:
+        pass
+    return max(1, n)
+
+
 def gen_pairs(seeds, width, height, stride, procs):
-    """Distinct synthetic scenes, rendered by worker PROCESSES (the ray caster is numpy-bound; called before any HIP state
-    exists in this process, so forking is safe)."""
+    """Distinct synthetic scenes, rendered by worker PROCESSES (the ray caster is numpy-bound).  Returns a function that waits
+    for the list: the workers are forked here, before any HIP state exists in this process, and none is forked later, so the
+    caller may import torch and open the GPU while they render."""
     seeds = list(seeds)
     if procs <= 1 or len(seeds) <= 2:
-        return [_gen_one((s, width, height, stride)) for s in seeds]
+        done = [_gen_one((s, width, height, stride)) for s in seeds]
+        return lambda: done
     import multiprocessing as mp
-    with mp.get_context("fork").Pool(min(procs, len(seeds))) as pool:
-        return pool.map(_gen_one, [(s, width, height, stride) for s in seeds], chunksize=1)
+    pool = mp.get_context("fork").Pool(min(procs, len(seeds)))
+    job = pool.map_async(_gen_one, [(s, width, height, stride) for s in seeds], chunksize=1)
+
+    def wait():
+        try:
+            return job.get()
+        finally:
+            pool.close()
+            pool.join()
+    return wait
 
 
 def spawn_ranks(n):
@@ -322,11 +362,18 @@ def main():
     ap.add_argument("--live-traffic-timeout-s", type=float, default=300.0,
                     help="both rocprofv3 --pmc child runs of the roofline.traffic leg together (GFS_BENCH_LIVE_TRAFFIC=0 skips the leg)")
     ap.add_argument("--no-supervisor", action="store_true", help="N = 1: run in this process (no child), side legs guarded by try/except only")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, run every side leg as well (roofline, CPU baseline, oracle check, other configurations, "
+                         "stream / PCIe / optical-flow figures, measured traffic); a plain run prints the headline alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32 / float64; per-key-point arrays for a "
+                         "fixed sample of 64 pairs, per-pair arrays for the whole batch)")
     args = ap.parse_args()
     t_start = time.perf_counter()
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         spawn_ranks(args.gpus)  # does not return
-    if int(os.environ.get("WORLD_SIZE", "1")) == 1 and args.gpus == 1 and not args.no_supervisor and "GFS_BENCH_CHILD" not in os.environ \
+    # (the supervising parent guards the headline against the side legs: a plain run has none)
+    if args.full and int(os.environ.get("WORLD_SIZE", "1")) == 1 and args.gpus == 1 and not args.no_supervisor and "GFS_BENCH_CHILD" not in os.environ \
             and "GFS_BENCH_NO_SUPERVISOR" not in os.environ:
         supervise(sys.argv[1:], args.deadline_s)  # does not return
     rank = int(os.environ.get("RANK", "0"))
@@ -347,11 +394,10 @@ def main():
     assert B > 0, "more ranks than pairs"
     nd = B if args.distinct <= 0 else max(1, min(args.distinct, B))
     seed0 = 1000 + first_pair
-    ncpu = os.cpu_count() or 1
+    ncpu = usable_cpus()
     gen_procs = args.gen_procs or max(1, min(96, ncpu // max(world, 1)))
     t_gen = time.perf_counter()
-    pairs = gen_pairs(range(seed0, seed0 + nd), W, H, STRIDE, gen_procs)
-    t_gen = time.perf_counter() - t_gen
+    pairs_ready = gen_pairs(range(seed0, seed0 + nd), W, H, STRIDE, gen_procs)  # (rendering while torch loads and the GPU opens)
 
     import torch
     if world > 1:
@@ -370,6 +416,9 @@ def main():
     dev = torch.device("cuda", local_rank)
 
     from geoflowslam_amd import api
+    api.lib()
+    pairs = pairs_ready()
+    t_gen = time.perf_counter() - t_gen
     sel = [i % nd for i in range(B)]
     npts = max(max(len(p["cloud0"]), len(p["cloud1"])) for p in pairs)
     SP = (npts + 1023) // 1024 * 1024
@@ -512,10 +561,63 @@ def main():
         dt = float(t.item())
     total_pairs = args.batch if args.strong else world * B
     fps = total_pairs * args.steps / dt
+
+    def dump_outputs(out_dir):
+        """What the last timed pass left for a caller: ORB key points / descriptors of the current frames, BF matches, GMS mask and
+        inlier counts, GICP results.  Per-key-point arrays for a fixed sample of pairs (seeded; <= 64), per-pair arrays for the whole
+        batch; entries past a pair's count are zero (-1 for match indices).  float32 holds every integer field exactly."""
+        os.makedirs(out_dir, exist_ok=True)
+        suffix = f"_rank{rank}" if world > 1 else ""
+        cap = max(l_.cap for l_ in lanes)
+        sample = np.sort(np.random.default_rng(0).choice(B, size=min(B, 64), replace=False))
+        kps = np.zeros((len(sample), cap, 7), np.float32)
+        desc = np.zeros((len(sample), cap, 32), np.float32)
+        m_idx = np.full((len(sample), cap), -1, np.float32)
+        m_dist = np.zeros((len(sample), cap), np.float32)
+        m_mask = np.zeros((len(sample), cap), np.float32)
+        counts, prev_counts, inliers = np.zeros(B, np.float32), np.zeros(B, np.float32), np.zeros(B, np.float32)
+        g = []
+        for ln in lanes:
+            cnt = np.zeros(ln.n, np.int32)
+            assert hip.hipMemcpy(cnt.ctypes.data, ln.res["counts"], ln.n * 4, 2) == 0
+            counts[ln.b0:ln.b0 + ln.n] = cnt
+            prev_counts[ln.b0:ln.b0 + ln.n] = ln.prev_cnt.cpu().numpy()
+            inliers[ln.b0:ln.b0 + ln.n] = ln.m_inl.cpu().numpy()
+            g += list(ln.gicp_out)
+        for j, b in enumerate(sample):
+            ln = next(l_ for l_ in lanes if l_.b0 <= b < l_.b0 + l_.n)
+            k = int(b) - ln.b0
+            n, nq = int(counts[b]), int(prev_counts[b])
+            lc = ln.cap
+            kp = np.zeros(lc, api.KP_DTYPE)
+            d8 = np.zeros((lc, 32), np.uint8)
+            assert hip.hipMemcpy(kp.ctypes.data, ln.res["kps"] + k * lc * 28, lc * 28, 2) == 0
+            assert hip.hipMemcpy(d8.ctypes.data, ln.res["desc"] + k * lc * 32, lc * 32, 2) == 0
+            kps[j, :n] = np.stack([kp[f][:n].astype(np.float32) for f in kp.dtype.names], 1)
+            desc[j, :n] = d8[:n]
+            m_idx[j, :nq] = ln.m_idx.view(ln.n, lc)[k, :nq].cpu().numpy()
+            m_dist[j, :nq] = ln.m_dist.view(ln.n, lc)[k, :nq].cpu().numpy()
+            m_mask[j, :nq] = ln.m_mask.view(ln.n, lc)[k, :nq].cpu().numpy()
+        arrays = dict(
+            sample_pairs=sample.astype(np.float64), orb_counts=counts, orb_keypoints=kps, orb_descriptors=desc,
+            match_train_idx=m_idx, match_distance=m_dist, gms_mask=m_mask, gms_inliers=inliers,
+            gicp_T=np.stack([np.array(r.T).reshape(4, 4).T for r in g]).astype(np.float64),
+            gicp_H=np.stack([np.array(r.H).reshape(6, 6).T for r in g]).astype(np.float64),
+            gicp_b=np.stack([np.array(r.b) for r in g]).astype(np.float64),
+            gicp_error=np.array([r.error for r in g], np.float64),
+            gicp_converged=np.array([r.converged for r in g], np.float64),
+            gicp_iterations=np.array([r.iterations for r in g], np.float64),
+            gicp_num_inliers=np.array([r.num_inliers for r in g], np.float64))
+        for name, a in arrays.items():
+            np.save(os.path.join(out_dir, name + suffix + ".npy"), a)
+
+    if args.dump_outputs:
+        torch.cuda.synchronize()
+        dump_outputs(args.dump_outputs)
     # ---- N > 1 without --strong: the weak figure above is the contract's line; BASELINE.json configs[3] (ONE batch of --batch pairs cut
-    #      over the ranks) is measured right after it, same K / W, and reported beside it as `strong`
+    #      over the ranks) is measured right after it, same K / W, and reported beside it as `strong` (--full)
     strong = None
-    if world > 1 and not args.strong:
+    if args.full and world > 1 and not args.strong:
         s0_, s1_ = shard_range(args.batch, rank, world)
         nb_ = s1_ - s0_  # this rank's block of the global batch (it takes the block from its own scene set: the blocks are independent)
         if nb_ > 0:
@@ -567,7 +669,7 @@ def main():
         }
         if args.gicp_stream:
             out["config"]["workload"] += " [EXPERIMENT --gicp-stream: target preprocessing reused from the previous call]"
-        verify_wanted = rank == 0 and args.verify > 0 and not args.no_cpu_baseline and not args.gicp_stream
+        verify_wanted = rank == 0 and args.full and args.verify > 0 and not args.no_cpu_baseline and not args.gicp_stream
         if verify_wanted:
             out["verify_requested"] = int(args.verify)
         if verify:
@@ -691,7 +793,7 @@ def main():
                         share_of_gpu_kernel_time=round(ms / tot, 3), largest_kernel_by_time=dominant_overall,
                         kernels_ms_per_step={k: round(v[0] / nprof, 4) for k, v in sorted(kern.items(), key=lambda kv: -kv[1][0])})
 
-    if rank == 0:
+    if rank == 0 and args.full:
         roofline = guarded(roofline_leg)
         emit()
 
@@ -738,7 +840,7 @@ def main():
                       max_gicp_rel_err=max(e for *_, e in res), failures=bad)
 
     # (run right behind the roofline leg and outside the leg budget: a headline without its oracle check is worth less than any extra)
-    if rank == 0 and args.verify > 0 and not args.no_cpu_baseline and not args.gicp_stream:
+    if rank == 0 and args.full and args.verify > 0 and not args.no_cpu_baseline and not args.gicp_stream:
         verify = guarded(verify_leg)
         emit()
 
@@ -747,7 +849,7 @@ def main():
     def cpu_leg():
         from oracle import oracle as O
         O.lib()
-        ncores = os.cpu_count() or 1
+        ncores = usable_cpus()
         orb0 = O.OrbOracle(NF, 1.2, NL, 20, 7)
         prev_full = [orb0.extract(p["gray0"]) for p in pairs]
         prev_cpu = [r[2] for r in prev_full]
@@ -791,12 +893,12 @@ def main():
                                   sample=f"{nall} pairs on {ncores} worker threads, single-threaded oracle per pair"),
                    note="CPU restatement of the reference algorithm (reference not buildable here: OpenCV/Eigen/PCL absent)")
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         cpu = guarded(cpu_leg)
         emit()
 
     # ---- the optical-flow stream next to the path: reported beside the metric, never part of `value`
-    if rank == 0 and world == 1 and not args.no_klt and not over_budget("optical_flow"):
+    if rank == 0 and world == 1 and args.full and not args.no_klt and not over_budget("optical_flow"):
         try:
             WIN = 35
             cap = lanes[0].cap
@@ -878,7 +980,7 @@ def main():
 
     # ---- the other SURVEY.md 8(d) figures, beside the metric (rank 0, N = 1): ORB only (configs[0]) and LBA windows (configs[4])
     emit()
-    if rank == 0 and world == 1 and not args.no_extras and not over_budget("orb_only/lba/c3/c4_shard"):
+    if rank == 0 and world == 1 and args.full and not args.no_extras and not over_budget("orb_only/lba/c3/c4_shard"):
         try:
             # all lanes' extractors at once, each on its own stream (the way the headline step runs them), and one lane alone
             def _orb_pass(lns, reps):
@@ -1022,7 +1124,7 @@ def main():
             try:
                 import subprocess
                 env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
-                cp = subprocess.run([sys.executable, os.path.abspath(__file__), "--workload", "c3", "--batch", "32", "--lanes", "2", "--steps", "10",
+                cp = subprocess.run([sys.executable, os.path.abspath(__file__), "--full", "--workload", "c3", "--batch", "32", "--lanes", "2", "--steps", "10",
                                      "--warmup", "3", "--no-klt", "--no-extras", "--no-cpu-baseline", "--verify", "0"],
                                     capture_output=True, text=True, timeout=600, env=env)
                 line = [ln_ for ln_ in cp.stdout.splitlines() if ln_.startswith("{")]
@@ -1040,7 +1142,7 @@ def main():
             try:
                 shard = {}
                 for nl_ in (4, 2):
-                    cp = subprocess.run([sys.executable, os.path.abspath(__file__), "--batch", "64", "--lanes", str(nl_), "--steps", str(args.steps),
+                    cp = subprocess.run([sys.executable, os.path.abspath(__file__), "--full", "--batch", "64", "--lanes", str(nl_), "--steps", str(args.steps),
                                          "--warmup", str(args.warmup), "--no-klt", "--no-extras", "--no-cpu-baseline", "--verify", "0"],
                                         capture_output=True, text=True, timeout=600, env=env)
                     line = [ln_ for ln_ in cp.stdout.splitlines() if ln_.startswith("{")]
@@ -1060,7 +1162,7 @@ def main():
     # ---- ONE live stream, a frame at a time, as System::TrackRGBD (src/System.cc:600) drives the path: ORB -> stereo from RGB-D ->
     #      depth -> cloud -> GICP against the previous cloud (gfs_gicp_align_next) -> SearchByProjection -> PoseOptimization
     emit()
-    if rank == 0 and world == 1 and not args.no_extras and args.workload == "c2" and not over_budget("single_stream"):
+    if rank == 0 and world == 1 and args.full and not args.no_extras and args.workload == "c2" and not over_budget("single_stream"):
         try:
             import bench_stream as bs
             Kc = synth.intrinsics(W, H)
@@ -1115,7 +1217,7 @@ def main():
 
     # ---- PCIe-inclusive figure (N = 1): images and depth maps start in pinned HOST memory every pass, the clouds are built on the
     #      device (Frame::ConvertDepthToPointCloud), the per-pair results come back to pinned host memory
-    if rank == 0 and world == 1 and not args.no_extras and args.workload == "c2" and not args.gicp_stream and not over_budget("h2d_inclusive"):
+    if rank == 0 and world == 1 and args.full and not args.no_extras and args.workload == "c2" and not args.gicp_stream and not over_budget("h2d_inclusive"):
         try:
             fx, fy, cx_, cy_ = synth.intrinsics(W, H)
             h_gray = torch.from_numpy(np.stack([pairs[i]["gray1"] for i in sel])).pin_memory()
@@ -1273,7 +1375,7 @@ def main():
     # ---- HBM-side traffic of the roofline's kernel, MEASURED BY THIS RUN: two child runs of this script (one step of the same batch and
     #      lane shape, 64 distinct scenes tiled) under `rocprofv3 --pmc FETCH_SIZE` / `--pmc WRITE_SIZE` -- counters in their own passes,
     #      no trace domains (MI355X_MICROARCH.md).  The last leg: whatever happens here costs nothing that was measured before.
-    if (rank == 0 and world == 1 and not args.no_extras and args.workload == "c2" and isinstance(roofline, dict) and roofline.get("kernel")
+    if (rank == 0 and world == 1 and args.full and not args.no_extras and args.workload == "c2" and isinstance(roofline, dict) and roofline.get("kernel")
             and os.environ.get("GFS_BENCH_LIVE_TRAFFIC", "1") != "0" and not over_budget("traffic_live")):
         try:
             live = measure_traffic_live(roofline["kernel"], B, nlanes, args.live_traffic_timeout_s, roofline.get("algorithmic_bytes_per_launch"))

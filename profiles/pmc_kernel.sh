@@ -13,7 +13,7 @@ for set in "$@"; do
   n=$((n+1))
   rm -rf $OUT/${TAG}_pmc$n
   timeout 600 rocprofv3 --pmc $set --output-format csv -d $OUT/${TAG}_pmc$n -- \
-    python $R/bench.py --steps 1 --warmup 1 --serial --lanes 1 --no-cpu-baseline --no-extras --no-klt --verify 0 --prime 0 > $OUT/${TAG}_pmc$n.log 2>&1
+    python $R/bench.py --full --steps 1 --warmup 1 --serial --lanes 1 --no-cpu-baseline --no-extras --no-klt --verify 0 --prime 0 > $OUT/${TAG}_pmc$n.log 2>&1
   python - "$OUT/${TAG}_pmc$n" "$K" <<'PY'
 import csv, glob, sys, collections
 per = collections.OrderedDict()

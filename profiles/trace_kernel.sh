@@ -11,7 +11,7 @@ cd /tmp && export TMPDIR=/tmp
 for kv in "$@"; do export "$kv"; done
 rm -rf $OUT/${TAG}_trace
 timeout 600 rocprofv3 --kernel-trace --output-format csv -d $OUT/${TAG}_trace -- \
-  python $R/bench.py --steps 1 --warmup 1 --serial --lanes 1 --no-cpu-baseline --no-extras --no-klt --verify 0 --prime 0 > $OUT/${TAG}_trace.log 2>&1
+  python $R/bench.py --full --steps 1 --warmup 1 --serial --lanes 1 --no-cpu-baseline --no-extras --no-klt --verify 0 --prime 0 > $OUT/${TAG}_trace.log 2>&1
 python - "$OUT/${TAG}_trace" "$K" <<'PY'
 import csv, glob, sys
 rows = []

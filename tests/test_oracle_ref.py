@@ -3,13 +3,31 @@
 result container of ann/kdtree.hpp:194-233) build from /root/reference without OpenCV / Eigen (oracle/ref_build.sh ->
 oracle/_ref/libgfs_ref_small_gicp.so; every other hot-path source includes one of the two and is unbuildable in this image).
 The reference runs its sort with OpenMP tasks on 4 threads (src/RegistrationGICP.cc:10); the tasks own disjoint ranges, so the
-permutation does not depend on the thread count -- checked here with 1, 4 and 7 threads."""
+permutation does not depend on the thread count -- checked here with 1, 4 and 7 threads.
+
+The reference library's results are recorded as SHA-256 digests in tests/golden/ref_small_gicp_results.json: the oracle is checked
+against the record everywhere, and against the library itself (which must still produce the record) wherever oracle/_ref is built.
+`PYTHONPATH=. python tests/test_oracle_ref.py` rewrites the record from the library."""
+import hashlib
+import json
+import os
+
 import numpy as np
-import pytest
 
 from oracle import oracle as O
 
-pytestmark = pytest.mark.skipif(O.ref_lib() is None, reason="oracle/_ref not built (needs /root/reference: bash oracle/ref_build.sh)")
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_small_gicp_results.json")
+
+
+def _digest(*arrays):
+    h = hashlib.sha256()
+    for a in arrays:
+        h.update(np.ascontiguousarray(a).tobytes())
+    return h.hexdigest()
+
+
+def _recorded(section):
+    return json.load(open(GOLDEN))[section]
 
 
 def _voxel_keys(x, y, z):
@@ -44,33 +62,23 @@ def sort_cases():
     return cases
 
 
-def test_restated_quick_sort_omp_is_the_references_permutation():
-    for name, k in sort_cases():
-        want, wk = O.ref_quick_sort_perm(k, 4)
-        got, gk = O.quick_sort_perm(k)
-        assert np.array_equal(gk, wk) and np.array_equal(got, want), (name, int((got != want).sum()))
-        for threads in (1, 7):
-            other, _ = O.ref_quick_sort_perm(k, threads)
-            assert np.array_equal(other, want), (name, threads)
-
-
-def test_restated_quick_sort_omp_on_depth_camera_clouds():
+def depth_cases():
     """The keys the path really sorts: voxel coordinates of the synthetic RGB-D clouds (raster order, 0.25 m / 0.1 m leaves)."""
     from geoflowslam_amd import synth
+    cases = []
     for seed in (1, 2, 202):
         fp = synth.frame_pair(seed)
         for key in ("cloud0", "cloud1"):
             pts = np.asarray(fp[key], np.float64)[:, :3]
             for leaf in (0.25, 0.1):
                 c = np.floor(pts / leaf).astype(np.int64) + (1 << 20)
-                k = _voxel_keys(c[:, 0], c[:, 1], c[:, 2])
-                want, _ = O.ref_quick_sort_perm(k, 4)
-                got, _ = O.quick_sort_perm(k)
-                assert np.array_equal(got, want), (seed, key, leaf)
+                cases.append((f"{seed}/{key}/{leaf}", _voxel_keys(c[:, 0], c[:, 1], c[:, 2])))
+    return cases
 
 
-def test_restated_knn_result_is_the_references_container():
+def knn_cases():
     rng = np.random.default_rng(3)
+    cases = []
     for case in range(400):
         k = int(rng.choice([1, 2, 10, 11, 20]))
         n = int(rng.integers(0, 200))
@@ -78,9 +86,63 @@ def test_restated_knn_result_is_the_references_container():
         if n and case % 2:
             d = np.round(d * 8) / 8  # exact distance ties: the first pushed stays ahead (strict <)
         idx = rng.integers(0, 1 << 40, n).astype(np.uint64)
+        cases.append((case, k, idx, d))
+    return cases
+
+
+def _ref_sort_digests(cases):
+    return {name: _digest(*O.ref_quick_sort_perm(k, 4)) for name, k in cases}
+
+
+def _ref_knn_digest():
+    h = [O.knn_push_stream(k, idx, d, ref=True) for _, k, idx, d in knn_cases()]
+    return _digest(*[np.array([n], np.int64) for n, _, _ in h], *[a for _, io, do in h for a in (io, do)])
+
+
+def test_restated_quick_sort_omp_is_the_references_permutation():
+    rec = _recorded("sort")
+    for name, k in sort_cases():
+        got, gk = O.quick_sort_perm(k)
+        assert _digest(got, gk) == rec[name], name
+        if O.ref_lib() is not None:
+            want, wk = O.ref_quick_sort_perm(k, 4)
+            assert np.array_equal(gk, wk) and np.array_equal(got, want), (name, int((got != want).sum()))
+            for threads in (1, 7):
+                other, _ = O.ref_quick_sort_perm(k, threads)
+                assert np.array_equal(other, want), (name, threads)
+
+
+def test_restated_quick_sort_omp_on_depth_camera_clouds():
+    """The keys the path really sorts: voxel coordinates of the synthetic RGB-D clouds (raster order, 0.25 m / 0.1 m leaves)."""
+    rec = _recorded("depth")
+    for name, k in depth_cases():
+        got, gk = O.quick_sort_perm(k)
+        assert _digest(got, gk) == rec[name], name
+        if O.ref_lib() is not None:
+            want, _ = O.ref_quick_sort_perm(k, 4)
+            assert np.array_equal(got, want), name
+
+
+def test_restated_knn_result_is_the_references_container():
+    got_all = []
+    for case, k, idx, d in knn_cases():
         got = O.knn_push_stream(k, idx, d)
-        want = O.knn_push_stream(k, idx, d, ref=True)
-        assert got[0] == want[0] and np.array_equal(got[1], want[1]) and np.array_equal(got[2], want[2]), (case, k, n)
-        if k == 1:  # the static N = 1 specialisation (the correspondence search of gicp_factor.hpp:35-73)
-            one = O.knn_push_stream(1, idx, d, ref=True, static_one=True)
-            assert got[0] == one[0] and np.array_equal(got[1], one[1]) and np.array_equal(got[2], one[2])
+        got_all.append(got)
+        if O.ref_lib() is not None:
+            want = O.knn_push_stream(k, idx, d, ref=True)
+            assert got[0] == want[0] and np.array_equal(got[1], want[1]) and np.array_equal(got[2], want[2]), (case, k, len(idx))
+            if k == 1:  # the static N = 1 specialisation (the correspondence search of gicp_factor.hpp:35-73)
+                one = O.knn_push_stream(1, idx, d, ref=True, static_one=True)
+                assert got[0] == one[0] and np.array_equal(got[1], one[1]) and np.array_equal(got[2], one[2])
+    assert _digest(*[np.array([n], np.int64) for n, _, _ in got_all], *[a for _, io, do in got_all for a in (io, do)]) == _recorded("knn")
+    if O.ref_lib() is not None:  # the library still produces the record
+        assert _ref_knn_digest() == _recorded("knn")
+        assert _ref_sort_digests(sort_cases()) == _recorded("sort") and _ref_sort_digests(depth_cases()) == _recorded("depth")
+
+
+if __name__ == "__main__":
+    assert O.ref_lib() is not None, "oracle/_ref not built (bash oracle/ref_build.sh)"
+    with open(GOLDEN, "w") as f:
+        json.dump(dict(sort=_ref_sort_digests(sort_cases()), depth=_ref_sort_digests(depth_cases()), knn=_ref_knn_digest()), f, indent=1)
+        f.write("\n")
+    print(f"wrote {GOLDEN}")
