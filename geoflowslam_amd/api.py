@@ -174,6 +174,57 @@ def sbp_struct(prob):
     return P, keep
 
 
+class PoseLidarProblem(C.Structure):
+    _fields_ = [("q", C.c_float * 4), ("t", C.c_float * 3), ("n_obs", C.c_int32), ("xw", C.c_void_p), ("obs", C.c_void_p),
+                ("inv_sigma2", C.c_void_p), ("stereo", C.c_void_p), ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double),
+                ("cy", C.c_double), ("bf", C.c_double), ("n_cloud", C.c_int32), ("cloud", C.c_void_p), ("map", C.c_void_p),
+                ("n_iterations", C.c_int32), ("two_camera", C.c_int32)]
+
+
+class PoseLidarSolution(C.Structure):
+    _fields_ = [("outlier", C.c_void_p), ("chi2", C.c_void_p), ("q", C.c_double * 4), ("t", C.c_double * 3), ("qf", C.c_float * 4),
+                ("tf", C.c_float * 3), ("avg_reproj_error", C.c_float), ("n_inliers", C.c_int32), ("n_lidar_inliers", C.c_int32),
+                ("residual", C.c_float), ("lidar_rounds", C.c_int32), ("rounds_run", C.c_int32), ("iterations_run", C.c_int32),
+                ("round_edges", C.c_int32 * 4), ("round_chi2", C.c_float * 4), ("round_valid", C.c_int32 * 4)]
+
+
+def pose_lidar_structs(prob, map_handle=None):
+    """ctypes views of one PoseLidarVisualOptimization problem dict (shared with the CPU restatement's tests: same layout).
+    prob: q, t (float Tcw), xw, obs, inv_sigma2, stereo, fx, fy, cx, cy, bf, cloud [n][3], n_iterations (+ optional
+    n_lidar_inliers / residual: the caller's values of the in/out parameters, two_camera)."""
+    P, S = PoseLidarProblem(), PoseLidarSolution()
+    xw = np.ascontiguousarray(prob["xw"], np.float64).reshape(-1, 3)
+    n = len(xw)
+    cloud = np.ascontiguousarray(prob["cloud"], np.float32).reshape(-1, 3)
+    keep = dict(xw=xw, obs=np.ascontiguousarray(prob["obs"], np.float64).reshape(-1, 3),
+                inv_sigma2=np.ascontiguousarray(prob["inv_sigma2"], np.float32), stereo=np.ascontiguousarray(prob["stereo"], np.uint8),
+                cloud=cloud, outlier=np.zeros(max(n, 1), np.uint8), chi2=np.zeros(max(n, 1), np.float64))
+    P.q[:] = [float(v) for v in np.asarray(prob["q"], np.float32)]
+    P.t[:] = [float(v) for v in np.asarray(prob["t"], np.float32)]
+    P.n_obs = n
+    for name in ("xw", "obs", "inv_sigma2", "stereo", "cloud"):
+        setattr(P, name, keep[name].ctypes.data)
+    for name in ("fx", "fy", "cx", "cy", "bf"):
+        setattr(P, name, float(prob[name]))
+    P.n_cloud = len(cloud)
+    P.map = map_handle
+    P.n_iterations = int(prob.get("n_iterations", 3))
+    P.two_camera = int(prob.get("two_camera", 0))
+    S.outlier = keep["outlier"].ctypes.data
+    S.chi2 = keep["chi2"].ctypes.data
+    S.n_lidar_inliers = int(prob.get("n_lidar_inliers", 0))
+    S.residual = float(prob.get("residual", 0.0))
+    return P, S, keep, n
+
+
+def pose_lidar_result(S, keep, n):
+    return dict(outlier=keep["outlier"][:n].astype(bool), chi2=keep["chi2"][:n].copy(), q=np.array(S.q[:]), t=np.array(S.t[:]),
+                qf=np.array(S.qf[:], np.float32), tf=np.array(S.tf[:], np.float32), avg_reproj_error=np.float32(S.avg_reproj_error),
+                n_inliers=int(S.n_inliers), n_lidar_inliers=int(S.n_lidar_inliers), residual=np.float32(S.residual),
+                lidar_rounds=int(S.lidar_rounds), rounds_run=int(S.rounds_run), iterations_run=int(S.iterations_run),
+                round_edges=list(S.round_edges), round_chi2=np.array(S.round_chi2[:], np.float32), round_valid=list(S.round_valid))
+
+
 # every symbol include/gfs_abi.h declares (tests/test_abi.py checks the built library exports all of them)
 ABI_SYMBOLS = [
     "gfs_abi_version", "gfs_last_error", "gfs_device_count",
@@ -191,6 +242,8 @@ ABI_SYMBOLS = [
     "gfs_frame_create", "gfs_frame_destroy", "gfs_depth_to_cloud", "gfs_depth_to_cloud_batch_device", "gfs_depth_convert_u16_batch_device", "gfs_stereo_from_rgbd",
     "gfs_stereo_from_rgbd_batch_device",
     "gfs_pose_create", "gfs_pose_destroy", "gfs_pose_optimize", "gfs_pose_set_sum_order",
+    "gfs_lidar_map_create", "gfs_lidar_map_set", "gfs_lidar_map_destroy", "gfs_pose_lidar_create", "gfs_pose_lidar_destroy",
+    "gfs_pose_lidar_set_sum_order", "gfs_pose_lidar_optimize", "gfs_pose_lidar_fetch_edges",
     "gfs_gms_create", "gfs_gms_destroy", "gfs_gms_inlier_mask", "gfs_gms_inlier_mask_batch_device",
     "gfs_sbp_create", "gfs_sbp_destroy", "gfs_search_by_projection", "gfs_search_by_projection_map",
     "gfs_klt_create", "gfs_klt_destroy", "gfs_klt_layout", "gfs_klt_pyramid_create", "gfs_klt_pyramid_destroy",
@@ -1043,6 +1096,73 @@ class PoseOptimizer:
         _check(lib().gfs_pose_optimize(self.h, PP, B, SS), "gfs_pose_optimize")
         res = [pose_result(SS[f], *keeps[f]) for f in range(B)]
         return res[0] if single else res
+
+
+class LidarMap:
+    """The local map of PoseLidarVisualOptimization (laserCloudSurfFromMapDS, reference src/Optimizer.cc:7698-8059) on the device:
+    uploaded once with set(), reused by every frame until the next set() (gfs_lidar_map_* in include/gfs_abi.h)."""
+
+    def __init__(self, max_points=65536, device=0):
+        self.h = C.c_void_p()
+        _check(lib().gfs_lidar_map_create(device, max_points, C.byref(self.h)), "gfs_lidar_map_create")
+
+    def set(self, xyz):
+        xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        _check(lib().gfs_lidar_map_set(self.h, _p(xyz), len(xyz)), "gfs_lidar_map_set")
+        return self
+
+    def close(self):
+        if getattr(self, "h", None) and _lib is not None:
+            _lib.gfs_lidar_map_destroy(self.h)
+        self.h = None
+
+    __del__ = close
+
+
+class PoseLidarOptimizer:
+    """ORB_SLAM3::Optimizer::PoseLidarVisualOptimization (reference src/Optimizer.cc:7698-8059), conventional-SLAM branch, on
+    flattened frames (gfs_pose_lidar_problem in include/gfs_abi.h): the visual edges of PoseOptimization plus point-to-plane edges
+    of the frame's cloud against a LidarMap.  A frame dict carries its map under "map" (a LidarMap)."""
+
+    SUMS_TREE, SUMS_EDGE_ORDER = 0, 1
+
+    def __init__(self, max_obs=4096, max_cloud=8192, max_batch=64, device=0, sums=None):
+        """sums: None / "edge_order" (g2o's order: the bits of the sequential restatement) or "tree" (opt-in, toleranced)."""
+        self.h = C.c_void_p()
+        _check(lib().gfs_pose_lidar_create(device, max_obs, max_cloud, max_batch, C.byref(self.h)), "gfs_pose_lidar_create")
+        if sums is not None:
+            _check(lib().gfs_pose_lidar_set_sum_order(self.h, {"tree": 0, "edge_order": 1}[sums]), "gfs_pose_lidar_set_sum_order")
+
+    def close(self):
+        if getattr(self, "h", None) and _lib is not None:
+            _lib.gfs_pose_lidar_destroy(self.h)
+        self.h = None
+
+    __del__ = close
+
+    def PoseLidarVisualOptimization(self, frames):
+        """frames: one problem dict or a list of them -> result dict(s): outlier, chi2, q, t (g2o estimate), qf, tf (SetPose),
+        avg_reproj_error, n_inliers (the return value), n_lidar_inliers, residual, lidar_rounds, rounds_run, iterations_run,
+        round_edges / round_chi2 / round_valid."""
+        single = isinstance(frames, dict)
+        probs = [frames] if single else list(frames)
+        B = len(probs)
+        PP, SS = (PoseLidarProblem * B)(), (PoseLidarSolution * B)()
+        keeps = []
+        for f, prob in enumerate(probs):
+            P, S, keep, n = pose_lidar_structs(prob, prob["map"].h)
+            PP[f], SS[f] = P, S
+            keeps.append((keep, n))
+        _check(lib().gfs_pose_lidar_optimize(self.h, PP, B, SS), "gfs_pose_lidar_optimize")
+        res = [pose_lidar_result(SS[f], *keeps[f]) for f in range(B)]
+        return res[0] if single else res
+
+    def fetch_edges(self, b, rnd, cap=8192):
+        """The lidar edges frame b of the last call generated in round rnd: (index [n], plane [n][4], s [n])."""
+        idx, pl, s, n = np.zeros(cap, np.int32), np.zeros((cap, 4), np.float32), np.zeros(cap, np.float32), C.c_int32()
+        _check(lib().gfs_pose_lidar_fetch_edges(self.h, b, rnd, _p(idx), _p(pl), _p(s), cap, C.byref(n)), "gfs_pose_lidar_fetch_edges")
+        m = min(n.value, cap)
+        return idx[:m].copy(), pl[:m].copy(), s[:m].copy()
 
 
 class Frame:

@@ -1,0 +1,1241 @@
+// Optimizer::PoseLidarVisualOptimization (reference src/Optimizer.cc:7698-8059) on MI355X: motion-only bundle adjustment of a batch
+// of frames with the visual edges of PoseOptimization plus, per round, the point-to-plane edges GenerateLidarEdge (:8339-8421) builds
+// from the frame's downsampled cloud and the local map (EdgeSE3LidarPoint2Plane, include/G2oTypes.h:574-600).
+//
+// A call runs k_pl_init, then per round k_pl_assoc (one thread per cloud point: pointAssociateToMap, exact 5-NN in the map's hash
+// grid, the float ColPivHouseholderQR plane fit, the gates, the weight) and k_pl_round (one 256-thread workgroup per frame: compaction
+// of the surviving edges in cloud-index order, chi2Lidar / valid_edge, the Levenberg-Marquardt loop over visual + lidar edges, the
+// re-classification of the visual edges, the float pose of the next association).  The edges live in global memory: a few thousand
+// lidar edges do not fit beside the LDS slab of the ordered sums.  Every sum over the edges is added in g2o's edge order (visual edges
+// by key-point index, then lidar edges by cloud index) on one lane per quantity (GFS_POSE_SUMS_EDGE_ORDER, the bits of the sequential
+// restatement tests/host/pose_lidar_restatement.cpp), or by a tree of fixed shape (GFS_POSE_SUMS_TREE).
+//
+// The numeric Jacobian of a lidar edge (core/base_unary_edge.hpp:82-123) evaluates the error at the estimate moved by +-1e-9 along
+// each of the six axes.  Those twelve poses -- and their inverses, which computeError takes -- are the same for every edge: they are
+// computed once per linearisation by twelve lanes and shared through LDS (g2o recomputes the same values edge by edge, so the bits do
+// not change).  A step of 1e-9 takes SE3Quat::exp's small-angle branch: no sin / cos is evaluated for them.
+#include <algorithm>
+#include <memory>
+#include <mutex>
+#include <vector>
+
+#include "g2o_se3_dev.hpp"
+#include "gfs_common.hpp"
+#include "wave_reduce.hpp"
+
+using namespace gfs_se3;
+
+namespace {
+
+constexpr int kThreads = 256;
+constexpr int kSys = 27;
+constexpr int kSlabStride = kThreads + 1;
+constexpr int kSlabDoubles = kSys * kSlabStride;
+// GenerateLidarEdge / PoseLidarVisualOptimization constants (tests/test_pose_lidar_constants.py reads them from here)
+constexpr int kIts[4] = {10, 5, 5, 5};
+constexpr int kMinCloud = 50;
+constexpr double kSqDisGate = 1.0;
+constexpr double kPlaneGate = 0.2;
+constexpr double kWeightSlope = 0.9;
+constexpr double kMinWeight = 0.1;
+constexpr double kLidarInfo = 1e2;
+constexpr double kLidarValidChi2 = 4.0;
+constexpr double kThHuberLidar = 1.0;  // sqrt(1.0)
+// The map grid: cells of 1.25 m.  A map point whose float squared distance to a query is < 1.0 differs from it by at most 1 m
+// (exactly) on every axis; cells are taken of q +- 1.01 (in double), so at most 3 cells per axis, and every such point is visited.
+constexpr double kInvCell = 0.8;
+
+struct LFrame {
+  float q[4], t[3];
+  float residual_in;
+  double fx, fy, cx, cy, bf;
+  int n_obs, n_cloud, n_iter, n_lidar_inliers_in;
+  const float4* map_pts;  // sorted by bucket; w = original index (bits)
+  const int* map_start;   // [nb + 1]
+  int map_nb, map_n;
+};
+struct LState {
+  double q[4], t[3];
+  double M[12];
+  float qf[4], tf[3];
+  float avg, residual;
+  int n_inliers, n_lidar_inliers, lidar_rounds, rounds_run, iterations_run, nBad, nGood, vis_robust, done;
+  int round_edges[4], round_valid[4];
+  float round_chi2[4];
+};
+
+// ------------------------------------------------------------------ Sophus::SE3f arithmetic (float)
+__device__ void so3f_normalize(float* q) {  // Quaternionf::norm left to right, coeffs /= norm
+  float s = q[0] * q[0];
+  s = s + q[1] * q[1];
+  s = s + q[2] * q[2];
+  s = s + q[3] * q[3];
+  const float len = sqrtf(s);
+  for (int i = 0; i < 4; i++) q[i] /= len;
+}
+__device__ void init_pose_f(const float* q, const float* t, double* M) {  // Converter::toMatrix4d(SE3f(q, t).inverse())
+  float qi[4] = {-q[0], -q[1], -q[2], q[3]};
+  so3f_normalize(qi);
+  const float p[3] = {t[0] * -1.0f, t[1] * -1.0f, t[2] * -1.0f};
+  float uv[3] = {qi[1] * p[2] - qi[2] * p[1], qi[2] * p[0] - qi[0] * p[2], qi[0] * p[1] - qi[1] * p[0]};
+  for (int i = 0; i < 3; i++) uv[i] += uv[i];
+  const float cr[3] = {qi[1] * uv[2] - qi[2] * uv[1], qi[2] * uv[0] - qi[0] * uv[2], qi[0] * uv[1] - qi[1] * uv[0]};
+  const float x = qi[0], y = qi[1], z = qi[2], w = qi[3];
+  const float tx = 2 * x, ty = 2 * y, tz = 2 * z;
+  const float twx = tx * w, twy = ty * w, twz = tz * w, txx = tx * x, txy = ty * x, txz = tz * x, tyy = ty * y, tyz = tz * y, tzz = tz * z;
+  const float R[9] = {1 - (tyy + tzz), txy - twz, txz + twy, txy + twz, 1 - (txx + tzz), tyz - twx, txz - twy, tyz + twx, 1 - (txx + tyy)};
+  for (int r = 0; r < 3; r++) {
+    for (int c = 0; c < 3; c++) M[4 * r + c] = (double)R[3 * r + c];
+    M[4 * r + 3] = (double)((p[r] + w * uv[r]) + cr[r]);
+  }
+}
+__device__ void se3f_of(const double* q, const double* t, float* qf, float* tf) {
+  for (int i = 0; i < 4; i++) qf[i] = (float)q[i];
+  for (int i = 0; i < 3; i++) tf[i] = (float)t[i];
+  so3f_normalize(qf);
+}
+
+// ------------------------------------------------------------------ the map grid
+__device__ __host__ inline long long cell_of(double v) { return (long long)floor(v * kInvCell); }
+__device__ __host__ inline unsigned cell_hash(long long x, long long y, long long z, int nb) {
+  return (((unsigned)x * 73856093u) ^ ((unsigned)y * 19349663u) ^ ((unsigned)z * 83492791u)) & (unsigned)(nb - 1);
+}
+
+// (d, i) < (d', i'): the float squared distance, ties by the lower map index
+__device__ __forceinline__ bool knn_less(float d, int i, float d2, int i2) { return d < d2 || (d == d2 && i < i2); }
+
+// Eigen ColPivHouseholderQR<Matrix<float, 5, 3>>(A).solve(-1) (see the restatement for the line-by-line references).  Every index is
+// a compile-time constant; the run-time pivot column is matched against its possible values.
+__device__ __forceinline__ float sq_tail(const float (&A)[5][3], int col, int from) {
+  float s = 0.0f;
+#pragma unroll
+  for (int r = 0; r < 5; r++)
+    if (r >= from) {
+      const float v = A[r][col] * A[r][col];
+      s = r == from ? v : s + v;
+    }
+  return s;
+}
+__device__ void qr_plane(float (&A)[5][3], float* x) {
+  const float eps = 1.1920928955078125e-07f, fmin_ = 1.17549435e-38f;
+  float hc[3], nU[3], nD[3];
+  int tr[3];
+#pragma unroll
+  for (int k = 0; k < 3; k++) nU[k] = nD[k] = sqrtf(sq_tail(A, k, 0));
+  float maxn = nU[0];
+  if (nU[1] > maxn) maxn = nU[1];
+  if (nU[2] > maxn) maxn = nU[2];
+  const float th_help = ((maxn * eps) * (maxn * eps)) / 5.0f;
+  const float downdate_th = sqrtf(eps);
+  int nz = 3;
+#pragma unroll
+  for (int k = 0; k < 3; k++) {
+    int bi = k;
+    float bv = nU[k];
+#pragma unroll
+    for (int j = k + 1; j < 3; j++)
+      if (nU[j] > bv) {
+        bv = nU[j];
+        bi = j;
+      }
+    if (nz == 3 && bv * bv < th_help * (float)(5 - k)) nz = k;
+    tr[k] = bi;
+#pragma unroll
+    for (int j = k + 1; j < 3; j++)
+      if (bi == j) {
+#pragma unroll
+        for (int r = 0; r < 5; r++) {
+          const float tmp = A[r][k];
+          A[r][k] = A[r][j];
+          A[r][j] = tmp;
+        }
+        float tmp = nU[k];
+        nU[k] = nU[j];
+        nU[j] = tmp;
+        tmp = nD[k];
+        nD[k] = nD[j];
+        nD[j] = tmp;
+      }
+    const float tailSq = sq_tail(A, k, k + 1), c0 = A[k][k];
+    float tau, beta;
+    if (tailSq <= fmin_) {
+      tau = 0.0f;
+      beta = c0;
+#pragma unroll
+      for (int r = k + 1; r < 5; r++) A[r][k] = 0.0f;
+    } else {
+      beta = sqrtf(c0 * c0 + tailSq);
+      if (c0 >= 0.0f) beta = -beta;
+      const float den = c0 - beta;
+#pragma unroll
+      for (int r = k + 1; r < 5; r++) A[r][k] = A[r][k] / den;
+      tau = (beta - c0) / beta;
+    }
+    A[k][k] = beta;
+    hc[k] = tau;
+    if (tau != 0.0f) {
+#pragma unroll
+      for (int j = k + 1; j < 3; j++) {
+        float tmp = 0.0f;
+#pragma unroll
+        for (int r = k + 1; r < 5; r++) {
+          const float v = A[r][k] * A[r][j];
+          tmp = r == k + 1 ? v : tmp + v;
+        }
+        tmp += A[k][j];
+        A[k][j] -= tau * tmp;
+#pragma unroll
+        for (int r = k + 1; r < 5; r++) A[r][j] -= (tau * A[r][k]) * tmp;
+      }
+    }
+#pragma unroll
+    for (int j = k + 1; j < 3; j++) {
+      if (nU[j] != 0.0f) {
+        float temp = fabsf(A[k][j]) / nU[j];
+        temp = (1.0f + temp) * (1.0f - temp);
+        temp = temp < 0.0f ? 0.0f : temp;
+        const float ratio = nU[j] / nD[j];
+        const float temp2 = temp * (ratio * ratio);
+        if (temp2 <= downdate_th) {
+          nD[j] = sqrtf(sq_tail(A, j, k + 1));
+          nU[j] = nD[j];
+        } else {
+          nU[j] *= sqrtf(temp);
+        }
+      }
+    }
+  }
+  if (nz == 0) {
+    x[0] = x[1] = x[2] = 0.0f;
+    return;
+  }
+  float c[5] = {-1.0f, -1.0f, -1.0f, -1.0f, -1.0f};
+#pragma unroll
+  for (int k = 0; k < 3; k++) {
+    if (k >= nz || hc[k] == 0.0f) continue;
+    const float tau = hc[k];
+    float tmp = 0.0f;
+#pragma unroll
+    for (int r = k + 1; r < 5; r++) {
+      const float v = A[r][k] * c[r];
+      tmp = r == k + 1 ? v : tmp + v;
+    }
+    tmp += c[k];
+    c[k] -= tau * tmp;
+#pragma unroll
+    for (int r = k + 1; r < 5; r++) c[r] -= (tau * A[r][k]) * tmp;
+  }
+#pragma unroll
+  for (int i = 2; i >= 0; i--) {
+    if (i < nz && c[i] != 0.0f) {
+      c[i] /= A[i][i];
+#pragma unroll
+      for (int r = 0; r < i; r++) c[r] -= c[i] * A[r][i];
+    }
+  }
+  // x[perm[i]] = c[i], perm = identity with the transpositions tr[0], tr[1], tr[2] applied on the right
+  int perm[3] = {0, 1, 2};
+#pragma unroll
+  for (int k = 0; k < 3; k++)
+#pragma unroll
+    for (int j = k + 1; j < 3; j++)
+      if (tr[k] == j) {
+        const int t = perm[k];
+        perm[k] = perm[j];
+        perm[j] = t;
+      }
+  float o[3] = {0.0f, 0.0f, 0.0f};
+#pragma unroll
+  for (int i = 0; i < 3; i++) {
+    const float v = i < nz ? c[i] : 0.0f;
+#pragma unroll
+    for (int j = 0; j < 3; j++)
+      if (perm[i] == j) o[j] = v;
+  }
+  x[0] = o[0];
+  x[1] = o[1];
+  x[2] = o[2];
+}
+
+__global__ __launch_bounds__(kThreads) void k_pl_assoc(const LFrame* __restrict__ frames, const LState* __restrict__ states,
+                                                      const float* __restrict__ cloud_all, int SC, int it, uint8_t* __restrict__ flag_all,
+                                                      float4* __restrict__ plane_all, float* __restrict__ s_all) {
+  const int f = blockIdx.y, i = blockIdx.x * kThreads + threadIdx.x;
+  const LFrame& F = frames[f];
+  const LState& S = states[f];
+  if (i >= F.n_cloud || it >= F.n_iter || S.done || F.n_cloud < kMinCloud) return;
+  uint8_t* flag = flag_all + (size_t)f * SC;
+  flag[i] = 0;
+  const float* po = cloud_all + ((size_t)f * SC + i) * 3;
+  const float ox = po[0], oy = po[1], oz = po[2];
+  float q[3];
+#pragma unroll
+  for (int r = 0; r < 3; r++)  // pointAssociateToMap: double expression, stored as float
+    q[r] = (float)(S.M[4 * r] * (double)ox + S.M[4 * r + 1] * (double)oy + S.M[4 * r + 2] * (double)oz + S.M[4 * r + 3]);
+  if (!(isfinite(q[0]) && isfinite(q[1]) && isfinite(q[2]))) return;
+  // map points lie within 1e6 m (gfs_lidar_map_set): a query beyond 2e6 m on any axis is more than 1 m from every one of them and
+  // fails the gate in the brute force too; skipping it here also keeps cell_of's conversion to long long in range
+  if (fabsf(q[0]) > 2e6f || fabsf(q[1]) > 2e6f || fabsf(q[2]) > 2e6f) return;
+  float d[5];
+  int ind[5], slot[5];  // map index (the tie rule) and position in the grid's sorted copy
+#pragma unroll
+  for (int k = 0; k < 5; k++) {
+    d[k] = __builtin_inff();
+    ind[k] = 0x7fffffff;
+    slot[k] = 0;
+  }
+  long long lo[3], hi[3];
+#pragma unroll
+  for (int a = 0; a < 3; a++) {
+    lo[a] = cell_of((double)q[a] - 1.01);
+    hi[a] = cell_of((double)q[a] + 1.01);
+  }
+  for (long long cz = lo[2]; cz <= hi[2]; cz++)
+    for (long long cy = lo[1]; cy <= hi[1]; cy++)
+      for (long long cx = lo[0]; cx <= hi[0]; cx++) {
+        const unsigned b = cell_hash(cx, cy, cz, F.map_nb);
+        const int e = F.map_start[b + 1];
+        for (int m = F.map_start[b]; m < e; m++) {
+          const float4 P = F.map_pts[m];
+          // the bucket may hold other cells' points (hash collisions): each point is taken in its own cell only
+          if (cell_of((double)P.x) != cx || cell_of((double)P.y) != cy || cell_of((double)P.z) != cz) continue;
+          const float dx = q[0] - P.x, dy = q[1] - P.y, dz = q[2] - P.z;
+          float dd = 0.0f;  // FLANN L2: ((0 + dx^2) + dy^2) + dz^2
+          dd += dx * dx;
+          dd += dy * dy;
+          dd += dz * dz;
+          const int mi = __float_as_int(P.w);
+          if (!knn_less(dd, mi, d[4], ind[4])) continue;
+#pragma unroll
+          for (int k = 4; k >= 0; k--) {  // insertion from the back: slot k - 1 is read before it is overwritten
+            const int kp = k > 0 ? k - 1 : 0;
+            const bool lt_k = knn_less(dd, mi, d[k], ind[k]);
+            const bool lt_prev = k > 0 && knn_less(dd, mi, d[kp], ind[kp]);
+            if (lt_k) {
+              d[k] = lt_prev ? d[kp] : dd;
+              ind[k] = lt_prev ? ind[kp] : mi;
+              slot[k] = lt_prev ? slot[kp] : m;
+            }
+          }
+        }
+      }
+  if (ind[4] == 0x7fffffff || !(d[4] < kSqDisGate)) return;
+  float N[5][3], A[5][3];  // matA0: the neighbours as rows, in distance order
+#pragma unroll
+  for (int k = 0; k < 5; k++) {
+    const float4 P = F.map_pts[slot[k]];
+    N[k][0] = A[k][0] = P.x;
+    N[k][1] = A[k][1] = P.y;
+    N[k][2] = A[k][2] = P.z;
+  }
+  float X[3];
+  qr_plane(A, X);
+  float pa = X[0], pb = X[1], pc = X[2], pd = 1;
+  const float ps = sqrtf(pa * pa + pb * pb + pc * pc);
+  pa /= ps;
+  pb /= ps;
+  pc /= ps;
+  pd /= ps;
+  bool valid = true;
+#pragma unroll
+  for (int k = 0; k < 5; k++)
+    if ((double)fabsf(pa * N[k][0] + pb * N[k][1] + pc * N[k][2] + pd) > kPlaneGate) valid = false;
+  if (!valid) return;
+  const float pd2 = pa * q[0] + pb * q[1] + pc * q[2] + pd;
+  const float s = (float)(1 - kWeightSlope * (double)fabsf(pd2) / (double)sqrtf(sqrtf(q[0] * q[0] + q[1] * q[1] + q[2] * q[2])));
+  if (!((double)s > kMinWeight)) return;
+  flag[i] = 1;
+  plane_all[(size_t)f * SC + i] = make_float4(pa, pb, pc, pd);
+  s_all[(size_t)f * SC + i] = s;
+}
+
+// ------------------------------------------------------------------ edges
+__device__ __forceinline__ void se3_inverse(const double* q, const double* t, double* W) {  // SE3Quat::inverse -> W = (q', t')
+  W[0] = -q[0];
+  W[1] = -q[1];
+  W[2] = -q[2];
+  W[3] = q[3];
+  const double nt[3] = {t[0] * -1., t[1] * -1., t[2] * -1.};
+  quat_rotate(W, nt, W + 4);
+}
+__device__ __forceinline__ double lidar_err(const double* W, const double* p, const float4 pl, float s) {
+  double pw[3];
+  quat_rotate(W, p, pw);
+  pw[0] += W[4];
+  pw[1] += W[5];
+  pw[2] += W[6];
+  const double dot = pw[0] * (double)pl.x + pw[1] * (double)pl.y + pw[2] * (double)pl.z;
+  return (double)s * (dot + (double)pl.w);
+}
+__device__ __forceinline__ void vis_err(const LFrame& F, const double* xw, const double* obs, bool st, const double* q, const double* t,
+                                        double* r) {
+  double xc[3];
+  quat_rotate(q, xw, xc);
+  xc[0] += t[0];
+  xc[1] += t[1];
+  xc[2] += t[2];
+  if (st) {
+    const float invz = (float)(1.0 / xc[2]);
+    const double u = xc[0] * (double)invz * F.fx + F.cx, v = xc[1] * (double)invz * F.fy + F.cy;
+    r[0] = obs[0] - u;
+    r[1] = obs[1] - v;
+    r[2] = obs[2] - (u - F.bf * (double)invz);
+  } else {
+    r[0] = obs[0] - (F.fx * xc[0] / xc[2] + F.cx);
+    r[1] = obs[1] - (F.fy * xc[1] / xc[2] + F.cy);
+    r[2] = 0;
+  }
+}
+__device__ __forceinline__ double vis_chi2(const double* r, double w, bool st) {
+  return st ? (r[0] * w * r[0] + r[1] * w * r[1] + r[2] * w * r[2]) : (r[0] * w * r[0] + r[1] * w * r[1]);
+}
+
+// Eigen::LDLT<MatrixXd> on the 6x6 (lower triangle H21, lambda on the diagonal), thread 0 only; false unless positive
+__device__ bool ldlt6(const double* H21, double lambda, const double* b, double* x) {
+  double A[6][6];
+  int o = 0;
+  for (int a = 0; a < 6; a++)
+    for (int c = 0; c <= a; c++) {
+      A[a][c] = H21[o];
+      A[c][a] = H21[o];
+      o++;
+    }
+  for (int a = 0; a < 6; a++) A[a][a] += lambda;
+  int tr[6], sign = 0;
+  for (int k = 0; k < 6; k++) {
+    int p = k;
+    double best = fabs(A[k][k]);
+    for (int i = k + 1; i < 6; i++)
+      if (fabs(A[i][i]) > best) {
+        best = fabs(A[i][i]);
+        p = i;
+      }
+    tr[k] = p;
+    if (p != k) {
+      for (int j = 0; j < k; j++) {
+        const double t = A[k][j];
+        A[k][j] = A[p][j];
+        A[p][j] = t;
+      }
+      for (int i = p + 1; i < 6; i++) {
+        const double t = A[i][k];
+        A[i][k] = A[i][p];
+        A[i][p] = t;
+      }
+      {
+        const double t = A[k][k];
+        A[k][k] = A[p][p];
+        A[p][p] = t;
+      }
+      for (int i = k + 1; i < p; i++) {
+        const double t = A[i][k];
+        A[i][k] = A[p][i];
+        A[p][i] = t;
+      }
+    }
+    if (k > 0) {
+      double temp[6];
+      for (int j = 0; j < k; j++) temp[j] = A[j][j] * A[k][j];
+      double acc = 0;
+      for (int j = 0; j < k; j++) acc += A[k][j] * temp[j];
+      A[k][k] -= acc;
+      for (int i = k + 1; i < 6; i++) {
+        double a2 = 0;
+        for (int j = 0; j < k; j++) a2 += A[i][j] * temp[j];
+        A[i][k] -= a2;
+      }
+    }
+    const double akk = A[k][k];
+    if (fabs(akk) > 0)
+      for (int i = k + 1; i < 6; i++) A[i][k] /= akk;
+    if (sign == 1) {
+      if (akk < 0) sign = 2;
+    } else if (sign == -1) {
+      if (akk > 0) sign = 2;
+    } else if (sign == 0) {
+      if (akk > 0) sign = 1;
+      else if (akk < 0) sign = -1;
+    }
+  }
+  if (sign != 1) return false;
+  double y[6];
+  for (int i = 0; i < 6; i++) y[i] = b[i];
+  for (int k = 0; k < 6; k++) {
+    const double t = y[k];
+    y[k] = y[tr[k]];
+    y[tr[k]] = t;
+  }
+  for (int i = 0; i < 6; i++)
+    for (int j = 0; j < i; j++) y[i] -= A[i][j] * y[j];
+  for (int i = 0; i < 6; i++) y[i] = fabs(A[i][i]) > 2.2250738585072014e-308 ? y[i] / A[i][i] : 0.0;
+  for (int i = 5; i >= 0; i--)
+    for (int j = i + 1; j < 6; j++) y[i] -= A[j][i] * y[j];
+  for (int k = 5; k >= 0; k--) {
+    const double t = y[k];
+    y[k] = y[tr[k]];
+    y[tr[k]] = t;
+  }
+  for (int i = 0; i < 6; i++) x[i] = y[i];
+  return true;
+}
+
+__device__ double block_sum(double v, double* s4) {  // fixed shape: wave shuffle tree, then the four waves in order
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int ofs = 32; ofs > 0; ofs >>= 1) v += __shfl_down(v, ofs, 64);
+  __syncthreads();
+  if (lane == 0) s4[wave] = v;
+  __syncthreads();
+  const double r = ((s4[0] + s4[1]) + s4[2]) + s4[3];
+  __syncthreads();
+  return r;
+}
+
+struct VisView {
+  const double *xw, *obs;
+  const float* w;
+  const uint8_t* st;
+  double *err, *chi2;
+  uint8_t *level, *outl;
+};
+
+template <bool kTree>
+__global__ __launch_bounds__(kThreads) void k_pl_round(const LFrame* __restrict__ frames, LState* __restrict__ states, VisView V, int S,
+                                                      const float* __restrict__ cloud_all, const uint8_t* __restrict__ flag_all,
+                                                      const float4* __restrict__ plane_all, const float* __restrict__ s_all, int SC,
+                                                      int* __restrict__ eidx_all, float4* __restrict__ eplane_all,
+                                                      float* __restrict__ es_all, double* __restrict__ lerr_all,
+                                                      double* __restrict__ lchi2_all, int it) {
+  __shared__ double s_slab[kSlabDoubles];
+  __shared__ double s4[4];
+  __shared__ double s_T[7], s_Tb[7], s_Wp[12][7], s_sys[kSys], s_x[6];
+  __shared__ int s_flag[3], s_wcnt[4];
+  const int f = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const LFrame F = frames[f];
+  LState& ST = states[f];
+  if (it >= F.n_iter || ST.done) return;
+  const int n = F.n_obs;
+  const double* xw = V.xw + (size_t)f * S * 3;
+  const double* obs = V.obs + (size_t)f * S * 3;
+  const float* wv = V.w + (size_t)f * S;
+  const uint8_t* st = V.st + (size_t)f * S;
+  double* err = V.err + (size_t)f * S * 3;
+  double* chi2 = V.chi2 + (size_t)f * S;
+  uint8_t* level = V.level + (size_t)f * S;
+  uint8_t* outl = V.outl + (size_t)f * S;
+  const size_t rbase = ((size_t)f * 4 + it) * SC;
+  int* eidx = eidx_all + rbase;
+  float4* eplane = eplane_all + rbase;
+  float* es = es_all + rbase;
+  double* lerr = lerr_all + (size_t)f * SC;
+  double* lchi2 = lchi2_all + (size_t)f * SC;
+  const float* cloud = cloud_all + (size_t)f * SC * 3;
+
+  // ---- compaction of the surviving points in cloud-index order (GenerateLidarEdge's vector, nullptr entries skipped)
+  int nl = 0;
+  if (F.n_cloud >= kMinCloud)
+    for (int base = 0; base < F.n_cloud; base += kThreads) {
+      const int i = base + tid;
+      const bool keep = i < F.n_cloud && flag_all[(size_t)f * SC + i];
+      const unsigned long long m = __ballot(keep);
+      const int below = __popcll(m & ((1ull << lane) - 1ull));
+      if (lane == 0) s_wcnt[wave] = __popcll(m);
+      __syncthreads();
+      int off = nl;
+      for (int w = 0; w < wave; w++) off += s_wcnt[w];
+      if (keep) {
+        const int pos = off + below;
+        eidx[pos] = i;
+        eplane[pos] = plane_all[(size_t)f * SC + i];
+        es[pos] = s_all[(size_t)f * SC + i];
+      }
+      nl += s_wcnt[0] + s_wcnt[1] + s_wcnt[2] + s_wcnt[3];
+      __syncthreads();
+    }
+  __syncthreads();
+  if (tid < 4) s_T[tid] = ST.q[tid];
+  if (tid < 3) s_T[4 + tid] = ST.t[tid];
+  __syncthreads();
+  auto edge_p = [&](int l, double* p) {
+    const int i = eidx[l];
+    p[0] = (double)cloud[3 * i];
+    p[1] = (double)cloud[3 * i + 1];
+    p[2] = (double)cloud[3 * i + 2];
+  };
+  // ---- chi2Lidar (a float, edge after edge) and valid_edge at the current estimate
+  {
+    double W[7];
+    se3_inverse(s_T, s_T + 4, W);
+    float chiL = 0.0f;  // thread 0
+    int valid = 0;
+    for (int base = 0; base < nl; base += kSlabDoubles) {
+      const int cnt = min(kSlabDoubles, nl - base);
+      for (int l = base + tid; l < base + cnt; l += kThreads) {
+        double p[3];
+        edge_p(l, p);
+        const double e = lidar_err(W, p, eplane[l], es[l]);
+        const double c = e * (kLidarInfo * e);
+        lerr[l] = e;
+        lchi2[l] = c;
+        valid += c < kLidarValidChi2 ? 1 : 0;
+        s_slab[l - base] = c;
+      }
+      __syncthreads();
+      if (tid == 0)
+        for (int j = 0; j < cnt; j++) chiL += s_slab[j];
+      __syncthreads();
+    }
+    const int n_valid = (int)block_sum((double)valid, s4);
+    if (tid == 0) {
+      ST.rounds_run = it + 1;
+      ST.round_edges[it] = nl;
+      ST.round_valid[it] = n_valid;
+      if (nl > 0) {
+        chiL /= (float)nl;
+        ST.round_chi2[it] = chiL;
+        ST.n_lidar_inliers = n_valid;
+        ST.residual = chiL;
+      }
+    }
+  }
+  if (nl == 0) return;  // `continue`: no optimisation, no re-classification
+  const bool vis_robust = ST.vis_robust != 0;
+  const double dMono = (double)(float)sqrt(5.991), dStereo = (double)(float)sqrt(7.815);
+  const int E = n + nl;
+
+  // errors + chi2 of the active edges at s_T; activeRobustChi2 (valid in thread 0)
+  auto compute_active = [&]() {
+    double T[7], W[7];
+    for (int k = 0; k < 7; k++) T[k] = s_T[k];
+    se3_inverse(T, T + 4, W);
+    auto term_of = [&](int e) -> double {
+      if (e < n) {
+        if (level[e]) return 0.0;
+        double r[3];
+        vis_err(F, xw + 3 * e, obs + 3 * e, st[e] != 0, T, T + 4, r);
+        const double c = vis_chi2(r, (double)wv[e], st[e] != 0);
+        err[3 * e] = r[0];
+        err[3 * e + 1] = r[1];
+        err[3 * e + 2] = r[2];
+        chi2[e] = c;
+        double t = c, r1;
+        if (vis_robust) huber(c, st[e] ? dStereo : dMono, &t, &r1);
+        return t;
+      }
+      const int l = e - n;
+      double p[3];
+      edge_p(l, p);
+      const double ev = lidar_err(W, p, eplane[l], es[l]);
+      const double c = ev * (kLidarInfo * ev);
+      lerr[l] = ev;
+      lchi2[l] = c;
+      double t, r1;
+      huber(c, kThHuberLidar, &t, &r1);
+      return t;
+    };
+    double chi = 0;
+    if constexpr (kTree) {
+      double mine = 0;
+      for (int e = tid; e < E; e += kThreads) mine += term_of(e);
+      return block_sum(mine, s4);
+    }
+    for (int base = 0; base < E; base += kSlabDoubles) {
+      const int cnt = min(kSlabDoubles, E - base);
+      for (int e = base + tid; e < base + cnt; e += kThreads) s_slab[e - base] = term_of(e);
+      __syncthreads();
+      if (tid == 0)
+        for (int j = 0; j < cnt; j++) chi += s_slab[j];
+      __syncthreads();
+    }
+    return chi;
+  };
+
+  int iterations = 0;
+  double currentLambda = -1, ni = 2;
+  int nBadLm = 0;
+  for (int iteration = 0; iteration < kIts[it]; iteration++) {
+    double currentChi = compute_active();
+    const double iniChi = currentChi;
+    // ---- the twelve perturbed poses of the numeric Jacobian, inverted (shared by every lidar edge)
+    if (tid < 12) {
+      double u[6] = {0, 0, 0, 0, 0, 0}, qp[4], tp[3];
+      u[tid >> 1] = (tid & 1) ? -1e-9 : 1e-9;
+      pose_oplus(s_T, s_T + 4, u, qp, tp);
+      se3_inverse(qp, tp, s_Wp[tid]);
+    }
+    __syncthreads();
+    // ---- buildSystem
+    {
+      double T[7];
+      for (int k = 0; k < 7; k++) T[k] = s_T[k];
+      double run = 0, tsum[kSys];
+#pragma unroll
+      for (int k = 0; k < kSys; k++) tsum[k] = 0;
+      for (int base = 0; base < E; base += kThreads) {
+        const int e = base + tid;
+        double acc[kSys];
+#pragma unroll
+        for (int k = 0; k < kSys; k++) acc[k] = 0;
+        if (e < n && !level[e]) {
+          double xc[3];
+          quat_rotate(T, xw + 3 * e, xc);
+          xc[0] += T[4];
+          xc[1] += T[5];
+          xc[2] += T[6];
+          const double x = xc[0], y = xc[1], z = xc[2];
+          double J[18];
+          const bool three = st[e] != 0;
+          if (three) {
+            const double invz = 1.0 / z, invz_2 = invz * invz;
+            J[0] = x * y * invz_2 * F.fx;
+            J[1] = -(1 + (x * x * invz_2)) * F.fx;
+            J[2] = y * invz * F.fx;
+            J[3] = -invz * F.fx;
+            J[4] = 0;
+            J[5] = x * invz_2 * F.fx;
+            J[6] = (1 + y * y * invz_2) * F.fy;
+            J[7] = -x * y * invz_2 * F.fy;
+            J[8] = -x * invz * F.fy;
+            J[9] = 0;
+            J[10] = -invz * F.fy;
+            J[11] = y * invz_2 * F.fy;
+            J[12] = J[0] - F.bf * y * invz_2;
+            J[13] = J[1] + F.bf * x * invz_2;
+            J[14] = J[2];
+            J[15] = J[3];
+            J[16] = 0;
+            J[17] = J[5] - F.bf * invz_2;
+          } else {
+            const double pj[6] = {F.fx / z, 0, -F.fx * x / (z * z), 0, F.fy / z, -F.fy * y / (z * z)};
+            const double D[18] = {0, z, -y, 1, 0, 0, -z, 0, x, 0, 1, 0, y, -x, 0, 0, 0, 1};
+#pragma unroll
+            for (int r = 0; r < 2; r++)
+#pragma unroll
+              for (int c = 0; c < 6; c++) J[6 * r + c] = -(pj[3 * r] * D[c] + pj[3 * r + 1] * D[6 + c] + pj[3 * r + 2] * D[12 + c]);
+#pragma unroll
+            for (int c = 0; c < 6; c++) J[12 + c] = 0;
+          }
+          const double w = (double)wv[e];
+          double rho1 = 1.0;
+          if (vis_robust) {
+            double r0;
+            huber(chi2[e], three ? dStereo : dMono, &r0, &rho1);
+          }
+          const double r[3] = {err[3 * e], err[3 * e + 1], err[3 * e + 2]};
+          int o = 0;
+#pragma unroll
+          for (int a = 0; a < 6; a++) {
+            double sb = 0;
+            sb += ((rho1 * J[a]) * w) * r[0];
+            sb += ((rho1 * J[6 + a]) * w) * r[1];
+            const double sb3 = sb + ((rho1 * J[12 + a]) * w) * r[2];
+            acc[21 + a] = -(three ? sb3 : sb);
+#pragma unroll
+            for (int c = 0; c <= a; c++) {
+              double hh = 0;
+              hh += (J[a] * (rho1 * w)) * J[c];
+              hh += (J[6 + a] * (rho1 * w)) * J[6 + c];
+              const double hh3 = hh + (J[12 + a] * (rho1 * w)) * J[12 + c];
+              acc[o++] = three ? hh3 : hh;
+            }
+          }
+        } else if (e >= n && e < E) {
+          const int l = e - n;
+          double p[3];
+          edge_p(l, p);
+          const float4 pl = eplane[l];
+          const float sl = es[l];
+          double J[6];
+#pragma unroll
+          for (int d = 0; d < 6; d++) J[d] = (1.0 / (2 * 1e-9)) * (lidar_err(s_Wp[2 * d], p, pl, sl) - lidar_err(s_Wp[2 * d + 1], p, pl, sl));
+          double r0, rho1;
+          huber(lchi2[l], kThHuberLidar, &r0, &rho1);
+          const double ev = lerr[l];
+          int o = 0;
+#pragma unroll
+          for (int a = 0; a < 6; a++) {
+            acc[21 + a] = -(((rho1 * J[a]) * kLidarInfo) * ev);
+#pragma unroll
+            for (int c = 0; c <= a; c++) acc[o++] = (J[a] * (rho1 * kLidarInfo)) * J[c];
+          }
+        }
+        if constexpr (kTree) {
+#pragma unroll
+          for (int k = 0; k < kSys; k++) tsum[k] += acc[k];
+        } else {
+#pragma unroll
+          for (int k = 0; k < kSys; k++) s_slab[k * kSlabStride + tid] = acc[k];
+          __syncthreads();
+          if (tid < kSys) {
+            const int cnt = min(kThreads, E - base);
+            const double* row = s_slab + tid * kSlabStride;
+            for (int j = 0; j < cnt; j++) run += row[j];
+          }
+          __syncthreads();
+        }
+      }
+      if constexpr (kTree) run = gfs_red::block_sum_many<kSys, kThreads / 64>(tsum, s_slab);
+      if (tid < kSys) s_sys[tid] = run;
+      __syncthreads();
+    }
+    if (tid == 0 && iteration == 0) {  // computeLambdaInit
+      double maxDiagonal = 0;
+      for (int a = 0; a < 6; a++) maxDiagonal = fmax(fabs(s_sys[a * (a + 1) / 2 + a]), maxDiagonal);
+      currentLambda = 1e-5 * maxDiagonal;
+      ni = 2;
+      nBadLm = 0;
+    }
+    double rho = 0;
+    int qmax = 0;
+    bool again = true;
+    while (again) {
+      if (tid == 0) {
+        for (int k = 0; k < 7; k++) s_Tb[k] = s_T[k];
+        double x[6], b6[6];
+        for (int k = 0; k < 6; k++) b6[k] = s_sys[21 + k];
+        const bool ok2 = ldlt6(s_sys, currentLambda, b6, x);
+        if (ok2) {
+          double qn[4], tn[3];
+          pose_oplus(s_T, s_T + 4, x, qn, tn);
+          for (int k = 0; k < 4; k++) s_T[k] = qn[k];
+          for (int k = 0; k < 3; k++) s_T[4 + k] = tn[k];
+        }
+        for (int a = 0; a < 6; a++) s_x[a] = ok2 ? x[a] : 0.0;
+        s_flag[0] = ok2 ? 1 : 0;
+      }
+      __syncthreads();
+      double tempChi = compute_active();
+      if (tid == 0) {
+        const bool ok2 = s_flag[0] != 0;
+        if (!ok2) tempChi = 1.79769313486231570e308;
+        rho = currentChi - tempChi;
+        double scale = 0;
+        if (ok2)
+          for (int a = 0; a < 6; a++) scale += s_x[a] * (currentLambda * s_x[a] + s_sys[21 + a]);
+        scale += 1e-3;
+        rho /= scale;
+        if (rho > 0 && isfinite(tempChi)) {
+          double alpha = 1. - gfs_glibc::pow3(2 * rho - 1);
+          alpha = fmin(alpha, 2. / 3.);
+          const double scaleFactor = fmax(1. / 3., alpha);
+          currentLambda *= scaleFactor;
+          ni = 2;
+          currentChi = tempChi;
+        } else {
+          currentLambda *= ni;
+          ni *= 2;
+          for (int k = 0; k < 7; k++) s_T[k] = s_Tb[k];
+        }
+        qmax++;
+        s_flag[1] = (rho < 0 && qmax < 10) ? 1 : 0;
+      }
+      __syncthreads();
+      again = s_flag[1] != 0;
+      __syncthreads();
+    }
+    iterations++;
+    if (tid == 0) {
+      int stop = 0;
+      if (qmax == 10 || rho == 0) stop = 1;
+      if (!stop) {
+        if ((iniChi - currentChi) * 1e3 < iniChi) nBadLm++;
+        else nBadLm = 0;
+        if (nBadLm >= 3) stop = 1;
+      }
+      s_flag[0] = stop;
+    }
+    __syncthreads();
+    const int stop = s_flag[0];
+    __syncthreads();
+    if (stop) break;
+  }
+  // ---- re-classification of the visual edges at the final estimate: mono list, then stereo list
+  {
+    double T[7];
+    for (int k = 0; k < 7; k++) T[k] = s_T[k];
+    for (int e = tid; e < n; e += kThreads)
+      if (outl[e]) {
+        double r[3];
+        vis_err(F, xw + 3 * e, obs + 3 * e, st[e] != 0, T, T + 4, r);
+        err[3 * e] = r[0];
+        err[3 * e + 1] = r[1];
+        err[3 * e + 2] = r[2];
+        chi2[e] = vis_chi2(r, (double)wv[e], st[e] != 0);
+      }
+  }
+  __syncthreads();
+  float* s_term = reinterpret_cast<float*>(s_slab);
+  constexpr int kTerms = 2 * kSlabDoubles;
+  int bad_local = 0, good_local = 0;
+  float avg = 0.0f;
+  double mine_avg = 0.0;
+  for (int pass = 0; pass < 2; pass++)
+    for (int base = 0; base < n; base += kTerms) {
+      const int cnt = min(kTerms, n - base);
+      for (int e = base + tid; e < base + cnt; e += kThreads) {
+        float term = 0.0f;
+        if ((st[e] != 0) == (pass == 1)) {
+          const float c = (float)chi2[e];
+          const bool out = c > (pass ? 7.815f : 5.991f);
+          outl[e] = out ? 1 : 0;
+          level[e] = out ? 1 : 0;
+          bad_local += out ? 1 : 0;
+          good_local += out ? 0 : 1;
+          if (!out) term = c;
+        }
+        if constexpr (kTree) mine_avg += (double)term;
+        else s_term[e - base] = term;
+      }
+      if constexpr (!kTree) {
+        __syncthreads();
+        if (tid == 0)
+          for (int j = 0; j < cnt; j++) avg += s_term[j];
+        __syncthreads();
+      }
+    }
+  if constexpr (kTree) avg = (float)block_sum(mine_avg, s4);
+  const int nBad = (int)block_sum((double)bad_local, s4);
+  const int nGood = (int)block_sum((double)good_local, s4);
+  if (tid == 0) {
+    ST.nBad = nBad;
+    ST.nGood += nGood;  // never reset
+    ST.avg = avg / (float)ST.nGood;
+    ST.n_inliers = n - nBad;
+    ST.iterations_run += iterations;
+    ST.lidar_rounds++;
+    for (int k = 0; k < 4; k++) ST.q[k] = s_T[k];
+    for (int k = 0; k < 3; k++) ST.t[k] = s_T[4 + k];
+    se3f_of(ST.q, ST.t, ST.qf, ST.tf);
+    init_pose_f(ST.qf, ST.tf, ST.M);
+    if (it == 2) ST.vis_robust = 0;
+    if (n < 10) ST.done = 1;  // optimizer.edges().size() < 10
+  }
+}
+
+__global__ void k_pl_init(const LFrame* __restrict__ frames, LState* __restrict__ states, VisView V, int S) {
+  const int f = blockIdx.x;
+  const LFrame& F = frames[f];
+  for (int e = threadIdx.x; e < F.n_obs; e += blockDim.x) {
+    V.outl[(size_t)f * S + e] = 0;
+    V.level[(size_t)f * S + e] = 0;
+    V.chi2[(size_t)f * S + e] = 0;
+  }
+  if (threadIdx.x) return;
+  LState s;
+  for (int k = 0; k < 4; k++) s.q[k] = (double)F.q[k];
+  for (int k = 0; k < 3; k++) s.t[k] = (double)F.t[k];
+  normalize_rotation(s.q);
+  init_pose_f(F.q, F.t, s.M);
+  s.done = F.n_obs < 3;  // return 0 before anything else, SetPose not called
+  if (s.done) {
+    for (int k = 0; k < 4; k++) s.qf[k] = F.q[k];
+    for (int k = 0; k < 3; k++) s.tf[k] = F.t[k];
+  } else {
+    se3f_of(s.q, s.t, s.qf, s.tf);
+  }
+  s.avg = 0.f;
+  s.residual = F.residual_in;
+  s.n_lidar_inliers = F.n_lidar_inliers_in;
+  s.lidar_rounds = s.rounds_run = s.iterations_run = s.nBad = s.nGood = 0;
+  s.n_inliers = s.done ? 0 : F.n_obs;  // nInitialCorrespondences - nBad when no round re-classifies
+  s.vis_robust = 1;
+  for (int k = 0; k < 4; k++) {
+    s.round_edges[k] = s.round_valid[k] = 0;
+    s.round_chi2[k] = 0.f;
+  }
+  states[f] = s;
+}
+
+size_t next_pow2(size_t v) {
+  size_t p = 64;
+  while (p < v) p <<= 1;
+  return p;
+}
+
+}  // namespace
+
+struct gfs_lidar_map {
+  int device, max_points, n = 0, nb = 0;
+  gfs::DevBuf<float4> d_pts;
+  gfs::DevBuf<int> d_start;
+};
+
+struct gfs_pose_lidar {
+  int device, max_obs, max_cloud, max_batch;
+  hipStream_t stream;
+  std::mutex mu;
+  int sum_order = GFS_POSE_SUMS_EDGE_ORDER;
+  struct Layout {
+    size_t o_xw, o_obs, o_w, o_st, o_cloud, in_bytes;
+  };
+  static Layout layout(size_t B, size_t S, size_t SC) {
+    auto up = [](size_t v) { return gfs::align_up(v, 256); };
+    Layout L;
+    L.o_xw = up(B * sizeof(LFrame));
+    L.o_obs = L.o_xw + up(B * S * 24);
+    L.o_w = L.o_obs + up(B * S * 24);
+    L.o_st = L.o_w + up(B * S * 4);
+    L.o_cloud = L.o_st + up(B * S);
+    L.in_bytes = L.o_cloud + up(B * SC * 12);
+    return L;
+  }
+  gfs::DevBuf<uint8_t> d_in;
+  gfs::PinBuf<uint8_t> h_in;
+  gfs::DevBuf<LState> d_state;
+  gfs::PinBuf<LState> h_state;
+  gfs::DevBuf<double> d_err, d_chi2, d_lerr, d_lchi2;
+  gfs::PinBuf<double> h_chi2;
+  gfs::DevBuf<uint8_t> d_level, d_outl, d_flag;
+  gfs::PinBuf<uint8_t> h_outl;
+  gfs::DevBuf<float4> d_plane, d_eplane;
+  gfs::DevBuf<float> d_s, d_es;
+  gfs::DevBuf<int> d_eidx;
+  // the last call's shape, for gfs_pose_lidar_fetch_edges
+  int last_B = 0, last_SC = 0;
+  std::vector<int> last_edges;  // [B][4]
+};
+
+extern "C" {
+
+int gfs_lidar_map_create(int device, int max_points, gfs_lidar_map** out) {
+  GFS_REQUIRE(out && max_points >= 5, GFS_ERR_INVALID_ARG, "gfs_lidar_map_create: invalid argument");
+  if (!gfs::device_ok(device)) return GFS_ERR_NO_DEVICE;
+  GFS_HIP(hipSetDevice(device));
+  std::unique_ptr<gfs_lidar_map> m(new gfs_lidar_map);
+  m->device = device;
+  m->max_points = max_points;
+  int rc = m->d_pts.alloc((size_t)max_points);
+  if (!rc) rc = m->d_start.alloc(next_pow2(2 * (size_t)max_points) + 1);
+  if (rc) return rc;
+  *out = m.release();
+  return GFS_OK;
+}
+
+void gfs_lidar_map_destroy(gfs_lidar_map* m) {
+  if (!m) return;
+  (void)hipSetDevice(m->device);
+  delete m;
+}
+
+// The grid is a counting sort of the points by the hash of their 1.25 m cell, built on the host (the map changes at key-frame rate)
+// and uploaded with the bucket offsets.  Points keep their original index for the distance ties.
+int gfs_lidar_map_set(gfs_lidar_map* m, const float* xyz, int n) {
+  GFS_REQUIRE(m && (xyz || n == 0), GFS_ERR_INVALID_ARG, "gfs_lidar_map_set: invalid argument");
+  GFS_REQUIRE(n >= 5, GFS_ERR_INVALID_ARG, "gfs_lidar_map_set: %d map points (the reference reads the 5th neighbour)", n);
+  GFS_REQUIRE(n <= m->max_points, GFS_ERR_CAPACITY, "gfs_lidar_map_set: %d points exceed capacity %d", n, m->max_points);
+  for (int i = 0; i < 3 * n; i++)
+    GFS_REQUIRE(std::isfinite(xyz[i]) && std::fabs(xyz[i]) < 1e6f, GFS_ERR_INVALID_ARG,
+                "gfs_lidar_map_set: point %d is not finite or beyond 1e6 m", i / 3);
+  const int nb = (int)next_pow2(2 * (size_t)n);
+  std::vector<unsigned> key(n);
+  std::vector<int> start(nb + 1, 0);
+  for (int i = 0; i < n; i++) {
+    key[i] = cell_hash(cell_of((double)xyz[3 * i]), cell_of((double)xyz[3 * i + 1]), cell_of((double)xyz[3 * i + 2]), nb);
+    start[key[i] + 1]++;
+  }
+  for (int b = 0; b < nb; b++) start[b + 1] += start[b];
+  std::vector<int> fill(start.begin(), start.end() - 1);
+  std::vector<float4> pts(n);
+  for (int i = 0; i < n; i++) {
+    float4 P;
+    P.x = xyz[3 * i];
+    P.y = xyz[3 * i + 1];
+    P.z = xyz[3 * i + 2];
+    int bits = i;
+    memcpy(&P.w, &bits, 4);
+    pts[fill[key[i]]++] = P;
+  }
+  GFS_HIP(hipSetDevice(m->device));
+  GFS_HIP(hipMemcpy(m->d_pts.p, pts.data(), (size_t)n * sizeof(float4), hipMemcpyHostToDevice));
+  GFS_HIP(hipMemcpy(m->d_start.p, start.data(), (size_t)(nb + 1) * sizeof(int), hipMemcpyHostToDevice));
+  m->n = n;
+  m->nb = nb;
+  return GFS_OK;
+}
+
+int gfs_pose_lidar_create(int device, int max_obs, int max_cloud, int max_batch, gfs_pose_lidar** out) {
+  GFS_REQUIRE(out && max_obs > 0 && max_cloud > 0 && max_batch > 0, GFS_ERR_INVALID_ARG, "gfs_pose_lidar_create: invalid argument");
+  if (!gfs::device_ok(device)) return GFS_ERR_NO_DEVICE;
+  GFS_HIP(hipSetDevice(device));
+  std::unique_ptr<gfs_pose_lidar> h(new gfs_pose_lidar);
+  h->device = device;
+  h->max_obs = max_obs;
+  h->max_cloud = max_cloud;
+  h->max_batch = max_batch;
+  GFS_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+  const size_t S = gfs::align_up((size_t)max_obs, 64), SC = gfs::align_up((size_t)max_cloud, 64), B = max_batch;
+  const gfs_pose_lidar::Layout L = gfs_pose_lidar::layout(B, S, SC);
+  int rc = 0;
+#define A(x) if (!rc) rc = (x)
+  A(h->d_in.alloc(L.in_bytes));
+  A(h->h_in.alloc(L.in_bytes));
+  A(h->d_state.alloc(B));
+  A(h->h_state.alloc(B));
+  A(h->d_err.alloc(B * S * 3));
+  A(h->d_chi2.alloc(B * S));
+  A(h->h_chi2.alloc(B * S));
+  A(h->d_level.alloc(B * S));
+  A(h->d_outl.alloc(B * S));
+  A(h->h_outl.alloc(B * S));
+  A(h->d_flag.alloc(B * SC));
+  A(h->d_plane.alloc(B * SC));
+  A(h->d_s.alloc(B * SC));
+  A(h->d_lerr.alloc(B * SC));
+  A(h->d_lchi2.alloc(B * SC));
+  A(h->d_eidx.alloc(B * 4 * SC));
+  A(h->d_eplane.alloc(B * 4 * SC));
+  A(h->d_es.alloc(B * 4 * SC));
+#undef A
+  if (rc) {
+    (void)hipStreamDestroy(h->stream);
+    return rc;
+  }
+  *out = h.release();
+  return GFS_OK;
+}
+
+void gfs_pose_lidar_destroy(gfs_pose_lidar* h) {
+  if (!h) return;
+  (void)hipSetDevice(h->device);
+  (void)hipStreamSynchronize(h->stream);
+  (void)hipStreamDestroy(h->stream);
+  delete h;
+}
+
+int gfs_pose_lidar_set_sum_order(gfs_pose_lidar* h, int order) {
+  GFS_REQUIRE(h && (order == GFS_POSE_SUMS_TREE || order == GFS_POSE_SUMS_EDGE_ORDER), GFS_ERR_INVALID_ARG,
+              "gfs_pose_lidar_set_sum_order: invalid argument");
+  std::lock_guard<std::mutex> lk(h->mu);
+  h->sum_order = order;
+  return GFS_OK;
+}
+
+int gfs_pose_lidar_optimize(gfs_pose_lidar* h, const gfs_pose_lidar_problem* problems, int B, gfs_pose_lidar_solution* solutions) {
+  GFS_REQUIRE(h && problems && solutions && B > 0, GFS_ERR_INVALID_ARG, "gfs_pose_lidar_optimize: invalid argument");
+  GFS_REQUIRE(B <= h->max_batch, GFS_ERR_CAPACITY, "gfs_pose_lidar_optimize: batch %d exceeds capacity %d", B, h->max_batch);
+  std::lock_guard<std::mutex> lk(h->mu);
+  GFS_HIP(hipSetDevice(h->device));
+  int S = 64, SC = 64, rounds = 0;
+  for (int f = 0; f < B; f++) {
+    const gfs_pose_lidar_problem& p = problems[f];
+    GFS_REQUIRE(!p.two_camera, GFS_ERR_UNSUPPORTED, "gfs_pose_lidar_optimize: frame %d: the two-camera branch is not implemented", f);
+    GFS_REQUIRE(p.n_obs >= 0 && p.n_obs <= h->max_obs, GFS_ERR_CAPACITY, "gfs_pose_lidar_optimize: frame %d has %d observations (capacity %d)",
+                f, p.n_obs, h->max_obs);
+    GFS_REQUIRE(p.n_cloud >= 0 && p.n_cloud <= h->max_cloud, GFS_ERR_CAPACITY,
+                "gfs_pose_lidar_optimize: frame %d has %d cloud points (capacity %d)", f, p.n_cloud, h->max_cloud);
+    GFS_REQUIRE(p.n_iterations >= 0 && p.n_iterations <= 4, GFS_ERR_INVALID_ARG,
+                "gfs_pose_lidar_optimize: frame %d: n_iterations %d (its[] has 4 entries)", f, p.n_iterations);
+    GFS_REQUIRE(p.map && p.map->n >= 5, GFS_ERR_INVALID_ARG, "gfs_pose_lidar_optimize: frame %d: no map, or a map of fewer than 5 points", f);
+    GFS_REQUIRE(p.map->device == h->device, GFS_ERR_INVALID_ARG, "gfs_pose_lidar_optimize: frame %d: map on another device", f);
+    GFS_REQUIRE(p.n_obs == 0 || (p.xw && p.obs && p.inv_sigma2 && p.stereo && solutions[f].outlier && solutions[f].chi2),
+                GFS_ERR_INVALID_ARG, "gfs_pose_lidar_optimize: frame %d has NULL observation arrays", f);
+    GFS_REQUIRE(p.n_cloud == 0 || p.cloud, GFS_ERR_INVALID_ARG, "gfs_pose_lidar_optimize: frame %d has a NULL cloud", f);
+    S = std::max(S, (int)gfs::align_up((size_t)p.n_obs, 64));
+    SC = std::max(SC, (int)gfs::align_up((size_t)p.n_cloud, 64));
+    rounds = std::max(rounds, (int)p.n_iterations);
+  }
+  const gfs_pose_lidar::Layout L = gfs_pose_lidar::layout((size_t)B, (size_t)S, (size_t)SC);
+  LFrame* hf = reinterpret_cast<LFrame*>(h->h_in.p);
+  double* h_xw = reinterpret_cast<double*>(h->h_in.p + L.o_xw);
+  double* h_obs = reinterpret_cast<double*>(h->h_in.p + L.o_obs);
+  float* h_w = reinterpret_cast<float*>(h->h_in.p + L.o_w);
+  uint8_t* h_st = h->h_in.p + L.o_st;
+  float* h_cloud = reinterpret_cast<float*>(h->h_in.p + L.o_cloud);
+  for (int f = 0; f < B; f++) {
+    const gfs_pose_lidar_problem& p = problems[f];
+    LFrame& F = hf[f];
+    for (int k = 0; k < 4; k++) F.q[k] = p.q[k];
+    for (int k = 0; k < 3; k++) F.t[k] = p.t[k];
+    F.residual_in = solutions[f].residual;
+    F.n_lidar_inliers_in = solutions[f].n_lidar_inliers;
+    F.fx = p.fx;
+    F.fy = p.fy;
+    F.cx = p.cx;
+    F.cy = p.cy;
+    F.bf = p.bf;
+    F.n_obs = p.n_obs;
+    F.n_cloud = p.n_cloud;
+    F.n_iter = p.n_iterations;
+    F.map_pts = p.map->d_pts.p;
+    F.map_start = p.map->d_start.p;
+    F.map_nb = p.map->nb;
+    F.map_n = p.map->n;
+    if (p.n_obs > 0) {
+      memcpy(h_xw + (size_t)f * S * 3, p.xw, (size_t)p.n_obs * 24);
+      memcpy(h_obs + (size_t)f * S * 3, p.obs, (size_t)p.n_obs * 24);
+      memcpy(h_w + (size_t)f * S, p.inv_sigma2, (size_t)p.n_obs * 4);
+      memcpy(h_st + (size_t)f * S, p.stereo, (size_t)p.n_obs);
+    }
+    if (p.n_cloud > 0) memcpy(h_cloud + (size_t)f * SC * 3, p.cloud, (size_t)p.n_cloud * 12);
+  }
+  hipStream_t s = h->stream;
+  GFS_HIP(hipMemcpyAsync(h->d_in.p, h->h_in.p, L.in_bytes, hipMemcpyHostToDevice, s));
+  const LFrame* d_frames = reinterpret_cast<const LFrame*>(h->d_in.p);
+  VisView V{reinterpret_cast<const double*>(h->d_in.p + L.o_xw), reinterpret_cast<const double*>(h->d_in.p + L.o_obs),
+            reinterpret_cast<const float*>(h->d_in.p + L.o_w), h->d_in.p + L.o_st, h->d_err.p, h->d_chi2.p, h->d_level.p, h->d_outl.p};
+  const float* d_cloud = reinterpret_cast<const float*>(h->d_in.p + L.o_cloud);
+  GFS_LAUNCH("k_pl_init", k_pl_init, dim3(B), dim3(64), 0, s, d_frames, h->d_state.p, V, S);
+  for (int it = 0; it < rounds; it++) {
+    GFS_LAUNCH("k_pl_assoc", k_pl_assoc, dim3(SC / kThreads + (SC % kThreads ? 1 : 0), B), dim3(kThreads), 0, s, d_frames, h->d_state.p,
+               d_cloud, SC, it, h->d_flag.p, h->d_plane.p, h->d_s.p);
+    if (h->sum_order == GFS_POSE_SUMS_EDGE_ORDER)
+      GFS_LAUNCH("k_pl_round", k_pl_round<false>, dim3(B), dim3(kThreads), 0, s, d_frames, h->d_state.p, V, S, d_cloud, h->d_flag.p,
+                 h->d_plane.p, h->d_s.p, SC, h->d_eidx.p, h->d_eplane.p, h->d_es.p, h->d_lerr.p, h->d_lchi2.p, it);
+    else
+      GFS_LAUNCH("k_pl_round", k_pl_round<true>, dim3(B), dim3(kThreads), 0, s, d_frames, h->d_state.p, V, S, d_cloud, h->d_flag.p,
+                 h->d_plane.p, h->d_s.p, SC, h->d_eidx.p, h->d_eplane.p, h->d_es.p, h->d_lerr.p, h->d_lchi2.p, it);
+  }
+  GFS_HIP(hipMemcpyAsync(h->h_state.p, h->d_state.p, (size_t)B * sizeof(LState), hipMemcpyDeviceToHost, s));
+  GFS_HIP(hipMemcpyAsync(h->h_outl.p, h->d_outl.p, (size_t)B * S, hipMemcpyDeviceToHost, s));
+  GFS_HIP(hipMemcpyAsync(h->h_chi2.p, h->d_chi2.p, (size_t)B * S * 8, hipMemcpyDeviceToHost, s));
+  GFS_HIP(hipStreamSynchronize(s));
+  h->last_B = B;
+  h->last_SC = SC;
+  h->last_edges.assign((size_t)B * 4, 0);
+  for (int f = 0; f < B; f++) {
+    const LState& O = h->h_state.p[f];
+    gfs_pose_lidar_solution& r = solutions[f];
+    const int n = problems[f].n_obs;
+    if (n > 0) {
+      memcpy(r.outlier, h->h_outl.p + (size_t)f * S, n);
+      memcpy(r.chi2, h->h_chi2.p + (size_t)f * S, (size_t)n * 8);
+    }
+    for (int k = 0; k < 4; k++) r.q[k] = O.q[k];
+    for (int k = 0; k < 3; k++) r.t[k] = O.t[k];
+    for (int k = 0; k < 4; k++) r.qf[k] = O.qf[k];
+    for (int k = 0; k < 3; k++) r.tf[k] = O.tf[k];
+    r.avg_reproj_error = O.avg;
+    r.n_inliers = O.n_inliers;
+    r.n_lidar_inliers = O.n_lidar_inliers;
+    r.residual = O.residual;
+    r.lidar_rounds = O.lidar_rounds;
+    r.rounds_run = O.rounds_run;
+    r.iterations_run = O.iterations_run;
+    for (int k = 0; k < 4; k++) {
+      r.round_edges[k] = O.round_edges[k];
+      r.round_chi2[k] = O.round_chi2[k];
+      r.round_valid[k] = O.round_valid[k];
+      h->last_edges[(size_t)f * 4 + k] = O.round_edges[k];
+    }
+  }
+  return GFS_OK;
+}
+
+int gfs_pose_lidar_fetch_edges(gfs_pose_lidar* h, int b, int round, int32_t* index, float* plane, float* s, int cap, int32_t* n) {
+  GFS_REQUIRE(h && n && cap >= 0 && (cap == 0 || (index && plane && s)), GFS_ERR_INVALID_ARG, "gfs_pose_lidar_fetch_edges: invalid argument");
+  std::lock_guard<std::mutex> lk(h->mu);
+  GFS_REQUIRE(b >= 0 && b < h->last_B && round >= 0 && round < 4, GFS_ERR_INVALID_ARG,
+              "gfs_pose_lidar_fetch_edges: frame %d / round %d outside the last call", b, round);
+  GFS_HIP(hipSetDevice(h->device));
+  const int cnt = h->last_edges[(size_t)b * 4 + round];
+  *n = cnt;
+  const int m = std::min(cnt, cap);
+  if (m == 0) return GFS_OK;
+  const size_t o = ((size_t)b * 4 + round) * h->last_SC;
+  GFS_HIP(hipMemcpy(index, h->d_eidx.p + o, (size_t)m * 4, hipMemcpyDeviceToHost));
+  GFS_HIP(hipMemcpy(plane, h->d_eplane.p + o, (size_t)m * 16, hipMemcpyDeviceToHost));
+  GFS_HIP(hipMemcpy(s, h->d_es.p + o, (size_t)m * 4, hipMemcpyDeviceToHost));
+  return GFS_OK;
+}
+
+}  // extern "C"

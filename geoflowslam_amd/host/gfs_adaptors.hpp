@@ -703,6 +703,99 @@ class PoseOptimizer {
   gfs_pose* h_ = nullptr;
 };
 
+// Optimizer::PoseLidarVisualOptimization (src/Optimizer.cc:7698-8059), conventional-SLAM branch.  The frame is read through an
+// access type (no PCL / Sophus / OpenCV here), with static members:
+//   int N(const F&); bool has_map_point(const F&, int i); void world_pos(const F&, int i, float xyz[3]);
+//   void key_point(const F&, int i, float* x, float* y, int* octave); float u_right(const F&, int i); float inv_level_sigma2(const F&, int o);
+//   void intrinsics(const F&, float* fx, float* fy, float* cx, float* cy, float* bf); bool two_camera(const F&);
+//   void get_pose(const F&, float q[4], float t[3]); void set_pose(F&, const float q[4], const float t[3]); void set_outlier(F&, int i, bool);
+// The local map (laserCloudSurfFromMapDS) is uploaded with SetLocalMap whenever the caller refreshes it; the frame's downsampled cloud
+// (mpPointCloudDownsampled) is passed as xyz floats.  Writes back mvbOutlier, the pose (SetPose) and the two out-parameters.
+class PoseLidarOptimizer {
+ public:
+  PoseLidarOptimizer(int max_obs = 8192, int max_cloud = 16384, int max_map = 262144, int device = 0) {
+    check(gfs_pose_lidar_create(device, max_obs, max_cloud, 1, &h_), "gfs_pose_lidar_create");
+    const int rc = gfs_lidar_map_create(device, max_map, &map_);
+    if (rc) {
+      gfs_pose_lidar_destroy(h_);
+      check(rc, "gfs_lidar_map_create");
+    }
+  }
+  ~PoseLidarOptimizer() {
+    gfs_pose_lidar_destroy(h_);
+    gfs_lidar_map_destroy(map_);
+  }
+  PoseLidarOptimizer(const PoseLidarOptimizer&) = delete;
+  PoseLidarOptimizer& operator=(const PoseLidarOptimizer&) = delete;
+  void SetLocalMap(const float* xyz, int n) { check(gfs_lidar_map_set(map_, xyz, n), "gfs_lidar_map_set"); }
+
+  template <class Access, class F>
+  int PoseLidarVisualOptimization(F* frame, const float* cloud_xyz, int n_cloud, int nIterations, int& nLidarInliers, float& residual) {
+    gfs_pose_lidar_problem p{};
+    Access::get_pose(*frame, p.q, p.t);
+    float fx, fy, cx, cy, bf;
+    Access::intrinsics(*frame, &fx, &fy, &cx, &cy, &bf);
+    p.fx = fx;
+    p.fy = fy;
+    p.cx = cx;
+    p.cy = cy;
+    p.bf = bf;
+    p.two_camera = Access::two_camera(*frame) ? 1 : 0;
+    idx_.clear();
+    xw_.clear();
+    obs_.clear();
+    w_.clear();
+    st_.clear();
+    const int N = Access::N(*frame);
+    for (int i = 0; i < N; i++) {  // key-point index order = the reference's edge creation order
+      if (!Access::has_map_point(*frame, i)) continue;
+      float X[3], x, y, ur = Access::u_right(*frame, i);
+      int octave;
+      Access::world_pos(*frame, i, X);
+      Access::key_point(*frame, i, &x, &y, &octave);
+      idx_.push_back(i);
+      for (int k = 0; k < 3; k++) xw_.push_back((double)X[k]);
+      obs_.push_back((double)x);
+      obs_.push_back((double)y);
+      obs_.push_back((double)ur);
+      w_.push_back(Access::inv_level_sigma2(*frame, octave));
+      st_.push_back(ur < 0 ? 0 : 1);
+    }
+    const int n = (int)idx_.size();
+    outlier_.assign(std::max(n, 1), 0);
+    chi2_.assign(std::max(n, 1), 0.0);
+    p.n_obs = n;
+    p.xw = xw_.data();
+    p.obs = obs_.data();
+    p.inv_sigma2 = w_.data();
+    p.stereo = st_.data();
+    p.n_cloud = n_cloud;
+    p.cloud = cloud_xyz;
+    p.map = map_;
+    p.n_iterations = nIterations;
+    gfs_pose_lidar_solution s{};
+    s.outlier = outlier_.data();
+    s.chi2 = chi2_.data();
+    s.n_lidar_inliers = nLidarInliers;
+    s.residual = residual;
+    check(gfs_pose_lidar_optimize(h_, &p, 1, &s), "gfs_pose_lidar_optimize");
+    for (int k = 0; k < n; k++) Access::set_outlier(*frame, idx_[k], outlier_[k] != 0);  // all false when n < 3 (:7754, :7782)
+    if (n < 3) return 0;  // nInitialCorrespondences < 3: return 0 before SetPose
+    Access::set_pose(*frame, s.qf, s.tf);
+    nLidarInliers = s.n_lidar_inliers;
+    residual = s.residual;
+    return s.n_inliers;
+  }
+
+ private:
+  gfs_pose_lidar* h_ = nullptr;
+  gfs_lidar_map* map_ = nullptr;
+  std::vector<int> idx_;
+  std::vector<double> xw_, obs_, chi2_;
+  std::vector<float> w_;
+  std::vector<uint8_t> st_, outlier_;
+};
+
 }  // namespace gfs_host
 
 // The drop-ins written against the reference's own types (cv::Mat, cv::KeyPoint, Eigen, Sophus, ORB_SLAM3::ORBextractor as a base

@@ -450,3 +450,66 @@ def cloud_pair(seed, width=160, height=120, trans=0.03, rot_deg=1.5):
     d0 = sc.render(width, height, None, 0)[1]
     d1 = sc.render(width, height, T1, 1)[1]
     return depth_to_cloud(d0, 1), depth_to_cloud(d1, 1), T1
+
+
+def voxel_average(xyz, res):
+    """Mean of the points of every res-metre voxel (a stand-in for the PCL voxel filter that builds the local map), float32."""
+    xyz = np.asarray(xyz, np.float64)
+    keys = np.floor(xyz / res).astype(np.int64)
+    _, inv = np.unique(keys, axis=0, return_inverse=True)
+    inv = inv.reshape(-1)
+    cnt = np.bincount(inv)
+    out = np.stack([np.bincount(inv, xyz[:, k]) / cnt for k in range(3)], 1)
+    return out.astype(np.float32)
+
+
+def pose_lidar_frame(seed, n_obs=600, n_cloud=3000, n_keyframes=3, voxel=0.1, width=320, height=240, rot_deg=1.0, trans=0.03,
+                     mono_frac=0.15, outlier_frac=0.1, outlier_px=25.0, n_iterations=3):
+    """Synthetic Optimizer::PoseLidarVisualOptimization problem (reference src/Optimizer.cc:7698-8059) on a Scene: the local map is
+    2-3 key-frame renders in world coordinates, voxel-averaged at `voxel` metres; the frame cloud is the current view in camera
+    coordinates (about n_cloud points); the visual observations are those of pose_frame, consistent with the true pose; the initial
+    pose (a Sophus::SE3f: float q, t) is the true one perturbed by ~rot_deg / ~trans metres.  Returns the fields of
+    gfs_pose_lidar_problem (include/gfs_abi.h) plus map_xyz and the ground truth (q_gt, t_gt of Tcw)."""
+    rng = np.random.default_rng(seed)
+    sc = Scene(seed)
+    T_wc = random_motion(rng, trans=0.05, rot_deg=2.0)
+    pts = []
+    for k in range(n_keyframes):
+        T_kf = T_wc @ random_motion(rng, trans=0.15, rot_deg=4.0)
+        _, d = sc.render(width, height, T_kf, 100 + k)
+        c = depth_to_cloud(d, 2)[:, :3].astype(np.float64)
+        pts.append(c @ T_kf[:3, :3].T + T_kf[:3, 3])
+    map_xyz = voxel_average(np.concatenate(pts), voxel)
+    _, d = sc.render(width, height, T_wc, 7)
+    cloud = depth_to_cloud(d, 1)[:, :3]
+    if len(cloud) > n_cloud:
+        cloud = cloud[np.sort(rng.choice(len(cloud), n_cloud, replace=False))]
+    Rcw, tcw = T_wc[:3, :3].T, -T_wc[:3, :3].T @ T_wc[:3, 3]
+    fx = fy = np.float64(np.float32(607.0))
+    cx, cy = np.float64(np.float32(319.5)), np.float64(np.float32(239.5))
+    bf = np.float64(np.float32(0.0745 * 607.0))
+    sigma2 = np.float64(np.float32(1.2) ** (2 * np.arange(8)))
+    inv_sigma2 = (np.float32(1.0) / np.float32(1.2) ** (2 * np.arange(8))).astype(np.float32)
+    xw, obs, w, st = [], [], [], []
+    while len(xw) < n_obs:
+        xc = np.array([rng.uniform(-3, 3), rng.uniform(-2, 2), rng.uniform(1.0, 6.0)])
+        u, v = fx * xc[0] / xc[2] + cx, fy * xc[1] / xc[2] + cy
+        if not (0 <= u < 640 and 0 <= v < 480):
+            continue
+        octv = int(rng.choice(8, p=np.array([217, 181, 151, 126, 105, 87, 73, 60]) / 1000.0))
+        noise = rng.normal(0, np.sqrt(sigma2[octv]), 3)
+        if rng.random() < outlier_frac:
+            noise[:2] += rng.choice([-1, 1], 2) * outlier_px
+        stereo = rng.random() >= mono_frac
+        ur = u - bf / xc[2]
+        xw.append((Rcw.T @ (xc - tcw)).astype(np.float32).astype(np.float64))
+        obs.append([np.float32(u + noise[0]), np.float32(v + noise[1]), np.float32(ur + noise[2]) if stereo else -1.0])
+        w.append(inv_sigma2[octv])
+        st.append(1 if stereo else 0)
+    dR = _rot(*(np.deg2rad(rot_deg) * rng.normal(size=3)))
+    q0 = _quat_from_R(dR @ Rcw).astype(np.float32)
+    t0 = (dR @ tcw + trans * rng.normal(size=3)).astype(np.float32)
+    return dict(q=q0, t=t0, xw=np.array(xw).reshape(-1, 3), obs=np.array(obs, np.float64).reshape(-1, 3),
+                inv_sigma2=np.array(w, np.float32), stereo=np.array(st, np.uint8), fx=fx, fy=fy, cx=cx, cy=cy, bf=bf,
+                cloud=np.ascontiguousarray(cloud, np.float32), map_xyz=map_xyz, n_iterations=n_iterations,
+                q_gt=_quat_from_R(Rcw), t_gt=tcw)

@@ -549,6 +549,70 @@ int gfs_find_fundamental_ransac_device(gfs_fmat* h, int B, int stride, const voi
                                        int32_t* n_inliers);
 
 /* ============================================================================================
+ * 11. Optimizer::PoseLidarVisualOptimization — motion-only BA of a frame with point-to-plane lidar edges
+ *      int Optimizer::PoseLidarVisualOptimization(Frame*, PointCloud::Ptr laserCloudSurfFromMapDS, bool, bool,
+ *                                                 int nIterations, int& nLidarInliers, float& residual)
+ *                                                                             src/Optimizer.cc:7698-8059
+ *    Replaces PoseOptimization when UsePointCloudObs: 1.  Visual edges as in section 6; per round, GenerateLidarEdge
+ *    (:8339-8421: 5-NN of the frame's downsampled cloud in the local map, ColPivHouseholderQR plane fit, gates) adds
+ *    EdgeSE3LidarPoint2Plane edges (include/G2oTypes.h:574-600, numeric Jacobian), optimize(its[it]) with its = {10, 5, 5, 5},
+ *    the lidar edges are removed and the visual edges re-classified.  Conventional-SLAM branch only (two_camera != 0 is refused
+ *    with GFS_ERR_UNSUPPORTED).  DESIGN.md "Pose with lidar edges" pins the two rules the reference leaves to Eigen / FLANN.
+ * ============================================================================================ */
+/* The local map (laserCloudSurfFromMapDS), uploaded once and reused by every frame until the next upload (the reference refreshes it
+ * at key-frame rate).  gfs_lidar_map_set builds the search grid; n < 5 is refused (the reference reads sqdis[4]). */
+typedef struct gfs_lidar_map gfs_lidar_map;
+int gfs_lidar_map_create(int device, int max_points, gfs_lidar_map** out);
+int gfs_lidar_map_set(gfs_lidar_map* map, const float* xyz /* [n][3] */, int n);
+void gfs_lidar_map_destroy(gfs_lidar_map* map);
+
+typedef struct {
+  float q[4], t[3];           /* Tcw = pFrame->GetPose(): Sophus::SE3f unit quaternion (x, y, z, w) and translation, as stored */
+  int32_t n_obs;              /* the visual observations, exactly as gfs_pose_problem */
+  const double* xw;           /* [n_obs][3] */
+  const double* obs;          /* [n_obs][3] */
+  const float* inv_sigma2;    /* [n_obs] */
+  const uint8_t* stereo;      /* [n_obs] */
+  double fx, fy, cx, cy, bf;
+  int32_t n_cloud;            /* pFrame->mpPointCloudDownsampled->size() (0 = no cloud) */
+  const float* cloud;         /* [n_cloud][3] camera frame */
+  const gfs_lidar_map* map;   /* laserCloudSurfFromMapDS, on the handle's device */
+  int32_t n_iterations;       /* nIterations, 1 .. 4 */
+  int32_t two_camera;         /* pFrame->mpCamera2 != nullptr: refused */
+} gfs_pose_lidar_problem;
+
+typedef struct {
+  uint8_t* outlier;           /* [n_obs] pFrame->mvbOutlier */
+  double* chi2;               /* [n_obs] e->chi2() as read by the last classification */
+  double q[4], t[3];          /* the g2o estimate after the last round */
+  float qf[4], tf[3];         /* the pose given to pFrame->SetPose (the estimate through Sophus::SE3f; the input when < 3 obs) */
+  float avg_reproj_error;     /* avgReprojectionError of the last classification (inf / NaN as the reference computes them) */
+  int32_t n_inliers;          /* return value: nInitialCorrespondences - nBad */
+  int32_t n_lidar_inliers;    /* in/out (int&): valid_edge of the last round that had lidar edges, else unchanged */
+  float residual;             /* in/out (float&): chi2Lidar of the last round that had lidar edges, else unchanged */
+  int32_t lidar_rounds;       /* rounds that had lidar edges (optimized and re-classified) */
+  int32_t rounds_run;         /* rounds entered (a round without lidar edges `continue`s) */
+  int32_t iterations_run;     /* LM iterations over all rounds */
+  int32_t round_edges[4];     /* lidar edges of each round */
+  float round_chi2[4];        /* chi2Lidar of each round (0 for a round without edges) */
+  int32_t round_valid[4];     /* valid_edge of each round */
+} gfs_pose_lidar_solution;
+
+typedef struct gfs_pose_lidar gfs_pose_lidar;
+int gfs_pose_lidar_create(int device, int max_obs, int max_cloud, int max_batch, gfs_pose_lidar** out);
+void gfs_pose_lidar_destroy(gfs_pose_lidar* h);
+/* GFS_POSE_SUMS_EDGE_ORDER (default): every sum in g2o's edge order, bit for bit the sequential restatement; GFS_POSE_SUMS_TREE:
+ * a fixed-shape tree, pose within 1e-6 relative (an LM accept / stop decision can flip where the sums round differently; 3.4e-7
+ * measured), flags equal up to chi2-threshold ties. */
+int gfs_pose_lidar_set_sum_order(gfs_pose_lidar* h, int order);
+/* B frames (host pointers; frames may share a map or use several maps on the handle's device). */
+int gfs_pose_lidar_optimize(gfs_pose_lidar* h, const gfs_pose_lidar_problem* problems, int B, gfs_pose_lidar_solution* solutions);
+/* Diagnostic: the lidar edges frame b of the last gfs_pose_lidar_optimize call generated in round `round` (cloud index order):
+ * point index, plane (pa, pb, pc, pd) and s.  Up to cap edges; *n = the round's edge count. */
+int gfs_pose_lidar_fetch_edges(gfs_pose_lidar* h, int b, int round, int32_t* index, float* plane /* [cap][4] */, float* s, int cap,
+                               int32_t* n);
+
+/* ============================================================================================
  * Timing helper for the harness: HIP events on a given stream (bench.py measures the dominant kernel
  * with these rather than torch events, which only see torch's current stream).
  * ============================================================================================ */
