@@ -63,6 +63,26 @@ class LbaSolution(C.Structure):
                 ("final_lambda", C.c_double)]
 
 
+class LbaLidar(C.Structure):
+    _fields_ = [("map", C.c_void_p), ("pose_local", C.c_void_p), ("matches_inliers", C.c_void_p), ("cloud_begin", C.c_void_p),
+                ("cloud", C.c_void_p), ("two_camera", C.c_int32)]
+
+
+def lba_lidar_struct(prob, map_handle=None):
+    """ctypes view of the lidar half of a LocalVisualLidarBA problem dict (pose_local, matches_inliers, cloud_begin, cloud,
+    optional two_camera); shared with the CPU restatement's tests."""
+    L = LbaLidar()
+    keep = dict(pose_local=np.ascontiguousarray(prob["pose_local"], np.uint8),
+                matches_inliers=np.ascontiguousarray(prob["matches_inliers"], np.int32),
+                cloud_begin=np.ascontiguousarray(prob["cloud_begin"], np.int32),
+                cloud=np.ascontiguousarray(prob["cloud"], np.float32).reshape(-1, 3))
+    for k, v in keep.items():
+        setattr(L, k, v.ctypes.data)
+    L.map = map_handle
+    L.two_camera = int(prob.get("two_camera", 0))
+    return L, keep
+
+
 class PoseProblem(C.Structure):
     _fields_ = [("q", C.c_double * 4), ("t", C.c_double * 3), ("n_obs", C.c_int32), ("xw", C.c_void_p), ("obs", C.c_void_p),
                 ("inv_sigma2", C.c_void_p), ("stereo", C.c_void_p), ("fx", C.c_double), ("fy", C.c_double),
@@ -238,7 +258,8 @@ ABI_SYMBOLS = [
     "gfs_gicp_default_config", "gfs_gicp_create", "gfs_gicp_destroy", "gfs_gicp_align", "gfs_gicp_align_batch_device",
     "gfs_gicp_fetch_preprocessed", "gfs_gicp_tile_stats", "gfs_gicp_knn_stats", "gfs_gicp_coop_stats", "gfs_frame_rgbd", "gfs_gicp_align_next", "gfs_gicp_align_next_batch_device", "gfs_test_voxel_sort", "gfs_test_wave_std_sort",
     "gfs_lba_create", "gfs_lba_destroy", "gfs_lba_solve", "gfs_lba_solve_bool", "gfs_lba_linearize", "gfs_lba_batch_create", "gfs_lba_batch_destroy",
-    "gfs_lba_solve_batch",
+    "gfs_lba_solve_batch", "gfs_lba_lidar_reserve", "gfs_lba_solve_lidar", "gfs_lba_solve_lidar_bool", "gfs_lba_linearize_lidar",
+    "gfs_lba_fetch_lidar_edges",
     "gfs_frame_create", "gfs_frame_destroy", "gfs_depth_to_cloud", "gfs_depth_to_cloud_batch_device", "gfs_depth_convert_u16_batch_device", "gfs_stereo_from_rgbd",
     "gfs_stereo_from_rgbd_batch_device",
     "gfs_pose_create", "gfs_pose_destroy", "gfs_pose_optimize", "gfs_pose_set_sum_order",
@@ -311,6 +332,13 @@ def lib():
             L.gfs_lba_batch_create.argtypes = [i, i, i, i, i, C.POINTER(vp)]
             L.gfs_lba_batch_destroy.argtypes = [vp]
             L.gfs_lba_solve_batch.argtypes = [vp, vp, vp, i, vp]
+        if hasattr(L, "gfs_lba_solve_lidar"):
+            L.gfs_lba_lidar_reserve.argtypes = [vp, i]
+            L.gfs_lba_solve_lidar.argtypes = [vp, C.POINTER(LbaProblem), C.POINTER(LbaLidar), C.POINTER(LbaSolution), vp, vp]
+            L.gfs_lba_solve_lidar_bool.argtypes = [vp, C.POINTER(LbaProblem), C.POINTER(LbaLidar), C.POINTER(LbaSolution), vp, vp]
+            L.gfs_lba_linearize_lidar.argtypes = [vp, C.POINTER(LbaProblem), C.POINTER(LbaLidar), vp, vp, vp, vp, vp, vp,
+                                                  C.POINTER(C.c_double), vp, i, vp]
+            L.gfs_lba_fetch_lidar_edges.argtypes = [vp, i, vp, vp, vp, i, vp]
         if hasattr(L, "gfs_frame_create"):
             f = C.c_float
             L.gfs_frame_create.argtypes = [i, i, i, i, C.POINTER(vp)]
@@ -742,6 +770,66 @@ class Optimizer:
         _check(rc, "gfs_lba_solve")
         out.update(iterations_run=S.iterations_run, final_chi2=S.final_chi2, final_lambda=S.final_lambda)
         return out
+
+    def _lidar(self, prob, lidar_map):
+        L, keep = lba_lidar_struct(prob, lidar_map.h)
+        cb = keep["cloud_begin"]
+        need = int(cb[-1] - cb[0]) if len(cb) else 0
+        if need > getattr(self, "lidar_cap", 0):  # (the library refuses a window beyond the reserve: it never truncates)
+            _check(lib().gfs_lba_lidar_reserve(self.h, need), "gfs_lba_lidar_reserve")
+            self.lidar_cap = need
+        return L, keep
+
+    def LocalVisualLidarBA(self, prob, lidar_map, stop_flag=None):
+        """ORB_SLAM3::Optimizer::LocalVisualLidarBA (reference src/Optimizer.cc:1101-1587): LocalBundleAdjustment's window plus the
+        point-to-plane edges of the local key-frames against lidar_map (a LidarMap).  prob: the LocalBundleAdjustment dict plus
+        pose_local [n_poses], matches_inliers [n_poses], cloud_begin [n_poses + 1], cloud [n][3].  -> LocalBundleAdjustment's dict
+        plus pose_lidar_edges [n_poses], or None when the stop flag was raised before the call."""
+        P, keep = _lba_problem(prob)
+        L, lkeep = self._lidar(prob, lidar_map)
+        out = dict(pose_q=np.zeros((P.n_poses, 4)), pose_t=np.zeros((P.n_poses, 3)), points=np.zeros((P.n_points, 3)),
+                   edge_chi2=np.zeros(P.n_edges), edge_depth_positive=np.zeros(P.n_edges, np.uint8))
+        S = LbaSolution()
+        for k, v in out.items():
+            setattr(S, k, v.ctypes.data)
+        ple = np.zeros(max(P.n_poses, 1), np.int32)
+        stop = stop_flag.ctypes.data_as(C.c_void_p) if stop_flag is not None else None
+        rc = lib().gfs_lba_solve_lidar(self.h, C.byref(P), C.byref(L), C.byref(S), _p(ple), stop)
+        if rc == -6:  # GFS_ERR_STOPPED (src/Optimizer.cc:1502-1503)
+            return None
+        _check(rc, "gfs_lba_solve_lidar")
+        out.update(iterations_run=S.iterations_run, final_chi2=S.final_chi2, final_lambda=S.final_lambda,
+                   pose_lidar_edges=ple[:P.n_poses].copy())
+        return out
+
+    def linearize_lidar(self, prob, lidar_map):
+        """linearize() with the lidar edges of LocalVisualLidarBA: their terms in Hpp / bp / chi2, plus lidar_edge_chi2 (every lidar
+        edge in g2o's order: key-frames in pose order, then cloud order) and pose_lidar_edges."""
+        P, keep = _lba_problem(prob)
+        L, lkeep = self._lidar(prob, lidar_map)
+        nf = int((np.asarray(prob["pose_fixed"]) == 0).sum())
+        Hpp = np.zeros((nf, 36)); Hll = np.zeros((P.n_points, 9)); Hpl = np.zeros((P.n_edges, 18))
+        bp = np.zeros((nf, 6)); bl = np.zeros((P.n_points, 3)); chi = np.zeros(P.n_edges)
+        cap = max(int(lkeep["cloud_begin"][-1]) if len(lkeep["cloud_begin"]) else 0, 1)
+        lchi, ple = np.zeros(cap), np.zeros(max(P.n_poses, 1), np.int32)
+        tot = C.c_double()
+        _check(lib().gfs_lba_linearize_lidar(self.h, C.byref(P), C.byref(L), _p(Hpp), _p(Hll), _p(Hpl), _p(bp), _p(bl), _p(chi),
+                                             C.byref(tot), _p(lchi), cap, _p(ple)), "gfs_lba_linearize_lidar")
+        ple = ple[:P.n_poses].copy()
+        return dict(Hpp=Hpp.reshape(nf, 6, 6).transpose(0, 2, 1).copy(), Hll=Hll.reshape(-1, 3, 3).transpose(0, 2, 1).copy(),
+                    Hpl=Hpl.reshape(-1, 3, 6).transpose(0, 2, 1).copy(), bp=bp, bl=bl, edge_chi2=chi, chi2=tot.value,
+                    lidar_edge_chi2=lchi[:int(ple.sum())].copy(), pose_lidar_edges=ple)
+
+    def fetch_lidar_edges(self, pose):
+        """The lidar edges of `pose` in the last lidar call: (index [n] in the pose's cloud, plane [n][4], s [n]), all of them."""
+        n = C.c_int32()
+        _check(lib().gfs_lba_fetch_lidar_edges(self.h, pose, None, None, None, 0, C.byref(n)), "gfs_lba_fetch_lidar_edges")
+        m = n.value
+        idx, pl, s = np.zeros(max(m, 1), np.int32), np.zeros((max(m, 1), 4), np.float32), np.zeros(max(m, 1), np.float32)
+        _check(lib().gfs_lba_fetch_lidar_edges(self.h, pose, _p(idx), _p(pl), _p(s), m, C.byref(n)), "gfs_lba_fetch_lidar_edges")
+        if n.value != m:
+            raise GfsError(f"gfs_lba_fetch_lidar_edges: {n.value} edges, expected {m}")
+        return idx[:m].copy(), pl[:m].copy(), s[:m].copy()
 
     def linearize(self, prob):
         P, keep = _lba_problem(prob)

@@ -25,6 +25,7 @@
 
 #include "g2o_se3_dev.hpp"
 #include "gfs_common.hpp"
+#include "lidar_assoc.hpp"
 #include "wave_reduce.hpp"
 
 namespace {
@@ -111,6 +112,19 @@ struct LbaDev {
   GFS_GLOBAL double* schur_part_b;
   int n_schur_chunks, n_pair_tiles, schur_sub;  // chunks of kSchurPts landmarks; tiles of kMk pose pairs; landmarks staged at a time
   int schur_mfma;  // 1: b_schur_mfma (n_schur_chunks chunks of kSchurMPts landmarks, n_pair_tiles = 128 x 128 blocks of the lower triangle)
+  // LocalVisualLidarBA (gfs_lba_solve_lidar): the point-to-plane edges of the window's lidar key-frames, compacted per key-frame in
+  // cloud order at the key-frame's offset in the concatenated cloud.  n_lidar_kf = 0 (every other entry): no lidar edges.
+  int n_lidar_kf;    // lidar key-frames: the first n_lidar_kf workgroups of k_lba_errors, ahead of the reprojection edges' (g2o's order)
+  int n_lidar_free;  // ... of which free: the workgroups of k_lba_lidar_build
+  const GFS_GLOBAL gfs_lidar::WindowKF* lkf;  // [n_lidar_kf]
+  const GFS_GLOBAL int* lkf_free;             // [n_lidar_free] -> lidar key-frame
+  const GFS_GLOBAL float* lcloud;             // [3 x concatenated cloud]
+  const GFS_GLOBAL int* l_cnt;                // [n_lidar_kf] edges of each lidar key-frame
+  const GFS_GLOBAL int* l_idx;                // edge -> cloud index in its key-frame's cloud
+  const GFS_GLOBAL float4* l_plane;           // edge -> (pa, pb, pc, pd)
+  const GFS_GLOBAL float* l_s;                // edge -> s
+  GFS_GLOBAL double* l_chi2;                  // edge -> chi2 of the last k_lba_errors
+  double l_info, l_huber;                     // the edges' information and Huber delta
 };
 
 using namespace gfs_se3;
@@ -600,6 +614,31 @@ __device__ __forceinline__ void b_init(const LbaDev& D, const int bx, const int 
 __global__ __launch_bounds__(kMk) void k_lba_init(LbaDev D) { b_init(D, blockIdx.x, gridDim.x); }
 
 
+// ---- LocalVisualLidarBA's point-to-plane edges (EdgeSE3LidarPoint2Plane, src/Optimizer.cc:1327-1362): information 1e2 (:1348) and
+// Huber delta thHuberLidar = (float) sqrt(1.0) (:1328) come in LbaDev::l_info / l_huber from pose_lidar.hip's definitions
+// (gfs_lidar::edge_information / edge_huber_delta)
+
+// the robust chi2 of lidar key-frame k's edges at the estimate (q, t), its edges over the threads, fixed-shape reduction: part_chi[k]
+__device__ __forceinline__ void b_lidar_errors(const LbaDev& D, const int k, const double* q, const double* t, double* s4) {
+  const gfs_lidar::WindowKF& K = D.lkf[k];
+  const int p = K.pose, n = D.l_cnt[k], base = K.begin;
+  double W[7];
+  gfs_lidar::se3_inverse(q + 4 * p, t + 3 * p, W);
+  double local = 0;
+  for (int l = threadIdx.x; l < n; l += kMk) {
+    const float* po = D.lcloud + 3 * ((size_t)base + D.l_idx[base + l]);
+    const double pt[3] = {(double)po[0], (double)po[1], (double)po[2]};
+    const double ev = gfs_lidar::lidar_err(W, pt, D.l_plane[base + l], D.l_s[base + l]);
+    const double c = ev * (D.l_info * ev);
+    D.l_chi2[base + l] = c;
+    double r0, r1;
+    huber(c, D.l_huber, &r0, &r1);
+    local += r0;
+  }
+  const double tot = block_sum256(local, s4);
+  if (threadIdx.x == 0) D.part_chi[k] = tot;
+}
+
 // computeActiveErrors on the accepted (trial = 0) or the trial estimate (trial = 1; falls back to the accepted one when the
 // linear solve failed, like the reference which restores the estimate before recomputing the errors)
 __device__ __forceinline__ void b_errors(const LbaDev& D, const int bx, const int gdx, int trial) {
@@ -610,8 +649,12 @@ __device__ __forceinline__ void b_errors(const LbaDev& D, const int bx, const in
   if (!trial && S.err_at_cur) return;
   const int which = (trial && S.solve_ok) ? (S.cur ^ 1) : S.cur;
   const double *q = sel(D.q, D.q_try, which), *t = sel(D.t, D.t_try, which), *X = sel(D.X, D.X_try, which);
+  if (bx < D.n_lidar_kf) {  // (uniform per workgroup)
+    b_lidar_errors(D, bx, q, t, s4);
+    return;
+  }
   double local = 0;
-  const int e = bx * kMk + threadIdx.x;
+  const int e = (bx - D.n_lidar_kf) * kMk + threadIdx.x;
   if (e < D.n_edges) {
     double xc[3], r[3];
     edge_residual(D, e, q, t, X, xc, r);
@@ -753,6 +796,94 @@ __device__ __forceinline__ void b_build_poses(const LbaDev& D, const int bx, con
 __global__ __launch_bounds__(kPoseWg) void k_lba_build_poses(LbaDev D, int gate) {
   if (gate && !D.S->spec_ok) return;
   b_build_poses(D, blockIdx.x, gridDim.x);
+}
+
+
+// buildSystem, lidar side: BaseUnaryEdge::linearizeOplus (core/base_unary_edge.hpp:82-123: central differences, delta 1e-9) and
+// constructQuadraticForm of the edges of one free lidar key-frame, one workgroup each.  The twelve perturbed poses (and their inverses,
+// which computeError takes) are the same for every edge: twelve lanes compute them once.  The 6 x 6 block and 6-vector are reduced
+// in a fixed shape and added to the key-frame's Hpp / bp after the reprojection edges' sum (k_lba_build_poses), before the initial
+// lambda and the Schur products.  A key-frame whose association left no edge is not touched.
+__global__ __launch_bounds__(kMk) void k_lba_lidar_build(LbaDev D, int gate) {
+  if (gate && !D.S->spec_ok) return;
+  __shared__ double s_Wp[12][7];
+  __shared__ double s_buf[(kMk / 64) * 32];
+  const int k = D.lkf_free[blockIdx.x];
+  const gfs_lidar::WindowKF& K = D.lkf[k];
+  const int n = D.l_cnt[k], base = K.begin, tid = threadIdx.x;
+  const double info = D.l_info;
+  if (n == 0) return;
+  const LbaState& S = *D.S;
+  const double *q = sel(D.q, D.q_try, S.cur) + 4 * K.pose, *t = sel(D.t, D.t_try, S.cur) + 3 * K.pose;
+  if (tid < 12) {
+    double u[6] = {0, 0, 0, 0, 0, 0}, qp[4], tp[3];
+    u[tid >> 1] = (tid & 1) ? -1e-9 : 1e-9;
+    pose_oplus(q, t, u, qp, tp);
+    gfs_lidar::se3_inverse(qp, tp, s_Wp[tid]);
+  }
+  double W[7];
+  gfs_lidar::se3_inverse(q, t, W);
+  __syncthreads();
+  double acc[27];
+#pragma unroll
+  for (int j = 0; j < 27; j++) acc[j] = 0;
+  for (int l = tid; l < n; l += kMk) {
+    const float* po = D.lcloud + 3 * ((size_t)base + D.l_idx[base + l]);
+    const double pt[3] = {(double)po[0], (double)po[1], (double)po[2]};
+    const float4 pl = D.l_plane[base + l];
+    const float sl = D.l_s[base + l];
+    double J[6];
+#pragma unroll
+    for (int d = 0; d < 6; d++)
+      J[d] = (1.0 / (2 * 1e-9)) * (gfs_lidar::lidar_err(s_Wp[2 * d], pt, pl, sl) - gfs_lidar::lidar_err(s_Wp[2 * d + 1], pt, pl, sl));
+    const double ev = gfs_lidar::lidar_err(W, pt, pl, sl);
+    double r0, rho1;
+    huber(ev * (info * ev), D.l_huber, &r0, &rho1);
+    int o = 0;
+#pragma unroll
+    for (int a = 0; a < 6; a++)
+#pragma unroll
+      for (int c = a; c < 6; c++) acc[o++] += (J[a] * (rho1 * info)) * J[c];
+#pragma unroll
+    for (int a = 0; a < 6; a++) acc[21 + a] += -(((rho1 * J[a]) * info) * ev);
+  }
+  const double v = gfs_red::block_sum_many<27, kMk / 64>(acc, s_buf);
+  const int f = D.free_index[K.pose];
+  if (tid < 21)
+    D.Hpp[21 * f + tid] += v;
+  else if (tid < 27)
+    D.bp[6 * f + (tid - 21)] += v;
+}
+
+// GenerateLidarEdge's vector, nullptr entries skipped: the points of lidar key-frame blockIdx.x that k_lba_lidar_assoc kept, compacted
+// in cloud-index order (ballot per wave, the waves in order) at the key-frame's offset; l_cnt = their number
+__global__ __launch_bounds__(kMk) void k_lba_lidar_compact(const gfs_lidar::WindowKF* __restrict__ kfs, const uint8_t* __restrict__ flag,
+                                                           const float4* __restrict__ plane, const float* __restrict__ s_in,
+                                                           int* __restrict__ cnt, int* __restrict__ idx, float4* __restrict__ eplane,
+                                                           float* __restrict__ es) {
+  __shared__ int s_wcnt[kMk / 64];
+  const gfs_lidar::WindowKF K = kfs[blockIdx.x];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  int nl = 0;
+  for (int b0 = 0; b0 < K.n; b0 += kMk) {
+    const int i = b0 + tid;
+    const bool keep = i < K.n && flag[(size_t)K.begin + i];
+    const unsigned long long m = __ballot(keep);
+    const int below = __popcll(m & ((1ull << lane) - 1ull));
+    if (lane == 0) s_wcnt[wave] = __popcll(m);
+    __syncthreads();
+    int off = nl;
+    for (int w = 0; w < wave; w++) off += s_wcnt[w];
+    if (keep) {
+      const size_t pos = (size_t)K.begin + off + below;
+      idx[pos] = i;
+      eplane[pos] = plane[(size_t)K.begin + i];
+      es[pos] = s_in[(size_t)K.begin + i];
+    }
+    for (int w = 0; w < kMk / 64; w++) nl += s_wcnt[w];
+    __syncthreads();
+  }
+  if (tid == 0) cnt[blockIdx.x] = nl;
 }
 
 
@@ -1822,6 +1953,19 @@ struct gfs_lba {
   gfs::PinBuf<double> h_out;
   gfs::DevBuf<double> d_q, d_t, d_X, d_qt, d_tt, d_Xt, d_chi2, d_err, d_Hpl, d_Hll, d_bl, d_Dinv, d_Hpp, d_bp, d_xl, d_xp, d_stats;
   gfs::DevBuf<int> d_info;
+  // LocalVisualLidarBA (gfs_lba_lidar_reserve): the concatenated clouds of a window's lidar key-frames and their edges
+  int lidar_cap = 0;
+  gfs::PinBuf<float> h_lcloud;
+  gfs::DevBuf<float> d_lcloud, d_ls, d_les;
+  gfs::PinBuf<gfs_lidar::WindowKF> h_lkf;
+  gfs::DevBuf<gfs_lidar::WindowKF> d_lkf;
+  gfs::PinBuf<int> h_lkf_free, h_lcnt;
+  gfs::DevBuf<int> d_lkf_free, d_lcnt, d_lidx;
+  gfs::DevBuf<uint8_t> d_lflag;
+  gfs::DevBuf<float4> d_lplane, d_leplane;
+  gfs::DevBuf<double> d_lchi2;
+  // the last lidar call's key-frames, for gfs_lba_fetch_lidar_edges: lidar key-frame of each pose (-1: none), its offset and edges
+  std::vector<int> last_lkf_of_pose, last_lbegin, last_lcnt;
 };
 
 namespace {
@@ -2100,19 +2244,40 @@ struct StopFlag {
   bool operator*() const { return (i && *i) || (b && *b); }
 };
 
-int run(gfs_lba* h, const gfs_lba_problem* p, const HostPrep& P, int mode, StopFlag stop) {
+// The lidar key-frames of a window (lidar_prepare): their association and compaction are queued on the handle's stream
+struct LidarRun {
+  int n_kf = 0, n_free = 0, total = 0;
+  std::vector<int> kf_of_pose;  // [n_poses] lidar key-frame or -1
+};
+
+int run(gfs_lba* h, const gfs_lba_problem* p, const HostPrep& P, int mode, StopFlag stop, const LidarRun* lid = nullptr) {
   hipStream_t s = h->stream;
   const int E = p->n_edges;
   LbaDev D;
   int rc = upload_and_fill(h, p, P, mode, s, D);
   if (rc) return rc;
+  if (lid && lid->n_kf > 0) {  // LocalVisualLidarBA: the lidar key-frames' workgroups go ahead of the reprojection edges' in k_lba_errors
+    D.n_lidar_kf = lid->n_kf;
+    D.n_lidar_free = lid->n_free;
+    D.lkf = (decltype(D.lkf))(h->d_lkf.p);
+    D.lkf_free = (decltype(D.lkf_free))(h->d_lkf_free.p);
+    D.lcloud = (decltype(D.lcloud))(h->d_lcloud.p);
+    D.l_cnt = (decltype(D.l_cnt))(h->d_lcnt.p);
+    D.l_idx = (decltype(D.l_idx))(h->d_lidx.p);
+    D.l_plane = (decltype(D.l_plane))(h->d_leplane.p);
+    D.l_s = (decltype(D.l_s))(h->d_les.p);
+    D.l_chi2 = (decltype(D.l_chi2))(h->d_lchi2.p);
+    D.l_info = gfs_lidar::edge_information();
+    D.l_huber = gfs_lidar::edge_huber_delta();
+    D.n_err_blocks += lid->n_kf;
+  }
   const int n = 6 * P.n_free;
   const bool in_lds = P.n_free <= kMaxFreeLds;
   const size_t lds = (in_lds ? (size_t)n * (n + 1) / 2 + 8 * n + 8 : (size_t)7 * n + 8) * sizeof(double);
   GFS_REQUIRE(lds <= 160 * 1024, GFS_ERR_CAPACITY, "gfs_lba: %d free poses exceed the solver's workspace", P.n_free);
   static const bool single_wg = getenv("GFS_LBA_SINGLE_WG") != nullptr;  // the round-1a kernel: whole solve in one workgroup
   h->last_desc = D;
-  if (single_wg && in_lds) {
+  if (single_wg && in_lds && D.n_lidar_kf == 0) {  // (the lidar entry always runs the multi-kernel path)
     GFS_REQUIRE(!D.e_dup, GFS_ERR_UNSUPPORTED, "gfs_lba: GFS_LBA_SINGLE_WG does not take several edges between one pose and one point");
     if (E) GFS_HIP(hipMemsetAsync(h->d_Hpl.p, 0, (size_t)E * 18 * sizeof(double), s));
     GFS_LAUNCH("k_lba", k_lba, dim3(1), dim3(kThreads), lds, s, D);
@@ -2140,6 +2305,7 @@ int run(gfs_lba* h, const gfs_lba_problem* p, const HostPrep& P, int mode, StopF
     if (mode == 1) {
       if (D.n_lm_wg > 0) GFS_LAUNCH("k_lba_build_landmarks", k_lba_build_landmarks, g_lm, dim3(kMk), 0, s, D, 0);
       if (P.n_free > 0) GFS_LAUNCH("k_lba_build_poses", k_lba_build_poses, dim3(P.n_free), dim3(kPoseWg), 0, s, D, 0);
+      if (D.n_lidar_free > 0) GFS_LAUNCH("k_lba_lidar_build", k_lba_lidar_build, dim3(D.n_lidar_free), dim3(kMk), 0, s, D, 0);
     }
     GFS_LAUNCH("k_lba_begin", k_lba_begin, dim3(1), dim3(kThreads), 0, s, D, 1, 0);
     LbaDev Df = D;
@@ -2165,6 +2331,7 @@ int run(gfs_lba* h, const gfs_lba_problem* p, const HostPrep& P, int mode, StopF
     GFS_LAUNCH("k_lba_errors", k_lba_errors, g_err, dim3(kMk), 0, s, D, 0, gate);
     if (D.n_lm_wg > 0) GFS_LAUNCH("k_lba_build_landmarks", k_lba_build_landmarks, g_lm, dim3(kMk), 0, s, D, gate);
     if (P.n_free > 0) GFS_LAUNCH("k_lba_build_poses", k_lba_build_poses, dim3(P.n_free), dim3(kPoseWg), 0, s, D, gate);
+    if (D.n_lidar_free > 0) GFS_LAUNCH("k_lba_lidar_build", k_lba_lidar_build, dim3(D.n_lidar_free), dim3(kMk), 0, s, D, gate);
     GFS_LAUNCH("k_lba_begin", k_lba_begin, dim3(1), dim3(kThreads), 0, s, D, iteration, gate);
     return GFS_OK;
   };
@@ -2257,6 +2424,82 @@ int run(gfs_lba* h, const gfs_lba_problem* p, const HostPrep& P, int mode, StopF
     fprintf(stderr, "  run: LM loop %.2f ms\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - Ta).count());
   }
   return GFS_OK;
+}
+
+// pKFi->mnMatchesInliers > 75 -> no lidar edges for this key-frame (src/Optimizer.cc:1338)
+constexpr int kLbaLidarMaxInliers = 75;
+
+// The lidar key-frames of a window: local (lLocalKeyFrames, the fixed initial key-frame included), at most 75 inliers, a cloud of at
+// least GenerateLidarEdge's minimum.  Their clouds go up concatenated in pose order; the association (one launch) and the compaction
+// are queued on the handle's stream.
+int lidar_prepare(gfs_lba* h, const gfs_lba_problem* p, const gfs_lba_lidar* L, LidarRun& R) {
+  h->last_lkf_of_pose.clear();  // the device edge lists are about to change: nothing to fetch until this call succeeds
+  GFS_REQUIRE(!L->two_camera, GFS_ERR_UNSUPPORTED, "gfs_lba_solve_lidar: key-frames with a second camera are not supported");
+  GFS_REQUIRE(L->map && L->map->n >= 5, GFS_ERR_INVALID_ARG, "gfs_lba_solve_lidar: no lidar map, or a map that was never set");
+  GFS_REQUIRE(L->map->device == h->device, GFS_ERR_INVALID_ARG, "gfs_lba_solve_lidar: the lidar map lives on device %d, the handle on %d",
+              L->map->device, h->device);
+  const int NQ = p->n_poses;
+  GFS_REQUIRE(NQ == 0 || (L->pose_local && L->matches_inliers && L->cloud_begin), GFS_ERR_INVALID_ARG,
+              "gfs_lba_solve_lidar: NULL key-frame arrays");
+  GFS_REQUIRE(NQ == 0 || L->cloud_begin[0] == 0, GFS_ERR_INVALID_ARG, "gfs_lba_solve_lidar: cloud_begin[0] must be 0");
+  const int min_cloud = gfs_lidar::min_cloud();
+  R = LidarRun{};
+  R.kf_of_pose.assign(NQ, -1);
+  long long total = 0;
+  for (int i = 0; i < NQ; i++) {
+    const int n = L->cloud_begin[i + 1] - L->cloud_begin[i];
+    GFS_REQUIRE(n >= 0, GFS_ERR_INVALID_ARG, "gfs_lba_solve_lidar: cloud_begin decreases at pose %d", i);
+    if (L->pose_local[i] && L->matches_inliers[i] <= kLbaLidarMaxInliers && n >= min_cloud) {
+      R.kf_of_pose[i] = R.n_kf++;
+      total += n;
+    }
+  }
+  GFS_REQUIRE(total <= h->lidar_cap, GFS_ERR_CAPACITY, "gfs_lba_solve_lidar: %lld cloud points of lidar key-frames exceed the reserved %d",
+              total, h->lidar_cap);
+  GFS_REQUIRE(total == 0 || L->cloud, GFS_ERR_INVALID_ARG, "gfs_lba_solve_lidar: NULL cloud");
+  R.total = (int)total;
+  if (R.n_kf == 0) return GFS_OK;
+  int at = 0, max_n = 0;
+  for (int i = 0; i < NQ; i++) {
+    const int k = R.kf_of_pose[i];
+    if (k < 0) continue;
+    gfs_lidar::WindowKF& K = h->h_lkf.p[k];
+    K.pose = i;
+    K.begin = at;
+    K.n = L->cloud_begin[i + 1] - L->cloud_begin[i];
+    for (int c = 0; c < 4; c++) K.q[c] = (float)p->pose_q[4 * (size_t)i + c];  // exact for poses that come from Sophus::SE3f
+    for (int c = 0; c < 3; c++) K.t[c] = (float)p->pose_t[3 * (size_t)i + c];
+    bool finite = true;
+    for (int c = 0; c < 4; c++) finite = finite && std::isfinite(K.q[c]);
+    for (int c = 0; c < 3; c++) finite = finite && std::isfinite(K.t[c]);
+    GFS_REQUIRE(finite, GFS_ERR_INVALID_ARG, "gfs_lba_solve_lidar: the float pose of key-frame %d is not finite", i);
+    memcpy(h->h_lcloud.p + 3 * (size_t)at, L->cloud + 3 * (size_t)L->cloud_begin[i], (size_t)K.n * 12);
+    if (!p->pose_fixed[i]) h->h_lkf_free.p[R.n_free++] = k;
+    at += K.n;
+    max_n = std::max(max_n, K.n);
+  }
+  hipStream_t s = h->stream;
+  GFS_HIP(hipMemcpyAsync(h->d_lkf.p, h->h_lkf.p, (size_t)R.n_kf * sizeof(gfs_lidar::WindowKF), hipMemcpyHostToDevice, s));
+  if (R.n_free) GFS_HIP(hipMemcpyAsync(h->d_lkf_free.p, h->h_lkf_free.p, (size_t)R.n_free * sizeof(int), hipMemcpyHostToDevice, s));
+  GFS_HIP(hipMemcpyAsync(h->d_lcloud.p, h->h_lcloud.p, (size_t)at * 12, hipMemcpyHostToDevice, s));
+  int rc = gfs_lidar::launch_window_assoc(L->map, h->d_lkf.p, R.n_kf, max_n, h->d_lcloud.p, h->d_lflag.p, h->d_lplane.p, h->d_ls.p, s);
+  if (rc) return rc;
+  GFS_LAUNCH("k_lba_lidar_compact", k_lba_lidar_compact, dim3(R.n_kf), dim3(kMk), 0, s, h->d_lkf.p, h->d_lflag.p, h->d_lplane.p, h->d_ls.p,
+             h->d_lcnt.p, h->d_lidx.p, h->d_leplane.p, h->d_les.p);
+  return GFS_OK;
+}
+
+// the edge counts of the last lidar call, kept for gfs_lba_fetch_lidar_edges (h_lcnt holds them once the stream is done)
+void lidar_keep(gfs_lba* h, const gfs_lba_problem* p, const LidarRun& R, int32_t* pose_lidar_edges) {
+  h->last_lkf_of_pose = R.kf_of_pose;
+  h->last_lbegin.assign(R.n_kf, 0);
+  h->last_lcnt.assign(R.n_kf, 0);
+  for (int k = 0; k < R.n_kf; k++) {
+    h->last_lbegin[k] = h->h_lkf.p[k].begin;
+    h->last_lcnt[k] = h->h_lcnt.p[k];
+  }
+  if (pose_lidar_edges)
+    for (int i = 0; i < p->n_poses; i++) pose_lidar_edges[i] = R.kf_of_pose[i] >= 0 ? h->last_lcnt[R.kf_of_pose[i]] : 0;
 }
 
 }  // namespace
@@ -2368,6 +2611,32 @@ static void lba_fetch_finish(const gfs_lba_problem* p, const HostPrep& P, const 
 }
 
 static int lba_solve_one_batched(gfs_lba* h, const gfs_lba_problem* p, gfs_lba_solution* sol, StopFlag stop);
+static int lba_solve_lidar_impl(gfs_lba* h, const gfs_lba_problem* p, const gfs_lba_lidar* L, gfs_lba_solution* sol,
+                                int32_t* pose_lidar_edges, StopFlag stop) {
+  GFS_REQUIRE(h && p && L && sol, GFS_ERR_INVALID_ARG, "gfs_lba_solve_lidar: NULL argument");
+  if (stop && *stop) {  // if (pbStopFlag) if (*pbStopFlag) return;  (src/Optimizer.cc:1502-1503)
+    gfs::set_error("gfs_lba_solve_lidar: stop flag raised before optimisation");
+    return GFS_ERR_STOPPED;
+  }
+  std::lock_guard<std::mutex> lk(h->mu);
+  GFS_HIP(hipSetDevice(h->device));
+  static thread_local HostPrep tl_prep;
+  static thread_local LidarRun tl_lidar;
+  HostPrep& P = tl_prep;
+  LidarRun& R = tl_lidar;
+  int rc = prepare(h, p, P);
+  if (rc) return rc;
+  if ((rc = lidar_prepare(h, p, L, R))) return rc;
+  if ((rc = run(h, p, P, 0, stop, &R))) return rc;
+  LbaFetch F;
+  GFS_LAUNCH("k_lba_pack", k_lba_pack, dim3(16), dim3(kMk), 0, h->stream, h->last_desc);
+  if ((rc = lba_fetch_issue(h, p, h->stream, F))) return rc;
+  if (R.n_kf) GFS_HIP(hipMemcpyAsync(h->h_lcnt.p, h->d_lcnt.p, (size_t)R.n_kf * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  GFS_HIP(hipStreamSynchronize(h->stream));
+  lba_fetch_finish(p, P, F, sol);
+  lidar_keep(h, p, R, pose_lidar_edges);
+  return GFS_OK;
+}
 static int lba_solve_impl(gfs_lba* h, const gfs_lba_problem* p, gfs_lba_solution* sol, StopFlag stop) {
   GFS_REQUIRE(h && p && sol, GFS_ERR_INVALID_ARG, "gfs_lba_solve: NULL argument");
   if (stop && *stop) {  // if (pbStopFlag) if (*pbStopFlag) return;  (src/Optimizer.cc:1955-1956)
@@ -2678,8 +2947,9 @@ static int lba_solve_one_batched(gfs_lba* h, const gfs_lba_problem* p, gfs_lba_s
   return rc;
 }
 
-int gfs_lba_linearize(gfs_lba* h, const gfs_lba_problem* p, double* Hpp, double* Hll, double* Hpl, double* bp, double* bl,
-                      double* edge_chi2, double* chi2) {
+static int lba_linearize_impl(gfs_lba* h, const gfs_lba_problem* p, const gfs_lba_lidar* L, double* Hpp, double* Hll, double* Hpl,
+                              double* bp, double* bl, double* edge_chi2, double* chi2, double* lidar_chi2, int lidar_cap,
+                              int32_t* pose_lidar_edges) {
   GFS_REQUIRE(h && p, GFS_ERR_INVALID_ARG, "gfs_lba_linearize: NULL argument");
   std::lock_guard<std::mutex> lk(h->mu);
   GFS_HIP(hipSetDevice(h->device));
@@ -2687,8 +2957,21 @@ int gfs_lba_linearize(gfs_lba* h, const gfs_lba_problem* p, double* Hpp, double*
   HostPrep& P = tl_prep;
   int rc = prepare(h, p, P);
   if (rc) return rc;
-  rc = run(h, p, P, 1, StopFlag{});
+  LidarRun R;
+  if (L && (rc = lidar_prepare(h, p, L, R))) return rc;
+  rc = run(h, p, P, 1, StopFlag{}, L ? &R : nullptr);
   if (rc) return rc;
+  if (L) {  // the per-edge chi2 of the lidar edges, in g2o's order (key-frames in pose order, then cloud order)
+    if (R.n_kf) GFS_HIP(hipMemcpyAsync(h->h_lcnt.p, h->d_lcnt.p, (size_t)R.n_kf * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    GFS_HIP(hipStreamSynchronize(h->stream));
+    lidar_keep(h, p, R, pose_lidar_edges);
+    int at = 0;
+    for (int k = 0; k < R.n_kf && lidar_chi2; k++) {
+      const int m = std::min(h->last_lcnt[k], lidar_cap - at);
+      if (m > 0) GFS_HIP(hipMemcpy(lidar_chi2 + at, h->d_lchi2.p + h->last_lbegin[k], (size_t)m * 8, hipMemcpyDeviceToHost));
+      at += std::max(m, 0);
+    }
+  }
   const int E = p->n_edges, NP = p->n_points, F = P.n_free;
   std::vector<double> hpp((size_t)F * 21), hll((size_t)NP * 6), hpl((size_t)E * 18), chi(E);
   if (F) GFS_HIP(hipMemcpy(hpp.data(), h->d_Hpp.p, hpp.size() * 8, hipMemcpyDeviceToHost));
@@ -2728,6 +3011,92 @@ int gfs_lba_linearize(gfs_lba* h, const gfs_lba_problem* p, double* Hpp, double*
       for (int a = 0; a < 6; a++)
         for (int c = 0; c < 3; c++) Hpl[18 * (size_t)e + a + 6 * c] = hpl[18 * (size_t)k + 3 * a + c];
   }
+  return GFS_OK;
+}
+
+int gfs_lba_linearize(gfs_lba* h, const gfs_lba_problem* p, double* Hpp, double* Hll, double* Hpl, double* bp, double* bl,
+                      double* edge_chi2, double* chi2) {
+  return lba_linearize_impl(h, p, nullptr, Hpp, Hll, Hpl, bp, bl, edge_chi2, chi2, nullptr, 0, nullptr);
+}
+
+int gfs_lba_linearize_lidar(gfs_lba* h, const gfs_lba_problem* p, const gfs_lba_lidar* lidar, double* Hpp, double* Hll, double* Hpl,
+                            double* bp, double* bl, double* edge_chi2, double* chi2, double* lidar_edge_chi2, int cap,
+                            int32_t* pose_lidar_edges) {
+  GFS_REQUIRE(lidar && cap >= 0, GFS_ERR_INVALID_ARG, "gfs_lba_linearize_lidar: invalid argument");
+  return lba_linearize_impl(h, p, lidar, Hpp, Hll, Hpl, bp, bl, edge_chi2, chi2, lidar_edge_chi2, cap, pose_lidar_edges);
+}
+
+int gfs_lba_lidar_reserve(gfs_lba* h, int max_cloud_points) {
+  GFS_REQUIRE(h && max_cloud_points >= 0, GFS_ERR_INVALID_ARG, "gfs_lba_lidar_reserve: invalid argument");
+  std::lock_guard<std::mutex> lk(h->mu);
+  GFS_HIP(hipSetDevice(h->device));
+  GFS_HIP(hipStreamSynchronize(h->stream));
+  const size_t N = std::max(max_cloud_points, 1), NQ = h->max_poses;
+  int rc = 0;
+#define A(x) if (!rc) rc = (x)
+  A(h->h_lcloud.alloc(3 * N));
+  A(h->d_lcloud.alloc(3 * N));
+  A(h->d_lflag.alloc(N));
+  A(h->d_lplane.alloc(N));
+  A(h->d_ls.alloc(N));
+  A(h->d_lidx.alloc(N));
+  A(h->d_leplane.alloc(N));
+  A(h->d_les.alloc(N));
+  A(h->d_lchi2.alloc(N));
+  A(h->h_lkf.alloc(NQ));
+  A(h->d_lkf.alloc(NQ));
+  A(h->h_lkf_free.alloc(NQ));
+  A(h->d_lkf_free.alloc(NQ));
+  A(h->h_lcnt.alloc(NQ));
+  A(h->d_lcnt.alloc(NQ));
+#undef A
+  // + one partial sum of k_lba_errors per lidar key-frame.  The plain solve uses this buffer too: it only grows, and the old one is
+  // kept until the new one exists.
+  const size_t need_chi = (size_t)h->max_edges / kMk + 2 + NQ;
+  if (!rc && h->d_part_chi.n < need_chi) {
+    double* np_ = nullptr;
+    if (hipMalloc((void**)&np_, need_chi * sizeof(double)) != hipSuccess) {
+      gfs::set_error("gfs_lba_lidar_reserve: hipMalloc of %zu partial sums failed", need_chi);
+      rc = GFS_ERR_HIP;
+    } else {
+      (void)hipFree(h->d_part_chi.p);
+      h->d_part_chi.p = np_;
+      h->d_part_chi.n = need_chi;
+    }
+  }
+  h->lidar_cap = rc ? 0 : max_cloud_points;
+  h->last_lkf_of_pose.clear();
+  return rc;
+}
+
+int gfs_lba_solve_lidar(gfs_lba* h, const gfs_lba_problem* p, const gfs_lba_lidar* lidar, gfs_lba_solution* sol,
+                        int32_t* pose_lidar_edges, volatile const int* stop) {
+  StopFlag f;
+  f.i = stop;
+  return lba_solve_lidar_impl(h, p, lidar, sol, pose_lidar_edges, f);
+}
+int gfs_lba_solve_lidar_bool(gfs_lba* h, const gfs_lba_problem* p, const gfs_lba_lidar* lidar, gfs_lba_solution* sol,
+                             int32_t* pose_lidar_edges, const volatile unsigned char* stop) {
+  StopFlag f;
+  f.b = stop;
+  return lba_solve_lidar_impl(h, p, lidar, sol, pose_lidar_edges, f);
+}
+
+int gfs_lba_fetch_lidar_edges(gfs_lba* h, int pose, int32_t* index, float* plane, float* s, int cap, int32_t* n) {
+  GFS_REQUIRE(h && n && cap >= 0 && (cap == 0 || (index && plane && s)), GFS_ERR_INVALID_ARG, "gfs_lba_fetch_lidar_edges: invalid argument");
+  std::lock_guard<std::mutex> lk(h->mu);
+  GFS_REQUIRE(pose >= 0 && pose < (int)h->last_lkf_of_pose.size(), GFS_ERR_INVALID_ARG,
+              "gfs_lba_fetch_lidar_edges: pose %d outside the last lidar call", pose);
+  GFS_HIP(hipSetDevice(h->device));
+  const int k = h->last_lkf_of_pose[pose];
+  const int cnt = k >= 0 ? h->last_lcnt[k] : 0;
+  *n = cnt;
+  const int m = std::min(cnt, cap);
+  if (m == 0) return GFS_OK;
+  const size_t o = h->last_lbegin[k];
+  GFS_HIP(hipMemcpy(index, h->d_lidx.p + o, (size_t)m * 4, hipMemcpyDeviceToHost));
+  GFS_HIP(hipMemcpy(plane, h->d_leplane.p + o, (size_t)m * 16, hipMemcpyDeviceToHost));
+  GFS_HIP(hipMemcpy(s, h->d_les.p + o, (size_t)m * 4, hipMemcpyDeviceToHost));
   return GFS_OK;
 }
 

@@ -146,10 +146,15 @@ class RegistrationGICP {
 // numeric core of Optimizer::LocalBundleAdjustment (reference include/Optimizer.h:62-65)
 class LocalBundleAdjuster {
  public:
-  LocalBundleAdjuster(int max_poses = 64, int max_points = 16384, int max_edges = 262144, int device = 0) {
+  LocalBundleAdjuster(int max_poses = 64, int max_points = 16384, int max_edges = 262144, int device = 0) : device_(device) {
     check(gfs_lba_create(device, max_poses, max_points, max_edges, &h_), "gfs_lba_create");
   }
-  ~LocalBundleAdjuster() { gfs_lba_destroy(h_); }
+  ~LocalBundleAdjuster() {
+    gfs_lba_destroy(h_);
+    gfs_lidar_map_destroy(map_);
+  }
+  LocalBundleAdjuster(const LocalBundleAdjuster&) = delete;
+  LocalBundleAdjuster& operator=(const LocalBundleAdjuster&) = delete;
   // returns false when *pbStopFlag was already set (the reference returns early, src/Optimizer.cc:1955-1956)
   bool solve(const gfs_lba_problem& p, gfs_lba_solution& s, const bool* pbStopFlag) {
     // the caller's flag itself goes down (a C++ bool is one byte): the solver reads it live, at the top of every iteration and
@@ -164,9 +169,32 @@ class LocalBundleAdjuster {
   template <class Access, class KeyFrame, class Map>
   void LocalBundleAdjustment(KeyFrame* pKF, bool* pbStopFlag, Map* pMap, int& num_fixedKF, int& num_OptKF, int& num_MPs,
                              int& num_edges);
+  // LocalVisualLidarBA's numeric core on the handle's owned local map (gfs_lba_solve_lidar_bool); false when *pbStopFlag was set
+  bool solve_lidar(const gfs_lba_problem& p, gfs_lba_lidar lidar, gfs_lba_solution& s, const bool* pbStopFlag,
+                   int32_t* pose_lidar_edges = nullptr) {
+    lidar.map = map_;
+    const int n = lidar.cloud_begin ? lidar.cloud_begin[p.n_poses] : 0;
+    if (n > lidar_cap_) {  // the library refuses a window beyond the reserve (it never truncates): grow it first
+      check(gfs_lba_lidar_reserve(h_, n), "gfs_lba_lidar_reserve");
+      lidar_cap_ = n;
+    }
+    static_assert(sizeof(bool) == 1, "gfs_lba_solve_lidar_bool reads the flag as one byte");
+    const int rc = gfs_lba_solve_lidar_bool(h_, &p, &lidar, &s, pose_lidar_edges, reinterpret_cast<const volatile unsigned char*>(pbStopFlag));
+    if (rc == GFS_ERR_STOPPED) return false;
+    check(rc, "gfs_lba_solve_lidar");
+    return true;
+  }
+  // Optimizer::LocalVisualLidarBA(pKF, laserCloudSurfFromMapDS, pbStopFlag, pMap, ...) (include/Optimizer.h:71) with the local map as
+  // packed xyz floats ([n_map][3]; pcl::PointXYZRGBA is 32 bytes), uploaded into the owned map (see LocalVisualLidarBA below)
+  template <class Access, class KeyFrame, class Map>
+  void LocalVisualLidarBA(KeyFrame* pKF, const float* map_xyz, int n_map, bool* pbStopFlag, Map* pMap, int& num_fixedKF,
+                          int& num_OptKF, int& num_MPs, int& num_edges);
 
  private:
   gfs_lba* h_ = nullptr;
+  int device_ = 0;
+  gfs_lidar_map* map_ = nullptr;  // created at the first LocalVisualLidarBA
+  int map_cap_ = 0, lidar_cap_ = 0;
 };
 
 // ------------------------------------------------------------------------------------------------------------------------
@@ -228,6 +256,9 @@ struct LbaFlat {  // the flattened graph, in the reference's vertex / edge creat
   }
 };
 
+// `solve` is called as solve(problem, solution, pbStopFlag), or -- when it takes them -- with two more arguments: the key-frame of
+// every pose in the problem's pose order (lLocalKeyFrames in list order, then lFixedCameras) and the number of local key-frames.
+// LocalVisualLidarBA (below) gathers its per-key-frame data through them.
 template <class Access, class KeyFrame, class MapPoint, class Map, class Solve>
 void LocalBundleAdjustment(Solve&& solve, KeyFrame* pKF, bool* pbStopFlag, Map* pMap, int& num_fixedKF, int& num_OptKF,
                            int& /*num_MPs: never written by the reference either*/, int& num_edges) {
@@ -274,12 +305,14 @@ void LocalBundleAdjustment(Solve&& solve, KeyFrame* pKF, bool* pbStopFlag, Map* 
   // ---- vertices (:1686-1721): pose index = creation order, local key-frames first
   LbaFlat F;
   std::map<const KeyFrame*, int32_t> pose_index;  // == optimizer.vertex(pKFi->mnId) != NULL
+  std::vector<KeyFrame*> pose_kf;                  // the key-frame of every pose, in pose order
   pCurrentMap->msOptKFs.clear();
   pCurrentMap->msFixedKFs.clear();
   auto add_pose = [&](KeyFrame* pKFi, bool fixed) {
     float q[4], t[3];
     Access::pose(pKFi, q, t);
     pose_index[pKFi] = (int32_t)F.pose_fixed.size();
+    pose_kf.push_back(pKFi);
     for (int k = 0; k < 4; k++) F.pose_q.push_back((double)q[k]);  // .cast<double>()
     for (int k = 0; k < 3; k++) F.pose_t.push_back((double)t[k]);
     F.pose_fixed.push_back(fixed ? 1 : 0);
@@ -352,7 +385,11 @@ void LocalBundleAdjustment(Solve&& solve, KeyFrame* pKF, bool* pbStopFlag, Map* 
   S.points = out_p.data();
   S.edge_chi2 = chi2.data();
   S.edge_depth_positive = depth_pos.data();
-  if (!solve(F.problem, S, pbStopFlag)) return;
+  if constexpr (std::is_invocable_v<Solve&, const gfs_lba_problem&, gfs_lba_solution&, const bool*, const std::vector<KeyFrame*>&, int>) {
+    if (!solve(F.problem, S, pbStopFlag, static_cast<const std::vector<KeyFrame*>&>(pose_kf), num_OptKF)) return;
+  } else {
+    if (!solve(F.problem, S, pbStopFlag)) return;
+  }
 
   // ---- check inlier observations (:1961-1999): mono edges first, then stereo, each in creation order
   std::vector<std::pair<KeyFrame*, MapPoint*>> vToErase;
@@ -407,6 +444,71 @@ void LocalBundleAdjuster::LocalBundleAdjustment(KeyFrame* pKF, bool* pbStopFlag,
   gfs_host::LocalBundleAdjustment<Access, KeyFrame, MapPoint, Map>(
       [this](const gfs_lba_problem& p, gfs_lba_solution& s, const bool* stop) { return this->solve(p, s, stop); }, pKF, pbStopFlag,
       pMap, num_fixedKF, num_OptKF, num_MPs, num_edges);
+}
+
+// ------------------------------------------------------------------------------------------------------------------------
+// Optimizer::LocalVisualLidarBA(KeyFrame* pKF, PointCloud::Ptr laserCloudSurfFromMapDS, bool* pbStopFlag, Map* pMap, int& num_fixedKF,
+//                               int& num_OptKF, int& num_MPs, int& num_edges)                   reference src/Optimizer.cc:1101-1587
+// LocalBundleAdjustment line for line (the gather, the stop flag, the classification and the write-back above are reused as they
+// are) plus the lidar edges of :1327-1362.  Per pose, in pose order, it hands the numeric core what those need: pose_local (1 for the
+// lLocalKeyFrames, 0 for lFixedCameras), pKFi->mnMatchesInliers and pKFi->mpPointCloudDownsampled, the clouds concatenated in
+// lLocalKeyFrames order (a fixed camera never gets edges, so its cloud is not read).  The library applies the 75-inlier and 50-point
+// gates.  `Access` adds to LocalBundleAdjustment's four functions
+//     static int matches_inliers(const KeyFrame*);                          // pKFi->mnMatchesInliers
+//     static const float* cloud(const KeyFrame*, int* n);                   // mpPointCloudDownsampled packed to [n][3] floats
+// `solve(problem, lidar, solution, pbStopFlag)`: LocalBundleAdjuster::solve_lidar on the GPU (lidar.map is set there).
+// num_edges counts the reprojection edges only (the lidar edges increment the reference's unused edge_num).
+// ------------------------------------------------------------------------------------------------------------------------
+struct LbaLidarFlat {  // the lidar half of the window, in pose order
+  std::vector<uint8_t> pose_local;
+  std::vector<int32_t> matches_inliers, cloud_begin;
+  std::vector<float> cloud;
+  gfs_lba_lidar lidar{};
+};
+
+template <class Access, class KeyFrame, class MapPoint, class Map, class SolveLidar>
+void LocalVisualLidarBA(SolveLidar&& solve, KeyFrame* pKF, bool* pbStopFlag, Map* pMap, int& num_fixedKF, int& num_OptKF, int& num_MPs,
+                        int& num_edges) {
+  LbaLidarFlat L;
+  LocalBundleAdjustment<Access, KeyFrame, MapPoint, Map>(
+      [&](const gfs_lba_problem& p, gfs_lba_solution& s, const bool* stop, const std::vector<KeyFrame*>& pose_kf, int n_local) {
+        L.cloud_begin.assign(1, 0);
+        for (size_t i = 0; i < pose_kf.size(); i++) {
+          const bool local = (int)i < n_local;
+          int n = 0;
+          const float* c = local ? Access::cloud(pose_kf[i], &n) : nullptr;
+          if (!c || n < 0) n = 0;
+          L.pose_local.push_back(local ? 1 : 0);
+          L.matches_inliers.push_back(local ? (int32_t)Access::matches_inliers(pose_kf[i]) : 0);
+          L.cloud.insert(L.cloud.end(), c, c + 3 * (size_t)n);
+          L.cloud_begin.push_back(L.cloud_begin.back() + n);
+        }
+        L.lidar.pose_local = L.pose_local.data();
+        L.lidar.matches_inliers = L.matches_inliers.data();
+        L.lidar.cloud_begin = L.cloud_begin.data();
+        L.lidar.cloud = L.cloud.data();
+        L.lidar.two_camera = 0;  // (observations of a second camera are refused by the gather, as in LocalBundleAdjustment)
+        return solve(p, static_cast<const gfs_lba_lidar&>(L.lidar), s, stop);
+      },
+      pKF, pbStopFlag, pMap, num_fixedKF, num_OptKF, num_MPs, num_edges);
+}
+
+template <class Access, class KeyFrame, class Map>
+void LocalBundleAdjuster::LocalVisualLidarBA(KeyFrame* pKF, const float* map_xyz, int n_map, bool* pbStopFlag, Map* pMap, int& num_fixedKF,
+                                             int& num_OptKF, int& num_MPs, int& num_edges) {
+  using MapPoint = typename std::remove_pointer<typename decltype(pKF->GetMapPointMatches())::value_type>::type;
+  if (!map_ || n_map > map_cap_) {
+    gfs_lidar_map_destroy(map_);
+    map_ = nullptr;
+    map_cap_ = std::max(n_map, 5);
+    check(gfs_lidar_map_create(device_, map_cap_, &map_), "gfs_lidar_map_create");
+  }
+  check(gfs_lidar_map_set(map_, map_xyz, n_map), "gfs_lidar_map_set");
+  gfs_host::LocalVisualLidarBA<Access, KeyFrame, MapPoint, Map>(
+      [this](const gfs_lba_problem& p, const gfs_lba_lidar& lidar, gfs_lba_solution& s, const bool* stop) {
+        return this->solve_lidar(p, lidar, s, stop);
+      },
+      pKF, pbStopFlag, pMap, num_fixedKF, num_OptKF, num_MPs, num_edges);
 }
 
 // gms_matcher(kp1, size1, kp2, size2, matches).GetInlierMask(mask, false, false) (reference Thirdparty/GMS/include/gms_matcher.h;

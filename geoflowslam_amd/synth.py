@@ -513,3 +513,60 @@ def pose_lidar_frame(seed, n_obs=600, n_cloud=3000, n_keyframes=3, voxel=0.1, wi
                 inv_sigma2=np.array(w, np.float32), stereo=np.array(st, np.uint8), fx=fx, fy=fy, cx=cx, cy=cy, bf=bf,
                 cloud=np.ascontiguousarray(cloud, np.float32), map_xyz=map_xyz, n_iterations=n_iterations,
                 q_gt=_quat_from_R(Rcw), t_gt=tcw)
+
+
+def lba_lidar_window(seed, n_free=20, n_fixed=5, n_points=3000, n_cloud=3000, voxel=0.04, width=160, height=120, n_map_kf=3,
+                     lidar=None, init_fixed=False, short_cloud=(), empty_cloud=(), map_shift=None, **kw):
+    """Synthetic Optimizer::LocalVisualLidarBA window (reference src/Optimizer.cc:1101-1587): an lba_window (poses 0 .. n_free - 1
+    are lLocalKeyFrames, the rest fixed cameras) on a Scene, with each key-frame's downsampled cloud rendered from its TRUE pose
+    (camera frame, about n_cloud points) and the local map voxel-averaged (`voxel` metres) from n_map_kf renders in world
+    coordinates, as pose_lidar_frame builds it.
+      lidar: local poses with mnMatchesInliers <= 75 (default: every other local pose, starting with 1); the others get 76 .. 300;
+      init_fixed: pose 0 is also fixed (the map's initial key-frame: local, fixed, with lidar edges);
+      short_cloud: poses whose cloud is cut to 49 points; empty_cloud: poses without a cloud;
+      map_shift: a translation added to the map (far away: no point gets an edge).
+    The stored poses stay float values (Sophus::SE3f).  Returns lba_window's dict plus pose_local, matches_inliers, cloud_begin,
+    cloud and map_xyz."""
+    w = lba_window(seed, n_free=n_free, n_fixed=n_fixed, n_points=n_points, **kw)
+    n_poses = w["n_poses"]
+    rng = np.random.default_rng(seed + 0x1DA)
+    sc = Scene(seed)
+    local = np.zeros(n_poses, np.uint8)
+    local[:n_free] = 1
+    if init_fixed:
+        w["pose_fixed"] = w["pose_fixed"].copy()
+        w["pose_fixed"][0] = 1
+        w["pose_q"][0], w["pose_t"][0] = w["gt_q"][0].astype(np.float32), w["gt_t"][0].astype(np.float32)
+    lidar = list(range(1, n_free, 2)) if lidar is None else list(lidar)
+    inl = rng.integers(76, 300, n_poses).astype(np.int32)
+    for i in lidar:
+        inl[i] = rng.integers(20, 76)
+    def T_wc(i):
+        Rcw = _rot_from_quat(w["gt_q"][i])
+        T = np.eye(4)
+        T[:3, :3] = Rcw.T
+        T[:3, 3] = -Rcw.T @ w["gt_t"][i]
+        return T
+    clouds = []
+    for i in range(n_poses):
+        if i in empty_cloud:
+            clouds.append(np.zeros((0, 3), np.float32))
+            continue
+        _, d = sc.render(width, height, T_wc(i), 200 + i)
+        c = depth_to_cloud(d, 1)[:, :3].astype(np.float32)
+        m = 49 if i in short_cloud else n_cloud
+        if len(c) > m:
+            c = c[np.sort(rng.choice(len(c), m, replace=False))]
+        clouds.append(np.ascontiguousarray(c, np.float32))
+    pts = []
+    for k in range(n_map_kf):
+        T = T_wc(int(round(k * (n_poses - 1) / max(n_map_kf - 1, 1))))
+        _, d = sc.render(2 * width, 2 * height, T, 300 + k)
+        c = depth_to_cloud(d, 1)[:, :3].astype(np.float64)
+        pts.append(c @ T[:3, :3].T + T[:3, 3])
+    map_xyz = voxel_average(np.concatenate(pts), voxel)
+    if map_shift is not None:
+        map_xyz = (map_xyz + np.asarray(map_shift, np.float32)).astype(np.float32)
+    w.update(pose_local=local, matches_inliers=inl, cloud_begin=np.r_[0, np.cumsum([len(c) for c in clouds])].astype(np.int32),
+             cloud=np.ascontiguousarray(np.concatenate(clouds), np.float32).reshape(-1, 3), map_xyz=map_xyz)
+    return w

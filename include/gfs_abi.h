@@ -279,6 +279,46 @@ void gfs_lba_batch_destroy(gfs_lba_batch* h);
 int gfs_lba_solve_batch(gfs_lba_batch* h, const gfs_lba_problem* problems, gfs_lba_solution* solutions, int n,
                         volatile const int* stop);
 
+/* Optimizer::LocalVisualLidarBA (include/Optimizer.h:71, src/Optimizer.cc:1101-1587), called by LocalMapping::Run instead of
+ * LocalBundleAdjustment when UsePointCloudObs and UseLidarLocalBA are both set (src/LocalMapping.cc:182-183, 231-240): the window
+ * of gfs_lba_problem plus, for every local key-frame with mnMatchesInliers <= 75 (:1338) and a downsampled cloud of at least 50
+ * points (GenerateLidarEdge, :8343-8345), the EdgeSE3LidarPoint2Plane edges GenerateLidarEdge builds (:1327-1362): 5-NN in the one
+ * local map, float ColPivHouseholderQR plane, the 0.2 plane and s > 0.1 weight gates, as in section 11.  The association runs once,
+ * before the optimisation, at the key-frame's stored pose: initPose = toMatrix4d(pKFi->GetPose().inverse()) (:1341) evaluated on
+ * ((float) pose_q, (float) pose_t), which is exact for poses that come from Sophus::SE3f as the reference's do.  The edges stay fixed
+ * for the 10 iterations.  Error s (n . (Twc p) + d), information 1e2 (:1348), Huber delta (float) sqrt(1.0) (:1328), g2o's numeric
+ * Jacobian (central differences, delta 1e-9).  The edges of the fixed initial key-frame count in chi2, not in H / b.  Edge order
+ * (g2o's sums): all lidar edges before the reprojection edges, key-frames in pose order (lLocalKeyFrames order), then cloud order.
+ * The reprojection-edge outputs (chi2, depth, num_edges) are those of gfs_lba_solve; lidar edges only move the estimate.  Fixed
+ * cameras (pose_local = 0) never get edges.  A window without lidar key-frames runs gfs_lba_solve's path: the same bits.
+ * Refused: a map on another device or never set (GFS_ERR_INVALID_ARG), lidar key-frames' clouds beyond the capacity reserved with
+ * gfs_lba_lidar_reserve (GFS_ERR_CAPACITY; nothing is truncated), two_camera != 0 (GFS_ERR_UNSUPPORTED).  GFS_LBA_SINGLE_WG and
+ * GFS_LBA_SINGLE=batched do not apply to this entry.  DESIGN.md "Local BA with lidar edges". */
+typedef struct {
+  const struct gfs_lidar_map* map; /* laserCloudSurfFromMapDS (section 11), on the handle's device */
+  const uint8_t* pose_local;      /* [n_poses] 1 = in lLocalKeyFrames (the fixed initial key-frame included), 0 = fixed camera */
+  const int32_t* matches_inliers; /* [n_poses] KeyFrame::mnMatchesInliers */
+  const int32_t* cloud_begin;     /* [n_poses + 1], cloud_begin[0] = 0 */
+  const float* cloud;             /* [cloud_begin[n_poses]][3] mpPointCloudDownsampled, camera frame */
+  int32_t two_camera;             /* some local key-frame has mpCamera2: refused */
+} gfs_lba_lidar;
+/* Capacity for the concatenated clouds of a window's lidar key-frames (call before the first lidar call; again to change it). */
+int gfs_lba_lidar_reserve(gfs_lba* h, int max_cloud_points);
+/* optimizer.optimize(10) with the lidar edges; stop flag as gfs_lba_solve.  pose_lidar_edges [n_poses] (may be NULL): edges of each pose. */
+int gfs_lba_solve_lidar(gfs_lba* h, const gfs_lba_problem* p, const gfs_lba_lidar* lidar, gfs_lba_solution* s, int32_t* pose_lidar_edges,
+                        volatile const int* stop);
+/* The same with the reference's C++ bool flag (see gfs_lba_solve_bool). */
+int gfs_lba_solve_lidar_bool(gfs_lba* h, const gfs_lba_problem* p, const gfs_lba_lidar* lidar, gfs_lba_solution* s,
+                             int32_t* pose_lidar_edges, const volatile unsigned char* stop);
+/* gfs_lba_linearize with the lidar edges: their terms in Hpp / bp and *chi2; lidar_edge_chi2 (up to cap) every lidar edge's chi2
+ * in edge order; pose_lidar_edges [n_poses] (may be NULL). */
+int gfs_lba_linearize_lidar(gfs_lba* h, const gfs_lba_problem* p, const gfs_lba_lidar* lidar, double* Hpp, double* Hll, double* Hpl,
+                            double* bp, double* bl, double* edge_chi2, double* chi2, double* lidar_edge_chi2, int cap,
+                            int32_t* pose_lidar_edges);
+/* Diagnostic: the lidar edges of `pose` in the last lidar call on this handle (cloud index order): point index in the pose's cloud,
+ * plane (pa, pb, pc, pd) and s.  Up to cap edges; *n = the pose's edge count. */
+int gfs_lba_fetch_lidar_edges(gfs_lba* h, int pose, int32_t* index, float* plane /* [cap][4] */, float* s, int cap, int32_t* n);
+
 /* ============================================================================================
  * 5. Frame helpers next to the hot path — keep GICP input and RGB-D "stereo" coordinates on device
  *      Frame::ConvertDepthToPointCloud(downSample, ...)   src/Frame.cc:590-623

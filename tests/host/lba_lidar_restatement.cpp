@@ -1,0 +1,336 @@
+// TEST INFRASTRUCTURE — NOT PRODUCT CODE.  Sequential CPU restatement of the numeric core of Optimizer::LocalVisualLidarBA (reference
+// src/Optimizer.cc:1101-1587): LocalBundleAdjustment's graph (oracle/lba_oracle.cpp) plus, for every local key-frame with
+// mnMatchesInliers <= 75 (:1338), the EdgeSE3LidarPoint2Plane edges GenerateLidarEdge builds (:1327-1362, :8339-8421) at the key-frame's
+// stored float pose (:1341), against one local map.  The checker of the lidar path of geoflowslam_amd/csrc/lba.hip; the tests build it
+// with g++ -O2 -std=c++17 -ffp-contract=off.
+//
+// It reuses, unchanged, the LBA oracle's edges, Huber kernel and Schur solve (oracle/lba_oracle.cpp) and the PoseLidarVisualOptimization
+// restatement's edge generator and lidar error (tests/host/pose_lidar_restatement.cpp: brute-force 5-NN, Eigen's ColPivHouseholderQR
+// step by step), each included into a namespace of its own.  What is new is g2o's order with both kinds of edges: the lidar edges are
+// added to the graph first (:1327-1362 come before the map-point loop), so every sum -- chi2, H, b -- takes them first, key-frame after
+// key-frame in pose order (lLocalKeyFrames order), each in cloud order; then the reprojection edges as the oracle sums them.  Without
+// lidar edges every sum is the oracle's, bit for bit.
+#include <algorithm>
+#include <cfloat>
+#include <cmath>
+#include <cstdint>
+#include <cstring>
+#include <limits>
+#include <vector>
+
+#include "g2o_se3.hpp"
+#include "gfs_abi.h"
+#include "gfs_oracle.h"
+
+namespace lbo {
+#include "lba_oracle.cpp"
+}
+namespace plr {
+#include "pose_lidar_restatement.cpp"
+}
+
+namespace {
+
+using namespace gfso_se3;
+
+constexpr int kMaxInliers = 75;                                      // pKFi->mnMatchesInliers > 75 -> continue (:1338)
+constexpr double kLidarInfo = 1e2;                                   // information(0, 0) = 1e2 (:1348)
+const double kThHuberLidar = (double)(float)std::sqrt(1.0);          // const float thHuberLidar = sqrt(1.0) (:1328)
+
+struct LidarKF {
+  int pose;
+  std::vector<plr::LidarEdge> E;
+  std::vector<double> err, chi2;
+};
+
+// GenerateLidarEdge for every qualifying local key-frame, in pose order
+std::vector<LidarKF> generate(const gfso_lba_problem* p, const gfs_lba_lidar* L, const float* map, int n_map) {
+  std::vector<LidarKF> out;
+  if (!L) return out;
+  for (int i = 0; i < p->n_poses; i++) {
+    const int n = L->cloud_begin[i + 1] - L->cloud_begin[i];
+    if (!L->pose_local[i] || L->matches_inliers[i] > kMaxInliers) continue;
+    LidarKF K;
+    K.pose = i;
+    if (n >= plr::kMinCloud) {  // (:8343-8345)
+      float qf[4], tf[3];
+      for (int c = 0; c < 4; c++) qf[c] = (float)p->pose_q[4 * i + c];
+      for (int c = 0; c < 3; c++) tf[c] = (float)p->pose_t[3 * i + c];
+      double M[12];
+      plr::init_pose(qf, tf, M);
+      for (int k = 0; k < n; k++) {
+        plr::LidarEdge E;
+        if (plr::lidar_edge_for_point(map, n_map, L->cloud + 3 * (size_t)(L->cloud_begin[i] + k), M, &E)) {
+          E.idx = k;
+          K.E.push_back(E);
+        }
+      }
+    }
+    K.err.assign(K.E.size(), 0.0);
+    K.chi2.assign(K.E.size(), 0.0);
+    out.push_back(K);
+  }
+  return out;
+}
+
+void lidar_errors(const lbo::Problem& S, std::vector<LidarKF>& LK) {
+  for (LidarKF& K : LK)
+    for (size_t l = 0; l < K.E.size(); l++) {
+      K.err[l] = plr::lidar_error(S.poses[K.pose], K.E[l]);
+      K.chi2[l] = plr::lidar_chi2(K.err[l]);
+    }
+}
+
+// activeRobustChi2 in edge-id order: the lidar edges, then the reprojection edges (the oracle's loop)
+double active_robust_chi2(const lbo::Problem& S, const std::vector<LidarKF>& LK) {
+  const gfso_lba_problem& p = *S.p;
+  double chi = 0;
+  for (const LidarKF& K : LK)
+    for (size_t l = 0; l < K.E.size(); l++) {
+      double rho[3];
+      lbo::huber(K.chi2[l], kThHuberLidar, rho);
+      chi += rho[0];
+    }
+  for (int e = 0; e < p.n_edges; e++) {
+    double rho[3];
+    lbo::huber(S.chi2[e], p.edge_stereo[e] ? p.huber_stereo : p.huber_mono, rho);
+    chi += rho[0];
+  }
+  return chi;
+}
+
+// BlockSolver::buildSystem with the lidar edges first: BaseUnaryEdge::linearizeOplus (core/base_unary_edge.hpp:82-123, central
+// differences, delta 1e-9; nothing for a fixed vertex) and constructQuadraticForm; then the reprojection edges as the oracle adds them
+void build_system(const lbo::Problem& S, const std::vector<LidarKF>& LK, lbo::System& A) {
+  const gfso_lba_problem& p = *S.p;
+  A.nf = S.n_free;
+  A.np = p.n_points;
+  A.ne = p.n_edges;
+  A.Hpp.assign((size_t)A.nf * 36, 0);
+  A.Hll.assign((size_t)A.np * 9, 0);
+  A.Hpl.assign((size_t)A.ne * 18, 0);
+  A.bp.assign((size_t)A.nf * 6, 0);
+  A.bl.assign((size_t)A.np * 3, 0);
+  const double delta = 1e-9, scalar = 1.0 / (2 * delta);
+  for (const LidarKF& K : LK) {
+    const int fi = S.free_index[K.pose];
+    if (fi < 0) continue;
+    const Pose& T = S.poses[K.pose];
+    for (size_t l = 0; l < K.E.size(); l++) {
+      double J[6];
+      for (int d = 0; d < 6; d++) {
+        double add[6] = {0, 0, 0, 0, 0, 0};
+        Pose Tp = T;
+        add[d] = delta;
+        pose_oplus(Tp, add);
+        const double e1 = plr::lidar_error(Tp, K.E[l]);
+        Pose Tm = T;
+        add[d] = -delta;
+        pose_oplus(Tm, add);
+        const double e2 = plr::lidar_error(Tm, K.E[l]);
+        J[d] = scalar * (e1 - e2);
+      }
+      double rho[3];
+      lbo::huber(K.chi2[l], kThHuberLidar, rho);
+      const double e = K.err[l];
+      for (int a = 0; a < 6; a++) {
+        A.bp[6 * fi + a] -= ((rho[1] * J[a]) * kLidarInfo) * e;
+        for (int c = 0; c < 6; c++) A.Hpp[36 * fi + 6 * a + c] += (J[a] * (rho[1] * kLidarInfo)) * J[c];
+      }
+    }
+  }
+  for (int e = 0; e < p.n_edges; e++) {  // lba_oracle.cpp build_system, edge by edge
+    double Ji[9], Jj[18];
+    int D;
+    lbo::edge_jacobians(S, e, Ji, Jj, &D);
+    double rho[3];
+    lbo::huber(S.chi2[e], p.edge_stereo[e] ? p.huber_stereo : p.huber_mono, rho);
+    const double w = rho[1] * p.edge_inv_sigma2[e];
+    const double* r = &S.err[3 * e];
+    double omega_r[3];
+    for (int k = 0; k < 3; k++) omega_r[k] = -(p.edge_inv_sigma2[e] * r[k]) * rho[1];
+    const int pt = p.edge_point[e], fi = S.free_index[p.edge_pose[e]];
+    for (int a = 0; a < 3; a++) {
+      for (int k = 0; k < D; k++) A.bl[3 * pt + a] += Ji[k * 3 + a] * omega_r[k];
+      for (int b = 0; b < 3; b++) {
+        double s = 0;
+        for (int k = 0; k < D; k++) s += Ji[k * 3 + a] * w * Ji[k * 3 + b];
+        A.Hll[9 * pt + 3 * a + b] += s;
+      }
+    }
+    if (fi >= 0) {
+      for (int a = 0; a < 6; a++) {
+        for (int k = 0; k < D; k++) A.bp[6 * fi + a] += Jj[k * 6 + a] * omega_r[k];
+        for (int b = 0; b < 6; b++) {
+          double s = 0;
+          for (int k = 0; k < D; k++) s += Jj[k * 6 + a] * w * Jj[k * 6 + b];
+          A.Hpp[36 * fi + 6 * a + b] += s;
+        }
+        for (int b = 0; b < 3; b++) {
+          double s = 0;
+          for (int k = 0; k < D; k++) s += Jj[k * 6 + a] * w * Ji[k * 3 + b];
+          A.Hpl[18 * e + 3 * a + b] += s;
+        }
+      }
+    }
+  }
+}
+
+// the edges in g2o's order: pose_edges [n_poses]; e_idx / e_plane / e_s [sum] (may be NULL); lidar_chi2 [sum] (may be NULL)
+int report_edges(const gfso_lba_problem* p, const std::vector<LidarKF>& LK, int32_t* pose_edges, int32_t* e_idx, float* e_plane,
+                 float* e_s, double* lidar_chi2) {
+  if (pose_edges)
+    for (int i = 0; i < p->n_poses; i++) pose_edges[i] = 0;
+  int at = 0;
+  for (const LidarKF& K : LK) {
+    if (pose_edges) pose_edges[K.pose] = (int)K.E.size();
+    for (size_t l = 0; l < K.E.size(); l++, at++) {
+      if (e_idx) e_idx[at] = K.E[l].idx;
+      if (e_plane) std::memcpy(e_plane + 4 * (size_t)at, K.E[l].plane, 16);
+      if (e_s) e_s[at] = K.E[l].s;
+      if (lidar_chi2) lidar_chi2[at] = K.chi2[l];
+    }
+  }
+  return at;
+}
+
+}  // namespace
+
+extern "C" {
+
+// One buildSystem at the initial estimates (gfso_lba_linearize's outputs, column-major) with the lidar edges; returns the robust chi2.
+// L may be NULL (no lidar edges).
+double lblr_linearize(const gfso_lba_problem* p, const gfs_lba_lidar* L, const float* map, int n_map, double* Hpp, double* Hll,
+                      double* Hpl, double* bp, double* bl, double* edge_chi2, double* lidar_chi2, int32_t* pose_edges, int32_t* e_idx,
+                      float* e_plane, float* e_s) {
+  lbo::Problem S;
+  lbo::init_problem(S, p);
+  std::vector<LidarKF> LK = generate(p, L, map, n_map);
+  lbo::compute_active_errors(S);
+  lidar_errors(S, LK);
+  lbo::System A;
+  build_system(S, LK, A);
+  for (int i = 0; i < A.nf; i++)
+    for (int a = 0; a < 6; a++)
+      for (int b = 0; b < 6; b++)
+        if (Hpp) Hpp[36 * i + a + 6 * b] = A.Hpp[36 * i + 6 * a + b];
+  for (int l = 0; l < A.np; l++)
+    for (int a = 0; a < 3; a++)
+      for (int b = 0; b < 3; b++)
+        if (Hll) Hll[9 * l + a + 3 * b] = A.Hll[9 * l + 3 * a + b];
+  for (int e = 0; e < A.ne; e++)
+    for (int a = 0; a < 6; a++)
+      for (int b = 0; b < 3; b++)
+        if (Hpl) Hpl[18 * e + a + 6 * b] = A.Hpl[18 * e + 3 * a + b];
+  if (bp) std::memcpy(bp, A.bp.data(), A.bp.size() * 8);
+  if (bl) std::memcpy(bl, A.bl.data(), A.bl.size() * 8);
+  if (edge_chi2) std::memcpy(edge_chi2, S.chi2.data(), S.chi2.size() * 8);
+  report_edges(p, LK, pose_edges, e_idx, e_plane, e_s, lidar_chi2);
+  return active_robust_chi2(S, LK);
+}
+
+// optimizer.optimize(10) (gfso_lba_solve's loop, core/optimization_algorithm_levenberg.cpp:61-168) with the lidar edges in every chi2,
+// every trial and the initial lambda; returns the number of lidar edges.
+int lblr_solve(const gfso_lba_problem* p, const gfs_lba_lidar* L, const float* map, int n_map, gfso_lba_solution* s, int32_t* pose_edges,
+               int32_t* e_idx, float* e_plane, float* e_s) {
+  lbo::Problem S;
+  lbo::init_problem(S, p);
+  std::vector<LidarKF> LK = generate(p, L, map, n_map);
+  lbo::System A;
+  const double tau = 1e-5, goodStepUpperScale = 2. / 3., goodStepLowerScale = 1. / 3.;
+  const int maxTrialsAfterFailure = 10;
+  double currentLambda = -1, ni = 2;
+  int nBad = 0, iters = 0;
+  double lastChi = 0;
+  for (int iteration = 0; iteration < p->iterations; iteration++) {
+    lbo::compute_active_errors(S);
+    lidar_errors(S, LK);
+    double currentChi = active_robust_chi2(S, LK);
+    double tempChi = currentChi;
+    const double iniChi = currentChi;
+    build_system(S, LK, A);
+    if (iteration == 0) {
+      double maxDiagonal = 0;
+      for (int i = 0; i < A.nf; i++)
+        for (int a = 0; a < 6; a++) maxDiagonal = std::max(std::fabs(A.Hpp[36 * i + 7 * a]), maxDiagonal);
+      for (int l = 0; l < A.np; l++)
+        for (int a = 0; a < 3; a++) maxDiagonal = std::max(std::fabs(A.Hll[9 * l + 4 * a]), maxDiagonal);
+      currentLambda = tau * maxDiagonal;
+      ni = 2;
+      nBad = 0;
+    }
+    double rho = 0;
+    int qmax = 0;
+    do {
+      const std::vector<Pose> poses_backup = S.poses;
+      const std::vector<double> points_backup = S.points;
+      std::vector<double> xp, xl;
+      const bool ok2 = lbo::solve_schur(S, A, currentLambda, xp, xl);
+      if (ok2) {
+        for (int i = 0; i < p->n_poses; i++)
+          if (S.free_index[i] >= 0) pose_oplus(S.poses[i], &xp[6 * S.free_index[i]]);
+        for (size_t k = 0; k < S.points.size(); k++) S.points[k] += xl[k];
+      }
+      lbo::compute_active_errors(S);
+      lidar_errors(S, LK);
+      tempChi = active_robust_chi2(S, LK);
+      if (!ok2) tempChi = std::numeric_limits<double>::max();
+      rho = (currentChi - tempChi);
+      double scale = 0;
+      if (ok2) {
+        for (size_t j = 0; j < xp.size(); j++) scale += xp[j] * (currentLambda * xp[j] + A.bp[j]);
+        for (size_t j = 0; j < xl.size(); j++) scale += xl[j] * (currentLambda * xl[j] + A.bl[j]);
+      }
+      scale += 1e-3;
+      rho /= scale;
+      if (rho > 0 && std::isfinite(tempChi)) {
+        double alpha = 1. - std::pow((2 * rho - 1), 3);
+        alpha = std::min(alpha, goodStepUpperScale);
+        const double scaleFactor = std::max(goodStepLowerScale, alpha);
+        currentLambda *= scaleFactor;
+        ni = 2;
+        currentChi = tempChi;
+      } else {
+        currentLambda *= ni;
+        ni *= 2;
+        S.poses = poses_backup;
+        S.points = points_backup;
+      }
+      qmax++;
+    } while (rho < 0 && qmax < maxTrialsAfterFailure);
+    iters++;
+    lastChi = currentChi;
+    if (qmax == maxTrialsAfterFailure || rho == 0) break;
+    if ((iniChi - currentChi) * 1e3 < iniChi)
+      nBad++;
+    else
+      nBad = 0;
+    if (nBad >= 3) break;
+  }
+  if (p->iterations <= 0) lbo::compute_active_errors(S);
+  for (int i = 0; i < p->n_poses; i++) {
+    std::memcpy(s->pose_q + 4 * i, S.poses[i].q, 32);
+    std::memcpy(s->pose_t + 3 * i, S.poses[i].t, 24);
+  }
+  std::memcpy(s->points, S.points.data(), S.points.size() * 8);
+  for (int e = 0; e < p->n_edges; e++) {
+    if (s->edge_chi2) s->edge_chi2[e] = S.chi2[e];
+    if (s->edge_depth_positive) {
+      double xc[3];
+      map_point(S.poses[p->edge_pose[e]], &S.points[3 * p->edge_point[e]], xc);
+      s->edge_depth_positive[e] = xc[2] > 0.0;
+    }
+  }
+  s->iterations_run = iters;
+  s->final_chi2 = lastChi;
+  s->final_lambda = currentLambda;
+  return report_edges(p, LK, pose_edges, e_idx, e_plane, e_s, nullptr);
+}
+
+// the literals the restatement compiles in: max inliers, information, Huber delta, min cloud, edge order (1 = lidar edges first)
+void lblr_constants(double* out /* [5] */) {
+  const double v[5] = {(double)kMaxInliers, kLidarInfo, kThHuberLidar, (double)plr::kMinCloud, 1.0};
+  std::memcpy(out, v, sizeof(v));
+}
+
+}  // extern "C"
