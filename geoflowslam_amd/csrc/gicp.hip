@@ -1500,9 +1500,9 @@ __global__ __launch_bounds__(128) void k_knn_cov(const double4* __restrict__ pts
   // here it would stall the other 63 lanes of its wave (and ~70 % of the waves hold such a lane), so it is deferred.
   if (!certified) {
     const int slot = atomicAdd(&ginfo_rw[8 * c + 7], 1);
-    hard_list[(size_t)c * P + slot] = (unsigned)i;
+    hard_list[(size_t)c * 2 * P + slot] = (unsigned)i;
     // k candidates already known: the true k nearest lie within this distance (bounds the follow-up probe)
-    hard_d[(size_t)c * P + slot] = kth_for_deferred;
+    hard_d[(size_t)c * 2 * P + slot] = kth_for_deferred;
     return;
   }
   TopK<10> res;  // the neighbours in key order (distance, then index)
@@ -1526,6 +1526,9 @@ __global__ __launch_bounds__(128) void k_knn_cov(const double4* __restrict__ pts
 // Two passes: <16, 2, true> takes k_knn_cov's list (front of hard_list, counter ginfo[7]) with one r = 2 probe and
 // defers the really isolated points (~1 % of the list, but thousands of candidates each) to <64, 4, false>
 // (back of hard_list, counter far2_count) so that they do not hold up the other queries of their workgroup.
+// hard_list / hard_d hold 2 P slots a cloud, the first list in the lower half, the second from the top of the upper half down: in a
+// sparse cloud EVERY point is on both lists (one buffer of P slots let the second list overwrite unread entries of the first as
+// soon as the two held more than P queries together: wrong neighbours for those, tests/test_gpu_gicp_geometry.py).
 // (three waves a SIMD: left alone the kernel takes 205 VGPRs = two waves, and it waits on dependent cell lookups — 1.24 -> 0.99 ms
 // per 1 024 clouds with the cap, a 124-byte spill included; four waves: no further gain)
 template <int LANES, int R0, bool DEFER>
@@ -1550,8 +1553,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))) voi
   const double4* p = pts + (size_t)c * P;
   const u64* uc = ucell + (size_t)c * (P + 1);
   const unsigned* ub = ubegin + (size_t)c * (P + 1);
-  unsigned* list = hard_list + (size_t)c * P;
-  double* list_d = hard_d + (size_t)c * P;
+  unsigned* list = hard_list + (size_t)c * 2 * P;
+  double* list_d = hard_d + (size_t)c * 2 * P;
   const int nu = n_ucell[c];
   const int nhard = DEFER ? gi[7] : far2_count[c];
   const int kk = min(prm.k_neighbors, 10);
@@ -1563,9 +1566,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))) voi
     const int h = base + grp;
     if (gl == 0) s_query[grp] = -1;
     if (h < nhard) {
-      const int i = (int)(DEFER ? list[h] : list[P - 1 - h]);
+      const int i = (int)(DEFER ? list[h] : list[2 * P - 1 - h]);
       // squared distance within which the k nearest are known to lie (k_knn_cov found k candidates), or "infinite"
-      const double Dk = DEFER ? list_d[h] : list_d[P - 1 - h];
+      const double Dk = DEFER ? list_d[h] : list_d[2 * P - 1 - h];
       const bool bounded = Dk < 1.0e300;
       const double4 q = p[i];
       const int cx = fast_floor_d(q.x * prm.inv_cell) + kCoordOffset, cy = fast_floor_d(q.y * prm.inv_cell) + kCoordOffset,
@@ -1660,8 +1663,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))) voi
           s_query[grp] = i;
         } else {
           const int slot = atomicAdd(&far2_count[c], 1);
-          list[P - 1 - slot] = (unsigned)i;
-          list_d[P - 1 - slot] = Dnext;
+          list[2 * P - 1 - slot] = (unsigned)i;
+          list_d[2 * P - 1 - slot] = Dnext;
         }
       }
     }
@@ -1711,8 +1714,8 @@ __global__ __launch_bounds__(256) void k_knn_cov_far_wg(const double4* __restric
   const double4* p = pts + (size_t)c * P;
   const u64* uc = ucell + (size_t)c * (P + 1);
   const unsigned* ub = ubegin + (size_t)c * (P + 1);
-  const unsigned* list = hard_list + (size_t)c * P;
-  const double* list_d = hard_d + (size_t)c * P;
+  const unsigned* list = hard_list + (size_t)c * 2 * P;
+  const double* list_d = hard_d + (size_t)c * 2 * P;
   const int nu = n_ucell[c];
   const int nhard = far2_count[c];
   const int kk = min(prm.k_neighbors, 10);
@@ -1721,8 +1724,8 @@ __global__ __launch_bounds__(256) void k_knn_cov_far_wg(const double4* __restric
             bz1 = bbox[6 * c + 5];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   for (int h = chunk; h < nhard; h += nchunks) {  // uniform per workgroup
-    const int i = (int)list[P - 1 - h];
-    double Dk = list_d[P - 1 - h];
+    const int i = (int)list[2 * P - 1 - h];
+    double Dk = list_d[2 * P - 1 - h];
     const double4 q = p[i];
     const int cx = fast_floor_d(q.x * prm.inv_cell) + kCoordOffset, cy = fast_floor_d(q.y * prm.inv_cell) + kCoordOffset,
               cz = fast_floor_d(q.z * prm.inv_cell) + kCoordOffset;
@@ -3383,9 +3386,10 @@ struct gfs_gicp {
   hipStream_t stream;
   std::recursive_mutex mu;  // the host-pointer entries hold it across staging upload + run
   gfs::DevBuf<float4> d_in_t, d_in_s;  // staging for the host-pointer entry
-  gfs::DevBuf<unsigned> d_hard;  // per cloud: indices of the points k_knn_cov deferred to k_knn_cov_far
+  gfs::DevBuf<unsigned> d_hard;  // per cloud, 2 P slots: indices of the points k_knn_cov deferred to k_knn_cov_far (from slot 0 up)
   gfs::DevBuf<double> d_hard_d;  // ... and the squared distance bounding their k nearest (same slots)
-  gfs::DevBuf<int> d_far2;  // per cloud: number of points deferred a second time (stored from the back of d_hard)
+  gfs::DevBuf<int> d_far2;  // per cloud: number of points deferred a second time (stored from slot 2 P - 1 of d_hard down: each list
+                            // can hold every point of the cloud, as in a sparse cloud both do)
   gfs::DevBuf<int> d_nt, d_ns, d_counts, d_which, d_m, d_which2, d_nucell, d_tgt_index, d_ndone, d_bbox, d_ginfo, d_kinfo1, d_kinfo2;
   gfs::DevBuf<u64> d_keys0, d_keys1, d_ck0, d_ck1, d_ucell;
   gfs::DevBuf<unsigned> d_val0, d_val1, d_ci0, d_ci1, d_ubegin, d_grid;
@@ -3591,8 +3595,8 @@ int gfs_gicp_create(int device, int max_points, int max_batch, gfs_gicp** out) {
   A(h->d_nucell.alloc(C2));
   A(h->d_bbox.alloc(C2 * 6));
   A(h->d_ginfo.alloc(C2 * 8));
-  A(h->d_hard.alloc((size_t)C2 * P));
-  A(h->d_hard_d.alloc((size_t)C2 * P));
+  A(h->d_hard.alloc((size_t)C2 * 2 * P));
+  A(h->d_hard_d.alloc((size_t)C2 * 2 * P));
   A(h->d_far2.alloc(C2));
   A(h->d_kinfo1.alloc(C2 * 8));
   A(h->d_kinfo2.alloc(C2 * 8));
@@ -4073,7 +4077,7 @@ int gfs_gicp_knn_stats(gfs_gicp* h, int b, int which, int out[3], double* dk, in
   const int n = std::min(out[2], cap);
   if (dk && n > 0) {
     std::vector<double> t((size_t)n);
-    GFS_HIP(hipMemcpy(t.data(), h->d_hard_d.p + (size_t)c * h->P + (h->P - n), (size_t)n * 8, hipMemcpyDeviceToHost));
+    GFS_HIP(hipMemcpy(t.data(), h->d_hard_d.p + (size_t)c * 2 * h->P + (2 * h->P - n), (size_t)n * 8, hipMemcpyDeviceToHost));
     for (int k = 0; k < n; k++) dk[k] = t[(size_t)(n - 1 - k)];
   }
   return GFS_OK;

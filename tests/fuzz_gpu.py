@@ -3,7 +3,8 @@
 voxel-sort permutations (random / tied / raster-like / adversarial keys, 1 .. 50 000 elements) bit-exact, GICP on random cloud
 pairs (sizes, truncations, motions) with equal iteration / inlier counts and the pose within the 1e-5 bar (the largest error is
 printed), ORB on odd image sizes / feature counts / level counts bit-exact, LocalBundleAdjustment windows of random size with
-and without second-camera edges, mixed LBA batches and ragged GICP batches bit for bit against single calls.  Exit code 1 on any failure.  Round 2: 900 k sorts, 13 000 GICP pairs (without a tie at the 10th neighbour the pose agrees to
+and without second-camera edges, mixed LBA batches and ragged GICP batches bit for bit against single calls, the GICP neighbour
+searches on non-camera clouds (section 8: brute-force covariances and the pass that answered).  Exit code 1 on any failure.  Round 2: 900 k sorts, 13 000 GICP pairs (without a tie at the 10th neighbour the pose agrees to
 1e-16; with one — noise-free raster clouds have one or two per cloud — 7 pairs over the 1e-5 bar), 2 200 ORB frames, 3 000 LBA windows, ~1 200 each of
 SearchByProjection / PoseOptimization / BF match / fbKltTracking / findFundamentalMat, 1 055 mixed LBA batches and 2 966 ragged GICP batches (device entry) against single calls: no failure; the total
 LM iteration count of PoseOptimization differs by one in ~5 % of the frames (poses equal to 1e-10)."""
@@ -24,7 +25,7 @@ def case_rng(section, index):  # a case's draws depend on (seed, section, index)
     return np.random.default_rng([1234 + seed0, section, index])
 
 
-SECTIONS = [int(v) for v in os.environ.get("FUZZ_SECTIONS", "1,2,3,4,5,6,7").split(",")]  # e.g. FUZZ_SECTIONS=2: cloud pairs only
+SECTIONS = [int(v) for v in os.environ.get("FUZZ_SECTIONS", "1,2,3,4,5,6,7,8").split(",")]  # e.g. FUZZ_SECTIONS=2: cloud pairs only
 ONLY = None  # "section:index" as the third argument replays one case
 if len(sys.argv) > 3:
     ONLY = tuple(int(v) for v in sys.argv[3].split(":"))
@@ -308,5 +309,57 @@ if 7 in SECTIONS and ONLY is None:
         hip.free()
         hip = _Hip()
 print("gicp batches", nb7, "fails", len(fails), flush=True)
+# ---- 8. the neighbour searches on clouds that are not depth-camera rasters (tests/gicp_geometry_support.py, random parameters: density,
+# extent, offsets up to +-50 m, 1 .. 8 000 points, a handle no larger than the cloud): voxel means bit for bit, covariances against
+# the brute force and the oracle, and the pass that answered (gfs_gicp_knn_stats) against what the true k-th distances allow --
+# checks (a) and (c) of tests/test_gpu_gicp_geometry.py.  Replay: python tests/fuzz_gpu.py 0 <seed> 8:<index>
+n8 = 0
+own8 = np.zeros(3, np.int64)
+if 8 in SECTIONS and (ONLY is None or ONLY[0] == 8):
+    import gicp_geometry_support as GS
+    T4 = time.time()
+    base8 = [n for n in GS.NAMES if not n.startswith("tiny_")]
+    while (ONLY is None and time.time() - T4 < budget * (0.15 if SECTIONS != [8] else 1.0)) or (ONLY is not None and n8 == 0):
+        ci = n8 if ONLY is None else ONLY[1]
+        rng = case_rng(8, ci)
+        n8 += 1
+        name = str(rng.choice(base8))
+        kw = dict(scale=float(np.exp(rng.uniform(np.log(0.4), np.log(2.5)))), offset=rng.uniform(-50, 50, 3) * int(rng.integers(0, 2)))
+        if name not in ("wall_and_cell_faces", "far_from_origin"):
+            kw["n"] = int(rng.choice([rng.integers(1, 30), rng.integers(30, 1500), rng.integers(1500, 8001)]))
+        c = GS.cloud(name, int(rng.integers(0, 1 << 30)), **kw)
+        if rng.integers(0, 3) == 0:
+            c = c[np.sort(rng.permutation(len(c))[:max(1, int(len(c) * rng.uniform(0.02, 1.0)))])]
+        tag = ("case 8:%d" % ci, name, len(c))
+        try:
+            f = GS.facts_of(c)
+            pc = GS.path_counts(f)
+            r8 = api.RegistrationGICP(max_points=len(c))
+            r8.RegisterPointClouds(c, c)
+            pts, cov = r8.preprocessed(0, 0)
+            m, to_r2, to_iso = (int(v) for v in r8.knn_stats(0, 0)[0])
+            r8.close()
+            ig, io = GS.lexorder(pts), GS.lexorder(f["po"])
+            if len(pts) != len(f["po"]) or not (pts[ig] == f["po"][io]).all():
+                fails.append(("geometry-voxel-means",) + tag)
+                continue
+            cg = np.zeros_like(cov)
+            cg[io] = cov[ig]
+            good = f["good"] if m >= 5 else ~f["tie"]
+            if good.any():
+                d_ref = np.abs(cg - f["ref"]).reshape(m, -1).max(1)[good].max()
+                d_or = np.abs(cg - f["co"]).reshape(m, -1).max(1)[good].max()
+                if not (d_ref <= 1e-9 + f["d_or_cov"] and d_or < 1e-9):
+                    fails.append(("geometry-cov",) + tag + (float(d_ref), float(d_or), f["d_or_cov"]))
+            on_cell = int((np.abs(f["d10"] - GS.CELL) <= 1e-9 * GS.CELL).sum())  # (undecided by the brute force: either side is right)
+            ok = 0 <= to_iso <= to_r2 <= m == pc["m"] and to_r2 <= pc["beyond_cell"] + pc["near_ties"] + on_cell
+            if (f["extent"] > 0.5).any():
+                ok = ok and to_r2 >= pc["must_r2"] and to_iso >= pc["must_isolated"]
+            if not ok:
+                fails.append(("geometry-path",) + tag + ((m, to_r2, to_iso), pc))
+            own8 += [m - to_r2, to_r2 - to_iso, to_iso]
+        except Exception as e:
+            fails.append(("geometry-exc",) + tag + (repr(e)[:200],))
+print("geometry clouds", n8, "points by pass (certified, r = 2, isolated)", own8.tolist(), "fails", len(fails), flush=True)
 for f in fails[:40]: print("FAIL", f)
 sys.exit(1 if fails else 0)

@@ -495,6 +495,8 @@ def test_random_pairs_meet_the_bar_or_have_a_proved_kth_distance_tie(gpu_api, or
             raise AssertionError(("still over the bar with every tie broken", ci))
         ties.append((ci, _rel(r["T"], ro["T"]), n_ties))
     pool.shutdown()
+    print(f"pairs that took the tie path: {len(ties)} of 2000 (pose error before the ties were broken: "
+          f"{max((e for _, e, _ in ties), default=0.0):.2e} at worst); worst pose error of the other pairs: {worst:.2e}")
     assert len(ties) <= 40, ties  # round 2 measured 7 of 13 000
     assert worst < 1e-5
 
