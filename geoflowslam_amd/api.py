@@ -208,6 +208,19 @@ class PoseLidarSolution(C.Structure):
                 ("round_edges", C.c_int32 * 4), ("round_chi2", C.c_float * 4), ("round_valid", C.c_int32 * 4)]
 
 
+class LidarMapInput(C.Structure):
+    _fields_ = [("n_keyframes", C.c_int32), ("q", C.c_void_p), ("t", C.c_void_p), ("cloud_begin", C.c_void_p), ("cloud", C.c_void_p),
+                ("leaf", C.c_float)]
+
+
+class LidarMapInfo(C.Structure):
+    _fields_ = [("n_in", C.c_int32), ("n_out", C.c_int32), ("passthrough", C.c_int32), ("div", C.c_int32 * 3)]
+
+
+def lidar_map_info(I):
+    return dict(n_in=int(I.n_in), n_out=int(I.n_out), passthrough=int(I.passthrough), div=tuple(int(v) for v in I.div))
+
+
 def pose_lidar_structs(prob, map_handle=None):
     """ctypes views of one PoseLidarVisualOptimization problem dict (shared with the CPU restatement's tests: same layout).
     prob: q, t (float Tcw), xw, obs, inv_sigma2, stereo, fx, fy, cx, cy, bf, cloud [n][3], n_iterations (+ optional
@@ -263,6 +276,8 @@ ABI_SYMBOLS = [
     "gfs_frame_create", "gfs_frame_destroy", "gfs_depth_to_cloud", "gfs_depth_to_cloud_batch_device", "gfs_depth_convert_u16_batch_device", "gfs_stereo_from_rgbd",
     "gfs_stereo_from_rgbd_batch_device",
     "gfs_pose_create", "gfs_pose_destroy", "gfs_pose_optimize", "gfs_pose_set_sum_order",
+    "gfs_lidar_mapper_create", "gfs_lidar_mapper_destroy", "gfs_lidar_map_build", "gfs_lidar_map_fetch", "gfs_voxel_grid_filter",
+    "gfs_test_lidar_map_grid",
     "gfs_lidar_map_create", "gfs_lidar_map_set", "gfs_lidar_map_destroy", "gfs_pose_lidar_create", "gfs_pose_lidar_destroy",
     "gfs_pose_lidar_set_sum_order", "gfs_pose_lidar_optimize", "gfs_pose_lidar_fetch_edges",
     "gfs_gms_create", "gfs_gms_destroy", "gfs_gms_inlier_mask", "gfs_gms_inlier_mask_batch_device",
@@ -339,6 +354,13 @@ def lib():
             L.gfs_lba_linearize_lidar.argtypes = [vp, C.POINTER(LbaProblem), C.POINTER(LbaLidar), vp, vp, vp, vp, vp, vp,
                                                   C.POINTER(C.c_double), vp, i, vp]
             L.gfs_lba_fetch_lidar_edges.argtypes = [vp, i, vp, vp, vp, i, vp]
+        if hasattr(L, "gfs_lidar_map_build"):
+            L.gfs_lidar_mapper_create.argtypes = [i, i, i, C.POINTER(vp)]
+            L.gfs_lidar_mapper_destroy.argtypes = [vp]
+            L.gfs_lidar_map_build.argtypes = [vp, C.POINTER(LidarMapInput), vp, C.POINTER(LidarMapInfo)]
+            L.gfs_lidar_map_fetch.argtypes = [vp, vp, i, C.POINTER(C.c_int32)]
+            L.gfs_voxel_grid_filter.argtypes = [vp, vp, i, C.c_float, vp, i, C.POINTER(LidarMapInfo)]
+            L.gfs_test_lidar_map_grid.argtypes = [vp, vp, i, vp, vp, i, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         if hasattr(L, "gfs_frame_create"):
             f = C.c_float
             L.gfs_frame_create.argtypes = [i, i, i, i, C.POINTER(vp)]
@@ -1199,9 +1221,62 @@ class LidarMap:
         _check(lib().gfs_lidar_map_set(self.h, _p(xyz), len(xyz)), "gfs_lidar_map_set")
         return self
 
+    def fetch(self):
+        """The map's points in map-index order (LidarMapping::GetLocalMap), float32 [n][3]."""
+        n = C.c_int32()
+        _check(lib().gfs_lidar_map_fetch(self.h, None, 0, C.byref(n)), "gfs_lidar_map_fetch")
+        xyz = np.zeros((max(n.value, 1), 3), np.float32)
+        _check(lib().gfs_lidar_map_fetch(self.h, _p(xyz), n.value, C.byref(n)), "gfs_lidar_map_fetch")
+        return xyz[:n.value].copy()
+
     def close(self):
         if getattr(self, "h", None) and _lib is not None:
             _lib.gfs_lidar_map_destroy(self.h)
+        self.h = None
+
+    __del__ = close
+
+
+class LidarMapper:
+    """The local map of LidarMapping::viewer (reference src/LidarMapping.cc:130-185) built on the device: the key-frames' clouds
+    transformed by their poses, concatenated, voxel-filtered under the rule of DESIGN.md section 11 and laid out in the search grid of
+    a LidarMap (gfs_lidar_mapper_* / gfs_lidar_map_build in include/gfs_abi.h)."""
+
+    def __init__(self, max_points_in=131072, max_keyframes=30, device=0):
+        self.h = C.c_void_p()
+        self.max_points_in = max_points_in
+        _check(lib().gfs_lidar_mapper_create(device, max_points_in, max_keyframes, C.byref(self.h)), "gfs_lidar_mapper_create")
+
+    def build(self, lidar_map, q, t, clouds, leaf):
+        """q [K][4], t [K][3]: the key-frames' stored Tcw; clouds: K arrays [n_k][3] (camera frame; empty ones allowed); leaf:
+        LidarMapping.LocalResolution.  Fills lidar_map; -> info dict (n_in, n_out, passthrough, div).  A refused build raises and leaves
+        lidar_map as it was."""
+        q = np.ascontiguousarray(q, np.float32).reshape(-1, 4)
+        t = np.ascontiguousarray(t, np.float32).reshape(-1, 3)
+        clouds = [np.asarray(c, np.float32).reshape(-1, 3) for c in clouds]
+        if not (len(q) == len(t) == len(clouds)):
+            raise ValueError("LidarMapper.build: q, t and clouds differ in length")
+        cb = np.r_[0, np.cumsum([len(c) for c in clouds])].astype(np.int32)
+        cloud = np.ascontiguousarray(np.concatenate(clouds) if clouds else np.zeros((0, 3)), np.float32).reshape(-1, 3)
+        I = LidarMapInput(len(q), q.ctypes.data, t.ctypes.data, cb.ctypes.data, cloud.ctypes.data, float(np.float32(leaf)))
+        info = LidarMapInfo()
+        self.last_info = info
+        _check(lib().gfs_lidar_map_build(self.h, C.byref(I), lidar_map.h, C.byref(info)), "gfs_lidar_map_build")
+        return lidar_map_info(info)
+
+    def voxel_filter(self, xyz, leaf, cap=None):
+        """pcl::VoxelGrid (default settings) of one cloud under the same rule -> (xyz [n_out][3] float32, info)."""
+        xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        cap = len(xyz) if cap is None else cap
+        out, info = np.zeros((max(cap, 1), 3), np.float32), LidarMapInfo()
+        self.last_info = info
+        _check(lib().gfs_voxel_grid_filter(self.h, _p(xyz), len(xyz), float(np.float32(leaf)), _p(out), cap, C.byref(info)),
+               "gfs_voxel_grid_filter")
+        return out[:info.n_out].copy(), lidar_map_info(info)
+
+    def close(self):
+        if getattr(self, "h", None) and _lib is not None:
+            _lib.gfs_lidar_mapper_destroy(self.h)
         self.h = None
 
     __del__ = close

@@ -20,6 +20,7 @@
 #include <cstdint>
 #include <list>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <set>
 #include <stdexcept>
@@ -143,6 +144,83 @@ class RegistrationGICP {
   gfs_gicp* h_ = nullptr;
 };
 
+// ------------------------------------------------------------------------------------------------------------------------
+// LidarMapping::viewer's loop body (reference src/LidarMapping.cc:162-182): localMap is cleared, every key-frame of lNewKeyFrames
+// (mlNewKeyFrames, at most 30: insertKeyFrame :72-80) that is not bad and has an mpPointCloudDownsampled is transformed by
+// toMatrix4d(GetPoseInverse()) and appended, and voxel_local filters the sum at LidarMapping.LocalResolution.  The gather is host code;
+// transform, filter and search grid run on the device (gfs_lidar_map_build) and land in a gfs_lidar_map the optimizers use as it is.
+// The key-frames are read through an access type (no PCL / Sophus here) with static members
+//     bool is_bad(const KeyFrame*);                          // pKF->isBad()
+//     const float* cloud(const KeyFrame*, int* n);           // mpPointCloudDownsampled packed to [n][3] floats; nullptr = no cloud
+//     void get_pose(const KeyFrame*, float q[4], float t[3]);   // GetPose(): unit_quaternion() (x, y, z, w), translation()
+// ------------------------------------------------------------------------------------------------------------------------
+struct LidarMapFlat {  // the key-frames that reach transformPointCloud, in list order
+  std::vector<float> q, t, cloud;
+  std::vector<int32_t> cloud_begin;
+  int n_keyframes() const { return (int)cloud_begin.size() - 1; }
+};
+
+template <class Access, class It>
+void GatherLidarKeyFrames(It first, It last, LidarMapFlat& f) {
+  f.q.clear();
+  f.t.clear();
+  f.cloud.clear();
+  f.cloud_begin.assign(1, 0);
+  for (It it = first; it != last; ++it) {
+    const auto* pKF = &**it;
+    if (Access::is_bad(pKF)) continue;  // :164
+    int n = 0;
+    const float* c = Access::cloud(pKF, &n);
+    if (!c) continue;  // :165
+    if (n < 0) n = 0;
+    float q[4], t[3];
+    Access::get_pose(pKF, q, t);
+    f.q.insert(f.q.end(), q, q + 4);
+    f.t.insert(f.t.end(), t, t + 3);
+    f.cloud.insert(f.cloud.end(), c, c + 3 * (size_t)n);
+    f.cloud_begin.push_back(f.cloud_begin.back() + n);
+  }
+}
+
+class LidarLocalMapper {
+ public:
+  LidarLocalMapper(int max_points_in = 262144, int max_keyframes = 30, int device = 0) {
+    check(gfs_lidar_mapper_create(device, max_points_in, max_keyframes, &h_), "gfs_lidar_mapper_create");
+  }
+  ~LidarLocalMapper() { gfs_lidar_mapper_destroy(h_); }
+  LidarLocalMapper(const LidarLocalMapper&) = delete;
+  LidarLocalMapper& operator=(const LidarLocalMapper&) = delete;
+  // [first, last): lNewKeyFrames (iterators to KeyFrame*); resolution: LidarMapping.LocalResolution.  Throws on a refusal (the map
+  // then keeps what it held).
+  template <class Access, class It>
+  gfs_lidar_map_info Update(It first, It last, float resolution, gfs_lidar_map* map) {
+    GatherLidarKeyFrames<Access>(first, last, flat_);
+    gfs_lidar_map_input in{};
+    in.n_keyframes = flat_.n_keyframes();
+    in.q = flat_.q.data();
+    in.t = flat_.t.data();
+    in.cloud_begin = flat_.cloud_begin.data();
+    in.cloud = flat_.cloud.data();
+    in.leaf = resolution;
+    gfs_lidar_map_info info{};
+    check(gfs_lidar_map_build(h_, &in, map, &info), "gfs_lidar_map_build");
+    return info;
+  }
+  // pcl::VoxelGrid (default settings) with leaf size `leaf` on one cloud -> out ([n][3] at most; resized to the result)
+  gfs_lidar_map_info VoxelFilter(const float* xyz, int n, float leaf, std::vector<float>& out) {
+    out.resize(3 * (size_t)n);
+    gfs_lidar_map_info info{};
+    check(gfs_voxel_grid_filter(h_, xyz, n, leaf, out.data(), n, &info), "gfs_voxel_grid_filter");
+    out.resize(3 * (size_t)info.n_out);
+    return info;
+  }
+  const LidarMapFlat& gathered() const { return flat_; }
+
+ private:
+  gfs_lidar_mapper* h_ = nullptr;
+  LidarMapFlat flat_;
+};
+
 // numeric core of Optimizer::LocalBundleAdjustment (reference include/Optimizer.h:62-65)
 class LocalBundleAdjuster {
  public:
@@ -189,10 +267,27 @@ class LocalBundleAdjuster {
   template <class Access, class KeyFrame, class Map>
   void LocalVisualLidarBA(KeyFrame* pKF, const float* map_xyz, int n_map, bool* pbStopFlag, Map* pMap, int& num_fixedKF,
                           int& num_OptKF, int& num_MPs, int& num_edges);
+  // The owned local map built on the device from lNewKeyFrames (LidarLocalMapper::Update) instead of uploaded: what
+  // mpLidarMapping->GetLocalMap() would have returned (src/LocalMapping.cc:216, 235).  max_map_points: the map's capacity.
+  template <class Access, class It>
+  gfs_lidar_map_info BuildLocalMap(It first, It last, float resolution, int max_map_points = 262144) {
+    if (!map_ || max_map_points > map_cap_) {
+      gfs_lidar_map_destroy(map_);
+      map_ = nullptr;
+      map_cap_ = std::max(max_map_points, 5);
+      check(gfs_lidar_map_create(device_, map_cap_, &map_), "gfs_lidar_map_create");
+    }
+    if (!mapper_) mapper_.reset(new LidarLocalMapper(map_cap_, 30, device_));
+    return mapper_->template Update<Access>(first, last, resolution, map_);
+  }
+  // LocalVisualLidarBA on the map BuildLocalMap left
+  template <class Access, class KeyFrame, class Map>
+  void LocalVisualLidarBA(KeyFrame* pKF, bool* pbStopFlag, Map* pMap, int& num_fixedKF, int& num_OptKF, int& num_MPs, int& num_edges);
 
  private:
   gfs_lba* h_ = nullptr;
   int device_ = 0;
+  std::unique_ptr<LidarLocalMapper> mapper_;  // created at the first BuildLocalMap
   gfs_lidar_map* map_ = nullptr;  // created at the first LocalVisualLidarBA
   int map_cap_ = 0, lidar_cap_ = 0;
 };
@@ -511,6 +606,18 @@ void LocalBundleAdjuster::LocalVisualLidarBA(KeyFrame* pKF, const float* map_xyz
       pKF, pbStopFlag, pMap, num_fixedKF, num_OptKF, num_MPs, num_edges);
 }
 
+template <class Access, class KeyFrame, class Map>
+void LocalBundleAdjuster::LocalVisualLidarBA(KeyFrame* pKF, bool* pbStopFlag, Map* pMap, int& num_fixedKF, int& num_OptKF, int& num_MPs,
+                                             int& num_edges) {
+  using MapPoint = typename std::remove_pointer<typename decltype(pKF->GetMapPointMatches())::value_type>::type;
+  if (!map_) throw std::runtime_error("LocalVisualLidarBA: no local map (BuildLocalMap first)");
+  gfs_host::LocalVisualLidarBA<Access, KeyFrame, MapPoint, Map>(
+      [this](const gfs_lba_problem& p, const gfs_lba_lidar& lidar, gfs_lba_solution& s, const bool* stop) {
+        return this->solve_lidar(p, lidar, s, stop);
+      },
+      pKF, pbStopFlag, pMap, num_fixedKF, num_OptKF, num_MPs, num_edges);
+}
+
 // gms_matcher(kp1, size1, kp2, size2, matches).GetInlierMask(mask, false, false) (reference Thirdparty/GMS/include/gms_matcher.h;
 // the filter SearchWithGMS applies to the brute-force matches, src/ORBmatcher.cc:761-762)
 class GmsMatcher {
@@ -815,7 +922,7 @@ class PoseOptimizer {
 // (mpPointCloudDownsampled) is passed as xyz floats.  Writes back mvbOutlier, the pose (SetPose) and the two out-parameters.
 class PoseLidarOptimizer {
  public:
-  PoseLidarOptimizer(int max_obs = 8192, int max_cloud = 16384, int max_map = 262144, int device = 0) {
+  PoseLidarOptimizer(int max_obs = 8192, int max_cloud = 16384, int max_map = 262144, int device = 0) : max_map_(max_map), device_(device) {
     check(gfs_pose_lidar_create(device, max_obs, max_cloud, 1, &h_), "gfs_pose_lidar_create");
     const int rc = gfs_lidar_map_create(device, max_map, &map_);
     if (rc) {
@@ -830,6 +937,12 @@ class PoseLidarOptimizer {
   PoseLidarOptimizer(const PoseLidarOptimizer&) = delete;
   PoseLidarOptimizer& operator=(const PoseLidarOptimizer&) = delete;
   void SetLocalMap(const float* xyz, int n) { check(gfs_lidar_map_set(map_, xyz, n), "gfs_lidar_map_set"); }
+  // The local map built on the device from lNewKeyFrames (LidarLocalMapper::Update) instead of uploaded
+  template <class Access, class It>
+  gfs_lidar_map_info BuildLocalMap(It first, It last, float resolution) {
+    if (!mapper_) mapper_.reset(new LidarLocalMapper(max_map_, 30, device_));
+    return mapper_->template Update<Access>(first, last, resolution, map_);
+  }
 
   template <class Access, class F>
   int PoseLidarVisualOptimization(F* frame, const float* cloud_xyz, int n_cloud, int nIterations, int& nLidarInliers, float& residual) {
@@ -892,6 +1005,8 @@ class PoseLidarOptimizer {
  private:
   gfs_pose_lidar* h_ = nullptr;
   gfs_lidar_map* map_ = nullptr;
+  int max_map_ = 0, device_ = 0;
+  std::unique_ptr<LidarLocalMapper> mapper_;  // created at the first BuildLocalMap
   std::vector<int> idx_;
   std::vector<double> xw_, obs_, chi2_;
   std::vector<float> w_;

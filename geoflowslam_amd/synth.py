@@ -570,3 +570,38 @@ def lba_lidar_window(seed, n_free=20, n_fixed=5, n_points=3000, n_cloud=3000, vo
     w.update(pose_local=local, matches_inliers=inl, cloud_begin=np.r_[0, np.cumsum([len(c) for c in clouds])].astype(np.int32),
              cloud=np.ascontiguousarray(np.concatenate(clouds), np.float32).reshape(-1, 3), map_xyz=map_xyz)
     return w
+
+
+def lidar_map_window(seed, n_keyframes=7, n_cloud=3000, width=160, height=120, trans=0.08, rot_deg=2.0, empty=(), around=None,
+                     quat_scale=None):
+    """Synthetic input of the lidar local-map build (LidarMapping::viewer, reference src/LidarMapping.cc:130-185): n_keyframes
+    key-frames along a random walk through a Scene (starting at the camera-to-world pose `around`, default a small random one), each
+    with its stored pose Tcw as a float quaternion (x, y, z, w) and translation, and its downsampled cloud rendered from that pose
+    (camera frame, about n_cloud points).
+      empty: key-frames whose cloud is empty;
+      quat_scale: [n_keyframes] factors on the stored quaternions (not exactly unit: SE3f's constructor normalises).
+    Returns q [K][4], t [K][3], clouds (list), cloud_begin [K + 1], cloud [n][3] (float32)."""
+    rng = np.random.default_rng(seed + 0x71D)
+    sc = Scene(seed)
+    T = random_motion(rng, trans=0.05, rot_deg=2.0) if around is None else np.array(around, np.float64)
+    q, t, clouds = [], [], []
+    for k in range(n_keyframes):
+        if k:
+            T = T @ random_motion(rng, trans, rot_deg)
+        Rcw, tcw = T[:3, :3].T, -T[:3, :3].T @ T[:3, 3]
+        qk = _quat_from_R(Rcw).astype(np.float32)
+        if quat_scale is not None:
+            qk = (qk * np.float32(quat_scale[k])).astype(np.float32)
+        q.append(qk)
+        t.append(tcw.astype(np.float32))
+        if k in empty:
+            clouds.append(np.zeros((0, 3), np.float32))
+            continue
+        _, d = sc.render(width, height, T, 400 + k)
+        c = depth_to_cloud(d, 1)[:, :3].astype(np.float32)
+        if len(c) > n_cloud:
+            c = c[np.sort(rng.choice(len(c), n_cloud, replace=False))]
+        clouds.append(np.ascontiguousarray(c, np.float32))
+    return dict(q=np.array(q, np.float32).reshape(-1, 4), t=np.array(t, np.float32).reshape(-1, 3), clouds=clouds,
+                cloud_begin=np.r_[0, np.cumsum([len(c) for c in clouds])].astype(np.int32),
+                cloud=np.ascontiguousarray(np.concatenate(clouds), np.float32).reshape(-1, 3))

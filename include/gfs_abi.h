@@ -606,6 +606,40 @@ int gfs_lidar_map_create(int device, int max_points, gfs_lidar_map** out);
 int gfs_lidar_map_set(gfs_lidar_map* map, const float* xyz /* [n][3] */, int n);
 void gfs_lidar_map_destroy(gfs_lidar_map* map);
 
+/* The local map built on the device -- LidarMapping::viewer's loop body (src/LidarMapping.cc:162-182): the key-frames that reach
+ * transformPointCloud (:107-127), each cloud moved by toMatrix4d(Tcw.inverse()), concatenated, pcl::VoxelGrid at
+ * LidarMapping.LocalResolution, and the search grid gfs_lidar_map_set would build -- straight into a gfs_lidar_map that
+ * gfs_pose_lidar_optimize and gfs_lba_solve_lidar use unchanged.  DESIGN.md section 11 states the filter's rule (index, order,
+ * float centroid).  In every refusal nothing is truncated and the map keeps its previous content:
+ *   points beyond the mapper's capacity, map points beyond map->max_points or cap      GFS_ERR_CAPACITY
+ *   map on another device; a transformed point not finite or not within 1e6 m; fewer than 5 map points (a build over zero points
+ *   included); leaf not positive and finite                                            GFS_ERR_INVALID_ARG
+ *   the filter's index range beyond int (where PCL's int arithmetic would overflow)    GFS_ERR_UNSUPPORTED */
+typedef struct gfs_lidar_mapper gfs_lidar_mapper;
+int gfs_lidar_mapper_create(int device, int max_points_in, int max_keyframes, gfs_lidar_mapper** out);
+void gfs_lidar_mapper_destroy(gfs_lidar_mapper* h);
+
+typedef struct {
+  int32_t n_keyframes;        /* the key-frames that reach transformPointCloud, in mlNewKeyFrames order */
+  const float* q;             /* [n_keyframes][4] Tcw as stored (x, y, z, w) */
+  const float* t;             /* [n_keyframes][3] */
+  const int32_t* cloud_begin; /* [n_keyframes + 1] */
+  const float* cloud;         /* [cloud_begin[n_keyframes]][3] mpPointCloudDownsampled, camera frame */
+  float leaf;                 /* (float) LidarMapping.LocalResolution */
+} gfs_lidar_map_input;
+typedef struct {
+  int32_t n_in, n_out, passthrough; /* passthrough: the filter returned its input (PCL's "leaf size is too small") */
+  int32_t div[3];                   /* the filter's grid (0 when passed through) */
+} gfs_lidar_map_info;
+
+int gfs_lidar_map_build(gfs_lidar_mapper* h, const gfs_lidar_map_input* in, gfs_lidar_map* map, gfs_lidar_map_info* info);
+/* The map's points in map-index order (GetLocalMap); *n = the map's size; up to cap points are written. */
+int gfs_lidar_map_fetch(const gfs_lidar_map* map, float* xyz /* [cap][3] */, int cap, int32_t* n);
+/* pcl::VoxelGrid under the same rule on one host cloud (n >= 1) -> host points (the filters of src/Frame.cc:388-390 and
+ * src/LidarProcess.cc are this filter). */
+int gfs_voxel_grid_filter(gfs_lidar_mapper* h, const float* xyz /* [n][3] */, int n, float leaf, float* out_xyz /* [cap][3] */, int cap,
+                          gfs_lidar_map_info* info);
+
 typedef struct {
   float q[4], t[3];           /* Tcw = pFrame->GetPose(): Sophus::SE3f unit quaternion (x, y, z, w) and translation, as stored */
   int32_t n_obs;              /* the visual observations, exactly as gfs_pose_problem */

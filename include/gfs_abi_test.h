@@ -39,6 +39,11 @@ int gfs_test_voxel_sort(gfs_gicp* h, const unsigned long long* keys, int n, unsi
  * (size, x) list, ORBextractor.cc:697-698) on n <= 1024 caller keys; perm_out[i] = original index of the element left at position i. */
 int gfs_test_wave_std_sort(int device, const unsigned* keys, int n, unsigned short* perm_out);
 
+/* GPU test hook: a map's search grid as the association kernels read it -- the bucket offsets start[nb + 1] and the bucket-sorted
+ * points pts[n][3] with their map-index words index[n] (copied when the caps suffice); *nb, *n = the map's sizes. */
+int gfs_test_lidar_map_grid(const gfs_lidar_map* map, int32_t* start, int cap_start, float* pts, int32_t* index, int cap_pts, int32_t* nb,
+                            int32_t* n);
+
 #ifdef __cplusplus
 }
 #endif
