@@ -576,17 +576,6 @@ constexpr int kMk = 256;  // threads per workgroup of the wide kernels
 
 __device__ __forceinline__ double* sel(double* a, double* b, int which) { return which ? b : a; }
 
-// deterministic 256-thread block sum: wave shuffle tree, then the four waves in order; result in every thread
-__device__ double block_sum256(double v, double* s4) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int ofs = 32; ofs > 0; ofs >>= 1) v += __shfl_down(v, ofs, 64);
-  __syncthreads();
-  if (lane == 0) s4[wave] = v;
-  __syncthreads();
-  return ((s4[0] + s4[1]) + s4[2]) + s4[3];
-}
-
 __device__ __forceinline__ void b_init(const LbaDev& D, const int bx, const int gdx) {
   const int g = bx * kMk + threadIdx.x, G = gdx * kMk;
   for (int i = g; i < D.n_poses; i += G) {
@@ -635,7 +624,7 @@ __device__ __forceinline__ void b_lidar_errors(const LbaDev& D, const int k, con
     huber(c, D.l_huber, &r0, &r1);
     local += r0;
   }
-  const double tot = block_sum256(local, s4);
+  const double tot = gfs_red::block_sum256(local, s4);
   if (threadIdx.x == 0) D.part_chi[k] = tot;
 }
 
@@ -667,7 +656,7 @@ __device__ __forceinline__ void b_errors(const LbaDev& D, const int bx, const in
     huber(c, D.e_stereo[e] ? D.huber_stereo : D.huber_mono, &r0, &r1);
     local = r0;
   }
-  const double tot = block_sum256(local, s4);
+  const double tot = gfs_red::block_sum256(local, s4);
   if (threadIdx.x == 0) D.part_chi[bx] = tot;
 }
 // gate = 1 (k_lba_errors / build_landmarks / build_poses / begin): a launch queued speculatively behind k_lba_decide -- it runs only if that
@@ -1697,7 +1686,7 @@ __device__ __forceinline__ void b_update(const LbaDev& D, const int bx, const in
       }
     }
   }
-  const double tot = block_sum256(loc, s4);
+  const double tot = gfs_red::block_sum256(loc, s4);
   if (threadIdx.x == 0) D.part_scale[bx] = tot;
 }
 __global__ __launch_bounds__(kMk) void k_lba_update(LbaDev D, int gate) {

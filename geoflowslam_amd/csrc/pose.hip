@@ -1,34 +1,36 @@
 // Optimizer::PoseOptimization (reference src/Optimizer.cc:763-1098) on MI355X: motion-only bundle adjustment of a
 // batch of frames, conventional-SLAM branch (pFrame->mpCamera2 == nullptr).
 //
-// One 256-thread workgroup owns one frame and runs its whole schedule on the device: 4 rounds x optimize(10) of the
-// g2o Levenberg-Marquardt loop (core/optimization_algorithm_levenberg.cpp:61-168) over one VertexSE3Expmap with unary
-// edges (EdgeSE3ProjectXYZOnlyPose: src/OptimizableTypes.cpp:49-63; g2o::EdgeStereoSE3ProjectXYZOnlyPose:
-// Thirdparty/g2o/g2o/types/types_six_dof_expmap.cpp:339-404), Huber kernels, a dense 6x6 system solved with Eigen::LDLT
-// semantics (solvers/linear_solver_dense.h:64-112), and the outlier re-classification between rounds (:972-1073).
+// One 256-thread workgroup owns one frame and runs its whole schedule on the device: 4 rounds x optimize(10) of the g2o
+// Levenberg-Marquardt loop over one VertexSE3Expmap with unary mono / stereo edges and Huber kernels, and the outlier
+// re-classification between rounds (:972-1073).  This file holds the kernel's loops, the edges kept in registers and the fast oplus of
+// the tree mode; the bodies the loops call -- edge error and quadratic form, the 6x6 solves, the ordered sum, the LM bookkeeping, the
+// classification step -- are pose_lm_dev.hpp's, shared with pose_lidar.hip.
 // Edges are spread over the threads, but every sum over the edges -- activeRobustChi2 (core/sparse_optimizer.cpp:104-122) and
 // the 21 + 6 entries of the normal equations (core/base_unary_edge.hpp:43-72, one edge after the other into the vertex's
 // block) -- is added in g2o's order, the edge order: the threads park their terms in an LDS slab and one lane per quantity
 // adds them up sequentially.  Together with glibc's sin / cos / pow (glibc_math.hpp) every double of the solve has the bits
 // the sequential CPU restatement (oracle/pose_oracle.cpp) produces; the sign of a gain ratio at a converged state (one more LM
-// iteration or not) depends on exactly that.  The 2- / 3-term products of an edge are associated the way Eigen evaluates
-// base_unary_edge.hpp:62-63 -- (A' weightedOmega) A and ((rho1 A') Omega) e, left to right -- but no Eigen / g2o build exists in
-// this image to pin that against: "bit-identical" is a statement about the restatement, the bar against the reference is 1e-5.  The scalar LM bookkeeping runs on thread 0 and is broadcast through LDS.
-// Quirks kept: every round restarts from the frame's pose, chi2 values are compared as floats, nGood is never reset,
-// the stereo projection uses a float 1/z, and the optimised pose is returned but meant to be discarded.
+// iteration or not) depends on exactly that.  No Eigen / g2o build exists in this image to pin the association of an edge's products
+// against: "bit-identical" is a statement about the restatement, the bar against the reference is 1e-5.  The scalar LM bookkeeping
+// runs on thread 0 and is broadcast through LDS.
+// Quirks kept: every round restarts from the frame's pose, nGood is never reset, and the optimised pose is returned but meant to
+// be discarded.
 #include <memory>
 #include <mutex>
 
 #include "g2o_se3_dev.hpp"
 #include "gfs_common.hpp"
+#include "pose_lm_dev.hpp"
 #include "wave_reduce.hpp"
 
 using namespace gfs_se3;
+using namespace gfs_pose_lm;
+using gfs_red::block_sum256;
 
 namespace {
 
 constexpr int kPoseThreads = 256;
-constexpr int kSys = 27;  // 21 (upper triangle of H) + 6 (b)
 
 struct PoseFrame {
   double q[4], t[3];
@@ -48,218 +50,17 @@ struct EdgeView {
   const uint8_t* stereo;
 };
 
-__device__ __forceinline__ void map3(const double* q, const double* t, const double* X, double* o) {  // SE3Quat::map
-  quat_rotate(q, X, o);
-  o[0] += t[0];
-  o[1] += t[1];
-  o[2] += t[2];
-}
-
-// computeError of an edge at pose (q, t) and its chi2
 // An edge as its thread keeps it: the inputs (read once) and the state g2o keeps per edge (error vector, chi2, level) plus mvbOutlier.
 struct EdgeReg {
   double xw[3], obs[3], err[3], chi2, w;
   int stereo, level, outlier;
 };
-__device__ __forceinline__ void pose_edge_error(const PoseFrame& F, const EdgeReg& R, const double* q, const double* t, double* r) {
-  double xc[3];
-  map3(q, t, R.xw, xc);
-  if (R.stereo) {  // cam_project (types_six_dof_expmap.cpp:339-346): float invz, double bf
-    const float invz = (float)(1.0 / xc[2]);
-    const double u = xc[0] * (double)invz * F.fx + F.cx, v = xc[1] * (double)invz * F.fy + F.cy;
-    r[0] = R.obs[0] - u;
-    r[1] = R.obs[1] - v;
-    r[2] = R.obs[2] - (u - F.bf * (double)invz);
-  } else {  // Pinhole::project(Vector3d), src/CameraModels/Pinhole.cpp:35-41
-    r[0] = R.obs[0] - (F.fx * xc[0] / xc[2] + F.cx);
-    r[1] = R.obs[1] - (F.fy * xc[1] / xc[2] + F.cy);
-    r[2] = 0;
-  }
-}
-__device__ __forceinline__ double pose_edge_chi2(const EdgeReg& R, const double* r) {
-  return R.stereo ? (r[0] * R.w * r[0] + r[1] * R.w * r[1] + r[2] * R.w * r[2]) : (r[0] * R.w * r[0] + r[1] * R.w * r[1]);
-}
-// deterministic block sum (256 threads): wave shuffle tree, then the four waves in order; result in every thread
-__device__ double block_sum256(double v, double* s4) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int ofs = 32; ofs > 0; ofs >>= 1) v += __shfl_down(v, ofs, 64);
-  __syncthreads();
-  if (lane == 0) s4[wave] = v;
-  __syncthreads();
-  return ((s4[0] + s4[1]) + s4[2]) + s4[3];
-}
 
 // Ordered sums: kChunk edges per pass (one per thread) park their 27 terms in an LDS slab, row q = quantity q with an odd
 // row stride (the 27 summing lanes then read different banks); lane q adds its row to its running value in index order.
 constexpr int kChunk = kPoseThreads;
 constexpr int kSlabStride = kChunk + 1;
 constexpr int kSlabDoubles = kSys * kSlabStride;  // also the capacity of one pass of the chi2 sum
-
-template <typename T>
-__device__ __forceinline__ T ordered_sum(const T* __restrict__ v, int cnt, T s) {
-  // one dependent chain of cnt additions; the terms of the NEXT batch are fetched from LDS while this batch is added (a plain loop
-  // waits for its eight reads, adds, and only then asks for the next eight: 250 cycles a batch instead of the 80 the adds take)
-  constexpr int kB = 8;
-  T a[kB];
-  int j = 0;
-  if (cnt >= kB) {
-#pragma unroll
-    for (int u = 0; u < kB; u++) a[u] = v[u];
-    for (; j + 2 * kB <= cnt; j += kB) {
-      T b[kB];
-#pragma unroll
-      for (int u = 0; u < kB; u++) b[u] = v[j + kB + u];
-#pragma unroll
-      for (int u = 0; u < kB; u++) s += a[u];
-#pragma unroll
-      for (int u = 0; u < kB; u++) a[u] = b[u];
-    }
-#pragma unroll
-    for (int u = 0; u < kB; u++) s += a[u];
-    j += kB;
-  }
-  for (; j < cnt; j++) s += v[j];
-  return s;
-}
-
-// Eigen::LDLT<MatrixXd>::compute + isPositive + solve on a 6x6 (see oracle/pose_oracle.cpp for the line-by-line restatement).
-// The pivot search and the symmetric transpositions index the matrix at run time.  A private array indexed at run time lives in
-// scratch memory, an LDS copy costs a round trip per access on the one lane everybody waits for (6.5 us a solve, a fifth of the
-// kernel): here every index is a compile-time constant -- the loops over k, i, j are unrolled and the run-time pivot p is matched
-// against its (at most five) possible values, each with its own statically indexed swaps -- so the 21 entries of the lower
-// triangle, y and the transpositions stay in registers.  The arithmetic, operation for operation, is the restatement's.
-template <int K, int PC>
-__device__ __forceinline__ void ldlt6_transpose(double (&A)[6][6]) {  // symmetric transposition k <-> p restricted to the lower triangle
-#pragma unroll
-  for (int j = 0; j < K; j++) {
-    const double tmp = A[K][j];
-    A[K][j] = A[PC][j];
-    A[PC][j] = tmp;
-  }
-#pragma unroll
-  for (int i = PC + 1; i < 6; i++) {
-    const double tmp = A[i][K];
-    A[i][K] = A[i][PC];
-    A[i][PC] = tmp;
-  }
-  {
-    const double tmp = A[K][K];
-    A[K][K] = A[PC][PC];
-    A[PC][PC] = tmp;
-  }
-#pragma unroll
-  for (int i = K + 1; i < PC; i++) {
-    const double tmp = A[i][K];
-    A[i][K] = A[PC][i];
-    A[PC][i] = tmp;
-  }
-}
-template <int K>
-__device__ __forceinline__ void ldlt6_step(double (&A)[6][6], int (&tr)[6], int& sign) {
-  int p = K;
-  double best = fabs(A[K][K]);
-#pragma unroll
-  for (int i = K + 1; i < 6; i++)
-    if (fabs(A[i][i]) > best) {
-      best = fabs(A[i][i]);
-      p = i;
-    }
-  tr[K] = p;
-  if constexpr (K + 1 < 6) { if (p == K + 1) ldlt6_transpose<K, K + 1 < 6 ? K + 1 : 5>(A); }
-  if constexpr (K + 2 < 6) { if (p == K + 2) ldlt6_transpose<K, K + 2 < 6 ? K + 2 : 5>(A); }
-  if constexpr (K + 3 < 6) { if (p == K + 3) ldlt6_transpose<K, K + 3 < 6 ? K + 3 : 5>(A); }
-  if constexpr (K + 4 < 6) { if (p == K + 4) ldlt6_transpose<K, K + 4 < 6 ? K + 4 : 5>(A); }
-  if constexpr (K + 5 < 6) { if (p == K + 5) ldlt6_transpose<K, K + 5 < 6 ? K + 5 : 5>(A); }
-  if constexpr (K > 0) {
-    double temp[K];
-#pragma unroll
-    for (int j = 0; j < K; j++) temp[j] = A[j][j] * A[K][j];
-    double acc = 0;
-#pragma unroll
-    for (int j = 0; j < K; j++) acc += A[K][j] * temp[j];
-    A[K][K] -= acc;
-#pragma unroll
-    for (int i = K + 1; i < 6; i++) {
-      double a2 = 0;
-#pragma unroll
-      for (int j = 0; j < K; j++) a2 += A[i][j] * temp[j];
-      A[i][K] -= a2;
-    }
-  }
-  const double akk = A[K][K];
-  if (fabs(akk) > 0) {
-#pragma unroll
-    for (int i = K + 1; i < 6; i++) A[i][K] /= akk;
-  }
-  if (sign == 1) {
-    if (akk < 0) sign = 2;
-  } else if (sign == -1) {
-    if (akk > 0) sign = 2;
-  } else if (sign == 0) {
-    if (akk > 0) sign = 1;
-    else if (akk < 0) sign = -1;
-  }
-}
-template <int K>
-__device__ __forceinline__ void ldlt6_swap_y(double (&y)[6], int p) {  // y[K] <-> y[p], p >= K
-  if constexpr (K + 1 < 6) { if (p == K + 1) { const double t = y[K]; y[K] = y[K + 1 < 6 ? K + 1 : 5]; y[K + 1 < 6 ? K + 1 : 5] = t; } }
-  if constexpr (K + 2 < 6) { if (p == K + 2) { const double t = y[K]; y[K] = y[K + 2 < 6 ? K + 2 : 5]; y[K + 2 < 6 ? K + 2 : 5] = t; } }
-  if constexpr (K + 3 < 6) { if (p == K + 3) { const double t = y[K]; y[K] = y[K + 3 < 6 ? K + 3 : 5]; y[K + 3 < 6 ? K + 3 : 5] = t; } }
-  if constexpr (K + 4 < 6) { if (p == K + 4) { const double t = y[K]; y[K] = y[K + 4 < 6 ? K + 4 : 5]; y[K + 4 < 6 ? K + 4 : 5] = t; } }
-  if constexpr (K + 5 < 6) { if (p == K + 5) { const double t = y[K]; y[K] = y[K + 5 < 6 ? K + 5 : 5]; y[K + 5 < 6 ? K + 5 : 5] = t; } }
-}
-// H: the 21 entries of the lower triangle, packed a (a + 1) / 2 + c; lambda is added to the diagonal
-__device__ __forceinline__ bool ldlt6_solve_positive(const double* H21, double lambda, const double* b, double* x) {
-  double A[6][6];
-  {
-    int o = 0;
-#pragma unroll
-    for (int a = 0; a < 6; a++)
-#pragma unroll
-      for (int c = 0; c <= a; c++) {
-        A[a][c] = H21[o];
-        A[c][a] = H21[o];
-        o++;
-      }
-  }
-#pragma unroll
-  for (int a = 0; a < 6; a++) A[a][a] += lambda;
-  int tr[6], sign = 0;
-  ldlt6_step<0>(A, tr, sign);
-  ldlt6_step<1>(A, tr, sign);
-  ldlt6_step<2>(A, tr, sign);
-  ldlt6_step<3>(A, tr, sign);
-  ldlt6_step<4>(A, tr, sign);
-  ldlt6_step<5>(A, tr, sign);
-  if (sign != 1) return false;
-  double y[6];
-#pragma unroll
-  for (int i = 0; i < 6; i++) y[i] = b[i];
-  ldlt6_swap_y<0>(y, tr[0]);
-  ldlt6_swap_y<1>(y, tr[1]);
-  ldlt6_swap_y<2>(y, tr[2]);
-  ldlt6_swap_y<3>(y, tr[3]);
-  ldlt6_swap_y<4>(y, tr[4]);
-#pragma unroll
-  for (int i = 0; i < 6; i++)
-#pragma unroll
-    for (int j = 0; j < i; j++) y[i] -= A[i][j] * y[j];
-#pragma unroll
-  for (int i = 0; i < 6; i++) y[i] = fabs(A[i][i]) > 2.2250738585072014e-308 ? y[i] / A[i][i] : 0.0;
-#pragma unroll
-  for (int i = 5; i >= 0; i--)
-#pragma unroll
-    for (int j = i + 1; j < 6; j++) y[i] -= A[j][i] * y[j];
-  ldlt6_swap_y<4>(y, tr[4]);
-  ldlt6_swap_y<3>(y, tr[3]);
-  ldlt6_swap_y<2>(y, tr[2]);
-  ldlt6_swap_y<1>(y, tr[1]);
-  ldlt6_swap_y<0>(y, tr[0]);
-#pragma unroll
-  for (int i = 0; i < 6; i++) x[i] = y[i];
-  return true;
-}
 
 // kTree = false: every sum over the edges in edge order on one lane (the bits of the sequential restatement; a chain of n dependent
 //   additions, 21 cycles each, three times an LM iteration).
@@ -268,59 +69,6 @@ __device__ __forceinline__ bool ldlt6_solve_positive(const double* H21, double l
 //   shape depends on nothing but the number of edges, so a frame gives the same bits alone or inside any batch; against the
 //   restatement the sums differ in their last bits (relative 1e-16), the bar on the pose is 1e-5, and an outlier flag can only
 //   differ where an edge's chi2 sits within rounding of its threshold (tests/test_gpu_pose.py proves that for every flip).
-
-// The 6x6 solve of the tree-sum default.  H + lambda I of an LM trial is symmetric positive definite unless the trial is hopeless, and
-// for such a matrix Eigen's diagonal pivoting only re-orders the rounding: an UN-pivoted LDL^T (as k_gicp_solve uses for the same
-// reason) gives the solution to rounding with ~150 instead of ~1 000 instructions on the one lane everybody waits for (no pivot
-// search, no transpositions, six reciprocals instead of 21 divisions).  "Not positive" (LinearSolverDense: the trial is rejected) =
-// a pivot that is not > 0 -- the same matrices, up to those within rounding of singular.
-__device__ __forceinline__ bool ldlt6_solve_spd_fast(const double* H21, double lambda, const double* b, double* x) {
-#pragma clang fp contract(fast)
-  double L[6][6], W[6][6], rd[6];  // L unit lower, W = L D, rd = 1 / d
-  {
-    int o = 0;
-#pragma unroll
-    for (int a = 0; a < 6; a++)
-#pragma unroll
-      for (int c = 0; c <= a; c++) L[a][c] = H21[o++];
-  }
-#pragma unroll
-  for (int a = 0; a < 6; a++) L[a][a] += lambda;
-  bool ok = true;
-#pragma unroll
-  for (int j = 0; j < 6; j++) {
-    double dj = L[j][j];
-#pragma unroll
-    for (int k = 0; k < j; k++) dj -= L[j][k] * W[j][k];
-    ok = ok && dj > 0.0;
-    rd[j] = 1.0 / dj;
-#pragma unroll
-    for (int i = j + 1; i < 6; i++) {
-      double v = L[i][j];
-#pragma unroll
-      for (int k = 0; k < j; k++) v -= L[i][k] * W[j][k];
-      W[i][j] = v;
-      L[i][j] = v * rd[j];
-    }
-  }
-  if (!ok) return false;
-  double y[6];
-#pragma unroll
-  for (int i = 0; i < 6; i++) {
-    y[i] = b[i];
-#pragma unroll
-    for (int j = 0; j < i; j++) y[i] -= L[i][j] * y[j];
-  }
-#pragma unroll
-  for (int i = 0; i < 6; i++) y[i] *= rd[i];
-#pragma unroll
-  for (int i = 5; i >= 0; i--) {
-#pragma unroll
-    for (int j = i + 1; j < 6; j++) y[i] -= L[j][i] * y[j];
-    x[i] = y[i];
-  }
-  return true;
-}
 
 // VertexSE3Expmap::oplusImpl as pose_oplus (g2o_se3_dev.hpp), for the tree-sum default: the device library's sin / cos and a plain
 // cube instead of the bit-for-bit restatement of glibc's (a few hundred instructions on the one lane everybody waits for), fused
@@ -398,7 +146,6 @@ __global__ __launch_bounds__(kPoseThreads) void k_pose_opt(const PoseFrame* __re
   double* chi2 = chi2_all + (size_t)f * stride;
   double* err = err_all + (size_t)f * stride * 3;
   uint8_t* level = level_all + (size_t)f * stride;
-  const double dMono = (double)(float)sqrt(5.991), dStereo = (double)(float)sqrt(7.815);  // deltaMono / deltaStereo are floats (:807-808)
   double q0[4] = {F.q[0], F.q[1], F.q[2], F.q[3]};
   normalize_rotation(q0);  // SE3Quat(q, t) constructor
   // Edge e belongs to thread e % 256 in every pass of the kernel.  The thread's first two edges (frames of up to 512 observations:
@@ -468,25 +215,10 @@ __global__ __launch_bounds__(kPoseThreads) void k_pose_opt(const PoseFrame* __re
     double chi = 0;
     if constexpr (kTree) {
       double mine = 0;
-      for (int e = tid; e < n; e += kPoseThreads) {
+      for (int e = tid; e < n; e += kPoseThreads)
         with_edge(e, [&](EdgeReg& R) {
-          if (!R.level) {
-            double r[3];
-            pose_edge_error(F, R, T, T + 4, r);
-            const double c = pose_edge_chi2(R, r);
-            R.err[0] = r[0];
-            R.err[1] = r[1];
-            R.err[2] = r[2];
-            R.chi2 = c;
-            double term = c;
-            if (robust) {
-              double r1;
-              huber(c, R.stereo ? dStereo : dMono, &term, &r1);
-            }
-            mine += term;
-          }
+          if (!R.level) mine += vis_edge_update(F, R.xw, R.obs, R.stereo != 0, R.w, T, robust, R.err, R.chi2);
         });
-      }
       return block_sum256(mine, s4);
     }
     for (int base = 0; base < n; base += kSlabDoubles) {
@@ -494,20 +226,7 @@ __global__ __launch_bounds__(kPoseThreads) void k_pose_opt(const PoseFrame* __re
       for (int e = base + tid; e < base + cnt; e += kPoseThreads) {
         double term = 0;  // an edge that is not active adds nothing (x + 0 = x)
         with_edge(e, [&](EdgeReg& R) {
-          if (!R.level) {
-            double r[3];
-            pose_edge_error(F, R, T, T + 4, r);
-            const double c = pose_edge_chi2(R, r);
-            R.err[0] = r[0];
-            R.err[1] = r[1];
-            R.err[2] = r[2];
-            R.chi2 = c;
-            term = c;
-            if (robust) {
-              double r1;
-              huber(c, R.stereo ? dStereo : dMono, &term, &r1);
-            }
-          }
+          if (!R.level) term = vis_edge_update(F, R.xw, R.obs, R.stereo != 0, R.w, T, robust, R.err, R.chi2);
         });
         s_slab[e - base] = term;
       }
@@ -527,8 +246,7 @@ __global__ __launch_bounds__(kPoseThreads) void k_pose_opt(const PoseFrame* __re
     for (int e = tid; e < n; e += kPoseThreads) with_edge(e, [&](EdgeReg& R) { local_active += R.level == 0; });
     __syncthreads();
     const int n_active = (int)block_sum256((double)local_active, s4);
-    double currentLambda = -1, ni = 2;  // thread 0 only
-    int nBadLm = 0;
+    LmState lm{-1, 2, 0};  // thread 0 only
     // g2o computes the active errors at the top of every iteration; after an ACCEPTED trial they are what that trial has just left
     // in the edges, at the same estimate -- same values, same sum -- so the pass is run only after a rejected one (pop(): estimate
     // restored, the edges keep the trial's errors) and at the start of a round
@@ -554,69 +272,7 @@ __global__ __launch_bounds__(kPoseThreads) void k_pose_opt(const PoseFrame* __re
           for (int k = 0; k < kSys; k++) acc[k] = 0;
           if (e < n) with_edge(e, [&](EdgeReg& R) {
             if (R.level) return;
-            double xc[3];
-            map3(T, T + 4, R.xw, xc);
-            const double x = xc[0], y = xc[1], z = xc[2];
-            double J[18];
-            int rows;
-            if (R.stereo) {  // types_six_dof_expmap.cpp:375-404
-              rows = 3;
-              const double invz = 1.0 / z, invz_2 = invz * invz;
-              J[0] = x * y * invz_2 * F.fx;
-              J[1] = -(1 + (x * x * invz_2)) * F.fx;
-              J[2] = y * invz * F.fx;
-              J[3] = -invz * F.fx;
-              J[4] = 0;
-              J[5] = x * invz_2 * F.fx;
-              J[6] = (1 + y * y * invz_2) * F.fy;
-              J[7] = -x * y * invz_2 * F.fy;
-              J[8] = -x * invz * F.fy;
-              J[9] = 0;
-              J[10] = -invz * F.fy;
-              J[11] = y * invz_2 * F.fy;
-              J[12] = J[0] - F.bf * y * invz_2;
-              J[13] = J[1] + F.bf * x * invz_2;
-              J[14] = J[2];
-              J[15] = J[3];
-              J[16] = 0;
-              J[17] = J[5] - F.bf * invz_2;
-            } else {  // src/OptimizableTypes.cpp:49-63: -projectJac(xyz) * SE3deriv
-              rows = 2;
-              const double pj[6] = {F.fx / z, 0, -F.fx * x / (z * z), 0, F.fy / z, -F.fy * y / (z * z)};
-              const double D[18] = {0, z, -y, 1, 0, 0, -z, 0, x, 0, 1, 0, y, -x, 0, 0, 0, 1};
-              for (int r = 0; r < 2; r++)
-                for (int c = 0; c < 6; c++) J[6 * r + c] = -(pj[3 * r] * D[c] + pj[3 * r + 1] * D[6 + c] + pj[3 * r + 2] * D[12 + c]);
-              for (int c = 0; c < 6; c++) J[12 + c] = 0;
-            }
-            const double w = R.w;
-            double rho1 = 1.0;
-            if (robust) {
-              double r0;
-              huber(R.chi2, R.stereo ? dStereo : dMono, &r0, &rho1);
-            }
-            const double r[3] = {R.err[0], R.err[1], R.err[2]};
-            // the lower triangle, row a / column c <= a: the entries Eigen's LDLT reads (packed a (a + 1) / 2 + c)
-            // (every index below is a compile-time constant: arrays indexed at run time would live in scratch memory.  The third
-            //  row is added by a select, not as a zero term, so that a mono edge sums exactly its two terms)
-            const bool three = rows == 3;
-            int o = 0;
-#pragma unroll
-            for (int a = 0; a < 6; a++) {
-              double sb = 0;
-              sb += ((rho1 * J[a]) * w) * r[0];
-              sb += ((rho1 * J[6 + a]) * w) * r[1];
-              const double sb3 = sb + ((rho1 * J[12 + a]) * w) * r[2];
-              sb = three ? sb3 : sb;
-              acc[21 + a] = -sb;  // b -= ((rho1 A') Omega) e, Eigen's left-to-right association of base_unary_edge.hpp:62
-#pragma unroll
-              for (int c = 0; c <= a; c++) {
-                double hh = 0;
-                hh += (J[a] * (rho1 * w)) * J[c];  // (A' weightedOmega) A: H(a, c) = sum_k (J_ka w') J_kc, base_unary_edge.hpp:63
-                hh += (J[6 + a] * (rho1 * w)) * J[6 + c];
-                const double hh3 = hh + (J[12 + a] * (rho1 * w)) * J[12 + c];
-                acc[o++] = three ? hh3 : hh;
-              }
-            }
+            vis_edge_quadratic_form(F, T, R.xw, R.stereo != 0, R.w, robust, R.chi2, R.err, acc);
           });
           if constexpr (kTree) {
 #pragma unroll
@@ -634,25 +290,15 @@ __global__ __launch_bounds__(kPoseThreads) void k_pose_opt(const PoseFrame* __re
         __syncthreads();
       }
       PT(2)
-      if (tid == 0 && iteration == 0) {  // computeLambdaInit: tau * max |diag(H)|
-        double maxDiagonal = 0;
-        for (int a = 0; a < 6; a++) maxDiagonal = fmax(fabs(s_sys[a * (a + 1) / 2 + a]), maxDiagonal);
-        currentLambda = 1e-5 * maxDiagonal;
-        ni = 2;
-        nBadLm = 0;
-      }
+      if (tid == 0 && iteration == 0) lm_lambda_init(lm, s_sys);
       double rho = 0;
       int qmax = 0;
       bool again = true;
       while (again) {
         if (tid == 0) {
           for (int k = 0; k < 7; k++) s_Tb[k] = s_T[k];  // push()
-          double x[6], H21[21], b6[6];
-#pragma unroll
-          for (int k = 0; k < 21; k++) H21[k] = s_sys[k];
-#pragma unroll
-          for (int k = 0; k < 6; k++) b6[k] = s_sys[21 + k];
-          const bool ok2 = kTree ? ldlt6_solve_spd_fast(H21, currentLambda, b6, x) : ldlt6_solve_positive(H21, currentLambda, b6, x);
+          double x[6];
+          const bool ok2 = kTree ? ldlt6_solve_spd_fast(s_sys, lm.currentLambda, s_sys + 21, x) : ldlt6_solve_positive(s_sys, lm.currentLambda, s_sys + 21, x);
           if (ok2) {
             double qn[4], tn[3];
             if constexpr (kTree) pose_oplus_fast(s_T, s_T + 4, x, qn, tn);
@@ -668,30 +314,11 @@ __global__ __launch_bounds__(kPoseThreads) void k_pose_opt(const PoseFrame* __re
         double tempChi = compute_active(robust);
         PT(4)
         if (tid == 0) {
-          const bool ok2 = s_flag[0] != 0;
-          if (!ok2) tempChi = 1.79769313486231570e308;
-          rho = currentChi - tempChi;
-          double scale = 0;
-          if (ok2)
-            for (int a = 0; a < 6; a++) scale += s_x[a] * (currentLambda * s_x[a] + s_sys[21 + a]);
-          scale += 1e-3;
-          rho /= scale;
-          if (rho > 0 && isfinite(tempChi)) {
-            const double g3 = 2 * rho - 1;
-            double alpha = 1. - (kTree ? g3 * g3 * g3 : gfs_glibc::pow3(g3));
-            alpha = fmin(alpha, 2. / 3.);
-            const double scaleFactor = fmax(1. / 3., alpha);
-            currentLambda *= scaleFactor;
-            ni = 2;
-            currentChi = tempChi;
-          } else {
-            currentLambda *= ni;
-            ni *= 2;
+          const LmVerdict v = lm_judge_trial(lm, s_flag[0] != 0, tempChi, s_x, s_sys + 21, kTree, currentChi, rho, qmax);
+          if (!v.accepted)
             for (int k = 0; k < 7; k++) s_T[k] = s_Tb[k];  // pop(): estimate restored, edge errors stay those of the trial
-          }
-          qmax++;
-          s_flag[1] = (rho < 0 && qmax < 10) ? 1 : 0;
-          s_flag[2] = (rho > 0 && isfinite(tempChi)) ? 1 : 0;  // the trial was accepted
+          s_flag[1] = v.again ? 1 : 0;
+          s_flag[2] = v.accepted ? 1 : 0;
         }
         __syncthreads();
         again = s_flag[1] != 0;
@@ -700,14 +327,7 @@ __global__ __launch_bounds__(kPoseThreads) void k_pose_opt(const PoseFrame* __re
       }
       if (tid == 0) {
         O.iterations_run++;
-        int stop = 0;
-        if (qmax == 10 || rho == 0) stop = 1;
-        if (!stop) {
-          if ((iniChi - currentChi) * 1e3 < iniChi) nBadLm++;
-          else nBadLm = 0;
-          if (nBadLm >= 3) stop = 1;
-        }
-        s_flag[0] = stop;
+        s_flag[0] = lm_stop(lm, qmax, rho, iniChi, currentChi) ? 1 : 0;
       }
       __syncthreads();
       const int stop = s_flag[0];
@@ -722,13 +342,7 @@ __global__ __launch_bounds__(kPoseThreads) void k_pose_opt(const PoseFrame* __re
       for (int k = 0; k < 7; k++) T[k] = s_T[k];
       for (int e = tid; e < n; e += kPoseThreads)
         with_edge(e, [&](EdgeReg& R) {
-          if (!R.outlier) return;
-          double r[3];
-          pose_edge_error(F, R, T, T + 4, r);
-          R.err[0] = r[0];
-          R.err[1] = r[1];
-          R.err[2] = r[2];
-          R.chi2 = pose_edge_chi2(R, r);
+          if (R.outlier) vis_edge_update(F, R.xw, R.obs, R.stereo != 0, R.w, T, false, R.err, R.chi2);
         });
     }
     __syncthreads();
@@ -746,17 +360,7 @@ __global__ __launch_bounds__(kPoseThreads) void k_pose_opt(const PoseFrame* __re
           const int cnt = min(kTerms, n - base);
           for (int e = base + tid; e < base + cnt; e += kPoseThreads) {
             float term = 0.0f;
-            with_edge(e, [&](EdgeReg& R) {
-              if ((R.stereo != 0) == (pass == 1)) {
-                const float c = (float)R.chi2;
-                const bool out = c > (pass ? 7.815f : 5.991f);
-                R.outlier = out ? 1 : 0;
-                R.level = out ? 1 : 0;
-                bad_local += out ? 1 : 0;
-                good_local += out ? 0 : 1;
-                if (!out) term = c;
-              }
-            });
+            with_edge(e, [&](EdgeReg& R) { term = classify_edge(R.stereo != 0, R.chi2, pass, R.outlier, R.level, bad_local, good_local); });
             if constexpr (kTree) mine_avg += (double)term;
             else s_term[e - base] = term;
           }

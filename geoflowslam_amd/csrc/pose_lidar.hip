@@ -8,7 +8,9 @@
 // re-classification of the visual edges, the float pose of the next association).  The edges live in global memory: a few thousand
 // lidar edges do not fit beside the LDS slab of the ordered sums.  Every sum over the edges is added in g2o's edge order (visual edges
 // by key-point index, then lidar edges by cloud index) on one lane per quantity (GFS_POSE_SUMS_EDGE_ORDER, the bits of the sequential
-// restatement tests/host/pose_lidar_restatement.cpp), or by a tree of fixed shape (GFS_POSE_SUMS_TREE).
+// restatement tests/host/pose_lidar_restatement.cpp), or by a tree of fixed shape (GFS_POSE_SUMS_TREE).  The visual-edge bodies, the
+// pivoted 6x6 solve (in both sum modes), the ordered sum and the LM bookkeeping are pose_lm_dev.hpp's, shared with pose.hip; the
+// lidar edges, the loops and the edge storage are this file's.
 //
 // The numeric Jacobian of a lidar edge (core/base_unary_edge.hpp:82-123) evaluates the error at the estimate moved by +-1e-9 along
 // each of the six axes.  Those twelve poses -- and their inverses, which computeError takes -- are the same for every edge: they are
@@ -22,15 +24,17 @@
 #include "g2o_se3_dev.hpp"
 #include "gfs_common.hpp"
 #include "lidar_assoc.hpp"
+#include "pose_lm_dev.hpp"
 #include "wave_reduce.hpp"
 
 using namespace gfs_se3;
 using namespace gfs_lidar;
+using namespace gfs_pose_lm;
+using gfs_red::block_sum256;
 
 namespace {
 
 constexpr int kThreads = 256;
-constexpr int kSys = 27;
 constexpr int kSlabStride = kThreads + 1;
 constexpr int kSlabDoubles = kSys * kSlabStride;
 // GenerateLidarEdge / PoseLidarVisualOptimization constants (tests/test_pose_lidar_constants.py reads them from here)
@@ -116,130 +120,6 @@ __global__ __launch_bounds__(kThreads) void k_lba_lidar_assoc(const WindowKF* __
   s_all[g] = s;
 }
 
-__device__ __forceinline__ void vis_err(const LFrame& F, const double* xw, const double* obs, bool st, const double* q, const double* t,
-                                        double* r) {
-  double xc[3];
-  quat_rotate(q, xw, xc);
-  xc[0] += t[0];
-  xc[1] += t[1];
-  xc[2] += t[2];
-  if (st) {
-    const float invz = (float)(1.0 / xc[2]);
-    const double u = xc[0] * (double)invz * F.fx + F.cx, v = xc[1] * (double)invz * F.fy + F.cy;
-    r[0] = obs[0] - u;
-    r[1] = obs[1] - v;
-    r[2] = obs[2] - (u - F.bf * (double)invz);
-  } else {
-    r[0] = obs[0] - (F.fx * xc[0] / xc[2] + F.cx);
-    r[1] = obs[1] - (F.fy * xc[1] / xc[2] + F.cy);
-    r[2] = 0;
-  }
-}
-__device__ __forceinline__ double vis_chi2(const double* r, double w, bool st) {
-  return st ? (r[0] * w * r[0] + r[1] * w * r[1] + r[2] * w * r[2]) : (r[0] * w * r[0] + r[1] * w * r[1]);
-}
-
-// Eigen::LDLT<MatrixXd> on the 6x6 (lower triangle H21, lambda on the diagonal), thread 0 only; false unless positive
-__device__ bool ldlt6(const double* H21, double lambda, const double* b, double* x) {
-  double A[6][6];
-  int o = 0;
-  for (int a = 0; a < 6; a++)
-    for (int c = 0; c <= a; c++) {
-      A[a][c] = H21[o];
-      A[c][a] = H21[o];
-      o++;
-    }
-  for (int a = 0; a < 6; a++) A[a][a] += lambda;
-  int tr[6], sign = 0;
-  for (int k = 0; k < 6; k++) {
-    int p = k;
-    double best = fabs(A[k][k]);
-    for (int i = k + 1; i < 6; i++)
-      if (fabs(A[i][i]) > best) {
-        best = fabs(A[i][i]);
-        p = i;
-      }
-    tr[k] = p;
-    if (p != k) {
-      for (int j = 0; j < k; j++) {
-        const double t = A[k][j];
-        A[k][j] = A[p][j];
-        A[p][j] = t;
-      }
-      for (int i = p + 1; i < 6; i++) {
-        const double t = A[i][k];
-        A[i][k] = A[i][p];
-        A[i][p] = t;
-      }
-      {
-        const double t = A[k][k];
-        A[k][k] = A[p][p];
-        A[p][p] = t;
-      }
-      for (int i = k + 1; i < p; i++) {
-        const double t = A[i][k];
-        A[i][k] = A[p][i];
-        A[p][i] = t;
-      }
-    }
-    if (k > 0) {
-      double temp[6];
-      for (int j = 0; j < k; j++) temp[j] = A[j][j] * A[k][j];
-      double acc = 0;
-      for (int j = 0; j < k; j++) acc += A[k][j] * temp[j];
-      A[k][k] -= acc;
-      for (int i = k + 1; i < 6; i++) {
-        double a2 = 0;
-        for (int j = 0; j < k; j++) a2 += A[i][j] * temp[j];
-        A[i][k] -= a2;
-      }
-    }
-    const double akk = A[k][k];
-    if (fabs(akk) > 0)
-      for (int i = k + 1; i < 6; i++) A[i][k] /= akk;
-    if (sign == 1) {
-      if (akk < 0) sign = 2;
-    } else if (sign == -1) {
-      if (akk > 0) sign = 2;
-    } else if (sign == 0) {
-      if (akk > 0) sign = 1;
-      else if (akk < 0) sign = -1;
-    }
-  }
-  if (sign != 1) return false;
-  double y[6];
-  for (int i = 0; i < 6; i++) y[i] = b[i];
-  for (int k = 0; k < 6; k++) {
-    const double t = y[k];
-    y[k] = y[tr[k]];
-    y[tr[k]] = t;
-  }
-  for (int i = 0; i < 6; i++)
-    for (int j = 0; j < i; j++) y[i] -= A[i][j] * y[j];
-  for (int i = 0; i < 6; i++) y[i] = fabs(A[i][i]) > 2.2250738585072014e-308 ? y[i] / A[i][i] : 0.0;
-  for (int i = 5; i >= 0; i--)
-    for (int j = i + 1; j < 6; j++) y[i] -= A[j][i] * y[j];
-  for (int k = 5; k >= 0; k--) {
-    const double t = y[k];
-    y[k] = y[tr[k]];
-    y[tr[k]] = t;
-  }
-  for (int i = 0; i < 6; i++) x[i] = y[i];
-  return true;
-}
-
-__device__ double block_sum(double v, double* s4) {  // fixed shape: wave shuffle tree, then the four waves in order
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int ofs = 32; ofs > 0; ofs >>= 1) v += __shfl_down(v, ofs, 64);
-  __syncthreads();
-  if (lane == 0) s4[wave] = v;
-  __syncthreads();
-  const double r = ((s4[0] + s4[1]) + s4[2]) + s4[3];
-  __syncthreads();
-  return r;
-}
-
 struct VisView {
   const double *xw, *obs;
   const float* w;
@@ -311,6 +191,15 @@ __global__ __launch_bounds__(kThreads) void k_pl_round(const LFrame* __restrict_
     p[1] = (double)cloud[3 * i + 1];
     p[2] = (double)cloud[3 * i + 2];
   };
+  auto lidar_update = [&](int l, const double* W) {  // computeError of lidar edge l at the inverse pose W; returns its chi2
+    double p[3];
+    edge_p(l, p);
+    const double e = lidar_err(W, p, eplane[l], es[l]);
+    const double c = e * (kLidarInfo * e);
+    lerr[l] = e;
+    lchi2[l] = c;
+    return c;
+  };
   // ---- chi2Lidar (a float, edge after edge) and valid_edge at the current estimate
   {
     double W[7];
@@ -320,21 +209,15 @@ __global__ __launch_bounds__(kThreads) void k_pl_round(const LFrame* __restrict_
     for (int base = 0; base < nl; base += kSlabDoubles) {
       const int cnt = min(kSlabDoubles, nl - base);
       for (int l = base + tid; l < base + cnt; l += kThreads) {
-        double p[3];
-        edge_p(l, p);
-        const double e = lidar_err(W, p, eplane[l], es[l]);
-        const double c = e * (kLidarInfo * e);
-        lerr[l] = e;
-        lchi2[l] = c;
+        const double c = lidar_update(l, W);
         valid += c < kLidarValidChi2 ? 1 : 0;
         s_slab[l - base] = c;
       }
       __syncthreads();
-      if (tid == 0)
-        for (int j = 0; j < cnt; j++) chiL += s_slab[j];
+      if (tid == 0) chiL = ordered_sum(s_slab, cnt, chiL);
       __syncthreads();
     }
-    const int n_valid = (int)block_sum((double)valid, s4);
+    const int n_valid = (int)block_sum256((double)valid, s4);
     if (tid == 0) {
       ST.rounds_run = it + 1;
       ST.round_edges[it] = nl;
@@ -349,7 +232,6 @@ __global__ __launch_bounds__(kThreads) void k_pl_round(const LFrame* __restrict_
   }
   if (nl == 0) return;  // `continue`: no optimisation, no re-classification
   const bool vis_robust = ST.vis_robust != 0;
-  const double dMono = (double)(float)sqrt(5.991), dStereo = (double)(float)sqrt(7.815);
   const int E = n + nl;
 
   // errors + chi2 of the active edges at s_T; activeRobustChi2 (valid in thread 0)
@@ -360,48 +242,30 @@ __global__ __launch_bounds__(kThreads) void k_pl_round(const LFrame* __restrict_
     auto term_of = [&](int e) -> double {
       if (e < n) {
         if (level[e]) return 0.0;
-        double r[3];
-        vis_err(F, xw + 3 * e, obs + 3 * e, st[e] != 0, T, T + 4, r);
-        const double c = vis_chi2(r, (double)wv[e], st[e] != 0);
-        err[3 * e] = r[0];
-        err[3 * e + 1] = r[1];
-        err[3 * e + 2] = r[2];
-        chi2[e] = c;
-        double t = c, r1;
-        if (vis_robust) huber(c, st[e] ? dStereo : dMono, &t, &r1);
-        return t;
+        return vis_edge_update(F, xw + 3 * e, obs + 3 * e, st[e] != 0, (double)wv[e], T, vis_robust, err + 3 * e, chi2[e]);
       }
-      const int l = e - n;
-      double p[3];
-      edge_p(l, p);
-      const double ev = lidar_err(W, p, eplane[l], es[l]);
-      const double c = ev * (kLidarInfo * ev);
-      lerr[l] = ev;
-      lchi2[l] = c;
       double t, r1;
-      huber(c, kThHuberLidar, &t, &r1);
+      huber(lidar_update(e - n, W), kThHuberLidar, &t, &r1);
       return t;
     };
     double chi = 0;
     if constexpr (kTree) {
       double mine = 0;
       for (int e = tid; e < E; e += kThreads) mine += term_of(e);
-      return block_sum(mine, s4);
+      return block_sum256(mine, s4);
     }
     for (int base = 0; base < E; base += kSlabDoubles) {
       const int cnt = min(kSlabDoubles, E - base);
       for (int e = base + tid; e < base + cnt; e += kThreads) s_slab[e - base] = term_of(e);
       __syncthreads();
-      if (tid == 0)
-        for (int j = 0; j < cnt; j++) chi += s_slab[j];
+      if (tid == 0) chi = ordered_sum(s_slab, cnt, chi);
       __syncthreads();
     }
     return chi;
   };
 
   int iterations = 0;
-  double currentLambda = -1, ni = 2;
-  int nBadLm = 0;
+  LmState lm{-1, 2, 0};  // thread 0 only
   for (int iteration = 0; iteration < kIts[it]; iteration++) {
     double currentChi = compute_active();
     const double iniChi = currentChi;
@@ -426,68 +290,7 @@ __global__ __launch_bounds__(kThreads) void k_pl_round(const LFrame* __restrict_
 #pragma unroll
         for (int k = 0; k < kSys; k++) acc[k] = 0;
         if (e < n && !level[e]) {
-          double xc[3];
-          quat_rotate(T, xw + 3 * e, xc);
-          xc[0] += T[4];
-          xc[1] += T[5];
-          xc[2] += T[6];
-          const double x = xc[0], y = xc[1], z = xc[2];
-          double J[18];
-          const bool three = st[e] != 0;
-          if (three) {
-            const double invz = 1.0 / z, invz_2 = invz * invz;
-            J[0] = x * y * invz_2 * F.fx;
-            J[1] = -(1 + (x * x * invz_2)) * F.fx;
-            J[2] = y * invz * F.fx;
-            J[3] = -invz * F.fx;
-            J[4] = 0;
-            J[5] = x * invz_2 * F.fx;
-            J[6] = (1 + y * y * invz_2) * F.fy;
-            J[7] = -x * y * invz_2 * F.fy;
-            J[8] = -x * invz * F.fy;
-            J[9] = 0;
-            J[10] = -invz * F.fy;
-            J[11] = y * invz_2 * F.fy;
-            J[12] = J[0] - F.bf * y * invz_2;
-            J[13] = J[1] + F.bf * x * invz_2;
-            J[14] = J[2];
-            J[15] = J[3];
-            J[16] = 0;
-            J[17] = J[5] - F.bf * invz_2;
-          } else {
-            const double pj[6] = {F.fx / z, 0, -F.fx * x / (z * z), 0, F.fy / z, -F.fy * y / (z * z)};
-            const double D[18] = {0, z, -y, 1, 0, 0, -z, 0, x, 0, 1, 0, y, -x, 0, 0, 0, 1};
-#pragma unroll
-            for (int r = 0; r < 2; r++)
-#pragma unroll
-              for (int c = 0; c < 6; c++) J[6 * r + c] = -(pj[3 * r] * D[c] + pj[3 * r + 1] * D[6 + c] + pj[3 * r + 2] * D[12 + c]);
-#pragma unroll
-            for (int c = 0; c < 6; c++) J[12 + c] = 0;
-          }
-          const double w = (double)wv[e];
-          double rho1 = 1.0;
-          if (vis_robust) {
-            double r0;
-            huber(chi2[e], three ? dStereo : dMono, &r0, &rho1);
-          }
-          const double r[3] = {err[3 * e], err[3 * e + 1], err[3 * e + 2]};
-          int o = 0;
-#pragma unroll
-          for (int a = 0; a < 6; a++) {
-            double sb = 0;
-            sb += ((rho1 * J[a]) * w) * r[0];
-            sb += ((rho1 * J[6 + a]) * w) * r[1];
-            const double sb3 = sb + ((rho1 * J[12 + a]) * w) * r[2];
-            acc[21 + a] = -(three ? sb3 : sb);
-#pragma unroll
-            for (int c = 0; c <= a; c++) {
-              double hh = 0;
-              hh += (J[a] * (rho1 * w)) * J[c];
-              hh += (J[6 + a] * (rho1 * w)) * J[6 + c];
-              const double hh3 = hh + (J[12 + a] * (rho1 * w)) * J[12 + c];
-              acc[o++] = three ? hh3 : hh;
-            }
-          }
+          vis_edge_quadratic_form(F, T, xw + 3 * e, st[e] != 0, (double)wv[e], vis_robust, chi2[e], err + 3 * e, acc);
         } else if (e >= n && e < E) {
           const int l = e - n;
           double p[3];
@@ -515,11 +318,7 @@ __global__ __launch_bounds__(kThreads) void k_pl_round(const LFrame* __restrict_
 #pragma unroll
           for (int k = 0; k < kSys; k++) s_slab[k * kSlabStride + tid] = acc[k];
           __syncthreads();
-          if (tid < kSys) {
-            const int cnt = min(kThreads, E - base);
-            const double* row = s_slab + tid * kSlabStride;
-            for (int j = 0; j < cnt; j++) run += row[j];
-          }
+          if (tid < kSys) run = ordered_sum(s_slab + tid * kSlabStride, min(kThreads, E - base), run);
           __syncthreads();
         }
       }
@@ -527,22 +326,15 @@ __global__ __launch_bounds__(kThreads) void k_pl_round(const LFrame* __restrict_
       if (tid < kSys) s_sys[tid] = run;
       __syncthreads();
     }
-    if (tid == 0 && iteration == 0) {  // computeLambdaInit
-      double maxDiagonal = 0;
-      for (int a = 0; a < 6; a++) maxDiagonal = fmax(fabs(s_sys[a * (a + 1) / 2 + a]), maxDiagonal);
-      currentLambda = 1e-5 * maxDiagonal;
-      ni = 2;
-      nBadLm = 0;
-    }
+    if (tid == 0 && iteration == 0) lm_lambda_init(lm, s_sys);
     double rho = 0;
     int qmax = 0;
     bool again = true;
     while (again) {
       if (tid == 0) {
         for (int k = 0; k < 7; k++) s_Tb[k] = s_T[k];
-        double x[6], b6[6];
-        for (int k = 0; k < 6; k++) b6[k] = s_sys[21 + k];
-        const bool ok2 = ldlt6(s_sys, currentLambda, b6, x);
+        double x[6];
+        const bool ok2 = ldlt6_solve_positive(s_sys, lm.currentLambda, s_sys + 21, x);  // in both sum modes
         if (ok2) {
           double qn[4], tn[3];
           pose_oplus(s_T, s_T + 4, x, qn, tn);
@@ -555,44 +347,17 @@ __global__ __launch_bounds__(kThreads) void k_pl_round(const LFrame* __restrict_
       __syncthreads();
       double tempChi = compute_active();
       if (tid == 0) {
-        const bool ok2 = s_flag[0] != 0;
-        if (!ok2) tempChi = 1.79769313486231570e308;
-        rho = currentChi - tempChi;
-        double scale = 0;
-        if (ok2)
-          for (int a = 0; a < 6; a++) scale += s_x[a] * (currentLambda * s_x[a] + s_sys[21 + a]);
-        scale += 1e-3;
-        rho /= scale;
-        if (rho > 0 && isfinite(tempChi)) {
-          double alpha = 1. - gfs_glibc::pow3(2 * rho - 1);
-          alpha = fmin(alpha, 2. / 3.);
-          const double scaleFactor = fmax(1. / 3., alpha);
-          currentLambda *= scaleFactor;
-          ni = 2;
-          currentChi = tempChi;
-        } else {
-          currentLambda *= ni;
-          ni *= 2;
-          for (int k = 0; k < 7; k++) s_T[k] = s_Tb[k];
-        }
-        qmax++;
-        s_flag[1] = (rho < 0 && qmax < 10) ? 1 : 0;
+        const LmVerdict v = lm_judge_trial(lm, s_flag[0] != 0, tempChi, s_x, s_sys + 21, false, currentChi, rho, qmax);
+        if (!v.accepted)
+          for (int k = 0; k < 7; k++) s_T[k] = s_Tb[k];  // pop()
+        s_flag[1] = v.again ? 1 : 0;
       }
       __syncthreads();
       again = s_flag[1] != 0;
       __syncthreads();
     }
     iterations++;
-    if (tid == 0) {
-      int stop = 0;
-      if (qmax == 10 || rho == 0) stop = 1;
-      if (!stop) {
-        if ((iniChi - currentChi) * 1e3 < iniChi) nBadLm++;
-        else nBadLm = 0;
-        if (nBadLm >= 3) stop = 1;
-      }
-      s_flag[0] = stop;
-    }
+    if (tid == 0) s_flag[0] = lm_stop(lm, qmax, rho, iniChi, currentChi) ? 1 : 0;
     __syncthreads();
     const int stop = s_flag[0];
     __syncthreads();
@@ -603,14 +368,7 @@ __global__ __launch_bounds__(kThreads) void k_pl_round(const LFrame* __restrict_
     double T[7];
     for (int k = 0; k < 7; k++) T[k] = s_T[k];
     for (int e = tid; e < n; e += kThreads)
-      if (outl[e]) {
-        double r[3];
-        vis_err(F, xw + 3 * e, obs + 3 * e, st[e] != 0, T, T + 4, r);
-        err[3 * e] = r[0];
-        err[3 * e + 1] = r[1];
-        err[3 * e + 2] = r[2];
-        chi2[e] = vis_chi2(r, (double)wv[e], st[e] != 0);
-      }
+      if (outl[e]) vis_edge_update(F, xw + 3 * e, obs + 3 * e, st[e] != 0, (double)wv[e], T, false, err + 3 * e, chi2[e]);
   }
   __syncthreads();
   float* s_term = reinterpret_cast<float*>(s_slab);
@@ -622,29 +380,19 @@ __global__ __launch_bounds__(kThreads) void k_pl_round(const LFrame* __restrict_
     for (int base = 0; base < n; base += kTerms) {
       const int cnt = min(kTerms, n - base);
       for (int e = base + tid; e < base + cnt; e += kThreads) {
-        float term = 0.0f;
-        if ((st[e] != 0) == (pass == 1)) {
-          const float c = (float)chi2[e];
-          const bool out = c > (pass ? 7.815f : 5.991f);
-          outl[e] = out ? 1 : 0;
-          level[e] = out ? 1 : 0;
-          bad_local += out ? 1 : 0;
-          good_local += out ? 0 : 1;
-          if (!out) term = c;
-        }
+        const float term = classify_edge(st[e] != 0, chi2[e], pass, outl[e], level[e], bad_local, good_local);
         if constexpr (kTree) mine_avg += (double)term;
         else s_term[e - base] = term;
       }
       if constexpr (!kTree) {
         __syncthreads();
-        if (tid == 0)
-          for (int j = 0; j < cnt; j++) avg += s_term[j];
+        if (tid == 0) avg = ordered_sum(s_term, cnt, avg);
         __syncthreads();
       }
     }
-  if constexpr (kTree) avg = (float)block_sum(mine_avg, s4);
-  const int nBad = (int)block_sum((double)bad_local, s4);
-  const int nGood = (int)block_sum((double)good_local, s4);
+  if constexpr (kTree) avg = (float)block_sum256(mine_avg, s4);
+  const int nBad = (int)block_sum256((double)bad_local, s4);
+  const int nGood = (int)block_sum256((double)good_local, s4);
   if (tid == 0) {
     ST.nBad = nBad;
     ST.nGood += nGood;  // never reset

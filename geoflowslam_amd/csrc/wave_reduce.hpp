@@ -46,4 +46,16 @@ __device__ __forceinline__ double block_sum_many(const double (&vals)[N], double
   return r;
 }
 
+// Deterministic sum of one value over a workgroup of 256 threads: wave shuffle tree, then the four waves in order; the result in
+// every thread.  s4: 4 doubles of LDS; the leading barrier covers a previous call's readers, so calls may follow one another.
+__device__ __forceinline__ double block_sum256(double v, double* s4) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int ofs = 32; ofs > 0; ofs >>= 1) v += __shfl_down(v, ofs, 64);
+  __syncthreads();
+  if (lane == 0) s4[wave] = v;
+  __syncthreads();
+  return ((s4[0] + s4[1]) + s4[2]) + s4[3];
+}
+
 }  // namespace gfs_red

@@ -170,7 +170,7 @@ def _parse_chi2():
 
 def test_chi2_and_huber_thresholds():
     """deltaMono / deltaStereo (src/Optimizer.cc:807-808), chi2Mono / chi2Stereo / its (:967-970), thHuberMono / thHuberStereo of
-    LocalBundleAdjustment (:1753-1754) and its outlier gates (:1972 ff.) -> oracle/pose_oracle.cpp, csrc/pose.hip, the LBA adaptor."""
+    LocalBundleAdjustment (:1753-1754) and its outlier gates (:1972 ff.) -> oracle/pose_oracle.cpp, csrc/pose_lm_dev.hpp, the LBA adaptor."""
     ref = _recorded("chi2")
     d_mono, d_stereo = ref["deltaMono"], ref["deltaStereo"]
     chi_m, chi_s = set(ref["chi2Mono"]), set(ref["chi2Stereo"])
@@ -182,9 +182,11 @@ def test_chi2_and_huber_thresholds():
     orc = _ours("oracle/pose_oracle.cpp")
     assert {float(v) for v in re.findall(r"std::sqrt\(([0-9.]+)\)", orc)} >= {d_mono, d_stereo}
     assert _one(r"chi2Mono\s*=\s*([0-9.]+)f", orc) == d_mono and _one(r"chi2Stereo\s*=\s*([0-9.]+)f", orc) == d_stereo
-    dev = _ours("geoflowslam_amd/csrc/pose.hip")
+    dev = _ours("geoflowslam_amd/csrc/pose_lm_dev.hpp")  # the one definition both pose kernels use
     assert re.search(rf"\(float\)sqrt\({d_mono}\)", dev) and re.search(rf"\(float\)sqrt\({d_stereo}\)", dev)
     assert re.search(rf"pass \? {d_stereo}f : {d_mono}f", dev)
+    for path in ("geoflowslam_amd/csrc/pose.hip", "geoflowslam_amd/csrc/pose_lidar.hip"):
+        assert str(d_mono) not in _ours(path) and str(d_stereo) not in _ours(path), path
     ad = _ours("geoflowslam_amd/host/gfs_adaptors.hpp")
     assert re.search(rf"thHuberMono = \(float\)std::sqrt\({d_mono}\)", ad) and re.search(rf"thHuberStereo = \(float\)std::sqrt\({d_stereo}\)", ad)
     assert re.search(rf"chi2\[e\] > {d_mono} ", ad) and re.search(rf"chi2\[e\] > {d_stereo} ", ad)
