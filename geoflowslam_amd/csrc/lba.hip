@@ -10,8 +10,6 @@
 // (LbaState) and the host only reads two mapped flags per trial.  The reduced pose system is factored by one workgroup with a
 // blocked 6-wide LDL^T: in LDS while its packed triangle fits (<= 30 free poses, 130 KB), in place in HBM / L2 with the
 // current panel staged in LDS for larger windows.  All sums are taken in a fixed order (deterministic, unlike atomics).
-// GFS_LBA_SINGLE_WG=1 selects the first implementation instead (k_lba: the whole LM loop of a window in ONE workgroup with
-// the reduced system in LDS, no host round trip; windows of <= 30 free poses only).
 //
 // Edge order: edges are stably re-ordered landmark-major on the host so each landmark's observations are
 // contiguous (the reference builds them that way, src/Optimizer.cc:1816-1952); a second CSR lists each free
@@ -95,7 +93,6 @@ struct LbaDev {
   GFS_GLOBAL double* bp;     // [n_free][6]
   GFS_GLOBAL double* xl;     // [n_points][3]
   GFS_GLOBAL double* xp;     // [n_free*6]
-  volatile GFS_GLOBAL int* stop;  // host-mapped force-stop flag
   GFS_GLOBAL int* out_info;       // [0]=iterations_run [1]=failed flag
   GFS_GLOBAL double* out_stats;   // [0]=final chi2 [1]=final lambda
   int mode;            // 0 = full solve, 1 = linearise only
@@ -196,18 +193,7 @@ __device__ __forceinline__ void edge_jacobians(const LbaDev& D, int e, const dou
   }
 }
 
-// deterministic block reductions (1024 threads): wave shuffle tree, then the 16 wave results in order
-__device__ double block_sum(double v, double* s16) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int ofs = 32; ofs > 0; ofs >>= 1) v += __shfl_down(v, ofs, 64);
-  __syncthreads();
-  if (lane == 0) s16[wave] = v;
-  __syncthreads();
-  double r = 0;
-  for (int w = 0; w < 16; w++) r += s16[w];
-  return r;
-}
+// deterministic block reduction (1024 threads): wave shuffle tree, then the 16 wave results in order
 __device__ double block_max(double v, double* s16) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
@@ -218,92 +204,6 @@ __device__ double block_max(double v, double* s16) {
   double r = 0;
   for (int w = 0; w < 16; w++) r = fmax(r, s16[w]);
   return r;
-}
-
-// SparseOptimizer::computeActiveErrors + activeRobustChi2 (core/sparse_optimizer.cpp:100-114)
-__device__ double compute_errors(const LbaDev& D, const double* q, const double* t, const double* X, double* s16) {
-  double local = 0;
-  for (int e = threadIdx.x; e < D.n_edges; e += kThreads) {
-    double xc[3], r[3];
-    edge_residual(D, e, q, t, X, xc, r);
-    const double c = (r[0] * r[0] + r[1] * r[1] + r[2] * r[2]) * D.e_w[e];
-    D.chi2[e] = c;
-    D.err[3 * e] = r[0];
-    D.err[3 * e + 1] = r[1];
-    D.err[3 * e + 2] = r[2];
-    double r0, r1;
-    huber(c, D.e_stereo[e] ? D.huber_stereo : D.huber_mono, &r0, &r1);
-    local += r0;
-  }
-  return block_sum(local, s16);
-}
-
-// BlockSolver::buildSystem + BaseBinaryEdge::constructQuadraticForm (block_solver.hpp:502-558, base_binary_edge.hpp:55-120)
-__device__ void build_system(const LbaDev& D, double* s16) {
-  // landmark sweep: Hll, bl and the per-edge pose-landmark blocks
-  for (int l = threadIdx.x; l < D.n_points; l += kThreads) {
-    double H[6] = {0, 0, 0, 0, 0, 0}, b[3] = {0, 0, 0};
-    for (int e = D.pt_begin[l]; e < D.pt_begin[l + 1]; e++) {
-      double xc[3], r[3], Ji[9], Jj[18];
-      edge_residual(D, e, D.q, D.t, D.X, xc, r);
-      edge_jacobians(D, e, D.q, xc, Ji, Jj);
-      double r0, r1;
-      huber(D.chi2[e], D.e_stereo[e] ? D.huber_stereo : D.huber_mono, &r0, &r1);
-      const double w = r1 * D.e_w[e];
-      double omr[3];
-      for (int k = 0; k < 3; k++) omr[k] = -(D.e_w[e] * D.err[3 * e + k]) * r1;
-      int o = 0;
-      for (int a = 0; a < 3; a++) {
-        b[a] += Ji[a] * omr[0] + Ji[3 + a] * omr[1] + Ji[6 + a] * omr[2];
-        for (int c = a; c < 3; c++) H[o++] += Ji[a] * w * Ji[c] + Ji[3 + a] * w * Ji[3 + c] + Ji[6 + a] * w * Ji[6 + c];
-      }
-      if (D.free_index[D.e_pose[e]] >= 0) {
-        double* B = D.Hpl + 18 * (size_t)e;
-        for (int a = 0; a < 6; a++)
-          for (int c = 0; c < 3; c++) B[3 * a + c] = Jj[a] * w * Ji[c] + Jj[6 + a] * w * Ji[3 + c] + Jj[12 + a] * w * Ji[6 + c];
-      }
-    }
-    for (int k = 0; k < 6; k++) D.Hll[6 * (size_t)l + k] = H[k];
-    for (int k = 0; k < 3; k++) D.bl[3 * (size_t)l + k] = b[k];
-  }
-  // pose sweep: one wave per free pose, lanes over its edges, fixed-order shuffle reduction
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  for (int f = wave; f < D.n_free; f += 16) {
-    double acc[27];
-#pragma unroll
-    for (int k = 0; k < 27; k++) acc[k] = 0;
-    for (int i = D.pose_begin[f] + lane; i < D.pose_begin[f + 1]; i += 64) {
-      const int e = D.pose_edges[i];
-      double xc[3], r[3], Ji[9], Jj[18];
-      edge_residual(D, e, D.q, D.t, D.X, xc, r);
-      edge_jacobians(D, e, D.q, xc, Ji, Jj);
-      double r0, r1;
-      huber(D.chi2[e], D.e_stereo[e] ? D.huber_stereo : D.huber_mono, &r0, &r1);
-      const double w = r1 * D.e_w[e];
-      double omr[3];
-      for (int k = 0; k < 3; k++) omr[k] = -(D.e_w[e] * D.err[3 * e + k]) * r1;
-      int o = 0;
-#pragma unroll
-      for (int a = 0; a < 6; a++)
-#pragma unroll
-        for (int c = a; c < 6; c++) acc[o++] += Jj[a] * w * Jj[c] + Jj[6 + a] * w * Jj[6 + c] + Jj[12 + a] * w * Jj[12 + c];
-#pragma unroll
-      for (int a = 0; a < 6; a++) acc[21 + a] += Jj[a] * omr[0] + Jj[6 + a] * omr[1] + Jj[12 + a] * omr[2];
-    }
-#pragma unroll
-    for (int k = 0; k < 27; k++) {
-      double v = acc[k];
-#pragma unroll
-      for (int ofs = 32; ofs > 0; ofs >>= 1) v += __shfl_down(v, ofs, 64);
-      if (lane == 0) {
-        if (k < 21)
-          D.Hpp[21 * f + k] = v;
-        else
-          D.bp[6 * f + (k - 21)] = v;
-      }
-    }
-  }
-  __syncthreads();
 }
 
 __device__ __forceinline__ int tri(int i, int j) { return i * (i + 1) / 2 + j; }  // packed lower, i >= j
@@ -321,254 +221,9 @@ __device__ __forceinline__ void inv3_sym(const double* h /*xx,xy,xz,yy,yz,zz*/, 
   o[5] = (a * d - b * b) * id;
 }
 
-// BlockSolver::solve (block_solver.hpp:354-487): Schur complement in LDS, LDL^T, landmark back-substitution.
-// Returns false iff a zero / non-finite pivot appears (LinearSolverEigen reports failure).
-__device__ bool solve_schur(const LbaDev& D, double lambda, double* Hs, double* bs, double* s16, int* s_flag) {
-  const int n = 6 * D.n_free;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  for (int l = threadIdx.x; l < D.n_points; l += kThreads) inv3_sym(D.Hll + 6 * (size_t)l, lambda, D.Dinv + 6 * (size_t)l);
-  for (int k = threadIdx.x; k < n * (n + 1) / 2; k += kThreads) Hs[k] = 0;
-  if (threadIdx.x == 0) *s_flag = 0;
-  __syncthreads();
-  // pose pairs (i1 >= i2), one wave per pair: Hs(i1,i2) = [i1==i2](Hpp + lambda I) - sum_l B_i1 Dinv_l B_i2^T
-  const int npairs = D.n_free * (D.n_free + 1) / 2;
-  for (int pr = wave; pr < npairs; pr += 16) {
-    int i1 = (int)((sqrt(8.0 * pr + 1.0) - 1.0) * 0.5);
-    while (i1 * (i1 + 1) / 2 > pr) i1--;
-    while ((i1 + 1) * (i1 + 2) / 2 <= pr) i1++;
-    const int i2 = pr - i1 * (i1 + 1) / 2;
-    double acc[36], accb[6];
-#pragma unroll
-    for (int k = 0; k < 36; k++) acc[k] = 0;
-#pragma unroll
-    for (int k = 0; k < 6; k++) accb[k] = 0;
-    const int* eo = D.edge_of + (size_t)i2 * D.n_points;
-    for (int i = D.pose_begin[i1] + lane; i < D.pose_begin[i1 + 1]; i += 64) {
-      const int e1 = D.pose_edges[i];
-      const int l = D.e_point[e1];
-      const int e2 = eo[l];
-      if (e2 < 0) continue;
-      const double* Bi = D.Hpl + 18 * (size_t)e1;
-      const double* Bj = D.Hpl + 18 * (size_t)e2;
-      const double* Di = D.Dinv + 6 * (size_t)l;
-      const double d9[9] = {Di[0], Di[1], Di[2], Di[1], Di[3], Di[4], Di[2], Di[4], Di[5]};
-      double BD[18];
-#pragma unroll
-      for (int a = 0; a < 6; a++)
-#pragma unroll
-        for (int c = 0; c < 3; c++) BD[3 * a + c] = Bi[3 * a] * d9[c] + Bi[3 * a + 1] * d9[3 + c] + Bi[3 * a + 2] * d9[6 + c];
-#pragma unroll
-      for (int a = 0; a < 6; a++)
-#pragma unroll
-        for (int c = 0; c < 6; c++) acc[6 * a + c] += BD[3 * a] * Bj[3 * c] + BD[3 * a + 1] * Bj[3 * c + 1] + BD[3 * a + 2] * Bj[3 * c + 2];
-      if (i1 == i2) {
-        const double* bl = D.bl + 3 * (size_t)l;
-#pragma unroll
-        for (int a = 0; a < 6; a++) accb[a] += BD[3 * a] * bl[0] + BD[3 * a + 1] * bl[1] + BD[3 * a + 2] * bl[2];
-      }
-    }
-#pragma unroll
-    for (int k = 0; k < 36; k++) {
-      double v = acc[k];
-#pragma unroll
-      for (int ofs = 32; ofs > 0; ofs >>= 1) v += __shfl_down(v, ofs, 64);
-      if (lane == 0) {
-        const int a = k / 6, c = k % 6;
-        if (i1 != i2) {
-          Hs[tri(6 * i1 + a, 6 * i2 + c)] = -v;
-        } else if (a >= c) {
-          const int ua = c, uc = a;  // Hpp upper-triangle index of (c, a)
-          const double hpp = D.Hpp[21 * i1 + (ua * 6 - ua * (ua - 1) / 2 + (uc - ua))];
-          Hs[tri(6 * i1 + a, 6 * i1 + c)] = hpp + (a == c ? lambda : 0.0) - v;
-        }
-      }
-    }
-    if (i1 == i2) {
-#pragma unroll
-      for (int k = 0; k < 6; k++) {
-        double v = accb[k];
-#pragma unroll
-        for (int ofs = 32; ofs > 0; ofs >>= 1) v += __shfl_down(v, ofs, 64);
-        if (lane == 0) bs[6 * i1 + k] = D.bp[6 * i1 + k] - v;
-      }
-    }
-  }
-  __syncthreads();
-  // LDL^T (right-looking) of the packed lower triangle; D on the diagonal, unit L below
-  for (int j = 0; j < n; j++) {
-    const double d = Hs[tri(j, j)];
-    if (threadIdx.x == 0 && (d == 0.0 || !isfinite(d))) *s_flag = 1;
-    __syncthreads();
-    if (*s_flag) return false;
-    for (int i = j + 1 + threadIdx.x; i < n; i += kThreads) Hs[tri(i, j)] /= d;
-    __syncthreads();
-    const int m = n - j - 1;  // trailing size
-    for (int k = threadIdx.x; k < m * (m + 1) / 2; k += kThreads) {
-      int r = (int)((sqrt(8.0 * k + 1.0) - 1.0) * 0.5);
-      while (r * (r + 1) / 2 > k) r--;
-      while ((r + 1) * (r + 2) / 2 <= k) r++;
-      const int c = k - r * (r + 1) / 2;
-      const int ii = j + 1 + r, kk = j + 1 + c;
-      Hs[tri(ii, kk)] -= Hs[tri(ii, j)] * Hs[tri(kk, j)] * d;
-    }
-    __syncthreads();
-  }
-  // forward, diagonal, backward substitution on bs (in place)
-  for (int j = 0; j < n; j++) {
-    const double xj = bs[j];
-    for (int i = j + 1 + threadIdx.x; i < n; i += kThreads) bs[i] -= Hs[tri(i, j)] * xj;
-    __syncthreads();
-  }
-  for (int i = threadIdx.x; i < n; i += kThreads) bs[i] /= Hs[tri(i, i)];
-  __syncthreads();
-  for (int j = n - 1; j >= 0; j--) {
-    const double xj = bs[j];
-    for (int i = threadIdx.x; i < j; i += kThreads) bs[i] -= Hs[tri(j, i)] * xj;
-    __syncthreads();
-  }
-  for (int i = threadIdx.x; i < n; i += kThreads) D.xp[i] = bs[i];
-  // landmarks: xl = Dinv (bl - Hpl^T xp)
-  for (int l = threadIdx.x; l < D.n_points; l += kThreads) {
-    double cl[3] = {D.bl[3 * (size_t)l], D.bl[3 * (size_t)l + 1], D.bl[3 * (size_t)l + 2]};
-    for (int e = D.pt_begin[l]; e < D.pt_begin[l + 1]; e++) {
-      const int f = D.free_index[D.e_pose[e]];
-      if (f < 0) continue;
-      const double* B = D.Hpl + 18 * (size_t)e;
-      for (int c = 0; c < 3; c++)
-        for (int a = 0; a < 6; a++) cl[c] -= B[3 * a + c] * bs[6 * f + a];
-    }
-    const double* Di = D.Dinv + 6 * (size_t)l;
-    D.xl[3 * (size_t)l] = Di[0] * cl[0] + Di[1] * cl[1] + Di[2] * cl[2];
-    D.xl[3 * (size_t)l + 1] = Di[1] * cl[0] + Di[3] * cl[1] + Di[4] * cl[2];
-    D.xl[3 * (size_t)l + 2] = Di[2] * cl[0] + Di[4] * cl[1] + Di[5] * cl[2];
-  }
-  __syncthreads();
-  return true;
-}
-
-// SparseOptimizer::optimize + OptimizationAlgorithmLevenberg::solve
-// (core/sparse_optimizer.cpp:354-419, core/optimization_algorithm_levenberg.cpp:61-168)
-__global__ __launch_bounds__(kThreads) void k_lba(LbaDev D) {
-  extern __shared__ __align__(16) double lds[];
-  __shared__ double s16[16];
-  __shared__ int s_flag;
-  const int n = 6 * D.n_free;
-  double* Hs = lds;
-  double* bs = lds + (size_t)n * (n + 1) / 2;
-  // load the initial estimates (SE3Quat ctor normalises the quaternion, src/Optimizer.cc:1693-1694)
-  for (int i = threadIdx.x; i < D.n_poses; i += kThreads) {
-    double q[4] = {D.pose_q0[4 * i], D.pose_q0[4 * i + 1], D.pose_q0[4 * i + 2], D.pose_q0[4 * i + 3]};
-    normalize_rotation(q);
-    for (int k = 0; k < 4; k++) D.q[4 * i + k] = D.q_try[4 * i + k] = q[k];
-    for (int k = 0; k < 3; k++) D.t[3 * i + k] = D.t_try[3 * i + k] = D.pose_t0[3 * i + k];
-  }
-  for (int i = threadIdx.x; i < 3 * D.n_points; i += kThreads) D.X[i] = D.X_try[i] = D.points0[i];
-  __syncthreads();
-  const double tau = 1e-5, good_up = 2. / 3., good_lo = 1. / 3.;
-  double lambda = -1, ni = 2, last_chi = 0;
-  int n_bad = 0, iters = 0;
-  if (D.mode == 1 || D.iterations <= 0) {
-    const double chi = compute_errors(D, D.q, D.t, D.X, s16);
-    if (D.mode == 1) build_system(D, s16);
-    if (threadIdx.x == 0) {
-      D.out_info[0] = 0;
-      D.out_info[1] = 0;
-      D.out_stats[0] = chi;
-      D.out_stats[1] = 0;
-    }
-    return;
-  }
-  for (int iteration = 0; iteration < D.iterations; iteration++) {
-    if (threadIdx.x == 0) s_flag = *D.stop;  // SparseOptimizer::terminate(): one reader, block-uniform decision
-    __syncthreads();
-    const int stop_now = s_flag;
-    __syncthreads();
-    if (stop_now) break;
-    double current_chi = compute_errors(D, D.q, D.t, D.X, s16);
-    const double ini_chi = current_chi;
-    build_system(D, s16);
-    if (iteration == 0) {  // computeLambdaInit
-      double mx = 0;
-      for (int i = threadIdx.x; i < D.n_free * 6; i += kThreads) {
-        const int f = i / 6, a = i % 6;
-        mx = fmax(mx, fabs(D.Hpp[21 * f + (a * 6 - a * (a - 1) / 2)]));
-      }
-      for (int i = threadIdx.x; i < D.n_points * 3; i += kThreads) {
-        const int l = i / 3, a = i % 3;
-        mx = fmax(mx, fabs(D.Hll[6 * (size_t)l + (a == 0 ? 0 : a == 1 ? 3 : 5)]));
-      }
-      lambda = tau * block_max(mx, s16);
-      ni = 2;
-      n_bad = 0;
-    }
-    double rho = 0;
-    int qmax = 0;
-    bool stopped = false;
-    do {
-      const bool ok2 = solve_schur(D, lambda, Hs, bs, s16, &s_flag);
-      double temp_chi, scale = 0;
-      if (ok2) {
-        for (int f = threadIdx.x; f < D.n_free; f += kThreads) {
-          const int p = D.free_pose[f];
-          pose_oplus(D.q + 4 * p, D.t + 3 * p, D.xp + 6 * f, D.q_try + 4 * p, D.t_try + 3 * p);
-        }
-        for (int i = threadIdx.x; i < 3 * D.n_points; i += kThreads) D.X_try[i] = D.X[i] + D.xl[i];
-        __syncthreads();
-        temp_chi = compute_errors(D, D.q_try, D.t_try, D.X_try, s16);
-        double loc = 0;  // computeScale
-        for (int i = threadIdx.x; i < n; i += kThreads) {
-          const int f = i / 6, a = i % 6;
-          loc += D.xp[i] * (lambda * D.xp[i] + D.bp[6 * f + a]);
-        }
-        for (int i = threadIdx.x; i < 3 * D.n_points; i += kThreads) loc += D.xl[i] * (lambda * D.xl[i] + D.bl[i]);
-        scale = block_sum(loc, s16);
-      } else {
-        temp_chi = compute_errors(D, D.q, D.t, D.X, s16);
-        temp_chi = 1.79769313486231570e308;
-      }
-      rho = (current_chi - temp_chi) / (scale + 1e-3);
-      if (rho > 0 && isfinite(temp_chi)) {
-        double alpha = 1. - gfs_glibc::pow3(2 * rho - 1);
-        alpha = fmin(alpha, good_up);
-        lambda *= fmax(good_lo, alpha);
-        ni = 2;
-        current_chi = temp_chi;
-        for (int f = threadIdx.x; f < D.n_free; f += kThreads) {  // discardTop: keep the trial
-          const int p = D.free_pose[f];
-          for (int k = 0; k < 4; k++) D.q[4 * p + k] = D.q_try[4 * p + k];
-          for (int k = 0; k < 3; k++) D.t[3 * p + k] = D.t_try[3 * p + k];
-        }
-        for (int i = threadIdx.x; i < 3 * D.n_points; i += kThreads) D.X[i] = D.X_try[i];
-      } else {
-        lambda *= ni;
-        ni *= 2;
-      }
-      if (threadIdx.x == 0) s_flag = *D.stop;
-      __syncthreads();
-      qmax++;
-      stopped = s_flag != 0;
-      __syncthreads();
-    } while (rho < 0 && qmax < 10 && !stopped);
-    iters++;
-    last_chi = current_chi;
-    if (qmax == 10 || rho == 0) break;
-    if ((ini_chi - current_chi) * 1e3 < ini_chi)
-      n_bad++;
-    else
-      n_bad = 0;
-    if (n_bad >= 3) break;
-  }
-  if (threadIdx.x == 0) {
-    D.out_info[0] = iters;
-    D.out_info[1] = 0;
-    D.out_stats[0] = last_chi;
-    D.out_stats[1] = lambda;
-  }
-}
-
 // ================================================================================================
-// Multi-kernel path: the same algorithm, one launch per phase so that every phase uses the whole chip instead of one
-// CU (the single-workgroup kernel above is latency-bound: 61 ms for the C5 window).  The scalar LM logic lives in
+// The phase kernels: one launch per phase so that every phase uses the whole chip instead of one CU (the whole LM loop in a
+// single workgroup, the first implementation, was latency-bound: 61 ms for the C5 window).  The scalar LM logic lives in
 // LbaState (HBM) and runs in k_lba_begin / k_lba_decide; the host only enqueues the phases and reads two flags per trial.
 // The two estimate buffers (q/t/X and q_try/t_try/X_try) swap roles when a step is accepted (S->cur).
 // ================================================================================================
@@ -1347,16 +1002,21 @@ __global__ __launch_bounds__(kMk) void k_lba_schur_reduce(LbaDev D, int gate) {
 
 
 
-// LDL^T + triangular solves of the reduced pose system by a single workgroup.  kLds: the packed triangle fits the 160 KB of
-// LDS (n <= 180, i.e. up to 30 free poses) and is factored there.  Otherwise (larger windows) it is factored in place in HBM /
-// L2; only the right-hand side and the current 6-column panel are held in LDS, so the trailing update reads and writes each
-// element once.  Same arithmetic, same order of operations per entry in both variants.
+// LDL^T + triangular solves of the reduced pose system by a single workgroup, 6-wide block columns (n = 6 n_free).  Two solvers
+// with two arithmetics; a window takes the one its size selects (kMaxFreeLds), alone or in a batch, so its result does not depend
+// on its company:
+//  - b_solve_lds: the packed triangle fits the 160 KB of LDS (n <= 180, i.e. up to 30 free poses) and is factored there, with
+//    reciprocal pivots and fused multiply-adds;
+//  - b_solve_hbm (larger windows): factored in place in HBM / L2 with divisions and separately rounded products, the subtraction
+//    sequence of the column-by-column form.
+// The reference solves this system with a sparse Cholesky (g2o LinearSolverEigen): there is no operation order to follow in
+// either, only a fixed one to keep.
+//
 // The reduced system in LDS (n <= 180): LDL^T by 6-wide block columns with the pivots' reciprocals and the scaled panel
 // P = L D kept beside L, so that a panel row costs 15 fused multiply-adds + 6 products instead of 6 dependent divisions and the
 // trailing update 6 fused multiply-adds an entry; the forward substitution rides along with the factorisation (the right-hand
 // side is one more row of every panel), and the backward substitution is done by a single wave (n values, no workgroup
-// barriers).  The reference solves this system with a sparse Cholesky (g2o LinearSolverEigen): there is no operation order to
-// follow here, only a fixed one to keep.
+// barriers).
 __device__ __forceinline__ void b_solve_lds(const LbaDev& D) {
   extern __shared__ __align__(16) double lds[];
   __shared__ int s_flag;
@@ -1479,15 +1139,15 @@ __device__ __forceinline__ void b_solve_lds(const LbaDev& D) {
   for (int i = lane; i < n; i += 64) D.xp[i] = bs[i];
 }
 
-template <bool kLds>
-__device__ __forceinline__ void b_solve(const LbaDev& D) {
+// The reduced system in HBM / L2 (n > 180), factored in place: only the right-hand side and the current 6-column panel are held
+// in LDS, so the trailing update reads and writes each element once.
+__device__ __forceinline__ void b_solve_hbm(const LbaDev& D) {
   extern __shared__ __align__(16) double lds[];
   __shared__ int s_flag;
   const int n = 6 * D.n_free;
-  double* Hs = kLds ? lds : D.Hs;
-  double* bs = kLds ? lds + (size_t)n * (n + 1) / 2 : lds;
-  double* pan = lds + n;  // !kLds only: panel rows [n][6] followed by the 6 pivots
-  if (kLds) gfs::strided_batch<8>(D.Hs, (int)threadIdx.x, kThreads, n * (n + 1) / 2, [&](int k, double v) { Hs[k] = v; });
+  double* Hs = D.Hs;
+  double* bs = lds;       // [n]
+  double* pan = lds + n;  // panel rows [n][6] followed by the 6 pivots
   for (int k = threadIdx.x; k < n; k += kThreads) bs[k] = D.bs[k];
   if (threadIdx.x == 0) s_flag = 0;
   __syncthreads();
@@ -1497,7 +1157,7 @@ __device__ __forceinline__ void b_solve(const LbaDev& D) {
   //   independent), (c) the trailing triangle takes the rank-6 update.
   bool ok = true;
   for (int jb = 0; jb < n && ok; jb += 6) {
-    if (threadIdx.x == 0) {  // the 21 entries are pulled into registers first: one LDS latency instead of ~100 dependent ones
+    if (threadIdx.x == 0) {  // the 21 entries are pulled into registers first: one memory latency instead of ~100 dependent ones
       double a[6][6];
 #pragma unroll
       for (int i = 0; i < 6; i++)
@@ -1536,12 +1196,10 @@ __device__ __forceinline__ void b_solve(const LbaDev& D) {
       }
     }
     __syncthreads();
-    const int m = n - jb - 6;  // (c) trailing size
-    if (!kLds) {               // panel and pivots into LDS: the update then touches HBM once per element
-      for (int k = threadIdx.x; k < 6 * m; k += kThreads) pan[k] = Hs[tri(jb + 6 + k / 6, jb + k % 6)];
-      if (threadIdx.x < 6) pan[6 * m + threadIdx.x] = Hs[tri(jb + threadIdx.x, jb + threadIdx.x)];
-      __syncthreads();
-    }
+    const int m = n - jb - 6;  // (c) trailing size; panel and pivots into LDS: the update then touches HBM once per element
+    for (int k = threadIdx.x; k < 6 * m; k += kThreads) pan[k] = Hs[tri(jb + 6 + k / 6, jb + k % 6)];
+    if (threadIdx.x < 6) pan[6 * m + threadIdx.x] = Hs[tri(jb + threadIdx.x, jb + threadIdx.x)];
+    __syncthreads();
     for (int k = threadIdx.x; k < m * (m + 1) / 2; k += kThreads) {
       int r = (int)((sqrt(8.0 * k + 1.0) - 1.0) * 0.5);
       while (r * (r + 1) / 2 > k) r--;
@@ -1549,11 +1207,7 @@ __device__ __forceinline__ void b_solve(const LbaDev& D) {
       const int c = k - r * (r + 1) / 2;
       const int ii = jb + 6 + r, kk = jb + 6 + c;
       double v = Hs[tri(ii, kk)];
-      if (kLds) {
-        for (int c2 = 0; c2 < 6; c2++) v -= Hs[tri(ii, jb + c2)] * Hs[tri(kk, jb + c2)] * Hs[tri(jb + c2, jb + c2)];
-      } else {
-        for (int c2 = 0; c2 < 6; c2++) v -= pan[6 * r + c2] * pan[6 * c + c2] * pan[6 * m + c2];
-      }
+      for (int c2 = 0; c2 < 6; c2++) v -= pan[6 * r + c2] * pan[6 * c + c2] * pan[6 * m + c2];
       Hs[tri(ii, kk)] = v;
     }
     __syncthreads();
@@ -1621,7 +1275,7 @@ __global__ __launch_bounds__(kThreads) void k_lba_solve(LbaDev D, int gate) {
   if (kLds)
     b_solve_lds(D);
   else
-    b_solve<false>(D);
+    b_solve_hbm(D);
 }
 
 
@@ -1784,7 +1438,7 @@ __global__ void k_lba_finish(LbaDev D) { b_finish(D, blockIdx.x); }
 
 // the results of a window gathered into one block (one copy to the host instead of six): layout of LbaDev::out_pack
 __device__ __forceinline__ void b_pack(const LbaDev& D, const int bx, const int gdx) {
-  const int cur = D.out_info[1];  // which estimate buffer holds the accepted state (b_finish; 0 on the single-workgroup path)
+  const int cur = D.out_info[1];  // which estimate buffer holds the accepted state (b_finish)
   const double *q = sel(D.q, D.q_try, cur), *t = sel(D.t, D.t_try, cur), *X = sel(D.X, D.X_try, cur);
   const int E = D.n_edges, NQ = D.n_poses, NP = D.n_points;
   double* o = D.out_pack;
@@ -1887,7 +1541,7 @@ __global__ __launch_bounds__(kThreads) void kb_lba_solve(const LbaDev* __restric
   if (kLds)
     b_solve_lds(D);
   else
-    b_solve<false>(D);
+    b_solve_hbm(D);
 }
 __global__ __launch_bounds__(kMk) void kb_lba_update(const LbaDev* __restrict__ DD) {
   GFS_LBAB_PROLOGUE(1, D.n_upd_blocks)
@@ -1922,14 +1576,10 @@ __global__ __launch_bounds__(kMk) void kb_lba_pack(const LbaDev* __restrict__ DD
 // host -> device through the pinned arena (bump allocation; the arena outlives the asynchronous copies of one call)
 }  // namespace
 
-struct gfs_lba_batch;
-extern "C" void gfs_lba_batch_destroy(gfs_lba_batch* b);
 struct gfs_lba {
-  gfs_lba_batch* self_batch = nullptr;  // one-window wrapper: gfs_lba_solve runs through the batched (device-driven) LM loop
   int device, max_poses, max_points, max_edges;
   hipStream_t stream;
   std::mutex mu;
-  int* h_stop = nullptr;  // host-mapped
   int* h_flags = nullptr;  // host-mapped, two slots of kFlagInts ints: {again, terminate, cur, iters | lambda, last_chi (doubles)} written by k_lba_decide
   hipEvent_t ev_decide[2] = {nullptr, nullptr};  // behind decide i: event i & 1 -- the host waits for THIS, not for what is queued behind it
   LbaDev last_desc;        // the window of the last run()
@@ -2141,10 +1791,6 @@ int upload_and_fill(gfs_lba* h, const gfs_lba_problem* p, const HostPrep& P, int
   D.bp = (decltype(D.bp))(h->d_bp.p);
   D.xl = (decltype(D.xl))(h->d_xl.p);
   D.xp = (decltype(D.xp))(h->d_xp.p);
-  int* d_stop = nullptr;
-  GFS_HIP(hipHostGetDevicePointer((void**)&d_stop, h->h_stop, 0));
-  *h->h_stop = 0;
-  D.stop = (decltype(D.stop))(d_stop);
   D.out_info = (decltype(D.out_info))(h->d_info.p);
   D.out_stats = (decltype(D.out_stats))(h->d_stats.p);
   D.out_pack = (decltype(D.out_pack))(h->d_out.p);
@@ -2215,7 +1861,7 @@ int lba_raise_lds_limits(int device) {
   std::lock_guard<std::mutex> lk(mu);
   if (device >= 0 && device < 64 && done[device]) return GFS_OK;
   const int lim = 160 * 1024 - 1024;
-  const void* fns[] = {(const void*)k_lba, (const void*)k_lba_solve<true>, (const void*)k_lba_solve<false>, (const void*)kb_lba_solve<true>,
+  const void* fns[] = {(const void*)k_lba_solve<true>, (const void*)k_lba_solve<false>, (const void*)kb_lba_solve<true>,
                        (const void*)kb_lba_solve<false>, (const void*)k_lba_schur_chunks, (const void*)kb_lba_schur_chunks,
                        (const void*)k_lba_schur_mfma<true>, (const void*)k_lba_schur_mfma<false>, (const void*)kb_lba_schur_mfma<true>,
                        (const void*)kb_lba_schur_mfma<false>};
@@ -2241,7 +1887,6 @@ struct LidarRun {
 
 int run(gfs_lba* h, const gfs_lba_problem* p, const HostPrep& P, int mode, StopFlag stop, const LidarRun* lid = nullptr) {
   hipStream_t s = h->stream;
-  const int E = p->n_edges;
   LbaDev D;
   int rc = upload_and_fill(h, p, P, mode, s, D);
   if (rc) return rc;
@@ -2264,23 +1909,8 @@ int run(gfs_lba* h, const gfs_lba_problem* p, const HostPrep& P, int mode, StopF
   const bool in_lds = P.n_free <= kMaxFreeLds;
   const size_t lds = (in_lds ? (size_t)n * (n + 1) / 2 + 8 * n + 8 : (size_t)7 * n + 8) * sizeof(double);
   GFS_REQUIRE(lds <= 160 * 1024, GFS_ERR_CAPACITY, "gfs_lba: %d free poses exceed the solver's workspace", P.n_free);
-  static const bool single_wg = getenv("GFS_LBA_SINGLE_WG") != nullptr;  // the round-1a kernel: whole solve in one workgroup
   h->last_desc = D;
-  if (single_wg && in_lds && D.n_lidar_kf == 0) {  // (the lidar entry always runs the multi-kernel path)
-    GFS_REQUIRE(!D.e_dup, GFS_ERR_UNSUPPORTED, "gfs_lba: GFS_LBA_SINGLE_WG does not take several edges between one pose and one point");
-    if (E) GFS_HIP(hipMemsetAsync(h->d_Hpl.p, 0, (size_t)E * 18 * sizeof(double), s));
-    GFS_LAUNCH("k_lba", k_lba, dim3(1), dim3(kThreads), lds, s, D);
-    // setForceStopFlag semantics (src/Optimizer.cc:1679): relay the caller's flag to the device-visible one
-    if (stop) {
-      while (hipStreamQuery(s) == hipErrorNotReady) {
-        if (*stop) *h->h_stop = 1;
-        std::this_thread::sleep_for(std::chrono::microseconds(50));
-      }
-    }
-    GFS_HIP(hipStreamSynchronize(s));
-    return GFS_OK;
-  }
-  // ---- multi-kernel path: one launch per phase, the host walks the LM control flow from two flags per trial
+  // one launch per phase, the host walks the LM control flow from two flags per trial
   static const bool timing = getenv("GFS_LBA_TIMING") != nullptr;
   if (timing) GFS_HIP(hipStreamSynchronize(s));
   const auto Ta = std::chrono::steady_clock::now();
@@ -2314,8 +1944,6 @@ int run(gfs_lba* h, const gfs_lba_problem* p, const HostPrep& P, int mode, StopF
   // g2o looks (top of an iteration, end of a rejected trial); if it is up when an iteration is already running ahead, that iteration
   // is DISCARDED: its trial wrote only the other estimate buffer, the scalar state decide k left is put back from its snapshot
   // (k_lba_restore) and the errors are evaluated again at that estimate -- what the loop without the look-ahead would have left.
-  // GFS_LBA_SPECULATE=0: that loop (every launch once the flags are known).
-  static const bool speculate = !(getenv("GFS_LBA_SPECULATE") && atoi(getenv("GFS_LBA_SPECULATE")) == 0);
   auto build_group = [&](int iteration, int gate) -> int {
     GFS_LAUNCH("k_lba_errors", k_lba_errors, g_err, dim3(kMk), 0, s, D, 0, gate);
     if (D.n_lm_wg > 0) GFS_LAUNCH("k_lba_build_landmarks", k_lba_build_landmarks, g_lm, dim3(kMk), 0, s, D, gate);
@@ -2351,29 +1979,7 @@ int run(gfs_lba* h, const gfs_lba_problem* p, const HostPrep& P, int mode, StopF
     return GFS_OK;
   };
   auto flags_of = [&](int i) { return h->h_flags + kFlagInts * (i & 1); };
-  if (!speculate) {
-    for (int iteration = 0; iteration < p->iterations; iteration++) {
-      if (stop && *stop) break;  // SparseOptimizer::terminate() at the top of the iteration
-      if ((rc = build_group(iteration, 0))) return rc;
-      bool terminate = false;
-      for (;;) {
-        if ((rc = trial_group(0))) return rc;
-        GFS_HIP(hipStreamSynchronize(s));
-        const int* f = flags_of(n_decides - 1);
-        const bool again = f[0] != 0;
-        terminate = f[1] != 0;
-        if (!again) break;
-        if (stop && *stop) {  // the stop flag ends the trial loop: close the iteration's bookkeeping on the device
-          GFS_LAUNCH("k_lba_decide", k_lba_decide, dim3(1), dim3(64), 0, s, D, 1, d_flags + kFlagInts * (n_decides & 1), 0);
-          n_decides++;
-          GFS_HIP(hipStreamSynchronize(s));
-          terminate = flags_of(n_decides - 1)[1] != 0;
-          break;
-        }
-      }
-      if (terminate) break;
-    }
-  } else if (!(stop && *stop)) {
+  if (!(stop && *stop)) {
     int iteration = 0;
     if ((rc = build_group(0, 0)) || (rc = trial_group(0))) return rc;
     int waiting = n_decides - 1;  // the decide whose verdict the host waits for next
@@ -2506,7 +2112,6 @@ int gfs_lba_create(int device, int max_poses, int max_points, int max_edges, gfs
   h->max_edges = max_edges;
   GFS_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
   if (int rc0 = lba_raise_lds_limits(device)) return rc0;
-  GFS_HIP(hipHostMalloc((void**)&h->h_stop, sizeof(int), hipHostMallocMapped));
   GFS_HIP(hipHostMalloc((void**)&h->h_flags, 2 * kFlagInts * sizeof(int), hipHostMallocMapped));
   for (int k = 0; k < 2; k++) GFS_HIP(hipEventCreateWithFlags(&h->ev_decide[k], hipEventDisableTiming));
   const size_t NP = max_points, E = max_edges, NQ = max_poses, F = max_poses;
@@ -2548,11 +2153,8 @@ int gfs_lba_create(int device, int max_poses, int max_points, int max_edges, gfs
 void gfs_lba_destroy(gfs_lba* h) {
   if (!h) return;
   (void)hipSetDevice(h->device);
-  if (h->self_batch) gfs_lba_batch_destroy(h->self_batch);  // (a wrapper: it does not own this window)
-  h->self_batch = nullptr;
   (void)hipStreamSynchronize(h->stream);
   (void)hipStreamDestroy(h->stream);
-  if (h->h_stop) (void)hipHostFree(h->h_stop);
   if (h->h_flags) (void)hipHostFree(h->h_flags);
   for (int k = 0; k < 2; k++)
     if (h->ev_decide[k]) (void)hipEventDestroy(h->ev_decide[k]);
@@ -2599,7 +2201,6 @@ static void lba_fetch_finish(const gfs_lba_problem* p, const HostPrep& P, const 
   sol->final_lambda = stats[1];
 }
 
-static int lba_solve_one_batched(gfs_lba* h, const gfs_lba_problem* p, gfs_lba_solution* sol, StopFlag stop);
 static int lba_solve_lidar_impl(gfs_lba* h, const gfs_lba_problem* p, const gfs_lba_lidar* L, gfs_lba_solution* sol,
                                 int32_t* pose_lidar_edges, StopFlag stop) {
   GFS_REQUIRE(h && p && L && sol, GFS_ERR_INVALID_ARG, "gfs_lba_solve_lidar: NULL argument");
@@ -2632,12 +2233,6 @@ static int lba_solve_impl(gfs_lba* h, const gfs_lba_problem* p, gfs_lba_solution
     gfs::set_error("gfs_lba_solve: stop flag raised before optimisation");
     return GFS_ERR_STOPPED;
   }
-  // GFS_LBA_SINGLE=batched: one window through the batched kernels, whose LM state machine lives on the device (the host queues
-  // rounds ahead and polls one round behind instead of waiting for two flags after every trial).  Measured in round 4: 2.29 ms
-  // against 2.23 ms for the host-driven loop below -- the descriptor indirection and the gated launches of the batched kernels
-  // cost what the saved round trips return -- so it is not the default.  Same arithmetic, bit-identical results.
-  static const bool batched_loop = getenv("GFS_LBA_SINGLE") && strcmp(getenv("GFS_LBA_SINGLE"), "batched") == 0 && !getenv("GFS_LBA_SINGLE_WG");
-  if (batched_loop) return lba_solve_one_batched(h, p, sol, stop);
   std::lock_guard<std::mutex> lk(h->mu);
   GFS_HIP(hipSetDevice(h->device));
   static const bool timing = getenv("GFS_LBA_TIMING") != nullptr;
@@ -2673,7 +2268,6 @@ struct gfs_lba_batch {
   gfs::DevBuf<int> d_flags, d_done;
   int* h_done = nullptr;           // pinned copy targets of the done counter (two rounds in flight)
   hipEvent_t ev_round[2] = {nullptr, nullptr};
-  bool owns_windows = true;        // false: the one-window wrapper of a gfs_lba (gfs_lba_solve runs through the batched kernels)
   gfs::PinBuf<int> h_cur;          // per window: which estimate buffer holds the result
   std::vector<HostPrep> prep;
 };
@@ -2722,8 +2316,7 @@ void gfs_lba_batch_destroy(gfs_lba_batch* b) {
   if (!b) return;
   (void)hipSetDevice(b->device);
   if (b->stream) (void)hipStreamSynchronize(b->stream);
-  if (b->owns_windows)
-    for (gfs_lba* x : b->win) gfs_lba_destroy(x);
+  for (gfs_lba* x : b->win) gfs_lba_destroy(x);
   if (b->stream) (void)hipStreamDestroy(b->stream);
   for (int k = 0; k < 2; k++)
     if (b->ev_round[k]) (void)hipEventDestroy(b->ev_round[k]);
@@ -2785,12 +2378,6 @@ static int lba_solve_batch_impl(gfs_lba_batch* b, const gfs_lba_problem* problem
     LbaDev D;
     const int rc = upload_and_fill(b->win[w], &problems[w], b->prep[w], 0, s, D, false);
     if (rc) return rc;
-    {
-      void* dstop = nullptr;
-      GFS_HIP(hipHostGetDevicePointer(&dstop, b->win[w]->h_stop, 0));
-      D.stop = (decltype(D.stop))dstop;
-    }
-    *b->win[w]->h_stop = 0;
     b->h_desc.p[w] = D;
     max_free = std::max(max_free, D.n_free);
     max_err = std::max(max_err, D.n_err_blocks);
@@ -2828,7 +2415,6 @@ static int lba_solve_batch_impl(gfs_lba_batch* b, const gfs_lba_problem* problem
   int rounds_run = 0;
   GFS_LAUNCH("kb_lba_init", kb_lba_init, dim3(64, n), dim3(kMk), 0, s, DD);
   const int max_rounds = std::max(max_iter, 0) * 11 + 1;  // (windows with iterations <= 0 leave in the first round, after the errors)
-  bool stopped = false;
   for (int round = 0; round < max_rounds; round++) {
     GFS_LAUNCH("kb_lba_errors", kb_lba_errors, dim3(max_err, n), dim3(kMk), 0, s, DD, 0);
     GFS_LAUNCH("kb_lba_build_landmarks", kb_lba_build_landmarks, dim3(max_lm, n), dim3(kMk), 0, s, DD);
@@ -2858,14 +2444,8 @@ static int lba_solve_batch_impl(gfs_lba_batch* b, const gfs_lba_problem* problem
     GFS_HIP(hipMemcpyAsync(b->h_done + (round & 1), b->d_done.p, sizeof(int), hipMemcpyDeviceToHost, s));
     GFS_HIP(hipEventRecord(b->ev_round[round & 1], s));
     rounds_run++;
-    static const bool poll_sync = getenv("GFS_LBA_POLL") && strcmp(getenv("GFS_LBA_POLL"), "sync") == 0;  // A/B: wait for every round
-    if (force_end || poll_sync) {
+    if (force_end) {
       GFS_HIP(hipStreamSynchronize(s));
-      if (poll_sync && !force_end) {
-        if (b->h_done[round & 1] >= n) break;
-        continue;
-      }
-      stopped = true;
       break;
     }
     if (round >= 1) {
@@ -2873,7 +2453,6 @@ static int lba_solve_batch_impl(gfs_lba_batch* b, const gfs_lba_problem* problem
       if (b->h_done[(round - 1) & 1] >= n) break;
     }
   }
-  (void)stopped;
   const auto T3 = now();
   GFS_LAUNCH("kb_lba_finish", kb_lba_finish, dim3(n), dim3(64), 0, s, DD);
   GFS_LAUNCH("kb_lba_pack", kb_lba_pack, dim3(8, n), dim3(kMk), 0, s, DD);
@@ -2901,39 +2480,6 @@ static int lba_solve_batch_impl(gfs_lba_batch* b, const gfs_lba_problem* problem
     fprintf(stderr, "gfs_lba_solve_batch(%d): prepare %.2f, upload %.2f, %d rounds %.2f, download %.2f, scatter %.2f ms\n", n, ms(T0, T1),
             ms(T1, T2), rounds_run, ms(T2, T3), ms(T3, T4), ms(T4, now()));
   return GFS_OK;
-}
-
-// gfs_lba_solve through the batched path: a wrapper batch of one window around the handle itself (created on first use)
-static int lba_solve_one_batched(gfs_lba* h, const gfs_lba_problem* p, gfs_lba_solution* sol, StopFlag stop) {
-  {
-    std::lock_guard<std::mutex> lk(h->mu);
-    if (!h->self_batch) {
-      GFS_HIP(hipSetDevice(h->device));
-      std::unique_ptr<gfs_lba_batch> b(new gfs_lba_batch);
-      b->device = h->device;
-      b->max_windows = 1;
-      b->owns_windows = false;
-      b->win.push_back(h);
-      int rc = 0;
-      if (hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking) != hipSuccess) rc = GFS_ERR_HIP;
-      if (!rc && ((rc = b->d_desc.alloc(1)) || (rc = b->h_desc.alloc(1)) || (rc = b->d_flags.alloc(4)) || (rc = b->d_done.alloc(1)) ||
-                  (rc = b->h_cur.alloc(1)))) {
-      }
-      if (!rc && hipHostMalloc((void**)&b->h_done, 2 * sizeof(int), hipHostMallocDefault) != hipSuccess) rc = GFS_ERR_HIP;
-      for (int k = 0; k < 2 && !rc; k++)
-        if (hipEventCreateWithFlags(&b->ev_round[k], hipEventDisableTiming) != hipSuccess) rc = GFS_ERR_HIP;
-      if (rc) {
-        gfs::set_error("gfs_lba_solve: could not set up the one-window batch");
-        gfs_lba_batch_destroy(b.release());
-        return rc;
-      }
-      b->prep.resize(1);
-      h->self_batch = b.release();
-    }
-  }
-  const int rc = lba_solve_batch_impl(h->self_batch, p, sol, 1, stop);
-  if (rc == GFS_ERR_STOPPED) gfs::set_error("gfs_lba_solve: stop flag raised before optimisation");
-  return rc;
 }
 
 static int lba_linearize_impl(gfs_lba* h, const gfs_lba_problem* p, const gfs_lba_lidar* L, double* Hpp, double* Hll, double* Hpl,

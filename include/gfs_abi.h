@@ -292,8 +292,8 @@ int gfs_lba_solve_batch(gfs_lba_batch* h, const gfs_lba_problem* problems, gfs_l
  * The reprojection-edge outputs (chi2, depth, num_edges) are those of gfs_lba_solve; lidar edges only move the estimate.  Fixed
  * cameras (pose_local = 0) never get edges.  A window without lidar key-frames runs gfs_lba_solve's path: the same bits.
  * Refused: a map on another device or never set (GFS_ERR_INVALID_ARG), lidar key-frames' clouds beyond the capacity reserved with
- * gfs_lba_lidar_reserve (GFS_ERR_CAPACITY; nothing is truncated), two_camera != 0 (GFS_ERR_UNSUPPORTED).  GFS_LBA_SINGLE_WG and
- * GFS_LBA_SINGLE=batched do not apply to this entry.  DESIGN.md "Local BA with lidar edges". */
+ * gfs_lba_lidar_reserve (GFS_ERR_CAPACITY; nothing is truncated), two_camera != 0 (GFS_ERR_UNSUPPORTED).
+ * DESIGN.md "Local BA with lidar edges". */
 typedef struct {
   const struct gfs_lidar_map* map; /* laserCloudSurfFromMapDS (section 11), on the handle's device */
   const uint8_t* pose_local;      /* [n_poses] 1 = in lLocalKeyFrames (the fixed initial key-frame included), 0 = fixed camera */

@@ -1,12 +1,17 @@
 """GPU parity tests for LocalBundleAdjustment (MI355X): normal-equation blocks within 1e-10 relative of the CPU
 oracle, optimised poses / points within 1e-5 relative Frobenius (BASELINE.json north_star tolerance), identical
 outlier classification, LM iteration counts equal."""
+import os
+import subprocess
+import sys
+
 import numpy as np
 import pytest
 
 from geoflowslam_amd import synth
 
 pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _rel(a, b):
@@ -279,3 +284,85 @@ def test_batch_mixing_one_block_and_several_block_schur_windows(gpu_api):
         assert r["iterations_run"] == r1["iterations_run"]
         for key in ("pose_q", "pose_t", "points", "edge_chi2", "edge_depth_positive"):
             assert np.array_equal(r[key], r1[key]), (w["n_poses"], key)
+
+
+_SOLVED = ("pose_q", "pose_t", "points", "edge_chi2", "edge_depth_positive")
+_SCHUR_KERNELS = {"chunks": "lba_schur_chunks", "pairs": "lba_schur"}  # behind k_ (one window) and kb_ (batch)
+
+
+def _fallback_windows():
+    """the smallest shapes at which the vector Schur kernels can still go wrong"""
+    base = synth.lba_window(4, n_free=3, n_fixed=2, n_points=50)
+    return [synth.lba_window(2, n_free=3, n_fixed=1, n_points=80, mono_frac=1.0),  # 6 pose pairs: one partial tile; 2 chunks of kSchurPts = 64
+            synth.lba_window(34, n_free=24, n_fixed=2, n_points=300),  # 300 pose pairs > kMk = 256: two pair tiles; 5 chunks, the last partial
+            _with_second_camera_edges(synth.lba_window(12, n_free=6, n_fixed=2, n_points=300), 12),  # several edges a (pose, point): e_dup
+            dict(base, pose_fixed=np.ones_like(base["pose_fixed"]))]  # n_free = 0: no Schur launch at all
+
+
+def _collect_fallbacks(api):
+    """every window alone and all of them in one batch, the blocks of the first, and which kernels were launched"""
+    wins = _fallback_windows()
+    api.profile_enable(True)
+    opt = api.Optimizer(max_poses=32, max_points=512, max_edges=16384)
+    bat = api.BatchOptimizer(max_windows=len(wins), max_poses=32, max_points=512, max_edges=16384)
+    out = {}
+    for tag, res in (("one", [opt.LocalBundleAdjustment(w) for w in wins]), ("bat", bat.LocalBundleAdjustment(wins))):
+        for i, r in enumerate(res):
+            for k in _SOLVED:
+                out[f"{tag}{i}/{k}"] = r[k]
+            out[f"{tag}{i}/stats"] = np.array([r["iterations_run"], r["final_chi2"], r["final_lambda"]], np.float64)
+    for k, v in opt.linearize(wins[0]).items():
+        out["lin/" + k] = np.asarray(v)
+    out["launched"] = np.array(sorted(name for name, (_, n) in api.profile_report().items() if n > 0))
+    return out
+
+
+def _child(tmp_path, env_knob, value):
+    out = str(tmp_path / f"{env_knob}_{value}.npz")
+    env = dict(os.environ)
+    env[env_knob] = value
+    env["PYTHONPATH"] = os.pathsep.join([ROOT] + ([env["PYTHONPATH"]] if env.get("PYTHONPATH") else []))
+    flags = ["-s"] if sys.flags.no_user_site else []
+    r = subprocess.run([sys.executable] + flags + [os.path.abspath(__file__), out], env=env, cwd=ROOT, timeout=300, capture_output=True, text=True)
+    assert r.returncode == 0, (env_knob, value, r.returncode, r.stdout[-2000:], r.stderr[-2000:])
+    return dict(np.load(out))
+
+
+def test_vector_schur_fallbacks_in_a_child_process(gpu_api, oracle, tmp_path):
+    """GFS_LBA_SCHUR=chunks / pairs select the two vector Schur kernels (b_schur_chunks + b_schur_reduce, b_schur), which are also the
+    fallbacks of windows too wide for the matrix-core kernel's partial blocks.  The knob is read once per process: each value runs
+    _collect_fallbacks() in a fresh child (one at a time; a failing child fails the test and no further one starts).  Solutions and
+    blocks are held to the oracle with the bars of test_solve_matches_oracle and test_linearize_blocks_match_oracle, and every batched
+    window to the bits of the same window solved alone in that child.  No bit-equality with the default is claimed: the matrix-core
+    kernel folds the sums in another order."""
+    wins = _fallback_windows()
+    solved = [oracle.lba_solve(w) for w in wins]
+    Lo = oracle.lba_linearize(wins[0])
+    for value in ("chunks", "pairs"):
+        got = _child(tmp_path, "GFS_LBA_SCHUR", value)
+        schur = sorted(n for n in got["launched"] if "lba_schur" in n and "reduce" not in n)
+        assert schur == ["k_" + _SCHUR_KERNELS[value], "kb_" + _SCHUR_KERNELS[value]], (value, schur)
+        for i, (w, ro) in enumerate(zip(wins, solved)):
+            r = {k: got[f"one{i}/{k}"] for k in _SOLVED}
+            its, final_chi2, _ = got[f"one{i}/stats"]
+            assert its == ro["iterations_run"], (value, i)
+            for j in range(w["n_poses"]):
+                assert _rel(r["pose_q"][j], ro["pose_q"][j]) < 1e-5 and _rel(r["pose_t"][j], ro["pose_t"][j]) < 1e-5, (value, i, j)
+            assert _rel(r["points"], ro["points"]) < 1e-5, (value, i)
+            assert _rel(final_chi2, ro["final_chi2"]) < 1e-6, (value, i)
+            thr = np.where(w["edge_stereo"] == 1, 7.815, 5.991)
+            near = np.abs(ro["edge_chi2"] - thr) < 1e-4 * thr
+            assert ((r["edge_chi2"] > thr) == (ro["edge_chi2"] > thr))[~near].all(), (value, i)
+            assert (r["edge_depth_positive"] == ro["edge_depth_positive"]).all(), (value, i)
+            for k in _SOLVED + ("stats",):
+                assert np.array_equal(got[f"bat{i}/{k}"], got[f"one{i}/{k}"]), (value, i, k)
+        for k in ("Hpp", "Hll", "Hpl", "bp", "bl", "edge_chi2"):
+            assert _rel(got["lin/" + k], Lo[k]) < 1e-10, (value, k, _rel(got["lin/" + k], Lo[k]))
+        assert abs(float(got["lin/chi2"]) - Lo["chi2"]) < 1e-9 * Lo["chi2"], value
+
+
+if __name__ == "__main__":  # the child of test_vector_schur_fallbacks_in_a_child_process: _collect_fallbacks() under the inherited environment
+    from geoflowslam_amd import api as A
+    A.lib()
+    assert A.device_count() >= 1
+    np.savez(sys.argv[1], **_collect_fallbacks(A))
