@@ -147,6 +147,64 @@ class SbpMapProblem(C.Structure):
                 ("n_levels", C.c_int32), ("th", C.c_float), ("nn_ratio", C.c_float)]
 
 
+class LocalPointsProblem(C.Structure):
+    _fields_ = [("n_mp", C.c_int32), ("mp_xw", C.c_void_p), ("mp_normal", C.c_void_p), ("mp_min_dist", C.c_void_p),
+                ("mp_max_dist", C.c_void_p), ("mp_desc", C.c_void_p), ("mp_has_obs", C.c_void_p), ("Rcw", C.c_float * 9),
+                ("tcw", C.c_float * 3), ("Ow", C.c_float * 3), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float),
+                ("cy", C.c_float), ("bf", C.c_float), ("min_x", C.c_float), ("max_x", C.c_float), ("min_y", C.c_float),
+                ("max_y", C.c_float), ("grid_w_inv", C.c_float), ("grid_h_inv", C.c_float), ("scale_factors", C.c_void_p),
+                ("n_levels", C.c_int32), ("log_scale_factor", C.c_float), ("view_cos_limit", C.c_float), ("far_points", C.c_int32),
+                ("th_far_points", C.c_float), ("th", C.c_float), ("nn_ratio", C.c_float), ("n_cur", C.c_int32),
+                ("cur_kps_un", C.c_void_p), ("cur_u_right", C.c_void_p), ("cur_desc", C.c_void_p), ("cur_has_mp_obs", C.c_void_p)]
+
+
+class LocalPointsResult(C.Structure):
+    _fields_ = [("in_view", C.c_void_p), ("proj", C.c_void_p), ("depth", C.c_void_p), ("view_cos", C.c_void_p), ("level", C.c_void_p),
+                ("cur_match", C.c_void_p), ("n_to_match", C.c_int32), ("n_searched", C.c_int32), ("nmatches", C.c_int32)]
+
+
+def local_points_structs(prob):
+    """ctypes views of one SearchLocalPoints problem dict (keys of gfs_local_points_problem; shared with the CPU restatement's
+    tests: same layout) -> (problem, result, arrays kept alive).  The result arrays are pre-filled with a pattern no output has."""
+    P, R = LocalPointsProblem(), LocalPointsResult()
+    keep = dict(mp_xw=np.ascontiguousarray(prob["mp_xw"], np.float32).reshape(-1, 3),
+                mp_normal=np.ascontiguousarray(prob["mp_normal"], np.float32).reshape(-1, 3),
+                mp_min_dist=np.ascontiguousarray(prob["mp_min_dist"], np.float32),
+                mp_max_dist=np.ascontiguousarray(prob["mp_max_dist"], np.float32),
+                mp_desc=np.ascontiguousarray(prob["mp_desc"], np.uint8).reshape(-1, 32),
+                mp_has_obs=np.ascontiguousarray(prob["mp_has_obs"], np.uint8),
+                cur_kps_un=np.ascontiguousarray(prob["cur_kps_un"], KP_DTYPE),
+                cur_u_right=np.ascontiguousarray(prob["cur_u_right"], np.float32),
+                cur_desc=np.ascontiguousarray(prob["cur_desc"], np.uint8).reshape(-1, 32),
+                cur_has_mp_obs=np.ascontiguousarray(prob["cur_has_mp_obs"], np.uint8),
+                scale_factors=np.ascontiguousarray(prob["scale_factors"], np.float32))
+    n, nc = len(keep["mp_xw"]), len(keep["cur_kps_un"])
+    P.n_mp, P.n_cur = n, nc
+    for name, a in keep.items():
+        setattr(P, name, a.ctypes.data)
+    for name in ("Rcw", "tcw", "Ow"):
+        getattr(P, name)[:] = [float(np.float32(v)) for v in np.asarray(prob[name]).reshape(-1)]
+    for name in ("fx", "fy", "cx", "cy", "bf", "min_x", "max_x", "min_y", "max_y", "grid_w_inv", "grid_h_inv", "log_scale_factor",
+                 "view_cos_limit", "th_far_points", "th", "nn_ratio"):
+        setattr(P, name, float(np.float32(prob[name])))
+    P.n_levels = int(prob.get("n_levels", len(keep["scale_factors"])))
+    P.far_points = int(prob.get("far_points", 0))
+    out = dict(in_view=np.full(max(n, 1), 0xEE, np.uint8), proj=np.full((max(n, 1), 3), -7.0, np.float32),
+               depth=np.full(max(n, 1), -7.0, np.float32), view_cos=np.full(max(n, 1), -7.0, np.float32),
+               level=np.full(max(n, 1), -9, np.int32), cur_match=np.full(max(nc, 1), -9, np.int32))
+    for name, a in out.items():
+        setattr(R, name, a.ctypes.data)
+    keep.update(out)
+    return P, R, keep
+
+
+def local_points_result(P, R, keep):
+    n, nc = P.n_mp, P.n_cur
+    return dict(in_view=keep["in_view"][:n].copy(), proj=keep["proj"][:n].copy(), depth=keep["depth"][:n].copy(),
+                view_cos=keep["view_cos"][:n].copy(), level=keep["level"][:n].copy(), cur_match=keep["cur_match"][:nc].copy(),
+                n_to_match=int(R.n_to_match), n_searched=int(R.n_searched), nmatches=int(R.nmatches))
+
+
 def sbp_map_struct(prob):
     P = SbpMapProblem()
     keep = dict(mp_proj=np.ascontiguousarray(prob["mp_proj"], np.float32).reshape(-1, 3),
@@ -282,6 +340,7 @@ ABI_SYMBOLS = [
     "gfs_pose_lidar_set_sum_order", "gfs_pose_lidar_optimize", "gfs_pose_lidar_fetch_edges",
     "gfs_gms_create", "gfs_gms_destroy", "gfs_gms_inlier_mask", "gfs_gms_inlier_mask_batch_device",
     "gfs_sbp_create", "gfs_sbp_destroy", "gfs_search_by_projection", "gfs_search_by_projection_map",
+    "gfs_sbp_reserve_local", "gfs_search_local_points", "gfs_test_glibc_logf",
     "gfs_klt_create", "gfs_klt_destroy", "gfs_klt_layout", "gfs_klt_pyramid_create", "gfs_klt_pyramid_destroy",
     "gfs_klt_build_pyramid", "gfs_klt_build_pyramid_device", "gfs_klt_pyramid_download", "gfs_klt_track", "gfs_klt_fb_track",
     "gfs_klt_fb_track_device",
@@ -318,6 +377,9 @@ def lib():
         L.gfs_orb_octree_host.argtypes = [vp, vp, vp, i, i, i, i, i, i, vp, i]
         L.gfs_orb_octree_device.argtypes = [i, vp, vp, vp, i, i, i, i, i, i, vp, vp, vp, i]
         L.gfs_test_glibc_math.argtypes = [i, vp, i, vp, vp, vp]
+        L.gfs_test_glibc_logf.argtypes = [i, vp, i, vp]
+        L.gfs_sbp_reserve_local.argtypes = [vp, i]
+        L.gfs_search_local_points.argtypes = [vp, C.POINTER(LocalPointsProblem), i, C.POINTER(LocalPointsResult)]
         L.gfs_test_traffic.argtypes = [i, i, C.c_longlong, C.c_longlong, i, C.POINTER(C.c_longlong)]
         L.gfs_hamming256.argtypes = [vp, vp]
         L.gfs_matcher_create.argtypes = [i, i, i, i, C.POINTER(vp)]
@@ -407,7 +469,9 @@ def _p(a):
 
 def _check(rc, what):
     if rc < 0:
-        raise GfsError(f"{what} failed ({rc}): {lib().gfs_last_error().decode()}")
+        err = GfsError(f"{what} failed ({rc}): {lib().gfs_last_error().decode()}")
+        err.code = rc  # GFS_ERR_* (include/gfs_abi.h)
+        raise err
     return rc
 
 
@@ -1167,6 +1231,32 @@ class ProjectionMatcher:
         nm = np.zeros(B, np.int32)
         _check(lib().gfs_search_by_projection_map(self.h, PP, B, ptrs, _p(nm)), "gfs_search_by_projection_map")
         res = [(outs[f][:PP[f].n_cur].copy(), int(nm[f])) for f in range(B)]
+        return res[0] if single else res
+
+
+    def reserve_local(self, max_local_points):
+        """Workspace of search_local_points for lists of up to max_local_points map points per frame."""
+        _check(lib().gfs_sbp_reserve_local(self.h, int(max_local_points)), "gfs_sbp_reserve_local")
+        self.max_local = int(max_local_points)
+
+    def search_local_points(self, frames):
+        """Tracking::SearchLocalPoints from its second loop on (src/Tracking.cc:4312-4358): Frame::isInFrustum + PredictScale for
+        every listed local map point, the far-points filter and SearchByProjection over the survivors, in one device call.
+        One problem dict (keys of gfs_local_points_problem) or a list -> per frame a dict in_view, proj [n][3], depth, view_cos,
+        level, cur_match (indices into the caller's list), n_to_match, n_searched, nmatches.  Raises GfsError (code
+        GFS_ERR_CAPACITY) when a list exceeds the reserve or a search set exceeds max_last."""
+        single = isinstance(frames, dict)
+        probs = [frames] if single else list(frames)
+        B = len(probs)
+        if getattr(self, "max_local", 0) <= 0:
+            self.reserve_local(max(max(len(p["mp_xw"]) for p in probs), 64))
+        PP, RR = (LocalPointsProblem * B)(), (LocalPointsResult * B)()
+        keeps = []
+        for f, prob in enumerate(probs):
+            PP[f], RR[f], keep = local_points_structs(prob)
+            keeps.append(keep)
+        _check(lib().gfs_search_local_points(self.h, PP, B, RR), "gfs_search_local_points")
+        res = [local_points_result(PP[f], RR[f], keeps[f]) for f in range(B)]
         return res[0] if single else res
 
 

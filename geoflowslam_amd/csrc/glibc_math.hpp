@@ -212,4 +212,41 @@ GFS_HD double pow3(double x) {  // pow(x, 3.0)
   return pow_exp_inline(ehi, elo, neg);
 }
 
+// ---- logf(x): flt-32/e_logf.c (the ARM optimized-routines logf: 16-entry table, degree-3 polynomial, all in double) ----
+// MapPoint::PredictScale (src/MapPoint.cc:565-579) is ceil(logf(ratio) / mfLogScaleFactor); at a level boundary the last bit of
+// logf decides the pyramid level.  Positive finite arguments (subnormals included) follow glibc bit for bit -- checked on every
+// one of them by tests/test_glibc_logf.py; +inf -> +inf, 0 -> -inf, negative or NaN -> NaN; no errno.  The a*b+c steps are
+// separate roundings here; glibc's FMA build fuses them, and the double result rounds to the same float either way (both forms
+// were compared with the host libm over all 2 139 095 039 arguments).
+GFS_HD float logf(float x) {
+  static constexpr double hdr[4] = {GFS_GLIBC_LOGF_HDR};
+  static constexpr double tab[32] = {GFS_GLIBC_LOGF_TAB};
+  uint32_t ix;
+  memcpy(&ix, &x, 4);
+  if (ix == 0x3f800000u) return 0.0f;
+  if (ix - 0x00800000u >= 0x7f800000u - 0x00800000u) {  // x < 0x1p-126, inf or nan
+    if (ix * 2 == 0) return -HUGE_VALF;
+    if (ix == 0x7f800000u) return x;
+    if ((ix & 0x80000000u) || ix * 2 >= 0xff000000u) return NAN;
+    // subnormal: asuint(x * 0x1p23f) - (23 << 23), in integers (x = ix * 2^-149: no dependence on the denormal mode)
+    const int p = 31 - __builtin_clz(ix);  // leading bit of the significand, 0 .. 22
+    ix = ((uint32_t)(p + 1) << 23) | ((ix << (23 - p)) & 0x007fffffu);
+    ix -= 23u << 23;
+  }
+  const uint32_t tmp = ix - 0x3f330000u;  // OFF
+  const int i = (int)((tmp >> (23 - 4)) % 16);
+  const int k = (int32_t)tmp >> 23;
+  const uint32_t iz = ix - (tmp & 0xff800000u);
+  float zf;
+  memcpy(&zf, &iz, 4);
+  const double invc = tab[2 * i], logc = tab[2 * i + 1], z = (double)zf;
+  const double r = z * invc - 1.0;
+  const double y0 = logc + (double)k * hdr[0];
+  const double r2 = r * r;
+  double y = hdr[2] * r + hdr[3];
+  y = hdr[1] * r2 + y;
+  y = y * r2 + (y0 + r);
+  return (float)y;
+}
+
 }  // namespace gfs_glibc

@@ -21,6 +21,7 @@
 #include <mutex>
 
 #include "gfs_common.hpp"
+#include "glibc_math.hpp"
 
 namespace {
 
@@ -560,6 +561,169 @@ __global__ __launch_bounds__(kSbpThreads) void k_sbp(const SbpPair* __restrict__
   if (tid == 0) nmatches[f] = s_ctl[0];
 }
 
+// ---- Tracking::SearchLocalPoints, second loop onwards (reference src/Tracking.cc:4312-4358) ----
+// Frame::isInFrustum (src/Frame.cc:876-931, Nleft == -1) + MapPoint::PredictScale (src/MapPoint.cc:565-579) for every listed
+// local map point, the filter of ORBmatcher.cc:53-58, a stable compaction of the survivors into the arrays k_sbp mode 1 reads, then
+// k_sbp itself -- all on one stream, no host step in between (DESIGN.md section 12 states the arithmetic).
+//   k_lp_frustum: a thread per map point, blockIdx.y = frame.  Per-point outputs, the point's rank inside its block's part of the
+//                 search set (wave ballots + the four wave totals through LDS), the block's counts to a small table.
+//   k_lp_compact: position = counts of the preceding blocks + rank: list order is kept, no atomic decides a position and no workgroup
+//                 waits for another (the kernel boundary is the only dependency).  Gathers projection / level / viewing cosine /
+//                 descriptor / has_obs into k_sbp's arrays, writes the list index of every entry and patches n_last in the header.
+// k_sbp writes cur_match / nmatches into the same result block as the per-point outputs and the index list: one copy out, after
+// which the host maps cur_match (indices into the compacted set) to the caller's list indices.
+constexpr int kLpThreads = 256, kLpWaves = kLpThreads / 64;
+constexpr float kLpMinDistFactor = 0.8f;  // MapPoint::GetMinDistanceInvariance (src/MapPoint.cc)
+constexpr float kLpMaxDistFactor = 1.2f;  // MapPoint::GetMaxDistanceInvariance
+
+struct LpFrame {
+  int n_mp, n_levels, far_points, max_last;
+  float R[9], t[3], Ow[3];
+  float fx, fy, cx, cy, bf, min_x, max_x, min_y, max_y;
+  float log_scale_factor, view_cos_limit, th_far_points;
+};
+struct LpMeta {
+  int n_to_match, n_searched, overflow, pad;
+};
+
+__global__ __launch_bounds__(kLpThreads) void k_lp_frustum(const LpFrame* __restrict__ frames, const float* __restrict__ xw,
+                                                           const float* __restrict__ normal, const float* __restrict__ min_dist,
+                                                           const float* __restrict__ max_dist, int SM, int NB,
+                                                           uint8_t* __restrict__ in_view, float* __restrict__ proj,
+                                                           float* __restrict__ depth, float* __restrict__ view_cos,
+                                                           int* __restrict__ level, int* __restrict__ rank, int2* __restrict__ block_cnt) {
+  __shared__ int s_search[kLpWaves], s_view[kLpWaves];
+  const int f = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int i = blockIdx.x * kLpThreads + tid;
+  const LpFrame& F = frames[f];
+  const size_t at = (size_t)f * SM + i;
+  bool inview = false, search = false;
+  if (i < F.n_mp) {
+    const float P[3] = {xw[3 * at], xw[3 * at + 1], xw[3 * at + 2]};
+    float pu = -1.0f, pv = -1.0f, pxr = 0.0f, vc = 0.0f;
+    int lv = 0;
+    float Pc[3];
+    for (int r = 0; r < 3; r++) Pc[r] = ((F.R[3 * r] * P[0] + F.R[3 * r + 1] * P[1]) + F.R[3 * r + 2] * P[2]) + F.t[r];
+    const float dep = sqrtf((Pc[0] * Pc[0] + Pc[1] * Pc[1]) + Pc[2] * Pc[2]);
+    const float invz = 1.0f / Pc[2];
+    do {
+      if (Pc[2] < 0.0f) break;
+      const float u = (F.fx * Pc[0]) / Pc[2] + F.cx, v = (F.fy * Pc[1]) / Pc[2] + F.cy;
+      if (u < F.min_x || u > F.max_x) break;
+      if (v < F.min_y || v > F.max_y) break;
+      if (!(fabsf(u) <= 3.402823466e38f) || !(fabsf(v) <= 3.402823466e38f)) break;  // chosen rule: 0 / 0 -> out, (-1, -1) stays
+      pu = u;
+      pv = v;
+      const float PO[3] = {P[0] - F.Ow[0], P[1] - F.Ow[1], P[2] - F.Ow[2]};
+      const float dist = sqrtf((PO[0] * PO[0] + PO[1] * PO[1]) + PO[2] * PO[2]);
+      const float mx = max_dist[at];
+      if (dist < kLpMinDistFactor * min_dist[at] || dist > kLpMaxDistFactor * mx) break;
+      const float Pn[3] = {normal[3 * at], normal[3 * at + 1], normal[3 * at + 2]};
+      vc = ((PO[0] * Pn[0] + PO[1] * Pn[1]) + PO[2] * Pn[2]) / dist;
+      if (vc < F.view_cos_limit) break;
+      // PredictScale: (int)std::ceil(logf(ratio) / mfLogScaleFactor); a value no int holds converts to INT_MIN on x86-64 -> level 0
+      const float c = ceilf(gfs_glibc::logf(mx / dist) / F.log_scale_factor);
+      lv = (c >= -2147483648.0f && c < 2147483648.0f) ? (int)c : 0;
+      lv = lv < 0 ? 0 : (lv >= F.n_levels ? F.n_levels - 1 : lv);
+      pxr = u - F.bf * invz;
+      inview = true;
+    } while (false);
+    search = inview && !(F.far_points && dep > F.th_far_points);
+    in_view[at] = inview ? 1 : 0;
+    proj[3 * at] = pu;
+    proj[3 * at + 1] = pv;
+    proj[3 * at + 2] = pxr;
+    depth[at] = dep;
+    view_cos[at] = vc;
+    level[at] = lv;
+  }
+  const unsigned long long ms = __ballot(search), mv = __ballot(inview);
+  if (lane == 0) {
+    s_search[wave] = __popcll(ms);
+    s_view[wave] = __popcll(mv);
+  }
+  __syncthreads();
+  if (i < F.n_mp) {
+    int before = 0;
+    for (int w = 0; w < wave; w++) before += s_search[w];
+    rank[at] = search ? before + __popcll(ms & ((1ull << lane) - 1ull)) : -1;
+  }
+  if (tid == 0) {
+    int a = 0, b = 0;
+    for (int w = 0; w < kLpWaves; w++) {
+      a += s_search[w];
+      b += s_view[w];
+    }
+    block_cnt[(size_t)f * NB + blockIdx.x] = make_int2(a, b);
+  }
+}
+
+__global__ __launch_bounds__(kLpThreads) void k_lp_compact(const LpFrame* __restrict__ frames, const int* __restrict__ rank,
+                                                           const int2* __restrict__ block_cnt, int SM, int NB, int nb_used,
+                                                           const float* __restrict__ proj, const float* __restrict__ view_cos,
+                                                           const int* __restrict__ level, const uint8_t* __restrict__ desc,
+                                                           const uint8_t* __restrict__ has_obs, SbpPair* __restrict__ pairs, int SL,
+                                                           float* __restrict__ o_proj, uint8_t* __restrict__ o_desc, int* __restrict__ o_level,
+                                                           float* __restrict__ o_cos, uint8_t* __restrict__ o_obs, int* __restrict__ o_index,
+                                                           LpMeta* __restrict__ meta) {
+  __shared__ int s_red[3][kLpWaves];
+  const int f = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const LpFrame& F = frames[f];
+  // the block's base (sum over the preceding blocks) and the frame's totals, from the count table
+  int base = 0, total = 0, views = 0;
+  for (int b = tid; b < nb_used; b += kLpThreads) {
+    const int2 c = block_cnt[(size_t)f * NB + b];
+    if (b < (int)blockIdx.x) base += c.x;
+    total += c.x;
+    views += c.y;
+  }
+  for (int ofs = 32; ofs > 0; ofs >>= 1) {
+    base += __shfl_down(base, ofs, 64);
+    total += __shfl_down(total, ofs, 64);
+    views += __shfl_down(views, ofs, 64);
+  }
+  if (lane == 0) {
+    s_red[0][wave] = base;
+    s_red[1][wave] = total;
+    s_red[2][wave] = views;
+  }
+  __syncthreads();
+  base = total = views = 0;
+  for (int w = 0; w < kLpWaves; w++) {
+    base += s_red[0][w];
+    total += s_red[1][w];
+    views += s_red[2][w];
+  }
+  const bool overflow = total > F.max_last;  // k_sbp's tables end there: nothing is truncated, the search is skipped
+  if (blockIdx.x == 0 && tid == 0) {
+    pairs[f].n_last = overflow ? 0 : total;
+    meta[f] = LpMeta{views, total, overflow ? 1 : 0, 0};
+  }
+  if (overflow) return;
+  const int i = blockIdx.x * kLpThreads + tid;
+  if (i >= F.n_mp) return;
+  const size_t at = (size_t)f * SM + i;
+  const int r = rank[at];
+  if (r < 0) return;
+  const size_t to = (size_t)f * SL + (base + r);  // base + r < total <= max_last <= SL
+  o_proj[3 * to] = proj[3 * at];
+  o_proj[3 * to + 1] = proj[3 * at + 1];
+  o_proj[3 * to + 2] = proj[3 * at + 2];
+  o_level[to] = level[at];
+  o_cos[to] = view_cos[at];
+  const uint4* d = reinterpret_cast<const uint4*>(desc + 32 * at);
+  uint4* o = reinterpret_cast<uint4*>(o_desc + 32 * to);
+  o[0] = d[0];
+  o[1] = d[1];
+  o_obs[to] = has_obs[at];
+  o_index[to] = i;
+}
+
+__global__ void k_test_logf(const float* __restrict__ x, int n, float* __restrict__ out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) out[i] = gfs_glibc::logf(x[i]);
+}
+
 }  // namespace
 
 struct gfs_sbp {
@@ -573,6 +737,43 @@ struct gfs_sbp {
   gfs::PinBuf<uint8_t> h_in, h_res;
   gfs::DevBuf<int> d_cand_cnt, d_lsel;
   gfs::DevBuf<unsigned> d_cand;
+  // gfs_search_local_points (allocated by gfs_sbp_reserve_local): the listed map points of a call, pinned and on the device; the
+  // results likewise (per-point outputs, the search set's list indices, k_sbp's cur_match / nmatches); ranks and block counts stay on
+  // the device
+  int max_local = 0;
+  gfs::DevBuf<uint8_t> d_lin, d_lout;
+  gfs::PinBuf<uint8_t> h_lin, h_lout;
+  gfs::DevBuf<int> d_rank;
+  gfs::DevBuf<int2> d_block_cnt;
+  struct LocalLayout {
+    int SM, NB;
+    size_t i_xw, i_nrm, i_min, i_max, i_desc, i_obs, in_bytes, o_view, o_proj, o_depth, o_cos, o_level, o_meta, o_index, o_match, o_nm, out_bytes;
+  };
+  LocalLayout local_layout(size_t B, int SM, int SL, int SC) const {
+    auto up = [](size_t v) { return gfs::align_up(v, 256); };
+    const size_t M = (size_t)SM * B;
+    LocalLayout Y;
+    Y.SM = SM;
+    Y.NB = SM / kLpThreads + 1;
+    Y.i_xw = up(B * sizeof(LpFrame));
+    Y.i_nrm = Y.i_xw + up(M * 12);
+    Y.i_min = Y.i_nrm + up(M * 12);
+    Y.i_max = Y.i_min + up(M * 4);
+    Y.i_desc = Y.i_max + up(M * 4);
+    Y.i_obs = Y.i_desc + up(M * 32);
+    Y.in_bytes = Y.i_obs + up(M);
+    Y.o_view = up(B * sizeof(LpMeta));
+    Y.o_meta = 0;
+    Y.o_proj = Y.o_view + up(M);
+    Y.o_depth = Y.o_proj + up(M * 12);
+    Y.o_cos = Y.o_depth + up(M * 4);
+    Y.o_level = Y.o_cos + up(M * 4);
+    Y.o_index = Y.o_level + up(M * 4);
+    Y.o_match = Y.o_index + up((size_t)SL * B * 4);
+    Y.o_nm = Y.o_match + up((size_t)SC * B * 4);
+    Y.out_bytes = Y.o_nm + up(B * 4);
+    return Y;
+  }
   struct Layout {
     int SL, SC;
     size_t o_xw, o_desc, o_oct, o_ang, o_lobs, o_kp, o_ur, o_cdesc, o_cobs, in_bytes, r_nm, res_bytes;
@@ -817,6 +1018,181 @@ int gfs_search_by_projection_map(gfs_sbp* h, const gfs_sbp_map_problem* problems
     if (problems[f].n_cur > 0) memcpy(cur_match[f], G.cur_match + (size_t)f * SC, (size_t)problems[f].n_cur * 4);
     nmatches[f] = G.nmatches[f];
   }
+  return GFS_OK;
+}
+
+int gfs_sbp_reserve_local(gfs_sbp* h, int max_local_points) {
+  GFS_REQUIRE(h && max_local_points > 0, GFS_ERR_INVALID_ARG, "gfs_sbp_reserve_local: invalid argument");
+  std::lock_guard<std::mutex> lk(h->mu);
+  GFS_HIP(hipSetDevice(h->device));
+  GFS_HIP(hipStreamSynchronize(h->stream));
+  const int SM = (int)gfs::align_up((size_t)max_local_points, 64), SL = (int)gfs::align_up((size_t)h->max_last, 64);
+  const int SC = (int)gfs::align_up((size_t)h->max_cur, 64);
+  const gfs_sbp::LocalLayout Y = h->local_layout((size_t)h->max_batch, SM, std::min(SM, SL), SC);
+  h->max_local = 0;
+  int rc = 0;
+#define A(x) if (!rc) rc = (x)
+  A(h->d_lin.alloc(Y.in_bytes));
+  A(h->h_lin.alloc(Y.in_bytes));
+  A(h->d_lout.alloc(Y.out_bytes));
+  A(h->h_lout.alloc(Y.out_bytes));
+  A(h->d_rank.alloc((size_t)SM * h->max_batch));
+  A(h->d_block_cnt.alloc((size_t)Y.NB * h->max_batch));
+#undef A
+  if (rc) return rc;
+  h->max_local = max_local_points;
+  return GFS_OK;
+}
+
+int gfs_search_local_points(gfs_sbp* h, const gfs_local_points_problem* problems, int B, gfs_local_points_result* results) {
+  GFS_REQUIRE(h && problems && results && B > 0, GFS_ERR_INVALID_ARG, "gfs_search_local_points: invalid argument");
+  GFS_REQUIRE(B <= h->max_batch, GFS_ERR_CAPACITY, "gfs_search_local_points: batch %d exceeds capacity %d", B, h->max_batch);
+  std::lock_guard<std::mutex> lk(h->mu);
+  GFS_REQUIRE(h->max_local > 0, GFS_ERR_CAPACITY, "gfs_search_local_points: call gfs_sbp_reserve_local first");
+  GFS_HIP(hipSetDevice(h->device));
+  const int capM = h->max_local, capC = h->max_cur;
+  int SM = 64, SC = 64;
+  for (int f = 0; f < B; f++) {
+    const gfs_local_points_problem& p = problems[f];
+    const gfs_local_points_result& r = results[f];
+    GFS_REQUIRE(p.n_mp >= 0 && p.n_mp <= capM && p.n_cur >= 0 && p.n_cur <= capC, GFS_ERR_CAPACITY,
+                "gfs_search_local_points: frame %d has %d map points / %d key-points (capacity %d / %d)", f, p.n_mp, p.n_cur, capM, capC);
+    GFS_REQUIRE(p.n_levels > 0 && p.n_levels <= 16 && p.scale_factors, GFS_ERR_INVALID_ARG,
+                "gfs_search_local_points: frame %d needs 1..16 scale factors", f);
+    GFS_REQUIRE(p.n_mp == 0 || (p.mp_xw && p.mp_normal && p.mp_min_dist && p.mp_max_dist && p.mp_desc && p.mp_has_obs),
+                GFS_ERR_INVALID_ARG, "gfs_search_local_points: frame %d has NULL map-point arrays", f);
+    GFS_REQUIRE(p.n_mp == 0 || (r.in_view && r.proj && r.depth && r.view_cos && r.level), GFS_ERR_INVALID_ARG,
+                "gfs_search_local_points: frame %d has NULL result arrays", f);
+    GFS_REQUIRE(p.n_cur == 0 || (p.cur_kps_un && p.cur_u_right && p.cur_desc && p.cur_has_mp_obs && r.cur_match), GFS_ERR_INVALID_ARG,
+                "gfs_search_local_points: frame %d has NULL key-point arrays", f);
+    SM = std::max(SM, (int)gfs::align_up((size_t)p.n_mp, 64));
+    SC = std::max(SC, (int)gfs::align_up((size_t)p.n_cur, 64));
+  }
+  const int SL = std::min(SM, (int)gfs::align_up((size_t)h->max_last, 64));
+  const gfs_sbp::Layout Y = h->layout((size_t)B, SL, SC);
+  const gfs_sbp::Stage G = h->stage(Y);
+  const gfs_sbp::LocalLayout Z = h->local_layout((size_t)B, SM, SL, SC);
+  uint8_t* li = h->h_lin.p;
+  LpFrame* frames = reinterpret_cast<LpFrame*>(li);
+  for (int f = 0; f < B; f++) {
+    const gfs_local_points_problem& p = problems[f];
+    LpFrame& F = frames[f];
+    F.n_mp = p.n_mp;
+    F.n_levels = p.n_levels;
+    F.far_points = p.far_points != 0;
+    F.max_last = h->max_last;
+    for (int k = 0; k < 9; k++) F.R[k] = p.Rcw[k];
+    for (int k = 0; k < 3; k++) {
+      F.t[k] = p.tcw[k];
+      F.Ow[k] = p.Ow[k];
+    }
+    F.fx = p.fx;
+    F.fy = p.fy;
+    F.cx = p.cx;
+    F.cy = p.cy;
+    F.bf = p.bf;
+    F.min_x = p.min_x;
+    F.max_x = p.max_x;
+    F.min_y = p.min_y;
+    F.max_y = p.max_y;
+    F.log_scale_factor = p.log_scale_factor;
+    F.view_cos_limit = p.view_cos_limit;
+    F.th_far_points = p.th_far_points;
+    SbpPair& S = G.pairs[f];
+    memset(&S, 0, sizeof(S));
+    S.n_last = 0;  // k_lp_compact writes the size of the search set
+    S.n_cur = p.n_cur;
+    S.n_levels = p.n_levels;
+    S.mode = 1;
+    S.nn_ratio = p.nn_ratio;
+    S.min_x = p.min_x;
+    S.min_y = p.min_y;
+    S.grid_w_inv = p.grid_w_inv;
+    S.grid_h_inv = p.grid_h_inv;
+    S.th = p.th;
+    for (int k = 0; k < 16; k++) S.scale[k] = k < p.n_levels ? p.scale_factors[k] : 0.f;
+    if (p.n_mp > 0) {
+      const size_t at = (size_t)f * SM, n = (size_t)p.n_mp;
+      memcpy(li + Z.i_xw + at * 12, p.mp_xw, n * 12);
+      memcpy(li + Z.i_nrm + at * 12, p.mp_normal, n * 12);
+      memcpy(li + Z.i_min + at * 4, p.mp_min_dist, n * 4);
+      memcpy(li + Z.i_max + at * 4, p.mp_max_dist, n * 4);
+      memcpy(li + Z.i_desc + at * 32, p.mp_desc, n * 32);
+      memcpy(li + Z.i_obs + at, p.mp_has_obs, n);
+    }
+    if (p.n_cur > 0) {
+      memcpy(G.cur_kp + (size_t)f * SC, p.cur_kps_un, (size_t)p.n_cur * sizeof(gfs_keypoint));
+      memcpy(G.cur_ur + (size_t)f * SC, p.cur_u_right, (size_t)p.n_cur * 4);
+      memcpy(G.cur_desc + (size_t)f * SC * 32, p.cur_desc, (size_t)p.n_cur * 32);
+      memcpy(G.cur_has_obs + (size_t)f * SC, p.cur_has_mp_obs, (size_t)p.n_cur);
+    }
+  }
+  hipStream_t s = h->stream;
+  uint8_t *d = h->d_in.p, *dl = h->d_lin.p, *dq = h->d_lout.p;
+  // three copies in: the listed map points, the pair headers, the key-point arrays (the map-point arrays of k_sbp are filled on the device)
+  GFS_HIP(hipMemcpyAsync(dl, li, Z.in_bytes, hipMemcpyHostToDevice, s));
+  GFS_HIP(hipMemcpyAsync(d, h->h_in.p, (size_t)B * sizeof(SbpPair), hipMemcpyHostToDevice, s));
+  GFS_HIP(hipMemcpyAsync(d + Y.o_kp, h->h_in.p + Y.o_kp, Y.in_bytes - Y.o_kp, hipMemcpyHostToDevice, s));
+  const int nb = (SM + kLpThreads - 1) / kLpThreads;
+  const LpFrame* dF = reinterpret_cast<const LpFrame*>(dl);
+  SbpPair* dP = reinterpret_cast<SbpPair*>(d);
+  GFS_LAUNCH("k_lp_frustum", k_lp_frustum, dim3(nb, B), dim3(kLpThreads), 0, s, dF, reinterpret_cast<const float*>(dl + Z.i_xw),
+             reinterpret_cast<const float*>(dl + Z.i_nrm), reinterpret_cast<const float*>(dl + Z.i_min),
+             reinterpret_cast<const float*>(dl + Z.i_max), SM, Z.NB, dq + Z.o_view, reinterpret_cast<float*>(dq + Z.o_proj),
+             reinterpret_cast<float*>(dq + Z.o_depth), reinterpret_cast<float*>(dq + Z.o_cos), reinterpret_cast<int*>(dq + Z.o_level),
+             h->d_rank.p, h->d_block_cnt.p);
+  GFS_LAUNCH("k_lp_compact", k_lp_compact, dim3(nb, B), dim3(kLpThreads), 0, s, dF, (const int*)h->d_rank.p, (const int2*)h->d_block_cnt.p,
+             SM, Z.NB, nb, reinterpret_cast<const float*>(dq + Z.o_proj), reinterpret_cast<const float*>(dq + Z.o_cos),
+             reinterpret_cast<const int*>(dq + Z.o_level), (const uint8_t*)(dl + Z.i_desc), (const uint8_t*)(dl + Z.i_obs), dP, SL,
+             reinterpret_cast<float*>(d + Y.o_xw), d + Y.o_desc, reinterpret_cast<int*>(d + Y.o_oct), reinterpret_cast<float*>(d + Y.o_ang),
+             d + Y.o_lobs, reinterpret_cast<int*>(dq + Z.o_index), reinterpret_cast<LpMeta*>(dq + Z.o_meta));
+  GFS_LAUNCH("k_sbp", k_sbp, dim3(B), dim3(kSbpThreads), 0, s, (const SbpPair*)dP, reinterpret_cast<const float*>(d + Y.o_xw),
+             (const uint8_t*)(d + Y.o_desc), reinterpret_cast<const int*>(d + Y.o_oct), reinterpret_cast<const float*>(d + Y.o_ang),
+             (const uint8_t*)(d + Y.o_lobs), reinterpret_cast<const gfs_keypoint*>(d + Y.o_kp), reinterpret_cast<const float*>(d + Y.o_ur),
+             (const uint8_t*)(d + Y.o_cdesc), (const uint8_t*)(d + Y.o_cobs), Y.SL, Y.SC, h->d_cand.p, h->d_cand_cnt.p, h->d_lsel.p,
+             reinterpret_cast<int*>(dq + Z.o_match), reinterpret_cast<int*>(dq + Z.o_nm));
+  GFS_HIP(hipMemcpyAsync(h->h_lout.p, dq, Z.out_bytes, hipMemcpyDeviceToHost, s));
+  GFS_HIP(hipStreamSynchronize(s));  // the call's one synchronisation
+  const uint8_t* lo = h->h_lout.p;
+  const LpMeta* meta = reinterpret_cast<const LpMeta*>(lo + Z.o_meta);
+  int over = -1;
+  for (int f = 0; f < B; f++) {
+    const gfs_local_points_problem& p = problems[f];
+    gfs_local_points_result& r = results[f];
+    if (p.n_mp > 0) {
+      const size_t at = (size_t)f * SM, n = (size_t)p.n_mp;
+      memcpy(r.in_view, lo + Z.o_view + at, n);
+      memcpy(r.proj, lo + Z.o_proj + at * 12, n * 12);
+      memcpy(r.depth, lo + Z.o_depth + at * 4, n * 4);
+      memcpy(r.view_cos, lo + Z.o_cos + at * 4, n * 4);
+      memcpy(r.level, lo + Z.o_level + at * 4, n * 4);
+    }
+    const int32_t* cm = reinterpret_cast<const int32_t*>(lo + Z.o_match) + (size_t)f * SC;
+    const int32_t* index = reinterpret_cast<const int32_t*>(lo + Z.o_index) + (size_t)f * SL;
+    for (int i = 0; i < p.n_cur; i++) r.cur_match[i] = cm[i] >= 0 ? index[cm[i]] : cm[i];  // compacted set -> the caller's list
+    r.n_to_match = meta[f].n_to_match;
+    r.n_searched = meta[f].n_searched;
+    r.nmatches = reinterpret_cast<const int32_t*>(lo + Z.o_nm)[f];
+    if (meta[f].overflow && over < 0) over = f;
+  }
+  GFS_REQUIRE(over < 0, GFS_ERR_CAPACITY, "gfs_search_local_points: frame %d has a search set of %d map points (capacity %d): not searched",
+              over, meta[over].n_searched, h->max_last);
+  return GFS_OK;
+}
+
+int gfs_test_glibc_logf(int device, const float* x, int n, float* out) {
+  GFS_REQUIRE(x && out && n >= 0, GFS_ERR_INVALID_ARG, "gfs_test_glibc_logf: invalid argument");
+  if (!gfs::device_ok(device)) return GFS_ERR_NO_DEVICE;
+  GFS_HIP(hipSetDevice(device));
+  if (n == 0) return GFS_OK;
+  gfs::DevBuf<float> dx, dy;
+  int rc = dx.alloc(n);
+  if (!rc) rc = dy.alloc(n);
+  if (rc) return rc;
+  GFS_HIP(hipMemcpy(dx.p, x, (size_t)n * 4, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(k_test_logf, dim3((n + 255) / 256), dim3(256), 0, 0, (const float*)dx.p, n, dy.p);
+  GFS_HIP(hipGetLastError());
+  GFS_HIP(hipMemcpy(out, dy.p, (size_t)n * 4, hipMemcpyDeviceToHost));
   return GFS_OK;
 }
 

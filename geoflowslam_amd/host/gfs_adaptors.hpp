@@ -897,6 +897,159 @@ class ProjectionMatcher {
   gfs_sbp* h_ = nullptr;
 };
 
+// ------------------------------------------------------------------------------------------------------------------------
+// void Tracking::SearchLocalPoints()                                                       reference src/Tracking.cc:4294-4359
+// as real code around one device call: the first loop (:4296-4310: bad matches dropped, the others marked seen), the gather of
+// the local map points that pass `mnLastFrameSeen != F.mnId && !isBad()` (:4320-4321), gfs_search_local_points (Frame::isInFrustum,
+// MapPoint::PredictScale, the far-points filter and ORBmatcher::SearchByProjection, src/ORBmatcher.cc:43-206), and the write-back
+// of what isInFrustum leaves on a map point (mbTrackInView, mTrackProjX / Y / XR, mnTrackScaleLevel, mTrackViewCos, mTrackDepth),
+// IncreaseVisible (:4324), mmProjectPoints (:4327-4330) and F.mvpMapPoints[idx] (ORBmatcher.cc:122).  The choice of th (:4335-4353)
+// stays with the caller.  Single-camera pinhole frames only: a frame with Nleft != -1 or another camera model throws.
+//
+// Frame and MapPoint are the reference's own classes, used through the members the reference function uses (F.mvpMapPoints, mnId,
+// Nleft, N, mvuRight, mbf, mnMinX .. mnMaxY, mfGridElementWidthInv / HeightInv, mvScaleFactors, mnScaleLevels, mfLogScaleFactor;
+// isBad(), IncreaseVisible(), Observations(), mnId, mnLastFrameSeen, mbTrackInView, mbTrackInViewR and the mTrack* fields).  What
+// touches Eigen / OpenCV value types or protected members goes through `Access` (INTEGRATION.md section 14 gives it for the
+// reference's types; tests/host/local_points_adaptor_test.cpp one for plain structs):
+//     static bool is_pinhole(const Frame&);                                    // mpCamera->GetType() == CAM_PINHOLE
+//     static void pose(const Frame&, float Rcw[9], float tcw[3], float Ow[3]); // mRcw (row-major), mtcw, mOw
+//     static void intrinsics(const Frame&, float k[4]);                        // fx, fy, cx, cy of mpCamera
+//     static const gfs_keypoint* keys_un(const Frame&);                        // mvKeysUn.data() (cv::KeyPoint layout)
+//     static const uint8_t* descriptors(const Frame&);                         // mDescriptors.data ([N][32], continuous)
+//     static void set_project_point(Frame&, unsigned long id, float x, float y);   // mmProjectPoints[id] = cv::Point2f(x, y)
+//     static void world_pos(const MapPoint*, float p[3]);                      // GetWorldPos()
+//     static void normal(const MapPoint*, float n[3]);                         // GetNormal()
+//     static void distances(const MapPoint*, float* min_d, float* max_d);      // mfMinDistance, mfMaxDistance (raw)
+//     static void descriptor(const MapPoint*, uint8_t d[32]);                  // GetDescriptor()
+// `solve(problem, result)` is the numeric core: LocalPointsSearcher::solve below (gfs_search_local_points on the GPU).  Returns the
+// matcher's return value (the reference drops it).
+// ------------------------------------------------------------------------------------------------------------------------
+constexpr float kSearchLocalPointsViewCosLimit = 0.5f;  // isInFrustum(pMP, 0.5) (:4323)
+constexpr float kSearchLocalPointsNNRatio = 0.8f;       // ORBmatcher matcher(0.8) (:4334)
+
+template <class Access, class Frame, class MapPoint, class Solve>
+int SearchLocalPoints(Frame& F, const std::vector<MapPoint*>& vpLocalMapPoints, float th, bool bFarPoints, float thFarPoints, Solve&& solve) {
+  if (F.Nleft != -1 || !Access::is_pinhole(F)) throw std::invalid_argument("SearchLocalPoints: single-camera pinhole frames only");
+  // Do not search map points already matched (:4296-4310)
+  for (auto vit = F.mvpMapPoints.begin(), vend = F.mvpMapPoints.end(); vit != vend; ++vit) {
+    MapPoint* pMP = *vit;
+    if (!pMP) continue;
+    if (pMP->isBad()) {
+      *vit = static_cast<MapPoint*>(nullptr);
+    } else {
+      pMP->IncreaseVisible();
+      pMP->mnLastFrameSeen = F.mnId;
+      pMP->mbTrackInView = false;
+      pMP->mbTrackInViewR = false;
+    }
+  }
+  // the points isInFrustum is called on (:4320-4321), in list order
+  std::vector<MapPoint*> listed;
+  listed.reserve(vpLocalMapPoints.size());
+  for (MapPoint* pMP : vpLocalMapPoints) {
+    if (pMP->mnLastFrameSeen == F.mnId) continue;
+    if (pMP->isBad()) continue;
+    listed.push_back(pMP);
+  }
+  const size_t n = listed.size(), nc = (size_t)F.N;
+  std::vector<float> xw(3 * n + 3), nrm(3 * n + 3), dmin(n + 1), dmax(n + 1), proj(3 * n + 3), depth(n + 1), vcos(n + 1);
+  std::vector<uint8_t> desc(32 * n + 32), has_obs(n + 1), in_view(n + 1), cur_obs(nc + 1);
+  std::vector<int32_t> level(n + 1), cur_match(nc + 1, -1);
+  for (size_t i = 0; i < n; i++) {
+    Access::world_pos(listed[i], &xw[3 * i]);
+    Access::normal(listed[i], &nrm[3 * i]);
+    Access::distances(listed[i], &dmin[i], &dmax[i]);
+    Access::descriptor(listed[i], &desc[32 * i]);
+    has_obs[i] = listed[i]->Observations() > 0;
+  }
+  for (size_t i = 0; i < nc; i++) cur_obs[i] = F.mvpMapPoints[i] && F.mvpMapPoints[i]->Observations() > 0;
+  gfs_local_points_problem p{};
+  p.n_mp = (int32_t)n;
+  p.mp_xw = xw.data();
+  p.mp_normal = nrm.data();
+  p.mp_min_dist = dmin.data();
+  p.mp_max_dist = dmax.data();
+  p.mp_desc = desc.data();
+  p.mp_has_obs = has_obs.data();
+  Access::pose(F, p.Rcw, p.tcw, p.Ow);
+  float k[4];
+  Access::intrinsics(F, k);
+  p.fx = k[0];
+  p.fy = k[1];
+  p.cx = k[2];
+  p.cy = k[3];
+  p.bf = F.mbf;
+  p.min_x = F.mnMinX;
+  p.max_x = F.mnMaxX;
+  p.min_y = F.mnMinY;
+  p.max_y = F.mnMaxY;
+  p.grid_w_inv = F.mfGridElementWidthInv;
+  p.grid_h_inv = F.mfGridElementHeightInv;
+  p.scale_factors = F.mvScaleFactors.data();
+  p.n_levels = F.mnScaleLevels;
+  p.log_scale_factor = F.mfLogScaleFactor;
+  p.view_cos_limit = kSearchLocalPointsViewCosLimit;
+  p.far_points = bFarPoints ? 1 : 0;
+  p.th_far_points = thFarPoints;
+  p.th = th;
+  p.nn_ratio = kSearchLocalPointsNNRatio;
+  p.n_cur = (int32_t)nc;
+  p.cur_kps_un = Access::keys_un(F);
+  p.cur_u_right = F.mvuRight.data();
+  p.cur_desc = Access::descriptors(F);
+  p.cur_has_mp_obs = cur_obs.data();
+  gfs_local_points_result r{};
+  r.in_view = in_view.data();
+  r.proj = proj.data();
+  r.depth = depth.data();
+  r.view_cos = vcos.data();
+  r.level = level.data();
+  r.cur_match = cur_match.data();
+  check(solve(p, r), "gfs_search_local_points");
+  for (size_t i = 0; i < n; i++) {  // what isInFrustum leaves on the point, then :4324-4330
+    MapPoint* pMP = listed[i];
+    pMP->mbTrackInView = in_view[i] != 0;
+    pMP->mTrackProjX = proj[3 * i];
+    pMP->mTrackProjY = proj[3 * i + 1];
+    if (!in_view[i]) continue;
+    pMP->mTrackProjXR = proj[3 * i + 2];
+    pMP->mTrackDepth = depth[i];
+    pMP->mnTrackScaleLevel = level[i];
+    pMP->mTrackViewCos = vcos[i];
+    pMP->IncreaseVisible();
+    Access::set_project_point(F, pMP->mnId, pMP->mTrackProjX, pMP->mTrackProjY);
+  }
+  for (size_t i = 0; i < nc; i++)
+    if (cur_match[i] >= 0) F.mvpMapPoints[i] = listed[(size_t)cur_match[i]];
+  return r.nmatches;
+}
+
+// the numeric core of SearchLocalPoints on the GPU: one handle, its reserve grown to the longest list seen
+class LocalPointsSearcher {
+ public:
+  LocalPointsSearcher(int max_search = 8192, int max_cur = 4096, int device = 0) { check(gfs_sbp_create(device, max_search, max_cur, 1, &h_), "gfs_sbp_create"); }
+  ~LocalPointsSearcher() { gfs_sbp_destroy(h_); }
+  LocalPointsSearcher(const LocalPointsSearcher&) = delete;
+  LocalPointsSearcher& operator=(const LocalPointsSearcher&) = delete;
+  int solve(const gfs_local_points_problem& p, gfs_local_points_result& r) {
+    if (p.n_mp > reserve_) {  // the library refuses a list beyond the reserve (it never truncates): grow it first
+      const int want = std::max(p.n_mp, 2 * reserve_);
+      check(gfs_sbp_reserve_local(h_, want), "gfs_sbp_reserve_local");
+      reserve_ = want;
+    }
+    return gfs_search_local_points(h_, &p, 1, &r);
+  }
+  template <class Access, class Frame, class MapPoint>
+  int SearchLocalPoints(Frame& F, const std::vector<MapPoint*>& vpLocalMapPoints, float th, bool bFarPoints, float thFarPoints) {
+    return gfs_host::SearchLocalPoints<Access>(F, vpLocalMapPoints, th, bFarPoints, thFarPoints,
+                                               [this](const gfs_local_points_problem& p, gfs_local_points_result& r) { return solve(p, r); });
+  }
+
+ private:
+  gfs_sbp* h_ = nullptr;
+  int reserve_ = 0;
+};
+
 // Optimizer::PoseOptimization on a flattened frame (reference src/Optimizer.cc:763-1098)
 class PoseOptimizer {
  public:

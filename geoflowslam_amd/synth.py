@@ -373,6 +373,127 @@ def sbp_map_frame(seed, th=1.0, nn_ratio=0.8, **kw):
                 scale_factors=p["scale_factors"], th=np.float32(th), nn_ratio=np.float32(nn_ratio))
 
 
+def local_points_frame(seed, n_points=2000, n_cur=None, scale_factor=1.2, n_levels=8, th=1.0, nn_ratio=0.8, far_points=True,
+                       th_far_points=6.0, view_cos_limit=0.5, share=0.5, **kw):
+    """Synthetic input of Tracking::SearchLocalPoints from its second loop on (reference src/Tracking.cc:4312-4358), flattened as
+    gfs_local_points_problem (include/gfs_abi.h): a frame pose, its key-points, and a list of `n_points` local map points with
+    world position, normal and scale-invariance distances.
+
+    About `share` of the list are the map points of sbp_pair's scene (same key-point and descriptor construction, so real matches
+    exist); their normals mostly face the camera, their distance ranges put the predicted level at the octave they were seen at.  A
+    few per cent each are bent away (viewing angle), too near, too far, or sit beyond the last / before the first pyramid level
+    (the clamps of MapPoint::PredictScale).  The rest are laid out in the camera frame: behind it, off each of the four image
+    sides, or in view without a key-point.  The list is shuffled, so the exits alternate along it.  One scene point that has a
+    key-point in the frame (the anchor) is kept clean and its key-point is moved to index 0, so a frame with any key-point has a
+    match.  n_cur: exact number of key-points (the scene's list cut or padded with unrelated ones); None = as the scene has them."""
+    rng = np.random.default_rng(seed + 104729)
+    f32 = np.float32
+    n_scene = min(n_points, max(int(round(n_points * share)), 1)) if n_points > 0 else 0
+    p = sbp_pair(seed, n_points=max(n_scene, 16), n_levels=n_levels, **kw)
+    sf = float(scale_factor)
+    scale = np.cumprod(np.r_[1.0, np.full(n_levels - 1, sf)]).astype(np.float32)
+    R = _rot_from_quat(p["Tcw_q"].astype(np.float64)).astype(np.float32)
+    t = p["Tcw_t"].astype(np.float32)
+    Ow = (-(R.T.astype(np.float64) @ t.astype(np.float64))).astype(np.float32)
+    R64, t64, Ow64 = R.astype(np.float64), t.astype(np.float64), Ow.astype(np.float64)
+    fx, fy, cx, cy, bf = (float(p[k]) for k in ("fx", "fy", "cx", "cy", "bf"))
+    W, H = float(p["max_x"]), float(p["max_y"])
+    kps, cur_ur, cur_desc, cur_obs = p["cur_kps_un"].copy(), p["cur_u_right"].copy(), p["cur_desc"].copy(), p["cur_has_mp_obs"].copy()
+    # the anchor: the first scene point whose key-point sits close to its projection, on a level the window accepts, not too deep
+    anchor, anchor_kp = None, None
+    if len(kps):
+        bits = np.unpackbits(cur_desc, axis=1)
+        for j in range(min(len(p["last_xw"]), 64)):
+            xc = R64 @ p["last_xw"][j].astype(np.float64) + t64
+            if not (0.3 < xc[2] and np.linalg.norm(xc) < 0.9 * th_far_points):
+                continue
+            u, v = fx * xc[0] / xc[2] + cx, fy * xc[1] / xc[2] + cy
+            d = (bits != np.unpackbits(p["last_desc"][j])[None, :]).sum(1)
+            i = int(np.argmin(d))
+            o = int(p["last_octave"][j])
+            if d[i] <= 24 and abs(kps["x"][i] - u) < 1.5 and abs(kps["y"][i] - v) < 1.5 and kps["octave"][i] in (o - 1, o) and \
+                    (cur_ur[i] <= 0 or abs(cur_ur[i] - (u - bf / xc[2])) < 2.0) and not cur_obs[i]:
+                anchor, anchor_kp = j, i
+                break
+    if anchor_kp is not None and anchor_kp != 0:
+        for a in (kps, cur_ur, cur_desc, cur_obs):
+            a[[0, anchor_kp]] = a[[anchor_kp, 0]]
+    if n_cur is not None:
+        if len(kps) >= n_cur:
+            kps, cur_ur, cur_desc, cur_obs = kps[:n_cur], cur_ur[:n_cur], cur_desc[:n_cur], cur_obs[:n_cur]
+        else:
+            m = n_cur - len(kps)
+            extra = np.zeros(m, kps.dtype)
+            extra["x"], extra["y"] = rng.uniform(0, W, m), rng.uniform(0, H, m)
+            extra["octave"], extra["angle"], extra["size"], extra["class_id"] = rng.integers(0, n_levels, m), rng.uniform(0, 360, m), 31.0, -1
+            kps = np.concatenate([kps, extra])
+            cur_ur = np.concatenate([cur_ur, np.where(rng.random(m) < 0.5, rng.uniform(1, W, m), -1).astype(np.float32)])
+            cur_desc = np.concatenate([cur_desc.reshape(-1, 32), rng.integers(0, 256, (m, 32), dtype=np.uint8)])
+            cur_obs = np.concatenate([cur_obs, np.zeros(m, np.uint8)])
+    # scene points: the anchor first, then the others in scene order
+    ids = ([anchor] if anchor is not None else []) + [j for j in range(len(p["last_xw"])) if j != anchor]
+    ids = ids[:n_scene]
+    xw, nrm, dmin, dmax, desc, obs = [], [], [], [], [], []
+
+    def unit(v):
+        return v / max(np.linalg.norm(v), 1e-12)
+
+    def add(P, octv, d, o, kind):
+        """kind: 0 clean, 1 bent away, 2 too far, 3 too near, 4 beyond the last level, 5 before the first level"""
+        PO = P.astype(np.float64) - Ow64
+        dist = np.linalg.norm(PO)
+        side = unit(np.cross(PO, rng.normal(size=3)))
+        if kind == 1:
+            n = unit(0.3 * unit(PO) + side)                      # cos ~ 0.29
+        elif rng.random() < 0.4:
+            n = unit(PO)                                         # cos ~ 1: the narrow window of RadiusByViewingCos
+        else:
+            n = unit(unit(PO) + rng.uniform(0.1, 1.2) * side)    # cos 0.64 .. 0.995
+        mx = dist * sf ** (octv - 0.5 + rng.uniform(-0.3, 0.3))
+        if kind == 4:
+            mx = dist * sf ** (n_levels - 1) * (1.0 + 0.5 * (sf - 1.0))
+        if kind == 5:
+            mx = dist * 0.85
+        mn = mx / sf ** (n_levels - 1)
+        if kind == 2:
+            mx = dist / 1.5
+            mn = mx / sf ** (n_levels - 1)
+        if kind == 3:
+            mn = dist * 1.5
+        xw.append(P.astype(np.float32)); nrm.append(n.astype(np.float32)); dmin.append(f32(mn)); dmax.append(f32(mx))
+        desc.append(d); obs.append(o)
+
+    for q, j in enumerate(ids):
+        kind = 0 if j == anchor else int(rng.choice(6, p=[0.74, 0.08, 0.05, 0.05, 0.04, 0.04]))
+        add(p["last_xw"][j], int(p["last_octave"][j]), p["last_desc"][j], int(p["last_mp_has_obs"][j]), kind)
+    for q in range(n_points - len(ids)):
+        where = q % 6  # behind, left, right, above, below, in view
+        z = rng.uniform(1.0, 7.0)
+        u, v = rng.uniform(0, W), rng.uniform(0, H)
+        if where == 0:
+            z = -rng.uniform(0.2, 5.0)
+        elif where == 1:
+            u = -rng.uniform(0.5, 300)
+        elif where == 2:
+            u = W + rng.uniform(0.5, 300)
+        elif where == 3:
+            v = -rng.uniform(0.5, 300)
+        elif where == 4:
+            v = H + rng.uniform(0.5, 300)
+        xc = np.array([(u - cx) / fx * abs(z), (v - cy) / fy * abs(z), z])
+        P = R64.T @ (xc - t64)
+        add(P, int(rng.integers(0, n_levels)), rng.integers(0, 256, 32, dtype=np.uint8), 1, 0)
+    order = rng.permutation(n_points)
+    take = lambda a, shape, dt: (np.array(a, dt).reshape(shape)[order] if n_points else np.zeros((0,) + shape[1:], dt))
+    return dict(mp_xw=take(xw, (-1, 3), np.float32), mp_normal=take(nrm, (-1, 3), np.float32), mp_min_dist=take(dmin, (-1,), np.float32),
+                mp_max_dist=take(dmax, (-1,), np.float32), mp_desc=take(desc, (-1, 32), np.uint8), mp_has_obs=take(obs, (-1,), np.uint8),
+                Rcw=R.reshape(9), tcw=t, Ow=Ow, fx=p["fx"], fy=p["fy"], cx=p["cx"], cy=p["cy"], bf=p["bf"], min_x=p["min_x"],
+                max_x=p["max_x"], min_y=p["min_y"], max_y=p["max_y"], grid_w_inv=p["grid_w_inv"], grid_h_inv=p["grid_h_inv"],
+                scale_factors=scale, n_levels=n_levels, log_scale_factor=f32(np.log(f32(sf))), view_cos_limit=f32(view_cos_limit),
+                far_points=int(bool(far_points)), th_far_points=f32(th_far_points), th=f32(th), nn_ratio=f32(nn_ratio),
+                cur_kps_un=kps, cur_u_right=cur_ur, cur_desc=cur_desc.reshape(-1, 32), cur_has_mp_obs=cur_obs)
+
+
 def _rot_from_quat(q):
     x, y, z, w = q / np.linalg.norm(q)
     return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)],

@@ -477,6 +477,60 @@ typedef struct {
 int gfs_search_by_projection_map(gfs_sbp* h, const gfs_sbp_map_problem* problems, int B, int32_t* const* cur_match,
                                  int32_t* nmatches);
 
+/*      void Tracking::SearchLocalPoints()                                       src/Tracking.cc:4294-4359
+ *    second loop onwards, in one call: Frame::isInFrustum (src/Frame.cc:876-931, Nleft == -1, Pinhole::project
+ *    src/CameraModels/Pinhole.cpp:43-49) with MapPoint::PredictScale (src/MapPoint.cc:565-579: std::ceil(float) of glibc's logf)
+ *    for every listed local map point, the filter of src/ORBmatcher.cc:53-58, and the search above over the survivors in list
+ *    order.  The caller lists the points that pass `mnLastFrameSeen != F.mnId && !isBad()` (:4320-4321).  All arithmetic is
+ *    float, every operation rounded once, sums left to right (DESIGN.md section 12 states the rule and its two chosen cases). */
+typedef struct {
+  int32_t n_mp;
+  const float* mp_xw;            /* [n_mp][3] GetWorldPos() */
+  const float* mp_normal;        /* [n_mp][3] GetNormal() */
+  const float* mp_min_dist;      /* [n_mp] mfMinDistance (raw: the 0.8f of GetMinDistanceInvariance is applied here) */
+  const float* mp_max_dist;      /* [n_mp] mfMaxDistance (raw: 1.2f likewise) */
+  const uint8_t* mp_desc;        /* [n_mp][32] GetDescriptor() */
+  const uint8_t* mp_has_obs;     /* [n_mp] Observations() > 0 */
+  float Rcw[9], tcw[3], Ow[3];   /* F.mRcw (row-major), F.mtcw, F.mOw */
+  float fx, fy, cx, cy, bf;      /* F.mpCamera (Pinhole), F.mbf */
+  float min_x, max_x, min_y, max_y; /* F.mnMinX ... mnMaxY */
+  float grid_w_inv, grid_h_inv;  /* F.mfGridElementWidthInv / HeightInv */
+  const float* scale_factors;    /* F.mvScaleFactors */
+  int32_t n_levels;              /* F.mnScaleLevels, <= 16 */
+  float log_scale_factor;        /* F.mfLogScaleFactor */
+  float view_cos_limit;          /* viewingCosLimit (0.5 in Tracking::SearchLocalPoints) */
+  int32_t far_points;            /* mpLocalMapper->mbFarPoints */
+  float th_far_points;           /* mpLocalMapper->mThFarPoints */
+  float th;                      /* window factor */
+  float nn_ratio;                /* ORBmatcher::mfNNratio (0.8) */
+  int32_t n_cur;
+  const gfs_keypoint* cur_kps_un; /* F.mvKeysUn */
+  const float* cur_u_right;      /* F.mvuRight */
+  const uint8_t* cur_desc;       /* F.mDescriptors */
+  const uint8_t* cur_has_mp_obs; /* F.mvpMapPoints[i] != NULL && ->Observations() > 0 on entry */
+} gfs_local_points_problem;
+
+typedef struct {                 /* caller-owned arrays */
+  uint8_t* in_view;              /* [n_mp] mbTrackInView */
+  float* proj;                   /* [n_mp][3] mTrackProjX, mTrackProjY (-1, -1 until the image-bounds tests are passed), mTrackProjXR
+                                  * (defined only where in_view) */
+  float* depth;                  /* [n_mp] mTrackDepth   (defined where in_view, like the next two) */
+  float* view_cos;               /* [n_mp] mTrackViewCos */
+  int32_t* level;                /* [n_mp] mnTrackScaleLevel */
+  int32_t* cur_match;            /* [n_cur] >= 0 = F.mvpMapPoints[i] := the caller's list entry cur_match[i]; -1 = left as it was */
+  int32_t n_to_match;            /* nToMatch: the number of in_view points */
+  int32_t n_searched;            /* size of the search set: in_view and not beyond th_far_points */
+  int32_t nmatches;              /* return value of SearchByProjection */
+} gfs_local_points_result;
+
+/* Allocates the workspace of gfs_search_local_points for lists of up to max_local_points map points per frame (handles that
+ * never call it are unchanged). */
+int gfs_sbp_reserve_local(gfs_sbp* h, int max_local_points);
+/* B independent frames (host pointers).  GFS_ERR_CAPACITY: a list longer than the reserve, or a search set larger than the handle's
+ * max_last (nothing is truncated: the per-point outputs and counts are delivered, the search is skipped, nmatches = 0 and cur_match
+ * all -1 for that frame).  GFS_ERR_INVALID_ARG: n_levels outside 1..16 or a NULL array.  The handle stays usable. */
+int gfs_search_local_points(gfs_sbp* h, const gfs_local_points_problem* problems, int B, gfs_local_points_result* results);
+
 /* ============================================================================================
  * 8. GMS filter of the brute-force matches (the second half of ORBmatcher::SearchWithGMS / SearchForInitializationWithGMS)
  *      gms_matcher gms(kp1, frameSize, kp2, frameSize, matches_all); nmatches = gms.GetInlierMask(vbInliers, false, false);

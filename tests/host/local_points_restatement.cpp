@@ -1,0 +1,199 @@
+// TEST INFRASTRUCTURE — NOT PRODUCT CODE.  Sequential CPU restatement of the second loop of Tracking::SearchLocalPoints (reference
+// src/Tracking.cc:4312-4358) for single-camera frames: Frame::isInFrustum (src/Frame.cc:876-931, Nleft == -1, Pinhole::project
+// src/CameraModels/Pinhole.cpp:43-49), MapPoint::PredictScale (src/MapPoint.cc:565-579) calling the HOST's logf, the far-points
+// filter of ORBmatcher::SearchByProjection (src/ORBmatcher.cc:53-58), then the search itself: oracle/sbp_oracle.cpp included
+// unchanged, gfso_search_by_projection_map on the compacted list.  The checker of gfs_search_local_points (geoflowslam_amd/csrc/
+// sbp.hip); the tests build it with g++ -O2 -std=c++17 -ffp-contract=off.
+//
+// Float arithmetic, one rounding per operation, sums left to right.  Two cases the reference leaves open
+// are decided there: a projection that is not finite after the image-bounds tests (0 / 0) puts the point out with (-1, -1) left
+// on it, and a level quotient that no int holds gives level 0 (what x86-64's conversion, INT_MIN, and the clamp produce).
+#include <algorithm>
+#include <climits>
+#include <cmath>
+#include <cstdint>
+#include <cstring>
+#include <vector>
+
+#include "gfs_abi.h"
+#include "gfs_oracle.h"
+
+namespace sbo {
+#include "sbp_oracle.cpp"
+}
+
+namespace {
+
+constexpr float kMinDistFactor = 0.8f;  // GetMinDistanceInvariance: 0.8f * mfMinDistance
+constexpr float kMaxDistFactor = 1.2f;  // GetMaxDistanceInvariance: 1.2f * mfMaxDistance
+
+// where isInFrustum returned
+enum Exit { kInView = 0, kNegDepth, kLeft, kRight, kTop, kBottom, kNotFinite, kTooNear, kTooFar, kViewAngle };
+
+struct PointOut {
+  int exit, raw_level, level;  // raw_level: before the clamp (INT_MIN when no int holds it)
+  bool in_view;
+  float proj[3], depth, view_cos;
+};
+
+// MapPoint::PredictScale(currentDist, Frame*)
+int predict_scale(float max_distance, float dist, float log_scale_factor, int n_levels, int* raw) {
+  volatile float ratio = max_distance / dist;  // (volatile: the call below is the library's logf, never a folded constant)
+  const float q = ::logf(ratio) / log_scale_factor;
+  const float c = std::ceil(q);
+  int n = (c >= -2147483648.0f && c < 2147483648.0f) ? (int)c : INT_MIN;
+  *raw = n;
+  if (n < 0)
+    n = 0;
+  else if (n >= n_levels)
+    n = n_levels - 1;
+  return n;
+}
+
+PointOut in_frustum(const gfs_local_points_problem& p, int i) {
+  PointOut o{};
+  o.in_view = false;
+  o.proj[0] = -1.0f;
+  o.proj[1] = -1.0f;
+  const float* P = p.mp_xw + 3 * i;
+  const float* R = p.Rcw;
+  float Pc[3];
+  for (int r = 0; r < 3; r++) Pc[r] = ((R[3 * r] * P[0] + R[3 * r + 1] * P[1]) + R[3 * r + 2] * P[2]) + p.tcw[r];
+  const float Pc_dist = std::sqrt((Pc[0] * Pc[0] + Pc[1] * Pc[1]) + Pc[2] * Pc[2]);
+  o.depth = Pc_dist;
+  const float invz = 1.0f / Pc[2];
+  if (Pc[2] < 0.0f) return o.exit = kNegDepth, o;
+  const float u = (p.fx * Pc[0]) / Pc[2] + p.cx;
+  const float v = (p.fy * Pc[1]) / Pc[2] + p.cy;
+  if (u < p.min_x) return o.exit = kLeft, o;
+  if (u > p.max_x) return o.exit = kRight, o;
+  if (v < p.min_y) return o.exit = kTop, o;
+  if (v > p.max_y) return o.exit = kBottom, o;
+  if (!std::isfinite(u) || !std::isfinite(v)) return o.exit = kNotFinite, o;
+  o.proj[0] = u;
+  o.proj[1] = v;
+  const float maxDistance = kMaxDistFactor * p.mp_max_dist[i], minDistance = kMinDistFactor * p.mp_min_dist[i];
+  const float PO[3] = {P[0] - p.Ow[0], P[1] - p.Ow[1], P[2] - p.Ow[2]};
+  const float dist = std::sqrt((PO[0] * PO[0] + PO[1] * PO[1]) + PO[2] * PO[2]);
+  if (dist < minDistance) return o.exit = kTooNear, o;
+  if (dist > maxDistance) return o.exit = kTooFar, o;
+  const float* Pn = p.mp_normal + 3 * i;
+  const float viewCos = ((PO[0] * Pn[0] + PO[1] * Pn[1]) + PO[2] * Pn[2]) / dist;
+  o.view_cos = viewCos;
+  if (viewCos < p.view_cos_limit) return o.exit = kViewAngle, o;
+  o.level = predict_scale(p.mp_max_dist[i], dist, p.log_scale_factor, p.n_levels, &o.raw_level);
+  o.in_view = true;
+  o.proj[2] = u - p.bf * invz;
+  o.exit = kInView;
+  return o;
+}
+
+struct Compacted {
+  std::vector<float> proj, cos;
+  std::vector<int32_t> level, index;
+  std::vector<uint8_t> desc, obs;
+};
+
+// the second loop of SearchLocalPoints and the filter of ORBmatcher.cc:53-58: per-point outputs, nToMatch, the search set
+int frustum_loop(const gfs_local_points_problem* p, gfs_local_points_result* r, int32_t* exits, int32_t* raw_level, Compacted& c) {
+  const int n = p->n_mp;
+  std::vector<float>&c_proj = c.proj, &c_cos = c.cos;
+  std::vector<int32_t>&c_level = c.level, &c_index = c.index;
+  std::vector<uint8_t>&c_desc = c.desc, &c_obs = c.obs;
+  int nToMatch = 0;
+  for (int i = 0; i < n; i++) {
+    const PointOut o = in_frustum(*p, i);
+    r->in_view[i] = o.in_view ? 1 : 0;
+    for (int k = 0; k < 3; k++) r->proj[3 * i + k] = o.proj[k];
+    r->depth[i] = o.depth;
+    r->view_cos[i] = o.view_cos;
+    r->level[i] = o.level;
+    if (exits) exits[i] = o.exit;
+    if (raw_level) raw_level[i] = o.in_view ? o.raw_level : 0;
+    if (!o.in_view) continue;
+    nToMatch++;
+    if (p->far_points && o.depth > p->th_far_points) continue;  // ORBmatcher.cc:55
+    c_index.push_back(i);
+    c_proj.insert(c_proj.end(), o.proj, o.proj + 3);
+    c_cos.push_back(o.view_cos);
+    c_level.push_back(o.level);
+    c_desc.insert(c_desc.end(), p->mp_desc + 32 * (size_t)i, p->mp_desc + 32 * (size_t)i + 32);
+    c_obs.push_back(p->mp_has_obs[i]);
+  }
+  r->n_to_match = nToMatch;
+  r->n_searched = (int)c_index.size();
+  return nToMatch;
+}
+
+}  // namespace
+
+// The frustum loop alone, with the compacted arrays handed out ([n_mp] entries each at most): what a caller of
+// gfs_search_by_projection_map had to do on the host before.  Returns the size of the search set.
+extern "C" int lpr_frustum_compact(const gfs_local_points_problem* p, gfs_local_points_result* r, int32_t* index, float* c_proj,
+                                   int32_t* c_level, float* c_cos, uint8_t* c_desc, uint8_t* c_obs) {
+  Compacted c;
+  c.index.reserve(p->n_mp);
+  c.proj.reserve(3 * (size_t)p->n_mp);
+  c.level.reserve(p->n_mp);
+  c.cos.reserve(p->n_mp);
+  c.desc.reserve(32 * (size_t)p->n_mp);
+  c.obs.reserve(p->n_mp);
+  frustum_loop(p, r, nullptr, nullptr, c);
+  std::copy(c.index.begin(), c.index.end(), index);
+  std::copy(c.proj.begin(), c.proj.end(), c_proj);
+  std::copy(c.level.begin(), c.level.end(), c_level);
+  std::copy(c.cos.begin(), c.cos.end(), c_cos);
+  std::copy(c.desc.begin(), c.desc.end(), c_desc);
+  std::copy(c.obs.begin(), c.obs.end(), c_obs);
+  return (int)c.index.size();
+}
+
+// The restatement of gfs_search_local_points for one frame.  exits / raw_level [n_mp] (what the input-condition tests look at),
+// index [n_mp] (the list index of every entry of the search set; the first n_searched are written) may be NULL.
+extern "C" int lpr_search_local_points(const gfs_local_points_problem* p, gfs_local_points_result* r, int32_t* exits, int32_t* raw_level,
+                                       int32_t* index) {
+  Compacted c;
+  frustum_loop(p, r, exits, raw_level, c);
+  std::vector<float>&c_proj = c.proj, &c_cos = c.cos;
+  std::vector<int32_t>&c_level = c.level, &c_index = c.index;
+  std::vector<uint8_t>&c_desc = c.desc, &c_obs = c.obs;
+  if (index) std::copy(c_index.begin(), c_index.end(), index);
+  std::vector<float> xy(2 * (size_t)p->n_cur);
+  std::vector<int32_t> oct(p->n_cur);
+  for (int i = 0; i < p->n_cur; i++) {
+    xy[2 * i] = p->cur_kps_un[i].x;
+    xy[2 * i + 1] = p->cur_kps_un[i].y;
+    oct[i] = p->cur_kps_un[i].octave;
+  }
+  gfso_sbp_map_problem m{};
+  m.n_mp = (int)c_index.size();
+  m.mp_proj = c_proj.data();
+  m.mp_level = c_level.data();
+  m.mp_view_cos = c_cos.data();
+  m.mp_desc = c_desc.data();
+  m.mp_has_obs = c_obs.data();
+  m.n_cur = p->n_cur;
+  m.cur_xy = xy.data();
+  m.cur_octave = oct.data();
+  m.cur_u_right = p->cur_u_right;
+  m.cur_desc = p->cur_desc;
+  m.cur_has_mp_obs = p->cur_has_mp_obs;
+  m.min_x = p->min_x;
+  m.min_y = p->min_y;
+  m.grid_w_inv = p->grid_w_inv;
+  m.grid_h_inv = p->grid_h_inv;
+  m.scale_factors = p->scale_factors;
+  m.n_levels = p->n_levels;
+  m.th = p->th;
+  m.nn_ratio = p->nn_ratio;
+  std::vector<int32_t> cm(std::max(p->n_cur, 1));
+  r->nmatches = sbo::gfso_search_by_projection_map(&m, cm.data());
+  for (int i = 0; i < p->n_cur; i++) r->cur_match[i] = cm[i] >= 0 ? c_index[cm[i]] : cm[i];
+  return 0;
+}
+
+// min / max distance factors as compiled in
+extern "C" void lpr_constants(float* out) {
+  out[0] = kMinDistFactor;
+  out[1] = kMaxDistFactor;
+}
