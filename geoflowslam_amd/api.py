@@ -330,7 +330,7 @@ ABI_SYMBOLS = [
     "gfs_gicp_fetch_preprocessed", "gfs_gicp_tile_stats", "gfs_gicp_knn_stats", "gfs_gicp_coop_stats", "gfs_frame_rgbd", "gfs_gicp_align_next", "gfs_gicp_align_next_batch_device", "gfs_test_voxel_sort", "gfs_test_wave_std_sort",
     "gfs_lba_create", "gfs_lba_destroy", "gfs_lba_solve", "gfs_lba_solve_bool", "gfs_lba_linearize", "gfs_lba_batch_create", "gfs_lba_batch_destroy",
     "gfs_lba_solve_batch", "gfs_lba_lidar_reserve", "gfs_lba_solve_lidar", "gfs_lba_solve_lidar_bool", "gfs_lba_linearize_lidar",
-    "gfs_lba_fetch_lidar_edges",
+    "gfs_lba_fetch_lidar_edges", "gfs_test_lba_stop_at_look", "gfs_test_lba_last_looks",
     "gfs_frame_create", "gfs_frame_destroy", "gfs_depth_to_cloud", "gfs_depth_to_cloud_batch_device", "gfs_depth_convert_u16_batch_device", "gfs_stereo_from_rgbd",
     "gfs_stereo_from_rgbd_batch_device",
     "gfs_pose_create", "gfs_pose_destroy", "gfs_pose_optimize", "gfs_pose_set_sum_order",
@@ -409,6 +409,8 @@ def lib():
             L.gfs_lba_batch_create.argtypes = [i, i, i, i, i, C.POINTER(vp)]
             L.gfs_lba_batch_destroy.argtypes = [vp]
             L.gfs_lba_solve_batch.argtypes = [vp, vp, vp, i, vp]
+            L.gfs_test_lba_stop_at_look.argtypes = [i]
+            L.gfs_test_lba_last_looks.argtypes = [C.POINTER(C.c_int32)] * 4
         if hasattr(L, "gfs_lba_solve_lidar"):
             L.gfs_lba_lidar_reserve.argtypes = [vp, i]
             L.gfs_lba_solve_lidar.argtypes = [vp, C.POINTER(LbaProblem), C.POINTER(LbaLidar), C.POINTER(LbaSolution), vp, vp]
@@ -825,6 +827,20 @@ def _lba_problem(prob):
     for name in ("fx", "fy", "cx", "cy", "bf", "huber_mono", "huber_stereo"):
         setattr(P, name, float(prob[name]))
     return P, keep
+
+
+def lba_stop_at_look(look):
+    """Test hook (include/gfs_abi_test.h): script the stop flag of THIS thread's next LocalBundleAdjustment / LocalVisualLidarBA /
+    batch call -- from its look-th evaluation on the flag reads as raised (look 0 = the entry check); negative disarms.  The call
+    needs a stop_flag array."""
+    _check(lib().gfs_test_lba_stop_at_look(int(look)), "gfs_test_lba_stop_at_look")
+
+
+def lba_last_looks():
+    """-> dict(looks, discarded, forced_decides, ahead_at_stop) of this thread's last LBA solve (gfs_test_lba_last_looks)."""
+    v = [C.c_int32() for _ in range(4)]
+    _check(lib().gfs_test_lba_last_looks(*[C.byref(x) for x in v]), "gfs_test_lba_last_looks")
+    return dict(looks=v[0].value, discarded=v[1].value, forced_decides=v[2].value, ahead_at_stop=v[3].value)
 
 
 class Optimizer:

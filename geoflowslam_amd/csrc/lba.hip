@@ -1872,11 +1872,36 @@ int lba_raise_lds_limits(int device) {
 
 // The caller's force-stop flag, read LIVE every time the host loop looks at it: an int (gfs_lba_solve) or the C++ bool the
 // reference hands in (Optimizer::LocalBundleAdjustment's pbStopFlag = &mbAbortBA, one byte: gfs_lba_solve_bool).
+// Test hook (include/gfs_abi_test.h: gfs_test_lba_stop_at_look): a SCRIPTED flag.  Every evaluation of the flag by the calling thread's
+// solve is a "look" (0 = the entry check); armed with `at`, looks at, at + 1, ... read as raised whatever the caller's memory holds.
+// Nothing else changes: the same kernels are queued in the same order as for a flag that another thread raises at that moment.
+struct StopScript {
+  int at = -1;         // < 0: not armed
+  int looks = 0;       // looks made by this thread's current / last call
+  int discarded = 0;   // iterations that had run ahead of a raised flag and were put back (k_lba_restore)
+  int forced = 0;      // forced decides queued (k_lba_decide / kb_lba_decide with force_end = 1)
+  int ahead = -1;      // was a gated iteration queued behind the decide the host waited for when it saw the flag up?  -1: never saw it
+};
+static thread_local StopScript tl_stop_script;
+struct StopScriptCall {  // one solve call: the counters start at zero, the script disarms itself when the call returns
+  StopScriptCall() {
+    StopScript& T = tl_stop_script;
+    T.looks = T.discarded = T.forced = 0;
+    T.ahead = -1;
+  }
+  ~StopScriptCall() { tl_stop_script.at = -1; }
+};
+
 struct StopFlag {
   volatile const int* i = nullptr;
   volatile const unsigned char* b = nullptr;
   explicit operator bool() const { return i || b; }
-  bool operator*() const { return (i && *i) || (b && *b); }
+  bool operator*() const {
+    StopScript& T = tl_stop_script;
+    const int look = T.looks++;
+    if (T.at >= 0 && look >= T.at) return true;
+    return (i && *i) || (b && *b);
+  }
 };
 
 // The lidar key-frames of a window (lidar_prepare): their association and compaction are queued on the handle's stream
@@ -1993,6 +2018,8 @@ int run(gfs_lba* h, const gfs_lba_problem* p, const HostPrep& P, int mode, StopF
         if (stop && *stop) {
           GFS_LAUNCH("k_lba_decide", k_lba_decide, dim3(1), dim3(64), 0, s, D, 1, d_flags + kFlagInts * (n_decides & 1), 0);
           n_decides++;
+          tl_stop_script.forced++;
+          tl_stop_script.ahead = ahead ? 1 : 0;
           break;
         }
         if ((rc = trial_group(0))) return rc;
@@ -2008,6 +2035,8 @@ int run(gfs_lba* h, const gfs_lba_problem* p, const HostPrep& P, int mode, StopF
         GFS_HIP(hipStreamSynchronize(s));  // (the iteration running ahead: let it finish, nothing reads the snapshot slot meanwhile)
         GFS_LAUNCH("k_lba_restore", k_lba_restore, dim3(1), dim3(64), 0, s, D, cur, iters, lambda, last_chi);
         GFS_LAUNCH("k_lba_errors", k_lba_errors, g_err, dim3(kMk), 0, s, D, 0, 0);
+        tl_stop_script.discarded++;
+        tl_stop_script.ahead = 1;
         break;
       }
       waiting = waiting + 1;
@@ -2203,6 +2232,7 @@ static void lba_fetch_finish(const gfs_lba_problem* p, const HostPrep& P, const 
 
 static int lba_solve_lidar_impl(gfs_lba* h, const gfs_lba_problem* p, const gfs_lba_lidar* L, gfs_lba_solution* sol,
                                 int32_t* pose_lidar_edges, StopFlag stop) {
+  StopScriptCall script_call;
   GFS_REQUIRE(h && p && L && sol, GFS_ERR_INVALID_ARG, "gfs_lba_solve_lidar: NULL argument");
   if (stop && *stop) {  // if (pbStopFlag) if (*pbStopFlag) return;  (src/Optimizer.cc:1502-1503)
     gfs::set_error("gfs_lba_solve_lidar: stop flag raised before optimisation");
@@ -2228,6 +2258,7 @@ static int lba_solve_lidar_impl(gfs_lba* h, const gfs_lba_problem* p, const gfs_
   return GFS_OK;
 }
 static int lba_solve_impl(gfs_lba* h, const gfs_lba_problem* p, gfs_lba_solution* sol, StopFlag stop) {
+  StopScriptCall script_call;
   GFS_REQUIRE(h && p && sol, GFS_ERR_INVALID_ARG, "gfs_lba_solve: NULL argument");
   if (stop && *stop) {  // if (pbStopFlag) if (*pbStopFlag) return;  (src/Optimizer.cc:1955-1956)
     gfs::set_error("gfs_lba_solve: stop flag raised before optimisation");
@@ -2327,6 +2358,7 @@ void gfs_lba_batch_destroy(gfs_lba_batch* b) {
 // n independent windows (replicas of the single-window solve: "LBA of one map does not shard") solved
 // together: per window exactly the arithmetic of gfs_lba_solve, the launches shared by all of them.
 static int lba_solve_batch_impl(gfs_lba_batch* b, const gfs_lba_problem* problems, gfs_lba_solution* solutions, int n, StopFlag stop) {
+  StopScriptCall script_call;
   GFS_REQUIRE(b && problems && solutions && n > 0, GFS_ERR_INVALID_ARG, "gfs_lba_solve_batch: invalid argument");
   GFS_REQUIRE(n <= b->max_windows, GFS_ERR_CAPACITY, "gfs_lba_solve_batch: %d windows exceed the handle's %d", n, b->max_windows);
   if (stop && *stop) {
@@ -2445,6 +2477,8 @@ static int lba_solve_batch_impl(gfs_lba_batch* b, const gfs_lba_problem* problem
     GFS_HIP(hipEventRecord(b->ev_round[round & 1], s));
     rounds_run++;
     if (force_end) {
+      tl_stop_script.forced++;
+      tl_stop_script.ahead = 0;
       GFS_HIP(hipStreamSynchronize(s));
       break;
     }
@@ -2632,6 +2666,19 @@ int gfs_lba_fetch_lidar_edges(gfs_lba* h, int pose, int32_t* index, float* plane
   GFS_HIP(hipMemcpy(index, h->d_lidx.p + o, (size_t)m * 4, hipMemcpyDeviceToHost));
   GFS_HIP(hipMemcpy(plane, h->d_leplane.p + o, (size_t)m * 16, hipMemcpyDeviceToHost));
   GFS_HIP(hipMemcpy(s, h->d_les.p + o, (size_t)m * 4, hipMemcpyDeviceToHost));
+  return GFS_OK;
+}
+
+int gfs_test_lba_stop_at_look(int look) {
+  tl_stop_script.at = look < 0 ? -1 : look;
+  return GFS_OK;
+}
+int gfs_test_lba_last_looks(int32_t* looks, int32_t* discarded, int32_t* forced_decides, int32_t* ahead_at_stop) {
+  const StopScript& T = tl_stop_script;
+  if (looks) *looks = T.looks;
+  if (discarded) *discarded = T.discarded;
+  if (forced_decides) *forced_decides = T.forced;
+  if (ahead_at_stop) *ahead_at_stop = T.ahead;
   return GFS_OK;
 }
 

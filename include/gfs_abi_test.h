@@ -47,6 +47,20 @@ int gfs_test_wave_std_sort(int device, const unsigned* keys, int n, unsigned sho
 int gfs_test_lidar_map_grid(const gfs_lidar_map* map, int32_t* start, int cap_start, float* pts, int32_t* index, int cap_pts, int32_t* nb,
                             int32_t* n);
 
+/* Test hook: a SCRIPTED stop flag for the calling thread's next gfs_lba_solve, gfs_lba_solve_bool, gfs_lba_solve_lidar(_bool) or
+ * gfs_lba_solve_batch call.  Every evaluation of the caller's stop flag by that call is a "look": look 0 is the entry check
+ * (src/Optimizer.cc:1955-1956), look 1 and every later top of an LM iteration is g2o's `i < iterations && !terminate()`
+ * (core/sparse_optimizer.cpp), and one more follows every rejected trial that is to be retried (`rho < 0 && qmax < max &&
+ * !terminate()`, core/optimization_algorithm_levenberg.cpp); the batched entry looks once per round of trials.  Armed with look >= 0,
+ * the looks number look, look + 1, ... read as raised, whatever the caller's memory holds; the call needs a non-NULL stop pointer
+ * (a NULL one is never looked at).  A negative value disarms; the script disarms itself when the call returns.  A call made while
+ * the hook is not armed queues exactly what it queued without the hook. */
+int gfs_test_lba_stop_at_look(int look);
+/* What the calling thread's last such call did: the looks it made; the iterations that had run ahead of a raised flag and were
+ * discarded (k_lba_restore); the forced decides it queued (a trial closed without a rho test); *ahead_at_stop = 1 / 0 when the flag
+ * was seen up with / without an iteration queued ahead of the host's knowledge, -1 when it was not seen up after the entry check. */
+int gfs_test_lba_last_looks(int32_t* looks, int32_t* discarded, int32_t* forced_decides, int32_t* ahead_at_stop);
+
 #ifdef __cplusplus
 }
 #endif

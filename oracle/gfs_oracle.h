@@ -163,6 +163,19 @@ typedef struct {
 } gfso_lba_solution;
 
 int gfso_lba_solve(const gfso_lba_problem*, gfso_lba_solution*);
+/* per LM trial, in order: the iteration it belongs to, its rho, 1 = accepted / 0 = rejected / 2 = closed by close_at_trial (no rho
+ * test); at most cap entries are written, n_trials counts all of them.  looks = evaluations of the stop flag. */
+typedef struct {
+  int32_t cap;
+  int32_t* iteration;
+  double* rho;
+  uint8_t* accepted;
+  int32_t n_trials, looks;
+} gfso_lba_trace;
+/* gfso_lba_solve with a scripted stop flag (raised from its stop_at_look-th evaluation on; look 0 = the entry check, which returns 1
+ * and writes nothing), or with the batched entry's closing rule (the (close_at_trial + 1)-th trial is evaluated and dropped, the
+ * loop ends); negative = not scripted.  trace may be NULL. */
+int gfso_lba_solve_scripted(const gfso_lba_problem*, gfso_lba_solution*, int stop_at_look, int close_at_trial, gfso_lba_trace* trace);
 /* one buildSystem (block_solver.hpp:502-558): Hpp (n_free*36 diag blocks), Hll (n_points*9), b (6*n_free+3*n_points),
  * Hpl per edge (18, pose-rows x point-cols, zero for fixed poses); returns active robust chi2 */
 double gfso_lba_linearize(const gfso_lba_problem*, double* Hpp, double* Hll, double* Hpl, double* bp, double* bl,

@@ -328,8 +328,36 @@ double gfso_lba_linearize(const gfso_lba_problem* p, double* Hpp, double* Hll, d
 }
 
 // SparseOptimizer::optimize (core/sparse_optimizer.cpp:354-419) + OptimizationAlgorithmLevenberg::solve
-// (core/optimization_algorithm_levenberg.cpp:61-168)
-int gfso_lba_solve(const gfso_lba_problem* p, gfso_lba_solution* s) {
+// (core/optimization_algorithm_levenberg.cpp:61-168), with a SCRIPTED force-stop flag and a trace.
+//
+// stop_at_look >= 0: the caller's flag (pbStopFlag -> setForceStopFlag -> terminate()) reads as raised from its stop_at_look-th
+// evaluation on.  The reference evaluates it
+//   look 0                                   if (pbStopFlag) if (*pbStopFlag) return;  (src/Optimizer.cc:1955-1956) -- returns 1, no outputs
+//   look 1 and every later top of an         for (i = 0; i < iterations && !terminate() && ok; i++)  (core/sparse_optimizer.cpp):
+//   iteration                                `i < iterations` short-circuits, so no look follows the last iteration, and a solver
+//                                            that returned Terminate breaks out of the body before the condition is reached
+//   after every rejected trial               while (rho < 0 && qmax < maxTrialsAfterFailure && !terminate())
+//                                            (core/optimization_algorithm_levenberg.cpp): only a trial that would be retried looks
+// A stop after a rejected trial ends solve() with OK (qmax < max, rho != 0): the iteration is counted, lambda keeps the rejection's
+// growth, the estimates are the popped ones and the edges keep the rejected trial's errors.  optimize()'s loop condition then
+// evaluates the flag once more and finds it up: that evaluation decides nothing and is not counted, `looks` of a stopped run is
+// stop_at_look + 1.
+//
+// close_at_trial = r >= 0 restates the batched entry's rule (gfs_lba_solve_batch, DESIGN.md: the flag is looked at once per round of
+// trials, a round that sees it up closes every running iteration): the window's (r + 1)-th trial is evaluated and dropped without a
+// rho test, the iteration is counted, lambda is left alone, the loop ends.  A window whose loop ended before that trial is untouched.
+int gfso_lba_solve_scripted(const gfso_lba_problem* p, gfso_lba_solution* s, int stop_at_look, int close_at_trial,
+                            gfso_lba_trace* trace) {
+  int looks = 0, n_trials = 0;
+  auto stopped = [&]() {  // one look (an unarmed script counts them too)
+    const int k = looks++;
+    return stop_at_look >= 0 && k >= stop_at_look;
+  };
+  if (trace) trace->n_trials = trace->looks = 0;
+  if (stopped()) {
+    if (trace) trace->looks = looks;
+    return 1;
+  }
   Problem S;
   init_problem(S, p);
   System A;
@@ -338,7 +366,7 @@ int gfso_lba_solve(const gfso_lba_problem* p, gfso_lba_solution* s) {
   double currentLambda = -1, ni = 2;
   int nBad = 0, iters = 0;
   double lastChi = 0;
-  for (int iteration = 0; iteration < p->iterations; iteration++) {
+  for (int iteration = 0; iteration < p->iterations && !stopped(); iteration++) {
     compute_active_errors(S);
     double currentChi = active_robust_chi2(S);
     double tempChi = currentChi;
@@ -356,6 +384,7 @@ int gfso_lba_solve(const gfso_lba_problem* p, gfso_lba_solution* s) {
     }
     double rho = 0;
     int qmax = 0;
+    bool closed = false, flag_up = false;
     do {
       const std::vector<Pose> poses_backup = S.poses;  // _optimizer->push()
       const std::vector<double> points_backup = S.points;
@@ -367,6 +396,18 @@ int gfso_lba_solve(const gfso_lba_problem* p, gfso_lba_solution* s) {
         for (size_t k = 0; k < S.points.size(); k++) S.points[k] += xl[k];
       }
       compute_active_errors(S);
+      if (close_at_trial >= 0 && n_trials == close_at_trial) {  // the batch rule: dropped without a rho test
+        S.poses = poses_backup;
+        S.points = points_backup;
+        if (trace && n_trials < trace->cap) {
+          trace->iteration[n_trials] = iteration;
+          trace->rho[n_trials] = 0;
+          trace->accepted[n_trials] = 2;
+        }
+        n_trials++;
+        closed = true;
+        break;
+      }
       tempChi = active_robust_chi2(S);
       if (!ok2) tempChi = std::numeric_limits<double>::max();
       rho = (currentChi - tempChi);
@@ -377,7 +418,8 @@ int gfso_lba_solve(const gfso_lba_problem* p, gfso_lba_solution* s) {
       }
       scale += 1e-3;
       rho /= scale;
-      if (rho > 0 && std::isfinite(tempChi)) {
+      const bool accept = rho > 0 && std::isfinite(tempChi);
+      if (accept) {
         double alpha = 1. - std::pow((2 * rho - 1), 3);
         alpha = std::min(alpha, goodStepUpperScale);
         const double scaleFactor = std::max(goodStepLowerScale, alpha);
@@ -391,15 +433,26 @@ int gfso_lba_solve(const gfso_lba_problem* p, gfso_lba_solution* s) {
         S.points = points_backup;
       }
       qmax++;
-    } while (rho < 0 && qmax < maxTrialsAfterFailure);
+      if (trace && n_trials < trace->cap) {
+        trace->iteration[n_trials] = iteration;
+        trace->rho[n_trials] = rho;
+        trace->accepted[n_trials] = accept ? 1 : 0;
+      }
+      n_trials++;
+    } while (rho < 0 && qmax < maxTrialsAfterFailure && !(flag_up = stopped()));
     iters++;
     lastChi = currentChi;
+    if (closed || flag_up) break;
     if (qmax == maxTrialsAfterFailure || rho == 0) break;  // Terminate
     if ((iniChi - currentChi) * 1e3 < iniChi)
       nBad++;
     else
       nBad = 0;
     if (nBad >= 3) break;
+  }
+  if (trace) {
+    trace->n_trials = n_trials;
+    trace->looks = looks;
   }
   if (p->iterations <= 0) compute_active_errors(S);
   for (int i = 0; i < p->n_poses; i++) {
@@ -420,5 +473,7 @@ int gfso_lba_solve(const gfso_lba_problem* p, gfso_lba_solution* s) {
   s->final_lambda = currentLambda;
   return 0;
 }
+
+int gfso_lba_solve(const gfso_lba_problem* p, gfso_lba_solution* s) { return gfso_lba_solve_scripted(p, s, -1, -1, nullptr); }
 
 }  // extern "C"

@@ -85,6 +85,17 @@ class LbaSolution(C.Structure):
     ]
 
 
+class LbaTrace(C.Structure):
+    _fields_ = [
+        ("cap", C.c_int32),
+        ("iteration", C.c_void_p),
+        ("rho", C.c_void_p),
+        ("accepted", C.c_void_p),
+        ("n_trials", C.c_int32),
+        ("looks", C.c_int32),
+    ]
+
+
 def build():
     subprocess.run(["make", "-s", "-C", _HERE, "libgfs_oracle.so"], check=True)
 
@@ -133,6 +144,8 @@ def lib():
         if hasattr(L, "gfso_lba_solve"):
             L.gfso_lba_solve.restype = C.c_int
             L.gfso_lba_solve.argtypes = [C.POINTER(LbaProblem), C.POINTER(LbaSolution)]
+            L.gfso_lba_solve_scripted.restype = C.c_int
+            L.gfso_lba_solve_scripted.argtypes = [C.POINTER(LbaProblem), C.POINTER(LbaSolution), C.c_int, C.c_int, C.POINTER(LbaTrace)]
             L.gfso_lba_linearize.restype = C.c_double
             L.gfso_lba_linearize.argtypes = [C.POINTER(LbaProblem)] + [C.c_void_p] * 6
         _LIB = L
@@ -405,6 +418,28 @@ def lba_solve(prob):
     lib().gfso_lba_solve(C.byref(P), C.byref(S))
     out.update(iterations_run=S.iterations_run, final_chi2=S.final_chi2, final_lambda=S.final_lambda)
     return out
+
+
+def lba_solve_scripted(prob, stop_at_look=-1, close_at_trial=-1):
+    """lba_solve with a scripted stop flag (raised from its stop_at_look-th evaluation on) or the batched entry's closing rule
+    (the (close_at_trial + 1)-th trial is evaluated and dropped, the loop ends).  -> (lba_solve's dict, or None when the entry check
+    stopped the call; trace = dict(iteration [n], rho [n], accepted [n]: 1 accepted / 0 rejected / 2 closed, looks))"""
+    P, keep = _lba_struct(LbaProblem, prob)
+    out = dict(pose_q=np.zeros((P.n_poses, 4)), pose_t=np.zeros((P.n_poses, 3)), points=np.zeros((P.n_points, 3)),
+               edge_chi2=np.zeros(P.n_edges), edge_depth_positive=np.zeros(P.n_edges, np.uint8))
+    S = LbaSolution()
+    for k, v in out.items():
+        setattr(S, k, v.ctypes.data)
+    cap = max(int(P.iterations), 0) * 10 + 1
+    it, rho, acc = np.zeros(cap, np.int32), np.zeros(cap), np.zeros(cap, np.uint8)
+    T = LbaTrace(cap=cap, iteration=it.ctypes.data, rho=rho.ctypes.data, accepted=acc.ctypes.data)
+    rc = lib().gfso_lba_solve_scripted(C.byref(P), C.byref(S), int(stop_at_look), int(close_at_trial), C.byref(T))
+    n = T.n_trials
+    trace = dict(iteration=it[:n].copy(), rho=rho[:n].copy(), accepted=acc[:n].copy(), looks=T.looks)
+    if rc == 1:
+        return None, trace
+    out.update(iterations_run=S.iterations_run, final_chi2=S.final_chi2, final_lambda=S.final_lambda)
+    return out, trace
 
 
 def lba_linearize(prob):

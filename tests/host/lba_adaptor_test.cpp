@@ -10,6 +10,7 @@
 #include <memory>
 
 #include "../../geoflowslam_amd/host/gfs_adaptors.hpp"
+#include "../../include/gfs_abi_test.h"
 
 namespace {
 struct MockMap;
@@ -129,7 +130,14 @@ extern "C" int lba_adaptor_test(const char* solver_lib, int n_poses, int n_point
       mps[edge_point[e]].obs[&k] = std::make_tuple(kp, init_kf_pose == -2 && e == 0 ? 0 : -1);
       if (init_kf_pose == -2 && e == 0) k.mpCamera2 = &k;
     }
-    bool stop = stop_flag == 1;  // 1: raised before the call; >= 2: raised by another thread that many microseconds into the solve
+    // 1: raised before the call; 2 .. kScripted - 1: raised by another thread that many microseconds into the solve; kScripted + look:
+    // never raised in memory, the library's scripted flag reads as raised from the solve's look-th evaluation on
+    // (gfs_test_lba_stop_at_look, include/gfs_abi_test.h)
+    constexpr int kScripted = 1 << 30;
+    const int script_look = stop_flag >= kScripted ? stop_flag - kScripted : -1;
+    const std::thread::id caller = std::this_thread::get_id();
+    int script_looks = -1;
+    bool stop = stop_flag == 1;
     int solver_iterations = -1;
     int num_fixedKF = -1, num_OptKF = -1, num_MPs = -7, num_edges = -1;
     gfs_lba_problem seen{};
@@ -162,7 +170,10 @@ extern "C" int lba_adaptor_test(const char* solver_lib, int n_poses, int n_point
           [&](const gfs_lba_problem& p, gfs_lba_solution& s, const bool* st) {
             record(p);
             std::thread raiser;
-            if (stop_flag >= 2)
+            if (script_look >= 0) {  // the script belongs to the thread that solves: the adaptor must solve on its caller's
+              if (std::this_thread::get_id() != caller) throw std::runtime_error("the adaptor solves on another thread than its caller's");
+              gfs_test_lba_stop_at_look(script_look);
+            } else if (stop_flag >= 2)
               raiser = std::thread([&] {
                 std::this_thread::sleep_for(std::chrono::microseconds(stop_flag));
                 stop = true;  // the tracking thread's mbAbortBA = true, while the adjustment runs
@@ -170,6 +181,11 @@ extern "C" int lba_adaptor_test(const char* solver_lib, int n_poses, int n_point
             const bool ok = lba.solve(p, s, st);
             if (raiser.joinable()) raiser.join();
             solver_iterations = s.iterations_run;
+            if (script_look >= 0) {
+              int32_t looks = -1;
+              gfs_test_lba_last_looks(&looks, nullptr, nullptr, nullptr);
+              script_looks = looks;
+            }
             return ok;
           },
           &kfs[pkf], stop_flag >= 0 ? &stop : nullptr, &map, num_fixedKF, num_OptKF, num_MPs, num_edges);
@@ -202,6 +218,7 @@ extern "C" int lba_adaptor_test(const char* solver_lib, int n_poses, int n_point
     hubers[0] = seen.huber_mono;
     hubers[1] = seen.huber_stereo;
     if (stop_flag >= 2) hubers[1] = (double)solver_iterations;  // (the raised-while-running test reads the iteration count here)
+    if (script_look >= 0) hubers[0] = (double)script_looks;     // (... and the looks the scripted solve made here)
     for (int e = 0; e < seen.n_edges; e++) {
       flat_inv_sigma2[e] = seen_is2[e];
       for (int c = 0; c < 3; c++) flat_obs[3 * e + c] = seen_obs[3 * e + c];

@@ -231,8 +231,19 @@ double lblr_linearize(const gfso_lba_problem* p, const gfs_lba_lidar* L, const f
 
 // optimizer.optimize(10) (gfso_lba_solve's loop, core/optimization_algorithm_levenberg.cpp:61-168) with the lidar edges in every chi2,
 // every trial and the initial lambda; returns the number of lidar edges.
-int lblr_solve(const gfso_lba_problem* p, const gfs_lba_lidar* L, const float* map, int n_map, gfso_lba_solution* s, int32_t* pose_edges,
-               int32_t* e_idx, float* e_plane, float* e_s) {
+//
+// stop_at_look >= 0: gfso_lba_solve_scripted's scripted stop flag (oracle/lba_oracle.cpp) -- raised from its stop_at_look-th
+// evaluation on; look 0 is the entry check (src/Optimizer.cc:1502-1503: returns -1, writes nothing), look 1 and every later top of an
+// iteration is optimize()'s loop condition, one more follows every rejected trial that would be retried.  *looks = evaluations made.
+int lblr_solve_scripted(const gfso_lba_problem* p, const gfs_lba_lidar* L, const float* map, int n_map, gfso_lba_solution* s,
+                        int32_t* pose_edges, int32_t* e_idx, float* e_plane, float* e_s, int stop_at_look, int32_t* looks_out) {
+  int looks = 0;
+  auto stopped = [&]() {
+    const int k = looks++;
+    return stop_at_look >= 0 && k >= stop_at_look;
+  };
+  if (looks_out) *looks_out = 1;
+  if (stopped()) return -1;
   lbo::Problem S;
   lbo::init_problem(S, p);
   std::vector<LidarKF> LK = generate(p, L, map, n_map);
@@ -242,7 +253,7 @@ int lblr_solve(const gfso_lba_problem* p, const gfs_lba_lidar* L, const float* m
   double currentLambda = -1, ni = 2;
   int nBad = 0, iters = 0;
   double lastChi = 0;
-  for (int iteration = 0; iteration < p->iterations; iteration++) {
+  for (int iteration = 0; iteration < p->iterations && !stopped(); iteration++) {
     lbo::compute_active_errors(S);
     lidar_errors(S, LK);
     double currentChi = active_robust_chi2(S, LK);
@@ -261,6 +272,7 @@ int lblr_solve(const gfso_lba_problem* p, const gfs_lba_lidar* L, const float* m
     }
     double rho = 0;
     int qmax = 0;
+    bool flag_up = false;
     do {
       const std::vector<Pose> poses_backup = S.poses;
       const std::vector<double> points_backup = S.points;
@@ -297,9 +309,10 @@ int lblr_solve(const gfso_lba_problem* p, const gfs_lba_lidar* L, const float* m
         S.points = points_backup;
       }
       qmax++;
-    } while (rho < 0 && qmax < maxTrialsAfterFailure);
+    } while (rho < 0 && qmax < maxTrialsAfterFailure && !(flag_up = stopped()));
     iters++;
     lastChi = currentChi;
+    if (flag_up) break;  // (solve() returns OK; optimize()'s loop condition then finds the flag up: not counted)
     if (qmax == maxTrialsAfterFailure || rho == 0) break;
     if ((iniChi - currentChi) * 1e3 < iniChi)
       nBad++;
@@ -307,6 +320,7 @@ int lblr_solve(const gfso_lba_problem* p, const gfs_lba_lidar* L, const float* m
       nBad = 0;
     if (nBad >= 3) break;
   }
+  if (looks_out) *looks_out = looks;
   if (p->iterations <= 0) lbo::compute_active_errors(S);
   for (int i = 0; i < p->n_poses; i++) {
     std::memcpy(s->pose_q + 4 * i, S.poses[i].q, 32);
@@ -325,6 +339,11 @@ int lblr_solve(const gfso_lba_problem* p, const gfs_lba_lidar* L, const float* m
   s->final_chi2 = lastChi;
   s->final_lambda = currentLambda;
   return report_edges(p, LK, pose_edges, e_idx, e_plane, e_s, nullptr);
+}
+
+int lblr_solve(const gfso_lba_problem* p, const gfs_lba_lidar* L, const float* map, int n_map, gfso_lba_solution* s, int32_t* pose_edges,
+               int32_t* e_idx, float* e_plane, float* e_s) {
+  return lblr_solve_scripted(p, L, map, n_map, s, pose_edges, e_idx, e_plane, e_s, -1, nullptr);
 }
 
 // the literals the restatement compiles in: max inliers, information, Huber delta, min cloud, edge order (1 = lidar edges first)

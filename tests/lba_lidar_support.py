@@ -33,6 +33,8 @@ def restatement():
         L.lblr_linearize.restype = C.c_double
         L.lblr_solve.argtypes = [C.POINTER(O.LbaProblem), vp, vp, C.c_int, C.POINTER(O.LbaSolution), vp, vp, vp, vp]
         L.lblr_solve.restype = C.c_int
+        L.lblr_solve_scripted.argtypes = L.lblr_solve.argtypes + [C.c_int, C.POINTER(C.c_int32)]
+        L.lblr_solve_scripted.restype = C.c_int
         L.lblr_constants.argtypes = [vp]
         _L = L
     return _L
@@ -59,8 +61,10 @@ def _bufs(prob):
     return (np.zeros(max(int(prob["n_poses"]), 1), np.int32), np.zeros(n, np.int32), np.zeros((n, 4), np.float32), np.zeros(n, np.float32))
 
 
-def solve(prob, lidar=True):
-    """The restatement's optimize(10) -> (LocalBundleAdjustment's dict + pose_lidar_edges, edges {pose: (index, plane, s)})."""
+def solve(prob, lidar=True, stop_at_look=-1):
+    """The restatement's optimize(10) -> (LocalBundleAdjustment's dict + pose_lidar_edges, edges {pose: (index, plane, s)}).
+    stop_at_look >= 0: with the stop flag raised from its stop_at_look-th evaluation on (oracle.lba_solve_scripted's script); the dict
+    then has `looks`, and is None when the entry check stopped the call."""
     L = restatement()
     P, keep = O._lba_struct(O.LbaProblem, prob)
     Lr, lkeep = _lidar(prob) if lidar else (None, None)
@@ -71,8 +75,12 @@ def solve(prob, lidar=True):
     for k, v in out.items():
         setattr(S, k, v.ctypes.data)
     pe, idx, pl, s = _bufs(prob)
-    L.lblr_solve(C.byref(P), C.byref(Lr) if Lr is not None else None, mp.ctypes.data, len(mp), C.byref(S), pe.ctypes.data,
-                 idx.ctypes.data, pl.ctypes.data, s.ctypes.data)
+    looks = C.c_int32()
+    rc = L.lblr_solve_scripted(C.byref(P), C.byref(Lr) if Lr is not None else None, mp.ctypes.data, len(mp), C.byref(S), pe.ctypes.data,
+                               idx.ctypes.data, pl.ctypes.data, s.ctypes.data, int(stop_at_look), C.byref(looks))
+    if rc < 0:
+        return None, {}
+    out["looks"] = looks.value
     out.update(iterations_run=S.iterations_run, final_chi2=S.final_chi2, final_lambda=S.final_lambda, pose_lidar_edges=pe[:P.n_poses].copy())
     return out, _edges(prob, pe, idx, pl, s)
 

@@ -104,44 +104,36 @@ def test_stop_flag_raised_while_solving(gpu_api, oracle):
 def test_stopped_solve_is_exactly_the_state_after_its_last_iteration(gpu_api):
     """gfs_lba_solve's host loop runs one LM iteration ahead of the flags it has read (round 6).  When the caller's stop flag goes up while
     an iteration is running ahead, that iteration is discarded: the result must be, bit for bit, what optimize(k) leaves for the k
-    iterations the stopped call reports -- estimates, per-edge chi2, final chi2, lambda.  The flag is raised at a sweep of delays so that
-    it lands in different iterations (and some calls see it only after they are done)."""
-    import threading
-    import time
+    iterations the stopped call reports -- estimates, per-edge chi2, final chi2, lambda.  The flag is scripted
+    (gfs_test_lba_stop_at_look) to go up at every look of the solve in turn: the top of every iteration, and past the last one.
+    (This window accepts every trial; tests/test_gpu_lba_stop.py does the same on windows that reject.)"""
     w = synth.lba_window(0, n_free=20, n_fixed=5, n_points=3000)
     opt = gpu_api.Optimizer()
     full = opt.LocalBundleAdjustment(w)
-    by_iterations = {}
+    r = opt.LocalBundleAdjustment(w, stop_flag=np.zeros(1, np.int32))
+    n_looks = gpu_api.lba_last_looks()["looks"]
+    assert n_looks == 1 + full["iterations_run"] and np.array_equal(r["points"], full["points"])
     seen = set()
-    for delay_us in (400, 600, 800, 1000, 1200, 1400, 1600, 1800, 2000, 2300, 700, 1100, 1500, 1900):
-        flag = np.zeros(1, np.int32)
-
-        def raiser():
-            time.sleep(delay_us * 1e-6)
-            flag[0] = 1
-
-        t = threading.Thread(target=raiser)
-        t.start()
-        r = opt.LocalBundleAdjustment(w, stop_flag=flag)
-        t.join()
+    for look in range(1, n_looks + 1):
+        gpu_api.lba_stop_at_look(look)
+        r = opt.LocalBundleAdjustment(w, stop_flag=np.zeros(1, np.int32))
+        L = gpu_api.lba_last_looks()
         assert r is not None
         k = r["iterations_run"]
+        assert k == look - 1, (look, k)   # look 1 + k is the top of iteration k; look n_looks is never made
         seen.add(k)
-        if k not in by_iterations:
-            wk = dict(w)
-            wk["iterations"] = k
-            by_iterations[k] = opt.LocalBundleAdjustment(wk)  # no flag: the loop runs ahead, nothing is discarded
-        ref = by_iterations[k]
-        if k == full["iterations_run"] and ref["iterations_run"] != k:
-            continue  # (the full run ended by its own termination rule before `iterations`)
+        # every stop with 0 < k < the full count goes through the discard: the next iteration is always running ahead when the flags are read
+        assert L["discarded"] == (1 if 0 < k < full["iterations_run"] else 0), (look, L)
+        wk = dict(w)
+        wk["iterations"] = k
+        ref = opt.LocalBundleAdjustment(wk)  # no flag: the loop runs ahead, nothing is discarded
         if k == 0:  # the flag was up before the first iteration: nothing was evaluated (g2o computes no errors either), the estimates stand
-            assert np.array_equal(r["points"], ref["points"]) and np.array_equal(r["pose_t"], ref["pose_t"]), delay_us
+            assert np.array_equal(r["points"], ref["points"]) and np.array_equal(r["pose_t"], ref["pose_t"]), look
             continue
         for key in ("points", "pose_t", "pose_q", "edge_chi2"):
-            assert np.array_equal(r[key], ref[key]), (delay_us, k, key)
-        assert r["final_chi2"] == ref["final_chi2"] and r["final_lambda"] == ref["final_lambda"] and r["iterations_run"] == ref["iterations_run"], (delay_us, k)
-    # (every stop with 0 < k < the full count went through the discard: the next iteration is always running ahead when the flags are read)
-    assert any(0 < k < full["iterations_run"] for k in seen), seen
+            assert np.array_equal(r[key], ref[key]), (look, k, key)
+        assert r["final_chi2"] == ref["final_chi2"] and r["final_lambda"] == ref["final_lambda"] and r["iterations_run"] == ref["iterations_run"], (look, k)
+    assert seen == set(range(full["iterations_run"] + 1)), seen
 
 
 def test_stop_flag_raised_while_a_batch_is_solving(gpu_api, oracle):

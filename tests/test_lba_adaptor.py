@@ -200,12 +200,26 @@ def test_adaptor_end_to_end_on_gpu(harness, gpu_api, oracle):
 
 @pytest.mark.gpu
 def test_adaptor_stop_flag_raised_while_the_adjustment_runs(harness, gpu_api, oracle):
-    """mbAbortBA raised by another thread DURING LocalBundleAdjustment: the solver reads the caller's bool live (top of every
-    iteration and after every trial step, g2o's setForceStopFlag, src/Optimizer.cc:1679), stops early, and -- like the reference, which
-    checks the flag only before optimize() (:1955-1956) -- the state reached so far is classified and written back."""
+    """mbAbortBA raised DURING LocalBundleAdjustment: the solver reads the caller's bool live (top of every iteration and after every
+    trial step, g2o's setForceStopFlag, src/Optimizer.cc:1679), stops early, and -- like the reference, which checks the flag only
+    before optimize() (:1955-1956) -- the state reached so far is classified and written back.  The flag goes up at a scripted look
+    (gfs_test_lba_stop_at_look, armed by the harness on the thread that solves) instead of after a sleep: the early solve must have run
+    exactly the iterations the oracle runs under the same script."""
     w = _window32(11, n_free=20, n_fixed=5, n_points=3000)
-    full = _run(harness, w, None, stop_flag=10_000_000)   # raised far too late: the complete optimisation
+    full = _run(harness, w, None, stop_flag=(1 << 30) + 1000)   # scripted past the last look: the complete optimisation
     assert full["rc"] > 0 and full["hubers"][1] >= 3
-    early = _run(harness, w, None, stop_flag=150)          # raised 150 us in: a window of this size needs ~2 ms
-    assert early["rc"] > 0 and early["counts"][3] == 1     # written back all the same
-    assert 0 <= early["hubers"][1] < full["hubers"][1], (early["hubers"][1], full["hubers"][1])
+    w2 = dict(w, huber_mono=float(np.float32(np.sqrt(5.991))), huber_stereo=float(np.float32(np.sqrt(7.815))))
+    wl, _ = _local_only(w2)
+    ro, tr = oracle.lba_solve_scripted(wl)
+    assert full["hubers"][1] == ro["iterations_run"] and full["hubers"][0] == tr["looks"]
+    for look in (2, 4):
+        ro, tr = oracle.lba_solve_scripted(wl, stop_at_look=look)
+        early = _run(harness, w, None, stop_flag=(1 << 30) + look)
+        assert early["rc"] > 0 and early["counts"][3] == 1     # written back all the same
+        assert early["hubers"][0] == look + 1 == tr["looks"]   # the script was armed on the thread that solved
+        assert early["hubers"][1] == ro["iterations_run"] == look - 1, (look, early["hubers"][1], ro["iterations_run"])
+        assert 0 <= early["hubers"][1] < full["hubers"][1], (early["hubers"][1], full["hubers"][1])
+        # the written-back state is that early state (poses through float, as _check compares them)
+        free = np.array(w["pose_fixed"]) == 0
+        assert np.abs(early["pose_t"] - ro["pose_t"])[free].max() < 1e-6
+        assert np.abs(early["pose_t"] - full["pose_t"])[free].max() > 0
