@@ -747,7 +747,8 @@ class RegistrationGICP:
         return [_result_dict(r) for r in out]
 
     def tile_stats(self, reset=True):
-        """Workgroups of the linearisation kernel by outcome of the LDS tile staging (index 0 = staged), see gfs_gicp_tile_stats."""
+        """The handle's diagnostics counter block (eight words; written by the -DGFS_KNN_UTIL / -DGFS_LIN_UTIL variant builds only: lanes at
+        work, steps, queries, waves of the neighbour searches, slot by slot in gfs_gicp_tile_stats' comment)."""
         out = np.zeros(8, np.uint64)
         _check(lib().gfs_gicp_tile_stats(self.h, _p(out), int(reset)), "gfs_gicp_tile_stats")
         return out

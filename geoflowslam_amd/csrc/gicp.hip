@@ -71,8 +71,11 @@ struct PairState {
 struct GicpParams {
   double inv_leaf, cell, inv_cell, max_dist_sq, rot_eps, trans_eps;
   int max_iterations, k_neighbors;
-  unsigned* tile_stats;  // optional [8]: workgroups of k_gicp_linearize by outcome of the tile staging (0 = tiled), diagnostics
-  int lin_tile;  // k_gicp_linearize stages its target tile in LDS (GFS_GICP_LIN_TILE=0 switches it off)
+  // optional [8]: the diagnostics counter block (GFS_GICP_TILE_STATS=1, read by gfs_gicp_tile_stats).  Written by the variant builds
+  // only: -DGFS_KNN_UTIL (k_knn_cov: lanes at work / steps of its two scans in slots 0 .. 3, queries / waves in 4, 5, own-row candidates
+  // in 6) and -DGFS_LIN_UTIL (the linearisation's search: lanes / rounds of neighbouring rows in 2, 3, lanes / steps of the walk in 4,
+  // 5, searches / waves in 6, 7)
+  unsigned* tile_stats;
   int nn_rings;  // ceil(max_corr / cell): rings of cells a 1-NN probe may need to certify "nothing within max_corr"
   // Cloud slots of pair b are 2b and 2b + 1.  src_slot: which of the two holds the SOURCE cloud (1 in the plain entry points;
   // the streaming entry alternates so that the previous call's preprocessed source becomes this call's target in place).
@@ -380,7 +383,7 @@ __global__ __launch_bounds__(1024) void k_cell_sort_lds(u64* __restrict__ keys0,
   if (bx + by + bz > 32 || n > kCsE * 1024) {  // uniform: left to k_radix_sort (the caller launches it when the count says so)
     // The kernels queued behind this one (cell build, grid fill, k-NN, the first LM rounds) run before the host sees *n_left: they
     // must not walk an UNSORTED key array with stale bit widths.  The cloud is emptied for them (an empty cloud is a regular input);
-    // the caller's rerun (gicp_run, sort_all_kernels) rebuilds everything from the input points, this count included.
+    // the caller's rerun (gicp_run, kAgainAllSorts) rebuilds everything from the input points, this count included.
     if (tid == 0) {
       atomicAdd(n_left, 1);
       which[c] = 0;
@@ -1515,23 +1518,23 @@ __global__ __launch_bounds__(128) void k_knn_cov(const double4* __restrict__ pts
   knn_write_cov(res, kk, p, cov6 + ((size_t)c * P + i) * 6);
 }
 
-// k_knn_cov_far<LANES, R0, DEFER>: the queries whose k-th neighbour is farther than one cell (sparse regions, a few %
-// of the points).  A group of LANES lanes per deferred query, 256 / LANES queries per workgroup and round.  Search,
+// k_knn_cov_far: the queries whose k-th neighbour is farther than one cell (sparse regions, a few %
+// of the points).  A group of kFarLanes = 16 lanes per deferred query, 16 queries per workgroup and round.  Search,
 // group-wide: the cells (small probes) or rows (big probes) of the ring-r cube are spread over the group's lanes (a
 // lone thread would walk them as one long dependent chain; a whole wave per query leaves the chip latency-bound on the
 // per-query fixed costs), every lane keeps the top-k of its share, and the k global winners are extracted by k
-// group-wide arg-min rounds over the lanes' list heads (ties: lower point index).  The probe grows until the k-th
-// distance is certified (<= r cells) or it covers the whole cloud.  The covariance / eigen step (scalar per query)
+// group-wide arg-min rounds over the lanes' list heads (ties: lower point index).  The covariance / eigen step (scalar per query)
 // then runs for the workgroup's queries side by side.
-// Two passes: <16, 2, true> takes k_knn_cov's list (front of hard_list, counter ginfo[7]) with one r = 2 probe and
-// defers the really isolated points (~1 % of the list, but thousands of candidates each) to <64, 4, false>
-// (back of hard_list, counter far2_count) so that they do not hold up the other queries of their workgroup.
+// It takes k_knn_cov's list (front of hard_list, counter ginfo[7]) with ONE r = 2 probe; a query that the probe does not certify
+// (k-th distance <= r cells, or the probe covers the whole cloud), or whose bound asks for more than two rings -- the really isolated
+// points, ~1 % of the list, but thousands of candidates each -- is deferred to k_knn_cov_far_wg (back of hard_list, counter
+// far2_count) so that it does not hold up the other queries of its workgroup.
 // hard_list / hard_d hold 2 P slots a cloud, the first list in the lower half, the second from the top of the upper half down: in a
 // sparse cloud EVERY point is on both lists (one buffer of P slots let the second list overwrite unread entries of the first as
 // soon as the two held more than P queries together: wrong neighbours for those, tests/test_gpu_gicp_geometry.py).
 // (three waves a SIMD: left alone the kernel takes 205 VGPRs = two waves, and it waits on dependent cell lookups — 1.24 -> 0.99 ms
 // per 1 024 clouds with the cap, a 124-byte spill included; four waves: no further gain)
-template <int LANES, int R0, bool DEFER>
+constexpr int kFarLanes = 16;
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))) void k_knn_cov_far(const double4* __restrict__ pts, const u64* __restrict__ ucell,
                                                      const unsigned* __restrict__ ubegin, const int* __restrict__ n_ucell,
                                                      const int* __restrict__ m_counts, const int* __restrict__ bbox,
@@ -1539,7 +1542,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))) voi
                                                      unsigned* __restrict__ hard_list, double* __restrict__ hard_d,
                                                      int* __restrict__ far2_count, int nchunks, int npairs, int P, GicpParams prm,
                                                      double* __restrict__ cov6) {
-  constexpr int kQueries = 256 / LANES;
+  constexpr int kQueries = 256 / kFarLanes;
   __shared__ int s_ids[kQueries][10];
   __shared__ int s_found[kQueries];
   __shared__ int s_query[kQueries];
@@ -1556,19 +1559,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))) voi
   unsigned* list = hard_list + (size_t)c * 2 * P;
   double* list_d = hard_d + (size_t)c * 2 * P;
   const int nu = n_ucell[c];
-  const int nhard = DEFER ? gi[7] : far2_count[c];
+  const int nhard = gi[7];
   const int kk = min(prm.k_neighbors, 10);
   const int want = min(kk, m);
   const int bx0 = bbox[6 * c], by0 = bbox[6 * c + 1], bz0 = bbox[6 * c + 2], bx1 = bbox[6 * c + 3], by1 = bbox[6 * c + 4],
             bz1 = bbox[6 * c + 5];
-  const int gl = threadIdx.x % LANES, grp = threadIdx.x / LANES;
+  const int gl = threadIdx.x % kFarLanes, grp = threadIdx.x / kFarLanes;
   for (int base = chunk * kQueries; base < nhard; base += nchunks * kQueries) {  // uniform per workgroup
     const int h = base + grp;
     if (gl == 0) s_query[grp] = -1;
     if (h < nhard) {
-      const int i = (int)(DEFER ? list[h] : list[2 * P - 1 - h]);
+      const int i = (int)list[h];
       // squared distance within which the k nearest are known to lie (k_knn_cov found k candidates), or "infinite"
-      const double Dk = DEFER ? list_d[h] : list_d[2 * P - 1 - h];
+      const double Dk = list_d[h];
       const bool bounded = Dk < 1.0e300;
       const double4 q = p[i];
       const int cx = fast_floor_d(q.x * prm.inv_cell) + kCoordOffset, cy = fast_floor_d(q.y * prm.inv_cell) + kCoordOffset,
@@ -1584,8 +1587,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))) voi
       bool done = false;
       double Dnext = Dk;  // bound handed to the next pass
       // bounded: one probe of ceil(sqrt(Dk) / cell) rings is final, and cells (rows) farther than sqrt(Dk) are skipped
-      int r = bounded ? max((int)ceil(sqrt(Dk) * prm.inv_cell), 2) : R0;
-      if (DEFER && r > 2) r = -1;  // beyond this pass: hand over at once
+      int r = bounded ? max((int)ceil(sqrt(Dk) * prm.inv_cell), 2) : 2;
+      if (r > 2) r = -1;  // beyond this pass: hand over at once
+      // (r is 2 or -1 here and the body always ends in `break`: the loop and the row-unit arms of larger r keep the form they had
+      // with R0 as a template parameter, so that the generated code stays the earlier <16, 2, true> instance's)
       for (; r > 0;) {
         TopK<10> loc;
         loc.init();
@@ -1595,11 +1600,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))) voi
         const int nx = x1 - x0 + 1, ny = y1 - y0 + 1, nrows = ny * (z1 - z0 + 1);
         const int upr = nx * nrows <= 128 ? nx : 1;  // work units per row: single cells for the r = 2 probe, whole rows otherwise
         const int nunits = nrows * upr;
-        for (int t = gl; t < nunits; t += 2 * LANES) {  // two units per trip: both lookups are in flight together
-          const int ta = t, tb = min(t + LANES, nunits - 1);
+        for (int t = gl; t < nunits; t += 2 * kFarLanes) {  // two units per trip: both lookups are in flight together
+          const int ta = t, tb = min(t + kFarLanes, nunits - 1);
           const int rowa = ta / upr, xa = ta - rowa * upr, rowb = tb / upr, xb = tb - rowb * upr;
           const int ya = y0 + rowa % ny, za = z0 + rowa / ny, yb = y0 + rowb % ny, zb = z0 + rowb / ny;
-          bool usea = true, useb = t + LANES < nunits;
+          bool usea = true, useb = t + kFarLanes < nunits;
           if (bounded) {
             const double la = axis_lb(ya - cy, uy), lza = axis_lb(za - cz, uz), lxa = upr == 1 ? 0.0 : axis_lb(x0 + xa - cx, ux);
             const double lb = axis_lb(yb - cy, uy), lzb = axis_lb(zb - cz, uz), lxb = upr == 1 ? 0.0 : axis_lb(x0 + xb - cx, ux);
@@ -1620,9 +1625,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))) voi
           double bd = hd;
           int bj = hj;
 #pragma unroll
-          for (int ofs = LANES / 2; ofs > 0; ofs >>= 1) {
-            const double od = __shfl_xor(bd, ofs, LANES);
-            const int oj = __shfl_xor(bj, ofs, LANES);
+          for (int ofs = kFarLanes / 2; ofs > 0; ofs >>= 1) {
+            const double od = __shfl_xor(bd, ofs, kFarLanes);
+            const int oj = __shfl_xor(bj, ofs, kFarLanes);
             if (od < bd || (od == bd && (unsigned)oj < (unsigned)bj)) {
               bd = od;
               bj = oj;
@@ -1650,10 +1655,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))) voi
           done = true;
           break;
         }
-        if (best.found >= want) Dnext = fmin(Dnext, kth);
-        if (DEFER) break;
-        // k candidates are known: the true k nearest lie within sqrt(kth), so the next probe is the last one
-        r = best.found >= want ? min(2 * r, (int)ceil(sqrt(kth) * prm.inv_cell)) : 2 * r;
+        if (best.found >= want) Dnext = fmin(Dnext, kth);  // (k candidates are known: the true k nearest lie within sqrt(kth))
+        break;  // one probe: what it did not settle goes to k_knn_cov_far_wg
       }
       if (gl == 0) {
         if (done) {
@@ -1688,8 +1691,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))) voi
 // already (Dk: k_knn_cov / the r = 2 pass found k points within sqrt(Dk)) needs ONE probe of ceil(sqrt(Dk) / cell) rings and
 // only candidates with d <= Dk can belong to the result, so the sorted insertion runs for those alone.  Per thread a top-k in
 // visiting order = ascending point index (rows are walked in (z, y) order, points are sorted by (z, y, x)); the k winners come
-// out of wave arg-min rounds and a 4-list merge, ties to the lower point index: the same set the lane-group version
-// (k_knn_cov_far<64, 4, false>, the previous form of this pass) selects.
+// out of wave arg-min rounds and a 4-list merge, ties to the lower point index.
 // ------------------------------------------------------------------------------------------------
 constexpr int kFarWgRows = 1024;  // rows of one chunk of the probe (begin, prefix) in LDS
 
@@ -1971,18 +1973,13 @@ __device__ __forceinline__ void wave_reduce_store_map(double (&vals)[N], const i
     else dst_block[wave * kRed + at] = tot;
   }
 }
-// A 256-point chunk of a cloud is one workgroup of four waves, or -- the search kernels that need no LDS -- four workgroups of one
-// wave (a CU takes a new workgroup only when all its waves fit: one-wave workgroups fill the slots that finished waves leave).
-// `chunk` comes in as the launch block's index within the pair; returns the lane's point and its wave's slot of the chunk.
-__device__ __forceinline__ int lin_point_of(int& chunk, int* wave_slot) {
-  const int per = kLinBlock / (int)blockDim.x, part = chunk % per;
-  chunk /= per;
-  *wave_slot = part * ((int)blockDim.x >> 6) + ((int)threadIdx.x >> 6);
-  return chunk * kLinBlock + part * (int)blockDim.x + (int)threadIdx.x;
+// A 256-point chunk of a cloud is one workgroup of four waves: the thread's point of chunk `chunk` and its wave's slot of the chunk.
+__device__ __forceinline__ int lin_point_of(int chunk, int* wave_slot) {
+  *wave_slot = (int)threadIdx.x >> 6;
+  return chunk * kLinBlock + (int)threadIdx.x;
 }
 
-// ---- the target cloud as the 1-NN search sees it: cell boundaries of a row, candidate points.  Two sources with the same
-//      interface: the cloud in HBM (dense cell grid G), and a workgroup's TILE of it staged in LDS (LinTile below).
+// ---- the target cloud as the 1-NN search sees it: cell boundaries of a row, candidate points, out of HBM (dense cell grid G)
 struct NnGlobal {
   const double4* tp;
   const int* gi;
@@ -1993,12 +1990,8 @@ struct NnGlobal {
 #ifdef GFS_LIN_UTIL
   unsigned* util;
 #endif
-  // boundaries (global point indices) of cells cx-1, cx, cx+1 of row (y, z); returns the offset that turns a global point index
-  // into this source's index (0 here)
-  __device__ __forceinline__ int cells3(int cx, int y, int z, int* e) const {
-    row_cells3(gi, G, uc, ub, nu, cx, y, z, e);
-    return 0;
-  }
+  // boundaries (point indices) of cells cx-1, cx, cx+1 of row (y, z)
+  __device__ __forceinline__ void cells3(int cx, int y, int z, int* e) const { row_cells3(gi, G, uc, ub, nu, cx, y, z, e); }
   __device__ __forceinline__ void load(int idx, double& x, double& y, double& z) const {
     const double4 q = ld_pt(tp, idx);
     x = q.x;
@@ -2007,64 +2000,11 @@ struct NnGlobal {
   }
 };
 
-// A workgroup's tile of the target cloud.  The 256 source points of a workgroup are consecutive in cell order, so under the
-// current pose they land in a compact set of target cells; the rows of cells (y, z) their 27-cell neighbourhoods touch, each cut
-// to the x range those neighbourhoods need, are copied once with coalesced loads -- coordinates as three arrays of doubles, and
-// the rows' cell boundaries out of the dense grid -- and every lane then walks ITS cells out of LDS instead of gathering 32-byte
-// points through the vector L1 (~2 500 L1 accesses per wave before).  Workgroups whose tile does not fit (a block that straddles
-// distant surfaces) use the cloud in HBM; both sources give the same correspondences.
-#ifndef GFS_TILE_CAP
-#define GFS_TILE_CAP 1664
-#endif
-#ifndef GFS_TILE_CELLS
-#define GFS_TILE_CELLS 1280
-#endif
-constexpr int kTileCap = GFS_TILE_CAP;      // staged points
-constexpr int kTileRows = 192;              // rows of cells in the box of a workgroup
-constexpr int kTileCells = GFS_TILE_CELLS;  // staged cell boundaries
-constexpr int kTileNz = 64;                 // non-empty rows of a tile
-struct LinTile {
-  double x[kTileCap], y[kTileCap], z[kTileCap];
-  unsigned cells[kTileCells];
-  int row_a[kTileRows], row_b[kTileRows];  // x range (min, max) of the lanes centred on the row
-  int row_lo[kTileRows];                   // x of the row's first staged cell boundary (-> index into cells)
-  int row_delta[kTileRows];                // LDS index = global point index + delta
-  int row_coff[kTileRows];                 // offset of the row's boundaries in cells[], -1: nothing staged (empty row)
-  // the non-empty rows in order (for the flat copy): end of their points / boundaries in the tile, and where they come from
-  int nz_pend[kTileNz], nz_cend[kTileNz], nz_delta[kTileNz], nz_cbase[kTileNz], nz_base[kTileNz];
-  int box[4];  // cymin, cymax, czmin, czmax
-  unsigned long long wave_tot[4];
-};
-struct NnTile {
-  const LinTile* t;
-  int y0, z0, ny;  // the box's first row (cymin - 1, czmin - 1) and its row count along y
-#ifdef GFS_LIN_UTIL
-  unsigned* util;
-#endif
-  __device__ __forceinline__ int cells3(int cx, int y, int z, int* e) const {
-    const int r = (y - y0) + ny * (z - z0);
-    const int coff = t->row_coff[r];
-    e[0] = e[1] = e[2] = e[3] = 0;
-    if (coff < 0) return 0;
-    const int k0 = coff + (cx - 1 - t->row_lo[r]);
-#pragma unroll
-    for (int k = 0; k < 4; k++) e[k] = (int)t->cells[k0 + k];
-    return t->row_delta[r];
-  }
-  __device__ __forceinline__ void load(int idx, double& x, double& y, double& z) const {
-    x = t->x[idx];
-    y = t->y[idx];
-    z = t->z[idx];
-  }
-};
-
-// The candidates of one row of cells (y, z): the strip [lo, hi) of points (global indices; index in the source = global + d) is
-// ordered by slices of 1 / kFine of a cell along x (the cell sort key, k_voxel_reduce).  Walk outwards from `start` in both directions, two
-// candidates a side per step; a side stops when everything still ahead of it is farther than the bound: a point ahead has an x of
+// The candidates of one row of cells (y, z): the strip [lo, hi) of points is ordered by slices of 1 / kFine of a cell along x (the
+// cell sort key, k_voxel_reduce).  Walk outwards from `start` in both directions, two candidates a side per step; a side stops when everything still ahead of it is farther than the bound: a point ahead has an x of
 // at least (x of the outermost point seen on that side) - slack, slack = one such slice (+ rounding).  row2 = squared
 // lower bound of the distance in y and z.  Any walk order gives the exact nearest neighbour; the order only breaks exact ties.
-template <class Src>
-__device__ __forceinline__ void nn_sweep(const Src& src, double tx, double ty, double tz, int lo, int hi, int d, int start, double row2,
+__device__ __forceinline__ void nn_sweep(const NnGlobal& src, double tx, double ty, double tz, int lo, int hi, int start, double row2,
                                          double slack, double max_dist_sq, double& B, double& best, int& bj) {
   int r = start, l = start - 1;
   bool ra = r < hi, la = l >= lo;
@@ -2084,7 +2024,7 @@ __device__ __forceinline__ void nn_sweep(const Src& src, double tx, double ty, d
 #pragma unroll
     for (int u = 0; u < 4; u++) {
       double qy, qz;
-      src.load(j[u] + d, qx[u], qy, qz);
+      src.load(j[u], qx[u], qy, qz);
       dd[u] = (qx[u] - tx) * (qx[u] - tx) + (qy - ty) * (qy - ty) + (qz - tz) * (qz - tz);
     }
 #pragma unroll
@@ -2112,8 +2052,7 @@ __device__ __forceinline__ void nn_sweep(const Src& src, double tx, double ty, d
 // linearisation re-evaluated under the new pose (or +inf / -1).  The own row of cells first (one sweep over its three cells from
 // the query's x outwards), then those of the other eight rows that are still within the bound: every lane works through ITS rows,
 // one per round.
-template <class Src>
-__device__ __forceinline__ void nn_search27(const Src& src, const GicpParams& prm, double tx, double ty, double tz, int cx, int cy, int cz,
+__device__ __forceinline__ void nn_search27(const NnGlobal& src, const GicpParams& prm, double tx, double ty, double tz, int cx, int cy, int cz,
                                             double& best, int& bj) {
   double B = fmin(prm.max_dist_sq, best);
   const double ux = tx * prm.inv_cell - (double)(cx - kCoordOffset), uy = ty * prm.inv_cell - (double)(cy - kCoordOffset),
@@ -2124,11 +2063,11 @@ __device__ __forceinline__ void nn_search27(const Src& src, const GicpParams& pr
   const double slack = prm.cell * (1.0 / kFine + 1e-9);
   auto row = [&](int y, int z, double row2) {
     int e[4];
-    const int d = src.cells3(cx, y, z, e);
+    src.cells3(cx, y, z, e);
     if (e[3] > e[0]) {
       const int n1 = e[2] - e[1];  // the walk starts where the query's x would fall among the points of its own cell
       const int start = e[1] + min(max((int)(ux * (double)n1), 0), n1);
-      nn_sweep(src, tx, ty, tz, e[0], e[3], d, start, row2, slack, prm.max_dist_sq, B, best, bj);
+      nn_sweep(src, tx, ty, tz, e[0], e[3], start, row2, slack, prm.max_dist_sq, B, best, bj);
     }
   };
 #ifdef GFS_LIN_UTIL
@@ -2169,162 +2108,6 @@ __device__ __forceinline__ void nn_search27(const Src& src, const GicpParams& pr
   }
 }
 
-// Stages the workgroup's tile (all threads call it; `inrange` = the lane holds a source point whose image has usable cell
-// coordinates cx, cy, cz).  Returns 0 -- for the whole workgroup -- when the tile is complete, else why not: 1 no dense grid, 2 no lane
-// with a usable image, 3 too many rows in the box, 4 too many points, 5 too many cell boundaries.
-// Two dependent round trips to memory: the rows' first / last points out of the grid, then ONE flat copy of all points and
-// boundaries (every thread takes slots t, t + 256, ... of the tile, finds the slot's row by bisection over the non-empty rows and
-// has all its loads in flight before it stores).
-__device__ __forceinline__ int lin_stage_tile(LinTile& T, bool inrange, int cx, int cy, int cz, const double4* __restrict__ tp,
-                                              const int* __restrict__ gi, const unsigned* __restrict__ G) {
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  if (!gi[6]) return 1;  // no dense grid for this cloud (uniform)
-  if (tid < 4) T.box[tid] = (tid & 1) ? INT_MIN : INT_MAX;
-  if (tid < kTileRows) {
-    T.row_a[tid] = INT_MAX;
-    T.row_b[tid] = INT_MIN;
-  }
-  __syncthreads();
-  {
-    int v[4] = {inrange ? cy : INT_MAX, inrange ? -cy : INT_MAX, inrange ? cz : INT_MAX, inrange ? -cz : INT_MAX};
-#pragma unroll
-    for (int ofs = 32; ofs > 0; ofs >>= 1)
-#pragma unroll
-      for (int k = 0; k < 4; k++) v[k] = min(v[k], __shfl_xor(v[k], ofs, 64));
-    if (lane == 0 && v[0] != INT_MAX) {
-      atomicMin(&T.box[0], v[0]);
-      atomicMax(&T.box[1], -v[1]);
-      atomicMin(&T.box[2], v[2]);
-      atomicMax(&T.box[3], -v[3]);
-    }
-  }
-  __syncthreads();
-  const int cymin = T.box[0], cymax = T.box[1], czmin = T.box[2], czmax = T.box[3];
-  if (cymin > cymax) return 2;  // no lane with a usable image
-  const long long nyl = (long long)cymax - cymin + 3, nzl = (long long)czmax - czmin + 3;
-  if (nyl * nzl > kTileRows) return 3;
-  const int ny = (int)nyl, nz = (int)nzl, nrows = ny * nz, y0 = cymin - 1, z0 = czmin - 1;
-  if (inrange) {  // x range of the lanes centred on each row
-    const int r = (cy - y0) + ny * (cz - z0);
-    atomicMin(&T.row_a[r], cx);
-    atomicMax(&T.row_b[r], cx);
-  }
-  __syncthreads();
-  int lo = INT_MAX, hi = INT_MIN, j0 = 0, len = 0, wid = 0;
-  size_t base = 0;
-  if (tid < nrows) {  // a row serves the lanes centred on it and on its eight neighbours
-    const int ry = tid % ny, rz = tid / ny;
-#pragma unroll
-    for (int dz = -1; dz <= 1; dz++)
-#pragma unroll
-      for (int dy = -1; dy <= 1; dy++) {
-        const int yy = ry + dy, zz = rz + dz;
-        if (yy >= 0 && yy < ny && zz >= 0 && zz < nz) {
-          lo = min(lo, T.row_a[yy + ny * zz]);
-          hi = max(hi, T.row_b[yy + ny * zz]);
-        }
-      }
-    if (lo <= hi) {
-      lo -= 1;
-      hi += 1;
-      const int gy = y0 + ry - gi[1], gz = z0 + rz - gi[2];
-      if ((unsigned)gy < (unsigned)gi[4] && (unsigned)gz < (unsigned)gi[5]) {
-        base = ((size_t)gz * gi[4] + gy) * gi[3];
-        j0 = (int)G[base + min(max(lo - gi[0], 0), gi[3])];
-        const int j1 = (int)G[base + min(max(hi + 1 - gi[0], 0), gi[3])];
-        len = max(j1 - j0, 0);
-        wid = len > 0 ? hi - lo + 2 : 0;  // the boundaries of cells lo .. hi + 1
-      }
-    }
-  }
-  // exclusive prefix sums of (points, boundaries, non-empty rows) over the rows: 24 + 24 + 16 bits, wave scan + four wave totals
-  // (a row longer than the tile cannot pass: clamp its length so that the packed sum cannot overflow its field)
-  const unsigned long long pk = (unsigned long long)min(len, kTileCap + 1) | ((unsigned long long)min(wid, kTileCells + 1) << 24) |
-                                ((unsigned long long)(len > 0 ? 1 : 0) << 48);
-  unsigned long long inc = pk;
-#pragma unroll
-  for (int ofs = 1; ofs < 64; ofs <<= 1) {
-    const unsigned long long o = __shfl_up(inc, ofs, 64);
-    if (lane >= ofs) inc += o;
-  }
-  __syncthreads();  // every thread has read its neighbours' row_a / row_b: they are reused below
-  if (lane == 63) T.wave_tot[wave] = inc;
-  __syncthreads();
-  unsigned long long before = 0, total = 0;
-#pragma unroll
-  for (int w = 0; w < 4; w++) {
-    const unsigned long long tw = T.wave_tot[w];
-    if (w < wave) before += tw;
-    total += tw;
-  }
-  const int tot_pts = (int)(total & 0xffffffu), tot_cells = (int)((total >> 24) & 0xffffffu), nnz = (int)(total >> 48);
-  if (tot_pts > kTileCap) return 4;  // uniform
-  if (tot_cells > kTileCells) return 5;
-  if (nnz > kTileNz) return 3;
-  if (tid < nrows) {
-    const unsigned long long exc = before + inc - pk;
-    const int poff = (int)(exc & 0xffffffu), coff = (int)((exc >> 24) & 0xffffffu), k = (int)(exc >> 48);
-    T.row_lo[tid] = lo;
-    T.row_delta[tid] = poff - j0;
-    T.row_coff[tid] = len > 0 ? coff : -1;
-    if (len > 0) {  // the non-empty rows, in order: where their points and boundaries end in the tile, and where they come from
-      T.nz_pend[k] = poff + len;
-      T.nz_cend[k] = coff + wid;
-      T.nz_delta[k] = poff - j0;
-      T.nz_cbase[k] = lo - gi[0] - coff;  // boundary slot s holds G[base + clamp(s + cbase, 0, nx)] (the grid has < 2^21 cells)
-      T.nz_base[k] = (int)base;
-    }
-  }
-  __syncthreads();
-  {
-    constexpr int kU = (kTileCap + kLinBlock - 1) / kLinBlock;
-    double4 q[kU];
-    int slot[kU];
-#pragma unroll
-    for (int u = 0; u < kU; u++) {
-      slot[u] = tid + u * kLinBlock;
-      if (slot[u] < tot_pts) {
-        int a = 0, b = nnz - 1;  // first non-empty row whose end lies beyond the slot
-        while (a < b) {
-          const int mid = (a + b) >> 1;
-          if (T.nz_pend[mid] > slot[u]) b = mid;
-          else a = mid + 1;
-        }
-        q[u] = tp[slot[u] - T.nz_delta[a]];
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < kU; u++)
-      if (slot[u] < tot_pts) {
-        T.x[slot[u]] = q[u].x;
-        T.y[slot[u]] = q[u].y;
-        T.z[slot[u]] = q[u].z;
-      }
-    constexpr int kUc = (kTileCells + kLinBlock - 1) / kLinBlock;
-    unsigned cv[kUc];
-#pragma unroll
-    for (int u = 0; u < kUc; u++) {
-      const int s = tid + u * kLinBlock;
-      if (s < tot_cells) {
-        int a = 0, b = nnz - 1;
-        while (a < b) {
-          const int mid = (a + b) >> 1;
-          if (T.nz_cend[mid] > s) b = mid;
-          else a = mid + 1;
-        }
-        cv[u] = G[T.nz_base[a] + min(max(s + T.nz_cbase[a], 0), gi[3])];
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < kUc; u++) {
-      const int s = tid + u * kLinBlock;
-      if (s < tot_cells) T.cells[s] = cv[u];
-    }
-  }
-  __syncthreads();
-  return 0;
-}
-
 // ---- the factor of one correspondence (factors/gicp_factor.hpp:52-73), round 5.
 // With J = [R skew(p) | -R] = R [S | -I] (S = skew(p), twist order rotation, translation) the quadratic form is
 //   J' M J = [S | -I]' N [S | -I],  N = R' M R,  J' M r = [S | -I]' u,  u = N w,  w = R' r,  r' M r = w' u
@@ -2346,8 +2129,8 @@ __device__ constexpr int kLinMapA[15] = {3, 8, 12, 4, 9, 13, 5, 10, 14, 15, 16, 
 __device__ constexpr int kLinMapB[14] = {0, 1, 2, 6, 7, 11, 21, 22, 23, 24, 25, 26, 27, 28};       // H_rr, b, e, count
 // (a0 b0 + a1 b1 + a2 b2) and c + (...) as chains of explicit fused multiply-adds.  The bar for GICP is 1e-5 on the pose (the sums
 // are re-associated by the reduction tree anyway), so the factor uses FMAs -- written out, NOT left to `fp contract(fast)`: which
-// products the compiler fuses may differ between two instantiations of the same source (k_gicp_linearize, coop_lin_chunk,
-// k_gicp_lm), and the three must give the same bits (round 6: one pair in ~60 differed in the last bit of e).  The search stays
+// products the compiler fuses may differ between two instantiations of the same source (k_gicp_linearize,
+// coop_pass_chunk), and the two must give the same bits (round 6: one pair in ~60 differed in the last bit of e).  The search stays
 // un-contracted so that the correspondences are decided on the same distances as in the oracle.
 __device__ __forceinline__ double fma3(double a0, double b0, double a1, double b1, double a2, double b2) {
   return __builtin_fma(a2, b2, __builtin_fma(a1, b1, a0 * b0));
@@ -2443,22 +2226,10 @@ __device__ __forceinline__ void lin_factor_batch_a(const LinFactor& F, double (&
 #pragma unroll
   for (int k = 0; k < 6; k++) v[9 + k] = F.N[k];
 }
-// the 29-vector of a point (callers that reduce all of it at once)
-__device__ __forceinline__ void lin_factor_accumulate(const LinFactor& F, double (&acc)[kRed]) {
-  double a[15], b[14];
-  lin_factor_batch_a(F, a);
-  lin_factor_batch_b(F, b);
-#pragma unroll
-  for (int k = 0; k < 15; k++) acc[kLinMapA[k]] += a[k];
-#pragma unroll
-  for (int k = 0; k < 14; k++) acc[kLinMapB[k]] += b[k];
-}
-
 // GICPFactor::linearize (factors/gicp_factor.hpp:35-73) of source point i of a pair under the pose T12 (R col-major | t): exact
 // 1-NN in the target cloud (through `src`), rejection beyond max_dist, the Mahalanobis matrix, and this point's terms ADDED to
 // acc (H upper triangle 21, b 6, e, inlier count).  Records the correspondence and the matrix for the error evaluations that follow.
-template <class Src>
-__device__ __forceinline__ void gicp_lin_point(const Src& src, int i, const double4 p, double tx, double ty, double tz, int cx, int cy, int cz,
+__device__ __forceinline__ void gicp_lin_point(const NnGlobal& src, int i, const double4 p, double tx, double ty, double tz, int cx, int cy, int cz,
                                                bool in_range, const double* __restrict__ T12, bool has_prev, int prev_j, const double4 prev_q,
                                                int pair, int cs, int ct, int P,
                                                const double4* __restrict__ pts, const double* __restrict__ cov6,
@@ -2557,19 +2328,11 @@ __device__ __forceinline__ void lin_image(const double4& p, const double* __rest
 #ifdef GFS_LIN_WAVES
 #define GFS_LIN_OCC __attribute__((amdgpu_waves_per_eu(GFS_LIN_WAVES, 8)))
 #else
-// 5 waves a SIMD is what the pass takes by itself (91 - 94 VGPRs); said explicitly because the scalar step it calls in its last
-// workgroup (pair_step_last, not inlined) is otherwise scheduled without an occupancy target, takes 180 and drags the kernel to 2
+// 5 waves a SIMD is what the pass takes by itself (88 - 90 VGPRs, one allocation granule under the 5-wave limit of 96).  Said
+// explicitly, as on k_gicp_lm_coop: the search is a chain of dependent look-ups that is paid in occupancy, and with the target stated a
+// change that costs a few registers is held to 5 waves by the register allocator instead of dropping the pass to 4 unnoticed
 #define GFS_LIN_OCC __attribute__((amdgpu_waves_per_eu(5, 8)))
 #endif
-struct CoopSync {
-  unsigned arrive;  // k_gicp_linearize: workgroups of the pair that have finished this pass (the last one resets it);
-                    // k_gicp_lm_coop: arrivals at the pair's barriers (monotonic within the launch); k_gicp_init zeroes it
-  unsigned gen;     // k_gicp_lm_coop: barriers completed
-};
-// (defined behind the scalar steps below) the pair's fold + scalar step, run by the workgroup of a pass that finishes last
-__device__ void pair_step_last(PairState* S, const double* part, const double* epart, int nblk_pair, int phase, double rot_eps,
-                               double trans_eps, int max_iterations, int pair, int* n_done, int* act_next, int* n_act_next, double* s_part,
-                               double* s_sum);
 
 // GICPFactor::error of a pending trial for source point i: 0.5 r' M r with the frozen correspondence q and matrix M (factors/gicp_factor.hpp:76-86);
 // (tx, ty, tz) = the point under the trial pose as lin_image computes it (the same expression, un-contracted)
@@ -2586,12 +2349,7 @@ __device__ __forceinline__ double gicp_trial_error(const double4 q, double tx, d
 //            the error's residual), so the error costs six more loads;
 //   phase 3: the trial's error only.
 // Per-block partial sums of H (upper), b, e, the inlier count (partial) and of the trial's error (epartial).
-// kFuse (256-thread workgroups): the pair's scalar step (k_gicp_step) is taken by the workgroup of the pair that finishes LAST, inside
-// this launch -- a round of the LM loop is ONE launch.  The partial sums then cross workgroups within the launch: they are stored
-// write-through (st_ag), every wave drains its stores before the workgroup's arrival is counted (one agent-scope atomic a
-// workgroup), and the last arriver folds them with L1-bypassing loads -- no release / acquire fence (round 5 had measured the
-// fence form of this pattern: 2.97 -> 23.8 ms a step).  Nobody waits for anybody: no residency requirement.
-template <bool kTiled, bool kFuse>
+// The pair's scalar step is the next launch (k_gicp_step).
 __global__ __launch_bounds__(kLinBlock) GFS_LIN_OCC void k_gicp_linearize(PairState* __restrict__ st,
                                                               const double4* __restrict__ pts,
                                                               const double* __restrict__ cov6, const u64* __restrict__ ucell,
@@ -2601,14 +2359,7 @@ __global__ __launch_bounds__(kLinBlock) GFS_LIN_OCC void k_gicp_linearize(PairSt
                                                               int nchunks, int npairs, int P, GicpParams prm,
                                                               int* __restrict__ tgt_index, double* __restrict__ maha6, size_t buf_stride,
                                                               double* __restrict__ partial, double* __restrict__ epartial, int nblk,
-                                                              const int* __restrict__ act, const int* __restrict__ n_act,
-                                                              CoopSync* __restrict__ sync, int* __restrict__ n_done,
-                                                              int* __restrict__ act_next, int* __restrict__ n_act_next,
-                                                              int* __restrict__ n_act_clear) {
-  __shared__ typename std::conditional<kTiled, LinTile, int>::type tile;  // the untiled instance keeps its LDS (and its occupancy)
-  if constexpr (kFuse) {
-    if (blockIdx.x == 0 && threadIdx.x == 0) *n_act_clear = 0;  // the counter the NEXT round's last arrivers fill
-  }
+                                                              const int* __restrict__ act, const int* __restrict__ n_act) {
   int pair, sub, chunk;
   if (act) {  // a late round: only the pairs on the list (the grid covers an upper bound of their number)
     const int slot = blockIdx.x / nchunks;
@@ -2620,7 +2371,7 @@ __global__ __launch_bounds__(kLinBlock) GFS_LIN_OCC void k_gicp_linearize(PairSt
   }
   // Everything this workgroup can ask for before it knows anything is asked for first -- the pair's state, the cloud sizes, the
   // grid header, the lane's source point and its previous correspondence -- so that the dependent round trips to memory that
-  // remain are: state -> (tile rows) -> (tile points) -> search in LDS -> target covariance.
+  // remain are: state -> search -> target covariance.
   const int cs = 2 * pair + prm.src_slot, ct = 2 * pair + 1 - prm.src_slot;
   const PairState* Sp = st + pair;
   const int phase = Sp->phase, n_lin = Sp->n_lin, cur = Sp->buf;
@@ -2639,8 +2390,7 @@ __global__ __launch_bounds__(kLinBlock) GFS_LIN_OCC void k_gicp_linearize(PairSt
   const double* maha_cur = maha6 + (size_t)cur * buf_stride * 6;
   const int prev_j = ti_cur[(size_t)pair * P + i];
   const int nblk_pair = (ms + kLinBlock - 1) / kLinBlock;
-  // (kFuse: a pair without source points still takes its scalar steps -- chunk 0's workgroup stays for that)
-  if (phase == 2 || chunk >= (kFuse ? max(nblk_pair, 1) : nblk_pair)) return;
+  if (phase == 2 || chunk >= nblk_pair) return;
   const bool has_prev = n_lin > 0;
   double4 prev_q = make_double4(0, 0, 0, 0);
   if (has_prev && i < ms && prev_j >= 0) prev_q = tp[prev_j];
@@ -2653,64 +2403,31 @@ __global__ __launch_bounds__(kLinBlock) GFS_LIN_OCC void k_gicp_linearize(PairSt
   if (phase != 0) {  // the pending trial's error (the separate k_gicp_error pass of rounds 1 - 5)
     double e[1] = {0.0};
     if (i < ms && prev_j >= 0) e[0] = gicp_trial_error(prev_q, tx, ty, tz, maha_cur + ((size_t)pair * P + i) * 6);
-    wave_reduce_store<1, kFuse>(e, epartial + ((size_t)pair * nblk + chunk) * kLinWaves, wave_slot);
+    wave_reduce_store<1>(e, epartial + ((size_t)pair * nblk + chunk) * kLinWaves, wave_slot);
   }
   if (phase != 3) {
     const int wr = phase == 0 ? cur : cur ^ 1;
     int* ti_wr = tgt_index + (size_t)wr * buf_stride;
     double* maha_wr = maha6 + (size_t)wr * buf_stride * 6;
-    bool tiled = false;
-    if constexpr (kTiled) {
-      const int why = prm.nn_rings <= 1 ? lin_stage_tile(tile, i < ms && in_range, cx, cy, cz, tp, gi, G) : 6;
-      tiled = why == 0;
-      if (prm.tile_stats && threadIdx.x == 0) atomicAdd(prm.tile_stats + why, 1u);
-    }
     if (i < ms) {
-      bool done = false;
-      if constexpr (kTiled) {
-        if (tiled) {
-          const NnTile src{&tile, tile.box[0] - 1, tile.box[2] - 1, tile.box[1] - tile.box[0] + 3};
-          gicp_lin_point(src, i, p, tx, ty, tz, cx, cy, cz, in_range, T12, has_prev, prev_j, prev_q, pair, cs, ct, P, pts, cov6, ucell, ubegin,
-                         n_ucell, G, gi, prm, ti_wr, maha_wr, F);
-          done = true;
-        }
-      }
-      if (!done) {
 #ifdef GFS_LIN_UTIL
-        const NnGlobal src{tp, gi, G, ucell + (size_t)ct * (P + 1), ubegin + (size_t)ct * (P + 1), n_ucell[ct], prm.tile_stats};
+      const NnGlobal src{tp, gi, G, ucell + (size_t)ct * (P + 1), ubegin + (size_t)ct * (P + 1), n_ucell[ct], prm.tile_stats};
 #else
-        const NnGlobal src{tp, gi, G, ucell + (size_t)ct * (P + 1), ubegin + (size_t)ct * (P + 1), n_ucell[ct]};
+      const NnGlobal src{tp, gi, G, ucell + (size_t)ct * (P + 1), ubegin + (size_t)ct * (P + 1), n_ucell[ct]};
 #endif
-        gicp_lin_point(src, i, p, tx, ty, tz, cx, cy, cz, in_range, T12, has_prev, prev_j, prev_q, pair, cs, ct, P, pts, cov6, ucell, ubegin, n_ucell,
-                       G, gi, prm, ti_wr, maha_wr, F);
-      }
+      gicp_lin_point(src, i, p, tx, ty, tz, cx, cy, cz, in_range, T12, has_prev, prev_j, prev_q, pair, cs, ct, P, pts, cov6, ucell, ubegin, n_ucell,
+                     G, gi, prm, ti_wr, maha_wr, F);
     }
     double* dst = partial + ((size_t)pair * nblk + chunk) * kLinWaves * kRed;
     {
       double vb[14];
       lin_factor_batch_b(F, vb);
-      wave_reduce_store_map<14, kFuse>(vb, kLinMapB, dst, wave_slot);
+      wave_reduce_store_map<14>(vb, kLinMapB, dst, wave_slot);
     }
     {
       double va[15];
       lin_factor_batch_a(F, va);
-      wave_reduce_store_map<15, kFuse>(va, kLinMapA, dst, wave_slot);
-    }
-  }
-  if constexpr (kFuse) {
-    __shared__ double s_part[8 * 32], s_sum[32];
-    __shared__ int s_last;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every storing wave: its partial sums have left before the arrival is counted
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      const unsigned old = __hip_atomic_fetch_add(&sync[pair].arrive, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      s_last = old + 1 == (unsigned)max(nblk_pair, 1) ? 1 : 0;
-    }
-    __syncthreads();
-    if (s_last) {
-      pair_step_last(st + pair, partial + (size_t)pair * nblk * kLinWaves * kRed, epartial + (size_t)pair * nblk * kLinWaves, nblk_pair, phase,
-                     prm.rot_eps, prm.trans_eps, prm.max_iterations, pair, n_done, act_next, n_act_next, s_part, s_sum);
-      if (threadIdx.x == 0) st_ag(&sync[pair].arrive, 0u);  // (everybody of this pair has arrived; the next pass is another launch)
+      wave_reduce_store_map<15>(va, kLinMapA, dst, wave_slot);
     }
   }
 }
@@ -2983,31 +2700,14 @@ __global__ __launch_bounds__(256) void k_gicp_step(PairState* __restrict__ st, c
   else act_next[atomicAdd(n_act_next, 1)] = pair;
 }
 
-// the same fold + step for the workgroup of a fused pass (k_gicp_linearize<.., true>) that arrives last: the partial sums come from
-// other workgroups of the running launch (L1-bypassing loads), the state is this pair's alone until the next launch
-__device__ __attribute__((noinline)) void pair_step_last(PairState* S, const double* part, const double* epart, int nblk_pair, int phase,
-                                                         double rot_eps, double trans_eps, int max_iterations, int pair, int* n_done,
-                                                         int* act_next, int* n_act_next, double* s_part, double* s_sum) {
-  fold_round<true>(part, epart, phase != 3, phase != 0, nblk_pair, s_part, s_sum);
-  if (threadIdx.x != 0) return;
-  GicpParams q{};
-  q.rot_eps = rot_eps;
-  q.trans_eps = trans_eps;
-  q.max_iterations = max_iterations;
-  bool done;
-  lm_round_step(*S, s_sum, q, &done);
-  if (done) atomicAdd(n_done, 1);
-  else act_next[atomicAdd(n_act_next, 1)] = pair;
-}
-
 // ------------------------------------------------------------------------------------------------
 // k_gicp_lm_coop: the Levenberg-Marquardt loop of a FEW pairs without the host and without a launch per step -- G workgroups a
 // pair walk the pair's 256-point chunks (workgroup g takes chunks g, g + G, ...), write the SAME per-wave partial sums into the
 // SAME slots as k_gicp_linearize, meet at a per-pair barrier, and the workgroup that arrives last folds them with
 // the SAME fold_round and takes the SAME scalar step (lm_round_step) as k_gicp_step: the results are those of the
 // launch-per-step form bit for bit, whatever G is and whichever workgroup folds.
-//   Used (gicp_run) where four launches + a host poll per step are most of the time: a single pair (one live stream: ~5 steps of
-// 75 workgroups each), and the tail of a batch whose last few pairs iterate on an otherwise idle chip.
+//   Used (gicp_run) where the launches + a host poll per step are most of the time: a batch that fits the workgroup budget whole -- a
+// single pair (one live stream: ~5 steps of 75 workgroups each).  Its pairs are 0 .. n_pairs - 1.
 //   What crosses workgroups -- the partial sums, the pair's state, the barrier words -- moves through 8-byte agent-scope accesses
 // (ld_ag / st_ag: write-through stores, L1-bypassing loads; every storing wave drains before its workgroup's arrival is counted,
 // MI355X guide: inter-workgroup communication).  tgt_index / maha6 of a point are written and re-read by the same thread (a chunk
@@ -3016,6 +2716,18 @@ __device__ __attribute__((noinline)) void pair_step_last(PairState* S, const dou
 // budget.  Spins are bounded: a workgroup that waits too long sets the error word and leaves, gicp_run then repeats the call
 // with launches.
 // ------------------------------------------------------------------------------------------------
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__)
+// The barrier below is relaxed agent-scope atomics plus `s_waitcnt vmcnt(0)`: no release / acquire fence.  That orders the partial
+// sums and the state before the arrival / generation words only because on gfx950 these accesses are write-through stores and
+// L1-bypassing loads (sc1) that are complete once the vector memory counter has drained.  Another target may keep such stores in a
+// cache that the counter does not cover (or count stores separately): there the protocol needs real fences.
+#error "k_gicp_lm_coop's inter-workgroup barrier (relaxed agent-scope atomics + s_waitcnt vmcnt(0)) is only correct on gfx950"
+#endif
+// the barrier words of a pair in k_gicp_lm_coop (k_gicp_init zeroes them)
+struct CoopSync {
+  unsigned arrive;  // arrivals of the pair's workgroups at its barriers (monotonic within the launch)
+  unsigned gen;     // barriers completed
+};
 // a wave-uniform double (read out of LDS) moved to scalar registers: what a scalar load of the launch-per-step kernels' state gives
 __device__ __forceinline__ double uniform_d(double v) {
   const int lo = __builtin_amdgcn_readfirstlane(__double2loint(v)), hi = __builtin_amdgcn_readfirstlane(__double2hiint(v));
@@ -3027,7 +2739,7 @@ constexpr unsigned kCoopSpinLimit = 4u << 20;  // polls of ~1 us: seconds, far b
 
 // What the two per-chunk bodies need, uniform per launch.  It sits in LDS and the bodies are separate (noinline) functions that
 // read it back into scalar registers: inlined into the kernel's loops the linearisation took 200 - 240 VGPRs instead of the 94 it
-// takes in k_gicp_linearize (1 - 2 workgroups a CU: no budget for a tail of several pairs); as a function of its own it keeps its
+// takes in k_gicp_linearize (1 - 2 workgroups a CU: hardly any budget); as a function of its own it keeps its
 // registers, and the kernel around it is small.
 struct CoopCtx {
   const double4* pts;
@@ -3057,7 +2769,7 @@ __device__ __forceinline__ void uniform_load(T& dst, const void* lds_generic) {
   __builtin_memcpy(&dst, tmp, sizeof(T));
 }
 
-// One chunk (256 source points, this workgroup's threads) of a pair's pass under the state in LDS: the untiled body of
+// One chunk (256 source points, this workgroup's threads) of a pair's pass under the state in LDS: the body of
 // k_gicp_linearize -- the pending trial's error and / or the linearisation, by phase -- with the partial sums stored write-through
 __device__ __attribute__((noinline)) void coop_pass_chunk(const void* ctx_lds, const void* state_lds, int pair_v, int chunk_v, int ms_v) {
   CoopCtx C;
@@ -3132,21 +2844,17 @@ __global__ __launch_bounds__(kLinBlock) __attribute__((amdgpu_waves_per_eu(5, 8)
     const unsigned* __restrict__ ubegin, const int* __restrict__ n_ucell, const int* __restrict__ m_counts,
     const unsigned* __restrict__ grid, const int* __restrict__ ginfo, int nchunks, int P, GicpParams prm, int* __restrict__ tgt_index,
     double* __restrict__ maha6, size_t buf_stride, double* __restrict__ partial, double* __restrict__ epartial, int nblk,
-    const int* __restrict__ act, const int* __restrict__ n_act, int n_fixed, CoopSync* __restrict__ sync, int* __restrict__ n_done,
-    int* __restrict__ n_err) {
+    int n_pairs, CoopSync* __restrict__ sync, int* __restrict__ n_done, int* __restrict__ n_err) {
   __shared__ double s_part[8 * 32], s_sum[32];
   __shared__ u64 s_state[64];
   __shared__ CoopCtx s_ctx;
   __shared__ int s_last;
   const int tid = threadIdx.x;
-  // pairs of this launch: the list the previous round's k_gicp_step wrote (act), or pairs 0 .. n_fixed - 1; every workgroup
-  // derives the same G from the same count
-  const int n = act ? *n_act : n_fixed;
-  if (n <= 0) return;
-  const int G = max(1, min(nchunks, (int)gridDim.x / n));
-  const int slot = blockIdx.x / G, g = blockIdx.x - slot * G;
-  if (slot >= n) return;
-  const int pair = act ? act[slot] : slot;
+  // every workgroup derives the same G from the same count
+  if (n_pairs <= 0) return;
+  const int G = max(1, min(nchunks, (int)gridDim.x / n_pairs));
+  const int pair = blockIdx.x / G, g = blockIdx.x - pair * G;
+  if (pair >= n_pairs) return;
   const int ms = m_counts[2 * pair + prm.src_slot];
   const int nblk_pair = (ms + kLinBlock - 1) / kLinBlock;
   const int Gp = max(1, min(G, nblk_pair));  // workgroups that have a chunk (at least one: the scalar steps must run)
@@ -3197,147 +2905,6 @@ __global__ __launch_bounds__(kLinBlock) __attribute__((amdgpu_waves_per_eu(5, 8)
     if (s_last < 0) return;  // (the other workgroups of the pair run into the same limit; gicp_run repeats the call with launches)
     episode++;
   }
-}
-
-// ------------------------------------------------------------------------------------------------
-// k_gicp_lm: LevenbergMarquardtOptimizer::optimize (registration/optimizer.hpp:83-147) of ONE pair per workgroup, start to
-// finish: linearise -> damped solve -> error of the trial -> accept / reject, until converged or out of iterations.  The
-// pairs of a batch converge after different numbers of iterations (3 ... 20): with one launch per step of the state machine
-// (k_gicp_linearize / solve / error / decide, the default) the late rounds run for a handful of pairs on an otherwise idle GPU
-// and every round pays four launches and a host poll; here a finished pair simply frees its compute unit.  Selected with
-// GFS_GICP_LM=persistent; results are identical to rounding (the sums are folded in a different fixed order).
-// 512 threads walk the source points with a stride, every thread adds its points into its own 29 sums, which are then
-// folded in a fixed order (wave halving tree, 8 waves in order): deterministic and independent of the batch.
-// ------------------------------------------------------------------------------------------------
-constexpr int kLmBlock = 512;
-
-__global__ __launch_bounds__(kLmBlock) __attribute__((amdgpu_waves_per_eu(4, 8))) void k_gicp_lm(
-    PairState* __restrict__ st, const double4* __restrict__ pts, const double* __restrict__ cov6, const u64* __restrict__ ucell,
-    const unsigned* __restrict__ ubegin, const int* __restrict__ n_ucell, const int* __restrict__ m_counts,
-    const unsigned* __restrict__ grid, const int* __restrict__ ginfo, int npairs, int P, GicpParams prm, int* __restrict__ tgt_index,
-    double* __restrict__ maha6) {
-  __shared__ PairState S;
-  __shared__ double s_red[(kLmBlock / 64) * 32], s_sum[32];
-  const int pair = blockIdx.x, tid = threadIdx.x;
-  if (pair >= npairs) return;
-  if (tid == 0) S = st[pair];  // initialised by k_gicp_init
-  __syncthreads();
-  const int cs = 2 * pair + prm.src_slot, ct = 2 * pair + 1 - prm.src_slot;
-  const int ms = m_counts[cs];
-  const unsigned* G = grid + (size_t)ct * (kGridCap + 1);
-  const int* gi = ginfo + 8 * ct;
-  while (true) {
-    const int phase = S.phase;  // uniform: read after a barrier
-    if (phase == 2) break;
-    if (phase == 0) {
-      double acc[kRed];
-#pragma unroll
-      for (int k = 0; k < kRed; k++) acc[k] = 0;
-      const bool has_prev = S.n_lin > 0;
-      for (int i = tid; i < ms; i += kLmBlock) {
-#ifdef GFS_LIN_UTIL
-        const NnGlobal src{pts + (size_t)ct * P, gi, G, ucell + (size_t)ct * (P + 1), ubegin + (size_t)ct * (P + 1), n_ucell[ct], nullptr};
-#else
-        const NnGlobal src{pts + (size_t)ct * P, gi, G, ucell + (size_t)ct * (P + 1), ubegin + (size_t)ct * (P + 1), n_ucell[ct]};
-#endif
-        const double4 p = pts[(size_t)cs * P + i];
-        double tx, ty, tz;
-        int cx, cy, cz;
-        bool in_range;
-        lin_image(p, S.T, prm, tx, ty, tz, cx, cy, cz, in_range);
-        const int prev_j = has_prev ? tgt_index[(size_t)pair * P + i] : -1;
-        const double4 prev_q = prev_j >= 0 ? pts[(size_t)ct * P + prev_j] : make_double4(0, 0, 0, 0);
-        LinFactor F;
-        gicp_lin_point(src, i, p, tx, ty, tz, cx, cy, cz, in_range, S.T, has_prev, prev_j, prev_q, pair, cs, ct, P, pts, cov6, ucell, ubegin, n_ucell, G, gi,
-                       prm, tgt_index, maha6, F);
-        lin_factor_accumulate(F, acc);
-      }
-      const double r = gfs_red::block_sum_many<kRed, kLmBlock / 64>(acc, s_red);
-      if (tid < kRed) s_sum[tid] = r;
-      __syncthreads();
-      if (tid == 0) {  // as k_gicp_solve
-        double H[21], b[6], T[12], delta[6], newT[12];
-#pragma unroll
-        for (int k = 0; k < 21; k++) H[k] = s_sum[k];
-#pragma unroll
-        for (int k = 0; k < 6; k++) b[k] = s_sum[21 + k];
-#pragma unroll
-        for (int k = 0; k < 12; k++) T[k] = S.T[k];
-        solve_and_propose(H, b, S.lambda, T, delta, newT);
-#pragma unroll
-        for (int k = 0; k < 21; k++) S.H[k] = H[k];
-#pragma unroll
-        for (int k = 0; k < 6; k++) S.b[k] = b[k];
-#pragma unroll
-        for (int k = 0; k < 6; k++) S.delta[k] = delta[k];
-#pragma unroll
-        for (int k = 0; k < 12; k++) S.newT[k] = newT[k];
-        S.e = s_sum[27];
-        S.inliers = (int)(s_sum[28] + 0.5);
-        S.n_lin++;
-        S.inner = 0;
-        S.phase = 1;
-      }
-      __threadfence_block();  // tgt_index / maha6 of this linearisation are read by other threads below
-      __syncthreads();
-    } else {
-      double e[1] = {0.0};
-      const double* R = S.newT;
-      const double* t = S.newT + 9;
-      for (int i = tid; i < ms; i += kLmBlock) {  // GICPFactor::error with the frozen correspondences (as k_gicp_error)
-        const int ti = tgt_index[(size_t)pair * P + i];
-        if (ti >= 0) {
-          const double4 p = pts[(size_t)cs * P + i];
-          const double tx = R[0] * p.x + R[3] * p.y + R[6] * p.z + t[0];
-          const double ty = R[1] * p.x + R[4] * p.y + R[7] * p.z + t[1];
-          const double tz = R[2] * p.x + R[5] * p.y + R[8] * p.z + t[2];
-          const double4 q = pts[(size_t)ct * P + ti];
-          const double r0 = q.x - tx, r1 = q.y - ty, r2 = q.z - tz;
-          const double* M = maha6 + ((size_t)pair * P + i) * 6;
-          const double m0 = M[0] * r0 + M[1] * r1 + M[2] * r2, m1 = M[1] * r0 + M[3] * r1 + M[4] * r2,
-                       m2 = M[2] * r0 + M[4] * r1 + M[5] * r2;
-          e[0] += 0.5 * (r0 * m0 + r1 * m1 + r2 * m2);
-        }
-      }
-      const double r = gfs_red::block_sum_many<1, kLmBlock / 64>(e, s_red);
-      if (tid == 0) {  // as k_gicp_decide (registration/optimizer.hpp:115-141)
-        const double new_e = r;
-        S.n_err++;
-        if (new_e <= S.e) {
-          const double dr = sqrt(S.delta[0] * S.delta[0] + S.delta[1] * S.delta[1] + S.delta[2] * S.delta[2]);
-          const double dt = sqrt(S.delta[3] * S.delta[3] + S.delta[4] * S.delta[4] + S.delta[5] * S.delta[5]);
-          S.converged = (dr <= prm.rot_eps && dt <= prm.trans_eps) ? 1 : 0;
-          for (int k = 0; k < 12; k++) S.T[k] = S.newT[k];
-          S.lambda /= 10.0;
-          S.iterations = S.outer;
-          S.outer++;
-          S.phase = (S.converged || S.outer >= prm.max_iterations) ? 2 : 0;
-        } else {
-          S.lambda *= 10.0;
-          S.inner++;
-          if (S.inner >= 10) {  // max_inner_iterations: !success -> break
-            S.iterations = S.outer;
-            S.phase = 2;
-          } else {
-            double H[21], b[6], T[12], delta[6], newT[12];
-#pragma unroll
-            for (int k = 0; k < 21; k++) H[k] = S.H[k];
-#pragma unroll
-            for (int k = 0; k < 6; k++) b[k] = S.b[k];
-#pragma unroll
-            for (int k = 0; k < 12; k++) T[k] = S.T[k];
-            solve_and_propose(H, b, S.lambda, T, delta, newT);
-#pragma unroll
-            for (int k = 0; k < 6; k++) S.delta[k] = delta[k];
-#pragma unroll
-            for (int k = 0; k < 12; k++) S.newT[k] = newT[k];
-          }
-        }
-      }
-      __syncthreads();
-    }
-  }
-  if (tid == 0) st[pair] = S;
 }
 
 __global__ void k_gicp_init(PairState* __restrict__ st, const double* __restrict__ init_T, int B, int max_iterations,
@@ -3397,38 +2964,31 @@ struct gfs_gicp {
   gfs::DevBuf<int> d_nleaf, d_nheap;
   gfs::DevBuf<unsigned> d_heap;  // per cloud: (begin, end) of the ranges that hit std::sort's depth limit (heap-sort fallback)
   int heap_cap = 0;
-  // one launch per step of the LM state machine (default).  GFS_GICP_LM=persistent: the whole loop of a pair in one workgroup
-  // (k_gicp_lm) — no launches / host polls inside the loop, but only one workgroup of parallelism per pair: measured 4x slower at
-  // 128 pairs per batch (25 vs 6 ms per 512 pairs), it pays only for batches of many thousand small pairs.
+  // one launch per step of the LM state machine
   gfs::DevBuf<int> d_active, d_nactive;  // [3][B] pairs still iterating (written by k_gicp_step for the next round), [3] their number (round r: r % 3)
-  bool lm_rounds = true;
   // k_gicp_lm_coop (the loop of a few pairs in one launch): GFS_GICP_COOP=0 switches it off; coop_cap = workgroups of it the device
   // holds at once (occupancy query, one fewer per CU than the API says: the hardware may admit fewer); a launch takes its
   // workgroups from a process-wide budget of half of that (CoopBudget) and gives them back when the call has been waited for
+  // (coop_reserved: what this handle holds of the budget, CoopLease)
   bool coop = true, coop_failed = false;
-  bool fuse_step = false;  // GFS_GICP_FUSE_STEP=1 (read at creation): see the round loop of gicp_run
   int coop_cap = 0, coop_reserved = 0, coop_launches = 0, coop_last_wgs = 0;
-  // GFS_GICP_COOP_TAIL = f > 0: the TAIL of a larger batch also goes to the kernel once (pairs left) x (chunks a pair) <= f x budget.
-  // Off by default -- measured (round 6, 64-pair block in 2 lanes): 2.07 ms a step without, 2.09 / 2.11 / 2.17 / 2.29 ms with f = 1 / 2 /
-  // 4 / 8: on a chip that other lanes keep busy a barrier episode (drain, arrival, fold by the last workgroup, publish, poll) costs
-  // what the two launch boundaries it replaces cost, and the resident workgroups are in the other lanes' way.
-  double coop_tail = 0.0;
   gfs::DevBuf<CoopSync> d_sync;
   bool tile_stats_on = false;  // GFS_GICP_TILE_STATS=1
-  gfs::DevBuf<unsigned> d_tile_stats;  // [8] outcome counters of k_gicp_linearize's tile staging (gfs_gicp_tile_stats)
+  gfs::DevBuf<unsigned> d_tile_stats;  // [8] the diagnostics counter block (GicpParams::tile_stats says who writes which slot; gfs_gicp_tile_stats reads it)
   bool vqs_lds = true;  // GFS_GICP_VQS_LDS=0: without k_voxel_qsort_top_lds
-  bool sort_all_kernels = false;  // set for the second run of a call whose first run found a cloud the LDS sort kernel could not take
-  int sort_all_hold = 0;  // ... and the next calls launch every sort kernel at once instead of finding out again (a stream of wide scenes
-                          // would pay every call twice); counted down, then the optimistic launch is tried again
+  // a call whose optimistic launch found a cloud the LDS sort kernels could not take is run again with every sort kernel (gicp_run), and
+  // the next calls launch every sort kernel at once instead of finding out again (a stream of wide scenes would pay every call
+  // twice); counted down a call, then the optimistic launch is tried again
+  int sort_all_hold = 0;
   bool stable_voxel_order = false;  // GFS_GICP_VOXEL_ORDER=stable: the round-1 stable radix order instead of the reference's
   gfs::DevBuf<double4> d_tmp, d_pts;
   gfs::DevBuf<double> d_cov6, d_maha6, d_partial, d_epartial;
   gfs::DevBuf<PairState> d_state;
   gfs::PinBuf<PairState> h_state;
   gfs::PinBuf<int> h_ndone, h_m;
-  static constexpr int kAheadMax = 8;
-  hipEvent_t ev_round[kAheadMax + 1] = {};  // completion of the LM rounds in flight
-  int ahead = 1;  // LM rounds queued beyond the one whose done counter the host waits for (GFS_GICP_AHEAD, measured in round 6: see gicp_run)
+  // ONE LM round is queued beyond the one whose done counter the host waits for (gicp_attempt): two rounds in flight, a slot each
+  static constexpr int kRoundSlots = 2;
+  hipEvent_t ev_round[kRoundSlots] = {};  // completion of the LM rounds in flight
   gfs::PinBuf<double> h_initT;
   const double* hd_initT = nullptr;  // h_initT as the device sees it (k_gicp_init reads the initial poses over the bus)
   PairState* hd_state = nullptr;     // h_state, h_m, the call's last look at the counters (h_ndone's tail) as the device sees them:
@@ -3444,7 +3004,7 @@ struct gfs_gicp {
 
 // Workgroups of k_gicp_lm_coop in flight in this process, per device: the kernel's workgroups wait for each other, so all of them
 // -- of every handle's launch -- must be resident together.  A launch reserves before it is enqueued and releases after its call's
-// final synchronisation; a launch that cannot get enough falls back to the launch-per-step rounds.
+// final synchronisation (CoopLease); a launch that cannot get enough falls back to the launch-per-step rounds.
 struct CoopBudget {
   static std::atomic<int>& in_use(int device) {
     static std::atomic<int> a[64];
@@ -3463,6 +3023,32 @@ struct CoopBudget {
     if (n > 0) in_use(device).fetch_sub(n);
   }
 };
+namespace {
+// What a handle holds of the budget (gfs_gicp::coop_reserved), for the scope of one attempt of a call: given back on every way out
+// of it, after waiting for the stream if the kernel may be running -- its workgroups count against the budget while they are resident.
+struct CoopLease {
+  gfs_gicp* h;
+  hipStream_t s;
+  bool in_flight = false;  // the kernel has been enqueued and the stream not waited for since
+  CoopLease(gfs_gicp* h_, hipStream_t s_) : h(h_), s(s_) {}
+  CoopLease(const CoopLease&) = delete;
+  CoopLease& operator=(const CoopLease&) = delete;
+  int reserve(int want, int least, int total) {
+    const int got = CoopBudget::reserve(h->device, want, least, total);
+    h->coop_reserved += got;
+    return got;
+  }
+  void release() {  // (the caller has waited for the stream, or nothing was enqueued)
+    CoopBudget::release(h->device, h->coop_reserved);
+    h->coop_reserved = 0;
+    in_flight = false;
+  }
+  ~CoopLease() {
+    if (h->coop_reserved > 0 && in_flight) (void)hipStreamSynchronize(s);
+    release();
+  }
+};
+}  // namespace
 
 // The n >= 1024 levels of the voxel sort: the LDS-resident kernel for clouds of at most kVqsLdsE * 1024 points whose keys compact to
 // 31 bits, the register-cached kernel for larger ones of that key width, the general kernel for the rest (each flags what it leaves).
@@ -3566,11 +3152,8 @@ int gfs_gicp_create(int device, int max_points, int max_batch, gfs_gicp** out) {
   GFS_HIP(hipFuncSetAttribute((const void*)vqs::k_voxel_qsort_top_lds<kVqsLdsGvE, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
                               kVqsLdsGvE * 1024 * 4));
   GFS_HIP(hipFuncSetAttribute((const void*)k_cell_sort_lds, hipFuncAttributeMaxDynamicSharedMemorySize, kCsLdsBytes));
-  if (const char* e = getenv("GFS_GICP_LM")) h->lm_rounds = strcmp(e, "persistent") != 0;
   if (const char* e = getenv("GFS_GICP_TILE_STATS")) h->tile_stats_on = atoi(e) != 0;
   if (const char* e = getenv("GFS_GICP_COOP")) h->coop = atoi(e) != 0;
-  if (const char* e = getenv("GFS_GICP_FUSE_STEP")) h->fuse_step = atoi(e) != 0;
-  if (const char* e = getenv("GFS_GICP_COOP_TAIL")) h->coop_tail = atof(e);
   {
     int per_cu = 0, cus = 0;
     hipDeviceProp_t prop;
@@ -3578,7 +3161,6 @@ int gfs_gicp_create(int device, int max_points, int max_batch, gfs_gicp** out) {
         hipGetDeviceProperties(&prop, device) == hipSuccess)
       cus = prop.multiProcessorCount;
     h->coop_cap = std::max(0, std::min(per_cu, 8) - 1) * cus;
-    if (const char* e = getenv("GFS_GICP_COOP_WGS")) h->coop_cap = std::min(h->coop_cap, 2 * std::max(0, atoi(e)));  // (budget = cap / 2)
     (void)hipGetLastError();
   }
   const size_t P = h->P, B = max_batch, C2 = 2 * B;
@@ -3630,10 +3212,9 @@ int gfs_gicp_create(int device, int max_points, int max_batch, gfs_gicp** out) {
   A(h->d_epartial.alloc(B * h->nblk * kLinWaves));
   A(h->d_state.alloc(B));
   A(h->h_state.alloc(B));
-  A(h->h_ndone.alloc(2 * (gfs_gicp::kAheadMax + 1) + 4));  // [2 slot ..] the rounds in flight, the last three: the call's last look
-  for (int k = 0; k <= gfs_gicp::kAheadMax; k++) GFS_HIP(hipEventCreateWithFlags(&h->ev_round[k], hipEventDisableTiming));
-  if (const char* e = getenv("GFS_GICP_AHEAD")) h->ahead = std::max(1, std::min(gfs_gicp::kAheadMax, atoi(e)));
-  GFS_HIP(hipHostGetDevicePointer((void**)&h->hd_last, h->h_ndone.p + 2 * (gfs_gicp::kAheadMax + 1), 0));
+  A(h->h_ndone.alloc(2 * gfs_gicp::kRoundSlots + 4));  // [2 slot ..] the rounds in flight, then the call's last look (three words)
+  for (int k = 0; k < gfs_gicp::kRoundSlots; k++) GFS_HIP(hipEventCreateWithFlags(&h->ev_round[k], hipEventDisableTiming));
+  GFS_HIP(hipHostGetDevicePointer((void**)&h->hd_last, h->h_ndone.p + 2 * gfs_gicp::kRoundSlots, 0));
   A(h->h_m.alloc(C2));
   A(h->h_initT.alloc(B * 16));
   GFS_HIP(hipHostGetDevicePointer((void**)&h->hd_initT, h->h_initT.p, 0));
@@ -3652,31 +3233,31 @@ void gfs_gicp_destroy(gfs_gicp* h) {
   if (!h) return;
   (void)hipSetDevice(h->device);
   (void)hipStreamSynchronize(h->stream);
+  CoopBudget::release(h->device, h->coop_reserved);  // (gicp_run leaves none behind: whatever a handle still held would be lost to the process)
+  h->coop_reserved = 0;
   (void)hipStreamDestroy(h->stream);
-  for (int k = 0; k <= gfs_gicp::kAheadMax; k++)
+  for (int k = 0; k < gfs_gicp::kRoundSlots; k++)
     if (h->ev_round[k]) (void)hipEventDestroy(h->ev_round[k]);
   delete h;
 }
 
+// What an attempt at a call (gicp_attempt) ends with besides a gfs_status (GFS_OK: done, the results are in `out`; < 0: an error):
+// nothing of such an attempt is ever returned, gicp_run makes another one
+constexpr int kAgainAllSorts = 1;  // a cloud needed the sort kernels that the optimistic launch leaves out: again, with every sort kernel
+constexpr int kAgainNoCoop = 2;    // a workgroup of k_gicp_lm_coop gave up waiting: again, with a launch per step
+
+// One attempt at a call (gicp_run has checked the arguments, holds the handle's mutex and has selected the device).
+// optimistic_sort: only the LDS-resident sort kernels are launched and the round loop looks at the count of clouds they left.
 // streaming = false: preprocess both clouds of every pair (slots 2b = target, 2b + 1 = source).
 // streaming = true : dev_target / dev_nt are ignored; the slot that holds the previous call's preprocessed source clouds
 //                    becomes the target as it is, the new source clouds go through preprocessing into the other slot.
-static int gicp_run(gfs_gicp* h, const void* dev_target, const void* dev_nt, const void* dev_source, const void* dev_ns, int B,
-                    int stride_pts, const double* init_T, const gfs_gicp_config* cfg, gfs_gicp_result* out, void* stream,
-                    bool streaming) {
-  GFS_REQUIRE(h && (streaming || (dev_target && dev_nt)) && dev_source && dev_ns && B > 0 && stride_pts > 0 && cfg && out,
-              GFS_ERR_INVALID_ARG, "gfs_gicp_align: invalid argument");
-  GFS_REQUIRE(B <= h->Bmax, GFS_ERR_CAPACITY, "batch %d exceeds handle max_batch %d", B, h->Bmax);
-  GFS_REQUIRE(cfg->downsampling_resolution > 0 && cfg->max_correspondence_distance > 0 && cfg->num_neighbors >= 1 &&
-                  cfg->num_neighbors <= 10,
-              GFS_ERR_UNSUPPORTED, "gfs_gicp: need resolution > 0, max_corr > 0, 1 <= num_neighbors <= 10");
-  std::lock_guard<std::recursive_mutex> lk(h->mu);
-  GFS_HIP(hipSetDevice(h->device));
-  hipStream_t s = stream ? (hipStream_t)stream : h->stream;
+static int gicp_attempt(gfs_gicp* h, const void* dev_target, const void* dev_nt, const void* dev_source, const void* dev_ns, int B,
+                        int stride_pts, const double* init_T, const gfs_gicp_config* cfg, gfs_gicp_result* out, hipStream_t s,
+                        bool streaming, bool optimistic_sort) {
   const int P = h->P, C2 = 2 * B;
-  // (the round loop below looks at the count the LDS sort kernel leaves; the persistent LM kernel has no such look)
-  const bool optimistic_sort = h->lm_rounds && !h->sort_all_kernels && h->sort_all_hold == 0;
-  if (h->sort_all_hold > 0 && !h->sort_all_kernels) h->sort_all_hold--;
+  // what the cooperative kernel takes of the process-wide budget is given back on EVERY way out of this function (the early
+  // returns of GFS_HIP / GFS_LAUNCH included)
+  CoopLease lease(h, s);
   GicpParams prm;
   prm.inv_leaf = 1.0 / cfg->downsampling_resolution;
   // cell edge = max correspondence distance: one ring of cells certifies every 1-NN probe and (for voxel-sized
@@ -3687,9 +3268,7 @@ static int gicp_run(gfs_gicp* h, const void* dev_target, const void* dev_nt, con
   prm.inv_cell = 1.0 / prm.cell;
   prm.nn_rings = (int)std::ceil(cfg->max_correspondence_distance / prm.cell - 1e-12);
   if (prm.nn_rings < 1) prm.nn_rings = 1;
-  prm.lin_tile = 0;  // measured (profiles/README.md, round 3): with the x-ordered sweep the search in HBM at 4 waves per SIMD beats the staged tile at 3
-  prm.tile_stats = h->tile_stats_on ? h->d_tile_stats.p : nullptr;  // one atomic per workgroup on one address: only on request
-  if (const char* e = getenv("GFS_GICP_LIN_TILE")) prm.lin_tile = atoi(e) != 0;  // 0: every workgroup searches the cloud in HBM
+  prm.tile_stats = h->tile_stats_on ? h->d_tile_stats.p : nullptr;  // atomics of every wave on a few addresses: only on request
   prm.max_dist_sq = cfg->max_correspondence_distance * cfg->max_correspondence_distance;
   prm.rot_eps = cfg->rotation_eps;
   prm.trans_eps = cfg->translation_eps;
@@ -3765,151 +3344,84 @@ static int gicp_run(gfs_gicp* h, const void* dev_target, const void* dev_nt, con
              h->d_ubegin.p, h->d_nucell.p, h->d_m.p, h->d_bbox.p, h->d_grid.p, h->d_ginfo.p, h->d_ginfo.p, h->d_hard.p,
              h->d_hard_d.p, knn_chunks, B, P, prm, h->d_cov6.p);
   const int far_chunks = std::max(1, std::min(32, knn_chunks));  // grid-stride over the deferred lists
-  GFS_LAUNCH("k_knn_cov_far", (k_knn_cov_far<16, 2, true>), dim3(xcd_grid(far_chunks, B, 2)), dim3(256), 0, s, h->d_pts.p,
+  GFS_LAUNCH("k_knn_cov_far", k_knn_cov_far, dim3(xcd_grid(far_chunks, B, 2)), dim3(256), 0, s, h->d_pts.p,
              h->d_ucell.p, h->d_ubegin.p, h->d_nucell.p, h->d_m.p, h->d_bbox.p, h->d_grid.p, h->d_ginfo.p, h->d_hard.p,
              h->d_hard_d.p, h->d_far2.p, far_chunks, B, P, prm, h->d_cov6.p);
   const int far2_chunks = std::max(1, std::min(32, knn_chunks));  // a handful of queries per cloud (a few dozen in the worst scenes), a workgroup each
-  static const bool far2_groups = getenv("GFS_GICP_FAR2") && strcmp(getenv("GFS_GICP_FAR2"), "groups") == 0;  // the lane-group form
-  if (far2_groups)
-    GFS_LAUNCH("k_knn_cov_far_groups", (k_knn_cov_far<64, 4, false>), dim3(xcd_grid(4, B, 2)), dim3(256), 0, s, h->d_pts.p,
-               h->d_ucell.p, h->d_ubegin.p, h->d_nucell.p, h->d_m.p, h->d_bbox.p, h->d_grid.p, h->d_ginfo.p, h->d_hard.p,
-               h->d_hard_d.p, h->d_far2.p, 4, B, P, prm, h->d_cov6.p);
-  else
-    GFS_LAUNCH("k_knn_cov_far_wg", k_knn_cov_far_wg, dim3(xcd_grid(far2_chunks, B, 2)), dim3(256), 0, s, h->d_pts.p, h->d_ucell.p,
-               h->d_ubegin.p, h->d_nucell.p, h->d_m.p, h->d_bbox.p, h->d_grid.p, h->d_ginfo.p, h->d_hard.p, h->d_hard_d.p,
-               h->d_far2.p, far2_chunks, B, P, prm, h->d_cov6.p);
+  GFS_LAUNCH("k_knn_cov_far_wg", k_knn_cov_far_wg, dim3(xcd_grid(far2_chunks, B, 2)), dim3(256), 0, s, h->d_pts.p, h->d_ucell.p,
+             h->d_ubegin.p, h->d_nucell.p, h->d_m.p, h->d_bbox.p, h->d_grid.p, h->d_ginfo.p, h->d_hard.p, h->d_hard_d.p,
+             h->d_far2.p, far2_chunks, B, P, prm, h->d_cov6.p);
   // ---- LevenbergMarquardtOptimizer::optimize: device state machine, host polls the done counter
   GFS_LAUNCH("k_gicp_init", k_gicp_init, dim3(gfs::div_up(B, 64)), dim3(64), 0, s, h->d_state.p, h->hd_initT, B,
              prm.max_iterations, h->d_ndone.p, h->d_sync.p);
-  if (!h->lm_rounds) {
-    // the whole Levenberg-Marquardt loop of a pair in one workgroup (k_gicp_lm): one launch, no host poll
-    GFS_LAUNCH("k_gicp_lm", k_gicp_lm, dim3(B), dim3(kLmBlock), 0, s, h->d_state.p, h->d_pts.p, h->d_cov6.p, h->d_ucell.p,
-               h->d_ubegin.p, h->d_nucell.p, h->d_m.p, h->d_grid.p, h->d_ginfo.p, B, P, prm, h->d_tgt_index.p, h->d_maha6.p);
-  } else {
-    const int nblk_run = gfs::div_up(npts, kLinBlock);
-    const int max_rounds = std::max(1, prm.max_iterations) * 11 + 2;
-    const size_t buf_stride = (size_t)h->Bmax * P;  // elements between a pair's two (tgt_index, maha6 / 6) buffers
-    int known_done = 0;  // pairs known to be done: the count polled one round behind
-    // k_gicp_lm_coop takes the loop of `n_ub` pairs (an upper bound of those still iterating; the exact list, if any, is on the
-    // device) off the host: the rest of the loop is ONE launch.  Its workgroups wait for each other, so they come out of the
-    // process-wide budget; with too few left the rounds below carry on.
-    static const bool lin_wg_default = !getenv("GFS_GICP_LIN_WG") || atoi(getenv("GFS_GICP_LIN_WG")) / 64 * 64 >= 256;
-    const bool coop_ok = h->coop && !h->coop_failed && !prm.lin_tile && lin_wg_default && h->coop_cap > 0 && prm.max_iterations > 0;
-    const int coop_budget = h->coop_cap / 2;
-    auto launch_coop = [&](int n_ub, const int* act_list, const int* n_act_list) -> bool {
-      static const int max_wg = getenv("GFS_GICP_COOP_MAXWG") ? std::max(1, atoi(getenv("GFS_GICP_COOP_MAXWG"))) : (1 << 30);  // debugging: fewer workgroups a pair
-      const int want = std::min(std::min(n_ub * nblk_run, coop_budget), std::max(n_ub, max_wg));
-      const int got = CoopBudget::reserve(h->device, want, std::max(n_ub, want / 2), coop_budget);
-      if (got <= 0) return false;
-      h->coop_reserved += got;
-      h->coop_launches++;
-      h->coop_last_wgs = got;
+  const int nblk_run = gfs::div_up(npts, kLinBlock);
+  const int max_rounds = std::max(1, prm.max_iterations) * 11 + 2;
+  const size_t buf_stride = (size_t)h->Bmax * P;  // elements between a pair's two (tgt_index, maha6 / 6) buffers
+  // A batch small enough for a workgroup per chunk of every pair (one live stream: B = 1) runs its whole loop in ONE launch of
+  // k_gicp_lm_coop, off the host.  The kernel's workgroups wait for each other, so they come out of the process-wide budget; with
+  // too few left the rounds below run instead, as they do for every larger batch.
+  const int coop_budget = h->coop_cap / 2;
+  bool in_coop = false;
+  if (h->coop && !h->coop_failed && prm.max_iterations > 0 && coop_budget > 0 && (long long)B * nblk_run <= coop_budget) {
+    const int want = B * nblk_run;
+    const int got = lease.reserve(want, std::max(B, want / 2), coop_budget);
+    if (got > 0) {
       GFS_LAUNCH("k_gicp_lm_coop", k_gicp_lm_coop, dim3(got), dim3(kLinBlock), 0, s, h->d_state.p, h->d_pts.p, h->d_cov6.p, h->d_ucell.p,
                  h->d_ubegin.p, h->d_nucell.p, h->d_m.p, h->d_grid.p, h->d_ginfo.p, nblk_run, P, prm, h->d_tgt_index.p, h->d_maha6.p,
-                 buf_stride, h->d_partial.p, h->d_epartial.p, h->nblk, act_list, n_act_list, n_ub, h->d_sync.p, h->d_ndone.p, h->d_ndone.p + 2);
-      return true;
-    };
-    // a batch small enough for a workgroup per chunk of every pair (one live stream: B = 1) runs its whole loop there
-    bool in_coop = coop_ok && (long long)B * nblk_run <= coop_budget && launch_coop(B, nullptr, nullptr);
-    for (int round = 0; round < max_rounds && !in_coop; round++) {
-      // Late rounds run for a handful of pairs: their grids are cut to the pairs still iterating.  The host knows an upper bound
-      // (the done counter it polled for round - 2); the list itself is written on the device by the previous round's
-      // k_gicp_decide.  While most pairs are active the full grid with its XCD-aware pair -> block map is kept.
-      const int ub = B - known_done;
-      // ... and once the pairs left would each get at least 1 / coop_tail of a workgroup per chunk, the tail goes to the cooperative kernel
-      if (coop_ok && round >= 2 && ub < B && (double)ub * nblk_run <= h->coop_tail * coop_budget &&
-          launch_coop(ub, h->d_active.p + (size_t)(round % 3) * B, h->d_nactive.p + (round % 3))) {
-        in_coop = true;
-        break;
-      }
-      const bool listed = round >= 2 && 4 * ub <= B;
-      const int* act = listed ? h->d_active.p + (size_t)(round % 3) * B : nullptr;
-      const int* n_act = h->d_nactive.p + (round % 3);
-      int* act_next = h->d_active.p + (size_t)((round + 1) % 3) * B;
-      int* n_act_next = h->d_nactive.p + ((round + 1) % 3);
-      int* n_act_clear = h->d_nactive.p + ((round + 2) % 3);
-      const dim3 grid_pts(listed ? std::max(ub, 1) * nblk_run : xcd_grid(nblk_run, B, 1));
-      // GFS_GICP_LIN_WG=64 / 128: the kernels without LDS as one- or two-wave workgroups, four or two to a chunk (lin_point_of).
-      // Measured in round 4: k_gicp_linearize alone 150 -> 137 us per launch of 512 pairs with one-wave workgroups (finished waves
-      // make room at once), the overlapped bench unchanged to slightly lower (37.2 against 37.3 k frames/s, the 64-pair block 28.8
-      // against 29.0 k: the other lanes' kernels already fill those gaps, and four times the workgroups go through the dispatcher)
-      static const int lin_wg = getenv("GFS_GICP_LIN_WG") ? std::max(64, std::min(256, atoi(getenv("GFS_GICP_LIN_WG")) / 64 * 64)) : 256;
-      const int per = kLinBlock / (lin_wg == 128 ? 128 : lin_wg == 256 ? 256 : 64), wg = kLinBlock / per;
-      const dim3 grid_w(listed ? std::max(ub, 1) * nblk_run * per : xcd_grid(nblk_run * per, B, 1));
-      // one pass per round: the pending trials' errors + the linearisations, and -- in the pair's last workgroup -- its scalar step
-      // (GFS_GICP_LIN_WG = 64 / 128, workgroups smaller than the fold needs: the step as a launch of its own, k_gicp_step)
-      // GFS_GICP_FUSE_STEP=1 (256-thread workgroups): the step inside the pass, taken by the pair's last workgroup -- a round is ONE
-      // launch.  Measured (round 6): SLOWER -- a lane of 32 pairs 8 x (45 + 11) -> 8 x 60 us of kernels a call, the 64-pair block 2.03 ->
-      // 2.07 ms, the headline 42.8 -> 41.3 k frames/s: the last workgroup's fold through L1-bypassing loads and its one-lane solve
-      // lengthen every pass by more than the launch boundary they save.  Kept behind the knob with its parity test.
-      const bool fuse = h->fuse_step && wg == kLinBlock;
-      if (prm.lin_tile) {
-        GFS_LAUNCH("k_gicp_linearize", (k_gicp_linearize<true, false>), grid_pts, dim3(kLinBlock), 0, s, h->d_state.p,
-                   h->d_pts.p, h->d_cov6.p, h->d_ucell.p, h->d_ubegin.p, h->d_nucell.p, h->d_m.p, h->d_grid.p, h->d_ginfo.p,
-                   nblk_run, B, P, prm, h->d_tgt_index.p, h->d_maha6.p, buf_stride, h->d_partial.p, h->d_epartial.p, h->nblk, act, n_act,
-                   nullptr, nullptr, nullptr, nullptr, nullptr);
-      } else if (fuse) {
-        GFS_LAUNCH("k_gicp_linearize", (k_gicp_linearize<false, true>), grid_w, dim3(wg), 0, s, h->d_state.p,
-                   h->d_pts.p, h->d_cov6.p, h->d_ucell.p, h->d_ubegin.p, h->d_nucell.p, h->d_m.p, h->d_grid.p, h->d_ginfo.p,
-                   nblk_run * per, B, P, prm, h->d_tgt_index.p, h->d_maha6.p, buf_stride, h->d_partial.p, h->d_epartial.p, h->nblk, act, n_act,
-                   h->d_sync.p, h->d_ndone.p, act_next, n_act_next, n_act_clear);
-      } else {
-        GFS_LAUNCH("k_gicp_linearize", (k_gicp_linearize<false, false>), grid_w, dim3(wg), 0, s, h->d_state.p,
-                   h->d_pts.p, h->d_cov6.p, h->d_ucell.p, h->d_ubegin.p, h->d_nucell.p, h->d_m.p, h->d_grid.p, h->d_ginfo.p,
-                   nblk_run * per, B, P, prm, h->d_tgt_index.p, h->d_maha6.p, buf_stride, h->d_partial.p, h->d_epartial.p, h->nblk, act, n_act,
-                   nullptr, nullptr, nullptr, nullptr, nullptr);
-      }
-      if (!fuse || prm.lin_tile)
-        GFS_LAUNCH("k_gicp_step", k_gicp_step, dim3(B), dim3(256), 0, s, h->d_state.p, h->d_partial.p, h->d_epartial.p, h->d_m.p, h->nblk, prm,
-                   h->d_ndone.p, act_next, n_act_next, n_act_clear);
-      // One round (`ahead`, GFS_GICP_AHEAD) is queued beyond the one being polled: the GPU does not idle on the host's round trip; the
-      // speculative round behind convergence finds every pair in phase 2 and its blocks exit at once.  The state machine lives on the
-      // device, so how far ahead the host runs changes no result.  Round 6 measured deeper queues, because a kernel trace of the
-      // 64-pair block under rocprofv3 shows the GICP stream idle for ~50 us behind every round's counter copy (tools/probes/
-      // chain_timeline.py): ahead = 1 / 2 / 3 / 4 / 6 -> 2.000 / 2.014 / 2.019 / 2.041 / 2.054 ms per 64 pairs (2 lanes), 11.92 / 11.93 /
-      // 11.98 / 12.05 / 12.09 ms per 512 -- the gaps are the profiler's, without it the host keeps up, and every extra round in flight
-      // is two empty launches and a copy at the end of the call.
-      const int nslot = h->ahead + 1, slot = round % nslot;
-      GFS_HIP(hipMemcpyAsync(h->h_ndone.p + 2 * slot, h->d_ndone.p, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
-      GFS_HIP(hipEventRecord(h->ev_round[slot], s));
-      if (round >= h->ahead) {
-        const int pslot = (round - h->ahead) % nslot;
-        GFS_HIP(hipEventSynchronize(h->ev_round[pslot]));
-        if (optimistic_sort && h->h_ndone.p[2 * pslot + 1] > 0) {
-          // a cloud needed the voxel-sort kernels that were not launched (keys wider than 31 bits): everything again, with them
-          GFS_HIP(hipStreamSynchronize(s));
-          h->sort_all_kernels = true;
-          const int rc_again = gicp_run(h, dev_target, dev_nt, dev_source, dev_ns, B, stride_pts, init_T, cfg, out, stream, streaming);
-          h->sort_all_kernels = false;
-          h->sort_all_hold = 64;
-          return rc_again;
-        }
-        known_done = h->h_ndone.p[2 * pslot];
-        if (known_done >= B) break;
-      }
+                 buf_stride, h->d_partial.p, h->d_epartial.p, h->nblk, B, h->d_sync.p, h->d_ndone.p, h->d_ndone.p + 2);
+      lease.in_flight = in_coop = true;  // (a launch that failed has returned above: its reservation goes back without a wait)
+      h->coop_launches++;
+      h->coop_last_wgs = got;
     }
   }
-  int* const last_look = h->h_ndone.p + 2 * (gfs_gicp::kAheadMax + 1);  // {pairs done, clouds the LDS sorts left, workgroups that gave up waiting}
+  int known_done = 0;  // pairs known to be done: the count polled one round behind
+  for (int round = 0; round < max_rounds && !in_coop; round++) {
+    // Late rounds run for a handful of pairs: their grids are cut to the pairs still iterating.  The host knows an upper bound
+    // (the done counter it polled for round - 2); the list itself is written on the device by the previous round's
+    // k_gicp_step.  While most pairs are active the full grid with its XCD-aware pair -> block map is kept.
+    const int ub = B - known_done;
+    const bool listed = round >= 2 && 4 * ub <= B;
+    const int* act = listed ? h->d_active.p + (size_t)(round % 3) * B : nullptr;
+    const int* n_act = h->d_nactive.p + (round % 3);
+    int* act_next = h->d_active.p + (size_t)((round + 1) % 3) * B;
+    int* n_act_next = h->d_nactive.p + ((round + 1) % 3);
+    int* n_act_clear = h->d_nactive.p + ((round + 2) % 3);
+    const dim3 grid_pts(listed ? std::max(ub, 1) * nblk_run : xcd_grid(nblk_run, B, 1));
+    // one pass per round -- the pending trials' errors + the linearisations -- and the pairs' scalar steps
+    GFS_LAUNCH("k_gicp_linearize", k_gicp_linearize, grid_pts, dim3(kLinBlock), 0, s, h->d_state.p, h->d_pts.p, h->d_cov6.p,
+               h->d_ucell.p, h->d_ubegin.p, h->d_nucell.p, h->d_m.p, h->d_grid.p, h->d_ginfo.p, nblk_run, B, P, prm, h->d_tgt_index.p,
+               h->d_maha6.p, buf_stride, h->d_partial.p, h->d_epartial.p, h->nblk, act, n_act);
+    GFS_LAUNCH("k_gicp_step", k_gicp_step, dim3(B), dim3(256), 0, s, h->d_state.p, h->d_partial.p, h->d_epartial.p, h->d_m.p, h->nblk, prm,
+               h->d_ndone.p, act_next, n_act_next, n_act_clear);
+    // One round is queued beyond the one being polled: the GPU does not idle on the host's round trip; the speculative round behind
+    // convergence finds every pair in phase 2 and its blocks exit at once.  The state machine lives on the device, so how far ahead
+    // the host runs changes no result (deeper queues were measured in round 6 and were slower: profiles/README.md).
+    const int slot = round % gfs_gicp::kRoundSlots;
+    GFS_HIP(hipMemcpyAsync(h->h_ndone.p + 2 * slot, h->d_ndone.p, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
+    GFS_HIP(hipEventRecord(h->ev_round[slot], s));
+    if (round >= 1) {
+      const int pslot = (round - 1) % gfs_gicp::kRoundSlots;
+      GFS_HIP(hipEventSynchronize(h->ev_round[pslot]));
+      if (optimistic_sort && h->h_ndone.p[2 * pslot + 1] > 0) {
+        // a cloud needed the voxel-sort kernels that were not launched (keys wider than 31 bits): everything again, with them
+        GFS_HIP(hipStreamSynchronize(s));
+        return kAgainAllSorts;
+      }
+      known_done = h->h_ndone.p[2 * pslot];
+      if (known_done >= B) break;
+    }
+  }
+  int* const last_look = h->h_ndone.p + 2 * gfs_gicp::kRoundSlots;  // {pairs done, clouds the LDS sorts left, workgroups that gave up waiting}
   last_look[0] = last_look[1] = last_look[2] = 0;
   GFS_LAUNCH("k_gicp_publish", k_gicp_publish, dim3(std::max(1, std::min(16, gfs::div_up(B * kStateWords, 256)))), dim3(256), 0, s, h->d_state.p,
              h->d_m.p, h->d_ndone.p, B, reinterpret_cast<u64*>(h->hd_state), h->hd_m, h->hd_last);
   const hipError_t rc_sync = hipStreamSynchronize(s);
-  CoopBudget::release(h->device, h->coop_reserved);  // (whatever happened: the kernel is not running any more)
-  h->coop_reserved = 0;
+  lease.release();  // (whatever happened: the kernel is not running any more)
   GFS_HIP(rc_sync);
-  if (last_look[2] > 0 && !h->coop_failed) {
-    // a workgroup of k_gicp_lm_coop gave up waiting (its grid was not resident together: another process on this device?): never
-    // return such a result -- the call again with a launch per step, and this handle stays with that
-    h->coop_failed = true;
-    return gicp_run(h, dev_target, dev_nt, dev_source, dev_ns, B, stride_pts, init_T, cfg, out, stream, streaming);
-  }
-  if (optimistic_sort && last_look[1] > 0) {  // (the polls inside the loop normally catch this after round 0; never return such a result)
-    h->sort_all_kernels = true;
-    const int rc_again = gicp_run(h, dev_target, dev_nt, dev_source, dev_ns, B, stride_pts, init_T, cfg, out, stream, streaming);
-    h->sort_all_kernels = false;
-    h->sort_all_hold = 64;
-    return rc_again;
-  }
+  // a workgroup of k_gicp_lm_coop gave up waiting (its grid was not resident together: another process on this device?)
+  if (last_look[2] > 0 && !h->coop_failed) return kAgainNoCoop;
+  // (the polls inside the loop normally catch this after round 0)
+  if (optimistic_sort && last_look[1] > 0) return kAgainAllSorts;
   for (int b = 0; b < B; b++) {
     const PairState& S = h->h_state.p[b];
     gfs_gicp_result& r = out[b];
@@ -3942,6 +3454,37 @@ static int gicp_run(gfs_gicp* h, const void* dev_target, const void* dev_nt, con
   h->last_cell = prm.cell;
   h->last_k = cfg->num_neighbors;
   return GFS_OK;
+}
+
+static int gicp_run(gfs_gicp* h, const void* dev_target, const void* dev_nt, const void* dev_source, const void* dev_ns, int B,
+                    int stride_pts, const double* init_T, const gfs_gicp_config* cfg, gfs_gicp_result* out, void* stream,
+                    bool streaming) {
+  GFS_REQUIRE(h && (streaming || (dev_target && dev_nt)) && dev_source && dev_ns && B > 0 && stride_pts > 0 && cfg && out,
+              GFS_ERR_INVALID_ARG, "gfs_gicp_align: invalid argument");
+  GFS_REQUIRE(B <= h->Bmax, GFS_ERR_CAPACITY, "batch %d exceeds handle max_batch %d", B, h->Bmax);
+  GFS_REQUIRE(cfg->downsampling_resolution > 0 && cfg->max_correspondence_distance > 0 && cfg->num_neighbors >= 1 &&
+                  cfg->num_neighbors <= 10,
+              GFS_ERR_UNSUPPORTED, "gfs_gicp: need resolution > 0, max_corr > 0, 1 <= num_neighbors <= 10");
+  std::lock_guard<std::recursive_mutex> lk(h->mu);
+  GFS_HIP(hipSetDevice(h->device));
+  hipStream_t s = stream ? (hipStream_t)stream : h->stream;
+  bool all_sorts = h->sort_all_hold > 0;
+  if (all_sorts) h->sort_all_hold--;
+  // at most three attempts: each of the two reasons to come back switches off what gave rise to it
+  int rc = GFS_OK;
+  for (int attempt = 0; attempt < 3; attempt++) {
+    rc = gicp_attempt(h, dev_target, dev_nt, dev_source, dev_ns, B, stride_pts, init_T, cfg, out, s, streaming, !all_sorts);
+    if (rc == kAgainAllSorts) {
+      all_sorts = true;
+      h->sort_all_hold = 64;
+    } else if (rc == kAgainNoCoop) {
+      h->coop_failed = true;  // this handle stays with a launch per step
+    } else {
+      return rc;
+    }
+  }
+  gfs::set_error("gfs_gicp_align: the call did not settle in three attempts (last: %d)", rc);
+  return GFS_ERR_HIP;
 }
 
 int gfs_gicp_align_batch_device(gfs_gicp* h, const void* dev_target, const void* dev_nt, const void* dev_source,
@@ -4059,7 +3602,7 @@ int gfs_gicp_coop_stats(gfs_gicp* h, int out[4]) {
   out[0] = h->coop_launches;
   out[1] = h->coop_last_wgs;
   out[2] = h->coop_failed ? 1 : 0;
-  out[3] = h->coop && h->lm_rounds ? h->coop_cap / 2 : 0;
+  out[3] = h->coop ? h->coop_cap / 2 : 0;
   return GFS_OK;
 }
 

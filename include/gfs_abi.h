@@ -210,16 +210,18 @@ int gfs_gicp_align_next_batch_device(gfs_gicp* h, const void* dev_source, const 
 /* Introspection for parity tests: preprocessing output (voxel means + covariances) of cloud `which`
  * (0 = target, 1 = source) of pair b of the last call. pts: [m][4] f64, covs: [m][9] f64 (3x3 col-major). */
 int gfs_gicp_fetch_preprocessed(gfs_gicp* h, int b, int which, double* pts, double* covs, int cap, int* m);
-/* Diagnostics: workgroups of the linearisation kernel since the last reset, by outcome of staging their tile of the target cloud in
- * LDS: out8[0] staged; [1] no dense grid; [2] no usable point; [3] / [4] / [5] too many rows / points / cell boundaries for the
- * tile (those workgroups search the cloud in HBM: same results); [6] tiling switched off.  Counted only by handles created with
- * GFS_GICP_TILE_STATS=1 in the environment (one atomic per workgroup on one address is not free). */
+/* Diagnostics: the handle's counter block of eight words since the last reset.  The library as built writes none of them; the
+ * variant builds do (tools/variant.sh): -DGFS_KNN_UTIL counts in k_knn_cov out8[0] / [1] lanes at work / steps of the own-row walk,
+ * [2] / [3] the same of the neighbouring rows' scan, [4] / [5] queries / waves, [6] candidates of the own rows
+ * (tools/probes/knn_util_probe.py); -DGFS_LIN_UTIL counts in the linearisation's 1-NN search [2] / [3] lanes / rounds of neighbouring
+ * rows, [4] / [5] lanes / steps of the walk, [6] / [7] searches / waves (tools/probes/lin_util_probe.py).  Counted only by handles
+ * created with GFS_GICP_TILE_STATS=1 in the environment (atomics of every wave on a few addresses are not free). */
 int gfs_gicp_tile_stats(gfs_gicp* h, unsigned long long* out8, int reset);
 /* Diagnostics (tools/knn_probe.py): out = {down-sampled points, queries deferred to the r = 2 pass, queries deferred to the
  * isolated-point pass} of cloud (b, which) of the last call; dk (may be NULL): the squared-distance bounds of the latter. */
 int gfs_gicp_knn_stats(gfs_gicp* h, int b, int which, int out[3], double* dk, int cap);
 /* Diagnostics: how the Levenberg-Marquardt loops of this handle's calls were driven.  out = {launches of the cooperative kernel
- * (the loop of a few pairs in ONE launch: a single live stream, the tail of a batch) so far, workgroups of the last such launch,
+ * (the loop of a few pairs in ONE launch: a single live stream, a batch that fits the workgroup budget) so far, workgroups of the last such launch,
  * 1 if a launch ever failed to become resident and the handle fell back to a launch per step for good, the workgroup budget}. */
 int gfs_gicp_coop_stats(gfs_gicp* h, int out[4]);
 

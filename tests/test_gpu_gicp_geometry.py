@@ -1,5 +1,5 @@
 """GPU half of the GICP geometry tests (MI355X): the neighbour searches of csrc/gicp.hip -- k_knn_cov, the r = 2 pass
-k_knn_cov_far<16, 2, true>, the isolated-point pass k_knn_cov_far_wg / k_knn_cov_far<64, 4, false>, the 1-NN walk of k_gicp_linearize
+k_knn_cov_far, the isolated-point pass k_knn_cov_far_wg, the 1-NN walk of k_gicp_linearize
 -- on clouds that are NOT depth-camera rasters (tests/gicp_geometry_support.py), against brute-force numpy references that share
 nothing with the kernels' cell grid or the oracle's KdTree, and with assertions on WHICH pass answered (gfs_gicp_knn_stats).
 tests/test_gicp_geometry_reference.py pins the references and the caps used here on the CPU.
@@ -10,8 +10,6 @@ normal minimises the neighbourhood's scatter); one linearisation within 100 x ma
 the GPU's own preprocessed clouds, inliers equal; full registrations by test_gpu_gicp._gicp_same."""
 import functools
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -19,7 +17,6 @@ import pytest
 import gicp_geometry_support as G
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SEED = G.SEEDS[0]
 CAP = 8192  # raw points per cloud: the largest generator draws 6 000
 LIN_NAMES = [n for n in G.NAMES if not (n.startswith("tiny_") and int(n[5:]) < 10)]  # clouds of >= 10 points
@@ -40,8 +37,7 @@ def _unpack(d, key):
 def collect(api, names=G.NAMES, seed=SEED):
     """Everything the tests compare, from ONE fresh handle under the environment of the moment: per cloud the preprocessing of
     (c, c) and its pass counts; per pair (c, moved(c)) one linearisation at init_T (max_iterations = 1) with both preprocessed clouds,
-    the full registration from init_T, and the registration of (c, nothing).  A flat dict of arrays (np.savez-able: the child
-    processes of the once-per-process knobs hand it over as a file)."""
+    the full registration from init_T, and the registration of (c, nothing).  A flat dict of arrays."""
     reg = api.RegistrationGICP(max_points=CAP)
     out = {}
     for name in names:
@@ -63,7 +59,7 @@ def collect(api, names=G.NAMES, seed=SEED):
 
 @pytest.fixture(scope="module")
 def default(gpu_api):
-    for k in ("GFS_GICP_KNN_EXACT", "GFS_GICP_LIN_TILE", "GFS_GICP_COOP", "GFS_GICP_LM", "GFS_GICP_FAR2", "GFS_GICP_LIN_WG", "GFS_GICP_CELL"):
+    for k in ("GFS_GICP_KNN_EXACT", "GFS_GICP_COOP", "GFS_GICP_CELL"):
         assert k not in os.environ, k + " is set: these tests compare the knobs with the default"
     return collect(gpu_api)
 
@@ -283,59 +279,11 @@ def _same_results(a, b, keys):
 
 
 def test_per_handle_knobs_on_these_clouds(gpu_api, default, monkeypatch):
-    """(f) GFS_GICP_LIN_TILE=1 and GFS_GICP_COOP=0 promise the default's bits (test_staged_tile_gives_the_same_bits,
-    test_cooperative_lm_kernel_gives_the_bits_of_the_launch_per_step_rounds): the same here, preprocessing included.
-    GFS_GICP_LM=persistent promises equality to rounding (csrc/gicp.hip: the sums are folded in another fixed order): it is held to
-    the bars of the default -- (d) against reference_linearize, (e) against the oracle -- on its own."""
-    for knob, val in (("GFS_GICP_LIN_TILE", "1"), ("GFS_GICP_COOP", "0")):
+    """(f) GFS_GICP_COOP=0 promises the default's bits (test_cooperative_lm_kernel_gives_the_bits_of_the_launch_per_step_rounds): the
+    same here, preprocessing included."""
+    for knob, val in (("GFS_GICP_COOP", "0"),):
         monkeypatch.setenv(knob, val)
         got = collect(gpu_api)
         monkeypatch.delenv(knob)
         diff = [k for k in default if not _same_results(got, default, [k])]
         assert not diff, (knob, diff[:8])
-    monkeypatch.setenv("GFS_GICP_LM", "persistent")
-    got = collect(gpu_api)
-    monkeypatch.delenv("GFS_GICP_LM")
-    for name in G.NAMES:
-        assert _same_results(got, default, [name + k for k in ("/pts", "/cov", "/stats", "/tpts", "/tcov", "/spts", "/scov")]), name
-        if name in LIN_NAMES:
-            _check_linearization(name, got, " (persistent)")
-        _check_full(name, got, " (persistent)")
-
-
-def _child(tmp_path, env_knob, value):
-    out = str(tmp_path / f"{env_knob}_{value}.npz")
-    env = dict(os.environ)
-    env[env_knob] = value
-    flags = ["-s"] if sys.flags.no_user_site else []
-    r = subprocess.run([sys.executable] + flags + [os.path.abspath(__file__), out], env=env, cwd=ROOT, timeout=600, capture_output=True, text=True)
-    assert r.returncode == 0, (env_knob, value, r.returncode, r.stdout[-2000:], r.stderr[-2000:])
-    return dict(np.load(out))
-
-
-def test_once_per_process_knobs_in_a_child_process(gpu_api, default, tmp_path):
-    """(f) GFS_GICP_FAR2=groups and GFS_GICP_LIN_WG=64 / 128 are read once per process: each runs collect() in a fresh child (one at
-    a time; a failing child fails the test and no further one starts).  FAR2=groups (the lane-group form of the isolated-point pass)
-    picks by distance, then lower index, as the workgroup form does: every bit of the default.  LIN_WG promises no bit-equality of the
-    sums (smaller workgroups fold the per-point terms in another order, the step is its own launch): its linearisation is held to
-    (d) against reference_linearize on its own, inliers equal to the default's, and its preprocessing to the default's bits."""
-    got = _child(tmp_path, "GFS_GICP_FAR2", "groups")
-    diff = [k for k in default if not _same_results(got, default, [k])]
-    assert not diff, ("GFS_GICP_FAR2=groups", diff[:8])
-    for wg in ("64", "128"):
-        got = _child(tmp_path, "GFS_GICP_LIN_WG", wg)
-        for name in G.NAMES:
-            assert _same_results(got, default, [name + k for k in ("/pts", "/cov", "/stats", "/tpts", "/tcov", "/spts", "/scov")]), (wg, name)
-            if name in LIN_NAMES:
-                _check_linearization(name, got, f" (LIN_WG={wg})")
-            a, b = _unpack(got, name + "/lin"), _unpack(default, name + "/lin")
-            assert a["num_inliers"] == b["num_inliers"] and a["iterations"] == b["iterations"], (wg, name)
-            _check_full(name, got, f" (LIN_WG={wg})")
-
-
-if __name__ == "__main__":  # the child of test_once_per_process_knobs_in_a_child_process: collect() under the inherited environment
-    sys.path.insert(0, ROOT)
-    from geoflowslam_amd import api as A
-    A.lib()
-    assert A.device_count() >= 1
-    np.savez(sys.argv[1], **collect(A))
