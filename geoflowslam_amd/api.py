@@ -327,7 +327,7 @@ ABI_SYMBOLS = [
     "gfs_hamming256", "gfs_matcher_create", "gfs_matcher_destroy", "gfs_bf_match_hamming",
     "gfs_bf_match_hamming_batch_device",
     "gfs_gicp_default_config", "gfs_gicp_create", "gfs_gicp_destroy", "gfs_gicp_align", "gfs_gicp_align_batch_device",
-    "gfs_gicp_fetch_preprocessed", "gfs_gicp_tile_stats", "gfs_gicp_knn_stats", "gfs_gicp_coop_stats", "gfs_frame_rgbd", "gfs_gicp_align_next", "gfs_gicp_align_next_batch_device", "gfs_test_voxel_sort", "gfs_test_wave_std_sort",
+    "gfs_gicp_fetch_preprocessed", "gfs_gicp_tile_stats", "gfs_gicp_knn_stats", "gfs_gicp_coop_stats", "gfs_frame_rgbd", "gfs_gicp_align_next", "gfs_gicp_align_next_batch_device", "gfs_test_voxel_sort", "gfs_test_voxel_sort_paths", "gfs_test_wave_std_sort",
     "gfs_lba_create", "gfs_lba_destroy", "gfs_lba_solve", "gfs_lba_solve_bool", "gfs_lba_linearize", "gfs_lba_batch_create", "gfs_lba_batch_destroy",
     "gfs_lba_solve_batch", "gfs_lba_lidar_reserve", "gfs_lba_solve_lidar", "gfs_lba_solve_lidar_bool", "gfs_lba_linearize_lidar",
     "gfs_lba_fetch_lidar_edges", "gfs_test_lba_stop_at_look", "gfs_test_lba_last_looks",
@@ -397,6 +397,7 @@ def lib():
             L.gfs_gicp_knn_stats.argtypes = [vp, i, i, vp, vp, i]
             L.gfs_gicp_coop_stats.argtypes = [vp, vp]
             L.gfs_test_voxel_sort.argtypes = [vp, vp, i, vp]
+            L.gfs_test_voxel_sort_paths.argtypes = [vp, vp]
             L.gfs_test_wave_std_sort.argtypes = [i, vp, i, vp]
             L.gfs_gicp_align_next.argtypes = [vp, vp, i, vp, C.POINTER(GicpConfig), C.POINTER(GicpResult)]
             L.gfs_gicp_align_next_batch_device.argtypes = [vp, vp, vp, i, i, vp, C.POINTER(GicpConfig), vp, vp]
@@ -708,6 +709,12 @@ class RegistrationGICP:
         perm = np.zeros(max(len(k), 1), np.uint32)
         _check(lib().gfs_test_voxel_sort(self.h, _p(k), len(k), _p(perm)), "gfs_test_voxel_sort")
         return perm[:len(k)].astype(np.int64)
+
+    def voxel_sort_paths(self):
+        """Test hook: leaf ranges of the last voxel sort on this handle by path -> dict(tie_free, harmless, replica)."""
+        out = np.zeros(3, np.int32)
+        _check(lib().gfs_test_voxel_sort_paths(self.h, _p(out)), "gfs_test_voxel_sort_paths")
+        return dict(tie_free=int(out[0]), harmless=int(out[1]), replica=int(out[2]))
 
     def RegisterNext(self, source_points, init_T_target_source=None, cfg=None):
         """Streaming form: the target is the source cloud of the previous call on this object (kept preprocessed in HBM), as in

@@ -99,11 +99,13 @@ __global__ __launch_bounds__(256) void k_voxel_keys(const float4* __restrict__ t
                                                     const int* __restrict__ nt, const int* __restrict__ ns,
                                                     int stride_pts, int P, double inv_leaf, double max_vox, u64* __restrict__ keys,
                                                     unsigned* __restrict__ idx, int* __restrict__ counts, int only,
-                                                    int* __restrict__ n_done4, int* __restrict__ n_heap, int* __restrict__ n_active4) {
+                                                    int* __restrict__ n_done4, int* __restrict__ n_heap, int* __restrict__ n_active4,
+                                                    int* __restrict__ leaf_paths) {
   const int c = blockIdx.y, pair = c >> 1, which = c & 1;
   // the first kernel of a call also zeroes the call's counters (round 6: three memset launches in front of it before): the done /
-  // left-over / gave-up counters, the per-cloud heap-range counts of the voxel sort, the active-pair counts of the LM rounds
+  // left-over / gave-up counters, the per-cloud heap-range and leaf-path counts of the voxel sort, the active-pair counts of the LM rounds
   if (blockIdx.x == 0 && threadIdx.x < 4) {
+    leaf_paths[4 * c + threadIdx.x] = 0;
     if (threadIdx.x == 0) n_heap[c] = 0;
     if (c == 0) {
       n_done4[threadIdx.x] = 0;
@@ -2962,6 +2964,8 @@ struct gfs_gicp {
   gfs::DevBuf<unsigned> d_val0, d_val1, d_ci0, d_ci1, d_ubegin, d_grid;
   gfs::DevBuf<unsigned> d_leaf;  // per cloud: (begin, end) of the < 1024-element ranges of the voxel sort (voxel_qsort.hpp)
   gfs::DevBuf<int> d_nleaf, d_nheap;
+  gfs::DevBuf<int> d_leaf_paths;  // per cloud: leaf ranges of the last voxel sort that ended {tie-free, with harmless ties, in the replay, -}
+  int sort_clouds = 0;            // clouds of the last voxel sort (gfs_test_voxel_sort_paths)
   gfs::DevBuf<unsigned> d_heap;  // per cloud: (begin, end) of the ranges that hit std::sort's depth limit (heap-sort fallback)
   int heap_cap = 0;
   // one launch per step of the LM state machine
@@ -3107,11 +3111,13 @@ static int voxel_qsort_leaves(gfs_gicp* h, int C2, int leaf_parts, hipStream_t s
                               const float4* in_even = nullptr, const float4* in_odd = nullptr, int stride_pts = 0) {
   const int P = h->P;
   GFS_LAUNCH("k_voxel_qsort_leaf", vqs::k_voxel_qsort_leaf<unsigned>, dim3(leaf_parts, C2), dim3(256), 0, s, h->d_keys0.p,
-             h->d_val0.p, h->d_kinfo1.p, h->d_leaf.p, h->d_nleaf.p, P, only, h->d_heap.p, h->d_nheap.p, h->heap_cap);
+             h->d_val0.p, h->d_kinfo1.p, h->d_leaf.p, h->d_nleaf.p, P, only, h->d_heap.p, h->d_nheap.p, h->heap_cap, in_even, in_odd, stride_pts,
+             h->d_leaf_paths.p);
   // (narrow_only: the caller knows, or will find out and come back, that no cloud has keys wider than 31 bits)
   if (!narrow_only)
     GFS_LAUNCH("k_voxel_qsort_leaf64", vqs::k_voxel_qsort_leaf<u64>, dim3(leaf_parts, C2), dim3(256), 0, s, h->d_keys0.p,
-               h->d_val0.p, h->d_kinfo1.p, h->d_leaf.p, h->d_nleaf.p, P, only, h->d_heap.p, h->d_nheap.p, h->heap_cap);
+               h->d_val0.p, h->d_kinfo1.p, h->d_leaf.p, h->d_nleaf.p, P, only, h->d_heap.p, h->d_nheap.p, h->heap_cap, in_even, in_odd, stride_pts,
+               h->d_leaf_paths.p);
   const int heap_parts = std::max(1, std::min(16, P / 4096));
   GFS_LAUNCH("k_voxel_qsort_heap", vqs::k_voxel_qsort_heap<unsigned>, dim3(heap_parts, C2), dim3(256), 0, s, h->d_keys0.p,
              h->d_val0.p, h->d_kinfo1.p, h->d_heap.p, h->d_nheap.p, h->heap_cap, P, only, in_even, in_odd, stride_pts);
@@ -3195,6 +3201,7 @@ int gfs_gicp_create(int device, int max_points, int max_batch, gfs_gicp** out) {
   A(h->d_leaf.alloc(C2 * P));
   A(h->d_nleaf.alloc(C2));
   A(h->d_nheap.alloc(C2));
+  A(h->d_leaf_paths.alloc(4 * C2));
   h->heap_cap = (int)(P / 8 + 2);  // ranges are disjoint and longer than 16 elements
   A(h->d_heap.alloc(C2 * (size_t)h->heap_cap));
   A(h->d_ck0.alloc(C2 * P));
@@ -3296,6 +3303,7 @@ static int gicp_attempt(gfs_gicp* h, const void* dev_target, const void* dev_nt,
     for (int k = 0; k < 16; k++) h->h_initT.p[16 * b + k] = init_T ? init_T[16 * b + k] : (k % 5 == 0 ? 1.0 : 0.0);
   // (no upload: k_gicp_init reads the poses out of the pinned buffer -- 128 bytes a pair -- and k_voxel_keys zeroes the counters)
   const int npts = std::min(stride_pts, P);
+  h->sort_clouds = C2;  // (k_voxel_keys zeroes the leaf-path counts of all of them, whichever sort follows)
   // The cell sort key gives the cell z 19 bits, y 20 and x (in 1 / kFine of a cell) 25: every coordinate of a voxel mean fits while
   // |coordinate| < 2^18 cells.  The voxel fields admit 10^6 leaves, which is less whenever cell >= 4 leaves (the reference's
   // 0.1 / 0.02 m); for a smaller ratio the admitted range shrinks to what the cell key can hold (>= 13 km at 0.05 m).
@@ -3303,7 +3311,7 @@ static int gicp_attempt(gfs_gicp* h, const void* dev_target, const void* dev_nt,
   // ---- preprocess_points x 2B (registration_helper.cpp:22-34)
   GFS_LAUNCH("k_voxel_keys", k_voxel_keys, dim3(gfs::div_up(npts, 256), C2), dim3(256), 0, s, in_even, in_odd, n_even, n_odd,
              stride_pts, P, prm.inv_leaf, max_vox, h->d_keys0.p, h->d_val0.p, h->d_counts.p, prm.only, h->d_ndone.p, h->d_nheap.p,
-             h->d_nactive.p);
+             h->d_nactive.p, h->d_leaf_paths.p);
   if (h->stable_voxel_order) {
     GFS_LAUNCH("k_radix_sort", k_radix_sort, dim3(C2), dim3(1024), 0, s, h->d_keys0.p, h->d_keys1.p, h->d_val0.p, h->d_val1.p,
                h->d_counts.p, P, h->d_which.p, h->d_kinfo1.p, prm.only, kCoordBits, 2 * kCoordBits);
@@ -3573,6 +3581,8 @@ int gfs_test_voxel_sort(gfs_gicp* h, const unsigned long long* keys, int n, unsi
   if (n) GFS_HIP(hipMemcpyAsync(h->d_val0.p, iota.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
   const int leaf_parts = std::max(1, std::min(64, P / 1024));  // x 4 waves: a wave per leaf for nearly every cloud (the longest leaf sets the time)
   GFS_HIP(hipMemsetAsync(h->d_nheap.p, 0, 2 * sizeof(int), s));
+  GFS_HIP(hipMemsetAsync(h->d_leaf_paths.p, 0, 2 * 4 * sizeof(int), s));
+  h->sort_clouds = 2;
   GFS_HIP(voxel_qsort_top(h, 2, s, -1, nullptr));
   {
     const int rc_leaf = voxel_qsort_leaves(h, 2, leaf_parts, s, -1, false);
@@ -3580,6 +3590,19 @@ int gfs_test_voxel_sort(gfs_gicp* h, const unsigned long long* keys, int n, unsi
   }
   if (n) GFS_HIP(hipMemcpyAsync(perm_out, h->d_val0.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
   GFS_HIP(hipStreamSynchronize(s));
+  return GFS_OK;
+}
+
+int gfs_test_voxel_sort_paths(gfs_gicp* h, int32_t out3[3]) {
+  GFS_REQUIRE(h && out3, GFS_ERR_INVALID_ARG, "gfs_test_voxel_sort_paths: invalid argument");
+  std::lock_guard<std::recursive_mutex> lk(h->mu);
+  GFS_HIP(hipSetDevice(h->device));
+  GFS_HIP(hipStreamSynchronize(h->stream));
+  std::vector<int> v((size_t)4 * std::max(h->sort_clouds, 1), 0);
+  if (h->sort_clouds) GFS_HIP(hipMemcpy(v.data(), h->d_leaf_paths.p, (size_t)4 * h->sort_clouds * sizeof(int), hipMemcpyDeviceToHost));
+  out3[0] = out3[1] = out3[2] = 0;
+  for (int c = 0; c < h->sort_clouds; c++)
+    for (int k = 0; k < 3; k++) out3[k] += v[4 * c + k];
   return GFS_OK;
 }
 

@@ -57,6 +57,30 @@ __device__ __forceinline__ int scan_1024(int v, int* s_wave /*16*/, int* total) 
   return base + incl - v;
 }
 
+// Cross-lane steps of the leaf sort as DPP moves (no index registers, no lane masks to keep alive across the leaf loop)
+template <int kCtrl>
+__device__ __forceinline__ unsigned dpp0(unsigned v) {  // lanes without a source read 0
+  return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, kCtrl, 0xf, 0xf, true);
+}
+__device__ __forceinline__ unsigned wave_or_u32(unsigned v) {  // all lanes active; the result is uniform
+  v |= dpp0<0xB1>(v);   // quad_perm:[1,0,3,2]
+  v |= dpp0<0x4E>(v);   // quad_perm:[2,3,0,1]
+  v |= dpp0<0x141>(v);  // row_half_mirror
+  v |= dpp0<0x140>(v);  // row_mirror: every row of 16 lanes holds its own OR
+  return (unsigned)(__builtin_amdgcn_readlane((int)v, 0) | __builtin_amdgcn_readlane((int)v, 16) |
+                    __builtin_amdgcn_readlane((int)v, 32) | __builtin_amdgcn_readlane((int)v, 48));
+}
+__device__ __forceinline__ unsigned wave_incl_scan_u32(unsigned v) {  // all lanes active
+  v += dpp0<0x111>(v);  // row_shr:1
+  v += dpp0<0x112>(v);  // row_shr:2
+  v += dpp0<0x114>(v);  // row_shr:4
+  v += dpp0<0x118>(v);  // row_shr:8: inclusive inside every row of 16 lanes
+  const unsigned t0 = (unsigned)__builtin_amdgcn_readlane((int)v, 15), t1 = (unsigned)__builtin_amdgcn_readlane((int)v, 31),
+                 t2 = (unsigned)__builtin_amdgcn_readlane((int)v, 47);
+  const int row = (threadIdx.x & 63) >> 4;
+  return v + (row == 0 ? 0u : row == 1 ? t0 : row == 2 ? t0 + t1 : t0 + t1 + t2);
+}
+
 __device__ __forceinline__ u64 med3(u64 a, u64 b, u64 c) {  // sort_omp.hpp:66-68 on the keys
   return a < b ? (b < c ? b : (a < c ? c : a)) : (a < c ? a : (b < c ? c : b));
 }
@@ -1211,24 +1235,158 @@ __global__ __launch_bounds__(1024) void k_voxel_qsort_top_lds(u64* keys_all, uns
 }
 
 // ------------------------------------------------------------------------------------------------
+// TieRule: when the order of equal keys inside a sorted range cannot change a voxel mean (k_voxel_qsort_leaf and
+// k_voxel_qsort_heap both decide with it).  What the order of a voxel's points decides downstream (k_voxel_reduce,
+// util/downsampling_omp.hpp:63-90) is (a) which of them fall on either side of a 1024-element block cut of the cloud's sorted
+// array and (b) the order in which their coordinates are added up in double precision.  If no tied voxel straddles a cut, and
+// the sums are exact whatever the order -- the coordinates are floats: a sum of up to 64 of them is exact in a double as long
+// as their binary exponents span less than 23 -- every order gives the reference's means bit for bit.
+// Every lane feeds its tied elements to add(); exact_sums() is then called by the whole wave.
+// (One exponent window for all three coordinates and all tied voxels of the range: coarser than needed, and still passed by
+// every depth-camera cloud -- |x|, |y| >= half a pixel's footprint, z >= the sensor's near limit.)
+// ------------------------------------------------------------------------------------------------
+struct TieRule {
+  bool bad = false;  // this lane saw a voxel whose order matters, or a coordinate that is inf / nan
+  int emin = 0x7fffffff, emax = -0x7fffffff;
+  // one point of a voxel with g > 1 points in the range, the first of them at position `first` of the cloud's sorted array;
+  // pt = that point (null: no point data, nothing is known about the sums).  Returns whether the voxel's order matters.
+  __device__ __forceinline__ bool add(int first, int g, const float4* pt) {
+    const bool matters = g > 64 || (first >> 10) != ((first + g - 1) >> 10);
+    bad = bad || matters;
+    if (pt) {
+      const float4 p = *pt;
+      const float co[3] = {p.x, p.y, p.z};
+#pragma unroll
+      for (int a = 0; a < 3; a++) {
+        const unsigned bits = __float_as_uint(co[a]) & 0x7fffffffu;
+        if (bits == 0) continue;                     // zeros add exactly
+        if (bits >= 0x7f800000u) bad = true;          // inf / nan: leave it to the exact order
+        const int e = max((int)(bits >> 23), 1);      // (subnormals share the smallest exponent)
+        emin = min(emin, e);
+        emax = max(emax, e);
+      }
+    }
+    return matters;
+  }
+  __device__ __forceinline__ bool exact_sums() {  // all lanes
+#pragma unroll
+    for (int ofs = 32; ofs > 0; ofs >>= 1) {
+      emin = min(emin, __shfl_xor(emin, ofs, 64));
+      emax = max(emax, __shfl_xor(emax, ofs, 64));
+    }
+    return emax < emin || emax - emin < 23;
+  }
+};
+
+// ------------------------------------------------------------------------------------------------
 // k_voxel_qsort_leaf<KT>: std::sort of every leaf range (< 1024 elements) by one wave, in LDS.  KT = unsigned when the
 // cloud's compacted keys fit 31 bits (kinfo[5] <= 31; the invalid key becomes 0xffffffff), else u64; clouds of the
 // other width are skipped (both instantiations are launched).
+//
+// The replay of libstdc++'s introsort exists to reproduce the reference's permutation of EQUAL keys.  The narrow instance
+// therefore first sorts the range's (key, position) pairs with a stable LSD radix sort over the bits in which the keys differ
+// (leaf_radix_sort) and looks at the neighbours in that order: without equal keys the sorted order is the only one, and with
+// equal keys that pass TieRule any order gives the same voxel means; such a range is final, ties in position order (the
+// convention of k_voxel_qsort_heap).  Only the other ranges -- and all ranges with ties when there are no point data
+// (GFS_GICP_VOXEL_TIES=exact, gfs_test_voxel_sort) -- run the replay, on the untouched input.
+// paths[4 c ..] counts the ranges of cloud c that ended tie-free / with harmless ties / in the replay.
 // ------------------------------------------------------------------------------------------------
+// Stable LSD radix sort of the positions 0 .. n - 1 (n < 1024) by K[position], one wave.  ia (holding the identity) and ib are
+// the two index buffers, bins [256] the running digit counts.  Digits are as wide as an even split of the varying bit span
+// [lb, hb] into the fewest passes of at most 8 bits asks for; a digit in which no key differs is skipped.  Per pass: every row of
+// 64 elements finds its equal-digit peers with one ballot a digit bit (rank among them = stable order inside the row), the last
+// peer moves the digit's running count on, and the element keeps (index, rank in its digit, digit) in one register; after the
+// exclusive scan of the digit counts everything is scattered.  Returns the buffer that holds the sorted order.
+__device__ __forceinline__ unsigned short* leaf_radix_sort(const unsigned* K, unsigned short* ia, unsigned short* ib,
+                                                           unsigned short* bins, int n, unsigned varying) {
+  const int lane = threadIdx.x & 63;
+  const int rows = (n + 63) >> 6;
+  if (varying == 0u) return ia;
+  const int lb = __builtin_ctz(varying), hb = 31 - __builtin_clz(varying);
+  const int nb = hb - lb + 1, passes = (nb + 7) >> 3, w = (nb + passes - 1) / passes;
+  unsigned short* src = ia;
+  unsigned short* dst = ib;
+  for (int pass = 0; pass < passes; pass++) {
+    const int shift = lb + pass * w, bits = min(w, hb + 1 - shift);
+    const unsigned dmask = (1u << bits) - 1u;
+    if (((varying >> shift) & dmask) == 0u) continue;  // uniform digit
+    for (int d = lane; d < 256; d += 64) bins[d] = 0;
+    VQS_WAVE_SYNC();
+    unsigned pk[16];  // index | rank inside the digit << 10 | digit << 20
+#pragma unroll
+    for (int r = 0; r < 16; r++) {
+      pk[r] = 0;
+      if (r < rows) {  // uniform
+        const int p = r * 64 + lane;
+        const bool valid = p < n;
+        const unsigned idx = valid ? (unsigned)src[p] : 0u;
+        const unsigned dg = valid ? ((K[idx] >> shift) & dmask) : 0u;
+        u64 peers = __ballot(valid);
+        for (int bit = 0; bit < bits; bit++) {
+          const bool set = (dg >> bit) & 1u;
+          const u64 bl = __ballot(set);
+          peers &= set ? bl : ~bl;
+        }
+        const int rank = __popcll(peers & lanemask_lt()), cnt = __popcll(peers);
+        const unsigned before = valid ? (unsigned)bins[dg] : 0u;
+        VQS_WAVE_SYNC();
+        if (valid && rank == cnt - 1) bins[dg] = (unsigned short)(before + cnt);
+        VQS_WAVE_SYNC();
+        pk[r] = idx | ((before + rank) << 10) | (dg << 20);
+      }
+    }
+    {  // exclusive scan of the 256 digit counts: four consecutive ones a lane
+      unsigned c4[4], sum = 0;
+#pragma unroll
+      for (int j = 0; j < 4; j++) {
+        c4[j] = bins[4 * lane + j];
+        sum += c4[j];
+      }
+      unsigned run = wave_incl_scan_u32(sum) - sum;
+      VQS_WAVE_SYNC();
+#pragma unroll
+      for (int j = 0; j < 4; j++) {
+        bins[4 * lane + j] = (unsigned short)run;
+        run += c4[j];
+      }
+      VQS_WAVE_SYNC();
+    }
+#pragma unroll
+    for (int r = 0; r < 16; r++) {
+      if (r < rows && r * 64 + lane < n) dst[bins[pk[r] >> 20] + ((pk[r] >> 10) & 1023u)] = (unsigned short)(pk[r] & 1023u);
+    }
+    VQS_WAVE_SYNC();
+    unsigned short* t = src;
+    src = dst;
+    dst = t;
+  }
+  return src;
+}
+
 // (l0 / l1, the stopper lists of a partition: only their first K + 1 <= 512 entries are ever read — pair k is swapped while
 // L_k < R_k, and 512 disjoint pairs do not fit a range of < 1024 elements.  The stack of pending parts lives in a register, entry k
 // in lane k.  With 4-byte keys that is 40 KB a workgroup: four workgroups a CU instead of three.)
 template <typename KT>
-struct LeafLds {
+struct alignas(8) LeafLds {
   KT K[4][1024];
   unsigned short Pm[4][1024], l0[4][512], l1[4][512], cl[4][1024];
 };
+// (the radix path keeps 64-bit masks in a wave's l0 slab)
+static_assert(offsetof(LeafLds<unsigned>, l0) % 8 == 0 && sizeof(unsigned short[512]) % 8 == 0, "l0 slabs must be 8-byte aligned");
 
+// (four workgroups a CU is what the narrow instance's 40 KB of LDS allow: kNarrowWaves holds its registers to that -- without it the
+// radix path's unrolled rows leave the kernel at 129 VGPRs and three workgroups; the u64 instances, bound by their LDS, get a minimum of one wave, which is the default and has no effect)
 template <typename KT>
-__global__ __launch_bounds__(256) void k_voxel_qsort_leaf(u64* keys_all, unsigned* vals_all,
+constexpr int kNarrowWaves = sizeof(KT) == 4 ? 4 : 1;
+template <typename KT>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kNarrowWaves<KT>))) void k_voxel_qsort_leaf(u64* keys_all, unsigned* vals_all,
                                                           const int* __restrict__ kinfo, const unsigned* __restrict__ leaf_all,
                                                           const int* __restrict__ nleaf, int P, int only,
-                                                          unsigned* __restrict__ heap_all, int* __restrict__ nheap, int heap_cap) {
+                                                          unsigned* __restrict__ heap_all, int* __restrict__ nheap, int heap_cap,
+                                                          const float4* __restrict__ pts_even, const float4* __restrict__ pts_odd,
+                                                          int stride_pts, int* __restrict__ paths) {
+  // pts_even / pts_odd: the input clouds of the even / odd slots as k_voxel_reduce reads them (null: ranges with equal keys get
+  // the exact permutation in every case)
   constexpr bool kNarrow = sizeof(KT) == 4;
   __shared__ LeafLds<KT> S;
   const int c = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -1248,6 +1406,7 @@ __global__ __launch_bounds__(256) void k_voxel_qsort_leaf(u64* keys_all, unsigne
   unsigned stk = 0;
   auto stk_pack = [](int lo, int hi, int depth) { return (unsigned)lo | ((unsigned)hi << 10) | ((unsigned)depth << 21); };
   const u64 lt = lanemask_lt();
+  int n_tiefree = 0, n_harmless = 0, n_replica = 0;  // this wave's ranges by the path they ended on (uniform)
   for (int l = blockIdx.x * 4 + wave; l < nl; l += gridDim.x * 4) {
     const int b = __builtin_amdgcn_readfirstlane((int)leaf[2 * l]), n = __builtin_amdgcn_readfirstlane((int)leaf[2 * l + 1]) - b;
     for (int p = lane; p < n; p += 64) {
@@ -1255,6 +1414,99 @@ __global__ __launch_bounds__(256) void k_voxel_qsort_leaf(u64* keys_all, unsigne
       K[p] = kNarrow ? (KT)(k == ~0ull ? 0xffffffffull : k) : (KT)k;
       Pm[p] = (unsigned short)p;
     }
+    if constexpr (kNarrow) {
+      VQS_WAVE_SYNC();
+      unsigned vor = 0u, vand = ~0u;
+      for (int p = lane; p < n; p += 64) {
+        const unsigned k = K[p];
+        vor |= k;
+        vand &= k;
+      }
+      const unsigned varying = wave_or_u32(vor) ^ ~wave_or_u32(~vand);
+      const unsigned short* so = leaf_radix_sort(K, Pm, cl, l0, n, varying);
+      // the heads of row r (64 positions of the sorted sequence) = its positions whose key differs from the one before (position
+      // 0, and every position from n on, count as such): the first elements of the groups of equal keys, kept as one 64-bit mask
+      // a row in the slab of the digit counts
+      const int rows = (n + 63) >> 6;
+      u64* hdm = reinterpret_cast<u64*>(l0);  // [17]
+      VQS_WAVE_SYNC();
+      if (lane < 17) hdm[lane] = ~0ull;
+      VQS_WAVE_SYNC();
+      bool ties = false;
+      {
+        unsigned last = 0u;  // the key before the row
+#pragma unroll 1
+        for (int r = 0; r < rows; r++) {
+          const int p = r * 64 + lane;
+          const bool valid = p < n;
+          const unsigned k = valid ? K[so[p]] : 0u;
+          unsigned prev = (unsigned)__builtin_amdgcn_update_dpp(0, (int)k, 0x138 /* wave_shr:1 */, 0xf, 0xf, false);
+          if (lane == 0) prev = last;
+          last = (unsigned)__builtin_amdgcn_readlane((int)k, 63);
+          const u64 hd = __ballot(!valid || p == 0 || k != prev);
+          if (lane == 0) hdm[r] = hd;
+          ties = ties || hd != ~0ull;
+        }
+      }
+      bool final_order = !ties;
+      VQS_WAVE_SYNC();
+      if (ties && (pts_even || pts_odd)) {
+        const float4* in = ((c & 1) ? pts_odd : pts_even);
+        TieRule tr;
+        tr.bad = in == nullptr;
+        const u64 le = lt | (1ull << lane);
+#pragma unroll 1
+        for (int r = 0; r < rows; r++) {
+          const int p = r * 64 + lane;
+          if (p < n) {
+            // the group's first element: the last head at or before this position; its end: the first head after it (looked for
+            // in this row and its neighbour: farther away means more than 64 equal keys)
+            const u64 hd = hdm[r], hd_before = hdm[r > 0 ? r - 1 : 0], hd_next = hdm[r + 1];
+            const u64 at = hd & le, after = hd & ~le;
+            int first = -1, end = -1;
+            if (at)
+              first = r * 64 + 63 - __clzll(at);
+            else if (r > 0 && hd_before)
+              first = (r - 1) * 64 + 63 - __clzll(hd_before);
+            if (after)
+              end = r * 64 + __builtin_ctzll(after);
+            else if (hd_next)
+              end = (r + 1) * 64 + __builtin_ctzll(hd_next);
+            const int g = (first < 0 || end < 0) ? 65 : end - first;
+            if (g > 1) tr.add(b + max(first, 0), g, in ? in + (size_t)(c >> 1) * stride_pts + va[b + so[p]] : nullptr);
+          }
+        }
+        const bool exact_sums = tr.exact_sums();
+        final_order = __ballot(tr.bad) == 0ull && exact_sums;
+        if (final_order) n_harmless++;
+      } else if (!ties) {
+        n_tiefree++;
+      }
+      if (final_order) {  // the range is rewritten in place, once every point index has been read
+        unsigned myv[16];
+#pragma unroll
+        for (int r = 0; r < 16; r++) {
+          const int p = r * 64 + lane;
+          myv[r] = (r < rows && p < n) ? va[b + so[p]] : 0u;
+        }
+        __threadfence_block();
+        VQS_WAVE_SYNC();
+#pragma unroll
+        for (int r = 0; r < 16; r++) {
+          const int p = r * 64 + lane;
+          if (r < rows && p < n) {
+            const unsigned k = K[so[p]];
+            ka[b + p] = k == 0xffffffffu ? ~0ull : (u64)k;
+            va[b + p] = myv[r];
+          }
+        }
+        VQS_WAVE_SYNC();
+        continue;
+      }
+      // the attempt is dropped: nothing has been written back, K is untouched, the positions start as the identity again
+      for (int p = lane; p < n; p += 64) Pm[p] = (unsigned short)p;
+    }
+    n_replica++;
     int lg = 0;
     for (int v = n; v > 1; v >>= 1) lg++;
     int sp = 0;
@@ -1515,6 +1767,11 @@ __global__ __launch_bounds__(256) void k_voxel_qsort_leaf(u64* keys_all, unsigne
     }
     VQS_WAVE_SYNC();
   }
+  if (lane == 0) {  // (a wave takes one or two ranges: a handful of atomics a cloud, each cloud on words of its own)
+    if (n_tiefree) atomicAdd(&paths[4 * c + 0], n_tiefree);
+    if (n_harmless) atomicAdd(&paths[4 * c + 1], n_harmless);
+    if (n_replica) atomicAdd(&paths[4 * c + 2], n_replica);
+  }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1528,8 +1785,10 @@ struct HeapLds {
   unsigned short Pm[4][1024], Rk[4][1024];
 };
 
+// (kNarrowWaves: with the tie rule behind TieRule's call the narrow instance compiles to 135 VGPRs, three waves a SIMD, unless it is
+// held to the four it had: 121 VGPRs then)
 template <typename KT>
-__global__ __launch_bounds__(256) void k_voxel_qsort_heap(u64* keys_all, unsigned* vals_all, const int* __restrict__ kinfo,
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kNarrowWaves<KT>))) void k_voxel_qsort_heap(u64* keys_all, unsigned* vals_all, const int* __restrict__ kinfo,
                                                           const unsigned* __restrict__ heap_all, const int* __restrict__ nheap,
                                                           int heap_cap, int P, int only, const float4* __restrict__ pts_even,
                                                           const float4* __restrict__ pts_odd, int stride_pts) {
@@ -1604,11 +1863,7 @@ __global__ __launch_bounds__(256) void k_voxel_qsort_heap(u64* keys_all, unsigne
           if (r * 64 + lane < n) K[rank[r]] = mykey[r];
       }
       if (replay && (pts_even || pts_odd)) {
-        // Equal keys exist (voxels with several points).  What their order decides downstream (k_voxel_reduce,
-        // util/downsampling_omp.hpp:63-90) is (a) which points of a voxel fall on either side of a 1024-element block cut and (b) the
-        // order in which a voxel's coordinates are added up in double precision.  If no tied voxel of this range straddles a cut,
-        // and the sums are exact whatever the order -- the coordinates are floats: a sum of up to 64 of them is exact in a double
-        // as long as their binary exponents span less than 23 -- every order gives the reference's means bit for bit, and the serial
+        // Equal keys exist (voxels with several points).  Where TieRule finds that their order cannot change a voxel mean, the serial
         // replay of the heap (~0.5 ms on one wave, with the rest of the chip waiting) is not needed: ties are ordered by position.
         const float4* in = ((c & 1) ? pts_odd : pts_even);
         int eqb[16], le[16];
@@ -1628,43 +1883,22 @@ __global__ __launch_bounds__(256) void k_voxel_qsort_heap(u64* keys_all, unsigne
               }
             }
         }
-        bool bad = in == nullptr;
+        TieRule tr;
+        tr.bad = in == nullptr;
         int below_bad = n;  // smallest rank among the voxels whose order does matter (they straddle a block cut)
-        int emin = 0x7fffffff, emax = -0x7fffffff;
 #pragma unroll
         for (int r = 0; r < 16; r++)
           if (r * 64 + lane < n) {
             const int g = le[r] - rank[r];  // points of this element's voxel in the range (the padding keys are larger than any key)
             if (g > 1) {
-              const int first = b + rank[r];
-              const bool matters = g > 64 || (first >> 10) != ((first + g - 1) >> 10);
-              bad = bad || matters;
+              const bool matters = tr.add(b + rank[r], g, in ? in + (size_t)(c >> 1) * stride_pts + va[b + r * 64 + lane] : nullptr);
               if (matters) below_bad = min(below_bad, rank[r]);
-              if (in) {
-                const float4 pt = in[(size_t)(c >> 1) * stride_pts + va[b + r * 64 + lane]];
-                const float co[3] = {pt.x, pt.y, pt.z};
-#pragma unroll
-                for (int a = 0; a < 3; a++) {
-                  const unsigned bits = __float_as_uint(co[a]) & 0x7fffffffu;
-                  if (bits == 0) continue;                     // zeros add exactly
-                  if (bits >= 0x7f800000u) bad = true;          // inf / nan: leave it to the replay
-                  const int e = max((int)(bits >> 23), 1);      // (subnormals share the smallest exponent)
-                  emin = min(emin, e);
-                  emax = max(emax, e);
-                }
-              }
             }
           }
 #pragma unroll
-        for (int ofs = 32; ofs > 0; ofs >>= 1) {
-          emin = min(emin, __shfl_xor(emin, ofs, 64));
-          emax = max(emax, __shfl_xor(emax, ofs, 64));
-          below_bad = min(below_bad, __shfl_xor(below_bad, ofs, 64));
-        }
-        // (one exponent window for all three coordinates and all tied voxels of the range: coarser than needed, and still passed
-        // by every depth-camera cloud -- |x|, |y| >= half a pixel's footprint, z >= the sensor's near limit)
-        const bool exact_sums = in != nullptr && (emax < emin || emax - emin < 23);
-        const bool harmless = __ballot(bad) == 0ull && exact_sums;
+        for (int ofs = 32; ofs > 0; ofs >>= 1) below_bad = min(below_bad, __shfl_xor(below_bad, ofs, 64));
+        const bool exact_sums = tr.exact_sums() && in != nullptr;
+        const bool harmless = __ballot(tr.bad) == 0ull && exact_sums;
         if (!harmless && exact_sums && below_bad < n) {
           // Some tied voxel does straddle a cut: its order is the heap's, and so is the order of everything popped before it (the
           // pops come out in descending key order).  But the replay can stop once that voxel has been popped: the ties left in the

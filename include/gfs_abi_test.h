@@ -38,6 +38,11 @@ int gfs_test_traffic(int device, int mode, long long n, long long table, int per
  * max_points caller keys (3 x 21-bit voxel fields, or all ones = invalid).  perm_out[i] = input index of the i-th
  * element of the sorted sequence. */
 int gfs_test_voxel_sort(gfs_gicp* h, const unsigned long long* keys, int n, unsigned* perm_out);
+/* GPU test hook: on which path the leaf ranges (< 1024 elements) of the handle's last voxel sort -- gfs_test_voxel_sort or the
+ * preprocessing of the last align call, all its clouds together -- ended (csrc/voxel_qsort.hpp k_voxel_qsort_leaf): out3 = {ranges
+ * without equal keys (any sort gives the reference's permutation), ranges whose equal keys cannot change a voxel mean (kept in
+ * position order), ranges that ran the libstdc++ introsort replica}.  Waits for the handle's stream. */
+int gfs_test_voxel_sort_paths(gfs_gicp* h, int32_t out3[3]);
 /* GPU test hook: the one-wave std::sort replica (csrc/wave_std_sort.hpp: the voxel sort's leaves, sort_omp.hpp:61, and the quadtree's
  * (size, x) list, ORBextractor.cc:697-698) on n <= 1024 caller keys; perm_out[i] = original index of the element left at position i. */
 int gfs_test_wave_std_sort(int device, const unsigned* keys, int n, unsigned short* perm_out);
