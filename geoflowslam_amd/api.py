@@ -1026,6 +1026,27 @@ class GmsMatcher:
         _check(lib().gfs_gms_inlier_mask(self.h, C.byref(P), 1, ptrs, _p(n)), "gfs_gms_inlier_mask")
         return mask[:len(q)].astype(bool), int(n[0])
 
+    def GetInlierMaskBatch(self, problems):
+        """problems: a list of (kp1, size1, kp2, size2, query_idx, train_idx), filtered in ONE gfs_gms_inlier_mask call
+        -> a list of (mask bool [n_matches], n_inliers)"""
+        B = len(problems)
+        P = (GmsProblem * B)()
+        ptrs = (C.c_void_p * B)()
+        keep, masks = [], []
+        for f, (kp1, size1, kp2, size2, query_idx, train_idx) in enumerate(problems):
+            kp1 = np.ascontiguousarray(kp1, KP_DTYPE)
+            kp2 = np.ascontiguousarray(kp2, KP_DTYPE)
+            q = np.ascontiguousarray(query_idx, np.int32)
+            t = np.ascontiguousarray(train_idx, np.int32)
+            P[f] = GmsProblem(len(kp1), len(kp2), kp1.ctypes.data, kp2.ctypes.data, int(size1[0]), int(size1[1]), int(size2[0]),
+                              int(size2[1]), len(q), q.ctypes.data, t.ctypes.data)
+            masks.append(np.zeros(max(len(q), 1), np.uint8))
+            ptrs[f] = masks[f].ctypes.data
+            keep.append((kp1, kp2, q, t))
+        n = np.zeros(max(B, 1), np.int32)
+        _check(lib().gfs_gms_inlier_mask(self.h, P, B, ptrs, _p(n)), "gfs_gms_inlier_mask")
+        return [(masks[f][:P[f].n_matches].astype(bool), int(n[f])) for f in range(B)]
+
     def inlier_mask_batch_device(self, d_kps1, d_n1, d_kps2, d_n2, B, kp_stride, d_train_idx, width, height, d_mask, d_counts,
                                  stream=None):
         _check(lib().gfs_gms_inlier_mask_batch_device(self.h, C.c_void_p(d_kps1), C.c_void_p(d_n1), C.c_void_p(d_kps2),
@@ -1456,6 +1477,14 @@ class Frame:
 
     __del__ = close
 
+    @staticmethod
+    def _rows_view(depth):
+        """-> (float32 map, row stride in elements): a view whose rows are contiguous is passed as it is (cv::Mat::step)"""
+        depth = np.asarray(depth, np.float32)
+        if depth.ndim != 2 or depth.strides[1] != 4 or depth.strides[0] % 4 or depth.strides[0] < depth.shape[1] * 4:
+            depth = np.ascontiguousarray(depth)
+        return depth, depth.strides[0] // 4
+
     def ConvertDepthToPointCloud(self, depth, downSample, fx, fy, cx, cy):
         depth = np.asarray(depth, np.float32)
         if depth.size == 0:
@@ -1469,14 +1498,14 @@ class Frame:
         return out[:n.value].copy()
 
     def ComputeStereoFromRGBD(self, kps, depth, bf, kps_un_x=None):
-        depth = np.ascontiguousarray(depth, np.float32)
+        depth, stride = self._rows_view(depth)
         kps = np.ascontiguousarray(kps)
         n = len(kps)
         ur = np.zeros(max(n, 1), np.float32)
         vd = np.zeros(max(n, 1), np.float32)
         unx = np.ascontiguousarray(kps_un_x, np.float32) if kps_un_x is not None else None
-        _check(lib().gfs_stereo_from_rgbd(self.h, _p(kps), _p(unx), n, _p(depth), depth.shape[0], depth.shape[1], depth.shape[1],
-                                          bf, _p(ur), _p(vd)), "gfs_stereo_from_rgbd")
+        _check(lib().gfs_stereo_from_rgbd(self.h, _p(kps), _p(unx), n, C.c_void_p(depth.ctypes.data), depth.shape[0], depth.shape[1],
+                                          stride, bf, _p(ur), _p(vd)), "gfs_stereo_from_rgbd")
         return ur[:n], vd[:n]
 
     def FrameRGBD(self, kps, depth, bf, downSample, fx, fy, cx, cy, kps_un_x=None, host_cloud=True, shape=None):
@@ -1484,10 +1513,10 @@ class Frame:
         590-623) in one call: gfs_frame_rgbd.  Returns (mvuRight, mvDepth, cloud or None, (dev_cloud, dev_count, stride, n)).
         depth=None (with shape=(rows, cols)): the depth map of the previous call, still on the device; downSample=0: no cloud."""
         if depth is not None:
-            depth = np.ascontiguousarray(depth, np.float32)
+            depth, row_stride = self._rows_view(depth)
             rows, cols = depth.shape
         else:
-            rows, cols = shape
+            (rows, cols), row_stride = shape, shape[1]
         kps = np.ascontiguousarray(kps)
         n = len(kps)
         ur = np.empty(max(n, 1), np.float32)
@@ -1497,7 +1526,8 @@ class Frame:
         out = np.empty((rows * cols // (downSample * downSample) + rows + cols, 4), np.float32) if want_cloud else None
         nc, stride = C.c_int(), C.c_int()
         dc, dn = C.c_void_p(), C.c_void_p()
-        _check(lib().gfs_frame_rgbd(self.h, _p(kps), _p(unx), n, _p(depth), rows, cols, cols, bf, downSample, fx, fy, cx, cy, _p(ur),
+        _check(lib().gfs_frame_rgbd(self.h, _p(kps), _p(unx), n, C.c_void_p(depth.ctypes.data) if depth is not None else None, rows, cols,
+                                    row_stride, bf, downSample, fx, fy, cx, cy, _p(ur),
                                     _p(vd), _p(out), len(out) if out is not None else 0, C.byref(nc), C.byref(dc), C.byref(dn),
                                     C.byref(stride)), "gfs_frame_rgbd")
         return ur[:n], vd[:n], (out[:nc.value] if out is not None else None), (dc.value, dn.value, stride.value, nc.value)
@@ -1511,3 +1541,12 @@ class Frame:
         _check(lib().gfs_depth_to_cloud_batch_device(self.h, C.c_void_p(d_depth), B, rows, cols, ds, fx, fy, cx, cy,
                                                      C.c_void_p(d_out), stride_pts, C.c_void_p(d_counts),
                                                      C.c_void_p(stream) if stream else None), "gfs_depth_to_cloud_batch_device")
+
+    def stereo_from_rgbd_batch_device(self, d_kps, d_kps_un_x, d_counts, B, kp_stride, d_depth, rows, cols, bf, d_u_right, d_depth_out,
+                                      stream=None):
+        """ComputeStereoFromRGBD for B frames in HBM: key-points [B, kp_stride] (counts[b] valid), depth maps [B, rows, cols];
+        d_kps_un_x None / 0: the undistorted x is the key-point's own"""
+        _check(lib().gfs_stereo_from_rgbd_batch_device(self.h, C.c_void_p(d_kps), C.c_void_p(d_kps_un_x) if d_kps_un_x else None,
+                                                       C.c_void_p(d_counts), B, kp_stride, C.c_void_p(d_depth), rows, cols, float(bf),
+                                                       C.c_void_p(d_u_right), C.c_void_p(d_depth_out),
+                                                       C.c_void_p(stream) if stream else None), "gfs_stereo_from_rgbd_batch_device")
