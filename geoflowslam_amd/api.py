@@ -205,6 +205,79 @@ def local_points_result(P, R, keep):
                 n_to_match=int(R.n_to_match), n_searched=int(R.n_searched), nmatches=int(R.nmatches))
 
 
+FUSE_EXITS = ("neg_depth", "not_in_image", "too_near", "too_far", "view_angle", "empty_window", "no_candidate", "matched")  # GFS_FUSE_*
+
+
+class FusePoints(C.Structure):
+    _fields_ = [("n_mp", C.c_int32), ("mp_xw", C.c_void_p), ("mp_normal", C.c_void_p), ("mp_min_dist", C.c_void_p),
+                ("mp_max_dist", C.c_void_p), ("mp_desc", C.c_void_p)]
+
+
+class FuseKeyframe(C.Structure):
+    _fields_ = [("Tcw_q", C.c_float * 4), ("Tcw_t", C.c_float * 3), ("Ow", C.c_float * 3), ("fx", C.c_float), ("fy", C.c_float),
+                ("cx", C.c_float), ("cy", C.c_float), ("bf", C.c_float), ("min_x", C.c_float), ("max_x", C.c_float), ("min_y", C.c_float),
+                ("max_y", C.c_float), ("grid_w_inv", C.c_float), ("grid_h_inv", C.c_float), ("scale_factors", C.c_void_p),
+                ("inv_level_sigma2", C.c_void_p), ("n_levels", C.c_int32), ("log_scale_factor", C.c_float), ("th", C.c_float),
+                ("n_kp", C.c_int32), ("kps_un", C.c_void_p), ("u_right", C.c_void_p), ("desc", C.c_void_p), ("list", C.c_int32)]
+
+
+class FuseResult(C.Structure):
+    _fields_ = [("exit", C.c_void_p), ("best_idx", C.c_void_p), ("best_dist", C.c_void_p), ("level", C.c_void_p), ("n_matched", C.c_int32)]
+
+
+def fuse_structs(lists, keyframes):
+    """ctypes views of one gfs_fuse_search call (shared with the CPU restatement's tests: same layout).  lists: dicts with the keys
+    of gfs_fuse_points; keyframes: dicts with the keys of gfs_fuse_keyframe (kps_un = KP_DTYPE array; `list` defaults to 0)
+    -> (lists array, key frames array, results array, arrays kept alive).  The result arrays are pre-filled with a pattern no
+    output has."""
+    nl, B = len(lists), len(keyframes)
+    LL, KK, RR = (FusePoints * max(nl, 1))(), (FuseKeyframe * max(B, 1))(), (FuseResult * max(B, 1))()
+    keep = []
+    for l, pts in enumerate(lists):
+        a = dict(mp_xw=np.ascontiguousarray(pts["mp_xw"], np.float32).reshape(-1, 3),
+                 mp_normal=np.ascontiguousarray(pts["mp_normal"], np.float32).reshape(-1, 3),
+                 mp_min_dist=np.ascontiguousarray(pts["mp_min_dist"], np.float32),
+                 mp_max_dist=np.ascontiguousarray(pts["mp_max_dist"], np.float32),
+                 mp_desc=np.ascontiguousarray(pts["mp_desc"], np.uint8).reshape(-1, 32))
+        LL[l].n_mp = len(a["mp_xw"])
+        for name, v in a.items():
+            setattr(LL[l], name, v.ctypes.data)
+        keep.append(a)
+    for f, kf in enumerate(keyframes):
+        a = dict(scale_factors=np.ascontiguousarray(kf["scale_factors"], np.float32),
+                 inv_level_sigma2=np.ascontiguousarray(kf["inv_level_sigma2"], np.float32),
+                 kps_un=np.ascontiguousarray(kf["kps_un"], KP_DTYPE), u_right=np.ascontiguousarray(kf["u_right"], np.float32),
+                 desc=np.ascontiguousarray(kf["desc"], np.uint8).reshape(-1, 32))
+        K = KK[f]
+        for name, v in a.items():
+            setattr(K, name, v.ctypes.data)
+        for name in ("Tcw_q", "Tcw_t", "Ow"):
+            getattr(K, name)[:] = [float(np.float32(v)) for v in np.asarray(kf[name]).reshape(-1)]
+        for name in ("fx", "fy", "cx", "cy", "bf", "min_x", "max_x", "min_y", "max_y", "grid_w_inv", "grid_h_inv", "log_scale_factor", "th"):
+            setattr(K, name, float(np.float32(kf[name])))
+        K.n_levels = int(kf.get("n_levels", len(a["scale_factors"])))
+        K.n_kp = len(a["kps_un"])
+        K.list = int(kf.get("list", 0))
+        n = max(LL[K.list].n_mp, 1) if 0 <= K.list < nl else 1
+        out = dict(exit=np.full(n, 0xEE, np.uint8), best_idx=np.full(n, -9, np.int32), best_dist=np.full(n, -9, np.int32),
+                   level=np.full(n, -9, np.int32))
+        for name, v in out.items():
+            setattr(RR[f], name, v.ctypes.data)
+        RR[f].n_matched = -9
+        a.update(out)
+        keep.append(a)
+    return LL, KK, RR, keep
+
+
+def fuse_results(LL, KK, RR, keep, n_lists):
+    out = []
+    for f in range(len(keep) - n_lists):
+        a, n = keep[n_lists + f], LL[KK[f].list].n_mp
+        out.append(dict(exit=a["exit"][:n].copy(), best_idx=a["best_idx"][:n].copy(), best_dist=a["best_dist"][:n].copy(),
+                        level=a["level"][:n].copy(), n_matched=int(RR[f].n_matched)))
+    return out
+
+
 def sbp_map_struct(prob):
     P = SbpMapProblem()
     keep = dict(mp_proj=np.ascontiguousarray(prob["mp_proj"], np.float32).reshape(-1, 3),
@@ -340,7 +413,7 @@ ABI_SYMBOLS = [
     "gfs_pose_lidar_set_sum_order", "gfs_pose_lidar_optimize", "gfs_pose_lidar_fetch_edges",
     "gfs_gms_create", "gfs_gms_destroy", "gfs_gms_inlier_mask", "gfs_gms_inlier_mask_batch_device",
     "gfs_sbp_create", "gfs_sbp_destroy", "gfs_search_by_projection", "gfs_search_by_projection_map",
-    "gfs_sbp_reserve_local", "gfs_search_local_points", "gfs_test_glibc_logf",
+    "gfs_sbp_reserve_local", "gfs_search_local_points", "gfs_sbp_reserve_fuse", "gfs_fuse_search", "gfs_test_glibc_logf",
     "gfs_klt_create", "gfs_klt_destroy", "gfs_klt_layout", "gfs_klt_pyramid_create", "gfs_klt_pyramid_destroy",
     "gfs_klt_build_pyramid", "gfs_klt_build_pyramid_device", "gfs_klt_pyramid_download", "gfs_klt_track", "gfs_klt_fb_track",
     "gfs_klt_fb_track_device",
@@ -380,6 +453,8 @@ def lib():
         L.gfs_test_glibc_logf.argtypes = [i, vp, i, vp]
         L.gfs_sbp_reserve_local.argtypes = [vp, i]
         L.gfs_search_local_points.argtypes = [vp, C.POINTER(LocalPointsProblem), i, C.POINTER(LocalPointsResult)]
+        L.gfs_sbp_reserve_fuse.argtypes = [vp, i, i, i]
+        L.gfs_fuse_search.argtypes = [vp, C.POINTER(FusePoints), i, C.POINTER(FuseKeyframe), i, C.POINTER(FuseResult)]
         L.gfs_test_traffic.argtypes = [i, i, C.c_longlong, C.c_longlong, i, C.POINTER(C.c_longlong)]
         L.gfs_hamming256.argtypes = [vp, vp]
         L.gfs_matcher_create.argtypes = [i, i, i, i, C.POINTER(vp)]
@@ -1302,6 +1377,27 @@ class ProjectionMatcher:
             keeps.append(keep)
         _check(lib().gfs_search_local_points(self.h, PP, B, RR), "gfs_search_local_points")
         res = [local_points_result(PP[f], RR[f], keeps[f]) for f in range(B)]
+        return res[0] if single else res
+
+    def reserve_fuse(self, max_lists, max_points_per_list, max_keyframes):
+        """Workspace of fuse_search: up to max_lists point lists of up to max_points_per_list map points, searched in up to
+        max_keyframes key frames per call."""
+        _check(lib().gfs_sbp_reserve_fuse(self.h, int(max_lists), int(max_points_per_list), int(max_keyframes)), "gfs_sbp_reserve_fuse")
+        self.fuse_reserve = (int(max_lists), int(max_points_per_list), int(max_keyframes))
+
+    def fuse_search(self, lists, keyframes):
+        """The search of ORBmatcher::Fuse(pKF, vpMapPoints, th) (src/ORBmatcher.cc:1424-1526) for every listed map point, any number
+        of (list, key frame) pairs in one device call.  lists: one dict (keys of gfs_fuse_points) or a list of them; keyframes:
+        one dict (keys of gfs_fuse_keyframe, `list` = index of its point list) or a list -> per key frame a dict exit (index into
+        FUSE_EXITS), best_idx, best_dist, level, n_matched.  Raises GfsError (code GFS_ERR_CAPACITY) beyond the reserve."""
+        single = isinstance(keyframes, dict)
+        lists = [lists] if isinstance(lists, dict) else list(lists)
+        kfs = [keyframes] if single else list(keyframes)
+        if not hasattr(self, "fuse_reserve"):
+            self.reserve_fuse(max(len(lists), 1), max(max([len(p["mp_xw"]) for p in lists] + [64]), 64), max(len(kfs), 1))
+        LL, KK, RR, keep = fuse_structs(lists, kfs)
+        _check(lib().gfs_fuse_search(self.h, LL, len(lists), KK, len(kfs), RR), "gfs_fuse_search")
+        res = fuse_results(LL, KK, RR, keep, len(lists))
         return res[0] if single else res
 
 

@@ -18,6 +18,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
+#include <cstring>
 #include <list>
 #include <map>
 #include <memory>
@@ -31,6 +32,7 @@
 #include <vector>
 
 #include "../../include/gfs_abi.h"
+#include "../csrc/fuse_rule.hpp"
 
 namespace gfs_host {
 
@@ -1048,6 +1050,297 @@ class LocalPointsSearcher {
  private:
   gfs_sbp* h_ = nullptr;
   int reserve_ = 0;
+};
+
+// ------------------------------------------------------------------------------------------------------------------------
+// int ORBmatcher::Fuse(KeyFrame* pKF, const vector<MapPoint*>& vpMapPoints, const float th, const bool bRight = false)
+//                                                                                          reference src/ORBmatcher.cc:1378-1548
+// void LocalMapping::SearchInNeighbors(), from `ORBmatcher matcher;` on                    reference src/LocalMapping.cc:1179-1234
+// as real code around gfs_fuse_search.  Inside one Fuse call the per-point search (:1424-1526) reads only data the loop never
+// changes (the point's position, normal, distances and descriptor; the key frame's pose, intrinsics, key-points, mvuRight,
+// descriptors and level tables), and the loop changes only pointer state, which it reads before the search (:1411-1422) and after it
+// (:1529-1544).  So the search of every listed point is done on the device from the entry state, and the decisions are replayed
+// here in list order against the live pointer state:
+//   gather:  every non-null slot uploads GetWorldPos / GetNormal / mfMinDistance / mfMaxDistance / GetDescriptor; a null slot is
+//            flagged.  isBad() and IsInKeyFrame are NOT evaluated here.
+//   replay:  per key frame in the reference's order, per point in list order: skip if null, isBad() or IsInKeyFrame(pKF), all live;
+//            if the point's descriptor is no longer the uploaded one (pMPinKF->Replace(pMP) ends in
+//            pMP->ComputeDistinctiveDescriptors(), src/MapPoint.cc:303-351 -- it happens between the Fuse calls of
+//            SearchInNeighbors) this one (point, key frame) search is recomputed on the host with the same rule
+//            (gfs_fuse::search_point, csrc/fuse_rule.hpp); then the Replace / AddObservation / AddMapPoint block of :1529-1544.
+// Compile the translation unit that includes this with -ffp-contract=off (the host rule is the device's arithmetic).
+// Single-camera pinhole key frames only: NLeft != -1 or another camera model throws.
+//
+// KeyFrame and MapPoint are the reference's own classes, used through the members the reference functions use (pKF->NLeft, N, fx,
+// fy, cx, cy, mbf, mnMinX .. mnMaxY, mfGridElementWidthInv / HeightInv, mvScaleFactors, mvInvLevelSigma2, mnScaleLevels,
+// mfLogScaleFactor, mvuRight, mnId, GetMapPoint, AddMapPoint, GetMapPointMatches, UpdateConnections; pMP->isBad, IsInKeyFrame,
+// Observations, Replace, AddObservation, mnFuseCandidateForKF, ComputeDistinctiveDescriptors, UpdateNormalAndDepth).  `Access` as for
+// SearchLocalPoints (world_pos, normal, distances, descriptor of a MapPoint), plus for a key frame:
+//     static bool is_pinhole(const KeyFrame&);                                       // mpCamera->GetType() == CAM_PINHOLE
+//     static void pose(const KeyFrame&, float q[4], float t[3], float Ow[3]);        // GetPose(): unit_quaternion() (x, y, z, w),
+//                                                                                    // translation(); GetCameraCenter()
+//     static const gfs_keypoint* keys_un(const KeyFrame&);                           // mvKeysUn.data()
+//     static const uint8_t* descriptors(const KeyFrame&);                            // mDescriptors.data
+// `solve(lists, n_lists, kfs, B, results)` is the numeric core: FuseSearcher::solve below (gfs_fuse_search on the GPU).
+// ------------------------------------------------------------------------------------------------------------------------
+struct FuseList {  // one gathered point list
+  std::vector<uint8_t> present, desc;
+  std::vector<float> xw, nrm, dmin, dmax;
+  gfs_fuse_points view() const {
+    gfs_fuse_points p{};
+    p.n_mp = (int32_t)present.size();
+    p.mp_xw = xw.data();
+    p.mp_normal = nrm.data();
+    p.mp_min_dist = dmin.data();
+    p.mp_max_dist = dmax.data();
+    p.mp_desc = desc.data();
+    return p;
+  }
+};
+
+struct FuseOutputs {  // the result arrays of one (list, key frame) search
+  std::vector<uint8_t> exit;
+  std::vector<int32_t> best_idx, best_dist, level;
+  gfs_fuse_result view(size_t n) {
+    exit.assign(n + 1, 0);
+    best_idx.assign(n + 1, -1);
+    best_dist.assign(n + 1, 256);
+    level.assign(n + 1, 0);
+    gfs_fuse_result r{};
+    r.exit = exit.data();
+    r.best_idx = best_idx.data();
+    r.best_dist = best_dist.data();
+    r.level = level.data();
+    return r;
+  }
+};
+
+template <class Access, class MapPoint>
+void fuse_gather(const std::vector<MapPoint*>& vpMapPoints, FuseList& L) {
+  const size_t n = vpMapPoints.size();
+  L.present.assign(n, 0);
+  L.xw.assign(3 * n + 3, 0.0f);
+  L.nrm.assign(3 * n + 3, 0.0f);
+  L.dmin.assign(n + 1, 0.0f);
+  L.dmax.assign(n + 1, 0.0f);
+  L.desc.assign(32 * n + 32, 0);
+  for (size_t i = 0; i < n; i++) {
+    const MapPoint* pMP = vpMapPoints[i];
+    if (!pMP) continue;  // (its slot is searched with zeros and skipped on replay)
+    L.present[i] = 1;
+    Access::world_pos(pMP, &L.xw[3 * i]);
+    Access::normal(pMP, &L.nrm[3 * i]);
+    Access::distances(pMP, &L.dmin[i], &L.dmax[i]);
+    Access::descriptor(pMP, &L.desc[32 * i]);
+  }
+}
+
+template <class Access, class KeyFrame>
+gfs_fuse_keyframe fuse_keyframe(const KeyFrame& KF, float th, int list) {
+  if (KF.NLeft != -1 || !Access::is_pinhole(KF)) throw std::invalid_argument("Fuse: single-camera pinhole key frames only");
+  gfs_fuse_keyframe k{};
+  Access::pose(KF, k.Tcw_q, k.Tcw_t, k.Ow);
+  k.fx = KF.fx;
+  k.fy = KF.fy;
+  k.cx = KF.cx;
+  k.cy = KF.cy;
+  k.bf = KF.mbf;
+  k.min_x = KF.mnMinX;
+  k.max_x = KF.mnMaxX;
+  k.min_y = KF.mnMinY;
+  k.max_y = KF.mnMaxY;
+  k.grid_w_inv = KF.mfGridElementWidthInv;
+  k.grid_h_inv = KF.mfGridElementHeightInv;
+  k.scale_factors = KF.mvScaleFactors.data();
+  k.inv_level_sigma2 = KF.mvInvLevelSigma2.data();
+  k.n_levels = KF.mnScaleLevels;
+  k.log_scale_factor = KF.mfLogScaleFactor;
+  k.th = th;
+  k.n_kp = KF.N;
+  k.kps_un = Access::keys_un(KF);
+  k.u_right = KF.mvuRight.data();
+  k.desc = Access::descriptors(KF);
+  k.list = list;
+  return k;
+}
+
+// one (point, key frame) search on the host from the point's CURRENT descriptor (the replay's recompute path)
+inline gfs_fuse::PointResult fuse_search_point_host(const gfs_fuse_keyframe& k, const float* P, const float* Pn, float min_d, float max_d,
+                                                    const uint8_t* desc) {
+  if (k.n_levels < 1 || k.n_levels > 16) throw std::invalid_argument("Fuse: 1..16 pyramid levels");
+  gfs_fuse::KeyFrame K{};
+  for (int c = 0; c < 4; c++) K.q[c] = k.Tcw_q[c];
+  for (int c = 0; c < 3; c++) {
+    K.t[c] = k.Tcw_t[c];
+    K.Ow[c] = k.Ow[c];
+  }
+  K.fx = k.fx;
+  K.fy = k.fy;
+  K.cx = k.cx;
+  K.cy = k.cy;
+  K.bf = k.bf;
+  K.min_x = k.min_x;
+  K.max_x = k.max_x;
+  K.min_y = k.min_y;
+  K.max_y = k.max_y;
+  K.grid_w_inv = k.grid_w_inv;
+  K.grid_h_inv = k.grid_h_inv;
+  K.log_scale_factor = k.log_scale_factor;
+  K.th = k.th;
+  K.n_levels = k.n_levels;
+  K.n_kp = k.n_kp;
+  for (int c = 0; c < k.n_levels; c++) {
+    K.scale[c] = k.scale_factors[c];
+    K.inv_sigma2[c] = k.inv_level_sigma2[c];
+  }
+  std::vector<float> kx((size_t)k.n_kp + 1), ky((size_t)k.n_kp + 1);
+  std::vector<int32_t> oct((size_t)k.n_kp + 1);
+  for (int i = 0; i < k.n_kp; i++) {
+    kx[i] = k.kps_un[i].x;
+    ky[i] = k.kps_un[i].y;
+    oct[i] = k.kps_un[i].octave;
+    if (oct[i] < 0 || oct[i] >= k.n_levels) throw std::invalid_argument("Fuse: key-point octave outside the pyramid");
+  }
+  return gfs_fuse::search_point(K, P, Pn, min_d, max_d, desc, kx.data(), ky.data(), k.u_right, oct.data(), k.desc);
+}
+
+// The loop of :1408-1545 around the device's search results of (L, k).  recomputed: incremented per host recompute.
+template <class Access, class KeyFrame, class MapPoint>
+int fuse_replay(KeyFrame* pKF, const std::vector<MapPoint*>& vpMapPoints, const FuseList& L, const gfs_fuse_keyframe& k, const FuseOutputs& r,
+                int* recomputed = nullptr) {
+  int nFused = 0;
+  for (size_t i = 0; i < vpMapPoints.size(); i++) {
+    MapPoint* pMP = vpMapPoints[i];
+    if (!L.present[i]) continue;
+    if (pMP->isBad()) continue;
+    if (pMP->IsInKeyFrame(pKF)) continue;
+    int exit = r.exit[i], bestIdx = r.best_idx[i];
+    uint8_t now[32];
+    Access::descriptor(pMP, now);
+    if (std::memcmp(now, &L.desc[32 * i], 32) != 0) {  // the descriptor changed after the upload: this pair again, on the host
+      const gfs_fuse::PointResult o = fuse_search_point_host(k, &L.xw[3 * i], &L.nrm[3 * i], L.dmin[i], L.dmax[i], now);
+      exit = o.exit;
+      bestIdx = o.best_idx;
+      if (recomputed) ++*recomputed;
+    }
+    if (exit != GFS_FUSE_MATCHED) continue;
+    // If there is already a MapPoint replace otherwise add new measurement (:1529-1542)
+    MapPoint* pMPinKF = pKF->GetMapPoint(bestIdx);
+    if (pMPinKF) {
+      if (!pMPinKF->isBad()) {
+        if (pMPinKF->Observations() > pMP->Observations())
+          pMP->Replace(pMPinKF);
+        else
+          pMPinKF->Replace(pMP);
+      }
+    } else {
+      pMP->AddObservation(pKF, bestIdx);
+      pKF->AddMapPoint(pMP, bestIdx);
+    }
+    nFused++;
+  }
+  return nFused;
+}
+
+// ORBmatcher::Fuse(pKF, vpMapPoints, th): one list, one key frame
+template <class Access, class KeyFrame, class MapPoint, class Solve>
+int Fuse(Solve&& solve, KeyFrame* pKF, const std::vector<MapPoint*>& vpMapPoints, float th = 3.0f, int* recomputed = nullptr) {
+  const gfs_fuse_keyframe k = fuse_keyframe<Access>(*pKF, th, 0);
+  FuseList L;
+  fuse_gather<Access>(vpMapPoints, L);
+  const gfs_fuse_points lp = L.view();
+  FuseOutputs out;
+  gfs_fuse_result r = out.view(vpMapPoints.size());
+  check(solve(&lp, 1, &k, 1, &r), "gfs_fuse_search");
+  return fuse_replay<Access>(pKF, vpMapPoints, L, k, out, recomputed);
+}
+
+struct SearchInNeighborsCounts {
+  int fused_in_targets = 0, fused_in_current = 0, recomputed = 0;
+  bool aborted = false;
+};
+
+// LocalMapping::SearchInNeighbors from `ORBmatcher matcher;` (:1180) to its end: the current key frame's points in every target (ONE
+// device call: list 0 against all targets), the targets' points in the current key frame (a second call: one list, one key frame),
+// then the update of the current key frame's points and connections.  The caller keeps the target selection (:1131-1177);
+// pbAbortBA is mbAbortBA, looked at where the reference looks (:1191).
+template <class Access, class KeyFrame, class Solve>
+SearchInNeighborsCounts SearchInNeighborsFuse(Solve&& solve, KeyFrame* pCurrentKF, const std::vector<KeyFrame*>& vpTargetKFs,
+                                              const bool* pbAbortBA = nullptr, float th = 3.0f) {
+  using MapPoint = std::remove_pointer_t<typename decltype(pCurrentKF->GetMapPointMatches())::value_type>;
+  SearchInNeighborsCounts c;
+  if (pCurrentKF->NLeft != -1 || !Access::is_pinhole(*pCurrentKF)) throw std::invalid_argument("Fuse: single-camera pinhole key frames only");
+  // Search matches by projection from current KF in target KFs
+  std::vector<MapPoint*> vpMapPointMatches = pCurrentKF->GetMapPointMatches();
+  if (!vpTargetKFs.empty()) {
+    std::vector<gfs_fuse_keyframe> kfs;
+    for (KeyFrame* pKFi : vpTargetKFs) kfs.push_back(fuse_keyframe<Access>(*pKFi, th, 0));
+    FuseList L;
+    fuse_gather<Access>(vpMapPointMatches, L);
+    const gfs_fuse_points lp = L.view();
+    std::vector<FuseOutputs> outs(kfs.size());
+    std::vector<gfs_fuse_result> rs;
+    for (FuseOutputs& o : outs) rs.push_back(o.view(vpMapPointMatches.size()));
+    check(solve(&lp, 1, kfs.data(), (int)kfs.size(), rs.data()), "gfs_fuse_search");
+    for (size_t f = 0; f < kfs.size(); f++)
+      c.fused_in_targets += fuse_replay<Access>(vpTargetKFs[f], vpMapPointMatches, L, kfs[f], outs[f], &c.recomputed);
+  }
+  if (pbAbortBA && *pbAbortBA) {
+    c.aborted = true;
+    return c;
+  }
+  // Search matches by projection from target KFs in current KF
+  std::vector<MapPoint*> vpFuseCandidates;
+  vpFuseCandidates.reserve(vpTargetKFs.size() * vpMapPointMatches.size());
+  for (KeyFrame* pKFi : vpTargetKFs) {
+    const std::vector<MapPoint*> vpMapPointsKFi = pKFi->GetMapPointMatches();
+    for (MapPoint* pMP : vpMapPointsKFi) {
+      if (!pMP) continue;
+      if (pMP->isBad() || pMP->mnFuseCandidateForKF == pCurrentKF->mnId) continue;
+      pMP->mnFuseCandidateForKF = pCurrentKF->mnId;
+      vpFuseCandidates.push_back(pMP);
+    }
+  }
+  c.fused_in_current = Fuse<Access>(solve, pCurrentKF, vpFuseCandidates, th, &c.recomputed);
+  // Update points
+  vpMapPointMatches = pCurrentKF->GetMapPointMatches();
+  for (MapPoint* pMP : vpMapPointMatches) {
+    if (pMP && !pMP->isBad()) {
+      pMP->ComputeDistinctiveDescriptors();
+      pMP->UpdateNormalAndDepth();
+    }
+  }
+  // Update connections in covisibility graph
+  pCurrentKF->UpdateConnections();
+  return c;
+}
+
+// the numeric core of Fuse on the GPU: one handle, its reserve grown to the largest call seen
+class FuseSearcher {
+ public:
+  FuseSearcher(int max_kp = 4096, int device = 0) { check(gfs_sbp_create(device, 64, max_kp, 1, &h_), "gfs_sbp_create"); }
+  ~FuseSearcher() { gfs_sbp_destroy(h_); }
+  FuseSearcher(const FuseSearcher&) = delete;
+  FuseSearcher& operator=(const FuseSearcher&) = delete;
+  int solve(const gfs_fuse_points* lists, int n_lists, const gfs_fuse_keyframe* kfs, int B, gfs_fuse_result* results) {
+    int n = 0;
+    for (int l = 0; l < n_lists; l++) n = std::max(n, lists[l].n_mp);
+    if (n_lists > lists_ || n > points_ || B > kfs_) {  // the library refuses what exceeds the reserve (it never truncates): grow it first
+      const int nl = std::max(n_lists, lists_), np = std::max(std::max(n, 64), points_), nk = std::max(B, kfs_);
+      check(gfs_sbp_reserve_fuse(h_, nl, np, nk), "gfs_sbp_reserve_fuse");
+      lists_ = nl;
+      points_ = np;
+      kfs_ = nk;
+    }
+    return gfs_fuse_search(h_, lists, n_lists, kfs, B, results);
+  }
+  auto solver() {
+    return [this](const gfs_fuse_points* l, int nl, const gfs_fuse_keyframe* k, int B, gfs_fuse_result* r) { return solve(l, nl, k, B, r); };
+  }
+
+ private:
+  gfs_sbp* h_ = nullptr;
+  int lists_ = 0, points_ = 0, kfs_ = 0;
 };
 
 // Optimizer::PoseOptimization on a flattened frame (reference src/Optimizer.cc:763-1098)

@@ -494,6 +494,123 @@ def local_points_frame(seed, n_points=2000, n_cur=None, scale_factor=1.2, n_leve
                 cur_kps_un=kps, cur_u_right=cur_ur, cur_desc=cur_desc.reshape(-1, 32), cur_has_mp_obs=cur_obs)
 
 
+def fuse_problem(seed, n_points=1000, n_kp=1000, n_keyframes=1, scale_factor=1.2, n_levels=8, th=3.0, width=640, height=480):
+    """Synthetic input of ORBmatcher::Fuse(pKF, vpMapPoints, th) (reference src/ORBmatcher.cc:1378-1548) for one list of `n_points` map
+    points searched in `n_keyframes` key frames of `n_kp` key-points each, as gfs_fuse_search takes it (include/gfs_abi.h):
+    -> dict(lists=[points dict], keyframes=[key-frame dict, ...]).
+
+    The key frames are small motions of one pose.  Seven in ten points lie in front of all of them; each key frame sees most of
+    those again (key-point = projection + noise growing with the level, some beyond the chi2 gates; octave = the predicted level or
+    one below, a few two below or one above; descriptor = the point's with up to 18 bits flipped, a few unrelated; mvuRight
+    present for most, a few exactly 0).  One in eight of these key-points has a twin a pixel or a cell away with the same
+    descriptor (a Hamming tie).  Some points are bent away, too near or too far; the rest sit behind the cameras, off the image
+    or in view without a key-point, so every exit of the loop is taken.  The list is shuffled."""
+    rng = np.random.default_rng(seed + 15485863)
+    f32 = np.float32
+    fx = fy = f32(607.0)
+    cx, cy = f32(width / 2 - 0.5), f32(height / 2 - 0.5)
+    bf = f32(0.0745 * 607.0)
+    sf = float(scale_factor)
+    scale = np.cumprod(np.r_[1.0, np.full(n_levels - 1, sf)]).astype(np.float32)
+    inv_sigma2 = (f32(1) / (scale * scale)).astype(np.float32)
+    W, H = float(width), float(height)
+    R0 = _rot(0.03 * rng.normal(), 0.2 * rng.normal(), 0.03 * rng.normal())
+    t0 = np.array([0.2 * rng.normal(), 0.05 * rng.normal(), 0.1 * rng.normal()])
+    poses = []
+    for f in range(n_keyframes):
+        dR = _rot(*(np.deg2rad(0.8) * rng.normal(size=3))) if f else np.eye(3)
+        q = _quat_from_R(dR @ R0).astype(np.float32)
+        t = (dR @ t0 + (0.04 * rng.normal(size=3) if f else 0)).astype(np.float32)
+        Rq = _rot_from_quat(q.astype(np.float64))
+        poses.append((q, t, Rq, t.astype(np.float64), (-(Rq.T @ t.astype(np.float64))).astype(np.float32)))
+    R0q, t0q = poses[0][2], poses[0][3]
+    Ow0 = poses[0][4].astype(np.float64)
+    xw, nrm, dmin, dmax, desc, octs, scene = [], [], [], [], [], [], []
+
+    def unit(v):
+        return v / max(np.linalg.norm(v), 1e-12)
+
+    for i in range(n_points):
+        where = int(rng.choice(7, p=[0.7, 0.05, 0.05, 0.05, 0.05, 0.05, 0.05]))  # in view; behind; left; right; above; below; in view
+        z = rng.uniform(1.0, 7.0)
+        u, v = rng.uniform(30, W - 30), rng.uniform(30, H - 30)
+        if where == 1:
+            z = -rng.uniform(0.2, 5.0)
+        elif where == 2:
+            u = -rng.uniform(0.5, 300)
+        elif where == 3:
+            u = W + rng.uniform(0.5, 300)
+        elif where == 4:
+            v = -rng.uniform(0.5, 300)
+        elif where == 5:
+            v = H + rng.uniform(0.5, 300)
+        xc = np.array([(u - cx) / fx * abs(z), (v - cy) / fy * abs(z), z])
+        P = (R0q.T @ (xc - t0q)).astype(np.float32)
+        PO = P.astype(np.float64) - Ow0
+        dist = np.linalg.norm(PO)
+        kind = int(rng.choice(4, p=[0.82, 0.06, 0.06, 0.06])) if where == 0 else 0  # clean, bent away, too far, too near
+        side = unit(np.cross(PO, rng.normal(size=3)))
+        n = unit(0.3 * unit(PO) + side) if kind == 1 else unit(unit(PO) + rng.uniform(0.0, 1.2) * side)
+        o = int(rng.integers(0, n_levels))
+        mx = dist * sf ** (o - 0.5 + rng.uniform(-0.3, 0.3))
+        mn = mx / sf ** (n_levels - 1)
+        if kind == 2:
+            mx = dist / 1.5
+            mn = mx / sf ** (n_levels - 1)
+        if kind == 3:
+            mn = dist * 1.5
+        xw.append(P); nrm.append(n.astype(np.float32)); dmin.append(f32(mn)); dmax.append(f32(mx)); octs.append(o)
+        desc.append(rng.integers(0, 256, 32, dtype=np.uint8))
+        scene.append(where == 0)
+    order = rng.permutation(n_points)
+    take = lambda a, shape, dt: (np.array(a, dt).reshape(shape)[order] if n_points else np.zeros((0,) + shape[1:], dt))
+    pts = dict(mp_xw=take(xw, (-1, 3), np.float32), mp_normal=take(nrm, (-1, 3), np.float32), mp_min_dist=take(dmin, (-1,), np.float32),
+               mp_max_dist=take(dmax, (-1,), np.float32), mp_desc=take(desc, (-1, 32), np.uint8))
+    kp_dtype = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"), ("response", "<f4"), ("octave", "<i4"),
+                         ("class_id", "<i4")])
+    kfs = []
+    for f, (q, t, Rq, tq, Ow) in enumerate(poses):
+        cur = []  # (x, y, octave, u_right, desc)
+        for i in range(n_points):
+            if not scene[i] or rng.random() < 0.25:
+                continue
+            xc = Rq @ xw[i].astype(np.float64) + tq
+            if xc[2] <= 0.2:
+                continue
+            uc, vc = fx * xc[0] / xc[2] + cx, fy * xc[1] / xc[2] + cy
+            if not (0 <= uc < W and 0 <= vc < H):
+                continue
+            o = int(np.clip(octs[i] + rng.choice([0, -1, -2, 1], p=[0.5, 0.4, 0.05, 0.05]), 0, n_levels - 1))
+            sig = (0.5 if rng.random() < 0.8 else 2.0) * float(scale[o])
+            x2, y2 = f32(np.clip(uc + rng.normal(0, sig), 0, W - 1)), f32(np.clip(vc + rng.normal(0, sig), 0, H - 1))
+            d = desc[i].copy()
+            if rng.random() < 0.1:
+                d = rng.integers(0, 256, 32, dtype=np.uint8)
+            else:
+                flip = rng.choice(256, int(rng.integers(0, 19)), replace=False)
+                np.bitwise_xor.at(d, flip // 8, (1 << (flip % 8)).astype(np.uint8))
+            r = rng.random()
+            ur = f32(x2 - bf / xc[2] + rng.normal(0, sig)) if r < 0.8 else (f32(0) if r < 0.83 else f32(-1))
+            cur.append((x2, y2, o, ur, d))
+            if rng.random() < 0.125:  # a twin with the same descriptor: a pixel away, or in the next grid column
+                dx = 1.0 if rng.random() < 0.5 else float(rng.choice([-1, 1])) * 0.6 * W / 64
+                cur.append((f32(np.clip(x2 + dx, 0, W - 1)), y2, o, ur, d.copy()))
+        order = rng.permutation(len(cur))
+        cur = [cur[i] for i in order][:n_kp]
+        while len(cur) < n_kp:
+            cur.append((f32(rng.uniform(0, W)), f32(rng.uniform(0, H)), int(rng.integers(0, n_levels)),
+                        f32(rng.uniform(1, W)) if rng.random() < 0.5 else f32(-1), rng.integers(0, 256, 32, dtype=np.uint8)))
+        kps = np.zeros(len(cur), kp_dtype)
+        kps["x"], kps["y"], kps["octave"] = [c[0] for c in cur], [c[1] for c in cur], [c[2] for c in cur]
+        kps["size"], kps["class_id"] = 31.0, -1
+        kfs.append(dict(Tcw_q=q, Tcw_t=t, Ow=Ow, fx=fx, fy=fy, cx=cx, cy=cy, bf=bf, min_x=f32(0), max_x=f32(W), min_y=f32(0), max_y=f32(H),
+                        grid_w_inv=f32(64) / f32(W), grid_h_inv=f32(48) / f32(H), scale_factors=scale, inv_level_sigma2=inv_sigma2,
+                        n_levels=n_levels, log_scale_factor=f32(np.log(f32(sf))), th=f32(th), kps_un=kps,
+                        u_right=np.array([c[3] for c in cur], np.float32),
+                        desc=np.array([c[4] for c in cur], np.uint8).reshape(-1, 32), list=0))
+    return dict(lists=[pts], keyframes=kfs)
+
+
 def _rot_from_quat(q):
     x, y, z, w = q / np.linalg.norm(q)
     return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)],

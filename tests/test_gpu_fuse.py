@@ -1,0 +1,118 @@
+"""gfs_fuse_search (k_fuse, geoflowslam_amd/csrc/sbp.hip) on the MI355X against the sequential CPU restatement
+(tests/host/fuse_restatement.cpp): bit equality of exit, best index, best distance and level, no tolerance."""
+import numpy as np
+import pytest
+
+import fuse_support as FS
+from geoflowslam_amd import synth
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def matcher(gpu_api):
+    m = gpu_api.ProjectionMatcher(max_last=64, max_cur=4096, max_batch=1)
+    m.reserve_fuse(3, 1024, 8)
+    yield m
+    m.close()
+
+
+@pytest.mark.parametrize("n_mp,n_kp", FS.CASES)
+def test_every_wave_and_workgroup_edge(matcher, n_mp, n_kp):
+    prob, want = FS.problem(n_mp, n_kp)
+    got = matcher.fuse_search(prob["lists"], prob["keyframes"])
+    FS.assert_equal(got, want, (n_mp, n_kp))
+    assert len(got[0]["exit"]) == n_mp
+    if n_mp >= 255 and n_kp == 500:
+        assert got[0]["n_matched"] > 0 and (np.bincount(got[0]["exit"], minlength=8) > 0).sum() >= 7
+
+
+def test_full_key_point_table(matcher):
+    prob, want = FS.problem(600, 4096)
+    FS.assert_equal(matcher.fuse_search(prob["lists"], prob["keyframes"]), want, "4096 key-points")
+    assert want[0]["n_matched"] > 0
+
+
+def test_one_list_in_five_key_frames(matcher):
+    prob, want = FS.five_keyframes()
+    got = matcher.fuse_search(prob["lists"], prob["keyframes"])
+    FS.assert_equal(got, want, "batch of five")
+    assert len({o["exit"].tobytes() for o in got}) == 5  # five different searches
+    for f, kf in enumerate(prob["keyframes"]):  # ... and each equals its own single call
+        FS.assert_equal([matcher.fuse_search(prob["lists"], kf)], [got[f]], ("single", f))
+
+
+def test_two_lists_of_different_lengths(matcher):
+    prob, want = FS.two_lists()
+    got = matcher.fuse_search(prob["lists"], prob["keyframes"])
+    FS.assert_equal(got, want, "two lists")
+    assert [len(o["exit"]) for o in got] == [777, 130, 777, 130, 777]
+
+
+def test_constructed_points(matcher):
+    prob, labels = FS.constructed()
+    got = matcher.fuse_search(prob["lists"], prob["keyframes"])
+    FS.check_constructed(prob, labels, got)
+    FS.assert_equal(got, FS.restate(prob), "constructed")
+
+
+def _refused(gpu_api, m, lists, kfs, code):
+    with pytest.raises(gpu_api.GfsError) as e:
+        m.fuse_search(lists, kfs)
+    assert e.value.code == code, (e.value.code, str(e.value))
+
+
+def test_refusals_leave_the_handle_usable(gpu_api):
+    """One above each reserve -> GFS_ERR_CAPACITY; 17 levels, a `list` index out of range, a NULL array -> GFS_ERR_INVALID_ARG.
+    Nothing is truncated, and after every refusal the previous call gives identical bytes."""
+    CAP, INV = -4, -1
+    hdr = open(FS.os.path.join(FS.ROOT, "include", "gfs_abi.h")).read()
+    assert "GFS_ERR_INVALID_ARG = -1," in hdr and "GFS_ERR_CAPACITY = -4," in hdr
+    m = gpu_api.ProjectionMatcher(max_last=64, max_cur=512, max_batch=1)
+    before = gpu_api.ProjectionMatcher(max_last=64, max_cur=512, max_batch=1)
+    prob, want = FS.two_lists()  # 2 lists (777 and 130 points), 5 key frames of 500 / 300 key-points
+    m.reserve_fuse(2, 777, 5)
+    base = m.fuse_search(prob["lists"], prob["keyframes"])
+    FS.assert_equal(base, want, "at the reserve exactly")
+
+    def again(what):
+        got = m.fuse_search(prob["lists"], prob["keyframes"])
+        for g, b in zip(got, base):
+            assert all(FS.same_bits(g[k], b[k]) for k in ("exit", "best_idx", "best_dist", "level")) and g["n_matched"] == b["n_matched"], what
+
+    big = synth.fuse_problem(603, n_points=778, n_kp=100, n_keyframes=1)
+    _refused(gpu_api, m, [big["lists"][0], prob["lists"][1]], prob["keyframes"], CAP)  # a list one longer than the reserve
+    again("long list")
+    _refused(gpu_api, m, prob["lists"] + prob["lists"][1:], prob["keyframes"], CAP)     # three lists
+    again("lists")
+    _refused(gpu_api, m, prob["lists"], prob["keyframes"] + prob["keyframes"][:1], CAP)  # six key frames
+    again("key frames")
+    wide = synth.fuse_problem(604, n_points=50, n_kp=513, n_keyframes=1)["keyframes"][0]
+    _refused(gpu_api, m, prob["lists"], prob["keyframes"][:4] + [wide], CAP)            # 513 key-points, max_cur = 512
+    again("key-points")
+    kf = prob["keyframes"][0]
+    lv17 = dict(kf, n_levels=17, scale_factors=np.ones(17, np.float32), inv_level_sigma2=np.ones(17, np.float32))
+    _refused(gpu_api, m, prob["lists"], [lv17], INV)
+    again("17 levels")
+    _refused(gpu_api, m, prob["lists"], [dict(kf, n_levels=0)], INV)
+    for bad_list in (-1, 2):
+        _refused(gpu_api, m, prob["lists"], [dict(kf, list=bad_list)], INV)
+    again("list index")
+    LL, KK, RR, keep = gpu_api.fuse_structs(prob["lists"], prob["keyframes"])
+    LL[1].mp_normal = None
+    rc = gpu_api.lib().gfs_fuse_search(m.h, LL, 2, KK, 5, RR)
+    assert rc == INV
+    LL, KK, RR, keep = gpu_api.fuse_structs(prob["lists"], prob["keyframes"])
+    RR[3].best_dist = None
+    assert gpu_api.lib().gfs_fuse_search(m.h, LL, 2, KK, 5, RR) == INV
+    KK[2].u_right = None
+    assert gpu_api.lib().gfs_fuse_search(m.h, LL, 2, KK, 5, RR) == INV
+    again("NULL arrays")
+    # a handle that never reserved refuses, and its other entry points are as before
+    LL, KK, RR, keep = gpu_api.fuse_structs(prob["lists"], prob["keyframes"])
+    assert gpu_api.lib().gfs_fuse_search(before.h, LL, 2, KK, 5, RR) == CAP
+    p = synth.sbp_pair(3, n_points=60, n_extra_cur=40)
+    a, b = before.SearchByProjection(p), m.SearchByProjection(p)
+    assert a[1] == b[1] and FS.same_bits(a[0], b[0])
+    m.close()
+    before.close()
