@@ -278,6 +278,107 @@ def fuse_results(LL, KK, RR, keep, n_lists):
     return out
 
 
+TRI_EXITS = ("no_match", "low_parallax", "svd_w_zero", "unproject_failed", "behind_1", "behind_2", "reproj_1", "reproj_2", "zero_dist", "far",
+             "scale", "created")  # GFS_TRI_*
+
+
+class TriKeyframe(C.Structure):
+    _fields_ = [("Tcw", C.c_float * 12), ("Ow", C.c_float * 3), ("Rwc", C.c_float * 9), ("twc", C.c_float * 3), ("fx", C.c_float),
+                ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("invfx", C.c_float), ("invfy", C.c_float), ("mbf", C.c_float),
+                ("mb", C.c_float), ("scale_factors", C.c_void_p), ("level_sigma2", C.c_void_p), ("n_levels", C.c_int32), ("n_kp", C.c_int32),
+                ("kps_un", C.c_void_p), ("kps", C.c_void_p), ("u_right", C.c_void_p), ("depth", C.c_void_p), ("desc", C.c_void_p),
+                ("has_mp", C.c_void_p), ("n_nodes", C.c_int32), ("node_id", C.c_void_p), ("node_start", C.c_void_p), ("feat_idx", C.c_void_p)]
+
+
+class TriNeighbour(C.Structure):
+    _fields_ = [("kf", TriKeyframe), ("ep", C.c_float * 2), ("F12", C.c_float * 9)]
+
+
+class TriProblem(C.Structure):
+    _fields_ = [("cur", TriKeyframe), ("neighbours", C.POINTER(TriNeighbour)), ("n_neighbours", C.c_int32), ("only_stereo", C.c_int32),
+                ("coarse", C.c_int32), ("check_orientation", C.c_int32), ("inertial", C.c_int32), ("far_points", C.c_int32),
+                ("th_far_points", C.c_float), ("ratio_factor", C.c_float)]
+
+
+class TriResult(C.Structure):
+    _fields_ = [("match12", C.c_void_p), ("exit", C.c_void_p), ("x3d", C.c_void_p), ("point_stereo", C.c_void_p), ("n_matches", C.c_int32),
+                ("n_created", C.c_int32)]
+
+
+def _tri_keyframe(K, kf, keep):
+    a = dict(scale_factors=np.ascontiguousarray(kf["scale_factors"], np.float32), level_sigma2=np.ascontiguousarray(kf["level_sigma2"], np.float32),
+             kps_un=np.ascontiguousarray(kf["kps_un"], KP_DTYPE), kps=np.ascontiguousarray(kf["kps"], KP_DTYPE),
+             u_right=np.ascontiguousarray(kf["u_right"], np.float32), depth=np.ascontiguousarray(kf["depth"], np.float32),
+             desc=np.ascontiguousarray(kf["desc"], np.uint8).reshape(-1, 32), has_mp=np.ascontiguousarray(kf["has_mp"], np.uint8),
+             node_id=np.ascontiguousarray(kf["node_id"], np.int32), node_start=np.ascontiguousarray(kf["node_start"], np.int32),
+             feat_idx=np.ascontiguousarray(kf["feat_idx"], np.int32))
+    for name, v in a.items():
+        setattr(K, name, v.ctypes.data)
+    for name in ("Tcw", "Ow", "Rwc", "twc"):
+        getattr(K, name)[:] = [float(np.float32(v)) for v in np.asarray(kf[name]).reshape(-1)]
+    for name in ("fx", "fy", "cx", "cy", "invfx", "invfy", "mbf", "mb"):
+        setattr(K, name, float(np.float32(kf[name])))
+    K.n_levels = int(kf.get("n_levels", len(a["scale_factors"])))
+    K.n_kp = len(a["kps_un"])
+    K.n_nodes = len(a["node_id"])
+    keep.append(a)
+
+
+def tri_structs(problems):
+    """ctypes views of one gfs_create_new_map_points call (shared with the CPU restatement's tests: same layout).  problems: dicts
+    with `cur` (keys of gfs_tri_keyframe; kps_un / kps = KP_DTYPE arrays), `neighbours` (the same keys plus ep, F12) and the flags of
+    gfs_tri_problem -> (problems array, array of result pointers, arrays kept alive).  The result arrays are pre-filled with a pattern
+    no output has."""
+    B = len(problems)
+    PP, RP = (TriProblem * max(B, 1))(), (C.POINTER(TriResult) * max(B, 1))()
+    keep = []
+    for b, prob in enumerate(problems):
+        P, nbs = PP[b], list(prob["neighbours"])
+        _tri_keyframe(P.cur, prob["cur"], keep)
+        NN, RR = (TriNeighbour * max(len(nbs), 1))(), (TriResult * max(len(nbs), 1))()
+        n, outs = max(P.cur.n_kp, 1), []
+        for i, nb in enumerate(nbs):
+            _tri_keyframe(NN[i].kf, nb, keep)
+            NN[i].ep[:] = [float(np.float32(v)) for v in np.asarray(nb["ep"]).reshape(-1)]
+            NN[i].F12[:] = [float(np.float32(v)) for v in np.asarray(nb["F12"]).reshape(-1)]
+            out = dict(match12=np.full(n, -9, np.int32), exit=np.full(n, 0xEE, np.uint8), x3d=np.full((n, 3), np.nan, np.float32),
+                       point_stereo=np.full(n, 0xEE, np.uint8))
+            for name, v in out.items():
+                setattr(RR[i], name, v.ctypes.data)
+            RR[i].n_matches = RR[i].n_created = -9
+            outs.append(out)
+        P.neighbours, P.n_neighbours = NN, len(nbs)
+        RP[b] = RR
+        for name in ("only_stereo", "coarse", "check_orientation", "inertial", "far_points"):
+            setattr(P, name, int(bool(prob.get(name, False))))
+        P.th_far_points = float(np.float32(prob.get("th_far_points", 0.0)))
+        P.ratio_factor = float(np.float32(prob["ratio_factor"]))
+        keep.append((NN, RR, outs))
+    return PP, RP, keep
+
+
+def tri_results(PP, RP, keep, B):
+    """-> per problem a list with one dict per neighbour: match12, exit (index into TRI_EXITS), x3d, point_stereo, n_matches, n_created."""
+    res, blocks = [], [k for k in keep if isinstance(k, tuple)]
+    for b in range(B):
+        NN, RR, outs = blocks[b]
+        n = PP[b].cur.n_kp
+        res.append([dict(match12=o["match12"][:n].copy(), exit=o["exit"][:n].copy(), x3d=o["x3d"][:n].copy(),
+                         point_stereo=o["point_stereo"][:n].copy(), n_matches=int(RR[i].n_matches), n_created=int(RR[i].n_created))
+                    for i, o in enumerate(outs)])
+    return res
+
+
+def tri_candidate_pairs(prob):
+    """Sum of n1 * n2 over the common nodes of all neighbours of a problem (what gfs_sbp_reserve_triangulation bounds)."""
+    cur, total = prob["cur"], 0
+    n1 = dict(zip(np.asarray(cur["node_id"]).tolist(), np.diff(np.asarray(cur["node_start"])).tolist()))
+    for nb in prob["neighbours"]:
+        for nid, n2 in zip(np.asarray(nb["node_id"]).tolist(), np.diff(np.asarray(nb["node_start"])).tolist()):
+            total += n1.get(nid, 0) * n2
+    return total
+
+
 def sbp_map_struct(prob):
     P = SbpMapProblem()
     keep = dict(mp_proj=np.ascontiguousarray(prob["mp_proj"], np.float32).reshape(-1, 3),
@@ -414,6 +515,7 @@ ABI_SYMBOLS = [
     "gfs_gms_create", "gfs_gms_destroy", "gfs_gms_inlier_mask", "gfs_gms_inlier_mask_batch_device",
     "gfs_sbp_create", "gfs_sbp_destroy", "gfs_search_by_projection", "gfs_search_by_projection_map",
     "gfs_sbp_reserve_local", "gfs_search_local_points", "gfs_sbp_reserve_fuse", "gfs_fuse_search", "gfs_test_glibc_logf",
+    "gfs_sbp_reserve_triangulation", "gfs_create_new_map_points",
     "gfs_klt_create", "gfs_klt_destroy", "gfs_klt_layout", "gfs_klt_pyramid_create", "gfs_klt_pyramid_destroy",
     "gfs_klt_build_pyramid", "gfs_klt_build_pyramid_device", "gfs_klt_pyramid_download", "gfs_klt_track", "gfs_klt_fb_track",
     "gfs_klt_fb_track_device",
@@ -455,6 +557,8 @@ def lib():
         L.gfs_search_local_points.argtypes = [vp, C.POINTER(LocalPointsProblem), i, C.POINTER(LocalPointsResult)]
         L.gfs_sbp_reserve_fuse.argtypes = [vp, i, i, i]
         L.gfs_fuse_search.argtypes = [vp, C.POINTER(FusePoints), i, C.POINTER(FuseKeyframe), i, C.POINTER(FuseResult)]
+        L.gfs_sbp_reserve_triangulation.argtypes = [vp, i, C.c_int64]
+        L.gfs_create_new_map_points.argtypes = [vp, C.POINTER(TriProblem), i, C.POINTER(C.POINTER(TriResult))]
         L.gfs_test_traffic.argtypes = [i, i, C.c_longlong, C.c_longlong, i, C.POINTER(C.c_longlong)]
         L.gfs_hamming256.argtypes = [vp, vp]
         L.gfs_matcher_create.argtypes = [i, i, i, i, C.POINTER(vp)]
@@ -1398,6 +1502,26 @@ class ProjectionMatcher:
         LL, KK, RR, keep = fuse_structs(lists, kfs)
         _check(lib().gfs_fuse_search(self.h, LL, len(lists), KK, len(kfs), RR), "gfs_fuse_search")
         res = fuse_results(LL, KK, RR, keep, len(lists))
+        return res[0] if single else res
+
+    def reserve_triangulation(self, max_neighbours, max_candidate_pairs):
+        """Workspace of create_new_map_points: up to max_neighbours neighbour key frames per problem, and up to max_candidate_pairs
+        for the sum of n1 * n2 over the common vocabulary nodes of all neighbours of one problem."""
+        _check(lib().gfs_sbp_reserve_triangulation(self.h, int(max_neighbours), int(max_candidate_pairs)), "gfs_sbp_reserve_triangulation")
+        self.tri_reserve = (int(max_neighbours), int(max_candidate_pairs))
+
+    def create_new_map_points(self, problems):
+        """LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:846-1100) for one problem dict or a list of them (tri_structs), one
+        device call: per problem a list with one dict per neighbour, in the loop's order: match12 (SearchForTriangulation's pairs),
+        exit (index into TRI_EXITS), x3d, point_stereo, n_matches, n_created.  A point created at one neighbour takes its idx1 out of
+        the searches at the later ones.  Raises GfsError (code GFS_ERR_CAPACITY) beyond the reserve."""
+        single = isinstance(problems, dict)
+        probs = [problems] if single else list(problems)
+        if not hasattr(self, "tri_reserve"):
+            self.reserve_triangulation(max([len(p["neighbours"]) for p in probs] + [1]), max([tri_candidate_pairs(p) for p in probs] + [1]))
+        PP, RP, keep = tri_structs(probs)
+        _check(lib().gfs_create_new_map_points(self.h, PP, len(probs), RP), "gfs_create_new_map_points")
+        res = tri_results(PP, RP, keep, len(probs))
         return res[0] if single else res
 
 

@@ -24,6 +24,7 @@
 #include "gfs_common.hpp"
 #include "glibc_math.hpp"
 #include "fuse_rule.hpp"
+#include "sbp_handle.hpp"
 
 namespace {
 
@@ -921,6 +922,7 @@ struct gfs_sbp {
   int fuse_lists = 0, fuse_points = 0, fuse_kfs = 0;
   gfs::DevBuf<uint8_t> d_fpts, d_fkf, d_fout;
   gfs::PinBuf<uint8_t> h_fpts, h_fkf, h_fout;
+  gfs_tri_workspace* tri = nullptr;  // gfs_create_new_map_points (triangulate.hip; allocated by gfs_sbp_reserve_triangulation)
   struct FuseLayout {
     size_t p_nrm, p_min, p_max, p_desc, pts_bytes;         // point block (xw at 0), T points
     size_t k_xy, k_ur, k_oct, k_desc, kf_bytes;            // key-frame block (headers at 0), B x SC key-points
@@ -1031,6 +1033,8 @@ static int sbp_run(gfs_sbp* h, int B, const gfs_sbp::Layout& Y) {
   return GFS_OK;
 }
 
+gfs_sbp_core gfs_sbp_core_of(gfs_sbp* h) { return gfs_sbp_core{h->device, h->max_cur, h->max_batch, h->stream, &h->mu, &h->tri}; }
+
 extern "C" {
 
 int gfs_sbp_create(int device, int max_last, int max_cur, int max_batch, gfs_sbp** out) {
@@ -1070,6 +1074,7 @@ void gfs_sbp_destroy(gfs_sbp* h) {
   if (!h) return;
   (void)hipSetDevice(h->device);
   (void)hipStreamSynchronize(h->stream);
+  gfs_tri_workspace_free(h->tri);
   (void)hipStreamDestroy(h->stream);
   delete h;
 }

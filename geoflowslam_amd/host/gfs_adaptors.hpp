@@ -33,6 +33,7 @@
 
 #include "../../include/gfs_abi.h"
 #include "../csrc/fuse_rule.hpp"
+#include "../csrc/triangulate_rule.hpp"
 
 namespace gfs_host {
 
@@ -1341,6 +1342,333 @@ class FuseSearcher {
  private:
   gfs_sbp* h_ = nullptr;
   int lists_ = 0, points_ = 0, kfs_ = 0;
+};
+
+// ------------------------------------------------------------------------------------------------------------------------
+// void LocalMapping::CreateNewMapPoints()                                                  reference src/LocalMapping.cc:803-1127
+// as real code around gfs_create_new_map_points.  The numeric result at neighbour i (SearchForTriangulation's pairs, each pair's
+// triangulation and gates) depends only on the entry state and on which idx1 of the current key frame received a point at the
+// neighbours before i; the device carries exactly that, so ONE call serves the whole neighbour loop and every prefix of it is exact.
+//   gather:  the neighbour list (:805-819); neighbours with a short baseline (:859-866) are not uploaded; every key frame's
+//            mFeatVec is flattened; `Access` computes ep and F12 with the reference's own Sophus / Eigen expressions.
+//   solve:   `solve(problems, 1, results)`: MapPointCreator::solve below (the GPU), or tri_solve_host (the same rule on the host).
+//   replay:  per neighbour of the ORIGINAL list in order: `if (i > 0 && check_new_key_frames()) return` (:847) -- exact, because the
+//            results of the neighbours before i do not depend on those after; then for ascending idx1 with GFS_TRI_CREATED the block
+//            :1103-1124 (new MapPoint, AddObservation x 2, the optical-flow feature's pointer, AddMapPoint x 2,
+//            ComputeDistinctiveDescriptors, UpdateNormalAndDepth, Atlas::AddMapPoint, mlpRecentAddedMapPoints).
+// What other threads change in the map during the call is not seen: has_mp is read at entry (as for Fuse).
+// Single-camera pinhole key frames only: NLeft != -1 or another camera model throws.  Compile with -ffp-contract=off when
+// tri_solve_host is used (the host rule is the device's arithmetic).
+//
+// KeyFrame / MapPoint / Atlas are the reference's own classes, used through the members the reference function uses (pKF->NLeft, N,
+// fx .. invfy, mbf, mb, mfScaleFactor, mnScaleLevels, mvScaleFactors, mvLevelSigma2, mvuRight, mvDepth, mPrevKF,
+// GetBestCovisibilityKeyFrames, GetMapPoint, AddMapPoint, ComputeSceneMedianDepth; pMP->AddObservation, ComputeDistinctiveDescriptors,
+// UpdateNormalAndDepth; atlas->AddMapPoint).  `Access` as for Fuse (is_pinhole, keys_un, descriptors), plus:
+//     static void pose3x4(const KeyFrame&, float Tcw[12], float Ow[3], float Rwc[9], float twc[3]);  // GetPose().matrix3x4() row-major,
+//                                                                       // GetCameraCenter(), mRwc row-major, mTwc.translation()
+//     static const gfs_keypoint* keys(const KeyFrame&);                 // mvKeys.data()
+//     template <class F> static void for_each_node(const KeyFrame&, F&& f);  // f(node id, const std::vector<unsigned>&) over mFeatVec
+//     static void epipolar(const KeyFrame& kf1, const KeyFrame& kf2, float ep[2], float F12[9]);  // src/ORBmatcher.cc:1165-1171 and
+//                                                                       // Pinhole.cpp:109-112 (F12 row-major), in float as written
+//     static MapPoint* new_map_point(const float x3D[3], KeyFrame* pRefKF, Atlas* atlas);  // new MapPoint(x3D, pKF, GetCurrentMap())
+//     static void set_tracked_feature(KeyFrame* pKF, int idx1, MapPoint* pMP);             // track_feature_pts_.at(idx1): mp, is_3d
+// ------------------------------------------------------------------------------------------------------------------------
+struct CreateNewMapPointsParams {
+  bool monocular = false, inertial = false, coarse = false, far_points = false, use_optical_flow = false;  // mbMonocular, mbInertial,
+  float th_far_points = 0.0f;  // bCoarse (:870), mbFarPoints, mpTracker->GetUseOpticalFlow(); mThFarPoints
+};
+
+struct TriKeyFrameFlat {  // one gathered key frame
+  std::vector<int32_t> node_id, node_start, feat_idx;
+  std::vector<uint8_t> has_mp;
+  gfs_tri_keyframe k{};
+};
+
+template <class Access, class KeyFrame>
+void tri_gather(KeyFrame* pKF, TriKeyFrameFlat& F) {
+  const KeyFrame& KF = *pKF;
+  if (KF.NLeft != -1 || !Access::is_pinhole(KF)) throw std::invalid_argument("CreateNewMapPoints: single-camera pinhole key frames only");
+  gfs_tri_keyframe& k = F.k;
+  Access::pose3x4(KF, k.Tcw, k.Ow, k.Rwc, k.twc);
+  k.fx = KF.fx;
+  k.fy = KF.fy;
+  k.cx = KF.cx;
+  k.cy = KF.cy;
+  k.invfx = KF.invfx;
+  k.invfy = KF.invfy;
+  k.mbf = KF.mbf;
+  k.mb = KF.mb;
+  k.scale_factors = KF.mvScaleFactors.data();
+  k.level_sigma2 = KF.mvLevelSigma2.data();
+  k.n_levels = KF.mnScaleLevels;
+  k.n_kp = KF.N;
+  k.kps_un = Access::keys_un(KF);
+  k.kps = Access::keys(KF);
+  k.u_right = KF.mvuRight.data();
+  k.depth = KF.mvDepth.data();
+  k.desc = Access::descriptors(KF);
+  F.has_mp.assign((size_t)KF.N + 1, 0);
+  for (int i = 0; i < KF.N; i++) F.has_mp[i] = pKF->GetMapPoint(i) != nullptr;
+  F.node_id.clear();
+  F.feat_idx.clear();
+  F.node_start.assign(1, 0);
+  Access::for_each_node(KF, [&](unsigned id, const std::vector<unsigned>& idx) {
+    F.node_id.push_back((int32_t)id);
+    for (unsigned i : idx) F.feat_idx.push_back((int32_t)i);
+    F.node_start.push_back((int32_t)F.feat_idx.size());
+  });
+  F.node_id.push_back(0);   // (never NULL)
+  F.feat_idx.push_back(0);
+  k.has_mp = F.has_mp.data();
+  k.n_nodes = (int32_t)F.node_start.size() - 1;
+  k.node_id = F.node_id.data();
+  k.node_start = F.node_start.data();
+  k.feat_idx = F.feat_idx.data();
+}
+
+struct TriOutputs {  // the result arrays of one neighbour
+  std::vector<int32_t> match12;
+  std::vector<uint8_t> exit, point_stereo;
+  std::vector<float> x3d;
+  gfs_tri_result view(size_t n) {
+    match12.assign(n + 1, -1);
+    exit.assign(n + 1, 0);
+    point_stereo.assign(n + 1, 0);
+    x3d.assign(3 * n + 3, 0.0f);
+    gfs_tri_result r{};
+    r.match12 = match12.data();
+    r.exit = exit.data();
+    r.point_stereo = point_stereo.data();
+    r.x3d = x3d.data();
+    return r;
+  }
+};
+
+// gfs_create_new_map_points on the host with the device's rule (csrc/triangulate_rule.hpp): per neighbour, per common node, every idx1
+// in list order takes the candidate of minimum distance, last list position among equals, that no earlier idx1 of the node took.
+inline int tri_solve_host(const gfs_tri_problem* problems, int B, gfs_tri_result* const* results) {
+  auto cam = [](const gfs_tri_keyframe& k) {
+    gfs_tri::Cam C{};
+    std::memcpy(C.Tcw, k.Tcw, sizeof(k.Tcw));
+    std::memcpy(C.Ow, k.Ow, sizeof(k.Ow));
+    std::memcpy(C.Rwc, k.Rwc, sizeof(k.Rwc));
+    std::memcpy(C.twc, k.twc, sizeof(k.twc));
+    C.fx = k.fx, C.fy = k.fy, C.cx = k.cx, C.cy = k.cy, C.invfx = k.invfx, C.invfy = k.invfy, C.mbf = k.mbf, C.mb = k.mb;
+    if (k.n_levels < 1 || k.n_levels > 16) throw std::invalid_argument("CreateNewMapPoints: 1..16 pyramid levels");
+    C.n_levels = k.n_levels;
+    for (int l = 0; l < k.n_levels; l++) C.scale[l] = k.scale_factors[l], C.sigma2[l] = k.level_sigma2[l];
+    return C;
+  };
+  auto kp = [](const gfs_tri_keyframe& k, int i) {
+    if (k.kps_un[i].octave < 0 || k.kps_un[i].octave >= k.n_levels) throw std::invalid_argument("CreateNewMapPoints: key-point octave outside the pyramid");
+    return gfs_tri::Kp{k.kps_un[i].x, k.kps_un[i].y, k.kps_un[i].angle, k.kps[i].x, k.kps[i].y, k.u_right[i], k.depth[i], k.kps_un[i].octave};
+  };
+  for (int b = 0; b < B; b++) {
+    const gfs_tri_problem& Q = problems[b];
+    const gfs_tri_keyframe& K1 = Q.cur;
+    const gfs_tri::Cam C1 = cam(K1);
+    std::vector<uint8_t> has1(K1.has_mp, K1.has_mp + K1.n_kp);
+    for (int i = 0; i < Q.n_neighbours; i++) {
+      const gfs_tri_neighbour& NB = Q.neighbours[i];
+      const gfs_tri_keyframe& K2 = NB.kf;
+      const gfs_tri::Cam C2 = cam(K2);
+      gfs_tri_result& R = results[b][i];
+      for (int p = 0; p < K1.n_kp; p++) {
+        R.match12[p] = -1;
+        R.exit[p] = GFS_TRI_NO_MATCH;
+        R.point_stereo[p] = 0;
+        R.x3d[3 * p] = R.x3d[3 * p + 1] = R.x3d[3 * p + 2] = 0.0f;
+      }
+      std::vector<uint8_t> taken;
+      for (int n1 = 0; n1 < K1.n_nodes; n1++) {
+        const int32_t* e = std::lower_bound(K2.node_id, K2.node_id + K2.n_nodes, K1.node_id[n1]);
+        if (e == K2.node_id + K2.n_nodes || *e != K1.node_id[n1]) continue;
+        const int n2 = (int)(e - K2.node_id), b2 = K2.node_start[n2], c2 = K2.node_start[n2 + 1] - b2;
+        taken.assign((size_t)c2, 0);
+        for (int a = K1.node_start[n1]; a < K1.node_start[n1 + 1]; a++) {
+          const int idx1 = K1.feat_idx[a];
+          const bool st1 = K1.u_right[idx1] >= 0;
+          if (has1[idx1] || (Q.only_stereo && !st1)) continue;
+          const gfs_tri::Line line = gfs_tri::epipolar_line(NB.F12, K1.kps_un[idx1].x, K1.kps_un[idx1].y);
+          int best = 256, at = -1;
+          for (int c = 0; c < c2; c++) {
+            const int idx2 = K2.feat_idx[b2 + c];
+            const bool st2 = K2.u_right[idx2] >= 0;
+            if (taken[c] || K2.has_mp[idx2] || (Q.only_stereo && !st2)) continue;
+            int d = 0;
+            for (int w = 0; w < 32; w++) d += __builtin_popcount((unsigned)(K1.desc[32 * (size_t)idx1 + w] ^ K2.desc[32 * (size_t)idx2 + w]));
+            if (d > gfs_tri::kThLow || d > best) continue;
+            const int o2 = K2.kps_un[idx2].octave;
+            if (o2 < 0 || o2 >= K2.n_levels) throw std::invalid_argument("CreateNewMapPoints: key-point octave outside the pyramid");
+            if (!gfs_tri::candidate_ok(line, NB.ep, st1, st2, K2.kps_un[idx2].x, K2.kps_un[idx2].y, K2.scale_factors[o2], K2.level_sigma2[o2], Q.coarse != 0))
+              continue;
+            best = d;
+            at = c;
+          }
+          if (at >= 0) {
+            taken[at] = 1;
+            R.match12[idx1] = K2.feat_idx[b2 + at];
+          }
+        }
+      }
+      if (Q.check_orientation) {
+        int hist[gfs_tri::kHisto] = {0}, ind1, ind2, ind3;
+        for (int p = 0; p < K1.n_kp; p++)
+          if (R.match12[p] >= 0) hist[gfs_tri::rot_bin(K1.kps_un[p].angle, K2.kps_un[R.match12[p]].angle)]++;
+        gfs_tri::three_maxima(hist, ind1, ind2, ind3);
+        for (int p = 0; p < K1.n_kp; p++) {
+          if (R.match12[p] < 0) continue;
+          const int bin = gfs_tri::rot_bin(K1.kps_un[p].angle, K2.kps_un[R.match12[p]].angle);
+          if (bin != ind1 && bin != ind2 && bin != ind3) R.match12[p] = -1;
+        }
+      }
+      R.n_matches = R.n_created = 0;
+      for (int p = 0; p < K1.n_kp; p++) {
+        if (R.match12[p] < 0) continue;
+        int ps = 0;
+        const int ex = gfs_tri::triangulate_match(C1, C2, kp(K1, p), kp(K2, R.match12[p]), Q.inertial != 0, Q.far_points != 0, Q.th_far_points,
+                                                  Q.ratio_factor, R.x3d + 3 * p, &ps);
+        R.exit[p] = (uint8_t)ex;
+        R.point_stereo[p] = (uint8_t)ps;
+        R.n_matches++;
+        if (ex == GFS_TRI_CREATED) {
+          has1[p] = 1;
+          R.n_created++;
+        }
+      }
+    }
+  }
+  return GFS_OK;
+}
+
+// LocalMapping::CreateNewMapPoints.  recent: mlpRecentAddedMapPoints.  -> the number of map points created.
+template <class Access, class KeyFrame, class MapPoint, class Atlas, class Solve, class CheckNewKeyFrames>
+int CreateNewMapPoints(Solve&& solve, KeyFrame* pCurrentKF, Atlas* atlas, std::list<MapPoint*>& recent, const CreateNewMapPointsParams& prm,
+                       CheckNewKeyFrames&& check_new_key_frames) {
+  // Retrieve neighbor keyframes in covisibility graph (:805-819)
+  int nn = gfs_tri::kNeighbours;
+  if (prm.monocular) nn = gfs_tri::kNeighboursMono;
+  std::vector<KeyFrame*> vpNeighKFs = pCurrentKF->GetBestCovisibilityKeyFrames(nn);
+  {
+    KeyFrame* pKF = pCurrentKF;
+    int count = 0;
+    while (((int)vpNeighKFs.size() <= nn) && (pKF->mPrevKF) && (count++ < nn)) {
+      if (std::find(vpNeighKFs.begin(), vpNeighKFs.end(), pKF->mPrevKF) == vpNeighKFs.end()) vpNeighKFs.push_back(pKF->mPrevKF);
+      pKF = pKF->mPrevKF;
+    }
+  }
+  std::vector<TriKeyFrameFlat> flat(vpNeighKFs.size() + 1);
+  tri_gather<Access>(pCurrentKF, flat[0]);
+  std::vector<gfs_tri_neighbour> nbs;
+  std::vector<int> slot_of(vpNeighKFs.size(), -1);  // which uploaded neighbour an entry of the list is, -1 = short baseline
+  for (size_t i = 0; i < vpNeighKFs.size(); i++) {
+    KeyFrame* pKF2 = vpNeighKFs[i];
+    tri_gather<Access>(pKF2, flat[i + 1]);
+    const float* Ow1 = flat[0].k.Ow;
+    const float* Ow2 = flat[i + 1].k.Ow;
+    const float v[3] = {Ow2[0] - Ow1[0], Ow2[1] - Ow1[1], Ow2[2] - Ow1[2]};
+    const float baseline = std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);  // vBaseline.norm()
+    if (!prm.monocular) {
+      if (baseline < pKF2->mb) continue;
+    } else {
+      const float medianDepthKF2 = pKF2->ComputeSceneMedianDepth(2);
+      const float ratioBaselineDepth = baseline / medianDepthKF2;
+      if (ratioBaselineDepth < 0.01) continue;
+    }
+    gfs_tri_neighbour nb{};
+    nb.kf = flat[i + 1].k;
+    Access::epipolar(*pCurrentKF, *pKF2, nb.ep, nb.F12);
+    slot_of[i] = (int)nbs.size();
+    nbs.push_back(nb);
+  }
+  gfs_tri_problem P{};
+  P.cur = flat[0].k;
+  P.neighbours = nbs.data();
+  P.n_neighbours = (int32_t)nbs.size();
+  P.only_stereo = 0;  // SearchForTriangulation(..., false, bCoarse) (:872)
+  P.coarse = prm.coarse;
+  P.check_orientation = 0;  // ORBmatcher matcher(th, false) (:824)
+  P.inertial = prm.inertial;
+  P.far_points = prm.far_points;
+  P.th_far_points = prm.th_far_points;
+  P.ratio_factor = gfs_tri::kRatioFactor * pCurrentKF->mfScaleFactor;
+  std::vector<TriOutputs> outs(nbs.size());
+  std::vector<gfs_tri_result> rs;
+  for (TriOutputs& o : outs) rs.push_back(o.view((size_t)P.cur.n_kp));
+  if (!nbs.empty()) {
+    gfs_tri_result* rp = rs.data();
+    check(solve(&P, 1, &rp), "gfs_create_new_map_points");
+  }
+  int created = 0;
+  for (size_t i = 0; i < vpNeighKFs.size(); i++) {
+    if (i > 0 && check_new_key_frames()) return created;
+    if (slot_of[i] < 0) continue;
+    KeyFrame* pKF2 = vpNeighKFs[i];
+    const TriOutputs& o = outs[(size_t)slot_of[i]];
+    for (int idx1 = 0; idx1 < P.cur.n_kp; idx1++) {
+      if (o.exit[idx1] != GFS_TRI_CREATED) continue;
+      const int idx2 = o.match12[idx1];
+      // Triangulation is succesfull (:1103-1124)
+      MapPoint* pMP = Access::new_map_point(&o.x3d[3 * (size_t)idx1], pCurrentKF, atlas);
+      pMP->AddObservation(pCurrentKF, idx1);
+      pMP->AddObservation(pKF2, idx2);
+      if (prm.use_optical_flow) Access::set_tracked_feature(pCurrentKF, idx1, pMP);
+      pCurrentKF->AddMapPoint(pMP, idx1);
+      pKF2->AddMapPoint(pMP, idx2);
+      pMP->ComputeDistinctiveDescriptors();
+      pMP->UpdateNormalAndDepth();
+      atlas->AddMapPoint(pMP);
+      recent.push_back(pMP);
+      created++;
+    }
+  }
+  return created;
+}
+
+// the numeric core of CreateNewMapPoints on the GPU: one handle, its reserve grown to the largest call seen
+class MapPointCreator {
+ public:
+  MapPointCreator(int max_kp = 4096, int device = 0) { check(gfs_sbp_create(device, 64, max_kp, 1, &h_), "gfs_sbp_create"); }
+  ~MapPointCreator() { gfs_sbp_destroy(h_); }
+  MapPointCreator(const MapPointCreator&) = delete;
+  MapPointCreator& operator=(const MapPointCreator&) = delete;
+  int solve(const gfs_tri_problem* problems, int B, gfs_tri_result* const* results) {
+    int nb = 1;
+    int64_t pairs = 1;
+    for (int b = 0; b < B; b++) {
+      const gfs_tri_problem& Q = problems[b];
+      nb = std::max(nb, (int)Q.n_neighbours);
+      int64_t sum = 0;
+      for (int i = 0; i < Q.n_neighbours; i++) {
+        const gfs_tri_keyframe& K2 = Q.neighbours[i].kf;
+        for (int n1 = 0, n2 = 0; n1 < Q.cur.n_nodes && n2 < K2.n_nodes;) {
+          if (Q.cur.node_id[n1] < K2.node_id[n2]) n1++;
+          else if (Q.cur.node_id[n1] > K2.node_id[n2]) n2++;
+          else {
+            sum += (int64_t)(Q.cur.node_start[n1 + 1] - Q.cur.node_start[n1]) * (K2.node_start[n2 + 1] - K2.node_start[n2]);
+            n1++, n2++;
+          }
+        }
+      }
+      pairs = std::max(pairs, sum);
+    }
+    if (nb > neighbours_ || pairs > pairs_) {  // the library refuses what exceeds the reserve (it never truncates): grow it first
+      const int n = std::max(nb, neighbours_);
+      const int64_t p = std::max(pairs, pairs_);
+      check(gfs_sbp_reserve_triangulation(h_, n, p), "gfs_sbp_reserve_triangulation");
+      neighbours_ = n;
+      pairs_ = p;
+    }
+    return gfs_create_new_map_points(h_, problems, B, results);
+  }
+  auto solver() {
+    return [this](const gfs_tri_problem* p, int B, gfs_tri_result* const* r) { return solve(p, B, r); };
+  }
+
+ private:
+  gfs_sbp* h_ = nullptr;
+  int neighbours_ = 0;
+  int64_t pairs_ = 0;
 };
 
 // Optimizer::PoseOptimization on a flattened frame (reference src/Optimizer.cc:763-1098)

@@ -843,3 +843,107 @@ def lidar_map_window(seed, n_keyframes=7, n_cloud=3000, width=160, height=120, t
     return dict(q=np.array(q, np.float32).reshape(-1, 4), t=np.array(t, np.float32).reshape(-1, 3), clouds=clouds,
                 cloud_begin=np.r_[0, np.cumsum([len(c) for c in clouds])].astype(np.int32),
                 cloud=np.ascontiguousarray(np.concatenate(clouds), np.float32).reshape(-1, 3))
+
+
+def triangulation_problem(seed, n_kp=1000, n_neighbours=10, n_nodes=100, n_kp_neighbour=None, mono_frac=0.3, has_mp_frac=0.3,
+                          node_perturb=0.1, noise_px=0.6, bad_depth_frac=0.0, scale_factor=1.2, n_levels=8, width=640, height=480,
+                          only_stereo=False, coarse=False, check_orientation=False, inertial=False, far_points=False, th_far_points=6.0,
+                          shuffle_lists=True):
+    """One LocalMapping::CreateNewMapPoints problem (gfs_tri_problem; api.tri_structs): a current key frame and n_neighbours
+    neighbours that see one shared scene of world points.  Per view: key-points with pixel noise, octaves that follow the depth,
+    descriptors a few bits from their world point's (points of one vocabulary node share a family, so wrong pairs and equal
+    distances occur), node ids shared through the world point with a share perturbed, a share of mono key-points and a share with
+    has_mp set, baselines above mb, ep / F12 computed in float32 with the reference's expressions.  bad_depth_frac: stereo
+    key-points whose depth is not positive (UnprojectStereo fails)."""
+    from .api import KP_DTYPE
+    rng = np.random.default_rng(seed)
+    f32 = np.float32
+    fx, fy, cx, cy = (f32(v) for v in intrinsics(width, height))
+    mb = f32(0.0745)
+    mbf = f32(mb * fx)
+    n_nb_kp = n_kp if n_kp_neighbour is None else n_kp_neighbour
+    n_world = max(int(1.4 * max(n_kp, n_nb_kp)), 8)
+    ids = 3 * np.arange(max(n_nodes, 1)) + 1  # vocabulary node ids (not consecutive)
+    w_node = rng.integers(0, max(n_nodes, 1), n_world)
+    fam = rng.integers(0, 256, (max(n_nodes, 1), 32), dtype=np.uint8)
+    bits = np.unpackbits(fam[w_node], axis=1)
+    for i in range(n_world):
+        bits[i, rng.choice(256, rng.integers(8, 22), replace=False)] ^= 1
+    w_bits = bits
+    w_angle = rng.uniform(0, 360, n_world)
+    # the world points in front of the current camera (identity-ish), 0.8 .. 9 m
+    z = rng.uniform(0.8, 9.0, n_world)
+    w_xyz = np.stack([(rng.uniform(0, width, n_world) - cx) / fx * z, (rng.uniform(0, height, n_world) - cy) / fy * z, z], 1)
+    scale = (f32(scale_factor) ** np.arange(n_levels)).astype(f32)
+    sigma2 = (scale * scale).astype(f32)
+
+    def view(n, T_wc, is_cur):
+        R, t = T_wc[:3, :3].T, -T_wc[:3, :3].T @ T_wc[:3, 3]  # Tcw
+        Tcw = np.concatenate([R, t[:, None]], 1).astype(f32)
+        R32, t32 = Tcw[:, :3], Tcw[:, 3]
+        Pc = w_xyz @ R.T + t
+        u, v = fx * Pc[:, 0] / Pc[:, 2] + cx, fy * Pc[:, 1] / Pc[:, 2] + cy
+        vis = np.nonzero((Pc[:, 2] > 0.3) & (u > 8) & (u < width - 8) & (v > 8) & (v < height - 8))[0]
+        pick = rng.permutation(vis)[:n]
+        kps_un, kps = np.zeros(n, KP_DTYPE), np.zeros(n, KP_DTYPE)
+        m = len(pick)
+        x = np.concatenate([u[pick] + noise_px * rng.standard_normal(m), rng.uniform(8, width - 8, n - m)])
+        y = np.concatenate([v[pick] + noise_px * rng.standard_normal(m), rng.uniform(8, height - 8, n - m)])
+        zz = np.concatenate([Pc[pick, 2], rng.uniform(0.8, 9.0, n - m)])
+        oct_ = np.clip(np.round(np.log(zz / 1.2) / np.log(scale_factor)) + rng.integers(-1, 2, n), 0, n_levels - 1).astype(np.int32)
+        kps_un["x"], kps_un["y"], kps_un["octave"] = x, y, oct_
+        kps_un["angle"] = np.concatenate([(w_angle[pick] + 6 * rng.standard_normal(m)) % 360, rng.uniform(0, 360, n - m)])
+        kps_un["size"] = 31 * scale[oct_]
+        kps[:] = kps_un
+        kps["x"], kps["y"] = kps_un["x"] + f32(0.25), kps_un["y"] - f32(0.125)  # (mvKeys: before undistortion)
+        mono = rng.random(n) < mono_frac
+        depth = (zz * (1 + 0.004 * rng.standard_normal(n))).astype(f32)
+        u_right = (kps_un["x"] - mbf / depth).astype(f32)
+        u_right[mono], depth[mono] = -1, -1
+        if bad_depth_frac > 0:
+            depth[(rng.random(n) < bad_depth_frac) & ~mono] = 0
+        db = np.concatenate([w_bits[pick], rng.integers(0, 2, (n - m, 256), dtype=np.uint8)])
+        flip = rng.random((n, 256)) < rng.uniform(0, 0.05, (n, 1))
+        desc = np.packbits(db ^ flip.astype(np.uint8), axis=1)
+        node = np.concatenate([w_node[pick], rng.integers(0, max(n_nodes, 1), n - m)])
+        pert = rng.random(n) < node_perturb
+        node[pert] = rng.integers(0, max(n_nodes, 1), int(pert.sum()))
+        nid = ids[node] if n else np.zeros(0, np.int64)
+        if n and n_nodes > 2:
+            nid = np.where(node == rng.integers(0, n_nodes), nid + 1, nid)  # one node this view has under an id of its own
+        order = rng.permutation(n)  # key-point indices differ from view to view
+        kps_un, kps, u_right, depth, desc, nid = kps_un[order], kps[order], u_right[order], depth[order], desc[order], nid[order]
+        node_id = np.unique(nid).astype(np.int32)
+        lists = [np.nonzero(nid == k)[0] for k in node_id]
+        if shuffle_lists:
+            lists = [rng.permutation(l) for l in lists]
+        node_start = np.concatenate([[0], np.cumsum([len(l) for l in lists])]).astype(np.int32)
+        feat_idx = (np.concatenate(lists) if lists else np.zeros(0)).astype(np.int32)
+        Ow = (-(R32.T @ t32)).astype(f32)
+        return dict(Tcw=Tcw.reshape(-1), Ow=Ow, Rwc=np.ascontiguousarray(R32.T).reshape(-1), twc=Ow.copy(), fx=fx, fy=fy, cx=cx, cy=cy,
+                    invfx=f32(1) / fx, invfy=f32(1) / fy, mbf=mbf, mb=mb, scale_factors=scale, level_sigma2=sigma2, n_levels=n_levels,
+                    kps_un=kps_un, kps=kps, u_right=u_right, depth=depth, desc=desc,
+                    has_mp=(rng.random(n) < has_mp_frac).astype(np.uint8), node_id=node_id, node_start=node_start, feat_idx=feat_idx)
+
+    T0 = random_motion(rng, trans=0.05, rot_deg=2.0)
+    cur = view(n_kp, T0, True)
+    K = np.array([[fx, 0, cx], [0, fy, cy], [0, 0, 1]], f32)
+    Kinv = np.linalg.inv(K.astype(np.float64)).astype(f32)
+    R1, t1 = cur["Tcw"].reshape(3, 4)[:, :3], cur["Tcw"].reshape(3, 4)[:, 3]
+    neighbours = []
+    for i in range(n_neighbours):
+        T = random_motion(rng, trans=0.0, rot_deg=4.0)
+        d = rng.standard_normal(3)
+        d[2] *= 0.3
+        T[:3, 3] = T0[:3, 3] + d / np.linalg.norm(d) * rng.uniform(0.12, 0.5)  # baseline above mb
+        nb = view(n_nb_kp, T, False)
+        R2, t2 = nb["Tcw"].reshape(3, 4)[:, :3], nb["Tcw"].reshape(3, 4)[:, 3]
+        C2 = (R2 @ cur["Ow"] + t2).astype(f32)
+        nb["ep"] = np.array([fx * C2[0] / C2[2] + cx, fy * C2[1] / C2[2] + cy], f32)
+        R12 = (R1 @ R2.T).astype(f32)
+        t12 = (t1 - R12 @ t2).astype(f32)
+        tx = np.array([[0, -t12[2], t12[1]], [t12[2], 0, -t12[0]], [-t12[1], t12[0], 0]], f32)
+        nb["F12"] = (((Kinv.T @ tx).astype(f32) @ R12).astype(f32) @ Kinv).astype(f32).reshape(-1)
+        neighbours.append(nb)
+    return dict(cur=cur, neighbours=neighbours, only_stereo=only_stereo, coarse=coarse, check_orientation=check_orientation, inertial=inertial,
+                far_points=far_points, th_far_points=f32(th_far_points), ratio_factor=f32(f32(1.5) * f32(scale_factor)))

@@ -591,6 +591,81 @@ int gfs_sbp_reserve_fuse(gfs_sbp* h, int max_lists, int max_points_per_list, int
  * [0, n_lists), a key-point octave outside [0, n_levels) or a NULL array.  Nothing is truncated; the handle stays usable. */
 int gfs_fuse_search(gfs_sbp* h, const gfs_fuse_points* lists, int n_lists, const gfs_fuse_keyframe* kfs, int B, gfs_fuse_result* results);
 
+/*      void LocalMapping::CreateNewMapPoints()                                   src/LocalMapping.cc:803-1127
+ *    for every neighbour key frame in order: ORBmatcher::SearchForTriangulation (src/ORBmatcher.cc:1158-1376: Hamming search over the
+ *    key-point pairs that share a vocabulary node, epipole and epipolar-line gates, optional rotation histogram) and the triangulation
+ *    of every match with its gates (:904-1100).  A point created at neighbour i takes its idx1 out of the searches at the neighbours
+ *    after i; that dependency is carried on the device.  What the loop does with a created point (:1103-1124) stays with the caller,
+ *    neighbour by neighbour in ascending idx1 (gfs_host::CreateNewMapPoints, geoflowslam_amd/host/gfs_adaptors.hpp).  Single-camera
+ *    pinhole key frames (NLeft == -1, mpCamera2 == nullptr).  DESIGN.md section 14 states the rule, with two written rules where the
+ *    reference's arithmetic is a library's (the 4 x 4 null vector, the stereo parallax cosine). */
+#define GFS_TRI_NO_MATCH 0          /* idx1 is in no pair of vMatchedIndices */
+#define GFS_TRI_LOW_PARALLAX 1      /* "No stereo and very low parallax" (:1020) */
+#define GFS_TRI_SVD_W_ZERO 2        /* GeometricTools::Triangulate returned false (:1010) */
+#define GFS_TRI_UNPROJECT_FAILED 3  /* UnprojectStereo returned false (:1025) */
+#define GFS_TRI_BEHIND_1 4          /* z1 <= 0 (:1029) */
+#define GFS_TRI_BEHIND_2 5          /* z2 <= 0 (:1032) */
+#define GFS_TRI_REPROJ_1 6          /* reprojection chi2 in the current key frame (:1045, :1054) */
+#define GFS_TRI_REPROJ_2 7          /* ... in the neighbour (:1068, :1076) */
+#define GFS_TRI_ZERO_DIST 8         /* dist1 == 0 || dist2 == 0 (:1088) */
+#define GFS_TRI_FAR 9               /* mbFarPoints and a distance >= mThFarPoints (:1090) */
+#define GFS_TRI_SCALE 10            /* scale consistency (:1098) */
+#define GFS_TRI_CREATED 11          /* the caller does :1103-1124 with x3d */
+typedef struct {
+  float Tcw[12];                 /* GetPose().matrix3x4(), row-major */
+  float Ow[3];                   /* GetCameraCenter() */
+  float Rwc[9], twc[3];          /* mRwc (row-major) and mTwc.translation(), read by UnprojectStereo */
+  float fx, fy, cx, cy, invfx, invfy, mbf, mb;
+  const float* scale_factors;    /* mvScaleFactors */
+  const float* level_sigma2;     /* mvLevelSigma2 */
+  int32_t n_levels;              /* 1..16 */
+  int32_t n_kp;                  /* N, <= the handle's max_cur */
+  const gfs_keypoint* kps_un;    /* [n_kp] mvKeysUn: position, octave in [0, n_levels), angle */
+  const gfs_keypoint* kps;       /* [n_kp] mvKeys (UnprojectStereo reads its position) */
+  const float* u_right;          /* [n_kp] mvuRight */
+  const float* depth;            /* [n_kp] mvDepth */
+  const uint8_t* desc;           /* [n_kp][32] mDescriptors */
+  const uint8_t* has_mp;         /* [n_kp] GetMapPoint(i) != nullptr at entry */
+  int32_t n_nodes;               /* mFeatVec, flattened: */
+  const int32_t* node_id;        /* [n_nodes] strictly ascending */
+  const int32_t* node_start;     /* [n_nodes + 1] non-decreasing from 0 */
+  const int32_t* feat_idx;       /* [node_start[n_nodes]] key-point indices in [0, n_kp), none twice */
+} gfs_tri_keyframe;
+
+typedef struct {
+  gfs_tri_keyframe kf;           /* pKF2 */
+  float ep[2];                   /* pKF2->mpCamera->project(T2w * Cw) (src/ORBmatcher.cc:1169-1171) */
+  float F12[9];                  /* K1.transpose().inverse() * t12x * R12 * K2.inverse(), row-major (Pinhole.cpp:112) */
+} gfs_tri_neighbour;
+
+typedef struct {
+  gfs_tri_keyframe cur;          /* mpCurrentKeyFrame */
+  const gfs_tri_neighbour* neighbours; /* [n_neighbours] in the loop's order; short baselines (:860) already left out */
+  int32_t n_neighbours;
+  int32_t only_stereo, coarse, check_orientation; /* bOnlyStereo, bCoarse, the ORBmatcher's checkOri */
+  int32_t inertial, far_points;  /* mbInertial, mbFarPoints */
+  float th_far_points;           /* mThFarPoints */
+  float ratio_factor;            /* 1.5f * mpCurrentKeyFrame->mfScaleFactor */
+} gfs_tri_problem;
+
+typedef struct {                 /* one per neighbour; caller-owned arrays of the current key frame's n_kp */
+  int32_t* match12;              /* idx2 or -1, after the orientation check */
+  uint8_t* exit;                 /* GFS_TRI_* */
+  float* x3d;                    /* [n_kp][3] the point where exit >= GFS_TRI_BEHIND_1, zeros before */
+  uint8_t* point_stereo;         /* bPointStereo */
+  int32_t n_matches, n_created;
+} gfs_tri_result;
+
+/* Allocates the workspace of gfs_create_new_map_points: up to max_neighbours neighbours per problem and up to max_candidate_pairs
+ * for the sum of n1 * n2 over the common nodes of all neighbours of one problem; max_batch problems of max_cur key-points per key
+ * frame as the handle was created (handles that never call it are unchanged). */
+int gfs_sbp_reserve_triangulation(gfs_sbp* h, int max_neighbours, int64_t max_candidate_pairs);
+/* B independent current key frames in one call (host pointers); results[b] points to problems[b].n_neighbours results.
+ * GFS_ERR_CAPACITY: above any reserve, or a handle that never reserved.  GFS_ERR_INVALID_ARG: a NULL array, n_levels outside 1..16,
+ * an octave outside [0, n_levels), a feature index outside [0, n_kp) or listed twice, node ids not ascending.  Nothing is
+ * truncated; the handle stays usable.  Two kernels (k_tri_candidates, k_tri_resolve), one synchronisation. */
+int gfs_create_new_map_points(gfs_sbp* h, const gfs_tri_problem* problems, int B, gfs_tri_result* const* results);
+
 /* ============================================================================================
  * 8. GMS filter of the brute-force matches (the second half of ORBmatcher::SearchWithGMS / SearchForInitializationWithGMS)
  *      gms_matcher gms(kp1, frameSize, kp2, frameSize, matches_all); nmatches = gms.GetInlierMask(vbInliers, false, false);
