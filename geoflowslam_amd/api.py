@@ -278,6 +278,54 @@ def fuse_results(LL, KK, RR, keep, n_lists):
     return out
 
 
+MAP_POINTS_FULL, MAP_POINTS_NORMALS_ONLY = 0, 1            # GFS_MAP_POINTS_*
+MAP_POINT_OBS_IN_NORMAL, MAP_POINT_OBS_IN_DESC = 1, 2      # GFS_MAP_POINT_OBS_*
+MAP_POINT_NORMAL_SET, MAP_POINT_DESC_SET = 1, 2            # GFS_MAP_POINT_*_SET
+
+
+class MapPointsProblem(C.Structure):
+    _fields_ = [("n_points", C.c_int32), ("mode", C.c_int32), ("obs_start", C.c_void_p), ("obs_Ow", C.c_void_p), ("obs_desc", C.c_void_p),
+                ("obs_flags", C.c_void_p), ("pos", C.c_void_p), ("ref_Ow", C.c_void_p), ("level_scale", C.c_void_p),
+                ("max_scale", C.c_void_p)]
+
+
+class MapPointsResult(C.Structure):
+    _fields_ = [("best_obs", C.c_void_p), ("best_median", C.c_void_p), ("normal", C.c_void_p), ("min_dist", C.c_void_p),
+                ("max_dist", C.c_void_p), ("status", C.c_void_p)]
+
+
+def map_points_structs(prob, normals_only=False):
+    """ctypes views of one gfs_map_points_update call (shared with the CPU restatement's tests: same layout).  prob: a dict with the
+    keys of gfs_map_points_problem (n_points is len(obs_start) - 1) -> (problem, result, arrays kept alive).  A normals-only call
+    passes no descriptors.  The result arrays are pre-filled with a pattern no output has."""
+    a = dict(obs_start=np.ascontiguousarray(prob["obs_start"], np.int32),
+             obs_Ow=np.ascontiguousarray(prob["obs_Ow"], np.float32).reshape(-1, 3),
+             obs_flags=np.ascontiguousarray(prob["obs_flags"], np.uint8),
+             pos=np.ascontiguousarray(prob["pos"], np.float32).reshape(-1, 3),
+             ref_Ow=np.ascontiguousarray(prob["ref_Ow"], np.float32).reshape(-1, 3),
+             level_scale=np.ascontiguousarray(prob["level_scale"], np.float32),
+             max_scale=np.ascontiguousarray(prob["max_scale"], np.float32))
+    if not normals_only:
+        a["obs_desc"] = np.ascontiguousarray(prob["obs_desc"], np.uint8).reshape(-1, 32)
+    P, R = MapPointsProblem(), MapPointsResult()
+    P.n_points = len(a["obs_start"]) - 1
+    P.mode = MAP_POINTS_NORMALS_ONLY if normals_only else MAP_POINTS_FULL
+    for name, v in a.items():
+        setattr(P, name, v.ctypes.data)
+    n = max(P.n_points, 1)
+    out = dict(best_obs=np.full(n, -9, np.int32), best_median=np.full(n, -9, np.int32), normal=np.full((n, 3), -9.0, np.float32),
+               min_dist=np.full(n, -9.0, np.float32), max_dist=np.full(n, -9.0, np.float32), status=np.full(n, 0xEE, np.uint8))
+    for name, v in out.items():
+        setattr(R, name, v.ctypes.data)
+    a.update(out)
+    return P, R, a
+
+
+def map_points_results(P, keep):
+    n = P.n_points
+    return {k: keep[k][:n].copy() for k in ("best_obs", "best_median", "normal", "min_dist", "max_dist", "status")}
+
+
 TRI_EXITS = ("no_match", "low_parallax", "svd_w_zero", "unproject_failed", "behind_1", "behind_2", "reproj_1", "reproj_2", "zero_dist", "far",
              "scale", "created")  # GFS_TRI_*
 
@@ -516,6 +564,7 @@ ABI_SYMBOLS = [
     "gfs_sbp_create", "gfs_sbp_destroy", "gfs_search_by_projection", "gfs_search_by_projection_map",
     "gfs_sbp_reserve_local", "gfs_search_local_points", "gfs_sbp_reserve_fuse", "gfs_fuse_search", "gfs_test_glibc_logf",
     "gfs_sbp_reserve_triangulation", "gfs_create_new_map_points",
+    "gfs_map_points_create", "gfs_map_points_destroy", "gfs_map_points_update",
     "gfs_klt_create", "gfs_klt_destroy", "gfs_klt_layout", "gfs_klt_pyramid_create", "gfs_klt_pyramid_destroy",
     "gfs_klt_build_pyramid", "gfs_klt_build_pyramid_device", "gfs_klt_pyramid_download", "gfs_klt_track", "gfs_klt_fb_track",
     "gfs_klt_fb_track_device",
@@ -559,6 +608,9 @@ def lib():
         L.gfs_fuse_search.argtypes = [vp, C.POINTER(FusePoints), i, C.POINTER(FuseKeyframe), i, C.POINTER(FuseResult)]
         L.gfs_sbp_reserve_triangulation.argtypes = [vp, i, C.c_int64]
         L.gfs_create_new_map_points.argtypes = [vp, C.POINTER(TriProblem), i, C.POINTER(C.POINTER(TriResult))]
+        L.gfs_map_points_create.argtypes = [i, i, i, C.POINTER(vp)]
+        L.gfs_map_points_destroy.argtypes = [vp]
+        L.gfs_map_points_update.argtypes = [vp, C.POINTER(MapPointsProblem), C.POINTER(MapPointsResult)]
         L.gfs_test_traffic.argtypes = [i, i, C.c_longlong, C.c_longlong, i, C.POINTER(C.c_longlong)]
         L.gfs_hamming256.argtypes = [vp, vp]
         L.gfs_matcher_create.argtypes = [i, i, i, i, C.POINTER(vp)]
@@ -1523,6 +1575,30 @@ class ProjectionMatcher:
         _check(lib().gfs_create_new_map_points(self.h, PP, len(probs), RP), "gfs_create_new_map_points")
         res = tri_results(PP, RP, keep, len(probs))
         return res[0] if single else res
+
+
+class MapPointUpdater:
+    """MapPoint::ComputeDistinctiveDescriptors and MapPoint::UpdateNormalAndDepth (reference src/MapPoint.cc:376-448, :468-532) for
+    any number of map points in one device call (gfs_map_points_problem in include/gfs_abi.h)."""
+
+    def __init__(self, max_points=4096, max_observations=65536, device=0):
+        self.h = C.c_void_p()
+        _check(lib().gfs_map_points_create(device, int(max_points), int(max_observations), C.byref(self.h)), "gfs_map_points_create")
+
+    def close(self):
+        if getattr(self, "h", None) and _lib is not None:
+            _lib.gfs_map_points_destroy(self.h)
+        self.h = None
+
+    __del__ = close
+
+    def update(self, problem, normals_only=False):
+        """problem: a dict with the keys of gfs_map_points_problem (synth.map_point_update_problem) -> dict of best_obs, best_median,
+        normal [n, 3], min_dist, max_dist, status.  normals_only: UpdateNormalAndDepth alone; no descriptor is uploaded and best_obs
+        and best_median are -1."""
+        P, R, keep = map_points_structs(problem, normals_only)
+        _check(lib().gfs_map_points_update(self.h, C.byref(P), C.byref(R)), "gfs_map_points_update")
+        return map_points_results(P, keep)
 
 
 class PoseOptimizer:

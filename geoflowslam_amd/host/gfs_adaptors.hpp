@@ -33,6 +33,7 @@
 
 #include "../../include/gfs_abi.h"
 #include "../csrc/fuse_rule.hpp"
+#include "../csrc/map_point_rule.hpp"
 #include "../csrc/triangulate_rule.hpp"
 
 namespace gfs_host {
@@ -250,6 +251,10 @@ class LocalBundleAdjuster {
   template <class Access, class KeyFrame, class Map>
   void LocalBundleAdjustment(KeyFrame* pKF, bool* pbStopFlag, Map* pMap, int& num_fixedKF, int& num_OptKF, int& num_MPs,
                              int& num_edges);
+  // ... with the write-back's UpdateNormalAndDepth loop as one call of `update_points` (MapPointUpdater::solver())
+  template <class Access, class KeyFrame, class Map, class UpdatePoints>
+  void LocalBundleAdjustment(KeyFrame* pKF, bool* pbStopFlag, Map* pMap, int& num_fixedKF, int& num_OptKF, int& num_MPs,
+                             int& num_edges, UpdatePoints&& update_points);
   // LocalVisualLidarBA's numeric core on the handle's owned local map (gfs_lba_solve_lidar_bool); false when *pbStopFlag was set
   bool solve_lidar(const gfs_lba_problem& p, gfs_lba_lidar lidar, gfs_lba_solution& s, const bool* pbStopFlag,
                    int32_t* pose_lidar_edges = nullptr) {
@@ -293,6 +298,198 @@ class LocalBundleAdjuster {
   std::unique_ptr<LidarLocalMapper> mapper_;  // created at the first BuildLocalMap
   gfs_lidar_map* map_ = nullptr;  // created at the first LocalVisualLidarBA
   int map_cap_ = 0, lidar_cap_ = 0;
+};
+
+// ------------------------------------------------------------------------------------------------------------------------
+// void MapPoint::ComputeDistinctiveDescriptors()                                           reference src/MapPoint.cc:376-448
+// void MapPoint::UpdateNormalAndDepth()                                                    reference src/MapPoint.cc:468-532
+// void LocalMapping::ProcessNewKeyFrame(), its map-point loop                              reference src/LocalMapping.cc:439-454
+// as real code around gfs_map_points_update, for a whole list of map points at once.  A point's update reads
+// its own observation list, its position and reference key frame, and of the key frames only what the loops around it never write
+// (camera centre, descriptors, isBad, the level tables); the two functions write disjoint fields (mDescriptor; mNormalVector,
+// mfMinDistance, mfMaxDistance) that neither reads.  So the points of a loop are independent, and one call serves the loop:
+//   gather:  per point, GetObservations() in map order.  A null or bad point uploads an empty list (both functions return at once).
+//            IN_NORMAL is leftIndex != -1 (:494); IN_DESC is a key frame that is not null and not bad with leftIndex != -1 and
+//            < its descriptor rows (:396-403).  The reference key frame's level is read at observations[pRefKF], which is index 0
+//            when the reference key frame is not among the observations (std::map::operator[] inserts a zero tuple, :511).
+//   solve:   `solve(problem, result)`: MapPointUpdater::solve below (the GPU), or map_points_update_host (the same rule on the host).
+//   write:   set_normal_and_depth where the status says NORMAL_SET, set_descriptor with the chosen observation's row where DESC_SET.
+// In normals-only mode IN_DESC is never set and descriptor_rows / descriptors / set_descriptor are not called.
+// Single-camera key frames only: a right index, NLeft != -1, or a null key frame that UpdateNormalAndDepth would dereference throws.
+// Compile with -ffp-contract=off when map_points_update_host is used (the host rule is the device's arithmetic).
+//
+// MapPoint / KeyFrame are the reference's own classes, used through pMP->isBad(), GetObservations(), IsInKeyFrame, AddObservation;
+// pKF->isBad(), NLeft, mvScaleFactors, mnScaleLevels, GetMapPointMatches.  `Access` (world_pos, keys_un, descriptors as for Fuse) plus:
+//     static int descriptor_rows(const KeyFrame&);                                   // mDescriptors.rows
+//     static void camera_center(const KeyFrame&, float Ow[3]);                       // GetCameraCenter()
+//     static KeyFrame* reference_keyframe(const MapPoint*);                          // GetReferenceKeyFrame()
+//     static void set_descriptor(MapPoint*, const uint8_t row[32]);                  // mDescriptor = row.clone() under mMutexFeatures
+//     static void set_normal_and_depth(MapPoint*, const float normal[3], float min_distance, float max_distance);  // under mMutexPos
+// ------------------------------------------------------------------------------------------------------------------------
+struct PerPointUpdate {};  // in place of a map-point solver: the adaptor calls the reference's own per-point functions
+
+// gfs_map_points_update on the host: one thread, the rule of csrc/map_point_rule.hpp, the library's refusals
+inline int map_points_update_host(const gfs_map_points_problem* pr, gfs_map_points_result* res) {
+  if (!pr || !res || pr->n_points < 0 || !pr->obs_start || pr->obs_start[0] != 0) return GFS_ERR_INVALID_ARG;
+  if (pr->mode != GFS_MAP_POINTS_FULL && pr->mode != GFS_MAP_POINTS_NORMALS_ONLY) return GFS_ERR_INVALID_ARG;
+  const bool with_desc = pr->mode == GFS_MAP_POINTS_FULL;
+  for (int p = 0; p < pr->n_points; p++)
+    if (pr->obs_start[p + 1] < pr->obs_start[p]) return GFS_ERR_INVALID_ARG;
+  if (pr->n_points == 0) return GFS_OK;
+  const int O = pr->obs_start[pr->n_points];
+  if (!pr->pos || !pr->ref_Ow || !pr->level_scale || !pr->max_scale) return GFS_ERR_INVALID_ARG;
+  if (O > 0 && (!pr->obs_Ow || !pr->obs_flags || (with_desc && !pr->obs_desc))) return GFS_ERR_INVALID_ARG;
+  if (!res->best_obs || !res->best_median || !res->normal || !res->min_dist || !res->max_dist || !res->status) return GFS_ERR_INVALID_ARG;
+  for (int p = 0; p < pr->n_points; p++) {
+    const size_t a = (size_t)pr->obs_start[p];
+    const int n = pr->obs_start[p + 1] - pr->obs_start[p];
+    const gfs_mp::PointResult r = gfs_mp::update_point(n, n ? pr->obs_Ow + 3 * a : nullptr, with_desc && n ? pr->obs_desc + 32 * a : nullptr,
+                                                       n ? pr->obs_flags + a : nullptr, pr->pos + 3 * (size_t)p, pr->ref_Ow + 3 * (size_t)p,
+                                                       pr->level_scale[p], pr->max_scale[p], with_desc);
+    res->best_obs[p] = r.best_obs;
+    res->best_median[p] = r.best_median;
+    for (int c = 0; c < 3; c++) res->normal[3 * (size_t)p + c] = r.normal[c];
+    res->min_dist[p] = r.min_dist;
+    res->max_dist[p] = r.max_dist;
+    res->status[p] = (uint8_t)r.status;
+  }
+  return GFS_OK;
+}
+
+template <class Access, class MapPoint, class Solve>
+void UpdateMapPoints(Solve&& solve, const std::vector<MapPoint*>& points, int mode = GFS_MAP_POINTS_FULL) {
+  const size_t n = points.size();
+  if (n == 0) return;
+  const bool with_desc = mode == GFS_MAP_POINTS_FULL;
+  std::vector<int32_t> obs_start(n + 1, 0);
+  std::vector<float> obs_Ow, pos(3 * n, 0.0f), ref_Ow(3 * n, 0.0f), level_scale(n, 1.0f), max_scale(n, 1.0f);
+  std::vector<uint8_t> obs_flags, obs_desc;
+  std::vector<const uint8_t*> obs_row;  // the key frame's own row of every IN_DESC observation
+  for (size_t p = 0; p < n; p++) {
+    const MapPoint* pMP = points[p];
+    obs_start[p + 1] = obs_start[p];
+    if (!pMP || pMP->isBad()) continue;  // if (mbBad) return; (:384, :475)
+    const auto observations = pMP->GetObservations();
+    if (observations.empty()) continue;  // (:388, :481)
+    for (const auto& mit : observations) {
+      const auto* pKF = mit.first;
+      const int leftIndex = std::get<0>(mit.second), rightIndex = std::get<1>(mit.second);
+      if (rightIndex != -1 || (pKF && pKF->NLeft != -1)) throw std::invalid_argument("UpdateMapPoints: single-camera key frames only");
+      uint8_t flags = 0;
+      float Ow[3] = {0.0f, 0.0f, 0.0f};
+      const uint8_t* row = nullptr;
+      if (leftIndex != -1) {
+        if (!pKF) throw std::invalid_argument("UpdateMapPoints: an observation with an index and no key frame");
+        flags |= GFS_MAP_POINT_OBS_IN_NORMAL;
+        Access::camera_center(*pKF, Ow);
+      }
+      if (with_desc && pKF && !pKF->isBad() && leftIndex != -1 && leftIndex < Access::descriptor_rows(*pKF)) {  // (normals only: not asked)
+        flags |= GFS_MAP_POINT_OBS_IN_DESC;
+        row = Access::descriptors(*pKF) + 32 * (size_t)leftIndex;
+      }
+      obs_flags.push_back(flags);
+      obs_Ow.insert(obs_Ow.end(), Ow, Ow + 3);
+      obs_row.push_back(row);
+      if (with_desc) {
+        obs_desc.resize(obs_desc.size() + 32, 0);
+        if (row) std::memcpy(&obs_desc[obs_desc.size() - 32], row, 32);
+      }
+      obs_start[p + 1]++;
+    }
+    Access::world_pos(pMP, &pos[3 * p]);
+    auto* pRefKF = Access::reference_keyframe(pMP);
+    if (!pRefKF || pRefKF->NLeft != -1) throw std::invalid_argument("UpdateMapPoints: a single-camera reference key frame is needed");
+    Access::camera_center(*pRefKF, &ref_Ow[3 * p]);
+    const auto at = observations.find(pRefKF);
+    const int refIndex = at == observations.end() ? 0 : std::get<0>(at->second);  // observations[pRefKF] (:511)
+    if (refIndex < 0) throw std::invalid_argument("UpdateMapPoints: the reference key frame observes the point without an index");
+    const int level = Access::keys_un(*pRefKF)[refIndex].octave;
+    level_scale[p] = pRefKF->mvScaleFactors[level];
+    max_scale[p] = pRefKF->mvScaleFactors[pRefKF->mnScaleLevels - 1];
+  }
+  // (one spare element each: a vector's data() may be null when it is empty)
+  obs_Ow.resize(obs_Ow.size() + 3, 0.0f);
+  obs_flags.push_back(0);
+  obs_desc.resize(obs_desc.size() + 32, 0);
+  gfs_map_points_problem pr{};
+  pr.n_points = (int32_t)n;
+  pr.mode = mode;
+  pr.obs_start = obs_start.data();
+  pr.obs_Ow = obs_Ow.data();
+  pr.obs_desc = with_desc ? obs_desc.data() : nullptr;
+  pr.obs_flags = obs_flags.data();
+  pr.pos = pos.data();
+  pr.ref_Ow = ref_Ow.data();
+  pr.level_scale = level_scale.data();
+  pr.max_scale = max_scale.data();
+  std::vector<int32_t> best_obs(n, -1), best_median(n, -1);
+  std::vector<float> normal(3 * n, 0.0f), min_dist(n, 0.0f), max_dist(n, 0.0f);
+  std::vector<uint8_t> status(n, 0);
+  gfs_map_points_result res{best_obs.data(), best_median.data(), normal.data(), min_dist.data(), max_dist.data(), status.data()};
+  check(solve(&pr, &res), "gfs_map_points_update");
+  for (size_t p = 0; p < n; p++) {
+    MapPoint* pMP = points[p];
+    if (status[p] & GFS_MAP_POINT_DESC_SET) Access::set_descriptor(pMP, obs_row[(size_t)obs_start[p] + (size_t)best_obs[p]]);
+    if (status[p] & GFS_MAP_POINT_NORMAL_SET) Access::set_normal_and_depth(pMP, &normal[3 * p], min_dist[p], max_dist[p]);
+  }
+}
+
+// The map-point loop of LocalMapping::ProcessNewKeyFrame (:439-454): the first pass adds the observations and fills
+// mlpRecentAddedMapPoints exactly as the loop does; the points that took the first branch are then updated in one call (a point
+// listed twice takes the else branch the second time, so no point is updated before its last AddObservation of this loop).
+// ComputeBoW, UpdateConnections and Atlas::AddKeyFrame stay with the caller.  If the gather of the second step throws (a two-camera
+// observation, a point without a reference key frame), the first pass has already happened: the observations are added and
+// mlpRecentAddedMapPoints is filled, and no point has been updated; the caller is left with a half-processed key frame.
+template <class Access, class KeyFrame, class MapPoint, class Solve>
+void ProcessNewKeyFrame(Solve&& solve, KeyFrame* pCurrentKF, std::list<MapPoint*>& mlpRecentAddedMapPoints) {
+  const std::vector<MapPoint*> vpMapPointMatches = pCurrentKF->GetMapPointMatches();
+  std::vector<MapPoint*> added;
+  for (size_t i = 0; i < vpMapPointMatches.size(); i++) {
+    MapPoint* pMP = vpMapPointMatches[i];
+    if (pMP) {
+      if (!pMP->isBad()) {
+        if (!pMP->IsInKeyFrame(pCurrentKF)) {
+          pMP->AddObservation(pCurrentKF, (int)i);
+          added.push_back(pMP);
+        } else {  // this can only happen for new stereo points inserted by the Tracking
+          mlpRecentAddedMapPoints.push_back(pMP);
+        }
+      }
+    }
+  }
+  UpdateMapPoints<Access>(solve, added, GFS_MAP_POINTS_FULL);
+}
+
+// the numeric core of the map-point update on the GPU: one handle, its reserve grown to the largest call seen
+class MapPointUpdater {
+ public:
+  explicit MapPointUpdater(int max_points = 4096, int max_observations = 65536, int device = 0)
+      : device_(device), points_(max_points), obs_(max_observations) {
+    check(gfs_map_points_create(device_, points_, obs_, &h_), "gfs_map_points_create");
+  }
+  ~MapPointUpdater() { gfs_map_points_destroy(h_); }
+  MapPointUpdater(const MapPointUpdater&) = delete;
+  MapPointUpdater& operator=(const MapPointUpdater&) = delete;
+  int solve(const gfs_map_points_problem* p, gfs_map_points_result* r) {
+    const int n_obs = (p && p->obs_start && p->n_points > 0) ? p->obs_start[p->n_points] : 0;
+    if (p && (p->n_points > points_ || n_obs > obs_)) {  // the library refuses what exceeds the reserve (it never truncates): grow it first
+      const int np = std::max(p->n_points, points_), no = std::max(n_obs, obs_);
+      gfs_map_points* bigger = nullptr;
+      check(gfs_map_points_create(device_, np, no, &bigger), "gfs_map_points_create");
+      gfs_map_points_destroy(h_);
+      h_ = bigger;
+      points_ = np;
+      obs_ = no;
+    }
+    return gfs_map_points_update(h_, p, r);
+  }
+  auto solver() {
+    return [this](const gfs_map_points_problem* p, gfs_map_points_result* r) { return solve(p, r); };
+  }
+
+ private:
+  gfs_map_points* h_ = nullptr;
+  int device_ = 0, points_ = 0, obs_ = 0;
 };
 
 // ------------------------------------------------------------------------------------------------------------------------
@@ -357,9 +554,15 @@ struct LbaFlat {  // the flattened graph, in the reference's vertex / edge creat
 // `solve` is called as solve(problem, solution, pbStopFlag), or -- when it takes them -- with two more arguments: the key-frame of
 // every pose in the problem's pose order (lLocalKeyFrames in list order, then lFixedCameras) and the number of local key-frames.
 // LocalVisualLidarBA (below) gathers its per-key-frame data through them.
-template <class Access, class KeyFrame, class MapPoint, class Map, class Solve>
+// `update_points`, when given, is a map-point solver (MapPointUpdater::solver(), or map_points_update_host): the write-back then runs
+// UpdateNormalAndDepth for all local map points in one normals-only call after the poses and positions are set (exact: a point's
+// update reads its own position and the camera centres, and writes what no other point's update reads); `Access` then needs the
+// members of UpdateMapPoints too.
+template <class Access, class KeyFrame, class MapPoint, class Map, class Solve, class UpdatePoints = PerPointUpdate>
 void LocalBundleAdjustment(Solve&& solve, KeyFrame* pKF, bool* pbStopFlag, Map* pMap, int& num_fixedKF, int& num_OptKF,
-                           int& /*num_MPs: never written by the reference either*/, int& num_edges) {
+                           int& /*num_MPs: never written by the reference either*/, int& num_edges,
+                           UpdatePoints&& update_points = UpdatePoints()) {
+  constexpr bool kPerPoint = std::is_same<typename std::decay<UpdatePoints>::type, PerPointUpdate>::value;
   // ---- Local KeyFrames: first breadth search from the current key-frame (:1592-1607)
   std::list<KeyFrame*> lLocalKeyFrames;
   lLocalKeyFrames.push_back(pKF);
@@ -528,8 +731,12 @@ void LocalBundleAdjustment(Solve&& solve, KeyFrame* pKF, bool* pbStopFlag, Map* 
       float X[3];
       for (int c = 0; c < 3; c++) X[c] = (float)out_p[3 * (size_t)k + c];
       Access::set_world_pos(pMP, X);
-      pMP->UpdateNormalAndDepth();
+      if constexpr (kPerPoint) pMP->UpdateNormalAndDepth();
       k++;
+    }
+    if constexpr (!kPerPoint) {
+      const std::vector<MapPoint*> vpLocal(lLocalMapPoints.begin(), lLocalMapPoints.end());
+      UpdateMapPoints<Access>(update_points, vpLocal, GFS_MAP_POINTS_NORMALS_ONLY);
     }
   }
   pMap->IncreaseChangeIndex();
@@ -542,6 +749,15 @@ void LocalBundleAdjuster::LocalBundleAdjustment(KeyFrame* pKF, bool* pbStopFlag,
   gfs_host::LocalBundleAdjustment<Access, KeyFrame, MapPoint, Map>(
       [this](const gfs_lba_problem& p, gfs_lba_solution& s, const bool* stop) { return this->solve(p, s, stop); }, pKF, pbStopFlag,
       pMap, num_fixedKF, num_OptKF, num_MPs, num_edges);
+}
+
+template <class Access, class KeyFrame, class Map, class UpdatePoints>
+void LocalBundleAdjuster::LocalBundleAdjustment(KeyFrame* pKF, bool* pbStopFlag, Map* pMap, int& num_fixedKF, int& num_OptKF,
+                                                int& num_MPs, int& num_edges, UpdatePoints&& update_points) {
+  using MapPoint = typename std::remove_pointer<typename decltype(pKF->GetMapPointMatches())::value_type>::type;
+  gfs_host::LocalBundleAdjustment<Access, KeyFrame, MapPoint, Map>(
+      [this](const gfs_lba_problem& p, gfs_lba_solution& s, const bool* stop) { return this->solve(p, s, stop); }, pKF, pbStopFlag,
+      pMap, num_fixedKF, num_OptKF, num_MPs, num_edges, update_points);
 }
 
 // ------------------------------------------------------------------------------------------------------------------------
@@ -1265,9 +1481,11 @@ struct SearchInNeighborsCounts {
 // device call: list 0 against all targets), the targets' points in the current key frame (a second call: one list, one key frame),
 // then the update of the current key frame's points and connections.  The caller keeps the target selection (:1131-1177);
 // pbAbortBA is mbAbortBA, looked at where the reference looks (:1191).
-template <class Access, class KeyFrame, class Solve>
+// `update_points`, when given, is a map-point solver (MapPointUpdater::solver(), or map_points_update_host): the update of the current
+// key frame's points is then one UpdateMapPoints call; `Access` then needs its members too.
+template <class Access, class KeyFrame, class Solve, class UpdatePoints = PerPointUpdate>
 SearchInNeighborsCounts SearchInNeighborsFuse(Solve&& solve, KeyFrame* pCurrentKF, const std::vector<KeyFrame*>& vpTargetKFs,
-                                              const bool* pbAbortBA = nullptr, float th = 3.0f) {
+                                              const bool* pbAbortBA = nullptr, float th = 3.0f, UpdatePoints&& update_points = UpdatePoints()) {
   using MapPoint = std::remove_pointer_t<typename decltype(pCurrentKF->GetMapPointMatches())::value_type>;
   SearchInNeighborsCounts c;
   if (pCurrentKF->NLeft != -1 || !Access::is_pinhole(*pCurrentKF)) throw std::invalid_argument("Fuse: single-camera pinhole key frames only");
@@ -1305,11 +1523,15 @@ SearchInNeighborsCounts SearchInNeighborsFuse(Solve&& solve, KeyFrame* pCurrentK
   c.fused_in_current = Fuse<Access>(solve, pCurrentKF, vpFuseCandidates, th, &c.recomputed);
   // Update points
   vpMapPointMatches = pCurrentKF->GetMapPointMatches();
-  for (MapPoint* pMP : vpMapPointMatches) {
-    if (pMP && !pMP->isBad()) {
-      pMP->ComputeDistinctiveDescriptors();
-      pMP->UpdateNormalAndDepth();
+  if constexpr (std::is_same<typename std::decay<UpdatePoints>::type, PerPointUpdate>::value) {
+    for (MapPoint* pMP : vpMapPointMatches) {
+      if (pMP && !pMP->isBad()) {
+        pMP->ComputeDistinctiveDescriptors();
+        pMP->UpdateNormalAndDepth();
+      }
     }
+  } else {
+    UpdateMapPoints<Access>(update_points, vpMapPointMatches, GFS_MAP_POINTS_FULL);  // (null and bad entries upload empty lists)
   }
   // Update connections in covisibility graph
   pCurrentKF->UpdateConnections();

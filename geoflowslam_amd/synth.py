@@ -947,3 +947,54 @@ def triangulation_problem(seed, n_kp=1000, n_neighbours=10, n_nodes=100, n_kp_ne
         neighbours.append(nb)
     return dict(cur=cur, neighbours=neighbours, only_stereo=only_stereo, coarse=coarse, check_orientation=check_orientation, inertial=inertial,
                 far_points=far_points, th_far_points=f32(th_far_points), ratio_factor=f32(f32(1.5) * f32(scale_factor)))
+
+
+def map_point_update_problem(seed, n_points=1000, obs_counts=(1, 20), n_keyframes=40, flip_bits=40, scale_factor=1.2, n_levels=8):
+    """Synthetic input of MapPoint::ComputeDistinctiveDescriptors and MapPoint::UpdateNormalAndDepth (reference src/MapPoint.cc:376-448,
+    :468-532) for `n_points` map points, as gfs_map_points_update takes it (include/gfs_abi.h): a dict with the keys of
+    gfs_map_points_problem.  obs_counts: the observations per point, an int, an inclusive (lo, hi) range or one count per point.
+
+    Camera centres are drawn per key frame; a point's observations are key frames in ascending index (the pointer order of
+    mObservations), distinct while there are enough.  A descriptor is the point's base pattern with 0..`flip_bits` random bits
+    flipped, so rows tie in their median and the best row is rarely the first.  One observation in twelve is IN_NORMAL only (a bad
+    key frame, or an index beyond mDescriptors.rows), one in thirty carries neither flag (leftIndex == -1), and every 17th point has
+    no IN_DESC observation at all.  The reference key frame is one of the point's own observations."""
+    rng = np.random.default_rng(seed + 32452843)
+    if np.isscalar(obs_counts):
+        counts = np.full(n_points, int(obs_counts), np.int64)
+    elif isinstance(obs_counts, tuple) and len(obs_counts) == 2:
+        counts = rng.integers(obs_counts[0], obs_counts[1] + 1, size=n_points)
+    else:
+        counts = np.asarray(obs_counts, np.int64)
+        assert len(counts) == n_points
+    obs_start = np.zeros(n_points + 1, np.int32)
+    obs_start[1:] = np.cumsum(counts)
+    n_obs = int(obs_start[-1])
+    kf_Ow = (rng.normal(size=(n_keyframes, 3)) * [1.5, 0.3, 1.5]).astype(np.float32)
+    pos = (rng.uniform([-4, -1.5, 2], [4, 1.5, 9], size=(n_points, 3))).astype(np.float32)
+    scale = np.cumprod(np.r_[1.0, np.full(n_levels - 1, float(scale_factor))]).astype(np.float32)
+    obs_kf = np.zeros(n_obs, np.int32)
+    obs_desc = np.zeros((n_obs, 32), np.uint8)
+    obs_flags = np.zeros(n_obs, np.uint8)
+    ref_Ow = np.zeros((n_points, 3), np.float32)
+    level_scale = np.ones(n_points, np.float32)
+    for p in range(n_points):
+        a, n = int(obs_start[p]), int(counts[p])
+        kfs = np.sort(rng.choice(n_keyframes, size=n, replace=n > n_keyframes))
+        obs_kf[a:a + n] = kfs
+        base = np.unpackbits(rng.integers(0, 256, size=32, dtype=np.uint8))
+        for i in range(n):
+            bits = base.copy()
+            k = int(rng.integers(0, flip_bits + 1))
+            if k:
+                bits[rng.choice(256, size=k, replace=False)] ^= 1
+            obs_desc[a + i] = np.packbits(bits)
+        r = rng.random(n)
+        fl = np.where(r < 1 / 30, 0, np.where(r < 1 / 30 + 1 / 12, 1, 3)).astype(np.uint8)
+        if p % 17 == 16:
+            fl &= 1
+        obs_flags[a:a + n] = fl
+        ref_Ow[p] = kf_Ow[kfs[int(rng.integers(0, n))]] if n else kf_Ow[int(rng.integers(0, n_keyframes))]
+        level_scale[p] = scale[int(rng.integers(0, n_levels))]
+    return dict(obs_start=obs_start, obs_kf=obs_kf, obs_Ow=kf_Ow[obs_kf].reshape(-1, 3).copy(), obs_desc=obs_desc, obs_flags=obs_flags,
+                pos=pos, ref_Ow=ref_Ow, level_scale=level_scale, max_scale=np.full(n_points, scale[-1], np.float32))
