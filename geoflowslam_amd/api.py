@@ -122,6 +122,13 @@ def pose_result(S, keep, n):
                 iterations_run=int(S.iterations_run))
 
 
+class ClaheConfig(C.Structure):
+    _fields_ = [("clip_limit", C.c_double), ("tiles_x", C.c_int32), ("tiles_y", C.c_int32), ("residual_variant", C.c_int32)]
+
+
+CLAHE_RESIDUAL_STEPPED, CLAHE_RESIDUAL_CONTIGUOUS = 0, 1  # GFS_CLAHE_RESIDUAL_* (include/gfs_abi.h)
+
+
 class GmsProblem(C.Structure):
     _fields_ = [("n1", C.c_int32), ("n2", C.c_int32), ("kp1", C.c_void_p), ("kp2", C.c_void_p), ("width1", C.c_int32),
                 ("height1", C.c_int32), ("width2", C.c_int32), ("height2", C.c_int32), ("n_matches", C.c_int32),
@@ -570,6 +577,8 @@ ABI_SYMBOLS = [
     "gfs_klt_fb_track_device",
     "gfs_fmat_create", "gfs_fmat_destroy", "gfs_find_fundamental_ransac", "gfs_find_fundamental_ransac_device",
     "gfs_klt_compact_tracks_device", "gfs_klt_apply_mask_device",
+    "gfs_clahe_default_config", "gfs_clahe_create", "gfs_clahe_destroy", "gfs_clahe_apply", "gfs_clahe_apply_device",
+    "gfs_clahe_download_luts", "gfs_klt_build_pyramid_clahe", "gfs_klt_build_pyramid_clahe_device",
     "gfs_timer_create", "gfs_timer_destroy", "gfs_timer_start", "gfs_timer_stop", "gfs_timer_elapsed_ms",
     "gfs_profile_enable", "gfs_profile_report", "gfs_profile_reset",
 ]
@@ -682,6 +691,15 @@ def lib():
             L.gfs_klt_fb_track_device.argtypes = [vp, vp, vp, i, i, vp, vp, vp, vp, vp, i, f, f, vp]
             L.gfs_klt_compact_tracks_device.argtypes = [vp, i, i, vp, vp, vp, vp, vp, vp, vp, vp, vp]
             L.gfs_klt_apply_mask_device.argtypes = [vp, i, i, vp, vp, vp, vp, vp]
+        L.gfs_clahe_default_config.argtypes = [C.POINTER(ClaheConfig)]
+        L.gfs_clahe_default_config.restype = None
+        L.gfs_clahe_create.argtypes = [i, i, i, i, C.POINTER(ClaheConfig), C.POINTER(vp)]
+        L.gfs_clahe_destroy.argtypes = [vp]
+        L.gfs_clahe_apply.argtypes = [vp, vp, i, i, i, i, vp, i]
+        L.gfs_clahe_apply_device.argtypes = [vp, vp, i, i, i, i, vp, i, vp]
+        L.gfs_clahe_download_luts.argtypes = [vp, i, vp]
+        L.gfs_klt_build_pyramid_clahe.argtypes = [vp, vp, vp, vp, i, i, vp, i]
+        L.gfs_klt_build_pyramid_clahe_device.argtypes = [vp, vp, vp, vp, i, i, vp, i, vp]
         if hasattr(L, "gfs_fmat_create"):
             L.gfs_fmat_create.argtypes = [i, i, i, C.POINTER(vp)]
             L.gfs_fmat_destroy.argtypes = [vp]
@@ -1289,6 +1307,55 @@ class GmsMatcher:
 KLT_USE_INITIAL_FLOW, KLT_GET_MIN_EIGENVALS = 4, 8
 
 
+class Clahe:
+    """cv::CLAHE on 8-bit single-channel images (cv::createCLAHE(3.0, cv::Size(8, 8)) of src/Frame.cc:367), DESIGN.md section 16.
+    residual_variant: CLAHE_RESIDUAL_STEPPED (OpenCV >= 3.4) or CLAHE_RESIDUAL_CONTIGUOUS (OpenCV <= 3.3)."""
+
+    def __init__(self, max_width=640, max_height=480, max_batch=1, clip_limit=3.0, tiles=(8, 8),
+                 residual_variant=CLAHE_RESIDUAL_STEPPED, device=0):
+        cfg = ClaheConfig()
+        lib().gfs_clahe_default_config(C.byref(cfg))
+        cfg.clip_limit, cfg.tiles_x, cfg.tiles_y, cfg.residual_variant = float(clip_limit), tiles[0], tiles[1], residual_variant
+        self.tiles = (int(tiles[0]), int(tiles[1]))
+        self.h = C.c_void_p()
+        _check(lib().gfs_clahe_create(device, max_width, max_height, max_batch, C.byref(cfg), C.byref(self.h)), "gfs_clahe_create")
+
+    def close(self):
+        if getattr(self, "h", None) and _lib is not None:
+            _lib.gfs_clahe_destroy(self.h)
+        self.h = None
+
+    __del__ = close
+
+    def apply(self, images, out=None):
+        """images: one [H, W] u8 array or a list of equally sized ones; rows may be padded (a view with a row stride), all images
+        with the same stride.  -> the equalised image(s), written into `out` (same form as `images`, may be `images`) when given."""
+        single = isinstance(images, np.ndarray) and images.ndim == 2
+        imgs = [images] if single else list(images)
+        outs = [np.empty(im.shape, np.uint8) for im in imgs] if out is None else ([out] if single else list(out))
+        H, W = imgs[0].shape
+        for a in imgs + outs:
+            if a.dtype != np.uint8 or a.shape != (H, W) or a.strides[1] != 1 or a.strides[0] < W:
+                raise GfsError("Clahe.apply: images must be equally sized u8 arrays with contiguous rows")
+        if len({im.strides[0] for im in imgs}) != 1 or len({o.strides[0] for o in outs}) != 1 or len(outs) != len(imgs):
+            raise GfsError("Clahe.apply: one stride for all images, one for all outputs")
+        ip = (C.c_void_p * len(imgs))(*[im.ctypes.data for im in imgs])
+        op = (C.c_void_p * len(outs))(*[o.ctypes.data for o in outs])
+        _check(lib().gfs_clahe_apply(self.h, ip, W, H, imgs[0].strides[0], len(imgs), op, outs[0].strides[0]), "gfs_clahe_apply")
+        return outs[0] if single else outs
+
+    def apply_device(self, d_in, width, height, in_stride, B, d_out, out_stride, stream=None):
+        """Device pointers ([B][height][stride] bytes); d_out may be d_in when the strides are equal."""
+        _check(lib().gfs_clahe_apply_device(self.h, C.c_void_p(d_in), width, height, in_stride, B, C.c_void_p(d_out), out_stride,
+                                            C.c_void_p(stream) if stream else None), "gfs_clahe_apply_device")
+
+    def luts(self, f=0):
+        """The look-up tables of frame f of the last call -> [tiles_y, tiles_x, 256] u8."""
+        lut = np.zeros((self.tiles[1], self.tiles[0], 256), np.uint8)
+        _check(lib().gfs_clahe_download_luts(self.h, f, _p(lut)), "gfs_clahe_download_luts")
+        return lut
+
+
 class KltPyramid:
     """The optical-flow pyramids (cv::buildOpticalFlowPyramid output, images + derivatives) of a batch of frames, resident in HBM."""
 
@@ -1336,22 +1403,39 @@ class KltTracker:
             raise GfsError("gfs_klt_layout failed")
         return lw[:n].copy(), lh[:n].copy(), off[:n + 1].copy()
 
-    def buildOpticalFlowPyramid(self, images, pyramid=None):
-        """images: one [H, W] u8 array or a list of them -> KltPyramid (reused when given)."""
-        if isinstance(images, np.ndarray) and images.ndim == 2:
+    def buildOpticalFlowPyramid(self, images, pyramid=None, clahe=None, return_equalized=False):
+        """images: one [H, W] u8 array or a list of them -> KltPyramid (reused when given).  clahe: a Clahe whose equalisation runs
+        on the device between the upload and the pyramid (src/Frame.cc:366-373); return_equalized: -> (KltPyramid, Frame::image as
+        one array or a list, like `images`)."""
+        single = isinstance(images, np.ndarray) and images.ndim == 2
+        if single:
             images = [images]
         imgs = [np.ascontiguousarray(im, np.uint8) for im in images]
         for im in imgs:
             if im.shape != (self.height, self.width):
                 raise GfsError(f"image shape {im.shape} != {(self.height, self.width)}")
+        if return_equalized and clahe is None:
+            raise GfsError("buildOpticalFlowPyramid: return_equalized needs a Clahe")
         pyr = pyramid if pyramid is not None else KltPyramid(self)
         ptrs = (C.c_void_p * len(imgs))(*[im.ctypes.data for im in imgs])
-        _check(lib().gfs_klt_build_pyramid(self.h, pyr.h, ptrs, self.width, len(imgs)), "gfs_klt_build_pyramid")
-        return pyr
+        if clahe is None:
+            _check(lib().gfs_klt_build_pyramid(self.h, pyr.h, ptrs, self.width, len(imgs)), "gfs_klt_build_pyramid")
+            return pyr
+        eq = [np.empty_like(im) for im in imgs] if return_equalized else None
+        eptrs = (C.c_void_p * len(imgs))(*[e.ctypes.data for e in eq]) if eq else None
+        _check(lib().gfs_klt_build_pyramid_clahe(self.h, clahe.h, pyr.h, ptrs, self.width, len(imgs), eptrs, self.width),
+               "gfs_klt_build_pyramid_clahe")
+        return (pyr, eq[0] if single else eq) if return_equalized else pyr
 
     def build_pyramid_device(self, d_images, stride, B, pyramid, stream=None):
         _check(lib().gfs_klt_build_pyramid_device(self.h, pyramid.h, C.c_void_p(d_images), stride, B,
                                                   C.c_void_p(stream) if stream else None), "gfs_klt_build_pyramid_device")
+
+    def build_pyramid_clahe_device(self, clahe, d_images, stride, B, pyramid, d_equalized=None, eq_stride=0, stream=None):
+        """The device form with CLAHE in front; d_equalized None: the equalised images stay in the Clahe handle's scratch."""
+        _check(lib().gfs_klt_build_pyramid_clahe_device(self.h, clahe.h, pyramid.h, C.c_void_p(d_images), stride, B,
+                                                        C.c_void_p(d_equalized) if d_equalized else None, eq_stride,
+                                                        C.c_void_p(stream) if stream else None), "gfs_klt_build_pyramid_clahe_device")
 
     @staticmethod
     def _lists(pts):

@@ -24,6 +24,7 @@
 #include <memory>
 #include <mutex>
 
+#include "clahe_handle.hpp"
 #include "gfs_common.hpp"
 
 namespace {
@@ -1006,6 +1007,70 @@ int gfs_klt_apply_mask_device(gfs_klt* h, int B, int pt_stride, const void* dev_
   hipStream_t s = stream ? (hipStream_t)stream : h->stream;
   GFS_LAUNCH("k_klt_apply_mask", k_klt_apply_mask, dim3(gfs::div_up(pt_stride, 256), B), dim3(256), 0, s, (const int*)dev_m, pt_stride,
              (const int*)dev_index, (const uint8_t*)dev_mask, (uint8_t*)dev_kpstatus);
+  if (!stream) GFS_HIP(hipStreamSynchronize(s));
+  return GFS_OK;
+}
+
+// The Frame constructor's pair (src/Frame.cc:366-373): the image is equalised where gfs_klt_build_pyramid stages it, then the same
+// klt_build runs on it.
+int gfs_klt_build_pyramid_clahe(gfs_klt* h, gfs_clahe* clahe, gfs_klt_pyramid* pyr, const uint8_t* const* images, int stride, int B,
+                                uint8_t* const* equalized_out, int eq_stride) {
+  GFS_REQUIRE(h && clahe && pyr && images && B > 0, GFS_ERR_INVALID_ARG, "gfs_klt_build_pyramid_clahe: invalid argument");
+  GFS_REQUIRE(pyr->owner == h, GFS_ERR_INVALID_ARG, "gfs_klt_build_pyramid_clahe: the pyramid belongs to another tracker");
+  const gfs_clahe_core c = gfs_clahe_core_of(clahe);
+  const int W = h->G.width, H = h->G.height;
+  GFS_REQUIRE(c.device == h->device, GFS_ERR_INVALID_ARG, "gfs_klt_build_pyramid_clahe: tracker on device %d, CLAHE on device %d",
+              h->device, c.device);
+  GFS_REQUIRE(c.max_width >= W && c.max_height >= H, GFS_ERR_INVALID_ARG,
+              "gfs_klt_build_pyramid_clahe: CLAHE reserve %d x %d below the tracker's image %d x %d", c.max_width, c.max_height, W, H);
+  GFS_REQUIRE(B <= h->max_batch && B <= c.max_batch, GFS_ERR_CAPACITY, "gfs_klt_build_pyramid_clahe: batch %d exceeds capacity %d / %d", B,
+              h->max_batch, c.max_batch);
+  GFS_REQUIRE(stride >= W && (!equalized_out || eq_stride >= W), GFS_ERR_INVALID_ARG,
+              "gfs_klt_build_pyramid_clahe: stride %d / %d < width %d", stride, eq_stride, W);
+  for (int f = 0; f < B; f++)
+    GFS_REQUIRE(images[f] && (!equalized_out || equalized_out[f]), GFS_ERR_INVALID_ARG, "gfs_klt_build_pyramid_clahe: image %d is NULL", f);
+  std::lock_guard<std::mutex> lk(h->mu);  // always the tracker's lock first
+  std::lock_guard<std::mutex> lc(*c.mu);
+  GFS_HIP(hipSetDevice(h->device));
+  for (int f = 0; f < B; f++)
+    for (int y = 0; y < H; y++) memcpy(h->h_images.p + ((size_t)f * H + y) * W, images[f] + (size_t)y * stride, W);
+  GFS_HIP(hipMemcpyAsync(h->d_images.p, h->h_images.p, (size_t)B * W * H, hipMemcpyHostToDevice, h->stream));
+  int rc = gfs_clahe_enqueue(clahe, h->d_images.p, W, H, W, B, h->d_images.p, W, h->stream);
+  if (!rc) rc = klt_build(h, pyr, h->d_images.p, W, B, h->stream);
+  if (rc) return rc;
+  if (equalized_out) GFS_HIP(hipMemcpyAsync(h->h_images.p, h->d_images.p, (size_t)B * W * H, hipMemcpyDeviceToHost, h->stream));
+  GFS_HIP(hipStreamSynchronize(h->stream));
+  if (equalized_out)
+    for (int f = 0; f < B; f++)
+      for (int y = 0; y < H; y++) memcpy(equalized_out[f] + (size_t)y * eq_stride, h->h_images.p + ((size_t)f * H + y) * W, W);
+  return GFS_OK;
+}
+
+int gfs_klt_build_pyramid_clahe_device(gfs_klt* h, gfs_clahe* clahe, gfs_klt_pyramid* pyr, const void* dev_images, int stride, int B,
+                                       void* dev_equalized, int eq_stride, void* stream) {
+  GFS_REQUIRE(h && clahe && pyr && dev_images && B > 0, GFS_ERR_INVALID_ARG, "gfs_klt_build_pyramid_clahe_device: invalid argument");
+  GFS_REQUIRE(pyr->owner == h, GFS_ERR_INVALID_ARG, "gfs_klt_build_pyramid_clahe_device: the pyramid belongs to another tracker");
+  const gfs_clahe_core c = gfs_clahe_core_of(clahe);
+  const int W = h->G.width, H = h->G.height;
+  GFS_REQUIRE(c.device == h->device, GFS_ERR_INVALID_ARG, "gfs_klt_build_pyramid_clahe_device: tracker on device %d, CLAHE on device %d",
+              h->device, c.device);
+  GFS_REQUIRE(c.max_width >= W && c.max_height >= H, GFS_ERR_INVALID_ARG,
+              "gfs_klt_build_pyramid_clahe_device: CLAHE reserve %d x %d below the tracker's image %d x %d", c.max_width, c.max_height, W, H);
+  GFS_REQUIRE(B <= h->max_batch && B <= c.max_batch, GFS_ERR_CAPACITY, "gfs_klt_build_pyramid_clahe_device: batch %d exceeds capacity %d / %d",
+              B, h->max_batch, c.max_batch);
+  GFS_REQUIRE(stride >= W && (!dev_equalized || eq_stride >= W), GFS_ERR_INVALID_ARG,
+              "gfs_klt_build_pyramid_clahe_device: stride %d / %d < width %d", stride, eq_stride, W);
+  GFS_REQUIRE(dev_equalized != dev_images || eq_stride == stride, GFS_ERR_INVALID_ARG,
+              "gfs_klt_build_pyramid_clahe_device: in place needs equal strides (%d, %d)", stride, eq_stride);
+  std::lock_guard<std::mutex> lk(h->mu);
+  std::lock_guard<std::mutex> lc(*c.mu);
+  GFS_HIP(hipSetDevice(h->device));
+  hipStream_t s = stream ? (hipStream_t)stream : h->stream;
+  uint8_t* eq = dev_equalized ? (uint8_t*)dev_equalized : c.scratch;  // the scratch image is packed: W bytes a row
+  const int es = dev_equalized ? eq_stride : W;
+  int rc = gfs_clahe_enqueue(clahe, (const uint8_t*)dev_images, W, H, stride, B, eq, es, s);
+  if (!rc) rc = klt_build(h, pyr, eq, es, B, s);
+  if (rc) return rc;
   if (!stream) GFS_HIP(hipStreamSynchronize(s));
   return GFS_OK;
 }

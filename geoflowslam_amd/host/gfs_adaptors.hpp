@@ -863,6 +863,33 @@ class GmsMatcher {
 // The optical-flow front end: cv::buildOpticalFlowPyramid (reference src/Frame.cc:373), ORBmatcher::fbKltTracking
 // (src/ORBmatcher.cc:2186-2297 == Tracking::fbKltTracking, src/Tracking.cc:3262-3366).  A Pyramid is what Frame::mImGray holds in
 // the reference (a std::vector<cv::Mat>), kept in HBM; build it once per frame, use it as `cur` and then as `prev`.
+// cv::CLAHE on 8-bit single-channel images (cv::createCLAHE(3.0, cv::Size(8, 8)), reference src/Frame.cc:366-369, 499-500).
+// residual_variant: GFS_CLAHE_RESIDUAL_STEPPED (OpenCV >= 3.4) or GFS_CLAHE_RESIDUAL_CONTIGUOUS (OpenCV <= 3.3).
+class Clahe {
+ public:
+  Clahe(int max_width, int max_height, double clip_limit = 3.0, int tiles_x = 8, int tiles_y = 8,
+        int residual_variant = GFS_CLAHE_RESIDUAL_STEPPED, int device = 0) {
+    gfs_clahe_config cfg;
+    gfs_clahe_default_config(&cfg);
+    cfg.clip_limit = clip_limit;
+    cfg.tiles_x = tiles_x;
+    cfg.tiles_y = tiles_y;
+    cfg.residual_variant = residual_variant;
+    check(gfs_clahe_create(device, max_width, max_height, 1, &cfg, &h_), "gfs_clahe_create");
+  }
+  ~Clahe() { gfs_clahe_destroy(h_); }
+  Clahe(const Clahe&) = delete;
+  Clahe& operator=(const Clahe&) = delete;
+  // clahe->apply(src, dst); dst may be src
+  void apply(const uint8_t* src, int width, int height, int stride, uint8_t* dst, int dst_stride) {
+    check(gfs_clahe_apply(h_, &src, width, height, stride, 1, &dst, dst_stride), "gfs_clahe_apply");
+  }
+  gfs_clahe* handle() const { return h_; }
+
+ private:
+  gfs_clahe* h_ = nullptr;
+};
+
 class KltTracker {
  public:
   class Pyramid {
@@ -873,6 +900,12 @@ class KltTracker {
     Pyramid& operator=(const Pyramid&) = delete;
     // cv::buildOpticalFlowPyramid(image, pyr, Size(win, win), max_level)
     void build(const uint8_t* image, int stride) { check(gfs_klt_build_pyramid(t_.h_, p_, &image, stride, 1), "gfs_klt_build_pyramid"); }
+    // clahe->apply(image, image); cv::buildOpticalFlowPyramid(image, pyr, ...) in one device pass (src/Frame.cc:366-373): `image`
+    // itself is left alone; equalized_out (rows of `stride` bytes, may be `image`) receives Frame::image when it is not null
+    void build(const uint8_t* image, int stride, Clahe& clahe, uint8_t* equalized_out = nullptr) {
+      check(gfs_klt_build_pyramid_clahe(t_.h_, clahe.handle(), p_, &image, stride, 1, equalized_out ? &equalized_out : nullptr, stride),
+            "gfs_klt_build_pyramid_clahe");
+    }
     gfs_klt_pyramid* get() const { return p_; }
 
    private:

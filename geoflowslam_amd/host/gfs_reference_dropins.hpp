@@ -159,4 +159,19 @@ struct LbaAccess {
   static void set_world_pos(MapPoint* p, const float x[3]) { p->SetWorldPos(Eigen::Vector3f(x[0], x[1], x[2])); }
 };
 
+// ---- 5. The Frame constructors' CLAHE + optical-flow pyramid (src/Frame.cc:366-373, 499-505): two lines -------------------------
+//      if (mpSettings->useClahe()) { cv::Ptr<cv::CLAHE> clahe = cv::createCLAHE(3.0, cv::Size(8, 8)); clahe->apply(image, image); }
+//      cv::buildOpticalFlowPyramid(image, mImGray, winSize, 3);
+//   ->
+//      gfs_dropin::build_flow_pyramid(klt, pyramid, mpSettings->useClahe() ? clahe : nullptr, image);
+// `image` is the clone of imGray (:345); with a CLAHE handle it holds the equalised frame afterwards, as Tracking::EstimatePoseByOF
+// (src/Tracking.cc:1961) expects; ORB has already run on imGray.  klt, pyramid and clahe live where the reference keeps mImGray.
+inline void build_flow_pyramid(gfs_klt* klt, gfs_klt_pyramid* pyramid, gfs_clahe* clahe, cv::Mat& image) {
+  const uint8_t* src = image.data;
+  uint8_t* eq = image.data;
+  const int rc = clahe ? gfs_klt_build_pyramid_clahe(klt, clahe, pyramid, &src, (int)(size_t)image.step, 1, &eq, (int)(size_t)image.step)
+                       : gfs_klt_build_pyramid(klt, pyramid, &src, (int)(size_t)image.step, 1);
+  if (rc != GFS_OK) throw std::runtime_error(gfs_last_error());
+}
+
 }  // namespace gfs_dropin

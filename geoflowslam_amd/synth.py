@@ -998,3 +998,16 @@ def map_point_update_problem(seed, n_points=1000, obs_counts=(1, 20), n_keyframe
         level_scale[p] = scale[int(rng.integers(0, n_levels))]
     return dict(obs_start=obs_start, obs_kf=obs_kf, obs_Ow=kf_Ow[obs_kf].reshape(-1, 3).copy(), obs_desc=obs_desc, obs_flags=obs_flags,
                 pos=pos, ref_Ow=ref_Ow, level_scale=level_scale, max_scale=np.full(n_points, scale[-1], np.float32))
+
+
+def clahe_image(seed, width, height):
+    """A frame for the CLAHE tests: a low-contrast sinusoid under Gaussian noise of sigma 12 plus a nearly flat patch of 4 grey
+    values.  The narrow histogram puts every tile of an 8 x 8 grid over the clip limit of 3.0 once tiles hold a few hundred pixels
+    and the patch makes single bins exceed it many times over, so the redistributed excess takes many sizes (a residual below and
+    above 128 both occur); a tile of one pixel clips nothing.  -> [height, width] u8."""
+    rng = np.random.default_rng(seed)
+    y, x = np.mgrid[0:height, 0:width].astype(np.float64)
+    img = 118.0 + 22.0 * np.sin(0.11 * x + 0.3 * seed) * np.cos(0.07 * y + 0.2 * seed) + rng.normal(0.0, 12.0, (height, width))
+    ph, pw, y0, x0 = max(height // 3, 1), max(width // 3, 1), height // 4, width // 2
+    img[y0:y0 + ph, x0:x0 + pw] = 96 + rng.integers(0, 4, img[y0:y0 + ph, x0:x0 + pw].shape)
+    return np.clip(np.rint(img), 0, 255).astype(np.uint8)

@@ -925,6 +925,52 @@ int gfs_pose_lidar_fetch_edges(gfs_pose_lidar* h, int b, int round, int32_t* ind
                                int32_t* n);
 
 /* ============================================================================================
+ * 12. cv::CLAHE on 8-bit single-channel images -- the equalisation of Frame::image in front of the optical-flow pyramid
+ *      cv::Ptr<cv::CLAHE> clahe = cv::createCLAHE(3.0, cv::Size(8, 8)); clahe->apply(image, image);
+ *                                                                              src/Frame.cc:366-369, 499-500 (UseClahe: 1)
+ *    ORB keeps running on the un-equalised imGray; Tracking::EstimatePoseByOF (src/Tracking.cc:1961) reads the equalised image.
+ *    The rule is DESIGN.md section 16 (a written restatement of OpenCV's imgproc/src/clahe.cpp): per-tile histogram of the image
+ *    extended by BORDER_REFLECT_101, clip, redistribution, look-up table, bilinear blend of four tables per pixel in a fixed float
+ *    order.  Bit-equal to tests/host/clahe_restatement.cpp.  residual_variant selects how the excess left after the even
+ *    redistribution is spread: OpenCV >= 3.4 steps through the bins, OpenCV <= 3.3 fills the first bins.
+ *    Refusals truncate nothing and leave the handle usable: a NULL pointer, a stride below the width, tiles outside 1 .. 16, an
+ *    unknown variant (GFS_ERR_INVALID_ARG); more frames or a larger image than reserved (GFS_ERR_CAPACITY).
+ * ============================================================================================ */
+#define GFS_CLAHE_RESIDUAL_STEPPED 0    /* OpenCV >= 3.4: h[k * step] += 1, step = max(256 / residual, 1), k < residual */
+#define GFS_CLAHE_RESIDUAL_CONTIGUOUS 1 /* OpenCV <= 3.3: h[i] += 1 for i < residual */
+typedef struct {
+  double clip_limit;        /* <= 0: no clipping (plain per-tile equalisation) */
+  int32_t tiles_x, tiles_y; /* 1 .. 16 */
+  int32_t residual_variant; /* GFS_CLAHE_RESIDUAL_* */
+} gfs_clahe_config;
+typedef struct gfs_clahe gfs_clahe;
+void gfs_clahe_default_config(gfs_clahe_config* cfg); /* 3.0, 8 x 8, stepped */
+/* Images up to max_width x max_height (<= 8192 per side), up to max_batch per call.  The handle has its own stream and lock. */
+int gfs_clahe_create(int device, int max_width, int max_height, int max_batch, const gfs_clahe_config* cfg, gfs_clahe** out);
+void gfs_clahe_destroy(gfs_clahe* h);
+/* clahe->apply for B host images of any width, height >= 1 within the reserve: images[f] = height rows of `stride` bytes,
+ * out[f] = height rows of `out_stride` bytes (may be images[f]). */
+int gfs_clahe_apply(gfs_clahe* h, const uint8_t* const* images, int width, int height, int stride, int B, uint8_t* const* out,
+                    int out_stride);
+/* Same in device memory: dev_in [B][height][in_stride], dev_out [B][height][out_stride]; dev_out == dev_in with equal strides
+ * equalises in place.  Asynchronous on `stream` when it is not NULL.  Calls on one handle share its table storage: calls issued on
+ * different streams must be ordered by the caller. */
+int gfs_clahe_apply_device(gfs_clahe* h, const void* dev_in, int width, int height, int in_stride, int B, void* dev_out, int out_stride,
+                           void* stream);
+/* The look-up tables of frame f of the last call, lut [tiles_y][tiles_x][256] (parity tests: tells which half is wrong).  Waits for
+ * the whole device. */
+int gfs_clahe_download_luts(gfs_clahe* h, int f, uint8_t* lut);
+/* The Frame constructor's pair in one call on the tracker's stream: one upload, CLAHE, then gfs_klt_build_pyramid's launches
+ * unchanged.  equalized_out (NULL, or B host pointers to height rows of eq_stride bytes) receives Frame::image.
+ * GFS_ERR_INVALID_ARG: handles on different devices, a CLAHE reserve smaller than the tracker's image. */
+int gfs_klt_build_pyramid_clahe(gfs_klt* h, gfs_clahe* clahe, gfs_klt_pyramid* pyr, const uint8_t* const* images, int stride, int B,
+                                uint8_t* const* equalized_out, int eq_stride);
+/* Same from device memory.  dev_equalized [B][height][eq_stride] receives the equalised images (it may be dev_images when the
+ * strides are equal); with NULL they live in scratch owned by the CLAHE handle until its next call. */
+int gfs_klt_build_pyramid_clahe_device(gfs_klt* h, gfs_clahe* clahe, gfs_klt_pyramid* pyr, const void* dev_images, int stride, int B,
+                                       void* dev_equalized, int eq_stride, void* stream);
+
+/* ============================================================================================
  * Timing helper for the harness: HIP events on a given stream (bench.py measures the dominant kernel
  * with these rather than torch events, which only see torch's current stream).
  * ============================================================================================ */
