@@ -63,6 +63,11 @@ class LbaSolution(C.Structure):
                 ("final_lambda", C.c_double)]
 
 
+class LbaTrial(C.Structure):  # gfs_test_lba_trial (include/gfs_abi_test.h)
+    _fields_ = [("Dinv", C.c_void_p), ("Hs", C.c_void_p), ("bs", C.c_void_p), ("xp", C.c_void_p), ("xl", C.c_void_p),
+                ("lambda_", C.c_double), ("scale", C.c_double), ("solve_ok", C.c_int32)]
+
+
 class LbaLidar(C.Structure):
     _fields_ = [("map", C.c_void_p), ("pose_local", C.c_void_p), ("matches_inliers", C.c_void_p), ("cloud_begin", C.c_void_p),
                 ("cloud", C.c_void_p), ("two_camera", C.c_int32)]
@@ -559,7 +564,7 @@ ABI_SYMBOLS = [
     "gfs_gicp_fetch_preprocessed", "gfs_gicp_tile_stats", "gfs_gicp_knn_stats", "gfs_gicp_coop_stats", "gfs_frame_rgbd", "gfs_gicp_align_next", "gfs_gicp_align_next_batch_device", "gfs_test_voxel_sort", "gfs_test_voxel_sort_paths", "gfs_test_wave_std_sort",
     "gfs_lba_create", "gfs_lba_destroy", "gfs_lba_solve", "gfs_lba_solve_bool", "gfs_lba_linearize", "gfs_lba_batch_create", "gfs_lba_batch_destroy",
     "gfs_lba_solve_batch", "gfs_lba_lidar_reserve", "gfs_lba_solve_lidar", "gfs_lba_solve_lidar_bool", "gfs_lba_linearize_lidar",
-    "gfs_lba_fetch_lidar_edges", "gfs_test_lba_stop_at_look", "gfs_test_lba_last_looks",
+    "gfs_lba_fetch_lidar_edges", "gfs_test_lba_stop_at_look", "gfs_test_lba_last_looks", "gfs_test_lba_first_trial",
     "gfs_frame_create", "gfs_frame_destroy", "gfs_depth_to_cloud", "gfs_depth_to_cloud_batch_device", "gfs_depth_convert_u16_batch_device", "gfs_stereo_from_rgbd",
     "gfs_stereo_from_rgbd_batch_device",
     "gfs_pose_create", "gfs_pose_destroy", "gfs_pose_optimize", "gfs_pose_set_sum_order",
@@ -652,6 +657,7 @@ def lib():
             L.gfs_lba_solve_batch.argtypes = [vp, vp, vp, i, vp]
             L.gfs_test_lba_stop_at_look.argtypes = [i]
             L.gfs_test_lba_last_looks.argtypes = [C.POINTER(C.c_int32)] * 4
+            L.gfs_test_lba_first_trial.argtypes = [vp, C.POINTER(LbaProblem), C.POINTER(LbaTrial)]
         if hasattr(L, "gfs_lba_solve_lidar"):
             L.gfs_lba_lidar_reserve.argtypes = [vp, i]
             L.gfs_lba_solve_lidar.argtypes = [vp, C.POINTER(LbaProblem), C.POINTER(LbaLidar), C.POINTER(LbaSolution), vp, vp]
@@ -1098,6 +1104,24 @@ def lba_last_looks():
     v = [C.c_int32() for _ in range(4)]
     _check(lib().gfs_test_lba_last_looks(*[C.byref(x) for x in v]), "gfs_test_lba_last_looks")
     return dict(looks=v[0].value, discarded=v[1].value, forced_decides=v[2].value, ahead_at_stop=v[3].value)
+
+
+def lba_first_trial(opt, prob, fill=np.nan):
+    """Test hook (include/gfs_abi_test.h: gfs_test_lba_first_trial): the linear step of the first LM trial of `prob` on the Optimizer
+    `opt`, through the product's dispatch -> dict(lam, Dinv [n_points, 6], Hs (packed lower triangle), bs, xp [6F], xl [n_points, 3],
+    solve_ok, scale).  The arrays are pre-written with `fill`: an entry the library did not deliver still holds it."""
+    P, keep = _lba_problem(prob)
+    nf = int((np.asarray(prob["pose_fixed"]) == 0).sum())
+    n, NP = 6 * nf, P.n_points
+    # (one spare element each: a window without free poses or landmarks still hands in non-NULL arrays)
+    buf = dict(Dinv=np.full(6 * NP + 1, fill), Hs=np.full(n * (n + 1) // 2 + 1, fill), bs=np.full(n + 1, fill),
+               xp=np.full(n + 1, fill), xl=np.full(3 * NP + 1, fill))
+    T = LbaTrial()
+    for k, v in buf.items():
+        setattr(T, k, v.ctypes.data)
+    _check(lib().gfs_test_lba_first_trial(opt.h, C.byref(P), C.byref(T)), "gfs_test_lba_first_trial")
+    return dict(lam=T.lambda_, scale=T.scale, solve_ok=int(T.solve_ok), Dinv=buf["Dinv"][:-1].reshape(NP, 6).copy(),
+                Hs=buf["Hs"][:-1].copy(), bs=buf["bs"][:-1].copy(), xp=buf["xp"][:-1].copy(), xl=buf["xl"][:-1].reshape(NP, 3).copy())
 
 
 class Optimizer:

@@ -1910,7 +1910,16 @@ struct LidarRun {
   std::vector<int> kf_of_pose;  // [n_poses] lidar key-frame or -1
 };
 
-int run(gfs_lba* h, const gfs_lba_problem* p, const HostPrep& P, int mode, StopFlag stop, const LidarRun* lid = nullptr) {
+// Test hook (include/gfs_abi_test.h: gfs_test_lba_first_trial): a tap in the trial sequence.  With a tap, run() queues init, the build
+// group of iteration 0 and ONE trial up to and including k_lba_update -- the launches, grids and LDS sizes of the product -- copies the
+// reduced system to the tap's host arrays between the Schur launches and k_lba_solve (the HBM factorisation works in place), and
+// returns with the stream drained.  Without one (every product call) nothing is queued that was not queued before.
+struct TrialTap {
+  double *Hs, *bs;  // host: packed lower triangle (6F (6F + 1) / 2) and right-hand side (6F) as the Schur stage left them
+};
+
+int run(gfs_lba* h, const gfs_lba_problem* p, const HostPrep& P, int mode, StopFlag stop, const LidarRun* lid = nullptr,
+        const TrialTap* tap = nullptr) {
   hipStream_t s = h->stream;
   LbaDev D;
   int rc = upload_and_fill(h, p, P, mode, s, D);
@@ -1943,7 +1952,7 @@ int run(gfs_lba* h, const gfs_lba_problem* p, const HostPrep& P, int mode, StopF
   GFS_HIP(hipHostGetDevicePointer((void**)&d_flags, h->h_flags, 0));
   const dim3 g_err(D.n_err_blocks), g_lm(std::max(D.n_lm_wg, 1)), g_upd(D.n_upd_blocks);
   GFS_LAUNCH("k_lba_init", k_lba_init, dim3(64), dim3(kMk), 0, s, D);
-  const bool lin_only = mode == 1 || p->iterations <= 0;
+  const bool lin_only = !tap && (mode == 1 || p->iterations <= 0);
   if (lin_only) {
     GFS_LAUNCH("k_lba_errors", k_lba_errors, g_err, dim3(kMk), 0, s, D, 0, 0);
     if (mode == 1) {
@@ -1992,11 +2001,16 @@ int run(gfs_lba* h, const gfs_lba_problem* p, const HostPrep& P, int mode, StopF
     } else if (npairs > 0) {
       GFS_LAUNCH("k_lba_schur", k_lba_schur, dim3(npairs), dim3(kMk), 0, s, D, gate);
     }
+    if (tap && n > 0) {  // stream-ordered: behind the Schur launches, ahead of the factorisation
+      GFS_HIP(hipMemcpyAsync(tap->Hs, h->d_Hs.p, (size_t)n * (n + 1) / 2 * sizeof(double), hipMemcpyDeviceToHost, s));
+      GFS_HIP(hipMemcpyAsync(tap->bs, h->d_bs.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s));
+    }
     if (in_lds)
       GFS_LAUNCH("k_lba_solve", k_lba_solve<true>, dim3(1), dim3(kThreads), lds, s, D, gate);
     else
       GFS_LAUNCH("k_lba_solve", k_lba_solve<false>, dim3(1), dim3(kThreads), lds, s, D, gate);
     GFS_LAUNCH("k_lba_update", k_lba_update, g_upd, dim3(kMk), 0, s, D, gate);
+    if (tap) return GFS_OK;  // the observed trial ends with the step: no errors at the trial estimate, no decision
     GFS_LAUNCH("k_lba_errors", k_lba_errors, g_err, dim3(kMk), 0, s, D, 1, gate);
     GFS_LAUNCH("k_lba_decide", k_lba_decide, dim3(1), dim3(64), 0, s, D, 0, d_flags + kFlagInts * (n_decides & 1), gate);
     GFS_HIP(hipEventRecord(h->ev_decide[n_decides & 1], s));
@@ -2004,6 +2018,11 @@ int run(gfs_lba* h, const gfs_lba_problem* p, const HostPrep& P, int mode, StopF
     return GFS_OK;
   };
   auto flags_of = [&](int i) { return h->h_flags + kFlagInts * (i & 1); };
+  if (tap) {
+    if ((rc = build_group(0, 0)) || (rc = trial_group(0))) return rc;
+    GFS_HIP(hipStreamSynchronize(s));
+    return GFS_OK;
+  }
   if (!(stop && *stop)) {
     int iteration = 0;
     if ((rc = build_group(0, 0)) || (rc = trial_group(0))) return rc;
@@ -2679,6 +2698,34 @@ int gfs_test_lba_last_looks(int32_t* looks, int32_t* discarded, int32_t* forced_
   if (discarded) *discarded = T.discarded;
   if (forced_decides) *forced_decides = T.forced;
   if (ahead_at_stop) *ahead_at_stop = T.ahead;
+  return GFS_OK;
+}
+
+int gfs_test_lba_first_trial(gfs_lba* h, const gfs_lba_problem* p, gfs_test_lba_trial* out) {
+  GFS_REQUIRE(h && p && out, GFS_ERR_INVALID_ARG, "gfs_test_lba_first_trial: NULL argument");
+  GFS_REQUIRE(out->Dinv && out->Hs && out->bs && out->xp && out->xl, GFS_ERR_INVALID_ARG, "gfs_test_lba_first_trial: NULL output array");
+  std::lock_guard<std::mutex> lk(h->mu);
+  GFS_HIP(hipSetDevice(h->device));
+  static thread_local HostPrep tl_prep;
+  HostPrep& P = tl_prep;
+  int rc = prepare(h, p, P);
+  if (rc) return rc;
+  const TrialTap tap{out->Hs, out->bs};
+  if ((rc = run(h, p, P, 0, StopFlag{}, nullptr, &tap))) return rc;  // returns with the stream drained
+  const size_t NP = p->n_points, n = 6 * (size_t)P.n_free;
+  const LbaDev& D = h->last_desc;
+  LbaState S;
+  GFS_HIP(hipMemcpy(&S, h->d_state.p, sizeof(S), hipMemcpyDeviceToHost));
+  if (NP) GFS_HIP(hipMemcpy(out->Dinv, h->d_Dinv.p, NP * 6 * sizeof(double), hipMemcpyDeviceToHost));
+  if (NP) GFS_HIP(hipMemcpy(out->xl, h->d_xl.p, NP * 3 * sizeof(double), hipMemcpyDeviceToHost));
+  if (n) GFS_HIP(hipMemcpy(out->xp, h->d_xp.p, n * sizeof(double), hipMemcpyDeviceToHost));
+  std::vector<double> part(D.n_upd_blocks);
+  GFS_HIP(hipMemcpy(part.data(), h->d_part_scale.p, part.size() * sizeof(double), hipMemcpyDeviceToHost));
+  double scale = 0;
+  for (double v : part) scale += v;  // k_lba_decide's order
+  out->lambda = S.lambda;
+  out->scale = scale;
+  out->solve_ok = S.solve_ok;
   return GFS_OK;
 }
 

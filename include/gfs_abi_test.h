@@ -66,6 +66,24 @@ int gfs_test_lba_stop_at_look(int look);
  * was seen up with / without an iteration queued ahead of the host's knowledge, -1 when it was not seen up after the entry check. */
 int gfs_test_lba_last_looks(int32_t* looks, int32_t* discarded, int32_t* forced_decides, int32_t* ahead_at_stop);
 
+/* GPU test hook: the linear step of the FIRST Levenberg-Marquardt trial of a window, stage by stage.  The problem is staged as
+ * gfs_lba_solve stages it; init, the build group of iteration 0 and the first trial run up to and including k_lba_update, through
+ * the dispatch of the product (the Schur kernel, one 128 x 128 block or several, the LDS or the HBM factorisation, the LDS sizes):
+ * the hook is a tap in that sequence, not a second copy of it.  Hs / bs are copied out, stream-ordered, between the Schur launches
+ * and k_lba_solve (the HBM factorisation works in place).  The blocks Hpp / Hll / Hpl / bp / bl of the same state are what
+ * gfs_lba_linearize reports for the same handle and problem.  Every pointer is required (sizes for F free poses, n_points landmarks). */
+typedef struct gfs_test_lba_trial {
+  double* Dinv;     /* [n_points][6]  (Hll + lambda I)^-1: xx, xy, xz, yy, yz, zz */
+  double* Hs;       /* [6F (6F + 1) / 2]  the reduced system as the Schur stage left it: packed lower triangle, row by row */
+  double* bs;       /* [6F] */
+  double* xp;       /* [6F]  the pose step */
+  double* xl;       /* [n_points][3]  the landmark step */
+  double lambda;    /* as k_lba_begin set it (computeLambdaInit) */
+  double scale;     /* computeScale: the partial sums of k_lba_update added in block order */
+  int32_t solve_ok; /* the reduced solve met no zero or non-finite pivot */
+} gfs_test_lba_trial;
+int gfs_test_lba_first_trial(gfs_lba* h, const gfs_lba_problem* p, gfs_test_lba_trial* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from geoflowslam_amd import synth
+from lba_step_support import with_second_camera_edges as _with_second_camera_edges
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -162,25 +163,6 @@ def test_stop_flag_raised_while_a_batch_is_solving(gpu_api, oracle):
     again = bat.LocalBundleAdjustment(wins)
     for a, f in zip(again, full):
         assert np.array_equal(a["points"], f["points"]) and a["iterations_run"] == f["iterations_run"]
-
-
-def _with_second_camera_edges(w, seed, frac=0.15):
-    """the window with a second edge between some (key-frame, point) pairs, the way a two-camera rig adds a right-camera
-    observation of a point the left camera sees too (src/Optimizer.cc:1859-1925): a monocular observation ~0.7 px away"""
-    rng = np.random.default_rng(seed)
-    E = w["n_edges"]
-    pick = np.sort(rng.choice(E, int(frac * E), replace=False))
-    w2 = dict(w)
-    obs2 = w["edge_obs"][pick].copy()
-    obs2[:, :2] += rng.normal(0, 0.7, (len(pick), 2))
-    obs2[:, 2] = 0
-    # point-major order like the reference builds it: the second edge right after the first
-    order = np.argsort(np.r_[np.arange(E), pick + 0.5], kind="stable")
-    for k, extra in (("edge_pose", w["edge_pose"][pick]), ("edge_point", w["edge_point"][pick]), ("edge_obs", obs2),
-                     ("edge_inv_sigma2", w["edge_inv_sigma2"][pick]), ("edge_stereo", np.zeros(len(pick), w["edge_stereo"].dtype))):
-        w2[k] = np.ascontiguousarray(np.concatenate([w[k], extra])[order])
-    w2["n_edges"] = E + len(pick)
-    return w2
 
 
 @pytest.mark.parametrize("cfg", [dict(seed=11, n_free=20, n_fixed=5, n_points=3000), dict(seed=12, n_free=6, n_fixed=2, n_points=300),
