@@ -509,6 +509,27 @@ class LidarMapInfo(C.Structure):
     _fields_ = [("n_in", C.c_int32), ("n_out", C.c_int32), ("passthrough", C.c_int32), ("div", C.c_int32 * 3)]
 
 
+class FrameCloudConfig(C.Structure):
+    _fields_ = [("horizontal_angle", C.c_double), ("max_distance", C.c_double), ("local_map_resolution", C.c_double),
+                ("downsize_resolution", C.c_float), ("angle_guard_deg", C.c_double)]
+
+
+class FrameCloudInfo(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("n_in", "n_scans", "n_edge_raw", "n_surf_raw", "n_edge_voxel", "n_surf_voxel", "n_edge", "n_surf",
+                                         "n_down", "host_scan_split")] + [("passthrough", C.c_int32 * 3)]
+
+
+class FrameCloudStageBuffers(C.Structure):  # gfs_test_frame_cloud_stage_buffers (include/gfs_abi_test.h)
+    _fields_ = [("scans", C.c_void_p), ("cap_scans", C.c_int32)] + \
+               [(k, C.c_void_p) for k in ("edge_raw", "surf_raw", "edge_voxel", "surf_voxel", "edge", "surf")] + [("cap_points", C.c_int32)]
+
+
+def frame_cloud_info(I):
+    d = {k: int(getattr(I, k)) for k, _ in FrameCloudInfo._fields_[:10]}
+    d["passthrough"] = tuple(int(v) for v in I.passthrough)
+    return d
+
+
 def lidar_map_info(I):
     return dict(n_in=int(I.n_in), n_out=int(I.n_out), passthrough=int(I.passthrough), div=tuple(int(v) for v in I.div))
 
@@ -570,6 +591,8 @@ ABI_SYMBOLS = [
     "gfs_pose_create", "gfs_pose_destroy", "gfs_pose_optimize", "gfs_pose_set_sum_order",
     "gfs_lidar_mapper_create", "gfs_lidar_mapper_destroy", "gfs_lidar_map_build", "gfs_lidar_map_fetch", "gfs_voxel_grid_filter",
     "gfs_test_lidar_map_grid",
+    "gfs_frame_cloud_default_config", "gfs_frame_cloud_create", "gfs_frame_cloud_destroy", "gfs_frame_cloud_extract",
+    "gfs_frame_cloud_extract_device", "gfs_test_frame_cloud_stages", "gfs_test_frame_cloud_radius",
     "gfs_lidar_map_create", "gfs_lidar_map_set", "gfs_lidar_map_destroy", "gfs_pose_lidar_create", "gfs_pose_lidar_destroy",
     "gfs_pose_lidar_set_sum_order", "gfs_pose_lidar_optimize", "gfs_pose_lidar_fetch_edges",
     "gfs_gms_create", "gfs_gms_destroy", "gfs_gms_inlier_mask", "gfs_gms_inlier_mask_batch_device",
@@ -672,6 +695,14 @@ def lib():
             L.gfs_lidar_map_fetch.argtypes = [vp, vp, i, C.POINTER(C.c_int32)]
             L.gfs_voxel_grid_filter.argtypes = [vp, vp, i, C.c_float, vp, i, C.POINTER(LidarMapInfo)]
             L.gfs_test_lidar_map_grid.argtypes = [vp, vp, i, vp, vp, i, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        L.gfs_frame_cloud_default_config.argtypes = [C.POINTER(FrameCloudConfig)]
+        L.gfs_frame_cloud_default_config.restype = None
+        L.gfs_frame_cloud_create.argtypes = [i, i, C.POINTER(FrameCloudConfig), C.POINTER(vp)]
+        L.gfs_frame_cloud_destroy.argtypes = [vp]
+        L.gfs_frame_cloud_extract.argtypes = [vp, vp, i, vp, i, vp, i, C.POINTER(FrameCloudInfo)]
+        L.gfs_frame_cloud_extract_device.argtypes = [vp, vp, vp, vp, i, vp, i, C.POINTER(FrameCloudInfo)]
+        L.gfs_test_frame_cloud_stages.argtypes = [vp, C.POINTER(FrameCloudStageBuffers)]
+        L.gfs_test_frame_cloud_radius.argtypes = [vp, vp, i, i, vp, i, C.POINTER(C.c_int32)]
         if hasattr(L, "gfs_frame_create"):
             f = C.c_float
             L.gfs_frame_create.argtypes = [i, i, i, i, C.POINTER(vp)]
@@ -1816,6 +1847,81 @@ class LidarMapper:
     def close(self):
         if getattr(self, "h", None) and _lib is not None:
             _lib.gfs_lidar_mapper_destroy(self.h)
+        self.h = None
+
+    __del__ = close
+
+
+class FrameCloud:
+    """The lidar-feature tail of the Frame constructor (reference src/Frame.cc:378-393, src/LidarProcess.cc:20-204) on the device:
+    featureExtraction of the camera-frame cloud, surf ++ edge (mpPointCloud) and its pcl::VoxelGrid at downsizeResolution()
+    (mpPointCloudDownsampled).  The rule is DESIGN.md section 17 (gfs_frame_cloud_* in include/gfs_abi.h)."""
+
+    def __init__(self, max_points=32768, downsize_resolution=0.05, horizontal_angle=None, max_distance=None, local_map_resolution=None,
+                 angle_guard_deg=None, device=0):
+        """The LidarParam fields default to the reference's (70.0, 9.0, 0.05); angle_guard_deg to 1e-9."""
+        cfg = FrameCloudConfig()
+        lib().gfs_frame_cloud_default_config(C.byref(cfg))
+        cfg.downsize_resolution = float(np.float32(downsize_resolution))
+        for k, v in (("horizontal_angle", horizontal_angle), ("max_distance", max_distance), ("local_map_resolution", local_map_resolution),
+                     ("angle_guard_deg", angle_guard_deg)):
+            if v is not None:
+                setattr(cfg, k, float(v))
+        self.cfg, self.max_points, self.h = cfg, max_points, C.c_void_p()
+        _check(lib().gfs_frame_cloud_create(device, max_points, C.byref(cfg), C.byref(self.h)), "gfs_frame_cloud_create")
+
+    def _call(self, fn, what, args, cap, cap_down, want_cloud):
+        cloud = np.zeros((max(cap, 1), 3), np.float32) if want_cloud else None
+        down, info = np.zeros((max(cap_down, 1), 3), np.float32), FrameCloudInfo()
+        self.last_info = info
+        _check(fn(self.h, *args, _p(cloud), cap, _p(down), cap_down, C.byref(info)), what)
+        I = frame_cloud_info(info)
+        return (cloud[:I["n_surf"] + I["n_edge"]].copy() if want_cloud else None), down[:I["n_down"]].copy(), I
+
+    def extract(self, xyzw, cap=None, cap_down=None, want_cloud=True):
+        """xyzw [n][4] (or [n][3]): the cloud of ConvertDepthToPointCloud in push_back order -> (cloud [n_surf + n_edge][3] surf
+        first, or None; downsampled cloud [n_down][3]; info dict).  A refused call raises GfsError (err.code)."""
+        xyzw = np.asarray(xyzw, np.float32)
+        xyzw = xyzw.reshape(-1, xyzw.shape[-1] if xyzw.ndim == 2 else 4)
+        if xyzw.shape[1] == 3:
+            xyzw = np.concatenate([xyzw, np.ones((len(xyzw), 1), np.float32)], 1)
+        xyzw = np.ascontiguousarray(xyzw, np.float32)
+        n = len(xyzw)
+        return self._call(lib().gfs_frame_cloud_extract, "gfs_frame_cloud_extract", (_p(xyzw) if n else xyzw.ctypes.data_as(C.c_void_p), n),
+                          n if cap is None else cap, n if cap_down is None else cap_down, want_cloud)
+
+    def extract_device(self, dev_xyzw, dev_count, cap=None, cap_down=None, want_cloud=True):
+        """Same on the cloud Frame.FrameRGBD left on the device (its dev_cloud / dev_count addresses)."""
+        return self._call(lib().gfs_frame_cloud_extract_device, "gfs_frame_cloud_extract_device", (C.c_void_p(dev_xyzw), C.c_void_p(dev_count)),
+                          self.max_points if cap is None else cap, self.max_points if cap_down is None else cap_down, want_cloud)
+
+    def stages(self):
+        """The stages of the last call through the test hook -> dict(scans [n_scans][4], edge_raw, surf_raw, edge_voxel, surf_voxel,
+        edge, surf: [n][3] each)."""
+        I = frame_cloud_info(self.last_info)
+        names = ("edge_raw", "surf_raw", "edge_voxel", "surf_voxel", "edge", "surf")
+        out = {k: np.zeros((max(I["n_" + k], 1), 3), np.float32) for k in names}
+        out["scans"] = np.zeros((max(I["n_scans"], 1), 4), np.int32)
+        B = FrameCloudStageBuffers()
+        B.scans, B.cap_scans, B.cap_points = out["scans"].ctypes.data, len(out["scans"]), max(max(I["n_" + k] for k in names), 1)
+        for k in names:
+            setattr(B, k, out[k].ctypes.data)
+        _check(lib().gfs_test_frame_cloud_stages(self.h, C.byref(B)), "gfs_test_frame_cloud_stages")
+        out["scans"] = out["scans"][:I["n_scans"]]
+        for k in names:
+            out[k] = out[k][:I["n_" + k]]
+        return out
+
+    def radius_filter(self, xyz, min_pts):
+        """The handle's RadiusOutlierRemoval on its own (test hook; radius = local_map_resolution) -> kept points [m][3]."""
+        xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        out, n = np.zeros((max(len(xyz), 1), 3), np.float32), C.c_int32()
+        _check(lib().gfs_test_frame_cloud_radius(self.h, _p(xyz), len(xyz), min_pts, _p(out), len(xyz), C.byref(n)), "gfs_test_frame_cloud_radius")
+        return out[:n.value].copy()
+
+    def close(self):
+        if getattr(self, "h", None) and _lib is not None:
+            _lib.gfs_frame_cloud_destroy(self.h)
         self.h = None
 
     __del__ = close

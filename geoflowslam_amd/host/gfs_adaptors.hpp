@@ -225,6 +225,62 @@ class LidarLocalMapper {
   LidarMapFlat flat_;
 };
 
+// ------------------------------------------------------------------------------------------------------------------------
+// Frame::Frame, the lidar-feature tail                                                      reference src/Frame.cc:378-393
+//     mpLidarProcess->featureExtraction(pointcloud_in, pointcloud_edge, pointcloud_surf);
+//     *mpPointCloud = *pointcloud_surf + *pointcloud_edge;
+//     downSizeFilter.setLeafSize(res, res, res); ... downSizeFilter.filter(*mpPointCloudDownsampled);
+// on plain arrays around gfs_frame_cloud_extract.  `LidarParam` is the reference's own class, read through
+// getHorizontalAngle(), getMaxDistance() and getLocalMapResolution() (src/Lidar.cc:100-128); downsize_resolution is
+// mpSettings->downsizeResolution().  Both clouds come back as [n][3] floats (colour is not carried).  The warning the constructor
+// prints when the downsampled cloud is empty stays with the caller.  A refusal throws.
+// ------------------------------------------------------------------------------------------------------------------------
+template <class LidarParam>
+inline gfs_frame_cloud_config FrameCloudConfigFrom(const LidarParam& lp, float downsize_resolution) {
+  gfs_frame_cloud_config cfg;
+  gfs_frame_cloud_default_config(&cfg);
+  cfg.horizontal_angle = lp.getHorizontalAngle();
+  cfg.max_distance = lp.getMaxDistance();
+  cfg.local_map_resolution = lp.getLocalMapResolution();
+  cfg.downsize_resolution = downsize_resolution;
+  return cfg;
+}
+
+class FrameCloudExtractor {
+ public:
+  template <class LidarParam>
+  FrameCloudExtractor(const LidarParam& lp, float downsize_resolution, int max_points = 131072, int device = 0) {
+    const gfs_frame_cloud_config cfg = FrameCloudConfigFrom(lp, downsize_resolution);
+    check(gfs_frame_cloud_create(device, max_points, &cfg, &h_), "gfs_frame_cloud_create");
+  }
+  ~FrameCloudExtractor() { gfs_frame_cloud_destroy(h_); }
+  FrameCloudExtractor(const FrameCloudExtractor&) = delete;
+  FrameCloudExtractor& operator=(const FrameCloudExtractor&) = delete;
+  // xyzw [n][4]: ConvertDepthToPointCloud's cloud in push_back order -> mpPointCloud (surf then edge) and mpPointCloudDownsampled
+  gfs_frame_cloud_info Extract(const float* xyzw, int n, std::vector<float>& cloud, std::vector<float>& down) {
+    cloud.resize(3 * (size_t)n);
+    down.resize(3 * (size_t)n);
+    gfs_frame_cloud_info info{};
+    check(gfs_frame_cloud_extract(h_, xyzw, n, cloud.data(), n, down.data(), n, &info), "gfs_frame_cloud_extract");
+    cloud.resize(3 * (size_t)(info.n_surf + info.n_edge));
+    down.resize(3 * (size_t)info.n_down);
+    return info;
+  }
+  // the same on the cloud gfs_frame_rgbd left on the device (n: its *n_cloud)
+  gfs_frame_cloud_info ExtractDevice(const void* dev_xyzw, const void* dev_count, int n, std::vector<float>& cloud, std::vector<float>& down) {
+    cloud.resize(3 * (size_t)n);
+    down.resize(3 * (size_t)n);
+    gfs_frame_cloud_info info{};
+    check(gfs_frame_cloud_extract_device(h_, dev_xyzw, dev_count, cloud.data(), n, down.data(), n, &info), "gfs_frame_cloud_extract_device");
+    cloud.resize(3 * (size_t)(info.n_surf + info.n_edge));
+    down.resize(3 * (size_t)info.n_down);
+    return info;
+  }
+
+ private:
+  gfs_frame_cloud* h_ = nullptr;
+};
+
 // numeric core of Optimizer::LocalBundleAdjustment (reference include/Optimizer.h:62-65)
 class LocalBundleAdjuster {
  public:

@@ -971,6 +971,45 @@ int gfs_klt_build_pyramid_clahe_device(gfs_klt* h, gfs_clahe* clahe, gfs_klt_pyr
                                        void* dev_equalized, int eq_stride, void* stream);
 
 /* ============================================================================================
+ * 14. The frame cloud -- the lidar-feature tail of the Frame constructor (UseICP / UsePointCloudObs)
+ *      mpLidarProcess->featureExtraction(pointcloud_in, pointcloud_edge, pointcloud_surf);     src/LidarProcess.cc:20-204
+ *      *mpPointCloud = *pointcloud_surf + *pointcloud_edge;  VoxelGrid at downsizeResolution()  src/Frame.cc:378-393
+ *    on the camera-frame cloud of gfs_depth_to_cloud / gfs_frame_rgbd: scan split by atan2(y, z), padded scans, curvature, the
+ *    std::sort pick of at most 10 edge points a scan, pcl::VoxelGrid (the rule of section 11) and RadiusOutlierRemoval on both
+ *    feature clouds, surf ++ edge, the final VoxelGrid.  DESIGN.md section 17 states the rule, including what the reference
+ *    leaves to libm, libstdc++ and PCL; the results are bit-equal to tests/host/frame_cloud_restatement.cpp for every input.
+ *    The three comparisons that read atan2 are taken on the device only when they lie farther than angle_guard_deg from their
+ *    threshold; otherwise the call redoes the scan table with the host's atan2 (info.host_scan_split = 1) -- same results.
+ *    Refusals truncate nothing, leave the outputs untouched and the handle usable:
+ *      GFS_ERR_INVALID_ARG  n == 0; a coordinate that is not finite or beyond 1e6 m, or a point whose float squared norm is 0
+ *                           (the curvature divides by it); non-positive or non-finite resolutions (at creation)
+ *      GFS_ERR_CAPACITY     n > max_points; a scan with more than 1024 candidates; cap / cap_down too small (info is filled)
+ *      GFS_ERR_UNSUPPORTED  a voxel index range beyond int, as in section 11
+ *    A cloud that yields no scan (a single row) is not an error: every output is empty.
+ * ============================================================================================ */
+typedef struct gfs_frame_cloud gfs_frame_cloud;
+typedef struct {
+  double horizontal_angle, max_distance, local_map_resolution; /* LidarParam: 70.0, 9.0, 0.05 */
+  float downsize_resolution;                                   /* Frame: mpSettings->downsizeResolution() */
+  double angle_guard_deg;                                      /* 1e-9 */
+} gfs_frame_cloud_config;
+typedef struct {
+  int32_t n_in, n_scans, n_edge_raw, n_surf_raw, n_edge_voxel, n_surf_voxel, n_edge, n_surf, n_down;
+  int32_t host_scan_split, passthrough[3]; /* edge, surf, final voxel filter returned its input */
+} gfs_frame_cloud_info;
+void gfs_frame_cloud_default_config(gfs_frame_cloud_config* cfg);
+/* Clouds of up to max_points points.  The handle has its own stream and lock; all workspace is allocated here. */
+int gfs_frame_cloud_create(int device, int max_points, const gfs_frame_cloud_config* cfg, gfs_frame_cloud** out);
+void gfs_frame_cloud_destroy(gfs_frame_cloud* h);
+/* xyzw [n][4]: the cloud in push_back order (w is not read).  cloud_xyz [cap][3] (may be NULL: not copied back) receives
+ * mpPointCloud, the n_surf surf points then the n_edge edge points; down_xyz [cap_down][3] mpPointCloudDownsampled (n_down). */
+int gfs_frame_cloud_extract(gfs_frame_cloud* h, const float* xyzw, int n, float* cloud_xyz, int cap, float* down_xyz, int cap_down,
+                            gfs_frame_cloud_info* info);
+/* Same on the cloud gfs_frame_rgbd left on the device (its *dev_cloud / *dev_count): nothing is uploaded. */
+int gfs_frame_cloud_extract_device(gfs_frame_cloud* h, const void* dev_xyzw, const void* dev_count, float* cloud_xyz, int cap,
+                                   float* down_xyz, int cap_down, gfs_frame_cloud_info* info);
+
+/* ============================================================================================
  * Timing helper for the harness: HIP events on a given stream (bench.py measures the dominant kernel
  * with these rather than torch events, which only see torch's current stream).
  * ============================================================================================ */

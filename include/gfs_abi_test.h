@@ -84,6 +84,22 @@ typedef struct gfs_test_lba_trial {
 } gfs_test_lba_trial;
 int gfs_test_lba_first_trial(gfs_lba* h, const gfs_lba_problem* p, gfs_test_lba_trial* out);
 
+/* GPU test hook: the stages of the handle's last gfs_frame_cloud_extract(_device) call, as they lie on the device: the scan table
+ * (rows of begin, count, pad flags 1 = start | 2 = end, candidates in the scans in front), edge_raw / surf_raw, the two voxel
+ * filters' outputs and the two radius filters' outputs.  Their sizes are the call's info; a NULL pointer skips a stage.  Refused
+ * after a refused call. */
+typedef struct gfs_test_frame_cloud_stage_buffers {
+  int32_t* scans; /* [cap_scans][4] */
+  int32_t cap_scans;
+  float *edge_raw, *surf_raw, *edge_voxel, *surf_voxel, *edge, *surf; /* [cap_points][3] each */
+  int32_t cap_points;
+} gfs_test_frame_cloud_stage_buffers;
+int gfs_test_frame_cloud_stages(gfs_frame_cloud* h, gfs_test_frame_cloud_stage_buffers* out);
+/* GPU test hook: the handle's radius filter on its own (radius = the handle's local_map_resolution): the points of xyz [n][3] with
+ * at least min_pts others within the radius, in input order -> out_xyz [cap >= n][3], *n_out.  Duplicates reach the filter only
+ * here (inside the chain a voxel filter runs in front of it). */
+int gfs_test_frame_cloud_radius(gfs_frame_cloud* h, const float* xyz, int n, int min_pts, float* out_xyz, int cap, int32_t* n_out);
+
 #ifdef __cplusplus
 }
 #endif
