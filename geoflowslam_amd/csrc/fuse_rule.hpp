@@ -1,7 +1,7 @@
 // The per-(map point, key frame) rule of ORBmatcher::Fuse(KeyFrame*, const vector<MapPoint*>&, th, bRight = false)
 // (reference src/ORBmatcher.cc:1424-1526) for single-camera pinhole key frames, stated once for the device and the host
 // (DESIGN.md section 13): float, every operation rounded once, sums left to right; the translation units that include this are
-// built with -ffp-contract=off.  k_fuse (sbp.hip) runs it with the key frame's grid in LDS; search_point below runs it on the
+// built with -ffp-contract=off.  k_fuse (fuse.hip) runs it with the key frame's grid in LDS; search_point below runs it on the
 // host for ONE pair, for the adaptor's replay when a point's descriptor changed after the upload (gfs_adaptors.hpp).
 #pragma once
 #include <cstdint>

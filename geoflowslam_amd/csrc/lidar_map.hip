@@ -26,6 +26,7 @@
 #include <mutex>
 #include <vector>
 
+#include "block_layouts.hpp"
 #include "gfs_common.hpp"
 #include "lidar_assoc.hpp"
 #include "voxel_filter_dev.hpp"
@@ -250,9 +251,8 @@ struct gfs_lidar_mapper {
   int device, max_points, max_kf, max_blk;
   hipStream_t stream;
   std::mutex mu;
-  size_t o_q, o_t, o_cloud, in_bytes;  // staging: cloud_begin | q | t | cloud
-  gfs::DevBuf<uint8_t> d_in;
-  gfs::PinBuf<uint8_t> h_in;
+  gfs::LidarMapLayout Y{0, 0};  // staging: cloud_begin | q | t | cloud, at the handle's capacity
+  gfs::Mirror in;
   gfs::DevBuf<double> d_M;
   gfs::DevBuf<float4> d_world, d_out;
   gfs::DevBuf<unsigned> d_key[2], d_val[2];
@@ -282,10 +282,9 @@ int radix_sort(gfs_lidar_mapper* h, int from, int n, const int* n_dev, int passe
 // Upload done: transform (M null: none), filter.  Leaves the sorted pairs' centroids in d_out, the grid pairs in buffer 1.
 int launch_filter(gfs_lidar_mapper* h, int n, int n_kf, float leaf) {
   hipStream_t s = h->stream;
-  const float* d_q = reinterpret_cast<const float*>(h->d_in.p + h->o_q);
-  const float* d_t = reinterpret_cast<const float*>(h->d_in.p + h->o_t);
-  const float* d_cloud = reinterpret_cast<const float*>(h->d_in.p + h->o_cloud);
-  const int* d_cb = reinterpret_cast<const int*>(h->d_in.p);
+  const uint8_t* di = h->in.d.p;
+  const float *d_q = h->Y.q.at(di), *d_t = h->Y.t.at(di), *d_cloud = h->Y.cloud.at(di);
+  const int* d_cb = h->Y.cloud_begin.at(di);
   const int nblk = gfs::div_up(n, kTile), nb256 = gfs::div_up(n, kThreads);
   GFS_LAUNCH("k_lm_init", k_lm_init, dim3(gfs::div_up(std::max(n_kf, 1), 64)), dim3(64), 0, s, d_q, d_t, n_kf, h->d_M.p, h->d_ctl.p);
   GFS_LAUNCH("k_lm_transform", k_lm_transform, dim3(nb256), dim3(kThreads), 0, s, d_cloud, n, d_cb, n_kf,
@@ -323,29 +322,22 @@ int gfs_lidar_mapper_create(int device, int max_points_in, int max_keyframes, gf
   h->max_kf = max_keyframes;
   h->max_blk = gfs::div_up(max_points_in, kTile);
   const size_t N = (size_t)max_points_in, K = (size_t)max_keyframes;
-  auto up = [](size_t v) { return gfs::align_up(v, 256); };
-  h->o_q = up((K + 1) * 4);
-  h->o_t = h->o_q + up(K * 16);
-  h->o_cloud = h->o_t + up(K * 12);
-  h->in_bytes = h->o_cloud + up(N * 12);
+  h->Y = gfs::LidarMapLayout{K, N};
   GFS_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
   int rc = 0;
-#define A(x) if (!rc) rc = (x)
-  A(h->d_in.alloc(h->in_bytes));
-  A(h->h_in.alloc(h->in_bytes));
-  A(h->d_M.alloc(12 * K));
-  A(h->d_world.alloc(N));
-  A(h->d_out.alloc(N));
+  if (!rc) rc = h->in.alloc(h->Y.in.bytes());
+  if (!rc) rc = h->d_M.alloc(12 * K);
+  if (!rc) rc = h->d_world.alloc(N);
+  if (!rc) rc = h->d_out.alloc(N);
   for (int k = 0; k < 2; k++) {
-    A(h->d_key[k].alloc(N));
-    A(h->d_val[k].alloc(N));
+    if (!rc) rc = h->d_key[k].alloc(N);
+    if (!rc) rc = h->d_val[k].alloc(N);
   }
-  A(h->d_hist.alloc((size_t)kBins * h->max_blk));
-  A(h->d_blk.alloc((size_t)h->max_blk));
-  A(h->d_ctl.alloc(1));
-  A(h->h_ctl.alloc(1));
-  A(h->h_out.alloc(N));
-#undef A
+  if (!rc) rc = h->d_hist.alloc((size_t)kBins * h->max_blk);
+  if (!rc) rc = h->d_blk.alloc((size_t)h->max_blk);
+  if (!rc) rc = h->d_ctl.alloc(1);
+  if (!rc) rc = h->h_ctl.alloc(1);
+  if (!rc) rc = h->h_out.alloc(N);
   if (rc) {
     (void)hipStreamDestroy(h->stream);
     return rc;
@@ -380,13 +372,15 @@ int gfs_lidar_map_build(gfs_lidar_mapper* h, const gfs_lidar_map_input* in, gfs_
   GFS_REQUIRE(in->cloud, GFS_ERR_INVALID_ARG, "gfs_lidar_map_build: NULL cloud");
   std::lock_guard<std::mutex> lk(h->mu);
   GFS_HIP(hipSetDevice(h->device));
-  memcpy(h->h_in.p, in->cloud_begin, (size_t)(K + 1) * 4);
-  memcpy(h->h_in.p + h->o_q, in->q, (size_t)K * 16);
-  memcpy(h->h_in.p + h->o_t, in->t, (size_t)K * 12);
-  memcpy(h->h_in.p + h->o_cloud, in->cloud, (size_t)n * 12);
+  const gfs::LidarMapLayout& Y = h->Y;
+  uint8_t* hi = h->in.h.p;
+  Y.cloud_begin.put(hi, 0, in->cloud_begin, (size_t)K + 1);
+  Y.q.put(hi, 0, in->q, (size_t)K);
+  Y.t.put(hi, 0, in->t, (size_t)K);
+  Y.cloud.put(hi, 0, in->cloud, (size_t)n);
   hipStream_t s = h->stream;
   // one copy up to the end of the cloud (the offsets, the poses and the cloud lie in one staging block)
-  GFS_HIP(hipMemcpyAsync(h->d_in.p, h->h_in.p, h->o_cloud + (size_t)n * 12, hipMemcpyHostToDevice, s));
+  if (int rc = h->in.upload(s, 0, Y.cloud.off + Y.cloud.bytes((size_t)n))) return rc;
   int rc = launch_filter(h, n, K, in->leaf);
   if (rc) return rc;
   // the grid: n_out <= n is known to the device only; the passes cover the largest nb it can give
@@ -441,9 +435,10 @@ int gfs_voxel_grid_filter(gfs_lidar_mapper* h, const float* xyz, int n, float le
   if (info) *info = gfs_lidar_map_info{n, 0, 0, {0, 0, 0}};
   std::lock_guard<std::mutex> lk(h->mu);
   GFS_HIP(hipSetDevice(h->device));
-  memcpy(h->h_in.p + h->o_cloud, xyz, (size_t)n * 12);
+  const gfs::LidarMapLayout& Y = h->Y;
+  Y.cloud.put(h->in.h.p, 0, xyz, (size_t)n);
   hipStream_t s = h->stream;
-  GFS_HIP(hipMemcpyAsync(h->d_in.p + h->o_cloud, h->h_in.p + h->o_cloud, (size_t)n * 12, hipMemcpyHostToDevice, s));
+  if (int rc = h->in.upload(s, Y.cloud.off, Y.cloud.off + Y.cloud.bytes((size_t)n))) return rc;
   int rc = launch_filter(h, n, 0, leaf);
   if (rc) return rc;
   // n_out <= n: the whole possible output comes back with the control block, one synchronisation

@@ -15,6 +15,7 @@
 // No global atomics, no library primitives.
 #include <memory>
 
+#include "block_layouts.hpp"
 #include "gfs_common.hpp"
 #include "map_point_rule.hpp"
 
@@ -196,44 +197,11 @@ __global__ __launch_bounds__(kThreads) void k_map_points(const MpArgs A) {
 
 // One pinned block and one device block for the inputs, one of each for the outputs, sized by the reserve; a call lays its arrays
 // out for its own sizes, so that what travels is what the call holds.
-struct MpLayout {  // byte offsets
-  size_t i_obs_start, i_dsc_start, i_pos, i_ref, i_lscale, i_mscale, i_Ow, i_dsc_obs, i_flags, i_words, in_bytes;
-  size_t o_best, o_median, o_normal, o_min, o_max, o_status, out_bytes;
-  MpLayout(size_t P, size_t O) {
-    size_t at = 0;
-    auto take = [&at](size_t bytes) {
-      const size_t o = at;
-      at = gfs::align_up(at + bytes, 64);
-      return o;
-    };
-    i_obs_start = take((P + 1) * 4);
-    i_dsc_start = take((P + 1) * 4);
-    i_pos = take(P * 12);
-    i_ref = take(P * 12);
-    i_lscale = take(P * 4);
-    i_mscale = take(P * 4);
-    i_Ow = take(O * 12);
-    i_dsc_obs = take(O * 4);
-    i_flags = take(O);
-    i_words = take(O * 32);  // last: a normals-only call does not upload it, a full call only the IN_DESC rows
-    in_bytes = at;
-    at = 0;
-    o_best = take(P * 4);
-    o_median = take(P * 4);
-    o_normal = take(P * 12);
-    o_min = take(P * 4);
-    o_max = take(P * 4);
-    o_status = take(P);
-    out_bytes = at;
-  }
-};
-
 struct gfs_map_points {
   int device, max_points, max_obs;
   hipStream_t stream;
   std::mutex mu;
-  gfs::PinBuf<uint8_t> h_in, h_out;
-  gfs::DevBuf<uint8_t> d_in, d_out;
+  gfs::Mirror in, out;
 };
 
 extern "C" {
@@ -248,15 +216,11 @@ int gfs_map_points_create(int device, int max_points, int max_observations, gfs_
   h->device = device;
   h->max_points = max_points;
   h->max_obs = max_observations;
-  const MpLayout L((size_t)max_points, (size_t)max_observations);
+  const gfs::MpLayout L{(size_t)max_points, (size_t)max_observations};
   GFS_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
   int rc = 0;
-#define A(x) if (!rc) rc = (x)
-  A(h->h_in.alloc(L.in_bytes));
-  A(h->h_out.alloc(L.out_bytes));
-  A(h->d_in.alloc(L.in_bytes));
-  A(h->d_out.alloc(L.out_bytes));
-#undef A
+  if (!rc) rc = h->in.alloc(L.in.bytes());
+  if (!rc) rc = h->out.alloc(L.out.bytes());
   if (rc) {
     (void)hipStreamDestroy(h->stream);
     return rc;
@@ -298,69 +262,64 @@ int gfs_map_points_update(gfs_map_points* h, const gfs_map_points_problem* pr, g
               "gfs_map_points_update: a NULL result array");
   std::lock_guard<std::mutex> lk(h->mu);
   GFS_HIP(hipSetDevice(h->device));
-  const MpLayout L((size_t)P, (size_t)O);
+  const gfs::MpLayout L{(size_t)P, (size_t)O};
   // ---- staging: one block; the IN_DESC descriptors are compacted per point, in list order
-  uint8_t* in = h->h_in.p;
-  memcpy(in + L.i_obs_start, pr->obs_start, ((size_t)P + 1) * 4);
-  memcpy(in + L.i_pos, pr->pos, (size_t)P * 12);
-  memcpy(in + L.i_ref, pr->ref_Ow, (size_t)P * 12);
-  memcpy(in + L.i_lscale, pr->level_scale, (size_t)P * 4);
-  memcpy(in + L.i_mscale, pr->max_scale, (size_t)P * 4);
-  if (O) {
-    memcpy(in + L.i_Ow, pr->obs_Ow, (size_t)O * 12);
-    memcpy(in + L.i_flags, pr->obs_flags, (size_t)O);
-  }
+  uint8_t* in = h->in.h.p;
+  L.obs_start.put(in, 0, pr->obs_start, (size_t)P + 1);
+  L.pos.put(in, 0, pr->pos, (size_t)P);
+  L.ref.put(in, 0, pr->ref_Ow, (size_t)P);
+  L.lscale.put(in, 0, pr->level_scale, (size_t)P);
+  L.mscale.put(in, 0, pr->max_scale, (size_t)P);
+  L.Ow.put(in, 0, pr->obs_Ow, (size_t)O);
+  L.flags.put(in, 0, pr->obs_flags, (size_t)O);
   int n_dsc = 0;
   if (with_desc) {
-    int* dsc_start = reinterpret_cast<int*>(in + L.i_dsc_start);
-    int* dsc_obs = reinterpret_cast<int*>(in + L.i_dsc_obs);
-    uint8_t* words = in + L.i_words;
+    int *dsc_start = L.dsc_start.at(in), *dsc_obs = L.dsc_obs.at(in);
     for (int p = 0; p < P; p++) {
       dsc_start[p] = n_dsc;
       const int o0 = pr->obs_start[p], o1 = pr->obs_start[p + 1];
       for (int o = o0; o < o1; o++)
         if (pr->obs_flags[o] & GFS_MAP_POINT_OBS_IN_DESC) {
           dsc_obs[n_dsc] = o - o0;
-          memcpy(words + 32 * (size_t)n_dsc, pr->obs_desc + 32 * (size_t)o, 32);
+          L.words.put(in, (size_t)n_dsc, pr->obs_desc + 32 * (size_t)o, 1);
           n_dsc++;
         }
     }
     dsc_start[P] = n_dsc;
   }
   hipStream_t s = h->stream;
-  const size_t up = with_desc ? L.i_words + 32 * (size_t)n_dsc : L.i_words;
-  GFS_HIP(hipMemcpyAsync(h->d_in.p, in, up, hipMemcpyHostToDevice, s));
+  if (int rc = h->in.upload(s, 0, L.words.off + L.words.bytes((size_t)n_dsc))) return rc;  // (n_dsc = 0 without descriptors)
   MpArgs A{};
   A.n_points = P;
   A.with_desc = with_desc ? 1 : 0;
-  const uint8_t* di = h->d_in.p;
-  uint8_t* dout = h->d_out.p;
-  A.obs_start = reinterpret_cast<const int*>(di + L.i_obs_start);
-  A.dsc_start = reinterpret_cast<const int*>(di + L.i_dsc_start);
-  A.obs_Ow = reinterpret_cast<const float*>(di + L.i_Ow);
-  A.obs_flags = di + L.i_flags;
-  A.dsc_words = reinterpret_cast<const uint32_t*>(di + L.i_words);
-  A.dsc_obs = reinterpret_cast<const int*>(di + L.i_dsc_obs);
-  A.pos = reinterpret_cast<const float*>(di + L.i_pos);
-  A.ref_Ow = reinterpret_cast<const float*>(di + L.i_ref);
-  A.level_scale = reinterpret_cast<const float*>(di + L.i_lscale);
-  A.max_scale = reinterpret_cast<const float*>(di + L.i_mscale);
-  A.best_obs = reinterpret_cast<int*>(dout + L.o_best);
-  A.best_median = reinterpret_cast<int*>(dout + L.o_median);
-  A.normal = reinterpret_cast<float*>(dout + L.o_normal);
-  A.min_dist = reinterpret_cast<float*>(dout + L.o_min);
-  A.max_dist = reinterpret_cast<float*>(dout + L.o_max);
-  A.status = dout + L.o_status;
+  const uint8_t* di = h->in.d.p;
+  uint8_t* dout = h->out.d.p;
+  A.obs_start = L.obs_start.at(di);
+  A.dsc_start = L.dsc_start.at(di);
+  A.obs_Ow = L.Ow.at(di);
+  A.obs_flags = L.flags.at(di);
+  A.dsc_words = L.words.at(di);
+  A.dsc_obs = L.dsc_obs.at(di);
+  A.pos = L.pos.at(di);
+  A.ref_Ow = L.ref.at(di);
+  A.level_scale = L.lscale.at(di);
+  A.max_scale = L.mscale.at(di);
+  A.best_obs = L.best.at(dout);
+  A.best_median = L.median.at(dout);
+  A.normal = L.normal.at(dout);
+  A.min_dist = L.dmin.at(dout);
+  A.max_dist = L.dmax.at(dout);
+  A.status = L.status.at(dout);
   GFS_LAUNCH("k_map_points", k_map_points, dim3(gfs::div_up(P, kWaves)), dim3(kThreads), 0, s, A);
-  GFS_HIP(hipMemcpyAsync(h->h_out.p, h->d_out.p, L.o_status + (size_t)P, hipMemcpyDeviceToHost, s));
+  if (int rc = h->out.download(s, 0, L.status.off + L.status.bytes((size_t)P))) return rc;
   GFS_HIP(hipStreamSynchronize(s));
-  const uint8_t* o = h->h_out.p;
-  memcpy(res->best_obs, o + L.o_best, (size_t)P * 4);
-  memcpy(res->best_median, o + L.o_median, (size_t)P * 4);
-  memcpy(res->normal, o + L.o_normal, (size_t)P * 12);
-  memcpy(res->min_dist, o + L.o_min, (size_t)P * 4);
-  memcpy(res->max_dist, o + L.o_max, (size_t)P * 4);
-  memcpy(res->status, o + L.o_status, (size_t)P);
+  const uint8_t* o = h->out.h.p;
+  L.best.get(res->best_obs, o, 0, (size_t)P);
+  L.median.get(res->best_median, o, 0, (size_t)P);
+  L.normal.get(res->normal, o, 0, (size_t)P);
+  L.dmin.get(res->min_dist, o, 0, (size_t)P);
+  L.dmax.get(res->max_dist, o, 0, (size_t)P);
+  L.status.get(res->status, o, 0, (size_t)P);
   return GFS_OK;
 }
 

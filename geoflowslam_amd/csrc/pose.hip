@@ -19,6 +19,7 @@
 #include <memory>
 #include <mutex>
 
+#include "block_layouts.hpp"
 #include "g2o_se3_dev.hpp"
 #include "gfs_common.hpp"
 #include "pose_lm_dev.hpp"
@@ -396,14 +397,6 @@ __global__ __launch_bounds__(kPoseThreads) void k_pose_opt(const PoseFrame* __re
   PT_END
 }
 
-__global__ void k_test_glibc_math(const double* __restrict__ x, int n, double* __restrict__ out) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  out[i] = gfs_glibc::sin(x[i]);
-  out[n + i] = gfs_glibc::cos(x[i]);
-  out[2 * (size_t)n + i] = gfs_glibc::pow3(x[i]);
-}
-
 }  // namespace
 
 struct gfs_pose {
@@ -413,26 +406,9 @@ struct gfs_pose {
   // One pinned arena that mirrors one device block for the inputs (frames | xw | obs | w | stereo) and one for the outputs
   // (out | chi2 | outlier): a call is ONE copy in, the kernel, ONE copy out (five + three copies before: ~10 us of host time and a
   // copy-engine round trip each, more than the kernel's share of a single frame).
-  gfs::DevBuf<uint8_t> d_in, d_res;
-  gfs::PinBuf<uint8_t> h_in, h_res;
-  // layout of a call with B frames, arrays strided by `stride` (the call's largest observation count, rounded up) per frame
-  struct Layout {
-    size_t o_xw, o_obs, o_w, o_st, in_bytes, r_chi, r_outl, res_bytes;
-  };
-  Layout layout(size_t B, size_t stride) const {
-    auto up = [](size_t v) { return gfs::align_up(v, 256); };
-    const size_t E = stride * B;
-    Layout L;
-    L.o_xw = up(B * sizeof(PoseFrame));
-    L.o_obs = L.o_xw + up(E * 24);
-    L.o_w = L.o_obs + up(E * 24);
-    L.o_st = L.o_w + up(E * 4);
-    L.in_bytes = L.o_st + up(E);
-    L.r_chi = up(B * sizeof(PoseOut));
-    L.r_outl = L.r_chi + up(E * 8);
-    L.res_bytes = L.r_outl + up(E);
-    return L;
-  }
+  // The layout is that of a call with B frames, arrays strided by the call's largest observation count, rounded up, per frame.
+  using Layout = gfs::PoseLayout<PoseFrame, PoseOut>;
+  gfs::Mirror in, res;
   gfs::DevBuf<double> d_err;
   gfs::DevBuf<uint8_t> d_level;
   int sum_order = GFS_POSE_SUMS_EDGE_ORDER;  // the ABI default reproduces g2o's integer outputs; the tree is opt-in (gfs_abi.h)
@@ -451,15 +427,11 @@ int gfs_pose_create(int device, int max_obs, int max_batch, gfs_pose** out) {
   GFS_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
   const size_t Smax = gfs::align_up((size_t)max_obs, 64), E = Smax * max_batch, B = max_batch;
   int rc = 0;
-#define A(x) if (!rc) rc = (x)
-  const gfs_pose::Layout L = h->layout(B, Smax);
-  A(h->d_in.alloc(L.in_bytes));
-  A(h->h_in.alloc(L.in_bytes));
-  A(h->d_res.alloc(L.res_bytes));
-  A(h->h_res.alloc(L.res_bytes));
-  A(h->d_err.alloc(E * 3));
-  A(h->d_level.alloc(E));
-#undef A
+  const gfs_pose::Layout L{B, Smax};
+  if (!rc) rc = h->in.alloc(L.in.bytes());
+  if (!rc) rc = h->res.alloc(L.res.bytes());
+  if (!rc) rc = h->d_err.alloc(E * 3);
+  if (!rc) rc = h->d_level.alloc(E);
   if (rc) {
     (void)hipStreamDestroy(h->stream);
     return rc;
@@ -496,22 +468,15 @@ int gfs_pose_optimize(gfs_pose* h, const gfs_pose_problem* problems, int B, gfs_
     S = std::max(S, (int)gfs::align_up((size_t)problems[f].n_obs, 64));
   }
   S = std::min(S, (int)gfs::align_up((size_t)h->max_obs, 64));
-  const gfs_pose::Layout L = h->layout((size_t)B, (size_t)S);
-  PoseFrame* h_frames = reinterpret_cast<PoseFrame*>(h->h_in.p);
-  double* h_xw = reinterpret_cast<double*>(h->h_in.p + L.o_xw);
-  double* h_obs = reinterpret_cast<double*>(h->h_in.p + L.o_obs);
-  float* h_w = reinterpret_cast<float*>(h->h_in.p + L.o_w);
-  uint8_t* h_stereo = h->h_in.p + L.o_st;
-  const PoseOut* h_out = reinterpret_cast<const PoseOut*>(h->h_res.p);
-  const double* h_chi2 = reinterpret_cast<const double*>(h->h_res.p + L.r_chi);
-  const uint8_t* h_outlier = h->h_res.p + L.r_outl;
+  const gfs_pose::Layout L{(size_t)B, (size_t)S};
+  uint8_t* hi = h->in.h.p;
   for (int f = 0; f < B; f++) {
     const gfs_pose_problem& p = problems[f];
     GFS_REQUIRE(p.n_obs == 0 || (p.xw && p.obs && p.inv_sigma2 && p.stereo), GFS_ERR_INVALID_ARG,
                 "gfs_pose_optimize: frame %d has NULL observation arrays", f);
     GFS_REQUIRE(p.n_obs == 0 || (solutions[f].outlier && solutions[f].chi2), GFS_ERR_INVALID_ARG,
                 "gfs_pose_optimize: frame %d has NULL output arrays", f);
-    PoseFrame& F = h_frames[f];
+    PoseFrame& F = L.frames.at(hi)[f];
     for (int k = 0; k < 4; k++) F.q[k] = p.q[k];
     for (int k = 0; k < 3; k++) F.t[k] = p.t[k];
     F.fx = p.fx;
@@ -523,34 +488,32 @@ int gfs_pose_optimize(gfs_pose* h, const gfs_pose_problem* problems, int B, gfs_
     F.n_rounds = p.n_rounds;
     F.its = p.its;
     F.pad = 0;
-    if (p.n_obs > 0) {
-      memcpy(h_xw + (size_t)f * S * 3, p.xw, (size_t)p.n_obs * 24);
-      memcpy(h_obs + (size_t)f * S * 3, p.obs, (size_t)p.n_obs * 24);
-      memcpy(h_w + (size_t)f * S, p.inv_sigma2, (size_t)p.n_obs * 4);
-      memcpy(h_stereo + (size_t)f * S, p.stereo, (size_t)p.n_obs);
-    }
+    const size_t at = (size_t)f * S, n = (size_t)p.n_obs;
+    L.xw.put(hi, at, p.xw, n);
+    L.obs.put(hi, at, p.obs, n);
+    L.w.put(hi, at, p.inv_sigma2, n);
+    L.stereo.put(hi, at, p.stereo, n);
   }
   hipStream_t s = h->stream;
-  GFS_HIP(hipMemcpyAsync(h->d_in.p, h->h_in.p, L.in_bytes, hipMemcpyHostToDevice, s));
+  if (int rc = h->in.upload(s, 0, L.in.bytes())) return rc;
+  const uint8_t* di = h->in.d.p;
+  uint8_t* dr = h->res.d.p;
   auto launch = [&](auto kernel) -> int {
-    GFS_LAUNCH("k_pose_opt", kernel, dim3(B), dim3(kPoseThreads), 0, s, reinterpret_cast<const PoseFrame*>(h->d_in.p),
-               reinterpret_cast<const double*>(h->d_in.p + L.o_xw), reinterpret_cast<const double*>(h->d_in.p + L.o_obs),
-               reinterpret_cast<const float*>(h->d_in.p + L.o_w), (const uint8_t*)(h->d_in.p + L.o_st), S, h->d_res.p + L.r_outl,
-               reinterpret_cast<double*>(h->d_res.p + L.r_chi), h->d_err.p, h->d_level.p, reinterpret_cast<PoseOut*>(h->d_res.p));
+    GFS_LAUNCH("k_pose_opt", kernel, dim3(B), dim3(kPoseThreads), 0, s, L.frames.at(di), L.xw.at(di), L.obs.at(di), L.w.at(di),
+               L.stereo.at(di), S, L.outlier.at(dr), L.chi2.at(dr), h->d_err.p, h->d_level.p, L.out.at(dr));
     return GFS_OK;
   };
   const int rc_launch = h->sum_order == GFS_POSE_SUMS_EDGE_ORDER ? launch(k_pose_opt<false>) : launch(k_pose_opt<true>);
   if (rc_launch) return rc_launch;
-  GFS_HIP(hipMemcpyAsync(h->h_res.p, h->d_res.p, L.res_bytes, hipMemcpyDeviceToHost, s));
+  if (int rc = h->res.download(s, 0, L.res.bytes())) return rc;
   GFS_HIP(hipStreamSynchronize(s));
+  const uint8_t* hr = h->res.h.p;
   for (int f = 0; f < B; f++) {
-    const PoseOut& O = h_out[f];
+    const PoseOut& O = L.out.at(hr)[f];
     gfs_pose_solution& r = solutions[f];
     const int n = problems[f].n_obs;
-    if (n > 0) {
-      memcpy(r.outlier, h_outlier + (size_t)f * S, n);
-      memcpy(r.chi2, h_chi2 + (size_t)f * S, (size_t)n * 8);
-    }
+    L.outlier.get(r.outlier, hr, (size_t)f * S, n);
+    L.chi2.get(r.chi2, hr, (size_t)f * S, n);
     for (int k = 0; k < 4; k++) r.q[k] = O.q[k];
     for (int k = 0; k < 3; k++) r.t[k] = O.t[k];
     r.avg_reproj_error = O.avg;
@@ -558,24 +521,6 @@ int gfs_pose_optimize(gfs_pose* h, const gfs_pose_problem* problems, int B, gfs_
     r.rounds_run = O.rounds_run;
     r.iterations_run = O.iterations_run;
   }
-  return GFS_OK;
-}
-
-// Test hook: the restated glibc functions evaluated on the device (tests/test_gpu_glibc_math.py).
-int gfs_test_glibc_math(int device, const double* x, int n, double* sin_out, double* cos_out, double* pow3_out) {
-  GFS_REQUIRE(x && sin_out && cos_out && pow3_out && n >= 0, GFS_ERR_INVALID_ARG, "gfs_test_glibc_math: invalid argument");
-  if (!gfs::device_ok(device)) return GFS_ERR_NO_DEVICE;
-  if (n == 0) return GFS_OK;
-  GFS_HIP(hipSetDevice(device));
-  gfs::DevBuf<double> d_x, d_o;
-  int rc = d_x.alloc(n);
-  if (!rc) rc = d_o.alloc((size_t)3 * n);
-  if (rc) return rc;
-  GFS_HIP(hipMemcpy(d_x.p, x, (size_t)n * 8, hipMemcpyHostToDevice));
-  GFS_LAUNCH("k_test_glibc_math", k_test_glibc_math, dim3(gfs::div_up(n, 256)), dim3(256), 0, (hipStream_t)0, d_x.p, n, d_o.p);
-  GFS_HIP(hipMemcpy(sin_out, d_o.p, (size_t)n * 8, hipMemcpyDeviceToHost));
-  GFS_HIP(hipMemcpy(cos_out, d_o.p + n, (size_t)n * 8, hipMemcpyDeviceToHost));
-  GFS_HIP(hipMemcpy(pow3_out, d_o.p + 2 * (size_t)n, (size_t)n * 8, hipMemcpyDeviceToHost));
   return GFS_OK;
 }
 

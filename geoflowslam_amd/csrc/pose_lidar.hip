@@ -21,6 +21,7 @@
 #include <mutex>
 #include <vector>
 
+#include "block_layouts.hpp"
 #include "g2o_se3_dev.hpp"
 #include "gfs_common.hpp"
 #include "lidar_assoc.hpp"
@@ -469,22 +470,8 @@ struct gfs_pose_lidar {
   hipStream_t stream;
   std::mutex mu;
   int sum_order = GFS_POSE_SUMS_EDGE_ORDER;
-  struct Layout {
-    size_t o_xw, o_obs, o_w, o_st, o_cloud, in_bytes;
-  };
-  static Layout layout(size_t B, size_t S, size_t SC) {
-    auto up = [](size_t v) { return gfs::align_up(v, 256); };
-    Layout L;
-    L.o_xw = up(B * sizeof(LFrame));
-    L.o_obs = L.o_xw + up(B * S * 24);
-    L.o_w = L.o_obs + up(B * S * 24);
-    L.o_st = L.o_w + up(B * S * 4);
-    L.o_cloud = L.o_st + up(B * S);
-    L.in_bytes = L.o_cloud + up(B * SC * 12);
-    return L;
-  }
-  gfs::DevBuf<uint8_t> d_in;
-  gfs::PinBuf<uint8_t> h_in;
+  using Layout = gfs::PoseLidarLayout<LFrame>;
+  gfs::Mirror in;
   gfs::DevBuf<LState> d_state;
   gfs::PinBuf<LState> h_state;
   gfs::DevBuf<double> d_err, d_chi2, d_lerr, d_lchi2;
@@ -568,28 +555,25 @@ int gfs_pose_lidar_create(int device, int max_obs, int max_cloud, int max_batch,
   h->max_batch = max_batch;
   GFS_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
   const size_t S = gfs::align_up((size_t)max_obs, 64), SC = gfs::align_up((size_t)max_cloud, 64), B = max_batch;
-  const gfs_pose_lidar::Layout L = gfs_pose_lidar::layout(B, S, SC);
+  const gfs_pose_lidar::Layout L{B, S, SC};
   int rc = 0;
-#define A(x) if (!rc) rc = (x)
-  A(h->d_in.alloc(L.in_bytes));
-  A(h->h_in.alloc(L.in_bytes));
-  A(h->d_state.alloc(B));
-  A(h->h_state.alloc(B));
-  A(h->d_err.alloc(B * S * 3));
-  A(h->d_chi2.alloc(B * S));
-  A(h->h_chi2.alloc(B * S));
-  A(h->d_level.alloc(B * S));
-  A(h->d_outl.alloc(B * S));
-  A(h->h_outl.alloc(B * S));
-  A(h->d_flag.alloc(B * SC));
-  A(h->d_plane.alloc(B * SC));
-  A(h->d_s.alloc(B * SC));
-  A(h->d_lerr.alloc(B * SC));
-  A(h->d_lchi2.alloc(B * SC));
-  A(h->d_eidx.alloc(B * 4 * SC));
-  A(h->d_eplane.alloc(B * 4 * SC));
-  A(h->d_es.alloc(B * 4 * SC));
-#undef A
+  if (!rc) rc = h->in.alloc(L.in.bytes());
+  if (!rc) rc = h->d_state.alloc(B);
+  if (!rc) rc = h->h_state.alloc(B);
+  if (!rc) rc = h->d_err.alloc(B * S * 3);
+  if (!rc) rc = h->d_chi2.alloc(B * S);
+  if (!rc) rc = h->h_chi2.alloc(B * S);
+  if (!rc) rc = h->d_level.alloc(B * S);
+  if (!rc) rc = h->d_outl.alloc(B * S);
+  if (!rc) rc = h->h_outl.alloc(B * S);
+  if (!rc) rc = h->d_flag.alloc(B * SC);
+  if (!rc) rc = h->d_plane.alloc(B * SC);
+  if (!rc) rc = h->d_s.alloc(B * SC);
+  if (!rc) rc = h->d_lerr.alloc(B * SC);
+  if (!rc) rc = h->d_lchi2.alloc(B * SC);
+  if (!rc) rc = h->d_eidx.alloc(B * 4 * SC);
+  if (!rc) rc = h->d_eplane.alloc(B * 4 * SC);
+  if (!rc) rc = h->d_es.alloc(B * 4 * SC);
   if (rc) {
     (void)hipStreamDestroy(h->stream);
     return rc;
@@ -638,16 +622,11 @@ int gfs_pose_lidar_optimize(gfs_pose_lidar* h, const gfs_pose_lidar_problem* pro
     SC = std::max(SC, (int)gfs::align_up((size_t)p.n_cloud, 64));
     rounds = std::max(rounds, (int)p.n_iterations);
   }
-  const gfs_pose_lidar::Layout L = gfs_pose_lidar::layout((size_t)B, (size_t)S, (size_t)SC);
-  LFrame* hf = reinterpret_cast<LFrame*>(h->h_in.p);
-  double* h_xw = reinterpret_cast<double*>(h->h_in.p + L.o_xw);
-  double* h_obs = reinterpret_cast<double*>(h->h_in.p + L.o_obs);
-  float* h_w = reinterpret_cast<float*>(h->h_in.p + L.o_w);
-  uint8_t* h_st = h->h_in.p + L.o_st;
-  float* h_cloud = reinterpret_cast<float*>(h->h_in.p + L.o_cloud);
+  const gfs_pose_lidar::Layout L{(size_t)B, (size_t)S, (size_t)SC};
+  uint8_t* hi = h->in.h.p;
   for (int f = 0; f < B; f++) {
     const gfs_pose_lidar_problem& p = problems[f];
-    LFrame& F = hf[f];
+    LFrame& F = L.frames.at(hi)[f];
     for (int k = 0; k < 4; k++) F.q[k] = p.q[k];
     for (int k = 0; k < 3; k++) F.t[k] = p.t[k];
     F.residual_in = solutions[f].residual;
@@ -664,20 +643,19 @@ int gfs_pose_lidar_optimize(gfs_pose_lidar* h, const gfs_pose_lidar_problem* pro
     F.map_start = p.map->d_start.p;
     F.map_nb = p.map->nb;
     F.map_n = p.map->n;
-    if (p.n_obs > 0) {
-      memcpy(h_xw + (size_t)f * S * 3, p.xw, (size_t)p.n_obs * 24);
-      memcpy(h_obs + (size_t)f * S * 3, p.obs, (size_t)p.n_obs * 24);
-      memcpy(h_w + (size_t)f * S, p.inv_sigma2, (size_t)p.n_obs * 4);
-      memcpy(h_st + (size_t)f * S, p.stereo, (size_t)p.n_obs);
-    }
-    if (p.n_cloud > 0) memcpy(h_cloud + (size_t)f * SC * 3, p.cloud, (size_t)p.n_cloud * 12);
+    const size_t at = (size_t)f * S, n = (size_t)p.n_obs;
+    L.xw.put(hi, at, p.xw, n);
+    L.obs.put(hi, at, p.obs, n);
+    L.w.put(hi, at, p.inv_sigma2, n);
+    L.stereo.put(hi, at, p.stereo, n);
+    L.cloud.put(hi, (size_t)f * SC, p.cloud, (size_t)p.n_cloud);
   }
   hipStream_t s = h->stream;
-  GFS_HIP(hipMemcpyAsync(h->d_in.p, h->h_in.p, L.in_bytes, hipMemcpyHostToDevice, s));
-  const LFrame* d_frames = reinterpret_cast<const LFrame*>(h->d_in.p);
-  VisView V{reinterpret_cast<const double*>(h->d_in.p + L.o_xw), reinterpret_cast<const double*>(h->d_in.p + L.o_obs),
-            reinterpret_cast<const float*>(h->d_in.p + L.o_w), h->d_in.p + L.o_st, h->d_err.p, h->d_chi2.p, h->d_level.p, h->d_outl.p};
-  const float* d_cloud = reinterpret_cast<const float*>(h->d_in.p + L.o_cloud);
+  if (int rc = h->in.upload(s, 0, L.in.bytes())) return rc;
+  const uint8_t* di = h->in.d.p;
+  const LFrame* d_frames = L.frames.at(di);
+  VisView V{L.xw.at(di), L.obs.at(di), L.w.at(di), L.stereo.at(di), h->d_err.p, h->d_chi2.p, h->d_level.p, h->d_outl.p};
+  const float* d_cloud = L.cloud.at(di);
   GFS_LAUNCH("k_pl_init", k_pl_init, dim3(B), dim3(64), 0, s, d_frames, h->d_state.p, V, S);
   for (int it = 0; it < rounds; it++) {
     GFS_LAUNCH("k_pl_assoc", k_pl_assoc, dim3(SC / kThreads + (SC % kThreads ? 1 : 0), B), dim3(kThreads), 0, s, d_frames, h->d_state.p,

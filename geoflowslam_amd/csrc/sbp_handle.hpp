@@ -1,16 +1,61 @@
-// What triangulate.hip needs of a gfs_sbp handle (the struct itself is sbp.hip's): its device, stream, lock and capacities, and the
-// slot that holds the triangulation workspace.
+// The gfs_sbp handle as sbp.hip, local_points.hip, fuse.hip and triangulate.hip see it: device, stream, lock and capacities, the
+// staging of gfs_search_by_projection*, and one slot per feature that reserves a workspace of its own (defined in the feature's file,
+// allocated by its gfs_sbp_reserve_*, freed with the handle).
 #pragma once
-#include "gfs_common.hpp"
+#include <memory>
 
-struct gfs_tri_workspace;  // triangulate.hip
+#include "block_layouts.hpp"
+#include "sbp_dev.hpp"
 
-struct gfs_sbp_core {
-  int device, max_cur, max_batch;
-  hipStream_t stream;
-  std::mutex* mu;
-  gfs_tri_workspace** tri;
+struct gfs_sbp_workspace {  // what a feature reserves: defined in the feature's file, allocated by its gfs_sbp_reserve_*
+  virtual ~gfs_sbp_workspace() = default;
 };
 
-gfs_sbp_core gfs_sbp_core_of(gfs_sbp* h);           // sbp.hip
-void gfs_tri_workspace_free(gfs_tri_workspace* w);  // triangulate.hip; called by gfs_sbp_destroy
+struct gfs_sbp {
+  int device, max_last, max_cur, max_batch;
+  hipStream_t stream;
+  std::mutex mu;
+  // One pinned arena that mirrors one device block for the inputs, one for the results: a call is ONE copy in, the kernel, ONE copy
+  // out (ten + two copies before -- ~10 us of host time and a copy-engine round trip each, twice the kernel's time for one frame).
+  // The per-frame arrays are strided by the CALL's largest counts (rounded up to 64), not by the handle's capacity.
+  gfs::Mirror in, res;
+  gfs::DevBuf<int> d_cand_cnt, d_lsel;
+  gfs::DevBuf<unsigned> d_cand;
+  std::unique_ptr<gfs_sbp_workspace> local, fuse, tri;  // local_points.hip, fuse.hip, triangulate.hip
+};
+
+namespace gfs {
+
+using SbpBlocks = SbpLayout<SbpPair>;
+
+// ---- sbp.hip, for the entry points that stage a current frame and run k_sbp ----
+// the call's stride of a per-frame array: the largest count of the call rounded up to 64, within the capacity
+template <class Count>
+int sbp_stride(int B, int cap, Count&& count) {
+  int S = 64;
+  for (int f = 0; f < B; f++) S = std::max(S, (int)align_up((size_t)std::max(count(f), 0), 64));
+  return std::min(S, (int)align_up((size_t)cap, 64));
+}
+// the header of a map search (mode 1: ORBmatcher.cc:43-206) with n_last map points
+template <class Problem>
+void sbp_map_pair(SbpPair& S, const Problem& p, int n_last) {
+  memset(&S, 0, sizeof(S));
+  S.n_last = n_last;
+  S.n_cur = p.n_cur;
+  S.n_levels = p.n_levels;
+  S.mode = 1;
+  S.nn_ratio = p.nn_ratio;
+  S.min_x = p.min_x;
+  S.min_y = p.min_y;
+  S.grid_w_inv = p.grid_w_inv;
+  S.grid_h_inv = p.grid_h_inv;
+  S.th = p.th;
+  for (int k = 0; k < 16; k++) S.scale[k] = k < p.n_levels ? p.scale_factors[k] : 0.f;
+}
+// copies frame f's key-point arrays into the pinned input block
+void sbp_stage_cur(gfs_sbp* h, const SbpBlocks& Y, int f, int n_cur, const gfs_keypoint* kps, const float* u_right, const uint8_t* desc,
+                   const uint8_t* has_mp_obs);
+// launches k_sbp on the device input block; cur_match [B][Y.SC] and nmatches [B] are device pointers
+int sbp_launch(gfs_sbp* h, int B, const SbpBlocks& Y, int* cur_match, int* nmatches);
+
+}  // namespace gfs

@@ -15,7 +15,6 @@
 // No global atomics; the results do not depend on scheduling.
 #include <algorithm>
 #include <climits>
-#include <memory>
 
 #include "sbp_handle.hpp"
 #include "triangulate_rule.hpp"
@@ -279,26 +278,19 @@ __global__ __launch_bounds__(kResThreads) void k_tri_resolve(const uint8_t* __re
   }
 }
 
-size_t up256(size_t v) { return gfs::align_up(v, 256); }
+using HeadLayout = gfs::TriHeadLayout<TriProb, TriSlot, TriFrame>;
 
 }  // namespace
 
-struct gfs_tri_workspace {
+struct gfs_tri_workspace : gfs_sbp_workspace {
   int max_neighbours = 0;
   long long max_pairs = 0;
-  gfs::DevBuf<uint8_t> d_in, d_out, d_mat;
-  gfs::PinBuf<uint8_t> h_in, h_out;
-  size_t in_bytes = 0, out_bytes = 0, mat_bytes = 0;
+  gfs::Mirror in, out;
+  gfs::DevBuf<uint8_t> d_mat;
+  size_t in_bytes = 0, mat_bytes = 0;
 };
 
-void gfs_tri_workspace_free(gfs_tri_workspace* w) { delete w; }
-
 namespace {
-
-// bytes of one key frame's arrays in the input block, n key-points (rounded up by the caller), m nodes
-size_t frame_bytes(size_t n, size_t m) {
-  return up256(n * 8) * 2 + up256(n * 4) * 3 + up256(n) * 2 + up256(n * 32) + up256(m * 4) + up256((m + 1) * 4) + up256(n * 4);
-}
 
 int validate_kf(const gfs_tri_keyframe& k, int max_cur, const char* what, int b, int i, std::vector<uint8_t>& seen) {
   GFS_REQUIRE(k.n_kp >= 0 && k.n_kp <= max_cur, GFS_ERR_CAPACITY, "gfs_create_new_map_points: problem %d %s %d has %d key-points (capacity %d)",
@@ -335,8 +327,8 @@ int validate_kf(const gfs_tri_keyframe& k, int max_cur, const char* what, int b,
   return GFS_OK;
 }
 
-// copies a key frame's arrays behind `at` in the staging block and fills its device header
-void stage_kf(const gfs_tri_keyframe& k, const float* ep, const float* F12, uint8_t* base, size_t& at, TriFrame& F) {
+// takes a key frame's arrays from the staging block's cursor, copies them there and fills its device header
+void stage_kf(const gfs_tri_keyframe& k, const float* ep, const float* F12, uint8_t* base, gfs::Block<256>& in, TriFrame& F) {
   memset(&F, 0, sizeof(F));
   memcpy(F.cam.Tcw, k.Tcw, sizeof(k.Tcw));
   memcpy(F.cam.Ow, k.Ow, sizeof(k.Ow));
@@ -360,40 +352,34 @@ void stage_kf(const gfs_tri_keyframe& k, const float* ep, const float* F12, uint
   F.n_kp = k.n_kp;
   F.n_nodes = k.n_nodes;
   const size_t n = (size_t)k.n_kp, m = (size_t)k.n_nodes, nf = (size_t)k.node_start[k.n_nodes];
-  auto take = [&](size_t bytes) {
-    const size_t o = at;
-    at += up256(bytes);
-    return o;
-  };
-  F.o_un = (unsigned)take(n * 8);
-  F.o_kps = (unsigned)take(n * 8);
-  F.o_ang = (unsigned)take(n * 4);
-  F.o_ur = (unsigned)take(n * 4);
-  F.o_depth = (unsigned)take(n * 4);
-  F.o_oct = (unsigned)take(n);
-  F.o_hasmp = (unsigned)take(n);
-  F.o_desc = (unsigned)take(n * 32);
-  F.o_nid = (unsigned)take(m * 4);
-  F.o_nstart = (unsigned)take((m + 1) * 4);
-  F.o_feat = (unsigned)take(nf * 4);
-  float2* un = reinterpret_cast<float2*>(base + F.o_un);
-  float2* raw = reinterpret_cast<float2*>(base + F.o_kps);
-  float* ang = reinterpret_cast<float*>(base + F.o_ang);
+  const gfs::TriKfArrays A{in, n, m, nf};
+  F.o_un = (unsigned)A.un.off;
+  F.o_kps = (unsigned)A.kps.off;
+  F.o_ang = (unsigned)A.ang.off;
+  F.o_ur = (unsigned)A.ur.off;
+  F.o_depth = (unsigned)A.depth.off;
+  F.o_oct = (unsigned)A.oct.off;
+  F.o_hasmp = (unsigned)A.hasmp.off;
+  F.o_desc = (unsigned)A.desc.off;
+  F.o_nid = (unsigned)A.nid.off;
+  F.o_nstart = (unsigned)A.nstart.off;
+  F.o_feat = (unsigned)A.feat.off;
+  float2 *un = A.un.at(base), *raw = A.kps.at(base);
+  float* ang = A.ang.at(base);
+  uint8_t *oct = A.oct.at(base), *hasmp = A.hasmp.at(base);
   for (size_t i = 0; i < n; i++) {
     un[i] = make_float2(k.kps_un[i].x, k.kps_un[i].y);
     raw[i] = make_float2(k.kps[i].x, k.kps[i].y);
     ang[i] = k.kps_un[i].angle;
-    base[F.o_oct + i] = (uint8_t)k.kps_un[i].octave;
-    base[F.o_hasmp + i] = k.has_mp[i] ? 1 : 0;
+    oct[i] = (uint8_t)k.kps_un[i].octave;
+    hasmp[i] = k.has_mp[i] ? 1 : 0;
   }
-  if (n > 0) {
-    memcpy(base + F.o_ur, k.u_right, n * 4);
-    memcpy(base + F.o_depth, k.depth, n * 4);
-    memcpy(base + F.o_desc, k.desc, n * 32);
-  }
-  if (m > 0) memcpy(base + F.o_nid, k.node_id, m * 4);
-  memcpy(base + F.o_nstart, k.node_start, (m + 1) * 4);
-  if (nf > 0) memcpy(base + F.o_feat, k.feat_idx, nf * 4);
+  A.ur.put(base, 0, k.u_right, n);
+  A.depth.put(base, 0, k.depth, n);
+  A.desc.put(base, 0, k.desc, n);
+  A.nid.put(base, 0, k.node_id, m);
+  A.nstart.put(base, 0, k.node_start, m + 1);
+  A.feat.put(base, 0, k.feat_idx, nf);
 }
 
 }  // namespace
@@ -403,42 +389,35 @@ extern "C" {
 int gfs_sbp_reserve_triangulation(gfs_sbp* h, int max_neighbours, int64_t max_candidate_pairs) {
   GFS_REQUIRE(h && max_neighbours > 0 && max_candidate_pairs > 0 && max_candidate_pairs <= INT_MAX, GFS_ERR_INVALID_ARG,
               "gfs_sbp_reserve_triangulation: invalid argument");
-  const gfs_sbp_core c = gfs_sbp_core_of(h);
-  std::lock_guard<std::mutex> lk(*c.mu);
-  GFS_HIP(hipSetDevice(c.device));
-  GFS_HIP(hipStreamSynchronize(c.stream));
-  delete *c.tri;
-  *c.tri = nullptr;
+  std::lock_guard<std::mutex> lk(h->mu);
+  GFS_HIP(hipSetDevice(h->device));
+  GFS_HIP(hipStreamSynchronize(h->stream));
+  h->tri.reset();
   std::unique_ptr<gfs_tri_workspace> w(new gfs_tri_workspace);
-  const size_t B = (size_t)c.max_batch, NB = (size_t)max_neighbours, SC = gfs::align_up((size_t)c.max_cur, 64);
-  w->in_bytes = up256(B * sizeof(TriProb)) + up256(B * NB * sizeof(TriSlot)) + up256(B * (NB + 1) * sizeof(TriFrame)) + up256(B * NB * SC * 4) +
-                B * (NB + 1) * frame_bytes(SC, SC);
+  const size_t B = (size_t)h->max_batch, NB = (size_t)max_neighbours, SC = gfs::align_up((size_t)h->max_cur, 64);
+  gfs::Block<256> one_kf;
+  const gfs::TriKfArrays widest{one_kf, SC, SC, SC};  // a key frame of the capacity: SC key-points, as many nodes, every key-point listed
+  w->in_bytes = HeadLayout{B, B * NB, B * (NB + 1), B * NB * SC}.in.bytes() + B * (NB + 1) * widest.in.bytes();
   GFS_REQUIRE(w->in_bytes < 0xffffffffull, GFS_ERR_UNSUPPORTED, "gfs_sbp_reserve_triangulation: the input block would exceed 4 GiB");
-  w->out_bytes = up256(B * NB * SC * 4) + up256(B * NB * SC) * 2 + up256(B * NB * SC * 12);
-  w->mat_bytes = up256(B * (size_t)max_candidate_pairs);
+  w->mat_bytes = gfs::align_up(B * (size_t)max_candidate_pairs, 256);
   int rc = 0;
-#define A(x) if (!rc) rc = (x)
-  A(w->d_in.alloc(w->in_bytes));
-  A(w->h_in.alloc(w->in_bytes));
-  A(w->d_out.alloc(w->out_bytes));
-  A(w->h_out.alloc(w->out_bytes));
-  A(w->d_mat.alloc(w->mat_bytes));
-#undef A
+  if (!rc) rc = w->in.alloc(w->in_bytes);
+  if (!rc) rc = w->out.alloc(gfs::TriOutLayout{B * NB * SC}.out.bytes());
+  if (!rc) rc = w->d_mat.alloc(w->mat_bytes);
   if (rc) return rc;
   w->max_neighbours = max_neighbours;
   w->max_pairs = max_candidate_pairs;
-  *c.tri = w.release();
+  h->tri = std::move(w);
   return GFS_OK;
 }
 
 int gfs_create_new_map_points(gfs_sbp* h, const gfs_tri_problem* problems, int B, gfs_tri_result* const* results) {
   GFS_REQUIRE(h && problems && results && B > 0, GFS_ERR_INVALID_ARG, "gfs_create_new_map_points: invalid argument");
-  const gfs_sbp_core c = gfs_sbp_core_of(h);
-  std::lock_guard<std::mutex> lk(*c.mu);
-  gfs_tri_workspace* w = *c.tri;
+  std::lock_guard<std::mutex> lk(h->mu);
+  gfs_tri_workspace* w = static_cast<gfs_tri_workspace*>(h->tri.get());
   GFS_REQUIRE(w, GFS_ERR_CAPACITY, "gfs_create_new_map_points: call gfs_sbp_reserve_triangulation first");
-  GFS_REQUIRE(B <= c.max_batch, GFS_ERR_CAPACITY, "gfs_create_new_map_points: batch %d exceeds capacity %d", B, c.max_batch);
-  GFS_HIP(hipSetDevice(c.device));
+  GFS_REQUIRE(B <= h->max_batch, GFS_ERR_CAPACITY, "gfs_create_new_map_points: batch %d exceeds capacity %d", B, h->max_batch);
+  GFS_HIP(hipSetDevice(h->device));
   // every refusal comes before anything is staged
   std::vector<uint8_t> seen;
   std::vector<int> pair_off;  // per (slot, node of the current key frame): the matrix's offset within the slot's problem, -1 = not common
@@ -451,11 +430,11 @@ int gfs_create_new_map_points(gfs_sbp* h, const gfs_tri_problem* problems, int B
     GFS_REQUIRE(Q.n_neighbours >= 0 && Q.n_neighbours <= w->max_neighbours, GFS_ERR_CAPACITY,
                 "gfs_create_new_map_points: problem %d has %d neighbours (reserve %d)", b, Q.n_neighbours, w->max_neighbours);
     GFS_REQUIRE(Q.n_neighbours == 0 || (Q.neighbours && results[b]), GFS_ERR_INVALID_ARG, "gfs_create_new_map_points: problem %d has NULL neighbours or results", b);
-    if (int rc = validate_kf(Q.cur, c.max_cur, "current key frame", b, 0, seen)) return rc;
+    if (int rc = validate_kf(Q.cur, h->max_cur, "current key frame", b, 0, seen)) return rc;
     long long pairs = 0;
     for (int i = 0; i < Q.n_neighbours; i++) {
       const gfs_tri_keyframe& K2 = Q.neighbours[i].kf;
-      if (int rc = validate_kf(K2, c.max_cur, "neighbour", b, i, seen)) return rc;
+      if (int rc = validate_kf(K2, h->max_cur, "neighbour", b, i, seen)) return rc;
       const gfs_tri_result& R = results[b][i];
       GFS_REQUIRE(Q.cur.n_kp == 0 || (R.match12 && R.exit && R.x3d && R.point_stereo), GFS_ERR_INVALID_ARG,
                   "gfs_create_new_map_points: problem %d neighbour %d has NULL result arrays", b, i);
@@ -481,20 +460,12 @@ int gfs_create_new_map_points(gfs_sbp* h, const gfs_tri_problem* problems, int B
   }
   if (n_slots == 0) return GFS_OK;
   // ---- stage: headers, the matrix offsets, then every key frame's arrays (all within the reserve: counts and sizes were checked)
-  uint8_t* hb = w->h_in.p;
-  size_t at = 0;
-  const size_t o_prob = at;
-  at += up256((size_t)B * sizeof(TriProb));
-  const size_t o_slot = at;
-  at += up256(n_slots * sizeof(TriSlot));
-  const size_t n_frames = n_slots + (size_t)B, o_frame = at;
-  at += up256(n_frames * sizeof(TriFrame));
-  const size_t o_pair = at;
-  at += up256(pair_off.size() * 4);
-  if (!pair_off.empty()) memcpy(hb + o_pair, pair_off.data(), pair_off.size() * 4);
-  TriProb* probs = reinterpret_cast<TriProb*>(hb + o_prob);
-  TriSlot* slots = reinterpret_cast<TriSlot*>(hb + o_slot);
-  TriFrame* frames = reinterpret_cast<TriFrame*>(hb + o_frame);
+  uint8_t* hb = w->in.h.p;
+  HeadLayout Y{(size_t)B, n_slots, n_slots + (size_t)B, pair_off.size()};
+  Y.pairs.put(hb, 0, pair_off.data(), pair_off.size());
+  TriProb* probs = Y.probs.at(hb);
+  TriSlot* slots = Y.slots.at(hb);
+  TriFrame* frames = Y.frames.at(hb);
   size_t slot = 0, frame = 0, out_at = 0;
   unsigned long long mat_at = 0;
   for (int b = 0; b < B; b++) {
@@ -510,7 +481,7 @@ int gfs_create_new_map_points(gfs_sbp* h, const gfs_tri_problem* problems, int B
     P.far_points = Q.far_points;
     P.th_far = Q.th_far_points;
     P.ratio_factor = Q.ratio_factor;
-    stage_kf(Q.cur, nullptr, nullptr, hb, at, frames[frame++]);
+    stage_kf(Q.cur, nullptr, nullptr, hb, Y.in, frames[frame++]);
     for (int i = 0; i < Q.n_neighbours; i++) {
       TriSlot& S = slots[slot];
       S.problem = b;
@@ -520,34 +491,35 @@ int gfs_create_new_map_points(gfs_sbp* h, const gfs_tri_problem* problems, int B
       S.out_at = (unsigned)out_at;
       S.mat_base = mat_at;
       out_at += gfs::align_up((size_t)Q.cur.n_kp, 64);
-      stage_kf(Q.neighbours[i].kf, Q.neighbours[i].ep, Q.neighbours[i].F12, hb, at, frames[frame++]);
+      stage_kf(Q.neighbours[i].kf, Q.neighbours[i].ep, Q.neighbours[i].F12, hb, Y.in, frames[frame++]);
       slot++;
     }
     mat_at += (unsigned long long)prob_pairs[b];
   }
+  const size_t at = Y.in.bytes();
   if (at > w->in_bytes || mat_at > w->mat_bytes) {  // (cannot happen: the reserve bounds every term above)
     gfs::set_error("gfs_create_new_map_points: internal: staged %zu of %zu bytes", at, w->in_bytes);
     return GFS_ERR_CAPACITY;
   }
-  const size_t q_exit = up256(out_elems * 4), q_stereo = q_exit + up256(out_elems), q_x3d = q_stereo + up256(out_elems);
-  const size_t out_bytes = q_x3d + up256(out_elems * 12);
+  const gfs::TriOutLayout Z{out_elems};
   if (out_elems > 0) {
-    hipStream_t s = c.stream;
-    uint8_t *di = w->d_in.p, *dq = w->d_out.p;
-    GFS_HIP(hipMemcpyAsync(di, hb, at, hipMemcpyHostToDevice, s));
-    const TriProb* dprob = reinterpret_cast<const TriProb*>(di + o_prob);
-    const TriSlot* dslot = reinterpret_cast<const TriSlot*>(di + o_slot);
-    const TriFrame* dframe = reinterpret_cast<const TriFrame*>(di + o_frame);
-    const int* dpair = reinterpret_cast<const int*>(di + o_pair);
+    hipStream_t s = h->stream;
+    const uint8_t* di = w->in.d.p;
+    uint8_t* dq = w->out.d.p;
+    if (int rc = w->in.upload(s, 0, at)) return rc;
+    const TriProb* dprob = Y.probs.at(di);
+    const TriSlot* dslot = Y.slots.at(di);
+    const TriFrame* dframe = Y.frames.at(di);
+    const int* dpair = Y.pairs.at(di);
     if (max_nodes1 > 0 && mat_at > 0)
-      GFS_LAUNCH("k_tri_candidates", k_tri_candidates, dim3(max_nodes1, (unsigned)n_slots), dim3(kCandThreads), 0, s, (const uint8_t*)di, dprob,
+      GFS_LAUNCH("k_tri_candidates", k_tri_candidates, dim3(max_nodes1, (unsigned)n_slots), dim3(kCandThreads), 0, s, di, dprob,
                  dslot, dframe, dpair, w->d_mat.p);
-    GFS_LAUNCH("k_tri_resolve", k_tri_resolve, dim3(B), dim3(kResThreads), 0, s, (const uint8_t*)di, dprob, dslot, dframe, dpair,
-               (const uint8_t*)w->d_mat.p, reinterpret_cast<int*>(dq), dq + q_exit, reinterpret_cast<float*>(dq + q_x3d), dq + q_stereo);
-    GFS_HIP(hipMemcpyAsync(w->h_out.p, dq, out_bytes, hipMemcpyDeviceToHost, s));
+    GFS_LAUNCH("k_tri_resolve", k_tri_resolve, dim3(B), dim3(kResThreads), 0, s, di, dprob, dslot, dframe, dpair,
+               (const uint8_t*)w->d_mat.p, Z.match.at(dq), Z.exit.at(dq), Z.x3d.at(dq), Z.stereo.at(dq));
+    if (int rc = w->out.download(s, 0, Z.out.bytes())) return rc;
     GFS_HIP(hipStreamSynchronize(s));  // the call's one synchronisation
   }
-  const uint8_t* ho = w->h_out.p;
+  const uint8_t* ho = w->out.h.p;
   slot = 0;
   for (int b = 0; b < B; b++) {
     const size_t n = (size_t)problems[b].cur.n_kp;
@@ -555,15 +527,13 @@ int gfs_create_new_map_points(gfs_sbp* h, const gfs_tri_problem* problems, int B
       gfs_tri_result& R = results[b][i];
       const size_t o = slots[slot].out_at;
       int nm = 0, ncr = 0;
-      if (n > 0) {
-        memcpy(R.match12, ho + o * 4, n * 4);
-        memcpy(R.exit, ho + q_exit + o, n);
-        memcpy(R.point_stereo, ho + q_stereo + o, n);
-        memcpy(R.x3d, ho + q_x3d + o * 12, n * 12);
-        for (size_t p = 0; p < n; p++) {
-          nm += R.match12[p] >= 0;
-          ncr += R.exit[p] == GFS_TRI_CREATED;
-        }
+      Z.match.get(R.match12, ho, o, n);
+      Z.exit.get(R.exit, ho, o, n);
+      Z.stereo.get(R.point_stereo, ho, o, n);
+      Z.x3d.get(R.x3d, ho, o, n);
+      for (size_t p = 0; p < n; p++) {
+        nm += R.match12[p] >= 0;
+        ncr += R.exit[p] == GFS_TRI_CREATED;
       }
       R.n_matches = nm;
       R.n_created = ncr;

@@ -3,7 +3,7 @@
 // action (Thirdparty/Sophus/sophus/so3.hpp:358-367), Pinhole::project (src/CameraModels/Pinhole.cpp:43-49), KeyFrame::IsInImage and
 // GetFeaturesInArea (src/KeyFrame.cc:848-850, 802-846) over a plain vector<vector<>> grid filled as Frame::AssignFeaturesToGrid
 // fills it (src/Frame.cc:734-761, 1073-1084), MapPoint::PredictScale (src/MapPoint.cc:549-563) calling the HOST's logf, and the
-// candidate loop.  The checker of gfs_fuse_search (geoflowslam_amd/csrc/sbp.hip) and of the host rule the adaptor replays with; it
+// candidate loop.  The checker of gfs_fuse_search (geoflowslam_amd/csrc/fuse.hip) and of the host rule the adaptor replays with; it
 // shares no code with either.  The tests build it with g++ -O2 -std=c++17 -ffp-contract=off.
 //
 // Float arithmetic, one rounding per operation, sums left to right.

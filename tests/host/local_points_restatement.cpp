@@ -3,7 +3,7 @@
 // src/CameraModels/Pinhole.cpp:43-49), MapPoint::PredictScale (src/MapPoint.cc:565-579) calling the HOST's logf, the far-points
 // filter of ORBmatcher::SearchByProjection (src/ORBmatcher.cc:53-58), then the search itself: oracle/sbp_oracle.cpp included
 // unchanged, gfso_search_by_projection_map on the compacted list.  The checker of gfs_search_local_points (geoflowslam_amd/csrc/
-// sbp.hip); the tests build it with g++ -O2 -std=c++17 -ffp-contract=off.
+// local_points.hip); the tests build it with g++ -O2 -std=c++17 -ffp-contract=off.
 //
 // Float arithmetic, one rounding per operation, sums left to right.  Two cases the reference leaves open
 // are decided there: a projection that is not finite after the image-bounds tests (0 / 0) puts the point out with (-1, -1) left

@@ -1,4 +1,4 @@
-"""gfs_fuse_search (k_fuse, geoflowslam_amd/csrc/sbp.hip) on the MI355X against the sequential CPU restatement
+"""gfs_fuse_search (k_fuse, geoflowslam_amd/csrc/fuse.hip) on the MI355X against the sequential CPU restatement
 (tests/host/fuse_restatement.cpp): bit equality of exit, best index, best distance and level, no tolerance."""
 import numpy as np
 import pytest

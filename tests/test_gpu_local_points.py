@@ -1,4 +1,4 @@
-"""gfs_search_local_points (geoflowslam_amd/csrc/sbp.hip: frustum cull, scale prediction, stable compaction, map search -- the
+"""gfs_search_local_points (geoflowslam_amd/csrc/local_points.hip: frustum cull, scale prediction, stable compaction, map search -- the
 second loop of Tracking::SearchLocalPoints, reference src/Tracking.cc:4312-4358, in one device call) against the sequential CPU
 restatement (tests/host/local_points_restatement.cpp), bit for bit: no tolerance appears anywhere."""
 import numpy as np

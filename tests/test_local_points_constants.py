@@ -70,13 +70,14 @@ def test_constants_match_reference():
     m = re.search(r"mp_view_cos\[l\] > ([0-9.]+) \? ([0-9.]+)f : ([0-9.]+)f;", orc)
     assert [float(v) for v in m.groups()] == [exp["radius_cos_threshold"], exp["radius_near"], exp["radius_far"]]
     # the HIP source
-    hip = open(os.path.join(ROOT, "geoflowslam_amd", "csrc", "sbp.hip")).read()
+    hip = open(os.path.join(ROOT, "geoflowslam_amd", "csrc", "local_points.hip")).read()
     assert float(re.search(r"kLpMinDistFactor = ([0-9.]+)f;", hip).group(1)) == exp["min_distance_factor"]
     assert float(re.search(r"kLpMaxDistFactor = ([0-9.]+)f;", hip).group(1)) == exp["max_distance_factor"]
     assert "dist < kLpMinDistFactor * min_dist[at] || dist > kLpMaxDistFactor * mx" in hip
     assert _ops(hip, "u", "v") == exp["bounds_tests"]
     assert re.search(r"if \(Pc\[2\] (\S+) 0\.0f\) break;", hip).group(1) == exp["depth_test"]
-    m = re.search(r"last_angle\[l\] > ([0-9.]+) \? ([0-9.]+)f : ([0-9.]+)f;", hip)
+    sbp = open(os.path.join(ROOT, "geoflowslam_amd", "csrc", "sbp.hip")).read()  # the search radius is k_sbp's
+    m = re.search(r"last_angle\[l\] > ([0-9.]+) \? ([0-9.]+)f : ([0-9.]+)f;", sbp)
     assert [float(v) for v in m.groups()] == [exp["radius_cos_threshold"], exp["radius_near"], exp["radius_far"]]
     # what the adaptor passes for the two arguments Tracking fixes
     ada = open(os.path.join(ROOT, "geoflowslam_amd", "host", "gfs_adaptors.hpp")).read()

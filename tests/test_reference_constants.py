@@ -138,7 +138,7 @@ def _parse_matcher():
 
 
 def test_matcher_thresholds():
-    """ORBmatcher::TH_HIGH / TH_LOW / HISTO_LENGTH, src/ORBmatcher.cc:36-38 -> oracle/sbp_oracle.cpp, csrc/sbp.hip."""
+    """ORBmatcher::TH_HIGH / TH_LOW / HISTO_LENGTH, src/ORBmatcher.cc:36-38 -> oracle/sbp_oracle.cpp, csrc/sbp.hip; the frame grid -> csrc/sbp_dev.hpp."""
     ref = _recorded("matcher")
     for path in ("oracle/sbp_oracle.cpp", "geoflowslam_amd/csrc/sbp.hip"):
         t = _ours(path)
@@ -148,7 +148,7 @@ def test_matcher_thresholds():
     rows, cols = ref["FRAME_GRID_ROWS"], ref["FRAME_GRID_COLS"]
     t = _ours("oracle/sbp_oracle.cpp")
     assert _one(r"kGridCols\s*=\s*(\d+)", t, int) == cols and _one(r"kGridRows\s*=\s*(\d+)", t, int) == rows
-    assert re.search(rf"\b{cols}\b", _ours("geoflowslam_amd/csrc/sbp.hip")) and re.search(rf"\b{rows}\b", _ours("geoflowslam_amd/csrc/sbp.hip"))
+    assert re.search(rf"\b{cols}\b", _ours("geoflowslam_amd/csrc/sbp_dev.hpp")) and re.search(rf"\b{rows}\b", _ours("geoflowslam_amd/csrc/sbp_dev.hpp"))
 
 
 # ---------------------------------------------------------------------------------------------- Optimizer
