@@ -72,8 +72,8 @@ struct GicpParams {
   double inv_leaf, cell, inv_cell, max_dist_sq, rot_eps, trans_eps;
   int max_iterations, k_neighbors;
   // optional [8]: the diagnostics counter block (GFS_GICP_TILE_STATS=1, read by gfs_gicp_tile_stats).  Written by the variant builds
-  // only: -DGFS_KNN_UTIL (k_knn_cov: lanes at work / steps of its two scans in slots 0 .. 3, queries / waves in 4, 5, own-row candidates
-  // in 6) and -DGFS_LIN_UTIL (the linearisation's search: lanes / rounds of neighbouring rows in 2, 3, lanes / steps of the walk in 4,
+  // only: -DGFS_KNN_UTIL (k_knn_cov: lanes at work / steps of the own-row walk in slots 0, 1, of the loop over the neighbouring rows in
+  // 2, 3, queries / waves in 4, 5, points of the own rows in 6) and -DGFS_LIN_UTIL (the linearisation's search: lanes / rounds of neighbouring rows in 2, 3, lanes / steps of the walk in 4,
   // 5, searches / waves in 6, 7)
   unsigned* tile_stats;
   int nn_rings;  // ceil(max_corr / cell): rings of cells a 1-NN probe may need to certify "nothing within max_corr"
@@ -1222,14 +1222,6 @@ __device__ __forceinline__ double knn_key(const double4& t, const double4& q, in
   const double ddx = t.x - q.x, ddy = t.y - q.y, ddz = t.z - q.z;
   return on ? TopKey11::key(ddx * ddx + ddy * ddy + ddz * ddz, j) : TopKey11::kNone;
 }
-// the run [j0, j1) of candidate points into the key list, four loads in flight
-__device__ __forceinline__ void knn_scan_run_keys(const double4* __restrict__ p, const double4& q, int j0, int j1, TopKey11& loc) {
-  for (int j = j0; j < j1; j += 4) {
-    const double4 t0 = ld_pt(p, j), t1 = ld_pt(p, min(j + 1, j1 - 1)), t2 = ld_pt(p, min(j + 2, j1 - 1)), t3 = ld_pt(p, min(j + 3, j1 - 1));
-    loc.push4(knn_key(t0, q, j, true), knn_key(t1, q, j + 1, j + 1 < j1), knn_key(t2, q, j + 2, j + 2 < j1),
-              knn_key(t3, q, j + 3, j + 3 < j1));
-  }
-}
 #ifdef GFS_KNN_UTIL
 // variant builds (tools/probes/knn_util_probe.py): lanes at work summed over the steps of a scan, and the steps (per wave)
 __device__ __forceinline__ void knn_util_step(unsigned* util, int slot) {
@@ -1244,54 +1236,128 @@ __device__ __forceinline__ void knn_util_step(unsigned* util, int slot) {
 #else
 #define GFS_KNN_UTIL_STEP(util, slot)
 #endif
-// The query's OWN row of cells [lo, hi) -- it holds the query itself, at index i -- walked from the query outwards, two candidates a
-// side per step (round 6).  The row is ordered by slices of 1 / kFine of a cell along x (the cell sort key), so everything beyond
-// the outermost point seen on a side has an x of at least that point's minus one slice: the side stops once that gap alone exceeds
-// the k-th distance so far.  A depth-camera cloud puts 25 points into a cell its surface crosses, the k-th neighbour is ~4 cm away
-// and the row 30 cm long: the walk takes a third of the row.  The keys are (distance | index), so the list does not depend on the
-// order of the visits, and what is left out is farther than the k-th candidate at that time (as with the neighbouring rows below).
-__device__ __forceinline__ void knn_walk_own_row(const double4* __restrict__ p, const double4& q, int i, int lo, int hi, double slack,
-                                                 int want, TopKey11& loc, unsigned* util = nullptr) {
-  int r = i, l = i - 1;
-  bool ra = r < hi, la = l >= lo;
-  const int kw_at = max(want - 1, 0);
-  while (ra || la) {
-    GFS_KNN_UTIL_STEP(util, 0);
-    const int j0 = min(r, hi - 1), j1 = max(l, lo), j2 = min(r + 1, hi - 1), j3 = max(l - 1, lo);
-    const bool on2 = ra && r + 1 < hi, on3 = la && l - 1 >= lo;
+// One row of cells of the 27-cell cube, walked outwards in both directions from `start` (k_knn_cov).  The strip [lo, hi) is ordered by
+// slices of 1 / kFine of a cell along x (the cell sort key), so everything beyond the outermost point seen on a side has an x of at
+// least that point's minus one slice (`slack`): the side stops once that gap and the row's own distance in y and z (row2) together
+// exceed B, the upper end of the k-th key so far -- strictly, so that what is left out can neither belong to the k nearest nor share
+// the k-th key's high bits (the tie test of the certification sees the same answer).  A depth-camera cloud puts 25 points into a cell
+// its surface crosses, the k-th neighbour is ~4 cm away and a row 30 cm long: the walk takes a third of the own row and about half
+// of a neighbouring one.  The keys are (distance | index), so the list does not depend on the order of the visits, and any `start`
+// is correct: the own row starts at the query itself, a neighbouring row where the query's x falls among the points of its middle
+// cell (as nn_search27 does).
+struct KnnRowWalk {
+  int lo, hi, r, l;  // the strip; the next candidate to the right and to the left
+  bool ra, la;       // which sides still walk
+  double row2;
+  __device__ __forceinline__ void stop() { ra = la = false; }
+  __device__ __forceinline__ bool live() const { return ra || la; }
+  __device__ __forceinline__ void begin(int lo_, int hi_, int start, double row2_) {
+    lo = lo_;
+    hi = hi_;
+    r = start;
+    l = start - 1;
+    ra = r < hi;
+    la = l >= lo;
+    row2 = row2_;
+  }
+  // One step (live() holds): four candidates into the list, two a side -- or all four on the one side that still walks, whose stop
+  // test then looks at the outermost of the four.  kFull: the cloud holds at least ten points, the k-th key is k[9].
+  template <bool kFull>
+  __device__ __forceinline__ void step(const double4* __restrict__ p, const double4& q, double slack, int kw_at, TopKey11& loc, double& B) {
+    const bool both = ra && la;
+    const int a = ra ? r : l, d = ra ? 1 : -1;
+    const int i1 = both ? l : a + d, i2 = both ? r + 1 : a + 2 * d, i3 = both ? l - 1 : a + 3 * d;
+    const unsigned n = (unsigned)(hi - lo);
+    // clamped into the strip: a clamped index is just another point of the strip, switched off
+    const int j0 = a, j1 = min(max(i1, lo), hi - 1), j2 = min(max(i2, lo), hi - 1), j3 = min(max(i3, lo), hi - 1);
     const double4 t0 = ld_pt(p, j0), t1 = ld_pt(p, j1), t2 = ld_pt(p, j2), t3 = ld_pt(p, j3);
-    loc.push4(knn_key(t0, q, j0, ra), knn_key(t1, q, j1, la), knn_key(t2, q, j2, on2), knn_key(t3, q, j3, on3));
-    const double kw = loc.at(kw_at);
-    const double B = kw < TopKey11::kNone ? TopKey11::upper(kw) : TopKey11::kNone;
-    if (ra) {
-      r += 2;
-      const double g = t2.x - slack - q.x;  // (t2 = t0 when the row ends at r: nothing is ahead then anyway)
-      ra = r < hi && !(g > 0.0 && g * g > B);
+    loc.push4(knn_key(t0, q, j0, true), knn_key(t1, q, j1, (unsigned)(i1 - lo) < n), knn_key(t2, q, j2, (unsigned)(i2 - lo) < n),
+              knn_key(t3, q, j3, (unsigned)(i3 - lo) < n));
+    B = TopKey11::upper(kFull ? loc.k[9] : loc.at(kw_at));  // (upper(kNone) = kNone: no bound yet, nothing stops)
+    const int adv = both ? 2 : 4;
+    if (ra) {  // outermost on the right: t2 of two, t3 of four (the row's last point when clamped: nothing is ahead then anyway)
+      r += adv;
+      const double g = (both ? t2.x : t3.x) - slack - q.x;
+      ra = r < hi && !(g > 0.0 && g * g + row2 > B);
     }
-    if (la) {
-      l -= 2;
+    if (la) {  // outermost on the left: t3 either way
+      l -= adv;
       const double g = q.x - t3.x - slack;
-      la = l >= lo && !(g > 0.0 && g * g > B);
+      la = l >= lo && !(g > 0.0 && g * g + row2 > B);
     }
   }
-}
-// the same over up to four runs (begin, length) concatenated into one lane-private sequence
-__device__ __forceinline__ void knn_scan_runs4_keys(const double4* __restrict__ p, const double4& q, int b0, int l0, int b1, int l1,
-                                                    int b2, int l2, int b3, int l3, TopKey11& loc, unsigned* util = nullptr) {
-  const int c1 = l0, c2 = c1 + l1, c3 = c2 + l2, total = c3 + l3;
-  const int o0 = b0, o1 = b1 - c1, o2 = b2 - c2, o3 = b3 - c3;
-  for (int v = 0; v < total; v += 4) {
-    GFS_KNN_UTIL_STEP(util, 2);
-    int j[4];
-#pragma unroll
-    for (int u = 0; u < 4; u++) {
-      const int vv = min(v + u, total - 1);
-      j[u] = vv + (vv < c1 ? o0 : vv < c2 ? o1 : vv < c3 ? o2 : o3);
+};
+
+// A neighbouring row of a query as k_knn_cov keeps it between the look-up and the walk: the strip and the start packed into one word
+// (lo | length << 20 | (start - lo) << 41: clouds hold at most 2^20 points) and the row's squared distance in y and z.  Eight a lane,
+// in LDS: the rows are taken in an order only known at run time, and a register array indexed at run time would live in scratch.
+struct KnnRowSlot {
+  u64 strip;
+  double row2;
+};
+constexpr int kKnnThreads = 128;
+
+// The 27-cell cube of query i, branch and bound per lane like the 1-NN search of k_gicp_linearize: the own row first, from the query
+// outwards; then the three cells of every neighbouring row within the k-th distance so far are looked up (row by row with the row's
+// place in the cube a compile-time constant, as before), trimmed by whole cells and kept in `rows` (this lane's column:
+// rows[t8 * kKnnThreads]); then ONE loop over those rows.  A lane takes its rows one at a time, faces before diagonals (the nearer rows tighten the bound for the
+// farther ones), each re-tested against the bound of that moment, and moves on to its next row inside the same loop: a wave
+// iterates max-over-lanes of a lane's steps summed over its rows (a lane has 1 - 2 surviving rows on a depth-camera cloud), not the
+// sum over rounds of the max.  What is skipped is strictly farther than the upper end of the k-th key at that time.
+template <bool kFull>
+__device__ __forceinline__ void knn_search_cube(const double4* __restrict__ p, const double4& q, int i, const int* __restrict__ gi,
+                                                const unsigned* __restrict__ G, const u64* __restrict__ uc, const unsigned* __restrict__ ub,
+                                                int nu, int cx, int cy, int cz, double ux, double uy, double uz, const GicpParams& prm,
+                                                int want, KnnRowSlot* __restrict__ rows, TopKey11& best) {
+  const double slack = prm.cell * (1.0 / kFine + 1e-9);
+  const int kw_at = max(want - 1, 0);
+  double B = TopKey11::kNone;  // upper end of the k-th key so far, or "none yet"
+  KnnRowWalk w;
+  {
+    int j0, j1;
+    row_range(gi, G, uc, ub, nu, cx - 1, cx + 1, cy, cz, &j0, &j1);
+    w.begin(j0, j1, min(max(i, j0), j1), 0.0);  // (the query is a point of its own cell: j0 <= i < j1)
+    while (w.live()) {
+      GFS_KNN_UTIL_STEP(prm.tile_stats, 0);
+      w.template step<kFull>(p, q, slack, kw_at, best, B);
     }
-    const int j0 = j[0], j1 = j[1], j2 = j[2], j3 = j[3];
-    const double4 t0 = ld_pt(p, j0), t1 = ld_pt(p, j1), t2 = ld_pt(p, j2), t3 = ld_pt(p, j3);
-    loc.push4(knn_key(t0, q, j0, true), knn_key(t1, q, j1, v + 1 < total), knn_key(t2, q, j2, v + 2 < total),
-              knn_key(t3, q, j3, v + 3 < total));
+  }
+  // lower bounds of the distance to the neighbouring cells and rows (a hair conservative: 1e-9 cells)
+  const double lx0 = fmax(ux - 1e-9, 0.0) * prm.cell, lx2 = fmax(1.0 - ux - 1e-9, 0.0) * prm.cell;
+  const double ly[3] = {fmax(uy - 1e-9, 0.0) * prm.cell, 0.0, fmax(1.0 - uy - 1e-9, 0.0) * prm.cell};
+  const double lz[3] = {fmax(uz - 1e-9, 0.0) * prm.cell, 0.0, fmax(1.0 - uz - 1e-9, 0.0) * prm.cell};
+  constexpr int row_of[8] = {1, 3, 5, 7, 0, 2, 6, 8};  // (dy + 1) + 3 (dz + 1): faces, then diagonals
+  unsigned need = 0;
+#pragma unroll
+  for (int t8 = 0; t8 < 8; t8++) {
+    const int dy = row_of[t8] % 3, dz = row_of[t8] / 3;
+    const double row2 = ly[dy] * ly[dy] + lz[dz] * lz[dz];
+    if (row2 <= B) {
+      int e[4];
+      row_cells3(gi, G, uc, ub, nu, cx, cy + dy - 1, cz + dz - 1, e);
+      const int lo = row2 + lx0 * lx0 <= B ? e[0] : e[1], hi = row2 + lx2 * lx2 <= B ? e[3] : e[2];
+      if (hi > lo) {
+        const int n1 = e[2] - e[1];  // the walk starts where the query's x would fall among the points of the row's middle cell
+        const int start = e[1] + min(max((int)(ux * (double)n1), 0), n1);
+        rows[t8 * kKnnThreads] = KnnRowSlot{(u64)(unsigned)lo | (u64)(unsigned)(hi - lo) << 20 | (u64)(unsigned)(start - lo) << 41, row2};
+        need |= 1u << t8;
+      }
+    }
+  }
+  for (;;) {
+    while (!w.live() && need != 0) {  // this lane's next row that is still within the bound
+      const KnnRowSlot s = rows[(__ffs(need) - 1) * kKnnThreads];
+      need &= need - 1;
+      if (s.row2 <= B) {
+        const int lo = (int)((unsigned)s.strip & 0xfffffu), len = (int)((unsigned)(s.strip >> 20) & 0x1fffffu);
+        w.begin(lo, lo + len, lo + (int)(s.strip >> 41), s.row2);
+      }
+    }
+    if (!__any(w.live())) break;
+    if (w.live()) {
+      GFS_KNN_UTIL_STEP(prm.tile_stats, 2);
+      w.template step<kFull>(p, q, slack, kw_at, best, B);
+    }
   }
 }
 
@@ -1402,7 +1468,7 @@ __device__ __forceinline__ void knn_scan_runs4(const double4* __restrict__ p, co
   }
 }
 
-__global__ __launch_bounds__(128) void k_knn_cov(const double4* __restrict__ pts, const u64* __restrict__ ucell,
+__global__ __launch_bounds__(kKnnThreads) void k_knn_cov(const double4* __restrict__ pts, const u64* __restrict__ ucell,
                                                  const unsigned* __restrict__ ubegin, const int* __restrict__ n_ucell,
                                                  const int* __restrict__ m_counts, const int* __restrict__ bbox,
                                                  const unsigned* __restrict__ grid, const int* __restrict__ ginfo,
@@ -1414,7 +1480,7 @@ __global__ __launch_bounds__(128) void k_knn_cov(const double4* __restrict__ pts
   if (prm.only >= 0 && which != prm.only) return;
   const int c = 2 * pair + which;
   const int m = m_counts[c];
-  const int i = chunk * 128 + threadIdx.x;
+  const int i = chunk * kKnnThreads + threadIdx.x;
   if (i >= m) return;
   const unsigned* G = grid + (size_t)c * (kGridCap + 1);
   const int* gi = ginfo + 8 * c;
@@ -1428,12 +1494,7 @@ __global__ __launch_bounds__(128) void k_knn_cov(const double4* __restrict__ pts
   TopKey11 best;
   const int kk = min(prm.k_neighbors, 10);
   const int want = min(kk, m);
-  // The 27-cell cube, branch-and-bound per lane like the 1-NN search of k_gicp_linearize: the own row (3 cells) is scanned
-  // first; once k candidates are known, a cell whose box is farther than the k-th distance so far cannot contribute and is
-  // skipped (same neighbours, same order of visits, same bound handed to the deferred passes).  The four rows sharing a face
-  // with the own row come next, then the four diagonal ones with the bound those left; each lane walks only ITS surviving
-  // cells as one concatenated sequence, four loads in flight (a wave iterates max-over-lanes(candidates) / 4 times: ~65 instead
-  // of ~105 candidates on a depth-camera cloud).
+  // the 27-cell cube (knn_search_cube); `want` is the same for the whole workgroup (one cloud)
   bool certified = false;
   double kth_for_deferred = TopKey11::kNone;
   {
@@ -1441,47 +1502,11 @@ __global__ __launch_bounds__(128) void k_knn_cov(const double4* __restrict__ pts
     const double cell2 = prm.cell * prm.cell;
     const double ux = q.x * prm.inv_cell - (double)(cx - kCoordOffset), uy = q.y * prm.inv_cell - (double)(cy - kCoordOffset),
                  uz = q.z * prm.inv_cell - (double)(cz - kCoordOffset);
-    const double lx0 = fmax(ux - 1e-9, 0.0) * prm.cell, lx2 = fmax(1.0 - ux - 1e-9, 0.0) * prm.cell;
-    const double ly[3] = {fmax(uy - 1e-9, 0.0) * prm.cell, 0.0, fmax(1.0 - uy - 1e-9, 0.0) * prm.cell};
-    const double lz[3] = {fmax(uz - 1e-9, 0.0) * prm.cell, 0.0, fmax(1.0 - uz - 1e-9, 0.0) * prm.cell};
-    {
-      int j0, j1;
-      row_range(gi, G, uc, ub, nu, cx - 1, cx + 1, cy, cz, &j0, &j1);
-#ifdef GFS_KNN_OWN_ROW_SCAN
-      knn_scan_run_keys(p, q, j0, j1, best);  // (rounds 3 - 5: the whole row)
-#else
-      if (i >= j0 && i < j1)  // (always: the query is a point of its own cell)
-        knn_walk_own_row(p, q, i, j0, j1, prm.cell * (1.0 / kFine + 1e-9), want, best, prm.tile_stats);
-      else
-        knn_scan_run_keys(p, q, j0, j1, best);
-#endif
-    }
-    // k-th distance so far (its upper end), or "none yet"
-    auto kth_bound = [&]() {
-      const double kw = best.at(max(want - 1, 0));
-      return kw < TopKey11::kNone ? TopKey11::upper(kw) : TopKey11::kNone;
-    };
-    constexpr int rows[2][4] = {{1, 3, 5, 7}, {0, 2, 6, 8}};  // (dy + 1) + 3 (dz + 1): faces, then diagonals
-#pragma unroll
-    for (int round = 0; round < 2; round++) {
-      const double B = kth_bound();
-      int rb[4], rl[4];
-#pragma unroll
-      for (int u = 0; u < 4; u++) {
-        const int t9 = rows[round][u], dy = t9 % 3, dz = t9 / 3;
-        const double row2 = ly[dy] * ly[dy] + lz[dz] * lz[dz];
-        rb[u] = 0;
-        rl[u] = 0;
-        if (row2 <= B) {
-          int e[4];
-          row_cells3(gi, G, uc, ub, nu, cx, cy + dy - 1, cz + dz - 1, e);
-          const int b0 = row2 + lx0 * lx0 <= B ? e[0] : e[1], e0 = row2 + lx2 * lx2 <= B ? e[3] : e[2];
-          rb[u] = b0;
-          rl[u] = e0 - b0;
-        }
-      }
-      knn_scan_runs4_keys(p, q, rb[0], rl[0], rb[1], rl[1], rb[2], rl[2], rb[3], rl[3], best, prm.tile_stats);
-    }
+    __shared__ KnnRowSlot s_rows[8 * kKnnThreads];  // (a column a lane: no lane reads another's, no barrier)
+    if (want == 10)
+      knn_search_cube<true>(p, q, i, gi, G, uc, ub, nu, cx, cy, cz, ux, uy, uz, prm, want, s_rows + threadIdx.x, best);
+    else
+      knn_search_cube<false>(p, q, i, gi, G, uc, ub, nu, cx, cy, cz, ux, uy, uz, prm, want, s_rows + threadIdx.x, best);
 #ifdef GFS_KNN_UTIL
     if (prm.tile_stats) {  // queries (lanes) and waves; the candidates of the own row as a whole
       GFS_KNN_UTIL_STEP(prm.tile_stats, 4);
@@ -3347,8 +3372,8 @@ static int gicp_attempt(gfs_gicp* h, const void* dev_target, const void* dev_nt,
              prm.only);
   GFS_LAUNCH("k_grid_fill", k_grid_fill, dim3(kGridFillParts, C2), dim3(256), 0, s, h->d_ucell.p, h->d_ubegin.p, h->d_nucell.p, h->d_m.p,
              h->d_bbox.p, P, h->d_grid.p, h->d_ginfo.p, h->d_far2.p, prm.only);
-  const int knn_chunks = gfs::div_up(npts, 128);
-  GFS_LAUNCH("k_knn_cov", k_knn_cov, dim3(xcd_grid(knn_chunks, B, 2)), dim3(128), 0, s, h->d_pts.p, h->d_ucell.p,
+  const int knn_chunks = gfs::div_up(npts, kKnnThreads);
+  GFS_LAUNCH("k_knn_cov", k_knn_cov, dim3(xcd_grid(knn_chunks, B, 2)), dim3(kKnnThreads), 0, s, h->d_pts.p, h->d_ucell.p,
              h->d_ubegin.p, h->d_nucell.p, h->d_m.p, h->d_bbox.p, h->d_grid.p, h->d_ginfo.p, h->d_ginfo.p, h->d_hard.p,
              h->d_hard_d.p, knn_chunks, B, P, prm, h->d_cov6.p);
   const int far_chunks = std::max(1, std::min(32, knn_chunks));  // grid-stride over the deferred lists

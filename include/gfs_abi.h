@@ -212,7 +212,7 @@ int gfs_gicp_align_next_batch_device(gfs_gicp* h, const void* dev_source, const 
 int gfs_gicp_fetch_preprocessed(gfs_gicp* h, int b, int which, double* pts, double* covs, int cap, int* m);
 /* Diagnostics: the handle's counter block of eight words since the last reset.  The library as built writes none of them; the
  * variant builds do (tools/variant.sh): -DGFS_KNN_UTIL counts in k_knn_cov out8[0] / [1] lanes at work / steps of the own-row walk,
- * [2] / [3] the same of the neighbouring rows' scan, [4] / [5] queries / waves, [6] candidates of the own rows
+ * [2] / [3] the same of the one loop over a lane's neighbouring rows, [4] / [5] queries / waves, [6] points of the own rows
  * (tools/probes/knn_util_probe.py); -DGFS_LIN_UTIL counts in the linearisation's 1-NN search [2] / [3] lanes / rounds of neighbouring
  * rows, [4] / [5] lanes / steps of the walk, [6] / [7] searches / waves (tools/probes/lin_util_probe.py).  Counted only by handles
  * created with GFS_GICP_TILE_STATS=1 in the environment (atomics of every wave on a few addresses are not free). */

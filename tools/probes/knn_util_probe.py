@@ -1,6 +1,7 @@
 """Variant build -DGFS_KNN_UTIL (tools/variant.sh build knnutil gicp -DGFS_KNN_UTIL): what the waves of k_knn_cov's first pass do.
 slots of gfs_gicp_tile_stats: [0] lanes at work summed over the steps of the own-row walk, [1] those steps (per wave); [2], [3] the same
-for the two scans of the neighbouring rows; [4] queries, [5] waves; [6] points in the queries' own rows (what a full scan would visit)."""
+for the one loop over a lane's neighbouring rows (each walked outwards from where the query's x falls); [4] queries, [5] waves; [6] points
+in the queries' own rows (what a full scan would visit)."""
 import os, sys; sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 os.environ['GFS_GICP_TILE_STATS'] = '1'
 import numpy as np

@@ -12,7 +12,8 @@ if [ "$mode" = build ]; then
   cd $R/geoflowslam_amd/csrc
   /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wno-unused-function -Wno-unused-result -mllvm -amdgpu-kernarg-preload-count=16 -ffp-contract=off "$@" -c $unit.hip -o /tmp/${unit}_$name.o || exit 1
   objs=""
-  for o in gfs_common match orb gicp lba frame pose sbp gms klt fmat orb_host; do
+  for f in *.o; do  # every object of the product library (built by make), the unit's replaced
+    o=${f%.o}
     if [ $o = $unit ]; then objs="$objs /tmp/${unit}_$name.o"; else objs="$objs $o.o"; fi
   done
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o ../variants/$name.so $objs
