@@ -21,6 +21,7 @@
 #include <memory>
 #include <type_traits>
 
+#include "eig3_direct.hpp"
 #include "gfs_common.hpp"
 #include "glibc_math.hpp"
 #include "voxel_qsort.hpp"
@@ -962,114 +963,6 @@ __device__ __forceinline__ bool xcd_pair_map(int nchunks, int npairs, int per_pa
 inline int xcd_grid(int nchunks, int npairs, int per_pair) { return ((npairs + 7) / 8) * 8 * per_pair * nchunks; }
 
 // ------------------------------------------------------------------------------------------------
-// Eigen 3.4 SelfAdjointEigenSolver<Matrix3d>::computeDirect (closed form) — same formulas as the oracle.
-// m: symmetric 3x3 as (xx, xy, xz, yy, yz, zz).  V column-major 3x3 (columns = eigenvectors, ascending).
-// ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void cross3(const double* a, const double* b, double* c) {
-  c[0] = a[1] * b[2] - a[2] * b[1];
-  c[1] = a[2] * b[0] - a[0] * b[2];
-  c[2] = a[0] * b[1] - a[1] * b[0];
-}
-__device__ __forceinline__ double sqn3(const double* a) { return a[0] * a[0] + a[1] * a[1] + a[2] * a[2]; }
-
-__device__ void extract_kernel(const double* s /*9 col-major*/, double* res, double* rep) {
-  int i0 = 0;
-  double best = fabs(s[0]);
-  if (fabs(s[4]) > best) {
-    best = fabs(s[4]);
-    i0 = 1;
-  }
-  if (fabs(s[8]) > best) i0 = 2;
-  const int j1 = (i0 + 1) % 3, j2 = (i0 + 2) % 3;
-  rep[0] = s[3 * i0];
-  rep[1] = s[3 * i0 + 1];
-  rep[2] = s[3 * i0 + 2];
-  double c0[3], c1[3];
-  cross3(rep, s + 3 * j1, c0);
-  cross3(rep, s + 3 * j2, c1);
-  const double n0 = sqn3(c0), n1 = sqn3(c1);
-  if (n0 > n1) {
-    const double d = sqrt(n0);
-    res[0] = c0[0] / d;
-    res[1] = c0[1] / d;
-    res[2] = c0[2] / d;
-  } else {
-    const double d = sqrt(n1);
-    res[0] = c1[0] / d;
-    res[1] = c1[1] / d;
-    res[2] = c1[2] / d;
-  }
-}
-
-__device__ void eig3_direct(const double* cov6, double* V) {
-  const double shift = (cov6[0] + cov6[3] + cov6[5]) / 3.0;
-  double s[9] = {cov6[0] - shift, cov6[1], cov6[2], cov6[1], cov6[3] - shift, cov6[4], cov6[2], cov6[4], cov6[5] - shift};
-  double scale = 0;
-  for (int i = 0; i < 9; i++) scale = fmax(scale, fabs(s[i]));
-  if (scale > 0)
-    for (int i = 0; i < 9; i++) s[i] /= scale;
-  double ev[3];
-  {
-    const double s_inv3 = 1.0 / 3.0, s_sqrt3 = sqrt(3.0);
-    const double c0 = s[0] * s[4] * s[8] + 2.0 * s[1] * s[2] * s[5] - s[0] * s[5] * s[5] - s[4] * s[2] * s[2] - s[8] * s[1] * s[1];
-    const double c1 = s[0] * s[4] - s[1] * s[1] + s[0] * s[8] - s[2] * s[2] + s[4] * s[8] - s[5] * s[5];
-    const double c2 = s[0] + s[4] + s[8];
-    const double c2_over_3 = c2 * s_inv3;
-    double a_over_3 = (c2 * c2_over_3 - c1) * s_inv3;
-    a_over_3 = fmax(a_over_3, 0.0);
-    const double half_b = 0.5 * (c0 + c2_over_3 * (2.0 * c2_over_3 * c2_over_3 - c1));
-    double q = a_over_3 * a_over_3 * a_over_3 - half_b * half_b;
-    q = fmax(q, 0.0);
-    const double rho = sqrt(a_over_3);
-    const double theta = atan2(sqrt(q), half_b) * s_inv3;
-    const double cos_theta = gfs_glibc::cos(theta), sin_theta = gfs_glibc::sin(theta);
-    ev[0] = c2_over_3 - rho * (cos_theta + s_sqrt3 * sin_theta);
-    ev[1] = c2_over_3 - rho * (cos_theta - s_sqrt3 * sin_theta);
-    ev[2] = c2_over_3 + 2.0 * rho * cos_theta;
-  }
-  const double eps = 2.220446049250313e-16;
-  if ((ev[2] - ev[0]) <= eps) {
-    for (int i = 0; i < 9; i++) V[i] = (i % 4 == 0) ? 1.0 : 0.0;
-    return;
-  }
-  double d0 = ev[2] - ev[1];
-  const double d1 = ev[1] - ev[0];
-  int k = 0, l = 2;
-  if (d0 > d1) {  // Eigen: swap(k, l); d0 = d1
-    k = 2;
-    l = 0;
-    d0 = d1;
-  }
-  double tmp[9], colk[3], coll[3];
-  for (int i = 0; i < 9; i++) tmp[i] = s[i];
-  tmp[0] -= ev[k];
-  tmp[4] -= ev[k];
-  tmp[8] -= ev[k];
-  extract_kernel(tmp, colk, coll);
-  if (d0 <= 2 * eps * d1) {
-    const double dot = colk[0] * coll[0] + colk[1] * coll[1] + colk[2] * coll[2];
-    for (int i = 0; i < 3; i++) coll[i] -= dot * coll[i];
-    const double nn = sqrt(sqn3(coll));
-    for (int i = 0; i < 3; i++) coll[i] /= nn;
-  } else {
-    for (int i = 0; i < 9; i++) tmp[i] = s[i];
-    tmp[0] -= ev[l];
-    tmp[4] -= ev[l];
-    tmp[8] -= ev[l];
-    double dummy[3];
-    extract_kernel(tmp, coll, dummy);
-  }
-  for (int i = 0; i < 3; i++) {
-    V[3 * k + i] = colk[i];
-    V[3 * l + i] = coll[i];
-  }
-  double c1v[3];
-  cross3(V + 6, V, c1v);
-  const double nn = sqrt(sqn3(c1v));
-  for (int i = 0; i < 3; i++) V[3 + i] = c1v[i] / nn;
-}
-
-// ------------------------------------------------------------------------------------------------
 // k_knn_cov: one thread per down-sampled point: exact 10-NN in its own cloud (the query itself included,
 // util/normal_estimation.hpp:69) through ring-expanding cell probes, 3x3 covariance, closed-form
 // eigen-decomposition, cov := V diag(1e-3, 1, 1) V^T.  Stored as 6 doubles (xx, xy, xz, yy, yz, zz).
@@ -1400,7 +1293,7 @@ __device__ __forceinline__ void knn_write_cov(const TopK<10>& best, int kk, cons
   cv[4] = (sc[4] - mean[2] * sp[1]) / dn;  // (2,1)
   cv[5] = (sc[5] - mean[2] * sp[2]) / dn;
   double V[9];
-  eig3_direct(cv, V);
+  gfs_eig3::eig3_direct(cv, V);  // closed form, csrc/eig3_direct.hpp
   const double dv[3] = {1e-3, 1.0, 1.0};
   int o = 0;
   for (int r = 0; r < 3; r++)
