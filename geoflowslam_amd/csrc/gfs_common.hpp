@@ -110,6 +110,28 @@ __device__ __forceinline__ int wave_max_i32(int v) {
   for (int o = 32; o >= 1; o >>= 1) v = max(v, __shfl_xor(v, o));
   return v;
 }
+// block-wide exclusive scan of one int per thread (1024 threads, all of them call it: two barriers); returns the exclusive prefix,
+// the total in *total.  s_wave: 16 ints of the workgroup's LDS
+__device__ __forceinline__ int block_scan_1024(int v, int* s_wave, int* total) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int incl = v;
+#pragma unroll
+  for (int ofs = 1; ofs < 64; ofs <<= 1) {
+    const int t = __shfl_up(incl, ofs, 64);
+    if (lane >= ofs) incl += t;
+  }
+  __syncthreads();
+  if (lane == 63) s_wave[wave] = incl;
+  __syncthreads();
+  int base = 0, tot = 0;
+  for (int w = 0; w < 16; w++) {
+    const int t = s_wave[w];
+    if (w < wave) base += t;
+    tot += t;
+  }
+  *total = tot;
+  return base + incl - v;
+}
 // Walks p[i0], p[i0 + stride], ... (index < n) with U loads in flight and hands every element to f(index, value) in index order.
 // A plain grid-stride loop over global memory is compiled into load - wait - use per trip: with the 17-odd trips a thread of a
 // one-workgroup-per-cloud kernel makes, that is 17 dependent round trips of ~1.5 us where two or three would do.

@@ -24,6 +24,7 @@
 #include "eig3_direct.hpp"
 #include "gfs_common.hpp"
 #include "glibc_math.hpp"
+#include "key_box.hpp"
 #include "voxel_qsort.hpp"
 #include "wave_reduce.hpp"
 
@@ -159,61 +160,19 @@ __global__ __launch_bounds__(1024) void k_radix_sort(u64* __restrict__ keys0, u6
   unsigned* va = val0 + (size_t)c * P;
   unsigned* vb = val1 + (size_t)c * P;
   int flip = 0;
-  // Key compaction: the keys pack three coordinate fields (x | y << sy | z << sz) but one cloud spans only a
-  // few hundred cells per axis.  Re-basing every field to the cloud's minimum and packing the fields tightly is order
-  // preserving and cuts the 8 radix passes to ceil((bx + by + bz) / 8) (typically 4).  kinfo = {xmin, ymin, zmin, bx, by}
-  // lets later kernels decode; equality and the invalid key (all ones) are preserved.
-  if (tid < 3) {
-    s_mn[tid] = 0x7fffffff;
-    s_mx[tid] = -1;
-  }
-  __syncthreads();
-  {
-    int mn[3] = {0x7fffffff, 0x7fffffff, 0x7fffffff}, mx[3] = {-1, -1, -1};
-    gfs::strided_batch<8>(ka, tid, 1024, n, [&](int, u64 k) {
-      if (k == kInvalidKey) return;
-      const int f[3] = {(int)(k & ((1ull << sy) - 1)), (int)((k >> sy) & ((1ull << (sz - sy)) - 1)), (int)(k >> sz)};
-      for (int a = 0; a < 3; a++) {
-        mn[a] = min(mn[a], f[a]);
-        mx[a] = max(mx[a], f[a]);
-      }
-    });
-    for (int a = 0; a < 3; a++) {  // one LDS atomic a wave
-      mn[a] = gfs::wave_min_i32(mn[a]);
-      mx[a] = gfs::wave_max_i32(mx[a]);
-      if ((tid & 63) == 0 && mx[a] >= 0) {
-        atomicMin(&s_mn[a], mn[a]);
-        atomicMax(&s_mx[a], mx[a]);
-      }
-    }
-  }
-  __syncthreads();
-  const bool any_valid = s_mx[0] >= 0;
-  const int mnx = any_valid ? s_mn[0] : 0, mny = any_valid ? s_mn[1] : 0, mnz = any_valid ? s_mn[2] : 0;
-  auto nbits = [](int range) {
-    int b = 1;
-    while ((1 << b) <= range) b++;
-    return b;
-  };
-  const int bx = any_valid ? nbits(s_mx[0] - mnx) : 1, by = any_valid ? nbits(s_mx[1] - mny) : 1,
-            bz = any_valid ? nbits(s_mx[2] - mnz) : 1;
+  // Key compaction (key_box.hpp) cuts the 8 radix passes to ceil(box.total() / 9) (typically 4); kinfo lets later kernels decode
+  gfs_kb::BoxAcc::begin(s_mn, s_mx);
+  gfs_kb::BoxAcc box_acc;
+  gfs::strided_batch<8>(ka, tid, 1024, n, [&](int, u64 k) { box_acc.add(k, sy, sz); });
+  const gfs_kb::KeyBox box = box_acc.finish(s_mn, s_mx);
   gfs::strided_batch<8>(ka, tid, 1024, n, [&](int i, u64 k) {
-    if (k == kInvalidKey) return;
-    const u64 x = (k & ((1ull << sy) - 1)) - mnx, y = ((k >> sy) & ((1ull << (sz - sy)) - 1)) - mny, z = (k >> sz) - mnz;
-    ka[i] = x | (y << bx) | (z << (bx + by));
+    if (k != kInvalidKey) ka[i] = gfs_kb::pack64(box, k, sy, sz);
   });
-  if (tid == 0) {
-    int* ki = kinfo + 8 * c;
-    ki[0] = mnx;
-    ki[1] = mny;
-    ki[2] = mnz;
-    ki[3] = bx;
-    ki[4] = by;
-  }
+  if (tid == 0) gfs_kb::store(kinfo + gfs_kb::kInfoStride * c, box);
   __syncthreads();
-  // valid keys have bx + by + bz bits; invalid keys (all ones) must still sort last: one more pass over a digit above
+  // valid keys have box.total() bits; invalid keys (all ones) must still sort last: one more pass over a digit above
   // the packed width places them (skipped as uniform when there is no invalid key)
-  const int npass = (bx + by + bz + kDB - 1) / kDB;  // <= 7
+  const int npass = (box.total() + kDB - 1) / kDB;  // <= 7
   for (int pass = 0; pass <= npass && n > 0; pass++) {
     const int shift = kDB * pass;
     for (int k = tid; k < kNB; k += 1024) hist[k] = 0;
@@ -309,8 +268,8 @@ __global__ __launch_bounds__(1024) void k_radix_sort(u64* __restrict__ keys0, u6
 
 // ------------------------------------------------------------------------------------------------
 // k_cell_sort_lds: the CELL sort of a cloud of at most kCsE * 1024 means (a VGA depth image sampled with stride 4) with the
-// cloud RESIDENT IN LDS for all passes: 4-byte compacted keys (the three fields re-based to the cloud's extent, like
-// k_radix_sort) + 2-byte indices = 6 bytes an element, 120 KB, + the sixteen per-wave digit histograms (32 KB).  Same stable LSD
+// cloud RESIDENT IN LDS for all passes: 4-byte compacted keys (the three fields re-based to the cloud's extent:
+// key_box.hpp) + 2-byte indices = 6 bytes an element, 120 KB, + the sixteen per-wave digit histograms (32 KB).  Same stable LSD
 // radix (9-bit digits), same permutation as k_radix_sort; the four passes through HBM of that kernel (2.1 GB moved for 0.42 GB of
 // keys per 1 024 clouds, r03f_pmc_traffic) become one read and one write.  A pass works in place: every thread first takes ITS
 // elements into registers -- wave w owns the contiguous chunk [w * chunk, (w + 1) * chunk) and walks it in rows of 64 lanes, so
@@ -338,11 +297,7 @@ __global__ __launch_bounds__(1024) void k_cell_sort_lds(u64* __restrict__ keys0,
   const int n = __builtin_amdgcn_readfirstlane(counts[c]);
   u64* ka = keys0 + (size_t)c * P;
   unsigned* va = val0 + (size_t)c * P;
-  if (tid < 3) {
-    s_mn[tid] = 0x7fffffff;
-    s_mx[tid] = -1;
-  }
-  __syncthreads();
+  gfs_kb::BoxAcc::begin(s_mn, s_mx);
   // wave w owns [w * chunk, (w + 1) * chunk), chunk a multiple of 64; its row r is elements w * chunk + 64 r + lane
   const int chunk = ((n + 16 * 64 - 1) / (16 * 64)) * 64, rows = chunk >> 6;
   const int base = wave * chunk;
@@ -352,38 +307,11 @@ __global__ __launch_bounds__(1024) void k_cell_sort_lds(u64* __restrict__ keys0,
     const int i = base + 64 * r + lane;
     kreg[r] = (r < rows && i < n) ? ka[i] : kInvalidKey;
   }
-  {
-    int mn[3] = {0x7fffffff, 0x7fffffff, 0x7fffffff}, mx[3] = {-1, -1, -1};
+  gfs_kb::BoxAcc box_acc;
 #pragma unroll
-    for (int r = 0; r < kCsRows; r++) {
-      const u64 k = kreg[r];
-      if (k == kInvalidKey) continue;
-      const int f[3] = {(int)(k & ((1ull << kCkSy) - 1)), (int)((k >> kCkSy) & ((1ull << (kCkSz - kCkSy)) - 1)), (int)(k >> kCkSz)};
-      for (int a = 0; a < 3; a++) {
-        mn[a] = min(mn[a], f[a]);
-        mx[a] = max(mx[a], f[a]);
-      }
-    }
-    for (int a = 0; a < 3; a++) {  // one LDS atomic a wave
-      mn[a] = gfs::wave_min_i32(mn[a]);
-      mx[a] = gfs::wave_max_i32(mx[a]);
-      if (lane == 0 && mx[a] >= 0) {
-        atomicMin(&s_mn[a], mn[a]);
-        atomicMax(&s_mx[a], mx[a]);
-      }
-    }
-  }
-  __syncthreads();
-  const bool any_valid = s_mx[0] >= 0;
-  const int mnx = any_valid ? s_mn[0] : 0, mny = any_valid ? s_mn[1] : 0, mnz = any_valid ? s_mn[2] : 0;
-  auto nbits = [](int range) {
-    int b = 1;
-    while ((1 << b) <= range) b++;
-    return b;
-  };
-  const int bx = any_valid ? nbits(s_mx[0] - mnx) : 1, by = any_valid ? nbits(s_mx[1] - mny) : 1,
-            bz = any_valid ? nbits(s_mx[2] - mnz) : 1;
-  if (bx + by + bz > 32 || n > kCsE * 1024) {  // uniform: left to k_radix_sort (the caller launches it when the count says so)
+  for (int r = 0; r < kCsRows; r++) box_acc.add(kreg[r], kCkSy, kCkSz);
+  const gfs_kb::KeyBox box = box_acc.finish(s_mn, s_mx);
+  if (box.total() > gfs_kb::kMaxBits32 || n > kCsE * 1024) {  // uniform: left to k_radix_sort (the caller launches it when the count says so)
     // The kernels queued behind this one (cell build, grid fill, k-NN, the first LM rounds) run before the host sees *n_left: they
     // must not walk an UNSORTED key array with stale bit widths.  The cloud is emptied for them (an empty cloud is a regular input);
     // the caller's rerun (gicp_run, kAgainAllSorts) rebuilds everything from the input points, this count included.
@@ -391,9 +319,7 @@ __global__ __launch_bounds__(1024) void k_cell_sort_lds(u64* __restrict__ keys0,
       atomicAdd(n_left, 1);
       which[c] = 0;
       counts[c] = 0;
-      int* ki = kinfo + 8 * c;
-      ki[0] = ki[1] = ki[2] = 0;
-      ki[3] = ki[4] = 1;
+      gfs_kb::store(kinfo + gfs_kb::kInfoStride * c, gfs_kb::empty_box());
     }
     return;
   }
@@ -401,23 +327,14 @@ __global__ __launch_bounds__(1024) void k_cell_sort_lds(u64* __restrict__ keys0,
   unsigned short val[kCsRows];
 #pragma unroll
   for (int r = 0; r < kCsRows; r++) {
-    const u64 k = kreg[r];
-    key[r] = 0xffffffffu;  // (a cell key is never the invalid key: every mean is a valid point)
-    if (k != kInvalidKey)
-      key[r] = (unsigned)((k & ((1ull << kCkSy) - 1)) - mnx) | ((unsigned)(((k >> kCkSy) & ((1ull << (kCkSz - kCkSy)) - 1)) - mny) << bx) |
-               ((unsigned)((k >> kCkSz) - mnz) << (bx + by));
+    key[r] = gfs_kb::pack32(box, kreg[r], kCkSy, kCkSz);  // (a cell key is never the invalid key: every mean is a valid point)
     val[r] = (unsigned short)(base + 64 * r + lane);  // the indices enter as the identity (k_voxel_reduce)
   }
   if (tid == 0) {
-    int* ki = kinfo + 8 * c;
-    ki[0] = mnx;
-    ki[1] = mny;
-    ki[2] = mnz;
-    ki[3] = bx;
-    ki[4] = by;
+    gfs_kb::store(kinfo + gfs_kb::kInfoStride * c, box);
     which[c] = 0;  // the sorted keys go back to buffer 0
   }
-  const int npass = (bx + by + bz + kDB - 1) / kDB;
+  const int npass = (box.total() + kDB - 1) / kDB;
   unsigned* myhist = s_hist + wave * kNB;
   const u64 ltm = (1ull << lane) - 1ull;
   for (int pass = 0; pass < npass && n > 0; pass++) {
@@ -517,28 +434,6 @@ __global__ __launch_bounds__(1024) void k_cell_sort_lds(u64* __restrict__ keys0,
   }
 }
 
-// block-wide exclusive scan of one int per thread (1024 threads); returns exclusive prefix, total in *total
-__device__ __forceinline__ int block_scan_1024(int v, int* s_wave /*16*/, int* total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int incl = v;
-#pragma unroll
-  for (int ofs = 1; ofs < 64; ofs <<= 1) {
-    const int t = __shfl_up(incl, ofs, 64);
-    if (lane >= ofs) incl += t;
-  }
-  __syncthreads();
-  if (lane == 63) s_wave[wave] = incl;
-  __syncthreads();
-  int base = 0, tot = 0;
-  for (int w = 0; w < 16; w++) {
-    const int t = s_wave[w];
-    if (w < wave) base += t;
-    tot += t;
-  }
-  *total = tot;
-  return base + incl - v;
-}
-
 // ------------------------------------------------------------------------------------------------
 // k_voxel_reduce: per sorted run of equal voxel keys, cut additionally at every multiple of 1024 in the
 // sorted array (the reference's block-wise reduction, util/downsampling_omp.hpp:63-90), emit the mean
@@ -585,7 +480,7 @@ __global__ __launch_bounds__(1024) void k_voxel_reduce(const float4* __restrict_
         before += (i + u * 1024 < e0 && k[u] != kInvalidKey && (tid == 0 || kp[u] != k[u])) ? 1 : 0;
     }
     int total;
-    (void)block_scan_1024(before, s_wave, &total);
+    (void)gfs::block_scan_1024(before, s_wave, &total);
     __syncthreads();
     if (tid == 0) s_carry = total;
   }
@@ -630,7 +525,7 @@ __global__ __launch_bounds__(1024) void k_voxel_reduce(const float4* __restrict_
     }
     s_stop[tid] = (start || !valid) ? 1 : 0;  // a run ends in front of the next start, of the first invalid key, or with the tile
     int total;
-    const int pos = block_scan_1024(start ? 1 : 0, s_wave, &total) + s_carry;  // (its barriers publish the tile)
+    const int pos = gfs::block_scan_1024(start ? 1 : 0, s_wave, &total) + s_carry;  // (its barriers publish the tile)
     if (start) {
       double sx = 0, sy = 0, sz = 0, sw = 0;
       int j = tid;
@@ -702,14 +597,14 @@ __global__ __launch_bounds__(1024) void k_cell_build(const double4* __restrict__
   // every thread owns a contiguous chunk of the part's sorted keys: one block scan numbers the cell starts
   const int chunk = (a1 - a0 + 1023) / 1024;
   const int i0 = min(a0 + tid * chunk, a1), i1 = min(i0 + chunk, a1);
-  // the sort compacted the keys (k_radix_sort); a CELL is the key without the kFineBits sub-cell bits of its x field
-  const int* ki = kinfo + 8 * c;
-  const int kbx = ki[3], kby = ki[4];
+  // the sort packed the keys into the cloud's key box (key_box.hpp); a CELL is the key without the kFineBits sub-cell bits of its x field
+  const gfs_kb::KeyBox box = gfs_kb::load(kinfo + gfs_kb::kInfoStride * c);
   auto cell_of = [&](u64 key, int& kx, int& ky, int& kz) {
-    const int xf = (int)(key & ((1ull << kbx) - 1)) + ki[0] - kCkOffX;
-    kx = (xf >> kFineBits) + kCoordOffset;  // arithmetic shift = floor
-    ky = (int)((key >> kbx) & ((1ull << kby) - 1)) + ki[1] - kCkOffY + kCoordOffset;
-    kz = (int)(key >> (kbx + kby)) + ki[2] - kCkOffZ + kCoordOffset;
+    int f[3];
+    gfs_kb::unpack_fields(box, key, f);
+    kx = ((f[0] - kCkOffX) >> kFineBits) + kCoordOffset;  // arithmetic shift = floor
+    ky = f[1] - kCkOffY + kCoordOffset;
+    kz = f[2] - kCkOffZ + kCoordOffset;
   };
   auto new_cell = [&](int i) {
     if (i == 0) return true;
@@ -767,11 +662,11 @@ __global__ __launch_bounds__(1024) void k_cell_build(const double4* __restrict__
         before += (i + u * 1024 < a0 && (i + u * 1024 == 0 || ax != bx_ || ay != by_ || az != bz_)) ? 1 : 0;
       }
     }
-    (void)block_scan_1024(before, s_wave, &carry);
+    (void)gfs::block_scan_1024(before, s_wave, &carry);
     __syncthreads();
   }
   int total;
-  int pos = carry + block_scan_1024(cnt, s_wave, &total);
+  int pos = carry + gfs::block_scan_1024(cnt, s_wave, &total);
   total += carry;
   {
     int mn[3] = {kCoordMask, kCoordMask, kCoordMask}, mx[3] = {0, 0, 0};

@@ -24,6 +24,8 @@
 // tests/test_gpu_gicp.py compares the permutation with the oracle's (which calls libstdc++'s std::partition / std::sort).
 #pragma once
 
+#include "gfs_common.hpp"
+#include "key_box.hpp"
 #include "wave_std_sort.hpp"
 
 namespace vqs {
@@ -32,30 +34,9 @@ typedef unsigned long long u64;
 constexpr int kMaxSeg = 1024;      // active ranges (each >= 1024 elements) of one cloud: clouds of up to 2^20 points
 constexpr int kLeafThreshold = 1024;  // sort_omp.hpp:61
 constexpr int kIntroThreshold = 16;   // libstdc++ _S_threshold
+constexpr int kSy = 21, kSz = 42;     // bit positions of the y and z fields of a voxel key (gicp.hip: pack_key)
 
 __device__ __forceinline__ u64 lanemask_lt() { return (1ull << (threadIdx.x & 63)) - 1ull; }
-
-// block-wide exclusive scan, 1024 threads (same helper as gicp.hip's, local copy to keep this header self-contained)
-__device__ __forceinline__ int scan_1024(int v, int* s_wave /*16*/, int* total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int incl = v;
-#pragma unroll
-  for (int ofs = 1; ofs < 64; ofs <<= 1) {
-    const int t = __shfl_up(incl, ofs, 64);
-    if (lane >= ofs) incl += t;
-  }
-  __syncthreads();
-  if (lane == 63) s_wave[wave] = incl;
-  __syncthreads();
-  int base = 0, tot = 0;
-  for (int w = 0; w < 16; w++) {
-    const int t = s_wave[w];
-    if (w < wave) base += t;
-    tot += t;
-  }
-  *total = tot;
-  return base + incl - v;
-}
 
 // Cross-lane steps of the leaf sort as DPP moves (no index registers, no lane masks to keep alive across the leaf loop)
 template <int kCtrl>
@@ -81,8 +62,117 @@ __device__ __forceinline__ unsigned wave_incl_scan_u32(unsigned v) {  // all lan
   return v + (row == 0 ? 0u : row == 1 ? t0 : row == 2 ? t0 + t1 : t0 + t1 + t2);
 }
 
-__device__ __forceinline__ u64 med3(u64 a, u64 b, u64 c) {  // sort_omp.hpp:66-68 on the keys
-  return a < b ? (b < c ? b : (a < c ? c : a)) : (a < c ? a : (b < c ? c : b));
+// ------------------------------------------------------------------------------------------------
+// What the three k_voxel_qsort_top* kernels share around their partition sweeps.  The tables live in the kernels' LDS and come in
+// by pointer.
+// ------------------------------------------------------------------------------------------------
+// Thread 0, once: a cloud of n elements is the first level's only range, or (below 1024) the only leaf
+__device__ __forceinline__ void seed_ranges(int n, int* seg_b, int* seg_e, int* s_nseg, unsigned* leaf, int* s_nleaf) {
+  *s_nleaf = 0;
+  *s_nseg = 0;
+  if (n >= kLeafThreshold) {
+    seg_b[0] = 0;
+    seg_e[0] = n;
+    *s_nseg = 1;
+  } else if (n >= 2) {
+    leaf[0] = 0u;
+    leaf[1] = (unsigned)n;
+    *s_nleaf = 1;
+  }
+}
+
+// sort_omp.hpp:66-75 on the keys f[0 .. len): the median of three medians of three, the samples len / 8 apart
+template <class K>
+__device__ __forceinline__ K pivot9(const K* f, int len) {
+  auto med3 = [](K a, K b, K c) { return a < b ? (b < c ? b : (a < c ? c : a)) : (a < c ? a : (b < c ? c : b)); };
+  const int off = len / 8;
+  return med3(med3(f[0], f[off], f[off * 2]), med3(f[off * 3], f[off * 4], f[off * 5]), med3(f[off * 6], f[off * 7], f[len - 1]));
+}
+
+// The end of a level, called by all threads: the thread of a range (on) hands in its children [b0, e0) = [first, middle1) and
+// [b1, e1) = [middle2, last).  Children of >= 1024 elements become the next level's ranges, in the order of their parents;
+// shorter ones of >= 2 join the leaf list.  Ends with a barrier.
+__device__ __forceinline__ void push_children(bool on, int b0, int e0, int b1, int e1, int* seg_b, int* seg_e, int* s_nseg, int* s_wave,
+                                              unsigned* leaf, int* s_nleaf) {
+  const int child_b[2] = {b0, b1}, child_e[2] = {e0, e1};
+  int nact = 0;
+  if (on)
+    for (int k = 0; k < 2; k++) nact += (child_e[k] - child_b[k] >= kLeafThreshold) ? 1 : 0;
+  int tot_act;
+  int pos = gfs::block_scan_1024(nact, s_wave, &tot_act);
+  __syncthreads();  // everybody has read the old tables
+  if (on) {
+    for (int k = 0; k < 2; k++) {
+      const int len = child_e[k] - child_b[k];
+      if (len >= kLeafThreshold) {
+        seg_b[pos] = child_b[k];
+        seg_e[pos] = child_e[k];
+        pos++;
+      } else if (len >= 2) {
+        const int slot = atomicAdd(s_nleaf, 1);
+        leaf[2 * slot] = (unsigned)child_b[k];
+        leaf[2 * slot + 1] = (unsigned)child_e[k];
+      }
+    }
+  }
+  if (threadIdx.x == 0) *s_nseg = tot_act;
+  __syncthreads();
+}
+
+// k_voxel_qsort_top_reg / _lds: a range as a wave walking the array sees it -- wave-uniform, kept in scalar registers.
+// first = where the partitioned region starts (mode 0: the range; mode 1, the second partition: middle1); base / m = the flagged
+// elements in front of the range / inside it (with_counts: once the counting phase has filled seg_base)
+struct SegP {
+  int b, e, first, base, m;
+  unsigned pv;
+};
+struct SegTables {
+  const int *seg_b, *seg_e, *seg_m1, *seg_base;
+  const unsigned* seg_pv;
+};
+__device__ __forceinline__ SegP load_seg(const SegTables& t, int sidx, int nseg, int mode, bool with_counts) {
+  SegP q;
+  q.b = q.e = q.first = 0x7fffffff;
+  q.base = q.m = 0;
+  q.pv = 0;
+  if (sidx < nseg) {
+    q.b = __builtin_amdgcn_readfirstlane(t.seg_b[sidx]);
+    q.e = __builtin_amdgcn_readfirstlane(t.seg_e[sidx]);
+    q.first = mode == 0 ? q.b : __builtin_amdgcn_readfirstlane(t.seg_m1[sidx]);
+    q.pv = (unsigned)__builtin_amdgcn_readfirstlane((int)t.seg_pv[sidx]);
+    if (with_counts) {
+      q.base = __builtin_amdgcn_readfirstlane(t.seg_base[sidx]);
+      q.m = __builtin_amdgcn_readfirstlane(t.seg_base[sidx + 1]) - q.base;
+    }
+  }
+  return q;
+}
+
+// k_voxel_qsort_top_reg / _lds, one thread a range: the second std::partition of a level (keys equal to the pivot to the front of
+// [m1, last)) by replaying its swaps.  q[0 .. m) = the positions of the m pivot keys, in any order (sorted here, ascending); the
+// k-th position of [m1, m1 + m) not holding a pivot key (from the left) swaps with the k-th pivot key beyond (from the right):
+// swap(j, jt) exchanges the elements at j < jt.
+template <class Swap>
+__device__ __forceinline__ void replay_second_partition(int m, int m1, int* q, Swap&& swap) {
+#pragma unroll 1
+  for (int a = 1; a < m; a++) {
+    const int v = q[a];
+    int bpos = a;
+    while (bpos > 0 && q[bpos - 1] > v) {
+      q[bpos] = q[bpos - 1];
+      bpos--;
+    }
+    q[bpos] = v;
+  }
+  int a = 0, t = m - 1;
+#pragma unroll 1
+  for (int j = m1; j < m1 + m; j++) {
+    if (a < m && q[a] == j) {
+      a++;
+      continue;
+    }
+    swap(j, q[t--]);  // q[t] >= m1 + m by counting
+  }
 }
 
 // One sweep over the elements of all active ranges ("virtual" index space = the ranges concatenated): wave w owns the
@@ -116,93 +206,43 @@ __device__ __forceinline__ void sweep(int A, int E, int nseg, const int* seg_v, 
 
 // ------------------------------------------------------------------------------------------------
 // k_voxel_qsort_top: one 1024-thread workgroup per cloud.  Compacts the 3 x 21-bit voxel keys to the cloud's extent
-// (order preserving, like k_radix_sort), then runs the n >= 1024 levels of quick_sort_omp_impl for all ranges of a level
+// (order preserving: key_box.hpp), then runs the n >= 1024 levels of quick_sort_omp_impl for all ranges of a level
 // at once; ranges that drop below 1024 elements are appended to the cloud's leaf list for k_voxel_qsort_leaf.
 // keys / vals are permuted in place; side_k / side_v hold the elements in flight of a partition sweep.
-// kinfo[8c ..] = {xmin, ymin, zmin, bx, by, total bits}.
+// kinfo[8c ..] = the cloud's key box and its total bits (key_box.hpp: slots 0 - 5).
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(1024) void k_voxel_qsort_top(u64* keys_all, unsigned* vals_all, u64* side_k_all, unsigned* side_v_all,
                                                           const int* __restrict__ counts, int P, int* __restrict__ which,
                                                           int* __restrict__ kinfo, unsigned* __restrict__ leaf_all,
                                                           int* __restrict__ nleaf, int only, int only_flagged) {
   constexpr u64 kInvalid = ~0ull;
-  constexpr int kCB = 21, kCM = (1 << kCB) - 1;
-  __shared__ int seg_b[kMaxSeg], seg_e[kMaxSeg], seg_v[kMaxSeg + 1], seg_base[kMaxSeg + 1], seg_off[kMaxSeg], seg_m1[kMaxSeg];
+  __shared__ int seg_b[kMaxSeg],seg_e[kMaxSeg], seg_v[kMaxSeg + 1], seg_base[kMaxSeg + 1], seg_off[kMaxSeg], seg_m1[kMaxSeg];
   __shared__ u64 seg_pv[kMaxSeg];
   __shared__ int s_wave[16];
   __shared__ int s_nseg, s_nleaf, s_A;
   __shared__ int s_mn[3], s_mx[3];
   const int c = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // scalar
   if (only >= 0 && (c & 1) != only) return;
-  if (only_flagged && kinfo[8 * c + 6] == 0) return;  // k_voxel_qsort_top_reg took this cloud
+  if (only_flagged && kinfo[gfs_kb::kInfoStride * c + gfs_kb::kInfoLeft] == 0) return;  // k_voxel_qsort_top_reg took this cloud
   const int n = counts[c];
   u64* ka = keys_all + (size_t)c * P;
   unsigned* va = vals_all + (size_t)c * P;
   u64* sk = side_k_all + (size_t)c * P;
   unsigned* sv = side_v_all + (size_t)c * P;
   unsigned* leaf = leaf_all + (size_t)c * P;
-  // ---- key compaction (see k_radix_sort)
-  if (tid < 3) {
-    s_mn[tid] = 0x7fffffff;
-    s_mx[tid] = -1;
-  }
-  __syncthreads();
-  {
-    int mn[3] = {0x7fffffff, 0x7fffffff, 0x7fffffff}, mx[3] = {-1, -1, -1};
-    for (int i = tid; i < n; i += 1024) {
-      const u64 k = ka[i];
-      if (k == kInvalid) continue;
-      const int f[3] = {(int)(k & kCM), (int)((k >> kCB) & kCM), (int)(k >> (2 * kCB))};
-      for (int a = 0; a < 3; a++) {
-        mn[a] = min(mn[a], f[a]);
-        mx[a] = max(mx[a], f[a]);
-      }
-    }
-    for (int a = 0; a < 3; a++) {  // one LDS atomic a wave
-      mn[a] = gfs::wave_min_i32(mn[a]);
-      mx[a] = gfs::wave_max_i32(mx[a]);
-      if (lane == 0 && mx[a] >= 0) {
-        atomicMin(&s_mn[a], mn[a]);
-        atomicMax(&s_mx[a], mx[a]);
-      }
-    }
-  }
-  __syncthreads();
-  const bool any_valid = s_mx[0] >= 0;
-  const int mnx = any_valid ? s_mn[0] : 0, mny = any_valid ? s_mn[1] : 0, mnz = any_valid ? s_mn[2] : 0;
-  auto nbits = [](int range) {
-    int b = 1;
-    while ((1 << b) <= range) b++;
-    return b;
-  };
-  const int bx = any_valid ? nbits(s_mx[0] - mnx) : 1, by = any_valid ? nbits(s_mx[1] - mny) : 1,
-            bz = any_valid ? nbits(s_mx[2] - mnz) : 1;
+  // ---- key compaction (key_box.hpp)
+  gfs_kb::BoxAcc::begin(s_mn, s_mx);
+  gfs_kb::BoxAcc box_acc;
+  for (int i = tid; i < n; i += 1024) box_acc.add(ka[i], kSy, kSz);
+  const gfs_kb::KeyBox box = box_acc.finish(s_mn, s_mx);
   for (int i = tid; i < n; i += 1024) {
     const u64 k = ka[i];
-    if (k == kInvalid) continue;
-    const u64 x = (k & kCM) - mnx, y = ((k >> kCB) & kCM) - mny, z = (k >> (2 * kCB)) - mnz;
-    ka[i] = x | (y << bx) | (z << (bx + by));
+    if (k != kInvalid) ka[i] = gfs_kb::pack64(box, k, kSy, kSz);
   }
   if (tid == 0) {
-    int* ki = kinfo + 8 * c;
-    ki[0] = mnx;
-    ki[1] = mny;
-    ki[2] = mnz;
-    ki[3] = bx;
-    ki[4] = by;
-    ki[5] = bx + by + bz;
+    gfs_kb::store_with_total(kinfo + gfs_kb::kInfoStride * c, box);
     which[c] = 0;  // sorted in place
-    s_nleaf = 0;
-    s_nseg = 0;
-    if (n >= kLeafThreshold) {
-      seg_b[0] = 0;
-      seg_e[0] = n;
-      s_nseg = 1;
-    } else if (n >= 2) {
-      leaf[0] = 0u;
-      leaf[1] = (unsigned)n;
-      s_nleaf = 1;
-    }
+    seed_ranges(n, seg_b, seg_e, &s_nseg, leaf, &s_nleaf);
   }
   __syncthreads();
   // ---- levels of the 3-way quicksort
@@ -213,16 +253,12 @@ __global__ __launch_bounds__(1024) void k_voxel_qsort_top(u64* keys_all, unsigne
     if (tid < nseg) {
       my_b = seg_b[tid];
       my_e = seg_e[tid];
-      const int len = my_e - my_b, off = len / 8;  // sort_omp.hpp:70-75
-      const u64* f = ka + my_b;
-      const u64 m1 = med3(f[0], f[off], f[off * 2]), m2 = med3(f[off * 3], f[off * 4], f[off * 5]),
-                m3 = med3(f[off * 6], f[off * 7], f[len - 1]);
-      seg_pv[tid] = med3(m1, m2, m3);
+      seg_pv[tid] = pivot9(ka + my_b, my_e - my_b);
       seg_off[tid] = 0;
     }
     {
       int tot;
-      const int ex = scan_1024(tid < nseg ? my_e - my_b : 0, s_wave, &tot);
+      const int ex = gfs::block_scan_1024(tid < nseg ? my_e - my_b : 0, s_wave, &tot);
       if (tid < nseg) seg_v[tid] = ex;
       if (tid == 0) {
         seg_v[nseg] = tot;
@@ -324,33 +360,10 @@ __global__ __launch_bounds__(1024) void k_voxel_qsort_top(u64* keys_all, unsigne
       __syncthreads();
     }
     // ---- children: [first, middle1) and [middle2, last)
-    int child_b[2] = {0, 0}, child_e[2] = {0, 0}, nact = 0;
-    if (tid < nseg) {
-      child_b[0] = my_b;
-      child_e[0] = seg_m1[tid];
-      child_b[1] = my_b + seg_off[tid];
-      child_e[1] = my_e;
-      for (int k = 0; k < 2; k++) nact += (child_e[k] - child_b[k] >= kLeafThreshold) ? 1 : 0;
+    {
+      const bool on = tid < nseg;
+      push_children(on, my_b, on ? seg_m1[tid] : 0, on ? my_b + seg_off[tid] : 0, my_e, seg_b, seg_e, &s_nseg, s_wave, leaf, &s_nleaf);
     }
-    int tot_act;
-    int pos = scan_1024(nact, s_wave, &tot_act);
-    __syncthreads();  // everybody has read the old tables
-    if (tid < nseg) {
-      for (int k = 0; k < 2; k++) {
-        const int len = child_e[k] - child_b[k];
-        if (len >= kLeafThreshold) {
-          seg_b[pos] = child_b[k];
-          seg_e[pos] = child_e[k];
-          pos++;
-        } else if (len >= 2) {
-          const int slot = atomicAdd(&s_nleaf, 1);
-          leaf[2 * slot] = (unsigned)child_b[k];
-          leaf[2 * slot + 1] = (unsigned)child_e[k];
-        }
-      }
-    }
-    if (tid == 0) s_nseg = tot_act;
-    __syncthreads();
   }
   if (tid == 0) nleaf[c] = s_nleaf;
 }
@@ -371,7 +384,6 @@ __global__ __launch_bounds__(1024) void k_voxel_qsort_top_reg(u64* keys_all, uns
                                                               int* __restrict__ kinfo, unsigned* __restrict__ leaf_all,
                                                               int* __restrict__ nleaf, int only, int only_flagged) {
   constexpr u64 kInvalid = ~0ull;
-  constexpr int kCB = 21, kCM = (1 << kCB) - 1;
   constexpr int kSeg = EMAX + 1, kEq = 32;
   __shared__ int seg_b[kSeg], seg_e[kSeg], seg_base[kSeg + 1], seg_m1[kSeg], seg_m2[kSeg], eq_cnt[kSeg], eq_pos[kSeg][kEq];
   __shared__ int seg_local[kSeg], seg_wave[kSeg];  // flagged count before a range's first element inside its wave's chunk; that wave
@@ -382,7 +394,7 @@ __global__ __launch_bounds__(1024) void k_voxel_qsort_top_reg(u64* keys_all, uns
   __shared__ int s_mn[3], s_mx[3];
   const int c = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // scalar
   if (only >= 0 && (c & 1) != only) return;
-  if (only_flagged && kinfo[8 * c + 6] == 0) return;  // k_voxel_qsort_top_lds took this cloud
+  if (only_flagged && kinfo[gfs_kb::kInfoStride * c + gfs_kb::kInfoLeft] == 0) return;  // k_voxel_qsort_top_lds took this cloud
   const int n = __builtin_amdgcn_readfirstlane(counts[c]);
   u64* ka = keys_all + (size_t)c * P;
   unsigned* va = vals_all + (size_t)c * P;
@@ -398,94 +410,35 @@ __global__ __launch_bounds__(1024) void k_voxel_qsort_top_reg(u64* keys_all, uns
   auto vbuf = [&](int w) { return w ? vbuf1 : vbuf0; };
   int cur = 0;
   unsigned* leaf = leaf_all + (size_t)c * P;
-  if (tid < 3) {
-    s_mn[tid] = 0x7fffffff;
-    s_mx[tid] = -1;
-  }
-  __syncthreads();
-  {
-    int mn[3] = {0x7fffffff, 0x7fffffff, 0x7fffffff}, mx[3] = {-1, -1, -1};
-    for (int i = tid; i < n; i += 1024) {
-      const u64 k = ka[i];
-      if (k == kInvalid) continue;
-      const int f[3] = {(int)(k & kCM), (int)((k >> kCB) & kCM), (int)(k >> (2 * kCB))};
-      for (int a = 0; a < 3; a++) {
-        mn[a] = min(mn[a], f[a]);
-        mx[a] = max(mx[a], f[a]);
-      }
-    }
-    for (int a = 0; a < 3; a++) {  // one LDS atomic a wave
-      mn[a] = gfs::wave_min_i32(mn[a]);
-      mx[a] = gfs::wave_max_i32(mx[a]);
-      if (lane == 0 && mx[a] >= 0) {
-        atomicMin(&s_mn[a], mn[a]);
-        atomicMax(&s_mx[a], mx[a]);
-      }
-    }
-  }
-  __syncthreads();
-  const bool any_valid = s_mx[0] >= 0;
-  const int mnx = any_valid ? s_mn[0] : 0, mny = any_valid ? s_mn[1] : 0, mnz = any_valid ? s_mn[2] : 0;
-  auto nbits = [](int range) {
-    int b = 1;
-    while ((1 << b) <= range) b++;
-    return b;
-  };
-  const int bx = any_valid ? nbits(s_mx[0] - mnx) : 1, by = any_valid ? nbits(s_mx[1] - mny) : 1,
-            bz = any_valid ? nbits(s_mx[2] - mnz) : 1;
-  if (bx + by + bz > 31 || n > 1024 * EMAX) {  // uniform: left to the general kernel
-    if (tid == 0) kinfo[8 * c + 6] = 1;
+  gfs_kb::BoxAcc::begin(s_mn, s_mx);
+  gfs_kb::BoxAcc box_acc;
+  for (int i = tid; i < n; i += 1024) box_acc.add(ka[i], kSy, kSz);
+  const gfs_kb::KeyBox box = box_acc.finish(s_mn, s_mx);
+  int* ki = kinfo + gfs_kb::kInfoStride * c;
+  if (box.total() > gfs_kb::kMaxBits32WithInvalid || n > 1024 * EMAX) {  // uniform: left to the general kernel
+    if (tid == 0) ki[gfs_kb::kInfoLeft] = 1;
     return;
   }
-  for (int i = tid; i < n; i += 1024) {
-    const u64 k = ka[i];
-    unsigned kk = 0xffffffffu;
-    if (k != kInvalid) kk = (unsigned)((k & kCM) - mnx) | ((unsigned)(((k >> kCB) & kCM) - mny) << bx) | ((unsigned)((k >> (2 * kCB)) - mnz) << (bx + by));
-    kscr[i] = kk;
-  }
+  for (int i = tid; i < n; i += 1024) kscr[i] = gfs_kb::pack32(box, ka[i], kSy, kSz);
   if (tid == 0) {
-    int* ki = kinfo + 8 * c;
-    ki[0] = mnx;
-    ki[1] = mny;
-    ki[2] = mnz;
-    ki[3] = bx;
-    ki[4] = by;
-    ki[5] = bx + by + bz;
-    ki[6] = 0;
+    gfs_kb::store_with_total(ki, box);
+    ki[gfs_kb::kInfoLeft] = 0;
     which[c] = 0;
-    s_nleaf = 0;
-    s_nseg = 0;
-    if (n >= kLeafThreshold) {
-      seg_b[0] = 0;
-      seg_e[0] = n;
-      s_nseg = 1;
-    } else if (n >= 2) {
-      leaf[0] = 0u;
-      leaf[1] = (unsigned)n;
-      s_nleaf = 1;
-    }
+    seed_ranges(n, seg_b, seg_e, &s_nseg, leaf, &s_nleaf);
   }
   __syncthreads();
   const int E = (n + 1023) / 1024;
   const u64 ltm = lanemask_lt();
+  const SegTables segs{seg_b, seg_e, seg_m1, seg_base, seg_pv};
   while (true) {
     const int nseg = __builtin_amdgcn_readfirstlane(s_nseg);
     if (nseg == 0) break;
     if (tid < nseg) {
-      const int b = seg_b[tid], len = seg_e[tid] - b, off = len / 8;  // sort_omp.hpp:70-75
-      const unsigned* f = kbuf(cur) + b;
-      auto m3 = [](unsigned x, unsigned y, unsigned z) { return x < y ? (y < z ? y : (x < z ? z : x)) : (x < z ? x : (y < z ? z : y)); };
-      const unsigned m1 = m3(f[0], f[off], f[off * 2]), m2 = m3(f[off * 3], f[off * 4], f[off * 5]),
-                     mm = m3(f[off * 6], f[off * 7], f[len - 1]);
-      seg_pv[tid] = m3(m1, m2, mm);
+      seg_pv[tid] = pivot9(kbuf(cur) + seg_b[tid], seg_e[tid] - seg_b[tid]);
       eq_cnt[tid] = 0;
     }
     if (tid == 0) s_over = 0;
     __syncthreads();
-    struct SegP {
-      int b, e, first, base, m;
-      unsigned pv;
-    };
     // Stores every cached element where std::partition leaves it: the k-th misplaced element of the front part (from the
     // left) and the k-th misplaced element of the back part (from the right) announce their positions in side_pos and take
     // each other's place; everything else stays.  (All elements are in registers, so the scatter is in place.)
@@ -494,29 +447,12 @@ __global__ __launch_bounds__(1024) void k_voxel_qsort_top_reg(u64* keys_all, uns
       const unsigned* vin = vbuf(cur);
       unsigned* kout = kbuf(cur ^ 1);
       unsigned* vout = vbuf(cur ^ 1);
-      auto load_seg = [&](int sidx, bool with_counts) {
-        SegP q;
-        q.b = q.e = q.first = 0x7fffffff;
-        q.base = q.m = 0;
-        q.pv = 0;
-        if (sidx < nseg) {  // wave-uniform: kept in scalar registers
-          q.b = __builtin_amdgcn_readfirstlane(seg_b[sidx]);
-          q.e = __builtin_amdgcn_readfirstlane(seg_e[sidx]);
-          q.first = mode == 0 ? q.b : __builtin_amdgcn_readfirstlane(seg_m1[sidx]);
-          q.pv = (unsigned)__builtin_amdgcn_readfirstlane((int)seg_pv[sidx]);
-          if (with_counts) {
-            q.base = __builtin_amdgcn_readfirstlane(seg_base[sidx]);
-            q.m = __builtin_amdgcn_readfirstlane(seg_base[sidx + 1]) - q.base;
-          }
-        }
-        return q;
-      };
 #define VQS_ROW_BEGIN(with_counts)                                       \
   const int row0 = (wave * E + r) * 64, i = row0 + lane;                 \
   while (row0 >= A.e && sA < nseg) {                                     \
     A = B;                                                               \
     sA++;                                                                \
-    B = load_seg(sA + 1, with_counts);                                   \
+    B = load_seg(segs, sA + 1, nseg, mode, with_counts);                 \
   }                                                                      \
   const bool inB = i >= B.b, in = inB || (i >= A.b && i < A.e);          \
   const unsigned pv = inB ? B.pv : A.pv;                                 \
@@ -529,7 +465,7 @@ __global__ __launch_bounds__(1024) void k_voxel_qsort_top_reg(u64* keys_all, uns
   const bool flag = in && (mode == 0 ? key_r < pv : (i >= first && !(pv < key_r)));
       {  // (A) flagged elements per wave, and before every range start inside its wave
         int cnt = 0, sA = 0;
-        SegP A = load_seg(0, false), B = load_seg(1, false);
+        SegP A = load_seg(segs, 0, nseg, mode, false), B = load_seg(segs, 1, nseg, mode, false);
         unsigned key_nx = (wave * E * 64 + lane) < n ? kin[wave * E * 64 + lane] : 0u;
 #pragma unroll 1
         for (int r = 0; r < E; r++) {
@@ -561,7 +497,7 @@ __global__ __launch_bounds__(1024) void k_voxel_qsort_top_reg(u64* keys_all, uns
       __syncthreads();
       for (int step = 0; step < 2; step++) {  // (B) announce, (C) take the partner's place
         int run = wave_base, sA = 0;
-        SegP A = load_seg(0, true), B = load_seg(1, true);
+        SegP A = load_seg(segs, 0, nseg, mode, true), B = load_seg(segs, 1, nseg, mode, true);
         unsigned key_nx = (wave * E * 64 + lane) < n ? kin[wave * E * 64 + lane] : 0u;
 #pragma unroll 1
         for (int r = 0; r < E; r++) {
@@ -613,26 +549,7 @@ __global__ __launch_bounds__(1024) void k_voxel_qsort_top_reg(u64* keys_all, uns
       if (m > kEq) {
         s_over = 1;
       } else {
-        int* q = eq_pos[tid];  // sorted in place (ascending positions)
-#pragma unroll 1
-        for (int a = 1; a < m; a++) {
-          const int v = q[a];
-          int bpos = a;
-          while (bpos > 0 && q[bpos - 1] > v) {
-            q[bpos] = q[bpos - 1];
-            bpos--;
-          }
-          q[bpos] = v;
-        }
-        // k-th position of [m1, m1 + m) not holding a pivot key (from the left) <-> k-th pivot key beyond (from the right)
-        int a = 0, t = m - 1;
-#pragma unroll 1
-        for (int j = m1; j < m1 + m; j++) {
-          if (a < m && q[a] == j) {
-            a++;
-            continue;
-          }
-          const int jt = q[t--];  // >= m1 + m by counting
+        replay_second_partition(m, m1, eq_pos[tid], [&](int j, int jt) {
           unsigned* kc = kbuf(cur);
           unsigned* vc = vbuf(cur);
           const unsigned kj = kc[j], vj = vc[j];
@@ -640,7 +557,7 @@ __global__ __launch_bounds__(1024) void k_voxel_qsort_top_reg(u64* keys_all, uns
           vc[j] = vc[jt];
           kc[jt] = kj;
           vc[jt] = vj;
-        }
+        });
       }
     }
     __syncthreads();
@@ -649,34 +566,11 @@ __global__ __launch_bounds__(1024) void k_voxel_qsort_top_reg(u64* keys_all, uns
       if (tid < nseg) seg_m2[tid] = seg_m1[tid] + (seg_base[tid + 1] - seg_base[tid]);
       __syncthreads();
     }
-    // children [first, middle1) and [middle2, last)
-    int child_b[2] = {0, 0}, child_e[2] = {0, 0}, nact = 0;
-    if (tid < nseg) {
-      child_b[0] = seg_b[tid];
-      child_e[0] = seg_m1[tid];
-      child_b[1] = seg_m2[tid];
-      child_e[1] = seg_e[tid];
-      for (int k = 0; k < 2; k++) nact += (child_e[k] - child_b[k] >= kLeafThreshold) ? 1 : 0;
+    {  // children [first, middle1) and [middle2, last)
+      const bool on = tid < nseg;
+      push_children(on, on ? seg_b[tid] : 0, on ? seg_m1[tid] : 0, on ? seg_m2[tid] : 0, on ? seg_e[tid] : 0, seg_b, seg_e, &s_nseg,
+                    s_wave, leaf, &s_nleaf);
     }
-    int tot_act;
-    int pos = scan_1024(nact, s_wave, &tot_act);
-    __syncthreads();
-    if (tid < nseg) {
-      for (int k = 0; k < 2; k++) {
-        const int len = child_e[k] - child_b[k];
-        if (len >= kLeafThreshold) {
-          seg_b[pos] = child_b[k];
-          seg_e[pos] = child_e[k];
-          pos++;
-        } else if (len >= 2) {
-          const int slot = atomicAdd(&s_nleaf, 1);
-          leaf[2 * slot] = (unsigned)child_b[k];
-          leaf[2 * slot + 1] = (unsigned)child_e[k];
-        }
-      }
-    }
-    if (tid == 0) s_nseg = tot_act;
-    __syncthreads();
   }
   // the keys go back as 64-bit compacted keys (k_voxel_qsort_leaf, k_voxel_reduce)
   {
@@ -724,7 +618,6 @@ __global__ __launch_bounds__(1024) void k_voxel_qsort_top_lds(u64* keys_all, uns
                                                               int* __restrict__ kinfo, unsigned* __restrict__ leaf_all,
                                                               int* __restrict__ nleaf, int only, int* __restrict__ n_left) {
   constexpr u64 kInvalid = ~0ull;
-  constexpr int kCB = 21, kCM = (1 << kCB) - 1;
   constexpr int kSeg = EMAX + 1, kEq = 32;
   __shared__ int seg_b[kSeg], seg_e[kSeg], seg_base[kSeg + 1], seg_m1[kSeg], seg_m2[kSeg], eq_cnt[kSeg], eq_pos[kSeg][kEq];
   __shared__ int seg_local[kSeg], seg_wave[kSeg];  // flagged count before a range's first element inside its wave's chunk; that wave
@@ -746,57 +639,27 @@ __global__ __launch_bounds__(1024) void k_voxel_qsort_top_lds(u64* keys_all, uns
   u64* ka = keys_all + (size_t)c * P;
   unsigned* va = vals_all + (size_t)c * P;
   unsigned* leaf = leaf_all + (size_t)c * P;
-  if (tid < 3) {
-    s_mn[tid] = 0x7fffffff;
-    s_mx[tid] = -1;
-  }
-  __syncthreads();
+  gfs_kb::BoxAcc::begin(s_mn, s_mx);
   // the thread's keys: all loads of a chunk in flight at once (one workgroup a CU: nothing else hides their latency); up to 19 rows
   // are ONE chunk that stays in registers for the compaction below, more rows are read twice, 19 at a time
   constexpr int kRows = EMAX <= 19 ? EMAX : 19, kChunks = (EMAX + kRows - 1) / kRows;
   u64 kreg[kRows];
-  {
-    int mn[3] = {0x7fffffff, 0x7fffffff, 0x7fffffff}, mx[3] = {-1, -1, -1};
+  gfs_kb::BoxAcc box_acc;
 #pragma unroll
-    for (int ch = 0; ch < kChunks; ch++) {
+  for (int ch = 0; ch < kChunks; ch++) {
 #pragma unroll
-      for (int r = 0; r < kRows; r++) {
-        const int i = (ch * kRows + r) * 1024 + tid;
-        kreg[r] = (ch * kRows + r < EMAX && i < n) ? ka[i] : kInvalid;
-      }
-#pragma unroll
-      for (int r = 0; r < kRows; r++) {
-        const u64 k = kreg[r];
-        if (k == kInvalid) continue;
-        const int f[3] = {(int)(k & kCM), (int)((k >> kCB) & kCM), (int)(k >> (2 * kCB))};
-        for (int a = 0; a < 3; a++) {
-          mn[a] = min(mn[a], f[a]);
-          mx[a] = max(mx[a], f[a]);
-        }
-      }
+    for (int r = 0; r < kRows; r++) {
+      const int i = (ch * kRows + r) * 1024 + tid;
+      kreg[r] = (ch * kRows + r < EMAX && i < n) ? ka[i] : kInvalid;
     }
-    for (int a = 0; a < 3; a++) {  // one LDS atomic a wave, not one a thread
-      mn[a] = gfs::wave_min_i32(mn[a]);
-      mx[a] = gfs::wave_max_i32(mx[a]);
-      if (lane == 0 && mx[a] >= 0) {
-        atomicMin(&s_mn[a], mn[a]);
-        atomicMax(&s_mx[a], mx[a]);
-      }
-    }
+#pragma unroll
+    for (int r = 0; r < kRows; r++) box_acc.add(kreg[r], kSy, kSz);
   }
-  __syncthreads();
-  const bool any_valid = s_mx[0] >= 0;
-  const int mnx = any_valid ? s_mn[0] : 0, mny = any_valid ? s_mn[1] : 0, mnz = any_valid ? s_mn[2] : 0;
-  auto nbits = [](int range) {
-    int b = 1;
-    while ((1 << b) <= range) b++;
-    return b;
-  };
-  const int bx = any_valid ? nbits(s_mx[0] - mnx) : 1, by = any_valid ? nbits(s_mx[1] - mny) : 1,
-            bz = any_valid ? nbits(s_mx[2] - mnz) : 1;
-  if (bx + by + bz > 31 || n > 1024 * EMAX) {  // uniform: left to the kernels that work through HBM
+  const gfs_kb::KeyBox box = box_acc.finish(s_mn, s_mx);
+  int* ki = kinfo + gfs_kb::kInfoStride * c;
+  if (box.total() > gfs_kb::kMaxBits32WithInvalid || n > 1024 * EMAX) {  // uniform: left to the kernels that work through HBM
     if (tid == 0) {
-      kinfo[8 * c + 6] = 2;
+      ki[gfs_kb::kInfoLeft] = 2;
       if (n_left) {  // the host launches those kernels only when a cloud asked for them (gicp_run); until then the cloud stays
         atomicAdd(n_left, 1);  // unsorted and the leaf kernels must find nothing to do in it
         nleaf[c] = 0;
@@ -817,9 +680,7 @@ __global__ __launch_bounds__(1024) void k_voxel_qsort_top_lds(u64* keys_all, uns
 #pragma unroll
     for (int r = 0; r < kRows; r++) {
       const int i = (ch * kRows + r) * 1024 + tid;
-      const u64 k = kreg[r];
-      unsigned kk = 0xffffffffu;
-      if (k != kInvalid) kk = (unsigned)((k & kCM) - mnx) | ((unsigned)(((k >> kCB) & kCM) - mny) << bx) | ((unsigned)((k >> (2 * kCB)) - mnz) << (bx + by));
+      const unsigned kk = gfs_kb::pack32(box, kreg[r], kSy, kSz);
       if (ch * kRows + r < EMAX && i < n) {
         s_key[i] = kk;
         s_val[i] = (unsigned short)i;  // the point indices enter as the identity (k_voxel_keys, gfs_test_voxel_sort)
@@ -827,78 +688,37 @@ __global__ __launch_bounds__(1024) void k_voxel_qsort_top_lds(u64* keys_all, uns
     }
   }
   if (tid == 0) {
-    int* ki = kinfo + 8 * c;
-    ki[0] = mnx;
-    ki[1] = mny;
-    ki[2] = mnz;
-    ki[3] = bx;
-    ki[4] = by;
-    ki[5] = bx + by + bz;
-    ki[6] = 0;
+    gfs_kb::store_with_total(ki, box);
+    ki[gfs_kb::kInfoLeft] = 0;
     which[c] = 0;
-    s_nleaf = 0;
-    s_nseg = 0;
-    if (n >= kLeafThreshold) {
-      seg_b[0] = 0;
-      seg_e[0] = n;
-      s_nseg = 1;
-    } else if (n >= 2) {
-      leaf[0] = 0u;
-      leaf[1] = (unsigned)n;
-      s_nleaf = 1;
-    }
+    seed_ranges(n, seg_b, seg_e, &s_nseg, leaf, &s_nleaf);
   }
   __syncthreads();  VQS_T(0)
   const int E4 = (n + 4095) / 4096, chunk = E4 * 256;  // rows of 256 elements a wave; its part of the array
   const u64 ltm = lanemask_lt();
+  const SegTables segs{seg_b, seg_e, seg_m1, seg_base, seg_pv};
   while (true) {
     const int nseg = __builtin_amdgcn_readfirstlane(s_nseg);
     if (nseg == 0) break;
     if (tid < nseg) {
-      const int b = seg_b[tid], len = seg_e[tid] - b, off = len / 8;  // sort_omp.hpp:70-75
-      const unsigned* f = s_key + b;
-      auto m3 = [](unsigned x, unsigned y, unsigned z) { return x < y ? (y < z ? y : (x < z ? z : x)) : (x < z ? x : (y < z ? z : y)); };
-      const unsigned m1 = m3(f[0], f[off], f[off * 2]), m2 = m3(f[off * 3], f[off * 4], f[off * 5]),
-                     mm = m3(f[off * 6], f[off * 7], f[len - 1]);
-      seg_pv[tid] = m3(m1, m2, mm);
+      seg_pv[tid] = pivot9(s_key + seg_b[tid], seg_e[tid] - seg_b[tid]);
       eq_cnt[tid] = 0;
     }
     if (tid == 0) s_over = 0;
     __syncthreads();  VQS_T(1)
-    struct SegP {
-      int b, e, first, base, m;
-      unsigned pv;
-    };
     // std::partition only swaps pairs: the k-th misplaced element of the front part (from the left) with the k-th misplaced
     // element of the back part (from the right).  (A) counts, (B) both announce their positions -- the back one in slot
     // first + k, the front one in slot last - 1 - k -- and (C) exchanges the pairs, K of them a range.
     // (A) and (B) walk the array in rows of 256 elements (four consecutive ones a lane, one 16-byte LDS read): wave w owns
     // [w * chunk, (w + 1) * chunk).  A row lies inside one range almost always; then everything about the range is scalar.
     auto partition_sweep = [&](int mode) {
-      auto load_seg = [&](int sidx, bool with_counts) {
-        SegP q;
-        q.b = q.e = q.first = 0x7fffffff;
-        q.base = q.m = 0;
-        q.pv = 0;
-        if (sidx < nseg) {  // wave-uniform: kept in scalar registers
-          q.b = __builtin_amdgcn_readfirstlane(seg_b[sidx]);
-          q.e = __builtin_amdgcn_readfirstlane(seg_e[sidx]);
-          q.first = mode == 0 ? q.b : __builtin_amdgcn_readfirstlane(seg_m1[sidx]);
-          q.pv = (unsigned)__builtin_amdgcn_readfirstlane((int)seg_pv[sidx]);
-          if (with_counts) {
-            q.base = __builtin_amdgcn_readfirstlane(seg_base[sidx]);
-            q.m = __builtin_amdgcn_readfirstlane(seg_base[sidx + 1]) - q.base;
-          }
-        }
-        return q;
-      };
 #define VQS_ROW_BEGIN(with_counts)                                                   \
   const int row0 = wave * chunk + r * 256;                                           \
   if (row0 >= n) break;                                                              \
   while (row0 >= A.e && sA < nseg) {                                                 \
     A = B;                                                                           \
     sA++;                                                                            \
-    B = load_seg(sA + 1, with_counts);                                               \
+    B = load_seg(segs, sA + 1, nseg, mode, with_counts);                             \
   }                                                                                  \
   const uint4 k4 = k4_nx;                                                            \
   if (r + 1 < E4) k4_nx = *reinterpret_cast<const uint4*>(s_key + row0 + 256 + 4 * lane); /* fetched while this row is processed */ \
@@ -907,7 +727,7 @@ __global__ __launch_bounds__(1024) void k_voxel_qsort_top_lds(u64* keys_all, uns
       {  // (A) flagged elements per wave, and before every range start inside its wave
         int cnt = 0, sA = 0;
         uint4 k4_nx = *reinterpret_cast<const uint4*>(s_key + wave * chunk + 4 * lane);
-        SegP A = load_seg(0, false), B = load_seg(1, false);
+        SegP A = load_seg(segs, 0, nseg, mode, false), B = load_seg(segs, 1, nseg, mode, false);
         VQS_T(9)
 #pragma unroll 1
         for (int r = 0; r < E4; r++) {
@@ -968,7 +788,7 @@ __global__ __launch_bounds__(1024) void k_voxel_qsort_top_lds(u64* keys_all, uns
       {  // (B) announce
         int run = wave_base, sA = 0;
         uint4 k4_nx = *reinterpret_cast<const uint4*>(s_key + wave * chunk + 4 * lane);
-        SegP A = load_seg(0, true), B = load_seg(1, true);
+        SegP A = load_seg(segs, 0, nseg, mode, true), B = load_seg(segs, 1, nseg, mode, true);
         auto row_body = [&](auto whole_c, int row0, const unsigned* kk) {
           constexpr bool kWhole = decltype(whole_c)::value;
           bool f[4], in[4], inB[4];
@@ -1132,27 +952,9 @@ __global__ __launch_bounds__(1024) void k_voxel_qsort_top_lds(u64* keys_all, uns
       if (m > kEq) {
         s_over = 1;
       } else {
-        int* q = eq_pos[tid];  // sorted in place (ascending positions)
-#pragma unroll 1
-        for (int a = 1; a < m; a++) {
-          const int v = q[a];
-          int bpos = a;
-          while (bpos > 0 && q[bpos - 1] > v) {
-            q[bpos] = q[bpos - 1];
-            bpos--;
-          }
-          q[bpos] = v;
-        }
-        // k-th position of [m1, m1 + m) not holding a pivot key (from the left) <-> k-th pivot key beyond (from the right)
-        int a = 0, t = m - 1;
+        int* q = eq_pos[tid];
         [[maybe_unused]] int nsw = 0;
-#pragma unroll 1
-        for (int j = m1; j < m1 + m; j++) {
-          if (a < m && q[a] == j) {
-            a++;
-            continue;
-          }
-          const int jt = q[t--];  // >= m1 + m by counting
+        replay_second_partition(m, m1, q, [&](int j, int jt) {
           const unsigned kj = s_key[j];
           s_key[j] = s_key[jt];
           s_key[jt] = kj;
@@ -1163,7 +965,7 @@ __global__ __launch_bounds__(1024) void k_voxel_qsort_top_lds(u64* keys_all, uns
             s_val[j] = s_val[jt];
             s_val[jt] = vj;
           }
-        }
+        });
         if constexpr (kGV) {  // swap s of the loop above paired j = eq_j[s] with jt = q[m - 1 - s]; all positions are distinct
 #pragma unroll 1
           for (int s0 = 0; s0 < nsw; s0 += 4) {
@@ -1193,34 +995,12 @@ __global__ __launch_bounds__(1024) void k_voxel_qsort_top_lds(u64* keys_all, uns
       if (tid < nseg) seg_m2[tid] = seg_m1[tid] + (seg_base[tid + 1] - seg_base[tid]);
       __syncthreads();
     }
-    // children [first, middle1) and [middle2, last)
-    int child_b[2] = {0, 0}, child_e[2] = {0, 0}, nact = 0;
-    if (tid < nseg) {
-      child_b[0] = seg_b[tid];
-      child_e[0] = seg_m1[tid];
-      child_b[1] = seg_m2[tid];
-      child_e[1] = seg_e[tid];
-      for (int k = 0; k < 2; k++) nact += (child_e[k] - child_b[k] >= kLeafThreshold) ? 1 : 0;
+    {  // children [first, middle1) and [middle2, last)
+      const bool on = tid < nseg;
+      push_children(on, on ? seg_b[tid] : 0, on ? seg_m1[tid] : 0, on ? seg_m2[tid] : 0, on ? seg_e[tid] : 0, seg_b, seg_e, &s_nseg,
+                    s_wave, leaf, &s_nleaf);
     }
-    int tot_act;
-    int pos = scan_1024(nact, s_wave, &tot_act);
-    __syncthreads();
-    if (tid < nseg) {
-      for (int k = 0; k < 2; k++) {
-        const int len = child_e[k] - child_b[k];
-        if (len >= kLeafThreshold) {
-          seg_b[pos] = child_b[k];
-          seg_e[pos] = child_e[k];
-          pos++;
-        } else if (len >= 2) {
-          const int slot = atomicAdd(&s_nleaf, 1);
-          leaf[2 * slot] = (unsigned)child_b[k];
-          leaf[2 * slot + 1] = (unsigned)child_e[k];
-        }
-      }
-    }
-    if (tid == 0) s_nseg = tot_act;
-    __syncthreads();  VQS_T(7)
+    VQS_T(7)
   }
   // the keys go back as 64-bit compacted keys (k_voxel_qsort_leaf, k_voxel_reduce)
   {

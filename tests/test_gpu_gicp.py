@@ -91,6 +91,19 @@ def test_voxel_sort_permutation_against_the_compiled_reference(gpu_api, oracle, 
         assert np.array_equal(got, want), (name, int((got != want).sum()), len(k))
 
 
+def test_voxel_sort_permutation_without_the_lds_kernels(gpu_api, oracle, monkeypatch):
+    """GFS_GICP_VQS_LDS=0 on a handle of at most 20480 points: the n >= 1024 levels run in k_voxel_qsort_top_reg<20> (no other test
+    reaches that instantiation) and, for the wide-extent clouds it flags, in k_voxel_qsort_top.  One and two ranges of about 1024 keys."""
+    monkeypatch.setenv("GFS_GICP_VQS_LDS", "0")
+    reg = gpu_api.RegistrationGICP(max_points=2048)
+    cases = [c for c in _sort_cases() if 1023 <= len(c[1]) <= 2048]
+    assert len(cases) == 30
+    for name, k in cases:
+        got = reg.voxel_sort_perm(k)
+        want, _ = oracle.quick_sort_perm(k)
+        assert np.array_equal(got, want), (name, int((got != want).sum()), len(k))
+
+
 def test_wave_std_sort_is_libstdcxx_std_sort(gpu_api, oracle):
     """csrc/wave_std_sort.hpp (one wave, LDS) against std::sort itself — the oracle's quick_sort_omp hands ranges below 1024
     elements to std::sort (util/sort_omp.hpp:61) —: the permutation, not just the order, on keys with many ties, sorted / reversed
