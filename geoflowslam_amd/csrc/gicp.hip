@@ -1150,8 +1150,10 @@ __device__ __forceinline__ void knn_search_cube(const double4* __restrict__ p, c
 }
 
 // covariance of the k nearest neighbours, regularised: cov := V diag(1e-3, 1, 1) V^T  (util/normal_estimation.hpp:66-92)
-__device__ __forceinline__ void knn_write_cov(const TopK<10>& best, int kk, const double4* __restrict__ p, double* __restrict__ out) {
-  const int n = min(best.found, kk);
+// id: the neighbours in the order (exact squared distance, then lower index), `found` of them; the sums are folded in that order
+__device__ __forceinline__ void knn_write_cov(const int (&id)[10], int found, int kk, const double4* __restrict__ p,
+                                              double* __restrict__ out) {
+  const int n = min(found, kk);
   if (n < 5) {  // NormalCovarianceSetter::set_invalid: cov = diag(1,1,1,0)
     out[0] = 1;
     out[1] = 0;
@@ -1165,7 +1167,7 @@ __device__ __forceinline__ void knn_write_cov(const TopK<10>& best, int kk, cons
 #pragma unroll
   for (int k = 0; k < 10; k++) {
     if (k < n) {
-      const double4 t = p[best.id[k]];
+      const double4 t = p[id[k]];
       sp[0] += t.x;
       sp[1] += t.y;
       sp[2] += t.z;
@@ -1197,63 +1199,6 @@ __device__ __forceinline__ void knn_write_cov(const TopK<10>& best, int kk, cons
       for (int k = 0; k < 3; k++) acc += (V[3 * k + r] * dv[k]) * V[3 * k + cc];
       out[o++] = acc;
     }
-}
-
-// scans the run [j0, j1) of candidate points, four loads in flight
-// (bound: candidates farther than that cannot belong to the result -- k nearer ones are known to exist -- and skip the insertion)
-__device__ __forceinline__ void knn_scan_run(const double4* __restrict__ p, const double4& q, int j0, int j1, TopK<10>& loc,
-                                             double bound = 1.79769313486231570e308) {
-  for (int j = j0; j < j1; j += 4) {  // four loads in flight
-    const double4 t0 = p[j], t1 = p[min(j + 1, j1 - 1)], t2 = p[min(j + 2, j1 - 1)], t3 = p[min(j + 3, j1 - 1)];
-    {
-      const double ddx = t0.x - q.x, ddy = t0.y - q.y, ddz = t0.z - q.z, d = ddx * ddx + ddy * ddy + ddz * ddz;
-      if (d <= bound) loc.push(j, d);
-    }
-    if (j + 1 < j1) {
-      const double ddx = t1.x - q.x, ddy = t1.y - q.y, ddz = t1.z - q.z, d = ddx * ddx + ddy * ddy + ddz * ddz;
-      if (d <= bound) loc.push(j + 1, d);
-    }
-    if (j + 2 < j1) {
-      const double ddx = t2.x - q.x, ddy = t2.y - q.y, ddz = t2.z - q.z, d = ddx * ddx + ddy * ddy + ddz * ddz;
-      if (d <= bound) loc.push(j + 2, d);
-    }
-    if (j + 3 < j1) {
-      const double ddx = t3.x - q.x, ddy = t3.y - q.y, ddz = t3.z - q.z, d = ddx * ddx + ddy * ddy + ddz * ddz;
-      if (d <= bound) loc.push(j + 3, d);
-    }
-  }
-}
-
-// the same over up to four runs (begin, length) concatenated into one lane-private sequence (every lane walks only ITS surviving cells, four loads in flight)
-__device__ __forceinline__ void knn_scan_runs4(const double4* __restrict__ p, const double4& q, int b0, int l0, int b1, int l1, int b2,
-                                               int l2, int b3, int l3, TopK<10>& loc) {
-  const int c1 = l0, c2 = c1 + l1, c3 = c2 + l2, total = c3 + l3;
-  const int o0 = b0, o1 = b1 - c1, o2 = b2 - c2, o3 = b3 - c3;
-  for (int v = 0; v < total; v += 4) {
-    int j[4];
-#pragma unroll
-    for (int u = 0; u < 4; u++) {
-      const int vv = min(v + u, total - 1);
-      j[u] = vv + (vv < c1 ? o0 : vv < c2 ? o1 : vv < c3 ? o2 : o3);
-    }
-    const double4 t0 = p[j[0]], t1 = p[j[1]], t2 = p[j[2]], t3 = p[j[3]];
-    {
-      const double ddx = t0.x - q.x, ddy = t0.y - q.y, ddz = t0.z - q.z;
-      loc.push(j[0], ddx * ddx + ddy * ddy + ddz * ddz);
-    }
-    if (v + 1 < total) {
-      const double ddx = t1.x - q.x, ddy = t1.y - q.y, ddz = t1.z - q.z;
-      loc.push(j[1], ddx * ddx + ddy * ddy + ddz * ddz);
-    }
-    if (v + 2 < total) {
-      const double ddx = t2.x - q.x, ddy = t2.y - q.y, ddz = t2.z - q.z;
-      loc.push(j[2], ddx * ddx + ddy * ddy + ddz * ddz);
-    }
-    if (v + 3 < total) {
-      const double ddx = t3.x - q.x, ddy = t3.y - q.y, ddz = t3.z - q.z;
-      loc.push(j[3], ddx * ddx + ddy * ddy + ddz * ddz);
-    }
-  }
 }
 
 __global__ __launch_bounds__(kKnnThreads) void k_knn_cov(const double4* __restrict__ pts, const u64* __restrict__ ucell,
@@ -1323,34 +1268,79 @@ __global__ __launch_bounds__(kKnnThreads) void k_knn_cov(const double4* __restri
     hard_d[(size_t)c * 2 * P + slot] = kth_for_deferred;
     return;
   }
-  TopK<10> res;  // the neighbours in key order (distance, then index)
-  res.found = 0;
+  int ids[10], found = 0;  // the neighbours in key order (distance, then index)
 #pragma unroll
   for (int k = 0; k < 10; k++) {
-    res.id[k] = best.k[k] < TopKey11::kNone ? TopKey11::index(best.k[k]) : -1;
-    res.found += best.k[k] < TopKey11::kNone ? 1 : 0;
+    ids[k] = best.k[k] < TopKey11::kNone ? TopKey11::index(best.k[k]) : -1;
+    found += best.k[k] < TopKey11::kNone ? 1 : 0;
   }
-  knn_write_cov(res, kk, p, cov6 + ((size_t)c * P + i) * 6);
+  knn_write_cov(ids, found, kk, p, cov6 + ((size_t)c * P + i) * 6);
 }
 
-// k_knn_cov_far: the queries whose k-th neighbour is farther than one cell (sparse regions, a few %
-// of the points).  A group of kFarLanes = 16 lanes per deferred query, 16 queries per workgroup and round.  Search,
-// group-wide: the cells (small probes) or rows (big probes) of the ring-r cube are spread over the group's lanes (a
-// lone thread would walk them as one long dependent chain; a whole wave per query leaves the chip latency-bound on the
-// per-query fixed costs), every lane keeps the top-k of its share, and the k global winners are extracted by k
-// group-wide arg-min rounds over the lanes' list heads (ties: lower point index).  The covariance / eigen step (scalar per query)
-// then runs for the workgroup's queries side by side.
-// It takes k_knn_cov's list (front of hard_list, counter ginfo[7]) with ONE r = 2 probe; a query that the probe does not certify
-// (k-th distance <= r cells, or the probe covers the whole cloud), or whose bound asks for more than two rings -- the really isolated
-// points, ~1 % of the list, but thousands of candidates each -- is deferred to k_knn_cov_far_wg (back of hard_list, counter
-// far2_count) so that it does not hold up the other queries of its workgroup.
+// The deferred passes leave a query's LIST -- its neighbours' indices in the order (exact squared distance, then lower index) and
+// their count: eleven ints -- in the query's own 48-byte slot of cov6, and k_knn_cov_settle turns every list into the covariance
+// afterwards, a thread a query at full lane width (in the passes themselves one lane of 16, or one thread of 256, held the list).
+__device__ __forceinline__ void knn_store_list(double* __restrict__ slot, int k, int v) { reinterpret_cast<int*>(slot)[k] = v; }
+
+// what lanes of one wave wrote to LDS is read by other lanes of the same wave (no barrier: only some groups of a wave may be here)
+__device__ __forceinline__ void wave_lds_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// k_knn_cov_far: the queries whose k-th neighbour is farther than one cell (sparse regions, a few % of the points).  A group of
+// kFarLanes = 16 lanes per deferred query, 16 queries per workgroup and round; the groups share nothing, so there is no barrier.
+// It takes k_knn_cov's list (front of hard_list, counter ginfo[7]) with ONE r = 2 probe:
+//   rows      the cube of +-2 cells, clamped to the occupied box, is at most 25 rows (y, z): lane gl looks up rows gl and gl + 16, both
+//             in flight together.  A query that knows k candidates (Dk: they lie within sqrt(Dk)) skips the rows beyond sqrt(Dk) and
+//             cuts the others' x range to what can lie within it (the rule of k_knn_cov_far_wg); one that does not takes all of them.
+//   numbering a group-wide exclusive scan of the 32 run lengths; (begin, prefix) per row in the group's LDS; the candidates are numbered
+//             through -- in ascending point index, rows in (z, y) order -- and lane gl takes candidates gl, gl + 16, ..., four loads
+//             in flight.
+//   survivors a candidate with d <= bound (bound = Dk at first; every candidate when there is none) is appended as (d, j) to the
+//             group's list in LDS, by ballot compaction.  A bounded query has the ten of its 27 cells and the few shell points that
+//             are nearer: 10 - 15 survivors.  When a batch would not fit the kFarCap entries, the ten best are kept at the front and
+//             the bound drops to the tenth's distance: any number of candidates is handled here.
+//   selection rank(s) = number of entries t with d_t < d_s || (d_t == d_s && j_t < j_s): a count over the list instead of a sorted
+//             insertion per candidate in every lane.  Ranks 0 .. 9 are the list.
+// A query that the probe certifies (k-th distance <= 2 cells, or the probe covers the whole cloud) gets its list stored; one that it
+// does not, or whose bound asks for more than two rings -- the really isolated points, ~1 % of the list, but thousands of candidates
+// each -- is handed to k_knn_cov_far_wg (back of hard_list, counter far2_count) so that it does not hold up its workgroup.
 // hard_list / hard_d hold 2 P slots a cloud, the first list in the lower half, the second from the top of the upper half down: in a
 // sparse cloud EVERY point is on both lists (one buffer of P slots let the second list overwrite unread entries of the first as
 // soon as the two held more than P queries together: wrong neighbours for those, tests/test_gpu_gicp_geometry.py).
-// (three waves a SIMD: left alone the kernel takes 205 VGPRs = two waves, and it waits on dependent cell lookups — 1.24 -> 0.99 ms
-// per 1 024 clouds with the cap, a 124-byte spill included; four waves: no further gain)
 constexpr int kFarLanes = 16;
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))) void k_knn_cov_far(const double4* __restrict__ pts, const u64* __restrict__ ucell,
+constexpr int kFarCap = 64;  // survivors a group keeps (four a lane for the ranking)
+constexpr int kFarRows = 32;  // two rows a lane: the 25 rows of the r = 2 cube
+
+// ranks the n <= kFarCap entries of a group's list and moves ranks 0 .. 9 to its front, in order (n is the same in all 16 lanes)
+__device__ __forceinline__ void far_keep_best(double* __restrict__ sd, int* __restrict__ sj, int n, int gl) {
+  wave_lds_sync();
+  double d0 = 0, d1 = 0, d2 = 0, d3 = 0;
+  int j0 = 0, j1 = 0, j2 = 0, j3 = 0, r0 = 0, r1 = 0, r2 = 0, r3 = 0;
+  const int s0 = gl, s1 = gl + kFarLanes, s2 = gl + 2 * kFarLanes, s3 = gl + 3 * kFarLanes;
+  if (s0 < n) d0 = sd[s0], j0 = sj[s0];
+  if (s1 < n) d1 = sd[s1], j1 = sj[s1];
+  if (s2 < n) d2 = sd[s2], j2 = sj[s2];
+  if (s3 < n) d3 = sd[s3], j3 = sj[s3];
+  for (int t = 0; t < n; t++) {  // (all lanes read the same entry: a broadcast)
+    const double dt = sd[t];
+    const unsigned jt = (unsigned)sj[t];
+    r0 += (dt < d0 || (dt == d0 && jt < (unsigned)j0)) ? 1 : 0;
+    r1 += (dt < d1 || (dt == d1 && jt < (unsigned)j1)) ? 1 : 0;
+    r2 += (dt < d2 || (dt == d2 && jt < (unsigned)j2)) ? 1 : 0;
+    r3 += (dt < d3 || (dt == d3 && jt < (unsigned)j3)) ? 1 : 0;
+  }
+  wave_lds_sync();  // every lane has read before any lane writes
+  if (s0 < n && r0 < 10) sd[r0] = d0, sj[r0] = j0;
+  if (s1 < n && r1 < 10) sd[r1] = d1, sj[r1] = j1;
+  if (s2 < n && r2 < 10) sd[r2] = d2, sj[r2] = j2;
+  if (s3 < n && r3 < 10) sd[r3] = d3, sj[r3] = j3;
+  wave_lds_sync();
+}
+
+__global__ __launch_bounds__(256) void k_knn_cov_far(const double4* __restrict__ pts, const u64* __restrict__ ucell,
                                                      const unsigned* __restrict__ ubegin, const int* __restrict__ n_ucell,
                                                      const int* __restrict__ m_counts, const int* __restrict__ bbox,
                                                      const unsigned* __restrict__ grid, const int* __restrict__ ginfo,
@@ -1358,9 +1348,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))) voi
                                                      int* __restrict__ far2_count, int nchunks, int npairs, int P, GicpParams prm,
                                                      double* __restrict__ cov6) {
   constexpr int kQueries = 256 / kFarLanes;
-  __shared__ int s_ids[kQueries][10];
-  __shared__ int s_found[kQueries];
-  __shared__ int s_query[kQueries];
+  __shared__ int s_beg[kQueries][kFarRows], s_pre[kQueries][kFarRows + 1];
+  __shared__ double s_d[kQueries][kFarCap];
+  __shared__ int s_j[kQueries][kFarCap];
   int pair, which, chunk;
   if (!xcd_pair_map(nchunks, npairs, 2, &pair, &which, &chunk)) return;
   if (prm.only >= 0 && which != prm.only) return;
@@ -1380,121 +1370,193 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))) voi
   const int bx0 = bbox[6 * c], by0 = bbox[6 * c + 1], bz0 = bbox[6 * c + 2], bx1 = bbox[6 * c + 3], by1 = bbox[6 * c + 4],
             bz1 = bbox[6 * c + 5];
   const int gl = threadIdx.x % kFarLanes, grp = threadIdx.x / kFarLanes;
-  for (int base = chunk * kQueries; base < nhard; base += nchunks * kQueries) {  // uniform per workgroup
-    const int h = base + grp;
-    if (gl == 0) s_query[grp] = -1;
-    if (h < nhard) {
-      const int i = (int)list[h];
-      // squared distance within which the k nearest are known to lie (k_knn_cov found k candidates), or "infinite"
-      const double Dk = list_d[h];
-      const bool bounded = Dk < 1.0e300;
-      const double4 q = p[i];
-      const int cx = fast_floor_d(q.x * prm.inv_cell) + kCoordOffset, cy = fast_floor_d(q.y * prm.inv_cell) + kCoordOffset,
-                cz = fast_floor_d(q.z * prm.inv_cell) + kCoordOffset;
-      // lower bound of the distance from q to the cells d steps away along one axis (a hair conservative)
-      const double ux = q.x * prm.inv_cell - (double)(cx - kCoordOffset), uy = q.y * prm.inv_cell - (double)(cy - kCoordOffset),
-                   uz = q.z * prm.inv_cell - (double)(cz - kCoordOffset);
-      auto axis_lb = [&](int d, double u) {
-        const double v = d == 0 ? 0.0 : d > 0 ? (double)d - u : u - (double)(d + 1);
-        return fmax(v - 1e-9, 0.0) * prm.cell;
-      };
-      TopK<10> best;  // merged result, identical in all lanes of the group
-      bool done = false;
-      double Dnext = Dk;  // bound handed to the next pass
-      // bounded: one probe of ceil(sqrt(Dk) / cell) rings is final, and cells (rows) farther than sqrt(Dk) are skipped
-      int r = bounded ? max((int)ceil(sqrt(Dk) * prm.inv_cell), 2) : 2;
-      if (r > 2) r = -1;  // beyond this pass: hand over at once
-      // (r is 2 or -1 here and the body always ends in `break`: the loop and the row-unit arms of larger r keep the form they had
-      // with R0 as a template parameter, so that the generated code stays the earlier <16, 2, true> instance's)
-      for (; r > 0;) {
-        TopK<10> loc;
-        loc.init();
-        // cells outside the occupied-cell bounding box are empty: clamp the probe to it
-        const int x0 = max(cx - r, bx0), x1 = min(cx + r, bx1), y0 = max(cy - r, by0), y1 = min(cy + r, by1),
-                  z0 = max(cz - r, bz0), z1 = min(cz + r, bz1);
-        const int nx = x1 - x0 + 1, ny = y1 - y0 + 1, nrows = ny * (z1 - z0 + 1);
-        const int upr = nx * nrows <= 128 ? nx : 1;  // work units per row: single cells for the r = 2 probe, whole rows otherwise
-        const int nunits = nrows * upr;
-        for (int t = gl; t < nunits; t += 2 * kFarLanes) {  // two units per trip: both lookups are in flight together
-          const int ta = t, tb = min(t + kFarLanes, nunits - 1);
-          const int rowa = ta / upr, xa = ta - rowa * upr, rowb = tb / upr, xb = tb - rowb * upr;
-          const int ya = y0 + rowa % ny, za = z0 + rowa / ny, yb = y0 + rowb % ny, zb = z0 + rowb / ny;
-          bool usea = true, useb = t + kFarLanes < nunits;
-          if (bounded) {
-            const double la = axis_lb(ya - cy, uy), lza = axis_lb(za - cz, uz), lxa = upr == 1 ? 0.0 : axis_lb(x0 + xa - cx, ux);
-            const double lb = axis_lb(yb - cy, uy), lzb = axis_lb(zb - cz, uz), lxb = upr == 1 ? 0.0 : axis_lb(x0 + xb - cx, ux);
-            usea = la * la + lza * lza + lxa * lxa <= Dk;
-            useb = useb && lb * lb + lzb * lzb + lxb * lxb <= Dk;
-          }
-          int ja0 = 0, ja1 = 0, jb0 = 0, jb1 = 0;
-          if (usea) row_range(gi, G, uc, ub, nu, upr == 1 ? x0 : x0 + xa, upr == 1 ? x1 : x0 + xa, ya, za, &ja0, &ja1);
-          if (useb) row_range(gi, G, uc, ub, nu, upr == 1 ? x0 : x0 + xb, upr == 1 ? x1 : x0 + xb, yb, zb, &jb0, &jb1);
-          knn_scan_run(p, q, ja0, ja1, loc, Dk);
-          knn_scan_run(p, q, jb0, jb1, loc, Dk);
-        }
-        best.init();
-#pragma unroll
-        for (int k = 0; k < 10; k++) {
-          const double hd = loc.d[0];
-          const int hj = loc.id[0];
-          double bd = hd;
-          int bj = hj;
-#pragma unroll
-          for (int ofs = kFarLanes / 2; ofs > 0; ofs >>= 1) {
-            const double od = __shfl_xor(bd, ofs, kFarLanes);
-            const int oj = __shfl_xor(bj, ofs, kFarLanes);
-            if (od < bd || (od == bd && (unsigned)oj < (unsigned)bj)) {
-              bd = od;
-              bj = oj;
-            }
-          }
-          if (bj >= 0) {
-            best.d[k] = bd;
-            best.id[k] = bj;
-            best.found = k + 1;
-          }
-          if (hj == bj && bj >= 0) {  // the owning lane pops its head
-#pragma unroll
-            for (int e = 0; e < 9; e++) {
-              loc.d[e] = loc.d[e + 1];
-              loc.id[e] = loc.id[e + 1];
-            }
-            loc.d[9] = 1.79769313486231570e308;
-            loc.id[9] = -1;
-          }
-        }
-        const double reach = (double)r * prm.cell;
-        const bool covers_all = cx - r <= bx0 && cx + r >= bx1 && cy - r <= by0 && cy + r >= by1 && cz - r <= bz0 && cz + r >= bz1;
-        const double kth = best.nth(max(want - 1, 0));
-        if ((best.found >= want && kth <= reach * reach) || covers_all || r > kCoordMask) {
-          done = true;
-          break;
-        }
-        if (best.found >= want) Dnext = fmin(Dnext, kth);  // (k candidates are known: the true k nearest lie within sqrt(kth))
-        break;  // one probe: what it did not settle goes to k_knn_cov_far_wg
-      }
+  int* sb = s_beg[grp];
+  int* sp = s_pre[grp];
+  double* sd = s_d[grp];
+  int* sj = s_j[grp];
+  for (int h = chunk * kQueries + grp; h < nhard; h += nchunks * kQueries) {  // (a group's own loop: nothing below waits for another group)
+    const int i = (int)list[h];
+    // squared distance within which the k nearest are known to lie (k_knn_cov found k candidates), or "infinite"
+    const double Dk = list_d[h];
+    const bool bounded = Dk < 1.0e300;
+    // bounded: one probe of ceil(sqrt(Dk) / cell) rings is final; more than two rings are beyond this pass: hand over at once
+    if (bounded && (int)ceil(sqrt(Dk) * prm.inv_cell) > 2) {
       if (gl == 0) {
-        if (done) {
+        const int slot = atomicAdd(&far2_count[c], 1);
+        list[2 * P - 1 - slot] = (unsigned)i;
+        list_d[2 * P - 1 - slot] = Dk;
+      }
+      continue;
+    }
+    const double4 q = p[i];
+    const int cx = fast_floor_d(q.x * prm.inv_cell) + kCoordOffset, cy = fast_floor_d(q.y * prm.inv_cell) + kCoordOffset,
+              cz = fast_floor_d(q.z * prm.inv_cell) + kCoordOffset;
+    const double uy = q.y * prm.inv_cell - (double)(cy - kCoordOffset), uz = q.z * prm.inv_cell - (double)(cz - kCoordOffset);
+    // lower bound of the distance from q to the cells d steps away along one axis (a hair conservative)
+    auto axis_lb = [&](int d, double u) {
+      const double v = d == 0 ? 0.0 : d > 0 ? (double)d - u : u - (double)(d + 1);
+      return fmax(v - 1e-9, 0.0) * prm.cell;
+    };
+    constexpr int r = 2;
+    // cells outside the occupied-cell bounding box are empty: clamp the probe to it
+    const int x0 = max(cx - r, bx0), x1 = min(cx + r, bx1), y0 = max(cy - r, by0), y1 = min(cy + r, by1), z0 = max(cz - r, bz0),
+              z1 = min(cz + r, bz1);
+    const int ny = y1 - y0 + 1, nrows = ny * (z1 - z0 + 1);  // <= 25
+    // (a) this lane's two rows: both look-ups before either is used
+    int beg[2] = {0, 0}, len[2] = {0, 0};
 #pragma unroll
-          for (int k = 0; k < 10; k++) s_ids[grp][k] = best.id[k];
-          s_found[grp] = best.found;
-          s_query[grp] = i;
-        } else {
-          const int slot = atomicAdd(&far2_count[c], 1);
-          list[2 * P - 1 - slot] = (unsigned)i;
-          list_d[2 * P - 1 - slot] = Dnext;
+    for (int u = 0; u < 2; u++) {
+      const int t = gl + u * kFarLanes;
+      if (t < nrows) {
+        const int y = y0 + t % ny, z = z0 + t / ny;
+        int xa = x0, xb = x1;
+        bool use = true;
+        if (bounded) {
+          const double ly = axis_lb(y - cy, uy), lz = axis_lb(z - cz, uz), rest = Dk - ly * ly - lz * lz;
+          use = rest >= 0.0;
+          if (use) {  // x cells farther than sqrt(rest): an integer bound one cell on the safe side
+            const int rx = (int)ceil(sqrt(rest) * prm.inv_cell) + 1;
+            xa = max(xa, cx - rx);
+            xb = min(xb, cx + rx);
+          }
+        }
+        if (use && xa <= xb) {
+          int j0, j1;
+          row_range(gi, G, uc, ub, nu, xa, xb, y, z, &j0, &j1);
+          beg[u] = j0;
+          len[u] = j1 - j0;
         }
       }
     }
-    __syncthreads();
-    if (threadIdx.x < kQueries && s_query[threadIdx.x] >= 0) {
-      TopK<10> res;
-      res.found = s_found[threadIdx.x];
+    // (b) the candidates numbered through: exclusive scan of the 32 run lengths (rows 0 .. 15, then 16 .. 31)
+    int inc0 = len[0], inc1 = len[1];
 #pragma unroll
-      for (int k = 0; k < 10; k++) res.id[k] = s_ids[threadIdx.x][k];
-      knn_write_cov(res, kk, p, cov6 + ((size_t)c * P + s_query[threadIdx.x]) * 6);
+    for (int ofs = 1; ofs < kFarLanes; ofs <<= 1) {
+      const int v0 = __shfl_up(inc0, ofs, kFarLanes), v1 = __shfl_up(inc1, ofs, kFarLanes);
+      if (gl >= ofs) {
+        inc0 += v0;
+        inc1 += v1;
+      }
     }
-    __syncthreads();
+    const int tot0 = __shfl(inc0, kFarLanes - 1, kFarLanes), total = tot0 + __shfl(inc1, kFarLanes - 1, kFarLanes);
+    sb[gl] = beg[0];
+    sp[gl] = inc0 - len[0];
+    sb[gl + kFarLanes] = beg[1];
+    sp[gl + kFarLanes] = tot0 + inc1 - len[1];
+    if (gl == 0) sp[kFarRows] = total;
+    wave_lds_sync();
+    // (c) survivors: lane gl takes candidates gl, gl + 16, ... four at a time
+    double bound = Dk;
+    int n = 0;  // entries of the group's list (the same in all its lanes)
+    int rr = 0, vend = sp[1];
+    for (int v0 = 0; v0 < total; v0 += 4 * kFarLanes) {
+      int j[4];
+      bool on[4];
+#pragma unroll
+      for (int u = 0; u < 4; u++) {
+        const int vv = v0 + u * kFarLanes + gl;
+        on[u] = vv < total;
+        j[u] = 0;
+        if (on[u]) {
+          while (vv >= vend) {  // (vv < total = sp[kFarRows]: rr stops at a row below kFarRows)
+            rr++;
+            vend = sp[rr + 1];
+          }
+          j[u] = sb[rr] + (vv - sp[rr]);
+        }
+      }
+      const double4 t0 = ld_pt(p, j[0]), t1 = ld_pt(p, j[1]), t2 = ld_pt(p, j[2]), t3 = ld_pt(p, j[3]);
+      double d[4];
+      {
+        const double ddx = t0.x - q.x, ddy = t0.y - q.y, ddz = t0.z - q.z;
+        d[0] = ddx * ddx + ddy * ddy + ddz * ddz;
+      }
+      {
+        const double ddx = t1.x - q.x, ddy = t1.y - q.y, ddz = t1.z - q.z;
+        d[1] = ddx * ddx + ddy * ddy + ddz * ddz;
+      }
+      {
+        const double ddx = t2.x - q.x, ddy = t2.y - q.y, ddz = t2.z - q.z;
+        d[2] = ddx * ddx + ddy * ddy + ddz * ddz;
+      }
+      {
+        const double ddx = t3.x - q.x, ddy = t3.y - q.y, ddz = t3.z - q.z;
+        d[3] = ddx * ddx + ddy * ddy + ddz * ddz;
+      }
+#pragma unroll
+      for (int u = 0; u < 4; u++) {
+        const bool pass = on[u] && d[u] <= bound;
+        const unsigned gm = (unsigned)(__ballot(pass) >> (threadIdx.x & 48)) & 0xffffu;  // this group's lanes
+        const int cnt = __popc(gm);
+        if (cnt == 0) continue;  // (the same in all lanes of the group)
+        if (n + cnt > kFarCap) {  // the batch does not fit: keep the ten best so far (n > kFarCap - 16 >= 10), tighten the bound
+          far_keep_best(sd, sj, n, gl);
+          n = 10;
+          bound = fmin(bound, sd[9]);
+        }
+        if (pass) {
+          const int pos = n + __popc(gm & ((1u << gl) - 1u));
+          sd[pos] = d[u];
+          sj[pos] = j[u];
+        }
+        n += cnt;
+      }
+    }
+    // (d) the list, and whether the probe settles the query
+    far_keep_best(sd, sj, n, gl);
+    const int found = min(n, 10);
+    const double reach = (double)r * prm.cell;
+    const bool covers_all = cx - r <= bx0 && cx + r >= bx1 && cy - r <= by0 && cy + r >= by1 && cz - r <= bz0 && cz + r >= bz1;
+    const double kth = found >= want ? sd[max(want - 1, 0)] : 1.79769313486231570e308;
+    if ((found >= want && kth <= reach * reach) || covers_all) {
+      double* slot = cov6 + ((size_t)c * P + i) * 6;
+      if (gl < 10) knn_store_list(slot, gl, gl < found ? sj[gl] : -1);
+      if (gl == 10) knn_store_list(slot, 10, found);
+    } else if (gl == 0) {  // what one probe did not settle goes to k_knn_cov_far_wg
+      const int slot = atomicAdd(&far2_count[c], 1);
+      list[2 * P - 1 - slot] = (unsigned)i;
+      // (k candidates are known: the true k nearest lie within sqrt(kth))
+      list_d[2 * P - 1 - slot] = found >= want ? fmin(Dk, kth) : Dk;
+    }
+    wave_lds_sync();  // (the group's tables are rewritten by its next query)
+  }
+}
+
+// k_knn_cov_settle: every query k_knn_cov deferred (front of hard_list, counter ginfo[7]) has its list in its cov6 slot by now, from
+// k_knn_cov_far or k_knn_cov_far_wg: a thread a query reads it and writes the covariance over it.  The slot holds whatever the call
+// before left there until a pass stores a list, so a slot that is no list -- a count outside 0 .. 10, an index outside the cloud --
+// is not followed: the query gets the invalid-normal covariance, which the tests see.
+constexpr int kSettleThreads = 64;
+__global__ __launch_bounds__(kSettleThreads) void k_knn_cov_settle(const double4* __restrict__ pts, const int* __restrict__ m_counts,
+                                                                   const int* __restrict__ ginfo, const unsigned* __restrict__ hard_list,
+                                                                   int nchunks, int npairs, int P, GicpParams prm,
+                                                                   double* __restrict__ cov6) {
+  int pair, which, chunk;
+  if (!xcd_pair_map(nchunks, npairs, 2, &pair, &which, &chunk)) return;
+  if (prm.only >= 0 && which != prm.only) return;
+  const int c = 2 * pair + which;
+  const int nhard = ginfo[8 * c + 7];
+  if (chunk * kSettleThreads >= nhard) return;
+  const int m = m_counts[c];
+  const double4* p = pts + (size_t)c * P;
+  const unsigned* list = hard_list + (size_t)c * 2 * P;
+  const int kk = min(prm.k_neighbors, 10);
+  for (int h = chunk * kSettleThreads + threadIdx.x; h < nhard; h += nchunks * kSettleThreads) {
+    const unsigned i = list[h];
+    if (i >= (unsigned)m) continue;
+    double* slot = cov6 + ((size_t)c * P + i) * 6;
+    const int4 a = reinterpret_cast<const int4*>(slot)[0], b = reinterpret_cast<const int4*>(slot)[1],
+               e = reinterpret_cast<const int4*>(slot)[2];
+    int ids[10] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w, e.x, e.y};
+    int found = e.z;
+    bool ok = (unsigned)found <= 10u;
+#pragma unroll
+    for (int k = 0; k < 10; k++) {
+      const bool used = k < min(found, kk);
+      ok = ok && (!used || (unsigned)ids[k] < (unsigned)m);
+    }
+    if (!ok) found = 0;
+    knn_write_cov(ids, found, kk, p, slot);
   }
 }
 
@@ -1506,7 +1568,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))) voi
 // already (Dk: k_knn_cov / the r = 2 pass found k points within sqrt(Dk)) needs ONE probe of ceil(sqrt(Dk) / cell) rings and
 // only candidates with d <= Dk can belong to the result, so the sorted insertion runs for those alone.  Per thread a top-k in
 // visiting order = ascending point index (rows are walked in (z, y) order, points are sorted by (z, y, x)); the k winners come
-// out of wave arg-min rounds and a 4-list merge, ties to the lower point index.
+// out of wave arg-min rounds and a 4-list merge, ties to the lower point index.  Thread 0 stores the list in the query's covariance
+// slot (k_knn_cov_settle makes the covariance of it); a workgroup whose cloud handed it no query -- nearly nine in ten -- leaves
+// before it loads anything else of the cloud.
 // ------------------------------------------------------------------------------------------------
 constexpr int kFarWgRows = 1024;  // rows of one chunk of the probe (begin, prefix) in LDS
 
@@ -1525,6 +1589,8 @@ __global__ __launch_bounds__(256) void k_knn_cov_far_wg(const double4* __restric
   if (!xcd_pair_map(nchunks, npairs, 2, &pair, &which, &chunk)) return;
   if (prm.only >= 0 && which != prm.only) return;
   const int c = 2 * pair + which;
+  const int nhard = far2_count[c];
+  if (chunk >= nhard) return;  // (nearly nine workgroups in ten: before the cloud's other loads)
   const int m = m_counts[c];
   const unsigned* G = grid + (size_t)c * (kGridCap + 1);
   const int* gi = ginfo + 8 * c;
@@ -1534,7 +1600,6 @@ __global__ __launch_bounds__(256) void k_knn_cov_far_wg(const double4* __restric
   const unsigned* list = hard_list + (size_t)c * 2 * P;
   const double* list_d = hard_d + (size_t)c * 2 * P;
   const int nu = n_ucell[c];
-  const int nhard = far2_count[c];
   const int kk = min(prm.k_neighbors, 10);
   const int want = min(kk, m);
   const int bx0 = bbox[6 * c], by0 = bbox[6 * c + 1], bz0 = bbox[6 * c + 2], bx1 = bbox[6 * c + 3], by1 = bbox[6 * c + 4],
@@ -1721,7 +1786,12 @@ __global__ __launch_bounds__(256) void k_knn_cov_far_wg(const double4* __restric
       __syncthreads();  // (s_md / s_mi are rewritten by the next probe or query)
       if (done) break;
     }
-    if (tid == 0) knn_write_cov(best, kk, p, cov6 + ((size_t)c * P + i) * 6);
+    if (tid == 0) {  // the list into the query's slot: k_knn_cov_settle turns it into the covariance
+      double* slot = cov6 + ((size_t)c * P + i) * 6;
+#pragma unroll
+      for (int k = 0; k < 10; k++) knn_store_list(slot, k, best.id[k]);
+      knn_store_list(slot, 10, best.found);
+    }
   }
 }
 
@@ -3172,6 +3242,10 @@ static int gicp_attempt(gfs_gicp* h, const void* dev_target, const void* dev_nt,
   GFS_LAUNCH("k_knn_cov_far_wg", k_knn_cov_far_wg, dim3(xcd_grid(far2_chunks, B, 2)), dim3(256), 0, s, h->d_pts.p, h->d_ucell.p,
              h->d_ubegin.p, h->d_nucell.p, h->d_m.p, h->d_bbox.p, h->d_grid.p, h->d_ginfo.p, h->d_hard.p, h->d_hard_d.p,
              h->d_far2.p, far2_chunks, B, P, prm, h->d_cov6.p);
+  // the lists the two passes left in the deferred queries' slots -> covariances (a thread a query; a few hundred queries a cloud)
+  const int settle_chunks = std::max(1, std::min(8, gfs::div_up(npts, kSettleThreads)));
+  GFS_LAUNCH("k_knn_cov_settle", k_knn_cov_settle, dim3(xcd_grid(settle_chunks, B, 2)), dim3(kSettleThreads), 0, s, h->d_pts.p, h->d_m.p,
+             h->d_ginfo.p, h->d_hard.p, settle_chunks, B, P, prm, h->d_cov6.p);
   // ---- LevenbergMarquardtOptimizer::optimize: device state machine, host polls the done counter
   GFS_LAUNCH("k_gicp_init", k_gicp_init, dim3(gfs::div_up(B, 64)), dim3(64), 0, s, h->d_state.p, h->hd_initT, B,
              prm.max_iterations, h->d_ndone.p, h->d_sync.p);
