@@ -68,6 +68,11 @@ class LbaTrial(C.Structure):  # gfs_test_lba_trial (include/gfs_abi_test.h)
                 ("lambda_", C.c_double), ("scale", C.c_double), ("solve_ok", C.c_int32)]
 
 
+class GbaInfo(C.Structure):  # gfs_gba_info (include/gfs_abi.h)
+    _fields_ = [("n_free", C.c_int32), ("panel_rows", C.c_int32), ("panels", C.c_int32), ("block_pairs", C.c_int64),
+                ("contributions", C.c_int64), ("system_bytes", C.c_int64), ("trials", C.c_int32), ("launches", C.c_int32)]
+
+
 class LbaLidar(C.Structure):
     _fields_ = [("map", C.c_void_p), ("pose_local", C.c_void_p), ("matches_inliers", C.c_void_p), ("cloud_begin", C.c_void_p),
                 ("cloud", C.c_void_p), ("two_camera", C.c_int32)]
@@ -586,6 +591,8 @@ ABI_SYMBOLS = [
     "gfs_lba_create", "gfs_lba_destroy", "gfs_lba_solve", "gfs_lba_solve_bool", "gfs_lba_linearize", "gfs_lba_batch_create", "gfs_lba_batch_destroy",
     "gfs_lba_solve_batch", "gfs_lba_lidar_reserve", "gfs_lba_solve_lidar", "gfs_lba_solve_lidar_bool", "gfs_lba_linearize_lidar",
     "gfs_lba_fetch_lidar_edges", "gfs_test_lba_stop_at_look", "gfs_test_lba_last_looks", "gfs_test_lba_first_trial",
+    "gfs_gba_create", "gfs_gba_destroy", "gfs_gba_solve", "gfs_gba_solve_bool", "gfs_gba_last_info", "gfs_test_gba_first_trial",
+    "gfs_test_gba_panel_rows", "gfs_test_gba_lists", "gfs_test_gba_tile_layout",
     "gfs_frame_create", "gfs_frame_destroy", "gfs_depth_to_cloud", "gfs_depth_to_cloud_batch_device", "gfs_depth_convert_u16_batch_device", "gfs_stereo_from_rgbd",
     "gfs_stereo_from_rgbd_batch_device",
     "gfs_pose_create", "gfs_pose_destroy", "gfs_pose_optimize", "gfs_pose_set_sum_order",
@@ -681,6 +688,16 @@ def lib():
             L.gfs_test_lba_stop_at_look.argtypes = [i]
             L.gfs_test_lba_last_looks.argtypes = [C.POINTER(C.c_int32)] * 4
             L.gfs_test_lba_first_trial.argtypes = [vp, C.POINTER(LbaProblem), C.POINTER(LbaTrial)]
+        if hasattr(L, "gfs_gba_create"):
+            L.gfs_gba_create.argtypes = [i, i, i, i, C.POINTER(vp)]
+            L.gfs_gba_destroy.argtypes = [vp]
+            L.gfs_gba_solve.argtypes = [vp, C.POINTER(LbaProblem), C.POINTER(LbaSolution), vp]
+            L.gfs_gba_solve_bool.argtypes = [vp, C.POINTER(LbaProblem), C.POINTER(LbaSolution), vp]
+            L.gfs_gba_last_info.argtypes = [vp, C.POINTER(GbaInfo)]
+            L.gfs_test_gba_first_trial.argtypes = [vp, C.POINTER(LbaProblem), C.POINTER(LbaTrial)]
+            L.gfs_test_gba_panel_rows.argtypes = []
+            L.gfs_test_gba_lists.argtypes = [i, i, i, vp, vp, vp, vp, vp, vp, vp, C.c_int64, vp, C.c_int64, vp, vp]
+            L.gfs_test_gba_tile_layout.argtypes = [C.c_int64, C.c_int64, C.c_int64, vp]
         if hasattr(L, "gfs_lba_solve_lidar"):
             L.gfs_lba_lidar_reserve.argtypes = [vp, i]
             L.gfs_lba_solve_lidar.argtypes = [vp, C.POINTER(LbaProblem), C.POINTER(LbaLidar), C.POINTER(LbaSolution), vp, vp]
@@ -1137,7 +1154,7 @@ def lba_last_looks():
     return dict(looks=v[0].value, discarded=v[1].value, forced_decides=v[2].value, ahead_at_stop=v[3].value)
 
 
-def lba_first_trial(opt, prob, fill=np.nan):
+def lba_first_trial(opt, prob, fill=np.nan, _entry="gfs_test_lba_first_trial"):
     """Test hook (include/gfs_abi_test.h: gfs_test_lba_first_trial): the linear step of the first LM trial of `prob` on the Optimizer
     `opt`, through the product's dispatch -> dict(lam, Dinv [n_points, 6], Hs (packed lower triangle), bs, xp [6F], xl [n_points, 3],
     solve_ok, scale).  The arrays are pre-written with `fill`: an entry the library did not deliver still holds it."""
@@ -1150,9 +1167,83 @@ def lba_first_trial(opt, prob, fill=np.nan):
     T = LbaTrial()
     for k, v in buf.items():
         setattr(T, k, v.ctypes.data)
-    _check(lib().gfs_test_lba_first_trial(opt.h, C.byref(P), C.byref(T)), "gfs_test_lba_first_trial")
+    _check(getattr(lib(), _entry)(opt.h, C.byref(P), C.byref(T)), _entry)
     return dict(lam=T.lambda_, scale=T.scale, solve_ok=int(T.solve_ok), Dinv=buf["Dinv"][:-1].reshape(NP, 6).copy(),
                 Hs=buf["Hs"][:-1].copy(), bs=buf["bs"][:-1].copy(), xp=buf["xp"][:-1].copy(), xl=buf["xl"][:-1].reshape(NP, 3).copy())
+
+
+def gba_first_trial(opt, prob, fill=np.nan):
+    """Test hook (gfs_test_gba_first_trial): lba_first_trial's dict for the GlobalOptimizer `opt`, through gfs_gba_solve's sequence."""
+    return lba_first_trial(opt, prob, fill, _entry="gfs_test_gba_first_trial")
+
+
+def gba_panel_rows():
+    """Rows of a tile of GlobalBundleAdjustment's tiled reduced system (gfs_test_gba_panel_rows)."""
+    return int(lib().gfs_test_gba_panel_rows())
+
+
+def gba_lists(prob):
+    """Host test hook (gfs_test_gba_lists, no GPU): the structure lists of the Schur assembly for `prob` -> dict(n_free, order [E],
+    blk_ij [B, 2], blk_begin [B + 1], contrib [C, 2], pose_begin [F + 1], pose_edges); edge ids are landmark-major positions."""
+    fixed = np.ascontiguousarray(prob["pose_fixed"], np.uint8)
+    ep, el = np.ascontiguousarray(prob["edge_pose"], np.int32), np.ascontiguousarray(prob["edge_point"], np.int32)
+    NQ, NP, E = int(prob["n_poses"]), int(prob["n_points"]), int(prob["n_edges"])
+    counts = np.zeros(3, np.int64)
+    rc = lib().gfs_test_gba_lists(NQ, NP, E, _p(fixed), _p(ep), _p(el), _p(counts), None, None, None, 0, None, 0, None, None)
+    if rc not in (0, -4):
+        _check(rc, "gfs_test_gba_lists")
+    F, B, Cn = (int(v) for v in counts)
+    order, blk, beg = np.zeros(E + 1, np.int32), np.zeros((B + 1, 2), np.int32), np.zeros(B + 2, np.int64)
+    con, pb, pe = np.zeros((Cn + 1, 2), np.int32), np.zeros(F + 2, np.int64), np.zeros(E + 1, np.int32)
+    _check(lib().gfs_test_gba_lists(NQ, NP, E, _p(fixed), _p(ep), _p(el), _p(counts), _p(order), _p(blk), _p(beg), B, _p(con), Cn, _p(pb),
+                                    _p(pe)), "gfs_test_gba_lists")
+    return dict(n_free=F, order=order[:E], blk_ij=blk[:B], blk_begin=beg[:B + 1], contrib=con[:Cn], pose_begin=pb[:F + 1],
+                pose_edges=pe[:int(pb[F])])
+
+
+def gba_tile_layout(n, r, c):
+    """Host test hook (gfs_test_gba_tile_layout, no GPU) -> dict(panels, storage_bytes, tile_index, byte_offset) as Python ints."""
+    out = np.zeros(4, np.uint64)
+    _check(lib().gfs_test_gba_tile_layout(int(n), int(r), int(c), _p(out)), "gfs_test_gba_tile_layout")
+    return dict(zip(("panels", "storage_bytes", "tile_index", "byte_offset"), (int(v) for v in out)))
+
+
+class GlobalOptimizer:
+    """The numeric core of ORB_SLAM3::Optimizer::GlobalBundleAdjustemnt / BundleAdjustment (reference src/Optimizer.cc:47-363) on a
+    flattened problem (gfs_lba_problem): the full map, the reduced pose system tiled over the whole device (gfs_gba_solve)."""
+
+    def __init__(self, max_poses=512, max_points=32768, max_edges=524288, device=0):
+        self.h = C.c_void_p()
+        _check(lib().gfs_gba_create(device, max_poses, max_points, max_edges, C.byref(self.h)), "gfs_gba_create")
+
+    def close(self):
+        if getattr(self, "h", None) and _lib is not None:
+            _lib.gfs_gba_destroy(self.h)
+        self.h = None
+
+    __del__ = close
+
+    def BundleAdjustment(self, prob, stop_flag=None, robust=True):
+        """optimizer.optimize(prob["iterations"]).  robust=False (bRobust = false: LoopClosing::RunGlobalBundleAdjustment) puts +inf
+        in the place of the two Huber thresholds.  stop_flag: an int32 array read live (pbStopFlag); a flag that is already up gives
+        iterations_run = 0 and the input estimate, never None."""
+        if not robust:
+            prob = dict(prob, huber_mono=np.inf, huber_stereo=np.inf)
+        P, keep = _lba_problem(prob)
+        out = dict(pose_q=np.zeros((P.n_poses, 4)), pose_t=np.zeros((P.n_poses, 3)), points=np.zeros((P.n_points, 3)),
+                   edge_chi2=np.zeros(P.n_edges), edge_depth_positive=np.zeros(P.n_edges, np.uint8))
+        S = LbaSolution()
+        for k, v in out.items():
+            setattr(S, k, v.ctypes.data)
+        stop = stop_flag.ctypes.data_as(C.c_void_p) if stop_flag is not None else None
+        _check(lib().gfs_gba_solve(self.h, C.byref(P), C.byref(S), stop), "gfs_gba_solve")
+        out.update(iterations_run=S.iterations_run, final_chi2=S.final_chi2, final_lambda=S.final_lambda)
+        return out
+
+    def last_info(self):
+        I = GbaInfo()
+        _check(lib().gfs_gba_last_info(self.h, C.byref(I)), "gfs_gba_last_info")
+        return {k: int(getattr(I, k)) for k, _ in GbaInfo._fields_}
 
 
 class Optimizer:

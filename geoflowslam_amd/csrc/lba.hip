@@ -1576,6 +1576,9 @@ __global__ __launch_bounds__(kMk) void kb_lba_pack(const LbaDev* __restrict__ DD
 // host -> device through the pinned arena (bump allocation; the arena outlives the asynchronous copies of one call)
 }  // namespace
 
+#include "gba_dev.hpp"  // the global bundle adjustment's assembly, tiled factorisation and substitutions (gfs_gba_solve)
+#include "gba_lists.hpp"
+
 struct gfs_lba {
   int device, max_poses, max_points, max_edges;
   hipStream_t stream;
@@ -1624,7 +1627,9 @@ struct HostPrep {
   size_t used = 0;  // bytes of the arena in use
 };
 
-int prepare(gfs_lba* h, const gfs_lba_problem* p, HostPrep& P) {
+// covis = false (gfs_gba_solve): no [free pose][landmark] table -- at map size it would be gigabytes, and the structure lists take its
+// place; the duplicate table comes from the landmark-major order itself (a pose's edges on one landmark are neighbours in it)
+int prepare(gfs_lba* h, const gfs_lba_problem* p, HostPrep& P, bool covis = true) {
   GFS_REQUIRE(p && p->n_poses >= 0 && p->n_points >= 0 && p->n_edges >= 0, GFS_ERR_INVALID_ARG, "gfs_lba: invalid problem");
   GFS_REQUIRE(p->n_poses <= h->max_poses && p->n_points <= h->max_points && p->n_edges <= h->max_edges, GFS_ERR_CAPACITY,
               "gfs_lba: problem (%d poses, %d points, %d edges) exceeds handle capacity (%d, %d, %d)", p->n_poses,
@@ -1653,7 +1658,7 @@ int prepare(gfs_lba* h, const gfs_lba_problem* p, HostPrep& P) {
     P.pt_begin = (int*)take((size_t)(NP + 1) * 4);
     P.pose_begin = (int*)take((size_t)(nf + 1) * 4);
     P.pose_edges = (int*)take((size_t)E * 4);
-    P.edge_of = (int*)take((size_t)nf * NP * 4);
+    P.edge_of = covis ? (int*)take((size_t)nf * NP * 4) : nullptr;
     P.stereo = take((size_t)E);
     P.lm_wg = (int*)take((size_t)(NP + 2) * 4);
     P.used = at;  // (grows by the duplicate table below when the window has any)
@@ -1697,7 +1702,9 @@ int prepare(gfs_lba* h, const gfs_lba_problem* p, HostPrep& P) {
     for (int e = 0; e < E; e++) P.order[pos[p->edge_point[e]]++] = e;  // stable
   }
   std::fill(P.pose_begin, P.pose_begin + P.n_free + 1, 0);
-  std::fill(P.edge_of, P.edge_of + (size_t)P.n_free * NP, -1);
+  if (covis) std::fill(P.edge_of, P.edge_of + (size_t)P.n_free * NP, -1);
+  static thread_local std::vector<int> tl_first;  // covis = false: the first edge of free pose f on the last landmark it was met on
+  if (!covis) tl_first.assign(P.n_free, -1);
   for (int k = 0; k < E; k++) {
     const int e = P.order[k];
     P.e_pose[k] = p->edge_pose[e];
@@ -1709,7 +1716,8 @@ int prepare(gfs_lba* h, const gfs_lba_problem* p, HostPrep& P) {
     P.e_dup[k] = -1;
     if (f >= 0) {
       P.pose_begin[f + 1]++;
-      int& slot = P.edge_of[(size_t)f * NP + P.e_point[k]];
+      int& slot = covis ? P.edge_of[(size_t)f * NP + P.e_point[k]] : tl_first[f];
+      if (!covis && slot >= 0 && P.e_point[slot] != P.e_point[k]) slot = -1;  // (that edge was on an earlier landmark)
       if (slot < 0) {
         slot = k;
       } else {  // a second edge between this pose and this landmark
@@ -1740,7 +1748,8 @@ int upload(gfs_lba* h, const HostPrep& P, hipStream_t s) {
 }
 
 // describes an uploaded window for the kernels
-int upload_and_fill(gfs_lba* h, const gfs_lba_problem* p, const HostPrep& P, int mode, hipStream_t s, LbaDev& D, bool do_upload = true) {
+int upload_and_fill(gfs_lba* h, const gfs_lba_problem* p, const HostPrep& P, int mode, hipStream_t s, LbaDev& D, bool do_upload = true,
+                    bool lba_schur = true) {
   const int E = p->n_edges, NP = p->n_points;
   int rc;
   if (do_upload && (rc = upload(h, P, s))) return rc;
@@ -1758,7 +1767,7 @@ int upload_and_fill(gfs_lba* h, const gfs_lba_problem* p, const HostPrep& P, int
   D.pt_begin = (decltype(D.pt_begin))((const int*)dev(P.pt_begin));
   D.pose_begin = (decltype(D.pose_begin))((const int*)dev(P.pose_begin));
   D.pose_edges = (decltype(D.pose_edges))((const int*)dev(P.pose_edges));
-  D.edge_of = (decltype(D.edge_of))((const int*)dev(P.edge_of));
+  D.edge_of = (decltype(D.edge_of))(P.edge_of ? (const int*)dev(P.edge_of) : nullptr);
   D.e_stereo = (decltype(D.e_stereo))((const unsigned char*)dev(P.stereo));
   D.e_dup = (decltype(D.e_dup))(P.e_dup ? (const int*)dev(P.e_dup) : nullptr);
   D.lm_wg = (decltype(D.lm_wg))((const int*)dev(P.lm_wg));
@@ -1804,7 +1813,7 @@ int upload_and_fill(gfs_lba* h, const gfs_lba_problem* p, const HostPrep& P, int
   D.n_upd_blocks = gfs::div_up(std::max(NP, 1), kMk);
   // Schur products: on the matrix cores by landmark chunks (b_schur_mfma), GFS_LBA_SCHUR=chunks | pairs select the vector kernels
   // (b_schur_chunks; one workgroup per pose pair, which also takes the windows too wide for the others' staging)
-  {
+  if (lba_schur) {
     const int F = P.n_free;
     static const char* mode = getenv("GFS_LBA_SCHUR");
     static const bool by_pairs = mode && !strcmp(mode, "pairs"), by_chunks = mode && !strcmp(mode, "chunks");
@@ -2149,7 +2158,8 @@ void lidar_keep(gfs_lba* h, const gfs_lba_problem* p, const LidarRun& R, int32_t
 
 extern "C" {
 
-int gfs_lba_create(int device, int max_poses, int max_points, int max_edges, gfs_lba** out) {
+// gba: the handle inside a gfs_gba -- no co-visibility table in the staging arena, no packed reduced system
+static int lba_create_impl(int device, int max_poses, int max_points, int max_edges, bool gba, gfs_lba** out) {
   GFS_REQUIRE(out && max_poses > 0 && max_points > 0 && max_edges > 0, GFS_ERR_INVALID_ARG, "gfs_lba_create: invalid argument");
   if (!gfs::device_ok(device)) return GFS_ERR_NO_DEVICE;
   GFS_HIP(hipSetDevice(device));
@@ -2184,18 +2194,21 @@ int gfs_lba_create(int device, int max_poses, int max_points, int max_edges, gfs
   A(h->d_stats.alloc(2));
   A(h->d_info.alloc(2));
   A(h->d_state.alloc(1));
-  A(h->h_stage.alloc(NQ * (32 + 24 + 4) + NP * (24 + 4) + E * (4 + 4 + 24 + 8 + 1 + 4 + 4) + F * (4 + 4 + NP * 4) + (NP + 2) * 4 + 4096));
+  A(h->h_stage.alloc(NQ * (32 + 24 + 4) + NP * (24 + 4) + E * (4 + 4 + 24 + 8 + 1 + 4 + 4) + F * (4 + 4 + (gba ? 0 : NP * 4)) + (NP + 2) * 4 + 4096));
   A(h->d_in.alloc(h->h_stage.n));
   A(h->d_out.alloc(E + 7 * NQ + 3 * NP + 4));
   A(h->h_out.alloc(E + 7 * NQ + 3 * NP + 4));
   A(h->d_part_chi.alloc(E / kMk + 2));
   A(h->d_part_scale.alloc(NP / kMk + 2));
-  A(h->d_Hs.alloc((size_t)(6 * F) * (6 * F + 1) / 2 + 8));
+  A(h->d_Hs.alloc(gba ? 8 : (size_t)(6 * F) * (6 * F + 1) / 2 + 8));
   A(h->d_bs.alloc(6 * F + 8));
 #undef A
   if (rc) return rc;
   *out = h.release();
   return GFS_OK;
+}
+int gfs_lba_create(int device, int max_poses, int max_points, int max_edges, gfs_lba** out) {
+  return lba_create_impl(device, max_poses, max_points, max_edges, false, out);
 }
 
 void gfs_lba_destroy(gfs_lba* h) {
@@ -2743,6 +2756,347 @@ int gfs_lba_solve_batch(gfs_lba_batch* b, const gfs_lba_problem* problems, gfs_l
   StopFlag f;
   f.i = stop;
   return lba_solve_batch_impl(b, problems, solutions, n, f);
+}
+
+// ---- global bundle adjustment (Optimizer::BundleAdjustment, src/Optimizer.cc:56-363) ---------------------------------------------
+// A gfs_gba is a gfs_lba (the problem staging, the LM state and every phase kernel but the Schur products and the reduced solve
+// are gfs_lba_solve's) plus the structure lists, the tiled reduced system and the panel workspace of gba_dev.hpp.
+struct gfs_gba {
+  gfs_lba* lba = nullptr;
+  int max_poses = 0;
+  gfs::DevBuf<double> d_tiles, d_W, d_rhs;
+  gfs::DevBuf<int> d_blk_i, d_blk_j, d_contrib, d_pose_edges;  // (d_contrib grows on demand)
+  gfs::DevBuf<long long> d_blk_begin, d_pose_begin;
+  gba_sys::Lists lists;
+  std::vector<int32_t> e_free;
+  gfs_gba_info info = {};
+};
+
+static int gba_raise_lds_limits(int device) {
+  static std::mutex mu;
+  static bool done[64] = {};
+  std::lock_guard<std::mutex> lk(mu);
+  if (device >= 0 && device < 64 && done[device]) return GFS_OK;
+  // (what each kernel is launched with: the sizes are compile-time constants, and the kernels hold static LDS besides)
+  GFS_HIP(hipFuncSetAttribute((const void*)k_gba_diag, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kGbaTileLds));
+  GFS_HIP(hipFuncSetAttribute((const void*)k_gba_back, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kGbaTileLds));
+  GFS_HIP(hipFuncSetAttribute((const void*)k_gba_panel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(2 * kGbaTileLds)));
+  if (device >= 0 && device < 64) done[device] = true;
+  return GFS_OK;
+}
+
+int gfs_gba_create(int device, int max_poses, int max_points, int max_edges, gfs_gba** out) {
+  GFS_REQUIRE(out && max_poses > 0 && max_points > 0 && max_edges > 0, GFS_ERR_INVALID_ARG, "gfs_gba_create: invalid argument");
+  std::unique_ptr<gfs_gba> g(new gfs_gba);
+  int rc = lba_create_impl(device, max_poses, max_points, max_edges, true, &g->lba);
+  if (!rc) rc = gba_raise_lds_limits(device);
+  const size_t n = 6 * (size_t)max_poses, T = gba_sys::panels(n), F = max_poses;
+  {  // the reduced system plus workspaces have to fit: refused here, not in the middle of a solve
+    size_t free_b = 0, total_b = 0;
+    if (!rc && hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
+      // the tiles, the panel workspace and the block tables (one entry per block of the packed lower triangle: F (F + 1) / 2 is the
+      // most a map can list, ~100 MB at 4 000 poses); the contribution list is sized by the map and grows in gba_lists_upload
+      const size_t need = gba_sys::storage_bytes(n) + T * gba_sys::kP * gba_sys::kP * sizeof(double) + F * (F + 1) / 2 * 16;
+      if (need > free_b) {
+        gfs::set_error("gfs_gba_create: the reduced system of %d poses needs %zu bytes, %zu are free", max_poses, need, free_b);
+        rc = GFS_ERR_CAPACITY;
+      }
+    }
+  }
+#define A(x) if (!rc) rc = (x)
+  A(g->d_tiles.alloc(gba_sys::storage_doubles(n)));
+  A(g->d_W.alloc(T * gba_sys::kP * gba_sys::kP));
+  A(g->d_rhs.alloc(T * gba_sys::kP));
+  A(g->d_blk_i.alloc(F * (F + 1) / 2));
+  A(g->d_blk_j.alloc(g->d_blk_i.n));
+  A(g->d_blk_begin.alloc(g->d_blk_i.n + 1));
+  A(g->d_pose_begin.alloc(F + 1));
+  A(g->d_pose_edges.alloc(max_edges));
+#undef A
+  if (rc) {
+    if (g->lba) gfs_lba_destroy(g->lba);
+    return rc;
+  }
+  g->max_poses = max_poses;
+  *out = g.release();
+  return GFS_OK;
+}
+
+void gfs_gba_destroy(gfs_gba* g) {
+  if (!g) return;
+  if (g->lba) {
+    (void)hipSetDevice(g->lba->device);
+    (void)hipStreamSynchronize(g->lba->stream);
+  }
+  g->d_tiles.free();
+  g->d_W.free();
+  g->d_rhs.free();
+  g->d_blk_i.free();
+  g->d_blk_j.free();
+  g->d_contrib.free();
+  g->d_pose_edges.free();
+  g->d_blk_begin.free();
+  g->d_pose_begin.free();
+  gfs_lba_destroy(g->lba);
+  delete g;
+}
+
+// the structure lists of a prepared problem, uploaded on the handle's stream
+static int gba_lists_upload(gfs_gba* g, const gfs_lba_problem* p, const HostPrep& P, GbaDev& G) {
+  gfs_lba* h = g->lba;
+  hipStream_t s = h->stream;
+  const int E = p->n_edges, F = P.n_free;
+  g->e_free.resize(E);
+  for (int k = 0; k < E; k++) g->e_free[k] = P.free_index[P.e_pose[k]];
+  gba_sys::Lists& L = g->lists;
+  gba_sys::build_lists(F, p->n_points, P.pt_begin, g->e_free.data(), L);
+  GFS_REQUIRE((size_t)L.n_blocks() <= g->d_blk_i.n, GFS_ERR_CAPACITY, "gfs_gba: %lld block pairs exceed the handle's %zu",
+              (long long)L.n_blocks(), g->d_blk_i.n);
+  if (g->d_contrib.n < L.contrib.size()) {  // (before anything of this solve is queued; a handle settles after its largest map)
+    GFS_HIP(hipStreamSynchronize(s));
+    if (int rc = g->d_contrib.alloc(L.contrib.size() + L.contrib.size() / 4)) return rc;
+  }
+  static_assert(sizeof(long long) == sizeof(int64_t), "the lists' 64-bit counts go up as they are");
+  auto up = [&](void* d, const void* src, size_t bytes) {
+    return bytes ? hipMemcpyAsync(d, src, bytes, hipMemcpyHostToDevice, s) : hipSuccess;
+  };
+  GFS_HIP(up(g->d_blk_i.p, L.blk_i.data(), L.blk_i.size() * 4));
+  GFS_HIP(up(g->d_blk_j.p, L.blk_j.data(), L.blk_j.size() * 4));
+  GFS_HIP(up(g->d_blk_begin.p, L.blk_begin.data(), L.blk_begin.size() * 8));
+  GFS_HIP(up(g->d_contrib.p, L.contrib.data(), L.contrib.size() * 4));
+  GFS_HIP(up(g->d_pose_begin.p, L.pose_begin.data(), L.pose_begin.size() * 8));
+  GFS_HIP(up(g->d_pose_edges.p, L.pose_edges.data(), L.pose_edges.size() * 4));
+  GFS_HIP(hipStreamSynchronize(s));  // (the host vectors are pageable: the copies have read them)
+  G = GbaDev{};
+  G.n = 6 * F;
+  G.T = (int)gba_sys::panels(6 * (size_t)F);
+  G.n_blocks = L.n_blocks();
+  G.blk_i = (decltype(G.blk_i))(g->d_blk_i.p);
+  G.blk_j = (decltype(G.blk_j))(g->d_blk_j.p);
+  G.blk_begin = (decltype(G.blk_begin))(g->d_blk_begin.p);
+  G.contrib = (decltype(G.contrib))(g->d_contrib.p);
+  G.pose_begin = (decltype(G.pose_begin))(g->d_pose_begin.p);
+  G.pose_edges = (decltype(G.pose_edges))(g->d_pose_edges.p);
+  G.tiles = (decltype(G.tiles))(g->d_tiles.p);
+  G.W = (decltype(G.W))(g->d_W.p);
+  G.rhs = (decltype(G.rhs))(g->d_rhs.p);
+  return GFS_OK;
+}
+
+// The LM loop of gfs_gba_solve.  The phase kernels are gfs_lba_solve's; the Schur products and the reduced solve are gba_dev.hpp's.
+// The host waits for every trial's verdict (no iteration is queued ahead: next to a map-sized factorisation the round trip is
+// nothing), so the caller's flag is looked at exactly where g2o looks: at the top of every iteration -- the first look is the top of
+// iteration 0, Optimizer::BundleAdjustment has no entry check -- and after every rejected trial that would be retried.
+// tap: init, the build group of iteration 0 and one trial up to and including k_lba_update, the reduced system copied out packed
+// between the assembly and the factorisation.
+static int gba_run(gfs_gba* g, const gfs_lba_problem* p, const HostPrep& P, StopFlag stop, const TrialTap* tap) {
+  gfs_lba* h = g->lba;
+  hipStream_t s = h->stream;
+  LbaDev D;
+  int rc = upload_and_fill(h, p, P, 0, s, D, true, false);
+  if (rc) return rc;
+  GbaDev G;
+  if ((rc = gba_lists_upload(g, p, P, G))) return rc;
+  h->last_desc = D;
+  gfs_gba_info& I = g->info;
+  I = gfs_gba_info{};
+  I.n_free = P.n_free;
+  I.panel_rows = kP;
+  I.panels = G.T;
+  I.block_pairs = G.n_blocks;
+  I.contributions = g->lists.n_contrib();
+  I.system_bytes = (int64_t)gba_sys::storage_bytes((size_t)G.n);
+  int launches = 0;
+#define GBA_LAUNCH(...)      \
+  do {                       \
+    GFS_LAUNCH(__VA_ARGS__); \
+    launches++;              \
+  } while (0)
+  int* d_flags = nullptr;
+  GFS_HIP(hipHostGetDevicePointer((void**)&d_flags, h->h_flags, 0));
+  const dim3 g_err(D.n_err_blocks), g_lm(std::max(D.n_lm_wg, 1)), g_upd(D.n_upd_blocks);
+  GBA_LAUNCH("k_lba_init", k_lba_init, dim3(64), dim3(kMk), 0, s, D);
+  auto build_group = [&](int iteration) -> int {
+    GBA_LAUNCH("k_lba_errors", k_lba_errors, g_err, dim3(kMk), 0, s, D, 0, 0);
+    if (D.n_lm_wg > 0) GBA_LAUNCH("k_lba_build_landmarks", k_lba_build_landmarks, g_lm, dim3(kMk), 0, s, D, 0);
+    if (P.n_free > 0) GBA_LAUNCH("k_lba_build_poses", k_lba_build_poses, dim3(P.n_free), dim3(kPoseWg), 0, s, D, 0);
+    GBA_LAUNCH("k_lba_begin", k_lba_begin, dim3(1), dim3(kThreads), 0, s, D, iteration, 0);
+    return GFS_OK;
+  };
+  gfs::DevBuf<double> d_tap;
+  auto trial_group = [&]() -> int {
+    I.trials++;
+    GBA_LAUNCH("k_lba_dinv", k_lba_dinv, g_upd, dim3(kMk), 0, s, D, 0);
+    const int T = G.T;
+    if (T > 0) {
+      GFS_HIP(hipMemsetAsync(g->d_tiles.p, 0, gba_sys::storage_bytes((size_t)G.n), s));
+      GBA_LAUNCH("k_gba_assemble", k_gba_assemble, dim3((unsigned)((G.n_blocks + kMk / 64 - 1) / (kMk / 64))), dim3(kMk), 0, s, D, G);
+      if (tap) {
+        const size_t n = (size_t)G.n, nt = n * (n + 1) / 2;
+        if (int rc2 = d_tap.alloc(nt + n)) return rc2;
+        GFS_LAUNCH("k_gba_pack_lower", k_gba_pack_lower, dim3(256), dim3(kMk), 0, s, G, d_tap.p, d_tap.p + nt);
+        GFS_HIP(hipMemcpyAsync(tap->Hs, d_tap.p, nt * sizeof(double), hipMemcpyDeviceToHost, s));
+        GFS_HIP(hipMemcpyAsync(tap->bs, d_tap.p + nt, n * sizeof(double), hipMemcpyDeviceToHost, s));
+      }
+      for (int q = 0; q < T; q++) {
+        GBA_LAUNCH("k_gba_diag", k_gba_diag, dim3(1), dim3(kMk), kGbaTileLds, s, D, G, q);
+        const int m = T - 1 - q;
+        if (m > 0) {
+          GBA_LAUNCH("k_gba_panel", k_gba_panel, dim3(m), dim3(kMk), 2 * kGbaTileLds, s, D, G, q);
+          GBA_LAUNCH("k_gba_trail", k_gba_trail, dim3((unsigned)((size_t)m * (m + 1) / 2)), dim3(kMk), 0, s, D, G, q);
+        }
+      }
+      GBA_LAUNCH("k_gba_scale", k_gba_scale, dim3(gfs::div_up(T * kP, kMk)), dim3(kMk), 0, s, D, G);
+      for (int q = T; q >= 1; q--) GBA_LAUNCH("k_gba_back", k_gba_back, dim3(q == T ? 1 : q), dim3(kMk), kGbaTileLds, s, D, G, q);
+    }
+    GBA_LAUNCH("k_lba_update", k_lba_update, g_upd, dim3(kMk), 0, s, D, 0);
+    if (tap) return GFS_OK;
+    GBA_LAUNCH("k_lba_errors", k_lba_errors, g_err, dim3(kMk), 0, s, D, 1, 0);
+    GBA_LAUNCH("k_lba_decide", k_lba_decide, dim3(1), dim3(64), 0, s, D, 0, d_flags, 0);
+    GFS_HIP(hipEventRecord(h->ev_decide[0], s));
+    return GFS_OK;
+  };
+  if (tap) {
+    if ((rc = build_group(0)) || (rc = trial_group())) return rc;
+    GFS_HIP(hipStreamSynchronize(s));
+    I.launches = launches;
+    return GFS_OK;
+  }
+  bool stopped = false, began = false;
+  for (int iteration = 0; iteration < p->iterations && !stopped; iteration++) {
+    if (stop && *stop) break;
+    if ((rc = build_group(iteration))) return rc;
+    began = true;
+    for (;;) {
+      if ((rc = trial_group())) return rc;
+      GFS_HIP(hipEventSynchronize(h->ev_decide[0]));
+      if (!h->h_flags[0]) break;  // accepted, or the iteration's last trial
+      if (stop && *stop) {        // a rejected trial that would be retried: the iteration ends here, counted (terminate())
+        GBA_LAUNCH("k_lba_decide", k_lba_decide, dim3(1), dim3(64), 0, s, D, 1, d_flags, 0);
+        tl_stop_script.forced++;
+        stopped = true;
+        break;
+      }
+    }
+    if (!stopped && h->h_flags[1]) break;
+  }
+  // e->chi2() at the estimate that is returned (after an accepted trial the arrays hold it already and the kernel leaves at once)
+  GBA_LAUNCH("k_lba_errors", k_lba_errors, g_err, dim3(kMk), 0, s, D, 0, 0);
+  LbaDev Df = D;
+  if (!began) {  // no iteration at all (the flag was up at the first look, or iterations <= 0): the robust chi2 of the estimate as it
+                 // came and lambda 0, what gfs_lba_solve reports for iterations <= 0
+    GBA_LAUNCH("k_lba_begin", k_lba_begin, dim3(1), dim3(kThreads), 0, s, D, 1, 0);
+    Df.mode = 1;
+  }
+  GBA_LAUNCH("k_lba_finish", k_lba_finish, dim3(1), dim3(64), 0, s, Df);
+  I.launches = launches;
+#undef GBA_LAUNCH
+  return GFS_OK;
+}
+
+static int gba_solve_impl(gfs_gba* g, const gfs_lba_problem* p, gfs_lba_solution* sol, StopFlag stop) {
+  StopScriptCall script_call;
+  GFS_REQUIRE(g && p && sol, GFS_ERR_INVALID_ARG, "gfs_gba_solve: NULL argument");
+  gfs_lba* h = g->lba;
+  std::lock_guard<std::mutex> lk(h->mu);
+  GFS_HIP(hipSetDevice(h->device));
+  static thread_local HostPrep tl_prep;
+  HostPrep& P = tl_prep;
+  int rc = prepare(h, p, P, false);
+  if (rc) return rc;
+  if ((rc = gba_run(g, p, P, stop, nullptr))) return rc;
+  LbaFetch F;
+  GFS_LAUNCH("k_lba_pack", k_lba_pack, dim3(16), dim3(kMk), 0, h->stream, h->last_desc);
+  if ((rc = lba_fetch_issue(h, p, h->stream, F))) return rc;
+  GFS_HIP(hipStreamSynchronize(h->stream));
+  lba_fetch_finish(p, P, F, sol);
+  // a run without an iteration hands the caller's estimate back as it came (the device holds the quaternions normalised)
+  if (sol->iterations_run == 0 && p->n_poses && sol->pose_q) memcpy(sol->pose_q, p->pose_q, (size_t)p->n_poses * 32);
+  return GFS_OK;
+}
+
+int gfs_gba_solve(gfs_gba* h, const gfs_lba_problem* p, gfs_lba_solution* sol, volatile const int* stop) {
+  StopFlag f;
+  f.i = stop;
+  return gba_solve_impl(h, p, sol, f);
+}
+int gfs_gba_solve_bool(gfs_gba* h, const gfs_lba_problem* p, gfs_lba_solution* sol, const volatile unsigned char* stop) {
+  StopFlag f;
+  f.b = stop;
+  return gba_solve_impl(h, p, sol, f);
+}
+int gfs_gba_last_info(const gfs_gba* h, gfs_gba_info* info) {
+  GFS_REQUIRE(h && info, GFS_ERR_INVALID_ARG, "gfs_gba_last_info: NULL argument");
+  *info = h->info;  // (not under the handle's lock: for the thread that made the call, after it returned)
+  return GFS_OK;
+}
+
+int gfs_test_gba_panel_rows(void) { return kP; }
+
+int gfs_test_gba_first_trial(gfs_gba* g, const gfs_lba_problem* p, gfs_test_lba_trial* out) {
+  GFS_REQUIRE(g && p && out, GFS_ERR_INVALID_ARG, "gfs_test_gba_first_trial: NULL argument");
+  GFS_REQUIRE(out->Dinv && out->Hs && out->bs && out->xp && out->xl, GFS_ERR_INVALID_ARG, "gfs_test_gba_first_trial: NULL output array");
+  gfs_lba* h = g->lba;
+  std::lock_guard<std::mutex> lk(h->mu);
+  GFS_HIP(hipSetDevice(h->device));
+  static thread_local HostPrep tl_prep;
+  HostPrep& P = tl_prep;
+  int rc = prepare(h, p, P, false);
+  if (rc) return rc;
+  const TrialTap tap{out->Hs, out->bs};
+  if ((rc = gba_run(g, p, P, StopFlag{}, &tap))) return rc;  // returns with the stream drained
+  const size_t NP = p->n_points, n = 6 * (size_t)P.n_free;
+  LbaState S;
+  GFS_HIP(hipMemcpy(&S, h->d_state.p, sizeof(S), hipMemcpyDeviceToHost));
+  if (NP) GFS_HIP(hipMemcpy(out->Dinv, h->d_Dinv.p, NP * 6 * sizeof(double), hipMemcpyDeviceToHost));
+  if (NP) GFS_HIP(hipMemcpy(out->xl, h->d_xl.p, NP * 3 * sizeof(double), hipMemcpyDeviceToHost));
+  if (n) GFS_HIP(hipMemcpy(out->xp, h->d_xp.p, n * sizeof(double), hipMemcpyDeviceToHost));
+  std::vector<double> part(h->last_desc.n_upd_blocks);
+  GFS_HIP(hipMemcpy(part.data(), h->d_part_scale.p, part.size() * sizeof(double), hipMemcpyDeviceToHost));
+  double scale = 0;
+  for (double v : part) scale += v;  // k_lba_decide's order
+  out->lambda = S.lambda;
+  out->scale = scale;
+  out->solve_ok = S.solve_ok;
+  return GFS_OK;
+}
+
+// host-only: the structure lists of a caller-order problem (gba_lists.hpp), in the landmark-major edge numbering `order` gives
+int gfs_test_gba_lists(int n_poses, int n_points, int n_edges, const uint8_t* pose_fixed, const int32_t* edge_pose, const int32_t* edge_point,
+                       int64_t* counts /* n_free, blocks, contributions */, int32_t* order, int32_t* blk_ij, int64_t* blk_begin,
+                       int64_t cap_blocks, int32_t* contrib, int64_t cap_contrib, int64_t* pose_begin, int32_t* pose_edges) {
+  GFS_REQUIRE(n_poses >= 0 && n_points >= 0 && n_edges >= 0 && counts, GFS_ERR_INVALID_ARG, "gfs_test_gba_lists: invalid argument");
+  for (int e = 0; e < n_edges; e++)
+    GFS_REQUIRE(edge_point[e] >= 0 && edge_point[e] < n_points && edge_pose[e] >= 0 && edge_pose[e] < n_poses, GFS_ERR_INVALID_ARG,
+                "gfs_test_gba_lists: edge %d references an unknown vertex", e);
+  std::vector<int32_t> ord, ptb, ef;
+  gba_sys::Lists L;
+  const int64_t F = gba_sys::landmark_major(n_poses, n_points, n_edges, pose_fixed, edge_pose, edge_point, ord, ptb, ef);
+  gba_sys::build_lists(F, n_points, ptb.data(), ef.data(), L);
+  counts[0] = F;
+  counts[1] = L.n_blocks();
+  counts[2] = L.n_contrib();
+  if (L.n_blocks() > cap_blocks || L.n_contrib() > cap_contrib) return GFS_ERR_CAPACITY;
+  if (order) std::copy(ord.begin(), ord.end(), order);
+  for (int64_t b = 0; b < L.n_blocks() && blk_ij; b++) {
+    blk_ij[2 * b] = L.blk_i[(size_t)b];
+    blk_ij[2 * b + 1] = L.blk_j[(size_t)b];
+  }
+  if (blk_begin) std::copy(L.blk_begin.begin(), L.blk_begin.end(), blk_begin);
+  if (contrib) std::copy(L.contrib.begin(), L.contrib.end(), contrib);
+  if (pose_begin) std::copy(L.pose_begin.begin(), L.pose_begin.end(), pose_begin);
+  if (pose_edges) std::copy(L.pose_edges.begin(), L.pose_edges.end(), pose_edges);
+  return GFS_OK;
+}
+
+// host-only: gba_tiles.hpp's arithmetic for n rows and the element (r, c), r >= c
+int gfs_test_gba_tile_layout(int64_t n, int64_t r, int64_t c, uint64_t* out /* panels, storage bytes, tile index, element byte offset */) {
+  GFS_REQUIRE(n >= 0 && c >= 0 && r >= c && out, GFS_ERR_INVALID_ARG, "gfs_test_gba_tile_layout: invalid argument");
+  out[0] = gba_sys::panels((size_t)n);
+  out[1] = gba_sys::storage_bytes((size_t)n);
+  out[2] = gba_sys::tile_index((size_t)r / kP, (size_t)c / kP);
+  out[3] = gba_sys::elem_offset((size_t)r, (size_t)c) * sizeof(double);
+  return GFS_OK;
 }
 
 }  // extern "C"

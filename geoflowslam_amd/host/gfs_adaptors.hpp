@@ -2098,6 +2098,179 @@ class PoseLidarOptimizer {
   std::vector<uint8_t> st_, outlier_;
 };
 
+// ------------------------------------------------------------------------------------------------------------------------
+// Optimizer::BundleAdjustment(const vector<KeyFrame*>& vpKFs, const vector<MapPoint*>& vpMP, int nIterations, bool* pbStopFlag,
+//                             const unsigned long nLoopKF, const bool bRobust)                  reference src/Optimizer.cc:56-363
+// and Optimizer::GlobalBundleAdjustemnt(Map*, ...) (:47-54) as real code around the flat solver, line for line: bad key-frames
+// skipped and maxKFid (:113-124), the init key-frame fixed (:121), per map point the `pKF->isBad() || pKF->mnId > maxKFid` and
+// null-vertex filters (:148-150), mono against stereo decided by mvuRight (:155, :185-186), a point with nEdges == 0 dropped and
+// vbNotIncludedMP set (:263-268), optimize(nIterations) with the caller's flag handed down (:78, :274), and both write-back
+// branches (:279-362): nLoopKF == pMap->GetOriginKF()->mnId -> SetPose / SetWorldPos + UpdateNormalAndDepth, otherwise mTcwGBA,
+// mPosGBA and mnBAGlobalForKF.  There is no stop-flag check in front of optimize() and no chi2 classification behind it.
+//
+// The block under `dist > 1` (:298-341) only counts inliers and outliers into locals that nothing reads: it is left out.
+//
+// Classes as for LocalBundleAdjustment, plus Map::GetOriginKF(), KeyFrame::mnBAGlobalForKF, MapPoint::mnBAGlobalForKF and two more
+// functions of `Access`:
+//     static void set_pose_gba(KeyFrame*, const double q_xyzw[4], const double t[3]);  // mTcwGBA = Sophus::SE3d(q, t).cast<float>()
+//     static void set_pos_gba(MapPoint*, const float p[3]);                            // mPosGBA
+// Arithmetic on the way in and out as in LocalBundleAdjustment; the Huber deltas here are `const float thHuber2D = sqrt(5.99)`
+// (5.99, not 5.991: :126) and `thHuber3D = sqrt(7.815)`; bRobust = false (no setRobustKernel, :172, :205) is +infinity for both
+// (include/gfs_abi.h).  Second-camera observations (EdgeSE3ProjectXYZToBody, :224-260) are refused.
+// `solve(problem, solution, pbStopFlag)` is the numeric core: GlobalBundleAdjuster::solve (gfs_gba_solve on the GPU).
+// ------------------------------------------------------------------------------------------------------------------------
+template <class Access, class KeyFrame, class MapPoint, class Solve>
+void BundleAdjustment(Solve&& solve, const std::vector<KeyFrame*>& vpKFs, const std::vector<MapPoint*>& vpMP, int nIterations = 5,
+                      bool* pbStopFlag = nullptr, const unsigned long nLoopKF = 0, const bool bRobust = true) {
+  std::vector<bool> vbNotIncludedMP;
+  vbNotIncludedMP.resize(vpMP.size());
+  auto* pMap = vpKFs[0]->GetMap();
+  unsigned long maxKFid = 0;
+  // ---- key-frame vertices (:113-124): pose index = creation order
+  LbaFlat F;
+  std::map<const KeyFrame*, int32_t> pose_index;  // == optimizer.vertex(pKF->mnId) != NULL
+  for (size_t i = 0; i < vpKFs.size(); i++) {
+    KeyFrame* pKF = vpKFs[i];
+    if (pKF->isBad()) continue;
+    float q[4], t[3];
+    Access::pose(pKF, q, t);
+    pose_index[pKF] = (int32_t)F.pose_fixed.size();
+    for (int k = 0; k < 4; k++) F.pose_q.push_back((double)q[k]);
+    for (int k = 0; k < 3; k++) F.pose_t.push_back((double)t[k]);
+    F.pose_fixed.push_back(pKF->mnId == pMap->GetInitKFid() ? 1 : 0);
+    if (pKF->mnId > maxKFid) maxKFid = pKF->mnId;
+  }
+  // ---- map-point vertices and their edges (:130-269)
+  std::vector<int32_t> point_of(vpMP.size(), -1);  // flat point of vpMP[i]; -1: bad or without an edge
+  for (size_t i = 0; i < vpMP.size(); i++) {
+    MapPoint* pMP = vpMP[i];
+    if (pMP->isBad()) continue;
+    float X[3];
+    Access::world_pos(pMP, X);
+    const int32_t point_index = (int32_t)(F.points.size() / 3);
+    const size_t edges_before = F.edge_pose.size();
+    const auto observations = pMP->GetObservations();
+    int nEdges = 0;
+    for (auto mit = observations.begin(); mit != observations.end(); ++mit) {
+      KeyFrame* pKF = mit->first;
+      if (pKF->isBad() || pKF->mnId > maxKFid) continue;
+      const auto pit = pose_index.find(pKF);
+      if (pit == pose_index.end()) continue;  // optimizer.vertex(pKF->mnId) == NULL
+      nEdges++;
+      const int leftIndex = std::get<0>(mit->second);
+      if (leftIndex != -1) {
+        const bool stereo = pKF->mvuRight[leftIndex] >= 0;
+        const auto& kpUn = pKF->mvKeysUn[leftIndex];
+        F.edge_pose.push_back(pit->second);
+        F.edge_point.push_back(point_index);
+        F.edge_obs.push_back((double)kpUn.pt.x);
+        F.edge_obs.push_back((double)kpUn.pt.y);
+        F.edge_obs.push_back(stereo ? (double)pKF->mvuRight[leftIndex] : 0.0);
+        const float& invSigma2 = pKF->mvInvLevelSigma2[kpUn.octave];
+        F.edge_inv_sigma2.push_back((double)invSigma2);
+        F.edge_stereo.push_back(stereo ? 1 : 0);
+      }
+      if (pKF->mpCamera2 && std::get<1>(mit->second) != -1)
+        throw std::runtime_error("BundleAdjustment: second-camera observations (EdgeSE3ProjectXYZToBody) are not supported");
+    }
+    if (nEdges == 0) {  // optimizer.removeVertex(vPoint)
+      vbNotIncludedMP[i] = true;
+    } else {
+      vbNotIncludedMP[i] = false;
+      if (F.edge_pose.size() == edges_before)  // (counted observations, none of them in the left image: a vertex without an edge)
+        throw std::runtime_error("BundleAdjustment: a map point seen by second cameras only is not supported");
+      for (int k = 0; k < 3; k++) F.points.push_back((double)X[k]);
+      point_of[i] = point_index;
+    }
+  }
+  KeyFrame* first = nullptr;
+  for (KeyFrame* pKF : vpKFs)
+    if (!pKF->isBad()) {
+      first = pKF;
+      break;
+    }
+  if (!first) return;  // (the reference would optimise an empty graph and write nothing back)
+  F.finish(first->fx, first->fy, first->cx, first->cy, first->mbf);
+  const float thHuber2D = (float)std::sqrt(5.99), thHuber3D = (float)std::sqrt(7.815);  // :126-127
+  F.problem.huber_mono = bRobust ? (double)thHuber2D : (double)INFINITY;
+  F.problem.huber_stereo = bRobust ? (double)thHuber3D : (double)INFINITY;
+  F.problem.iterations = nIterations;
+  // ---- optimizer.initializeOptimization(); optimizer.optimize(nIterations);  (no entry check)
+  std::vector<double> out_q(F.pose_q.size()), out_t(F.pose_t.size()), out_p(F.points.size());
+  gfs_lba_solution S{};
+  S.pose_q = out_q.data();
+  S.pose_t = out_t.data();
+  S.points = out_p.data();
+  solve(F.problem, S, pbStopFlag);
+  // ---- recover optimised data: key-frames (:279-343)
+  const bool in_place = nLoopKF == pMap->GetOriginKF()->mnId;
+  for (size_t i = 0; i < vpKFs.size(); i++) {
+    KeyFrame* pKF = vpKFs[i];
+    if (pKF->isBad()) continue;
+    const size_t k = (size_t)pose_index[pKF];
+    if (in_place) {
+      float q[4], t[3];
+      for (int c = 0; c < 4; c++) q[c] = (float)out_q[4 * k + c];
+      for (int c = 0; c < 3; c++) t[c] = (float)out_t[3 * k + c];
+      Access::set_pose(pKF, q, t);
+    } else {
+      Access::set_pose_gba(pKF, &out_q[4 * k], &out_t[3 * k]);
+      pKF->mnBAGlobalForKF = nLoopKF;
+    }
+  }
+  // ---- points (:346-362)
+  for (size_t i = 0; i < vpMP.size(); i++) {
+    if (vbNotIncludedMP[i]) continue;
+    MapPoint* pMP = vpMP[i];
+    if (pMP->isBad()) continue;
+    float X[3];
+    for (int c = 0; c < 3; c++) X[c] = (float)out_p[3 * (size_t)point_of[i] + c];
+    if (in_place) {
+      Access::set_world_pos(pMP, X);
+      pMP->UpdateNormalAndDepth();
+    } else {
+      Access::set_pos_gba(pMP, X);
+      pMP->mnBAGlobalForKF = nLoopKF;
+    }
+  }
+}
+
+// Optimizer::GlobalBundleAdjustemnt (src/Optimizer.cc:47-54)
+template <class Access, class Map, class Solve>
+void GlobalBundleAdjustemnt(Solve&& solve, Map* pMap, int nIterations = 5, bool* pbStopFlag = nullptr, const unsigned long nLoopKF = 0,
+                            const bool bRobust = true) {
+  auto vpKFs = pMap->GetAllKeyFrames();
+  auto vpMP = pMap->GetAllMapPoints();
+  using KeyFrame = typename std::remove_pointer<typename decltype(vpKFs)::value_type>::type;
+  using MapPoint = typename std::remove_pointer<typename decltype(vpMP)::value_type>::type;
+  BundleAdjustment<Access, KeyFrame, MapPoint>(solve, vpKFs, vpMP, nIterations, pbStopFlag, nLoopKF, bRobust);
+}
+
+// numeric core of Optimizer::BundleAdjustment: the full map on the device (gfs_gba_solve)
+class GlobalBundleAdjuster {
+ public:
+  GlobalBundleAdjuster(int max_poses = 2048, int max_points = 262144, int max_edges = 4194304, int device = 0) {
+    check(gfs_gba_create(device, max_poses, max_points, max_edges, &h_), "gfs_gba_create");
+  }
+  ~GlobalBundleAdjuster() { gfs_gba_destroy(h_); }
+  GlobalBundleAdjuster(const GlobalBundleAdjuster&) = delete;
+  GlobalBundleAdjuster& operator=(const GlobalBundleAdjuster&) = delete;
+  // the caller's flag itself goes down (&mbStopGBA): read live at the top of every iteration and after every rejected trial
+  void solve(const gfs_lba_problem& p, gfs_lba_solution& s, const bool* pbStopFlag) {
+    static_assert(sizeof(bool) == 1, "gfs_gba_solve_bool reads the flag as one byte");
+    check(gfs_gba_solve_bool(h_, &p, &s, reinterpret_cast<const volatile unsigned char*>(pbStopFlag)), "gfs_gba_solve");
+  }
+  template <class Access, class Map>
+  void GlobalBundleAdjustemnt(Map* pMap, int nIterations = 5, bool* pbStopFlag = nullptr, const unsigned long nLoopKF = 0,
+                              const bool bRobust = true) {
+    gfs_host::GlobalBundleAdjustemnt<Access>([this](const gfs_lba_problem& p, gfs_lba_solution& s, const bool* stop) { this->solve(p, s, stop); },
+                                             pMap, nIterations, pbStopFlag, nLoopKF, bRobust);
+  }
+
+ private:
+  gfs_gba* h_ = nullptr;
+};
+
 }  // namespace gfs_host
 
 // The drop-ins written against the reference's own types (cv::Mat, cv::KeyPoint, Eigen, Sophus, ORB_SLAM3::ORBextractor as a base

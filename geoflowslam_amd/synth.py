@@ -224,6 +224,80 @@ def lba_window(seed, n_free=20, n_fixed=5, n_points=3000, mono_frac=0.1, outlier
                 iterations=10, gt_q=q_gt, gt_t=t_gt, gt_points=pts)
 
 
+def gba_map(seed, n_keyframes, n_points, mono_frac=0.1, outlier_frac=0.03, step=0.5, fixed=()):
+    """Synthetic map for GlobalBundleAdjustment: key-frames `step` metres apart along a corridor, looking sideways at `n_points`
+    points on a band 3 - 6 m away, so that a point is seen only by the ten-odd key-frames whose frustum passes it and most pairs
+    of key-frames share nothing (lba_window is fully covisible).  Key-frame 0 is fixed (pKF->mnId == pMap->GetInitKFid(),
+    src/Optimizer.cc:121) plus the indices in `fixed`; RGB-D edges with a fraction `mono_frac` of mono ones, pixel noise, gross
+    outliers, float-then-widened perturbed initial values: all as in lba_window.  Point-major edge order.  Every point has at
+    least one observation.  Returns lba_window's dict."""
+    rng = np.random.default_rng(seed)
+    fx = fy = np.float64(np.float32(607.0))
+    cx, cy = np.float64(np.float32(319.5)), np.float64(np.float32(239.5))
+    bf = np.float64(np.float32(0.0745 * 607.0))
+    length = step * max(n_keyframes - 1, 1)
+    pts = np.c_[np.sort(rng.uniform(-1.0, length + 1.0, n_points)), rng.uniform(-1.5, 1.5, n_points), rng.uniform(3.0, 6.0, n_points)]
+    Rs, ts = [], []
+    for i in range(n_keyframes):
+        c = np.array([step * i + 0.02 * rng.normal(), 0.05 * rng.normal(), 0.02 * rng.normal()])
+        Rcw = _rot(0.02 * rng.normal(), 0.05 * rng.normal(), 0.02 * rng.normal()).T
+        Rs.append(Rcw)
+        ts.append(-Rcw @ c)
+    sigma2 = np.float64(np.float32(1.2) ** (2 * np.arange(8))).astype(np.float64)
+    inv_sigma2 = np.float64(np.float32(1.0) / np.float32(1.2) ** (2 * np.arange(8)))
+    cols = dict(pose=[], point=[], obs=[], is2=[], stereo=[])
+    for i in range(n_keyframes):  # the points within reach of key-frame i (pts is sorted by x)
+        c_x = step * i
+        j0, j1 = np.searchsorted(pts[:, 0], [c_x - 4.5, c_x + 4.5])
+        xc = pts[j0:j1] @ Rs[i].T + ts[i]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            u, v = fx * xc[:, 0] / xc[:, 2] + cx, fy * xc[:, 1] / xc[:, 2] + cy
+        ok = np.nonzero((xc[:, 2] >= 0.3) & (u >= 0) & (u < 640) & (v >= 0) & (v < 480))[0]
+        m = len(ok)
+        octv = rng.choice(8, m, p=np.array([217, 181, 151, 126, 105, 87, 73, 60]) / 1000.0)
+        noise = rng.normal(0, 1, (m, 3)) * np.sqrt(sigma2[octv])[:, None]
+        out = rng.random(m) < outlier_frac
+        noise[out, :2] += rng.choice([-1.0, 1.0], (int(out.sum()), 2)) * 20.0
+        stereo = rng.random(m) >= mono_frac
+        ur = u[ok] - bf / xc[ok, 2]
+        obs = np.stack([np.float32(u[ok] + noise[:, 0]), np.float32(v[ok] + noise[:, 1]),
+                        np.where(stereo, np.float32(ur + noise[:, 2]), np.float32(-1.0))], 1).astype(np.float64)
+        cols["pose"].append(np.full(m, i, np.int32))
+        cols["point"].append((j0 + ok).astype(np.int32))
+        cols["obs"].append(obs)
+        cols["is2"].append(inv_sigma2[octv])
+        cols["stereo"].append(stereo.astype(np.uint8))
+    e_pose, e_point = np.concatenate(cols["pose"]), np.concatenate(cols["point"])
+    seen = np.zeros(n_points, bool)
+    seen[e_point] = True
+    new_id = np.cumsum(seen) - 1  # points nobody sees are left out (src/Optimizer.cc:263-268 drops them from the graph)
+    order = np.argsort(e_point, kind="stable")  # point-major, key-frames ascending within a point
+    e_pose, e_point = e_pose[order], new_id[e_point[order]].astype(np.int32)
+    pts = pts[seen]
+    fixed_flags = np.zeros(n_keyframes, np.uint8)
+    fixed_flags[[0] + [int(k) for k in fixed]] = 1
+    q_gt = np.array([_quat_from_R(R) for R in Rs])
+    t_gt = np.array(ts)
+    q0, t0 = q_gt.copy(), t_gt.copy()
+    for i in range(n_keyframes):
+        if fixed_flags[i]:
+            continue
+        dR = _rot(*(np.deg2rad(0.3) * rng.normal(size=3)))
+        q0[i] = _quat_from_R(dR @ Rs[i])
+        t0[i] = dR @ ts[i] + 0.01 * rng.normal(size=3)
+    q0 = q0.astype(np.float32).astype(np.float64)
+    t0 = t0.astype(np.float32).astype(np.float64)
+    p0 = (pts + 0.02 * rng.normal(size=pts.shape)).astype(np.float32).astype(np.float64)
+    return dict(n_poses=n_keyframes, n_points=len(pts), n_edges=len(e_pose), pose_q=np.ascontiguousarray(q0),
+                pose_t=np.ascontiguousarray(t0), pose_fixed=fixed_flags, points=np.ascontiguousarray(p0),
+                edge_pose=np.ascontiguousarray(e_pose), edge_point=np.ascontiguousarray(e_point),
+                edge_obs=np.ascontiguousarray(np.concatenate(cols["obs"])[order]),
+                edge_inv_sigma2=np.ascontiguousarray(np.concatenate(cols["is2"])[order]),
+                edge_stereo=np.ascontiguousarray(np.concatenate(cols["stereo"])[order]), fx=fx, fy=fy, cx=cx, cy=cy, bf=bf,
+                huber_mono=float(np.float32(np.sqrt(5.99))),  # thHuber2D = sqrt(5.99), not LocalBundleAdjustment's 5.991 (src/Optimizer.cc:126)
+                huber_stereo=float(np.float32(np.sqrt(7.815))), iterations=10, gt_q=q_gt, gt_t=t_gt, gt_points=pts)
+
+
 def pose_frame(seed, n_obs=300, mono_frac=0.15, outlier_frac=0.1, rot_deg=1.0, trans=0.03, outlier_px=25.0, noise_scale=1.0):
     """Synthetic Optimizer::PoseOptimization problem (reference src/Optimizer.cc:763-1098): one frame looking at `n_obs`
     map points in a 6x4x3 m box, RGB-D ("stereo", 3-D) observations with a fraction without depth (mono, 2-D), pixel noise

@@ -321,6 +321,41 @@ int gfs_lba_linearize_lidar(gfs_lba* h, const gfs_lba_problem* p, const gfs_lba_
  * plane (pa, pb, pc, pd) and s.  Up to cap edges; *n = the pose's edge count. */
 int gfs_lba_fetch_lidar_edges(gfs_lba* h, int pose, int32_t* index, float* plane /* [cap][4] */, float* s, int cap, int32_t* n);
 
+/* Optimizer::GlobalBundleAdjustemnt -> Optimizer::BundleAdjustment (src/Optimizer.cc:47-363): optimizer.optimize(iterations) of the
+ * full map after a loop closure or map merge (LoopClosing::RunGlobalBundleAdjustment, src/LoopClosing.cc:2378: 10 iterations,
+ * &mbStopGBA, bRobust = false) and of the monocular initial map (Tracking::CreateInitialMapMonocular, src/Tracking.cc:2963: 20
+ * iterations).  The graph is LocalBundleAdjustment's (VertexSE3Expmap, marginalised VertexSBAPointXYZ, EdgeSE3ProjectXYZ /
+ * EdgeStereoSE3ProjectXYZ, BlockSolver_6_3, Levenberg), so the problem and the solution are gfs_lba_problem / gfs_lba_solution; the
+ * size is a map's: the reduced pose system is assembled from the pose pairs that share landmarks only and factored as a tiled dense
+ * L D L^T over the whole device (DESIGN.md "Global bundle adjustment"), at every size.
+ *  - No entry check: BundleAdjustment has no `if (*pbStopFlag) return` in front of optimize() (unlike src/Optimizer.cc:1955-1956).
+ *    A flag that is already up gives GFS_OK, iterations_run = 0 and the caller's estimate bit for bit; never GFS_ERR_STOPPED.
+ *    final_chi2 is then the robust chi2 of that estimate and final_lambda 0 (as gfs_lba_solve with iterations <= 0).
+ *  - The flag (setForceStopFlag, src/Optimizer.cc:70-71) is read live where g2o reads it: at the top of every iteration
+ *    (core/sparse_optimizer.cpp, `i < iterations && !terminate()`) -- the first look is the top of iteration 0 -- and after every
+ *    rejected trial that would be retried (core/optimization_algorithm_levenberg.cpp).
+ *  - bRobust = false (src/Optimizer.cc:171-176, 209-214: no setRobustKernel) is huber_mono = huber_stereo = +INFINITY:
+ *    RobustKernelHuber::robustify then takes its `e <= dsqr` branch, rho = (e, 1, 0), and the multiplications by rho[1] = 1.0 are
+ *    exact -- the kernel-free arithmetic.  A finite value is g2o with the kernel (thHuber2D / thHuber3D, :60-61).
+ *  - gfs_gba_create fails cleanly (GFS_ERR_CAPACITY / GFS_ERR_HIP) when the reduced system and the workspaces of max_poses poses do
+ *    not fit the device; gfs_gba_solve returns GFS_ERR_CAPACITY above the handle's limits.
+ *  - edge_chi2 and edge_depth_positive are evaluated at the estimate that is returned.
+ * Second-camera observations are the adaptor's to refuse, as for LocalBundleAdjustment. */
+typedef struct gfs_gba gfs_gba;
+typedef struct {
+  int32_t n_free, panel_rows, panels; /* free poses; rows of a tile of the reduced system; tile rows */
+  int64_t block_pairs, contributions; /* listed 6 x 6 blocks of the lower triangle; (edge, edge) terms in their lists */
+  int64_t system_bytes;               /* bytes of the tiled reduced system */
+  int32_t trials, launches;           /* Levenberg trials run; kernel launches of the call */
+} gfs_gba_info;
+int gfs_gba_create(int device, int max_poses, int max_points, int max_edges, gfs_gba** out);
+void gfs_gba_destroy(gfs_gba* h);
+int gfs_gba_solve(gfs_gba* h, const gfs_lba_problem* p, gfs_lba_solution* s, volatile const int* stop);
+/* The same with the reference's own flag type (a C++ bool: &mbStopGBA). */
+int gfs_gba_solve_bool(gfs_gba* h, const gfs_lba_problem* p, gfs_lba_solution* s, const volatile unsigned char* stop);
+/* What the handle's last gfs_gba_solve did. */
+int gfs_gba_last_info(const gfs_gba* h, gfs_gba_info* info);
+
 /* ============================================================================================
  * 5. Frame helpers next to the hot path — keep GICP input and RGB-D "stereo" coordinates on device
  *      Frame::ConvertDepthToPointCloud(downSample, ...)   src/Frame.cc:590-623

@@ -84,6 +84,23 @@ typedef struct gfs_test_lba_trial {
 } gfs_test_lba_trial;
 int gfs_test_lba_first_trial(gfs_lba* h, const gfs_lba_problem* p, gfs_test_lba_trial* out);
 
+/* GPU test hook: the same tap in gfs_gba_solve's sequence (gfs_test_lba_stop_at_look scripts that entry's flag too; its look 0 is
+ * the top of iteration 0).  Hs is delivered as the packed lower triangle row by row, whatever the tiling, copied out between the
+ * assembly and the in-place factorisation. */
+int gfs_test_gba_first_trial(gfs_gba* h, const gfs_lba_problem* p, gfs_test_lba_trial* out);
+/* Rows of a tile of the tiled reduced system (csrc/gba_tiles.hpp: kP). */
+int gfs_test_gba_panel_rows(void);
+/* Host test hook (no GPU): the structure lists of csrc/gba_lists.hpp for a caller-order problem.  counts = {free poses, listed
+ * blocks, contributions} is always filled; GFS_ERR_CAPACITY when a cap is too small.  order [n_edges]: the caller's edge at each
+ * landmark-major position (the numbering of every edge id below); blk_ij [blocks][2]; blk_begin [blocks + 1]; contrib
+ * [contributions][2] = (e1, e2); pose_begin [free poses + 1]; pose_edges [edges on free poses]. */
+int gfs_test_gba_lists(int n_poses, int n_points, int n_edges, const uint8_t* pose_fixed, const int32_t* edge_pose, const int32_t* edge_point,
+                       int64_t* counts, int32_t* order, int32_t* blk_ij, int64_t* blk_begin, int64_t cap_blocks, int32_t* contrib,
+                       int64_t cap_contrib, int64_t* pose_begin, int32_t* pose_edges);
+/* Host test hook (no GPU): csrc/gba_tiles.hpp for a system of n rows and its element (r, c), r >= c: out = {panels, bytes of the
+ * storage, index of the element's tile, byte offset of the element}. */
+int gfs_test_gba_tile_layout(int64_t n, int64_t r, int64_t c, uint64_t* out);
+
 /* GPU test hook: the stages of the handle's last gfs_frame_cloud_extract(_device) call, as they lie on the device: the scan table
  * (rows of begin, count, pad flags 1 = start | 2 = end, candidates in the scans in front), edge_raw / surf_raw, the two voxel
  * filters' outputs and the two radius filters' outputs.  Their sizes are the call's info; a NULL pointer skips a stage.  Refused
