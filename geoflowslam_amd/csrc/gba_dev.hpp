@@ -1,6 +1,7 @@
 // Global bundle adjustment (gfs_gba_solve): the reduced pose system of a whole map, assembled from structure lists and factored
-// tile by tile over the whole chip.  Included by lba.hip behind the kernels of the local bundle adjustment, whose descriptor
-// (LbaDev), LM state and every other phase kernel (errors, build, begin, dinv, update, decide, finish) this path shares.
+// tile by tile over the whole chip.  Included by lba.hip behind lba_dev.hpp, the kernels of the local bundle adjustment, whose
+// descriptor (LbaDev), LM state and every other phase kernel (errors, build, begin, dinv, update, decide, finish) this path shares;
+// gba_host.hpp queues them.
 //
 // Storage: gba_tiles.hpp (lower-triangle tiles of kP = 96 rows in HBM).  One launch per dependent step, no waiting between
 // workgroups.  Per trial:

@@ -25,7 +25,7 @@ from geoflowslam_amd import synth
 LD = np.longdouble
 LONGDOUBLE_OK = bool(np.finfo(np.longdouble).eps < 2.0 ** -60)
 U = LD(2) ** -53
-K_SCHUR_CHUNK = 64  # kSchurPts = kSchurMPts of csrc/lba.hip
+K_SCHUR_CHUNK = 64  # kSchurPts = kSchurMPts of csrc/lba_dev.hpp
 _EDGE_KEYS = ("edge_pose", "edge_point", "edge_obs", "edge_inv_sigma2", "edge_stereo")
 
 

@@ -1,5 +1,5 @@
 """GPU tests of the LM loop's rejected trials and of the stop flag at every place gfs_lba_solve looks at it (geoflowslam_amd/csrc/lba.hip:
-run(), k_lba_decide, k_lba_restore, kb_lba_decide), on windows that reject trials (tests/lba_stop_support.py).  The flag is SCRIPTED
+solve_window(), lba_solve_batch_impl(); lba_dev.hpp: k_lba_decide, k_lba_restore, kb_lba_decide), on windows that reject trials (tests/lba_stop_support.py).  The flag is SCRIPTED
 (gfs_test_lba_stop_at_look, include/gfs_abi_test.h): it reads as raised from a chosen look on, so every stop is deterministic, and the
 oracle says what it must leave (oracle.lba_solve_scripted: the same look numbering, restated from g2o).
 
