@@ -250,7 +250,7 @@ __global__ __launch_bounds__(kPoseThreads) void k_pose_opt(const PoseFrame* __re
     LmState lm{-1, 2, 0};  // thread 0 only
     // g2o computes the active errors at the top of every iteration; after an ACCEPTED trial they are what that trial has just left
     // in the edges, at the same estimate -- same values, same sum -- so the pass is run only after a rejected one (pop(): estimate
-    // restored, the edges keep the trial's errors) and at the start of a round
+    // restored, the edges keep the trial's errors), after an accepted one whose solve had failed, and at the start of a round
     bool fresh = false;       // uniform
     double currentChi = 0;    // thread 0
     for (int iteration = 0; iteration < F.its && n_active > 0; iteration++) {
@@ -319,7 +319,9 @@ __global__ __launch_bounds__(kPoseThreads) void k_pose_opt(const PoseFrame* __re
           if (!v.accepted)
             for (int k = 0; k < 7; k++) s_T[k] = s_Tb[k];  // pop(): estimate restored, edge errors stay those of the trial
           s_flag[1] = v.again ? 1 : 0;
-          s_flag[2] = v.accepted ? 1 : 0;
+          // (an unsolved trial can be "accepted" too -- currentChi = inf from an edge at z = 0 beats the DBL_MAX an unsolved trial
+          //  counts as -- and then currentChi is that DBL_MAX, not the sum the edges hold: the next iteration computes it afresh)
+          s_flag[2] = v.accepted && s_flag[0] != 0 ? 1 : 0;
         }
         __syncthreads();
         again = s_flag[1] != 0;

@@ -12,6 +12,7 @@
 #include <hip/hip_runtime.h>
 
 #include "g2o_se3_dev.hpp"
+#include "lm_lambda_rule.hpp"
 
 namespace gfs_pose_lm {
 
@@ -359,9 +360,7 @@ struct LmState {
   int nBadLm;
 };
 __device__ __forceinline__ void lm_lambda_init(LmState& L, const double* H21) {  // computeLambdaInit: tau * max |diag(H)|
-  double maxDiagonal = 0;
-  for (int a = 0; a < 6; a++) maxDiagonal = fmax(fabs(H21[a * (a + 1) / 2 + a]), maxDiagonal);
-  L.currentLambda = 1e-5 * maxDiagonal;
+  L.currentLambda = 1e-5 * max_abs_diagonal6(H21);  // std::max's way with a NaN, not fmax's: lm_lambda_rule.hpp
   L.ni = 2;
   L.nBadLm = 0;
 }

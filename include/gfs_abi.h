@@ -404,6 +404,10 @@ int gfs_frame_rgbd(gfs_frame* h, const gfs_keypoint* kps, const float* kps_un_x,
  *    g2o::EdgeStereoSE3ProjectXYZOnlyPose (Thirdparty/g2o/g2o/types/types_six_dof_expmap.cpp:339-404), Huber kernels,
  *    4 rounds x optimize(10) with BlockSolver_6_3 + LinearSolverDense + OptimizationAlgorithmLevenberg.
  *    The two-camera rigid-body branch (:883-951, EdgeSE3ProjectXYZOnlyPoseToBody) is not implemented.
+ *    Non-finite input is not rejected: a NaN / inf observation, point or information and a point at camera z = 0 go through the
+ *    arithmetic as they do in g2o (a NaN chi2 is never above its gate, so the edge stays an inlier and no trial is accepted: the input
+ *    pose comes back, avg_reproj_error is NaN; an inf chi2 leaves after round 0), the call returns, and the default sum order gives
+ *    the sequential code's outputs for them too (tests/test_gpu_pose_step.py).
  * ============================================================================================ */
 typedef struct {
   double q[4], t[3];          /* Tcw = pFrame->GetPose(): unit quaternion (x, y, z, w) and translation cast to double (:784-786) */
