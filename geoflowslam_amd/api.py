@@ -73,6 +73,29 @@ class GbaInfo(C.Structure):  # gfs_gba_info (include/gfs_abi.h)
                 ("contributions", C.c_int64), ("system_bytes", C.c_int64), ("trials", C.c_int32), ("launches", C.c_int32)]
 
 
+class EssentialGraphProblem(C.Structure):  # gfs_essential_graph_problem (include/gfs_abi.h)
+    _fields_ = [("n_vertices", C.c_int32), ("n_edges", C.c_int32), ("n_points", C.c_int32), ("vertex_q", C.c_void_p),
+                ("vertex_t", C.c_void_p), ("vertex_s", C.c_void_p), ("vertex_fixed", C.c_void_p), ("edge_i", C.c_void_p),
+                ("edge_j", C.c_void_p), ("edge_q", C.c_void_p), ("edge_t", C.c_void_p), ("edge_s", C.c_void_p), ("edge_w", C.c_void_p),
+                ("fix_scale", C.c_int32), ("iterations", C.c_int32), ("lambda_init", C.c_double), ("points", C.c_void_p),
+                ("point_ref", C.c_void_p)]
+
+
+class EssentialGraphSolution(C.Structure):
+    _fields_ = [("vertex_q", C.c_void_p), ("vertex_t", C.c_void_p), ("vertex_s", C.c_void_p), ("points", C.c_void_p),
+                ("edge_chi2", C.c_void_p), ("iterations_run", C.c_int32), ("final_chi2", C.c_double), ("final_lambda", C.c_double)]
+
+
+class EssentialGraphInfo(C.Structure):
+    _fields_ = [("n_free", C.c_int32), ("dimension", C.c_int32), ("panels", C.c_int32), ("blocks", C.c_int64), ("trials", C.c_int32),
+                ("launches", C.c_int32), ("system_bytes", C.c_int64)]
+
+
+class EssentialGraphTrial(C.Structure):  # gfs_test_essential_graph_trial (include/gfs_abi_test.h)
+    _fields_ = [("H", C.c_void_p), ("b", C.c_void_p), ("x", C.c_void_p), ("chi2", C.c_double), ("trial_chi2", C.c_double),
+                ("scale", C.c_double), ("n_free", C.c_int32), ("dimension", C.c_int32), ("solve_ok", C.c_int32)]
+
+
 class LbaLidar(C.Structure):
     _fields_ = [("map", C.c_void_p), ("pose_local", C.c_void_p), ("matches_inliers", C.c_void_p), ("cloud_begin", C.c_void_p),
                 ("cloud", C.c_void_p), ("two_camera", C.c_int32)]
@@ -593,6 +616,8 @@ ABI_SYMBOLS = [
     "gfs_lba_fetch_lidar_edges", "gfs_test_lba_stop_at_look", "gfs_test_lba_last_looks", "gfs_test_lba_first_trial",
     "gfs_gba_create", "gfs_gba_destroy", "gfs_gba_solve", "gfs_gba_solve_bool", "gfs_gba_last_info", "gfs_test_gba_first_trial",
     "gfs_test_gba_panel_rows", "gfs_test_gba_lists", "gfs_test_gba_tile_layout",
+    "gfs_essential_graph_create", "gfs_essential_graph_destroy", "gfs_essential_graph_optimize", "gfs_essential_graph_correct_points",
+    "gfs_essential_graph_last_info", "gfs_test_essential_graph_first_trial", "gfs_test_essential_graph_lists",
     "gfs_frame_create", "gfs_frame_destroy", "gfs_depth_to_cloud", "gfs_depth_to_cloud_batch_device", "gfs_depth_convert_u16_batch_device", "gfs_stereo_from_rgbd",
     "gfs_stereo_from_rgbd_batch_device",
     "gfs_pose_create", "gfs_pose_destroy", "gfs_pose_optimize", "gfs_pose_set_sum_order",
@@ -698,6 +723,14 @@ def lib():
             L.gfs_test_gba_panel_rows.argtypes = []
             L.gfs_test_gba_lists.argtypes = [i, i, i, vp, vp, vp, vp, vp, vp, vp, C.c_int64, vp, C.c_int64, vp, vp]
             L.gfs_test_gba_tile_layout.argtypes = [C.c_int64, C.c_int64, C.c_int64, vp]
+        if hasattr(L, "gfs_essential_graph_create"):
+            L.gfs_essential_graph_create.argtypes = [i, i, i, i, C.POINTER(vp)]
+            L.gfs_essential_graph_destroy.argtypes = [vp]
+            L.gfs_essential_graph_optimize.argtypes = [vp, C.POINTER(EssentialGraphProblem), C.POINTER(EssentialGraphSolution)]
+            L.gfs_essential_graph_correct_points.argtypes = [vp, i, vp, vp, i, vp, vp, vp]
+            L.gfs_essential_graph_last_info.argtypes = [vp, C.POINTER(EssentialGraphInfo)]
+            L.gfs_test_essential_graph_first_trial.argtypes = [vp, C.POINTER(EssentialGraphProblem), C.POINTER(EssentialGraphTrial)]
+            L.gfs_test_essential_graph_lists.argtypes = [i, i, vp, vp, vp, vp, vp, vp, vp, C.c_int64, vp, C.c_int64]
         if hasattr(L, "gfs_lba_solve_lidar"):
             L.gfs_lba_lidar_reserve.argtypes = [vp, i]
             L.gfs_lba_solve_lidar.argtypes = [vp, C.POINTER(LbaProblem), C.POINTER(LbaLidar), C.POINTER(LbaSolution), vp, vp]
@@ -1244,6 +1277,108 @@ class GlobalOptimizer:
         I = GbaInfo()
         _check(lib().gfs_gba_last_info(self.h, C.byref(I)), "gfs_gba_last_info")
         return {k: int(getattr(I, k)) for k, _ in GbaInfo._fields_}
+
+
+# optimize(20), setUserLambdaInit(1e-16), covisibility weight minFeat = 100, the ICP edges' 3 x information (reference
+# src/Optimizer.cc:2362, :2059, :2145, :2306)
+ESSENTIAL_GRAPH_ITERATIONS = 20
+ESSENTIAL_GRAPH_LAMBDA_INIT = 1e-16
+ESSENTIAL_GRAPH_MIN_FEAT = 100
+ESSENTIAL_GRAPH_ICP_WEIGHT = 3.0
+
+
+def _essential_graph_problem(prob):
+    P = EssentialGraphProblem()
+    keep = {}
+    for name, dt in (("vertex_q", np.float64), ("vertex_t", np.float64), ("vertex_s", np.float64), ("vertex_fixed", np.uint8),
+                     ("edge_i", np.int32), ("edge_j", np.int32), ("edge_q", np.float64), ("edge_t", np.float64), ("edge_s", np.float64),
+                     ("edge_w", np.float64), ("points", np.float32), ("point_ref", np.int32)):
+        default = np.zeros((0, 3), np.float32) if name == "points" else np.zeros(0, np.int32)
+        keep[name] = np.ascontiguousarray(prob.get(name, default), dt)
+        setattr(P, name, keep[name].ctypes.data)
+    P.n_vertices, P.n_edges, P.n_points = len(keep["vertex_s"]), len(keep["edge_i"]), len(keep["point_ref"])
+    P.fix_scale = int(bool(prob.get("fix_scale", True)))
+    P.iterations = int(prob.get("iterations", ESSENTIAL_GRAPH_ITERATIONS))
+    P.lambda_init = float(prob.get("lambda_init", ESSENTIAL_GRAPH_LAMBDA_INIT))
+    return P, keep
+
+
+def essential_graph_lists(vertex_fixed, edge_i, edge_j):
+    """Host test hook (gfs_test_essential_graph_lists, no GPU): the structure lists of the essential graph's pose system ->
+    dict(n_free, free_index [V], blk_ij [B, 2], blk_begin [B + 1], contrib [C] = 4 edge + kind)."""
+    fixed = np.ascontiguousarray(vertex_fixed, np.uint8)
+    ei, ej = np.ascontiguousarray(edge_i, np.int32), np.ascontiguousarray(edge_j, np.int32)
+    V, E = len(fixed), len(ei)
+    counts = np.zeros(3, np.int64)
+    rc = lib().gfs_test_essential_graph_lists(V, E, _p(fixed), _p(ei), _p(ej), _p(counts), None, None, None, 0, None, 0)
+    if rc not in (0, -4):
+        _check(rc, "gfs_test_essential_graph_lists")
+    F, B, Cn = (int(v) for v in counts)
+    fi, blk, beg, con = np.zeros(V + 1, np.int32), np.zeros((B + 1, 2), np.int32), np.zeros(B + 2, np.int64), np.zeros(Cn + 1, np.int32)
+    _check(lib().gfs_test_essential_graph_lists(V, E, _p(fixed), _p(ei), _p(ej), _p(counts), _p(fi), _p(blk), _p(beg), B, _p(con), Cn),
+           "gfs_test_essential_graph_lists")
+    return dict(n_free=F, free_index=fi[:V], blk_ij=blk[:B], blk_begin=beg[:B + 1], contrib=con[:Cn])
+
+
+def essential_graph_first_trial(opt, prob, fill=np.nan):
+    """Test hook (gfs_test_essential_graph_first_trial): the first Levenberg trial of `prob` on the EssentialGraphOptimizer `opt`,
+    through the product's launch sequence -> dict(H (packed lower triangle, lambda on the diagonal), b, x, chi2, trial_chi2, scale,
+    n_free, dimension, solve_ok).  The arrays are pre-written with `fill`."""
+    P, keep = _essential_graph_problem(prob)
+    n = (6 if P.fix_scale else 7) * int((keep["vertex_fixed"] == 0).sum())
+    buf = dict(H=np.full(n * (n + 1) // 2 + 1, fill), b=np.full(n + 1, fill), x=np.full(n + 1, fill))
+    T = EssentialGraphTrial()
+    for k, v in buf.items():
+        setattr(T, k, v.ctypes.data)
+    _check(lib().gfs_test_essential_graph_first_trial(opt.h, C.byref(P), C.byref(T)), "gfs_test_essential_graph_first_trial")
+    return dict(H=buf["H"][:-1].copy(), b=buf["b"][:-1].copy(), x=buf["x"][:-1].copy(), chi2=T.chi2, trial_chi2=T.trial_chi2,
+                scale=T.scale, n_free=int(T.n_free), dimension=int(T.dimension), solve_ok=int(T.solve_ok))
+
+
+class EssentialGraphOptimizer:
+    """The numeric core of ORB_SLAM3::Optimizer::OptimizeEssentialGraph (reference src/Optimizer.cc:2042-2413) on a flattened Sim3
+    pose graph (gfs_essential_graph_problem): Levenberg on VertexSim3Expmap / EdgeSim3 with g2o's numeric Jacobians, the pose system
+    tiled over the whole device, then the map points moved with their reference key-frames."""
+
+    def __init__(self, max_vertices=512, max_edges=8192, max_points=65536, device=0):
+        self.h = C.c_void_p()
+        _check(lib().gfs_essential_graph_create(device, max_vertices, max_edges, max_points, C.byref(self.h)), "gfs_essential_graph_create")
+
+    def close(self):
+        if getattr(self, "h", None) and _lib is not None:
+            _lib.gfs_essential_graph_destroy(self.h)
+        self.h = None
+
+    __del__ = close
+
+    def OptimizeEssentialGraph(self, prob):
+        """prob: vertex_q [V, 4] (x, y, z, w), vertex_t, vertex_s, vertex_fixed; edge_i, edge_j, edge_q, edge_t, edge_s, edge_w in the
+        reference's creation order; fix_scale, iterations (20), lambda_init (1e-16); points [M, 3] float32 and point_ref [M] (optional)
+        -> dict(vertex_q, vertex_t, vertex_s, points, edge_chi2, iterations_run, final_chi2, final_lambda)."""
+        P, keep = _essential_graph_problem(prob)
+        out = dict(vertex_q=np.zeros((P.n_vertices, 4)), vertex_t=np.zeros((P.n_vertices, 3)), vertex_s=np.zeros(P.n_vertices),
+                   points=np.zeros((P.n_points, 3), np.float32), edge_chi2=np.zeros(P.n_edges))
+        S = EssentialGraphSolution()
+        for k, v in out.items():
+            setattr(S, k, v.ctypes.data)
+        _check(lib().gfs_essential_graph_optimize(self.h, C.byref(P), C.byref(S)), "gfs_essential_graph_optimize")
+        out.update(iterations_run=S.iterations_run, final_chi2=S.final_chi2, final_lambda=S.final_lambda)
+        return out
+
+    def correct_points(self, before, after, points, point_ref):
+        """correctedSwr.map(Srw.map(P)) alone: before / after [V, 8] = (q, t, s) of every vertex before and after a correction,
+        points [M, 3] float32, point_ref [M] (-1: as is) -> [M, 3] float32."""
+        b, a = np.ascontiguousarray(before, np.float64), np.ascontiguousarray(after, np.float64)
+        pts, ref = np.ascontiguousarray(points, np.float32), np.ascontiguousarray(point_ref, np.int32)
+        out = np.zeros((len(ref), 3), np.float32)
+        _check(lib().gfs_essential_graph_correct_points(self.h, len(b), _p(b), _p(a), len(ref), _p(pts), _p(ref), _p(out)),
+               "gfs_essential_graph_correct_points")
+        return out
+
+    def last_info(self):
+        I = EssentialGraphInfo()
+        _check(lib().gfs_essential_graph_last_info(self.h, C.byref(I)), "gfs_essential_graph_last_info")
+        return {k: int(getattr(I, k)) for k, _ in EssentialGraphInfo._fields_}
 
 
 class Optimizer:

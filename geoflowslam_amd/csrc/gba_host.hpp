@@ -147,6 +147,25 @@ static int gba_map(gfs_gba* g, const gfs_lba_problem* p, const HostPrep& P, LbaD
   return GFS_OK;
 }
 
+// The tiled L D L^T of an assembled system and its substitutions, queued on `ph` (anything with a stream `s` and a `launches` count):
+// panel by panel, then z = D^-1 y, then the back substitution from the last panel.  The kernels read D.S and D.xp and G's n, T, tiles,
+// W and rhs, nothing else: gfs_gba_solve and gfs_essential_graph_optimize (eg_host.hpp) both come through here.
+extern "C++" template <class Queue>
+int gba_factor_and_solve(Queue& ph, const LbaDev& D, const GbaDev& G) {
+  const int T = G.T;
+  for (int q = 0; q < T; q++) {
+    LM_LAUNCH(ph, "k_gba_diag", k_gba_diag, dim3(1), dim3(kMk), kGbaTileLds, D, G, q);
+    const int m = T - 1 - q;
+    if (m > 0) {
+      LM_LAUNCH(ph, "k_gba_panel", k_gba_panel, dim3(m), dim3(kMk), 2 * kGbaTileLds, D, G, q);
+      LM_LAUNCH(ph, "k_gba_trail", k_gba_trail, dim3((unsigned)((size_t)m * (m + 1) / 2)), dim3(kMk), 0, D, G, q);
+    }
+  }
+  LM_LAUNCH(ph, "k_gba_scale", k_gba_scale, dim3(gfs::div_up(T * kP, kMk)), dim3(kMk), 0, D, G);
+  for (int q = T; q >= 1; q--) LM_LAUNCH(ph, "k_gba_back", k_gba_back, dim3(q == T ? 1 : q), dim3(kMk), kGbaTileLds, D, G, q);
+  return GFS_OK;
+}
+
 // The reduced system of a global trial (LmPhases::trial), gba_dev.hpp's: the tiles cleared and assembled from the lists, factored
 // panel by panel, the substitutions.  Nothing is ever queued ahead of a verdict here, so there is no gate.
 struct GbaReduced {
@@ -167,17 +186,7 @@ struct GbaReduced {
       GFS_HIP(hipMemcpyAsync(tap->Hs, d_tap->p, nt * sizeof(double), hipMemcpyDeviceToHost, ph.s));
       GFS_HIP(hipMemcpyAsync(tap->bs, d_tap->p + nt, n * sizeof(double), hipMemcpyDeviceToHost, ph.s));
     }
-    for (int q = 0; q < T; q++) {
-      LM_LAUNCH(ph, "k_gba_diag", k_gba_diag, dim3(1), dim3(kMk), kGbaTileLds, D, G, q);
-      const int m = T - 1 - q;
-      if (m > 0) {
-        LM_LAUNCH(ph, "k_gba_panel", k_gba_panel, dim3(m), dim3(kMk), 2 * kGbaTileLds, D, G, q);
-        LM_LAUNCH(ph, "k_gba_trail", k_gba_trail, dim3((unsigned)((size_t)m * (m + 1) / 2)), dim3(kMk), 0, D, G, q);
-      }
-    }
-    LM_LAUNCH(ph, "k_gba_scale", k_gba_scale, dim3(gfs::div_up(T * kP, kMk)), dim3(kMk), 0, D, G);
-    for (int q = T; q >= 1; q--) LM_LAUNCH(ph, "k_gba_back", k_gba_back, dim3(q == T ? 1 : q), dim3(kMk), kGbaTileLds, D, G, q);
-    return GFS_OK;
+    return gba_factor_and_solve(ph, D, G);
   }
 };
 

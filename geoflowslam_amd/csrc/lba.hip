@@ -29,6 +29,8 @@
 #include "lba_dev.hpp"
 #include "gba_dev.hpp"  // the global bundle adjustment's assembly, tiled factorisation and substitutions (gfs_gba_solve)
 #include "gba_lists.hpp"
+#include "eg_dev.hpp"  // the essential graph's linearisation, assembly, update and point correction (gfs_essential_graph_optimize)
+#include "eg_lists.hpp"
 #include "lba_host.hpp"
 
 namespace {
@@ -789,3 +791,4 @@ int gfs_test_lba_first_trial(gfs_lba* h, const gfs_lba_problem* p, gfs_test_lba_
 }  // extern "C"
 
 #include "gba_host.hpp"
+#include "eg_host.hpp"

@@ -34,6 +34,7 @@
 #include "../../include/gfs_abi.h"
 #include "../csrc/fuse_rule.hpp"
 #include "../csrc/map_point_rule.hpp"
+#include "../csrc/sim3_dev.hpp"
 #include "../csrc/triangulate_rule.hpp"
 
 namespace gfs_host {
@@ -2269,6 +2270,286 @@ class GlobalBundleAdjuster {
 
  private:
   gfs_gba* h_ = nullptr;
+};
+
+// ------------------------------------------------------------------------------------------------------------------------
+// Optimizer::OptimizeEssentialGraph(Map*, pLoopKF, pCurKF, NonCorrectedSim3, CorrectedSim3, LoopConnections, bFixScale,
+//                                   bUseICPConstraint)                                       reference src/Optimizer.cc:2042-2413
+// as real code around the flat solver, line for line.  Vertices (:2099-2136): one per key-frame that is not bad, the estimate from
+// CorrectedSim3 or GetPose().cast<double>() with scale 1, the init key-frame fixed.  Edges in creation order: the loop connections
+// (:2147-2186; the weight test spares the (pCurKF, pLoopKF) pair; a missing vertex skips the edge, :2170), then per key-frame --
+// bad ones too, this loop has no isBad() test -- the spanning-tree edge (a missing vertex ends the KEY-FRAME, the `continue` of
+// :2224-2225 sits in the key-frame loop), the loop edges to older key-frames (:2236-2290; a missing vertex skips the edge, :2254)
+// each followed, with bUseICPConstraint, by a registration whose accepted result becomes an edge of information 3 I, the
+// covisibility edges of weight >= 100 that are neither parent nor child nor already inserted (:2294-2331; :2319 skips one edge), and
+// the inertial edge to mPrevKF (:2334-2355; a missing vertex ends the key-frame there too, :2345-2347).  Every measurement is
+// Sjw * Swi with NonCorrectedSim3 where it has the key-frame, vScw else.  Then optimize(20), and under mMutexMapUpdate the poses
+// (:2369-2383) and every map point that is not bad through its reference key-frame (:2387-2409), UpdateNormalAndDepth, and
+// IncreaseChangeIndex.  A reference key-frame without a vertex has default Sim3s in vScw and vCorrectedSwc: the point keeps its
+// position (reference -1).
+//
+// Classes as for BundleAdjustment, plus KeyFrame::GetParent(), GetLoopEdges(), GetCovisiblesByWeight(int), hasChild(), GetWeight(),
+// bImu, mPrevKF; MapPoint::mnCorrectedByKF, mnCorrectedReference, GetReferenceKeyFrame(); Map::GetAllKeyFrames(), GetAllMapPoints();
+// the two KeyFrameAndPose maps and LoopConnections as the reference passes them; and of `Access`:
+//     static void pose_d(const KeyFrame*, double q_xyzw[4], double t[3]);  // GetPose().cast<double>(): unit_quaternion(), translation()
+//     static void sim3(const Sim3&, double S[8]);          // g2o::Sim3 -> rotation().coeffs() (x, y, z, w), translation(), scale()
+//     static void set_pose(KeyFrame*, const float q_xyzw[4], const float t[3]);   // SetPose(Sophus::SE3f(q, t))
+//     static void world_pos / set_world_pos                                       // as above
+// `solve(problem, solution)` is the numeric core (EssentialGraphOptimizer::solve: gfs_essential_graph_optimize on the GPU);
+// `reg(pLKF, pKF, init_T_target_source[16]) -> gfs_gicp_result` is mpRegistration->RegisterPointClouds(*pLKF->source_points,
+// *pKF->source_points, init_T).
+// ------------------------------------------------------------------------------------------------------------------------
+constexpr int kEssentialGraphMinFeat = 100;            // :2075
+constexpr int kEssentialGraphIterations = 20;          // :2362
+constexpr double kEssentialGraphLambdaInit = 1e-16;    // :2058
+constexpr double kEssentialGraphIcpInformation = 3.0;  // :2285
+constexpr uint64_t kEssentialGraphIcpMinInliers = 100;  // :2277
+constexpr double kEssentialGraphIcpMaxError = 0.1;     // :2278
+
+struct EssentialGraphFlat {
+  std::vector<double> vq, vt, vs, eq, et, es, ew;
+  std::vector<uint8_t> vfixed;
+  std::vector<int32_t> ei, ej, pref;
+  std::vector<float> points;
+  void add_edge(int32_t i, int32_t j, const double S[8], double w) {
+    ei.push_back(i);
+    ej.push_back(j);
+    eq.insert(eq.end(), S, S + 4);
+    et.insert(et.end(), S + 4, S + 7);
+    es.push_back(S[7]);
+    ew.push_back(w);
+  }
+};
+
+template <class Access, class Map, class KeyFrame, class KeyFrameAndPose, class LoopConnectionsT, class Solve, class Register>
+void OptimizeEssentialGraph(Solve&& solve, Register&& reg, Map* pMap, KeyFrame* pLoopKF, KeyFrame* pCurKF, const KeyFrameAndPose& NonCorrectedSim3,
+                            const KeyFrameAndPose& CorrectedSim3, const LoopConnectionsT& LoopConnections, const bool& bFixScale,
+                            const bool& bUseICPConstraint) {
+  const auto vpKFs = pMap->GetAllKeyFrames();
+  const auto vpMPs = pMap->GetAllMapPoints();
+  const int minFeat = kEssentialGraphMinFeat;
+  EssentialGraphFlat F;
+  std::map<unsigned long, int32_t> vertex;  // mnId -> flat vertex: optimizer.vertex(id) != NULL
+  std::vector<double> vScw;                 // [vertex][8]
+  auto has = [&](unsigned long id) { return vertex.find(id) != vertex.end(); };
+  auto scw = [&](unsigned long id) { return &vScw[8 * (size_t)vertex.find(id)->second]; };
+  // ---- key-frame vertices (:2099-2136)
+  for (size_t i = 0, iend = vpKFs.size(); i < iend; i++) {
+    KeyFrame* pKF = vpKFs[i];
+    if (pKF->isBad()) continue;
+    double S[8];
+    auto it = CorrectedSim3.find(pKF);
+    if (it != CorrectedSim3.end()) {
+      Access::sim3(it->second, S);
+    } else {
+      Access::pose_d(pKF, S, S + 4);
+      S[7] = 1.0;
+    }
+    vertex[pKF->mnId] = (int32_t)F.vs.size();
+    vScw.insert(vScw.end(), S, S + 8);
+    F.vq.insert(F.vq.end(), S, S + 4);
+    F.vt.insert(F.vt.end(), S + 4, S + 7);
+    F.vs.push_back(S[7]);
+    F.vfixed.push_back(pKF->mnId == pMap->GetInitKFid() ? 1 : 0);
+  }
+  std::set<std::pair<unsigned long, unsigned long>> sInsertedEdges;
+  // the Sim3 an edge is measured on: NonCorrectedSim3 where it has the key-frame, vScw else (a default Sim3 without a vertex)
+  auto measured = [&](KeyFrame* pKF, double S[8]) {
+    auto it = NonCorrectedSim3.find(pKF);
+    if (it != NonCorrectedSim3.end()) {
+      Access::sim3(it->second, S);
+    } else if (has(pKF->mnId)) {
+      std::memcpy(S, scw(pKF->mnId), 8 * sizeof(double));
+    } else {
+      const double I[8] = {0, 0, 0, 1, 0, 0, 0, 1};
+      std::memcpy(S, I, sizeof(I));
+    }
+  };
+  // ---- loop edges (:2147-2186)
+  for (auto mit = LoopConnections.begin(), mend = LoopConnections.end(); mit != mend; mit++) {
+    KeyFrame* pKF = mit->first;
+    const unsigned long nIDi = pKF->mnId;
+    const auto& spConnections = mit->second;
+    for (auto sit = spConnections.begin(), send = spConnections.end(); sit != send; sit++) {
+      const unsigned long nIDj = (*sit)->mnId;
+      if ((nIDi != pCurKF->mnId || nIDj != pLoopKF->mnId) && pKF->GetWeight(*sit) < minFeat) continue;
+      if (!has(nIDj) || !has(nIDi)) continue;
+      double Swi[8], Sji[8];
+      gfs_sim3::sim3_inverse(scw(nIDi), Swi);
+      gfs_sim3::sim3_mul(scw(nIDj), Swi, Sji);
+      F.add_edge(vertex[nIDi], vertex[nIDj], Sji, 1.0);
+      sInsertedEdges.insert(std::make_pair(std::min(nIDi, nIDj), std::max(nIDi, nIDj)));
+    }
+  }
+  // ---- normal edges (:2190-2356)
+  for (size_t i = 0, iend = vpKFs.size(); i < iend; i++) {
+    KeyFrame* pKF = vpKFs[i];
+    const unsigned long nIDi = pKF->mnId;
+    double Siw[8], Swi[8];
+    measured(pKF, Siw);
+    gfs_sim3::sim3_inverse(Siw, Swi);
+    KeyFrame* pParentKF = pKF->GetParent();
+    // spanning tree edge
+    if (pParentKF) {
+      const unsigned long nIDj = pParentKF->mnId;
+      double Sjw[8], Sji[8];
+      measured(pParentKF, Sjw);
+      gfs_sim3::sim3_mul(Sjw, Swi, Sji);
+      if (!has(nIDj) || !has(nIDi)) continue;  // (the rest of this key-frame goes with it)
+      F.add_edge(vertex[nIDi], vertex[nIDj], Sji, 1.0);
+    }
+    // loop edges
+    const auto sLoopEdges = pKF->GetLoopEdges();
+    for (auto sit = sLoopEdges.begin(), send = sLoopEdges.end(); sit != send; sit++) {
+      KeyFrame* pLKF = *sit;
+      if (pLKF->mnId < pKF->mnId) {
+        double Slw[8], Sli[8];
+        measured(pLKF, Slw);
+        gfs_sim3::sim3_mul(Slw, Swi, Sli);
+        if (!has(pLKF->mnId) || !has(nIDi)) continue;
+        F.add_edge(vertex[nIDi], vertex[pLKF->mnId], Sli, 1.0);
+        if (bUseICPConstraint) {
+          double R[9], init_T[16] = {0};  // column-major: linear() = Sli.rotation().toRotationMatrix(), translation() = t / s
+          gfs_sim3::quat_to_R(Sli, R);
+          for (int r = 0; r < 3; r++)
+            for (int c = 0; c < 3; c++) init_T[4 * c + r] = R[3 * r + c];
+          for (int r = 0; r < 3; r++) init_T[12 + r] = Sli[4 + r] / Sli[7];
+          init_T[15] = 1.0;
+          const gfs_gicp_result result = reg(pLKF, pKF, init_T);
+          double icp[8], Ricp[9];
+          for (int r = 0; r < 3; r++)
+            for (int c = 0; c < 3; c++) Ricp[3 * r + c] = result.T_target_source[4 * c + r];
+          gfs_sim3::R_to_quat(Ricp, icp);
+          for (int r = 0; r < 3; r++) icp[4 + r] = result.T_target_source[12 + r];
+          icp[7] = 1.0;
+          if (result.converged && result.num_inliers > kEssentialGraphIcpMinInliers &&
+              (result.error / result.num_inliers) < kEssentialGraphIcpMaxError)
+            F.add_edge(vertex[nIDi], vertex[pLKF->mnId], icp, kEssentialGraphIcpInformation);
+        }
+      }
+    }
+    // covisibility graph edges
+    const auto vpConnectedKFs = pKF->GetCovisiblesByWeight(minFeat);
+    for (auto vit = vpConnectedKFs.begin(); vit != vpConnectedKFs.end(); vit++) {
+      KeyFrame* pKFn = *vit;
+      if (pKFn && pKFn != pParentKF && !pKF->hasChild(pKFn)) {
+        if (!pKFn->isBad() && pKFn->mnId < pKF->mnId) {
+          if (sInsertedEdges.count(std::make_pair(std::min(pKF->mnId, pKFn->mnId), std::max(pKF->mnId, pKFn->mnId)))) continue;
+          double Snw[8], Sni[8];
+          measured(pKFn, Snw);
+          gfs_sim3::sim3_mul(Snw, Swi, Sni);
+          if (!has(pKFn->mnId) || !has(nIDi)) continue;
+          F.add_edge(vertex[nIDi], vertex[pKFn->mnId], Sni, 1.0);
+        }
+      }
+    }
+    // inertial edges if inertial
+    if (pKF->bImu && pKF->mPrevKF) {
+      double Spw[8], Spi[8];
+      measured(pKF->mPrevKF, Spw);
+      gfs_sim3::sim3_mul(Spw, Swi, Spi);
+      if (!has(pKF->mPrevKF->mnId) || !has(nIDi)) continue;
+      F.add_edge(vertex[nIDi], vertex[pKF->mPrevKF->mnId], Spi, 1.0);
+    }
+  }
+  // ---- the map points and their reference vertices (:2387-2401)
+  F.points.resize(3 * vpMPs.size());
+  F.pref.assign(vpMPs.size(), -1);
+  for (size_t i = 0, iend = vpMPs.size(); i < iend; i++) {
+    auto* pMP = vpMPs[i];
+    if (pMP->isBad()) continue;
+    unsigned long nIDr;
+    if (pMP->mnCorrectedByKF == pCurKF->mnId)
+      nIDr = pMP->mnCorrectedReference;
+    else
+      nIDr = pMP->GetReferenceKeyFrame()->mnId;
+    Access::world_pos(pMP, &F.points[3 * i]);
+    if (has(nIDr)) F.pref[i] = vertex[nIDr];
+  }
+  if (F.vs.empty()) return;  // (the reference would optimise an empty graph and move nothing)
+  // ---- optimizer.initializeOptimization(); optimizer.optimize(20)
+  gfs_essential_graph_problem P{};
+  P.n_vertices = (int32_t)F.vs.size();
+  P.n_edges = (int32_t)F.ei.size();
+  P.n_points = (int32_t)F.pref.size();
+  P.vertex_q = F.vq.data();
+  P.vertex_t = F.vt.data();
+  P.vertex_s = F.vs.data();
+  P.vertex_fixed = F.vfixed.data();
+  P.edge_i = F.ei.data();
+  P.edge_j = F.ej.data();
+  P.edge_q = F.eq.data();
+  P.edge_t = F.et.data();
+  P.edge_s = F.es.data();
+  P.edge_w = F.ew.data();
+  P.fix_scale = bFixScale ? 1 : 0;
+  P.iterations = kEssentialGraphIterations;
+  P.lambda_init = kEssentialGraphLambdaInit;
+  P.points = F.points.data();
+  P.point_ref = F.pref.data();
+  std::vector<double> oq(F.vq.size()), ot(F.vt.size()), os(F.vs.size());
+  std::vector<float> op(F.points.size());
+  gfs_essential_graph_solution S{};
+  S.vertex_q = oq.data();
+  S.vertex_t = ot.data();
+  S.vertex_s = os.data();
+  S.points = op.data();
+  solve(P, S);
+  std::unique_lock<std::mutex> lock(pMap->mMutexMapUpdate);
+  // SE3 pose recovering.  Sim3: [sR t; 0 1] -> SE3: [R t/s; 0 1]  (:2369-2383)
+  for (size_t i = 0; i < vpKFs.size(); i++) {
+    KeyFrame* pKFi = vpKFs[i];
+    if (!pKFi) continue;
+    if (!has(pKFi->mnId)) continue;
+    const size_t k = (size_t)vertex[pKFi->mnId];
+    float q[4], t[3];
+    for (int c = 0; c < 4; c++) q[c] = (float)oq[4 * k + c];
+    for (int c = 0; c < 3; c++) t[c] = (float)ot[3 * k + c] / (float)os[k];  // translation().cast<float>() / s
+    Access::set_pose(pKFi, q, t);
+  }
+  // correct points (:2387-2409)
+  for (size_t i = 0, iend = vpMPs.size(); i < iend; i++) {
+    auto* pMP = vpMPs[i];
+    if (pMP->isBad()) continue;
+    Access::set_world_pos(pMP, &op[3 * i]);
+    pMP->UpdateNormalAndDepth();
+  }
+  pMap->IncreaseChangeIndex();
+}
+
+// numeric core of Optimizer::OptimizeEssentialGraph: the pose graph on the device (gfs_essential_graph_optimize).  The ICP edges come
+// from RegistrationGICP above, with `static const float* source_points(const KeyFrame*, int* n)` of Access ([n][4] floats).
+class EssentialGraphOptimizer {
+ public:
+  EssentialGraphOptimizer(int max_vertices = 4096, int max_edges = 65536, int max_points = 1048576, int device = 0) : device_(device) {
+    check(gfs_essential_graph_create(device, max_vertices, max_edges, max_points, &h_), "gfs_essential_graph_create");
+  }
+  ~EssentialGraphOptimizer() { gfs_essential_graph_destroy(h_); }
+  EssentialGraphOptimizer(const EssentialGraphOptimizer&) = delete;
+  EssentialGraphOptimizer& operator=(const EssentialGraphOptimizer&) = delete;
+  void solve(const gfs_essential_graph_problem& p, gfs_essential_graph_solution& s) {
+    check(gfs_essential_graph_optimize(h_, &p, &s), "gfs_essential_graph_optimize");
+  }
+  template <class Access, class Map, class KeyFrame, class KeyFrameAndPose, class LoopConnectionsT>
+  void OptimizeEssentialGraph(Map* pMap, KeyFrame* pLoopKF, KeyFrame* pCurKF, const KeyFrameAndPose& NonCorrectedSim3,
+                              const KeyFrameAndPose& CorrectedSim3, const LoopConnectionsT& LoopConnections, const bool& bFixScale,
+                              const bool& bUseICPConstraint = false) {
+    auto reg = [this](const KeyFrame* pLKF, const KeyFrame* pKF, const double init_T[16]) {
+      if (!gicp_) gicp_.reset(new RegistrationGICP(65536, device_));
+      int nt = 0, ns = 0;
+      const float* target = Access::source_points(pLKF, &nt);
+      const float* source = Access::source_points(pKF, &ns);
+      return gicp_->RegisterPointClouds(target, nt, source, ns, init_T);
+    };
+    gfs_host::OptimizeEssentialGraph<Access>([this](const gfs_essential_graph_problem& p, gfs_essential_graph_solution& s) { this->solve(p, s); },
+                                             reg, pMap, pLoopKF, pCurKF, NonCorrectedSim3, CorrectedSim3, LoopConnections, bFixScale,
+                                             bUseICPConstraint);
+  }
+
+ private:
+  gfs_essential_graph* h_ = nullptr;
+  std::unique_ptr<RegistrationGICP> gicp_;
+  int device_;
 };
 
 }  // namespace gfs_host

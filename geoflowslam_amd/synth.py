@@ -1085,3 +1085,99 @@ def clahe_image(seed, width, height):
     ph, pw, y0, x0 = max(height // 3, 1), max(width // 3, 1), height // 4, width // 2
     img[y0:y0 + ph, x0:x0 + pw] = 96 + rng.integers(0, 4, img[y0:y0 + ph, x0:x0 + pw].shape)
     return np.clip(np.rint(img), 0, 255).astype(np.uint8)
+
+
+def _quat_xyzw(R):
+    """unit quaternion (x, y, z, w), w >= 0, of a rotation matrix"""
+    w = np.sqrt(max(0.0, 1.0 + R[0, 0] + R[1, 1] + R[2, 2])) / 2
+    if w > 1e-6:
+        q = np.array([(R[2, 1] - R[1, 2]) / (4 * w), (R[0, 2] - R[2, 0]) / (4 * w), (R[1, 0] - R[0, 1]) / (4 * w), w])
+    else:  # half a turn: the axis from the diagonal
+        x, y, z = np.sqrt(np.maximum(0.0, (np.diag(R) + 1) / 2))
+        q = np.array([x, np.copysign(y, R[0, 1]), np.copysign(z, R[0, 2]), 0.0])
+    return q / np.linalg.norm(q)
+
+
+def pose_graph(seed, n_keyframes, fix_scale=True, drift=0.05, loop=0, icp_edges=False, n_corrected=3, points_per_kf=20, radius=5.0):
+    """Synthetic input of Optimizer::OptimizeEssentialGraph (reference src/Optimizer.cc:2042-2413), flattened the way the adaptor
+    flattens a map: a closed ring of `n_keyframes` key-frames (2 `radius` m across) whose odometry accumulated about `drift` radians
+    of heading error and 2 % of scale error by the time the last key-frame sees key-frame `loop` again.  The current key-frame and its
+    n_corrected - 1 predecessors are already corrected (CorrectedSim3: their estimates, with the loop's scale when fix_scale is
+    off); every edge that touches them is measured on their drifted poses (NonCorrectedSim3), every other estimate is the drifted
+    pose with scale 1.  Edges in the reference's order: the loop connections (:2147-2186), then per key-frame the spanning-tree edge
+    to its predecessor, one older loop edge (with icp_edges followed by its ICP edge, information 3 I: :2266-2288), and the
+    covisibility edge to the key-frame two back unless a loop connection already joins the pair.  Key-frame 0 is the map's init
+    key-frame (fixed).  Map points sit in front of their reference key-frames' drifted poses; every 16th has no reference (-1).
+    -> dict for api.EssentialGraphOptimizer.OptimizeEssentialGraph, plus true_R / true_t (world -> camera) and kind [E] (0 loop
+    connection, 1 spanning tree, 2 loop edge, 3 ICP, 4 covisibility)."""
+    rng = np.random.default_rng(seed)
+    n = int(n_keyframes)
+    assert n >= 6 and 0 <= loop < n - n_corrected - 2
+    # world -> camera of the truth: centres on the ring, heading along it, a small wobble
+    Rt, tt = [], []
+    for k in range(n):
+        a = 2 * np.pi * k / n
+        Rwc = _rot(*(0.05 * rng.uniform(-1, 1, 3))) @ _rot(0, 0, a + np.pi / 2)
+        c = np.array([radius * np.cos(a), radius * np.sin(a), 0.2 * rng.uniform(-1, 1)])
+        Rt.append(Rwc.T)
+        tt.append(-Rwc.T @ c)
+    # the map's poses: the true relative motions with a heading bias, noise and a scale error, chained from key-frame 0
+    Rd, td = [Rt[0]], [tt[0]]
+    for k in range(1, n):
+        Rrel, trel = Rt[k] @ Rt[k - 1].T, tt[k] - Rt[k] @ Rt[k - 1].T @ tt[k - 1]
+        Rn = _rot(*(drift / n * np.array([0.2 * rng.normal(), 0.2 * rng.normal(), 1.0 + 0.3 * rng.normal()])))
+        Rrel, trel = Rn @ Rrel, 1.02 * trel + 0.002 * rng.normal(size=3)
+        Rd.append(Rrel @ Rd[k - 1])
+        td.append(Rrel @ td[k - 1] + trel)
+
+    def mul(a, b):  # Sim3 as (R, t, s): x -> s R x + t
+        return a[0] @ b[0], a[2] * (a[0] @ b[1]) + a[1], a[2] * b[2]
+
+    def inv(a):
+        return a[0].T, -(a[0].T @ a[1]) / a[2], 1.0 / a[2]
+
+    non_corrected = [(Rd[k], td[k], 1.0) for k in range(n)]
+    cur = n - 1
+    s_c = 1.0 if fix_scale else float(1.0 + 0.08 * rng.uniform(0.5, 1.0))
+    cur_corr = (_rot(*(0.002 * rng.normal(size=3))) @ Rt[cur], s_c * (tt[cur] + 0.005 * rng.normal(size=3)), s_c)
+    corrected = {k: mul(mul(non_corrected[k], inv(non_corrected[cur])), cur_corr) for k in range(n - n_corrected, n)}
+    scw = [corrected.get(k, non_corrected[k]) for k in range(n)]
+    drifted = lambda k: non_corrected[k]  # (NonCorrectedSim3 where there is one, else vScw: the same Sim3 here)
+
+    edges = []  # (i, j, measurement, weight, kind)
+    inserted = set()
+    loop_connections = {cur: [loop, loop + 1], cur - 1: [loop]}
+    for i in sorted(loop_connections):
+        for j in loop_connections[i]:
+            edges.append((i, j, mul(scw[j], inv(scw[i])), 1.0, 0))
+            inserted.add((min(i, j), max(i, j)))
+    old_i, old_l = n // 2, 1
+    for i in range(n):
+        Swi = inv(drifted(i))
+        if i >= 1:
+            edges.append((i, i - 1, mul(drifted(i - 1), Swi), 1.0, 1))
+        if i == old_i and old_l < i - 2:
+            Sli = mul(drifted(old_l), Swi)
+            edges.append((i, old_l, Sli, 1.0, 2))
+            if icp_edges:
+                icp = (_rot(*(0.003 * rng.normal(size=3))) @ Sli[0], Sli[1] / Sli[2] + 0.01 * rng.normal(size=3), 1.0)
+                edges.append((i, old_l, icp, 3.0, 3))
+        if i >= 2 and (i - 2, i) not in inserted:
+            edges.append((i, i - 2, mul(drifted(i - 2), Swi), 1.0, 4))
+
+    pts, ref = [], []
+    for k in range(n):
+        p_cam = np.stack([rng.uniform(-1, 1, points_per_kf), rng.uniform(-0.5, 0.5, points_per_kf), rng.uniform(1, 4, points_per_kf)], 1)
+        pts.append((p_cam - td[k]) @ Rd[k])  # Rd^T (p - t)
+        ref.append(np.full(points_per_kf, k))
+    pts, ref = np.concatenate(pts).astype(np.float32), np.concatenate(ref).astype(np.int32)
+    ref[::16] = -1
+    fixed = np.zeros(n, np.uint8)
+    fixed[0] = 1
+    return dict(vertex_q=np.stack([_quat_xyzw(S[0]) for S in scw]), vertex_t=np.stack([S[1] for S in scw]),
+                vertex_s=np.array([S[2] for S in scw]), vertex_fixed=fixed,
+                edge_i=np.array([e[0] for e in edges], np.int32), edge_j=np.array([e[1] for e in edges], np.int32),
+                edge_q=np.stack([_quat_xyzw(e[2][0]) for e in edges]), edge_t=np.stack([e[2][1] for e in edges]),
+                edge_s=np.array([e[2][2] for e in edges]), edge_w=np.array([e[3] for e in edges]),
+                fix_scale=bool(fix_scale), iterations=20, lambda_init=1e-16, points=pts, point_ref=ref,
+                kind=np.array([e[4] for e in edges], np.int32), true_R=np.stack(Rt), true_t=np.stack(tt))

@@ -1049,6 +1049,67 @@ int gfs_frame_cloud_extract_device(gfs_frame_cloud* h, const void* dev_xyzw, con
                                    float* down_xyz, int cap_down, gfs_frame_cloud_info* info);
 
 /* ============================================================================================
+ * 15. Optimizer::OptimizeEssentialGraph (src/Optimizer.cc:2042-2413) — the Sim3 pose graph of LoopClosing::CorrectLoop
+ *     (src/LoopClosing.cc:1257), between gfs_fuse_search and gfs_gba_solve.
+ *    The flattened graph: one VertexSim3Expmap per vertex (the estimate Siw = (q, t, s), `fixed` for the map's init key-frame,
+ *    _fix_scale = fix_scale for all), one EdgeSim3 per edge with vertex 0 = i, vertex 1 = j, the measurement Sji (ICP edges: Sij, the
+ *    vertices swapped) and information w I_7 (1; ICP edges 3), in the order the reference makes them: the sums run in this order.
+ *    BlockSolver_7_3 + LinearSolverEigen + Levenberg with setUserLambdaInit(lambda_init = 1e-16), optimize(iterations = 20), no stop
+ *    flag, no robust kernel, g2o's numeric Jacobians (central differences, delta 1e-9).  The pose system is factored as a tiled dense
+ *    L D L^T over the whole device (the factorisation of gfs_gba_solve).  With fix_scale the scale column of every Jacobian is exactly
+ *    zero and a vertex has 6 dimensions in the system; without, 7.  DESIGN.md "Essential graph".
+ *    Then every map point goes through correctedSwr.map(Srw.map(P)) of its reference vertex (:2387-2409), in double, cast to float.
+ *    The pointer-graph gather, the ICP registrations and the write-back stay in the C++ adaptor.
+ *    Refused with GFS_ERR_INVALID_ARG before anything is queued: a vertex index outside the graph, an edge from a vertex to itself, a
+ *    point reference >= n_vertices (negative: the point is left as it is), a scale or weight that is not positive and finite.
+ *    GFS_ERR_CAPACITY above the handle's limits; gfs_essential_graph_create refuses with it when the tiles of 7 max_vertices rows do
+ *    not fit the device.
+ * ============================================================================================ */
+typedef struct {
+  int32_t n_vertices, n_edges, n_points;
+  const double* vertex_q;      /* [n_vertices][4] (x, y, z, w) */
+  const double* vertex_t;      /* [n_vertices][3] */
+  const double* vertex_s;      /* [n_vertices] */
+  const uint8_t* vertex_fixed; /* [n_vertices] */
+  const int32_t* edge_i;       /* [n_edges] vertex 0 */
+  const int32_t* edge_j;       /* [n_edges] vertex 1 */
+  const double* edge_q;        /* [n_edges][4] the measurement */
+  const double* edge_t;        /* [n_edges][3] */
+  const double* edge_s;        /* [n_edges] */
+  const double* edge_w;        /* [n_edges] information = w I_7 */
+  int32_t fix_scale;           /* bFixScale */
+  int32_t iterations;          /* 20 (src/Optimizer.cc:2362); <= 0: the estimate as it came and the chi2 at it */
+  double lambda_init;          /* 1e-16 (src/Optimizer.cc:2059) */
+  const float* points;         /* [n_points][3] world positions (may be NULL when n_points = 0) */
+  const int32_t* point_ref;    /* [n_points] the reference vertex, or -1: leave the point as it is */
+} gfs_essential_graph_problem;
+typedef struct {
+  double* vertex_q; /* [n_vertices][4] as g2o leaves it: not renormalised */
+  double* vertex_t; /* [n_vertices][3] */
+  double* vertex_s; /* [n_vertices] */
+  float* points;    /* [n_points][3] (may be NULL) */
+  double* edge_chi2; /* [n_edges] e->chi2() at the estimate that is returned (may be NULL) */
+  int32_t iterations_run;
+  double final_chi2, final_lambda;
+} gfs_essential_graph_solution;
+typedef struct {
+  int32_t n_free, dimension, panels; /* free vertices; their dimension (6 or 7); tile rows of the system */
+  int64_t blocks;                    /* listed blocks of the lower triangle */
+  int32_t trials, launches;          /* Levenberg trials run; kernel launches of the call */
+  int64_t system_bytes;              /* bytes of the tiled system */
+} gfs_essential_graph_info;
+typedef struct gfs_essential_graph gfs_essential_graph;
+int gfs_essential_graph_create(int device, int max_vertices, int max_edges, int max_points, gfs_essential_graph** out);
+void gfs_essential_graph_destroy(gfs_essential_graph* h);
+int gfs_essential_graph_optimize(gfs_essential_graph* h, const gfs_essential_graph_problem* p, gfs_essential_graph_solution* s);
+/* The point correction alone, on given Sim3s [n_vertices][8] = (q, t, s): `before` the reference vertices' Srw, `after` their
+ * corrected Siw (inverted on the device).  LoopClosing::CorrectLoop maps the points of the corrected key-frames the same way. */
+int gfs_essential_graph_correct_points(gfs_essential_graph* h, int n_vertices, const double* before, const double* after, int n_points,
+                                       const float* points, const int32_t* point_ref, float* out);
+/* What the handle's last gfs_essential_graph_optimize did. */
+int gfs_essential_graph_last_info(const gfs_essential_graph* h, gfs_essential_graph_info* info);
+
+/* ============================================================================================
  * Timing helper for the harness: HIP events on a given stream (bench.py measures the dominant kernel
  * with these rather than torch events, which only see torch's current stream).
  * ============================================================================================ */

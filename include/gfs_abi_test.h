@@ -101,6 +101,27 @@ int gfs_test_gba_lists(int n_poses, int n_points, int n_edges, const uint8_t* po
  * storage, index of the element's tile, byte offset of the element}. */
 int gfs_test_gba_tile_layout(int64_t n, int64_t r, int64_t c, uint64_t* out);
 
+/* GPU test hook: the first trial of gfs_essential_graph_optimize's sequence (the estimates set, iteration 0 linearised, lambda =
+ * lambda_init, the system assembled -- copied out here, ahead of the in-place factorisation -- factored and solved, the step applied,
+ * the errors at the trial estimate).  n = dimension x free vertices.  Every pointer is required. */
+typedef struct gfs_test_essential_graph_trial {
+  double* H;        /* [n (n + 1) / 2] packed lower triangle, row by row, lambda on the diagonal */
+  double* b;        /* [n] */
+  double* x;        /* [n] */
+  double chi2;      /* at the estimate as it came, summed in edge order */
+  double trial_chi2; /* at the trial estimate */
+  double scale;     /* computeScale: the vertices' terms added in vertex order */
+  int32_t n_free, dimension;
+  int32_t solve_ok;
+} gfs_test_essential_graph_trial;
+int gfs_test_essential_graph_first_trial(gfs_essential_graph* h, const gfs_essential_graph_problem* p, gfs_test_essential_graph_trial* out);
+/* Host test hook (no GPU): the structure lists of csrc/eg_lists.hpp.  counts = {free vertices, listed blocks, terms} is always filled;
+ * GFS_ERR_CAPACITY when a cap is too small.  free_index [n_vertices]; blk_ij [blocks][2]; blk_begin [blocks + 1]; contrib [terms] =
+ * 4 edge + kind. */
+int gfs_test_essential_graph_lists(int n_vertices, int n_edges, const uint8_t* vertex_fixed, const int32_t* edge_i, const int32_t* edge_j,
+                                   int64_t* counts, int32_t* free_index, int32_t* blk_ij, int64_t* blk_begin, int64_t cap_blocks,
+                                   int32_t* contrib, int64_t cap_contrib);
+
 /* GPU test hook: the stages of the handle's last gfs_frame_cloud_extract(_device) call, as they lie on the device: the scan table
  * (rows of begin, count, pad flags 1 = start | 2 = end, candidates in the scans in front), edge_raw / surf_raw, the two voxel
  * filters' outputs and the two radius filters' outputs.  Their sizes are the call's info; a NULL pointer skips a stage.  Refused
