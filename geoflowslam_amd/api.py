@@ -318,6 +318,67 @@ def fuse_results(LL, KK, RR, keep, n_lists):
     return out
 
 
+SIM3_FUSE, SIM3_SBP, SIM3_SBP_KFS = 0, 1, 2   # GFS_SIM3_*
+SIM3_SEARCH_EXITS = FUSE_EXITS + ("skipped",)  # GFS_FUSE_* 0..7, GFS_FUSE_SKIPPED
+SIM3_SEARCH_LISTED = 4                         # GFS_SIM3_SEARCH_LISTED
+INT_MAX = 2147483647
+
+
+class Sim3SearchProblem(C.Structure):
+    _fields_ = [("mode", C.c_int32), ("ratio_hamming", C.c_float), ("Tcw_q", C.c_float * 4), ("Tcw_t", C.c_float * 3), ("Ow", C.c_float * 3),
+                ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("min_x", C.c_float), ("max_x", C.c_float),
+                ("min_y", C.c_float), ("max_y", C.c_float), ("grid_w_inv", C.c_float), ("grid_h_inv", C.c_float),
+                ("scale_factors", C.c_void_p), ("n_levels", C.c_int32), ("log_scale_factor", C.c_float), ("th", C.c_float),
+                ("n_kp", C.c_int32), ("kps_un", C.c_void_p), ("desc", C.c_void_p), ("kp_taken", C.c_void_p), ("mp_skip", C.c_void_p),
+                ("list", C.c_int32)]
+
+
+Sim3SearchResult = FuseResult  # gfs_sim3_search_result has gfs_fuse_result's layout
+
+
+def sim3_search_structs(lists, problems):
+    """ctypes views of one gfs_sim3_search call (shared with the CPU restatement's tests: same layout).  lists: dicts with the keys
+    of gfs_fuse_points; problems: dicts with the keys of gfs_sim3_search_problem (kps_un = KP_DTYPE array; `list` defaults to 0,
+    ratio_hamming to 1, kp_taken and mp_skip to None = NULL) -> (lists array, problems array, results array, arrays kept alive).
+    The result arrays are pre-filled with a pattern no output has."""
+    nl, B = len(lists), len(problems)
+    LL, _, _, keep = fuse_structs(lists, [])
+    PP, RR = (Sim3SearchProblem * max(B, 1))(), (Sim3SearchResult * max(B, 1))()
+    for f, pr in enumerate(problems):
+        a = dict(scale_factors=np.ascontiguousarray(pr["scale_factors"], np.float32), kps_un=np.ascontiguousarray(pr["kps_un"], KP_DTYPE),
+                 desc=np.ascontiguousarray(pr["desc"], np.uint8).reshape(-1, 32))
+        for name in ("kp_taken", "mp_skip"):
+            if pr.get(name) is not None:
+                a[name] = np.ascontiguousarray(pr[name], np.uint8)
+        K = PP[f]
+        for name, v in a.items():
+            setattr(K, name, v.ctypes.data)
+        for name in ("Tcw_q", "Tcw_t", "Ow"):
+            getattr(K, name)[:] = [float(np.float32(v)) for v in np.asarray(pr[name]).reshape(-1)]
+        for name in ("fx", "fy", "cx", "cy", "min_x", "max_x", "min_y", "max_y", "grid_w_inv", "grid_h_inv", "log_scale_factor", "th"):
+            setattr(K, name, float(np.float32(pr[name])))
+        K.mode = int(pr["mode"])
+        K.ratio_hamming = float(np.float32(pr.get("ratio_hamming", 1.0)))
+        K.n_levels = int(pr.get("n_levels", len(a["scale_factors"])))
+        K.n_kp = len(a["kps_un"])
+        K.list = int(pr.get("list", 0))
+        n = max(LL[K.list].n_mp, 1) if 0 <= K.list < nl else 1
+        assert "kp_taken" not in a or len(a["kp_taken"]) == K.n_kp, "kp_taken must have one byte per key-point"
+        assert "mp_skip" not in a or not (0 <= K.list < nl) or len(a["mp_skip"]) == LL[K.list].n_mp, "mp_skip must have one byte per listed point"
+        out = dict(exit=np.full(n, 0xEE, np.uint8), best_idx=np.full(n, -9, np.int32), best_dist=np.full(n, -9, np.int32),
+                   level=np.full(n, -9, np.int32))
+        for name, v in out.items():
+            setattr(RR[f], name, v.ctypes.data)
+        RR[f].n_matched = -9
+        a.update(out)
+        keep.append(a)
+    return LL, PP, RR, keep
+
+
+def sim3_search_results(LL, PP, RR, keep, n_lists):
+    return fuse_results(LL, PP, RR, keep, n_lists)
+
+
 MAP_POINTS_FULL, MAP_POINTS_NORMALS_ONLY = 0, 1            # GFS_MAP_POINTS_*
 MAP_POINT_OBS_IN_NORMAL, MAP_POINT_OBS_IN_DESC = 1, 2      # GFS_MAP_POINT_OBS_*
 MAP_POINT_NORMAL_SET, MAP_POINT_DESC_SET = 1, 2            # GFS_MAP_POINT_*_SET
@@ -630,6 +691,7 @@ ABI_SYMBOLS = [
     "gfs_gms_create", "gfs_gms_destroy", "gfs_gms_inlier_mask", "gfs_gms_inlier_mask_batch_device",
     "gfs_sbp_create", "gfs_sbp_destroy", "gfs_search_by_projection", "gfs_search_by_projection_map",
     "gfs_sbp_reserve_local", "gfs_search_local_points", "gfs_sbp_reserve_fuse", "gfs_fuse_search", "gfs_test_glibc_logf",
+    "gfs_sbp_reserve_sim3_search", "gfs_sim3_search", "gfs_test_sim3_search_groups",
     "gfs_sbp_reserve_triangulation", "gfs_create_new_map_points",
     "gfs_map_points_create", "gfs_map_points_destroy", "gfs_map_points_update",
     "gfs_klt_create", "gfs_klt_destroy", "gfs_klt_layout", "gfs_klt_pyramid_create", "gfs_klt_pyramid_destroy",
@@ -675,6 +737,9 @@ def lib():
         L.gfs_search_local_points.argtypes = [vp, C.POINTER(LocalPointsProblem), i, C.POINTER(LocalPointsResult)]
         L.gfs_sbp_reserve_fuse.argtypes = [vp, i, i, i]
         L.gfs_fuse_search.argtypes = [vp, C.POINTER(FusePoints), i, C.POINTER(FuseKeyframe), i, C.POINTER(FuseResult)]
+        L.gfs_sbp_reserve_sim3_search.argtypes = [vp, i, i, i]
+        L.gfs_sim3_search.argtypes = [vp, C.POINTER(FusePoints), i, C.POINTER(Sim3SearchProblem), i, C.POINTER(Sim3SearchResult)]
+        L.gfs_test_sim3_search_groups.argtypes = [vp, i]
         L.gfs_sbp_reserve_triangulation.argtypes = [vp, i, C.c_int64]
         L.gfs_create_new_map_points.argtypes = [vp, C.POINTER(TriProblem), i, C.POINTER(C.POINTER(TriResult))]
         L.gfs_map_points_create.argtypes = [i, i, i, C.POINTER(vp)]
@@ -1919,6 +1984,29 @@ class ProjectionMatcher:
         LL, KK, RR, keep = fuse_structs(lists, kfs)
         _check(lib().gfs_fuse_search(self.h, LL, len(lists), KK, len(kfs), RR), "gfs_fuse_search")
         res = fuse_results(LL, KK, RR, keep, len(lists))
+        return res[0] if single else res
+
+    def reserve_sim3_search(self, max_lists, max_points_per_list, max_problems):
+        """Workspace of sim3_search: up to max_lists point lists of up to max_points_per_list map points, searched in up to
+        max_problems problems per call."""
+        _check(lib().gfs_sbp_reserve_sim3_search(self.h, int(max_lists), int(max_points_per_list), int(max_problems)), "gfs_sbp_reserve_sim3_search")
+        self.sim3_reserve = (int(max_lists), int(max_points_per_list), int(max_problems))
+
+    def sim3_search(self, lists, problems):
+        """The three Sim3 searches of loop closing -- ORBmatcher::Fuse(pKF, Scw, ...) (src/ORBmatcher.cc:1550-1654, mode SIM3_FUSE) and
+        the two SearchByProjection(pKF, Scw, ...) (:432-529 SIM3_SBP, :531-636 SIM3_SBP_KFS) -- for every listed map point, any number
+        of (list, problem) pairs in one device call.  lists: one dict (keys of gfs_fuse_points) or a list of them; problems: one dict
+        (keys of gfs_sim3_search_problem, `list` = index of its point list) or a list -> per problem a dict exit (index into
+        SIM3_SEARCH_EXITS), best_idx, best_dist, level, n_matched; in the projection modes after the dependency between the points
+        of a list.  Raises GfsError (code GFS_ERR_CAPACITY beyond the reserve, GFS_ERR_INVALID_ARG for what the entry refuses)."""
+        single = isinstance(problems, dict)
+        lists = [lists] if isinstance(lists, dict) else list(lists)
+        probs = [problems] if single else list(problems)
+        if not hasattr(self, "sim3_reserve"):
+            self.reserve_sim3_search(max(len(lists), 1), max(max([len(p["mp_xw"]) for p in lists] + [64]), 64), max(len(probs), 1))
+        LL, PP, RR, keep = sim3_search_structs(lists, probs)
+        _check(lib().gfs_sim3_search(self.h, LL, len(lists), PP, len(probs), RR), "gfs_sim3_search")
+        res = sim3_search_results(LL, PP, RR, keep, len(lists))
         return res[0] if single else res
 
     def reserve_triangulation(self, max_neighbours, max_candidate_pairs):

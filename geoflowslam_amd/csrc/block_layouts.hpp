@@ -75,6 +75,22 @@ struct FuseLayout {
   Field<int> idx{out, O}, dist{out, O}, level{out, O};
 };
 
+// gfs_sim3_search (sim3_search.hip): T points of all lists, B problems of SC key-points, O result slots and OC listed candidates
+template <class Problem>
+struct Sim3SearchLayout {
+  size_t T, B, SC, O, OC;
+  Block<256> pts, kf, out;
+  Field<float, 3> xw{pts, T}, nrm{pts, T};
+  Field<float> dmin{pts, T}, dmax{pts, T};
+  Field<uint8_t, 32> desc{pts, T};
+  Field<Problem> problems{kf, B};
+  Field<xy_t> xy{kf, B * SC};
+  Field<uint8_t> oct{kf, B * SC};  // the octave, bit 7 = the key-point is taken at entry
+  Field<uint8_t, 32> kdesc{kf, B * SC};
+  Field<uint8_t> exit{out, O};
+  Field<int> level{out, O}, count{out, O}, cidx{out, OC}, cdist{out, OC};
+};
+
 // gfs_create_new_map_points (triangulate.hip): the arrays of one key frame (n key-points, m nodes, nf listed features), taken from
 // the call's running input block -- and from an empty block, the bytes a key frame of the capacity needs
 struct TriKfArrays {

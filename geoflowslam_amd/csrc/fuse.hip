@@ -46,75 +46,25 @@ __global__ __launch_bounds__(kFuseThreads) void k_fuse(const FuseProblem* __rest
   __shared__ FuseProblem s_P;
   static_assert(sizeof(float) * kSbpMaxCur >= sizeof(int) * kCells, "the mvuRight table must hold the cell counters");
   int* s_cnt = reinterpret_cast<int*>(s_ur);
-  const int f = blockIdx.y, tid = threadIdx.x, lane = tid & 63;
+  const int f = blockIdx.y, tid = threadIdx.x;
   if ((int)blockIdx.x * kFuseThreads >= problems[f].n_mp) return;  // (uniform: the grid is sized by the call's longest list)
   if (tid == 0) s_P = problems[f];
-  for (int c = tid; c < kCells; c += kFuseThreads) s_cnt[c] = 0;
   __syncthreads();
   const gfs_fuse::KeyFrame& K = s_P.K;
   const int N = K.n_kp;
   const size_t kf_at = (size_t)f * SC;
-  auto cell_of = [&](float x, float y) {
-    const int px = (int)roundf((x - K.min_x) * K.grid_w_inv), py = (int)roundf((y - K.min_y) * K.grid_h_inv);
-    return (px >= 0 && px < kGridCols && py >= 0 && py < kGridRows) ? px * kGridRows + py : -1;
-  };
-  // ---- the grid (Frame::AssignFeaturesToGrid: the key-points of a cell in index order)
   for (int i = tid; i < N; i += kFuseThreads) {
     const float2 p = kf_xy[kf_at + i];
     s_kx[i] = p.x;
     s_ky[i] = p.y;
     s_oct[i] = kf_oct[kf_at + i];
-    const int c = cell_of(p.x, p.y);
-    if (c >= 0) atomicAdd(&s_cnt[c], 1);
   }
-  __syncthreads();
-  {
-    constexpr int per = kCells / kFuseThreads;  // 12 (3072 cells over 256 threads)
-    static_assert(per * kFuseThreads == kCells, "the cells divide over the threads");
-    int cnt[per], local = 0;
-#pragma unroll
-    for (int k = 0; k < per; k++) {
-      cnt[k] = s_cnt[tid * per + k];
-      local += cnt[k];
-    }
-    int incl = local;  // exclusive scan over the threads: shuffles inside the wave, the four wave totals through LDS
-#pragma unroll
-    for (int ofs = 1; ofs < 64; ofs <<= 1) {
-      const int v = __shfl_up(incl, ofs, 64);
-      if (lane >= ofs) incl += v;
-    }
-    if (lane == 63) s_scan[tid >> 6] = incl;
-    __syncthreads();
-    int run = incl - local;
-    for (int w = 0; w < (tid >> 6); w++) run += s_scan[w];
-#pragma unroll
-    for (int k = 0; k < per; k++) {
-      s_start[tid * per + k] = (unsigned short)run;
-      s_cnt[tid * per + k] = 0;  // now the fill counter of the cell
-      run += cnt[k];
-    }
-    if (tid == kFuseThreads - 1) s_start[kCells] = (unsigned short)run;
-  }
-  __syncthreads();
-  for (int i = tid; i < N; i += kFuseThreads) {  // into the cell in arrival order ...
-    const int c = cell_of(s_kx[i], s_ky[i]);
-    if (c < 0) continue;
-    s_items[s_start[c] + atomicAdd(&s_cnt[c], 1)] = (unsigned short)i;
-  }
-  __syncthreads();
-  for (int c = tid; c < kCells; c += kFuseThreads) {  // ... then every cell in index order (a handful of items: insertion sort)
-    const int b = s_start[c], e = s_start[c + 1];
-    for (int a = b + 1; a < e; a++) {
-      const unsigned short v = s_items[a];
-      int q = a;
-      while (q > b && s_items[q - 1] > v) {
-        s_items[q] = s_items[q - 1];
-        q--;
-      }
-      s_items[q] = v;
-    }
-  }
-  __syncthreads();  // the counters are done with: their table becomes mvuRight
+  auto cell_of = [&](int i) {  // Frame::PosInGrid
+    const int px = (int)roundf((s_kx[i] - K.min_x) * K.grid_w_inv), py = (int)roundf((s_ky[i] - K.min_y) * K.grid_h_inv);
+    return (px >= 0 && px < kGridCols && py >= 0 && py < kGridRows) ? px * kGridRows + py : -1;
+  };
+  // ---- the grid; the counters are done with when it stands: their table becomes mvuRight
+  build_grid_lds<kFuseThreads>(N, cell_of, s_start, s_items, s_cnt, s_scan);
   for (int i = tid; i < N; i += kFuseThreads) s_ur[i] = kf_ur[kf_at + i];
   __syncthreads();
   // ---- a lane per map point

@@ -50,45 +50,69 @@ GFS_HD int predict_scale(float max_dist, float dist, float log_scale_factor, int
   return lv < 0 ? 0 : (lv >= n_levels ? n_levels - 1 : lv);
 }
 
-// :1424-1470 up to the cell range of KeyFrame::GetFeaturesInArea (src/KeyFrame.cc:802-827)
-GFS_HD Proj project(const KeyFrame& K, const float* P, const float* Pn, float min_dist, float max_dist) {
+// every field defined, for a point that leaves before its window is known
+GFS_HD Proj no_projection() {
   Proj R;
-  R.level = 0;
+  R.exit = R.level = 0;
   R.x0 = R.x1 = R.y0 = R.y1 = 0;
   R.u = R.v = R.ur = R.radius = 0.0f;
-  float Pc[3];
+  return R;
+}
+
+// Tcw * p3Dw
+GFS_HD void camera_point(const KeyFrame& K, const float* P, float* Pc) {
   so3_act(K.q, P, Pc);
   for (int k = 0; k < 3; k++) Pc[k] += K.t[k];
-  if (Pc[2] < 0.0f) return R.exit = kNegDepth, R;
-  const float invz = 1.0f / Pc[2];
-  const float u = K.fx * Pc[0] / Pc[2] + K.cx, v = K.fy * Pc[1] / Pc[2] + K.cy;
-  // KeyFrame::IsInImage (src/KeyFrame.cc:848-850): half open; NaN and +-inf fail it by themselves
-  if (!(u >= K.min_x && u < K.max_x && v >= K.min_y && v < K.max_y)) return R.exit = kNotInImage, R;
-  R.u = u;
-  R.v = v;
-  R.ur = u - K.bf * invz;
+}
+
+// KeyFrame::IsInImage (src/KeyFrame.cc:848-850): half open; NaN and +-inf fail it by themselves
+GFS_HD bool in_image(const KeyFrame& K, float u, float v) {
+  if (!(u >= K.min_x && u < K.max_x && v >= K.min_y && v < K.max_y)) return false;
+  return true;
+}
+
+// From the distance gates to the cell range of KeyFrame::GetFeaturesInArea (src/KeyFrame.cc:802-827) for a point that projects to
+// (R.u, R.v) inside the image (:1444-1470; the Sim3 searches of sim3_search_rule.hpp run the same steps): sets R.exit, R.level,
+// R.radius and the cell range.
+GFS_HD void gates_and_window(const KeyFrame& K, const float* P, const float* Pn, float min_dist, float max_dist, Proj& R) {
+  const float u = R.u, v = R.v;
   const float PO[3] = {P[0] - K.Ow[0], P[1] - K.Ow[1], P[2] - K.Ow[2]};
   const float dist = sqrtf((PO[0] * PO[0] + PO[1] * PO[1]) + PO[2] * PO[2]);
-  if (dist < kMinDistFactor * min_dist) return R.exit = kTooNear, R;
-  if (dist > kMaxDistFactor * max_dist) return R.exit = kTooFar, R;
+  if (dist < kMinDistFactor * min_dist) return (void)(R.exit = kTooNear);
+  if (dist > kMaxDistFactor * max_dist) return (void)(R.exit = kTooFar);
   const float dot = (PO[0] * Pn[0] + PO[1] * Pn[1]) + PO[2] * Pn[2];
-  if ((double)dot < kViewCosHalf * (double)dist) return R.exit = kViewAngle, R;
+  if ((double)dot < kViewCosHalf * (double)dist) return (void)(R.exit = kViewAngle);
   R.level = predict_scale(max_dist, dist, K.log_scale_factor, K.n_levels);
   R.radius = K.th * K.scale[R.level];
   R.exit = kEmptyWindow;
   R.x0 = (int)floorf((u - K.min_x - R.radius) * K.grid_w_inv);
   if (R.x0 < 0) R.x0 = 0;
-  if (R.x0 >= kGridCols) return R;
+  if (R.x0 >= kGridCols) return;
   R.x1 = (int)ceilf((u - K.min_x + R.radius) * K.grid_w_inv);
   if (R.x1 > kGridCols - 1) R.x1 = kGridCols - 1;
-  if (R.x1 < 0) return R;
+  if (R.x1 < 0) return;
   R.y0 = (int)floorf((v - K.min_y - R.radius) * K.grid_h_inv);
   if (R.y0 < 0) R.y0 = 0;
-  if (R.y0 >= kGridRows) return R;
+  if (R.y0 >= kGridRows) return;
   R.y1 = (int)ceilf((v - K.min_y + R.radius) * K.grid_h_inv);
   if (R.y1 > kGridRows - 1) R.y1 = kGridRows - 1;
-  if (R.y1 < 0) return R;
+  if (R.y1 < 0) return;
   R.exit = -1;
+}
+
+// :1424-1470 up to the cell range
+GFS_HD Proj project(const KeyFrame& K, const float* P, const float* Pn, float min_dist, float max_dist) {
+  Proj R = no_projection();
+  float Pc[3];
+  camera_point(K, P, Pc);
+  if (Pc[2] < 0.0f) return R.exit = kNegDepth, R;
+  const float invz = 1.0f / Pc[2];
+  const float u = K.fx * Pc[0] / Pc[2] + K.cx, v = K.fy * Pc[1] / Pc[2] + K.cy;
+  if (!in_image(K, u, v)) return R.exit = kNotInImage, R;
+  R.u = u;
+  R.v = v;
+  R.ur = u - K.bf * invz;
+  gates_and_window(K, P, Pn, min_dist, max_dist, R);
   return R;
 }
 

@@ -33,6 +33,7 @@
 
 #include "../../include/gfs_abi.h"
 #include "../csrc/fuse_rule.hpp"
+#include "../csrc/sim3_search_rule.hpp"
 #include "../csrc/map_point_rule.hpp"
 #include "../csrc/sim3_dev.hpp"
 #include "../csrc/triangulate_rule.hpp"
@@ -1654,6 +1655,314 @@ class FuseSearcher {
  private:
   gfs_sbp* h_ = nullptr;
   int lists_ = 0, points_ = 0, kfs_ = 0;
+};
+
+// ------------------------------------------------------------------------------------------------------------------------
+// int ORBmatcher::Fuse(KeyFrame* pKF, Sophus::Sim3f& Scw, const vector<MapPoint*>& vpPoints, float th,
+//                      vector<MapPoint*>& vpReplacePoint)                                  reference src/ORBmatcher.cc:1550-1654
+// void LoopClosing::SearchAndFuse(const KeyFrameAndPose& CorrectedPosesMap, vector<MapPoint*>& vpMapPoints)
+// void LoopClosing::SearchAndFuse(const vector<KeyFrame*>& vConectedKFs, vector<MapPoint*>& vpMapPoints)
+//                                                                                          reference src/LoopClosing.cc:2224-2302
+// int ORBmatcher::SearchByProjection(KeyFrame* pKF, Sophus::Sim3f& Scw, const vector<MapPoint*>& vpPoints,
+//                      vector<MapPoint*>& vpMatched, int th, float ratioHamming)           reference src/ORBmatcher.cc:432-529
+// int ORBmatcher::SearchByProjection(KeyFrame* pKF, Sophus::Sim3f& Scw, const vector<MapPoint*>& vpPoints,
+//                      const vector<KeyFrame*>& vpPointsKFs, vector<MapPoint*>& vpMatched, vector<KeyFrame*>& vpMatchedKF, int th,
+//                      float ratioHamming)                                                 reference src/ORBmatcher.cc:531-636
+// as real code around gfs_sim3_search.
+//   The projection searches change nothing but vpMatched (and vpMatchedKF), and the entry resolves that dependency itself: the
+//   adaptor uploads isBad() || spAlreadyFound.count(pMP) as mp_skip and vpMatched[idx] != NULL as kp_taken, and writes the matches.
+//   Fuse reads pointer state before the search (isBad(), the GetMapPoints() set taken at entry) and after it (GetMapPoint(bestIdx),
+//   isBad() of the point there), and SearchAndFuse changes it between two key frames (pRep->Replace(vpMapPoints[i]), which ends in
+//   vpMapPoints[i]->ComputeDistinctiveDescriptors()).  So SearchAndFuse searches every (key frame, point) pair in ONE device call
+//   from the entry state and replays key frame by key frame in the reference's order against the live state; a point whose
+//   descriptor is no longer the uploaded one is searched again on the host with the same rule (gfs_sim3::search_point,
+//   csrc/sim3_search_rule.hpp), as in Fuse above.
+// Compile the translation unit that includes this with -ffp-contract=off.  Single-camera pinhole key frames only: NLeft != -1 or
+// another camera model throws.
+//
+// KeyFrame and MapPoint members used: pKF->NLeft, N, fx, fy, cx, cy, mnMinX .. mnMaxY, mfGridElementWidthInv / HeightInv,
+// mvScaleFactors, mnScaleLevels, mfLogScaleFactor, GetMapPoints, GetMapPoint, AddMapPoint, GetPose (through Access); pMP->isBad,
+// AddObservation, Replace.  `Access` as for Fuse (is_pinhole, keys_un, descriptors; world_pos, normal, distances, descriptor), plus:
+//     template <class Sim3> static void sim3_pose(const Sim3& Scw, float q[4], float t[3], float Ow[3]);
+//         // the caller's own Sophus, as :442-444 / :1560-1562: Sophus::SE3f Tcw(Scw.rotationMatrix(), Scw.translation() / Scw.scale());
+//         // q = Tcw.unit_quaternion() (x, y, z, w), t = Tcw.translation(), Ow = Tcw.inverse().translation().  For a g2o::Sim3 (the
+//         // values of KeyFrameAndPose) Converter::toSophus first (:2241).
+//     static void pose_as_sim3(const KeyFrame&, float q[4], float t[3], float Ow[3]);
+//         // :2277-2279: Sophus::Sim3f Scw(Tcw.unit_quaternion(), Tcw.translation()); Scw.setScale(1.f); then as sim3_pose
+//     static Guard lock_map_update(KeyFrame*);   // unique_lock<mutex>(pKF->GetMap()->mMutexMapUpdate), held over the Replace loop
+// `solve(lists, n_lists, problems, B, results)` is the numeric core: Sim3Searcher::solve below (gfs_sim3_search on the GPU).
+// ------------------------------------------------------------------------------------------------------------------------
+struct Sim3SearchOutputs {  // the result arrays of one (list, problem) search
+  std::vector<uint8_t> exit;
+  std::vector<int32_t> best_idx, best_dist, level;
+  gfs_sim3_search_result view(size_t n) {
+    exit.assign(n + 1, 0);
+    best_idx.assign(n + 1, -1);
+    best_dist.assign(n + 1, 256);
+    level.assign(n + 1, 0);
+    gfs_sim3_search_result r{};
+    r.exit = exit.data();
+    r.best_idx = best_idx.data();
+    r.best_dist = best_dist.data();
+    r.level = level.data();
+    return r;
+  }
+};
+
+// the problem of one key frame; Tcw_q / Tcw_t / Ow are the caller's to fill
+template <class Access, class KeyFrame>
+gfs_sim3_search_problem sim3_search_keyframe(const KeyFrame& KF, int mode, float th, float ratio_hamming, int list) {
+  if (KF.NLeft != -1 || !Access::is_pinhole(KF)) throw std::invalid_argument("Sim3 search: single-camera pinhole key frames only");
+  gfs_sim3_search_problem k{};
+  k.mode = mode;
+  k.ratio_hamming = ratio_hamming;
+  k.fx = KF.fx;
+  k.fy = KF.fy;
+  k.cx = KF.cx;
+  k.cy = KF.cy;
+  k.min_x = KF.mnMinX;
+  k.max_x = KF.mnMaxX;
+  k.min_y = KF.mnMinY;
+  k.max_y = KF.mnMaxY;
+  k.grid_w_inv = KF.mfGridElementWidthInv;
+  k.grid_h_inv = KF.mfGridElementHeightInv;
+  k.scale_factors = KF.mvScaleFactors.data();
+  k.n_levels = KF.mnScaleLevels;
+  k.log_scale_factor = KF.mfLogScaleFactor;
+  k.th = th;
+  k.n_kp = KF.N;
+  k.kps_un = Access::keys_un(KF);
+  k.desc = Access::descriptors(KF);
+  k.list = list;
+  return k;
+}
+
+// one (point, problem) search on the host from the point's CURRENT descriptor (the replay's recompute path); taken may be NULL
+inline gfs_sim3::PointResult sim3_search_point_host(const gfs_sim3_search_problem& k, const float* P, const float* Pn, float min_d, float max_d,
+                                                    const uint8_t* desc, const uint8_t* taken = nullptr) {
+  if (k.n_levels < 1 || k.n_levels > 16) throw std::invalid_argument("Sim3 search: 1..16 pyramid levels");
+  gfs_fuse::KeyFrame K{};
+  for (int c = 0; c < 4; c++) K.q[c] = k.Tcw_q[c];
+  for (int c = 0; c < 3; c++) {
+    K.t[c] = k.Tcw_t[c];
+    K.Ow[c] = k.Ow[c];
+  }
+  K.fx = k.fx;
+  K.fy = k.fy;
+  K.cx = k.cx;
+  K.cy = k.cy;
+  K.min_x = k.min_x;
+  K.max_x = k.max_x;
+  K.min_y = k.min_y;
+  K.max_y = k.max_y;
+  K.grid_w_inv = k.grid_w_inv;
+  K.grid_h_inv = k.grid_h_inv;
+  K.log_scale_factor = k.log_scale_factor;
+  K.th = k.th;
+  K.n_levels = k.n_levels;
+  K.n_kp = k.n_kp;
+  for (int c = 0; c < k.n_levels; c++) K.scale[c] = k.scale_factors[c];
+  for (int i = 0; i < k.n_kp; i++)
+    if (k.kps_un[i].octave < 0 || k.kps_un[i].octave >= k.n_levels) throw std::invalid_argument("Sim3 search: key-point octave outside the pyramid");
+  return gfs_sim3::search_point(
+      K, k.mode, k.ratio_hamming, P, Pn, min_d, max_d, desc,
+      [&](int j, float* x, float* y, int* oct) {
+        *x = k.kps_un[j].x;
+        *y = k.kps_un[j].y;
+        *oct = k.kps_un[j].octave;
+      },
+      k.desc, taken);
+}
+
+// The loop of :1572-1651 around the device's search results of (L, k), which were computed WITHOUT mp_skip: the skip test and the
+// replace / add block run here against the live state.  recomputed: incremented per host recompute.
+template <class Access, class KeyFrame, class MapPoint>
+int fuse_sim3_replay(KeyFrame* pKF, const std::vector<MapPoint*>& vpPoints, const FuseList& L, const gfs_sim3_search_problem& k,
+                     const Sim3SearchOutputs& r, std::vector<MapPoint*>& vpReplacePoint, int* recomputed = nullptr) {
+  // Set of MapPoints already found in the KeyFrame
+  const auto spAlreadyFound = pKF->GetMapPoints();
+  int nFused = 0;
+  for (size_t iMP = 0; iMP < vpPoints.size(); iMP++) {
+    MapPoint* pMP = vpPoints[iMP];
+    if (!L.present[iMP]) continue;
+    // Discard Bad MapPoints and already found
+    if (pMP->isBad() || spAlreadyFound.count(pMP)) continue;
+    int exit = r.exit[iMP], bestIdx = r.best_idx[iMP];
+    uint8_t now[32];
+    Access::descriptor(pMP, now);
+    if (std::memcmp(now, &L.desc[32 * iMP], 32) != 0) {  // the descriptor changed after the upload: this pair again, on the host
+      const gfs_sim3::PointResult o = sim3_search_point_host(k, &L.xw[3 * iMP], &L.nrm[3 * iMP], L.dmin[iMP], L.dmax[iMP], now);
+      exit = o.exit;
+      bestIdx = o.best_idx;
+      if (recomputed) ++*recomputed;
+    }
+    if (exit != GFS_FUSE_MATCHED) continue;
+    // If there is already a MapPoint replace otherwise add new measurement (:1641-1649)
+    MapPoint* pMPinKF = pKF->GetMapPoint(bestIdx);
+    if (pMPinKF) {
+      if (!pMPinKF->isBad()) vpReplacePoint[iMP] = pMPinKF;
+    } else {
+      pMP->AddObservation(pKF, bestIdx);
+      pKF->AddMapPoint(pMP, bestIdx);
+    }
+    nFused++;
+  }
+  return nFused;
+}
+
+// ORBmatcher::Fuse(pKF, Scw, vpPoints, th, vpReplacePoint): one list, one key frame
+template <class Access, class KeyFrame, class MapPoint, class Sim3, class Solve>
+int FuseSim3(Solve&& solve, KeyFrame* pKF, const Sim3& Scw, const std::vector<MapPoint*>& vpPoints, float th, std::vector<MapPoint*>& vpReplacePoint,
+             int* recomputed = nullptr) {
+  gfs_sim3_search_problem k = sim3_search_keyframe<Access>(*pKF, GFS_SIM3_FUSE, th, 1.0f, 0);
+  Access::sim3_pose(Scw, k.Tcw_q, k.Tcw_t, k.Ow);
+  FuseList L;
+  fuse_gather<Access>(vpPoints, L);
+  const gfs_fuse_points lp = L.view();
+  Sim3SearchOutputs out;
+  gfs_sim3_search_result r = out.view(vpPoints.size());
+  check(solve(&lp, 1, &k, 1, &r), "gfs_sim3_search");
+  return fuse_sim3_replay<Access>(pKF, vpPoints, L, k, out, vpReplacePoint, recomputed);
+}
+
+struct SearchAndFuseCounts {
+  int fused = 0, replaced = 0, recomputed = 0;
+};
+
+// both SearchAndFuse overloads from `ORBmatcher matcher(0.8);` on: problems[f] is key frame vpKFs[f]'s, its pose filled
+template <class Access, class KeyFrame, class MapPoint, class Solve>
+SearchAndFuseCounts search_and_fuse(Solve&& solve, const std::vector<KeyFrame*>& vpKFs, std::vector<gfs_sim3_search_problem>& problems,
+                                    std::vector<MapPoint*>& vpMapPoints) {
+  SearchAndFuseCounts c;
+  if (vpKFs.empty()) return c;
+  FuseList L;
+  fuse_gather<Access>(vpMapPoints, L);
+  const gfs_fuse_points lp = L.view();
+  std::vector<Sim3SearchOutputs> outs(vpKFs.size());
+  std::vector<gfs_sim3_search_result> rs;
+  for (Sim3SearchOutputs& o : outs) rs.push_back(o.view(vpMapPoints.size()));
+  check(solve(&lp, 1, problems.data(), (int)problems.size(), rs.data()), "gfs_sim3_search");
+  for (size_t f = 0; f < vpKFs.size(); f++) {
+    KeyFrame* pKFi = vpKFs[f];
+    std::vector<MapPoint*> vpReplacePoints(vpMapPoints.size(), static_cast<MapPoint*>(nullptr));
+    c.fused += fuse_sim3_replay<Access>(pKFi, vpMapPoints, L, problems[f], outs[f], vpReplacePoints, &c.recomputed);
+    // Get Map Mutex
+    auto lock = Access::lock_map_update(pKFi);
+    (void)lock;
+    const int nLP = (int)vpMapPoints.size();
+    for (int i = 0; i < nLP; i++) {
+      MapPoint* pRep = vpReplacePoints[i];
+      if (pRep) {
+        c.replaced += 1;
+        pRep->Replace(vpMapPoints[i]);
+      }
+    }
+  }
+  return c;
+}
+
+// LoopClosing::SearchAndFuse(CorrectedPosesMap, vpMapPoints): a map from KeyFrame* to the corrected Sim3, walked in its own order
+template <class Access, class PosesMap, class MapPoint, class Solve>
+SearchAndFuseCounts SearchAndFuse(Solve&& solve, const PosesMap& CorrectedPosesMap, std::vector<MapPoint*>& vpMapPoints, float th = 4.0f) {
+  using KeyFrame = std::remove_pointer_t<typename PosesMap::key_type>;
+  std::vector<KeyFrame*> kfs;
+  std::vector<gfs_sim3_search_problem> problems;
+  for (auto mit = CorrectedPosesMap.begin(), mend = CorrectedPosesMap.end(); mit != mend; mit++) {
+    KeyFrame* pKFi = mit->first;
+    problems.push_back(sim3_search_keyframe<Access>(*pKFi, GFS_SIM3_FUSE, th, 1.0f, 0));
+    Access::sim3_pose(mit->second, problems.back().Tcw_q, problems.back().Tcw_t, problems.back().Ow);
+    kfs.push_back(pKFi);
+  }
+  return search_and_fuse<Access>(solve, kfs, problems, vpMapPoints);
+}
+
+// LoopClosing::SearchAndFuse(vConectedKFs, vpMapPoints): every key frame under its own pose as a Sim3 of scale 1
+template <class Access, class KeyFrame, class MapPoint, class Solve>
+SearchAndFuseCounts SearchAndFuse(Solve&& solve, const std::vector<KeyFrame*>& vConectedKFs, std::vector<MapPoint*>& vpMapPoints, float th = 4.0f) {
+  std::vector<gfs_sim3_search_problem> problems;
+  for (KeyFrame* pKF : vConectedKFs) {
+    problems.push_back(sim3_search_keyframe<Access>(*pKF, GFS_SIM3_FUSE, th, 1.0f, 0));
+    Access::pose_as_sim3(*pKF, problems.back().Tcw_q, problems.back().Tcw_t, problems.back().Ow);
+  }
+  return search_and_fuse<Access>(solve, vConectedKFs, problems, vpMapPoints);
+}
+
+// both SearchByProjection(pKF, Scw, ...) overloads: vpPointsKFs / vpMatchedKF are NULL for the first
+template <class Access, class KeyFrame, class MapPoint, class Sim3, class Solve>
+int search_by_projection_sim3(Solve&& solve, KeyFrame* pKF, const Sim3& Scw, const std::vector<MapPoint*>& vpPoints,
+                              const std::vector<KeyFrame*>* vpPointsKFs, std::vector<MapPoint*>& vpMatched, std::vector<KeyFrame*>* vpMatchedKF,
+                              int th, float ratioHamming) {
+  gfs_sim3_search_problem k = sim3_search_keyframe<Access>(*pKF, vpPointsKFs ? GFS_SIM3_SBP_KFS : GFS_SIM3_SBP, (float)th, ratioHamming, 0);
+  Access::sim3_pose(Scw, k.Tcw_q, k.Tcw_t, k.Ow);
+  if ((int)vpMatched.size() < k.n_kp || (vpMatchedKF && (int)vpMatchedKF->size() < k.n_kp) || (vpPointsKFs && vpPointsKFs->size() < vpPoints.size()))
+    throw std::invalid_argument("SearchByProjection: vpMatched / vpMatchedKF / vpPointsKFs are too short");
+  // Set of MapPoints already found in the KeyFrame
+  std::set<MapPoint*> spAlreadyFound(vpMatched.begin(), vpMatched.end());
+  spAlreadyFound.erase(static_cast<MapPoint*>(nullptr));
+  FuseList L;
+  fuse_gather<Access>(vpPoints, L);
+  std::vector<uint8_t> skip(vpPoints.size() + 1, 0), taken((size_t)k.n_kp + 1, 0);
+  for (size_t i = 0; i < vpPoints.size(); i++) skip[i] = !L.present[i] || vpPoints[i]->isBad() || spAlreadyFound.count(vpPoints[i]);
+  for (int j = 0; j < k.n_kp; j++) taken[j] = vpMatched[j] != nullptr;
+  k.mp_skip = skip.data();
+  k.kp_taken = taken.data();
+  const gfs_fuse_points lp = L.view();
+  Sim3SearchOutputs out;
+  gfs_sim3_search_result r = out.view(vpPoints.size());
+  check(solve(&lp, 1, &k, 1, &r), "gfs_sim3_search");
+  int nmatches = 0;
+  for (size_t iMP = 0; iMP < vpPoints.size(); iMP++) {
+    if (out.exit[iMP] != GFS_FUSE_MATCHED) continue;
+    vpMatched[out.best_idx[iMP]] = vpPoints[iMP];
+    if (vpMatchedKF) (*vpMatchedKF)[out.best_idx[iMP]] = (*vpPointsKFs)[iMP];
+    nmatches++;
+  }
+  return nmatches;
+}
+
+// ORBmatcher::SearchByProjection(pKF, Scw, vpPoints, vpMatched, th, ratioHamming)
+template <class Access, class KeyFrame, class MapPoint, class Sim3, class Solve>
+int SearchByProjectionSim3(Solve&& solve, KeyFrame* pKF, const Sim3& Scw, const std::vector<MapPoint*>& vpPoints, std::vector<MapPoint*>& vpMatched,
+                           int th, float ratioHamming = 1.0f) {
+  return search_by_projection_sim3<Access, KeyFrame, MapPoint>(solve, pKF, Scw, vpPoints, nullptr, vpMatched, nullptr, th, ratioHamming);
+}
+
+// ORBmatcher::SearchByProjection(pKF, Scw, vpPoints, vpPointsKFs, vpMatched, vpMatchedKF, th, ratioHamming)
+template <class Access, class KeyFrame, class MapPoint, class Sim3, class Solve>
+int SearchByProjectionSim3(Solve&& solve, KeyFrame* pKF, const Sim3& Scw, const std::vector<MapPoint*>& vpPoints,
+                           const std::vector<KeyFrame*>& vpPointsKFs, std::vector<MapPoint*>& vpMatched, std::vector<KeyFrame*>& vpMatchedKF, int th,
+                           float ratioHamming = 1.0f) {
+  return search_by_projection_sim3<Access, KeyFrame, MapPoint>(solve, pKF, Scw, vpPoints, &vpPointsKFs, vpMatched, &vpMatchedKF, th, ratioHamming);
+}
+
+// the numeric core of the Sim3 searches on the GPU: one handle, its reserve grown to the largest call seen
+class Sim3Searcher {
+ public:
+  Sim3Searcher(int max_kp = 4096, int device = 0) { check(gfs_sbp_create(device, 64, max_kp, 1, &h_), "gfs_sbp_create"); }
+  ~Sim3Searcher() { gfs_sbp_destroy(h_); }
+  Sim3Searcher(const Sim3Searcher&) = delete;
+  Sim3Searcher& operator=(const Sim3Searcher&) = delete;
+  int solve(const gfs_fuse_points* lists, int n_lists, const gfs_sim3_search_problem* problems, int B, gfs_sim3_search_result* results) {
+    int n = 0;
+    for (int l = 0; l < n_lists; l++) n = std::max(n, lists[l].n_mp);
+    if (n_lists > lists_ || n > points_ || B > problems_) {  // the library refuses what exceeds the reserve (it never truncates): grow it first
+      const int nl = std::max(n_lists, lists_), np = std::max(std::max(n, 64), points_), nk = std::max(B, problems_);
+      check(gfs_sbp_reserve_sim3_search(h_, nl, np, nk), "gfs_sbp_reserve_sim3_search");
+      lists_ = nl;
+      points_ = np;
+      problems_ = nk;
+    }
+    return gfs_sim3_search(h_, lists, n_lists, problems, B, results);
+  }
+  auto solver() {
+    return [this](const gfs_fuse_points* l, int nl, const gfs_sim3_search_problem* k, int B, gfs_sim3_search_result* r) {
+      return solve(l, nl, k, B, r);
+    };
+  }
+
+ private:
+  gfs_sbp* h_ = nullptr;
+  int lists_ = 0, points_ = 0, problems_ = 0;
 };
 
 // ------------------------------------------------------------------------------------------------------------------------

@@ -685,6 +685,81 @@ def fuse_problem(seed, n_points=1000, n_kp=1000, n_keyframes=1, scale_factor=1.2
     return dict(lists=[pts], keyframes=kfs)
 
 
+def sim3_search_problem(seed, mode, n_points=1000, n_kp=1000, n_problems=1, th=None, ratio_hamming=None, scale_factor=1.2, n_levels=8,
+                        cluster_every=10, taken_frac=0.08, skip_frac=0.05, masks=True, width=640, height=480):
+    """Synthetic input of the three Sim3 searches of loop closing (reference src/ORBmatcher.cc:1550-1654 mode 0, :432-529 mode 1,
+    :531-636 mode 2) for one list of `n_points` map points searched in `n_problems` key frames of `n_kp` key-points each, as
+    gfs_sim3_search takes it (include/gfs_abi.h): -> dict(lists=[points dict], problems=[problem dict, ...]).
+
+    The scene is fuse_problem's (every exit of the loop is taken, Hamming ties included), the key frame's pose standing for the
+    SE3 part of Scw.  On top of it one point in `cluster_every` heads a cluster: two to four other list entries become copies of
+    it (same position, normal and distances, so the same projection in every key frame) whose descriptors differ from the head's in
+    one to three bits, and every key frame gets two or three more key-points within a pixel and a half of the head's own key-point,
+    on its octave, a few bits from the head's descriptor -- so the members of a cluster want the same key-points, and in the
+    projection modes who comes first decides who gets which.  With `masks`, `taken_frac` of the key-points are taken at entry
+    (kp_taken; projection modes only), a cluster's best key-point more often than others, and `skip_frac` of the points carry
+    mp_skip.  th and ratio_hamming default to the call sites' values: 4 for Fuse; 3 and 1.5 for mode 1; 8 and 1.5 for mode 2."""
+    mode = int(mode)
+    th = {0: 4.0, 1: 3.0, 2: 8.0}[mode] if th is None else th
+    ratio_hamming = 1.5 if ratio_hamming is None else ratio_hamming
+    base = fuse_problem(seed, n_points=n_points, n_kp=n_kp, n_keyframes=n_problems, scale_factor=scale_factor, n_levels=n_levels, th=th,
+                        width=width, height=height)
+    rng = np.random.default_rng(seed + 32452843)
+    pts = {k: np.array(v) for k, v in base["lists"][0].items()}
+    kfs = [dict(kf, kps_un=kf["kps_un"].copy(), desc=kf["desc"].copy()) for kf in base["keyframes"]]
+
+    def flipped(d, nbits):
+        d = d.copy()
+        b = rng.choice(256, nbits, replace=False)
+        np.bitwise_xor.at(d, b // 8, (1 << (b % 8)).astype(np.uint8))
+        return d
+
+    heads = []
+    if n_points >= 4 and cluster_every > 0:
+        free = list(rng.permutation(n_points))
+        for _ in range(max(1, n_points // cluster_every)):
+            if len(free) < 5:
+                break
+            h = int(free.pop())
+            members = [int(free.pop()) for _ in range(int(rng.integers(2, 5)))]
+            for m in members:
+                for k in ("mp_xw", "mp_normal", "mp_min_dist", "mp_max_dist"):
+                    pts[k][m] = pts[k][h]
+                pts["mp_desc"][m] = flipped(pts["mp_desc"][h], int(rng.integers(1, 4)))
+            heads.append(h)
+    problems = []
+    for kf in kfs:
+        n = len(kf["kps_un"])
+        taken = (rng.random(n) < taken_frac).astype(np.uint8)
+        if n >= 8 and heads:
+            kbits = np.unpackbits(kf["desc"], axis=1)
+            used = set()
+            for h in heads:
+                d = (kbits != np.unpackbits(pts["mp_desc"][h])[None, :]).sum(1)
+                j = int(np.argmin(d))
+                if d[j] > 18 or j in used:  # the head has no key-point of its own in this key frame
+                    continue
+                used.add(j)
+                for _ in range(int(rng.integers(2, 4))):
+                    e = int(rng.integers(0, n))
+                    if e in used:
+                        continue
+                    used.add(e)
+                    kf["kps_un"][e] = kf["kps_un"][j]
+                    kf["kps_un"]["x"][e] = np.float32(np.clip(kf["kps_un"]["x"][j] + rng.uniform(-1.5, 1.5), 0, width - 1))
+                    kf["kps_un"]["y"][e] = np.float32(np.clip(kf["kps_un"]["y"][j] + rng.uniform(-1.5, 1.5), 0, height - 1))
+                    kf["desc"][e] = flipped(pts["mp_desc"][h], int(rng.integers(1, 9)))
+                    taken[e] = 0
+                taken[j] = rng.random() < 0.3
+        p = {k: kf[k] for k in ("Tcw_q", "Tcw_t", "Ow", "fx", "fy", "cx", "cy", "min_x", "max_x", "min_y", "max_y", "grid_w_inv", "grid_h_inv",
+                                "scale_factors", "n_levels", "log_scale_factor", "kps_un", "desc", "list")}
+        p.update(mode=mode, th=np.float32(th), ratio_hamming=np.float32(ratio_hamming),
+                 kp_taken=taken if (masks and mode != 0) else None,
+                 mp_skip=(rng.random(n_points) < skip_frac).astype(np.uint8) if masks else None)
+        problems.append(p)
+    return dict(lists=[pts], problems=problems)
+
+
 def _rot_from_quat(q):
     x, y, z, w = q / np.linalg.norm(q)
     return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)],

@@ -630,6 +630,67 @@ int gfs_sbp_reserve_fuse(gfs_sbp* h, int max_lists, int max_points_per_list, int
  * [0, n_lists), a key-point octave outside [0, n_levels) or a NULL array.  Nothing is truncated; the handle stays usable. */
 int gfs_fuse_search(gfs_sbp* h, const gfs_fuse_points* lists, int n_lists, const gfs_fuse_keyframe* kfs, int B, gfs_fuse_result* results);
 
+/*      int ORBmatcher::Fuse(KeyFrame* pKF, Sophus::Sim3f& Scw, const vector<MapPoint*>& vpPoints, float th,
+ *                           vector<MapPoint*>& vpReplacePoint)                   src/ORBmatcher.cc:1550-1654
+ *      int ORBmatcher::SearchByProjection(KeyFrame* pKF, Sophus::Sim3f& Scw, const vector<MapPoint*>& vpPoints,
+ *                           vector<MapPoint*>& vpMatched, int th, float ratioHamming)                  :432-529
+ *      int ORBmatcher::SearchByProjection(KeyFrame* pKF, Sophus::Sim3f& Scw, const vector<MapPoint*>& vpPoints,
+ *                           const vector<KeyFrame*>& vpPointsKFs, vector<MapPoint*>& vpMatched,
+ *                           vector<KeyFrame*>& vpMatchedKF, int th, float ratioHamming)                :531-636
+ *    the three Sim3 searches of loop closing (src/LoopClosing.cc:811, :841, :1016, :2224-2302) under one rule, any number of
+ *    (list, problem) pairs in one launch: projection with Tcw = SE3f(Scw.rotationMatrix(), Scw.translation() / Scw.scale()) and
+ *    Ow = Tcw.inverse().translation(), which the CALLER forms (gfs_host::FuseSim3 / SearchAndFuse / SearchByProjectionSim3,
+ *    geoflowslam_amd/host/gfs_adaptors.hpp); the gates of gfs_fuse_search without the chi2 gates and mvuRight; the window; the
+ *    level filter; the Hamming minimum.  In the projection modes a match takes its key-point away from every later point of the
+ *    list (vpMatched[bestIdx] = pMP): the results are those of the sequential loop.  Single-camera pinhole key frames.  float,
+ *    every operation rounded once, sums left to right: DESIGN.md section 20 states the rule. */
+#define GFS_SIM3_FUSE 0          /* Fuse: Pinhole::project; bestDist starts at INT_MAX; matched when bestDist <= TH_LOW */
+#define GFS_SIM3_SBP 1           /* :432: Pinhole::project; key-points with kp_taken or taken by an earlier point are skipped;
+                                    bestDist starts at 256; matched when bestDist <= TH_LOW * ratio_hamming */
+#define GFS_SIM3_SBP_KFS 2       /* :531: as GFS_SIM3_SBP with u = fx * (Pc0 * (1 / Pc2)) + cx (:571-576) */
+#define GFS_FUSE_SKIPPED 8       /* the point's mp_skip byte is set: pMP->isBad() || spAlreadyFound.count(pMP) at entry */
+#define GFS_SIM3_SEARCH_LISTED 4 /* candidates the device lists per point in the projection modes; a point whose listed candidates
+                                    are all taken by earlier points while more exist is searched again on the host */
+typedef struct {
+  int32_t mode;                  /* GFS_SIM3_* */
+  float ratio_hamming;           /* ratioHamming (projection modes; not read in GFS_SIM3_FUSE) */
+  float Tcw_q[4], Tcw_t[3];      /* Tcw: unit quaternion (x, y, z, w), translation */
+  float Ow[3];                   /* Tcw.inverse().translation() */
+  float fx, fy, cx, cy;          /* pKF->fx .. cy (Pinhole) */
+  float min_x, max_x, min_y, max_y; /* mnMinX ... mnMaxY */
+  float grid_w_inv, grid_h_inv;  /* mfGridElementWidthInv / HeightInv (64 x 48 grid) */
+  const float* scale_factors;    /* mvScaleFactors */
+  int32_t n_levels;              /* mnScaleLevels, 1..16 */
+  float log_scale_factor;        /* mfLogScaleFactor */
+  float th;                      /* window factor; the int th of the projection searches as the float it converts to */
+  int32_t n_kp;                  /* N, <= the handle's max_cur */
+  const gfs_keypoint* kps_un;    /* [n_kp] mvKeysUn (octave in [0, n_levels)) */
+  const uint8_t* desc;           /* [n_kp][32] mDescriptors */
+  const uint8_t* kp_taken;       /* [n_kp] vpMatched[idx] != NULL at entry, or NULL = none; must be NULL in GFS_SIM3_FUSE */
+  const uint8_t* mp_skip;        /* [n_mp of the list] the point leaves at entry with GFS_FUSE_SKIPPED, or NULL = none */
+  int32_t list;                  /* which of the call's point lists is searched in this problem */
+} gfs_sim3_search_problem;
+
+typedef struct {                 /* caller-owned arrays, [n_mp of the problem's list] */
+  uint8_t* exit;                 /* GFS_FUSE_* 0..7, or GFS_FUSE_SKIPPED */
+  int32_t* best_idx;             /* bestIdx when the point's candidate loop ended, after the dependency between points (projection
+                                    modes); -1 where nothing survived or the point left earlier */
+  int32_t* best_dist;            /* bestDist likewise; 256, or INT_MAX in GFS_SIM3_FUSE, where nothing survived or the point left earlier */
+  int32_t* level;                /* nPredictedLevel; defined where exit is GFS_FUSE_EMPTY_WINDOW .. GFS_FUSE_MATCHED */
+  int32_t n_matched;             /* the number of points with exit == GFS_FUSE_MATCHED */
+} gfs_sim3_search_result;
+
+/* Allocates the workspace of gfs_sim3_search: up to max_lists lists of up to max_points_per_list map points, searched in up to
+ * max_problems problems per call (handles that never call it are unchanged). */
+int gfs_sbp_reserve_sim3_search(gfs_sbp* h, int max_lists, int max_points_per_list, int max_problems);
+/* B (list, problem) searches in one launch (host pointers); the lists are uploaded once.  Refused before anything is staged, the
+ * handle left usable -- GFS_ERR_CAPACITY: more lists, a longer list, more problems or more key-points (the handle's max_cur) than
+ * reserved.  GFS_ERR_INVALID_ARG: an unknown mode, n_levels outside 1..16, a key-point octave outside [0, n_levels), a `list` index
+ * outside [0, n_lists), a NULL required array, kp_taken given in GFS_SIM3_FUSE, or in a projection mode a ratio_hamming that is
+ * negative, NaN or has 50.0f * ratio_hamming >= 256.0f (the reference would then write vpMatched[-1]). */
+int gfs_sim3_search(gfs_sbp* h, const gfs_fuse_points* lists, int n_lists, const gfs_sim3_search_problem* problems, int B,
+                    gfs_sim3_search_result* results);
+
 /*      void LocalMapping::CreateNewMapPoints()                                   src/LocalMapping.cc:803-1127
  *    for every neighbour key frame in order: ORBmatcher::SearchForTriangulation (src/ORBmatcher.cc:1158-1376: Hamming search over the
  *    key-point pairs that share a vocabulary node, epipole and epipolar-line gates, optional rotation histogram) and the triangulation
@@ -1050,7 +1111,7 @@ int gfs_frame_cloud_extract_device(gfs_frame_cloud* h, const void* dev_xyzw, con
 
 /* ============================================================================================
  * 15. Optimizer::OptimizeEssentialGraph (src/Optimizer.cc:2042-2413) — the Sim3 pose graph of LoopClosing::CorrectLoop
- *     (src/LoopClosing.cc:1257), between gfs_fuse_search and gfs_gba_solve.
+ *     (src/LoopClosing.cc:1257), between SearchAndFuse (gfs_sim3_search in GFS_SIM3_FUSE mode) and gfs_gba_solve.
  *    The flattened graph: one VertexSim3Expmap per vertex (the estimate Siw = (q, t, s), `fixed` for the map's init key-frame,
  *    _fix_scale = fix_scale for all), one EdgeSim3 per edge with vertex 0 = i, vertex 1 = j, the measurement Sji (ICP edges: Sij, the
  *    vertices swapped) and information w I_7 (1; ICP edges 3), in the order the reference makes them: the sums run in this order.

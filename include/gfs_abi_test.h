@@ -122,6 +122,11 @@ int gfs_test_essential_graph_lists(int n_vertices, int n_edges, const uint8_t* v
                                    int64_t* counts, int32_t* free_index, int32_t* blk_ij, int64_t* blk_begin, int64_t cap_blocks,
                                    int32_t* contrib, int64_t cap_contrib);
 
+/* Test hook: how many workgroups a gfs_sim3_search launch of this handle may hold (csrc/sim3_search.hip: beyond the cap a workgroup
+ * keeps its grid and walks several 256-point chunks).  0 = the default, what the device holds at once; < 0 = a workgroup a chunk;
+ * > 0 = that many.  The results do not depend on it.  After gfs_sbp_reserve_sim3_search; a new reserve resets it. */
+int gfs_test_sim3_search_groups(gfs_sbp* h, int max_groups);
+
 /* GPU test hook: the stages of the handle's last gfs_frame_cloud_extract(_device) call, as they lie on the device: the scan table
  * (rows of begin, count, pad flags 1 = start | 2 = end, candidates in the scans in front), edge_raw / surf_raw, the two voxel
  * filters' outputs and the two radius filters' outputs.  Their sizes are the call's info; a NULL pointer skips a stage.  Refused
