@@ -155,6 +155,48 @@ def pose_result(S, keep, n):
                 iterations_run=int(S.iterations_run))
 
 
+class Sim3OptProblem(C.Structure):
+    _fields_ = [("s12", C.c_double * 8), ("cam1", C.c_double * 4), ("cam2", C.c_double * 4), ("th2", C.c_float),
+                ("fix_scale", C.c_int32), ("n_pairs", C.c_int32), ("x1c", C.c_void_p), ("x2c", C.c_void_p), ("obs1", C.c_void_p),
+                ("obs2", C.c_void_p), ("inv_sigma2_1", C.c_void_p), ("inv_sigma2_2", C.c_void_p)]
+
+
+class Sim3OptSolution(C.Structure):
+    _fields_ = [("s12", C.c_double * 8), ("n_in", C.c_int32), ("n_bad", C.c_int32), ("status", C.c_int32),
+                ("iterations_run", C.c_int32 * 2), ("pair_state", C.c_void_p), ("chi2", C.c_void_p)]
+
+
+SIM3_OPT_EARLY_RETURN, SIM3_OPT_BOTH_PHASES = 0, 1  # GFS_SIM3_OPT_* (include/gfs_abi.h)
+SIM3_PAIR_INLIER, SIM3_PAIR_REMOVED_FIRST, SIM3_PAIR_REMOVED_FINAL = 0, 1, 2  # GFS_SIM3_PAIR_*
+
+
+def sim3_opt_structs(prob):
+    """ctypes views of one OptimizeSim3 problem dict (synth.sim3_opt_problem; shared with the CPU restatement's tests)."""
+    P, S = Sim3OptProblem(), Sim3OptSolution()
+    n = int(prob["n_pairs"]) if "n_pairs" in prob else len(prob["x1c"])
+    keep = dict(x1c=np.ascontiguousarray(prob["x1c"], np.float64).reshape(-1, 3), x2c=np.ascontiguousarray(prob["x2c"], np.float64).reshape(-1, 3),
+                obs1=np.ascontiguousarray(prob["obs1"], np.float64).reshape(-1, 2), obs2=np.ascontiguousarray(prob["obs2"], np.float64).reshape(-1, 2),
+                inv_sigma2_1=np.ascontiguousarray(prob["inv_sigma2_1"], np.float32), inv_sigma2_2=np.ascontiguousarray(prob["inv_sigma2_2"], np.float32),
+                pair_state=np.zeros(max(n, 1), np.uint8), chi2=np.zeros((max(n, 1), 2), np.float64))
+    P.s12[:] = [float(v) for v in prob["s12"]]
+    P.cam1[:] = [float(v) for v in prob["cam1"]]
+    P.cam2[:] = [float(v) for v in prob["cam2"]]
+    P.th2 = float(prob["th2"])
+    P.fix_scale = int(bool(prob["fix_scale"]))
+    P.n_pairs = n
+    for name in ("x1c", "x2c", "obs1", "obs2", "inv_sigma2_1", "inv_sigma2_2"):
+        setattr(P, name, keep[name].ctypes.data)
+    S.pair_state = keep["pair_state"].ctypes.data
+    S.chi2 = keep["chi2"].ctypes.data
+    return P, S, keep, n
+
+
+def sim3_opt_result(S, keep, n):
+    return dict(s12=np.array(S.s12[:]), n_in=int(S.n_in), n_bad=int(S.n_bad), status=int(S.status),
+                iterations_run=(int(S.iterations_run[0]), int(S.iterations_run[1])), pair_state=keep["pair_state"][:max(n, 0)].copy(),
+                chi2=keep["chi2"][:max(n, 0)].copy())
+
+
 class ClaheConfig(C.Structure):
     _fields_ = [("clip_limit", C.c_double), ("tiles_x", C.c_int32), ("tiles_y", C.c_int32), ("residual_variant", C.c_int32)]
 
@@ -679,6 +721,7 @@ ABI_SYMBOLS = [
     "gfs_test_gba_panel_rows", "gfs_test_gba_lists", "gfs_test_gba_tile_layout",
     "gfs_essential_graph_create", "gfs_essential_graph_destroy", "gfs_essential_graph_optimize", "gfs_essential_graph_correct_points",
     "gfs_essential_graph_last_info", "gfs_test_essential_graph_first_trial", "gfs_test_essential_graph_lists",
+    "gfs_sim3_opt_create", "gfs_sim3_opt_destroy", "gfs_sim3_optimize", "gfs_test_glibc_exp",
     "gfs_frame_create", "gfs_frame_destroy", "gfs_depth_to_cloud", "gfs_depth_to_cloud_batch_device", "gfs_depth_convert_u16_batch_device", "gfs_stereo_from_rgbd",
     "gfs_stereo_from_rgbd_batch_device",
     "gfs_pose_create", "gfs_pose_destroy", "gfs_pose_optimize", "gfs_pose_set_sum_order",
@@ -796,6 +839,11 @@ def lib():
             L.gfs_essential_graph_last_info.argtypes = [vp, C.POINTER(EssentialGraphInfo)]
             L.gfs_test_essential_graph_first_trial.argtypes = [vp, C.POINTER(EssentialGraphProblem), C.POINTER(EssentialGraphTrial)]
             L.gfs_test_essential_graph_lists.argtypes = [i, i, vp, vp, vp, vp, vp, vp, vp, C.c_int64, vp, C.c_int64]
+        if hasattr(L, "gfs_sim3_opt_create"):
+            L.gfs_sim3_opt_create.argtypes = [i, i, i, C.POINTER(vp)]
+            L.gfs_sim3_opt_destroy.argtypes = [vp]
+            L.gfs_sim3_optimize.argtypes = [vp, vp, i, vp]
+            L.gfs_test_glibc_exp.argtypes = [i, vp, i, vp]
         if hasattr(L, "gfs_lba_solve_lidar"):
             L.gfs_lba_lidar_reserve.argtypes = [vp, i]
             L.gfs_lba_solve_lidar.argtypes = [vp, C.POINTER(LbaProblem), C.POINTER(LbaLidar), C.POINTER(LbaSolution), vp, vp]
@@ -2089,6 +2137,39 @@ class PoseOptimizer:
             keeps.append((keep, n))
         _check(lib().gfs_pose_optimize(self.h, PP, B, SS), "gfs_pose_optimize")
         res = [pose_result(SS[f], *keeps[f]) for f in range(B)]
+        return res[0] if single else res
+
+
+class Sim3Optimizer:
+    """ORB_SLAM3::Optimizer::OptimizeSim3 (reference src/Optimizer.cc:2797-3054) on flattened pairs (gfs_sim3_opt_problem in
+    include/gfs_abi.h).  A batch of problems is one kernel launch, one workgroup each."""
+
+    def __init__(self, max_batch=16, max_pairs=2048, device=0):
+        self.h = C.c_void_p()
+        _check(lib().gfs_sim3_opt_create(device, int(max_batch), int(max_pairs), C.byref(self.h)), "gfs_sim3_opt_create")
+
+    def close(self):
+        if getattr(self, "h", None) and _lib is not None:
+            _lib.gfs_sim3_opt_destroy(self.h)
+        self.h = None
+
+    __del__ = close
+
+    def OptimizeSim3(self, problems):
+        """problems: one problem dict or a list of them (sim3_opt_structs) -> result dict(s): s12 [8] (the input after the early
+        return), n_in, n_bad, status (SIM3_OPT_*), iterations_run (two), pair_state [n] (SIM3_PAIR_*), chi2 [n, 2].  Raises GfsError
+        (code GFS_ERR_CAPACITY / GFS_ERR_INVALID_ARG) on a refusal; the handle stays usable."""
+        single = isinstance(problems, dict)
+        probs = [problems] if single else list(problems)
+        B = len(probs)
+        PP, SS = (Sim3OptProblem * max(B, 1))(), (Sim3OptSolution * max(B, 1))()
+        keeps = []
+        for f, prob in enumerate(probs):
+            P, S, keep, n = sim3_opt_structs(prob)
+            PP[f], SS[f] = P, S
+            keeps.append((keep, n))
+        _check(lib().gfs_sim3_optimize(self.h, PP, B, SS), "gfs_sim3_optimize")
+        res = [sim3_opt_result(SS[f], *keeps[f]) for f in range(B)]
         return res[0] if single else res
 
 

@@ -189,6 +189,13 @@ GFS_HD double pow_exp_inline(double x, double xtail, bool negate) {
   const double scale = as_f64(sbits);
   return fma_(scale, tmp, scale);
 }
+// exp(x): e_exp.c is exp_inline without the tail (same table, same polynomial, same r and scale; for |x| < 2^-54 it returns 1.0 + x,
+// which rounds to the 1.0 returned here).  VertexSim3Expmap::oplusImpl takes the scale of an update through it (types/sim3.h:82).
+// Checked against the host's libm by tests/test_glibc_exp.py.
+GFS_HD double exp(double x) {
+  if (x != x) return x + x;
+  return pow_exp_inline(x, 0.0, false);
+}
 GFS_HD double pow3(double x) {  // pow(x, 3.0)
   uint64_t ix = as_u64(x);
   const bool neg = (ix >> 63) != 0;

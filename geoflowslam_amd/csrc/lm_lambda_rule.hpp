@@ -14,14 +14,16 @@
 
 namespace gfs_pose_lm {
 
-// H21: the lower triangle of a 6x6, packed a (a + 1) / 2 + c
-GFS_LMR_HD double max_abs_diagonal6(const double* H21) {
+// Hp: the lower triangle of an N x N, packed a (a + 1) / 2 + c (N = 7: the Sim3 block of k_sim3_opt, sim3_opt.hip)
+template <int N>
+GFS_LMR_HD double max_abs_diagonal(const double* Hp) {
   double maxDiagonal = 0;
-  for (int a = 0; a < 6; a++) {
-    const double h = fabs(H21[a * (a + 1) / 2 + a]);
+  for (int a = 0; a < N; a++) {
+    const double h = fabs(Hp[a * (a + 1) / 2 + a]);
     maxDiagonal = h < maxDiagonal ? maxDiagonal : h;
   }
   return maxDiagonal;
 }
+GFS_LMR_HD double max_abs_diagonal6(const double* H21) { return max_abs_diagonal<6>(H21); }
 
 }  // namespace gfs_pose_lm

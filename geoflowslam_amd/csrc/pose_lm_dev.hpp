@@ -162,14 +162,14 @@ __device__ __forceinline__ S ordered_sum(const T* __restrict__ v, int cnt, S s) 
   return s;
 }
 
-// Eigen::LDLT<MatrixXd>::compute + isPositive + solve on a 6x6 (see oracle/pose_oracle.cpp for the line-by-line restatement).
+// Eigen::LDLT<MatrixXd>::compute + isPositive + solve on an N x N, N = 6 or 7 (see oracle/pose_oracle.cpp for the line-by-line restatement).
 // The pivot search and the symmetric transpositions index the matrix at run time.  A private array indexed at run time lives in
 // scratch memory, an LDS copy costs a round trip per access on the one lane everybody waits for (6.5 us a solve, a fifth of
 // k_pose_opt): here every index is a compile-time constant -- the loops over k, i, j are unrolled and the run-time pivot p is matched
-// against its (at most five) possible values, each with its own statically indexed swaps -- so the 21 entries of the lower
+// against its (at most N - 1) possible values, each with its own statically indexed swaps -- so the entries of the lower
 // triangle, y and the transpositions stay in registers.  The arithmetic, operation for operation, is the restatement's.
-template <int K, int PC>
-__device__ __forceinline__ void ldlt6_transpose(double (&A)[6][6]) {  // symmetric transposition k <-> p restricted to the lower triangle
+template <int N, int K, int PC>
+__device__ __forceinline__ void ldlt_transpose(double (&A)[N][N]) {  // symmetric transposition k <-> p restricted to the lower triangle
 #pragma unroll
   for (int j = 0; j < K; j++) {
     const double tmp = A[K][j];
@@ -177,7 +177,7 @@ __device__ __forceinline__ void ldlt6_transpose(double (&A)[6][6]) {  // symmetr
     A[PC][j] = tmp;
   }
 #pragma unroll
-  for (int i = PC + 1; i < 6; i++) {
+  for (int i = PC + 1; i < N; i++) {
     const double tmp = A[i][K];
     A[i][K] = A[i][PC];
     A[i][PC] = tmp;
@@ -194,22 +194,23 @@ __device__ __forceinline__ void ldlt6_transpose(double (&A)[6][6]) {  // symmetr
     A[PC][i] = tmp;
   }
 }
-template <int K>
-__device__ __forceinline__ void ldlt6_step(double (&A)[6][6], int (&tr)[6], int& sign) {
+template <int N, int K>
+__device__ __forceinline__ void ldlt_step(double (&A)[N][N], int (&tr)[N], int& sign) {
   int p = K;
   double best = fabs(A[K][K]);
 #pragma unroll
-  for (int i = K + 1; i < 6; i++)
+  for (int i = K + 1; i < N; i++)
     if (fabs(A[i][i]) > best) {
       best = fabs(A[i][i]);
       p = i;
     }
   tr[K] = p;
-  if constexpr (K + 1 < 6) { if (p == K + 1) ldlt6_transpose<K, K + 1 < 6 ? K + 1 : 5>(A); }
-  if constexpr (K + 2 < 6) { if (p == K + 2) ldlt6_transpose<K, K + 2 < 6 ? K + 2 : 5>(A); }
-  if constexpr (K + 3 < 6) { if (p == K + 3) ldlt6_transpose<K, K + 3 < 6 ? K + 3 : 5>(A); }
-  if constexpr (K + 4 < 6) { if (p == K + 4) ldlt6_transpose<K, K + 4 < 6 ? K + 4 : 5>(A); }
-  if constexpr (K + 5 < 6) { if (p == K + 5) ldlt6_transpose<K, K + 5 < 6 ? K + 5 : 5>(A); }
+  if constexpr (K + 1 < N) { if (p == K + 1) ldlt_transpose<N, K, K + 1 < N ? K + 1 : N - 1>(A); }
+  if constexpr (K + 2 < N) { if (p == K + 2) ldlt_transpose<N, K, K + 2 < N ? K + 2 : N - 1>(A); }
+  if constexpr (K + 3 < N) { if (p == K + 3) ldlt_transpose<N, K, K + 3 < N ? K + 3 : N - 1>(A); }
+  if constexpr (K + 4 < N) { if (p == K + 4) ldlt_transpose<N, K, K + 4 < N ? K + 4 : N - 1>(A); }
+  if constexpr (K + 5 < N) { if (p == K + 5) ldlt_transpose<N, K, K + 5 < N ? K + 5 : N - 1>(A); }
+  if constexpr (K + 6 < N) { if (p == K + 6) ldlt_transpose<N, K, K + 6 < N ? K + 6 : N - 1>(A); }
   if constexpr (K > 0) {
     double temp[K];
 #pragma unroll
@@ -219,7 +220,7 @@ __device__ __forceinline__ void ldlt6_step(double (&A)[6][6], int (&tr)[6], int&
     for (int j = 0; j < K; j++) acc += A[K][j] * temp[j];
     A[K][K] -= acc;
 #pragma unroll
-    for (int i = K + 1; i < 6; i++) {
+    for (int i = K + 1; i < N; i++) {
       double a2 = 0;
 #pragma unroll
       for (int j = 0; j < K; j++) a2 += A[i][j] * temp[j];
@@ -229,7 +230,7 @@ __device__ __forceinline__ void ldlt6_step(double (&A)[6][6], int (&tr)[6], int&
   const double akk = A[K][K];
   if (fabs(akk) > 0) {
 #pragma unroll
-    for (int i = K + 1; i < 6; i++) A[i][K] /= akk;
+    for (int i = K + 1; i < N; i++) A[i][K] /= akk;
   }
   if (sign == 1) {
     if (akk < 0) sign = 2;
@@ -240,64 +241,74 @@ __device__ __forceinline__ void ldlt6_step(double (&A)[6][6], int (&tr)[6], int&
     else if (akk < 0) sign = -1;
   }
 }
-template <int K>
-__device__ __forceinline__ void ldlt6_swap_y(double (&y)[6], int p) {  // y[K] <-> y[p], p >= K
-  if constexpr (K + 1 < 6) { if (p == K + 1) { const double t = y[K]; y[K] = y[K + 1 < 6 ? K + 1 : 5]; y[K + 1 < 6 ? K + 1 : 5] = t; } }
-  if constexpr (K + 2 < 6) { if (p == K + 2) { const double t = y[K]; y[K] = y[K + 2 < 6 ? K + 2 : 5]; y[K + 2 < 6 ? K + 2 : 5] = t; } }
-  if constexpr (K + 3 < 6) { if (p == K + 3) { const double t = y[K]; y[K] = y[K + 3 < 6 ? K + 3 : 5]; y[K + 3 < 6 ? K + 3 : 5] = t; } }
-  if constexpr (K + 4 < 6) { if (p == K + 4) { const double t = y[K]; y[K] = y[K + 4 < 6 ? K + 4 : 5]; y[K + 4 < 6 ? K + 4 : 5] = t; } }
-  if constexpr (K + 5 < 6) { if (p == K + 5) { const double t = y[K]; y[K] = y[K + 5 < 6 ? K + 5 : 5]; y[K + 5 < 6 ? K + 5 : 5] = t; } }
+template <int N, int K>
+__device__ __forceinline__ void ldlt_swap_y(double (&y)[N], int p) {  // y[K] <-> y[p], p >= K
+  if constexpr (K + 1 < N) { if (p == K + 1) { const double t = y[K]; y[K] = y[K + 1 < N ? K + 1 : N - 1]; y[K + 1 < N ? K + 1 : N - 1] = t; } }
+  if constexpr (K + 2 < N) { if (p == K + 2) { const double t = y[K]; y[K] = y[K + 2 < N ? K + 2 : N - 1]; y[K + 2 < N ? K + 2 : N - 1] = t; } }
+  if constexpr (K + 3 < N) { if (p == K + 3) { const double t = y[K]; y[K] = y[K + 3 < N ? K + 3 : N - 1]; y[K + 3 < N ? K + 3 : N - 1] = t; } }
+  if constexpr (K + 4 < N) { if (p == K + 4) { const double t = y[K]; y[K] = y[K + 4 < N ? K + 4 : N - 1]; y[K + 4 < N ? K + 4 : N - 1] = t; } }
+  if constexpr (K + 5 < N) { if (p == K + 5) { const double t = y[K]; y[K] = y[K + 5 < N ? K + 5 : N - 1]; y[K + 5 < N ? K + 5 : N - 1] = t; } }
+  if constexpr (K + 6 < N) { if (p == K + 6) { const double t = y[K]; y[K] = y[K + 6 < N ? K + 6 : N - 1]; y[K + 6 < N ? K + 6 : N - 1] = t; } }
 }
-// H: the 21 entries of the lower triangle, packed a (a + 1) / 2 + c; lambda is added to the diagonal.  false unless positive
-__device__ __forceinline__ bool ldlt6_solve_positive(const double* H21, double lambda, const double* b, double* x) {
-  double A[6][6];
+// H: the N (N + 1) / 2 entries of the lower triangle, packed a (a + 1) / 2 + c; lambda is added to the diagonal.  false unless
+// positive.  N = 6: the pose block of k_pose_opt and k_pl_round; N = 7: the Sim3 block of k_sim3_opt (sim3_opt.hip)
+template <int N>
+__device__ __forceinline__ bool ldlt_solve_positive(const double* Hp, double lambda, const double* b, double* x) {
+  double A[N][N];
   {
     int o = 0;
 #pragma unroll
-    for (int a = 0; a < 6; a++)
+    for (int a = 0; a < N; a++)
 #pragma unroll
       for (int c = 0; c <= a; c++) {
-        A[a][c] = H21[o];
-        A[c][a] = H21[o];
+        A[a][c] = Hp[o];
+        A[c][a] = Hp[o];
         o++;
       }
   }
 #pragma unroll
-  for (int a = 0; a < 6; a++) A[a][a] += lambda;
-  int tr[6], sign = 0;
-  ldlt6_step<0>(A, tr, sign);
-  ldlt6_step<1>(A, tr, sign);
-  ldlt6_step<2>(A, tr, sign);
-  ldlt6_step<3>(A, tr, sign);
-  ldlt6_step<4>(A, tr, sign);
-  ldlt6_step<5>(A, tr, sign);
+  for (int a = 0; a < N; a++) A[a][a] += lambda;
+  static_assert(N == 6 || N == 7, "the steps and transpositions below are written out for 6 and 7");
+  int tr[N], sign = 0;
+  ldlt_step<N, 0>(A, tr, sign);
+  ldlt_step<N, 1>(A, tr, sign);
+  ldlt_step<N, 2>(A, tr, sign);
+  ldlt_step<N, 3>(A, tr, sign);
+  ldlt_step<N, 4>(A, tr, sign);
+  ldlt_step<N, 5>(A, tr, sign);
+  if constexpr (N > 6) ldlt_step<N, 6>(A, tr, sign);
   if (sign != 1) return false;
-  double y[6];
+  double y[N];
 #pragma unroll
-  for (int i = 0; i < 6; i++) y[i] = b[i];
-  ldlt6_swap_y<0>(y, tr[0]);
-  ldlt6_swap_y<1>(y, tr[1]);
-  ldlt6_swap_y<2>(y, tr[2]);
-  ldlt6_swap_y<3>(y, tr[3]);
-  ldlt6_swap_y<4>(y, tr[4]);
+  for (int i = 0; i < N; i++) y[i] = b[i];
+  ldlt_swap_y<N, 0>(y, tr[0]);
+  ldlt_swap_y<N, 1>(y, tr[1]);
+  ldlt_swap_y<N, 2>(y, tr[2]);
+  ldlt_swap_y<N, 3>(y, tr[3]);
+  ldlt_swap_y<N, 4>(y, tr[4]);
+  if constexpr (N > 6) ldlt_swap_y<N, 5>(y, tr[5]);
 #pragma unroll
-  for (int i = 0; i < 6; i++)
+  for (int i = 0; i < N; i++)
 #pragma unroll
     for (int j = 0; j < i; j++) y[i] -= A[i][j] * y[j];
 #pragma unroll
-  for (int i = 0; i < 6; i++) y[i] = fabs(A[i][i]) > 2.2250738585072014e-308 ? y[i] / A[i][i] : 0.0;
+  for (int i = 0; i < N; i++) y[i] = fabs(A[i][i]) > 2.2250738585072014e-308 ? y[i] / A[i][i] : 0.0;
 #pragma unroll
-  for (int i = 5; i >= 0; i--)
+  for (int i = N - 1; i >= 0; i--)
 #pragma unroll
-    for (int j = i + 1; j < 6; j++) y[i] -= A[j][i] * y[j];
-  ldlt6_swap_y<4>(y, tr[4]);
-  ldlt6_swap_y<3>(y, tr[3]);
-  ldlt6_swap_y<2>(y, tr[2]);
-  ldlt6_swap_y<1>(y, tr[1]);
-  ldlt6_swap_y<0>(y, tr[0]);
+    for (int j = i + 1; j < N; j++) y[i] -= A[j][i] * y[j];
+  if constexpr (N > 6) ldlt_swap_y<N, 5>(y, tr[5]);
+  ldlt_swap_y<N, 4>(y, tr[4]);
+  ldlt_swap_y<N, 3>(y, tr[3]);
+  ldlt_swap_y<N, 2>(y, tr[2]);
+  ldlt_swap_y<N, 1>(y, tr[1]);
+  ldlt_swap_y<N, 0>(y, tr[0]);
 #pragma unroll
-  for (int i = 0; i < 6; i++) x[i] = y[i];
+  for (int i = 0; i < N; i++) x[i] = y[i];
   return true;
+}
+__device__ __forceinline__ bool ldlt6_solve_positive(const double* H21, double lambda, const double* b, double* x) {
+  return ldlt_solve_positive<6>(H21, lambda, b, x);
 }
 
 // The 6x6 solve of k_pose_opt's tree-sum mode (k_pl_round never calls it: its tree mode keeps the pivoted solve).  H + lambda I of

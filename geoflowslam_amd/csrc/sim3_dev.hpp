@@ -130,14 +130,13 @@ GFS_SIM3_HD void w_coefficients(double sigma, double s, double theta, bool small
   }
 }
 
-// Sim3(const Vector7d& update), sim3.h:70-142; returns the branch taken
-GFS_SIM3_HD int sim3_exp(const double* u, double* S) {
+// Sim3(const Vector7d& update), sim3.h:70-142, with s = exp(sigma) handed in; returns the branch taken
+GFS_SIM3_HD int sim3_exp_given_scale(const double* u, double s, double* S) {
   const double om[3] = {u[0], u[1], u[2]}, ups[3] = {u[3], u[4], u[5]};
   const double sigma = u[6];
   const double theta = sqrt(om[0] * om[0] + om[1] * om[1] + om[2] * om[2]);
   double O[9], O2[9], R[9];
   skew_and_square(om, O, O2);
-  const double s = ::exp(sigma);
   const bool small_angle = theta < kEps;
   double A, B, C;
   w_coefficients(sigma, s, theta, small_angle, &A, &B, &C);
@@ -154,6 +153,9 @@ GFS_SIM3_HD int sim3_exp(const double* u, double* S) {
   S[7] = s;
   return (fabs(sigma) < kEps ? 0 : kBranchSigma) | (small_angle ? 0 : kBranchAngle);
 }
+
+// the scale by the library's exp: glibc's on the host, the device library's on the device (the essential-graph kernels)
+GFS_SIM3_HD int sim3_exp(const double* u, double* S) { return sim3_exp_given_scale(u, ::exp(u[6]), S); }
 
 // W.lu().solve(t): PartialPivLU of a 3 x 3 (the first largest |entry| of the column is the pivot), then the two column-oriented
 // triangular solves
@@ -247,6 +249,14 @@ GFS_SIM3_HD void sim3_oplus(const double* est, const double* update, bool fix_sc
   for (int i = 0; i < 7; i++) u[i] = update[i];
   if (fix_scale) u[6] = 0;
   sim3_exp(u, e);
+  sim3_mul(e, est, out);
+}
+// the same with glibc's exp restated (glibc_math.hpp): host and device give the same bits also when the scale is free (sim3_opt.hip)
+GFS_SIM3_HD void sim3_oplus_glibc_exp(const double* est, const double* update, bool fix_scale, double* out) {
+  double u[7], e[8];
+  for (int i = 0; i < 7; i++) u[i] = update[i];
+  if (fix_scale) u[6] = 0;
+  sim3_exp_given_scale(u, gfs_glibc::exp(u[6]), e);
   sim3_mul(e, est, out);
 }
 // EdgeSim3::computeError: (C v0 v1^-1).log(); returns the log's branch

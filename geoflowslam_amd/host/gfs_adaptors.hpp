@@ -2861,6 +2861,164 @@ class EssentialGraphOptimizer {
   int device_;
 };
 
+// ------------------------------------------------------------------------------------------------------------------------
+// int Optimizer::OptimizeSim3(KeyFrame* pKF1, KeyFrame* pKF2, vector<MapPoint*>& vpMatches1, g2o::Sim3& g2oS12, const float th2,
+//                             const bool bFixScale, Eigen::Matrix<double, 7, 7>& mAcumHessian, const bool bAllPoints)
+//                                                                                          reference src/Optimizer.cc:2797-3054
+// as real code around the flat solver.  Everything of :2815-2984 that touches pointers runs here, with the
+// caller's own Eigen as the reference writes it: P3D1c = R1w * P3D1w + t1w in float, cast to double; the skips (no match; a bad point:
+// nBadMPs; no pMP1: nMatchWithoutMP; i2 < 0 && !bAllPoints; P3D2c(2) < 0) in the reference's order; the i2 < 0 branch's float
+// invz, x, y.  The pairs that get edges are compacted, vnIndexEdge kept.  After the solve vpMatches1[idx] is nulled for the pairs the
+// first check removed (also when the early return follows) and for those the final check rejects; g2oS12 is written and mAcumHessian
+// zeroed (:3031: it is never filled) only when both optimizations ran; the return value is nIn, or 0 after the early return.
+// One thing reads differently from what its text suggests: cv::KeyPoint(cv::Point2f(x, y), pMP2->mnTrackScaleLevel) (:2957) passes
+// the level as the key-point's SIZE; its octave stays 0, so the i2 < 0 branch weighs its edge with pKF2->mvInvLevelSigma2[0].
+// Single-camera pinhole key frames only (NLeft == -1, Access::is_pinhole): anything else throws.
+// Classes as for the Sim3 searches, plus KeyFrame::GetRotation(), GetTranslation() (Eigen floats), mvKeysUn, mvInvLevelSigma2, fx, fy,
+// cx, cy; MapPoint::GetWorldPos(), GetIndexInKeyFrame(), isBad(); and of `Access`:
+//     static void sim3(const Sim3&, double S[8]);      // g2o::Sim3 -> rotation().coeffs() (x, y, z, w), translation(), scale()
+//     static void set_sim3(Sim3&, const double S[8]);  // g2oS12 = g2o::Sim3(Quaterniond(w, x, y, z), t, s): as they are, not renormalised
+// `solve(problem, solution)` is the numeric core: Sim3Optimizer::solve below (gfs_sim3_optimize on the GPU).
+// ------------------------------------------------------------------------------------------------------------------------
+struct Sim3OptCounters {  // the reference's local counters (:2845-2849, :2991-2992), for whoever wants to log them
+  int nCorrespondences = 0, nBadMPs = 0, nInKF2 = 0, nOutKF2 = 0, nMatchWithoutMP = 0, nBad = 0, nBadOutKF2 = 0;
+};
+
+template <class Access, class KeyFrame, class MapPoint, class Sim3, class Hessian, class Solve>
+int OptimizeSim3(Solve&& solve, KeyFrame* pKF1, KeyFrame* pKF2, std::vector<MapPoint*>& vpMatches1, Sim3& g2oS12, const float th2,
+                 const bool bFixScale, Hessian& mAcumHessian, const bool bAllPoints, Sim3OptCounters* counters = nullptr) {
+  if (pKF1->NLeft != -1 || pKF2->NLeft != -1 || !Access::is_pinhole(*pKF1) || !Access::is_pinhole(*pKF2))
+    throw std::invalid_argument("OptimizeSim3: single-camera pinhole key frames only");
+  // Camera poses
+  const auto R1w = pKF1->GetRotation();
+  const auto t1w = pKF1->GetTranslation();
+  const auto R2w = pKF2->GetRotation();
+  const auto t2w = pKF2->GetTranslation();
+  using Vector3f = typename std::decay<decltype(t1w)>::type;
+
+  const int N = vpMatches1.size();
+  const std::vector<MapPoint*> vpMapPoints1 = pKF1->GetMapPointMatches();
+  std::vector<size_t> vnIndexEdge;
+  std::vector<bool> vbIsInKF2;
+  std::vector<double> x1c, x2c, obs1, obs2;
+  std::vector<float> w1, w2;
+  Sim3OptCounters c;
+
+  for (int i = 0; i < N; i++) {
+    if (!vpMatches1[i]) continue;
+
+    MapPoint* pMP1 = vpMapPoints1[i];
+    MapPoint* pMP2 = vpMatches1[i];
+
+    const int i2 = std::get<0>(pMP2->GetIndexInKeyFrame(pKF2));
+
+    Vector3f P3D1c;
+    Vector3f P3D2c;
+
+    if (pMP1 && pMP2) {
+      if (!pMP1->isBad() && !pMP2->isBad()) {
+        Vector3f P3D1w = pMP1->GetWorldPos();
+        P3D1c = R1w * P3D1w + t1w;
+        Vector3f P3D2w = pMP2->GetWorldPos();
+        P3D2c = R2w * P3D2w + t2w;
+      } else {
+        c.nBadMPs++;
+        continue;
+      }
+    } else {
+      c.nMatchWithoutMP++;
+      continue;  // (the reference adds a lone vertex for pMP2 here: no edge ever uses it)
+    }
+
+    if (i2 < 0 && !bAllPoints) continue;
+
+    if (P3D2c(2) < 0) continue;
+
+    c.nCorrespondences++;
+
+    // Set edge x1 = S12*X2
+    const auto& kpUn1 = pKF1->mvKeysUn[i];
+    obs1.push_back(kpUn1.pt.x);
+    obs1.push_back(kpUn1.pt.y);
+    w1.push_back(pKF1->mvInvLevelSigma2[kpUn1.octave]);
+
+    // Set edge x2 = S21*X1
+    if (i2 >= 0) {
+      const auto& kpUn2 = pKF2->mvKeysUn[i2];
+      obs2.push_back(kpUn2.pt.x);
+      obs2.push_back(kpUn2.pt.y);
+      w2.push_back(pKF2->mvInvLevelSigma2[kpUn2.octave]);
+      c.nInKF2++;
+    } else {
+      float invz = 1 / P3D2c(2);
+      float x = P3D2c(0) * invz;
+      float y = P3D2c(1) * invz;
+      obs2.push_back(x);
+      obs2.push_back(y);
+      w2.push_back(pKF2->mvInvLevelSigma2[0]);  // cv::KeyPoint(pt, size = mnTrackScaleLevel): octave 0
+      c.nOutKF2++;
+    }
+    for (int k = 0; k < 3; k++) {
+      x1c.push_back((double)P3D1c(k));
+      x2c.push_back((double)P3D2c(k));
+    }
+    vnIndexEdge.push_back(i);
+    vbIsInKF2.push_back(i2 >= 0);
+  }
+
+  const int n = (int)vnIndexEdge.size();
+  gfs_sim3_opt_problem p{};
+  Access::sim3(g2oS12, p.s12);
+  p.cam1[0] = pKF1->fx, p.cam1[1] = pKF1->fy, p.cam1[2] = pKF1->cx, p.cam1[3] = pKF1->cy;
+  p.cam2[0] = pKF2->fx, p.cam2[1] = pKF2->fy, p.cam2[2] = pKF2->cx, p.cam2[3] = pKF2->cy;
+  p.th2 = th2;
+  p.fix_scale = bFixScale ? 1 : 0;
+  p.n_pairs = n;
+  p.x1c = x1c.data();
+  p.x2c = x2c.data();
+  p.obs1 = obs1.data();
+  p.obs2 = obs2.data();
+  p.inv_sigma2_1 = w1.data();
+  p.inv_sigma2_2 = w2.data();
+  std::vector<uint8_t> state(n + 1, 0);
+  gfs_sim3_opt_solution s{};
+  s.pair_state = state.data();
+  solve(p, s);
+
+  for (int i = 0; i < n; i++) {
+    if (state[i] == GFS_SIM3_PAIR_INLIER) continue;
+    vpMatches1[vnIndexEdge[i]] = static_cast<MapPoint*>(NULL);
+    if (state[i] == GFS_SIM3_PAIR_REMOVED_FIRST && !vbIsInKF2[i]) c.nBadOutKF2++;
+  }
+  c.nBad = s.n_bad;
+  if (counters) *counters = c;
+  if (s.status != GFS_SIM3_OPT_BOTH_PHASES) return 0;  // nCorrespondences - nBad < 10 (:3024)
+  mAcumHessian.setZero();
+  Access::set_sim3(g2oS12, s.s12);
+  return s.n_in;
+}
+
+// numeric core of Optimizer::OptimizeSim3 on the device (gfs_sim3_optimize)
+class Sim3Optimizer {
+ public:
+  explicit Sim3Optimizer(int max_batch = 16, int max_pairs = 4096, int device = 0) {
+    check(gfs_sim3_opt_create(device, max_batch, max_pairs, &h_), "gfs_sim3_opt_create");
+  }
+  ~Sim3Optimizer() { gfs_sim3_opt_destroy(h_); }
+  Sim3Optimizer(const Sim3Optimizer&) = delete;
+  Sim3Optimizer& operator=(const Sim3Optimizer&) = delete;
+  void solve(const gfs_sim3_opt_problem& p, gfs_sim3_opt_solution& s) { check(gfs_sim3_optimize(h_, &p, 1, &s), "gfs_sim3_optimize"); }
+  template <class Access, class KeyFrame, class MapPoint, class Sim3, class Hessian>
+  int OptimizeSim3(KeyFrame* pKF1, KeyFrame* pKF2, std::vector<MapPoint*>& vpMatches1, Sim3& g2oS12, const float th2, const bool bFixScale,
+                   Hessian& mAcumHessian, const bool bAllPoints = false, Sim3OptCounters* counters = nullptr) {
+    return gfs_host::OptimizeSim3<Access>([this](const gfs_sim3_opt_problem& p, gfs_sim3_opt_solution& s) { this->solve(p, s); }, pKF1, pKF2,
+                                          vpMatches1, g2oS12, th2, bFixScale, mAcumHessian, bAllPoints, counters);
+  }
+
+ private:
+  gfs_sim3_opt* h_ = nullptr;
+};
+
 }  // namespace gfs_host
 
 // The drop-ins written against the reference's own types (cv::Mat, cv::KeyPoint, Eigen, Sophus, ORB_SLAM3::ORBextractor as a base

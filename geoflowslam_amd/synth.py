@@ -1256,3 +1256,46 @@ def pose_graph(seed, n_keyframes, fix_scale=True, drift=0.05, loop=0, icp_edges=
                 edge_s=np.array([e[2][2] for e in edges]), edge_w=np.array([e[3] for e in edges]),
                 fix_scale=bool(fix_scale), iterations=20, lambda_init=1e-16, points=pts, point_ref=ref,
                 kind=np.array([e[4] for e in edges], np.int32), true_R=np.stack(Rt), true_t=np.stack(tt))
+
+
+def sim3_opt_problem(seed, n_pairs=150, fix_scale=True, outlier_share=0.15, noise_px=0.7, th2=10.0, rot_deg=2.0, trans=0.05,
+                     scale=None, estimate_rot_deg=0.5, estimate_trans=0.02, estimate_scale=0.01, outlier_px=40.0, n_levels=8,
+                     scale_factor=1.2, width=640, height=480):
+    """Synthetic input of Optimizer::OptimizeSim3 (reference src/Optimizer.cc:2797-3054), flattened the way the adaptor flattens two
+    key frames: camera 1 and camera 2 see `n_pairs` common points, x1 = s R x2 + t with the true S12 = (R, t, s) (s = 1 with fix_scale
+    unless `scale` is given, else a few percent off 1); x1c / x2c are the points in the two camera frames computed in float and cast
+    to double as the reference does, the observations their projections plus noise_px of Gaussian noise, rounded to float like
+    cv::KeyPoint, each at a random pyramid level with inv_sigma2 = scale_factor^(-2 level).  A share of the pairs are gross outliers
+    (one observation moved by about outlier_px).  The estimate handed in is the truth perturbed by estimate_rot_deg / estimate_trans
+    (and estimate_scale when the scale is free).  -> dict for api.Sim3Optimizer.OptimizeSim3, plus true_s12 [8] and outlier [n]."""
+    rng = np.random.default_rng(seed)
+    n = int(n_pairs)
+    fx, fy, cx, cy = (float(np.float32(v)) for v in intrinsics(width, height))
+    s_true = float(scale) if scale is not None else (1.0 if fix_scale else float(1.0 + 0.05 * rng.uniform(-1, 1)))
+    R = _rot(*(np.deg2rad(rot_deg) * rng.uniform(-1, 1, 3)))
+    t = trans * rng.uniform(-1, 1, 3)
+    u, v, z = rng.uniform(20, width - 20, n), rng.uniform(20, height - 20, n), rng.uniform(1.0, 6.0, n)
+    x2 = np.stack([(u - cx) / fx * z, (v - cy) / fy * z, z], 1).astype(np.float32).reshape(n, 3)
+    x1 = (s_true * (x2.astype(np.float64) @ R.T) + t).astype(np.float32).reshape(n, 3)
+    x1c, x2c = x1.astype(np.float64), x2.astype(np.float64)
+
+    def project(x):
+        return np.stack([fx * x[:, 0] / x[:, 2] + cx, fy * x[:, 1] / x[:, 2] + cy], 1).reshape(n, 2)
+
+    obs1, obs2 = project(x1c) + noise_px * rng.normal(size=(n, 2)), project(x2c) + noise_px * rng.normal(size=(n, 2))
+    outlier = rng.random(n) < outlier_share
+    side = rng.random(n) < 0.5
+    kick = outlier_px * (1.0 + rng.random((n, 2))) * rng.choice([-1.0, 1.0], (n, 2))
+    obs1[outlier & side] += kick[outlier & side]
+    obs2[outlier & ~side] += kick[outlier & ~side]
+    obs1, obs2 = obs1.astype(np.float32).astype(np.float64), obs2.astype(np.float32).astype(np.float64)
+    sigma2 = (np.float32(scale_factor) ** np.arange(n_levels, dtype=np.float32)) ** 2
+    inv_sigma2 = (np.float32(1.0) / sigma2).astype(np.float32)
+    w1, w2 = inv_sigma2[rng.integers(0, n_levels, n)], inv_sigma2[rng.integers(0, n_levels, n)]
+    Re = _rot(*(np.deg2rad(estimate_rot_deg) * rng.uniform(-1, 1, 3))) @ R
+    te = t + estimate_trans * rng.uniform(-1, 1, 3)
+    se = s_true if fix_scale else s_true * float(1.0 + estimate_scale * rng.uniform(-1, 1))
+    return dict(s12=np.concatenate([_quat_xyzw(Re), te, [se]]), cam1=np.array([fx, fy, cx, cy]), cam2=np.array([fx, fy, cx, cy]),
+                th2=float(np.float32(th2)), fix_scale=bool(fix_scale), x1c=x1c, x2c=x2c, obs1=obs1, obs2=obs2,
+                inv_sigma2_1=np.ascontiguousarray(w1, np.float32), inv_sigma2_2=np.ascontiguousarray(w2, np.float32),
+                true_s12=np.concatenate([_quat_xyzw(R), t, [s_true]]), outlier=outlier)

@@ -1171,6 +1171,51 @@ int gfs_essential_graph_correct_points(gfs_essential_graph* h, int n_vertices, c
 int gfs_essential_graph_last_info(const gfs_essential_graph* h, gfs_essential_graph_info* info);
 
 /* ============================================================================================
+ * 16. Optimizer::OptimizeSim3 (src/Optimizer.cc:2797-3054) — the Sim3 refinement of loop verification, between the two Sim3
+ *     projection searches of LoopClosing::DetectCommonRegionsFromBoW (:811-841) and DetectAndReffineSim3FromLastKF (:579-616).
+ *    One free VertexSim3Expmap (S12, _fix_scale = fix_scale); per pair, in this order, an EdgeSim3ProjectXYZ (obs1 - cam1.project(
+ *    S12.map(x2c))) and an EdgeInverseSim3ProjectXYZ (obs2 - cam2.project(S12.inverse().map(x1c))) against fixed points, information
+ *    inv_sigma2 I_2, g2o's numeric Jacobians (central differences through the vertex's oplus, delta 1e-9).  BlockSolverX +
+ *    LinearSolverDense (Eigen::LDLT of the 7 x 7, also with fix_scale) + Levenberg.  The schedule: optimize(5) with Huber kernels of
+ *    delta (float)sqrt(th2); a pair leaves when either chi2 -- as the solve's last computeActiveErrors left it, which after rejected
+ *    trials is NOT the chi2 at the estimate -- is > th2; fewer than 10 pairs left: return 0, S12 untouched; else optimize(10 if a pair
+ *    left else 5) without kernels, the errors recomputed, nIn counted.  Every sum over the edges runs in edge order (e12(0), e21(0),
+ *    e12(1), ...).  B problems are one launch, one workgroup each.  DESIGN.md section 21.
+ *    Refused before anything is staged, the handle left usable -- GFS_ERR_CAPACITY: B above max_batch or n_pairs above max_pairs;
+ *    GFS_ERR_INVALID_ARG: a NULL required array, n_pairs < 0, th2 not finite or <= 0.  n_pairs == 0 is valid (the early return).
+ * ============================================================================================ */
+#define GFS_SIM3_OPT_EARLY_RETURN 0 /* status: nCorrespondences - nBad < 10 after the first phase; s12 is the input */
+#define GFS_SIM3_OPT_BOTH_PHASES 1  /* status: both phases ran */
+#define GFS_SIM3_PAIR_INLIER 0        /* pair_state: counted in n_in (after an early return: not removed by the first check) */
+#define GFS_SIM3_PAIR_REMOVED_FIRST 1 /* removed by the first check (vpMatches1[idx] = NULL, edges removed) */
+#define GFS_SIM3_PAIR_REMOVED_FINAL 2 /* failed the final check (vpMatches1[idx] = NULL) */
+typedef struct {
+  double s12[8];            /* g2oS12: quaternion (x, y, z, w), translation, scale */
+  double cam1[4], cam2[4];  /* fx, fy, cx, cy of pKF1->mpCamera / pKF2->mpCamera (pinhole) */
+  float th2;
+  int32_t fix_scale;
+  int32_t n_pairs;          /* the pairs that got edges, in the order of the reference's loop */
+  const double* x1c;        /* [n_pairs][3] P3D1c.cast<double>() */
+  const double* x2c;        /* [n_pairs][3] P3D2c.cast<double>() */
+  const double* obs1;       /* [n_pairs][2] kpUn1.pt */
+  const double* obs2;       /* [n_pairs][2] kpUn2.pt, or the float x / z, y / z of the i2 < 0 branch */
+  const float* inv_sigma2_1; /* [n_pairs] pKF1->mvInvLevelSigma2[kpUn1.octave] */
+  const float* inv_sigma2_2; /* [n_pairs] pKF2->mvInvLevelSigma2[kpUn2.octave] */
+} gfs_sim3_opt_problem;
+typedef struct {
+  double s12[8];                  /* vSim3_recov->estimate(); the input after an early return */
+  int32_t n_in, n_bad, status;    /* the return value (0 after an early return); nBad of the first check; GFS_SIM3_OPT_* */
+  int32_t iterations_run[2];      /* outer Levenberg iterations of the two optimize() calls */
+  uint8_t* pair_state;            /* [n_pairs] GFS_SIM3_PAIR_* */
+  double* chi2;                   /* [n_pairs][2] (may be NULL) e12 / e21 chi2 as last read by a check: the final one for a pair that
+                                     reached it, else the first one's */
+} gfs_sim3_opt_solution;
+typedef struct gfs_sim3_opt gfs_sim3_opt;
+int gfs_sim3_opt_create(int device, int max_batch, int max_pairs, gfs_sim3_opt** out);
+void gfs_sim3_opt_destroy(gfs_sim3_opt* h);
+int gfs_sim3_optimize(gfs_sim3_opt* h, const gfs_sim3_opt_problem* problems, int B, gfs_sim3_opt_solution* solutions);
+
+/* ============================================================================================
  * Timing helper for the harness: HIP events on a given stream (bench.py measures the dominant kernel
  * with these rather than torch events, which only see torch's current stream).
  * ============================================================================================ */

@@ -24,6 +24,9 @@ int gfs_test_orb_blur_tiles(int rows, int cols, int nlevels, float scale_factor,
  * (csrc/glibc_math.hpp) that the pose / window / registration optimizers use for SE3Quat::exp
  * (Thirdparty/g2o/g2o/types/se3quat.h:223-257) and the Levenberg step control (core/optimization_algorithm_levenberg.cpp:127). */
 int gfs_test_glibc_math(int device, const double* x, int n, double* sin_out, double* cos_out, double* pow3_out);
+/* GPU test hook: exp(x) of n doubles on the device with the restated glibc 2.35 arithmetic (csrc/glibc_math.hpp) that k_sim3_opt uses
+ * for the scale of a VertexSim3Expmap update (Thirdparty/g2o/g2o/types/sim3.h:82). */
+int gfs_test_glibc_exp(int device, const double* x, int n, double* out);
 /* GPU test hook: logf(x) of n floats on the device with the restated glibc 2.35 arithmetic (csrc/glibc_math.hpp) that the frustum
  * kernel uses for MapPoint::PredictScale (src/MapPoint.cc:565-579). */
 int gfs_test_glibc_logf(int device, const float* x, int n, float* out);

@@ -1,0 +1,511 @@
+// Sequential host statement of Optimizer::OptimizeSim3 (reference src/Optimizer.cc:2797-3054) on the structs of gfs_sim3_optimize, for
+// tests/test_sim3_opt_restatement.py, tests/test_gpu_sim3_opt.py and tests/host/sim3_opt_adaptor_test.cpp.  One loop per edge as g2o
+// runs it: every edge computes its own perturbed estimates in linearizeOplus (core/base_binary_edge.hpp:131-205), the sums are plain
+// `+=` in edge order, the 7 x 7 goes through a line-by-line Eigen::LDLT (unblocked, diagonal pivoting).  It shares no code with
+// geoflowslam_amd/csrc/sim3_opt.hip: the Sim3 arithmetic below restates g2o's types/sim3.h itself, templated on the scalar so that the
+// same text runs in double (the bits the device is held to; std::sin / cos / exp / pow are glibc's) and in long double (how far
+// double's own rounding moves the result).  Built with g++ -O2 -ffp-contract=off.
+#include <algorithm>
+#include <cmath>
+#include <cstdint>
+#include <cstring>
+#include <limits>
+#include <vector>
+
+#include "../../include/gfs_abi.h"
+
+namespace {
+
+constexpr int kFirstIterations = 5, kMoreIterationsAfterRemoval = 10, kMoreIterations = 5;  // :2988, :3019-3022
+constexpr int kMinCorrespondences = 10;                                                     // :3024
+constexpr double kNumericDelta = 1e-9;                                                      // base_binary_edge.hpp:147
+
+template <class T>
+struct S3 {  // g2o::Sim3: quaternion (x, y, z, w), translation, scale
+  T q[4], t[3], s;
+};
+
+template <class T>
+void quat_rotate(const T* q, const T* v, T* o) {  // Eigen _transformVector
+  const T ux = 2 * (q[1] * v[2] - q[2] * v[1]), uy = 2 * (q[2] * v[0] - q[0] * v[2]), uz = 2 * (q[0] * v[1] - q[1] * v[0]);
+  o[0] = v[0] + q[3] * ux + (q[1] * uz - q[2] * uy);
+  o[1] = v[1] + q[3] * uy + (q[2] * ux - q[0] * uz);
+  o[2] = v[2] + q[3] * uz + (q[0] * uy - q[1] * ux);
+}
+template <class T>
+void R_to_quat(const T* m, T* q) {  // Quaterniond(R), Eigen 3.4: no normalisation
+  T t = m[0] + m[4] + m[8];
+  if (t > 0) {
+    t = std::sqrt(t + T(1.0));
+    q[3] = T(0.5) * t;
+    t = T(0.5) / t;
+    q[0] = (m[7] - m[5]) * t;
+    q[1] = (m[2] - m[6]) * t;
+    q[2] = (m[3] - m[1]) * t;
+    return;
+  }
+  int i = 0;
+  if (m[4] > m[0]) i = 1;
+  if (m[8] > m[4 * i]) i = 2;
+  const int j = (i + 1) % 3, k = (j + 1) % 3;
+  t = std::sqrt(m[4 * i] - m[4 * j] - m[4 * k] + T(1.0));
+  q[i] = T(0.5) * t;
+  t = T(0.5) / t;
+  q[3] = (m[3 * k + j] - m[3 * j + k]) * t;
+  q[j] = (m[3 * j + i] + m[3 * i + j]) * t;
+  q[k] = (m[3 * k + i] + m[3 * i + k]) * t;
+}
+
+// Sim3(const Vector7d& update), sim3.h:70-142
+template <class T>
+S3<T> sim3_exp(const T* u) {
+  const T eps = 0.00001;
+  const T om[3] = {u[0], u[1], u[2]}, ups[3] = {u[3], u[4], u[5]}, sigma = u[6];
+  const T theta = std::sqrt(om[0] * om[0] + om[1] * om[1] + om[2] * om[2]);
+  const T O[9] = {0, -om[2], om[1], om[2], 0, -om[0], -om[1], om[0], 0};
+  T O2[9], R[9], W[9];
+  for (int r = 0; r < 3; r++)
+    for (int c = 0; c < 3; c++) O2[3 * r + c] = O[3 * r] * O[c] + O[3 * r + 1] * O[3 + c] + O[3 * r + 2] * O[6 + c];
+  S3<T> out;
+  out.s = std::exp(sigma);
+  const T s = out.s;
+  T A, B, C;
+  const bool small = theta < eps;
+  if (std::fabs(sigma) < eps) {
+    C = 1;
+    if (small) {
+      A = T(1.) / T(2.);
+      B = T(1.) / T(6.);
+    } else {
+      const T theta2 = theta * theta;
+      A = (1 - std::cos(theta)) / (theta2);
+      B = (theta - std::sin(theta)) / (theta2 * theta);
+    }
+  } else {
+    C = (s - 1) / sigma;
+    if (small) {
+      const T sigma2 = sigma * sigma;
+      A = ((sigma - 1) * s + 1) / sigma2;
+      B = ((T(0.5) * sigma2 - sigma + 1) * s) / (sigma2 * sigma);
+    } else {
+      const T a = s * std::sin(theta), b = s * std::cos(theta), theta2 = theta * theta, sigma2 = sigma * sigma, c = theta2 + sigma2;
+      A = (a * sigma + (1 - b) * theta) / (theta * c);
+      B = (C - ((b - 1) * sigma + a * theta) / (c)) * T(1.) / (theta2);
+    }
+  }
+  if (small) {
+    for (int i = 0; i < 9; i++) R[i] = (i % 4 == 0 ? T(1) : T(0)) + O[i] + O2[i];
+  } else {
+    const T ca = std::sin(theta) / theta, cb = (1 - std::cos(theta)) / (theta * theta);
+    for (int i = 0; i < 9; i++) R[i] = (i % 4 == 0 ? T(1) : T(0)) + ca * O[i] + cb * O2[i];
+  }
+  R_to_quat(R, out.q);
+  for (int i = 0; i < 9; i++) W[i] = A * O[i] + B * O2[i] + C * (i % 4 == 0 ? T(1) : T(0));
+  for (int r = 0; r < 3; r++) out.t[r] = W[3 * r] * ups[0] + W[3 * r + 1] * ups[1] + W[3 * r + 2] * ups[2];
+  return out;
+}
+template <class T>
+S3<T> sim3_mul(const S3<T>& a, const S3<T>& b) {  // operator*, sim3.h:266-272
+  S3<T> o;
+  const T *p = a.q, *q = b.q;
+  o.q[3] = p[3] * q[3] - p[0] * q[0] - p[1] * q[1] - p[2] * q[2];
+  o.q[0] = p[3] * q[0] + p[0] * q[3] + p[1] * q[2] - p[2] * q[1];
+  o.q[1] = p[3] * q[1] + p[1] * q[3] + p[2] * q[0] - p[0] * q[2];
+  o.q[2] = p[3] * q[2] + p[2] * q[3] + p[0] * q[1] - p[1] * q[0];
+  T rt[3];
+  quat_rotate(a.q, b.t, rt);
+  for (int i = 0; i < 3; i++) o.t[i] = a.s * rt[i] + a.t[i];
+  o.s = a.s * b.s;
+  return o;
+}
+template <class T>
+S3<T> sim3_inverse(const S3<T>& a) {  // sim3.h:233-236
+  S3<T> o;
+  o.q[0] = -a.q[0], o.q[1] = -a.q[1], o.q[2] = -a.q[2], o.q[3] = a.q[3];
+  const T k = T(-1.) / a.s;
+  const T v[3] = {k * a.t[0], k * a.t[1], k * a.t[2]};
+  quat_rotate(o.q, v, o.t);
+  o.s = T(1.) / a.s;
+  return o;
+}
+template <class T>
+void sim3_map(const S3<T>& a, const T* xyz, T* o) {  // sim3.h:144-146
+  T r[3];
+  quat_rotate(a.q, xyz, r);
+  for (int i = 0; i < 3; i++) o[i] = a.s * r[i] + a.t[i];
+}
+
+// Eigen::LDLT<MatrixXd>::compute + isPositive + solve (LDLT.h, ldlt_inplace<Lower>::unblocked) on the full symmetric 7 x 7
+template <class T>
+bool ldlt7_solve_positive(const T H[49], const T* b, T* x) {
+  constexpr int N = 7;
+  T A[N][N];
+  for (int i = 0; i < N; i++)
+    for (int j = 0; j < N; j++) A[i][j] = H[N * i + j];
+  int tr[N], sign = 0;
+  for (int k = 0; k < N; k++) {
+    int p = k;
+    T best = std::fabs(A[k][k]);
+    for (int i = k + 1; i < N; i++)
+      if (std::fabs(A[i][i]) > best) {
+        best = std::fabs(A[i][i]);
+        p = i;
+      }
+    tr[k] = p;
+    if (p != k) {
+      for (int j = 0; j < k; j++) std::swap(A[k][j], A[p][j]);
+      for (int i = p + 1; i < N; i++) std::swap(A[i][k], A[i][p]);
+      std::swap(A[k][k], A[p][p]);
+      for (int i = k + 1; i < p; i++) std::swap(A[i][k], A[p][i]);
+    }
+    if (k > 0) {
+      T temp[N];
+      for (int j = 0; j < k; j++) temp[j] = A[j][j] * A[k][j];
+      T acc = 0;
+      for (int j = 0; j < k; j++) acc += A[k][j] * temp[j];
+      A[k][k] -= acc;
+      for (int i = k + 1; i < N; i++) {
+        T a2 = 0;
+        for (int j = 0; j < k; j++) a2 += A[i][j] * temp[j];
+        A[i][k] -= a2;
+      }
+    }
+    const T akk = A[k][k];
+    if (std::fabs(akk) > 0)
+      for (int i = k + 1; i < N; i++) A[i][k] /= akk;
+    if (sign == 1) {
+      if (akk < 0) sign = 2;
+    } else if (sign == -1) {
+      if (akk > 0) sign = 2;
+    } else if (sign == 0) {
+      if (akk > 0) sign = 1;
+      else if (akk < 0) sign = -1;
+    }
+  }
+  if (sign != 1) return false;
+  T y[N];
+  for (int i = 0; i < N; i++) y[i] = b[i];
+  for (int k = 0; k < N; k++) std::swap(y[k], y[tr[k]]);
+  for (int i = 0; i < N; i++)
+    for (int j = 0; j < i; j++) y[i] -= A[i][j] * y[j];
+  const T tol = std::numeric_limits<T>::min();
+  for (int i = 0; i < N; i++) y[i] = std::fabs(A[i][i]) > tol ? y[i] / A[i][i] : T(0);
+  for (int i = N - 1; i >= 0; i--)
+    for (int j = i + 1; j < N; j++) y[i] -= A[j][i] * y[j];
+  for (int k = N - 1; k >= 0; k--) std::swap(y[k], y[tr[k]]);
+  for (int i = 0; i < N; i++) x[i] = y[i];
+  return true;
+}
+
+}  // namespace
+
+// what a run went through, for the tests that assert their inputs reach the branches they are meant for
+struct s3r_trace {
+  int32_t end_reason[2];           // of each optimize(): 0 not run, 1 the iterations ran out, 2 qmax == 10, 3 rho == 0, 4 _nBad >= 3
+  int32_t rejected_trials[2];      // Levenberg trials that were popped
+  int32_t failed_solves[2];        // trials whose 7 x 7 was not positive
+  int32_t last_trial_rejected[2];  // the last trial of the call was popped: the edges hold errors that are not the estimate's
+  int32_t stale_flag_differences;  // pairs the first check would have flagged differently after a computeError()
+  int32_t pad;
+  double final_lambda[2];
+  double stale_largest_difference;  // largest |chi2 the first check read - chi2 at the estimate| over the edges
+};
+
+namespace {
+
+template <class T>
+struct Graph {
+  const gfs_sim3_opt_problem* p;
+  int n;
+  bool fix_scale;
+  T cam1[4], cam2[4], th2, delta;
+  S3<T> est;          // the vertex
+  std::vector<T> err;  // [2 n][2]: edge 2 i = e12(i), 2 i + 1 = e21(i)
+  std::vector<char> active, robust;
+  T x[7] = {0, 0, 0, 0, 0, 0, 0}, b[7], H[49];  // the solver's x lives as long as the optimizer
+
+  explicit Graph(const gfs_sim3_opt_problem* p_) : p(p_), n(p_->n_pairs), fix_scale(p_->fix_scale != 0) {
+    for (int k = 0; k < 4; k++) {
+      cam1[k] = p->cam1[k];
+      cam2[k] = p->cam2[k];
+      est.q[k] = p->s12[k];
+    }
+    for (int k = 0; k < 3; k++) est.t[k] = p->s12[4 + k];
+    est.s = p->s12[7];
+    th2 = (T)p->th2;                              // `> th2`: the float promoted
+    delta = (T)(float)std::sqrt(p->th2);          // const float deltaHuber = sqrt(th2)
+    err.assign(4 * (size_t)n, T(0));
+    active.assign(2 * (size_t)n, 1);
+    robust.assign(2 * (size_t)n, 1);
+  }
+  void oplus(const T* update_) {  // VertexSim3Expmap::oplusImpl: writes through its argument
+    T* update = const_cast<T*>(update_);
+    if (fix_scale) update[6] = 0;
+    est = sim3_mul(sim3_exp(update), est);
+  }
+  void compute_error(int e) {
+    const int i = e / 2;
+    T X[3], m[3];
+    if (e % 2 == 0) {  // EdgeSim3ProjectXYZ
+      for (int k = 0; k < 3; k++) X[k] = p->x2c[3 * i + k];
+      sim3_map(est, X, m);
+      err[2 * e] = (T)p->obs1[2 * i] - (cam1[0] * m[0] / m[2] + cam1[2]);
+      err[2 * e + 1] = (T)p->obs1[2 * i + 1] - (cam1[1] * m[1] / m[2] + cam1[3]);
+    } else {  // EdgeInverseSim3ProjectXYZ
+      for (int k = 0; k < 3; k++) X[k] = p->x1c[3 * i + k];
+      sim3_map(sim3_inverse(est), X, m);
+      err[2 * e] = (T)p->obs2[2 * i] - (cam2[0] * m[0] / m[2] + cam2[2]);
+      err[2 * e + 1] = (T)p->obs2[2 * i + 1] - (cam2[1] * m[1] / m[2] + cam2[3]);
+    }
+  }
+  T info(int e) const { return (T)(e % 2 == 0 ? p->inv_sigma2_1[e / 2] : p->inv_sigma2_2[e / 2]); }
+  T chi2(int e) const {
+    const T w = info(e);
+    return err[2 * e] * w * err[2 * e] + err[2 * e + 1] * w * err[2 * e + 1];
+  }
+  void huber(T e, T* rho) const {  // RobustKernelHuber::robustify
+    const T dsqr = delta * delta;
+    if (e <= dsqr) {
+      rho[0] = e;
+      rho[1] = 1.;
+    } else {
+      const T sqrte = std::sqrt(e);
+      rho[0] = 2 * sqrte * delta - dsqr;
+      rho[1] = delta / sqrte;
+    }
+  }
+  void compute_active_errors() {
+    for (int e = 0; e < 2 * n; e++)
+      if (active[e]) compute_error(e);
+  }
+  T active_robust_chi2() const {
+    T chi = 0.0;
+    for (int e = 0; e < 2 * n; e++) {
+      if (!active[e]) continue;
+      if (robust[e]) {
+        T rho[2];
+        huber(chi2(e), rho);
+        chi += rho[0];
+      } else {
+        chi += chi2(e);
+      }
+    }
+    return chi;
+  }
+  // BaseBinaryEdge::linearizeOplus, the Xj half (vertex 1 is the Sim3; vertex 0 is fixed)
+  void linearize(int e, T J[2][7]) {
+    const T delta_ = kNumericDelta;
+    const T scalar = 1.0 / (2 * delta_);
+    const T before[2] = {err[2 * e], err[2 * e + 1]};
+    T add[7] = {0, 0, 0, 0, 0, 0, 0}, bak[2];
+    for (int d = 0; d < 7; d++) {
+      const S3<T> backup = est;  // push
+      add[d] = delta_;
+      oplus(add);
+      compute_error(e);
+      bak[0] = err[2 * e], bak[1] = err[2 * e + 1];
+      est = backup;  // pop, push
+      add[d] = -delta_;
+      oplus(add);
+      compute_error(e);
+      bak[0] -= err[2 * e], bak[1] -= err[2 * e + 1];
+      est = backup;
+      add[d] = 0.0;
+      J[0][d] = scalar * bak[0];
+      J[1][d] = scalar * bak[1];
+    }
+    err[2 * e] = before[0], err[2 * e + 1] = before[1];
+  }
+  void build_system() {
+    for (int k = 0; k < 49; k++) H[k] = 0;
+    for (int k = 0; k < 7; k++) b[k] = 0;
+    for (int e = 0; e < 2 * n; e++) {
+      if (!active[e]) continue;
+      T J[2][7];
+      linearize(e, J);
+      const T w = info(e);
+      T omega_r[2] = {-(w * err[2 * e]), -(w * err[2 * e + 1])}, ww = w;
+      if (robust[e]) {
+        T rho[2];
+        huber(chi2(e), rho);
+        ww = rho[1] * w;
+        omega_r[0] *= rho[1];
+        omega_r[1] *= rho[1];
+      }
+      for (int a = 0; a < 7; a++) {
+        b[a] += J[0][a] * omega_r[0] + J[1][a] * omega_r[1];
+        for (int c = 0; c < 7; c++) H[7 * a + c] += (J[0][a] * ww) * J[0][c] + (J[1][a] * ww) * J[1][c];
+      }
+    }
+  }
+  // SparseOptimizer::optimize(its) around OptimizationAlgorithmLevenberg::solve; returns the outer iterations run
+  int optimize(int its, int phase, s3r_trace* tr) {
+    int n_active = 0;
+    for (int e = 0; e < 2 * n; e++) n_active += active[e];
+    if (n_active == 0) return 0;  // no vertex to optimize
+    T lambda = 0, ni = 2;
+    int n_bad = 0, run = 0, reason = 1;
+    for (int it = 0; it < its; it++) {
+      compute_active_errors();
+      T currentChi = active_robust_chi2(), tempChi = currentChi;
+      const T iniChi = currentChi;
+      build_system();
+      if (it == 0) {
+        T maxDiagonal = 0;
+        for (int j = 0; j < 7; j++) maxDiagonal = std::max(std::fabs(H[8 * j]), maxDiagonal);
+        lambda = T(1e-5) * maxDiagonal;
+        ni = 2;
+        n_bad = 0;
+      }
+      T rho = 0;
+      int qmax = 0;
+      do {
+        const S3<T> backup = est;
+        T Hl[49];
+        for (int k = 0; k < 49; k++) Hl[k] = H[k];
+        for (int j = 0; j < 7; j++) Hl[8 * j] += lambda;
+        const bool ok2 = ldlt7_solve_positive(Hl, b, x);
+        oplus(x);
+        compute_active_errors();
+        tempChi = active_robust_chi2();
+        if (!ok2) tempChi = std::numeric_limits<T>::max();
+        rho = (currentChi - tempChi);
+        T scale = 0;
+        for (int j = 0; j < 7; j++) scale += x[j] * (lambda * x[j] + b[j]);
+        scale += 1e-3;
+        rho /= scale;
+        const bool good = rho > 0 && std::isfinite(tempChi);
+        if (good) {
+          T alpha = T(1.) - std::pow((2 * rho - 1), 3);
+          alpha = (std::min)(alpha, T(2. / 3.));
+          const T scaleFactor = (std::max)(T(1. / 3.), alpha);
+          lambda *= scaleFactor;
+          ni = 2;
+          currentChi = tempChi;
+        } else {
+          lambda *= ni;
+          ni *= 2;
+          est = backup;
+        }
+        qmax++;
+        if (tr) {
+          tr->rejected_trials[phase] += !good;
+          tr->failed_solves[phase] += !ok2;
+          tr->last_trial_rejected[phase] = !good;
+        }
+      } while (rho < 0 && qmax < 10);
+      run++;
+      if (qmax == 10 || rho == 0) {
+        reason = qmax == 10 ? 2 : 3;
+        break;
+      }
+      if ((iniChi - currentChi) * 1e3 < iniChi)
+        n_bad++;
+      else
+        n_bad = 0;
+      if (n_bad >= 3) {
+        reason = 4;
+        break;
+      }
+    }
+    if (tr) {
+      tr->end_reason[phase] = reason;
+      tr->final_lambda[phase] = (double)lambda;
+    }
+    return run;
+  }
+};
+
+template <class T>
+int optimize_sim3(const gfs_sim3_opt_problem* p, gfs_sim3_opt_solution* sol, s3r_trace* tr) {
+  if (tr) memset(tr, 0, sizeof(*tr));
+  Graph<T> G(p);
+  const int n = G.n;
+  for (int k = 0; k < 8; k++) sol->s12[k] = p->s12[k];
+  sol->n_in = 0;
+  sol->status = GFS_SIM3_OPT_EARLY_RETURN;
+  sol->iterations_run[0] = G.optimize(kFirstIterations, 0, tr);
+  sol->iterations_run[1] = 0;
+  int nBad = 0;
+  std::vector<T> fresh;
+  if (tr) {  // what a computeError() in front of the first check would have seen
+    Graph<T> G2 = G;
+    G2.compute_active_errors();
+    for (int e = 0; e < 2 * n; e++) fresh.push_back(G2.chi2(e));
+  }
+  for (int i = 0; i < n; i++) {
+    const T c12 = G.chi2(2 * i), c21 = G.chi2(2 * i + 1);
+    const bool bad = c12 > G.th2 || c21 > G.th2;
+    if (tr) {
+      tr->stale_flag_differences += bad != (fresh[2 * i] > G.th2 || fresh[2 * i + 1] > G.th2);
+      tr->stale_largest_difference = std::max({tr->stale_largest_difference, (double)std::fabs(c12 - fresh[2 * i]), (double)std::fabs(c21 - fresh[2 * i + 1])});
+    }
+    if (sol->chi2) sol->chi2[2 * i] = (double)c12, sol->chi2[2 * i + 1] = (double)c21;
+    sol->pair_state[i] = bad ? GFS_SIM3_PAIR_REMOVED_FIRST : GFS_SIM3_PAIR_INLIER;
+    if (bad) {
+      G.active[2 * i] = G.active[2 * i + 1] = 0;
+      nBad++;
+      continue;
+    }
+    G.robust[2 * i] = G.robust[2 * i + 1] = 0;
+  }
+  sol->n_bad = nBad;
+  const int nMoreIterations = nBad > 0 ? kMoreIterationsAfterRemoval : kMoreIterations;
+  if (n - nBad < kMinCorrespondences) return 0;
+  sol->iterations_run[1] = G.optimize(nMoreIterations, 1, tr);
+  int nIn = 0;
+  for (int i = 0; i < n; i++) {
+    if (!G.active[2 * i]) continue;
+    G.compute_error(2 * i);
+    G.compute_error(2 * i + 1);
+    const T c12 = G.chi2(2 * i), c21 = G.chi2(2 * i + 1);
+    if (sol->chi2) sol->chi2[2 * i] = (double)c12, sol->chi2[2 * i + 1] = (double)c21;
+    if (c12 > G.th2 || c21 > G.th2)
+      sol->pair_state[i] = GFS_SIM3_PAIR_REMOVED_FINAL;
+    else
+      nIn++;
+  }
+  for (int k = 0; k < 4; k++) sol->s12[k] = (double)G.est.q[k];
+  for (int k = 0; k < 3; k++) sol->s12[4 + k] = (double)G.est.t[k];
+  sol->s12[7] = (double)G.est.s;
+  sol->n_in = nIn;
+  sol->status = GFS_SIM3_OPT_BOTH_PHASES;
+  return nIn;
+}
+
+}  // namespace
+
+extern "C" {
+
+int s3r_optimize(const gfs_sim3_opt_problem* p, gfs_sim3_opt_solution* sol, s3r_trace* tr) { return optimize_sim3<double>(p, sol, tr); }
+int s3r_optimize_ld(const gfs_sim3_opt_problem* p, gfs_sim3_opt_solution* sol, s3r_trace* tr) {
+  return optimize_sim3<long double>(p, sol, tr);
+}
+// B problems, as gfs_sim3_optimize takes them (the adaptor test's stand-in for the device call, and the benchmark's host side)
+int s3r_optimize_batch(const gfs_sim3_opt_problem* p, int B, gfs_sim3_opt_solution* sol) {
+  for (int f = 0; f < B; f++) optimize_sim3<double>(p + f, sol + f, nullptr);
+  return 0;
+}
+// One linearisation at the problem's estimate with Huber kernels on (robust != 0) or off: the errors [2 n][2] and Jacobians [2 n][2][7]
+// of the edges in edge order, the full H [7][7], b [7] and activeRobustChi2
+void s3r_linearize(const gfs_sim3_opt_problem* p, int robust, double* err, double* J, double* H, double* b, double* chi) {
+  Graph<double> G(p);
+  for (auto& r : G.robust) r = robust != 0;
+  G.compute_active_errors();
+  *chi = G.active_robust_chi2();
+  G.build_system();
+  for (int e = 0; e < 2 * G.n; e++) {
+    double Je[2][7];
+    G.linearize(e, Je);
+    memcpy(J + 14 * e, Je, sizeof(Je));
+  }
+  memcpy(err, G.err.data(), sizeof(double) * G.err.size());
+  memcpy(H, G.H, sizeof(G.H));
+  memcpy(b, G.b, sizeof(G.b));
+}
+void s3r_constants(double* out /* first, more after a removal, more, minimum correspondences, numeric delta */) {
+  out[0] = kFirstIterations, out[1] = kMoreIterationsAfterRemoval, out[2] = kMoreIterations, out[3] = kMinCorrespondences;
+  out[4] = kNumericDelta;
+}
+
+}  // extern "C"

@@ -1,0 +1,145 @@
+"""gfs_sim3_optimize (geoflowslam_amd/csrc/sim3_opt.hip, Optimizer::OptimizeSim3 of reference src/Optimizer.cc:2797-3054) against the
+sequential float64 restatement (tests/host/sim3_opt_restatement.cpp): byte equality of everything the call returns -- s12, n_in, n_bad,
+status, both iteration counts, pair_state, chi2.  With a free scale too: the device takes the scale's exp through glibc's arithmetic
+restated (glibc_math.hpp, checked here against the host's libm), so the stated bar of four float64 - long double distances is met
+with a distance of zero; the test still asserts the bar itself and the equality of flags and counts first."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import sim3_opt_support as S
+from geoflowslam_amd import api, synth
+
+pytestmark = pytest.mark.gpu
+
+MAX_BATCH, MAX_PAIRS = 12, 640
+
+
+@pytest.fixture(scope="module")
+def opt():
+    o = api.Sim3Optimizer(max_batch=MAX_BATCH, max_pairs=MAX_PAIRS)
+    yield o
+    o.close()
+
+
+@pytest.fixture(scope="module")
+def sized():
+    """(name, problem, float64 restatement) of every size with and without outliers, fixed scale; computed once."""
+    out = []
+    for n in S.SIZES:
+        for outliers in (False, True):
+            p = S.sized_problem(n, outliers)
+            out.append((f"n{n}_{'out' if outliers else 'clean'}", p, S.run(p)))
+    return out
+
+
+def _assert_same(name, got, want):
+    for k in S.RESULT_KEYS:
+        assert np.ascontiguousarray(got[k]).tobytes() == np.ascontiguousarray(want[k]).tobytes(), (name, k, got[k], want[k])
+
+
+def test_restated_exp_on_the_device_equals_the_host_libm():
+    rng = np.random.default_rng(5)
+    x = np.concatenate([[0.0, -0.0, 1e-9, -1e-9, 1.0, -1.0, 709.78, -745.2, 1e300, -1e300, np.inf, -np.inf],
+                        rng.uniform(-1, 1, 20000) * 1e-8, rng.uniform(-1, 1, 20000) * 2.0 ** -rng.integers(0, 64, 20000),
+                        rng.uniform(-750, 750, 20000)])
+    out = np.zeros_like(x)
+    api._check(api.lib().gfs_test_glibc_exp(0, x.ctypes.data, len(x), out.ctypes.data), "gfs_test_glibc_exp")
+    libm = C.CDLL("libm.so.6")
+    libm.exp.restype, libm.exp.argtypes = C.c_double, [C.c_double]
+    want = np.array([libm.exp(float(v)) for v in x])
+    assert out.tobytes() == want.tobytes()
+
+
+def test_every_size_alone_equals_the_restatement(opt, sized):
+    for name, p, want in sized:
+        _assert_same(name, opt.OptimizeSim3(p), want)
+    assert {w["status"] for _, _, w in sized} == {0, 1} and any(w["n_bad"] > 0 for _, _, w in sized)
+
+
+def test_constructed_cases_equal_the_restatement(opt):
+    cases = {k: p for k, p in S.constructed_cases().items() if isinstance(p, dict)}
+    got = opt.OptimizeSim3(list(cases.values())[:MAX_BATCH]) + opt.OptimizeSim3(list(cases.values())[MAX_BATCH:])
+    assert len(got) == len(cases)
+    for (name, p), g in zip(cases.items(), got):
+        _assert_same(name, g, S.run(p))
+
+
+def test_same_bytes_alone_and_inside_batches_of_mixed_sizes(opt, sized):
+    by_name = {name: (p, want) for name, p, want in sized}
+    probe, want = by_name["n65_out"]
+    alone = opt.OptimizeSim3(probe)
+    _assert_same("alone", alone, want)
+    others = [by_name[k][0] for k in ("n600_out", "n0_clean", "n9_out", "n257_clean", "n1_clean", "n64_out", "n11_out", "n255_clean",
+                                      "n10_clean", "n256_out", "n63_clean")]
+    for B in (2, 7, MAX_BATCH):
+        for slot in (0, B - 1):
+            batch = others[:B - 1]
+            batch.insert(slot, probe)
+            res = opt.OptimizeSim3(batch)
+            assert S.result_bytes(res[slot]) == S.result_bytes(alone), (B, slot)
+            for p, r in zip(batch, res):  # and every neighbour is its own restatement
+                if p is not probe:
+                    _assert_same((B, slot), r, S.run(p))
+
+
+def test_refusals_leave_the_handle_usable(opt, sized):
+    probe, want = next((p, w) for name, p, w in sized if name == "n64_out")
+    before = S.result_bytes(opt.OptimizeSim3(probe))
+    assert before == S.result_bytes(want)
+
+    def refused(code, problems):
+        with pytest.raises(api.GfsError) as e:
+            opt.OptimizeSim3(problems)
+        assert e.value.code == code
+        assert S.result_bytes(opt.OptimizeSim3(probe)) == before, "the call after a refusal"
+
+    refused(-4, [probe] * (MAX_BATCH + 1))                                       # GFS_ERR_CAPACITY: batch
+    refused(-4, [probe, S.sized_problem(MAX_PAIRS + 1, False)])                  # pairs
+    refused(-1, dict(probe, n_pairs=-1))                                         # GFS_ERR_INVALID_ARG
+    for th2 in (0.0, -1.0, float("nan"), float("inf")):
+        refused(-1, [probe, dict(probe, th2=th2)])
+    # a NULL required array, straight through the C ABI (the second problem of a batch: nothing of the first may be staged)
+    for field in ("x1c", "x2c", "obs1", "obs2", "inv_sigma2_1", "inv_sigma2_2"):
+        PP, SS = (api.Sim3OptProblem * 2)(), (api.Sim3OptSolution * 2)()
+        keeps = [api.sim3_opt_structs(probe) for _ in range(2)]
+        for f, (P, Sl, _, _) in enumerate(keeps):
+            PP[f], SS[f] = P, Sl
+        setattr(PP[1], field, None)
+        assert api.lib().gfs_sim3_optimize(opt.h, PP, 2, SS) == -1
+        assert S.result_bytes(opt.OptimizeSim3(probe)) == before
+    PP, SS = (api.Sim3OptProblem * 1)(), (api.Sim3OptSolution * 1)()
+    P, Sl, keep, _ = api.sim3_opt_structs(probe)
+    PP[0], SS[0] = P, Sl
+    SS[0].pair_state = None
+    assert api.lib().gfs_sim3_optimize(opt.h, PP, 1, SS) == -1
+    assert api.lib().gfs_sim3_optimize(opt.h, None, 1, SS) == -1 and api.lib().gfs_sim3_optimize(opt.h, PP, 0, SS) == -1
+    assert S.result_bytes(opt.OptimizeSim3(probe)) == before
+    # chi2 is optional
+    SS[0].pair_state, SS[0].chi2 = keep["pair_state"].ctypes.data, None
+    assert api.lib().gfs_sim3_optimize(opt.h, PP, 1, SS) == 0 and keep["pair_state"][:64].tobytes() == want["pair_state"].tobytes()
+
+
+def test_free_scale(opt):
+    """Flags and counts equal; s12 within 4 x the case's float64 - long double distance of the float64 restatement (measured: 0, the
+    bytes are equal, because the scale's exp is glibc's on the device too)."""
+    cases = S.free_scale_cases()
+    got = opt.OptimizeSim3([p for _, p, _, _ in cases])
+    for (name, p, want, dist), g in zip(cases, got):
+        d = S.s12_distance(g, want)
+        print(f"{name}: device - float64 = {d:.3e}, float64 - long double = {dist:.3e}, ratio {d / dist:.3f}")
+        assert S.same_flags(g, want), name
+        assert d <= 4 * dist, (name, d, dist)
+        _assert_same(name, g, want)
+
+
+@pytest.mark.parametrize("n_good,all_points", [(20, True), (8, False)])
+def test_adaptor_end_to_end_equals_its_cpu_run(n_good, all_points):
+    """gfs_host::OptimizeSim3 on mock key frames with the device as its solve against the same adaptor with the restatement: the
+    return value, vpMatches1, g2oS12, mAcumHessian and the counters (both phases, and the early return)."""
+    scene = S.adaptor_scene(11, n_good=n_good, n_gross=4)
+    cpu, dev = S.run_adaptor(scene, all_points), S.run_adaptor(scene, all_points, use_device=True)
+    assert cpu["status_n"][1] == (1 if n_good == 20 else 0) and dev["ret"] == cpu["ret"]
+    for k in ("matched", "s12", "hessian", "counters", "status_n", "flat_n", "x1c", "x2c", "obs1", "obs2", "w1", "w2"):
+        assert dev[k].tobytes() == cpu[k].tobytes(), k
