@@ -570,6 +570,66 @@ def tri_candidate_pairs(prob):
     return total
 
 
+class BowKeyframe(C.Structure):  # gfs_bow_keyframe
+    _fields_ = [("n_kp", C.c_int32), ("angle", C.c_void_p), ("desc", C.c_void_p), ("has_mp", C.c_void_p), ("n_nodes", C.c_int32),
+                ("node_id", C.c_void_p), ("node_start", C.c_void_p), ("feat_idx", C.c_void_p)]
+
+
+class BowProblem(C.Structure):  # gfs_bow_problem
+    _fields_ = [("kf1", BowKeyframe), ("kf2", C.POINTER(BowKeyframe)), ("n_kf2", C.c_int32), ("nn_ratio", C.c_float),
+                ("check_orientation", C.c_int32)]
+
+
+class BowResult(C.Structure):  # gfs_bow_result
+    _fields_ = [("match12", C.c_void_p), ("n_matches", C.c_int32)]
+
+
+def _bow_keyframe(K, kf, keep):
+    a = dict(angle=np.ascontiguousarray(kf["angle"], np.float32), desc=np.ascontiguousarray(kf["desc"], np.uint8).reshape(-1, 32),
+             has_mp=np.ascontiguousarray(kf["has_mp"], np.uint8), node_id=np.ascontiguousarray(kf["node_id"], np.int32),
+             node_start=np.ascontiguousarray(kf["node_start"], np.int32), feat_idx=np.ascontiguousarray(kf["feat_idx"], np.int32))
+    for name, v in a.items():
+        setattr(K, name, v.ctypes.data)
+    K.n_kp = len(a["angle"])
+    K.n_nodes = len(a["node_id"])
+    keep.append(a)
+
+
+def bow_structs(problems):
+    """ctypes views of one gfs_search_by_bow call (shared with the CPU restatement's tests: same layout).  problems: dicts with `kf1`
+    (keys of gfs_bow_keyframe), `kf2` (a list of such dicts), nn_ratio and check_orientation -> (problems array, array of result
+    pointers, arrays kept alive).  The result arrays are pre-filled with a pattern no output has."""
+    B = len(problems)
+    PP, RP = (BowProblem * max(B, 1))(), (C.POINTER(BowResult) * max(B, 1))()
+    keep = []
+    for b, prob in enumerate(problems):
+        P, k2s = PP[b], list(prob["kf2"])
+        _bow_keyframe(P.kf1, prob["kf1"], keep)
+        KK, RR = (BowKeyframe * max(len(k2s), 1))(), (BowResult * max(len(k2s), 1))()
+        n, outs = max(P.kf1.n_kp, 1), []
+        for i, k2 in enumerate(k2s):
+            _bow_keyframe(KK[i], k2, keep)
+            out = np.full(n, -9, np.int32)
+            RR[i].match12, RR[i].n_matches = out.ctypes.data, -9
+            outs.append(out)
+        P.kf2, P.n_kf2 = KK, len(k2s)
+        P.nn_ratio = float(np.float32(prob["nn_ratio"]))
+        P.check_orientation = int(bool(prob.get("check_orientation", True)))
+        RP[b] = RR
+        keep.append((KK, RR, outs))
+    return PP, RP, keep
+
+
+def bow_results(PP, RP, keep, B):
+    """-> per problem a list with one dict per key frame 2: match12 [kf1.n_kp] (idx2 or -1), n_matches."""
+    res, blocks = [], [k for k in keep if isinstance(k, tuple)]
+    for b in range(B):
+        KK, RR, outs = blocks[b]
+        n = PP[b].kf1.n_kp
+        res.append([dict(match12=o[:n].copy(), n_matches=int(RR[i].n_matches)) for i, o in enumerate(outs)])
+    return res
+
+
 def sbp_map_struct(prob):
     P = SbpMapProblem()
     keep = dict(mp_proj=np.ascontiguousarray(prob["mp_proj"], np.float32).reshape(-1, 3),
@@ -735,7 +795,7 @@ ABI_SYMBOLS = [
     "gfs_sbp_create", "gfs_sbp_destroy", "gfs_search_by_projection", "gfs_search_by_projection_map",
     "gfs_sbp_reserve_local", "gfs_search_local_points", "gfs_sbp_reserve_fuse", "gfs_fuse_search", "gfs_test_glibc_logf",
     "gfs_sbp_reserve_sim3_search", "gfs_sim3_search", "gfs_test_sim3_search_groups",
-    "gfs_sbp_reserve_triangulation", "gfs_create_new_map_points",
+    "gfs_sbp_reserve_triangulation", "gfs_create_new_map_points", "gfs_sbp_reserve_bow", "gfs_search_by_bow",
     "gfs_map_points_create", "gfs_map_points_destroy", "gfs_map_points_update",
     "gfs_klt_create", "gfs_klt_destroy", "gfs_klt_layout", "gfs_klt_pyramid_create", "gfs_klt_pyramid_destroy",
     "gfs_klt_build_pyramid", "gfs_klt_build_pyramid_device", "gfs_klt_pyramid_download", "gfs_klt_track", "gfs_klt_fb_track",
@@ -785,6 +845,8 @@ def lib():
         L.gfs_test_sim3_search_groups.argtypes = [vp, i]
         L.gfs_sbp_reserve_triangulation.argtypes = [vp, i, C.c_int64]
         L.gfs_create_new_map_points.argtypes = [vp, C.POINTER(TriProblem), i, C.POINTER(C.POINTER(TriResult))]
+        L.gfs_sbp_reserve_bow.argtypes = [vp, i, i]
+        L.gfs_search_by_bow.argtypes = [vp, C.POINTER(BowProblem), i, C.POINTER(C.POINTER(BowResult))]
         L.gfs_map_points_create.argtypes = [i, i, i, C.POINTER(vp)]
         L.gfs_map_points_destroy.argtypes = [vp]
         L.gfs_map_points_update.argtypes = [vp, C.POINTER(MapPointsProblem), C.POINTER(MapPointsResult)]
@@ -2075,6 +2137,26 @@ class ProjectionMatcher:
         PP, RP, keep = tri_structs(probs)
         _check(lib().gfs_create_new_map_points(self.h, PP, len(probs), RP), "gfs_create_new_map_points")
         res = tri_results(PP, RP, keep, len(probs))
+        return res[0] if single else res
+
+    def reserve_bow(self, max_problems, max_kf2_per_call):
+        """Workspace of search_by_bow: up to max_problems key frames 1 and up to max_kf2_per_call key frames 2 (over all problems)
+        per call."""
+        _check(lib().gfs_sbp_reserve_bow(self.h, int(max_problems), int(max_kf2_per_call)), "gfs_sbp_reserve_bow")
+        self.bow_reserve = (int(max_problems), int(max_kf2_per_call))
+
+    def search_by_bow(self, problems):
+        """ORBmatcher::SearchByBoW(pKF1, pKF2, vpMatches12) (src/ORBmatcher.cc:936-1053) for one problem dict or a list of them
+        (bow_structs), every (key frame 1, key frame 2) pair in one device call: per problem a list with one dict per key frame 2:
+        match12 (idx2 or -1, after the orientation check) and n_matches.  Raises GfsError (code GFS_ERR_CAPACITY beyond the
+        reserve, GFS_ERR_INVALID_ARG for what the entry refuses)."""
+        single = isinstance(problems, dict)
+        probs = [problems] if single else list(problems)
+        if not hasattr(self, "bow_reserve"):
+            self.reserve_bow(max(len(probs), 1), max(sum(len(p["kf2"]) for p in probs), 1))
+        PP, RP, keep = bow_structs(probs)
+        _check(lib().gfs_search_by_bow(self.h, PP, len(probs), RP), "gfs_search_by_bow")
+        res = bow_results(PP, RP, keep, len(probs))
         return res[0] if single else res
 
 

@@ -120,6 +120,24 @@ struct TriOutLayout {
   Field<float, 3> x3d{out, n};
 };
 
+// gfs_search_by_bow (bow_search.hip): the arrays of one key frame, as TriKfArrays; then the headers of the input block, the key
+// frames' arrays behind them on the same cursor; the results are one int per (slot, key-point of key frame 1)
+struct BowKfArrays {
+  Block<256>& in;
+  size_t n, m, nf;
+  Field<float> ang{in, n};
+  Field<uint8_t> hasmp{in, n};
+  Field<uint8_t, 32> desc{in, n};
+  Field<int> nid{in, m}, nstart{in, m + 1}, feat{in, nf};
+};
+template <class Slot, class Frame>
+struct BowHeadLayout {
+  size_t n_slots, n_frames;
+  Block<256> in;
+  Field<Slot> slots{in, n_slots};
+  Field<Frame> frames{in, n_frames};
+};
+
 // gfs_map_points_update (map_points.hip): P points, O observations; blocks aligned to 64
 struct MpLayout {
   size_t P, O;

@@ -21,7 +21,7 @@ struct gfs_sbp {
   gfs::Mirror in, res;
   gfs::DevBuf<int> d_cand_cnt, d_lsel;
   gfs::DevBuf<unsigned> d_cand;
-  std::unique_ptr<gfs_sbp_workspace> local, fuse, tri, sim3;  // local_points.hip, fuse.hip, triangulate.hip, sim3_search.hip
+  std::unique_ptr<gfs_sbp_workspace> local, fuse, tri, sim3, bow;  // local_points.hip, fuse.hip, triangulate.hip, sim3_search.hip, bow_search.hip
 };
 
 namespace gfs {

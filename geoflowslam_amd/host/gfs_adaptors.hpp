@@ -3019,6 +3019,174 @@ class Sim3Optimizer {
   gfs_sim3_opt* h_ = nullptr;
 };
 
+// ------------------------------------------------------------------------------------------------------------------------
+// int ORBmatcher::SearchByBoW(KeyFrame* pKF1, KeyFrame* pKF2, vector<MapPoint*>& vpMatches12)  reference src/ORBmatcher.cc:936-1053
+// for ONE key frame 1 against a list of key frames 2 in one device call, as LoopClosing::DetectCommonRegionsFromBoW needs it
+// (src/LoopClosing.cc:706-715), and the merge of the per-key-frame lists behind it (:717-730)  (DESIGN.md section 22).
+//   gather:  per key frame mvKeysUn's angles, mDescriptors, GetMapPointMatches() folded into has_mp (pMP && !pMP->isBad()), mFeatVec
+//            flattened.  A null or bad key frame 2 is not uploaded.
+//   solve:   `solve(problems, 1, results)`: BowSearcher::solve below (gfs_search_by_bow on the GPU).
+//   scatter: vvpMatches12[j][idx1] = GetMapPointMatches()[idx2] of key frame 2 j, vnMatches[j] = SearchByBoW's return value; for a key
+//            frame 2 that was skipped the list stays EMPTY and the count 0, as :707 leaves vvpMatchedMPs[j].
+// What other threads change in the map during the call is not seen: the map points are read once, at the gather.
+// Single-camera key frames only: NLeft != -1 throws.  `Access` as for Fuse: keys_un, descriptors, for_each_node.  KeyFrame: NLeft, N,
+// isBad(), GetMapPointMatches(); MapPoint: isBad().
+// ------------------------------------------------------------------------------------------------------------------------
+struct BowKeyFrameFlat {  // one gathered key frame
+  std::vector<float> angle;
+  std::vector<uint8_t> has_mp;
+  std::vector<int32_t> node_id, node_start, feat_idx;
+  gfs_bow_keyframe k{};
+};
+
+template <class Access, class KeyFrame, class MapPoint>
+void bow_gather(KeyFrame* pKF, const std::vector<MapPoint*>& vpMapPoints, BowKeyFrameFlat& F) {
+  const KeyFrame& KF = *pKF;
+  if (KF.NLeft != -1) throw std::invalid_argument("SearchByBoW: single-camera key frames only");
+  const size_t N = vpMapPoints.size();
+  const gfs_keypoint* kps = Access::keys_un(KF);
+  F.angle.assign(N + 1, 0.0f);
+  F.has_mp.assign(N + 1, 0);
+  for (size_t i = 0; i < N; i++) {
+    F.angle[i] = kps[i].angle;
+    MapPoint* pMP = vpMapPoints[i];
+    F.has_mp[i] = pMP && !pMP->isBad();
+  }
+  F.node_id.clear();
+  F.feat_idx.clear();
+  F.node_start.assign(1, 0);
+  Access::for_each_node(KF, [&](unsigned id, const std::vector<unsigned>& idx) {
+    F.node_id.push_back((int32_t)id);
+    for (unsigned i : idx) F.feat_idx.push_back((int32_t)i);
+    F.node_start.push_back((int32_t)F.feat_idx.size());
+  });
+  F.node_id.push_back(0);  // (never NULL)
+  F.feat_idx.push_back(0);
+  gfs_bow_keyframe& k = F.k;
+  k.n_kp = (int32_t)N;
+  k.angle = F.angle.data();
+  k.desc = Access::descriptors(KF);
+  k.has_mp = F.has_mp.data();
+  k.n_nodes = (int32_t)F.node_start.size() - 1;
+  k.node_id = F.node_id.data();
+  k.node_start = F.node_start.data();
+  k.feat_idx = F.feat_idx.data();
+}
+
+template <class Access, class KeyFrame, class MapPoint, class Solve>
+void SearchByBoW(Solve&& solve, KeyFrame* pKF1, const std::vector<KeyFrame*>& vpKF2, const float nnratio, const bool checkOri,
+                 std::vector<std::vector<MapPoint*>>& vvpMatches12, std::vector<int>& vnMatches) {
+  const std::vector<MapPoint*> vpMapPoints1 = pKF1->GetMapPointMatches();
+  const size_t N = vpMapPoints1.size();
+  vvpMatches12.assign(vpKF2.size(), std::vector<MapPoint*>());
+  vnMatches.assign(vpKF2.size(), 0);
+  BowKeyFrameFlat F1;
+  bow_gather<Access>(pKF1, vpMapPoints1, F1);
+  std::vector<size_t> used;  // the entries of vpKF2 that are searched
+  for (size_t j = 0; j < vpKF2.size(); j++)
+    if (vpKF2[j] && !vpKF2[j]->isBad()) used.push_back(j);
+  if (used.empty()) return;
+  std::vector<BowKeyFrameFlat> F2(used.size());
+  std::vector<std::vector<MapPoint*>> vpMapPoints2(used.size());
+  std::vector<gfs_bow_keyframe> k2(used.size());
+  std::vector<std::vector<int32_t>> match12(used.size());
+  std::vector<gfs_bow_result> res(used.size());
+  for (size_t u = 0; u < used.size(); u++) {
+    vpMapPoints2[u] = vpKF2[used[u]]->GetMapPointMatches();
+    bow_gather<Access>(vpKF2[used[u]], vpMapPoints2[u], F2[u]);
+    k2[u] = F2[u].k;
+    match12[u].assign(N + 1, -1);
+    res[u].match12 = match12[u].data();
+    res[u].n_matches = 0;
+  }
+  gfs_bow_problem p{};
+  p.kf1 = F1.k;
+  p.kf2 = k2.data();
+  p.n_kf2 = (int32_t)used.size();
+  p.nn_ratio = nnratio;
+  p.check_orientation = checkOri ? 1 : 0;
+  gfs_bow_result* rp = res.data();
+  check(solve(&p, 1, &rp), "SearchByBoW");
+  for (size_t u = 0; u < used.size(); u++) {
+    std::vector<MapPoint*>& vpMatches12 = vvpMatches12[used[u]];
+    vpMatches12.assign(N, static_cast<MapPoint*>(NULL));
+    for (size_t i = 0; i < N; i++)
+      if (match12[u][i] >= 0) vpMatches12[i] = vpMapPoints2[u][match12[u][i]];
+    vnMatches[used[u]] = res[u].n_matches;
+  }
+}
+
+// src/LoopClosing.cc:692-730 for one candidate: SearchByBoW against every covisible of the candidate (a null or bad one is skipped and
+// its list stays empty), then the merge: in the order of vpCovKFi, a point that an earlier key frame already gave is not taken again.
+// nIndexMostBoWMatchesKF is computed as the reference computes it; the reference never reads it (the line that would assign
+// pMostBoWMatchesKF from it, :732, is commented out), so pMostBoWMatchesKF stays the candidate itself at the caller.
+template <class KeyFrame, class MapPoint>
+struct BowCandidateMatches {
+  std::vector<MapPoint*> vpMatchedPoints;
+  std::vector<KeyFrame*> vpKeyFrameMatchedMP;
+  std::vector<std::vector<MapPoint*>> vvpMatchedMPs;
+  int numBoWMatches = 0, nIndexMostBoWMatchesKF = 0, nMostBoWNumMatches = 0;
+};
+
+template <class Access, class MapPoint, class KeyFrame, class Solve>
+BowCandidateMatches<KeyFrame, MapPoint> BowMatchesOfCandidate(Solve&& solve, KeyFrame* pCurrentKF, const std::vector<KeyFrame*>& vpCovKFi,
+                                                              const float nnratio = 0.9f, const bool checkOri = true) {
+  BowCandidateMatches<KeyFrame, MapPoint> out;
+  std::vector<int> vnMatches;
+  SearchByBoW<Access>(solve, pCurrentKF, vpCovKFi, nnratio, checkOri, out.vvpMatchedMPs, vnMatches);
+  for (size_t j = 0; j < vpCovKFi.size(); ++j) {
+    if (!vpCovKFi[j] || vpCovKFi[j]->isBad()) continue;
+    if (vnMatches[j] > out.nMostBoWNumMatches) {
+      out.nMostBoWNumMatches = vnMatches[j];
+      out.nIndexMostBoWMatchesKF = (int)j;
+    }
+  }
+  const size_t N = pCurrentKF->GetMapPointMatches().size();
+  out.vpMatchedPoints.assign(N, static_cast<MapPoint*>(NULL));
+  out.vpKeyFrameMatchedMP.assign(N, static_cast<KeyFrame*>(NULL));
+  std::set<MapPoint*> spMatchedMPi;
+  for (size_t j = 0; j < vpCovKFi.size(); ++j) {
+    for (size_t k = 0; k < out.vvpMatchedMPs[j].size(); ++k) {
+      MapPoint* pMPi_j = out.vvpMatchedMPs[j][k];
+      if (!pMPi_j || pMPi_j->isBad()) continue;
+      if (spMatchedMPi.find(pMPi_j) == spMatchedMPi.end()) {
+        spMatchedMPi.insert(pMPi_j);
+        out.numBoWMatches++;
+        out.vpMatchedPoints[k] = pMPi_j;
+        out.vpKeyFrameMatchedMP[k] = vpCovKFi[j];
+      }
+    }
+  }
+  return out;
+}
+
+// the numeric core of SearchByBoW on the GPU: one handle, its reserve grown to the largest call seen
+class BowSearcher {
+ public:
+  BowSearcher(int max_kp = 4096, int device = 0) { check(gfs_sbp_create(device, 64, max_kp, 1, &h_), "gfs_sbp_create"); }
+  ~BowSearcher() { gfs_sbp_destroy(h_); }
+  BowSearcher(const BowSearcher&) = delete;
+  BowSearcher& operator=(const BowSearcher&) = delete;
+  int solve(const gfs_bow_problem* problems, int B, gfs_bow_result* const* results) {
+    int n2 = 1;
+    for (int b = 0, sum = 0; b < B; b++) n2 = std::max(n2, sum += problems[b].n_kf2);
+    if (B > problems_ || n2 > kf2_) {  // the library refuses what exceeds the reserve (it never truncates): grow it first
+      const int p = std::max(std::max(B, 1), problems_), k = std::max(n2, kf2_);
+      check(gfs_sbp_reserve_bow(h_, p, k), "gfs_sbp_reserve_bow");
+      problems_ = p;
+      kf2_ = k;
+    }
+    return gfs_search_by_bow(h_, problems, B, results);
+  }
+  auto solver() {
+    return [this](const gfs_bow_problem* p, int B, gfs_bow_result* const* r) { return solve(p, B, r); };
+  }
+
+ private:
+  gfs_sbp* h_ = nullptr;
+  int problems_ = 0, kf2_ = 0;
+};
+
 }  // namespace gfs_host
 
 // The drop-ins written against the reference's own types (cv::Mat, cv::KeyPoint, Eigen, Sophus, ORB_SLAM3::ORBextractor as a base

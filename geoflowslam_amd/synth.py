@@ -1098,7 +1098,90 @@ def triangulation_problem(seed, n_kp=1000, n_neighbours=10, n_nodes=100, n_kp_ne
                 far_points=far_points, th_far_points=f32(th_far_points), ratio_factor=f32(f32(1.5) * f32(scale_factor)))
 
 
-def map_point_update_problem(seed, n_points=1000, obs_counts=(1, 20), n_keyframes=40, flip_bits=40, scale_factor=1.2, n_levels=8):
+def _flip_bits(rng, desc, n_bits):
+    """Copies of the 32-byte descriptors with n_bits[i] distinct random bits of row i flipped."""
+    bits = np.unpackbits(np.asarray(desc, np.uint8).reshape(-1, 32), axis=1)
+    order = np.argsort(rng.random(bits.shape), axis=1)
+    flip = np.zeros(bits.shape, bool)
+    np.put_along_axis(flip, order, np.arange(256)[None, :] < np.asarray(n_bits)[:, None], axis=1)
+    return np.packbits(bits ^ flip, axis=1)
+
+
+def _bow_lists(rng, node_of, shuffle_lists):
+    """A feature vector from the node id of every key-point: (node_id ascending, node_start, feat_idx)."""
+    ids = np.unique(node_of)
+    lists = []
+    for v in ids:
+        l = np.nonzero(node_of == v)[0]
+        lists.append(rng.permutation(l) if shuffle_lists else l)
+    start = np.concatenate([[0], np.cumsum([len(l) for l in lists])]).astype(np.int32)
+    feat = np.concatenate(lists).astype(np.int32) if lists else np.zeros(0, np.int32)
+    return ids.astype(np.int32), start, feat
+
+
+def bow_search_problem(seed, n_kp=1000, n_kf2=1, n_nodes=100, n_kp2=None, no_mp_frac=0.15, dup_frac=0.08, shuffle_lists=True,
+                       one_sided_frac=0.1, max_flip_bits=70, wrong_node_frac=0.1, angle_outlier_frac=0.2, nn_ratio=0.9,
+                       check_orientation=True):
+    """Synthetic input of ORBmatcher::SearchByBoW(pKF1, pKF2, ...) (reference src/ORBmatcher.cc:936-1053) for one key frame 1 and
+    n_kf2 key frames 2, as gfs_search_by_bow takes it (include/gfs_abi.h): dict(kf1, kf2 = [...], nn_ratio, check_orientation), a
+    key frame being dict(angle, desc, has_mp, node_id, node_start, feat_idx).  The descriptors of a key frame 2 are copies of key
+    frame 1's with 0..max_flip_bits bits flipped, so that the best distances land on both sides of TH_LOW and of the ratio.
+      no_mp_frac      the share of key-points without a (good) map point, in every key frame
+      dup_frac        the share of key-points whose descriptor is a copy of another one's of the same node (within a few bits in key
+                      frame 1: two idx1 want one idx2; exact in key frame 2: equal best and second-best distances)
+      shuffle_lists   the per-node lists in random order instead of ascending index order
+      one_sided_frac  the share of a key frame's nodes whose id the other key frame does not have
+      wrong_node_frac the share of key-points of a key frame 2 filed under another node than their source's
+      angle_outlier_frac  the share of key-points of a key frame 2 whose angle is unrelated to their source's"""
+    rng = np.random.default_rng(seed)
+    n2 = n_kp if n_kp2 is None else n_kp2
+    f32 = np.float32
+    ids = np.sort(rng.choice(max(4 * n_nodes, 8), n_nodes, replace=False)).astype(np.int32) * 2  # even ids; private nodes get odd ones
+
+    def duplicate(desc, node_of, flips):
+        """dup_frac of the rows become copies of another row of their node with 0..flips bits flipped"""
+        n = len(desc)
+        for i in np.nonzero(rng.random(n) < dup_frac)[0]:
+            same = np.nonzero(node_of == node_of[i])[0]
+            src = int(same[rng.integers(len(same))])
+            if src != i:
+                desc[i] = _flip_bits(rng, desc[src:src + 1], [int(rng.integers(flips + 1))])[0]
+        return desc
+
+    def one_sided(node_of):
+        """moves the key-points of one_sided_frac of the nodes to ids nobody else has"""
+        for v in np.unique(node_of):
+            if rng.random() < one_sided_frac:
+                node_of[node_of == v] = v + 1
+        return node_of
+
+    node1 = ids[rng.integers(n_nodes, size=n_kp)] if n_kp else np.zeros(0, np.int32)
+    desc1 = duplicate(rng.integers(0, 256, (n_kp, 32)).astype(np.uint8), node1, 3)
+    ang1 = (rng.random(n_kp) * 360).astype(f32)
+    nid, ns, fi = _bow_lists(rng, one_sided(node1.copy()), shuffle_lists)
+    kf1 = dict(angle=ang1, desc=desc1, has_mp=(rng.random(n_kp) >= no_mp_frac).astype(np.uint8), node_id=nid, node_start=ns, feat_idx=fi)
+    kf2 = []
+    for _ in range(n_kf2):
+        if n_kp == 0 or n2 == 0:
+            src = np.zeros(n2, np.int64)
+            desc2, node2, ang2 = rng.integers(0, 256, (n2, 32)).astype(np.uint8), ids[rng.integers(n_nodes, size=n2)], (rng.random(n2) * 360).astype(f32)
+        else:
+            src = rng.permutation(np.arange(n2) % n_kp)
+            desc2 = _flip_bits(rng, desc1[src], rng.integers(0, max_flip_bits + 1, n2))
+            node2 = node1[src].copy()
+            wrong = rng.random(n2) < wrong_node_frac
+            node2[wrong] = ids[rng.integers(n_nodes, size=int(wrong.sum()))]
+            desc2 = duplicate(desc2, node2, 0)
+            turn = f32(rng.random() * 360)
+            ang2 = ((ang1[src] - turn + rng.normal(0, 4, n2)) % 360).astype(f32)
+            out = rng.random(n2) < angle_outlier_frac
+            ang2[out] = (rng.random(int(out.sum())) * 360).astype(f32)
+        nid, ns, fi = _bow_lists(rng, one_sided(node2.copy()), shuffle_lists)
+        kf2.append(dict(angle=ang2, desc=desc2, has_mp=(rng.random(n2) >= no_mp_frac).astype(np.uint8), node_id=nid, node_start=ns, feat_idx=fi))
+    return dict(kf1=kf1, kf2=kf2, nn_ratio=f32(nn_ratio), check_orientation=bool(check_orientation))
+
+
+def map_point_update_problem(seed, n_points=1000,obs_counts=(1, 20), n_keyframes=40, flip_bits=40, scale_factor=1.2, n_levels=8):
     """Synthetic input of MapPoint::ComputeDistinctiveDescriptors and MapPoint::UpdateNormalAndDepth (reference src/MapPoint.cc:376-448,
     :468-532) for `n_points` map points, as gfs_map_points_update takes it (include/gfs_abi.h): a dict with the keys of
     gfs_map_points_problem.  obs_counts: the observations per point, an int, an inclusive (lo, hi) range or one count per point.

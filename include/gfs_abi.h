@@ -767,6 +767,46 @@ int gfs_sbp_reserve_triangulation(gfs_sbp* h, int max_neighbours, int64_t max_ca
 int gfs_create_new_map_points(gfs_sbp* h, const gfs_tri_problem* problems, int B, gfs_tri_result* const* results);
 
 /* ============================================================================================
+ * 7a'. Loop detection's BoW-guided matching —
+ *      int ORBmatcher::SearchByBoW(KeyFrame* pKF1, KeyFrame* pKF2, vector<MapPoint*>& vpMatches12)   src/ORBmatcher.cc:936-1053
+ *    as LoopClosing::DetectCommonRegionsFromBoW calls it for every covisible of every candidate (src/LoopClosing.cc:706-715), for
+ *    single-camera key frames (NLeft == -1).  One problem is one key frame 1 and any number of key frames 2; every (key frame 1,
+ *    key frame 2) pair is independent.  Integer throughout but the ratio test; DESIGN.md section 22 states the rule. */
+typedef struct {
+  int32_t n_kp;                  /* N, <= the handle's max_cur */
+  const float* angle;            /* [n_kp] mvKeysUn[i].angle */
+  const uint8_t* desc;           /* [n_kp][32] mDescriptors */
+  const uint8_t* has_mp;         /* [n_kp] GetMapPointMatches()[i] != nullptr && !isBad() */
+  int32_t n_nodes;               /* mFeatVec, flattened as in gfs_tri_keyframe: */
+  const int32_t* node_id;        /* [n_nodes] strictly ascending */
+  const int32_t* node_start;     /* [n_nodes + 1] non-decreasing from 0 */
+  const int32_t* feat_idx;       /* [node_start[n_nodes]] key-point indices in [0, n_kp), none twice */
+} gfs_bow_keyframe;
+
+typedef struct {
+  gfs_bow_keyframe kf1;          /* pKF1 (mpCurrentKF), uploaded once */
+  const gfs_bow_keyframe* kf2;   /* [n_kf2] pKF2 (vpCovKFi[j]) */
+  int32_t n_kf2;
+  float nn_ratio;                /* mfNNratio */
+  int32_t check_orientation;     /* mbCheckOrientation */
+} gfs_bow_problem;
+
+typedef struct {                 /* one per key frame 2 */
+  int32_t* match12;              /* [kf1.n_kp] caller-owned: idx2 or -1, after the orientation check */
+  int32_t n_matches;             /* SearchByBoW's return value */
+} gfs_bow_result;
+
+/* Allocates the workspace of gfs_search_by_bow: up to max_problems key frames 1 and up to max_kf2_per_call key frames 2 (summed
+ * over the problems) per call, each of up to the handle's max_cur key-points (handles that never call it are unchanged). */
+int gfs_sbp_reserve_bow(gfs_sbp* h, int max_problems, int max_kf2_per_call);
+/* B independent problems in one call (host pointers); results[b] points to problems[b].n_kf2 results.  GFS_ERR_CAPACITY: more
+ * problems or more key frames 2 than reserved, or a handle that never reserved.  GFS_ERR_INVALID_ARG: a NULL array, node ids not
+ * ascending, node_start not a prefix sum, a feature index outside [0, n_kp) or listed twice, n_kp or n_nodes above the handle's
+ * max_cur.  Every refusal comes before anything is staged or written; nothing is truncated; the handle stays usable.  B == 0,
+ * n_kf2 == 0 and n_nodes == 0 are valid.  One upload, one kernel (k_bow_search), one download, one synchronisation. */
+int gfs_search_by_bow(gfs_sbp* h, const gfs_bow_problem* problems, int B, gfs_bow_result* const* results);
+
+/* ============================================================================================
  * 7b. Map-point update — the numeric cores of
  *      void MapPoint::ComputeDistinctiveDescriptors()                            src/MapPoint.cc:376-448
  *      void MapPoint::UpdateNormalAndDepth()                                     src/MapPoint.cc:468-532
