@@ -35,6 +35,27 @@ class OrbConfig(C.Structure):
                 ("blur_taps_variant", C.c_int32)]
 
 
+def _i32_fields(names):
+    return [(n, C.c_int32) for n in names.split()]
+
+
+class OrbGeometryInfo(C.Structure):  # gfs_test_orb_geometry_info (include/gfs_abi_test.h)
+    _fields_ = _i32_fields("supported pyr_strips pyr_strips_fine pyr_in_lds xtab_in_lds xtab_in_lds_fine kp_cap octree_on_device "
+                           "oct_node_cap n_cells n_blur_tiles fast_lds_wave")
+
+
+class OrbLevelInfo(C.Structure):  # gfs_test_orb_level_info
+    _fields_ = _i32_fields("rows cols n_cell_cols n_cell_rows w_cell h_cell n_cells max_cell_w max_cell_h quota n_ini kp_cap "
+                           "octree_on_device")
+
+
+class OrbPaths(C.Structure):  # gfs_test_orb_paths
+    _fields_ = _i32_fields("octree_on_device pyr_kernel pyr_fine_cut geometry_builds last_batch rows cols")
+
+
+ORB_PYR_NONE, ORB_PYR_LDS, ORB_PYR_HBM = 0, 1, 2  # GFS_TEST_ORB_PYR_*
+
+
 class GicpConfig(C.Structure):
     _fields_ = [("num_threads", C.c_int32), ("downsampling_resolution", C.c_double),
                 ("max_correspondence_distance", C.c_double), ("rotation_eps", C.c_double),
@@ -769,7 +790,7 @@ ABI_SYMBOLS = [
     "gfs_orb_extract", "gfs_orb_extract_batch", "gfs_orb_extract_batch_device", "gfs_orb_device_results",
     "gfs_orb_fetch", "gfs_orb_level_size", "gfs_orb_fetch_level", "gfs_orb_fetch_candidates", "gfs_orb_octree_host",
     "gfs_orb_octree_device", "gfs_test_sort_replica", "gfs_test_heap_sort_replica", "gfs_test_glibc_math", "gfs_test_traffic",
-    "gfs_test_orb_blur_tiles",
+    "gfs_test_orb_blur_tiles", "gfs_test_orb_geometry", "gfs_test_orb_last_paths",
     "gfs_hamming256", "gfs_matcher_create", "gfs_matcher_destroy", "gfs_bf_match_hamming",
     "gfs_bf_match_hamming_batch_device",
     "gfs_gicp_default_config", "gfs_gicp_create", "gfs_gicp_destroy", "gfs_gicp_align", "gfs_gicp_align_batch_device",
@@ -832,6 +853,8 @@ def lib():
         L.gfs_orb_level_size.argtypes = [vp, i, ip, ip]
         L.gfs_orb_fetch_level.argtypes = [vp, i, i, i, vp]
         L.gfs_orb_fetch_candidates.argtypes = [vp, i, i, vp, vp, vp, i]
+        L.gfs_test_orb_geometry.argtypes = [i, i, i, i, C.c_float, C.POINTER(OrbGeometryInfo), vp, i]
+        L.gfs_test_orb_last_paths.argtypes = [vp, C.POINTER(OrbPaths)]
         L.gfs_orb_octree_host.argtypes = [vp, vp, vp, i, i, i, i, i, i, vp, i]
         L.gfs_orb_octree_device.argtypes = [i, vp, vp, vp, i, i, i, i, i, i, vp, vp, vp, i]
         L.gfs_test_glibc_math.argtypes = [i, vp, i, vp, vp, vp]
@@ -1053,7 +1076,9 @@ class ORBextractor:
         r = lib().gfs_orb_extract(self.h, C.c_void_p(image.ctypes.data), image.shape[0], image.shape[1], stride,
                                   vLappingArea[0], vLappingArea[1], _p(kps), _p(desc), self.cap, C.byref(n))
         if r < -1:
-            raise GfsError(f"gfs_orb_extract failed ({r + 100}): {lib().gfs_last_error().decode()}")
+            err = GfsError(f"gfs_orb_extract failed ({r + 100}): {lib().gfs_last_error().decode()}")
+            err.code = r + 100  # GFS_ERR_* (include/gfs_abi.h)
+            raise err
         return r, kps[:n.value].copy(), desc[:n.value].copy()
 
     def extract_batch(self, images, vLappingArea=(0, 0)):
@@ -1104,6 +1129,27 @@ class ORBextractor:
         x, y, s = (np.zeros(max(n, 1), np.int32) for _ in range(3))
         lib().gfs_orb_fetch_candidates(self.h, b, l, _p(x), _p(y), _p(s), n)
         return x[:n], y[:n], s[:n]
+
+
+    def last_paths(self):
+        """gfs_test_orb_last_paths: the paths of the handle's last call and its count of geometry rebuilds (test hook)."""
+        P = OrbPaths()
+        _check(lib().gfs_test_orb_last_paths(self.h, C.byref(P)), "gfs_test_orb_last_paths")
+        return {n: int(getattr(P, n)) for n, _ in OrbPaths._fields_}
+
+
+def orb_geometry(rows, cols, nfeatures=1000, nlevels=8, scale_factor=1.2):
+    """gfs_test_orb_geometry (host only): what OrbGeometry::build decides for rows x cols -> dict of the frame's figures with
+    "levels": a list of per-level dicts; "supported" is False (and "levels" empty) for a size build refuses."""
+    I = OrbGeometryInfo()
+    Lv = (OrbLevelInfo * nlevels)()
+    rc = lib().gfs_test_orb_geometry(rows, cols, nfeatures, nlevels, scale_factor, C.byref(I), C.cast(Lv, C.c_void_p), nlevels)
+    out = {n: int(getattr(I, n)) for n, _ in OrbGeometryInfo._fields_}
+    out["supported"] = bool(out["supported"])
+    if rc == -5:  # GFS_ERR_UNSUPPORTED: build refuses the size
+        return dict(out, levels=[])
+    _check(rc, "gfs_test_orb_geometry")
+    return dict(out, levels=[{n: int(getattr(Lv[l], n)) for n, _ in OrbLevelInfo._fields_} for l in range(nlevels)])
 
 
 def wave_std_sort_perm(keys, device=0):

@@ -913,7 +913,7 @@ __global__ __launch_bounds__(256) void k_cand_pack(const LevelDev* __restrict__ 
 // L1 / L2), the node arrays live in LDS.
 // ------------------------------------------------------------------------------------------------
 constexpr int kOctThreads = 256;
-constexpr int kOctMaxNodes = 768;
+constexpr int kOctMaxNodes = gfs::kOctMaxNodes;  // (orb_host.hpp: the rule of which levels the kernel takes is stated there)
 inline size_t oct_lds_bytes(int node_cap) { return (size_t)node_cap * (2 * 16 + 2 * 16 + 8 + 2 * 8 + 8 + 1) + 16; }
 
 struct ONode {
@@ -2097,6 +2097,7 @@ struct gfs_orb {
   gfs::PinBuf<int> h_cand_off, h_kp_count, h_mono;
   gfs::PinBuf<uint32_t> h_cand;
   gfs::PinBuf<KpIn> h_kpin;
+  int geometry_builds = 0;  // times ensure_geometry rewrote the tables (the first image counts)
   // last call
   int last_B = 0;
   Lvl0 last_l0{};
@@ -2105,6 +2106,22 @@ struct gfs_orb {
 };
 
 namespace {
+
+// Which pyramid kernel a call of B frames runs, and with which cut of row strips.  run_batch launches by it, gfs_test_orb_last_paths
+// reports it.  None: nlevels = 1 -- no level above 0 (OrbGeometry::build leaves pyr_strips = 0), and level 0 is read from the
+// caller's image by every later kernel.
+enum PyrKernel { kPyrNone = 0, kPyrLds = 1, kPyrHbm = 2 };
+struct PyrPath {
+  PyrKernel kernel;
+  bool fine;  // a few frames: the finer cut, so that the launch has workgroups for the chip (a frame's strips are dependent chains of levels)
+};
+inline PyrPath pyr_path(const gfs_orb* h, int B) {
+  const gfs::OrbGeometry& G = h->G;
+  if (G.pyr_strips <= 0) return {kPyrNone, false};
+  if (G.pyr_lds_a + G.pyr_lds_b > 0 && !h->pyr_in_hbm) return {kPyrLds, G.pyr_strips_fine > 0 && B * G.pyr_strips < 128};
+  return {kPyrHbm, false};
+}
+inline bool octree_on_device(const gfs_orb* h) { return h->device_octree && h->octree_supported; }
 
 int ensure_geometry(gfs_orb* h, int rows, int cols) {
   if (h->geom_rows == rows && h->geom_cols == cols) return GFS_OK;
@@ -2125,37 +2142,33 @@ int ensure_geometry(gfs_orb* h, int rows, int cols) {
   GFS_HIP(hipMemcpyAsync(h->d_levels.p, G.levels.data(), G.levels.size() * sizeof(LevelDev), hipMemcpyHostToDevice, s));
   GFS_HIP(hipMemcpyAsync(h->d_cells.p, G.cells.data(), G.cells.size() * sizeof(CellDev), hipMemcpyHostToDevice, s));
   GFS_HIP(hipMemcpyAsync(h->d_tiles.p, G.blur_tiles.data(), G.blur_tiles.size() * sizeof(BlurTileDev), hipMemcpyHostToDevice, s));
-  GFS_HIP(hipMemcpyAsync(h->d_strip_rows.p, G.strip_rows.data(), G.strip_rows.size() * 4, hipMemcpyHostToDevice, s));
-  if (G.pyr_strips_fine > 0)
-    GFS_HIP(hipMemcpyAsync(h->d_strip_rows_fine.p, G.strip_rows_fine.data(), G.strip_rows_fine.size() * 4, hipMemcpyHostToDevice, s));
-  GFS_HIP(hipMemcpyAsync(h->d_xt_start.p, G.xt_start.data(), G.xt_start.size() * 4, hipMemcpyHostToDevice, s));
-  GFS_HIP(hipMemcpyAsync(h->d_xt_n.p, G.xt_n.data(), G.xt_n.size() * 4, hipMemcpyHostToDevice, s));
-  GFS_HIP(hipMemcpyAsync(h->d_xt_alpha.p, G.xt_alpha.data(), G.xt_alpha.size() * 4, hipMemcpyHostToDevice, s));
-  GFS_HIP(hipMemcpyAsync(h->d_yt_start.p, G.yt_start.data(), G.yt_start.size() * 4, hipMemcpyHostToDevice, s));
-  GFS_HIP(hipMemcpyAsync(h->d_yt_n.p, G.yt_n.data(), G.yt_n.size() * 4, hipMemcpyHostToDevice, s));
-  GFS_HIP(hipMemcpyAsync(h->d_yt_alpha.p, G.yt_alpha.data(), G.yt_alpha.size() * 4, hipMemcpyHostToDevice, s));
+  if (G.pyr_strips > 0) {  // (nlevels = 1: no level above 0, no strips and no INTER_AREA tables)
+    GFS_HIP(hipMemcpyAsync(h->d_strip_rows.p, G.strip_rows.data(), G.strip_rows.size() * 4, hipMemcpyHostToDevice, s));
+    if (G.pyr_strips_fine > 0)
+      GFS_HIP(hipMemcpyAsync(h->d_strip_rows_fine.p, G.strip_rows_fine.data(), G.strip_rows_fine.size() * 4, hipMemcpyHostToDevice, s));
+    GFS_HIP(hipMemcpyAsync(h->d_xt_start.p, G.xt_start.data(), G.xt_start.size() * 4, hipMemcpyHostToDevice, s));
+    GFS_HIP(hipMemcpyAsync(h->d_xt_n.p, G.xt_n.data(), G.xt_n.size() * 4, hipMemcpyHostToDevice, s));
+    GFS_HIP(hipMemcpyAsync(h->d_xt_alpha.p, G.xt_alpha.data(), G.xt_alpha.size() * 4, hipMemcpyHostToDevice, s));
+    GFS_HIP(hipMemcpyAsync(h->d_yt_start.p, G.yt_start.data(), G.yt_start.size() * 4, hipMemcpyHostToDevice, s));
+    GFS_HIP(hipMemcpyAsync(h->d_yt_n.p, G.yt_n.data(), G.yt_n.size() * 4, hipMemcpyHostToDevice, s));
+    GFS_HIP(hipMemcpyAsync(h->d_yt_alpha.p, G.yt_alpha.data(), G.yt_alpha.size() * 4, hipMemcpyHostToDevice, s));
+  }
   std::vector<int> kept_off(G.levels.size());
-  bool oct_ok = true;
-  int oct_cap = 8;
   {
     int o = 0;
     for (size_t l = 0; l < G.levels.size(); l++) {
       kept_off[l] = o;
       o += G.levels[l].kp_cap;
-      const LevelDev& L = G.levels[l];
-      int nIni = (int)std::round((float)(L.max_bx - 16) / (float)(L.max_by - 16));
-      if (nIni == 0) nIni = 1;
-      if (nIni > 4 || L.quota + 4 * nIni + 8 > kOctMaxNodes) oct_ok = false;  // outside what k_octree holds in LDS
-      oct_cap = std::max(oct_cap, (L.quota + 4 * nIni + 8 + 7) / 8 * 8);
     }
   }
   GFS_HIP(hipMemcpyAsync(h->d_kept_off.p, kept_off.data(), kept_off.size() * sizeof(int), hipMemcpyHostToDevice, s));
   GFS_HIP(hipStreamSynchronize(s));
-  h->octree_supported = oct_ok;
-  h->oct_node_cap = std::min(oct_cap, kOctMaxNodes);
+  h->octree_supported = G.oct_on_device;  // a level outside what k_octree holds in LDS (gfs::oct_level_fit): the host quadtree
+  h->oct_node_cap = G.oct_node_cap;
   h->G = std::move(G);
   h->geom_rows = rows;
   h->geom_cols = cols;
+  h->geometry_builds++;
   return GFS_OK;
 }
 
@@ -2166,9 +2179,9 @@ int run_batch(gfs_orb* h, Lvl0 l0, int B, int rows, int cols, int lap0, int lap1
   const int n_cells = (int)G.cells.size();
   const size_t cap_pyr = h->cap_pyr, cap_blur = h->cap_blur, cap_slab = h->cap_slab;
   // 1. pyramid chain (level l depends on l-1): one launch, row strips with recomputed halos
-  if (G.pyr_lds_a + G.pyr_lds_b > 0 && !h->pyr_in_hbm) {
-    // a few frames: the finer cut, so that the launch has workgroups for the chip (a frame's strips are dependent chains of levels)
-    const bool fine = G.pyr_strips_fine > 0 && B * G.pyr_strips < 128;
+  const PyrPath pp = pyr_path(h, B);
+  if (pp.kernel == kPyrLds) {
+    const bool fine = pp.fine;
     const int S = fine ? G.pyr_strips_fine : G.pyr_strips;
     const size_t la = fine ? G.pyr_lds_a_fine : G.pyr_lds_a, lb = fine ? G.pyr_lds_b_fine : G.pyr_lds_b;
     const size_t lx = fine ? G.pyr_lds_x_fine : G.pyr_lds_x;
@@ -2176,7 +2189,7 @@ int run_batch(gfs_orb* h, Lvl0 l0, int B, int rows, int cols, int lap0, int lap1
                fine ? h->d_strip_rows_fine.p : h->d_strip_rows.p, (unsigned)la, lx ? (unsigned)(la + lb) : 0u, (int)G.xt_start.size(),
                h->d_xt_start.p, h->d_xt_n.p, h->d_xt_alpha.p,
                h->d_yt_start.p, h->d_yt_n.p, h->d_yt_alpha.p);
-  } else {
+  } else if (pp.kernel == kPyrHbm) {
     GFS_LAUNCH("k_pyr_area_hbm", k_pyr_area_hbm, dim3(G.pyr_strips, B), dim3(kPyrThreads), 0, s, h->d_levels.p, nl, l0, h->d_pyr.p,
                cap_pyr, h->d_strip_rows.p, h->d_xt_start.p, h->d_xt_n.p, h->d_xt_alpha.p, h->d_yt_start.p, h->d_yt_n.p,
                h->d_yt_alpha.p);
@@ -2187,7 +2200,7 @@ int run_batch(gfs_orb* h, Lvl0 l0, int B, int rows, int cols, int lap0, int lap1
   GFS_LAUNCH("k_fast_cells", k_fast_cells, dim3(fm.grid), dim3(64 * kFcWaves), (size_t)kFcWaves * G.fast_lds_wave, s, h->d_cells.p, l0,
              h->d_pyr.p, cap_pyr, h->P.ini_th, h->P.min_th, n_cells, fm, (int)G.fast_lds_wave, cap_slab, h->d_slab.p, h->d_cell_cnt.p);
   const int* tp = kBlurTaps[h->P.blur_variant ? 1 : 0];
-  if (h->device_octree && h->octree_supported) {
+  if (octree_on_device(h)) {
     // 3-6 (device): quadtree (it takes its level's candidates straight from the cell slabs), slot assignment, blur, orientation +
     // descriptors — no host round trip at all; the dense candidate list is only laid out when an introspection call asks for it
     GFS_LAUNCH("k_octree", k_octree, dim3(B * nl), dim3(kOctThreads), oct_lds_bytes(h->oct_node_cap), s, h->d_levels.p, nl, nullptr,
@@ -2597,10 +2610,9 @@ int gfs_orb_octree_device(int device, const int32_t* x, const int32_t* y, const 
   L.max_bx = max_x;
   L.max_by = max_y;
   L.quota = n_features;
-  int nIni = (int)std::round((float)(max_x - 16) / (float)(max_y - 16));
-  if (nIni == 0) nIni = 1;
-  GFS_REQUIRE(nIni <= 4 && n_features + 4 * nIni + 8 <= kOctMaxNodes, GFS_ERR_UNSUPPORTED, "outside k_octree limits");
-  const int kcap = n_features + 3 + 4 * nIni + 8;
+  const gfs::OctLevelFit fit = gfs::oct_level_fit(max_x, max_y, n_features);
+  GFS_REQUIRE(fit.on_device, GFS_ERR_UNSUPPORTED, "outside k_octree limits");
+  const int kcap = n_features + 3 + 4 * fit.n_ini + 8;
   std::vector<uint32_t> c(std::max(n, 1));
   for (int i = 0; i < n; i++) c[i] = (uint32_t)x[i] | ((uint32_t)y[i] << 12) | ((uint32_t)score[i] << 24);
   gfs::DevBuf<LevelDev> dL;
@@ -2617,7 +2629,7 @@ int gfs_orb_octree_device(int device, const int32_t* x, const int32_t* y, const 
   GFS_HIP(hipMemcpy(dc.p, c.data(), c.size() * 4, hipMemcpyHostToDevice));
   GFS_HIP(hipMemcpy(doff.p, off, sizeof(off), hipMemcpyHostToDevice));
   GFS_HIP(hipMemcpy(dko.p, &ko, sizeof(ko), hipMemcpyHostToDevice));
-  const int node_cap = (n_features + 4 * nIni + 8 + 7) / 8 * 8;
+  const int node_cap = (fit.nodes + 7) / 8 * 8;
   GFS_HIP(hipFuncSetAttribute((const void*)k_octree, hipFuncAttributeMaxDynamicSharedMemorySize, (int)oct_lds_bytes(kOctMaxNodes)));
   hipLaunchKernelGGL(k_octree, dim3(1), dim3(kOctThreads), oct_lds_bytes(node_cap), 0, dL.p, 1, dc.p, doff.p, c.size(), p0.p, p1.p, s0.p, s1.p,
                      dko.p, kcap, dk.p, dcnt.p, node_cap, (const CellDev*)nullptr, (const int*)nullptr, 0, (const uint32_t*)nullptr);
@@ -2632,6 +2644,21 @@ int gfs_orb_octree_device(int device, const int32_t* x, const int32_t* y, const 
     out_score[i] = gfs::cand_score(k[i]);
   }
   return cnt;
+}
+
+// Test hook (include/gfs_abi_test.h): the paths of the handle's last call, read from what run_batch itself branches on.
+int gfs_test_orb_last_paths(gfs_orb* h, gfs_test_orb_paths* out) {
+  GFS_REQUIRE(h && out, GFS_ERR_INVALID_ARG, "gfs_test_orb_last_paths: NULL argument");
+  std::lock_guard<std::mutex> lk(h->mu);
+  const PyrPath pp = pyr_path(h, h->last_B);
+  out->octree_on_device = octree_on_device(h) ? 1 : 0;
+  out->pyr_kernel = (int)pp.kernel;
+  out->pyr_fine_cut = pp.fine ? 1 : 0;
+  out->geometry_builds = h->geometry_builds;
+  out->last_batch = h->last_B;
+  out->rows = h->geom_rows;
+  out->cols = h->geom_cols;
+  return GFS_OK;
 }
 
 // Host-logic hook for the CPU test-suite: the product's index-based DistributeOctTree on caller candidates.

@@ -96,6 +96,15 @@ static bool area_tab(int ssize, int dsize, std::vector<int>& start, std::vector<
   return true;
 }
 
+OctLevelFit oct_level_fit(int max_bx, int max_by, int quota) {
+  OctLevelFit f;
+  f.n_ini = (int)std::round((float)(max_bx - 16) / (float)(max_by - 16));  // (minBorder = EDGE_THRESHOLD - 3 = 16 on both axes)
+  if (f.n_ini == 0) f.n_ini = 1;
+  f.nodes = quota + 4 * f.n_ini + 8;
+  f.on_device = f.n_ini <= 4 && f.nodes <= kOctMaxNodes;
+  return f;
+}
+
 void OrbGeometry::build(const OrbParams& p, int rows_, int cols_) {
   rows = rows_;
   cols = cols_;
@@ -114,6 +123,8 @@ void OrbGeometry::build(const OrbParams& p, int rows_, int cols_) {
   kp_cap = 0;
   max_tile_w = max_tile_h = 0;
   fast_lds_wave = 0;
+  oct_on_device = true;
+  oct_node_cap = 8;
   for (int l = 0; l < p.nlevels; l++) {
     LevelDev& L = levels[l];
     // ComputePyramid, src/ORBextractor.cc:1228-1231
@@ -197,10 +208,11 @@ void OrbGeometry::build(const OrbParams& p, int rows_, int cols_) {
       }
     }
     L.n_cells = (int)cells.size() - L.cell_base;
-    int nIni = (int)std::round(width / height);
-    if (nIni == 0) nIni = 1;
-    L.kp_cap = L.quota + 3 + 4 * nIni;
+    const OctLevelFit fit = oct_level_fit(L.max_bx, L.max_by, L.quota);
+    L.kp_cap = L.quota + 3 + 4 * fit.n_ini;
     kp_cap += L.kp_cap;
+    if (!fit.on_device) oct_on_device = false;
+    oct_node_cap = std::min(std::max(oct_node_cap, (fit.nodes + 7) / 8 * 8), kOctMaxNodes);
     for (int ty = 0; ty < (L.rows + 31) / 32; ty++)  // 64 x 32 tiles (k_blur7)
       for (int tx = 0; tx < (L.cols + 63) / 64; tx++) blur_tiles.push_back(BlurTileDev{(short)l, (short)tx, (short)ty, 0, L.rows, L.cols, L.pitch, L.plane_off, L.blur_off, 0u});
   }
@@ -585,6 +597,53 @@ extern "C" int gfs_test_orb_blur_tiles(int rows, int cols, int nlevels, float sc
     level_tx_ty[3 * i + 2] = G.blur_tiles[i].ty;
   }
   return n;
+}
+
+// ---- test hook: what OrbGeometry::build decides for one image size (include/gfs_abi_test.h), host only ----
+#include "../../include/gfs_abi_test.h"
+extern "C" int gfs_test_orb_geometry(int rows, int cols, int nfeatures, int nlevels, float scale_factor, gfs_test_orb_geometry_info* info,
+                                     gfs_test_orb_level_info* levels, int cap_levels) {
+  if (!info || rows <= 0 || cols <= 0 || nfeatures <= 0 || nlevels <= 0 || nlevels > 16 || !(scale_factor > 1.f)) return GFS_ERR_INVALID_ARG;
+  gfs::OrbParams P;
+  P.init(nfeatures, scale_factor, nlevels, 20, 7, 0);
+  gfs::OrbGeometry G;
+  G.build(P, rows, cols);
+  *info = gfs_test_orb_geometry_info{};
+  info->supported = G.supported ? 1 : 0;
+  if (!G.supported) return GFS_ERR_UNSUPPORTED;
+  info->pyr_strips = G.pyr_strips;
+  info->pyr_strips_fine = G.pyr_strips_fine;
+  info->pyr_in_lds = G.pyr_lds_a + G.pyr_lds_b > 0 ? 1 : 0;
+  info->xtab_in_lds = G.pyr_lds_x > 0 ? 1 : 0;
+  info->xtab_in_lds_fine = G.pyr_lds_x_fine > 0 ? 1 : 0;
+  info->kp_cap = G.kp_cap;
+  info->octree_on_device = G.oct_on_device ? 1 : 0;
+  info->oct_node_cap = G.oct_node_cap;
+  info->n_cells = (int)G.cells.size();
+  info->n_blur_tiles = (int)G.blur_tiles.size();
+  info->fast_lds_wave = (int)G.fast_lds_wave;
+  for (int l = 0; l < nlevels && l < cap_levels && levels; l++) {
+    const gfs::LevelDev& L = G.levels[l];
+    const gfs::OctLevelFit fit = gfs::oct_level_fit(L.max_bx, L.max_by, L.quota);
+    gfs_test_orb_level_info& o = levels[l];
+    o.rows = L.rows;
+    o.cols = L.cols;
+    o.n_cell_cols = L.n_cell_cols;
+    o.n_cell_rows = L.n_cell_rows;
+    o.w_cell = L.w_cell;
+    o.h_cell = L.h_cell;
+    o.n_cells = L.n_cells;
+    o.max_cell_w = o.max_cell_h = 0;
+    for (int c = L.cell_base; c < L.cell_base + L.n_cells; c++) {
+      o.max_cell_w = std::max(o.max_cell_w, (int)G.cells[c].w);
+      o.max_cell_h = std::max(o.max_cell_h, (int)G.cells[c].h);
+    }
+    o.quota = L.quota;
+    o.n_ini = fit.n_ini;
+    o.kp_cap = L.kp_cap;
+    o.octree_on_device = fit.on_device ? 1 : 0;
+  }
+  return nlevels;
 }
 
 // ---- test hook: the std::sort replica used by the device quadtree, run on the host against caller data ----

@@ -14,6 +14,17 @@ constexpr int kHalfPatch = 15;      // :52
 constexpr int kEdgeThreshold = 19;  // :53
 constexpr int kMaxAreaTaps = 4;     // INTER_AREA taps per destination pixel we support (level ratio < 3)
 
+// What the device quadtree (k_octree, csrc/orb.hip) takes of one level: its node list lives in LDS, kOctMaxNodes entries at most, and
+// its first sweep cuts the border box into at most four initial nodes.  A level outside sends the whole call to the host quadtree
+// (distribute_octree below).  Stated here once: OrbGeometry::build, the handle and the test hooks all read this.
+constexpr int kOctMaxNodes = 768;
+struct OctLevelFit {
+  int n_ini;       // DistributeOctTree's initial nodes (src/ORBextractor.cc:573): the rounded aspect of the border box, at least 1
+  int nodes;       // most nodes the level's list can hold: quota + 4 n_ini + 8
+  bool on_device;  // k_octree takes the level
+};
+OctLevelFit oct_level_fit(int max_bx, int max_by, int quota);
+
 // Device-visible per-level geometry (POD, uploaded as an array).
 struct LevelDev {
   int rows, cols, pitch;
@@ -94,6 +105,8 @@ struct OrbGeometry {
   int kp_cap = 0;                        // keypoint capacity per frame
   int max_tile_w = 0, max_tile_h = 0;    // FAST cell tile bounds
   size_t fast_lds_wave = 0;              // LDS bytes of one cell in k_fast_cells (tile + score map + offset list), the largest cell's
+  bool oct_on_device = true;             // every level within k_octree (oct_level_fit); false: the host quadtree runs the whole call
+  int oct_node_cap = 8;                  // nodes k_octree's LDS list is sized for: the largest level's, whole eights, <= kOctMaxNodes
   bool supported = true;
   const char* why = "";
   void build(const OrbParams& p, int rows, int cols);

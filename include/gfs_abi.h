@@ -71,6 +71,27 @@ typedef struct {
 } gfs_orb_config;
 
 void gfs_orb_default_config(gfs_orb_config* cfg);
+/* One handle per extractor.  nlevels = 1 is accepted (no pyramid is built; level 0 is the caller's image).
+ *
+ * WHICH IMAGES A HANDLE TAKES.  The workspace is sized once, from the geometry of max_rows x max_cols; a call with another size
+ * rewrites the handle's tables (a device synchronisation and a dozen small uploads: not per-frame work) and is taken when
+ *   - rows <= max_rows and cols <= max_cols                                          (else GFS_ERR_CAPACITY),
+ *   - every pyramid level holds at least one 35 x 35 FAST cell inside its 16-pixel border, i.e. the top level is at least 67 x 67,
+ *     and the image is smaller than 4096 x 4096                                      (else GFS_ERR_UNSUPPORTED),
+ *   - the image's own geometry fits what the max size reserved: pyramid and blur bytes, FAST cells, candidate slots, and the
+ *     key-point capacity kp_cap = sum over levels of (quota + 3 + 4 nIni), nIni = max(1, round(width / height)) of the level's
+ *     border box (cols - 32, rows - 32) -- the handle holds kp_cap of max_rows x max_cols, + 8  (else GFS_ERR_CAPACITY).
+ * The last rule is NOT "any smaller image": nIni is rounded per level, and the small top levels of a smaller image can round up where
+ * those of the max size round down.  With the default configuration (1000 features, 8 levels, 640 x 480: kp_cap 1056, 1064 held)
+ *   - 320 x 240, the same aspect ratio, needs 1068 -- its top three levels are 129 x 96, 107 x 80 and 89 x 67, nIni = 2 each -- and
+ *   - 640 x 300 needs 1100 (nIni = 2 on levels 0..4, 3 above);
+ * both are refused with GFS_ERR_CAPACITY, gfs_last_error() = "image 320x240 needs more workspace than the handle reserved".  A
+ * refused call changes nothing: the handle keeps the geometry, the results and the device buffers of its last accepted call and
+ * takes the next image as if the refused one had not been tried.  A caller that feeds several sizes creates one handle per size, or
+ * creates the handle with the max_rows x max_cols whose kp_cap is the largest of its sizes (gfs_orb_max_keypoints reports
+ * what a handle holds).  Resizing a handle's workspace is not implemented.
+ * A level whose nIni exceeds 4, or whose quota + 4 nIni + 8 exceeds 768, is outside the device quadtree: such a call is taken, with
+ * the same results, through the host quadtree (slower: one round trip of the candidates). */
 int gfs_orb_create(const gfs_orb_config* cfg, gfs_orb** out);
 void gfs_orb_destroy(gfs_orb* h);
 
@@ -78,7 +99,8 @@ void gfs_orb_destroy(gfs_orb* h);
  * (include/ORBextractor.h:66-80) plus the per-level feature quota and the umax table. Any pointer may be NULL. */
 int gfs_orb_get_tables(const gfs_orb* h, float* scale, float* inv_scale, float* sigma2, float* inv_sigma2,
                        int32_t* features_per_level, int32_t* umax16);
-/* upper bound of keypoints one image can produce (sum of quotas + 3 per level: the octree may overshoot). */
+/* upper bound of keypoints one image can produce: kp_cap of max_rows x max_cols + 8 (per level quota + 3 + 4 nIni: the octree may
+ * overshoot its quota, and keeps the 4 nIni nodes of its first sweep whatever the quota; see gfs_orb_create). */
 int gfs_orb_max_keypoints(const gfs_orb* h);
 
 /* operator()(image, mask (ignored), keypoints, descriptors, vLappingArea): host image (CV_8UC1, `stride`

@@ -20,6 +20,48 @@ int gfs_test_heap_sort_replica(int32_t* size_key, int32_t* x_key, int32_t* paylo
  * tiles.  The 2 x 2 tiles over the same 128-byte lines sit at positions p, p + 8, p + 16, p + 24 (one XCD's L2 serves them). */
 int gfs_test_orb_blur_tiles(int rows, int cols, int nlevels, float scale_factor, int32_t* level_tx_ty, int cap);
 
+/* Host test hook (no GPU): what OrbGeometry::build (csrc/orb_host.cpp) decides for an image of rows x cols under an extractor of
+ * nfeatures / nlevels / scale_factor -- the very object gfs_orb_create sizes a handle from and every call lays its tables out from,
+ * not a second statement of its rules.  *info is always filled; levels[0 .. min(nlevels, cap_levels)) when supported.  Returns the
+ * number of levels, or GFS_ERR_UNSUPPORTED when build refuses the size (a level smaller than one FAST cell, an integer level ratio,
+ * 4096 pixels or more), GFS_ERR_INVALID_ARG for arguments gfs_orb_create refuses. */
+typedef struct gfs_test_orb_geometry_info {
+  int32_t supported;
+  int32_t pyr_strips, pyr_strips_fine; /* row strips of the pyramid kernel: the coarse cut, the fine cut (0 = none); both 0 with one level */
+  int32_t pyr_in_lds;                  /* the strips fit the LDS (k_pyr_area_lds); 0 = k_pyr_area_hbm, or no pyramid kernel at all */
+  int32_t xtab_in_lds, xtab_in_lds_fine; /* the x tables sit in LDS behind the strips of the coarse / fine cut; 0 = read from memory */
+  int32_t kp_cap;                      /* key points a frame can give: the sum of the levels' kp_cap.  A handle holds its max size's + 8 */
+  int32_t octree_on_device;            /* every level within k_octree; 0 = the whole call runs the host quadtree */
+  int32_t oct_node_cap;                /* nodes k_octree's LDS list is sized for */
+  int32_t n_cells, n_blur_tiles;       /* FAST cells and 64 x 32 blur tiles of all levels */
+  int32_t fast_lds_wave;               /* LDS bytes of the largest cell in k_fast_cells */
+} gfs_test_orb_geometry_info;
+typedef struct gfs_test_orb_level_info {
+  int32_t rows, cols;
+  int32_t n_cell_cols, n_cell_rows, w_cell, h_cell; /* the FAST cell grid (src/ORBextractor.cc:778-806) */
+  int32_t n_cells;                                  /* cells that are launched (the reference skips a cell that starts in the border) */
+  int32_t max_cell_w, max_cell_h;                   /* the largest cell's window, its 3-pixel FAST margins included */
+  int32_t quota;                                    /* mnFeaturesPerLevel */
+  int32_t n_ini;                                    /* DistributeOctTree's initial nodes (:573), at least 1 */
+  int32_t kp_cap;                                   /* quota + 3 + 4 n_ini */
+  int32_t octree_on_device;                         /* k_octree takes this level: n_ini <= 4 and quota + 4 n_ini + 8 <= 768 */
+} gfs_test_orb_level_info;
+int gfs_test_orb_geometry(int rows, int cols, int nfeatures, int nlevels, float scale_factor, gfs_test_orb_geometry_info* info,
+                          gfs_test_orb_level_info* levels, int cap_levels);
+
+/* Test hook: the paths the handle's last extract call took, from the flags the call itself branched on. */
+#define GFS_TEST_ORB_PYR_NONE 0 /* nlevels = 1: no level above 0, no pyramid launch */
+#define GFS_TEST_ORB_PYR_LDS 1  /* k_pyr_area_lds */
+#define GFS_TEST_ORB_PYR_HBM 2  /* k_pyr_area_hbm */
+typedef struct gfs_test_orb_paths {
+  int32_t octree_on_device; /* 1 = k_octree; 0 = the host quadtree (GFS_ORB_OCTREE=host, or a level k_octree does not take) */
+  int32_t pyr_kernel;       /* GFS_TEST_ORB_PYR_* */
+  int32_t pyr_fine_cut;     /* 1 = the fine cut of row strips (few frames), 0 = the coarse cut or no LDS pyramid kernel */
+  int32_t geometry_builds;  /* times the handle (re)wrote its geometry tables since gfs_orb_create; a refused call does not count */
+  int32_t last_batch, rows, cols; /* the last accepted call; 0 before the first */
+} gfs_test_orb_paths;
+int gfs_test_orb_last_paths(gfs_orb* h, gfs_test_orb_paths* out);
+
 /* GPU test hook: sin(x), cos(x), pow(x, 3.0) of n doubles evaluated on the device with the restated glibc 2.35 arithmetic
  * (csrc/glibc_math.hpp) that the pose / window / registration optimizers use for SE3Quat::exp
  * (Thirdparty/g2o/g2o/types/se3quat.h:223-257) and the Levenberg step control (core/optimization_algorithm_levenberg.cpp:127). */
