@@ -218,6 +218,47 @@ def sim3_opt_result(S, keep, n):
                 chi2=keep["chi2"][:max(n, 0)].copy())
 
 
+class Sim3RansacProblem(C.Structure):
+    _fields_ = [("n_pairs", C.c_int32), ("x3d_c1", C.c_void_p), ("x3d_c2", C.c_void_p), ("max_err1", C.c_void_p), ("max_err2", C.c_void_p),
+                ("fx1", C.c_float), ("fy1", C.c_float), ("cx1", C.c_float), ("cy1", C.c_float), ("fx2", C.c_float), ("fy2", C.c_float),
+                ("cx2", C.c_float), ("cy2", C.c_float), ("fix_scale", C.c_int32), ("min_inliers", C.c_int32), ("n_iterations", C.c_int32),
+                ("draws", C.c_void_p)]
+
+
+class Sim3RansacSolution(C.Structure):
+    _fields_ = [("T12", C.c_float * 16), ("R12", C.c_float * 9), ("t12", C.c_float * 3), ("s12", C.c_float), ("n_inliers", C.c_int32),
+                ("iterations", C.c_int32), ("status", C.c_int32), ("inlier", C.c_void_p), ("counts", C.c_void_p)]
+
+
+SIM3_RANSAC_CONVERGED, SIM3_RANSAC_NO_MORE, SIM3_RANSAC_TOO_FEW = 0, 1, 2  # GFS_SIM3_RANSAC_* (include/gfs_abi.h)
+
+
+def sim3_ransac_structs(prob):
+    """ctypes views of one Sim3Solver problem dict (synth.sim3_ransac_problem; shared with the CPU restatement's tests): x3d_c1 /
+    x3d_c2 [n, 3], max_err1 / max_err2 [n], cam1 / cam2 (fx, fy, cx, cy), fix_scale, min_inliers, draws [n_iterations, 3]."""
+    P, S = Sim3RansacProblem(), Sim3RansacSolution()
+    n = len(prob["x3d_c1"])
+    draws = np.ascontiguousarray(prob["draws"], np.int32).reshape(-1, 3)
+    H = int(prob.get("n_iterations", len(draws)))
+    keep = dict(x3d_c1=np.ascontiguousarray(prob["x3d_c1"], np.float32).reshape(-1, 3), x3d_c2=np.ascontiguousarray(prob["x3d_c2"], np.float32).reshape(-1, 3),
+                max_err1=np.ascontiguousarray(prob["max_err1"], np.float32), max_err2=np.ascontiguousarray(prob["max_err2"], np.float32),
+                draws=draws, inlier=np.zeros(max(n, 1), np.uint8), counts=np.full(max(H, 1), -1, np.int32))
+    P.n_pairs = n
+    for name in ("x3d_c1", "x3d_c2", "max_err1", "max_err2", "draws"):
+        setattr(P, name, keep[name].ctypes.data)
+    P.fx1, P.fy1, P.cx1, P.cy1 = (float(v) for v in prob["cam1"])
+    P.fx2, P.fy2, P.cx2, P.cy2 = (float(v) for v in prob["cam2"])
+    P.fix_scale, P.min_inliers, P.n_iterations = int(bool(prob["fix_scale"])), int(prob["min_inliers"]), H
+    S.inlier, S.counts = keep["inlier"].ctypes.data, keep["counts"].ctypes.data
+    return P, S, keep, n
+
+
+def sim3_ransac_result(S, keep, n):
+    return dict(T12=np.array(S.T12[:], np.float32).reshape(4, 4), R12=np.array(S.R12[:], np.float32).reshape(3, 3), t12=np.array(S.t12[:], np.float32),
+                s12=np.float32(S.s12), n_inliers=int(S.n_inliers), iterations=int(S.iterations), status=int(S.status),
+                inlier=keep["inlier"][:n].copy(), counts=keep["counts"].copy())
+
+
 class ClaheConfig(C.Structure):
     _fields_ = [("clip_limit", C.c_double), ("tiles_x", C.c_int32), ("tiles_y", C.c_int32), ("residual_variant", C.c_int32)]
 
@@ -803,6 +844,7 @@ ABI_SYMBOLS = [
     "gfs_essential_graph_create", "gfs_essential_graph_destroy", "gfs_essential_graph_optimize", "gfs_essential_graph_correct_points",
     "gfs_essential_graph_last_info", "gfs_test_essential_graph_first_trial", "gfs_test_essential_graph_lists",
     "gfs_sim3_opt_create", "gfs_sim3_opt_destroy", "gfs_sim3_optimize", "gfs_test_glibc_exp",
+    "gfs_sim3_ransac_iterations", "gfs_sim3_ransac_create", "gfs_sim3_ransac_solve", "gfs_sim3_ransac_destroy",
     "gfs_frame_create", "gfs_frame_destroy", "gfs_depth_to_cloud", "gfs_depth_to_cloud_batch_device", "gfs_depth_convert_u16_batch_device", "gfs_stereo_from_rgbd",
     "gfs_stereo_from_rgbd_batch_device",
     "gfs_pose_create", "gfs_pose_destroy", "gfs_pose_optimize", "gfs_pose_set_sum_order",
@@ -929,6 +971,11 @@ def lib():
             L.gfs_sim3_opt_destroy.argtypes = [vp]
             L.gfs_sim3_optimize.argtypes = [vp, vp, i, vp]
             L.gfs_test_glibc_exp.argtypes = [i, vp, i, vp]
+        if hasattr(L, "gfs_sim3_ransac_create"):
+            L.gfs_sim3_ransac_iterations.argtypes = [i, C.c_double, i, i]
+            L.gfs_sim3_ransac_create.argtypes = [i, i, i, i, C.POINTER(vp)]
+            L.gfs_sim3_ransac_destroy.argtypes = [vp]
+            L.gfs_sim3_ransac_solve.argtypes = [vp, vp, i, vp]
         if hasattr(L, "gfs_lba_solve_lidar"):
             L.gfs_lba_lidar_reserve.argtypes = [vp, i]
             L.gfs_lba_solve_lidar.argtypes = [vp, C.POINTER(LbaProblem), C.POINTER(LbaLidar), C.POINTER(LbaSolution), vp, vp]
@@ -2298,6 +2345,44 @@ class Sim3Optimizer:
             keeps.append((keep, n))
         _check(lib().gfs_sim3_optimize(self.h, PP, B, SS), "gfs_sim3_optimize")
         res = [sim3_opt_result(SS[f], *keeps[f]) for f in range(B)]
+        return res[0] if single else res
+
+
+class Sim3RansacSolver:
+    """ORB_SLAM3::Sim3Solver (reference src/Sim3Solver.cc) on flattened pairs (gfs_sim3_ransac_problem in include/gfs_abi.h; DESIGN.md
+    section 23): every hypothesis of every problem of a call is scored at once, the result is what the sequential loop returns."""
+
+    def __init__(self, max_batch=8, max_pairs=2048, max_iterations=300, device=0):
+        self.h = C.c_void_p()
+        _check(lib().gfs_sim3_ransac_create(device, int(max_batch), int(max_pairs), int(max_iterations), C.byref(self.h)), "gfs_sim3_ransac_create")
+
+    def close(self):
+        if getattr(self, "h", None) and _lib is not None:
+            _lib.gfs_sim3_ransac_destroy(self.h)
+        self.h = None
+
+    __del__ = close
+
+    @staticmethod
+    def iterations(n_pairs, probability=0.99, min_inliers=6, max_iterations=300):
+        """Sim3Solver::SetRansacParameters: mRansacMaxIts for n_pairs correspondences."""
+        return int(lib().gfs_sim3_ransac_iterations(int(n_pairs), float(probability), int(min_inliers), int(max_iterations)))
+
+    def solve(self, problems):
+        """problems: one problem dict or a list of them (sim3_ransac_structs) -> result dict(s): T12 [4, 4], R12 [3, 3], t12 [3], s12,
+        n_inliers, iterations, status (SIM3_RANSAC_*), inlier [n], counts [n_iterations] (every hypothesis's count).  Raises GfsError
+        (code GFS_ERR_CAPACITY / GFS_ERR_INVALID_ARG) on a refusal; the handle stays usable."""
+        single = isinstance(problems, dict)
+        probs = [problems] if single else list(problems)
+        B = len(probs)
+        PP, SS = (Sim3RansacProblem * max(B, 1))(), (Sim3RansacSolution * max(B, 1))()
+        keeps = []
+        for f, prob in enumerate(probs):
+            P, S, keep, n = sim3_ransac_structs(prob)
+            PP[f], SS[f] = P, S
+            keeps.append((keep, n))
+        _check(lib().gfs_sim3_ransac_solve(self.h, PP, B, SS), "gfs_sim3_ransac_solve")
+        res = [sim3_ransac_result(SS[f], *keeps[f]) for f in range(B)]
         return res[0] if single else res
 
 

@@ -36,6 +36,7 @@
 #include "../csrc/sim3_search_rule.hpp"
 #include "../csrc/map_point_rule.hpp"
 #include "../csrc/sim3_dev.hpp"
+#include "../csrc/sim3_ransac_rule.hpp"
 #include "../csrc/triangulate_rule.hpp"
 
 namespace gfs_host {
@@ -3017,6 +3018,194 @@ class Sim3Optimizer {
 
  private:
   gfs_sim3_opt* h_ = nullptr;
+};
+
+// ------------------------------------------------------------------------------------------------------------------------
+// class Sim3Solver                                                     reference include/Sim3Solver.h, src/Sim3Solver.cc
+// with the interface its one live call site uses (src/LoopClosing.cc:742-759, :796-798), so that the call site changes only the type
+// name: the constructor, SetRansacParameters, the five-argument iterate, GetEstimatedRotation / Translation / Scale  (DESIGN.md
+// section 23).  The constructor runs :43-116 on the caller's classes.  Kept as the reference has them:
+//   - an empty vpKeyFrameMatchedMP (the default) means every pMP2 is looked up in pKF2 (:44-47);
+//   - every X3Dc2 goes through pKF2's pose (Rcw2, tcw2) and is projected with pKF2's camera also when the point was matched in a
+//     covisible key frame pKFm, while its key-point, and so its threshold, come from pKFm's mvKeysUn / mvLevelSigma2 (:82-106);
+//   - mvnIndices1: vbInliers is indexed by the position in vpMatched12, not by the pair (:100, :263);
+//   - mvnMaxError1 / 2 are vector<size_t> (include/Sim3Solver.h:85-86): 9.210 * sigma2 is truncated to an integer before the float
+//     comparison reads it.
+// The first iterate() draws all 3 * mRansacMaxIts values through Access::random_int (the reference draws them as it goes: when it
+// converges early this uses more of the global rand() stream, whose position other threads move anyway), makes ONE solve call and
+// answers itself and every later call by replaying the result in steps of nIterations: bConverge in the step that contains the
+// converging iteration, bNoMore when the count reaches mRansacMaxIts.  The matrix a step returns is the result's T12 when the step
+// converges or ends the run, the identity otherwise (the reference returns its best so far there, or an uninitialised matrix when
+// the step found none; the call site reads it only after bConverge).  After bConverge or bNoMore a further call answers bNoMore.
+// Single-camera pinhole key frames only (NLeft == -1, Access::is_pinhole): anything else throws.
+// KeyFrame: NLeft, fx, fy, cx, cy, GetRotation(), GetTranslation(), GetMapPointMatches(), mvKeysUn, mvLevelSigma2; MapPoint: isBad(),
+// GetWorldPos(), GetIndexInKeyFrame(); and of `Access`:
+//     static int random_int(int min, int max);                          // DUtils::Random::RandomInt
+//     static void sim3_ransac_solve(const gfs_sim3_ransac_problem&, gfs_sim3_ransac_solution&);   // Sim3RansacDevice::solve below
+//     static Matrix4f matrix4f(const float T[16]); static Matrix3f matrix3f(const float R[9]);    // row-major -> Eigen
+//     static Vector3f vector3f(const float t[3]);
+// ------------------------------------------------------------------------------------------------------------------------
+constexpr double kSim3RansacProbability = 0.99;  // the call site's SetRansacParameters(0.99, nBoWInliers, 300) (src/LoopClosing.cc:745)
+constexpr int kSim3RansacMaxIterations = 300, kSim3RansacStep = 20, kSim3RansacBoWInliers = 15;  // :745, :754 iterate(20, ...), :632
+
+template <class Access>
+class Sim3RansacSolver {
+ public:
+  using Matrix4f = decltype(Access::matrix4f(static_cast<const float*>(nullptr)));
+  using Matrix3f = decltype(Access::matrix3f(static_cast<const float*>(nullptr)));
+  using Vector3f = decltype(Access::vector3f(static_cast<const float*>(nullptr)));
+
+  template <class KeyFrame, class MapPoint>
+  Sim3RansacSolver(KeyFrame* pKF1, KeyFrame* pKF2, const std::vector<MapPoint*>& vpMatched12, const bool bFixScale = true,
+                   std::vector<KeyFrame*> vpKeyFrameMatchedMP = std::vector<KeyFrame*>())
+      : mbFixScale(bFixScale) {
+    auto single_pinhole = [](const KeyFrame& k) { return k.NLeft == -1 && Access::is_pinhole(k); };
+    if (!single_pinhole(*pKF1) || !single_pinhole(*pKF2)) throw std::invalid_argument("Sim3Solver: single-camera pinhole key frames only");
+    bool bDifferentKFs = true;
+    if (vpKeyFrameMatchedMP.empty()) {
+      bDifferentKFs = false;
+      vpKeyFrameMatchedMP = std::vector<KeyFrame*>(vpMatched12.size(), pKF2);
+    }
+    const std::vector<MapPoint*> vpKeyFrameMP1 = pKF1->GetMapPointMatches();
+    mN1 = (int)vpMatched12.size();
+    const auto Rcw1 = pKF1->GetRotation();
+    const auto tcw1 = pKF1->GetTranslation();
+    const auto Rcw2 = pKF2->GetRotation();
+    const auto tcw2 = pKF2->GetTranslation();
+    KeyFrame* pKFm = pKF2;  // Default variable
+    for (int i1 = 0; i1 < mN1; i1++) {
+      if (vpMatched12[i1]) {
+        MapPoint* pMP1 = vpKeyFrameMP1[i1];
+        MapPoint* pMP2 = vpMatched12[i1];
+        if (!pMP1) continue;
+        if (pMP1->isBad() || pMP2->isBad()) continue;
+        if (bDifferentKFs) pKFm = vpKeyFrameMatchedMP[i1];
+        if (!single_pinhole(*pKFm)) throw std::invalid_argument("Sim3Solver: single-camera pinhole key frames only");
+        const int indexKF1 = std::get<0>(pMP1->GetIndexInKeyFrame(pKF1));
+        const int indexKF2 = std::get<0>(pMP2->GetIndexInKeyFrame(pKFm));
+        if (indexKF1 < 0 || indexKF2 < 0) continue;
+        const auto& kp1 = pKF1->mvKeysUn[indexKF1];
+        const auto& kp2 = pKFm->mvKeysUn[indexKF2];
+        const float sigmaSquare1 = pKF1->mvLevelSigma2[kp1.octave];
+        const float sigmaSquare2 = pKFm->mvLevelSigma2[kp2.octave];
+        mvnMaxError1.push_back((float)(size_t)(gfs_s3r::kChi2 * sigmaSquare1));  // (a vector<size_t> in the reference)
+        mvnMaxError2.push_back((float)(size_t)(gfs_s3r::kChi2 * sigmaSquare2));
+        mvnIndices1.push_back(i1);
+        const auto X3D1c = Rcw1 * pMP1->GetWorldPos() + tcw1;
+        const auto X3D2c = Rcw2 * pMP2->GetWorldPos() + tcw2;  // pKF2's pose also when pKFm is another key frame
+        for (int k = 0; k < 3; k++) {
+          mvX3Dc1.push_back(X3D1c(k));
+          mvX3Dc2.push_back(X3D2c(k));
+        }
+      }
+    }
+    cam1_[0] = pKF1->fx, cam1_[1] = pKF1->fy, cam1_[2] = pKF1->cx, cam1_[3] = pKF1->cy;
+    cam2_[0] = pKF2->fx, cam2_[1] = pKF2->fy, cam2_[2] = pKF2->cx, cam2_[3] = pKF2->cy;
+    SetRansacParameters();
+  }
+
+  void SetRansacParameters(double probability = gfs_s3r::kDefaultProbability, int minInliers = gfs_s3r::kDefaultMinInliers,
+                           int maxIterations = gfs_s3r::kDefaultMaxIterations) {
+    mRansacMinInliers = minInliers;
+    N = (int)mvnIndices1.size();
+    mRansacMaxIts = gfs_s3r::ransac_iterations(N, probability, minInliers, maxIterations);
+    mnIterations = 0;
+    solved_ = finished_ = false;
+  }
+
+  Matrix4f iterate(int nIterations, bool& bNoMore, std::vector<bool>& vbInliers, int& nInliers, bool& bConverge) {
+    bNoMore = false;
+    bConverge = false;
+    vbInliers = std::vector<bool>(mN1, false);
+    nInliers = 0;
+    const float identity[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+    if (N < mRansacMinInliers || N < 3 || finished_) {  // (N < 3: the reference would index out of range)
+      bNoMore = true;
+      return Access::matrix4f(identity);
+    }
+    if (!solved_) solve();
+    const int end = std::min(mRansacMaxIts, mnIterations + std::max(nIterations, 0));
+    if (sol_.status == GFS_SIM3_RANSAC_CONVERGED && sol_.iterations <= end) {
+      mnIterations = sol_.iterations;
+      nInliers = sol_.n_inliers;
+      for (int i = 0; i < N; i++)
+        if (inlier_[i]) vbInliers[mvnIndices1[i]] = true;
+      bConverge = true;
+      finished_ = true;
+      return Access::matrix4f(sol_.T12);
+    }
+    mnIterations = end;
+    if (mnIterations >= mRansacMaxIts) {
+      bNoMore = true;
+      finished_ = true;
+      return Access::matrix4f(sol_.T12);
+    }
+    return Access::matrix4f(identity);
+  }
+
+  Matrix3f GetEstimatedRotation() { return Access::matrix3f(sol_.R12); }
+  Vector3f GetEstimatedTranslation() { return Access::vector3f(sol_.t12); }
+  float GetEstimatedScale() { return sol_.s12; }
+
+  // what the solve call was given and what the run used, for whoever wants to log it
+  int pairs() const { return N; }
+  int max_iterations() const { return mRansacMaxIts; }
+  int iterations() const { return mnIterations; }
+  const std::vector<float>& X3Dc1() const { return mvX3Dc1; }
+  const std::vector<float>& X3Dc2() const { return mvX3Dc2; }
+  const std::vector<float>& MaxError1() const { return mvnMaxError1; }
+  const std::vector<float>& MaxError2() const { return mvnMaxError2; }
+  const std::vector<size_t>& Indices1() const { return mvnIndices1; }
+
+ private:
+  void solve() {
+    draws_.resize(3 * (size_t)mRansacMaxIts);
+    for (int it = 0; it < mRansacMaxIts; it++)
+      for (int k = 0; k < 3; k++) draws_[3 * it + k] = Access::random_int(0, N - k - 1);  // RandomInt(0, vAvailableIndices.size() - 1)
+    inlier_.assign(N, 0);
+    gfs_sim3_ransac_problem p{};
+    p.n_pairs = N;
+    p.x3d_c1 = mvX3Dc1.data();
+    p.x3d_c2 = mvX3Dc2.data();
+    p.max_err1 = mvnMaxError1.data();
+    p.max_err2 = mvnMaxError2.data();
+    p.fx1 = cam1_[0], p.fy1 = cam1_[1], p.cx1 = cam1_[2], p.cy1 = cam1_[3];
+    p.fx2 = cam2_[0], p.fy2 = cam2_[1], p.cx2 = cam2_[2], p.cy2 = cam2_[3];
+    p.fix_scale = mbFixScale ? 1 : 0;
+    p.min_inliers = mRansacMinInliers;
+    p.n_iterations = mRansacMaxIts;
+    p.draws = draws_.data();
+    sol_ = gfs_sim3_ransac_solution{};
+    sol_.inlier = inlier_.data();
+    Access::sim3_ransac_solve(p, sol_);
+    solved_ = true;
+  }
+
+  bool mbFixScale;
+  int mN1 = 0, N = 0, mRansacMinInliers = 0, mRansacMaxIts = 0, mnIterations = 0;
+  bool solved_ = false, finished_ = false;
+  float cam1_[4], cam2_[4];
+  std::vector<float> mvX3Dc1, mvX3Dc2, mvnMaxError1, mvnMaxError2;
+  std::vector<size_t> mvnIndices1;
+  std::vector<int32_t> draws_;
+  std::vector<uint8_t> inlier_;
+  gfs_sim3_ransac_solution sol_{};
+};
+
+// numeric core of Sim3Solver on the device (gfs_sim3_ransac_solve): one handle, sized for the call site's 300 iterations
+class Sim3RansacDevice {
+ public:
+  explicit Sim3RansacDevice(int max_batch = 4, int max_pairs = 4096, int max_iterations = kSim3RansacMaxIterations, int device = 0) {
+    check(gfs_sim3_ransac_create(device, max_batch, max_pairs, max_iterations, &h_), "gfs_sim3_ransac_create");
+  }
+  ~Sim3RansacDevice() { gfs_sim3_ransac_destroy(h_); }
+  Sim3RansacDevice(const Sim3RansacDevice&) = delete;
+  Sim3RansacDevice& operator=(const Sim3RansacDevice&) = delete;
+  void solve(const gfs_sim3_ransac_problem& p, gfs_sim3_ransac_solution& s) { check(gfs_sim3_ransac_solve(h_, &p, 1, &s), "gfs_sim3_ransac_solve"); }
+  void solve(const gfs_sim3_ransac_problem* p, int B, gfs_sim3_ransac_solution* s) { check(gfs_sim3_ransac_solve(h_, p, B, s), "gfs_sim3_ransac_solve"); }
+
+ private:
+  gfs_sim3_ransac* h_ = nullptr;
 };
 
 // ------------------------------------------------------------------------------------------------------------------------

@@ -1382,3 +1382,54 @@ def sim3_opt_problem(seed, n_pairs=150, fix_scale=True, outlier_share=0.15, nois
                 th2=float(np.float32(th2)), fix_scale=bool(fix_scale), x1c=x1c, x2c=x2c, obs1=obs1, obs2=obs2,
                 inv_sigma2_1=np.ascontiguousarray(w1, np.float32), inv_sigma2_2=np.ascontiguousarray(w2, np.float32),
                 true_s12=np.concatenate([_quat_xyzw(R), t, [s_true]]), outlier=outlier)
+
+
+def sim3_ransac_iterations(n_pairs, probability=0.99, min_inliers=6, max_iterations=300):
+    """Sim3Solver::SetRansacParameters (reference src/Sim3Solver.cc:119-143) evaluated directly: epsilon a float, the rest in double."""
+    n, m = int(n_pairs), int(min_inliers)
+    if m == n:
+        return 1
+    with np.errstate(all="ignore"):
+        eps = np.float64(np.float32(m) / np.float32(n)) if n else np.float64(np.inf)
+        v = np.ceil(np.log(1 - np.float64(probability)) / np.log(1 - eps ** 3))
+    its = int(v) if np.isfinite(v) and abs(v) < 2 ** 31 else -2 ** 31  # x86-64's answer for a NaN or a value beyond int
+    return max(1, min(its, int(max_iterations)))
+
+
+def sim3_ransac_problem(seed, n_pairs=150, inlier_share=0.6, fix_scale=True, noise_px=0.5, min_inliers=15, n_iterations=None,
+                        probability=0.99, max_iterations=300, rot_deg=25.0, trans=0.8, scale=None, n_levels=8, scale_factor=1.2,
+                        width=640, height=480):
+    """Synthetic input of Sim3Solver (reference src/Sim3Solver.cc), flattened as its constructor leaves it: two clouds of `n_pairs`
+    points in the frames of camera 1 and camera 2, x1 = s R x2 + t with a known S12 = (R, t, s) (s = 1 with fix_scale unless `scale`
+    is given) plus noise of about noise_px pixels at the point's depth; a share 1 - inlier_share of the pairs are outliers (x1 is
+    another point of the frustum).  Each pair sits at a random pyramid level; its thresholds are mvnMaxError as the reference compares
+    them, (float)(size_t)(9.210 * sigma2).  draws [n_iterations, 3]: r0 in [0, n-1], r1 in [0, n-2], r2 in [0, n-3], as
+    DUtils::Random::RandomInt would return them; n_iterations defaults to SetRansacParameters(probability, min_inliers,
+    max_iterations).  -> dict for api.Sim3RansacSolver.solve, plus true_R / true_t / true_s and outlier [n]."""
+    rng = np.random.default_rng(seed)
+    n = int(n_pairs)
+    f32 = np.float32
+    fx, fy, cx, cy = (float(f32(v)) for v in intrinsics(width, height))
+    s_true = float(scale) if scale is not None else (1.0 if fix_scale else float(1.0 + 0.2 * rng.uniform(-1, 1)))
+    R = _rot(*(np.deg2rad(rot_deg) * rng.uniform(-1, 1, 3)))
+    t = trans * rng.uniform(-1, 1, 3)
+
+    def frustum(k):
+        u, v, z = rng.uniform(20, width - 20, k), rng.uniform(20, height - 20, k), rng.uniform(1.0, 6.0, k)
+        return np.stack([(u - cx) / fx * z, (v - cy) / fy * z, z], 1).reshape(k, 3)
+
+    x2 = frustum(n)
+    x1 = s_true * (x2 @ R.T) + t
+    x1 += noise_px / fx * np.abs(x1[:, 2:3]) * rng.normal(size=(n, 3))
+    outlier = rng.random(n) >= inlier_share
+    x1[outlier] = frustum(int(outlier.sum()))
+    sigma2 = (f32(scale_factor) ** np.arange(n_levels, dtype=f32)) ** 2
+    max_err = np.floor(9.210 * sigma2.astype(np.float64)).astype(f32)  # a vector<size_t> in the reference: truncated
+    H = sim3_ransac_iterations(n, probability, min_inliers, max_iterations) if n_iterations is None else int(n_iterations)
+    draws = np.zeros((H, 3), np.int32)
+    if n >= 3:
+        draws = np.stack([rng.integers(0, n - k, H) for k in range(3)], 1).astype(np.int32)
+    return dict(x3d_c1=x1.astype(f32), x3d_c2=x2.astype(f32), max_err1=max_err[rng.integers(0, n_levels, n)],
+                max_err2=max_err[rng.integers(0, n_levels, n)], cam1=np.array([fx, fy, cx, cy], f32), cam2=np.array([fx, fy, cx, cy], f32),
+                fix_scale=bool(fix_scale), min_inliers=int(min_inliers), n_iterations=H, draws=draws, true_R=R, true_t=t, true_s=s_true,
+                outlier=outlier)

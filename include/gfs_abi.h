@@ -1278,6 +1278,48 @@ void gfs_sim3_opt_destroy(gfs_sim3_opt* h);
 int gfs_sim3_optimize(gfs_sim3_opt* h, const gfs_sim3_opt_problem* problems, int B, gfs_sim3_opt_solution* solutions);
 
 /* ============================================================================================
+ * 17. Sim3Solver (src/Sim3Solver.cc) — the RANSAC step of LoopClosing::DetectCommonRegionsFromBoW (:742-759), between
+ *     gfs_search_by_bow and the first gfs_sim3_search: every hypothesis of a candidate, and every candidate, in one call.
+ *    A problem is what the constructor (:43-116) leaves: N pairs of camera-frame points, their thresholds, two pinhole cameras, and
+ *    the draws of DUtils::Random::RandomInt for every iteration (an input: the reference reads the process-global rand()).  Each of
+ *    the n_iterations hypotheses is the closed-form Horn solve of the three drawn pairs, scored by projecting all N pairs both ways
+ *    (csrc/sim3_ransac_rule.hpp, DESIGN.md section 23: three written rules stand for Eigen::EigenSolver, Sophus::SO3f::exp and
+ *    Eigen's reductions).  The solution is what the sequential loop of iterate() would have returned after running to its end:
+ *    the FIRST hypothesis with more than min_inliers inliers (status CONVERGED, iterations = its index + 1), else the LAST of those
+ *    with the most inliers (NO_MORE, iterations = n_iterations).  n_pairs < min_inliers or n_pairs < 3 (where the reference would
+ *    index out of range) is TOO_FEW: nothing is iterated, T12 and R12 are the identity, t12 = 0, s12 = 1, the mask is cleared.
+ *    Refused before anything is staged, the handle left usable, nothing truncated -- GFS_ERR_CAPACITY: B above max_batch, n_pairs
+ *    above max_pairs, n_iterations above max_iterations; GFS_ERR_INVALID_ARG: a NULL required array, n_pairs < 0, n_iterations < 1
+ *    or a draw outside its range [0, N-1], [0, N-2], [0, N-3] in a problem that iterates.
+ * ============================================================================================ */
+#define GFS_SIM3_RANSAC_CONVERGED 0 /* bConverge */
+#define GFS_SIM3_RANSAC_NO_MORE 1   /* bNoMore after mRansacMaxIts iterations: the best hypothesis, not good enough */
+#define GFS_SIM3_RANSAC_TOO_FEW 2   /* bNoMore at once (:215-218) */
+typedef struct {
+  int32_t n_pairs;                 /* N: pairs that passed the constructor's filter (:73-111) */
+  const float* x3d_c1;             /* [N][3] mvX3Dc1 */
+  const float* x3d_c2;             /* [N][3] mvX3Dc2 */
+  const float* max_err1;           /* [N] mvnMaxError1 as the comparison reads it: (float)(size_t)(9.210 * sigma2) of kp1's level
+                                      (the member is a vector<size_t>, include/Sim3Solver.h:85) */
+  const float* max_err2;           /* [N] the same for kp2 */
+  float fx1, fy1, cx1, cy1, fx2, fy2, cx2, cy2;
+  int32_t fix_scale, min_inliers, n_iterations;   /* n_iterations = mRansacMaxIts after SetRansacParameters */
+  const int32_t* draws;            /* [n_iterations][3] r0, r1, r2 as RandomInt returned them */
+} gfs_sim3_ransac_problem;
+typedef struct {
+  float T12[16], R12[9], t12[3], s12;  /* mBestT12 (row-major), mBestRotation (row-major), mBestTranslation, mBestScale */
+  int32_t n_inliers, iterations, status;   /* GFS_SIM3_RANSAC_CONVERGED / _NO_MORE / _TOO_FEW */
+  uint8_t* inlier;                 /* [N] mask of the returned hypothesis */
+  int32_t* counts;                 /* [n_iterations] (may be NULL) every hypothesis's count, for tests */
+} gfs_sim3_ransac_solution;
+typedef struct gfs_sim3_ransac gfs_sim3_ransac;
+/* SetRansacParameters (:119-143): mRansacMaxIts for n_pairs correspondences, with the host's libm */
+int gfs_sim3_ransac_iterations(int n_pairs, double probability, int min_inliers, int max_iterations);
+int gfs_sim3_ransac_create(int device, int max_batch, int max_pairs, int max_iterations, gfs_sim3_ransac** out);
+int gfs_sim3_ransac_solve(gfs_sim3_ransac* h, const gfs_sim3_ransac_problem* problems, int B, gfs_sim3_ransac_solution* solutions);
+void gfs_sim3_ransac_destroy(gfs_sim3_ransac* h);
+
+/* ============================================================================================
  * Timing helper for the harness: HIP events on a given stream (bench.py measures the dominant kernel
  * with these rather than torch events, which only see torch's current stream).
  * ============================================================================================ */
