@@ -835,7 +835,7 @@ ABI_SYMBOLS = [
     "gfs_hamming256", "gfs_matcher_create", "gfs_matcher_destroy", "gfs_bf_match_hamming",
     "gfs_bf_match_hamming_batch_device",
     "gfs_gicp_default_config", "gfs_gicp_create", "gfs_gicp_destroy", "gfs_gicp_align", "gfs_gicp_align_batch_device",
-    "gfs_gicp_fetch_preprocessed", "gfs_gicp_tile_stats", "gfs_gicp_knn_stats", "gfs_gicp_coop_stats", "gfs_frame_rgbd", "gfs_gicp_align_next", "gfs_gicp_align_next_batch_device", "gfs_test_voxel_sort", "gfs_test_voxel_sort_paths", "gfs_test_wave_std_sort",
+    "gfs_gicp_fetch_preprocessed", "gfs_gicp_tile_stats", "gfs_gicp_knn_stats", "gfs_gicp_coop_stats", "gfs_test_gicp_coop_hold", "gfs_test_gicp_coop_release", "gfs_test_gicp_coop_in_use", "gfs_frame_rgbd", "gfs_gicp_align_next", "gfs_gicp_align_next_batch_device", "gfs_test_voxel_sort", "gfs_test_voxel_sort_paths", "gfs_test_wave_std_sort",
     "gfs_lba_create", "gfs_lba_destroy", "gfs_lba_solve", "gfs_lba_solve_bool", "gfs_lba_linearize", "gfs_lba_batch_create", "gfs_lba_batch_destroy",
     "gfs_lba_solve_batch", "gfs_lba_lidar_reserve", "gfs_lba_solve_lidar", "gfs_lba_solve_lidar_bool", "gfs_lba_linearize_lidar",
     "gfs_lba_fetch_lidar_edges", "gfs_test_lba_stop_at_look", "gfs_test_lba_last_looks", "gfs_test_lba_first_trial",
@@ -931,6 +931,9 @@ def lib():
             L.gfs_gicp_tile_stats.argtypes = [vp, vp, i]
             L.gfs_gicp_knn_stats.argtypes = [vp, i, i, vp, vp, i]
             L.gfs_gicp_coop_stats.argtypes = [vp, vp]
+            L.gfs_test_gicp_coop_hold.argtypes = [vp, i]
+            L.gfs_test_gicp_coop_release.argtypes = [vp, i]
+            L.gfs_test_gicp_coop_in_use.argtypes = [i]
             L.gfs_test_voxel_sort.argtypes = [vp, vp, i, vp]
             L.gfs_test_voxel_sort_paths.argtypes = [vp, vp]
             L.gfs_test_wave_std_sort.argtypes = [i, vp, i, vp]
@@ -1370,6 +1373,15 @@ class RegistrationGICP:
         _check(lib().gfs_gicp_coop_stats(self.h, _p(out)), "gfs_gicp_coop_stats")
         return dict(launches=int(out[0]), last_workgroups=int(out[1]), failed=bool(out[2]), budget=int(out[3]))
 
+    def coop_hold(self, n):
+        """Test hook (gfs_test_gicp_coop_hold): take exactly n workgroups out of the device's cooperative budget, as another handle's
+        launch in flight would; GfsError (GFS_ERR_CAPACITY) when n are not free.  Only coop_release(n) gives them back."""
+        _check(lib().gfs_test_gicp_coop_hold(self.h, int(n)), "gfs_test_gicp_coop_hold")
+
+    def coop_release(self, n):
+        """Test hook (gfs_test_gicp_coop_release): give back n workgroups taken with coop_hold."""
+        _check(lib().gfs_test_gicp_coop_release(self.h, int(n)), "gfs_test_gicp_coop_release")
+
     def knn_stats(self, b, which, cap=256):
         """(points, deferred to the r = 2 pass, deferred to the isolated-point pass), bounds of the latter: gfs_gicp_knn_stats."""
         out = np.zeros(3, np.int32)
@@ -1385,6 +1397,11 @@ class RegistrationGICP:
         _check(lib().gfs_gicp_fetch_preprocessed(self.h, b, which, _p(pts), _p(covs), cap, C.byref(m)),
                "gfs_gicp_fetch_preprocessed")
         return pts[:m.value], covs[:m.value].reshape(-1, 3, 3).transpose(0, 2, 1).copy()
+
+
+def gicp_coop_in_use(device=0):
+    """Test hook (gfs_test_gicp_coop_in_use): workgroups of the device's cooperative budget that are taken right now."""
+    return int(lib().gfs_test_gicp_coop_in_use(device))
 
 
 class Timer:

@@ -3114,6 +3114,7 @@ int gfs_gicp_create(int device, int max_points, int max_batch, gfs_gicp** out) {
 #undef A
   if (!rc) (void)hipMemset(h->d_tile_stats.p, 0, 8 * sizeof(unsigned));
   if (!rc) GFS_HIP(hipMemset(h->d_zero.p, 0, B * sizeof(int)));
+  if (!rc) GFS_HIP(hipStreamSynchronize(nullptr));  // (the fills run on the null stream, which the handle's non-blocking stream does not wait for)
   if (rc) return rc;
   *out = h.release();
   return GFS_OK;
@@ -3515,6 +3516,26 @@ int gfs_gicp_coop_stats(gfs_gicp* h, int out[4]) {
   out[3] = h->coop ? h->coop_cap / 2 : 0;
   return GFS_OK;
 }
+
+// Test hooks (tests/test_gpu_gicp_coop_budget.py): workgroups taken out of the device's CoopBudget as another handle's launch in
+// flight would take them -- all n or none, against the budget gicp_attempt reserves against -- and given back.  Not booked on the
+// handle (its own leases and gfs_gicp_destroy never touch them); no kernel is launched, no lock is taken (coop_cap is set once).
+int gfs_test_gicp_coop_hold(gfs_gicp* h, int n) {
+  GFS_REQUIRE(h && n >= 0, GFS_ERR_INVALID_ARG, "gfs_test_gicp_coop_hold: invalid argument");
+  if (n == 0) return GFS_OK;
+  GFS_REQUIRE(CoopBudget::reserve(h->device, n, n, h->coop_cap / 2) == n, GFS_ERR_CAPACITY,
+              "gfs_test_gicp_coop_hold: %d workgroups are not free (budget %d, in use %d)", n, h->coop_cap / 2,
+              CoopBudget::in_use(h->device).load());
+  return GFS_OK;
+}
+
+int gfs_test_gicp_coop_release(gfs_gicp* h, int n) {
+  GFS_REQUIRE(h && n >= 0, GFS_ERR_INVALID_ARG, "gfs_test_gicp_coop_release: invalid argument");
+  CoopBudget::release(h->device, n);
+  return GFS_OK;
+}
+
+int gfs_test_gicp_coop_in_use(int device) { return CoopBudget::in_use(device).load(); }
 
 int gfs_gicp_knn_stats(gfs_gicp* h, int b, int which, int out[3], double* dk, int cap) {
   GFS_REQUIRE(h && b >= 0 && b < h->last_B && (which == 0 || which == 1) && out, GFS_ERR_INVALID_ARG, "gfs_gicp_knn_stats: invalid argument");

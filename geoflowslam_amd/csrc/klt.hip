@@ -792,6 +792,10 @@ int gfs_klt_pyramid_create(gfs_klt* h, gfs_klt_pyramid** out) {
   if (rc) return rc;
   GFS_HIP(hipMemset(p->img.p, 0, n));
   GFS_HIP(hipMemset(p->deriv.p, 0, n * sizeof(short2)));
+  // hipMemset of device memory returns before the fill has run, and the fill is ordered on the null stream, which the trackers'
+  // non-blocking streams do not wait for: on a busy device it could land AFTER the first build into this pyramid and zero it
+  // (found by tests/test_gpu_concurrent_handles.py: wrong tracks in a few rounds of 200, only with other threads' kernels in flight)
+  GFS_HIP(hipStreamSynchronize(nullptr));
   *out = p.release();
   return GFS_OK;
 }

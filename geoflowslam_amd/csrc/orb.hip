@@ -2422,6 +2422,7 @@ int gfs_orb_create(const gfs_orb_config* cfg, gfs_orb** out) {
   GFS_HIP(hipMemcpy(h->d_umax.p, h->P.umax, 16 * sizeof(int), hipMemcpyHostToDevice));
   GFS_HIP(hipMemcpy(h->d_pattern.p, kPattern, 1024, hipMemcpyHostToDevice));
   GFS_HIP(hipMemset(h->d_kp_count.p, 0, B * sizeof(int)));
+  GFS_HIP(hipStreamSynchronize(nullptr));  // (the fill runs on the null stream, which the handle's non-blocking stream does not wait for)
   h->host_threads = (int)std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
   if (const char* e = getenv("GFS_ORB_HOST_THREADS")) h->host_threads = std::max(1, atoi(e));
   h->pool.reset(new WorkerPool(h->host_threads));

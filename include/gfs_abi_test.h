@@ -92,6 +92,16 @@ int gfs_test_voxel_sort_paths(gfs_gicp* h, int32_t out3[3]);
  * (size, x) list, ORBextractor.cc:697-698) on n <= 1024 caller keys; perm_out[i] = original index of the element left at position i. */
 int gfs_test_wave_std_sort(int device, const unsigned* keys, int n, unsigned short* perm_out);
 
+/* Test hooks (no kernel is launched): the process-wide workgroup budget of the cooperative LM kernel (csrc/gicp.hip CoopBudget), held
+ * as another handle's launch in flight would hold it, so that a test decides how many workgroups the next call of a handle is granted.
+ * gfs_test_gicp_coop_hold takes exactly n workgroups of h's device out of the budget h's own calls reserve against (half of what the
+ * device holds at once: out[3] of gfs_gicp_coop_stats), or none and GFS_ERR_CAPACITY when n are not free.  They are NOT booked on the
+ * handle: only gfs_test_gicp_coop_release(h, n) gives them back, and the caller must (a budget left held makes every later call of
+ * the process run its launch-per-step rounds).  gfs_test_gicp_coop_in_use = workgroups of the device's budget that are taken now. */
+int gfs_test_gicp_coop_hold(gfs_gicp* h, int n);
+int gfs_test_gicp_coop_release(gfs_gicp* h, int n);
+int gfs_test_gicp_coop_in_use(int device);
+
 /* GPU test hook: a map's search grid as the association kernels read it -- the bucket offsets start[nb + 1] and the bucket-sorted
  * points pts[n][3] with their map-index words index[n] (copied when the caps suffice); *nb, *n = the map's sizes. */
 int gfs_test_lidar_map_grid(const gfs_lidar_map* map, int32_t* start, int cap_start, float* pts, int32_t* index, int cap_pts, int32_t* nb,

@@ -199,3 +199,38 @@ def test_huge_and_infinite_coordinates(gpu_api, oracle):
     assert g[2] == o[2] and np.array_equal(g[1], o[1]) and not g[1][:6].any() and g[1][6:].all()
     ok = g[1]
     assert np.array_equal(_bits(g[0][ok]), _bits(o[0][ok]))
+
+
+def test_a_pyramid_created_while_the_null_stream_is_busy(gpu_api, oracle):
+    """gfs_klt_pyramid_create zero-fills the new pyramid with hipMemset, which runs on the null stream and returns before the fill has
+    run; the tracker's stream is non-blocking and does not wait for it.  With 4 GiB of fills queued on the null stream in front
+    (another thread's work, here made by the test through the same HIP runtime), a pyramid that is built right after it was created
+    must still hold the frame: pyramids and tracks bit-exact.  (Before gfs_klt_pyramid_create waited for its own fills they
+    landed after the build and zeroed it; tests/test_gpu_concurrent_handles.py met that in a few rounds of 200.)"""
+    from test_gpu_gms import _Hip
+    w, h, win = 160, 120, 15
+    i0, i1, _ = synth.klt_texture_pair(3, w, h, shift=(1.0, 0.5))
+    trk = gpu_api.KltTracker(w, h, win, max_batch=1, max_points=64)
+    o0, o1 = oracle.klt_build_pyramid(i0, win), oracle.klt_build_pyramid(i1, win)
+    kps = _points(np.random.default_rng(0), 24, w, h, 10.0)
+    want = oracle.fb_klt_tracking(o0, o1, w, h, win, 3, 15.0, 0.5, kps, kps.copy())
+    hip = _Hip()
+    hip.lib.hipMemset.argtypes = [C.c_void_p, C.c_int, C.c_size_t]
+    big = C.c_void_p()
+    assert hip.lib.hipMalloc(C.byref(big), 1 << 30) == 0
+    hip.ptrs.append(big)
+    try:
+        for _ in range(4):
+            assert hip.lib.hipMemset(big, 0, 1 << 30) == 0  # (device memory: queued on the null stream, the call does not wait)
+        p0 = trk.buildOpticalFlowPyramid(i0)  # creates the pyramid, then builds into it on the tracker's stream
+        for _ in range(4):
+            assert hip.lib.hipMemset(big, 0, 1 << 30) == 0
+        p1 = trk.buildOpticalFlowPyramid(i1)
+        got = trk.fbKltTracking(p0, p1, 3, 15.0, 0.5, kps, kps.copy())
+        for pyr, (oi, od) in ((p0, o0), (p1, o1)):
+            gi, gd = pyr.download(0)
+            assert np.array_equal(gi, oi) and np.array_equal(gd, od)
+        assert got[2] == want[2] > 0 and np.array_equal(got[1], want[1]) and np.array_equal(_bits(got[0][got[1]]), _bits(want[0][want[1]]))
+    finally:
+        assert hip.lib.hipDeviceSynchronize() == 0
+        hip.free()

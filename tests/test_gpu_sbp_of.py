@@ -136,14 +136,15 @@ def _reference_transcription(O, g0, g1, win, keys_last, has_mp, bad, outl, xw, k
     return good, t3, t2, mask
 
 
-@pytest.mark.gpu
-@pytest.mark.parametrize("seed", [3, 8])
-def test_search_by_projection_with_of(harness, gpu_api, oracle, seed):
+def of_case(harness, gpu_api, oracle, seed, n_last=None):
+    """The adaptor and the transcription on the frame pair of `seed` (the first n_last key points of frame 0, or all of them) ->
+    (k0, (good, n3, n2, o3, i3, o2, i2, mask) of the adaptor, (good, tracked 3-D list, tracked 2-D list, mask) of the transcription)."""
     W, H, WIN = 320, 240, 21
     fp = synth.frame_pair(seed, W, H, 4)
     orb = oracle.OrbOracle(600, 1.2, 6, 20, 7)
     _, k0, _ = orb.extract(fp["gray0"])
     _, k1, _ = orb.extract(fp["gray1"])
+    k0 = k0 if n_last is None else np.ascontiguousarray(k0[:n_last])
     k1 = k1[::3]                                 # the current frame already has some key points (they seed the mask)
     rng = np.random.default_rng(seed)
     n = len(k0)
@@ -175,10 +176,24 @@ def test_search_by_projection_with_of(harness, gpu_api, oracle, seed):
                                outl.ctypes.data, xw.ctypes.data, len(k1c), k1c.ctypes.data, q.ctypes.data, t.ctypes.data, K8.ctypes.data,
                                F_THR, DIST, mask.ctypes.data, o3.ctypes.data, i3.ctypes.data, C.addressof(n3), o2.ctypes.data,
                                i2.ctypes.data, C.addressof(n2))
-    assert good == want_good and n3.value == len(w3) and n2.value == len(w2)
-    assert want_good > 50 and len(w3) > 20 and len(w2) > 3
+    return k0, (good, n3.value, n2.value, o3, i3, o2, i2, mask), (want_good, w3, w2, wmask)
+
+
+def assert_of_equal(k0, got, want):
+    good, n3, n2, o3, i3, o2, i2, mask = got
+    want_good, w3, w2, wmask = want
+    assert good == want_good and n3 == len(w3) and n2 == len(w2)
     for (got_k, got_i, want) in ((o3, i3, w3), (o2, i2, w2)):
         for j, (i, x, y) in enumerate(want):
             assert got_i[j] == i and got_k[j]["x"] == x and got_k[j]["y"] == y           # bit-exact positions
             assert got_k[j]["octave"] == k0[i]["octave"] and got_k[j]["angle"] == k0[i]["angle"]   # "the other properties as before"
     assert np.array_equal(mask, wmask)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("seed", [3, 8])
+def test_search_by_projection_with_of(harness, gpu_api, oracle, seed):
+    k0, got, want = of_case(harness, gpu_api, oracle, seed)
+    want_good, w3, w2, _ = want
+    assert want_good > 50 and len(w3) > 20 and len(w2) > 3
+    assert_of_equal(k0, got, want)
