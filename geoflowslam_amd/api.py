@@ -369,6 +369,31 @@ class FuseResult(C.Structure):
     _fields_ = [("exit", C.c_void_p), ("best_idx", C.c_void_p), ("best_dist", C.c_void_p), ("level", C.c_void_p), ("n_matched", C.c_int32)]
 
 
+def _fill_search_keyframe(K, src, arrays):
+    """The fields gfs_fuse_keyframe and gfs_sim3_search_problem share, from the dict src: the pointers of `arrays` (named as the
+    struct's fields), the pose, the intrinsics and image bounds, the level count, the key-point count and the list index."""
+    for name, v in arrays.items():
+        setattr(K, name, v.ctypes.data)
+    for name in ("Tcw_q", "Tcw_t", "Ow"):
+        getattr(K, name)[:] = [float(np.float32(v)) for v in np.asarray(src[name]).reshape(-1)]
+    for name in ("fx", "fy", "cx", "cy", "min_x", "max_x", "min_y", "max_y", "grid_w_inv", "grid_h_inv", "log_scale_factor", "th"):
+        setattr(K, name, float(np.float32(src[name])))
+    K.n_levels = int(src.get("n_levels", len(arrays["scale_factors"])))
+    K.n_kp = len(arrays["kps_un"])
+    K.list = int(src.get("list", 0))
+
+
+def _prefilled_results(R, n_mp):
+    """Points a gfs_fuse_result at arrays for n_mp points, pre-filled with a pattern no output has -> the arrays by field name."""
+    n = max(n_mp, 1)
+    out = dict(exit=np.full(n, 0xEE, np.uint8), best_idx=np.full(n, -9, np.int32), best_dist=np.full(n, -9, np.int32),
+               level=np.full(n, -9, np.int32))
+    for name, v in out.items():
+        setattr(R, name, v.ctypes.data)
+    R.n_matched = -9
+    return out
+
+
 def fuse_structs(lists, keyframes):
     """ctypes views of one gfs_fuse_search call (shared with the CPU restatement's tests: same layout).  lists: dicts with the keys
     of gfs_fuse_points; keyframes: dicts with the keys of gfs_fuse_keyframe (kps_un = KP_DTYPE array; `list` defaults to 0)
@@ -393,22 +418,9 @@ def fuse_structs(lists, keyframes):
                  kps_un=np.ascontiguousarray(kf["kps_un"], KP_DTYPE), u_right=np.ascontiguousarray(kf["u_right"], np.float32),
                  desc=np.ascontiguousarray(kf["desc"], np.uint8).reshape(-1, 32))
         K = KK[f]
-        for name, v in a.items():
-            setattr(K, name, v.ctypes.data)
-        for name in ("Tcw_q", "Tcw_t", "Ow"):
-            getattr(K, name)[:] = [float(np.float32(v)) for v in np.asarray(kf[name]).reshape(-1)]
-        for name in ("fx", "fy", "cx", "cy", "bf", "min_x", "max_x", "min_y", "max_y", "grid_w_inv", "grid_h_inv", "log_scale_factor", "th"):
-            setattr(K, name, float(np.float32(kf[name])))
-        K.n_levels = int(kf.get("n_levels", len(a["scale_factors"])))
-        K.n_kp = len(a["kps_un"])
-        K.list = int(kf.get("list", 0))
-        n = max(LL[K.list].n_mp, 1) if 0 <= K.list < nl else 1
-        out = dict(exit=np.full(n, 0xEE, np.uint8), best_idx=np.full(n, -9, np.int32), best_dist=np.full(n, -9, np.int32),
-                   level=np.full(n, -9, np.int32))
-        for name, v in out.items():
-            setattr(RR[f], name, v.ctypes.data)
-        RR[f].n_matched = -9
-        a.update(out)
+        _fill_search_keyframe(K, kf, a)
+        K.bf = float(np.float32(kf["bf"]))
+        a.update(_prefilled_results(RR[f], LL[K.list].n_mp if 0 <= K.list < nl else 0))
         keep.append(a)
     return LL, KK, RR, keep
 
@@ -455,26 +467,12 @@ def sim3_search_structs(lists, problems):
             if pr.get(name) is not None:
                 a[name] = np.ascontiguousarray(pr[name], np.uint8)
         K = PP[f]
-        for name, v in a.items():
-            setattr(K, name, v.ctypes.data)
-        for name in ("Tcw_q", "Tcw_t", "Ow"):
-            getattr(K, name)[:] = [float(np.float32(v)) for v in np.asarray(pr[name]).reshape(-1)]
-        for name in ("fx", "fy", "cx", "cy", "min_x", "max_x", "min_y", "max_y", "grid_w_inv", "grid_h_inv", "log_scale_factor", "th"):
-            setattr(K, name, float(np.float32(pr[name])))
+        _fill_search_keyframe(K, pr, a)
         K.mode = int(pr["mode"])
         K.ratio_hamming = float(np.float32(pr.get("ratio_hamming", 1.0)))
-        K.n_levels = int(pr.get("n_levels", len(a["scale_factors"])))
-        K.n_kp = len(a["kps_un"])
-        K.list = int(pr.get("list", 0))
-        n = max(LL[K.list].n_mp, 1) if 0 <= K.list < nl else 1
         assert "kp_taken" not in a or len(a["kp_taken"]) == K.n_kp, "kp_taken must have one byte per key-point"
         assert "mp_skip" not in a or not (0 <= K.list < nl) or len(a["mp_skip"]) == LL[K.list].n_mp, "mp_skip must have one byte per listed point"
-        out = dict(exit=np.full(n, 0xEE, np.uint8), best_idx=np.full(n, -9, np.int32), best_dist=np.full(n, -9, np.int32),
-                   level=np.full(n, -9, np.int32))
-        for name, v in out.items():
-            setattr(RR[f], name, v.ctypes.data)
-        RR[f].n_matched = -9
-        a.update(out)
+        a.update(_prefilled_results(RR[f], LL[K.list].n_mp if 0 <= K.list < nl else 0))
         keep.append(a)
     return LL, PP, RR, keep
 

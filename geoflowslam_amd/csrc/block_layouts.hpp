@@ -58,14 +58,21 @@ struct LocalLayout {
   Field<int> level{out, M}, index{out, NL}, match{out, NC}, nm{out, B};
 };
 
+// The point block of gfs_fuse_search and gfs_sim3_search (point_search.hpp stages it): the T points of all lists
+struct PointListFields {
+  Block<256>& pts;
+  size_t T;
+  Field<float, 3> xw{pts, T}, nrm{pts, T};
+  Field<float> dmin{pts, T}, dmax{pts, T};
+  Field<uint8_t, 32> desc{pts, T};
+};
+
 // gfs_fuse_search (fuse.hip): T points of all lists, B key frames of SC key-points, O result slots -- three blocks
 template <class Problem>
 struct FuseLayout {
   size_t T, B, SC, O;
   Block<256> pts, kf, out;
-  Field<float, 3> xw{pts, T}, nrm{pts, T};
-  Field<float> dmin{pts, T}, dmax{pts, T};
-  Field<uint8_t, 32> desc{pts, T};
+  PointListFields p{pts, T};
   Field<Problem> problems{kf, B};
   Field<xy_t> xy{kf, B * SC};
   Field<float> ur{kf, B * SC};
@@ -80,9 +87,7 @@ template <class Problem>
 struct Sim3SearchLayout {
   size_t T, B, SC, O, OC;
   Block<256> pts, kf, out;
-  Field<float, 3> xw{pts, T}, nrm{pts, T};
-  Field<float> dmin{pts, T}, dmax{pts, T};
-  Field<uint8_t, 32> desc{pts, T};
+  PointListFields p{pts, T};
   Field<Problem> problems{kf, B};
   Field<xy_t> xy{kf, B * SC};
   Field<uint8_t> oct{kf, B * SC};  // the octave, bit 7 = the key-point is taken at entry

@@ -34,15 +34,6 @@ struct BowSlot {  // one (key frame 1, key frame 2)
   int check_orientation;
 };
 
-__device__ __forceinline__ int bow_find_node(const int* __restrict__ ids, int n, int id) {
-  int lo = 0, hi = n;
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (ids[mid] < id) lo = mid + 1; else hi = mid;
-  }
-  return (lo < n && ids[lo] == id) ? lo : -1;
-}
-
 struct Desc {
   uint4 a, b;
 };
@@ -76,7 +67,7 @@ __global__ __launch_bounds__(kBowThreads) void k_bow_search(const uint8_t* __res
   const uint8_t *has1 = in + F1.o_hasmp, *has2 = in + F2.o_hasmp, *desc1 = in + F1.o_desc, *desc2 = in + F2.o_desc;
   // ---- the search: the merge loop of :964-1034, a node per wave
   for (int node = wave; node < F1.n_nodes; node += kBowWaves) {
-    const int j = bow_find_node(nid2, F2.n_nodes, nid1[node]);
+    const int j = gfs::find_node(nid2, F2.n_nodes, nid1[node]);
     if (j < 0) continue;
     const int b1 = ns1[node], n1 = ns1[node + 1] - b1, b2 = ns2[j], n2 = ns2[j + 1] - b2;
     if (n1 <= 0 || n2 <= 0) continue;
@@ -183,24 +174,7 @@ int validate_kf(const gfs_bow_keyframe& k, int max_cur, const char* what, int b,
   GFS_REQUIRE(k.n_kp == 0 || (k.angle && k.desc && k.has_mp), GFS_ERR_INVALID_ARG, "gfs_search_by_bow: problem %d %s %d has NULL key-point arrays", b,
               what, i);
   GFS_REQUIRE(k.node_start && (k.n_nodes == 0 || k.node_id), GFS_ERR_INVALID_ARG, "gfs_search_by_bow: problem %d %s %d has NULL node arrays", b, what, i);
-  GFS_REQUIRE(k.node_start[0] == 0, GFS_ERR_INVALID_ARG, "gfs_search_by_bow: problem %d %s %d: node_start[0] != 0", b, what, i);
-  for (int n = 0; n < k.n_nodes; n++) {
-    GFS_REQUIRE(n == 0 || k.node_id[n] > k.node_id[n - 1], GFS_ERR_INVALID_ARG, "gfs_search_by_bow: problem %d %s %d: node ids not ascending at %d", b,
-                what, i, n);
-    GFS_REQUIRE(k.node_start[n + 1] >= k.node_start[n] && k.node_start[n + 1] <= k.n_kp, GFS_ERR_INVALID_ARG,
-                "gfs_search_by_bow: problem %d %s %d: node_start not a prefix sum within n_kp at %d", b, what, i, n);
-  }
-  const int nf = k.node_start[k.n_nodes];
-  GFS_REQUIRE(nf == 0 || k.feat_idx, GFS_ERR_INVALID_ARG, "gfs_search_by_bow: problem %d %s %d has a NULL feature list", b, what, i);
-  seen.assign((size_t)k.n_kp, 0);
-  for (int p = 0; p < nf; p++) {
-    const int f = k.feat_idx[p];
-    GFS_REQUIRE(f >= 0 && f < k.n_kp, GFS_ERR_INVALID_ARG, "gfs_search_by_bow: problem %d %s %d: feature index %d outside [0, %d)", b, what, i, f,
-                k.n_kp);
-    GFS_REQUIRE(!seen[f], GFS_ERR_INVALID_ARG, "gfs_search_by_bow: problem %d %s %d: feature index %d listed twice", b, what, i, f);
-    seen[f] = 1;
-  }
-  return GFS_OK;
+  return gfs::check_feature_vector("gfs_search_by_bow", k, what, b, i, seen);
 }
 
 // takes a key frame's arrays from the staging block's cursor, copies them there and fills its device header

@@ -2,17 +2,15 @@
 // const vector<MapPoint*>&, th) (reference src/ORBmatcher.cc:1378-1548), the search of every listed map point (DESIGN.md section 13;
 // the rule itself is fuse_rule.hpp, shared with the host).
 // Grid (ceil(n / 256), B), blockIdx.y = the (list, key frame) problem.  Every workgroup builds its key frame's 64 x 48 grid in LDS
-// as k_sbp does (cell starts + the items sorted by cell, cells in index order), with position, mvuRight and octave of the key-points
-// next to it and the level tables in the header; then a lane owns one map point: projection, gates, PredictScale, the window walked
-// as the runs of its grid columns (a cell is ix * kGridRows + iy, so the cells iy = y0 .. y1 of one column are one contiguous run of
-// s_items), four items at a time with the descriptors of the survivors fetched together.  No point competes with another for a
-// key-point, so nothing is resolved across lanes: no global atomics, no waiting between workgroups.
+// (load_keyframe_grid_lds, sbp_dev.hpp: cell starts + the items sorted by cell, cells in index order), with position, mvuRight and
+// octave of the key-points next to it and the level tables in the header; then a lane owns one map point: projection, gates,
+// PredictScale and the walk of its window (walk_window, sbp_dev.hpp).  No point competes with another for a key-point, so nothing is
+// resolved across lanes: no global atomics, no waiting between workgroups.
 // LDS: 6 146 (cell starts) + 8 192 (items) + 3 x 16 384 (x, y, mvuRight) + 4 096 (octave) + the header = 67.8 KB, two workgroups a CU
 // (160 KB).  The cell counters of the build (12 KB) live in the mvuRight table, which is filled after the grid is built; the cell
 // of a key-point is recomputed from its position instead of kept.
 
-#include "fuse_rule.hpp"
-#include "sbp_handle.hpp"
+#include "point_search.hpp"
 
 using namespace gfs;
 
@@ -53,18 +51,8 @@ __global__ __launch_bounds__(kFuseThreads) void k_fuse(const FuseProblem* __rest
   const gfs_fuse::KeyFrame& K = s_P.K;
   const int N = K.n_kp;
   const size_t kf_at = (size_t)f * SC;
-  for (int i = tid; i < N; i += kFuseThreads) {
-    const float2 p = kf_xy[kf_at + i];
-    s_kx[i] = p.x;
-    s_ky[i] = p.y;
-    s_oct[i] = kf_oct[kf_at + i];
-  }
-  auto cell_of = [&](int i) {  // Frame::PosInGrid
-    const int px = (int)roundf((s_kx[i] - K.min_x) * K.grid_w_inv), py = (int)roundf((s_ky[i] - K.min_y) * K.grid_h_inv);
-    return (px >= 0 && px < kGridCols && py >= 0 && py < kGridRows) ? px * kGridRows + py : -1;
-  };
-  // ---- the grid; the counters are done with when it stands: their table becomes mvuRight
-  build_grid_lds<kFuseThreads>(N, cell_of, s_start, s_items, s_cnt, s_scan);
+  // ---- the key-points and the grid; the counters are done with when it stands: their table becomes mvuRight
+  load_keyframe_grid_lds<kFuseThreads>(K, N, kf_xy + kf_at, kf_oct + kf_at, s_kx, s_ky, s_oct, s_start, s_items, s_cnt, s_scan);
   for (int i = tid; i < N; i += kFuseThreads) s_ur[i] = kf_ur[kf_at + i];
   __syncthreads();
   // ---- a lane per map point
@@ -76,51 +64,21 @@ __global__ __launch_bounds__(kFuseThreads) void k_fuse(const FuseProblem* __rest
   const gfs_fuse::Proj R = gfs_fuse::project(K, P, Pn, mp_min[at], mp_max[at]);
   int best_dist = 256, best_idx = -1, ex = R.exit;
   if (R.exit < 0) {
-    const uint4* dl = reinterpret_cast<const uint4*>(mp_desc + 32 * at);
-    const uint4 a0 = dl[0], a1 = dl[1];
-    const uint8_t* kd = kf_desc + 32 * kf_at;
-    bool any = false, more = true;
-    int ix = R.x0;
-    int k = s_start[ix * kGridRows + R.y0], kend = s_start[ix * kGridRows + R.y1 + 1];
-    auto next_item = [&]() {  // the next key-point index of the window in visiting order, or -1
-      while (more && k >= kend) {
-        if (++ix > R.x1) {
-          more = false;
-          break;
-        }
-        k = s_start[ix * kGridRows + R.y0];
-        kend = s_start[ix * kGridRows + R.y1 + 1];
-      }
-      return more ? (int)s_items[k++] : -1;
-    };
-    while (more) {
-      int j[4];
-      bool pass[4];
-      uint4 b0[4], b1[4];
-#pragma unroll
-      for (int u = 0; u < 4; u++) {
-        j[u] = next_item();
-        pass[u] = false;
-        if (j[u] < 0) continue;
-        const float kx = s_kx[j[u]], ky = s_ky[j[u]];
-        if (!gfs_fuse::in_window(R, kx, ky)) continue;
-        any = true;
-        if (!gfs_fuse::candidate_ok(K, R, kx, ky, s_ur[j[u]], (int)s_oct[j[u]])) continue;
-        pass[u] = true;
-        const uint4* dc = reinterpret_cast<const uint4*>(kd + 32 * (size_t)j[u]);
-        b0[u] = dc[0];
-        b1[u] = dc[1];
-      }
-#pragma unroll
-      for (int u = 0; u < 4; u++) {
-        if (!pass[u]) continue;
-        const int d = hamming256(a0, a1, b0[u], b1[u]);
-        if (d < best_dist) {  // strict: the first visited of equal distances wins
-          best_dist = d;
-          best_idx = j[u];
-        }
-      }
-    }
+    bool any = false;
+    walk_window(
+        R.x0, R.x1, R.y0, R.y1, s_start, s_items, mp_desc + 32 * at, kf_desc + 32 * kf_at,
+        [&](int j) {
+          const float kx = s_kx[j], ky = s_ky[j];
+          if (!gfs_fuse::in_window(R, kx, ky)) return false;
+          any = true;
+          return gfs_fuse::candidate_ok(K, R, kx, ky, s_ur[j], (int)s_oct[j]);
+        },
+        [&](int j, int d) {
+          if (d < best_dist) {  // strict: the first visited of equal distances wins
+            best_dist = d;
+            best_idx = j;
+          }
+        });
     ex = gfs_fuse::search_exit(any, best_dist);
   }
   o_exit[to] = (uint8_t)ex;
@@ -133,11 +91,7 @@ using Layout = gfs::FuseLayout<FuseProblem>;
 
 }  // namespace
 
-// The point lists, the key frames (headers + key-point arrays) and the per-point results, each one pinned block mirrored by one device block
-struct gfs_fuse_workspace : gfs_sbp_workspace {
-  int lists = 0, points = 0, kfs = 0;
-  gfs::Mirror pts, kf, out;
-};
+struct gfs_fuse_workspace : gfs::PointSearchWorkspace {};
 
 extern "C" {
 
@@ -150,18 +104,13 @@ int gfs_sbp_reserve_fuse(gfs_sbp* h, int max_lists, int max_points_per_list, int
   const Layout Y{SP * max_lists, (size_t)max_keyframes, SC, SP * max_keyframes};
   h->fuse.reset();
   std::unique_ptr<gfs_fuse_workspace> w(new gfs_fuse_workspace);
-  int rc = w->pts.alloc(Y.pts.bytes());
-  if (!rc) rc = w->kf.alloc(Y.kf.bytes());
-  if (!rc) rc = w->out.alloc(Y.out.bytes());
-  if (rc) return rc;
-  w->lists = max_lists;
-  w->points = max_points_per_list;
-  w->kfs = max_keyframes;
+  if (int rc = w->alloc(Y.pts.bytes(), Y.kf.bytes(), Y.out.bytes(), max_lists, max_points_per_list, max_keyframes)) return rc;
   h->fuse = std::move(w);
   return GFS_OK;
 }
 
 int gfs_fuse_search(gfs_sbp* h, const gfs_fuse_points* lists, int n_lists, const gfs_fuse_keyframe* kfs, int B, gfs_fuse_result* results) {
+  static const char who[] = "gfs_fuse_search", what[] = "key frame";
   GFS_REQUIRE(h && lists && kfs && results && n_lists > 0 && B > 0, GFS_ERR_INVALID_ARG, "gfs_fuse_search: invalid argument");
   std::lock_guard<std::mutex> lk(h->mu);
   gfs_fuse_workspace* w = static_cast<gfs_fuse_workspace*>(h->fuse.get());
@@ -172,100 +121,50 @@ int gfs_fuse_search(gfs_sbp* h, const gfs_fuse_points* lists, int n_lists, const
   // every refusal comes before anything is staged
   size_t T = 0, O = 0, SC = 64;
   int n_max = 0;
-  std::vector<size_t> list_base((size_t)n_lists);
-  for (int l = 0; l < n_lists; l++) {
-    const gfs_fuse_points& L = lists[l];
-    GFS_REQUIRE(L.n_mp >= 0 && L.n_mp <= w->points, GFS_ERR_CAPACITY, "gfs_fuse_search: list %d has %d map points (reserve %d)", l,
-                L.n_mp, w->points);
-    GFS_REQUIRE(L.n_mp == 0 || (L.mp_xw && L.mp_normal && L.mp_min_dist && L.mp_max_dist && L.mp_desc), GFS_ERR_INVALID_ARG,
-                "gfs_fuse_search: list %d has NULL arrays", l);
-    list_base[l] = T;
-    T += gfs::align_up((size_t)L.n_mp, 64);
-  }
+  std::vector<size_t> list_base;
+  if (int rc = check_point_lists(who, lists, n_lists, w->points, list_base, &T)) return rc;
   for (int f = 0; f < B; f++) {
     const gfs_fuse_keyframe& k = kfs[f];
-    GFS_REQUIRE(k.n_kp >= 0 && k.n_kp <= h->max_cur, GFS_ERR_CAPACITY, "gfs_fuse_search: key frame %d has %d key-points (capacity %d)", f,
-                k.n_kp, h->max_cur);
-    GFS_REQUIRE(k.n_levels > 0 && k.n_levels <= 16 && k.scale_factors && k.inv_level_sigma2, GFS_ERR_INVALID_ARG,
-                "gfs_fuse_search: key frame %d needs 1..16 scale factors and inverse level variances", f);
-    GFS_REQUIRE(k.list >= 0 && k.list < n_lists, GFS_ERR_INVALID_ARG, "gfs_fuse_search: key frame %d names list %d of %d", f, k.list, n_lists);
+    if (int rc = check_search_kf_head(who, what, f, k, h->max_cur, k.scale_factors && k.inv_level_sigma2, "scale factors and inverse level variances", n_lists))
+      return rc;
     GFS_REQUIRE(k.n_kp == 0 || (k.kps_un && k.u_right && k.desc), GFS_ERR_INVALID_ARG, "gfs_fuse_search: key frame %d has NULL key-point arrays", f);
     const int n = lists[k.list].n_mp;
-    GFS_REQUIRE(n == 0 || (results[f].exit && results[f].best_idx && results[f].best_dist && results[f].level), GFS_ERR_INVALID_ARG,
-                "gfs_fuse_search: key frame %d has NULL result arrays", f);
-    for (int i = 0; i < k.n_kp; i++)
-      GFS_REQUIRE(k.kps_un[i].octave >= 0 && k.kps_un[i].octave < k.n_levels, GFS_ERR_INVALID_ARG,
-                  "gfs_fuse_search: key frame %d key-point %d has octave %d outside [0, %d)", f, i, k.kps_un[i].octave, k.n_levels);
+    if (int rc = check_search_kf_tail(who, what, f, k, n, results[f])) return rc;
     SC = std::max(SC, gfs::align_up((size_t)k.n_kp, 64));
     O += gfs::align_up((size_t)n, 64);
     n_max = std::max(n_max, n);
   }
   const Layout Y{T, (size_t)B, SC, O};  // within the reserve: T <= lists x SP, O <= B x SP, SC <= max_cur
-  uint8_t *hp = w->pts.h.p, *hk = w->kf.h.p;
-  for (int l = 0; l < n_lists; l++) {
-    const gfs_fuse_points& L = lists[l];
-    const size_t at = list_base[l], n = (size_t)L.n_mp;
-    Y.xw.put(hp, at, L.mp_xw, n);
-    Y.nrm.put(hp, at, L.mp_normal, n);
-    Y.dmin.put(hp, at, L.mp_min_dist, n);
-    Y.dmax.put(hp, at, L.mp_max_dist, n);
-    Y.desc.put(hp, at, L.mp_desc, n);
-  }
+  uint8_t* hk = w->kf.h.p;
+  stage_point_lists(Y.p, w->pts.h.p, lists, n_lists, list_base);
   std::vector<size_t> out_base((size_t)B);
   size_t o_at = 0;
   for (int f = 0; f < B; f++) {
     const gfs_fuse_keyframe& k = kfs[f];
     FuseProblem& Q = Y.problems.at(hk)[f];
     memset(&Q, 0, sizeof(Q));
-    for (int c = 0; c < 4; c++) Q.K.q[c] = k.Tcw_q[c];
-    for (int c = 0; c < 3; c++) {
-      Q.K.t[c] = k.Tcw_t[c];
-      Q.K.Ow[c] = k.Ow[c];
-    }
-    Q.K.fx = k.fx;
-    Q.K.fy = k.fy;
-    Q.K.cx = k.cx;
-    Q.K.cy = k.cy;
+    fill_search_keyframe(Q.K, k);
     Q.K.bf = k.bf;
-    Q.K.min_x = k.min_x;
-    Q.K.max_x = k.max_x;
-    Q.K.min_y = k.min_y;
-    Q.K.max_y = k.max_y;
-    Q.K.grid_w_inv = k.grid_w_inv;
-    Q.K.grid_h_inv = k.grid_h_inv;
-    Q.K.log_scale_factor = k.log_scale_factor;
-    Q.K.th = k.th;
-    Q.K.n_levels = k.n_levels;
-    Q.K.n_kp = k.n_kp;
-    for (int c = 0; c < k.n_levels; c++) {
-      Q.K.scale[c] = k.scale_factors[c];
-      Q.K.inv_sigma2[c] = k.inv_level_sigma2[c];
-    }
+    for (int c = 0; c < k.n_levels; c++) Q.K.inv_sigma2[c] = k.inv_level_sigma2[c];
     Q.n_mp = lists[k.list].n_mp;
     Q.list_base = (int)list_base[k.list];
     Q.out_base = (int)o_at;
     out_base[f] = o_at;
     o_at += gfs::align_up((size_t)Q.n_mp, 64);
-    float2* xy = Y.xy.at(hk, (size_t)f * SC);
-    uint8_t* oct = Y.oct.at(hk, (size_t)f * SC);
-    for (int i = 0; i < k.n_kp; i++) {
-      xy[i] = make_float2(k.kps_un[i].x, k.kps_un[i].y);
-      oct[i] = (uint8_t)k.kps_un[i].octave;
-    }
+    stage_xy_oct(k.kps_un, k.n_kp, Y.xy.at(hk, (size_t)f * SC), Y.oct.at(hk, (size_t)f * SC));
     Y.ur.put(hk, (size_t)f * SC, k.u_right, (size_t)k.n_kp);
     Y.kdesc.put(hk, (size_t)f * SC, k.desc, (size_t)k.n_kp);
   }
   if (n_max > 0) {
-    hipStream_t s = h->stream;
     const uint8_t *dp = w->pts.d.p, *dk = w->kf.d.p;
     uint8_t* dq = w->out.d.p;
-    if (int rc = w->pts.upload(s, 0, Y.pts.bytes())) return rc;
-    if (int rc = w->kf.upload(s, 0, Y.kf.bytes())) return rc;
-    GFS_LAUNCH("k_fuse", k_fuse, dim3((n_max + kFuseThreads - 1) / kFuseThreads, B), dim3(kFuseThreads), 0, s, Y.problems.at(dk), Y.xw.at(dp),
-               Y.nrm.at(dp), Y.dmin.at(dp), Y.dmax.at(dp), Y.desc.at(dp), Y.xy.at(dk), Y.ur.at(dk), Y.oct.at(dk), Y.kdesc.at(dk), (int)SC,
-               Y.exit.at(dq), Y.idx.at(dq), Y.dist.at(dq), Y.level.at(dq));
-    if (int rc = w->out.download(s, 0, Y.out.bytes())) return rc;
-    GFS_HIP(hipStreamSynchronize(s));  // the call's one synchronisation
+    const int rc = w->run(h->stream, Y.pts.bytes(), Y.kf.bytes(), Y.out.bytes(), [&]() -> int {
+      GFS_LAUNCH("k_fuse", k_fuse, dim3((n_max + kFuseThreads - 1) / kFuseThreads, B), dim3(kFuseThreads), 0, h->stream, Y.problems.at(dk),
+                 Y.p.xw.at(dp), Y.p.nrm.at(dp), Y.p.dmin.at(dp), Y.p.dmax.at(dp), Y.p.desc.at(dp), Y.xy.at(dk), Y.ur.at(dk), Y.oct.at(dk),
+                 Y.kdesc.at(dk), (int)SC, Y.exit.at(dq), Y.idx.at(dq), Y.dist.at(dq), Y.level.at(dq));
+      return GFS_OK;
+    });
+    if (rc) return rc;
   }
   const uint8_t* ho = w->out.h.p;
   for (int f = 0; f < B; f++) {

@@ -113,68 +113,33 @@ struct SbpCur {
   const uint8_t* has_obs;
 };
 
-// GetFeaturesInArea + the static filters of the candidate loop, in the reference's visiting order (ix, iy, cell order).
+// GetFeaturesInArea + the static filters of the candidate loop, in the reference's visiting order (walk_window, sbp_dev.hpp).
 // f(i2, dist) is called for every candidate that survives them; returns whether vIndices2 was non-empty.
-// A cell is c = ix * kGridRows + iy and the items are stored by cell, so the cells iy = y0 .. y1 of one grid column are ONE
-// contiguous run of s_items: a window is x1 - x0 + 1 runs (<= 13 for the largest radius), not (x1 - x0 + 1) (y1 - y0 + 1) cells of
-// which two thirds are empty.  The items are walked four at a time: their fields come from LDS, the descriptors of the survivors
-// are fetched together -- one round trip to memory per four items, for the survivors only.
 template <class F>
 __device__ __forceinline__ bool sbp_candidates(const SbpPair& P, const SbpView& V, const SbpCur& C, const Proj& R, int l,
                                                const unsigned short* s_start, const unsigned short* s_items, F&& f) {
   const bool bCheckLevels = (R.minLevel > 0) || (R.maxLevel >= 0);
   bool any = false;
-  const uint4* dl = reinterpret_cast<const uint4*>(V.last_desc + 32 * (size_t)l);
-  const uint4 a0 = dl[0], a1 = dl[1];
-  int ix = R.x0;
-  int k = s_start[ix * kGridRows + R.y0], kend = s_start[ix * kGridRows + R.y1 + 1];
-  bool more = true;
-  auto next_item = [&]() {  // the next key-point index of the window in visiting order, or -1
-    while (more && k >= kend) {
-      if (++ix > R.x1) {
-        more = false;
-        break;
-      }
-      k = s_start[ix * kGridRows + R.y0];
-      kend = s_start[ix * kGridRows + R.y1 + 1];
-    }
-    return more ? (int)s_items[k++] : -1;
-  };
-  while (more) {
-    int i2[4];
-    bool pass[4];
-    uint4 b0[4], b1[4];
-#pragma unroll
-    for (int u = 0; u < 4; u++) {
-      i2[u] = next_item();
-      pass[u] = false;
-      if (i2[u] < 0) continue;
-      const int j = i2[u];
-      if (bCheckLevels) {
-        const int oct = C.oct[j];
-        if (oct < R.minLevel) continue;
-        if (R.maxLevel >= 0 && oct > R.maxLevel) continue;
-      }
-      const float distx = C.x[j] - R.u, disty = C.y[j] - R.v;
-      if (!(fabsf(distx) < R.radius && fabsf(disty) < R.radius)) continue;
-      any = true;
-      if (C.has_obs[j]) continue;  // a map point with observations was there on entry: never replaced
-      const float ur2 = C.ur[j];
-      if (ur2 > 0) {
-        const float er = fabsf(R.ur - ur2);
-        if (er > R.ur_gate) continue;
-      }
-      pass[u] = true;
-      const uint4* dc = reinterpret_cast<const uint4*>(V.cur_desc + 32 * (size_t)j);
-      b0[u] = dc[0];
-      b1[u] = dc[1];
-    }
-#pragma unroll
-    for (int u = 0; u < 4; u++)
-      if (pass[u])
-        f(i2[u], __popc(a0.x ^ b0[u].x) + __popc(a0.y ^ b0[u].y) + __popc(a0.z ^ b0[u].z) + __popc(a0.w ^ b0[u].w) + __popc(a1.x ^ b1[u].x) +
-                     __popc(a1.y ^ b1[u].y) + __popc(a1.z ^ b1[u].z) + __popc(a1.w ^ b1[u].w));
-  }
+  walk_window(
+      R.x0, R.x1, R.y0, R.y1, s_start, s_items, V.last_desc + 32 * (size_t)l, V.cur_desc,
+      [&](int j) {
+        if (bCheckLevels) {
+          const int oct = C.oct[j];
+          if (oct < R.minLevel) return false;
+          if (R.maxLevel >= 0 && oct > R.maxLevel) return false;
+        }
+        const float distx = C.x[j] - R.u, disty = C.y[j] - R.v;
+        if (!(fabsf(distx) < R.radius && fabsf(disty) < R.radius)) return false;
+        any = true;
+        if (C.has_obs[j]) return false;  // a map point with observations was there on entry: never replaced
+        const float ur2 = C.ur[j];
+        if (ur2 > 0) {
+          const float er = fabsf(R.ur - ur2);
+          if (er > R.ur_gate) return false;
+        }
+        return true;
+      },
+      f);
   return any;
 }
 
@@ -241,65 +206,19 @@ __global__ __launch_bounds__(kSbpThreads) void k_sbp(const SbpPair* __restrict__
   for (int c = tid; c < kCells; c += kSbpThreads) s_cnt[c] = 0;
   if (tid < kHisto) s_hist[tid] = 0;
   __syncthreads();
-  for (int i = tid; i < N; i += kSbpThreads) {
+  for (int i = tid; i < N; i += kSbpThreads) {  // (the cell count of build_grid_lds, fused with the loads)
     const gfs_keypoint kp = V.cur_kp[i];
-    const int px = (int)roundf((kp.x - P.min_x) * P.grid_w_inv), py = (int)roundf((kp.y - P.min_y) * P.grid_h_inv);
-    const bool in = px >= 0 && px < kGridCols && py >= 0 && py < kGridRows;
-    s_cell[i] = in ? (unsigned short)(px * kGridRows + py) : (unsigned short)0xffff;
+    const int c = pos_in_grid(P, kp.x, kp.y);
+    s_cell[i] = (unsigned short)c;  // 0xffff outside the grid
     s_state[i] = -1;
     s_oct[i] = (uint8_t)kp.octave;
     s_kx[i] = kp.x;
     s_ky[i] = kp.y;
     s_ur[i] = V.cur_ur[i];
     s_ho[i] = V.cur_has_obs[i];
-    if (in) atomicAdd(&s_cnt[px * kGridRows + py], 1);
+    if (c >= 0) atomicAdd(&s_cnt[c], 1);
   }
-  __syncthreads();
-  {
-    constexpr int per = kCells / kSbpThreads;  // 3 (3072 cells over 1024 threads)
-    int cnt[per], local = 0;
-#pragma unroll
-    for (int k = 0; k < per; k++) {
-      cnt[k] = s_cnt[tid * per + k];
-      local += cnt[k];
-    }
-    int incl = local;  // exclusive scan over the threads: shuffles inside the wave, the sixteen wave totals through LDS
-#pragma unroll
-    for (int ofs = 1; ofs < 64; ofs <<= 1) {
-      const int v = __shfl_up(incl, ofs, 64);
-      if (lane >= ofs) incl += v;
-    }
-    if (lane == 63) s_scan[tid >> 6] = incl;
-    __syncthreads();
-    int run = incl - local;
-    for (int w = 0; w < (tid >> 6); w++) run += s_scan[w];
-#pragma unroll
-    for (int k = 0; k < per; k++) {
-      s_start[tid * per + k] = (unsigned short)run;
-      s_cnt[tid * per + k] = 0;  // now the fill counter of the cell
-      run += cnt[k];
-    }
-    if (tid == kSbpThreads - 1) s_start[kCells] = (unsigned short)run;
-  }
-  __syncthreads();
-  for (int i = tid; i < N; i += kSbpThreads) {  // into the cell in arrival order ...
-    const unsigned short c = s_cell[i];
-    if (c == 0xffff) continue;
-    s_items[s_start[c] + atomicAdd(&s_cnt[c], 1)] = (unsigned short)i;
-  }
-  __syncthreads();
-  for (int c = tid; c < kCells; c += kSbpThreads) {  // ... then every cell in index order (a handful of items: insertion sort)
-    const int b = s_start[c], e = s_start[c + 1];
-    for (int a = b + 1; a < e; a++) {
-      const unsigned short v = s_items[a];
-      int q = a;
-      while (q > b && s_items[q - 1] > v) {
-        s_items[q] = s_items[q - 1];
-        q--;
-      }
-      s_items[q] = v;
-    }
-  }
+  grid_from_counts_lds<kSbpThreads>(N, [&](int i) { return s_cell[i] == 0xffff ? -1 : (int)s_cell[i]; }, s_start, s_items, s_cnt, s_scan);
   const SbpCur Cur{s_kx, s_ky, s_oct, s_ur, s_ho};
   // twc = Tcw.inverse().translation(); tlc = Tlw * twc  (se3.hpp:208-211; the SO3 constructor re-normalises the conjugate)
   float qi[4] = {-P.Tcw_q[0], -P.Tcw_q[1], -P.Tcw_q[2], P.Tcw_q[3]};
@@ -313,7 +232,6 @@ __global__ __launch_bounds__(kSbpThreads) void k_sbp(const SbpPair* __restrict__
   so3_act(P.Tlw_q, twc, tlc);
   for (int k = 0; k < 3; k++) tlc[k] += P.Tlw_t[k];
   const bool bForward = tlc[2] > P.b && !P.mono, bBackward = -tlc[2] > P.b && !P.mono;
-  __syncthreads();
   SBP_T(1)
   // ---- A. candidates of every map point (parallel)
   for (int l = tid; l < NL; l += kSbpThreads) {

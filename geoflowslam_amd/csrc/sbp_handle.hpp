@@ -1,8 +1,9 @@
-// The gfs_sbp handle as sbp.hip, local_points.hip, fuse.hip and triangulate.hip see it: device, stream, lock and capacities, the
+// The gfs_sbp handle as sbp.hip, local_points.hip, fuse.hip, sim3_search.hip, triangulate.hip and bow_search.hip see it: device, stream, lock and capacities, the
 // staging of gfs_search_by_projection*, and one slot per feature that reserves a workspace of its own (defined in the feature's file,
 // allocated by its gfs_sbp_reserve_*, freed with the handle).
 #pragma once
 #include <memory>
+#include <vector>
 
 #include "block_layouts.hpp"
 #include "sbp_dev.hpp"
@@ -51,6 +52,28 @@ void sbp_map_pair(SbpPair& S, const Problem& p, int n_last) {
   S.grid_h_inv = p.grid_h_inv;
   S.th = p.th;
   for (int k = 0; k < 16; k++) S.scale[k] = k < p.n_levels ? p.scale_factors[k] : 0.f;
+}
+// ---- triangulate.hip and bow_search.hip: a key frame's feature vector (gfs_tri_keyframe, gfs_bow_keyframe) ----
+// From the node arrays on (the caller has checked the counts and that they are not NULL): node_start begins at 0 and is a prefix sum
+// within n_kp, the node ids ascend, every listed feature is a key-point and is listed once.  `seen` is scratch.
+template <class KF>
+int check_feature_vector(const char* who, const KF& k, const char* what, int b, int i, std::vector<uint8_t>& seen) {
+  GFS_REQUIRE(k.node_start[0] == 0, GFS_ERR_INVALID_ARG, "%s: problem %d %s %d: node_start[0] != 0", who, b, what, i);
+  for (int n = 0; n < k.n_nodes; n++) {
+    GFS_REQUIRE(n == 0 || k.node_id[n] > k.node_id[n - 1], GFS_ERR_INVALID_ARG, "%s: problem %d %s %d: node ids not ascending at %d", who, b, what, i, n);
+    GFS_REQUIRE(k.node_start[n + 1] >= k.node_start[n] && k.node_start[n + 1] <= k.n_kp, GFS_ERR_INVALID_ARG,
+                "%s: problem %d %s %d: node_start not a prefix sum within n_kp at %d", who, b, what, i, n);
+  }
+  const int nf = k.node_start[k.n_nodes];
+  GFS_REQUIRE(nf == 0 || k.feat_idx, GFS_ERR_INVALID_ARG, "%s: problem %d %s %d has a NULL feature list", who, b, what, i);
+  seen.assign((size_t)k.n_kp, 0);
+  for (int p = 0; p < nf; p++) {
+    const int f = k.feat_idx[p];
+    GFS_REQUIRE(f >= 0 && f < k.n_kp, GFS_ERR_INVALID_ARG, "%s: problem %d %s %d: feature index %d outside [0, %d)", who, b, what, i, f, k.n_kp);
+    GFS_REQUIRE(!seen[f], GFS_ERR_INVALID_ARG, "%s: problem %d %s %d: feature index %d listed twice", who, b, what, i, f);
+    seen[f] = 1;
+  }
+  return GFS_OK;
 }
 // copies frame f's key-point arrays into the pinned input block
 void sbp_stage_cur(gfs_sbp* h, const SbpBlocks& Y, int f, int n_cur, const gfs_keypoint* kps, const float* u_right, const uint8_t* desc,

@@ -52,15 +52,6 @@ struct TriProb {
   float th_far, ratio_factor;
 };
 
-__device__ __forceinline__ int find_node(const int* __restrict__ ids, int n, int id) {
-  int lo = 0, hi = n;
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (ids[mid] < id) lo = mid + 1; else hi = mid;
-  }
-  return (lo < n && ids[lo] == id) ? lo : -1;
-}
-
 // bit 0: not out by the entry state (no map point; stereo when only_stereo), bit 1: stereo
 __device__ __forceinline__ int kp_flags(const uint8_t* __restrict__ in, const TriFrame& F, int i, int only_stereo) {
   const bool st = reinterpret_cast<const float*>(in + F.o_ur)[i] >= 0;
@@ -82,7 +73,7 @@ __global__ __launch_bounds__(kCandThreads) void k_tri_candidates(const uint8_t* 
   const int node = blockIdx.x, tid = threadIdx.x;
   if (node >= F1.n_nodes) return;  // (uniform: the grid is sized by the call's longest node list)
   const int off = pair_off[S.pair_at + node];
-  const int j = find_node(reinterpret_cast<const int*>(in + F2.o_nid), F2.n_nodes, reinterpret_cast<const int*>(in + F1.o_nid)[node]);
+  const int j = gfs::find_node(reinterpret_cast<const int*>(in + F2.o_nid), F2.n_nodes, reinterpret_cast<const int*>(in + F1.o_nid)[node]);
   if (j < 0 || off < 0) return;  // (the host's merge, which laid the matrices out, and this search agree)
   const int only_stereo = probs[S.problem].only_stereo;
   const bool coarse = probs[S.problem].coarse != 0;
@@ -201,7 +192,7 @@ __global__ __launch_bounds__(kResThreads) void k_tri_resolve(const uint8_t* __re
     for (int node = wave; node < F1.n_nodes; node += kResWaves) {
       const int off = pair_off[S.pair_at + node];
       if (off < 0) continue;
-      const int j = find_node(nid2, F2.n_nodes, nid1[node]);
+      const int j = gfs::find_node(nid2, F2.n_nodes, nid1[node]);
       if (j < 0) continue;
       const int b1 = ns1[node], n1 = ns1[node + 1] - b1, b2 = ns2[j], n2 = ns2[j + 1] - b2;
       const int* feat1 = feat1_all + b1;
@@ -307,24 +298,7 @@ int validate_kf(const gfs_tri_keyframe& k, int max_cur, const char* what, int b,
     GFS_REQUIRE(k.kps_un[p].octave >= 0 && k.kps_un[p].octave < k.n_levels, GFS_ERR_INVALID_ARG,
                 "gfs_create_new_map_points: problem %d %s %d key-point %d has octave %d outside [0, %d)", b, what, i, p, k.kps_un[p].octave,
                 k.n_levels);
-  GFS_REQUIRE(k.node_start[0] == 0, GFS_ERR_INVALID_ARG, "gfs_create_new_map_points: problem %d %s %d: node_start[0] != 0", b, what, i);
-  for (int n = 0; n < k.n_nodes; n++) {
-    GFS_REQUIRE(n == 0 || k.node_id[n] > k.node_id[n - 1], GFS_ERR_INVALID_ARG, "gfs_create_new_map_points: problem %d %s %d: node ids not ascending at %d",
-                b, what, i, n);
-    GFS_REQUIRE(k.node_start[n + 1] >= k.node_start[n] && k.node_start[n + 1] <= k.n_kp, GFS_ERR_INVALID_ARG,
-                "gfs_create_new_map_points: problem %d %s %d: node_start not a prefix sum within n_kp at %d", b, what, i, n);
-  }
-  const int nf = k.node_start[k.n_nodes];
-  GFS_REQUIRE(nf == 0 || k.feat_idx, GFS_ERR_INVALID_ARG, "gfs_create_new_map_points: problem %d %s %d has a NULL feature list", b, what, i);
-  seen.assign((size_t)k.n_kp, 0);
-  for (int p = 0; p < nf; p++) {
-    const int f = k.feat_idx[p];
-    GFS_REQUIRE(f >= 0 && f < k.n_kp, GFS_ERR_INVALID_ARG, "gfs_create_new_map_points: problem %d %s %d: feature index %d outside [0, %d)", b, what, i,
-                f, k.n_kp);
-    GFS_REQUIRE(!seen[f], GFS_ERR_INVALID_ARG, "gfs_create_new_map_points: problem %d %s %d: feature index %d listed twice", b, what, i, f);
-    seen[f] = 1;
-  }
-  return GFS_OK;
+  return gfs::check_feature_vector("gfs_create_new_map_points", k, what, b, i, seen);
 }
 
 // takes a key frame's arrays from the staging block's cursor, copies them there and fills its device header

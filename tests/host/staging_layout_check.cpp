@@ -94,7 +94,7 @@ int main() {
           o.f("level", Y.level, M, o_level).f("index", Y.index, n3 * B, o_index).f("match", Y.match, n2 * B, o_match).f("nm", Y.nm, B, o_nm);
           o.total(Y.out.bytes(), out_bytes);
         }
-        for (size_t O : {n2, 2 * n2 + 1}) {  // fuse.hip: T = n1 points, B key frames of SC = n2 key-points, O slots
+        for (size_t O : {n2, 2 * n2 + 1}) {  // fuse.hip: T = n1 points, B key frames of SC = n2 key-points, O slots; then sim3_search.hip
           using Q = Hdr<228>;
           const FuseLayout<Q> Y{n1, B, n2, O};
           const size_t T = n1, SC = n2;
@@ -104,13 +104,28 @@ int main() {
                        kf_bytes = k_desc + up(B * SC * 32);
           const size_t o_idx = up(O), o_dist = o_idx + up(O * 4), o_level = o_dist + up(O * 4), out_bytes = o_level + up(O * 4);
           Walk p("fuse.pts", 256);
-          p.f("xw", Y.xw, T, 0).f("nrm", Y.nrm, T, p_nrm).f("dmin", Y.dmin, T, p_min).f("dmax", Y.dmax, T, p_max).f("desc", Y.desc, T, p_desc);
+          p.f("xw", Y.p.xw, T, 0).f("nrm", Y.p.nrm, T, p_nrm).f("dmin", Y.p.dmin, T, p_min).f("dmax", Y.p.dmax, T, p_max).f("desc", Y.p.desc, T, p_desc);
           p.total(Y.pts.bytes(), pts_bytes);
           Walk k("fuse.kf", 256);
           k.f("problems", Y.problems, B, 0).f("xy", Y.xy, B * SC, k_xy).f("ur", Y.ur, B * SC, k_ur).f("oct", Y.oct, B * SC, k_oct);
           k.f("kdesc", Y.kdesc, B * SC, k_desc).total(Y.kf.bytes(), kf_bytes);
           Walk o("fuse.out", 256);
           o.f("exit", Y.exit, O, 0).f("idx", Y.idx, O, o_idx).f("dist", Y.dist, O, o_dist).f("level", Y.level, O, o_level).total(Y.out.bytes(), out_bytes);
+          // sim3_search.hip: the same point block; the key frames without mvuRight; O slots and OC = 3 O + 1 listed candidates
+          const size_t OC = 3 * O + 1;
+          const Sim3SearchLayout<Q> Z{n1, B, n2, O, OC};
+          const size_t z_oct = k_xy + up(B * SC * 8), z_desc = z_oct + up(B * SC), z_kf_bytes = z_desc + up(B * SC * 32);
+          const size_t z_level = up(O), z_count = z_level + up(O * 4), z_cidx = z_count + up(O * 4), z_cdist = z_cidx + up(OC * 4),
+                       z_out_bytes = z_cdist + up(OC * 4);
+          Walk zp("sim3_search.pts", 256);
+          zp.f("xw", Z.p.xw, T, 0).f("nrm", Z.p.nrm, T, p_nrm).f("dmin", Z.p.dmin, T, p_min).f("dmax", Z.p.dmax, T, p_max).f("desc", Z.p.desc, T, p_desc);
+          zp.total(Z.pts.bytes(), pts_bytes);
+          Walk zk("sim3_search.kf", 256);
+          zk.f("problems", Z.problems, B, 0).f("xy", Z.xy, B * SC, k_xy).f("oct", Z.oct, B * SC, z_oct).f("kdesc", Z.kdesc, B * SC, z_desc);
+          zk.total(Z.kf.bytes(), z_kf_bytes);
+          Walk zo("sim3_search.out", 256);
+          zo.f("exit", Z.exit, O, 0).f("level", Z.level, O, z_level).f("count", Z.count, O, z_count).f("cidx", Z.cidx, OC, z_cidx);
+          zo.f("cdist", Z.cdist, OC, z_cdist).total(Z.out.bytes(), z_out_bytes);
         }
         {  // triangulate.hip: B problems, n1 slots, n1 + B frames, n2 matrix offsets, then a key frame of n1 key-points, n2 nodes, n2 features
           using Pr = Hdr<40>;

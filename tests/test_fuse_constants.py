@@ -91,7 +91,7 @@ def test_constants_in_restatement_rule_and_adaptor():
     assert re.search(r"best_dist (\S+) kThLow \? kMatched : kNoCandidate", rule).group(1) == g["match_test"]
     hip = open(os.path.join(ROOT, "geoflowslam_amd", "csrc", "fuse.hip")).read()
     k = hip[hip.index("void k_fuse("):hip.index("}  // namespace")]
-    assert "gfs_fuse::project(K, P, Pn, mp_min[at], mp_max[at])" in k and "gfs_fuse::candidate_ok(K, R, kx, ky, s_ur[j[u]], (int)s_oct[j[u]])" in k
+    assert "gfs_fuse::project(K, P, Pn, mp_min[at], mp_max[at])" in k and "gfs_fuse::candidate_ok(K, R, kx, ky, s_ur[j], (int)s_oct[j])" in k
     assert re.search(r"if \(d (\S+) best_dist\) \{", k).group(1) == g["best_test"] and "gfs_fuse::search_exit(any, best_dist)" in k
     # the adaptor acts on the device's verdict and on nothing else
     ada = open(os.path.join(ROOT, "geoflowslam_amd", "host", "gfs_adaptors.hpp")).read()

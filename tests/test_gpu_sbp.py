@@ -15,10 +15,33 @@ CASES = [dict(seed=1), dict(seed=2, dup_frac=0.3, zero_obs_frac=0.3, preassigned
          dict(seed=7, motion=-0.3, rot_deg=2.0), dict(seed=8, th=3.0, desc_flip_bits=60)]
 
 
-@pytest.mark.parametrize("cfg", CASES)
+def full_table_pair():
+    """The current frame fills k_sbp's LDS tables: n_cur = 4096, the key-points the 2000 map points do not account for are extra."""
+    seen = len(synth.sbp_pair(9, n_points=2000, n_extra_cur=0)["cur_kps_un"])  # (the extra ones are drawn after these)
+    p = synth.sbp_pair(9, n_points=2000, n_extra_cur=4096 - seen)
+    assert len(p["cur_kps_un"]) == 4096 and len(p["last_xw"]) == 2000
+    return p
+
+
+def one_cell_pair():
+    """Every key-point of the current frame in ONE grid cell (the longest per-cell insertion sort the grid build can meet), apart from
+    40 outside the grid (cell -1: never a candidate).  The image shrinks towards its centre into cell (32, 24) of 10 x 10 pixels; a
+    wide th lets the windows of most map points reach that cell, so the map points compete for the key-points in it."""
+    p = synth.sbp_pair(10, n_points=500, n_extra_cur=140, th=60.0, mono=True)
+    k = p["cur_kps_un"].copy()
+    k["x"] = np.float32(320.0) + (k["x"] - np.float32(320.0)) * np.float32(4.0 / 320.0)
+    k["y"] = np.float32(240.0) + (k["y"] - np.float32(240.0)) * np.float32(4.0 / 240.0)
+    cell = np.stack([np.round(k["x"] / np.float32(10.0)), np.round(k["y"] / np.float32(10.0))], 1)
+    assert (cell == [32, 24]).all()
+    out = np.arange(0, len(k), len(k) // 40)[:40]
+    k["x"][out[0::4]], k["x"][out[1::4]], k["y"][out[2::4]], k["y"][out[3::4]] = -30.0, 700.0, -30.0, 520.0
+    return dict(p, cur_kps_un=k)
+
+
+@pytest.mark.parametrize("cfg", CASES + [full_table_pair, one_cell_pair], ids=lambda c: c.__name__ if callable(c) else None)
 def test_single_pair_matches_oracle(gpu_api, oracle, cfg):
-    p = synth.sbp_pair(**cfg)
-    pm = gpu_api.ProjectionMatcher(max_last=2048, max_cur=2560, max_batch=2)
+    p = cfg() if callable(cfg) else synth.sbp_pair(**cfg)
+    pm = gpu_api.ProjectionMatcher(max_last=2048, max_cur=max(2560, len(p["cur_kps_un"])), max_batch=2)
     m, n = pm.SearchByProjection(p)
     mo, no = oracle.search_by_projection(p)
     assert n == no

@@ -105,9 +105,9 @@ def test_constants_in_rule_restatement_and_kernel():
     # ---- the kernel and the entry's replay
     hip = open(os.path.join(csrc, "sim3_search.hip")).read()
     k = hip[hip.index("void k_sim3_search("):hip.index("using Layout")]
-    assert "gfs_sim3::project(K, mode, P, Pn, mp_min[at], mp_max[at])" in k and "gfs_fuse::in_window(R, s_kx[j[u]], s_ky[j[u]])" in k
-    assert 0 < k.index("if (o & kTakenBit) continue;") < k.index("if (!gfs_sim3::level_ok(R, o)) continue;")
-    assert "const int first = gfs_sim3::first_best_dist(mode)" in k and "if (d >= first) continue;" in k
+    assert "gfs_sim3::project(K, mode, P, Pn, mp_min[at], mp_max[at])" in k and "gfs_fuse::in_window(R, s_kx[j], s_ky[j])" in k
+    assert 0 < k.index("if (o & kTakenBit) return false;") < k.index("return gfs_sim3::level_ok(R, o);")  # (the walk's gate)
+    assert "const int first = gfs_sim3::first_best_dist(mode)" in k and "if (d >= first) return;" in k
     assert re.search(r"if \(d (\S+) c_dist\[kListed - 1\]\) \{", k).group(1) == g["sbp"]["best_test"]
     assert re.search(r"if \(c_dist\[s\] (\S+) c_dist\[s - 1\]\) \{", k).group(1) == g["sbp"]["best_test"]
     entry = hip[hip.index("int gfs_sim3_search("):]
