@@ -690,6 +690,62 @@ def bow_results(PP, RP, keep, B):
     return res
 
 
+class BowVocabularyStruct(C.Structure):  # gfs_bow_vocabulary
+    _fields_ = [("k", C.c_int32), ("L", C.c_int32), ("scoring", C.c_int32), ("weighting", C.c_int32), ("n_nodes", C.c_int32),
+                ("parent", C.c_void_p), ("child_start", C.c_void_p), ("children", C.c_void_p), ("desc", C.c_void_p), ("weight", C.c_void_p),
+                ("word_id", C.c_void_p)]
+
+
+class BowVectors(C.Structure):  # gfs_bow_vectors
+    _fields_ = [("n_words", C.c_int32), ("word_id", C.c_void_p), ("word_value", C.c_void_p), ("n_nodes", C.c_int32), ("node_id", C.c_void_p),
+                ("node_start", C.c_void_p), ("feat_idx", C.c_void_p), ("word_of_feature", C.c_void_p)]
+
+
+def bow_vocabulary_struct(vocab):
+    """vocab: dict(k, L, scoring, weighting, parent, child_start, children, desc [n_nodes, 32], weight, word_id) -> (struct, keep)"""
+    i32 = lambda a: np.ascontiguousarray(a, np.int32)
+    keep = dict(parent=i32(vocab["parent"]), child_start=i32(vocab["child_start"]), children=i32(vocab["children"]),
+                desc=np.ascontiguousarray(vocab["desc"], np.uint8).reshape(-1, 32), weight=np.ascontiguousarray(vocab["weight"], np.float64),
+                word_id=i32(vocab["word_id"]))
+    V = BowVocabularyStruct(int(vocab["k"]), int(vocab["L"]), int(vocab.get("scoring", 0)), int(vocab.get("weighting", 0)),
+                            int(vocab.get("n_nodes", len(keep["word_id"]))))
+    for k, a in keep.items():
+        setattr(V, k, a.ctypes.data)
+    return V, keep
+
+
+def bow_frames(descs):
+    """one descriptor array [n, 32] or a list of them -> (single, [contiguous uint8 [n, 32]])"""
+    single = isinstance(descs, np.ndarray)
+    return single, [np.ascontiguousarray(d, np.uint8).reshape(-1, 32) for d in ([descs] if single else list(descs))]
+
+
+def bow_vectors_alloc(B, cap, with_words=True):
+    """B gfs_bow_vectors with arrays of `cap` entries (node_start cap + 1) -> (array of structs, keep)"""
+    VV, keep = (BowVectors * max(B, 1))(), []
+    for b in range(B):
+        k = dict(word_id=np.full(cap, -7, np.int32), word_value=np.full(cap, np.nan), node_id=np.full(cap, -7, np.int32),
+                 node_start=np.full(cap + 1, -7, np.int32), feat_idx=np.full(cap, -7, np.int32),
+                 word_of_feature=np.full(cap, -7, np.int32) if with_words else None)
+        for name, a in k.items():
+            setattr(VV[b], name, a.ctypes.data if a is not None else None)
+        keep.append(k)
+    return VV, keep
+
+
+def bow_vectors_results(VV, keep, counts):
+    """-> per frame dict(word_id, word_value, node_id, node_start, feat_idx, word_of_feature): the BowVector in ascending word id, the
+    FeatureVector in the layout of gfs_bow_keyframe, the word id of every feature (-1 when stopped)"""
+    out = []
+    for b, k in enumerate(keep):
+        nw, nn = VV[b].n_words, VV[b].n_nodes
+        m = int(k["node_start"][nn])
+        out.append(dict(word_id=k["word_id"][:nw].copy(), word_value=k["word_value"][:nw].copy(), node_id=k["node_id"][:nn].copy(),
+                        node_start=k["node_start"][:nn + 1].copy(), feat_idx=k["feat_idx"][:m].copy(),
+                        word_of_feature=None if k["word_of_feature"] is None or counts is None else k["word_of_feature"][:counts[b]].copy()))
+    return out
+
+
 def sbp_map_struct(prob):
     P = SbpMapProblem()
     keep = dict(mp_proj=np.ascontiguousarray(prob["mp_proj"], np.float32).reshape(-1, 3),
@@ -858,6 +914,8 @@ ABI_SYMBOLS = [
     "gfs_sbp_reserve_sim3_search", "gfs_sim3_search", "gfs_test_sim3_search_groups",
     "gfs_sbp_reserve_triangulation", "gfs_create_new_map_points", "gfs_sbp_reserve_bow", "gfs_search_by_bow",
     "gfs_map_points_create", "gfs_map_points_destroy", "gfs_map_points_update",
+    "gfs_bow_create", "gfs_bow_destroy", "gfs_bow_transform", "gfs_bow_transform_device",
+    "gfs_bow_db_create", "gfs_bow_db_destroy", "gfs_bow_db_add", "gfs_bow_db_erase", "gfs_bow_db_query",
     "gfs_klt_create", "gfs_klt_destroy", "gfs_klt_layout", "gfs_klt_pyramid_create", "gfs_klt_pyramid_destroy",
     "gfs_klt_build_pyramid", "gfs_klt_build_pyramid_device", "gfs_klt_pyramid_download", "gfs_klt_track", "gfs_klt_fb_track",
     "gfs_klt_fb_track_device",
@@ -977,6 +1035,17 @@ def lib():
             L.gfs_sim3_ransac_create.argtypes = [i, i, i, i, C.POINTER(vp)]
             L.gfs_sim3_ransac_destroy.argtypes = [vp]
             L.gfs_sim3_ransac_solve.argtypes = [vp, vp, i, vp]
+        L.gfs_bow_create.argtypes = [i, C.POINTER(BowVocabularyStruct), i, i, C.POINTER(vp)]
+        L.gfs_bow_destroy.argtypes = [vp]
+        L.gfs_bow_destroy.restype = None
+        L.gfs_bow_transform.argtypes = [vp, C.POINTER(vp), vp, i, i, C.POINTER(BowVectors)]
+        L.gfs_bow_transform_device.argtypes = [vp, vp, vp, i, i, i, C.POINTER(BowVectors)]
+        L.gfs_bow_db_create.argtypes = [i, i, i, C.POINTER(vp)]
+        L.gfs_bow_db_destroy.argtypes = [vp]
+        L.gfs_bow_db_destroy.restype = None
+        L.gfs_bow_db_add.argtypes = [vp, i, i, vp, vp]
+        L.gfs_bow_db_erase.argtypes = [vp, i]
+        L.gfs_bow_db_query.argtypes = [vp, i, vp, vp, vp, vp, vp]
         if hasattr(L, "gfs_lba_solve_lidar"):
             L.gfs_lba_lidar_reserve.argtypes = [vp, i]
             L.gfs_lba_solve_lidar.argtypes = [vp, C.POINTER(LbaProblem), C.POINTER(LbaLidar), C.POINTER(LbaSolution), vp, vp]
@@ -2399,6 +2468,86 @@ class Sim3RansacSolver:
         _check(lib().gfs_sim3_ransac_solve(self.h, PP, B, SS), "gfs_sim3_ransac_solve")
         res = [sim3_ransac_result(SS[f], *keeps[f]) for f in range(B)]
         return res[0] if single else res
+
+
+class BowVocabulary:
+    """DBoW2::TemplatedVocabulary::transform(features, BowVector&, FeatureVector&, levelsup) (TF_IDF, L1_NORM) as KeyFrame::ComputeBoW and
+    Frame::ComputeBoW call it, for any number of frames in one device call (gfs_bow_* in include/gfs_abi.h; DESIGN.md section 24).
+    vocab_dict: the tree as gfs_bow_vocabulary lays it out (synth.bow_vocabulary builds one); it is validated, repacked and uploaded."""
+
+    def __init__(self, vocab_dict, max_batch=8, max_features=2048, device=0):
+        self.h = C.c_void_p()
+        self.max_features = int(max_features)
+        V, keep = bow_vocabulary_struct(vocab_dict)
+        _check(lib().gfs_bow_create(device, C.byref(V), int(max_batch), int(max_features), C.byref(self.h)), "gfs_bow_create")
+
+    def close(self):
+        if getattr(self, "h", None) and _lib is not None:
+            _lib.gfs_bow_destroy(self.h)
+        self.h = None
+
+    __del__ = close
+
+    def transform(self, descs, levelsup=4):
+        """descs: one uint8 array [n, 32] or a list of them -> result dict(s) (bow_vectors_results).  Raises GfsError (code
+        GFS_ERR_CAPACITY / GFS_ERR_INVALID_ARG) on a refusal; the handle stays usable."""
+        single, frames = bow_frames(descs)
+        B = len(frames)
+        ptrs = (C.c_void_p * max(B, 1))(*[f.ctypes.data for f in frames])
+        n = np.array([len(f) for f in frames], np.int32)
+        VV, keep = bow_vectors_alloc(B, self.max_features)
+        _check(lib().gfs_bow_transform(self.h, ptrs, _p(n), B, int(levelsup), VV), "gfs_bow_transform")
+        res = bow_vectors_results(VV, keep, n)
+        return res[0] if single else res
+
+    def transform_device(self, dev_desc, dev_counts, stride, B, levelsup=4, counts=None):
+        """The same on descriptors in HBM as ORBextractor.device_results() leaves them ([B][stride][32] u8, [B] int32 counts); counts:
+        the host's copy of the counts where it has one (word_of_feature is cut to it, else left out)."""
+        VV, keep = bow_vectors_alloc(B, self.max_features)
+        _check(lib().gfs_bow_transform_device(self.h, C.c_void_p(dev_desc), C.c_void_p(dev_counts), int(stride), int(B), int(levelsup), VV),
+               "gfs_bow_transform_device")
+        return bow_vectors_results(VV, keep, counts)
+
+
+class BowDatabase:
+    """The numeric core of KeyFrameDatabase::DetectNBestCandidates (reference src/KeyFrameDatabase.cc:596-645): a fixed-stride store of
+    BowVectors, one slot per key frame, and the query of one BowVector against all of them (gfs_bow_db_* in include/gfs_abi.h)."""
+
+    def __init__(self, max_entries=1024, max_words=2048, device=0):
+        self.h = C.c_void_p()
+        self.max_entries = int(max_entries)
+        _check(lib().gfs_bow_db_create(device, int(max_entries), int(max_words), C.byref(self.h)), "gfs_bow_db_create")
+
+    def close(self):
+        if getattr(self, "h", None) and _lib is not None:
+            _lib.gfs_bow_db_destroy(self.h)
+        self.h = None
+
+    __del__ = close
+
+    @staticmethod
+    def _vector(word_id, word_value):
+        ids, vals = np.ascontiguousarray(word_id, np.int32).ravel(), np.ascontiguousarray(word_value, np.float64).ravel()
+        if len(ids) != len(vals):
+            raise ValueError("BowDatabase: word_id and word_value differ in length")
+        return ids, vals
+
+    def add(self, slot, word_id, word_value):
+        ids, vals = self._vector(word_id, word_value)
+        _check(lib().gfs_bow_db_add(self.h, int(slot), len(ids), _p(ids), _p(vals)), "gfs_bow_db_add")
+
+    def erase(self, slot):
+        _check(lib().gfs_bow_db_erase(self.h, int(slot)), "gfs_bow_db_erase")
+
+    def query(self, word_id, word_value):
+        """-> dict(n_common, first_word, score), each [max_entries]: mnPlaceRecognitionWords, the lowest common word id (-1: none) and
+        (float)L1Scoring::score of every slot against the query"""
+        ids, vals = self._vector(word_id, word_value)
+        out = dict(n_common=np.full(self.max_entries, -7, np.int32), first_word=np.full(self.max_entries, -7, np.int32),
+                   score=np.full(self.max_entries, np.nan, np.float32))
+        _check(lib().gfs_bow_db_query(self.h, len(ids), _p(ids), _p(vals), _p(out["n_common"]), _p(out["first_word"]), _p(out["score"])),
+               "gfs_bow_db_query")
+        return out
 
 
 class LidarMap:

@@ -19,11 +19,13 @@
 #include <cmath>
 #include <cstdint>
 #include <cstring>
+#include <fstream>
 #include <list>
 #include <map>
 #include <memory>
 #include <mutex>
 #include <set>
+#include <sstream>
 #include <stdexcept>
 #include <string>
 #include <tuple>
@@ -32,6 +34,7 @@
 #include <vector>
 
 #include "../../include/gfs_abi.h"
+#include "../csrc/bow_vocab_rule.hpp"
 #include "../csrc/fuse_rule.hpp"
 #include "../csrc/sim3_search_rule.hpp"
 #include "../csrc/map_point_rule.hpp"
@@ -3374,6 +3377,274 @@ class BowSearcher {
  private:
   gfs_sbp* h_ = nullptr;
   int problems_ = 0, kf2_ = 0;
+};
+
+// ------------------------------------------------------------------------------------------------------------------------
+// ComputeBoW and the place-recognition query:
+//   bool TemplatedVocabulary::loadFromTextFile(filename)                    Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h:1338-1424
+//   void KeyFrame::ComputeBoW() / void Frame::ComputeBoW()                   src/KeyFrame.cc:219-227, src/Frame.cc:1086-1091
+//   void KeyFrameDatabase::DetectNBestCandidates(pKF, loop, merge, n)        src/KeyFrameDatabase.cc:583-718
+// LoadVocabularyText fills a gfs_bow_vocabulary as the loader fills m_nodes: node id = line order (the root is node 0 and has no
+// line), children in line order, word ids in leaf line order, the 32 descriptor bytes as decimal tokens.  Empty lines are skipped: the
+// reference builds a node with an uninitialised parent from the empty line that getline returns after a trailing newline.
+// ComputeBoW fills mBowVec and mFeatVec from one `transform` call under the reference's empty() guards.  DetectNBestCandidates takes the
+// three arrays of `query` (gfs_bow_db_query's) and replays the rest of :587-717 in the reference's order.  `transform` and `query` are
+// callables, as `solve` is in the other adaptors: BowTransformer::transformer() and BowDatabaseDevice::querier() below on the GPU.
+// ------------------------------------------------------------------------------------------------------------------------
+struct BowVocabularyFlat {  // a vocabulary backed by vectors
+  std::vector<int32_t> parent, child_start, children, word_id;
+  std::vector<uint8_t> desc;
+  std::vector<double> weight;
+  gfs_bow_vocabulary v{};
+};
+
+inline bool LoadVocabularyText(const std::string& path, BowVocabularyFlat& F) {
+  std::ifstream f(path.c_str());
+  if (!f.is_open()) return false;
+  std::string s;
+  std::getline(f, s);
+  std::stringstream ss;
+  ss << s;
+  int k = -1, L = -1, n1 = -1, n2 = -1;
+  ss >> k >> L >> n1 >> n2;
+  if (ss.fail() || k < 0 || k > gfs_bowv::kMaxK || L < 1 || L > gfs_bowv::kMaxL || n1 < 0 || n1 > 5 || n2 < 0 || n2 > 3) return false;
+  F = BowVocabularyFlat{};
+  std::vector<std::vector<int32_t>> kids(1);
+  F.parent.assign(1, 0);
+  F.word_id.assign(1, -1);
+  F.weight.assign(1, 0.0);
+  F.desc.assign(32, 0);
+  int n_words = 0;
+  while (std::getline(f, s)) {
+    if (s.find_first_not_of(" \t\r\n") == std::string::npos) continue;
+    std::stringstream ssnode;
+    ssnode << s;
+    const int nid = (int)F.parent.size();
+    int pid = -1, nIsLeaf = 0;
+    ssnode >> pid >> nIsLeaf;
+    if (ssnode.fail() || pid < 0 || pid >= nid) return false;
+    F.parent.push_back(pid);
+    kids[(size_t)pid].push_back(nid);
+    kids.emplace_back();
+    for (int iD = 0; iD < 32; iD++) {
+      int e = 0;
+      ssnode >> e;  // FORB::fromString: `ss >> n` into an int, stored as a byte
+      F.desc.push_back((uint8_t)e);
+    }
+    double w = 0;
+    ssnode >> w;
+    if (ssnode.fail()) return false;
+    F.weight.push_back(w);
+    F.word_id.push_back(nIsLeaf > 0 ? n_words++ : -1);
+  }
+  F.child_start.assign(1, 0);
+  for (const std::vector<int32_t>& c : kids) {
+    F.children.insert(F.children.end(), c.begin(), c.end());
+    F.child_start.push_back((int32_t)F.children.size());
+  }
+  F.children.push_back(0);  // (never NULL)
+  F.v.k = k;
+  F.v.L = L;
+  F.v.scoring = n1;
+  F.v.weighting = n2;
+  F.v.n_nodes = (int32_t)F.parent.size();
+  F.v.parent = F.parent.data();
+  F.v.child_start = F.child_start.data();
+  F.v.children = F.children.data();
+  F.v.desc = F.desc.data();
+  F.v.weight = F.weight.data();
+  F.v.word_id = F.word_id.data();
+  return true;
+}
+
+// Access: n_descriptors(kf), descriptors(kf) ([n][32] bytes, mDescriptors' rows); kf.mBowVec is a map<unsigned, double>, kf.mFeatVec a
+// map<unsigned, vector<unsigned>>.  KeyFrameGuard: `mBowVec.empty() || mFeatVec.empty()` (KeyFrame), else `mBowVec.empty()` (Frame).
+template <class Access, bool KeyFrameGuard, class KeyFrameOrFrame, class Transform>
+void ComputeBoW(Transform&& transform, KeyFrameOrFrame& kf) {
+  if (!(kf.mBowVec.empty() || (KeyFrameGuard && kf.mFeatVec.empty()))) return;
+  const int32_t n = (int32_t)Access::n_descriptors(kf);
+  const uint8_t* desc = Access::descriptors(kf);
+  std::vector<int32_t> word_id((size_t)n + 1), node_id((size_t)n + 1), node_start((size_t)n + 2), feat_idx((size_t)n + 1);
+  std::vector<double> word_value((size_t)n + 1);
+  gfs_bow_vectors o{};
+  o.word_id = word_id.data();
+  o.word_value = word_value.data();
+  o.node_id = node_id.data();
+  o.node_start = node_start.data();
+  o.feat_idx = feat_idx.data();
+  check(transform(&desc, &n, 1, gfs_bowv::kLevelsUp, &o), "ComputeBoW");
+  kf.mBowVec.clear();
+  kf.mFeatVec.clear();
+  for (int i = 0; i < o.n_words; i++) kf.mBowVec.insert(kf.mBowVec.end(), std::make_pair((unsigned)word_id[i], word_value[i]));
+  for (int q = 0; q < o.n_nodes; q++)
+    kf.mFeatVec.insert(kf.mFeatVec.end(), std::make_pair((unsigned)node_id[q], std::vector<unsigned>(feat_idx.begin() + node_start[q],
+                                                                                                      feat_idx.begin() + node_start[q + 1])));
+}
+
+// The caller's half of the database: which key frame sits in which slot, and the order in which they were added (the order of an
+// inverted file's lists).  add() of a key frame that has a slot moves it to the end of that order, as erase + add does.
+template <class KeyFrame>
+struct BowDatabaseIndex {
+  std::vector<KeyFrame*> kf;       // [max_entries] or nullptr
+  std::vector<long long> seq;      // [max_entries] add sequence number
+  std::map<KeyFrame*, int> slot_of;
+  long long next = 0;
+  explicit BowDatabaseIndex(int max_entries) : kf((size_t)max_entries, nullptr), seq((size_t)max_entries, 0) {}
+  int add(KeyFrame* p) {  // -> the slot, -1 when full
+    int s = -1;
+    auto it = slot_of.find(p);
+    if (it != slot_of.end()) s = it->second;
+    for (size_t i = 0; s < 0 && i < kf.size(); i++)
+      if (!kf[i]) s = (int)i;
+    if (s < 0) return -1;
+    kf[(size_t)s] = p;
+    seq[(size_t)s] = next++;
+    slot_of[p] = s;
+    return s;
+  }
+  int erase(KeyFrame* p) {  // -> the slot it had, -1 when it had none
+    auto it = slot_of.find(p);
+    if (it == slot_of.end()) return -1;
+    const int s = it->second;
+    kf[(size_t)s] = nullptr;
+    slot_of.erase(it);
+    return s;
+  }
+};
+
+// KeyFrame: mnId, mBowVec, GetConnectedKeyFrames(), GetBestCovisibilityKeyFrames(int), isBad(), GetMap() (-> a Map with IsBad()), and
+// the three members the reference writes: mnPlaceRecognitionQuery, mnPlaceRecognitionWords, mPlaceRecognitionScore.
+// query(n_words, word_id, word_value, n_common, first_word, score) -> gfs_status, the arrays [index.kf.size()].
+template <class KeyFrame, class Query>
+void DetectNBestCandidates(Query&& query, const BowDatabaseIndex<KeyFrame>& index, KeyFrame* pKF, std::vector<KeyFrame*>& vpLoopCand,
+                           std::vector<KeyFrame*>& vpMergeCand, int nNumCandidates = gfs_bowv::kLoopNumCandidates) {
+  const std::set<KeyFrame*> spConnectedKF = pKF->GetConnectedKeyFrames();
+  std::vector<int32_t> ids;
+  std::vector<double> vals;
+  for (const auto& w : pKF->mBowVec) {
+    ids.push_back((int32_t)w.first);
+    vals.push_back(w.second);
+  }
+  const size_t E = index.kf.size();
+  std::vector<int32_t> n_common(E + 1, 0), first_word(E + 1, -1);
+  std::vector<float> score(E + 1, 0.0f);
+  ids.push_back(0), vals.push_back(0.0);  // (never NULL)
+  check(query((int)ids.size() - 1, ids.data(), vals.data(), n_common.data(), first_word.data(), score.data()), "DetectNBestCandidates");
+  // lKFsSharingWords (:596-614): the query's words ascending, a word's list in insertion order -> (lowest common word, add sequence)
+  std::vector<size_t> sharing;
+  for (size_t s = 0; s < E; s++) {
+    KeyFrame* pKFi = index.kf[s];
+    if (!pKFi || n_common[s] <= 0) continue;
+    if (pKFi->mnPlaceRecognitionQuery == pKF->mnId) {  // (already this query's: :605 only counts on)
+      pKFi->mnPlaceRecognitionWords += n_common[s];
+      continue;
+    }
+    if (spConnectedKF.count(pKFi)) {
+      pKFi->mnPlaceRecognitionWords = 1;  // reset and incremented at every shared word, never marked
+      continue;
+    }
+    pKFi->mnPlaceRecognitionQuery = pKF->mnId;
+    pKFi->mnPlaceRecognitionWords = n_common[s];
+    sharing.push_back(s);
+  }
+  std::sort(sharing.begin(), sharing.end(), [&](size_t a, size_t b) {
+    return first_word[a] != first_word[b] ? first_word[a] < first_word[b] : index.seq[a] < index.seq[b];
+  });
+  if (sharing.empty()) return;
+  int maxCommonWords = 0;
+  for (size_t s : sharing)
+    if (index.kf[s]->mnPlaceRecognitionWords > maxCommonWords) maxCommonWords = index.kf[s]->mnPlaceRecognitionWords;
+  int minCommonWords = maxCommonWords * gfs_bowv::kMinCommonShare;
+  std::vector<std::pair<float, KeyFrame*>> lScoreAndMatch;
+  for (size_t s : sharing) {
+    KeyFrame* pKFi = index.kf[s];
+    if (pKFi->mnPlaceRecognitionWords > minCommonWords) {
+      float si = score[s];
+      pKFi->mPlaceRecognitionScore = si;
+      lScoreAndMatch.push_back(std::make_pair(si, pKFi));
+    }
+  }
+  if (lScoreAndMatch.empty()) return;
+  std::vector<std::pair<float, KeyFrame*>> lAccScoreAndMatch;
+  for (const auto& sm : lScoreAndMatch) {
+    KeyFrame* pKFi = sm.second;
+    std::vector<KeyFrame*> vpNeighs = pKFi->GetBestCovisibilityKeyFrames(gfs_bowv::kCovisibles);
+    float bestScore = sm.first;
+    float accScore = bestScore;
+    KeyFrame* pBestKF = pKFi;
+    for (KeyFrame* pKF2 : vpNeighs) {
+      if (pKF2->mnPlaceRecognitionQuery != pKF->mnId) continue;
+      accScore += pKF2->mPlaceRecognitionScore;
+      if (pKF2->mPlaceRecognitionScore > bestScore) {
+        pBestKF = pKF2;
+        bestScore = pKF2->mPlaceRecognitionScore;
+      }
+    }
+    lAccScoreAndMatch.push_back(std::make_pair(accScore, pBestKF));
+  }
+  // list::sort(compFirst) is stable: equal accumulated scores keep list order
+  std::stable_sort(lAccScoreAndMatch.begin(), lAccScoreAndMatch.end(),
+                   [](const std::pair<float, KeyFrame*>& a, const std::pair<float, KeyFrame*>& b) { return a.first > b.first; });
+  vpLoopCand.reserve((size_t)nNumCandidates);
+  vpMergeCand.reserve((size_t)nNumCandidates);
+  std::set<KeyFrame*> spAlreadyAddedKF;
+  for (size_t i = 0; i < lAccScoreAndMatch.size() && ((int)vpLoopCand.size() < nNumCandidates || (int)vpMergeCand.size() < nNumCandidates); i++) {
+    KeyFrame* pKFi = lAccScoreAndMatch[i].second;
+    if (pKFi->isBad()) continue;
+    if (spAlreadyAddedKF.count(pKFi)) continue;
+    if (pKF->GetMap() == pKFi->GetMap() && (int)vpLoopCand.size() < nNumCandidates) {
+      vpLoopCand.push_back(pKFi);
+    } else if (pKF->GetMap() != pKFi->GetMap() && (int)vpMergeCand.size() < nNumCandidates && !pKFi->GetMap()->IsBad()) {
+      vpMergeCand.push_back(pKFi);
+    }
+    spAlreadyAddedKF.insert(pKFi);
+  }
+}
+
+// the vocabulary transform on the GPU
+class BowTransformer {
+ public:
+  BowTransformer(const gfs_bow_vocabulary& v, int max_batch = 1, int max_features = 4096, int device = 0) {
+    check(gfs_bow_create(device, &v, max_batch, max_features, &h_), "gfs_bow_create");
+  }
+  ~BowTransformer() { gfs_bow_destroy(h_); }
+  BowTransformer(const BowTransformer&) = delete;
+  BowTransformer& operator=(const BowTransformer&) = delete;
+  auto transformer() {
+    return [this](const uint8_t* const* desc, const int32_t* n, int B, int levelsup, gfs_bow_vectors* out) {
+      return gfs_bow_transform(h_, desc, n, B, levelsup, out);
+    };
+  }
+
+ private:
+  gfs_bow_vocab* h_ = nullptr;
+};
+
+// the database's store on the GPU; the BowDatabaseIndex beside it says which key frame a slot holds
+class BowDatabaseDevice {
+ public:
+  BowDatabaseDevice(int max_entries, int max_words, int device = 0) { check(gfs_bow_db_create(device, max_entries, max_words, &h_), "gfs_bow_db_create"); }
+  ~BowDatabaseDevice() { gfs_bow_db_destroy(h_); }
+  BowDatabaseDevice(const BowDatabaseDevice&) = delete;
+  BowDatabaseDevice& operator=(const BowDatabaseDevice&) = delete;
+  template <class BowVector>
+  void add(int slot, const BowVector& v) {  // KeyFrameDatabase::add: pKF->mBowVec into the key frame's slot
+    std::vector<int32_t> ids;
+    std::vector<double> vals;
+    for (const auto& w : v) ids.push_back((int32_t)w.first), vals.push_back(w.second);
+    const int n = (int)ids.size();
+    ids.push_back(0), vals.push_back(0.0);
+    check(gfs_bow_db_add(h_, slot, n, ids.data(), vals.data()), "gfs_bow_db_add");
+  }
+  void erase(int slot) { check(gfs_bow_db_erase(h_, slot), "gfs_bow_db_erase"); }
+  auto querier() {
+    return [this](int n, const int32_t* id, const double* value, int32_t* n_common, int32_t* first_word, float* score) {
+      return gfs_bow_db_query(h_, n, id, value, n_common, first_word, score);
+    };
+  }
+
+ private:
+  gfs_bow_db* h_ = nullptr;
 };
 
 }  // namespace gfs_host

@@ -1181,6 +1181,71 @@ def bow_search_problem(seed, n_kp=1000, n_kf2=1, n_nodes=100, n_kp2=None, no_mp_
     return dict(kf1=kf1, kf2=kf2, nn_ratio=f32(nn_ratio), check_orientation=bool(check_orientation))
 
 
+def bow_vocabulary(seed, k=10, L=4, stop_frac=0.0, prune_frac=0.0, shuffle_children=False, level_flip_bits=(90, 60, 40, 28, 20, 14, 10, 8, 6, 4)):
+    """A random vocabulary tree as gfs_bow_create takes it (gfs_bow_vocabulary in include/gfs_abi.h): dict(k, L, scoring = 0 (L1_NORM),
+    weighting = 0 (TF_IDF), n_nodes, parent, child_start, children, desc [n_nodes, 32], weight, word_id).  Every inner node has k
+    children; a child's descriptor is its parent's with about level_flip_bits[level - 1] bits flipped, so a feature near a leaf
+    descends to it and siblings tie now and then.
+      prune_frac        the share of the nodes of levels 1 .. L-1 that become leaves early (an irregular tree)
+      shuffle_children  the node ids (all but the root's) and the word ids are random permutations: child ids are neither contiguous
+                        nor ascending, as no text file can give them
+      stop_frac         the share of the words with weight 0 (stopped); the others carry log(N / n_i)-like positive doubles"""
+    rng = np.random.default_rng(seed + 49979687)
+    parent, level_of, desc, leaf = [np.zeros(1, np.int64)], [np.zeros(1, np.int64)], [rng.integers(0, 256, (1, 32)).astype(np.uint8)], [np.zeros(1, bool)]
+    inner, n = np.zeros(1, np.int64), 1  # the inner nodes of the level above, the nodes so far
+    for lev in range(1, L + 1):
+        m = len(inner) * k
+        if m == 0:
+            break
+        par = np.repeat(inner, k)
+        src = desc[0][par]
+        flips = np.clip(rng.normal(level_flip_bits[lev - 1], 3, m).round().astype(np.int64), 0, 256)
+        d = _flip_bits(rng, src, flips)
+        is_leaf = np.ones(m, bool) if lev == L else rng.random(m) < prune_frac
+        parent.append(par), level_of.append(np.full(m, lev)), desc.append(d), leaf.append(is_leaf)
+        inner = n + np.nonzero(~is_leaf)[0]
+        n += m
+        desc = [np.concatenate(desc)]
+    parent, desc, leaf = np.concatenate(parent), np.concatenate(desc), np.concatenate(leaf)
+    n_words = int(leaf.sum())
+    perm = np.arange(n)
+    word_of_leaf = np.arange(n_words)
+    if shuffle_children:
+        perm[1:] = 1 + rng.permutation(n - 1)
+        word_of_leaf = rng.permutation(n_words)
+    counts = np.bincount(parent[1:], minlength=n)
+    first = np.concatenate([[1], 1 + np.cumsum(counts)[:-1]])  # the first child of every node in the contiguous numbering
+    cnt_new = np.zeros(n, np.int64)
+    cnt_new[perm] = counts
+    child_start = np.concatenate([[0], np.cumsum(cnt_new)])
+    children = np.zeros(n - 1, np.int64)
+    c = np.arange(1, n)
+    children[child_start[perm[parent[c]]] + (c - first[parent[c]])] = perm[c]
+    out_parent, out_desc, out_word, out_weight = np.zeros(n, np.int32), np.zeros((n, 32), np.uint8), np.full(n, -1, np.int32), np.zeros(n)
+    out_parent[perm] = perm[parent]
+    out_desc[perm] = desc
+    N = 10000.0
+    w = np.log(N / rng.integers(1, 5000, n_words))
+    w[rng.random(n_words) < stop_frac] = 0.0
+    leaves = np.nonzero(leaf)[0]
+    out_word[perm[leaves]] = word_of_leaf
+    out_weight[perm[leaves]] = w
+    return dict(k=k, L=L, scoring=0, weighting=0, n_nodes=n, parent=out_parent, child_start=child_start.astype(np.int32),
+                children=children.astype(np.int32), desc=out_desc, weight=out_weight, word_id=out_word)
+
+
+def bow_features(seed, vocab, n, max_flip_bits=12, dup_frac=0.0):
+    """n descriptors [n, 32] for gfs_bow_transform: leaf descriptors of `vocab` with 0..max_flip_bits bits flipped; dup_frac of them are
+    exact copies of another feature, so that several features fall into one word."""
+    rng = np.random.default_rng(seed + 15485863)
+    leaves = np.nonzero(np.asarray(vocab["word_id"]) >= 0)[0]
+    d = _flip_bits(rng, np.asarray(vocab["desc"], np.uint8)[leaves[rng.integers(len(leaves), size=n)]], rng.integers(0, max_flip_bits + 1, n)) \
+        if n else np.zeros((0, 32), np.uint8)
+    for i in np.nonzero(rng.random(n) < dup_frac)[0]:
+        d[i] = d[int(rng.integers(n))]
+    return np.ascontiguousarray(d, np.uint8)
+
+
 def map_point_update_problem(seed, n_points=1000,obs_counts=(1, 20), n_keyframes=40, flip_bits=40, scale_factor=1.2, n_levels=8):
     """Synthetic input of MapPoint::ComputeDistinctiveDescriptors and MapPoint::UpdateNormalAndDepth (reference src/MapPoint.cc:376-448,
     :468-532) for `n_points` map points, as gfs_map_points_update takes it (include/gfs_abi.h): a dict with the keys of

@@ -1320,6 +1320,73 @@ int gfs_sim3_ransac_solve(gfs_sim3_ransac* h, const gfs_sim3_ransac_problem* pro
 void gfs_sim3_ransac_destroy(gfs_sim3_ransac* h);
 
 /* ============================================================================================
+ * 18. ComputeBoW and the BoW database query — the head of loop detection, and the one piece of it the tracking thread runs too:
+ *      DBoW2::TemplatedVocabulary::transform(features, BowVector&, FeatureVector&, levelsup)   TemplatedVocabulary.h:1119-1259
+ *        as KeyFrame::ComputeBoW (src/KeyFrame.cc:219-227) and Frame::ComputeBoW (src/Frame.cc:1086-1091) call it, and
+ *      the numeric core of KeyFrameDatabase::DetectNBestCandidates (src/KeyFrameDatabase.cc:583-718): the common-word count of the
+ *        query against every key frame of the database and L1Scoring::score (ScoringObject.cpp:23-68).
+ *    csrc/bow_vocab_rule.hpp and DESIGN.md section 24 state the rule: the descent by strict `<` in `children` order, the
+ *    accumulation in feature order, the L1 norm summed in ascending word id, the score's terms added in ascending word id.  Every
+ *    output is the reference's byte for byte.  Only TF_IDF weighting with L1_NORM scoring is accepted: the header `10 6 0 0` of
+ *    ORBvoc.txt, scoring = 0 (L1_NORM), weighting = 0 (TF_IDF).
+ *
+ *    gfs_bow_create validates the tree on the host before anything is uploaded (GFS_ERR_INVALID_ARG): 1 <= k <= 20, 1 <= L <= 10,
+ *    scoring == 0 and weighting == 0, the root an inner node, every non-root node listed once and under its `parent` only, no
+ *    cycles, every index in range, an inner node (word_id == -1) with 1..k children, a leaf (word_id >= 0) with none, the word ids
+ *    a permutation of 0..n_words-1, depth <= L, weights finite.  It uploads a repacked table in which the children of a node are
+ *    contiguous and in `children` order.  max_features <= 4096 (else GFS_ERR_UNSUPPORTED: one workgroup sorts a frame in LDS).
+ * ============================================================================================ */
+typedef struct {
+  int32_t k, L, scoring, weighting;  /* header of the vocabulary */
+  int32_t n_nodes;                   /* node 0 is the root */
+  const int32_t* parent;             /* [n_nodes], parent[0] ignored */
+  const int32_t* child_start;        /* [n_nodes + 1] prefix sum */
+  const int32_t* children;           /* [child_start[n_nodes]] in the order of m_nodes[n].children */
+  const uint8_t* desc;               /* [n_nodes][32] */
+  const double*  weight;             /* [n_nodes] */
+  const int32_t* word_id;            /* [n_nodes] >= 0 for a leaf, -1 for an inner node */
+} gfs_bow_vocabulary;
+typedef struct gfs_bow_vocab gfs_bow_vocab;  /* (not gfs_bow: that names the rule of section 7a' inside the library) */
+int  gfs_bow_create(int device, const gfs_bow_vocabulary* v, int max_batch, int max_features, gfs_bow_vocab** out);
+void gfs_bow_destroy(gfs_bow_vocab* h);
+
+typedef struct {           /* caller-owned, capacities = max_features of the handle (node_start: max_features + 1) */
+  int32_t n_words;  int32_t* word_id; double* word_value;          /* BowVector, ascending id */
+  int32_t n_nodes;  int32_t* node_id; int32_t* node_start; int32_t* feat_idx; /* FeatureVector in the layout of gfs_bow_keyframe */
+  int32_t* word_of_feature;  /* [n] (may be NULL) word id of every feature, -1 when stopped: for tests */
+} gfs_bow_vectors;
+/* B frames in one call: desc[b] is [n[b]][32] (host pointers), out[b] the vectors of frame b.  feat_idx is ascending within a node,
+ * node_id strictly ascending, node_start a prefix sum: gfs_search_by_bow and gfs_create_new_map_points accept the output unchanged.
+ * Refused before anything is staged, nothing truncated, the handle left usable -- GFS_ERR_CAPACITY: B > max_batch or
+ * n[b] > max_features; GFS_ERR_INVALID_ARG: a NULL array, n[b] < 0, levelsup < 0, or a vocabulary with a leaf shallower than level
+ * L - levelsup (where the reference leaves *nid uninitialised).  B == 0 and n[b] == 0 are valid: an empty frame yields empty vectors.
+ * One upload, two kernels (k_bow_descend, k_bow_vectors), one download, one synchronisation. */
+int gfs_bow_transform(gfs_bow_vocab* h, const uint8_t* const* desc, const int32_t* n, int B, int levelsup, gfs_bow_vectors* out);
+/* The same on descriptors as gfs_orb_device_results leaves them: dev_desc [B][stride][32] u8 (16-byte aligned), dev_counts [B]
+ * int32, both in HBM; no upload.  The counts are only known on the device: a frame with more than max_features or more than `stride`
+ * key-points is found by the kernel, which writes nothing for it, and the call returns GFS_ERR_CAPACITY after the synchronisation. */
+int gfs_bow_transform_device(gfs_bow_vocab* h, const void* dev_desc, const void* dev_counts, int stride, int B, int levelsup,
+                             gfs_bow_vectors* out);
+
+/* The database: a fixed-stride store of BowVectors, one slot per key frame.  The caller owns the mapping from key frame to slot and
+ * the `add` sequence numbers.  add to an occupied slot replaces its contents; erase of an empty slot is valid and does nothing.
+ * query fills, for every slot (each array [max_entries]): n_common = mnPlaceRecognitionWords (0 for an empty slot), first_word =
+ * the lowest common word id or -1 (the sharing list of :596-614 is ordered by (first_word, add sequence)), score =
+ * (float)L1Scoring::score(query, entry) where n_common > 0, else 0: the score of every sharing entry, since the `> minCommonWords`
+ * filter needs the maximum over the non-connected entries, which only the caller knows.
+ * Refused before anything is staged, the handle left usable -- GFS_ERR_INVALID_ARG: a NULL array, ids not strictly ascending or
+ * negative, a non-finite value, a slot outside [0, max_entries); GFS_ERR_CAPACITY: n_words > max_words.  max_words <= 4096 (else
+ * GFS_ERR_UNSUPPORTED at creation: the query lives in LDS).  query: one upload, one kernel (k_bow_score), one download, one
+ * synchronisation. */
+typedef struct gfs_bow_db gfs_bow_db;
+int  gfs_bow_db_create(int device, int max_entries, int max_words, gfs_bow_db** out);
+void gfs_bow_db_destroy(gfs_bow_db* h);
+int  gfs_bow_db_add(gfs_bow_db* h, int slot, int n_words, const int32_t* word_id, const double* word_value);
+int  gfs_bow_db_erase(gfs_bow_db* h, int slot);
+int  gfs_bow_db_query(gfs_bow_db* h, int n_words, const int32_t* word_id, const double* word_value,
+                      int32_t* n_common, int32_t* first_word, float* score);   /* each [max_entries] */
+
+/* ============================================================================================
  * Timing helper for the harness: HIP events on a given stream (bench.py measures the dominant kernel
  * with these rather than torch events, which only see torch's current stream).
  * ============================================================================================ */

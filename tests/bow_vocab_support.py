@@ -1,0 +1,410 @@
+"""Shared by the ComputeBoW / BoW database tests: builds and calls the sequential CPU restatement (tests/host/bow_vocab_restatement.cpp)
+and the rule header's host build, an independent Python statement of both, the hand-built cases with the outputs their labels
+promise, and the seeded problems.  Not a test module."""
+import ctypes as C
+import functools
+import os
+import subprocess
+
+import numpy as np
+
+from geoflowslam_amd import api, synth
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+_SRC = os.path.join(ROOT, "tests", "host", "bow_vocab_restatement.cpp")
+_SO = os.path.join(ROOT, "tests", "host", "_bow_vocab_restatement.so")
+_L = None
+
+CONSTANTS = ("max_k", "max_L", "scoring", "weighting", "levelsup", "w_gt_0", "d_lt_best_d", "min_common_share", "covisibles", "nNumCandidates")
+VECTOR_KEYS = ("word_id", "word_value", "node_id", "node_start", "feat_idx", "word_of_feature")
+ERR_INVALID_ARG, ERR_CAPACITY, ERR_UNSUPPORTED = -1, -4, -5  # GFS_ERR_* (include/gfs_abi.h)
+
+
+def restatement():
+    global _L
+    if _L is None:
+        csrc = os.path.join(ROOT, "geoflowslam_amd", "csrc")
+        deps = [_SRC, os.path.join(csrc, "bow_vocab_rule.hpp"), os.path.join(ROOT, "include", "gfs_abi.h")]
+        if not os.path.exists(_SO) or os.path.getmtime(_SO) < max(os.path.getmtime(d) for d in deps):
+            tmp = _SO + f".{os.getpid()}.tmp"
+            subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-Wall", "-I" + os.path.join(ROOT, "include"),
+                            "-I" + csrc, "-o", tmp, _SRC], check=True)
+            os.replace(tmp, _SO)
+        L = C.CDLL(_SO)
+        vp, i = C.c_void_p, C.c_int
+        V, O = C.POINTER(api.BowVocabularyStruct), C.POINTER(api.BowVectors)
+        L.bv_transform.argtypes = [V, C.POINTER(vp), vp, i, i, O]
+        L.bv_rule_transform.argtypes = [V, C.POINTER(vp), vp, i, i, O, C.c_char_p, i]
+        L.bv_rule_validate.argtypes = [V, vp, C.c_char_p, i]
+        L.bv_db_create.argtypes = [i]
+        L.bv_db_create.restype = vp
+        L.bv_db_destroy.argtypes = [vp]
+        L.bv_db_destroy.restype = None
+        L.bv_db_erase.argtypes = [vp, i]
+        L.bv_db_erase.restype = None
+        L.bv_db_add.argtypes = [vp, i, i, vp, vp]
+        L.bv_db_add.restype = None
+        L.bv_db_query.argtypes = [vp, i, vp, vp, vp, vp, vp, vp]
+        L.bv_rule_score.argtypes = [i, vp, vp, i, vp, vp, vp, vp, vp]
+        L.bv_rule_score.restype = None
+        L.bv_rule_valid_vector.argtypes = [i, vp, vp]
+        L.bv_constants.argtypes = [vp]
+        L.bv_constants.restype = None
+        _L = L
+    return _L
+
+
+# ---------------------------------------------------------------- the transform
+
+def _call(fn, vocab, descs, levelsup, extra=()):
+    single, frames = api.bow_frames(descs)
+    V, keep_v = api.bow_vocabulary_struct(vocab)
+    B = len(frames)
+    ptrs = (C.c_void_p * max(B, 1))(*[f.ctypes.data for f in frames])
+    n = np.array([len(f) for f in frames] + [0], np.int32)
+    VV, keep = api.bow_vectors_alloc(B, max([len(f) for f in frames] + [1]))
+    rc = fn(C.byref(V), ptrs, n.ctypes.data, B, int(levelsup), VV, *extra)
+    if rc != 0:
+        return rc, None
+    res = api.bow_vectors_results(VV, keep, n)
+    return rc, (res[0] if single else res)
+
+
+def restate(vocab, descs, levelsup=4):
+    """The restatement -> (0, result dict(s) as api.BowVocabulary.transform returns them), or (-2, None) where the reference would
+    have left a node id uninitialised."""
+    return _call(restatement().bv_transform, vocab, descs, levelsup)
+
+
+def rule_host(vocab, descs, levelsup=4):
+    """The rule header's host build -> (rc, results, reason): rc -1 with the validator's reason, -2 for the shallow leaf."""
+    why = C.create_string_buffer(256)
+    rc, res = _call(restatement().bv_rule_transform, vocab, descs, levelsup, (why, 256))
+    return rc, res, why.value.decode()
+
+
+def rule_validate(vocab):
+    """-> (n_words, min_leaf_depth) or the validator's reason (a str)"""
+    V, keep = api.bow_vocabulary_struct(vocab)
+    info, why = np.zeros(2, np.int32), C.create_string_buffer(256)
+    rc = restatement().bv_rule_validate(C.byref(V), info.ctypes.data, why, 256)
+    return (int(info[0]), int(info[1])) if rc == 0 else why.value.decode()
+
+
+def rule_constants():
+    out = np.zeros(len(CONSTANTS), np.float64)
+    restatement().bv_constants(out.ctypes.data)
+    return dict(zip(CONSTANTS, out.tolist()))
+
+
+def python_transform(vocab, desc, levelsup=4):
+    """An independent statement of the transform of ONE frame in plain Python: dicts for both vectors, Python floats (IEEE doubles)
+    added in the same order.  -> result dict, or None where a node id would stay unassigned."""
+    cs, ch, w, wid = vocab["child_start"], vocab["children"], vocab["weight"], vocab["word_id"]
+    bits = np.unpackbits(np.asarray(vocab["desc"], np.uint8).reshape(-1, 32), axis=1).astype(np.int16)
+    fb = np.unpackbits(np.asarray(desc, np.uint8).reshape(-1, 32), axis=1).astype(np.int16)
+    nid_level = vocab["L"] - levelsup
+    bow, fv, word_of = {}, {}, []
+    for i in range(len(fb)):
+        node, level, nid = 0, 0, (0 if nid_level <= 0 else None)
+        while True:
+            level += 1
+            kids = ch[cs[node]:cs[node + 1]]
+            best, node = None, None
+            for c in kids:  # strict <: the first of equals stays
+                d = int(np.abs(bits[c] - fb[i]).sum())
+                if best is None or d < best:
+                    best, node = d, int(c)
+            if level == nid_level:
+                nid = node
+            if cs[node] == cs[node + 1]:
+                break
+        if nid is None:
+            return None
+        weight = float(w[node])
+        word_of.append(int(wid[node]) if weight > 0 else -1)
+        if weight > 0:
+            bow[int(wid[node])] = bow[int(wid[node])] + weight if int(wid[node]) in bow else weight
+            fv.setdefault(nid, []).append(i)
+    ids = sorted(bow)
+    norm = 0.0
+    for k in ids:
+        norm += abs(bow[k])
+    vals = [bow[k] / norm if norm > 0.0 else bow[k] for k in ids]
+    nodes = sorted(fv)
+    return dict(word_id=np.array(ids, np.int32), word_value=np.array(vals, np.float64), node_id=np.array(nodes, np.int32),
+                node_start=np.concatenate([[0], np.cumsum([len(fv[k]) for k in nodes])]).astype(np.int32),
+                feat_idx=np.array([i for k in nodes for i in fv[k]], np.int32), word_of_feature=np.array(word_of, np.int32))
+
+
+def assert_vectors_equal(got, want, what=""):
+    """Byte equality of everything gfs_bow_transform delivers for ONE frame."""
+    for k in VECTOR_KEYS:
+        if got[k] is None and k == "word_of_feature":
+            continue
+        g, w = np.asarray(got[k]), np.asarray(want[k])
+        assert g.dtype == w.dtype and g.shape == w.shape, (what, k, g.dtype, w.dtype, g.shape, w.shape)
+        assert g.tobytes() == w.tobytes(), (what, k, np.nonzero(g != w)[0][:8])
+
+
+# ---------------------------------------------------------------- the database
+
+class RestatedDatabase:
+    """The restatement's KeyFrameDatabase: an inverted file with lists."""
+
+    def __init__(self, max_entries):
+        self.n, self.h = max_entries, restatement().bv_db_create(max_entries)
+
+    def __del__(self):
+        if _L is not None and self.h:
+            _L.bv_db_destroy(self.h)
+            self.h = None
+
+    def add(self, slot, word_id, word_value):
+        ids, vals = np.ascontiguousarray(word_id, np.int32), np.ascontiguousarray(word_value, np.float64)
+        restatement().bv_db_add(self.h, slot, len(ids), ids.ctypes.data, vals.ctypes.data)
+
+    def erase(self, slot):
+        restatement().bv_db_erase(self.h, slot)
+
+    def query(self, word_id, word_value):
+        """-> dict(n_common, first_word, score [max_entries], list = lKFsSharingWords as slots in list order)"""
+        ids, vals = np.ascontiguousarray(word_id, np.int32), np.ascontiguousarray(word_value, np.float64)
+        o = dict(n_common=np.full(self.n, -7, np.int32), first_word=np.full(self.n, -7, np.int32), score=np.full(self.n, np.nan, np.float32))
+        lst = np.full(self.n, -7, np.int32)
+        m = restatement().bv_db_query(self.h, len(ids), ids.ctypes.data, vals.ctypes.data, *[o[k].ctypes.data for k in ("n_common", "first_word", "score")],
+                                      lst.ctypes.data)
+        o["list"] = lst[:m].copy()
+        return o
+
+
+def rule_query(entries, max_entries, word_id, word_value):
+    """The rule's host statement: entries = {slot: (ids, values)} -> dict(n_common, first_word, score)"""
+    ids, vals = np.ascontiguousarray(word_id, np.int32), np.ascontiguousarray(word_value, np.float64)
+    o = dict(n_common=np.zeros(max_entries, np.int32), first_word=np.full(max_entries, -1, np.int32), score=np.zeros(max_entries, np.float32))
+    for s, (di, dv) in entries.items():
+        di, dv = np.ascontiguousarray(di, np.int32), np.ascontiguousarray(dv, np.float64)
+        nc, fw, sc = C.c_int32(), C.c_int32(), C.c_float()
+        restatement().bv_rule_score(len(ids), ids.ctypes.data, vals.ctypes.data, len(di), di.ctypes.data, dv.ctypes.data, C.byref(nc), C.byref(fw), C.byref(sc))
+        o["n_common"][s], o["first_word"][s], o["score"][s] = nc.value, fw.value, sc.value
+    return o
+
+
+def python_query(entries, order, max_entries, word_id, word_value):
+    """An independent statement in plain Python: entries = {slot: (ids, values)}, order = the slots in `add` order.  The sharing list
+    by the walk of the query's words over per-word lists, the score by the merge over the common words in ascending id."""
+    q = dict(zip([int(i) for i in word_id], [float(v) for v in word_value]))
+    inverted = {}
+    for s in order:
+        for wd in entries[s][0]:
+            inverted.setdefault(int(wd), []).append(s)
+    o = dict(n_common=np.zeros(max_entries, np.int32), first_word=np.full(max_entries, -1, np.int32), score=np.zeros(max_entries, np.float32), list=[])
+    for wd in sorted(q):
+        for s in inverted.get(wd, []):
+            if o["n_common"][s] == 0:
+                o["first_word"][s] = wd
+                o["list"].append(s)
+            o["n_common"][s] += 1
+    for s in o["list"]:
+        e = dict(zip([int(i) for i in entries[s][0]], [float(v) for v in entries[s][1]]))
+        score = 0.0
+        for wd in sorted(set(q) & set(e)):
+            score += abs(q[wd] - e[wd]) - abs(q[wd]) - abs(e[wd])
+        o["score"][s] = np.float32(-score / 2.0)
+    o["list"] = np.array(o["list"], np.int32)
+    return o
+
+
+def assert_query_equal(got, want, what=""):
+    for k in ("n_common", "first_word", "score"):
+        g, w = np.asarray(got[k]), np.asarray(want[k])
+        assert g.dtype == w.dtype and g.tobytes() == w.tobytes(), (what, k, np.nonzero(g.view(np.int32) != w.view(np.int32))[0][:8])
+
+
+def bow_vector(seed, n_words, id_range, ids=None):
+    """A normalised BowVector of n_words words with ids below id_range (or the given ids): (ids ascending, values)"""
+    rng = np.random.default_rng(seed)
+    ids = np.sort(rng.choice(id_range, n_words, replace=False)).astype(np.int32) if ids is None else np.asarray(ids, np.int32)
+    v = rng.random(len(ids)) + 0.05
+    return ids, v / v.sum()
+
+
+# ---------------------------------------------------------------- the adaptors' harness
+
+_ADAPTOR_SRC = os.path.join(ROOT, "tests", "host", "bow_vocab_adaptor_test.cpp")
+_ADAPTOR_SO = os.path.join(ROOT, "tests", "host", "_bow_vocab_adaptor_test.so")
+_H = None
+
+
+def harness():
+    """tests/host/bow_vocab_adaptor_test.cpp, linked against the library (which must be built)"""
+    global _H
+    if _H is None:
+        api.lib()
+        csrc = os.path.join(ROOT, "geoflowslam_amd", "csrc")
+        deps = [_ADAPTOR_SRC, _SRC, os.path.join(ROOT, "geoflowslam_amd", "host", "gfs_adaptors.hpp"), os.path.join(ROOT, "include", "gfs_abi.h"),
+                os.path.join(csrc, "bow_vocab_rule.hpp")]
+        if not os.path.exists(_ADAPTOR_SO) or os.path.getmtime(_ADAPTOR_SO) < max(os.path.getmtime(d) for d in deps):
+            libdir = os.path.dirname(api._LIB_PATH)
+            tmp = _ADAPTOR_SO + f".{os.getpid()}.tmp"
+            subprocess.run(["g++", "-std=c++17", "-O1", "-ffp-contract=off", "-fPIC", "-shared", "-Wall", "-I" + os.path.join(ROOT, "include"),
+                            "-I" + csrc, "-o", tmp, _ADAPTOR_SRC, "-L" + libdir, "-lgfs_hip", "-Wl,-rpath," + libdir], check=True)
+            os.replace(tmp, _ADAPTOR_SO)
+        L = C.CDLL(_ADAPTOR_SO)
+        vp, i = C.c_void_p, C.c_int
+        L.bow_load_vocabulary_text.argtypes = [C.c_char_p, i] + [vp] * 7
+        L.bow_compute_bow_test.argtypes = [i, C.POINTER(api.BowVocabularyStruct), vp, i, i, i] + [vp] * 7
+        L.bow_detect_test.argtypes = [i, i, vp, vp, vp, vp, i, vp, vp, vp, vp, i, vp, vp, vp, i, i, i, i] + [vp] * 7
+        _H = L
+    return _H
+
+
+def load_vocabulary_text(path, cap=4096):
+    """gfs_host::LoadVocabularyText -> a vocabulary dict, or None when the loader refuses the file"""
+    hdr = np.zeros(4, np.int32)
+    a = dict(parent=np.zeros(cap, np.int32), child_start=np.zeros(cap + 1, np.int32), children=np.zeros(cap, np.int32),
+             desc=np.zeros((cap, 32), np.uint8), weight=np.zeros(cap), word_id=np.zeros(cap, np.int32))
+    n = harness().bow_load_vocabulary_text(path.encode(), cap, hdr.ctypes.data, *[a[k].ctypes.data for k in ("parent", "child_start", "children", "desc", "weight", "word_id")])
+    if n < 0:
+        return None
+    return dict(k=int(hdr[0]), L=int(hdr[1]), scoring=int(hdr[2]), weighting=int(hdr[3]), n_nodes=n, parent=a["parent"][:n], child_start=a["child_start"][:n + 1],
+                children=a["children"][:a["child_start"][n]], desc=a["desc"][:n], weight=a["weight"][:n], word_id=a["word_id"][:n])
+
+
+# ---------------------------------------------------------------- hand-built cases
+
+def bits(*ranges):
+    """One descriptor with the bits of the given (first, count) ranges set."""
+    b = np.zeros(256, np.uint8)
+    for a, n in ranges:
+        b[a:a + n] = 1
+    return np.packbits(b)
+
+
+def tree(k, L, nodes):
+    """A hand-made vocabulary: nodes = [(parent, descriptor, weight or None for an inner node)] for nodes 1.., children in list order,
+    word ids in leaf order."""
+    n = len(nodes) + 1
+    parent = np.array([0] + [p for p, _, _ in nodes], np.int32)
+    kids = [[i for i in range(1, n) if parent[i] == j] for j in range(n)]
+    word, nw = np.full(n, -1, np.int32), 0
+    weight = np.zeros(n)
+    for i, (_, _, w) in enumerate(nodes, 1):
+        if w is not None:
+            word[i], weight[i], nw = nw, w, nw + 1
+    return dict(k=k, L=L, scoring=0, weighting=0, n_nodes=n, parent=parent,
+                child_start=np.concatenate([[0], np.cumsum([len(c) for c in kids])]).astype(np.int32),
+                children=np.array([c for l in kids for c in l], np.int32),
+                desc=np.stack([bits()] + [d for _, d, _ in nodes]).astype(np.uint8), weight=weight, word_id=word)
+
+
+def vec(word_id, word_value, node_id, lists, word_of_feature):
+    return dict(word_id=np.array(word_id, np.int32), word_value=np.array(word_value, np.float64), node_id=np.array(node_id, np.int32),
+                node_start=np.concatenate([[0], np.cumsum([len(l) for l in lists])]).astype(np.int32),
+                feat_idx=np.array([i for l in lists for i in l], np.int32), word_of_feature=np.array(word_of_feature, np.int32))
+
+
+def constructed():
+    """Hand-made cases with the outputs their labels promise: -> {label: (vocab, desc [n, 32], levelsup, expected result or None for
+    the refused combination)}."""
+    cases = {}
+    # k = 2, L = 2: the feature (all zero) is 8 bits from both children of the root; the FIRST wins, then its nearer leaf (node 4)
+    t = tree(2, 2, [(0, bits((0, 8)), None), (0, bits((8, 8)), None), (1, bits((0, 20)), 1.5), (1, bits((0, 3)), 2.5),
+                    (2, bits((8, 1)), 3.5), (2, bits((8, 2)), 4.5)])
+    cases["two equidistant children: the first wins"] = (t, np.stack([bits()]), 1, vec([1], [1.0], [1], [[0]], [1]))
+    # ten children under the root, positions 0 and 9 tie at distance 4 below all others: position 0; with 0 moved away, position 9
+    ten = [(0, bits((0, 4)) if c in (0, 9) else bits((0, 30 + c)), 1.0 + c) for c in range(10)]
+    cases["a tie between positions 0 and 9 of ten children"] = (tree(10, 1, ten), np.stack([bits()]), 1, vec([0], [1.0], [0], [[0]], [0]))
+    ten2 = [(0, bits((0, 5)), 1.0)] + ten[1:]
+    cases["... and position 9 alone when position 0 is one bit further"] = (tree(10, 1, ten2), np.stack([bits()]), 1, vec([9], [1.0], [0], [[0]], [9]))
+    # a stopped word: feature 1 lands in the word of weight 0 and is in neither vector; features 0 and 2 in words 0 and 2
+    t = tree(3, 1, [(0, bits((0, 40)), 2.0), (0, bits((40, 40)), 0.0), (0, bits((80, 40)), 6.0)])
+    f = np.stack([bits((0, 40)), bits((40, 40)), bits((80, 40))])
+    cases["a stopped word is in neither vector"] = (t, f, 1, vec([0, 2], [0.25, 0.75], [0], [[0, 2]], [0, -1, 2]))
+    # every feature in one word: w + w + w over its own sum is exactly 1.0
+    cases["all features in one word: the value is exactly 1.0"] = (
+        t, np.stack([bits((80, 40)), bits((80, 39)), bits((81, 39))]), 1, vec([2], [1.0], [0], [[0, 1, 2]], [2, 2, 2]))
+    # levelsup >= L: every node id is 0, whatever the depth
+    t2 = tree(2, 2, [(0, bits((0, 40)), None), (0, bits((40, 40)), None), (1, bits((0, 40)), 1.0), (1, bits((0, 30)), 2.0),
+                     (2, bits((40, 40)), 3.0), (2, bits((40, 30)), 5.0)])
+    f2 = np.stack([bits((40, 30)), bits((0, 40)), bits((40, 40))])
+    cases["levelsup >= L: every node is 0"] = (t2, f2, 2, vec([0, 2, 3], [1.0 / 9.0, 3.0 / 9.0, 5.0 / 9.0], [0], [[0, 1, 2]], [3, 0, 2]))
+    cases["levelsup > L: every node is 0"] = (t2, f2, 7, vec([0, 2, 3], [1.0 / 9.0, 3.0 / 9.0, 5.0 / 9.0], [0], [[0, 1, 2]], [3, 0, 2]))
+    # ... and one level up the nodes are the root's children, feature indices ascending within a node
+    cases["levelsup = L - 1: the root's children"] = (t2, f2, 1, vec([0, 2, 3], [1.0 / 9.0, 3.0 / 9.0, 5.0 / 9.0], [1, 2], [[1], [0, 2]], [3, 0, 2]))
+    # a leaf at depth 1 with the node wanted at level 2: the reference leaves *nid uninitialised; refused
+    t3 = tree(2, 2, [(0, bits((0, 40)), 1.0), (0, bits((40, 40)), None), (2, bits((40, 40)), 3.0), (2, bits((40, 30)), 5.0)])
+    cases["a leaf shallower than level L - levelsup: refused"] = (t3, np.stack([bits((0, 40))]), 0, None)
+    cases["... and accepted one level up"] = (t3, np.stack([bits((0, 40)), bits((40, 31))]), 1, vec([0, 2], [1.0 / 6.0, 5.0 / 6.0], [1, 2], [[0], [1]], [0, 2]))
+    return cases
+
+
+def malformed():
+    """-> {label: vocab} that gfs_bow_create must refuse"""
+    ok = tree(2, 2, [(0, bits((0, 8)), None), (0, bits((8, 8)), None), (1, bits((0, 20)), 1.5), (1, bits((0, 3)), 2.5),
+                     (2, bits((8, 1)), 3.5), (2, bits((8, 2)), 4.5)])
+    def mod(**kw):
+        v = {k: (a.copy() if isinstance(a, np.ndarray) else a) for k, a in ok.items()}
+        for k, f in kw.items():
+            v[k] = f(v[k]) if callable(f) else f
+        return v
+    def setv(i, x):
+        def f(a):
+            a[i] = x
+            return a
+        return f
+    cases = {
+        # nodes 3 and 4 are each other's only child; everything else hangs from the root
+        "a cycle": dict(ok, parent=np.array([0, 0, 0, 4, 3, 1, 1], np.int32), child_start=np.array([0, 2, 4, 4, 5, 6, 6, 6], np.int32),
+                        children=np.array([1, 2, 5, 6, 4, 3], np.int32), word_id=np.array([-1, -1, 0, -1, -1, 1, 2], np.int32)),
+        "a child listed under two parents": mod(children=setv(5, 3)),
+        "an index out of range": mod(children=setv(2, 7)),
+        "a negative index": mod(children=setv(2, -1)),
+        "the root as a child": mod(children=setv(2, 0)),
+        "a leaf with children": mod(word_id=setv(1, 4)),
+        "an inner node without children": mod(word_id=setv(3, -1)),
+        "a parent that disagrees": mod(parent=setv(3, 2)),
+        "word ids with a gap": mod(word_id=setv(3, 9)),
+        "a word id twice": mod(word_id=setv(3, 1)),
+        "deeper than L": mod(L=1),
+        "k = 0": mod(k=0),
+        "k = 21": mod(k=21),
+        "more children than k": mod(k=1),
+        "L = 11": mod(L=11),
+        "TF weighting": mod(weighting=1),
+        "L2 scoring": mod(scoring=1),
+        "a weight that is not finite": mod(weight=setv(3, np.inf)),
+        "child_start that decreases": mod(child_start=setv(1, 5)),
+        "the root alone": dict(ok, n_nodes=1, child_start=np.zeros(2, np.int32)),
+    }
+    return ok, cases
+
+
+# ---------------------------------------------------------------- seeded problems
+
+@functools.lru_cache(maxsize=None)
+def vocabulary(seed, k, L, stop_frac=0.0, prune_frac=0.0, shuffle_children=False):
+    return synth.bow_vocabulary(seed, k=k, L=L, stop_frac=stop_frac, prune_frac=prune_frac, shuffle_children=shuffle_children)
+
+
+@functools.lru_cache(maxsize=None)
+def problem(seed, k, L, counts, levelsup=None, stop_frac=0.1, prune_frac=0.0, shuffle_children=False, max_flip_bits=12, dup_frac=0.3):
+    """A seeded vocabulary, frames of the given feature counts and their restatement (computed once, shared, left unchanged):
+    -> (vocab, [desc], levelsup, [result])"""
+    v = vocabulary(seed, k, L, stop_frac, prune_frac, shuffle_children)
+    if levelsup is None:
+        levelsup = L - min(rule_validate(v)[1], 2)  # the nodes two levels below the root, or as deep as the shallowest leaf allows
+    descs = [synth.bow_features(seed * 100 + j, v, n, max_flip_bits, dup_frac) for j, n in enumerate(counts)]
+    rc, want = restate(v, descs, levelsup)
+    assert rc == 0
+    return v, descs, levelsup, want
+
+
+def write_vocabulary_text(vocab, path, trailing_newline=True):
+    """The vocabulary in the format of ORBvoc.txt (saveToTextFile): nodes 1.. in id order, `parent is_leaf 32 bytes weight`."""
+    lines = ["%d %d %d %d" % (vocab["k"], vocab["L"], vocab["scoring"], vocab["weighting"])]
+    for i in range(1, vocab["n_nodes"]):
+        lines.append("%d %d %s %s" % (vocab["parent"][i], int(vocab["word_id"][i] >= 0), " ".join(str(int(b)) for b in vocab["desc"][i]),
+                                      repr(float(vocab["weight"][i]))))
+    with open(path, "w") as f:
+        f.write("\n".join(lines) + ("\n" if trailing_newline else ""))
