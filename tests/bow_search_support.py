@@ -84,6 +84,166 @@ def assert_equal(got, want, what=""):
             (what, i, np.nonzero(g["match12"] != w["match12"])[0][:8])
 
 
+# ---------------------------------------------------------------- an independent statement in Python
+
+_POPCOUNT = np.array([bin(i).count("1") for i in range(256)], np.uint8)
+
+
+def python_scan(dists):
+    """The scan of :978-1006 over the distances of the candidates in list order, statement by statement (a candidate that the
+    reference skips is given as 256: it improves on nothing) -> (bestDist1, position of bestIdx2 in the list or -1, bestDist2)"""
+    bestDist1, bestPos2, bestDist2 = 256, -1, 256
+    for i2, dist in enumerate(dists):
+        dist = int(dist)
+        if dist < bestDist1:
+            bestDist2 = bestDist1
+            bestDist1 = dist
+            bestPos2 = i2
+        elif dist < bestDist2:
+            bestDist2 = dist
+    return bestDist1, bestPos2, bestDist2
+
+
+def numpy_scan(d):
+    """python_scan on an int array in three numpy calls: the strict `<` keeps the FIRST position at the minimum; bestDist2 ends as the
+    smallest of all other entries (an equal one included) and of the initial 256."""
+    if len(d) == 0:
+        return 256, -1, 256
+    pos = int(d.argmin())
+    best1 = int(d[pos])
+    if best1 >= 256:
+        return 256, -1, 256
+    best2 = min(int(d[:pos].min()) if pos else 256, int(d[pos + 1:].min()) if pos + 1 < len(d) else 256, 256)
+    return best1, pos, best2
+
+
+def _round_half_away(x):
+    """C's round() of a float that is exact as a double"""
+    x = float(x)
+    return int(np.floor(x + 0.5)) if x >= 0 else -int(np.floor(-x + 0.5))
+
+
+def python_search(prob, detail=False):
+    """An independent statement of ORBmatcher::SearchByBoW(pKF1, pKF2, vpMatches12) in sequential Python, written from the reference's
+    text (src/ORBmatcher.cc:936-1053, ComputeThreeMaxima :2500-2532) and sharing nothing with bow_search_rule.hpp or the C++
+    restatement: the feature vectors as dicts walked in key order with lower_bound, the scan of every idx1 in list order over the
+    candidates that have a map point and are not in vbMatched2 (numpy only computes the node's Hamming distances and the scan's two
+    minima, numpy_scan), TH_LOW, the float32 ratio product, rotHist as thirty lists, the three maxima and the 0.1f cuts.  A bin
+    outside [0, 30) trips the reference's assert; as in DESIGN.md section 22 such a match is in no bin and the check removes it.
+    -> what restate(prob) returns for ONE problem; detail=True adds per key frame 2 `before` (match12 before the orientation check) and
+    `changed`: (idx1, list position of the candidate it would have taken had none been taken before it, or -1) of every idx1 whose
+    outcome a taken candidate changed."""
+    TH_LOW, HISTO_LENGTH = 50, 30
+    factor = f32(1.0) / f32(HISTO_LENGTH)
+    mfNNratio, mbCheckOrientation = f32(prob["nn_ratio"]), bool(prob.get("check_orientation", True))
+    k1 = prob["kf1"]
+    desc1, has1, ang1 = np.asarray(k1["desc"], np.uint8).reshape(-1, 32), np.asarray(k1["has_mp"]), np.asarray(k1["angle"], f32)
+
+    def feature_vector(k):
+        return {int(v): [int(i) for i in k["feat_idx"][a:b]] for v, a, b in zip(k["node_id"], k["node_start"][:-1], k["node_start"][1:])}
+
+    def lower_bound(keys, v):
+        lo, hi = 0, len(keys)
+        while lo < hi:
+            mid = (lo + hi) // 2
+            if keys[mid] < v:
+                lo = mid + 1
+            else:
+                hi = mid
+        return lo
+
+    vFeatVec1 = feature_vector(k1)
+    keys1 = sorted(vFeatVec1)
+    out = []
+    for k2 in prob["kf2"]:
+        desc2, has2, ang2 = np.asarray(k2["desc"], np.uint8).reshape(-1, 32), np.asarray(k2["has_mp"]), np.asarray(k2["angle"], f32)
+        vFeatVec2 = feature_vector(k2)
+        keys2 = sorted(vFeatVec2)
+        vpMatches12 = [-1] * len(desc1)
+        vbMatched2 = np.zeros(len(desc2), bool)
+        rotHist = [[] for _ in range(HISTO_LENGTH)]
+        no_bin, changed = [], []
+        nmatches = 0
+        f1it, f2it = 0, 0
+        while f1it != len(keys1) and f2it != len(keys2):
+            if keys1[f1it] == keys2[f2it]:
+                list1, list2 = vFeatVec1[keys1[f1it]], np.array(vFeatVec2[keys2[f2it]], np.int64)
+                eligible = [idx1 for idx1 in list1 if has1[idx1]]  # `if (!pMP1) continue; if (pMP1->isBad()) continue;`
+                if eligible and len(list2):
+                    dist = _POPCOUNT[desc1[eligible][:, None, :] ^ desc2[list2][None, :, :]].sum(-1, dtype=np.int32)  # DescriptorDistance
+                    pMP2 = has2[list2] != 0
+                    for row, idx1 in enumerate(eligible):
+                        usable = pMP2 & ~vbMatched2[list2]  # `if (vbMatched2[idx2] || !pMP2) continue;`
+                        bestDist1, pos, bestDist2 = numpy_scan(np.where(usable, dist[row], 256))
+                        matched = False
+                        if bestDist1 < TH_LOW:
+                            if f32(bestDist1) < mfNNratio * f32(bestDist2):
+                                bestIdx2 = int(list2[pos])
+                                vpMatches12[idx1] = bestIdx2
+                                vbMatched2[bestIdx2] = True
+                                matched = True
+                                if mbCheckOrientation:
+                                    rot = ang1[idx1] - ang2[bestIdx2]
+                                    if rot < 0.0:
+                                        rot = rot + f32(360.0)
+                                    b = _round_half_away(f32(rot * factor))
+                                    if b == HISTO_LENGTH:
+                                        b = 0
+                                    (rotHist[b] if 0 <= b < HISTO_LENGTH else no_bin).append(idx1)
+                                nmatches += 1
+                        if detail:
+                            fd1, fpos, fd2 = numpy_scan(np.where(pMP2, dist[row], 256))
+                            free = fd1 < TH_LOW and bool(f32(fd1) < mfNNratio * f32(fd2))
+                            if free != matched or (matched and fpos != pos):
+                                changed.append((idx1, fpos if free else -1))
+                f1it += 1
+                f2it += 1
+            elif keys1[f1it] < keys2[f2it]:
+                f1it = lower_bound(keys1, keys2[f2it])
+            else:
+                f2it = lower_bound(keys2, keys1[f1it])
+        before = np.array(vpMatches12, np.int32).reshape(-1)
+        if mbCheckOrientation:
+            max1 = max2 = max3 = 0
+            ind1 = ind2 = ind3 = -1
+            for i in range(HISTO_LENGTH):
+                s = len(rotHist[i])
+                if s > max1:
+                    max3, max2, max1 = max2, max1, s
+                    ind3, ind2, ind1 = ind2, ind1, i
+                elif s > max2:
+                    max3, max2 = max2, s
+                    ind3, ind2 = ind2, i
+                elif s > max3:
+                    max3, ind3 = s, i
+            if f32(max2) < f32(0.1) * f32(max1):
+                ind2 = ind3 = -1
+            elif f32(max3) < f32(0.1) * f32(max1):
+                ind3 = -1
+            for i in range(HISTO_LENGTH):
+                if i == ind1 or i == ind2 or i == ind3:
+                    continue
+                for idx1 in rotHist[i]:
+                    vpMatches12[idx1] = -1
+                    nmatches -= 1
+            for idx1 in no_bin:
+                vpMatches12[idx1] = -1
+                nmatches -= 1
+        o = dict(match12=np.array(vpMatches12, np.int32).reshape(-1), n_matches=nmatches)
+        if detail:
+            o.update(before=before, changed=changed)
+        out.append(o)
+    return out
+
+
+def list_positions(k2):
+    """-> position of every key-point of a key frame in its node's list (-1: in no list)"""
+    pos = np.full(len(k2["angle"]), -1, np.int64)
+    for a, b in zip(k2["node_start"][:-1], k2["node_start"][1:]):
+        pos[k2["feat_idx"][a:b]] = np.arange(b - a)
+    return pos
+
+
 # ---------------------------------------------------------------- hand-built cases
 
 def bits(*ranges):
@@ -217,3 +377,20 @@ def problem(seed, n_kp, n_kp2, n_kf2=1, n_nodes=1, **kw):
     """A seeded problem of the GPU tests and its restatement (computed once, shared, left unchanged)."""
     p = synth.bow_search_problem(seed, n_kp=n_kp, n_kf2=n_kf2, n_nodes=n_nodes, n_kp2=n_kp2, **kw)
     return p, restate(p)
+
+
+# ---------------------------------------------------------------- key frames of up to 4096 key-points
+
+def capacity_cases():
+    """Problems at the sizes where k_bow_search first uses the high bits of a lane's 64-bit chunk mask and a second stride of its
+    per-key-point loops, each the smallest such shape: -> {label: (problem, restatement)}.  The seeds were chosen on the CPU so that the
+    restatement accepts matches at the list positions and key-point indices that tests/test_bow_capacity_cases.py asserts."""
+    one = dict(n_nodes=1, one_sided_frac=0.0, wrong_node_frac=0.0)
+    return {
+        "one node, n2 = 4096: 64 chunks": problem(21, 200, 4096, n_kf2=2, **one),
+        "one node, n2 = 2048: 32 chunks": problem(3, 200, 2048, n_kf2=2, **one),
+        "one node, n2 = 2049: 33 chunks": problem(11, 200, 2049, n_kf2=2, **one),
+        "N1 = 1025 over 100 nodes": problem(3, 1025, 1025, n_kf2=4, n_nodes=100),
+        "N1 = 4096 over 100 nodes": problem(3, 4096, 4096, n_kf2=2, n_nodes=100),
+        "one key-point": problem(8, 1, 1, n_kf2=3, no_mp_frac=0.0, max_flip_bits=30, **one),
+    }

@@ -400,6 +400,102 @@ def problem(seed, k, L, counts, levelsup=None, stop_frac=0.1, prune_frac=0.0, sh
     return v, descs, levelsup, want
 
 
+# ---------------------------------------------------------------- frames of up to 4096 features, entries of up to 4096 words
+
+CAPACITY_SIZES = (512, 513, 1024, 1025, 2048, 2049, 4095, 4096)
+TIE_PAIRS = ((0, 16), (3, 19), (2, 17))  # positions under a root of 20 children: one lane's two rounds twice, then lane 2's first round against lane 1's second
+
+
+def sort_width(n):
+    """The keys k_bow_vectors sorts for a frame of n features: max(64, the next power of two >= n)"""
+    return max(64, 1 << (int(n) - 1).bit_length())
+
+
+def node_depths(vocab):
+    """-> depth of every node (the root 0)"""
+    cs, ch = vocab["child_start"], vocab["children"]
+    depth, order, at = np.zeros(vocab["n_nodes"], np.int64), [0], 0
+    while at < len(order):
+        n = order[at]
+        at += 1
+        for c in ch[cs[n]:cs[n + 1]]:
+            depth[c] = depth[n] + 1
+            order.append(int(c))
+    return depth
+
+
+def tie_tree(lo, hi, lower_moved):
+    """Twenty leaves under the root, leaf c the word c: positions lo and hi are 4 bits from the zero descriptor (lo 5 bits when moved
+    away), every other position c 30 + c bits."""
+    return tree(20, 1, [(0, bits((0, 5 if c == lo and lower_moved else 4)) if c in (lo, hi) else bits((0, 30 + c)), 1.0 + c) for c in range(20)])
+
+
+@functools.lru_cache(maxsize=None)
+def capacity_cases():
+    """Frames at the sizes where k_bow_vectors first fills its 1024 threads, strides its sort and runs long serial sums, and trees where
+    k_bow_descend runs six levels and ties across its two rounds of 16 lanes: -> {label: dict(vocab, descs, levelsup, want (the
+    restatement, computed once, shared, left unchanged), hand (the answer stated by hand, or None))}.  The seeded frames use one tree
+    of 8^4 = 4096 words under three weightings: no stopped word, 3 % stopped, every word stopped."""
+    cases = {}
+
+    def add(label, v, descs, levelsup, hand=None):
+        rc, want = restate(v, descs, levelsup)
+        assert rc == 0, label
+        cases[label] = dict(vocab=v, descs=descs, levelsup=levelsup, want=want, hand=hand)
+
+    none, few, every = vocabulary(5, 8, 4, 0.0), vocabulary(5, 8, 4, 0.03), vocabulary(5, 8, 4, 1.0)
+    for j, n in enumerate(CAPACITY_SIZES):
+        add("n = %d" % n, few, [synth.bow_features(600 + j, few, n, 12, 0.3)], 2)
+    full = synth.bow_features(500, none, 4096, 12, 0.3)
+    add("n = 4096, no stopped word", none, [full], 2)
+    add("n = 4096, 3 % of the words stopped", few, [full], 2)
+    add("n = 4096, every word stopped", every, [full], 2)
+    leaf = int(np.nonzero(none["word_id"] == 1234)[0][0])
+    add("4096 copies of one descriptor", none, [np.ascontiguousarray(np.repeat(none["desc"][leaf][None, :], 4096, 0))], 2)
+    ragged = [synth.bow_features(700 + j, few, n, 12, 0.3) for j, n in enumerate((4096, 0, 1, 2049))]
+    add("a batch of 4096, 0, 1 and 2049 features", few, ragged, 2)
+    add("... then 5 features on the same handle", few, [ragged[3][:5].copy()], 2)
+    v, descs, levelsup, _ = problem(7, 3, 6, (300,), levelsup=4)
+    add("k = 3, L = 6, levelsup = 4", v, descs, levelsup)
+    v, descs, levelsup, _ = problem(3, 10, 6, (300,), prune_frac=0.8, shuffle_children=True)
+    add("k = 10, L = 6, pruned, shuffled children", v, descs, levelsup)
+    for lo, hi in TIE_PAIRS:
+        add("k = 20: positions %d and %d tie, the lower wins" % (lo, hi), tie_tree(lo, hi, False), [np.stack([bits()])], 1,
+            vec([lo], [1.0], [0], [[0]], [lo]))
+        add("k = 20: position %d one bit further, position %d wins" % (lo, hi), tie_tree(lo, hi, True), [np.stack([bits()])], 1,
+            vec([hi], [1.0], [0], [[0]], [hi]))
+    return cases
+
+
+CAPACITY_ID_RANGE = 20000
+
+
+@functools.lru_cache(maxsize=None)
+def capacity_database():
+    """Vectors of up to 4096 words for the database query: -> (queries {label: (ids, values)}, entries {label: (ids, values)}, stores
+    {max_entries: [(slot, entry label) in add order]})."""
+    R = CAPACITY_ID_RANGE
+    q = bow_vector(1, 4096, R)
+    others = np.setdiff1d(np.arange(R), q[0])
+    entries = {
+        "4095 words": bow_vector(2, 4095, R),
+        "4096 words": bow_vector(3, 4096, R),
+        "identical to the query": (q[0].copy(), q[1].copy()),
+        "one common word, the last id of both": bow_vector(4, 0, 0, ids=np.concatenate([others[others < q[0][-1]][:40], q[0][-1:]])),
+        "4096 words, none common": bow_vector(5, 0, 0, ids=others[:4096]),
+        "one word": (q[0][2000:2001].copy(), np.array([1.0])),
+    }
+    queries = {"4096 words": q, "one word, the last of the 4096-word entry": (entries["4096 words"][0][-1:].copy(), np.array([1.0]))}
+    names = list(entries)
+    stores = {
+        1: [(0, "identical to the query")],
+        4: [(0, "4095 words"), (3, "4096 words"), (1, "one common word, the last id of both"), (2, "4096 words, none common")],
+        5: [(4, "4096 words"), (0, "one word"), (2, "identical to the query"), (3, "4096 words, none common"), (1, "4095 words")],
+        70: [(s, names[i]) for i, s in enumerate((69, 0, 33, 7, 64, 5))],
+    }
+    return queries, entries, stores
+
+
 def write_vocabulary_text(vocab, path, trailing_newline=True):
     """The vocabulary in the format of ORBvoc.txt (saveToTextFile): nodes 1.. in id order, `parent is_leaf 32 bytes weight`."""
     lines = ["%d %d %d %d" % (vocab["k"], vocab["L"], vocab["scoring"], vocab["weighting"])]
