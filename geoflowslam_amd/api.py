@@ -259,6 +259,71 @@ def sim3_ransac_result(S, keep, n):
                 inlier=keep["inlier"][:n].copy(), counts=keep["counts"].copy())
 
 
+class ImuState(C.Structure):
+    _fields_ = [("Rwb", C.c_double * 9), ("twb", C.c_double * 3), ("Rcw", C.c_double * 9), ("tcw", C.c_double * 3), ("v", C.c_double * 3),
+                ("bg", C.c_double * 3), ("ba", C.c_double * 3)]
+
+
+class ImuEstimate(C.Structure):
+    _fields_ = [("Rwb", C.c_double * 9), ("twb", C.c_double * 3), ("v", C.c_double * 3), ("bg", C.c_double * 3), ("ba", C.c_double * 3)]
+
+
+class PoseInertialProblem(C.Structure):
+    _fields_ = [("mode", C.c_int32), ("n_obs", C.c_int32), ("n_rounds", C.c_int32), ("rec_init", C.c_int32), ("xw", C.c_void_p), ("obs", C.c_void_p),
+                ("inv_sigma2", C.c_void_p), ("stereo", C.c_void_p), ("close", C.c_void_p), ("fx", C.c_double), ("fy", C.c_double),
+                ("cx", C.c_double), ("cy", C.c_double), ("bf", C.c_double), ("Rcb", C.c_double * 9), ("tcb", C.c_double * 3),
+                ("Rbc", C.c_double * 9), ("tbc", C.c_double * 3), ("cur", ImuState), ("other", ImuState), ("dR", C.c_float * 9),
+                ("dV", C.c_float * 3), ("dP", C.c_float * 3), ("JRg", C.c_float * 9), ("JVg", C.c_float * 9), ("JVa", C.c_float * 9),
+                ("JPg", C.c_float * 9), ("JPa", C.c_float * 9), ("preint_bg", C.c_float * 3), ("preint_ba", C.c_float * 3), ("dT", C.c_float),
+                ("info_inertial", C.c_double * 81), ("info_gyro_rw", C.c_double * 9), ("info_acc_rw", C.c_double * 9),
+                ("prior_Rwb", C.c_double * 9), ("prior_twb", C.c_double * 3), ("prior_vwb", C.c_double * 3), ("prior_bg", C.c_double * 3),
+                ("prior_ba", C.c_double * 3), ("prior_H", C.c_double * 225)]
+
+
+class PoseInertialSolution(C.Structure):
+    _fields_ = [("cur", ImuEstimate), ("other", ImuEstimate), ("outlier", C.c_void_p), ("n_good", C.c_int32), ("n_inliers", C.c_int32),
+                ("rounds_run", C.c_int32), ("avg_reproj", C.c_float), ("H", C.c_double * 900)]
+
+
+POSE_INERTIAL_LAST_KEYFRAME, POSE_INERTIAL_LAST_FRAME = 0, 1  # GFS_POSE_INERTIAL_* (include/gfs_abi.h)
+
+
+def _fill(dst, src):
+    a = np.ascontiguousarray(src).ravel()
+    assert len(a) == len(dst), (len(a), len(dst))
+    dst[:] = a.tolist()
+
+
+def pose_inertial_structs(prob):
+    """ctypes views of one problem dict (synth.pose_inertial_problem; shared with the CPU restatement's tests).  Arrays are row-major;
+    keys as the fields of gfs_pose_inertial_problem, `cur` / `other` dicts of Rwb, twb, Rcw, tcw, v, bg, ba."""
+    P, S = PoseInertialProblem(), PoseInertialSolution()
+    n = int(prob["n_obs"])
+    keep = dict(xw=np.ascontiguousarray(prob["xw"], np.float64).reshape(-1, 3), obs=np.ascontiguousarray(prob["obs"], np.float64).reshape(-1, 3),
+                inv_sigma2=np.ascontiguousarray(prob["inv_sigma2"], np.float32), stereo=np.ascontiguousarray(prob["stereo"], np.uint8),
+                close=np.ascontiguousarray(prob["close"], np.uint8), outlier=np.zeros(max(n, 1), np.uint8))
+    P.mode, P.n_obs, P.n_rounds, P.rec_init = int(prob["mode"]), n, int(prob["n_rounds"]), int(prob["rec_init"])
+    for name in ("xw", "obs", "inv_sigma2", "stereo", "close"):
+        setattr(P, name, keep[name].ctypes.data if n > 0 or len(keep[name]) else None)
+    for name in ("fx", "fy", "cx", "cy", "bf", "dT"):
+        setattr(P, name, float(prob[name]))
+    for name in ("Rcb", "tcb", "Rbc", "tbc", "dR", "dV", "dP", "JRg", "JVg", "JVa", "JPg", "JPa", "preint_bg", "preint_ba", "info_inertial",
+                 "info_gyro_rw", "info_acc_rw", "prior_Rwb", "prior_twb", "prior_vwb", "prior_bg", "prior_ba", "prior_H"):
+        _fill(getattr(P, name), prob[name])
+    for end in ("cur", "other"):
+        for name in ("Rwb", "twb", "Rcw", "tcw", "v", "bg", "ba"):
+            _fill(getattr(getattr(P, end), name), prob[end][name])
+    S.outlier = keep["outlier"].ctypes.data
+    return P, S, keep, n
+
+
+def pose_inertial_result(S, keep, n, mode):
+    D = 30 if mode == POSE_INERTIAL_LAST_FRAME else 15
+    est = lambda e: dict(Rwb=np.array(e.Rwb[:]).reshape(3, 3), twb=np.array(e.twb[:]), v=np.array(e.v[:]), bg=np.array(e.bg[:]), ba=np.array(e.ba[:]))
+    return dict(cur=est(S.cur), other=est(S.other), outlier=keep["outlier"][:max(n, 0)].copy(), n_good=int(S.n_good), n_inliers=int(S.n_inliers),
+                rounds_run=int(S.rounds_run), avg_reproj=np.float32(S.avg_reproj), H=np.array(S.H[:D * D]).reshape(D, D))
+
+
 class ClaheConfig(C.Structure):
     _fields_ = [("clip_limit", C.c_double), ("tiles_x", C.c_int32), ("tiles_y", C.c_int32), ("residual_variant", C.c_int32)]
 
@@ -899,6 +964,7 @@ ABI_SYMBOLS = [
     "gfs_essential_graph_last_info", "gfs_test_essential_graph_first_trial", "gfs_test_essential_graph_lists",
     "gfs_sim3_opt_create", "gfs_sim3_opt_destroy", "gfs_sim3_optimize", "gfs_test_glibc_exp",
     "gfs_sim3_ransac_iterations", "gfs_sim3_ransac_create", "gfs_sim3_ransac_solve", "gfs_sim3_ransac_destroy",
+    "gfs_pose_inertial_create", "gfs_pose_inertial_optimize", "gfs_pose_inertial_destroy",
     "gfs_frame_create", "gfs_frame_destroy", "gfs_depth_to_cloud", "gfs_depth_to_cloud_batch_device", "gfs_depth_convert_u16_batch_device", "gfs_stereo_from_rgbd",
     "gfs_stereo_from_rgbd_batch_device",
     "gfs_pose_create", "gfs_pose_destroy", "gfs_pose_optimize", "gfs_pose_set_sum_order",
@@ -1030,6 +1096,10 @@ def lib():
             L.gfs_sim3_opt_destroy.argtypes = [vp]
             L.gfs_sim3_optimize.argtypes = [vp, vp, i, vp]
             L.gfs_test_glibc_exp.argtypes = [i, vp, i, vp]
+        if hasattr(L, "gfs_pose_inertial_create"):
+            L.gfs_pose_inertial_create.argtypes = [i, i, i, C.POINTER(vp)]
+            L.gfs_pose_inertial_destroy.argtypes = [vp]
+            L.gfs_pose_inertial_optimize.argtypes = [vp, vp, i, vp]
         if hasattr(L, "gfs_sim3_ransac_create"):
             L.gfs_sim3_ransac_iterations.argtypes = [i, C.c_double, i, i]
             L.gfs_sim3_ransac_create.argtypes = [i, i, i, i, C.POINTER(vp)]
@@ -2467,6 +2537,40 @@ class Sim3RansacSolver:
             keeps.append((keep, n))
         _check(lib().gfs_sim3_ransac_solve(self.h, PP, B, SS), "gfs_sim3_ransac_solve")
         res = [sim3_ransac_result(SS[f], *keeps[f]) for f in range(B)]
+        return res[0] if single else res
+
+
+class PoseInertialOptimizer:
+    """Optimizer::PoseInertialOptimizationLastKeyFrame / ...LastFrame (reference src/Optimizer.cc:5899-6283, 6762-7171) on flattened
+    problems (gfs_pose_inertial_problem in include/gfs_abi.h): a batch of problems, the two modes mixed freely,
+    in one device call; every output is the sequential restatement's byte for byte."""
+
+    def __init__(self, max_obs=2048, max_batch=8, device=0):
+        self.h = C.c_void_p()
+        _check(lib().gfs_pose_inertial_create(device, int(max_obs), int(max_batch), C.byref(self.h)), "gfs_pose_inertial_create")
+
+    def close(self):
+        if getattr(self, "h", None) and _lib is not None:
+            _lib.gfs_pose_inertial_destroy(self.h)
+        self.h = None
+
+    __del__ = close
+
+    def optimize(self, problems):
+        """problems: one problem dict or a list of them (pose_inertial_structs) -> result dict(s): cur / other (Rwb, twb, v, bg, ba as
+        doubles), outlier [n], n_good (the reference's return value), n_inliers, rounds_run, avg_reproj (float32), H [15, 15] or
+        [30, 30] before Marginalize.  Raises GfsError (GFS_ERR_CAPACITY / GFS_ERR_INVALID_ARG) on a refusal; the handle stays usable."""
+        single = isinstance(problems, dict)
+        probs = [problems] if single else list(problems)
+        B = len(probs)
+        PP, SS = (PoseInertialProblem * max(B, 1))(), (PoseInertialSolution * max(B, 1))()
+        keeps = []
+        for f, prob in enumerate(probs):
+            P, S, keep, n = pose_inertial_structs(prob)
+            PP[f], SS[f] = P, S
+            keeps.append((keep, n, P.mode))
+        _check(lib().gfs_pose_inertial_optimize(self.h, PP, B, SS), "gfs_pose_inertial_optimize")
+        res = [pose_inertial_result(SS[f], *keeps[f]) for f in range(B)]
         return res[0] if single else res
 
 

@@ -21,6 +21,8 @@
 #endif
 #endif
 
+#include "so3_quat_rule.hpp"
+
 namespace gfs_s3r {
 
 constexpr double kChi2 = 9.210;            // mvnMaxError = 9.210 * sigma2 (:95-96)
@@ -118,18 +120,8 @@ GFS_HD void largest_eigenvector(const float (&Nf)[4][4], double* q) {  // q = (w
 // matrix of the unit quaternion of rule A, computed in double and rounded to float once per entry: the same rotation, more
 // accurate in the last bits.  The reference's vec.norm() == 0 branch (the vector of 1e-6) is the quaternion (1, 0, 0, 0): its matrix
 // here is the identity exactly, which the formula below gives without a branch.
-GFS_HD void quaternion_matrix(const double* q, float* R) {  // R row-major
-  const double w = q[0], x = q[1], y = q[2], z = q[3];
-  R[0] = (float)(1.0 - 2.0 * (y * y + z * z));
-  R[1] = (float)(2.0 * (x * y - w * z));
-  R[2] = (float)(2.0 * (x * z + w * y));
-  R[3] = (float)(2.0 * (x * y + w * z));
-  R[4] = (float)(1.0 - 2.0 * (x * x + z * z));
-  R[5] = (float)(2.0 * (y * z - w * x));
-  R[6] = (float)(2.0 * (x * z - w * y));
-  R[7] = (float)(2.0 * (y * z + w * x));
-  R[8] = (float)(1.0 - 2.0 * (x * x + y * y));
-}
+// (the formula lives in so3_quat_rule.hpp, shared with rule E of pose_inertial_rule.hpp)
+using gfs_so3::quaternion_matrix;
 
 // ComputeCentroid (:282-287): C = P.rowwise().sum() (rule C: columns left to right), C / P.cols() (the Index becomes a float: Eigen
 // promotes a scalar operand to the expression's scalar type), Pr.col(i) = P.col(i) - C.  P[c] is column c, a point.

@@ -3647,6 +3647,125 @@ class BowDatabaseDevice {
   gfs_bow_db* h_ = nullptr;
 };
 
+// ------------------------------------------------------------------------------------------------------------------------
+// int Optimizer::PoseInertialOptimizationLastKeyFrame(Frame* pFrame, bool bRecInit, const bool bFrame2FrameReprojError,
+//                                                     const bool bFrame2MapReprojError, const int nIterations)   src/Optimizer.cc:5899-6283
+// int Optimizer::PoseInertialOptimizationLastFrame(...same...)                                                   :6762-7171
+// the two calls that end Tracking::TrackLocalMap once the IMU is initialised (src/Tracking.cc:3763-3798), around one flat solve
+// (include/gfs_abi.h section 19).
+//   gather:     the visual edges in the index order of mvpMapPoints (every non-NULL pMP; mvbOutlier[i] = false): GetWorldPos, mvKeysUn,
+//               mvuRight, mvInvLevelSigma2[octave], stereo = mvuRight[i] >= 0, close = mTrackDepth < 10.f; both ends of the inertial
+//               edge, the calibration, the preintegration, the information matrices and (frame mode) pFp->mpcpi through `Access`, which
+//               runs the reference's own constructors on the reference's own types (Eigen is not restated here).
+//   solve:      `solve(problem, solution)`: PoseInertialDevice::solve below (gfs_pose_inertial_optimize on the GPU).
+//   write back: mvbOutlier, SetImuPoseVelocity and mImuBias (the casts are Access's), the reprojection error under the two flags, the
+//               new pFrame->mpcpi from the returned H with the reference's own Optimizer::Marginalize and ConstraintPoseImu
+//               (Access::new_constraint), and in frame mode `delete pFp->mpcpi; pFp->mpcpi = NULL`.
+// Refused (std::runtime_error, nothing touched): Nleft != -1, a camera that is not the pinhole, and in frame mode a missing
+// pFp->mpcpi, which the reference would dereference.
+// Frame: N, Nleft, mvpMapPoints, mvbOutlier, mvKeysUn, mvuRight, mvInvLevelSigma2, mpLastKeyFrame, mpPrevFrame, mpImuPreintegrated,
+// mpImuPreintegratedFrame, mpcpi, SetFrame2FrameReprojError, SetFrame2MapReprojError; MapPoint: mTrackDepth; and of `Access`:
+//     static bool is_pinhole(const Frame*);
+//     static void world_pos(const MapPoint*, float X[3]);
+//     static void calibration(const Frame*, gfs_pose_inertial_problem&);                 // fx fy cx cy bf Rcb tcb Rbc tbc
+//     static void state(const Frame*, gfs_imu_state&); static void state(const KeyFrame*, gfs_imu_state&);  // ImuCamPose + Vertex* ctors
+//     static void preintegration(const Preintegrated*, gfs_pose_inertial_problem&);      // dR .. dT and info_inertial (EdgeInertial's ctor)
+//     static void random_walk_information(const Preintegrated*, double info_gyro[9], double info_acc[9]);
+//     static void prior(const Constraint*, gfs_pose_inertial_problem&);                  // prior_Rwb .. prior_H
+//     static void set_imu_pose_velocity_bias(Frame*, const gfs_imu_estimate&);
+//     static Constraint* new_constraint(const gfs_imu_estimate&, const double* H, int mode);  // mode 1: Marginalize(H, 0, 14) first
+// ------------------------------------------------------------------------------------------------------------------------
+template <class Access, class Frame, class Solve>
+int PoseInertialOptimization(Solve&& solve, int mode, Frame* pFrame, bool bRecInit, const bool bFrame2FrameReprojError,
+                             const bool bFrame2MapReprojError, const int nIterations) {
+  const bool frame_mode = mode == GFS_POSE_INERTIAL_LAST_FRAME;
+  if (pFrame->Nleft != -1) throw std::runtime_error("PoseInertialOptimization: two-camera frames (Nleft != -1) are not supported");
+  if (!Access::is_pinhole(pFrame)) throw std::runtime_error("PoseInertialOptimization: only the pinhole camera is supported");
+  if (frame_mode && !pFrame->mpPrevFrame->mpcpi) throw std::runtime_error("PoseInertialOptimization: pFp->mpcpi does not exist");
+  const int N = pFrame->N;
+  std::vector<int> idx;
+  std::vector<double> xw, obs;
+  std::vector<float> w;
+  std::vector<uint8_t> st, close;
+  for (int i = 0; i < N; i++) {
+    auto* pMP = pFrame->mvpMapPoints[i];
+    if (!pMP) continue;
+    pFrame->mvbOutlier[i] = false;
+    const auto& kpUn = pFrame->mvKeysUn[i];
+    const bool stereo = !(pFrame->mvuRight[i] < 0);  // (!bRight && mvuRight[i] < 0) is the mono branch (:5963)
+    float X[3];
+    Access::world_pos(pMP, X);
+    for (int k = 0; k < 3; k++) xw.push_back((double)X[k]);
+    obs.push_back((double)kpUn.pt.x);
+    obs.push_back((double)kpUn.pt.y);
+    obs.push_back((double)pFrame->mvuRight[i]);
+    w.push_back(pFrame->mvInvLevelSigma2[kpUn.octave]);  // / uncertainty2 == 1 for the pinhole
+    st.push_back(stereo ? 1 : 0);
+    close.push_back(pMP->mTrackDepth < 10.f ? 1 : 0);
+    idx.push_back(i);
+  }
+  const int n = (int)idx.size();
+  gfs_pose_inertial_problem P{};
+  P.mode = mode;
+  P.n_obs = n;
+  P.n_rounds = nIterations;
+  P.rec_init = bRecInit ? 1 : 0;
+  P.xw = xw.data(), P.obs = obs.data(), P.inv_sigma2 = w.data(), P.stereo = st.data(), P.close = close.data();
+  Access::calibration(pFrame, P);
+  Access::state(pFrame, P.cur);
+  if (frame_mode) {
+    Access::state(pFrame->mpPrevFrame, P.other);
+    Access::preintegration(pFrame->mpImuPreintegratedFrame, P);
+    Access::prior(pFrame->mpPrevFrame->mpcpi, P);
+  } else {
+    Access::state(pFrame->mpLastKeyFrame, P.other);
+    Access::preintegration(pFrame->mpImuPreintegrated, P);
+  }
+  Access::random_walk_information(pFrame->mpImuPreintegrated, P.info_gyro_rw, P.info_acc_rw);  // mpImuPreintegrated in BOTH modes (:6961)
+  std::vector<uint8_t> outlier((size_t)std::max(n, 1));
+  gfs_pose_inertial_solution S{};
+  S.outlier = outlier.data();
+  solve(P, S);
+  for (int k = 0; k < n; k++) pFrame->mvbOutlier[idx[k]] = outlier[k] != 0;
+  if (bFrame2FrameReprojError) pFrame->SetFrame2FrameReprojError(S.avg_reproj);
+  if (bFrame2MapReprojError) pFrame->SetFrame2MapReprojError(S.avg_reproj);
+  Access::set_imu_pose_velocity_bias(pFrame, S.cur);
+  pFrame->mpcpi = Access::new_constraint(S.cur, S.H, mode);
+  if (frame_mode) {
+    delete pFrame->mpPrevFrame->mpcpi;
+    pFrame->mpPrevFrame->mpcpi = nullptr;
+  }
+  return S.n_good;
+}
+template <class Access, class Frame, class Solve>
+int PoseInertialOptimizationLastKeyFrame(Solve&& solve, Frame* pFrame, bool bRecInit = false, const bool bFrame2FrameReprojError = false,
+                                         const bool bFrame2MapReprojError = false, const int nIterations = 4) {
+  return PoseInertialOptimization<Access>(solve, GFS_POSE_INERTIAL_LAST_KEYFRAME, pFrame, bRecInit, bFrame2FrameReprojError, bFrame2MapReprojError,
+                                          nIterations);
+}
+template <class Access, class Frame, class Solve>
+int PoseInertialOptimizationLastFrame(Solve&& solve, Frame* pFrame, bool bRecInit = false, const bool bFrame2FrameReprojError = false,
+                                      const bool bFrame2MapReprojError = false, const int nIterations = 4) {
+  return PoseInertialOptimization<Access>(solve, GFS_POSE_INERTIAL_LAST_FRAME, pFrame, bRecInit, bFrame2FrameReprojError, bFrame2MapReprojError,
+                                          nIterations);
+}
+
+// numeric core of both: one problem (or a batch) on the device
+class PoseInertialDevice {
+ public:
+  explicit PoseInertialDevice(int max_obs = 4096, int max_batch = 1, int device = 0) {
+    check(gfs_pose_inertial_create(device, max_obs, max_batch, &h_), "gfs_pose_inertial_create");
+  }
+  ~PoseInertialDevice() { gfs_pose_inertial_destroy(h_); }
+  PoseInertialDevice(const PoseInertialDevice&) = delete;
+  PoseInertialDevice& operator=(const PoseInertialDevice&) = delete;
+  void solve(const gfs_pose_inertial_problem& p, gfs_pose_inertial_solution& s) { check(gfs_pose_inertial_optimize(h_, &p, 1, &s), "gfs_pose_inertial_optimize"); }
+  void solve(const gfs_pose_inertial_problem* p, int B, gfs_pose_inertial_solution* s) { check(gfs_pose_inertial_optimize(h_, p, B, s), "gfs_pose_inertial_optimize"); }
+
+ private:
+  gfs_pose_inertial* h_ = nullptr;
+};
+
 }  // namespace gfs_host
 
 // The drop-ins written against the reference's own types (cv::Mat, cv::KeyPoint, Eigen, Sophus, ORB_SLAM3::ORBextractor as a base

@@ -1498,3 +1498,122 @@ def sim3_ransac_problem(seed, n_pairs=150, inlier_share=0.6, fix_scale=True, noi
                 max_err2=max_err[rng.integers(0, n_levels, n)], cam1=np.array([fx, fy, cx, cy], f32), cam2=np.array([fx, fy, cx, cy], f32),
                 fix_scale=bool(fix_scale), min_inliers=int(min_inliers), n_iterations=H, draws=draws, true_R=R, true_t=t, true_s=s_true,
                 outlier=outlier)
+
+
+def _exp_so3(w):
+    th = np.linalg.norm(w)
+    W = np.array([[0, -w[2], w[1]], [w[2], 0, -w[0]], [-w[1], w[0], 0]])
+    if th < 1e-12:
+        return np.eye(3) + W
+    return np.eye(3) + np.sin(th) / th * W + (1 - np.cos(th)) / th ** 2 * (W @ W)
+
+
+def _f32(a):
+    return np.asarray(a, np.float64).astype(np.float32).astype(np.float64)
+
+
+def _spd(rng, diag, mix=0.05):
+    """A dense symmetric positive definite matrix with the given eigenvalues, turned a little away from the axes."""
+    n = len(diag)
+    Q, _ = np.linalg.qr(np.eye(n) + mix * rng.normal(size=(n, n)))
+    M = Q @ np.diag(np.asarray(diag, np.float64)) @ Q.T
+    return (M + M.T) / 2
+
+
+POSE_INERTIAL_LAST_KEYFRAME, POSE_INERTIAL_LAST_FRAME = 0, 1  # GFS_POSE_INERTIAL_* (include/gfs_abi.h)
+
+
+def pose_inertial_problem(seed, mode, n_obs=300, outlier_share=0.15, stereo_share=0.85, preint_noise=1.0, inconsistent=False, n_rounds=4,
+                          rec_init=False, dt=None, outlier_px=25.0, pose_error=1.0, depth=(1.0, 14.0), start=None):
+    """Synthetic Optimizer::PoseInertialOptimizationLastKeyFrame (mode 0) / ...LastFrame (mode 1) problem (include/gfs_abi.h section 19):
+    a body that turns and accelerates for `dt` seconds between the other end of the inertial edge (the last key frame, or the previous
+    frame) and the current frame; a preintegration made from that motion with noise `preint_noise` times its covariance
+    (`inconsistent`: off by several degrees and decimetres a second, so that chi2IMU > 15 -- the knob for the 1e-2 branch);
+    `n_obs` map points seen from the true current pose, pixel noise by octave, `outlier_share` gross outliers (a share near 1 is
+    the knob for few inliers), `stereo_share` with depth.  The current frame's estimate starts `pose_error` times a
+    motion-model error away from the truth.  `start` (Rwb, twb, v, bg, ba): the true state of the other end, to chain problems.
+    Returns the fields of gfs_pose_inertial_problem plus the truth."""
+    rng = np.random.default_rng(seed)
+    frame = mode == POSE_INERTIAL_LAST_FRAME
+    dt = float(np.float32((0.05 if frame else 0.4) if dt is None else dt))
+    g = np.array([0.0, 0.0, -float(np.float32(9.81))])
+    fx = fy = np.float64(np.float32(607.0))
+    cx, cy = np.float64(np.float32(319.5)), np.float64(np.float32(239.5))
+    bf = np.float64(np.float32(0.0745 * 607.0))
+    # camera <- body: the camera looks along the body's x, with a small mounting error; floats widened, as Sophus::SE3f mTcb is
+    Rcb = _f32(np.array([[0.0, -1, 0], [0, 0, -1], [1, 0, 0]]) @ _rot(*(0.02 * rng.normal(size=3))))
+    tcb = _f32(0.05 * rng.normal(size=3))
+    Rbc, tbc = Rcb.T.copy(), _f32(-Rcb.T @ tcb)
+    # the true motion
+    Rwb1 = _rot(0.05 * rng.normal(), 0.05 * rng.normal(), rng.uniform(-np.pi, np.pi))
+    p1, v1 = rng.uniform(-2, 2, 3), np.array([0.8, 0.1, 0.02]) * rng.normal(size=3)
+    omega, acc = 0.4 * rng.normal(size=3), 0.8 * rng.normal(size=3)
+    bg_true, ba_true = 0.002 * rng.normal(size=3), 0.02 * rng.normal(size=3)
+    if start is not None:
+        Rwb1, p1, v1, bg_true, ba_true = (np.asarray(start[k], np.float64) for k in ("Rwb", "twb", "v", "bg", "ba"))
+        if "Rcb" in start:  # the same mounting along a chain
+            Rcb, tcb = _f32(start["Rcb"]), _f32(start["tcb"])
+            Rbc, tbc = Rcb.T.copy(), _f32(-Rcb.T @ tcb)
+    Rwb2 = Rwb1 @ _exp_so3(omega * dt)
+    v2, p2 = v1 + acc * dt, p1 + v1 * dt + 0.5 * acc * dt * dt
+    # the preintegration: the ideal deltas, noise, plausible bias Jacobians, the bias it was integrated with
+    sr, sv, sp = 1e-3 * np.sqrt(dt / 0.05), 4e-3 * np.sqrt(dt / 0.05), 1e-3 * np.sqrt(dt / 0.05)
+    nr, nv, npos = preint_noise * sr * rng.normal(size=3), preint_noise * sv * rng.normal(size=3), preint_noise * sp * rng.normal(size=3)
+    if inconsistent:
+        nr, nv = nr + np.deg2rad(4.0) * rng.choice([-1, 1], 3), nv + 0.3 * rng.choice([-1, 1], 3)
+    dR = Rwb1.T @ Rwb2 @ _exp_so3(nr)
+    dV = Rwb1.T @ (v2 - v1 - g * dt) + nv
+    dP = Rwb1.T @ (p2 - p1 - v1 * dt - 0.5 * g * dt * dt) + npos
+    JRg = -dt * (np.eye(3) + 0.05 * rng.normal(size=(3, 3)))
+    JVa = -dt * (np.eye(3) + 0.05 * rng.normal(size=(3, 3)))
+    JPa = -0.5 * dt * dt * (np.eye(3) + 0.05 * rng.normal(size=(3, 3)))
+    JVg, JPg = 0.3 * dt * dt * rng.normal(size=(3, 3)), 0.1 * dt ** 3 * rng.normal(size=(3, 3))
+    pre_bg, pre_ba = (bg_true + 1e-4 * rng.normal(size=3)).astype(np.float32), (ba_true + 1e-3 * rng.normal(size=3)).astype(np.float32)
+    info_inertial = _spd(rng, np.r_[np.full(3, sr ** -2), np.full(3, sv ** -2), np.full(3, sp ** -2)], 0.02)
+    info_gyro_rw = _spd(rng, np.full(3, 1.0 / (1e-4 ** 2 * dt)), 0.02)
+    info_acc_rw = _spd(rng, np.full(3, 1.0 / (1e-3 ** 2 * dt)), 0.02)
+
+    def state(Rwb, p, v, bg, ba):  # as ImuCamPose(Frame*) leaves it: floats widened, the camera pose from the float pose
+        Rwb, p = _f32(Rwb), _f32(p)
+        Rcw = _f32(Rcb @ Rwb.T)
+        tcw = _f32(Rcb @ (-Rwb.T @ p) + tcb)
+        return dict(Rwb=Rwb, twb=p, Rcw=Rcw, tcw=tcw, v=_f32(v), bg=_f32(bg), ba=_f32(ba))
+
+    e1 = 0.1 if frame else 0.0  # the previous frame's estimate is an optimised one; the key frame is fixed
+    other = state(Rwb1 @ _exp_so3(e1 * 0.002 * rng.normal(size=3)), p1 + e1 * 0.005 * rng.normal(size=3), v1 + e1 * 0.01 * rng.normal(size=3),
+                  bg_true + 1e-4 * rng.normal(size=3), ba_true + 1e-3 * rng.normal(size=3))
+    cur = state(Rwb2 @ _exp_so3(pose_error * 0.008 * rng.normal(size=3)), p2 + pose_error * 0.02 * rng.normal(size=3),
+                v2 + pose_error * 0.05 * rng.normal(size=3), other["bg"], other["ba"])
+    prior_H = _spd(rng, np.r_[np.full(3, 2e4), np.full(3, 1e4), np.full(3, 4e2), np.full(3, 1e6), np.full(3, 1e4)], 0.02)
+    # the map points, seen from the true current camera
+    Rcw_t, tcw_t = Rcb @ Rwb2.T, Rcb @ (-Rwb2.T @ p2) + tcb
+    sigma2 = np.float64(np.float32(1.2) ** (2 * np.arange(8)))
+    inv_sigma2 = (np.float32(1.0) / np.float32(1.2) ** (2 * np.arange(8))).astype(np.float32)
+    xw, obs, w = np.zeros((n_obs, 3)), np.zeros((n_obs, 3)), np.zeros(n_obs, np.float32)
+    st, close, is_out = np.zeros(n_obs, np.uint8), np.zeros(n_obs, np.uint8), np.zeros(n_obs, bool)
+    k = 0
+    while k < n_obs:
+        z = rng.uniform(*depth)
+        xc = np.array([rng.uniform(-0.5, 0.5) * z, rng.uniform(-0.38, 0.38) * z, z])
+        u, v = fx * xc[0] / xc[2] + cx, fy * xc[1] / xc[2] + cy
+        if not (0 <= u < 640 and 0 <= v < 480):
+            continue
+        octv = int(rng.choice(8, p=np.array([217, 181, 151, 126, 105, 87, 73, 60]) / 1000.0))
+        noise = rng.normal(0, np.sqrt(sigma2[octv]), 3)
+        is_out[k] = rng.random() < outlier_share
+        if is_out[k]:
+            noise[:2] += rng.choice([-1, 1], 2) * outlier_px
+        st[k] = rng.random() < stereo_share
+        xw[k] = _f32(Rcw_t.T @ (xc - tcw_t))
+        obs[k] = [np.float32(u + noise[0]), np.float32(v + noise[1]), np.float32(u - bf / z + noise[2]) if st[k] else -1.0]
+        w[k] = inv_sigma2[octv]
+        close[k] = np.float32(z) < np.float32(10.0)
+        k += 1
+    f32 = lambda a: np.ascontiguousarray(a, np.float32)
+    return dict(mode=int(mode), n_obs=int(n_obs), n_rounds=int(n_rounds), rec_init=int(bool(rec_init)), xw=xw, obs=obs, inv_sigma2=w, stereo=st,
+                close=close, fx=fx, fy=fy, cx=cx, cy=cy, bf=bf, Rcb=Rcb, tcb=tcb, Rbc=Rbc, tbc=tbc, cur=cur, other=other,
+                dR=f32(dR), dV=f32(dV), dP=f32(dP), JRg=f32(JRg), JVg=f32(JVg), JVa=f32(JVa), JPg=f32(JPg), JPa=f32(JPa), preint_bg=pre_bg,
+                preint_ba=pre_ba, dT=np.float32(dt), info_inertial=info_inertial, info_gyro_rw=info_gyro_rw, info_acc_rw=info_acc_rw,
+                prior_Rwb=other["Rwb"].copy(), prior_twb=other["twb"].copy(), prior_vwb=other["v"].copy(), prior_bg=other["bg"].copy(),
+                prior_ba=other["ba"].copy(), prior_H=prior_H, is_outlier=is_out,
+                truth=dict(Rwb=Rwb2, twb=p2, v=v2, bg=bg_true, ba=ba_true))

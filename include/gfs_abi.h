@@ -1387,6 +1387,71 @@ int  gfs_bow_db_query(gfs_bow_db* h, int n_words, const int32_t* word_id, const 
                       int32_t* n_common, int32_t* first_word, float* score);   /* each [max_entries] */
 
 /* ============================================================================================
+ * 19. PoseInertialOptimization — the IMU pose step that ends Tracking::TrackLocalMap once the IMU is initialised
+ *     (src/Tracking.cc:3763-3798): Optimizer::PoseInertialOptimizationLastKeyFrame (src/Optimizer.cc:5899-6283, mode
+ *     GFS_POSE_INERTIAL_LAST_KEYFRAME: the other end of the inertial edge is the last key frame, fixed, 15 unknowns) and
+ *     ...LastFrame (:6762-7171, mode GFS_POSE_INERTIAL_LAST_FRAME: the previous frame, free, 30 unknowns, with its prior).
+ *    One graph with two settings, one kernel: n_rounds <= 4 rounds of ten Gauss-Newton iterations over the dense 15 x 15 / 30 x 30
+ *    system, the re-classification of the visual edges after each, the recovery pass and the Hessian of the new prior, B problems
+ *    a call with the modes mixed freely, one workgroup a problem, no host round trip.  csrc/pose_inertial_rule.hpp and DESIGN.md
+ *    section 25 state the rule, the quirks kept and the written rules N / E / L / S; every output is the sequential restatement's
+ *    (tests/host/pose_inertial_restatement.cpp) byte for byte, alone or inside any batch.
+ *    A problem carries what the reference's constructors leave: no matrix inverse and no eigen-solver runs here.  Matrices are
+ *    row-major.  Only Nleft == -1 and the pinhole camera (uncertainty2 == 1).
+ *    Refused before anything is staged, the handle left usable, nothing truncated -- GFS_ERR_CAPACITY: B above max_batch, n_obs
+ *    above max_obs; GFS_ERR_INVALID_ARG: a NULL required array (xw, obs, inv_sigma2, stereo, close, outlier when n_obs > 0), n_obs < 0,
+ *    n_rounds outside 1..4, an unknown mode.
+ * ============================================================================================ */
+#define GFS_POSE_INERTIAL_LAST_KEYFRAME 0
+#define GFS_POSE_INERTIAL_LAST_FRAME 1
+typedef struct {  /* one end of the inertial edge as ImuCamPose(Frame*) / (KeyFrame*) and the Vertex* constructors leave it */
+  double Rwb[9], twb[3], Rcw[9], tcw[3];   /* src/G2oTypes.cc:28-119 */
+  double v[3], bg[3], ba[3];               /* VertexVelocity, VertexGyroBias, VertexAccBias */
+} gfs_imu_state;
+typedef struct {
+  int32_t mode;                    /* GFS_POSE_INERTIAL_LAST_KEYFRAME / _LAST_FRAME */
+  int32_t n_obs;                   /* visual edges, in the reference's index order (mono and stereo interleaved) */
+  int32_t n_rounds;                /* nIterations, 1..4 */
+  int32_t rec_init;                /* bRecInit */
+  const double* xw;                /* [n][3] pMP->GetWorldPos(), doubles from floats */
+  const double* obs;               /* [n][3] kpUn.pt.x, kpUn.pt.y, mvuRight (ignored for a mono edge), doubles from floats */
+  const float* inv_sigma2;         /* [n] mvInvLevelSigma2[octave] / uncertainty2 */
+  const uint8_t* stereo;           /* [n] 1: EdgeStereoOnlyPose, 0: EdgeMonoOnlyPose */
+  const uint8_t* close;            /* [n] bClose = mTrackDepth < 10.f (read for mono edges) */
+  double fx, fy, cx, cy, bf;       /* the pinhole's float parameters and mbf as doubles */
+  double Rcb[9], tcb[3], Rbc[9], tbc[3];
+  gfs_imu_state cur;               /* pFrame: vertices 0..3 */
+  gfs_imu_state other;             /* pFrame->mpLastKeyFrame (fixed) or pFrame->mpPrevFrame (free): vertices 4..7 */
+  /* the preintegration of the inertial edge: mpImuPreintegrated (key-frame mode) or mpImuPreintegratedFrame (frame mode) */
+  float dR[9], dV[3], dP[3], JRg[9], JVg[9], JVa[9], JPg[9], JPa[9];
+  float preint_bg[3], preint_ba[3];  /* its bias b: bwx bwy bwz, bax bay baz */
+  float dT;
+  double info_inertial[81];        /* EdgeInertial's information after the constructor's inverse and eigenvalue clamp (:485-492) */
+  double info_gyro_rw[9];          /* mpImuPreintegrated->C.block<3,3>(9,9).cast<double>().inverse(), in both modes (:6961) */
+  double info_acc_rw[9];           /* ... block<3,3>(12,12) ... (:6968) */
+  /* frame mode only: pFp->mpcpi */
+  double prior_Rwb[9], prior_twb[3], prior_vwb[3], prior_bg[3], prior_ba[3], prior_H[225];
+} gfs_pose_inertial_problem;
+typedef struct {  /* the estimates as doubles: the caller casts, as SetImuPoseVelocity and IMU::Bias do */
+  double Rwb[9], twb[3], v[3], bg[3], ba[3];
+} gfs_imu_estimate;
+typedef struct {
+  gfs_imu_estimate cur;            /* VP, VV, VG, VA */
+  gfs_imu_estimate other;          /* frame mode: the previous frame's (for tests); key-frame mode: the key frame's, unchanged */
+  uint8_t* outlier;                /* [n] mvbOutlier */
+  int32_t n_good;                  /* the return value: nInitialCorrespondences - nBad */
+  int32_t n_inliers;               /* nInliers of the last round */
+  int32_t rounds_run;
+  float avg_reproj;                /* avgReprojectionError of the last round */
+  double H[900];                   /* row-major 15 x 15 (key-frame mode: VP, VV, VG, VA) or 30 x 30 (frame mode: the previous
+                                      frame's 15, then the current frame's), BEFORE Optimizer::Marginalize and ConstraintPoseImu */
+} gfs_pose_inertial_solution;
+typedef struct gfs_pose_inertial gfs_pose_inertial;
+int gfs_pose_inertial_create(int device, int max_obs, int max_batch, gfs_pose_inertial** out);
+void gfs_pose_inertial_destroy(gfs_pose_inertial* h);
+int gfs_pose_inertial_optimize(gfs_pose_inertial* h, const gfs_pose_inertial_problem* problems, int B, gfs_pose_inertial_solution* solutions);
+
+/* ============================================================================================
  * Timing helper for the harness: HIP events on a given stream (bench.py measures the dominant kernel
  * with these rather than torch events, which only see torch's current stream).
  * ============================================================================================ */
