@@ -324,6 +324,82 @@ def pose_inertial_result(S, keep, n, mode):
                 rounds_run=int(S.rounds_run), avg_reproj=np.float32(S.avg_reproj), H=np.array(S.H[:D * D]).reshape(D, D))
 
 
+class LbaInertialEdge(C.Structure):
+    _fields_ = [("dR", C.c_float * 9), ("dV", C.c_float * 3), ("dP", C.c_float * 3), ("JRg", C.c_float * 9), ("JVg", C.c_float * 9),
+                ("JVa", C.c_float * 9), ("JPg", C.c_float * 9), ("JPa", C.c_float * 9), ("preint_bg", C.c_float * 3), ("preint_ba", C.c_float * 3),
+                ("dT", C.c_float), ("info_inertial", C.c_double * 81), ("info_gyro_rw", C.c_double * 9), ("info_acc_rw", C.c_double * 9)]
+
+
+class LbaInertialProblem(C.Structure):
+    _fields_ = [("n_opt", C.c_int32), ("n_fixed", C.c_int32), ("n_points", C.c_int32), ("n_edges", C.c_int32), ("iterations", C.c_int32),
+                ("n_cameras", C.c_int32), ("lambda_init", C.c_double), ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double),
+                ("cy", C.c_double), ("bf", C.c_double), ("Rcb", C.c_double * 9), ("tcb", C.c_double * 3), ("Rbc", C.c_double * 9),
+                ("tbc", C.c_double * 3), ("window", C.c_void_p), ("window_imu", C.c_void_p), ("prev", ImuState), ("fixed_Rcw", C.c_void_p),
+                ("fixed_tcw", C.c_void_p), ("inertial", C.c_void_p), ("points", C.c_void_p), ("point_edge_begin", C.c_void_p),
+                ("edge_kf", C.c_void_p), ("obs", C.c_void_p), ("inv_sigma2", C.c_void_p), ("stereo", C.c_void_p), ("close", C.c_void_p)]
+
+
+class LbaInertialSolution(C.Structure):
+    _fields_ = [("window", C.c_void_p), ("points", C.c_void_p), ("edge_chi2", C.c_void_p), ("edge_depth_positive", C.c_void_p),
+                ("edge_erase", C.c_void_p), ("err", C.c_float), ("err_end", C.c_float), ("iterations_run", C.c_int32),
+                ("trials_run", C.c_int32), ("final_lambda", C.c_double)]
+
+
+_IMU_STATE_KEYS = ("Rwb", "twb", "Rcw", "tcw", "v", "bg", "ba")
+
+
+def lba_inertial_structs(prob):
+    """ctypes views of one window dict (synth.lba_inertial_window; shared with the CPU restatement's tests): keys as the fields of
+    gfs_lba_inertial_problem, `window` a list of state dicts (Rwb, twb, Rcw, tcw, v, bg, ba), `prev` one, `inertial` a list of dicts
+    with the fields of gfs_lba_inertial_edge.  A key whose value is None becomes a NULL pointer."""
+    P, S = LbaInertialProblem(), LbaInertialSolution()
+    N, F, n_pts, n_e = (int(prob[k]) for k in ("n_opt", "n_fixed", "n_points", "n_edges"))
+    keep = dict(window=(ImuState * max(len(prob["window"]), 1))(), inertial=(LbaInertialEdge * max(len(prob["inertial"]), 1))(),
+                out_window=(ImuState * max(N, 1))(), out_points=np.zeros((max(n_pts, 1), 3)), edge_chi2=np.zeros(max(n_e, 1)),
+                edge_depth_positive=np.zeros(max(n_e, 1), np.uint8), edge_erase=np.zeros(max(n_e, 1), np.uint8))
+    for i, st in enumerate(prob["window"]):
+        for name in _IMU_STATE_KEYS:
+            _fill(getattr(keep["window"][i], name), st[name])
+    for i, ed in enumerate(prob["inertial"]):
+        for name, _ in LbaInertialEdge._fields_:
+            if name == "dT":
+                keep["inertial"][i].dT = float(ed["dT"])
+            else:
+                _fill(getattr(keep["inertial"][i], name), ed[name])
+    for name in _IMU_STATE_KEYS:
+        _fill(getattr(P.prev, name), prob["prev"][name])
+    for name, dt in (("window_imu", np.uint8), ("fixed_Rcw", np.float64), ("fixed_tcw", np.float64), ("points", np.float64),
+                     ("point_edge_begin", np.int32), ("edge_kf", np.int32), ("obs", np.float64), ("inv_sigma2", np.float32), ("stereo", np.uint8),
+                     ("close", np.uint8)):
+        if prob.get(name) is None:
+            setattr(P, name, None)
+            continue
+        a = np.ascontiguousarray(prob[name], dt)
+        keep[name] = a if a.size else np.zeros(1, dt)
+        setattr(P, name, keep[name].ctypes.data)
+    P.window = C.addressof(keep["window"]) if prob.get("window_null") is None else None
+    P.inertial = C.addressof(keep["inertial"]) if prob.get("inertial_null") is None else None
+    P.n_opt, P.n_fixed, P.n_points, P.n_edges = N, F, n_pts, n_e
+    P.iterations, P.n_cameras, P.lambda_init = int(prob["iterations"]), int(prob.get("n_cameras", 1)), float(prob["lambda_init"])
+    for name in ("fx", "fy", "cx", "cy", "bf"):
+        setattr(P, name, float(prob[name]))
+    for name in ("Rcb", "tcb", "Rbc", "tbc"):
+        _fill(getattr(P, name), prob[name])
+    S.window, S.points = C.addressof(keep["out_window"]), keep["out_points"].ctypes.data
+    S.edge_chi2, S.edge_depth_positive, S.edge_erase = (keep[k].ctypes.data for k in ("edge_chi2", "edge_depth_positive", "edge_erase"))
+    return P, S, keep
+
+
+def lba_inertial_result(S, keep, prob):
+    N, n_pts, n_e = max(int(prob["n_opt"]), 0), max(int(prob["n_points"]), 0), max(int(prob["n_edges"]), 0)
+    win = [{name: np.array(getattr(keep["out_window"][i], name)[:]).reshape((3, 3) if name[0] == "R" else (3,)) for name in _IMU_STATE_KEYS}
+           for i in range(N)]
+    return dict(window=win, points=keep["out_points"][:n_pts].copy(), edge_chi2=keep["edge_chi2"][:n_e].copy(),
+                edge_depth_positive=keep["edge_depth_positive"][:n_e].copy(), edge_erase=keep["edge_erase"][:n_e].copy(), err=np.float32(S.err),
+                err_end=np.float32(S.err_end), iterations_run=int(S.iterations_run), trials_run=int(S.trials_run),
+                final_lambda=float(S.final_lambda))
+
+
 class ClaheConfig(C.Structure):
     _fields_ = [("clip_limit", C.c_double), ("tiles_x", C.c_int32), ("tiles_y", C.c_int32), ("residual_variant", C.c_int32)]
 
@@ -965,6 +1041,7 @@ ABI_SYMBOLS = [
     "gfs_sim3_opt_create", "gfs_sim3_opt_destroy", "gfs_sim3_optimize", "gfs_test_glibc_exp",
     "gfs_sim3_ransac_iterations", "gfs_sim3_ransac_create", "gfs_sim3_ransac_solve", "gfs_sim3_ransac_destroy",
     "gfs_pose_inertial_create", "gfs_pose_inertial_optimize", "gfs_pose_inertial_destroy",
+    "gfs_lba_inertial_create", "gfs_lba_inertial_solve", "gfs_lba_inertial_destroy",
     "gfs_frame_create", "gfs_frame_destroy", "gfs_depth_to_cloud", "gfs_depth_to_cloud_batch_device", "gfs_depth_convert_u16_batch_device", "gfs_stereo_from_rgbd",
     "gfs_stereo_from_rgbd_batch_device",
     "gfs_pose_create", "gfs_pose_destroy", "gfs_pose_optimize", "gfs_pose_set_sum_order",
@@ -1100,6 +1177,10 @@ def lib():
             L.gfs_pose_inertial_create.argtypes = [i, i, i, C.POINTER(vp)]
             L.gfs_pose_inertial_destroy.argtypes = [vp]
             L.gfs_pose_inertial_optimize.argtypes = [vp, vp, i, vp]
+        if hasattr(L, "gfs_lba_inertial_create"):
+            L.gfs_lba_inertial_create.argtypes = [i, i, i, i, i, C.POINTER(vp)]
+            L.gfs_lba_inertial_destroy.argtypes = [vp]
+            L.gfs_lba_inertial_solve.argtypes = [vp, C.POINTER(LbaInertialProblem), C.POINTER(LbaInertialSolution)]
         if hasattr(L, "gfs_sim3_ransac_create"):
             L.gfs_sim3_ransac_iterations.argtypes = [i, C.c_double, i, i]
             L.gfs_sim3_ransac_create.argtypes = [i, i, i, i, C.POINTER(vp)]
@@ -2572,6 +2653,33 @@ class PoseInertialOptimizer:
         _check(lib().gfs_pose_inertial_optimize(self.h, PP, B, SS), "gfs_pose_inertial_optimize")
         res = [pose_inertial_result(SS[f], *keeps[f]) for f in range(B)]
         return res[0] if single else res
+
+
+class LocalInertialBA:
+    """Optimizer::LocalInertialBA's numeric core (reference src/Optimizer.cc:3589-3626) on one flattened window
+    (gfs_lba_inertial_problem in include/gfs_abi.h): one Levenberg optimize() over the window's key frames
+    (15 unknowns each), the marginalised map points and the inertial edges, queued at once with the trial decisions on the device;
+    every output is the sequential restatement's byte for byte."""
+
+    def __init__(self, max_opt=20, max_fixed=200, max_points=4096, max_edges=65536, device=0):
+        self.h = C.c_void_p()
+        _check(lib().gfs_lba_inertial_create(device, int(max_opt), int(max_fixed), int(max_points), int(max_edges), C.byref(self.h)),
+               "gfs_lba_inertial_create")
+
+    def close(self):
+        if getattr(self, "h", None) and _lib is not None:
+            _lib.gfs_lba_inertial_destroy(self.h)
+        self.h = None
+
+    __del__ = close
+
+    def solve(self, problem):
+        """problem: a window dict (lba_inertial_structs) -> dict(window: list of state dicts as doubles, points [P, 3], edge_chi2 [E],
+        edge_depth_positive, edge_erase [E] uint8, err, err_end (float32), iterations_run, trials_run, final_lambda).  Raises GfsError
+        (GFS_ERR_CAPACITY / GFS_ERR_INVALID_ARG / GFS_ERR_UNSUPPORTED) on a refusal; the handle stays usable."""
+        P, S, keep = lba_inertial_structs(problem)
+        _check(lib().gfs_lba_inertial_solve(self.h, C.byref(P), C.byref(S)), "gfs_lba_inertial_solve")
+        return lba_inertial_result(S, keep, problem)
 
 
 class BowVocabulary:

@@ -20,6 +20,7 @@
 #include <cstdint>
 #include <cstring>
 #include <fstream>
+#include <functional>
 #include <list>
 #include <map>
 #include <memory>
@@ -36,6 +37,7 @@
 #include "../../include/gfs_abi.h"
 #include "../csrc/bow_vocab_rule.hpp"
 #include "../csrc/fuse_rule.hpp"
+#include "../csrc/lba_inertial_rule.hpp"
 #include "../csrc/sim3_search_rule.hpp"
 #include "../csrc/map_point_rule.hpp"
 #include "../csrc/sim3_dev.hpp"
@@ -3764,6 +3766,211 @@ class PoseInertialDevice {
 
  private:
   gfs_pose_inertial* h_ = nullptr;
+};
+
+// ------------------------------------------------------------------------------------------------------------------------
+// void Optimizer::LocalInertialBA(KeyFrame* pKF, bool* pbStopFlag, bool pbICPFlag, Map* pMap, int& num_fixedKF, int& num_OptKF,
+//                                 int& num_MPs, int& num_edges, bool bLarge, bool bRecInit)                  src/Optimizer.cc:3056-3702
+// the local BA LocalMapping::Run calls for every new key frame once the IMU is initialised (src/LocalMapping.cc:186-228), around one
+// flat solve (include/gfs_abi.h section 20).
+//   gather:     exactly :3060-3166 -- the window along the mPrevKF chain (at most 10, or 20 with bLarge; Nd from KeyFramesInMap() - 2),
+//               its map points in match order, the fixed predecessor or, without one, the oldest key frame popped and fixed, no
+//               "optimisable visual" key frames (maxCovKF is 0), the other fixed key frames from the observations until the list holds
+//               gfs_li::kMaxFixKF, with the mnBALocalForKF / mnBAFixedForKF marks; SetNewBias on every preintegration (:3336); the
+//               visual edges point by point in the order of GetObservations() (:3446-3578).  The reference's constructors run on the
+//               reference's own types inside `Access`.
+//   solve:      `solve(problem, solution)`: LocalInertialBADevice::solve below (gfs_lba_inertial_solve on the GPU).
+//   write back: the fail gate (:3632; the marks are left as they are there, as the reference leaves them), EraseMapPointMatch /
+//               EraseObservation of the flagged observations whose point is not bad, the marks' reset, SetPose / SetVelocity /
+//               SetNewBias (the casts are Access's), SetWorldPos + UpdateNormalAndDepth, IncreaseChangeIndex, under mMutexMapUpdate.
+// pbICPFlag == true goes to `reference(...)`, the reference's own function: the EdgeICP block registers a GICP per key frame, and no
+// shipped configuration enables it.  pbStopFlag is never polled by the reference (:3594) and is not read; num_* are never written by
+// it; bRecInit is unused by it.
+// Refused (std::runtime_error, every mark put back, nothing else touched): a window key frame or the predecessor without IMU or without
+// a preintegration, a key frame with a second camera, a camera that is not the pinhole.  Returns false when the fail gate fired.
+// Of `Access`:
+//     static bool is_pinhole(const KeyFrame*);
+//     static void calibration(const KeyFrame*, gfs_lba_inertial_problem&);          // fx fy cx cy bf Rcb tcb Rbc tbc
+//     static void state(const KeyFrame*, gfs_imu_state&);                            // ImuCamPose(KeyFrame*) + the Vertex* constructors
+//     static void preintegration(const Preintegrated*, gfs_lba_inertial_edge&);      // dR .. dT, info_inertial, info_gyro_rw, info_acc_rw
+//     static void world_pos(const MapPoint*, float X[3]); static void set_world_pos(MapPoint*, const double X[3]);
+//     static void set_pose_velocity_bias(KeyFrame*, const gfs_imu_state&);           // SetPose(Tcw), SetVelocity, SetNewBias(IMU::Bias)
+// ------------------------------------------------------------------------------------------------------------------------
+template <class Access, class KeyFrame, class Map, class Solve, class Reference>
+bool LocalInertialBA(Solve&& solve, Reference&& reference, KeyFrame* pKF, bool* pbStopFlag, bool pbICPFlag, Map* pMap, int& num_fixedKF,
+                     int& num_OptKF, int& num_MPs, int& num_edges, bool bLarge = false, bool bRecInit = false) {
+  if (pbICPFlag) {
+    reference(pKF, pbStopFlag, pbICPFlag, pMap, num_fixedKF, num_OptKF, num_MPs, num_edges, bLarge, bRecInit);
+    return true;
+  }
+  using MapPoint = std::remove_pointer_t<std::decay_t<decltype(pKF->GetMapPointMatches()[0])>>;
+  auto* pCurrentMap = pKF->GetMap();
+  const int maxOpt = bLarge ? gfs_li::kMaxWindowLarge : gfs_li::kMaxWindow;
+  const int Nd = std::min((int)pCurrentMap->KeyFramesInMap() - 2, maxOpt);
+  std::vector<std::function<void()>> undo;  // every mark the gather sets, for a refusal
+  auto mark = [&](auto& field, auto value) {
+    const auto old = field;
+    undo.push_back([&field, old] { field = old; });
+    field = value;
+  };
+  auto refuse = [&](const char* what) {
+    for (auto it = undo.rbegin(); it != undo.rend(); ++it) (*it)();
+    throw std::runtime_error(what);
+  };
+  std::vector<KeyFrame*> vpOptimizableKFs;
+  vpOptimizableKFs.push_back(pKF);
+  mark(pKF->mnBALocalForKF, pKF->mnId);
+  for (int i = 1; i < Nd; i++) {
+    if (!vpOptimizableKFs.back()->mPrevKF) break;
+    vpOptimizableKFs.push_back(vpOptimizableKFs.back()->mPrevKF);
+    mark(vpOptimizableKFs.back()->mnBALocalForKF, pKF->mnId);
+  }
+  int N = (int)vpOptimizableKFs.size();
+  std::list<MapPoint*> lLocalMapPoints;
+  for (int i = 0; i < N; i++)
+    for (MapPoint* pMP : vpOptimizableKFs[i]->GetMapPointMatches())
+      if (pMP && !pMP->isBad() && pMP->mnBALocalForKF != pKF->mnId) {
+        lLocalMapPoints.push_back(pMP);
+        mark(pMP->mnBALocalForKF, pKF->mnId);
+      }
+  std::list<KeyFrame*> lFixedKeyFrames;
+  if (vpOptimizableKFs.back()->mPrevKF) {
+    lFixedKeyFrames.push_back(vpOptimizableKFs.back()->mPrevKF);
+    mark(vpOptimizableKFs.back()->mPrevKF->mnBAFixedForKF, pKF->mnId);
+  } else {
+    mark(vpOptimizableKFs.back()->mnBALocalForKF, decltype(pKF->mnId)(0));
+    mark(vpOptimizableKFs.back()->mnBAFixedForKF, pKF->mnId);
+    lFixedKeyFrames.push_back(vpOptimizableKFs.back());
+    vpOptimizableKFs.pop_back();
+  }
+  N = (int)vpOptimizableKFs.size();
+  for (MapPoint* pMP : lLocalMapPoints) {
+    const auto observations = pMP->GetObservations();
+    for (const auto& ob : observations) {
+      KeyFrame* pKFi = ob.first;
+      if (pKFi->mnBALocalForKF != pKF->mnId && pKFi->mnBAFixedForKF != pKF->mnId) {
+        mark(pKFi->mnBAFixedForKF, pKF->mnId);
+        if (!pKFi->isBad()) {
+          lFixedKeyFrames.push_back(pKFi);
+          break;
+        }
+      }
+    }
+    if ((int)lFixedKeyFrames.size() >= gfs_li::kMaxFixKF) break;
+  }
+  if (N < 1) refuse("LocalInertialBA: no optimisable key frame");
+  // key-frame indices: the window, the predecessor, the other fixed ones in list order
+  std::map<KeyFrame*, int> index;
+  for (int i = 0; i < N; i++) index[vpOptimizableKFs[i]] = i;
+  KeyFrame* prev = lFixedKeyFrames.front();
+  if (vpOptimizableKFs.back()->mPrevKF != prev) refuse("LocalInertialBA: the window has no fixed predecessor");
+  std::vector<KeyFrame*> fixed(std::next(lFixedKeyFrames.begin()), lFixedKeyFrames.end());
+  index[prev] = N;
+  for (size_t k = 0; k < fixed.size(); k++) index[fixed[k]] = N + 1 + (int)k;
+  for (const auto& kv : index) {
+    if (kv.first->mpCamera2) refuse("LocalInertialBA: key frames with a second camera are not supported");
+    if (!Access::is_pinhole(kv.first)) refuse("LocalInertialBA: only the pinhole camera is supported");
+  }
+  if (!prev->bImu) refuse("LocalInertialBA: the key frame in front of the window has no IMU");
+  for (int i = 0; i < N; i++)
+    if (!vpOptimizableKFs[i]->bImu || !vpOptimizableKFs[i]->mpImuPreintegrated) refuse("LocalInertialBA: a window key frame has no IMU preintegration");
+  gfs_lba_inertial_problem P{};
+  P.n_opt = N, P.n_fixed = (int)fixed.size(), P.n_cameras = 1;
+  P.iterations = bLarge ? gfs_li::kOptItLarge : gfs_li::kOptIt;
+  P.lambda_init = bLarge ? gfs_li::kLambdaInitLarge : gfs_li::kLambdaInit;
+  Access::calibration(pKF, P);
+  std::vector<gfs_imu_state> window((size_t)N), window_out((size_t)N);
+  std::vector<uint8_t> window_imu((size_t)N, 1);
+  std::vector<gfs_lba_inertial_edge> inertial((size_t)N);
+  for (int i = 0; i < N; i++) {
+    KeyFrame* pKFi = vpOptimizableKFs[i];
+    Access::state(pKFi, window[(size_t)i]);
+    pKFi->mpImuPreintegrated->SetNewBias(pKFi->mPrevKF->GetImuBias());
+    Access::preintegration(pKFi->mpImuPreintegrated, inertial[(size_t)i]);
+  }
+  Access::state(prev, P.prev);
+  std::vector<double> fixed_Rcw(9 * fixed.size() + 1), fixed_tcw(3 * fixed.size() + 1);
+  for (size_t k = 0; k < fixed.size(); k++) {
+    gfs_imu_state s{};
+    Access::state(fixed[k], s);
+    memcpy(&fixed_Rcw[9 * k], s.Rcw, sizeof(s.Rcw)), memcpy(&fixed_tcw[3 * k], s.tcw, sizeof(s.tcw));
+  }
+  std::vector<double> points, obs;
+  std::vector<int32_t> begin{0}, edge_kf;
+  std::vector<float> w;
+  std::vector<uint8_t> stereo, close;
+  std::vector<std::pair<KeyFrame*, MapPoint*>> edge_of;
+  std::vector<MapPoint*> vpPoints(lLocalMapPoints.begin(), lLocalMapPoints.end());
+  for (MapPoint* pMP : vpPoints) {
+    float X[3];
+    Access::world_pos(pMP, X);
+    for (int k = 0; k < 3; k++) points.push_back((double)X[k]);
+    const auto observations = pMP->GetObservations();
+    for (const auto& ob : observations) {
+      KeyFrame* pKFi = ob.first;
+      if (pKFi->mnBALocalForKF != pKF->mnId && pKFi->mnBAFixedForKF != pKF->mnId) continue;
+      if (pKFi->isBad() || pKFi->GetMap() != pCurrentMap) continue;
+      const int leftIndex = std::get<0>(ob.second);
+      if (leftIndex == -1) continue;
+      const auto it = index.find(pKFi);
+      if (it == index.end()) continue;  // marked fixed but bad when it was met (:3157-3161): it has no vertex, g2o drops the edge
+      const auto& kpUn = pKFi->mvKeysUn[(size_t)leftIndex];
+      const float ur = pKFi->mvuRight[(size_t)leftIndex];
+      obs.push_back((double)kpUn.pt.x), obs.push_back((double)kpUn.pt.y), obs.push_back((double)ur);
+      w.push_back(pKFi->mvInvLevelSigma2[(size_t)kpUn.octave]);  // / uncertainty2 == 1 for the pinhole
+      stereo.push_back(ur < 0 ? 0 : 1);
+      close.push_back(pMP->mTrackDepth < gfs_li::kTrackDepthClose ? 1 : 0);
+      edge_kf.push_back(it->second);
+      edge_of.emplace_back(pKFi, pMP);
+    }
+    begin.push_back((int32_t)edge_kf.size());
+  }
+  const size_t n_e = edge_kf.size(), n_p = vpPoints.size();
+  P.n_points = (int)n_p, P.n_edges = (int)n_e;
+  P.window = window.data(), P.window_imu = window_imu.data(), P.inertial = inertial.data();
+  P.fixed_Rcw = fixed_Rcw.data(), P.fixed_tcw = fixed_tcw.data(), P.points = points.data(), P.point_edge_begin = begin.data();
+  P.edge_kf = edge_kf.data(), P.obs = obs.data(), P.inv_sigma2 = w.data(), P.stereo = stereo.data(), P.close = close.data();
+  std::vector<double> points_out(3 * n_p + 1), chi2(n_e + 1);
+  std::vector<uint8_t> depth_positive(n_e + 1), erase(n_e + 1);
+  gfs_lba_inertial_solution S{};
+  S.window = window_out.data(), S.points = points_out.data(), S.edge_chi2 = chi2.data(), S.edge_depth_positive = depth_positive.data();
+  S.edge_erase = erase.data();
+  solve(P, S);
+  std::unique_lock<std::mutex> lock(pMap->mMutexMapUpdate);
+  const float err = S.err, err_end = S.err_end;
+  if (((float)gfs_li::kFailGateFactor * err < err_end || std::isnan(err) || std::isnan(err_end)) && !bLarge) return false;
+  for (size_t e = 0; e < n_e; e++)
+    if (erase[e] && !edge_of[e].second->isBad()) {
+      edge_of[e].first->EraseMapPointMatch(edge_of[e].second);
+      edge_of[e].second->EraseObservation(edge_of[e].first);
+    }
+  for (KeyFrame* pKFi : lFixedKeyFrames) pKFi->mnBAFixedForKF = 0;
+  for (int i = 0; i < N; i++) {
+    Access::set_pose_velocity_bias(vpOptimizableKFs[i], window_out[(size_t)i]);
+    vpOptimizableKFs[i]->mnBALocalForKF = 0;
+  }
+  for (size_t l = 0; l < n_p; l++) {
+    Access::set_world_pos(vpPoints[l], &points_out[3 * l]);
+    vpPoints[l]->UpdateNormalAndDepth();
+  }
+  pMap->IncreaseChangeIndex();
+  return true;
+}
+
+// numeric core: one window on the device
+class LocalInertialBADevice {
+ public:
+  explicit LocalInertialBADevice(int max_points = 8192, int max_edges = 131072, int max_opt = gfs_li::kMaxWindowLarge,
+                                 int max_fixed = gfs_li::kMaxFixKF, int device = 0) {
+    check(gfs_lba_inertial_create(device, max_opt, max_fixed, max_points, max_edges, &h_), "gfs_lba_inertial_create");
+  }
+  ~LocalInertialBADevice() { gfs_lba_inertial_destroy(h_); }
+  LocalInertialBADevice(const LocalInertialBADevice&) = delete;
+  LocalInertialBADevice& operator=(const LocalInertialBADevice&) = delete;
+  void solve(const gfs_lba_inertial_problem& p, gfs_lba_inertial_solution& s) { check(gfs_lba_inertial_solve(h_, &p, &s), "gfs_lba_inertial_solve"); }
+
+ private:
+  gfs_lba_inertial* h_ = nullptr;
 };
 
 }  // namespace gfs_host

@@ -1617,3 +1617,147 @@ def pose_inertial_problem(seed, mode, n_obs=300, outlier_share=0.15, stereo_shar
                 prior_Rwb=other["Rwb"].copy(), prior_twb=other["twb"].copy(), prior_vwb=other["v"].copy(), prior_bg=other["bg"].copy(),
                 prior_ba=other["ba"].copy(), prior_H=prior_H, is_outlier=is_out,
                 truth=dict(Rwb=Rwb2, twb=p2, v=v2, bg=bg_true, ba=ba_true))
+
+
+def lba_inertial_window(seed, n_opt=10, n_fixed=5, n_points=300, stereo_share=0.85, outlier_share=0.05, large=False, inconsistent=(),
+                        single_mono_points=0, fixed_heavy_points=0, pose_error=1.0, point_error=1.0, obs_per_point=(3, 7), outlier_px=25.0,
+                        dt=0.4, preint_noise=1.0, noise_scale=1.0, iterations=None, lambda_init=None):
+    """Synthetic Optimizer::LocalInertialBA window (include/gfs_abi.h section 20): a body on a smooth trajectory (angular rate and
+    acceleration drift slowly from one key-frame interval to the next) sampled every `dt` seconds; key frame 0 is the newest, key frame
+    n_opt - 1 the oldest of the window, `prev` the fixed one in front of it, and `n_fixed` further fixed key frames stand near the
+    start of the trajectory.  Each interval's preintegration is made from the true motion as pose_inertial_problem makes it, with
+    noise `preint_noise` times its covariance; `inconsistent`: the edge sets whose preintegration is off by several degrees and
+    decimetres a second.  `n_points` map points in front of the window, each observed from `obs_per_point` key frames in a random
+    order (at least one of them in the window), `stereo_share` of the observations with depth, pixel noise by octave times
+    `noise_scale`,
+    `outlier_share` gross outliers.  Knobs for the degenerate cases: `single_mono_points` further points with ONE mono observation,
+    `fixed_heavy_points` further points seen from one window key frame and otherwise only from fixed ones.  The window's estimates start
+    `pose_error` times a motion-model error from the truth, the points `point_error` times 2 cm.  `large`: the bLarge settings
+    (4 iterations, lambda 1e-2).  Returns the fields of gfs_lba_inertial_problem plus the truth and is_outlier per edge."""
+    rng = np.random.default_rng(seed)
+    N, F = int(n_opt), int(n_fixed)
+    dt = float(np.float32(dt))
+    g = np.array([0.0, 0.0, -float(np.float32(9.81))])
+    fx = fy = np.float64(np.float32(607.0))
+    cx, cy = np.float64(np.float32(319.5)), np.float64(np.float32(239.5))
+    bf = np.float64(np.float32(0.0745 * 607.0))
+    Rcb = _f32(np.array([[0.0, -1, 0], [0, 0, -1], [1, 0, 0]]) @ _rot(*(0.02 * rng.normal(size=3))))
+    tcb = _f32(0.05 * rng.normal(size=3))
+    Rbc, tbc = Rcb.T.copy(), _f32(-Rcb.T @ tcb)
+    # the true trajectory at times 0 (prev) .. N (key frame 0)
+    R = [_rot(0.05 * rng.normal(), 0.05 * rng.normal(), rng.uniform(-np.pi, np.pi))]
+    p, v = [rng.uniform(-2, 2, 3)], [np.array([0.5, 0.1, 0.02]) * rng.normal(size=3)]
+    omega, acc = 0.06 * rng.normal(size=3), 0.4 * rng.normal(size=3)  # slow turns: the window's key frames share their view
+    bg_true, ba_true = 0.002 * rng.normal(size=3), 0.02 * rng.normal(size=3)
+    steps = []
+    for k in range(N):
+        omega, acc = omega + 0.015 * rng.normal(size=3), acc + 0.08 * rng.normal(size=3)
+        steps.append((omega.copy(), acc.copy()))
+        R.append(R[k] @ _exp_so3(omega * dt))
+        v.append(v[k] + acc * dt)
+        p.append(p[k] + v[k] * dt + 0.5 * acc * dt * dt)
+
+    def state(Rwb, pp, vv, bg, ba):
+        Rwb, pp = _f32(Rwb), _f32(pp)
+        return dict(Rwb=Rwb, twb=pp, Rcw=_f32(Rcb @ Rwb.T), tcw=_f32(Rcb @ (-Rwb.T @ pp) + tcb), v=_f32(vv), bg=_f32(bg), ba=_f32(ba))
+
+    f32 = lambda a: np.ascontiguousarray(a, np.float32)
+    sr, sv, sp = 1e-3 * np.sqrt(dt / 0.05), 4e-3 * np.sqrt(dt / 0.05), 1e-3 * np.sqrt(dt / 0.05)
+    inertial = [None] * N
+    for k in range(N):  # the interval from time k to k + 1 is edge set N - 1 - k
+        i = N - 1 - k
+        nr, nv, npos = preint_noise * sr * rng.normal(size=3), preint_noise * sv * rng.normal(size=3), preint_noise * sp * rng.normal(size=3)
+        if i in tuple(inconsistent):
+            nr, nv = nr + np.deg2rad(4.0) * rng.choice([-1, 1], 3), nv + 0.3 * rng.choice([-1, 1], 3)
+        JRg = -dt * (np.eye(3) + 0.05 * rng.normal(size=(3, 3)))
+        JVa = -dt * (np.eye(3) + 0.05 * rng.normal(size=(3, 3)))
+        JPa = -0.5 * dt * dt * (np.eye(3) + 0.05 * rng.normal(size=(3, 3)))
+        JVg, JPg = 0.3 * dt * dt * rng.normal(size=(3, 3)), 0.1 * dt ** 3 * rng.normal(size=(3, 3))
+        inertial[i] = dict(dR=f32(R[k].T @ R[k + 1] @ _exp_so3(nr)), dV=f32(R[k].T @ (v[k + 1] - v[k] - g * dt) + nv),
+                           dP=f32(R[k].T @ (p[k + 1] - p[k] - v[k] * dt - 0.5 * g * dt * dt) + npos), JRg=f32(JRg), JVg=f32(JVg), JVa=f32(JVa),
+                           JPg=f32(JPg), JPa=f32(JPa), preint_bg=(bg_true + 1e-4 * rng.normal(size=3)).astype(np.float32),
+                           preint_ba=(ba_true + 1e-3 * rng.normal(size=3)).astype(np.float32), dT=np.float32(dt),
+                           info_inertial=_spd(rng, np.r_[np.full(3, sr ** -2), np.full(3, sv ** -2), np.full(3, sp ** -2)], 0.02),
+                           info_gyro_rw=_spd(rng, np.full(3, 1.0 / (1e-4 ** 2 * dt)), 0.02),
+                           info_acc_rw=_spd(rng, np.full(3, 1.0 / (1e-3 ** 2 * dt)), 0.02))
+    prev = state(R[0], p[0], v[0], bg_true + 1e-4 * rng.normal(size=3), ba_true + 1e-3 * rng.normal(size=3))
+    truth, window = [], []
+    for i in range(N):
+        k = N - i
+        truth.append(dict(Rwb=R[k], twb=p[k], v=v[k], bg=bg_true, ba=ba_true))
+        window.append(state(R[k] @ _exp_so3(pose_error * 0.008 * rng.normal(size=3)), p[k] + pose_error * 0.02 * rng.normal(size=3),
+                            v[k] + pose_error * 0.05 * rng.normal(size=3), prev["bg"] + 1e-5 * rng.normal(size=3),
+                            prev["ba"] + 1e-4 * rng.normal(size=3)))
+    # the other fixed key frames: earlier poses beside the start of the trajectory, looking the same way
+    fixed_R, fixed_p = [], []
+    for k in range(F):
+        fixed_R.append(R[0] @ _exp_so3(0.05 * rng.normal(size=3)))
+        fixed_p.append(p[0] + 0.3 * rng.normal(size=3))
+    cams = []  # true camera poses by key-frame index: the window, prev, the fixed ones
+    for i in range(N):
+        cams.append((Rcb @ R[N - i].T, Rcb @ (-R[N - i].T @ p[N - i]) + tcb))
+    cams.append((prev["Rcw"], prev["tcw"]))
+    fixed_Rcw, fixed_tcw = np.zeros((F, 3, 3)), np.zeros((F, 3))
+    for k in range(F):
+        Rwb, pp = _f32(fixed_R[k]), _f32(fixed_p[k])
+        fixed_Rcw[k], fixed_tcw[k] = _f32(Rcb @ Rwb.T), _f32(Rcb @ (-Rwb.T @ pp) + tcb)
+        cams.append((fixed_Rcw[k], fixed_tcw[k]))
+    K = N + 1 + F
+    sigma2 = np.float64(np.float32(1.2) ** (2 * np.arange(8)))
+    inv_sigma2 = (np.float32(1.0) / np.float32(1.2) ** (2 * np.arange(8))).astype(np.float32)
+    pts_true, pts, begin = [], [], [0]
+    edge_kf, obs, w, st, close, is_out = [], [], [], [], [], []
+
+    def observe(xw_true, kf, mono, outlier_ok=True):
+        Rcw, tcw = cams[kf]
+        xc = Rcw @ xw_true + tcw
+        if xc[2] < 0.5:
+            return False
+        u, vv = fx * xc[0] / xc[2] + cx, fy * xc[1] / xc[2] + cy
+        if not (0 <= u < 640 and 0 <= vv < 480):
+            return False
+        octv = int(rng.choice(8, p=np.array([217, 181, 151, 126, 105, 87, 73, 60]) / 1000.0))
+        noise = noise_scale * rng.normal(0, np.sqrt(sigma2[octv]), 3)
+        out = outlier_ok and rng.random() < outlier_share
+        if out:
+            noise[:2] += rng.choice([-1, 1], 2) * outlier_px
+        stereo = (not mono) and rng.random() < stereo_share
+        edge_kf.append(kf), w.append(inv_sigma2[octv]), st.append(stereo), is_out.append(out)
+        obs.append([np.float32(u + noise[0]), np.float32(vv + noise[1]), np.float32(u - bf / xc[2] + noise[2]) if stereo else -1.0])
+        return True
+
+    kinds = ["normal"] * int(n_points) + ["single_mono"] * int(single_mono_points) + ["fixed_heavy"] * int(fixed_heavy_points)
+    for kind in kinds:
+        while True:
+            home = int(rng.integers(0, N))
+            z = rng.uniform(1.5, 14.0)
+            xc = np.array([rng.uniform(-0.4, 0.4) * z, rng.uniform(-0.3, 0.3) * z, z])
+            xw_true = _f32(cams[home][0].T @ (xc - cams[home][1]))
+            n0 = len(edge_kf)
+            if kind == "single_mono":
+                order = [home]
+            elif kind == "fixed_heavy":
+                order = [home] + [N + int(k) for k in rng.permutation(F + 1)[:max(1, min(F + 1, 4))]]
+                order = [order[k] for k in rng.permutation(len(order))]
+            else:
+                others = [k for k in rng.permutation(K) if k != home][:int(rng.integers(obs_per_point[0], obs_per_point[1] + 1)) - 1]
+                order = [home] + [int(k) for k in others]
+                order = [order[k] for k in rng.permutation(len(order))]
+            for kf in order:
+                observe(xw_true, kf, kind == "single_mono", kind == "normal")
+            if home in edge_kf[n0:]:
+                break
+            del edge_kf[n0:], obs[n0:], w[n0:], st[n0:], is_out[n0:]
+        zc = (cams[0][0] @ xw_true + cams[0][1])[2]
+        close += [np.float32(zc) < np.float32(10.0)] * (len(edge_kf) - n0)
+        pts_true.append(xw_true)
+        pts.append(_f32(xw_true + point_error * 0.02 * rng.normal(size=3)))
+        begin.append(len(edge_kf))
+    n_pts = len(pts)
+    return dict(n_opt=N, n_fixed=F, n_points=n_pts, n_edges=len(edge_kf), iterations=int((4 if large else 8) if iterations is None else iterations),
+                n_cameras=1, lambda_init=float((1e-2 if large else 1e0) if lambda_init is None else lambda_init), fx=fx, fy=fy, cx=cx, cy=cy, bf=bf,
+                Rcb=Rcb, tcb=tcb, Rbc=Rbc, tbc=tbc, window=window, window_imu=np.ones(N, np.uint8), prev=prev, fixed_Rcw=fixed_Rcw,
+                fixed_tcw=fixed_tcw, inertial=inertial, points=np.array(pts, np.float64).reshape(n_pts, 3),
+                point_edge_begin=np.array(begin, np.int32), edge_kf=np.array(edge_kf, np.int32), obs=np.array(obs, np.float64).reshape(-1, 3),
+                inv_sigma2=np.array(w, np.float32), stereo=np.array(st, np.uint8), close=np.array(close, np.uint8),
+                is_outlier=np.array(is_out, bool), large=bool(large), truth=dict(window=truth, points=np.array(pts_true).reshape(n_pts, 3)))

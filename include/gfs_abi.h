@@ -1452,6 +1452,70 @@ void gfs_pose_inertial_destroy(gfs_pose_inertial* h);
 int gfs_pose_inertial_optimize(gfs_pose_inertial* h, const gfs_pose_inertial_problem* problems, int B, gfs_pose_inertial_solution* solutions);
 
 /* ============================================================================================
+ * 20. LocalInertialBA — the inertial local bundle adjustment of LocalMapping::Run once the IMU is initialised
+ *     (src/LocalMapping.cc:186-228, Optimizer::LocalInertialBA src/Optimizer.cc:3056-3702): the numeric core from
+ *     optimizer.initializeOptimization() (:3589) to the end of the two classification loops (:3626).  The pointer-graph gather and
+ *     the write-back are gfs_host::LocalInertialBA's (geoflowslam_amd/host/gfs_adaptors.hpp).
+ *    One optimize(iterations) of the fork's OptimizationAlgorithmLevenberg over n_opt window key frames of 15 unknowns (pose,
+ *    velocity, gyro bias, accelerometer bias), marginalised map points and the chain of inertial edges; the whole solve is queued at
+ *    once, the trial decisions are made on the device, the host waits once.  csrc/lba_inertial_rule.hpp and DESIGN.md section 26
+ *    state the rule, the quirks kept and the written rules; every output is the sequential restatement's
+ *    (tests/host/lba_inertial_restatement.cpp) byte for byte.  There is no stop flag: the reference polls none (:3594).
+ *    Key-frame indices of edge_kf: 0 .. n_opt - 1 the window, newest first; n_opt the fixed key frame in front of the window (prev);
+ *    n_opt + 1 + k the k-th other fixed key frame.  The visual edges come point by point (point_edge_begin), within a point in
+ *    observation order.  One camera and one IMU calibration for the whole window; matrices row-major.
+ *    Refused before anything is staged, the handle left usable -- GFS_ERR_CAPACITY: n_opt, n_fixed, n_points, n_edges or the number
+ *    of Schur pairs above what the handle was created for; GFS_ERR_INVALID_ARG: a NULL required array, n_opt < 1, iterations < 0,
+ *    a negative count, point_edge_begin not ascending from 0 to n_edges, an edge_kf out of range; GFS_ERR_UNSUPPORTED: a window key
+ *    frame without IMU (window_imu[i] == 0), n_cameras != 1.
+ * ============================================================================================ */
+typedef struct {  /* EdgeInertial, EdgeGyroRW, EdgeAccRW onto window key frame i: pKFi->mpImuPreintegrated as the constructors leave it */
+  float dR[9], dV[3], dP[3], JRg[9], JVg[9], JVa[9], JPg[9], JPa[9];
+  float preint_bg[3], preint_ba[3];
+  float dT;
+  double info_inertial[81];        /* after the constructor's inverse and eigenvalue clamp; the library applies the 1e-2 of i = N - 1 */
+  double info_gyro_rw[9];          /* C.block<3,3>(9,9).cast<double>().inverse() (:3384) */
+  double info_acc_rw[9];           /* C.block<3,3>(12,12)... (:3393) */
+} gfs_lba_inertial_edge;
+typedef struct {
+  int32_t n_opt;                   /* N: optimisable temporal key frames, newest first */
+  int32_t n_fixed;                 /* other fixed key frames (lFixedKeyFrames without the window's predecessor), at most 200 */
+  int32_t n_points, n_edges;
+  int32_t iterations;              /* opt_it: 8, or 4 with bLarge */
+  int32_t n_cameras;               /* 1; anything else is refused */
+  double lambda_init;              /* setUserLambdaInit: 1e0, or 1e-2 with bLarge */
+  double fx, fy, cx, cy, bf;
+  double Rcb[9], tcb[3], Rbc[9], tbc[3];
+  const gfs_imu_state* window;     /* [n_opt] */
+  const uint8_t* window_imu;       /* [n_opt] pKFi->bImu */
+  gfs_imu_state prev;              /* the fixed key frame in front of the window: all four vertices fixed */
+  const double* fixed_Rcw;         /* [n_fixed][9] */
+  const double* fixed_tcw;         /* [n_fixed][3] */
+  const gfs_lba_inertial_edge* inertial;  /* [n_opt]: set i joins key frame i + 1 (or prev) to key frame i */
+  const double* points;            /* [n_points][3] pMP->GetWorldPos(), doubles from floats */
+  const int32_t* point_edge_begin; /* [n_points + 1] */
+  const int32_t* edge_kf;          /* [n_edges] */
+  const double* obs;               /* [n_edges][3] kpUn.pt.x, kpUn.pt.y, mvuRight (ignored for a mono edge) */
+  const float* inv_sigma2;         /* [n_edges] */
+  const uint8_t* stereo;           /* [n_edges] 1: EdgeStereo, 0: EdgeMono */
+  const uint8_t* close;            /* [n_edges] pMP->mTrackDepth < 10.f (read for mono edges) */
+} gfs_lba_inertial_problem;
+typedef struct {
+  gfs_imu_state* window;           /* [n_opt] Rwb, twb, Rcw, tcw, v, bg, ba as doubles */
+  double* points;                  /* [n_points][3] */
+  double* edge_chi2;               /* [n_edges] e->chi2() as the edges hold it after optimize */
+  uint8_t* edge_depth_positive;    /* [n_edges] isDepthPositive() at the returned estimate */
+  uint8_t* edge_erase;             /* [n_edges] the classification loops' verdict (:3601-3626) */
+  float err, err_end;              /* the fail gate (2 * err < err_end || isnan ...) && !bLarge is the caller's */
+  int32_t iterations_run, trials_run;
+  double final_lambda;
+} gfs_lba_inertial_solution;
+typedef struct gfs_lba_inertial gfs_lba_inertial;
+int gfs_lba_inertial_create(int device, int max_opt, int max_fixed, int max_points, int max_edges, gfs_lba_inertial** out);
+void gfs_lba_inertial_destroy(gfs_lba_inertial* h);
+int gfs_lba_inertial_solve(gfs_lba_inertial* h, const gfs_lba_inertial_problem* problem, gfs_lba_inertial_solution* solution);
+
+/* ============================================================================================
  * Timing helper for the harness: HIP events on a given stream (bench.py measures the dominant kernel
  * with these rather than torch events, which only see torch's current stream).
  * ============================================================================================ */
