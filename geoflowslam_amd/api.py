@@ -324,6 +324,39 @@ def pose_inertial_result(S, keep, n, mode):
                 rounds_run=int(S.rounds_run), avg_reproj=np.float32(S.avg_reproj), H=np.array(S.H[:D * D]).reshape(D, D))
 
 
+class PoseLidarInertialProblem(C.Structure):  # gfs_pose_lidar_inertial_problem
+    _fields_ = [("vi", PoseInertialProblem), ("q", C.c_float * 4), ("t", C.c_float * 3), ("tcb_q", C.c_float * 4), ("tcb_t", C.c_float * 3),
+                ("kf_time_gap", C.c_double), ("n_cloud", C.c_int32), ("cloud", C.c_void_p), ("map", C.c_void_p)]
+
+
+class PoseLidarInertialSolution(C.Structure):  # gfs_pose_lidar_inertial_solution
+    _fields_ = [("vi", PoseInertialSolution), ("n_lidar_inliers", C.c_int32), ("residual", C.c_float), ("round_edges", C.c_int32 * 4),
+                ("round_chi2", C.c_float * 4), ("round_valid", C.c_int32 * 4)]
+
+
+def pose_lidar_inertial_structs(prob, map_handle=None):
+    """ctypes views of one problem dict (synth.pose_lidar_inertial_problem; shared with the CPU restatement's tests): the keys of
+    pose_inertial_structs plus q, t (the stored float Tcw), tcb_q, tcb_t, kf_time_gap and cloud [n][3] (None: a null cloud)."""
+    P, S = PoseLidarInertialProblem(), PoseLidarInertialSolution()
+    P.vi, S.vi, keep, n = pose_inertial_structs(prob)
+    cloud = np.zeros((0, 3), np.float32) if prob.get("cloud") is None else np.ascontiguousarray(prob["cloud"], np.float32).reshape(-1, 3)
+    keep["cloud"] = cloud
+    for name in ("q", "t", "tcb_q", "tcb_t"):
+        _fill(getattr(P, name), np.asarray(prob[name], np.float32))
+    P.kf_time_gap = float(prob["kf_time_gap"])
+    P.n_cloud = len(cloud)
+    P.cloud = cloud.ctypes.data if len(cloud) else None
+    P.map = map_handle
+    return P, S, keep, n
+
+
+def pose_lidar_inertial_result(S, keep, n, mode):
+    r = pose_inertial_result(S.vi, keep, n, mode)
+    r.update(n_lidar_inliers=int(S.n_lidar_inliers), residual=np.float32(S.residual), round_edges=list(S.round_edges),
+             round_chi2=np.array(S.round_chi2[:], np.float32), round_valid=list(S.round_valid))
+    return r
+
+
 class LbaInertialEdge(C.Structure):
     _fields_ = [("dR", C.c_float * 9), ("dV", C.c_float * 3), ("dP", C.c_float * 3), ("JRg", C.c_float * 9), ("JVg", C.c_float * 9),
                 ("JVa", C.c_float * 9), ("JPg", C.c_float * 9), ("JPa", C.c_float * 9), ("preint_bg", C.c_float * 3), ("preint_ba", C.c_float * 3),
@@ -1041,6 +1074,8 @@ ABI_SYMBOLS = [
     "gfs_sim3_opt_create", "gfs_sim3_opt_destroy", "gfs_sim3_optimize", "gfs_test_glibc_exp",
     "gfs_sim3_ransac_iterations", "gfs_sim3_ransac_create", "gfs_sim3_ransac_solve", "gfs_sim3_ransac_destroy",
     "gfs_pose_inertial_create", "gfs_pose_inertial_optimize", "gfs_pose_inertial_destroy",
+    "gfs_pose_lidar_inertial_create", "gfs_pose_lidar_inertial_optimize", "gfs_pose_lidar_inertial_destroy",
+    "gfs_pose_lidar_inertial_fetch_edges",
     "gfs_lba_inertial_create", "gfs_lba_inertial_solve", "gfs_lba_inertial_destroy",
     "gfs_frame_create", "gfs_frame_destroy", "gfs_depth_to_cloud", "gfs_depth_to_cloud_batch_device", "gfs_depth_convert_u16_batch_device", "gfs_stereo_from_rgbd",
     "gfs_stereo_from_rgbd_batch_device",
@@ -1177,6 +1212,11 @@ def lib():
             L.gfs_pose_inertial_create.argtypes = [i, i, i, C.POINTER(vp)]
             L.gfs_pose_inertial_destroy.argtypes = [vp]
             L.gfs_pose_inertial_optimize.argtypes = [vp, vp, i, vp]
+        if hasattr(L, "gfs_pose_lidar_inertial_create"):
+            L.gfs_pose_lidar_inertial_create.argtypes = [i, i, i, i, C.POINTER(vp)]
+            L.gfs_pose_lidar_inertial_destroy.argtypes = [vp]
+            L.gfs_pose_lidar_inertial_optimize.argtypes = [vp, vp, i, vp]
+            L.gfs_pose_lidar_inertial_fetch_edges.argtypes = [vp, i, i, vp, vp, vp, i, C.POINTER(C.c_int32)]
         if hasattr(L, "gfs_lba_inertial_create"):
             L.gfs_lba_inertial_create.argtypes = [i, i, i, i, i, C.POINTER(vp)]
             L.gfs_lba_inertial_destroy.argtypes = [vp]
@@ -2653,6 +2693,51 @@ class PoseInertialOptimizer:
         _check(lib().gfs_pose_inertial_optimize(self.h, PP, B, SS), "gfs_pose_inertial_optimize")
         res = [pose_inertial_result(SS[f], *keeps[f]) for f in range(B)]
         return res[0] if single else res
+
+
+class PoseLidarInertialOptimizer:
+    """Optimizer::PoseLidarVisualInertialOptimizationLastKeyFrame / ...LastFrame (reference src/Optimizer.cc:6285-6760, 7173-7678) on
+    flattened problems (gfs_pose_lidar_inertial_problem in include/gfs_abi.h): the inertial pose graph plus, in
+    every round, the point-to-plane edges of the frame's cloud against a LidarMap.  A problem dict carries its map under "map" (a
+    LidarMap, or None without a cloud); every output is the sequential restatement's byte for byte."""
+
+    def __init__(self, max_obs=2048, max_cloud=8192, max_batch=8, device=0):
+        self.h = C.c_void_p()
+        _check(lib().gfs_pose_lidar_inertial_create(device, int(max_obs), int(max_cloud), int(max_batch), C.byref(self.h)),
+               "gfs_pose_lidar_inertial_create")
+
+    def close(self):
+        if getattr(self, "h", None) and _lib is not None:
+            _lib.gfs_pose_lidar_inertial_destroy(self.h)
+        self.h = None
+
+    __del__ = close
+
+    def optimize(self, problems):
+        """problems: one problem dict or a list of them (pose_lidar_inertial_structs) -> result dict(s): those of
+        PoseInertialOptimizer.optimize plus n_lidar_inliers, residual (float32), round_edges / round_chi2 / round_valid [4].  Raises
+        GfsError (GFS_ERR_CAPACITY / GFS_ERR_INVALID_ARG) on a refusal; the handle stays usable."""
+        single = isinstance(problems, dict)
+        probs = [problems] if single else list(problems)
+        B = len(probs)
+        PP, SS = (PoseLidarInertialProblem * max(B, 1))(), (PoseLidarInertialSolution * max(B, 1))()
+        keeps = []
+        for f, prob in enumerate(probs):
+            m = prob.get("map")
+            P, S, keep, n = pose_lidar_inertial_structs(prob, m.h if m is not None else None)
+            PP[f], SS[f] = P, S
+            keeps.append((keep, n, P.vi.mode))
+        _check(lib().gfs_pose_lidar_inertial_optimize(self.h, PP, B, SS), "gfs_pose_lidar_inertial_optimize")
+        res = [pose_lidar_inertial_result(SS[f], *keeps[f]) for f in range(B)]
+        return res[0] if single else res
+
+    def fetch_edges(self, b, rnd, cap=8192):
+        """The lidar edges problem b of the last call generated in round rnd: (index [n], plane [n][4], s [n])."""
+        idx, pl, s, n = np.zeros(cap, np.int32), np.zeros((cap, 4), np.float32), np.zeros(cap, np.float32), C.c_int32()
+        _check(lib().gfs_pose_lidar_inertial_fetch_edges(self.h, b, rnd, _p(idx), _p(pl), _p(s), cap, C.byref(n)),
+               "gfs_pose_lidar_inertial_fetch_edges")
+        m = min(n.value, cap)
+        return idx[:m].copy(), pl[:m].copy(), s[:m].copy()
 
 
 class LocalInertialBA:

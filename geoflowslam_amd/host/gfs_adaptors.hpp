@@ -3769,6 +3769,83 @@ class PoseInertialDevice {
 };
 
 // ------------------------------------------------------------------------------------------------------------------------
+// int Optimizer::PoseLidarVisualInertialOptimizationLastKeyFrame(Frame* pFrame, pcl::PointCloud<PointType>::Ptr laserCloudSurfFromMapDS,
+//     bool bRecInit, const bool bFrame2FrameReprojError, const bool bFrame2MapReprojError, const int nIterations,
+//     int& nInliersLidar, float& residual)                                                                     src/Optimizer.cc:6285-6760
+// int Optimizer::PoseLidarVisualInertialOptimizationLastFrame(...same...)                                      :7173-7678
+// the two calls that end Tracking::TrackLocalMap for IMU_RGBD with useLidarObs() (src/Tracking.cc:3763-3798), around one flat solve
+// (include/gfs_abi.h section 21).  The gather and the write-back are those of PoseInertialOptimization above,
+// which runs underneath; on top of them:
+//   gather:     the stored Tcw and mTcb as float quaternion (x, y, z, w) and translation, the signed time gap to the last key frame
+//               (key-frame mode), the downsampled cloud in the camera frame (a null mpPointCloudDownsampled gives n_cloud = 0), the map
+//               handle in place of laserCloudSurfFromMapDS (gfs_lidar_map_build or gfs_lidar_map_set made it).
+//   write back: nInliersLidar and residual, by reference.
+// Marginalize and ConstraintPoseImu stay the reference's own (Access::new_constraint).
+// Frame, beyond the list above: mTimeStamp, mpPointCloudDownsampled; KeyFrame: mTimeStamp; and of `Access`, beyond the list above:
+//     static void stored_pose(const Frame*, float q[4], float t[3]);       // pFrame->GetPose(): unit_quaternion().coeffs(), translation()
+//     static void stored_tcb(const Frame*, float q[4], float t[3]);        // pFrame->mImuCalib.mTcb
+//     static void cloud(const Cloud&, std::vector<float>& xyz);            // the points of *mpPointCloudDownsampled, [n][3]
+// ------------------------------------------------------------------------------------------------------------------------
+template <class Access, class Frame, class Solve>
+int PoseLidarVisualInertialOptimization(Solve&& solve, int mode, Frame* pFrame, const gfs_lidar_map* map, bool bRecInit,
+                                        const bool bFrame2FrameReprojError, const bool bFrame2MapReprojError, const int nIterations,
+                                        int& nInliersLidar, float& residual) {
+  auto with_lidar = [&](const gfs_pose_inertial_problem& p, gfs_pose_inertial_solution& s) {
+    gfs_pose_lidar_inertial_problem P{};
+    P.vi = p;
+    Access::stored_pose(pFrame, P.q, P.t);
+    Access::stored_tcb(pFrame, P.tcb_q, P.tcb_t);
+    P.kf_time_gap = mode == GFS_POSE_INERTIAL_LAST_KEYFRAME ? pFrame->mTimeStamp - pFrame->mpLastKeyFrame->mTimeStamp : 0.0;
+    std::vector<float> cloud;
+    if (pFrame->mpPointCloudDownsampled) Access::cloud(*pFrame->mpPointCloudDownsampled, cloud);
+    P.n_cloud = (int)(cloud.size() / 3);
+    P.cloud = cloud.data();
+    P.map = map;
+    gfs_pose_lidar_inertial_solution S{};
+    S.vi.outlier = s.outlier;
+    solve(P, S);
+    s = S.vi;
+    nInliersLidar = S.n_lidar_inliers;
+    residual = S.residual;
+  };
+  return PoseInertialOptimization<Access>(with_lidar, mode, pFrame, bRecInit, bFrame2FrameReprojError, bFrame2MapReprojError, nIterations);
+}
+template <class Access, class Frame, class Solve>
+int PoseLidarVisualInertialOptimizationLastKeyFrame(Solve&& solve, Frame* pFrame, const gfs_lidar_map* map, bool bRecInit,
+                                                    const bool bFrame2FrameReprojError, const bool bFrame2MapReprojError, const int nIterations,
+                                                    int& nInliersLidar, float& residual) {
+  return PoseLidarVisualInertialOptimization<Access>(solve, GFS_POSE_INERTIAL_LAST_KEYFRAME, pFrame, map, bRecInit, bFrame2FrameReprojError,
+                                                     bFrame2MapReprojError, nIterations, nInliersLidar, residual);
+}
+template <class Access, class Frame, class Solve>
+int PoseLidarVisualInertialOptimizationLastFrame(Solve&& solve, Frame* pFrame, const gfs_lidar_map* map, bool bRecInit,
+                                                 const bool bFrame2FrameReprojError, const bool bFrame2MapReprojError, const int nIterations,
+                                                 int& nInliersLidar, float& residual) {
+  return PoseLidarVisualInertialOptimization<Access>(solve, GFS_POSE_INERTIAL_LAST_FRAME, pFrame, map, bRecInit, bFrame2FrameReprojError,
+                                                     bFrame2MapReprojError, nIterations, nInliersLidar, residual);
+}
+
+// numeric core of both: one problem (or a batch) on the device
+class PoseLidarInertialDevice {
+ public:
+  explicit PoseLidarInertialDevice(int max_obs = 4096, int max_cloud = 8192, int max_batch = 1, int device = 0) {
+    check(gfs_pose_lidar_inertial_create(device, max_obs, max_cloud, max_batch, &h_), "gfs_pose_lidar_inertial_create");
+  }
+  ~PoseLidarInertialDevice() { gfs_pose_lidar_inertial_destroy(h_); }
+  PoseLidarInertialDevice(const PoseLidarInertialDevice&) = delete;
+  PoseLidarInertialDevice& operator=(const PoseLidarInertialDevice&) = delete;
+  void solve(const gfs_pose_lidar_inertial_problem& p, gfs_pose_lidar_inertial_solution& s) {
+    check(gfs_pose_lidar_inertial_optimize(h_, &p, 1, &s), "gfs_pose_lidar_inertial_optimize");
+  }
+  void solve(const gfs_pose_lidar_inertial_problem* p, int B, gfs_pose_lidar_inertial_solution* s) {
+    check(gfs_pose_lidar_inertial_optimize(h_, p, B, s), "gfs_pose_lidar_inertial_optimize");
+  }
+
+ private:
+  gfs_pose_lidar_inertial* h_ = nullptr;
+};
+
+// ------------------------------------------------------------------------------------------------------------------------
 // void Optimizer::LocalInertialBA(KeyFrame* pKF, bool* pbStopFlag, bool pbICPFlag, Map* pMap, int& num_fixedKF, int& num_OptKF,
 //                                 int& num_MPs, int& num_edges, bool bLarge, bool bRecInit)                  src/Optimizer.cc:3056-3702
 // the local BA LocalMapping::Run calls for every new key frame once the IMU is initialised (src/LocalMapping.cc:186-228), around one

@@ -1619,6 +1619,46 @@ def pose_inertial_problem(seed, mode, n_obs=300, outlier_share=0.15, stereo_shar
                 truth=dict(Rwb=Rwb2, twb=p2, v=v2, bg=bg_true, ba=ba_true))
 
 
+def pose_lidar_inertial_problem(seed, mode, n_obs=300, n_cloud=600, voxel=0.1, kf_time_gap=0.4, map_shift=0.0, start=None, n_keyframes=3,
+                                width=320, height=240, prior_scale=1.0, **kw):
+    """Synthetic Optimizer::PoseLidarVisualInertialOptimizationLastKeyFrame (mode 0) / ...LastFrame (mode 1) problem (include/gfs_abi.h
+    section 21): a pose_inertial_problem (`kw` and `start` go to it) put on a Scene.  The frame cloud is the scene seen from the TRUE
+    current camera, about `n_cloud` points in camera coordinates; the local map is `n_keyframes` renders from nearby poses carried
+    into the problem's world and voxel-averaged at `voxel` metres, as pose_lidar_frame builds them, then moved by `map_shift` metres
+    along every axis (a large shift: no point gets an edge).  `prior_scale` multiplies the previous frame's prior: 1e6 holds that frame
+    still, so that in frame mode an `inconsistent` preintegration stays in the inertial edge (chi2IMU > 15).  Returns the fields of
+    gfs_pose_lidar_inertial_problem plus map_xyz and the truth."""
+    p = pose_inertial_problem(seed, mode, n_obs=n_obs, start=start, **kw)
+    p["prior_H"] = p["prior_H"] * float(prior_scale)
+    rng = np.random.default_rng(seed + 0x51D)
+    sc = Scene(seed)
+    Rwb, twb = p["truth"]["Rwb"], p["truth"]["twb"]
+    Rcb, tcb = p["Rcb"], p["tcb"]
+    T_wc = np.eye(4)  # world <- camera, at the truth
+    T_wc[:3, :3] = (Rcb @ Rwb.T).T
+    T_wc[:3, 3] = -T_wc[:3, :3] @ (Rcb @ (-Rwb.T @ twb) + tcb)
+    S_c = random_motion(rng, trans=0.05, rot_deg=2.0)  # scene <- camera
+    A = T_wc @ np.linalg.inv(S_c)  # world <- scene
+    pts = []
+    for k in range(n_keyframes):
+        S_kf = S_c @ random_motion(rng, trans=0.15, rot_deg=4.0)
+        _, d = sc.render(width, height, S_kf, 100 + k)
+        c = depth_to_cloud(d, 2)[:, :3].astype(np.float64)
+        c = c @ S_kf[:3, :3].T + S_kf[:3, 3]
+        pts.append(c @ A[:3, :3].T + A[:3, 3])
+    map_xyz = voxel_average(np.concatenate(pts), voxel) + np.float32(map_shift)
+    cloud = np.zeros((0, 3), np.float32)
+    if n_cloud > 0:
+        _, d = sc.render(width, height, S_c, 7)
+        cloud = depth_to_cloud(d, 1)[:, :3]
+        assert len(cloud) >= n_cloud, (len(cloud), n_cloud)
+        cloud = cloud[np.sort(rng.choice(len(cloud), n_cloud, replace=False))]
+    cur = p["cur"]
+    p.update(q=_quat_from_R(cur["Rcw"]).astype(np.float32), t=cur["tcw"].astype(np.float32), tcb_q=_quat_from_R(Rcb).astype(np.float32),
+             tcb_t=tcb.astype(np.float32), kf_time_gap=float(kf_time_gap), cloud=np.ascontiguousarray(cloud, np.float32), map_xyz=map_xyz)
+    return p
+
+
 def lba_inertial_window(seed, n_opt=10, n_fixed=5, n_points=300, stereo_share=0.85, outlier_share=0.05, large=False, inconsistent=(),
                         single_mono_points=0, fixed_heavy_points=0, pose_error=1.0, point_error=1.0, obs_per_point=(3, 7), outlier_px=25.0,
                         dt=0.4, preint_noise=1.0, noise_scale=1.0, iterations=None, lambda_init=None):

@@ -1516,6 +1516,46 @@ void gfs_lba_inertial_destroy(gfs_lba_inertial* h);
 int gfs_lba_inertial_solve(gfs_lba_inertial* h, const gfs_lba_inertial_problem* problem, gfs_lba_inertial_solution* solution);
 
 /* ============================================================================================
+ * 21. PoseLidarVisualInertialOptimization — the pose step that ends Tracking::TrackLocalMap for IMU_RGBD with point-cloud
+ *     observations (src/Tracking.cc:3763-3798): Optimizer::PoseLidarVisualInertialOptimizationLastKeyFrame (src/Optimizer.cc:6285-6760)
+ *     and ...LastFrame (:7173-7678).  The graph of section 19 plus, in every round, the point-to-plane edges GenerateLidarEdge builds
+ *     from the frame's downsampled cloud and the local map (the association of section 11: 5-NN, float QR plane, gates, weight),
+ *     differentiated numerically as g2o does.  Per round an association launch over all problems and a round launch (one workgroup a
+ *     problem), then one final launch; everything is queued at once and the host waits once.  csrc/pose_lidar_inertial_rule.hpp and
+ *     DESIGN.md section 27 state the rule and the quirks kept; every output is the sequential restatement's
+ *     (tests/host/pose_lidar_inertial_restatement.cpp) byte for byte, alone or inside any batch.
+ *    Refused before anything is staged, the handle left usable -- GFS_ERR_CAPACITY: B above max_batch, n_obs above max_obs, n_cloud
+ *    above max_cloud; GFS_ERR_INVALID_ARG: a NULL required array (those of section 19; cloud when n_cloud > 0), a negative count,
+ *    n_rounds outside 1..4, an unknown mode, n_cloud > 0 with a NULL map or a map of fewer than 5 points, a map on another device.
+ * ============================================================================================ */
+typedef struct {
+  gfs_pose_inertial_problem vi;    /* every field of section 19, with its meaning there */
+  float q[4], t[3];                /* pFrame->GetPose(): the stored Sophus::SE3f Tcw, quaternion (x, y, z, w) */
+  float tcb_q[4], tcb_t[3];        /* pFrame->mImuCalib.mTcb as stored, beside the doubles vi.Rcb / vi.tcb */
+  double kf_time_gap;              /* pFrame->mTimeStamp - pKF->mTimeStamp, signed (read in key-frame mode) */
+  int32_t n_cloud;                 /* mpPointCloudDownsampled->size(); 0 for a null cloud */
+  const float* cloud;              /* [n_cloud][3] camera frame */
+  const struct gfs_lidar_map* map; /* laserCloudSurfFromMapDS (section 11), on the handle's device; may be NULL when n_cloud == 0 */
+} gfs_pose_lidar_inertial_problem;
+typedef struct {
+  gfs_pose_inertial_solution vi;   /* every field of section 19; H includes the lidar edges of the last entered round */
+  int32_t n_lidar_inliers;         /* nInliersLidar */
+  float residual;                  /* residual */
+  int32_t round_edges[4];          /* lidar edges generated in each round that ran */
+  float round_chi2[4];             /* chi2Lidar of the round */
+  int32_t round_valid[4];          /* valid_edge of the round */
+} gfs_pose_lidar_inertial_solution;
+typedef struct gfs_pose_lidar_inertial gfs_pose_lidar_inertial;
+int gfs_pose_lidar_inertial_create(int device, int max_obs, int max_cloud, int max_batch, gfs_pose_lidar_inertial** out);
+void gfs_pose_lidar_inertial_destroy(gfs_pose_lidar_inertial* h);
+int gfs_pose_lidar_inertial_optimize(gfs_pose_lidar_inertial* h, const gfs_pose_lidar_inertial_problem* problems, int B,
+                                     gfs_pose_lidar_inertial_solution* solutions);
+/* Diagnostic: the lidar edges problem b of the last call generated in `round`, in cloud-index order.  *n is their number; at most
+ * cap are written to index [cap], plane [cap][4], s [cap]. */
+int gfs_pose_lidar_inertial_fetch_edges(gfs_pose_lidar_inertial* h, int b, int round, int32_t* index, float* plane, float* s, int cap,
+                                        int32_t* n);
+
+/* ============================================================================================
  * Timing helper for the harness: HIP events on a given stream (bench.py measures the dominant kernel
  * with these rather than torch events, which only see torch's current stream).
  * ============================================================================================ */
