@@ -209,6 +209,8 @@ struct s3r_trace {
   int32_t pad;
   double final_lambda[2];
   double stale_largest_difference;  // largest |chi2 the first check read - chi2 at the estimate| over the edges
+  int32_t stale_x_applied[2];        // failed solves at which the x the solver kept (an earlier solve's, of this phase or the one before) was non-zero
+  int32_t failed_after_success[2];   // a failed solve followed a successful one inside the same optimize()
 };
 
 namespace {
@@ -345,6 +347,7 @@ struct Graph {
     if (n_active == 0) return 0;  // no vertex to optimize
     T lambda = 0, ni = 2;
     int n_bad = 0, run = 0, reason = 1;
+    bool solved = false;  // a solve of this call succeeded
     for (int it = 0; it < its; it++) {
       compute_active_errors();
       T currentChi = active_robust_chi2(), tempChi = currentChi;
@@ -365,6 +368,13 @@ struct Graph {
         for (int k = 0; k < 49; k++) Hl[k] = H[k];
         for (int j = 0; j < 7; j++) Hl[8 * j] += lambda;
         const bool ok2 = ldlt7_solve_positive(Hl, b, x);
+        if (tr && !ok2) {
+          bool kept = false;
+          for (int j = 0; j < 7; j++) kept = kept || x[j] != 0;  // (a NaN counts: it is not the zero a fresh solver starts with)
+          tr->stale_x_applied[phase] += kept;
+          tr->failed_after_success[phase] |= solved;
+        }
+        solved = solved || ok2;
         oplus(x);
         compute_active_errors();
         tempChi = active_robust_chi2();

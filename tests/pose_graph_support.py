@@ -392,12 +392,13 @@ class PoseGraph:
         return x, ok, trial, scale
 
     def optimize(self, iterations=20, lambda_init=1e-16):
-        """optimize(iterations) -> dict(est, edge_chi2, iterations_run, final_chi2, final_lambda, trace); trace: one (iteration,
-        accepted, chi2 before, chi2 of the trial) per trial"""
+        """optimize(iterations) -> dict(est, edge_chi2, iterations_run, final_chi2, final_lambda, trace, alphas, gains); trace: one
+        (iteration, accepted, chi2 before, chi2 of the trial) per trial; alphas: per trial 1 - (2 rho - 1)^3 where it was accepted, else
+        None; gains: per iteration (chi2 it began with, chi2 it ended with), the two sides of `(ini - current) 1e3 < ini`"""
         dt = self.dt
         est = self.est.copy()
         lam, ni, n_bad, iters = dt(lambda_init), dt(2), 0, 0
-        trace = []
+        trace, alphas, gains = [], [], []
         last_chi = None
         runs = iterations > 0 and self.F > 0
         for it in range(iterations if runs else 0):
@@ -410,6 +411,7 @@ class PoseGraph:
                 rho = (current - temp) / (scale + dt(1e-3))
                 accepted = bool(rho > 0 and np.isfinite(temp))
                 trace.append((it, accepted, current, temp))
+                alphas.append(1 - (2 * rho - 1) ** 3 if accepted else None)
                 if accepted:
                     alpha = 1 - (2 * rho - 1) ** 3
                     alpha = min(alpha, dt(2) / dt(3))
@@ -425,6 +427,7 @@ class PoseGraph:
                     break
             iters += 1
             last_chi = current
+            gains.append((ini, current))
             if qmax == 10 or rho == 0:
                 break
             n_bad = n_bad + 1 if (ini - current) * 1e3 < ini else 0
@@ -432,7 +435,7 @@ class PoseGraph:
                 break
         chi = self.errors(est)[1]
         return dict(est=est, edge_chi2=chi, iterations_run=iters, final_chi2=last_chi if runs else self.total(chi),
-                    final_lambda=lam if runs else dt(0), trace=trace)
+                    final_lambda=lam if runs else dt(0), trace=trace, alphas=alphas, gains=gains)
 
 
 def correct_points(before, after, points, ref):
@@ -487,6 +490,131 @@ def map_solution(name, dtype=np.float64):
         p = map_problem(name)
         _cache[key] = PoseGraph(p, dtype).optimize(p["iterations"], p["lambda_init"])
     return _cache[key]
+
+
+# ---- full solves whose Levenberg decisions are not rounding noise (tests/test_pose_graph_levenberg_inputs.py holds each to its shape
+# and its margins on the CPU; tests/test_gpu_pose_graph.py compares iterations, trials and the final lambda on them) -------------------
+DECISION_MARGIN = 1e-4  # of chi2: 100 x the 1e-6 relative bar the GPU's final chi2 is held to
+
+
+def decisions(sol):
+    """an optimize() result -> per iteration (accept / reject sequence "rrA", smallest relative margin of its decisions, an accepted
+    trial has 1/3 < alpha < 2/3).  The decisions: the sign of current - temp in every trial, relative to current, and
+    (ini - current) 1e3 < ini at the iteration's end, relative to ini.  A failed solve or a chi2 that is no number has margin 0."""
+    out = []
+    for (it, accepted, current, temp), alpha in zip(sol["trace"], sol["alphas"]):
+        current, temp = float(current), float(temp)
+        margin = abs(current - temp) / abs(current) if np.isfinite(temp) and np.isfinite(current) and current != 0 and temp < 1e300 else 0.0
+        if it == len(out):
+            out.append(["", np.inf, False])
+        out[it][0] += "A" if accepted else "r"
+        out[it][1] = min(out[it][1], margin)
+        out[it][2] = out[it][2] or (alpha is not None and 1 / 3 < float(alpha) < 2 / 3)
+    for row, (ini, current) in zip(out, sol["gains"]):
+        ini, current = float(ini), float(current)
+        row[1] = min(row[1], abs((ini - current) * 1e3 - ini) / abs(ini) if np.isfinite(ini) and ini != 0 else 0.0)
+    return [tuple(r) for r in out]
+
+
+def _ring10():
+    V = 10
+    return [1] + [0] * (V - 1), [(i, i - 1) for i in range(1, V)] + [(i, i - 2) for i in range(2, V)] + [(V - 1, 0), (0, V - 2)]
+
+
+def _far_start_ring(seed):
+    """a ring of nine free vertices, fixed scale, consistent measurements, whose estimates start about a radian and two metres away
+    from them: far enough from linear for Levenberg to reject steps (synth.pose_graph's fixed-scale maps never do before chi2 has
+    converged), and with small residuals at the end, so that the rule's own rounding noise stays small"""
+    fixed, edges = _ring10()
+    p = random_graph(seed, fixed, edges, True)
+    rng = np.random.default_rng(2000 + seed)
+    V = len(fixed)
+    u = np.concatenate([rng.normal(0, 1.0, (V, 3)), rng.normal(0, 2.0, (V, 3)), np.zeros((V, 1))], 1)
+    u[0] = 0
+    est = sim3_mul(sim3_exp(u)[0], pack8(p["vertex_q"], p["vertex_t"], p["vertex_s"], np.float64))
+    est[:, :4] /= np.linalg.norm(est[:, :4], axis=1)[:, None]
+    return dict(p, vertex_q=est[:, :4].copy(), vertex_t=est[:, 4:7].copy())
+
+
+def _drifted_ring(seed):
+    from geoflowslam_amd import synth
+    return synth.pose_graph(seed, n_keyframes=10, fix_scale=False, icp_edges=True, drift=0.3)
+
+
+def _rejected_then_accepted(rows):
+    return any("r" in r[0] and r[0].endswith("A") for r in rows)
+
+
+# name -> (problem of a seed, first lambda, what the decisions must show, the seeds searched, the run ends at qmax == 10)
+LEVENBERG_SEARCHES = {
+    "rejected_then_accepted_fixed": (_far_start_ring, 1e-6, _rejected_then_accepted, range(0, 200), False),
+    "rejected_then_accepted_free": (_drifted_ring, 1.0, _rejected_then_accepted, range(0, 200), False),
+    "ends_qmax": (lambda seed: map_problem("ring10_free_icp"), 1e-16,
+                  lambda rows: len(rows) > 1 and rows[-1][0] == "r" * 10 and any("A" in r[0] for r in rows[:-1]), range(1), True),
+    "unclamped_alpha": (_drifted_ring, 1e-6, lambda rows: any(r[2] for r in rows), range(95, 200), False),  # (of range(200), 95 is the first)
+}
+INPUTS_BAR = 1e-6  # tests/test_pose_graph_oracle_inputs.py's: float64 and long double agree to this on a map that is a fair test
+
+
+def levenberg_case(name):
+    """The first seed whose float64 run shows what the case is named for within the iterations all of whose decisions hold at
+    DECISION_MARGIN, and on which the long-double run takes the same decisions and ends within INPUTS_BAR of the float64 poses.
+    `iterations` is the number of those iterations (for ends_qmax: up to the iteration that uses its ten trials), and less than the
+    run would go on for, so the run ends by using its iterations up -> (problem, seed), computed once."""
+    if ("l", name) not in _cache:
+        make, lam, wanted, seeds, at_qmax = LEVENBERG_SEARCHES[name]
+        for seed in seeds:
+            p = make(seed)
+            rows = decisions(PoseGraph(p).optimize(20, lam))
+            good = 0
+            while good < len(rows) and rows[good][1] >= DECISION_MARGIN:
+                good += 1
+            # (an iteration that the 20-iteration run went on from did not end it: a run of that many iterations uses them up)
+            n = good if at_qmax else min(good, len(rows) - 1)
+            if n < 1 or (at_qmax and n != len(rows)) or not wanted(rows[:n]):
+                continue
+            p = dict(p, iterations=n, lambda_init=lam)
+            a, b = PoseGraph(p).optimize(n, lam), PoseGraph(p, np.longdouble).optimize(n, lam)
+            if [r[0] for r in decisions(a)] != [r[0] for r in decisions(b)] or max(pose_difference(a["est"], b["est"].astype(np.float64))[:2]) > INPUTS_BAR:
+                continue
+            _cache[("l", name)] = (p, seed)
+            _cache[("ls", name, "float64")], _cache[("ls", name, "longdouble")] = a, b
+            break
+        else:
+            raise AssertionError(f"{name}: no seed gives the wanted decisions")
+    return _cache[("l", name)]
+
+
+def levenberg_solution(name, dtype=np.float64):
+    key = ("ls", name, np.dtype(dtype).name)
+    if key not in _cache:
+        p = levenberg_case(name)[0]
+        _cache[key] = PoseGraph(p, dtype).optimize(p["iterations"], p["lambda_init"])
+    return _cache[key]
+
+
+# ---- estimates and measurements that are no numbers (eg_check validates scales and weights only) ---------------------------------
+def non_finite_problems():
+    """name -> ring10_fixed with one entry replaced: NaN in a free vertex's translation, inf in a measurement's, NaN in the fixed
+    vertex's quaternion"""
+    p = map_problem("ring10_fixed")
+    assert p["vertex_fixed"][0] and not p["vertex_fixed"][4]
+
+    def put(key, index, value):
+        a = np.array(p[key], np.float64, copy=True)
+        a[index] = value
+        return dict(p, **{key: a})
+    return {"nan_free_vertex_t": put("vertex_t", (4, 1), np.nan), "inf_edge_t": put("edge_t", (5, 0), np.inf),
+            "nan_fixed_vertex_q": put("vertex_q", (0, 2), np.nan)}
+
+
+def non_finite_solution(name):
+    """the float64 restatement's optimize() of one of non_finite_problems(), computed once"""
+    if ("n", name) not in _cache:
+        p = non_finite_problems()[name]
+        with np.errstate(all="ignore"):
+            _cache[("n", name)] = PoseGraph(p).optimize(p["iterations"], p["lambda_init"])
+    return _cache[("n", name)]
 
 
 def pose_difference(a, b):

@@ -21,7 +21,8 @@ END_NOT_RUN, END_ITERATIONS, END_QMAX, END_RHO_ZERO, END_NBAD = range(5)
 class Trace(C.Structure):
     _fields_ = [("end_reason", C.c_int32 * 2), ("rejected_trials", C.c_int32 * 2), ("failed_solves", C.c_int32 * 2),
                 ("last_trial_rejected", C.c_int32 * 2), ("stale_flag_differences", C.c_int32), ("pad", C.c_int32),
-                ("final_lambda", C.c_double * 2), ("stale_largest_difference", C.c_double)]
+                ("final_lambda", C.c_double * 2), ("stale_largest_difference", C.c_double), ("stale_x_applied", C.c_int32 * 2),
+                ("failed_after_success", C.c_int32 * 2)]
 
 
 def restatement():
@@ -52,7 +53,8 @@ def run(prob, long_double=False):
     res["ret"] = ret
     res["trace"] = dict(end_reason=tuple(T.end_reason), rejected_trials=tuple(T.rejected_trials), failed_solves=tuple(T.failed_solves),
                         last_trial_rejected=tuple(T.last_trial_rejected), stale_flag_differences=int(T.stale_flag_differences),
-                        final_lambda=tuple(T.final_lambda), stale_largest_difference=float(T.stale_largest_difference))
+                        final_lambda=tuple(T.final_lambda), stale_largest_difference=float(T.stale_largest_difference),
+                        stale_x_applied=tuple(T.stale_x_applied), failed_after_success=tuple(T.failed_after_success))
     return res
 
 
@@ -147,7 +149,104 @@ def constructed_cases():
     cases["rejected_trial"] = _search(far, lambda p, r: sum(r["trace"]["rejected_trials"]) > 0 and r["status"] == 1, range(1800, 2400))[0]
     cases["stale"] = _stale_case(far)
     cases["tie_below"], cases["tie_above"], cases["tie_pair"] = _tie_cases(cases["no_removal"])
+    cases.update(_degenerate_cases())
     return cases
+
+
+PROBLEM_ARRAYS = ("x1c", "x2c", "obs1", "obs2", "inv_sigma2_1", "inv_sigma2_2")
+DEGENERATE_CASES = ("failed_first_solve", "failed_after_success", "failed_across_phases", "nan_observation", "inf_observation", "nan_point",
+                    "nan_survives_first_check", "nan_survives_first_check_600", "z_zero", "behind_camera", "huge_observation",
+                    "fewer_than_ten_after_nan")
+NAN_PAIR = {"nan_survives_first_check": 4, "nan_survives_first_check_600": 520}  # case -> the pair whose x2c is NaN
+
+
+def changed(p, **changes):
+    """A copy of problem p with entries set: changed(p, obs1=((3, 0), nan)) sets obs1[3, 0]; a callable value is applied to the array."""
+    q = dict(p)
+    for k, v in changes.items():
+        q[k] = p[k].copy()
+        if callable(v):
+            v(q[k])
+        else:
+            q[k][v[0]] = v[1]
+    return q
+
+
+def _degenerate_cases():
+    """The part of constructed_cases() named by DEGENERATE_CASES: inputs on which the 7 x 7 solve fails or an edge's chi2 is not finite, every one found by a seeded search
+    on the float64 restatement (fixed scale; tests/test_sim3_opt_restatement.py asserts that each reaches what it is named for).  A
+    negative information is a test device only: it makes a system that is not positive, as lba_inertial_support._failed does.
+      failed_first_solve     all information zero: lambda = 0, no pivot, every solve fails and the solver's x stays 0
+      failed_after_success   negative information on the first 40 % of the pairs: in the first optimize() a solve fails after one that
+                             succeeded, and the x it kept is applied again
+      failed_across_phases   the first optimize() has no failed solve, the second fails at its first solve and applies the x that the
+                             first one left behind (the inliers carry a small negative information, the gross outliers hold the
+                             system positive until the first check removes them)
+      nan_observation / inf_observation / nan_point   one non-finite number in obs1, obs2 (an e21 edge: an odd lane), x1c (e21)
+      nan_survives_first_check       x2c of pair 4 is NaN (edge 8: an even lane's first register edge): its chi2 is NaN at the first
+                                     check, `NaN > th2` is false, the pair stays INLIER and every solve of the second phase fails
+      nan_survives_first_check_600   the same at pair 520 of 600 (edge 1040: beyond the four register edges, through global memory)
+      z_zero / behind_camera / huge_observation   a point with z = 0 in camera 1, with z = -3, an observation of 1e300 px
+      fewer_than_ten_after_nan   nine pairs survive the first check, one of them with a NaN chi2: the early return"""
+    nan, inf = float("nan"), float("inf")
+    dirty = lambda seed, n=40, **kw: synth.sim3_opt_problem(seed, n_pairs=n, outlier_share=0.2, **kw)
+    both = lambda r: r["status"] == 1
+    cases = {}
+
+    def negated(share, factor=-1.0, of=None):
+        def make(seed):
+            p = synth.sim3_opt_problem(seed, n_pairs=40, outlier_share=0.5 if of else 0.2)
+            m = ~p["outlier"] if of else np.arange(40) < int(share * 40)
+
+            def scale(a):
+                a[m] *= np.float32(factor)
+            return changed(p, inv_sigma2_1=scale, inv_sigma2_2=scale)
+        return make
+
+    def zero(a):
+        a[:] = 0
+    cases["failed_first_solve"] = _search(lambda s: changed(dirty(s), inv_sigma2_1=zero, inv_sigma2_2=zero),
+                                          lambda p, r: both(r) and min(r["trace"]["failed_solves"]) > 0 and r["trace"]["stale_x_applied"] == (0, 0), range(31, 41))[0]
+    cases["failed_after_success"] = _search(negated(0.4), lambda p, r: both(r) and r["trace"]["stale_x_applied"][0] > 0 and
+                                            r["trace"]["failed_after_success"][0] == 1, range(31, 71))[0]
+    # (failed_solves[1] > 0 without a failure after a success: the phase's first solve is among the failed ones)
+    cases["failed_across_phases"] = _search(negated(None, -0.01, of="inliers"), lambda p, r: both(r) and r["trace"]["failed_solves"][0] == 0 and
+                                            r["trace"]["failed_solves"][1] > 0 and r["trace"]["failed_after_success"][1] == 0 and
+                                            r["trace"]["stale_x_applied"][1] > 0, range(31, 131))[0]
+    finite_s12 = lambda p, r: both(r) and np.isfinite(r["s12"]).all()
+    cases["nan_observation"] = _search(lambda s: changed(dirty(s), obs1=((3, 0), nan)), finite_s12, range(31, 41))[0]
+    cases["inf_observation"] = _search(lambda s: changed(dirty(s), obs2=((5, 1), inf)), finite_s12, range(31, 41))[0]
+    cases["nan_point"] = _search(lambda s: changed(dirty(s), x1c=((7, 1), nan)), finite_s12, range(31, 41))[0]
+    for name, n in (("nan_survives_first_check", 40), ("nan_survives_first_check_600", 600)):
+        k = NAN_PAIR[name]
+        cases[name] = _search(lambda s: changed(dirty(s, n), x2c=(k, nan)),
+                              lambda p, r: both(r) and r["pair_state"][k] == api.SIM3_PAIR_INLIER and np.isnan(r["chi2"][k, 0]) and
+                              r["trace"]["failed_solves"][1] == r["iterations_run"][1] > 0, range(31, 71))[0]
+    cases["z_zero"] = changed(dirty(31), x1c=((6, 2), 0.0))
+    cases["behind_camera"] = _search(lambda s: changed(dirty(s), x1c=((6, 2), -3.0)), finite_s12, range(31, 41))[0]
+    cases["huge_observation"] = _search(lambda s: changed(dirty(s), obs1=(2, 1e300)), finite_s12, range(31, 41))[0]
+
+    def nine(seed):  # nine pairs with small errors, one of them not a number, and six gross outliers
+        p = synth.sim3_opt_problem(seed, n_pairs=15, outlier_share=0.0, noise_px=0.2)
+        p["obs1"][9:] += 80.0
+        return changed(p, obs1=((2, 1), nan))
+    cases["fewer_than_ten_after_nan"] = _search(nine, lambda p, r: r["status"] == 0 and 15 - r["n_bad"] == 9 and r["pair_state"][2] == 0, range(300, 400))[0]
+    return cases
+
+
+def same_where_finite(a, b):
+    """tests/test_gpu_pose_step.py's rule for results that hold a NaN: equal integers, equal NaN masks and equal bits where a number
+    is one (a NaN's payload is nobody's contract) -> the first key that differs, or None"""
+    for k in RESULT_KEYS:
+        x, y = np.ascontiguousarray(a[k]), np.ascontiguousarray(b[k])
+        if x.dtype.kind != "f":
+            if x.tobytes() != y.tobytes():
+                return k
+            continue
+        nx, ny = np.isnan(x), np.isnan(y)
+        if (nx != ny).any() or x[~nx].tobytes() != y[~ny].tobytes():
+            return k
+    return None
 
 
 def _tie_cases(base, pair=0):

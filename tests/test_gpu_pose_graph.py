@@ -3,7 +3,12 @@ tests/test_pose_graph_oracle_inputs.py holds to the inputs condition: rings of 1
 and without ICP edges.  Final poses within the project's pose bar of 1e-5 (translation in metres, quaternion components after fixing
 the sign), the final chi2 within 1e-6 relative, every edge's chi2 within 1e-5 relative plus 1e-12; iterations_run is reported, not
 compared (after convergence the accept / reject decisions are rounding noise).  Also: a smaller map on a used handle (stale tiles),
-iterations = 0, the refusals, and the map points moved with the poses the GPU itself returned, bit for bit."""
+iterations = 0, the refusals, and the map points moved with the poses the GPU itself returned, bit for bit.
+
+On pose_graph_support.LEVENBERG_SEARCHES' cases the decisions are no noise (tests/test_pose_graph_levenberg_inputs.py: every one holds
+at 1e-4 of chi2): there iterations_run and the number of trials equal the restatement's, and the final lambda is within 4 x the
+case's float64 - long double distance of the float64 restatement's.  Estimates and measurements that are no numbers (the entry does
+not validate them) are rejected trial by trial, as the restatement rejects them, and leave the handle as good as new."""
 import numpy as np
 import pytest
 
@@ -107,3 +112,63 @@ def test_refusals(gpu_api, opt):
             small.close()
     r = opt.OptimizeEssentialGraph(p)  # the handle is as usable as before
     assert r["iterations_run"] >= 1
+
+
+@pytest.mark.parametrize("name", sorted(pg.LEVENBERG_SEARCHES))
+def test_levenberg_decisions(opt, name):
+    """A rejected trial followed by an accepted one (the grown lambda's step is kept), an iteration that uses its ten trials up, an
+    accepted trial whose alpha is not clamped (the final lambda carries rho, and through it computeScale's lambda x term)."""
+    p = pg.levenberg_case(name)[0]
+    ref, ref_l = pg.levenberg_solution(name), pg.levenberg_solution(name, np.longdouble)
+    r = opt.OptimizeEssentialGraph(p)
+    info = opt.last_info()
+    dq, dt, ds = pg.pose_difference(_est(r), ref["est"])
+    chi = abs(r["final_chi2"] / float(ref["final_chi2"]) - 1)
+    lam, dist = float(ref["final_lambda"]), abs(float(ref["final_lambda"]) - float(ref_l["final_lambda"]))
+    err = abs(r["final_lambda"] - lam)
+    print(f"{name}: dq {dq:.1e} dt {dt:.1e} ds {ds:.1e}; chi2 rel {chi:.1e}; iterations {r['iterations_run']} (restatement {ref['iterations_run']}), trials "
+          f"{info['trials']} ({len(ref['trace'])}); final lambda {r['final_lambda']:.17g} against {lam:.17g}: |GPU - float64| = {err:.1e}, float64 - long double "
+          f"{dist:.1e}, ratio {err / dist if dist else float(err != 0):.3f}")
+    assert dq <= POSE_BAR and dt <= POSE_BAR and ds <= POSE_BAR
+    assert chi <= 1e-6
+    assert r["iterations_run"] == ref["iterations_run"] == p["iterations"]
+    assert info["trials"] == len(ref["trace"])
+    assert err <= 4 * dist if dist else r["final_lambda"] == lam
+
+
+@pytest.fixture(scope="module")
+def clean_on_a_fresh_handle(gpu_api):
+    fresh = gpu_api.EssentialGraphOptimizer(max_vertices=16, max_edges=64, max_points=256)
+    r = fresh.OptimizeEssentialGraph(pg.map_problem("ring10_fixed"))
+    fresh.close()
+    return r
+
+
+@pytest.mark.parametrize("name", sorted(pg.non_finite_problems()))
+def test_non_finite_estimates_and_measurements(gpu_api, clean_on_a_fresh_handle, name):
+    """NaN in a free vertex's translation, inf in a measurement's translation, NaN in the fixed vertex's quaternion: some edge's chi2
+    is NaN, so the sum and rho are NaN (a failed solve gives (NaN - DBL_MAX) / 1e-3, NaN as well).  Why the device's loops end:
+    b_decide accepts only if rho > 0 and sets `again` only if rho < 0 -- both false for a NaN -- so every trial is rejected, eg_solve's
+    for (;;) leaves after the iteration's first trial (h_flags[0] == 0), and b_decide's terminate needs qmax == 10, rho == 0 or
+    (ini - current) 1e3 < ini three times, all false; the outer loop then runs its 20 iterations and stops.  No kernel loops on a
+    value: the factorisation returns at the first pivot that is no number (k_gba_diag), the later kernels of the trial return on
+    solve_ok == 0.  So: iterations and trials as the restatement, the estimate that was given returned bit for bit, the same edges
+    NaN, and the handle's next solve of a clean map equal to a fresh handle's byte for byte."""
+    p, ref = pg.non_finite_problems()[name], pg.non_finite_solution(name)
+    h = gpu_api.EssentialGraphOptimizer(max_vertices=16, max_edges=64, max_points=256)
+    try:
+        r = h.OptimizeEssentialGraph(p)
+        info = h.last_info()
+        after = h.OptimizeEssentialGraph(pg.map_problem("ring10_fixed"))
+    finally:
+        h.close()
+    assert r["iterations_run"] == ref["iterations_run"] == 20 and info["trials"] == len(ref["trace"]) == 20
+    assert ref["est"].tobytes() == pg.PoseGraph(p).est.tobytes() and _est(r).tobytes() == ref["est"].tobytes()
+    assert (np.isnan(r["edge_chi2"]) == np.isnan(ref["edge_chi2"])).all() and np.isnan(ref["edge_chi2"]).any()
+    ok = ~np.isnan(ref["edge_chi2"])
+    assert np.allclose(r["edge_chi2"][ok], ref["edge_chi2"][ok], rtol=1e-5, atol=1e-12)
+    assert np.isnan(r["final_chi2"]) and r["final_lambda"] == float(ref["final_lambda"])
+    for k in ("vertex_q", "vertex_t", "vertex_s", "points", "edge_chi2"):
+        assert after[k].tobytes() == clean_on_a_fresh_handle[k].tobytes(), k
+    assert (after["iterations_run"], after["final_chi2"], after["final_lambda"]) == \
+        (clean_on_a_fresh_handle["iterations_run"], clean_on_a_fresh_handle["final_chi2"], clean_on_a_fresh_handle["final_lambda"])

@@ -6,7 +6,11 @@ The tolerance is the reference rule's own noise, measured per case: the spread b
 relative to the largest entry of the block row (of the vector; of chi2).  Two float64 evaluations each sit within one spread of the
 exact value, and a factor 2 on top is for the device's acos / log / exp differing from glibc's by a few ulp: the GPU gets 4 x the
 spread.  A tolerance above 1e-5 would mean the case is ill-posed.  Structural zeros -- blocks of pairs that share no edge, and with a
-fixed scale the absence of a scale dimension -- are exactly zero."""
+fixed scale the absence of a scale dimension -- are exactly zero.
+
+Every case runs at the first lambda of the full solves, 1e-16, which in double leaves H as it is; LAMBDA_CASES run also at 1e-3, 1 and
+1e3 times the largest diagonal entry of H, where a lambda that is missing, or on the wrong rows, moves x by far more than the bar
+(tests/test_pose_graph_levenberg_inputs.py holds the inputs to that, without a GPU)."""
 import numpy as np
 import pytest
 
@@ -52,6 +56,24 @@ CASES.update({f"structure_{k}_{'fixed' if fs else 'free'}": (lambda k=k, fs=fs: 
 CASES["eps_branches"] = _branch_map
 
 
+LAMBDA_CASES = ["fixed_scale_F1", "fixed_scale_F17", "fixed_scale_F33", "free_scale_F14", "free_scale_F28"] + \
+    [f"structure_{k}_{fs}" for k in ("free_vertex_without_edge", "duplicates_both_orientations") for fs in ("fixed", "free")]
+LAMBDA_FACTORS = (1e-3, 1.0, 1e3)
+
+
+def lambda_problem(name, factor):
+    """the case with lambda_init = factor x the largest diagonal entry of the float64 restatement's H at the starting estimate"""
+    p = CASES[name]()
+    G = pg.PoseGraph(p)
+    return dict(p, lambda_init=float(factor * np.abs(np.diag(G.system(G.est)[0])).max()))
+
+
+def edgeless_free_slots(p):
+    """free slots of the vertices that no edge touches"""
+    G = pg.PoseGraph(p)
+    return [f for f, v in enumerate(G.free_vert) if v not in set(G.ei.tolist()) | set(G.ej.tolist())]
+
+
 @pytest.fixture(scope="module")
 def opt(gpu_api):
     o = gpu_api.EssentialGraphOptimizer(max_vertices=48, max_edges=256, max_points=16)
@@ -68,7 +90,29 @@ def _reference(p, dtype):
 
 @pytest.mark.parametrize("name", sorted(CASES))
 def test_first_trial(gpu_api, opt, name):
-    p = CASES[name]()
+    _check_first_trial(gpu_api, opt, name, CASES[name]())
+
+
+@pytest.mark.parametrize("factor", LAMBDA_FACTORS)
+@pytest.mark.parametrize("name", LAMBDA_CASES)
+def test_first_trial_at_a_lambda_that_matters(gpu_api, opt, name, factor):
+    """The same comparison, under the same bars, at lambda = factor x max |diag H|: lambda on every diagonal entry of every free
+    vertex (the scale's too, the second panel's too) and in computeScale's lambda x term, or H, x and the trial's chi2 miss the bars
+    by orders of magnitude.  A free vertex without an edge has lambda I for its diagonal block and a step of exactly zero."""
+    p = lambda_problem(name, factor)
+    t = _check_first_trial(gpu_api, opt, f"{name} at lambda {p['lambda_init']:.3g}", p)
+    G = pg.PoseGraph(p)
+    Hg = np.zeros((G.n, G.n))
+    Hg[np.tril_indices(G.n)] = t["H"]
+    slots = edgeless_free_slots(p)
+    assert bool(slots) == ("free_vertex_without_edge" in name)
+    for f in slots:
+        rows = slice(G.dim * f, G.dim * f + G.dim)
+        assert (Hg[rows, rows] == p["lambda_init"] * np.eye(G.dim)).all() and (Hg[rows, :G.dim * f] == 0).all() and (Hg[G.dim * f + G.dim:, rows] == 0).all()
+        assert (t["x"][rows] == 0).all() and (t["b"][rows] == 0).all()
+
+
+def _check_first_trial(gpu_api, opt, name, p):
     G, H, b, x, chi, trial_chi, ok = _reference(p, np.float64)
     _, Hl, bl, xl, chil, trial_chil, _ = _reference(p, np.longdouble)
     t = gpu_api.essential_graph_first_trial(opt, p)
@@ -108,3 +152,4 @@ def test_first_trial(gpu_api, opt, name):
     assert t["chi2"] == float(chi) or abs(t["chi2"] - float(chi)) <= 4 * abs(float(chi) - float(chil))
     assert max(worst.values()) <= 4.0
     assert err_chi <= 4 * spread_chi
+    return t

@@ -59,11 +59,44 @@ def test_every_size_alone_equals_the_restatement(opt, sized):
 
 
 def test_constructed_cases_equal_the_restatement(opt):
-    cases = {k: p for k, p in S.constructed_cases().items() if isinstance(p, dict)}
+    cases = {k: p for k, p in S.constructed_cases().items() if isinstance(p, dict) and k not in S.DEGENERATE_CASES}
     got = opt.OptimizeSim3(list(cases.values())[:MAX_BATCH]) + opt.OptimizeSim3(list(cases.values())[MAX_BATCH:])
     assert len(got) == len(cases)
     for (name, p), g in zip(cases.items(), got):
         _assert_same(name, g, S.run(p))
+
+
+@pytest.fixture(scope="module")
+def degenerate():
+    """name -> (problem, float64 restatement) of the failed-solve and non-finite cases; computed once."""
+    cases = S.constructed_cases()
+    return {k: (cases[k], S.run(cases[k])) for k in S.DEGENERATE_CASES}
+
+
+@pytest.mark.parametrize("name", S.DEGENERATE_CASES)
+def test_failed_solves_and_non_finite_pairs_alone_equal_the_restatement(opt, degenerate, name):
+    """Failed 7 x 7 solves (the x the solver kept applied again, within one optimize() and across the two), and pairs whose chi2 is
+    NaN or infinite at both `> th2` checks and in the neighbouring lane's read of it: equal integers, equal NaN masks, equal bits where
+    a number is one.  The kernel's loops end under a NaN: the trial loop repeats only while rho < 0 (false for a NaN) and at most ten
+    times, and the iterations are counted."""
+    p, want = degenerate[name]
+    got = opt.OptimizeSim3(p)
+    assert S.same_where_finite(got, want) is None, (name, S.same_where_finite(got, want))
+
+
+def test_failed_solves_and_non_finite_pairs_leave_their_neighbours_alone(opt, degenerate, sized):
+    """Each of those cases in slot 0 and in slot B - 1 of a batch of clean problems: the case is its restatement there too, and the
+    clean neighbours return the bytes they return alone."""
+    by_name = {name: p for name, p, _ in sized}
+    clean = [by_name[k] for k in ("n65_out", "n11_clean", "n64_clean")]
+    alone = [S.result_bytes(opt.OptimizeSim3(p)) for p in clean]
+    for name, (p, want) in degenerate.items():
+        for slot in (0, len(clean)):
+            batch = list(clean)
+            batch.insert(slot, p)
+            res = opt.OptimizeSim3(batch)
+            assert S.same_where_finite(res.pop(slot), want) is None, (name, slot)
+            assert [S.result_bytes(r) for r in res] == alone, (name, slot)
 
 
 def test_same_bytes_alone_and_inside_batches_of_mixed_sizes(opt, sized):

@@ -61,7 +61,56 @@ def test_phase_endings_and_rejected_trials(runs):
     assert S.END_QMAX in runs["ends_qmax"]["trace"]["end_reason"]
     assert S.END_NBAD in runs["ends_nbad"]["trace"]["end_reason"]
     assert sum(runs["rejected_trial"]["trace"]["rejected_trials"]) > 0
-    assert all(sum(r["trace"]["failed_solves"]) == 0 for r in runs.values())
+    assert all(sum(r["trace"]["failed_solves"]) == 0 for k, r in runs.items() if k not in S.DEGENERATE_CASES)
+    assert set(S.DEGENERATE_CASES) <= set(runs)
+
+
+def test_failed_solves_apply_the_x_the_solver_kept(cases, runs):
+    """The solver's x outlives a failed solve and both optimize() calls (OptimizeSim3 quirks, item 7): each case reaches the
+    part of it that it is named for."""
+    t = runs["failed_first_solve"]["trace"]
+    assert min(t["failed_solves"]) > 0 and t["stale_x_applied"] == (0, 0) and t["failed_after_success"] == (0, 0), "x stays 0"
+    assert runs["failed_first_solve"]["s12"].tobytes() == np.asarray(cases["failed_first_solve"]["s12"], np.float64).tobytes()
+    assert t["final_lambda"] == (0.0, 0.0)
+    t = runs["failed_after_success"]["trace"]
+    assert t["stale_x_applied"][0] > 0 and t["failed_after_success"][0] == 1
+    r = runs["failed_across_phases"]
+    t = r["trace"]
+    # failed_solves[1] > 0 with no failure after a success: the second optimize()'s first solve failed, and what it applied is the
+    # x of the first optimize()
+    assert t["failed_solves"][0] == 0 and r["iterations_run"][0] > 0 and t["failed_solves"][1] > 0 and t["failed_after_success"][1] == 0
+    assert t["stale_x_applied"][1] == t["failed_solves"][1] > 0
+    for k in ("failed_first_solve", "failed_after_success", "failed_across_phases"):
+        assert runs[k]["status"] == api.SIM3_OPT_BOTH_PHASES and np.isfinite(runs[k]["s12"]).all() and np.isfinite(runs[k]["chi2"]).all(), k
+
+
+def test_non_finite_pairs_reach_both_checks(cases, runs):
+    """`chi2 > th2` is false for a NaN: a pair whose chi2 is NaN is removed only through its other edge.  The NaN is once at an even
+    lane's first register edge of the kernel and once beyond the fourth (tests/sim3_opt_support.py)."""
+    for name, k in S.NAN_PAIR.items():
+        r, n = runs[name], len(cases[name]["x1c"])
+        assert (n, 2 * k < 256, 2 * k >= 1024) in ((40, True, False), (600, False, True))
+        assert np.isnan(r["chi2"][k, 0]) and r["pair_state"][k] == api.SIM3_PAIR_INLIER and r["status"] == api.SIM3_OPT_BOTH_PHASES
+        # in the graph in the second phase: every one of its solves fails on a NaN system, and the pair is counted an inlier
+        assert r["trace"]["failed_solves"][1] == r["iterations_run"][1] > 0 and r["trace"]["failed_solves"][0] == 5
+        assert r["n_in"] == (r["pair_state"] == 0).sum() and np.isnan(r["chi2"]).any(1).sum() == 1
+        assert r["s12"].tobytes() == np.asarray(cases[name]["s12"], np.float64).tobytes(), "no trial was kept"
+    for name, pair in (("nan_observation", 3), ("nan_point", 7)):  # removed through the pair's other edge; the NaN chi2 is reported
+        r = runs[name]
+        assert np.isnan(r["chi2"][pair]).any() and r["pair_state"][pair] == api.SIM3_PAIR_REMOVED_FIRST
+        assert r["trace"]["failed_solves"] == (5, 0) and r["status"] == api.SIM3_OPT_BOTH_PHASES and np.isfinite(r["s12"]).all()
+    r = runs["inf_observation"]
+    assert np.isinf(r["chi2"][5, 1]) and r["pair_state"][5] == api.SIM3_PAIR_REMOVED_FIRST and r["trace"]["failed_solves"] == (5, 0)
+    r = runs["z_zero"]  # a division by z = 0: an infinite error, and a first phase that goes far enough astray for the early return
+    assert r["status"] == api.SIM3_OPT_EARLY_RETURN and r["pair_state"][6] == api.SIM3_PAIR_REMOVED_FIRST and sum(r["trace"]["failed_solves"]) == 0
+    for name, pair in (("behind_camera", 6), ("huge_observation", 2)):
+        r = runs[name]
+        assert r["status"] == api.SIM3_OPT_BOTH_PHASES and r["pair_state"][pair] == api.SIM3_PAIR_REMOVED_FIRST and np.isfinite(r["s12"]).all()
+        assert sum(r["trace"]["failed_solves"]) == 0
+    assert runs["huge_observation"]["chi2"][2, 0] > 1e300
+    r = runs["fewer_than_ten_after_nan"]  # the NaN pair is one of the nine that are left
+    assert r["status"] == api.SIM3_OPT_EARLY_RETURN and len(cases["fewer_than_ten_after_nan"]["x1c"]) - r["n_bad"] == 9
+    assert r["pair_state"][2] == api.SIM3_PAIR_INLIER and np.isnan(r["chi2"][2, 0]) and r["iterations_run"] == (5, 0)
 
 
 def test_first_check_reads_stale_errors(cases, runs):
